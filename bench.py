@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the tiled recursive-filter hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--size S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--size S] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the outputs of the last timed step under --dump-outputs DIR
+when asked, and prints the result line.  Everything else described below -- the per-kernel pass and roofline, the second
+(steady) timed region, the sharded parity check and the phases of a sharded step, the CPU baseline and the extra
+configurations of a default run -- runs only with --full.
 
 A "step" is one execute of the whole filter (pass 1, carry stages, pass 2) over one synthetic
 image already resident in HBM.  N=1 runs BASELINE.json configs[2] ("apps/gaussian: 2D order-2
@@ -17,14 +22,14 @@ GPU (strictly one after the other on one stream: what `kernels_ms` adds up to an
 profiles/ show), two in flight on N > 1 GPUs, where the second step keeps the all-gather's latency off the critical
 path (`config.steps_in_flight` says which; on one GPU two in flight are worth 2 %).
 
-After the timed region of a sharded run the result is CHECKED: every rank gathers all input slabs, runs the unsharded plan
+With --full, after the timed region of a sharded run the result is CHECKED: every rank gathers all input slabs, runs the unsharded plan
 on the whole image and compares its slab of that with what the sharded protocol produced (`sharded_parity`, max over ranks;
-above 1e-4 the bench exits non-zero).  A default run (no --workload / --size) also measures BASELINE config 5 -- 2048^3, six
-order-2 scans, sharded along z over the N GPUs, strong scaling -- and carries its line, same keys, as `configs[0]`.
+above 1e-4 the bench exits non-zero).  A default --full run (no --workload / --size) also measures BASELINE config 5 -- 2048^3,
+six order-2 scans, sharded along z over the N GPUs, strong scaling -- and carries its line, same keys, as `configs[0]`.
 
-Prints ONE JSON line (rank 0).  `value` = Mpixels/s over all GPUs; `roofline` prices the dominant
-kernel against the 8 TB/s HBM peak with HIP-event timing of that kernel; `cpu_baseline` is the CPU
-oracle (a port of the reference's scan operator, OpenMP over all host cores) on a bounded sample.
+Prints ONE JSON line (rank 0).  `value` = Mpixels/s over all GPUs, `ms_per_step` the time of one timed step; with --full,
+`roofline` prices the dominant kernel against the 8 TB/s HBM peak with HIP-event timing of that kernel and `cpu_baseline`
+is the CPU oracle (a port of the reference's scan operator, OpenMP over all host cores) on a bounded sample.
 """
 import argparse
 import json
@@ -232,9 +237,34 @@ def strict_rel_err(got, want):
     return worst
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # all files of one --dump-outputs run together, every plane of every rank
+
+
+def dump_outputs(directory, outputs, rank, world):
+    """--dump-outputs: the output planes of the last timed step as <directory>/output_plane<p>[_rank<r>].npy.  A plane that
+    does not fit its share of DUMP_BUDGET_BYTES is written as a sample: its values at the sorted, de-duplicated flat
+    indices np.unique(np.random.default_rng(0).integers(0, numel, share // itemsize)) -- the same indices for the same
+    shape in every run, so that two builds compare sample for sample."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    for p, out in enumerate(outputs):
+        flat = out.reshape(-1)
+        keep = DUMP_BUDGET_BYTES // (len(outputs) * world * flat.element_size())
+        if flat.numel() > keep:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), keep))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.cpu().numpy()
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        name = f"output_plane{p}" + (f"_rank{rank}" if world > 1 else "")
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def run_workload(args, dist, rank, world, name, size, strong, primary):
-    """One bench line (a dict; meaningful on rank 0) for one workload: cold region, per-kernel pass, timed region, and -- for a
-    sharded run -- the parity of the sharded result against the unsharded plan on the gathered image."""
+    """One bench line (a dict; meaningful on rank 0) for one workload: cold region, and with --full the per-kernel pass, the
+    steady timed region and -- for a sharded run -- the parity of the sharded result against the unsharded plan on the
+    gathered image."""
     import numpy as np
     import torch
     import recfilter_amd as rfa
@@ -292,6 +322,8 @@ def run_workload(args, dist, rank, world, name, size, strong, primary):
     # ms_per_step_cold / value_cold: the strict reading of the protocol; with the driver's 5 + 20 steps -- 15 ms of work -- the
     # GPU has not reached its steady clocks yet: 0.62 against 0.59 ms on cfg3) ------------------------------------------------
     elapsed_cold = timed_region()
+    if primary and args.dump_outputs:
+        dump_outputs(args.dump_outputs, output_sets[(args.steps - 1) % inflight], rank, world)
 
     # --- per-kernel timing with HIP events on the launch stream (single-device plan) -----------------
     # Before the timed region proper, on every rank (rank 0 reports).  A GPU that starts from idle needs some 25 ms of load
@@ -355,16 +387,16 @@ def run_workload(args, dist, rank, world, name, size, strong, primary):
             plan.close()
         return roofline, kernels, preheat
 
-    roofline, kernels, preheat = per_kernel_pass()
-
-    # --- steady: the same W + K steps once the GPU runs at its steady clocks (value, ms_per_step: the protocol of rounds 2
-    # and 3, kept so that the rounds' headline numbers stay comparable; the cold figure is reported beside it) ---------------
-    elapsed = timed_region()
+    if args.full:
+        roofline, kernels, preheat = per_kernel_pass()
+        # --- steady: the same W + K steps once the GPU runs at its steady clocks (value, ms_per_step: the protocol of rounds
+        # 2 and 3, kept so that the rounds' headline numbers stay comparable; the cold figure is reported beside it) --------
+        elapsed = timed_region()
+        ms_per_step_steady = elapsed * 1000.0 / args.steps
     joined = dist.get_world_size() if dist is not None else 1      # ranks that actually took part
     # `value` / `ms_per_step` are the STRICT reading of the protocol since round 5: the first W + K steps this process ran
     # (VERDICT r4 weak 7); the figure at steady clocks -- what rounds 2-4 printed as `value` -- rides beside it
     # as value_steady / ms_per_step_steady.
-    ms_per_step_steady = elapsed * 1000.0 / args.steps
     ms_per_step = elapsed_cold * 1000.0 / args.steps
     total_px = samples_local * joined
     value = total_px / (ms_per_step * 1e-3) / 1e6
@@ -376,7 +408,7 @@ def run_workload(args, dist, rank, world, name, size, strong, primary):
     # cleared planes.  MAX over ranks; above 1e-4 the bench fails (a wrong exchange must not print as a speed-up).
     parity = None
     parity_sat = None
-    if stepping and not args.no_sharded_parity:
+    if args.full and stepping and not args.no_sharded_parity:
         if args.corrupt_exchange:
             # (test hook) what a broken exchange looks like: every rank receives carries that are not the ones that were sent
             def corrupted(gathered, send):
@@ -439,7 +471,7 @@ def run_workload(args, dist, rank, world, name, size, strong, primary):
     # carries), interior (the work enqueued beside the all-gather), exchange_wait (the stream blocked on the collective beyond
     # that), apply, finish.  Mean of 5 steps after 2 unrecorded ones; MAX over ranks per phase.
     phases = None
-    if stepping:
+    if args.full and stepping:
         acc = {}
         for i in range(7):
             ph = filt.profile_step(inputs, outputs)
@@ -459,14 +491,6 @@ def run_workload(args, dist, rank, world, name, size, strong, primary):
         "metric": metric_name(name, cfg["shape"], planes),
         "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": joined, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        # value / ms_per_step: the FIRST W + K steps this process ran (nothing but the generation of the inputs before them) --
-        # the driver's protocol read strictly; value_steady / ms_per_step_steady: the same W + K steps once the GPU runs at its
-        # steady clocks, behind that region and the per-kernel pass (preheat_executions executions, six device copies) -- the
-        # figure rounds 2-4 printed as `value`.  (ms_per_step_cold / value_cold: kept as aliases of the strict figure.)
-        "ms_per_step_steady": round(ms_per_step_steady, 4),
-        "value_steady": round(total_px / (ms_per_step_steady * 1e-3) / 1e6, 1),
-        "ms_per_step_cold": round(ms_per_step, 4), "value_cold": round(value, 1),
-        "preheat_executions": preheat + args.warmup + args.steps, "preheat_copies": 6,
         "higher_is_better": True,
         "scaling": "strong" if (strong and world > 1) else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{name}: {'x'.join(map(str, shape))} f32 x{planes} plane(s) per GPU, "
@@ -482,26 +506,39 @@ def run_workload(args, dist, rank, world, name, size, strong, primary):
                    "steps_in_flight": inflight,
                    "backend": (args.backend if dist is not None else "none"),
                    "rccl_ranks": (joined if (dist is not None and args.backend == "nccl") else 0)},
-        # max over ranks and samples of |sharded - unsharded| / max(|unsharded|, 1e-6), the unsharded plan run on the gathered
-        # image; null when nothing was sharded (one rank, plain execute)
-        "sharded_parity": parity, "sharded_parity_bar": SHARDED_PARITY_BAR,
-        # the same comparison for a summed-area table over the same slabs (carries that do not decay: every slab's entering
-        # carry is the sum over ALL slabs before it, so multi-hop exchange tables are numerically alive at bench size)
-        "sharded_parity_sat": parity_sat,
-        # one sharded step taken apart (HIP events on its stream, max over ranks; null when nothing was sharded): where the
-        # time of a step goes -- a run on real xGMI whose exchange_wait_ms is not ~0 has a collective the interior work does
-        # not cover
-        "step_phases": phases,
         "filter_gbps": round(whole, 1), "filter_roofline_frac": round(whole / HBM_PEAK_GBPS / joined, 4),
-        # the whole filter against what an exact two-pass scheme can reach at this box's measured copy rate (see roofline)
-        "filter_frac_of_two_pass_ceiling": (round(whole / HBM_PEAK_GBPS / joined / roofline["two_pass_ceiling_frac"], 4)
-                                            if roofline.get("two_pass_ceiling_frac") else None),
         "mibipixels_per_s": round(total_px * 1000.0 / (ms_per_step * 2 ** 20), 1),   # lib/timing.cpp:3-5
-        "roofline": roofline,
-        "kernels_ms": {k: round(v, 4) for k, v in kernels.items()},
     }
-    if primary and rank == 0 and not args.no_cpu_baseline and world == 1:
-        line["cpu_baseline"] = cpu_baseline(cfg)
+    if args.full:
+        line.update({
+            # value / ms_per_step: the FIRST W + K steps this process ran (nothing but the generation of the inputs before
+            # them) -- the driver's protocol read strictly; value_steady / ms_per_step_steady: the same W + K steps once the GPU
+            # runs at its steady clocks, behind that region and the per-kernel pass (preheat_executions executions, six device
+            # copies) -- the figure rounds 2-4 printed as `value`.  (ms_per_step_cold / value_cold: kept as aliases of the
+            # strict figure.)
+            "ms_per_step_steady": round(ms_per_step_steady, 4),
+            "value_steady": round(total_px / (ms_per_step_steady * 1e-3) / 1e6, 1),
+            "ms_per_step_cold": round(ms_per_step, 4), "value_cold": round(value, 1),
+            "preheat_executions": preheat + args.warmup + args.steps, "preheat_copies": 6,
+            # max over ranks and samples of |sharded - unsharded| / max(|unsharded|, 1e-6), the unsharded plan run on the
+            # gathered image; null when nothing was sharded (one rank, plain execute)
+            "sharded_parity": parity, "sharded_parity_bar": SHARDED_PARITY_BAR,
+            # the same comparison for a summed-area table over the same slabs (carries that do not decay: every slab's
+            # entering carry is the sum over ALL slabs before it, so multi-hop exchange tables are numerically alive at bench
+            # size)
+            "sharded_parity_sat": parity_sat,
+            # one sharded step taken apart (HIP events on its stream, max over ranks; null when nothing was sharded): where
+            # the time of a step goes -- a run on real xGMI whose exchange_wait_ms is not ~0 has a collective the interior
+            # work does not cover
+            "step_phases": phases,
+            # the whole filter against what an exact two-pass scheme can reach at this box's measured copy rate (see roofline)
+            "filter_frac_of_two_pass_ceiling": (round(whole / HBM_PEAK_GBPS / joined / roofline["two_pass_ceiling_frac"], 4)
+                                                if roofline.get("two_pass_ceiling_frac") else None),
+            "roofline": roofline,
+            "kernels_ms": {k: round(v, 4) for k, v in kernels.items()},
+        })
+        if primary and rank == 0 and not args.no_cpu_baseline and world == 1:
+            line["cpu_baseline"] = cpu_baseline(cfg)
     # leave the GPU as it was found: the next workload of this process needs the memory
     for pl in filt.plans:
         pl.close()
@@ -526,13 +563,18 @@ def main():
                     "under a one-rank launcher is ONE rank's share of `--gpus 8 --workload cfg3 --strong`, driven through the "
                     "sharded protocol on one GPU (tools/rehearse_n8.py)")
     ap.add_argument("--path", type=int, default=0, help="rf_path override (debug)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the per-kernel pass and "
+                    "roofline, the steady timed region, the sharded parity check and step phases, the CPU baseline and the extra "
+                    "configurations of a default run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the output planes of the last timed step as "
+                    "DIR/output_plane<p>[_rank<r>].npy (a fixed, seeded sample of planes larger than the 48 MiB budget)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="default run: only the headline workload, not config 5 behind it")
-    ap.add_argument("--extra-size", type=int, default=0, help="override every extent of the config-5 line of a default run (debug)")
-    ap.add_argument("--no-sharded-parity", action="store_true", help="skip the check of the sharded result against the unsharded "
-                    "plan on the gathered image (it runs outside the timed region)")
-    ap.add_argument("--corrupt-exchange", action="store_true", help="(test hook) scale the gathered carries of the parity execute: "
-                    "the bench must then fail")
+    ap.add_argument("--no-extra-configs", action="store_true", help="default --full run: only the headline workload, not config 5 behind it")
+    ap.add_argument("--extra-size", type=int, default=0, help="override every extent of the config-5 line of a default --full run (debug)")
+    ap.add_argument("--no-sharded-parity", action="store_true", help="--full: skip the check of the sharded result against the "
+                    "unsharded plan on the gathered image (it runs outside the timed region)")
+    ap.add_argument("--corrupt-exchange", action="store_true", help="(test hook, with --full) scale the gathered carries of the "
+                    "parity execute: the bench must then fail")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to exercise the "
                     "multi-rank path on a box with one GPU)")
     ap.add_argument("--device", type=int, default=-1, help="device ordinal for every rank (debug; default LOCAL_RANK)")
@@ -547,6 +589,8 @@ def main():
                     "that per-kernel durations under rocprofv3 are those of kernels running alone, 2 on several GPUs, "
                     "where the second step hides the all-gather)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not launched by torch.distributed.run: become the launcher.  This process only counts the devices, starts the
@@ -575,14 +619,14 @@ def main():
         else:
             dist.init_process_group(args.backend)
 
-    # The default run -- what a driver that only varies --gpus gets -- is the headline workload (cfg3; weak scaling on N
-    # GPUs) AND north_star's config 5: 2048^3, six scans of order 2, sharded along z over the N GPUs (strong scaling, the
-    # early exchange); its line, same keys, is the one entry of "configs".  Any explicit --workload / --size / --path /
+    # The default --full run is the headline workload (cfg3; weak scaling on N GPUs) AND north_star's config 5: 2048^3, six
+    # scans of order 2, sharded along z over the N GPUs (strong scaling, the early exchange); its line, same keys, is the one
+    # entry of "configs".  A plain default run is the headline workload alone.  Any explicit --workload / --size / --path /
     # --force-stepping runs exactly what it names.
     default_run = args.workload is None and not args.size and not args.rows and not args.path and not args.force_stepping and not args.strong
     name = args.workload or "cfg3"
     line = run_workload(args, dist, rank, world, name, args.size, args.strong, primary=True)
-    if default_run and not args.no_extra_configs:
+    if args.full and default_run and not args.no_extra_configs:
         if (args.extra_size or 2048) % (world * 64) == 0:
             extra = run_workload(args, dist, rank, world, "cfg5", args.extra_size, True, primary=False)
             extra["scaling"] = "strong"                  # (one GPU holds the whole volume: the N = 1 point of the strong curve)

@@ -109,7 +109,7 @@ def test_bench_two_ranks_over_gloo(launcher):
     import json
     import subprocess
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--device", "0",
-            "--size", "1024"]
+            "--size", "1024", "--full"]
     if launcher == "self":
         cmd = [sys.executable] + tail
     else:
@@ -140,7 +140,7 @@ def test_bench_fails_on_a_corrupted_exchange():
     import subprocess
     for extra in (["--size", "1024"], ["--workload", "cfg5", "--size", "256", "--strong"]):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--device", "0",
-               "--corrupt-exchange"] + extra
+               "--corrupt-exchange", "--full"] + extra
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         assert out.returncode != 0, out.stdout[-2000:]
@@ -149,14 +149,14 @@ def test_bench_fails_on_a_corrupted_exchange():
 
 
 def test_bench_default_run_carries_config5_strong():
-    """What a driver that only varies --gpus gets: the headline line (cfg3, weak) with north_star's config 5 -- the volume
+    """What a default --full run gets: the headline line (cfg3, weak) with north_star's config 5 -- the volume
     sharded along z, strong scaling, early exchange -- as configs[0] and the headline image in strong scaling (16384^2 split
     into N row slabs) as configs[1], all checked against the unsharded plan.  Two ranks on
     this box's one GPU over gloo; config 5 shrunk to 256^3 (two ranks of the full volume do not fit one device)."""
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--device", "0",
-           "--extra-size", "256"]
+           "--extra-size", "256", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -182,7 +182,7 @@ def test_bench_strong_scaling_volume_two_ranks_over_gloo():
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--device", "0",
-           "--workload", "cfg5", "--size", "256", "--strong"]
+           "--workload", "cfg5", "--size", "256", "--strong", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -322,7 +322,7 @@ def test_bench_forced_stepping_one_rank_over_rccl():
     for extra in (["--size", "2048"], ["--workload", "cfg5", "--size", "256"]):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-               "--no-cpu-baseline", "--force-stepping"] + extra
+               "--no-cpu-baseline", "--force-stepping", "--full"] + extra
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)

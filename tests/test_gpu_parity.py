@@ -1096,10 +1096,19 @@ def test_one_plan_executes_concurrently_on_distinct_streams():
     """a plan is immutable after create, executes on distinct streams with distinct workspaces may overlap.
     Four images through ONE plan on four streams back to back (nothing waits in between), twice; then from four host
     threads at once.  Every result against the oracle; the plan built replicas for the overlapping executions and reuses
-    an idle instance for a later execute on yet another stream."""
+    an idle instance for a later execute on yet another stream.  In a fresh child process: the runtime spreads a process's
+    streams over a few hardware queues, and a replica's table upload that lands on the queue of a busy stream waits for
+    it -- which queue that is depends on the streams the process created before, i.e. on the tests that ran earlier."""
+    import torch.multiprocessing as mp
+    mp.spawn(_executes_concurrently_on_distinct_streams, nprocs=1, join=True)
+
+
+def _executes_concurrently_on_distinct_streams(_rank):
     import threading
     import torch
     import recfilter_amd as rfa
+    import recfilter_amd.plan as rp
+    rp.DEFAULT_FLAGS = TILED                                 # (tests/conftest.py's default; a child process does not load it)
     scans = rc.xy_pm(rc.GAUSS2)
     shape = (1024, 2048)
     imgs = [rc.random_image(shape, np.float32, 700 + i) for i in range(4)]
@@ -1111,7 +1120,8 @@ def test_one_plan_executes_concurrently_on_distinct_streams():
         outs = [torch.empty_like(d) for d in dev]
         for st in streams:                                   # every stream is busy for a while: the executes below are
             with torch.cuda.stream(st):                      # all in flight at the same time, whatever the host's pace
-                torch.cuda._sleep(50_000_000)
+                torch.cuda._sleep(500_000_000)               # (~0.2 s: the process's first execute and three replica
+                                                             #  builds take ~20 ms of host time)
         for rep in range(2):
             for i in range(4):
                 plan.execute([dev[i]], [outs[i]], stream=streams[i])

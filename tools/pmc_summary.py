@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; collected separately as MI355X_MICROARCH.md
-prescribes) of `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline` into per-kernel HBM bytes per launch.
+prescribes) of `python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline` into per-kernel HBM bytes per launch.
 
     python tools/pmc_summary.py <fetch counter_collection.csv> <write counter_collection.csv> <out.json>
 
