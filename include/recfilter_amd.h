@@ -159,7 +159,12 @@ typedef struct {
  *                           a final z pass that reads and writes the same addresses runs 4 % slower (its read and write
  *                           fronts chase each other through the same DRAM banks: tools/microbench/zpass_shape.hip) -- as
  *                           long as that volume is at most a third of the device memory free when the plan is built.
- *                           Same kernels, same results either way. */
+ *                           Same kernels, same results either way.
+ *   RF_PLAN_FULL_CARRY_SCAN the fused x/y stage runs its carry scans (carry_x / carry_y) for every filter.  Default: an f32
+ *                           2-D image (or batched Tuple planes), unsharded, whose scans along a dimension are one scan or
+ *                           a causal-then-anticausal pair, completes that dimension's carries from the neighbouring
+ *                           tiles' tails alone where the filter decays within a tile -- the part that form drops is
+ *                           at most 2^-32 of the largest carry (rf_plan_table("neighbour_carries")). */
 #define RF_PLAN_FORCE_EXCHANGE  0x01u
 #define RF_PLAN_TILED_ONLY      0x02u
 #define RF_PLAN_NO_CASCADE      0x04u
@@ -173,7 +178,8 @@ typedef struct {
 #define RF_PLAN_WALK_PASS1      0x04000000u
 #define RF_PLAN_NO_OVERLAP      0x08000000u
 #define RF_PLAN_INPLACE_Z       0x10000000u
-#define RF_PLAN_ALL_FLAGS       0x1f0000ffu
+#define RF_PLAN_FULL_CARRY_SCAN 0x20000000u
+#define RF_PLAN_ALL_FLAGS       0x3f0000ffu
 #define RF_PLAN_TILE_ROWS(n)    (((uint32_t)(n) & 0xffu) << 8)
 #define RF_PLAN_TILE_PLANES(n)  (((uint32_t)(n) & 0xffu) << 16)
 
@@ -295,7 +301,10 @@ int rf_plan_abort(rf_plan *plan);
  * pass out = NULL to query the size.  Names are documented in DESIGN.md ("plan tables").
  * "scans" lists the scans the plan EXECUTES, one row of 5 + 2 * RF_MAX_ORDER doubles each: where the plan rewrote the filter --
  * merged runs of a 1-D signal (one scan per run, RF_PLAN_NO_OVERLAP forbids it), sections of order <= 3 in place of a scan of
- * order 4..8 (RF_PLAN_NO_SECTIONS), the first stage of an in-plan cascade -- these are not the scans the caller gave. */
+ * order 4..8 (RF_PLAN_NO_SECTIONS), the first stage of an in-plan cascade -- these are not the scans the caller gave.
+ * "neighbour_carries" (fused x/y plans): {bound x, taken x, bound y, taken y} -- the largest part of a consumed carry the
+ * neighbour form would drop, relative to the largest carry (-1: the dimension cannot take that form), and 1 / 0 for whether
+ * the plan runs it (RF_PLAN_FULL_CARRY_SCAN). */
 int rf_plan_table(const rf_plan *plan, const char *name, double *out, size_t capacity, size_t *n_out);
 
 /* Debugging aid: device pointer and size of the i-th buffer the plan owns (tables, tails, carries,

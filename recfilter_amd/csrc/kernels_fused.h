@@ -72,6 +72,10 @@ struct FusedArgs {
                              // The slab's y tails were completed with ZERO entering carries; pass 2 adds what the true
                              // ones (y_incoming) contribute, Y * in, as it loads a carry, so the tails are not rewritten
                              // by a separate launch.  Null otherwise.
+    const Acc *y_nb_W;       // neighbour-form y carries (plan_fused.cpp, neighbour_carry_bound): the chaining tables of the y scans,
+                             // W[v][q][s][r][o].  The y tails were never scanned: pass 2 adds W_v(ty+1)[0->1] * (its own tile's
+                             // causal tail) to the anticausal carry it loads from tile ty + 1.  Null otherwise.  128-row final
+                             // pass only.
     const Acc *x_incoming;   // carry entering each row along x, [s][r][y + NY*z]: zeros for an image; for a long
                              // 1-D signal folded into rows it is the state the previous row hands over
     // pointwise stages fused into the passes (rf_pointwise_desc; float pixels only): bit 0 = x' = pre_s*in + pre_b
@@ -222,7 +226,10 @@ int launch_walk_tails(int K, const float *src, const FusedArgs<float> &a, const 
 // tile-local x scans of the combined rows + cross-dimension residual, in place in yt (G == nullptr: no residual)
 template <typename Acc>
 int launch_xscan_rows(int K, int TY, const FusedArgs<Acc> &a, const Acc *Hy, const Acc *G, hipStream_t stream,
-                      const Acc *Wx = nullptr, const Acc *Ax = nullptr, Acc *xt_done = nullptr);
+                      const Acc *Wx = nullptr, const Acc *Ax = nullptr, Acc *xt_done = nullptr, bool neighbour = false);
+// neighbour = true (f32; a causal x scan followed by an anticausal one; Ax unused): the x tails are completed from the
+// neighbouring tiles' alone, c_0(t) = tau_0(t), c_1(t) = tau_1(t) + W_v(t)[0->1] tau_0(t-1) (plan_fused.cpp,
+// neighbour_carry_bound) -- for the residual and, into xt_done, for the final pass; there is no carry scan along x
 // Wx / Ax / xt_done given: the launch also completes the x tails (the carry scan along x), into xt_done -- for images this
 // predicate accepts (few tiles per row: the separate carry launch is all launch and latency there)
 bool xscan_completes_x_tails(int K, int TY, int MX, int nx, int ny, size_t acc_bytes, int64_t tile_rows /* MY * NZ */);

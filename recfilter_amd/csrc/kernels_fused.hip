@@ -490,6 +490,7 @@ int launch_fused_pass2(int K, int TY, const void *src, bool src_u8, P *dst, cons
                        hipStream_t stream) {
     if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
     if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    if (a.y_nb_W != nullptr) { set_error("fused pass 2: neighbour-form y carries need the 128-row final pass"); return RF_ERR_INVALID_ARG; }
     if constexpr (std::is_same<P, float>::value) {
         if (src_u8) return launch_fused_pass2_typed<P, uint8_t>(K, TY, (const uint8_t *)src, dst, a, stream);
     }

@@ -111,14 +111,33 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     // entering carries are requested here, with the other carries; the correction itself waits until the pixels have been
     // requested (apply_entering_carries below) -- computed here it made every tile wait for its carry loads before it asked
     // for a single pixel.
+    // Neighbour-form y carries (FusedArgs::y_nb_W): the anticausal carry from tile ty + 1 is that tile's own tail plus
+    // W_v(ty+1)[0->1] * this tile's causal tail -- the same shape, a k-vector requested here and a k x k product applied
+    // after the pixels, with the tile's own scan-0 tail in the place of the slab's entering carries.
     Acc yin[kFusedMaxScans][K];
     if (a.y_apply != nullptr) {
 #pragma unroll
         for (int q = 0; q < kFusedMaxScans; q++)
 #pragma unroll
             for (int o = 0; o < K; o++) yin[q][o] = q < a.ny ? a.y_incoming[((int64_t)q * K + o) * Ly + line] : Acc(0);
+    } else if (a.y_nb_W != nullptr && ty < a.MY - 1) {
+#pragma unroll
+        for (int o = 0; o < K; o++) yin[0][o] = a.yt[a.yt_index(0, ty, o, K, line)];
     }
     auto apply_entering_carries = [&]() {
+        if (a.y_nb_W != nullptr) {
+            if (ty < a.MY - 1) {          // (the last tile row's anticausal carry enters at the border: nothing chains on it)
+                const int v = (ty + 1 == a.MY - 1) ? 2 : 0;
+                const Acc *Wm = a.y_nb_W + ((v * a.ny + 0) * a.ny + 1) * K * K;
+                // (term by term onto the loaded tail, in the order the carry scan adds them: W has entries of either sign
+                //  several times the sum of a row, so a partial sum formed first rounds differently)
+#pragma unroll
+                for (int r = 0; r < K; r++)
+#pragma unroll
+                    for (int o = 0; o < K; o++) CY[1][r] = CY[1][r] + Wm[r * K + o] * yin[0][o];
+            }
+            return;
+        }
         if (a.y_apply == nullptr) return;
 #pragma unroll
         for (int j = 0; j < kFusedMaxScans; j++) {

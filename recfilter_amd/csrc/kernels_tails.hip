@@ -345,9 +345,15 @@ fused_tails_kernel(const PI *__restrict__ src, FusedArgs<typename PixelTraits<P>
 // a second array (xt_done): the other workgroups of the tile row read the incomplete ones whenever they get to run.  The
 // workgroups of a tile row repeat that recurrence (redundant, but it needs no hand-off between them).
 constexpr int kXcMaxTiles = 32;   // XC = tiles per wave (four waves): 4 up to 16 tiles per row, 8 up to 32 (order 1)
+//
+// NB (neighbour-form x carries, plan_fused.cpp neighbour_carry_bound; f32, a causal x scan followed by an anticausal one): there
+// is no carry scan along x.  The completed carries are the neighbours' tails, c_0(t) = tau_0(t), c_1(t) = tau_1(t) +
+// W_v(t)[0->1] tau_0(t-1): the residual takes c_1(tx+1) from tile tx+1's anticausal tail and this tile's own causal tail, and the
+// workgroups of the first group of combined rows (jg == 0) store the completed tails of their x tiles to xt_done for the final
+// pass -- the contract XC has.  Any number of tiles per row.
 
 
-template <typename Acc, int K, bool EDGE, bool TALL, int XC = 0, bool MOD = false>
+template <typename Acc, int K, bool EDGE, bool TALL, int XC = 0, bool MOD = false, bool NB = false>
 __global__ void __launch_bounds__(256, XC ? (sizeof(Acc) == 8 ? 2 : 3) : (sizeof(Acc) == 8 ? 3 : 6))
 xscan_rows_kernel(FusedArgs<Acc> a, int gj, int TY, const Acc *__restrict__ Hy, const Acc *__restrict__ G,
                   const Acc *__restrict__ Wx = nullptr, const Acc *__restrict__ Ax = nullptr, Acc *__restrict__ xt_done = nullptr) {
@@ -572,6 +578,13 @@ xscan_rows_kernel(FusedArgs<Acc> a, int gj, int TY, const Acc *__restrict__ Hy, 
                 A4 hy = A4{Acc(0), Acc(0), Acc(0), Acc(0)};
                 if (lane_in) hy = *reinterpret_cast<const A4 *>(Hy + ((size_t)(vy * a.ny + j) * K + r) * TY + blk + 4 * l);
                 const int64_t y0 = (int64_t)ty * TY + a.NYP * z + blk + 4 * l;
+                A4 own[K];                  // NB: this tile's causal tail, which the anticausal carry entering it chains on
+                if constexpr (NB) {
+                    const bool need = lane_in && tx < a.MX - 1;
+#pragma unroll
+                    for (int o = 0; o < K; o++)
+                        own[o] = need ? *reinterpret_cast<const A4 *>(a.xt + ((int64_t)tx * K + o) * Lx + y0) : A4{Acc(0), Acc(0), Acc(0), Acc(0)};
+                }
 #pragma unroll
                 for (int q = 0; q < kFusedMaxScans; q++) {
                     if (q < a.nx) {
@@ -584,6 +597,18 @@ xscan_rows_kernel(FusedArgs<Acc> a, int gj, int TY, const Acc *__restrict__ Hy, 
                             if (!q_first && lane_in) {
                                 if constexpr (XC > 0) c = *reinterpret_cast<const A4 *>(xc + ((q * a.MX + tp) * K + o) * TY + blk + 4 * l);
                                 else c = *reinterpret_cast<const A4 *>(a.xt + (((int64_t)q * a.MX + tp) * K + o) * Lx + y0);
+                            }
+                            if constexpr (NB) {
+                                if (q == 1 && !q_first) {       // c_1(tx+1) = tau_1(tx+1) + W_v(tx+1)[0->1] tau_0(tx)
+                                    const int vn = (tx + 1 == a.MX - 1) ? 2 : 0;
+                                    const Acc *Wm = Wx + ((vn * a.nx + 0) * a.nx + 1) * K * K + o * K;
+#pragma unroll
+                                    for (int m = 0; m < K; m++) {
+                                        const Acc w = Wm[m];
+                                        c.x = c.x + w * own[m].x; c.y = c.y + w * own[m].y;
+                                        c.z = c.z + w * own[m].z; c.w = c.w + w * own[m].w;
+                                    }
+                                }
                             }
                             tv[q * K + o] = tv[q * K + o] + (hy.x * c.x + hy.y * c.y + hy.z * c.z + hy.w * c.w);
                         }
@@ -683,6 +708,32 @@ xscan_rows_kernel(FusedArgs<Acc> a, int gj, int TY, const Acc *__restrict__ Hy, 
         tile_of(r, jr_i, tx_i);
         if (tx_i < a.MX) yt4[row_tile_index(jr_i, tx_i) * 64 + cc] = rows4[r * 64 + swz_chunk(cc)];
     }
+    if constexpr (NB) {
+        // the completed x tails of this workgroup's x tiles, [s][tx][r][TY rows of this tile row], for the final pass
+        if (jg == 0) {
+            const int64_t Lx = a.NYP * a.NZ;
+            const int64_t ybase = (int64_t)ty * TY + a.NYP * z;
+            const int cps = TY / 4;                              // 16-byte chunks per strip
+            for (int e = t; e < txp * a.nx * K * cps; e += 256) {
+                const int c4 = e % cps, sr = e / cps;            // sr = (ti * nx + s) * K + r
+                const int r = sr % K, s = (sr / K) % a.nx, tx_i = xg * txp + sr / (K * a.nx);
+                if (tx_i >= a.MX) continue;
+                const int64_t y = ybase + 4 * c4;
+                A4 v = *reinterpret_cast<const A4 *>(a.xt + (((int64_t)s * a.MX + tx_i) * K + r) * Lx + y);
+                if (s == 1 && tx_i > 0) {                        // c_1(t) = tau_1(t) + W_v(t)[0->1] tau_0(t-1)
+                    const int vt = (tx_i == a.MX - 1) ? 2 : 0;
+                    const Acc *Wm = Wx + ((vt * a.nx + 0) * a.nx + 1) * K * K + r * K;
+#pragma unroll
+                    for (int m = 0; m < K; m++) {
+                        const A4 p = *reinterpret_cast<const A4 *>(a.xt + ((int64_t)(tx_i - 1) * K + m) * Lx + y);
+                        const Acc w = Wm[m];
+                        v.x = v.x + w * p.x; v.y = v.y + w * p.y; v.z = v.z + w * p.z; v.w = v.w + w * p.w;
+                    }
+                }
+                *reinterpret_cast<A4 *>(xt_done + (((int64_t)s * a.MX + tx_i) * K + r) * Lx + y) = v;
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -781,7 +832,7 @@ bool xscan_completes_x_tails(int K, int TY, int MX, int nx, int ny, size_t acc_b
 
 template <typename Acc>
 int launch_xscan_rows(int K, int TY, const FusedArgs<Acc> &a, const Acc *Hy, const Acc *G, hipStream_t stream,
-                      const Acc *Wx, const Acc *Ax, Acc *xt_done) {
+                      const Acc *Wx, const Acc *Ax, Acc *xt_done, bool neighbour) {
     // yt is [j][ty][r][x + NX*z]: every run of 256 consecutive samples is one combined row of one x tile
     const int n_jr = a.ny * K;
     if (n_jr <= 0 || a.MY <= 0 || a.MX <= 0 || a.NZ <= 0 || a.nx == 0) return RF_OK;
@@ -795,6 +846,27 @@ int launch_xscan_rows(int K, int TY, const FusedArgs<Acc> &a, const Acc *Hy, con
     const unsigned grid = (unsigned)blocks;
     const bool edge = a.last_cols != kFusedTX;       // images of whole tiles keep the lean kernel
     const size_t g_bytes = (size_t)a.nx * K * kFusedTX * sizeof(Acc);
+    if (neighbour) {          // the x tails completed from the neighbours' (NB)
+        if constexpr (std::is_same<Acc, float>::value) {
+            if (G == nullptr || Wx == nullptr || xt_done == nullptr || a.nx != 2 || a.mod_form || a.xs[0].causal == 0 || a.xs[1].causal != 0) {
+                set_error("xscan rows: neighbour-form x carries misconfigured");
+                return RF_ERR_INVALID_ARG;
+            }
+#define RF_NB(KK, E, T) hipLaunchKernelGGL((xscan_rows_kernel<Acc, KK, E, T, 0, false, true>), dim3(grid), dim3(256), g_bytes, stream, a, gj, TY, Hy, G, Wx, (const Acc *)nullptr, xt_done)
+#define RF_CASE(KK)                                                                                                        \
+            if (K == KK) {                                                                                                 \
+                if (TY > 64) { if (edge) RF_NB(KK, true, true); else RF_NB(KK, false, true); }                             \
+                else         { if (edge) RF_NB(KK, true, false); else RF_NB(KK, false, false); }                           \
+                RF_HIP_CHECK(hipGetLastError());                                                                           \
+                return RF_OK;                                                                                              \
+            }
+            RF_CASE(1) RF_CASE(2) RF_CASE(3)
+#undef RF_CASE
+#undef RF_NB
+        }
+        set_error("xscan rows: no neighbour-form x carries for order %d", K);
+        return RF_ERR_UNSUPPORTED;
+    }
     if (Wx != nullptr) {      // the kernel completes the x tails too (XC)
         if (G == nullptr || Ax == nullptr || xt_done == nullptr || TY > 64 || a.MX > kXcMaxTiles) { set_error("xscan rows: merged carry scan misconfigured"); return RF_ERR_INVALID_ARG; }
         const size_t xc_bytes = g_bytes + (size_t)a.nx * a.MX * K * TY * sizeof(Acc);
@@ -834,8 +906,8 @@ template int launch_fused_tails<int32_t>(int, int, const void *, bool, const Fus
 template int launch_fused_tails<int16_t>(int, int, const void *, bool, const FusedArgs<uint32_t> &, const uint32_t *,
                                          const uint32_t *, hipStream_t);
 template int launch_fused_tails<double>(int, int, const void *, bool, const FusedArgs<double> &, const double *, const double *, hipStream_t);
-template int launch_xscan_rows<float>(int, int, const FusedArgs<float> &, const float *, const float *, hipStream_t, const float *, const float *, float *);
-template int launch_xscan_rows<uint32_t>(int, int, const FusedArgs<uint32_t> &, const uint32_t *, const uint32_t *, hipStream_t, const uint32_t *, const uint32_t *, uint32_t *);
-template int launch_xscan_rows<double>(int, int, const FusedArgs<double> &, const double *, const double *, hipStream_t, const double *, const double *, double *);
+template int launch_xscan_rows<float>(int, int, const FusedArgs<float> &, const float *, const float *, hipStream_t, const float *, const float *, float *, bool);
+template int launch_xscan_rows<uint32_t>(int, int, const FusedArgs<uint32_t> &, const uint32_t *, const uint32_t *, hipStream_t, const uint32_t *, const uint32_t *, uint32_t *, bool);
+template int launch_xscan_rows<double>(int, int, const FusedArgs<double> &, const double *, const double *, hipStream_t, const double *, const double *, double *, bool);
 
 }  // namespace rf

@@ -4,11 +4,14 @@
 // with the generic dimension builder):
 //   fused_tails      pass 1: tile-local tails of every x scan (per row) and the y tails' combined rows, by
 //                    contraction with precomputed impulse responses
-//   carry_x          x carry recurrence, all x scans (same-dimension chaining included)
+//   carry_x          x carry recurrence, all x scans (same-dimension chaining included); not run where the x carries
+//                    take the neighbour form (neighbour_carry_bound below)
 //   xscan_rows       finishes the y tails: tile-local x scans of the combined rows + the cross-dimension
 //                    residual of the completed x carries (lib/split.cpp:1215-1633)
-//   carry_y          y carry recurrence, all y scans (one launch per scan around the exchanges when sharded)
+//   carry_y          y carry recurrence, all y scans (one launch per scan around the exchanges when sharded); not run
+//                    where the y carries take the neighbour form
 //   fused_pass2      final correction pass
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -48,6 +51,55 @@ int64_t chained_row_length(int64_t N) {
     for (int64_t nx = 16384; nx >= kFusedTX; nx /= 2)
         if (N % nx == 0 && (N / nx) % 32 == 0) return nx;
     return 0;
+}
+
+// Neighbour-form carries.  The carry scans of a dimension compute, for scan s and tile t,
+//   c_s(t) = tau_s(t) + sum_{q<s} W_v(t)[q->s] c_q(tile entering t) + A_s^L c_s(previous tile in s's direction)
+// (tau: the tile-local tail with zero entering carries, W_v: the chaining table of t's border variant, A_s^L: the scan's
+// transition across a tile).  For a filter that decays within a tile the last term is beyond what an f32 result can see,
+// and without it a dimension of one scan, or of a causal scan s0 followed by an anticausal s1, needs no scan at all:
+//   c_s0(t) = tau_s0(t),   c_s1(t) = tau_s1(t) + W_v(t)[0->1] tau_s0(t-1)
+// -- the neighbour's own tail and, for s1, a k x k product with the tile's own causal tail.  What that form drops from a
+// consumed carry, relative to the largest carry, is at most (infinity norms, in double)
+//   one scan: |A^L|;   s0, s1: max(|A_s0^L|, max_v |W_v[0->1] A_s0^L| + |A_s1^L|)
+// Every dropped transfer crosses a WHOLE tile: only the last tile may be partial, and the only carry that crosses it is the
+// causal one leaving the image, which an unsharded plan never consumes (the caller checks that the plan is unsharded).
+// Returns -1 for any other pattern of scans.
+constexpr double kNeighbourCarryBound = 1.0 / 4294967296.0;      // 2^-32: 1/256 of the rounding the scan form applies to a tail
+
+template <typename S>
+double neighbour_carry_bound(const DimTables<S> &tab, const std::vector<int> &ids, const rf_plan *plan) {
+    const int n = (int)ids.size(), k = tab.k;
+    if (n < 1 || n > 2 || (n == 2 && !(plan->scans[ids[0]].causal && !plan->scans[ids[1]].causal))) return -1.0;
+    auto norm = [k](const std::vector<double> &m) {
+        double best = 0.0;
+        for (int r = 0; r < k; r++) {
+            double row = 0.0;
+            for (int o = 0; o < k; o++) row += std::fabs(m[(size_t)r * k + o]);
+            best = std::max(best, row);
+        }
+        return best;
+    };
+    auto to_double = [](const std::vector<S> &m) {
+        std::vector<double> d(m.size());
+        for (size_t e = 0; e < m.size(); e++) d[e] = table_to_double<S>(m[e]);
+        return d;
+    };
+    const std::vector<double> A0 = to_double(tab.A[0]);
+    double bound = norm(A0);
+    if (n == 2) {
+        double chained = 0.0;
+        for (int v : {0, 2}) {       // the tiles whose entering causal carry is dropped: interior ones and the last one
+            const std::vector<double> W = to_double(tab.Wm(v, 0, 1));
+            std::vector<double> WA((size_t)k * k, 0.0);
+            for (int r = 0; r < k; r++)
+                for (int o = 0; o < k; o++)
+                    for (int m = 0; m < k; m++) WA[(size_t)r * k + o] += W[(size_t)r * k + m] * A0[(size_t)m * k + o];
+            chained = std::max(chained, norm(WA));
+        }
+        bound = std::max(bound, chained + norm(to_double(tab.A[1])));
+    }
+    return bound;
 }
 
 template <typename P, typename S>
@@ -188,6 +240,10 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         plan->tables["A_" + dn] = dA;
     };
 
+    // neighbour-form carries (neighbour_carry_bound): f32 images and batched Tuple planes, unsharded, not chained rows, not in
+    // mod form (a 3-D plan's x/y stage keeps its scans); the bound is reported whatever RF_PLAN_FULL_CARRY_SCAN says
+    const bool neighbour_plan = std::is_same<P, float>::value && plan->ndim == 2 && !plan->sharded() && !chained && !plan->mod_form;
+    double nb_bound_x = -1.0, nb_bound_y = -1.0;
     std::vector<FusedScan<Acc>> hxs = fused_scans(dx.scan_ids, true), hys = fused_scans(dy.scan_ids, false);
     if (nx > 0) {
         // segment tables as the x phase reads them (float pixels: exact values of the kernel constants)
@@ -209,6 +265,7 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     if (nx > 0) {
         DimTables<S> tx = build_dim_tables<S>(table_scans(dx.scan_ids), K, kFusedTX, plan->clamped, TVx);
         flatten_W(tx, nx, hWx, hAx, "x");
+        if (neighbour_plan) nb_bound_x = neighbour_carry_bound<S>(tx, dx.scan_ids, plan);
         if (chained) hApowX = carry_apply_powers<S, Acc>(tx.A, MX, K);
         {
             std::vector<S> H = build_tail_responses<S>(table_scans(dx.scan_ids), K, kFusedTX, plan->clamped, TVx);
@@ -248,6 +305,7 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     if (ny > 0) {
         ty = build_dim_tables<S>(table_scans(dy.scan_ids), K, TY, plan->clamped, TVy);
         flatten_W(ty, ny, hWy, hAy, "y");
+        if (neighbour_plan) nb_bound_y = neighbour_carry_bound<S>(ty, dy.scan_ids, plan);
         if (y_sharded) hApowY = carry_apply_powers<S, Acc>(ty.A, MY, K);
         {
             std::vector<S> H = build_tail_responses<S>(table_scans(dy.scan_ids), K, TY, plan->clamped, TVy);
@@ -263,6 +321,18 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
             for (int e = 0; e < K * K; e++) hACy[(size_t)j * K * K + e] = table_to_acc<S, Acc>(ac[e]);
         }
     }
+
+    // Which dimensions take the neighbour form.  x: one scan needs nothing but the tails pass 1 left; a pair is completed by
+    // xscan_rows (kernels_tails.hip, NB), which runs only with y scans in the filter.  y: one scan likewise; a pair needs the
+    // final pass to add W * (the tile's own causal tail) to the anticausal carry it loads (FusedArgs::y_nb_W), which the
+    // 128-row final pass does (kernels_fused_tall.hip).
+    const bool full_scan = (plan->flags & RF_PLAN_FULL_CARRY_SCAN) != 0;
+    const bool nb_x = !full_scan && nb_bound_x >= 0.0 && nb_bound_x <= kNeighbourCarryBound && (nx == 1 || ny > 0);
+    const bool nb_y = !full_scan && nb_bound_y >= 0.0 && nb_bound_y <= kNeighbourCarryBound && (ny == 1 || TY == 128);
+    const bool nb_x_pair = nb_x && nx == 2, nb_y_pair = nb_y && ny == 2;
+    // (every dropped transfer crosses a whole tile: neighbour_plan admits unsharded plans only, which hold both borders of both
+    // dimensions, so the only partial tile is a last one and the causal carry leaving it is never consumed)
+    plan->tables["neighbour_carries"] = {nb_bound_x, nb_x ? 1.0 : 0.0, nb_bound_y, nb_y ? 1.0 : 0.0};
 
     // ---- device memory --------------------------------------------------------------------
     auto up = [&](const auto &vec) {
@@ -280,9 +350,11 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     const size_t xin_pp = (size_t)nx * K * Lx, yin_pp = (size_t)ny * K * Ly;
     const int np = batch ? 1 : plan->n_planes;         // batched planes are inside Lx / Ly already (NZ)
     // few tiles per row: xscan_rows completes the x tails itself, into a second array (kernels_tails.hip, XC)
-    const bool merged_cx = !chained && xscan_completes_x_tails(K, TY, (int)MX, nx, ny, sizeof(Acc), (int64_t)MY * NZ);
+    // (the neighbour form needs no recurrence at all: it takes such images too -- 2-4 µs per step ahead of XC on 1280^2 x 3 ...
+    //  4096^2, orders 1-3, profiles/r7/xc_vs_nb.txt)
+    const bool merged_cx = !chained && !nb_x && xscan_completes_x_tails(K, TY, (int)MX, nx, ny, sizeof(Acc), (int64_t)MY * NZ);
     Acc *xt = (Acc *)plan->alloc(xt_pp * np * sizeof(Acc), false, &status);
-    Acc *xt_done = merged_cx ? (Acc *)plan->alloc(xt_pp * np * sizeof(Acc), false, &status) : nullptr;
+    Acc *xt_done = (merged_cx || nb_x_pair) ? (Acc *)plan->alloc(xt_pp * np * sizeof(Acc), false, &status) : nullptr;
     Acc *yt = (Acc *)plan->alloc(yt_pp * np * sizeof(Acc), false, &status);
     Acc *xin = (Acc *)plan->alloc(xin_pp * np * sizeof(Acc), true, &status);
     Acc *yin = (Acc *)plan->alloc(yin_pp * np * sizeof(Acc), true, &status);
@@ -488,7 +560,7 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         plan->begin_steps.push_back(ci);
     }
     plan->begin_steps.push_back(p1);
-    if (nx > 0 && !chained && !merged_cx) {
+    if (nx > 0 && !chained && !merged_cx && !nb_x) {
         Step cx;
         cx.name = "carry_x";
         cx.run = [plan, gxargs, K, nx, d_ACx, Cx, xmask](int pl) {
@@ -562,16 +634,18 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         // completed x carries (lib/split.cpp:1215-1633)
         Step xs;
         xs.name = "xscan_rows";
-        xs.run = [plan, fargs, K, TY, d_Hy, d_G, merged_cx, d_Wx, d_Ax, xt_done, xt_pp](int pl) {
+        xs.run = [plan, fargs, K, TY, d_Hy, d_G, merged_cx, nb_x_pair, d_Wx, d_Ax, xt_done, xt_pp](int pl) {
             if (merged_cx)
                 return launch_xscan_rows<Acc>(K, TY, fargs(pl), d_Hy, d_G, plan->stream, d_Wx, d_Ax, xt_done + (size_t)pl * xt_pp);
+            if (nb_x_pair)      // neighbour form: the x tails completed from the neighbours' (NB)
+                return launch_xscan_rows<Acc>(K, TY, fargs(pl), d_Hy, d_G, plan->stream, d_Wx, nullptr, xt_done + (size_t)pl * xt_pp, true);
             return launch_xscan_rows<Acc>(K, TY, fargs(pl), d_Hy, d_G, plan->stream);
         };
         plan->begin_steps.push_back(xs);
     }
     const Acc *d_Yapply = nullptr;
     if (!y_sharded) {   // one launch for every y scan; per-scan launches only around the exchanges
-        if (ny > 0) {
+        if (ny > 0 && !nb_y) {
             Step cy;
             cy.name = "carry_y";
             cy.run = [plan, gyargs, K, ny, d_ACy, Cy, ymask](int pl) {
@@ -623,10 +697,12 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     }
     Step p2;
     p2.name = "fused_pass2";
-    p2.run = [plan, fargs, K, TY, d_Yapply, padded, merged_cx, xt_done, xt_pp](int pl) {
+    const Acc *d_Ynb = nb_y_pair ? d_Wy : nullptr;
+    p2.run = [plan, fargs, K, TY, d_Yapply, d_Ynb, padded, merged_cx, nb_x_pair, xt_done, xt_pp](int pl) {
         FusedArgs<Acc> a = fargs(pl);
         a.y_apply = d_Yapply;
-        if (merged_cx) a.xt = xt_done + (size_t)pl * xt_pp;
+        a.y_nb_W = d_Ynb;
+        if (merged_cx || nb_x_pair) a.xt = xt_done + (size_t)pl * xt_pp;
         if constexpr (sizeof(Acc) == 4) {
             if (TY == 128) return launch_fused_pass2_tall<P>(K, plan->in[pl], plan->pw.in_u8, (P *)plan->xy_result(pl), a, plan->stream);
         }
