@@ -66,6 +66,17 @@ template <> struct RecFilterPixel<float>   { static constexpr int dtype = RF_F32
 template <> struct RecFilterPixel<double>  { static constexpr int dtype = RF_F64; };
 template <> struct RecFilterPixel<int32_t> { static constexpr int dtype = RF_I32; };
 template <> struct RecFilterPixel<int16_t> { static constexpr int dtype = RF_I16; };
+/** 16-bit floating-point pixels: STORAGE types -- the planes hold IEEE binary16 / bfloat16 bit patterns, the filter runs in
+ *  f32 and rounds once at the final store (recfilter_amd.h, rf_dtype).  Tag types any host compiler accepts; a compiler that
+ *  has the native types may bind `const _Float16 *` / `const __bf16 *` planes as well. */
+struct rf_half { uint16_t bits; };
+struct rf_bfloat16 { uint16_t bits; };
+template <> struct RecFilterPixel<rf_half>     { static constexpr int dtype = RF_F16; };
+template <> struct RecFilterPixel<rf_bfloat16> { static constexpr int dtype = RF_BF16; };
+#if defined(__HIP__)      /* hipcc: both native types exist on host and device */
+template <> struct RecFilterPixel<_Float16>    { static constexpr int dtype = RF_F16; };
+template <> struct RecFilterPixel<__bf16>      { static constexpr int dtype = RF_BF16; };
+#endif
 
 /** A dense x-fastest DEVICE image bound as (one Tuple element of) the filter's definition. */
 struct RecFilterImageRef {
@@ -209,7 +220,7 @@ class RecFilter {
     size_t plane_elems() const { size_t n = 1; for (auto &d : c->dims) n *= (size_t)d.num_pixels(); return n; }
     int dtype() const { return c->source ? RecFilter(c->source).dtype() : c->inputs.at(0).dtype; }
     size_t n_planes() const { return c->source ? RecFilter(c->source).n_planes() : c->inputs.size(); }
-    static size_t dtype_size(int dt) { return dt == RF_F64 ? 8 : (dt == RF_I16 ? 2 : 4); }
+    static size_t dtype_size(int dt) { return dt == RF_F64 ? 8 : ((dt == RF_I16 || dt == RF_F16 || dt == RF_BF16) ? 2 : 4); }
     explicit RecFilter(std::shared_ptr<Contents> p) : c(std::move(p)) {}
 
 public:

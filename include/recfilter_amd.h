@@ -53,8 +53,17 @@ typedef enum {
 } rf_status;
 
 /* pixel type P = type of the defining expression (lib/recfilter.cpp:197); coefficients are
- * cast to P (lib/recfilter.cpp:324,335) */
-typedef enum { RF_F32 = 0, RF_F64 = 1, RF_I32 = 2, RF_I16 = 3 } rf_dtype;
+ * cast to P (lib/recfilter.cpp:324,335).
+ *
+ * RF_F16 (IEEE binary16) and RF_BF16 (bfloat16) deliberately depart from that rule: they are STORAGE types.  Input and output
+ * planes hold 16-bit floats; every sample is widened exactly to f32 as it is loaded; coefficients, tails, carries, tables,
+ * pointwise stages and every intermediate are those of an RF_F32 plan of the same description; the result is rounded ONCE,
+ * to nearest even, at the final store (overflow to +-inf, NaN propagates):  out = round16(F_f32(widen(in))).
+ * 2-D images (width a multiple of 4) and long 1-D signals run natively on RF_PATH_TILED_FUSED; every other plan is staged
+ * through plan-owned f32 planes (steps "convert_in" / "convert_out", counted in rf_plan_workspace_bytes; rf_plan_path
+ * reports the inner f32 plan's path).  RF_IN_U8 input and shards other than the row shards of a 2-D image on the fused
+ * path: RF_ERR_UNSUPPORTED. */
+typedef enum { RF_F32 = 0, RF_F64 = 1, RF_I32 = 2, RF_I16 = 3, RF_F16 = 4, RF_BF16 = 5 } rf_dtype;
 
 /* default border is zero; RecFilter::set_clamped_image_border (lib/recfilter.cpp:252-258) */
 typedef enum { RF_BORDER_ZERO = 0, RF_BORDER_CLAMP = 1 } rf_border;
@@ -164,7 +173,10 @@ typedef struct {
  *                           2-D image (or batched Tuple planes), unsharded, whose scans along a dimension are one scan or
  *                           a causal-then-anticausal pair, completes that dimension's carries from the neighbouring
  *                           tiles' tails alone where the filter decays within a tile -- the part that form drops is
- *                           at most 2^-32 of the largest carry (rf_plan_table("neighbour_carries")). */
+ *                           at most 2^-32 of the largest carry (rf_plan_table("neighbour_carries")).
+ *   RF_PLAN_STAGE_HALF      RF_F16 / RF_BF16 pixels: the plan is staged through f32 planes even where the fused kernels
+ *                           would run it natively (same result to the last rounding; for comparisons).  Ignored for the
+ *                           other pixel types. */
 #define RF_PLAN_FORCE_EXCHANGE  0x01u
 #define RF_PLAN_TILED_ONLY      0x02u
 #define RF_PLAN_NO_CASCADE      0x04u
@@ -179,7 +191,8 @@ typedef struct {
 #define RF_PLAN_NO_OVERLAP      0x08000000u
 #define RF_PLAN_INPLACE_Z       0x10000000u
 #define RF_PLAN_FULL_CARRY_SCAN 0x20000000u
-#define RF_PLAN_ALL_FLAGS       0x3f0000ffu
+#define RF_PLAN_STAGE_HALF      0x40000000u
+#define RF_PLAN_ALL_FLAGS       0x7f0000ffu
 #define RF_PLAN_TILE_ROWS(n)    (((uint32_t)(n) & 0xffu) << 8)
 #define RF_PLAN_TILE_PLANES(n)  (((uint32_t)(n) & 0xffu) << 16)
 

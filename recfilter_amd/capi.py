@@ -23,7 +23,7 @@ RF_MAX_PLANES = 16
 RF_DEVICE_HOST_ONLY = -2
 
 RF_OK, RF_ERR_INVALID_ARG, RF_ERR_UNSUPPORTED, RF_ERR_HIP, RF_ERR_NOMEM, RF_ERR_STATE = range(6)
-RF_F32, RF_F64, RF_I32, RF_I16 = range(4)
+RF_F32, RF_F64, RF_I32, RF_I16, RF_F16, RF_BF16 = range(6)      # RF_F16 / RF_BF16: 16-bit float STORAGE, f32 arithmetic
 RF_BORDER_ZERO, RF_BORDER_CLAMP = 0, 1
 RF_POINTWISE_PRE, RF_POINTWISE_POST = 1, 2
 RF_IN_PIXEL, RF_IN_U8 = 0, 1
@@ -37,6 +37,7 @@ RF_PLAN_WALK_PASS1 = 0x04000000
 RF_PLAN_NO_OVERLAP = 0x08000000
 RF_PLAN_INPLACE_Z = 0x10000000
 RF_PLAN_FULL_CARRY_SCAN = 0x20000000
+RF_PLAN_STAGE_HALF = 0x40000000       # 16-bit float pixels: staged through f32 planes even where the fused kernels run them
 
 
 def RF_PLAN_TILE_ROWS(n: int) -> int:

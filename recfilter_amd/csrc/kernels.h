@@ -39,6 +39,10 @@ int launch_pointwise(const P *f, const P *x, P *dst, int64_t n, double c0, doubl
 template <typename P, typename X>
 int launch_pointwise_from(const P *f, const X *x, P *dst, int64_t n, double c0, double c1, double c2, hipStream_t stream);
 
+// ---- conversion of a plane between a 16-bit float storage type (_Float16, __bf16) and f32 (staged 16-bit plans) ----
+template <typename D, typename S>
+int launch_convert(const S *src, D *dst, int64_t n, hipStream_t stream);
+
 // ---- finite differences of summed-area tables (rf_box_difference) ----
 struct BoxDiffArgs {
     int64_t n[RF_MAX_DIMS];       // extents, x first (1 for missing dimensions)

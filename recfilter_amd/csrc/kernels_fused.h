@@ -202,8 +202,9 @@ bool stream_tails_applicable(int K, int TY, bool src_u8, int pw_flags, int last_
 int launch_stream_tails(int K, const float *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream);
 // pass 1 with the x-tail contraction on the matrix cores, one tile per workgroup (kernels_tails_mfma.hip)
 bool mfma_tails_applicable(int K, int TY, bool src_u8, int pw_flags, int last_cols, int last_rows, int64_t lin_limit, int nx, int ny,
-                           int mode);
-int launch_mfma_tails(int K, int TY, const float *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream);
+                           int mode, bool narrow = false /* planes of a 16-bit float storage type */);
+template <typename PI>      // float, _Float16, __bf16
+int launch_mfma_tails(int K, int TY, const PI *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream);
 // pass 1 of a 3-D plan in one read of the volume: x tails, the parts of the y tails' combined rows and the z tails
 // (kernels_tails_walk.hip)
 struct WalkArgs {

@@ -300,11 +300,20 @@ fused_pass2_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<ty
             constexpr bool EARLY = YPAT > 2;
             char *dpb_early = reinterpret_cast<char *>(dst + tile_off);
             // (with the pointwise epilogue applied on the way out: EPI has this thread's input column in registers)
+            Acc held = Acc(0);
+            (void)held;
             auto row_out = [&](int m, Acc v) __attribute__((always_inline)) {
                 if constexpr (!PixelTraits<P>::is_integer) {
                     if constexpr (EPI) v = a.post_f * v + (a.post_i * orig[m] + a.post_b);
                     else if (a.pw_flags & 2) v = a.post_f * v + a.post_b;
                 }
+                if constexpr (packed_stores<P>::value) {
+                    // 16-bit float pixels: two rows at a time, one dword per lane (scan_device.h, store_row_pair); the scan
+                    // hands the rows over in its own direction, so the first row of a pair waits for the second
+                    constexpr bool up = PAT == 2;
+                    if (((m & 1) != 0) == up) held = v;
+                    else store_row_pair<P>(dpb_early, (uint32_t)t, (uint32_t)(m & ~1), a.row_bytes, up ? v : held, up ? held : v, (uint32_t)TY);
+                } else
                 __builtin_nontemporal_store(PixelTraits<P>::store(v),
                                             reinterpret_cast<P *>(dpb_early + ((uint32_t)t * (uint32_t)sizeof(P) + (uint32_t)m * a.row_bytes)));
             };
@@ -385,6 +394,15 @@ fused_pass2_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<ty
                 my_rows = left < (int64_t)rows_here ? (int)left : rows_here;
             }
             if (t < last_cols) {
+                if constexpr (packed_stores<P>::value && !LIN) {
+                    // (16-bit float pixels, scan_device.h: last_cols is a multiple of 4, so a column pair is stored or not as one;
+                    // rows_here is tile-uniform)
+                    if constexpr (std::is_same<Acc, float>::value) {
+#pragma unroll
+                        for (int i = 0; i < TY; i += 2)
+                            store_row_pair<P>(dpb, (uint32_t)t, (uint32_t)i, row_bytes, col[i], col[i + 1], (uint32_t)my_rows);
+                    }
+                } else
                 if (my_rows == TY) {
 #pragma unroll
                     for (int i = 0; i < TY; i++)
@@ -432,7 +450,8 @@ static int launch_fused_pass2_typed(int K, int TY, const PI *src, P *dst, const 
     const bool edge = a.last_cols != kFusedTX || a.last_rows != TY;
     // (three launches like the 128-row final pass's -- whole tiles lean, edge strips on the EDGE variant -- gain nothing here:
     // the 64-row EDGE variant costs 20-35 % per tile, what the two extra strips cost: 8192 x 8188, 0.134 / 0.135 ms)
-    if constexpr (!PixelTraits<P>::is_integer) epi = (a.pw_flags & 2) && a.post_i != typename PixelTraits<P>::Acc(0) && K <= 2;
+    // (16-bit float pixels: no such instances -- their input operand comes back through the caches, as at order 3)
+    if constexpr (!PixelTraits<P>::is_integer && !is_half_pixel<P>::value) epi = (a.pw_flags & 2) && a.post_i != typename PixelTraits<P>::Acc(0) && K <= 2;
     if (a.lin_limit > 0 && (a.ny != 0 || a.NZ != 1 || a.plane_batch || epi || edge)) {
         set_error("fused pass 2: a signal that ends inside the image needs a 1-D plan of whole tiles without an input-operand epilogue");
         return RF_ERR_INVALID_ARG;
@@ -455,7 +474,7 @@ static int launch_fused_pass2_typed(int K, int TY, const PI *src, P *dst, const 
         if constexpr (std::is_same<P, PI>::value) {                                                             \
             if (a.lin_limit > 0) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 0, false, true>(src, dst, a, stream); \
         }                                                                                                       \
-        if constexpr (!PixelTraits<P>::is_integer) {                                                            \
+        if constexpr (!PixelTraits<P>::is_integer && !is_half_pixel<P>::value) {                                \
             if (epi && edge) return launch_fused_pass2_impl<P, KK, TT, true, true, PI>(src, dst, a, stream);    \
             if constexpr (TT == 64 && std::is_same<P, PI>::value) {                                             \
                 if (epi && ypat == 1) return launch_fused_pass2_impl<P, KK, TT, true, false, PI, 3>(src, dst, a, stream); \
@@ -500,6 +519,8 @@ int launch_fused_pass2(int K, int TY, const void *src, bool src_u8, P *dst, cons
 template int launch_fused_pass2<float>(int, int, const void *, bool, float *, const FusedArgs<float> &, hipStream_t);
 template int launch_fused_pass2<int32_t>(int, int, const void *, bool, int32_t *, const FusedArgs<uint32_t> &, hipStream_t);
 template int launch_fused_pass2<int16_t>(int, int, const void *, bool, int16_t *, const FusedArgs<uint32_t> &, hipStream_t);
+template int launch_fused_pass2<_Float16>(int, int, const void *, bool, _Float16 *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2<__bf16>(int, int, const void *, bool, __bf16 *, const FusedArgs<float> &, hipStream_t);
 template int launch_fused_pass2<double>(int, int, const void *, bool, double *, const FusedArgs<double> &, hipStream_t);
 
 }  // namespace rf

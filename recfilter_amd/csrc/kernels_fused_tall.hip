@@ -324,7 +324,16 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     // whole tiles without an epilogue: the rows are stored from inside the last scan, each as soon as it is final
     char *dpb_early = reinterpret_cast<char *>(dst + tile_off);
     static_assert(!EARLY || (!EDGE && YPAT > 0), "early stores: whole tiles, fixed scan pattern");
+    Acc held = Acc(0);
+    (void)held;
     auto row_out = [&](int m, Acc v) __attribute__((always_inline)) {
+        if constexpr (packed_stores<P>::value) {
+            // 16-bit float pixels: two rows at a time, one dword per lane (scan_device.h, store_row_pair); the scan hands the
+            // rows over in its own direction, so the first row of a pair waits for the second
+            constexpr bool up = YPAT == 2;
+            if (((m & 1) != 0) == up) held = v;
+            else store_row_pair<P>(dpb_early, (uint32_t)t, (uint32_t)(m & ~1), a.row_bytes, up ? v : held, up ? held : v, (uint32_t)TY);
+        } else
         __builtin_nontemporal_store(PixelTraits<P>::store(v),
                                     reinterpret_cast<P *>(dpb_early + ((uint32_t)t * (uint32_t)sizeof(P) + (uint32_t)m * a.row_bytes)));
     };
@@ -372,6 +381,12 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
         char *dpb = reinterpret_cast<char *>(dst + tile_off);
         const uint32_t row_bytes = a.row_bytes;
         if (t < last_cols) {
+            if constexpr (packed_stores<P>::value) {
+                // (16-bit float pixels, scan_device.h: last_cols is a multiple of 4, so a column pair is stored or not as one)
+#pragma unroll
+                for (int i = 0; i < TY; i += 2)
+                    store_row_pair<P>(dpb, (uint32_t)t, (uint32_t)i, row_bytes, col[i], col[i + 1], (uint32_t)(EDGE ? rows_here : TY));
+            } else
 #pragma unroll
             for (int i = 0; i < TY; i++)
                 if (!EDGE || i < rows_here)
@@ -466,6 +481,8 @@ int launch_fused_pass2_tall(int K, const void *src, bool src_u8, P *dst, const F
 }
 
 template int launch_fused_pass2_tall<float>(int, const void *, bool, float *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2_tall<_Float16>(int, const void *, bool, _Float16 *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2_tall<__bf16>(int, const void *, bool, __bf16 *, const FusedArgs<float> &, hipStream_t);
 template int launch_fused_pass2_tall<int32_t>(int, const void *, bool, int32_t *, const FusedArgs<uint32_t> &, hipStream_t);
 template int launch_fused_pass2_tall<int16_t>(int, const void *, bool, int16_t *, const FusedArgs<uint32_t> &, hipStream_t);
 

@@ -842,6 +842,36 @@ template int launch_pointwise_from<float, uint8_t>(const float *, const uint8_t 
 template int launch_pointwise<float>(const float *, const float *, float *, int64_t, double, double, double, hipStream_t);
 template int launch_pointwise<double>(const double *, const double *, double *, int64_t, double, double, double, hipStream_t);
 
+// ---- conversion between a 16-bit float storage type and f32 planes (staged 16-bit plans, plan.cpp) ----
+// Eight samples per thread (16 bytes of the narrow type) where both planes are 16-byte aligned, sample by sample otherwise
+// and for the last n % 8.  Widening is exact; narrowing is the one rounding of the plan (to nearest even).
+template <typename D, typename S>
+__global__ void __launch_bounds__(kBlock)
+convert_kernel(const S *__restrict__ src, D *__restrict__ dst, int64_t n, int64_t n8) {
+    typedef S S8 __attribute__((ext_vector_type(8)));
+    typedef D D8 __attribute__((ext_vector_type(8)));
+    const int64_t step = (int64_t)gridDim.x * kBlock, first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    for (int64_t i = first; i < n8; i += step)
+        reinterpret_cast<D8 *>(dst)[i] = __builtin_convertvector(reinterpret_cast<const S8 *>(src)[i], D8);
+    for (int64_t i = 8 * n8 + first; i < n; i += step) dst[i] = (D)(float)src[i];
+}
+
+template <typename D, typename S>
+int launch_convert(const S *src, D *dst, int64_t n, hipStream_t stream) {
+    if (n <= 0) return RF_OK;
+    const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0;
+    const int64_t n8 = aligned ? n / 8 : 0;
+    const int64_t want = ((aligned ? n8 + 8 : n) + kBlock - 1) / kBlock;
+    const unsigned blocks = (unsigned)(want < 256 * 64 ? want : 256 * 64);
+    hipLaunchKernelGGL((convert_kernel<D, S>), dim3(blocks), dim3(kBlock), 0, stream, src, dst, n, n8);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
+}
+template int launch_convert<float, _Float16>(const _Float16 *, float *, int64_t, hipStream_t);
+template int launch_convert<float, __bf16>(const __bf16 *, float *, int64_t, hipStream_t);
+template int launch_convert<_Float16, float>(const float *, _Float16 *, int64_t, hipStream_t);
+template int launch_convert<__bf16, float>(const float *, __bf16 *, int64_t, hipStream_t);
+
 template <typename P>
 int launch_box_difference(const P *in, P *out, const BoxDiffArgs &a, hipStream_t stream) {
     if (a.n[0] <= 0 || a.n[1] <= 0 || a.n[2] <= 0) return RF_OK;

@@ -775,7 +775,7 @@ int launch_fused_tails(int K, int TY, const void *src, bool src_u8, const FusedA
                 return RF_OK;                                                                                        \
             }                                                                                                        \
         }                                                                                                            \
-        if constexpr (std::is_same<P, float>::value && TT >= 32) {                                                   \
+        if constexpr (is_f32_arith<P>::value && TT >= 32) {                                                          \
             if (ymfma) {        /* y tails on the matrix cores; the step's Hy slice behind Hx in the dynamic LDS */         \
                 hipLaunchKernelGGL((fused_tails_kernel<P, KK, TT, P, 0, true>), grid, dim3(kFusedThreads), hx_bytes + hy_bytes, \
                                    stream, (const P *)src, a, Hx, Hy);                                               \
@@ -901,6 +901,8 @@ int launch_xscan_rows(int K, int TY, const FusedArgs<Acc> &a, const Acc *Hy, con
 }
 
 template int launch_fused_tails<float>(int, int, const void *, bool, const FusedArgs<float> &, const float *, const float *, hipStream_t);
+template int launch_fused_tails<_Float16>(int, int, const void *, bool, const FusedArgs<float> &, const float *, const float *, hipStream_t);
+template int launch_fused_tails<__bf16>(int, int, const void *, bool, const FusedArgs<float> &, const float *, const float *, hipStream_t);
 template int launch_fused_tails<int32_t>(int, int, const void *, bool, const FusedArgs<uint32_t> &, const uint32_t *,
                                          const uint32_t *, hipStream_t);
 template int launch_fused_tails<int16_t>(int, int, const void *, bool, const FusedArgs<uint32_t> &, const uint32_t *,

@@ -18,7 +18,7 @@
 // per step 96-110 KiB instead of 258.  The tile image is XOR-swizzled per ROW (kernels_stream.hip, slot_pos): the 16 rows an
 // A operand gathers at one column sit on 16 different bank groups.
 //
-// Takes f32 images of whole tiles (width % 256 == 0, height % TY == 0) without a fused prologue; everything else stays on
+// Takes f32 images (and images stored as 16-bit floats) of whole tiles (width % 256 == 0, height % TY == 0) without a fused prologue; everything else stays on
 // fused_tails_kernel.  Same tables, same tails (summation order differs: results equal to rounding).
 #include <atomic>
 #include <cstdlib>
@@ -53,9 +53,12 @@ __device__ __forceinline__ int row_swz(int row, int c) { return c ^ (row & 15) ^
 
 // NX, NY: scans along x / y (compile time: they size the Hx register fragments and the y accumulators -- at four workgroups
 // per CU the kernel has 128 registers and uses nearly all of them); YM: y tails on the matrix cores
-template <int K, int TY, int NX, int NY, bool YM>
+// PI: what the planes hold -- float, or a 16-bit float storage type (pixel.h): a thread then fetches its four samples of a row
+// as 8 bytes, keeps them packed until the step's rows are written into the LDS tile, and widens them there; the tile, the
+// contraction and the tails are f32 either way
+template <int K, int TY, int NX, int NY, bool YM, typename PI = float>
 __global__ void __launch_bounds__(kFusedThreads, 4)
-mfma_tails_kernel(const float *__restrict__ src, FusedArgs<float> a,
+mfma_tails_kernel(const PI *__restrict__ src, FusedArgs<float> a,
                   const float *__restrict__ Hx,     // [vx][s][r][256]
                   const float *__restrict__ Hy) {   // [vy][j][r][TY]
     __shared__ __attribute__((aligned(16))) float tile[kRows * kFusedTX];
@@ -71,7 +74,7 @@ mfma_tails_kernel(const float *__restrict__ src, FusedArgs<float> a,
     const int t = threadIdx.x;
     const int tx = blockIdx.x, ty = blockIdx.y;
     const int64_t z = blockIdx.z;
-    if (a.plane_batch) src = reinterpret_cast<const float *>(a.in_planes[z]);
+    if (a.plane_batch) src = reinterpret_cast<const PI *>(a.in_planes[z]);
     const int64_t tile_off = (a.plane_batch ? 0 : z * a.NX * a.NY) + (int64_t)ty * TY * a.NX + (int64_t)tx * kFusedTX;
     const int vx = (tx == 0 ? 1 : 0) | (tx == a.MX - 1 ? 2 : 0);
     const int vy = ((ty == 0 && a.y_first_border) ? 1 : 0) | ((ty == a.MY - 1 && a.y_last_border) ? 2 : 0);
@@ -84,10 +87,11 @@ mfma_tails_kernel(const float *__restrict__ src, FusedArgs<float> a,
     const int lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int row16 = lane & 15, cg = lane >> 4, j4 = lane & 3;      // x part: A row, column phase; B tail within its group
     const char *spb = reinterpret_cast<const char *>(src + tile_off);
-    const uint32_t off0 = (uint32_t)rg * a.row_bytes + (uint32_t)cc * 16u;
-    auto ld = [&](int row) { return __builtin_nontemporal_load(reinterpret_cast<const F4 *>(spb + (off0 + (uint32_t)row * a.row_bytes))); };
+    typedef PI Raw4 __attribute__((ext_vector_type(4)));              // (row_bytes counts the planes' bytes)
+    const uint32_t off0 = (uint32_t)rg * a.row_bytes + (uint32_t)cc * (uint32_t)sizeof(Raw4);
+    auto ld = [&](int row) { return __builtin_nontemporal_load(reinterpret_cast<const Raw4 *>(spb + (off0 + (uint32_t)row * a.row_bytes))); };
 
-    F4 pre[NL];
+    Raw4 pre[NL];
     F4 hy_pre = F4{0.f, 0.f, 0.f, 0.f};
     const int hy_jr = t >> 3, hy_m = t & 7;
     const int nyk4 = (nyk + 3) & ~3;
@@ -147,7 +151,7 @@ mfma_tails_kernel(const float *__restrict__ src, FusedArgs<float> a,
             if (nxk > 0) flush_xtails(h - 1);
         }
 #pragma unroll
-        for (int i = 0; i < NL; i++) tile4[(rg + 4 * i) * 64 + row_swz(rg + 4 * i, cc)] = pre[i];
+        for (int i = 0; i < NL; i++) tile4[(rg + 4 * i) * 64 + row_swz(rg + 4 * i, cc)] = __builtin_convertvector(pre[i], F4);
         if constexpr (YM) {
             if (hy_jr < nyk4) hy4[hy_jr * kHyPitch4 + hy_m] = hy_pre;
         }
@@ -267,8 +271,10 @@ mfma_tails_kernel(const float *__restrict__ src, FusedArgs<float> a,
 
 // When pass 1 takes this kernel: f32 images of whole tiles, no prologue, pixel-typed planes (the launch is the same grid as
 // fused_tails_kernel's: one workgroup per tile).  mode: 0 automatic, +1 wherever the shape allows, -1 never.
+// narrow: the planes hold a 16-bit float storage type -- orders 2 and 3, one scan or a pair per dimension (the instances built)
 bool mfma_tails_applicable(int K, int TY, bool src_u8, int pw_flags, int last_cols, int last_rows, int64_t lin_limit, int nx, int ny,
-                           int mode) {
+                           int mode, bool narrow) {
+    if (narrow && (K < 2 || nx != ny || nx < 1)) return false;
     static const char *knob = RF_KNOB("RF_TAILS_XMFMA");              // A/B: 0 = never, 1 = wherever the shape allows
     if (knob) mode = atoi(knob) != 0 ? 1 : -1;
     if (mode < 0) return false;
@@ -282,7 +288,8 @@ bool mfma_tails_applicable(int K, int TY, bool src_u8, int pw_flags, int last_co
     return K >= 2;
 }
 
-int launch_mfma_tails(int K, int TY, const float *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream) {
+template <typename PI>
+int launch_mfma_tails(int K, int TY, const PI *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream) {
     if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
     if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
     dim3 grid((unsigned)a.MX, (unsigned)a.MY, (unsigned)a.NZ);
@@ -293,19 +300,31 @@ int launch_mfma_tails(int K, int TY, const float *src, const FusedArgs<float> &a
     (void)nyk;
 #define RF_CASE(KK, TT, XX, YY)                                                                                           \
     if (K == KK && TY == TT && a.nx == XX && a.ny == YY) {                                                                \
-        hipLaunchKernelGGL((mfma_tails_kernel<KK, TT, XX, YY, false>), grid, dim3(kFusedThreads), stage_bytes, stream, src, a, Hx, Hy);            \
+        hipLaunchKernelGGL((mfma_tails_kernel<KK, TT, XX, YY, false, PI>), grid, dim3(kFusedThreads), stage_bytes, stream, src, a, Hx, Hy);        \
         RF_HIP_CHECK(hipGetLastError());                                                                                  \
         return RF_OK;                                                                                                     \
     }
-#define RF_CASES(KK, TT) RF_CASE(KK, TT, 2, 2) RF_CASE(KK, TT, 1, 1) RF_CASE(KK, TT, 2, 0) RF_CASE(KK, TT, 0, 2) RF_CASE(KK, TT, 1, 0) \
+#define RF_CASES_PAIRS(KK, TT) RF_CASE(KK, TT, 2, 2) RF_CASE(KK, TT, 1, 1)
+#define RF_CASES(KK, TT) RF_CASES_PAIRS(KK, TT) RF_CASE(KK, TT, 2, 0) RF_CASE(KK, TT, 0, 2) RF_CASE(KK, TT, 1, 0) \
     RF_CASE(KK, TT, 0, 1) RF_CASE(KK, TT, 2, 1) RF_CASE(KK, TT, 1, 2)
-    RF_CASES(1, 32) RF_CASES(1, 64) RF_CASES(1, 128)
-    RF_CASES(2, 32) RF_CASES(2, 64) RF_CASES(2, 128)
-    RF_CASES(3, 32) RF_CASES(3, 64) RF_CASES(3, 128)
+    if constexpr (std::is_same<PI, float>::value) {
+        RF_CASES(1, 32) RF_CASES(1, 64) RF_CASES(1, 128)
+        RF_CASES(2, 32) RF_CASES(2, 64) RF_CASES(2, 128)
+        RF_CASES(3, 32) RF_CASES(3, 64) RF_CASES(3, 128)
+    } else {
+        // 16-bit float planes (mfma_tails_applicable, narrow): the instances the automatic choice takes for the usual filters
+        RF_CASES_PAIRS(2, 32) RF_CASES_PAIRS(2, 64) RF_CASES_PAIRS(2, 128)
+        RF_CASES_PAIRS(3, 32) RF_CASE(3, 64, 1, 1) RF_CASES_PAIRS(3, 128)
+    }
 #undef RF_CASES
+#undef RF_CASES_PAIRS
 #undef RF_CASE
     set_error("mfma tails: unsupported order %d / tile height %d / %d + %d scans", K, TY, a.nx, a.ny);
     return RF_ERR_UNSUPPORTED;
 }
+
+template int launch_mfma_tails<float>(int, int, const float *, const FusedArgs<float> &, const float *, const float *, hipStream_t);
+template int launch_mfma_tails<_Float16>(int, int, const _Float16 *, const FusedArgs<float> &, const float *, const float *, hipStream_t);
+template int launch_mfma_tails<__bf16>(int, int, const __bf16 *, const FusedArgs<float> &, const float *, const float *, hipStream_t);
 
 }  // namespace rf

@@ -29,6 +29,7 @@ namespace {
 double cast_coeff(double c, int dtype) {
     switch (dtype) {
         case RF_F32: return (double)(float)c;
+        case RF_F16: case RF_BF16: return (double)(float)c;      // storage types: the coefficients are the f32 plan's (pixel.h)
         case RF_F64: return c;
         case RF_I32: return (double)(int32_t)c;   // Cast::make(Int(32), float): truncation
         case RF_I16: return (double)(int16_t)c;
@@ -376,6 +377,88 @@ int build_clamped_1d(const rf_filter_desc *desc, rf_plan *parent) {
     return RF_OK;
 }
 
+// ---- staged 16-bit plans ---------------------------------------------------------------------------------------------------
+// RF_F16 / RF_BF16 are storage types: out = round16(F_f32(widen(in))), no intermediate is ever rounded (pixel.h).  The fused
+// x/y kernels keep that contract by themselves (2-D images, 1-D signals: plan_fused.cpp).  Every other structure keeps an
+// intermediate in the output planes -- the x stage in front of the y stage of the line-parallel, generic, overlapped and
+// matrix paths, the x/y stage in front of a volume's z stage, the earlier stages of a cascade -- so such a plan owns one f32
+// plane per image plane and runs
+//     convert_in -> the f32 plan of the same description, in place in those planes -> convert_out
+// (an epilogue with an input operand needs out != in: a second f32 plane per image plane).  The steps carry those two
+// names, rf_plan_path reports the inner plan's path, rf_plan_workspace_bytes includes the planes.
+template <typename H>
+int build_staged_half_typed(const rf_filter_desc *desc, rf_plan *parent) {
+    rf_filter_desc fd = *desc;
+    fd.dtype = RF_F32;
+    rf_plan *child = nullptr;
+    int rc = build_plan(&fd, &child);
+    if (rc != RF_OK) return rc;
+    std::unique_ptr<rf_plan> holder(child);
+    int status = RF_OK;
+    const bool two = parent->pw.post && parent->pw.post_i != 0.0;
+    const size_t plane_bytes = (size_t)parent->total * sizeof(float);
+    std::vector<float *> pa((size_t)parent->n_planes, nullptr), pb((size_t)parent->n_planes, nullptr);
+    for (int pl = 0; pl < parent->n_planes; pl++) {
+        pa[(size_t)pl] = (float *)parent->alloc(plane_bytes, false, &status);
+        pb[(size_t)pl] = two ? (float *)parent->alloc(plane_bytes, false, &status) : pa[(size_t)pl];
+    }
+    if (status != RF_OK) return status;
+    const int64_t total = parent->total;
+    Step ci;
+    ci.name = "convert_in";
+    ci.run = [parent, pa, total](int pl) {
+        return launch_convert<float, H>((const H *)parent->orig_in[pl], pa[(size_t)pl], total, parent->stream);
+    };
+    parent->begin_steps.push_back(ci);
+    std::vector<const Step *> steps;
+    for (const Step &s : child->begin_steps) steps.push_back(&s);
+    for (const auto &ex : child->exchange_local_steps)
+        for (const Step &s : ex) steps.push_back(&s);
+    for (const Step &s : child->finish_steps) steps.push_back(&s);
+    for (size_t k = 0; k < steps.size(); k++) {
+        const Step *sp = steps[k];
+        Step w;
+        w.name = sp->name;
+        const bool first = k == 0;
+        w.run = [parent, child, sp, first, pa, pb](int pl) {
+            if (first && pl == 0) {          // the child's context, all planes
+                for (int q = 0; q < parent->n_planes; q++) {
+                    child->in[q] = child->orig_in[q] = pa[(size_t)q];
+                    child->out[q] = pb[(size_t)q];
+                }
+                child->stream = parent->stream;
+            }
+            return sp->run(pl);
+        };
+        parent->begin_steps.push_back(w);
+    }
+    Step co;
+    co.name = "convert_out";
+    co.run = [parent, pb, total](int pl) {
+        return launch_convert<H, float>(pb[(size_t)pl], (H *)parent->out[pl], total, parent->stream);
+    };
+    parent->begin_steps.push_back(co);
+    for (auto &ex : child->exchanges) ex.send = ex.scratch;
+    parent->path = child->path;
+    parent->vector_access = false;           // (the conversions take any element-aligned plane)
+    parent->workspace_bytes += child->workspace_bytes;
+    for (int d = 0; d < RF_MAX_DIMS; d++) { parent->dims[d].T = child->dims[d].T; parent->dims[d].M = child->dims[d].M; }
+    parent->tables = child->tables;
+    parent->stages.push_back(std::move(holder));
+    return RF_OK;
+}
+
+int build_staged_half(const rf_filter_desc *desc, rf_plan *parent) {
+    if (parent->sharded()) {
+        set_error("16-bit float pixels: only row-sharded 2-D images on the fused path can be sharded");
+        return RF_ERR_UNSUPPORTED;
+    }
+    parent->begin_steps.clear();
+    parent->finish_steps.clear();
+    parent->stages.clear();
+    return desc->dtype == RF_F16 ? build_staged_half_typed<_Float16>(desc, parent) : build_staged_half_typed<__bf16>(desc, parent);
+}
+
 // what a replica of this plan is built from (concurrent executions, capi.cpp)
 void save_desc(rf_plan *plan, const rf_filter_desc *desc) {
     plan->saved.d = *desc;
@@ -399,7 +482,7 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
     }
     if (desc->ndim < 1 || desc->ndim > RF_MAX_DIMS) { set_error("ndim must be 1..%d", RF_MAX_DIMS); return RF_ERR_INVALID_ARG; }
     if (desc->n_planes < 1 || desc->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d", RF_MAX_PLANES); return RF_ERR_INVALID_ARG; }
-    if (desc->dtype < RF_F32 || desc->dtype > RF_I16) { set_error("unknown dtype %d", desc->dtype); return RF_ERR_INVALID_ARG; }
+    if (desc->dtype < RF_F32 || desc->dtype > RF_BF16) { set_error("unknown dtype %d", desc->dtype); return RF_ERR_INVALID_ARG; }
     if (desc->n_scans < 0 || desc->n_scans > RF_MAX_SCANS || (desc->n_scans > 0 && !desc->scans)) {
         set_error("n_scans must be 0..%d", RF_MAX_SCANS);
         return RF_ERR_INVALID_ARG;
@@ -429,7 +512,8 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
     if (pwd.flags & ~(RF_POINTWISE_PRE | RF_POINTWISE_POST)) { set_error("unknown pointwise flags 0x%x", pwd.flags); return RF_ERR_INVALID_ARG; }
     if (pwd.in_dtype != RF_IN_PIXEL && pwd.in_dtype != RF_IN_U8) { set_error("unknown pointwise input type %d", pwd.in_dtype); return RF_ERR_INVALID_ARG; }
     if (pwd.in_dtype == RF_IN_U8 && desc->dtype != RF_F32) { set_error("unsigned-byte input needs f32 pixels"); return RF_ERR_UNSUPPORTED; }
-    if (pwd.flags != 0 && desc->dtype != RF_F32 && desc->dtype != RF_F64) {
+    const bool half = desc->dtype == RF_F16 || desc->dtype == RF_BF16;      // storage types with f32 arithmetic (pixel.h)
+    if (pwd.flags != 0 && desc->dtype != RF_F32 && desc->dtype != RF_F64 && !half) {
         set_error("pointwise stages need a floating-point pixel type");
         return RF_ERR_UNSUPPORTED;
     }
@@ -574,6 +658,23 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
         }
     }
 
+    // 16-bit float pixels: native where the fused kernels take the filter in one piece (no intermediate then reaches a plane),
+    // staged through f32 planes everywhere else ("staged 16-bit plans" above).  A native plan goes on below; the rewrites and
+    // the cascade that follow apply to f32 / f64 plans or to filters the fused kernels refuse, i.e. not to it.
+    auto finish_staged = [&](int rc) -> int {
+        if (rc != RF_OK) return rc;
+        save_desc(plan.get(), desc);
+        if (int fb = plan->finish_build()) return fb;
+        *out = plan.release();
+        return RF_OK;
+    };
+    if (half) {
+        std::string unused;
+        const bool native = (desc->path == RF_PATH_AUTO || desc->path == RF_PATH_TILED_FUSED) && !(desc->flags & RF_PLAN_STAGE_HALF) &&
+                            fused_plan_applicable(plan.get(), desc, &unused);
+        if (!native) return finish_staged(build_staged_half(desc, plan.get()));
+    }
+
     // Orders above 3 (lib/split.cpp:575-578 pads any order; the fused kernels stop at 3): with a zero border and float
     // pixels a scan of order 4..RF_MAX_ORDER is the same filter as its first/second/third-order sections applied one after
     // the other (sections.h), and those the fused kernels take -- as long as no dimension ends up with more than four scans.
@@ -700,8 +801,8 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
         // split() filter takes the line kernels too: the reference's own sweep, scripts/profile_app.sh, tiles at 32)
         // (scans in mod form -- clamped sections, above -- exist for the fused kernels only)
         if (fused_ok && !plan->mod_form && !plan->sharded() && max_extent <= long_limit && plan->total * plan->n_planes <= long_limit * long_limit * 4 &&
-            plan->pw.pre == false && plan->pw.post == false && line_scans_applicable(plan.get()))
-            path = RF_PATH_UNTILED;
+            plan->pw.pre == false && plan->pw.post == false && !half && line_scans_applicable(plan.get()))
+            path = RF_PATH_UNTILED;     // (16-bit float pixels: a native plan stays on the fused kernels, which round once)
         else if (fused_ok) path = RF_PATH_TILED_FUSED;
         // a filter split() along two or more dimensions with small tiles: the fully overlapped tiling (two passes over
         // the image instead of two per dimension)
@@ -743,6 +844,17 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
         return RF_ERR_INVALID_ARG;
     };
     int rc = build(path);
+    if (half && rc == RF_ERR_UNSUPPORTED && !plan->sharded()) {      // the fused builder refused the shape after all
+        std::unique_ptr<rf_plan> fresh(new rf_plan);
+        fresh->ndim = plan->ndim; fresh->dtype = plan->dtype; fresh->n_planes = plan->n_planes;
+        fresh->clamped = plan->clamped; fresh->device = plan->device; fresh->host_only = plan->host_only;
+        fresh->shard_rank = plan->shard_rank; fresh->shard_world = plan->shard_world; fresh->flags = plan->flags;
+        fresh->shard_extents = plan->shard_extents; fresh->shard_common = plan->shard_common;
+        fresh->scans = plan->scans; fresh->total = plan->total; fresh->pw = plan->pw;
+        for (int d = 0; d < RF_MAX_DIMS; d++) { fresh->dims[d] = plan->dims[d]; fresh->dims[d].T = 0; fresh->dims[d].M = 0; }
+        plan.swap(fresh);
+        return finish_staged(build_staged_half(desc, plan.get()));
+    }
     if (rc == RF_ERR_UNSUPPORTED && desc->path == RF_PATH_AUTO && path != RF_PATH_UNTILED && !plan->sharded() && !plan->mod_form) {
         // auto mode: a shape no tile fits falls back to the untiled recurrence (still on the GPU)
         std::unique_ptr<rf_plan> fresh(new rf_plan);

@@ -242,7 +242,8 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
 
     // neighbour-form carries (neighbour_carry_bound): f32 images and batched Tuple planes, unsharded, not chained rows, not in
     // mod form (a 3-D plan's x/y stage keeps its scans); the bound is reported whatever RF_PLAN_FULL_CARRY_SCAN says
-    const bool neighbour_plan = std::is_same<P, float>::value && plan->ndim == 2 && !plan->sharded() && !chained && !plan->mod_form;
+    // (f32 arithmetic: 16-bit float storage types take the same decision as the f32 plan of the same description)
+    const bool neighbour_plan = is_f32_arith<P>::value && plan->ndim == 2 && !plan->sharded() && !chained && !plan->mod_form;
     double nb_bound_x = -1.0, nb_bound_y = -1.0;
     std::vector<FusedScan<Acc>> hxs = fused_scans(dx.scan_ids, true), hys = fused_scans(dy.scan_ids, false);
     if (nx > 0) {
@@ -538,7 +539,12 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
                 return launch_stream_tails(K, (const float *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
             // ... other f32 images of whole tiles contract their x tails on the matrix cores (kernels_tails_mfma.hip)
             if (mfma_tails_applicable(K, TY, plan->pw.in_u8, a.pw_flags, a.last_cols, a.last_rows, a.lin_limit, a.nx, a.ny, mfma_mode))
-                return launch_mfma_tails(K, TY, (const float *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
+                return launch_mfma_tails<float>(K, TY, (const float *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
+        }
+        // ... and so do images stored as 16-bit floats (the kernel widens the samples on their way into its f32 tile)
+        if constexpr (is_half_pixel<P>::value) {
+            if (mfma_tails_applicable(K, TY, false, a.pw_flags, a.last_cols, a.last_rows, a.lin_limit, a.nx, a.ny, mfma_mode, true))
+                return launch_mfma_tails<P>(K, TY, (const P *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
         }
         return launch_fused_tails<P>(K, TY, padded ? plan->pad_in[pl] : plan->in[pl], plan->pw.in_u8, a, d_Hx, d_Hy, plan->stream);
     };
@@ -742,6 +748,10 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
             }
         }
         int rc;
+        if constexpr (is_half_pixel<P>::value) {      // (fused_plan_applicable: no volumes of 16-bit float pixels)
+            set_error("fused path: volumes of 16-bit float pixels are staged through f32 planes");
+            return RF_ERR_UNSUPPORTED;
+        } else
         if constexpr (sizeof(Acc) == 4)
             rc = strided_tile(plan, 2) > 0 ? add_strided_dimension<P, S>(plan, 2, /*from_input=*/false, desc, first_begin_step,
                                                                          walk_hook.get(), walk_hook ? walk_child.release() : nullptr)
@@ -767,8 +777,14 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
 
 bool fused_plan_applicable(const rf_plan *plan, const rf_filter_desc *, std::string *why) {
     auto no = [&](const char *msg) { if (why) *why = msg; return false; };
-    if (plan->dtype != RF_F32 && plan->dtype != RF_I32 && plan->dtype != RF_I16 && plan->dtype != RF_F64)
-        return no("pixel type must be f32, f64, i32 or i16");
+    const bool half = plan->dtype == RF_F16 || plan->dtype == RF_BF16;
+    if (plan->dtype != RF_F32 && plan->dtype != RF_I32 && plan->dtype != RF_I16 && plan->dtype != RF_F64 && !half)
+        return no("pixel type must be f32, f64, i32, i16, f16 or bf16");
+    // 16-bit float storage types (pixel.h): 2-D images and 1-D signals run here natively -- no intermediate of theirs ever
+    // reaches a plane.  A volume's z stage would read the x/y stage's result back from the output planes, i.e. rounded to 16
+    // bits: volumes are staged through f32 planes (plan.cpp, "staged 16-bit plans").
+    if (half && plan->ndim > 2) return no("16-bit float pixels: 1-D signals and 2-D images");
+    if (half && plan->pw.in_u8) return no("16-bit float pixels: no unsigned-byte input");
     if (plan->dtype == RF_F64 && (plan->ndim < 2 || plan->pw.in_u8)) return no("f64 pixels: 2-D / 3-D images of f64 samples");
     if (plan->ndim == 1) {
         // a long 1-D signal folded into chained rows (zero border only: the clamped prologue would differ per row)
@@ -806,8 +822,8 @@ bool fused_plan_applicable(const rf_plan *plan, const rf_filter_desc *, std::str
     // rows of 4- and 8-byte pixels only have to be element-aligned: a width that is not a multiple of 4 ends every row in a
     // partial chunk, loaded sample by sample (scan_device.h, load_chunk_cols); 2-byte pixels and unsigned-byte inputs are
     // moved in 8- and 4-byte pieces and keep the rule
-    if (plan->dims[0].N % 4 != 0 && (plan->dtype == RF_I16 || plan->pw.in_u8))
-        return no("int16 pixels / uint8 inputs: width must be a multiple of 4");
+    if (plan->dims[0].N % 4 != 0 && (plan->dtype == RF_I16 || half || plan->pw.in_u8))
+        return no("2-byte pixels / uint8 inputs: width must be a multiple of 4");
     if (plan->ndim == 2 && plan->sharded() && plan->shard_common % 32 != 0)
         return no("row-sharded slabs must be whole tiles (height a multiple of 32)");
     const int K = fused_order(plan);
@@ -829,6 +845,8 @@ int build_fused_plan(rf_plan *plan, const rf_filter_desc *desc) {
     if (plan->dtype == RF_I32) return build_fused<int32_t, uint64_t>(plan, desc);
     if (plan->dtype == RF_I16) return build_fused<int16_t, uint64_t>(plan, desc);
     if (plan->dtype == RF_F64) return build_fused<double, double>(plan, desc);
+    if (plan->dtype == RF_F16) return build_fused<_Float16, double>(plan, desc);
+    if (plan->dtype == RF_BF16) return build_fused<__bf16, double>(plan, desc);
     set_error("fused path: unsupported pixel type");
     return RF_ERR_UNSUPPORTED;
 }

@@ -305,6 +305,37 @@ __device__ __forceinline__ void border_mod_col(Acc (&col)[TY], const SC &sc) {
     }
 }
 
+// ---- final stores of 16-bit float pixels ------------------------------------------------------------------------------
+// A lane of the y phase owns a column, so the plain store of a 16-bit pixel is a 2-byte store per lane and row
+// (global_store_short): as many store instructions as f32 pixels need, for half the bytes.  That is the form the library ships.
+// The packed form below -- built with -DRF_HALF_PACKED_STORES for A/B runs -- halves the store instructions: the lanes of a
+// column pair (t, t ^ 1) exchange one value (v_mov_b32_dpp quad_perm:[1,0,3,2]) so that the even lane holds both columns of
+// the even row and the odd lane both columns of the odd row; each converts its two values at once (v_cvt_pk_*) and stores one
+// dword, and every instruction of a wave still writes whole 128-byte pieces of two rows.  Measured level with the plain form
+// (cfg3 at 16384^2, same box, alternating: final pass 255 / 264 us packed against 256 / 254 us plain for f16, 255 / 257 against
+// 249 / 253 for bf16; profiles/r7/half_pixels_16384.txt): the 16-bit final pass is not bound by its store issue.
+// Call with the lanes of a pair either both active or both inactive (the callers' column bound is a multiple of 4).
+// row_even: the even row of the pair; rows: the rows that exist (a row >= rows is not stored).
+#ifdef RF_HALF_PACKED_STORES
+template <typename P> struct packed_stores { static constexpr bool value = is_half_pixel<P>::value; };
+#else
+template <typename P> struct packed_stores { static constexpr bool value = false; };
+#endif
+template <typename P>
+__device__ __forceinline__ void store_row_pair(char *tile_base, uint32_t t, uint32_t row_even, uint32_t row_bytes, float v_even,
+                                               float v_odd, uint32_t rows) {
+    typedef float F2 __attribute__((ext_vector_type(2)));
+    typedef P P2 __attribute__((ext_vector_type(2)));
+    const bool odd = (t & 1u) != 0;
+    const float got = dpp_move<0xB1>(odd ? v_even : v_odd);       // quad_perm:[1,0,3,2]: the pair partner's value of MY row
+    const F2 both = odd ? F2{got, v_odd} : F2{v_even, got};
+    const P2 packed = __builtin_convertvector(both, P2);
+    const uint32_t row = row_even + (odd ? 1u : 0u);
+    if (row < rows)
+        __builtin_nontemporal_store(__builtin_bit_cast(uint32_t, packed),
+                                    reinterpret_cast<uint32_t *>(tile_base + ((t & ~1u) * 2u + row * row_bytes)));
+}
+
 template <typename Acc>
 struct Vec4 {
     typedef Acc type __attribute__((ext_vector_type(4)));
@@ -320,7 +351,12 @@ __device__ __forceinline__ typename Vec4<Acc>::type load_chunk(const char *p) {
     using A4 = typename Vec4<Acc>::type;
     if constexpr (sizeof(PI) == sizeof(Acc)) {
         return __builtin_nontemporal_load(reinterpret_cast<const A4 *>(p));
-    } else if constexpr (sizeof(PI) == 2) {
+    } else if constexpr (is_half_pixel<PI>::value) {
+        // 16-bit float pixels (storage types, pixel.h): one 8-byte load, widened exactly to f32
+        typedef PI H4 __attribute__((ext_vector_type(4)));
+        const H4 w = __builtin_nontemporal_load(reinterpret_cast<const H4 *>(p));
+        return __builtin_convertvector(w, A4);
+    } else if constexpr (std::is_same<PI, int16_t>::value) {
         // int16 pixels (tests/test_type_invariance.cpp): one 8-byte load, sign-extended into the 32-bit ring
         typedef short S4 __attribute__((ext_vector_type(4)));
         const S4 w = __builtin_nontemporal_load(reinterpret_cast<const S4 *>(p));

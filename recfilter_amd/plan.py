@@ -21,23 +21,35 @@ Scan = Tuple[int, bool, Sequence[float]]   # (dim, causal, [feedfwd, fb1..fbk]);
 DEFAULT_FLAGS = 0
 
 _NP_DTYPES = {np.dtype(np.float32): capi.RF_F32, np.dtype(np.float64): capi.RF_F64,
-              np.dtype(np.int32): capi.RF_I32, np.dtype(np.int16): capi.RF_I16}
+              np.dtype(np.int32): capi.RF_I32, np.dtype(np.int16): capi.RF_I16, np.dtype(np.float16): capi.RF_F16}
+# the numpy type of the planes of every pixel type that has one (numpy has no bfloat16: such a plan is keyed on the torch type)
+_CODE_NP = {code: dt for dt, code in _NP_DTYPES.items()}
+_TORCH_NAMES = {"float32": capi.RF_F32, "float64": capi.RF_F64, "int32": capi.RF_I32, "int16": capi.RF_I16,
+                "float16": capi.RF_F16, "bfloat16": capi.RF_BF16}
 
 
 def _dtype_code(dtype) -> int:
+    """rf_dtype of a numpy / torch pixel type.  torch.float16 / np.float16 and torch.bfloat16 are STORAGE types: the planes
+    hold 16-bit floats, the filter runs in f32 and rounds once at the final store (include/recfilter_amd.h, rf_dtype)."""
     try:
         import torch
         if isinstance(dtype, torch.dtype):
-            dtype = {torch.float32: np.float32, torch.float64: np.float64,
-                     torch.int32: np.int32, torch.int16: np.int16}[dtype]
+            name = str(dtype).replace("torch.", "")
+            if name not in _TORCH_NAMES:
+                raise TypeError(f"unsupported pixel type {dtype}")
+            return _TORCH_NAMES[name]
     except ImportError:  # pragma: no cover
         pass
-    except KeyError:
-        raise TypeError(f"unsupported pixel type {dtype}")
     dt = np.dtype(dtype)
     if dt not in _NP_DTYPES:
         raise TypeError(f"unsupported pixel type {dt}")
     return _NP_DTYPES[dt]
+
+
+def _torch_dtype(code: int):
+    import torch
+    return {capi.RF_F32: torch.float32, capi.RF_F64: torch.float64, capi.RF_I32: torch.int32, capi.RF_I16: torch.int16,
+            capi.RF_F16: torch.float16, capi.RF_BF16: torch.bfloat16}[code]
 
 
 class Plan:
@@ -112,8 +124,8 @@ class Plan:
         self._desc = d
         self.shape = shape
         self.planes = int(planes)
-        self.np_dtype = np.dtype({capi.RF_F32: np.float32, capi.RF_F64: np.float64,
-                                  capi.RF_I32: np.int32, capi.RF_I16: np.int16}[d.dtype])
+        self.np_dtype = _CODE_NP.get(d.dtype)        # None for bfloat16, which numpy does not have
+        self.dtype_code = int(d.dtype)
         self.shard_world = int(shard_world)
         self._h = ctypes.c_void_p()
         capi.check(L.rf_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
@@ -197,8 +209,7 @@ class Plan:
 
     def _new_outputs(self, inputs):
         import torch
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
-               np.dtype(np.int16): torch.int16}[self.np_dtype]
+        tdt = _torch_dtype(self.dtype_code)
         return [torch.empty(t.shape, dtype=tdt, device=t.device) for t in inputs]
 
     @staticmethod
@@ -300,6 +311,8 @@ def box_difference(table, radius: int, order: Sequence[int], out=None, stream=No
     ords = (ctypes.c_int32 * len(shape))(*order[:len(shape)])
     if not table.is_cuda or not table.is_contiguous() or not out.is_contiguous():
         raise ValueError("box_difference needs contiguous device tensors")
+    if _dtype_code(table.dtype) in (capi.RF_F16, capi.RF_BF16):
+        raise TypeError("box_difference takes f32 / f64 tables: differences of a table rounded to 16 bits are not a box filter")
     capi.check(capi.lib().rf_box_difference(ctypes.c_void_p(table.data_ptr()), ctypes.c_void_p(out.data_ptr()), len(shape), ext,
                                             _dtype_code(table.dtype), int(radius), ords, Plan._stream(stream)))
     return out
@@ -317,6 +330,8 @@ def tap_filter(inputs, taps, out=None, stream=None):
     for t in inputs + [out]:
         if not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape or t.dtype != inputs[0].dtype:
             raise ValueError("tap_filter needs contiguous device tensors of one shape and type")
+    if _dtype_code(inputs[0].dtype) in (capi.RF_F16, capi.RF_BF16):
+        raise TypeError("tap_filter takes f32 / f64 planes, not 16-bit float planes")
     nd = len(shape)
     ext = (ctypes.c_int64 * nd)(*reversed(shape))
     arr = (capi.Tap * len(taps))()
