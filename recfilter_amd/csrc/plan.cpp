@@ -470,6 +470,19 @@ void save_desc(rf_plan *plan, const rf_filter_desc *desc) {
     plan->saved.d.shard_extents = nullptr;
 }
 
+// A new plan with the description part of `plan` and nothing a builder added (no tiles, steps, tables or buffers): what a
+// second builder starts from when the first one refused the shape.
+std::unique_ptr<rf_plan> fresh_description(const rf_plan &plan) {
+    std::unique_ptr<rf_plan> fresh(new rf_plan);
+    fresh->ndim = plan.ndim; fresh->dtype = plan.dtype; fresh->n_planes = plan.n_planes;
+    fresh->clamped = plan.clamped; fresh->device = plan.device; fresh->host_only = plan.host_only;
+    fresh->shard_rank = plan.shard_rank; fresh->shard_world = plan.shard_world; fresh->flags = plan.flags;
+    fresh->shard_extents = plan.shard_extents; fresh->shard_common = plan.shard_common;
+    fresh->scans = plan.scans; fresh->total = plan.total; fresh->pw = plan.pw;
+    for (int d = 0; d < RF_MAX_DIMS; d++) { fresh->dims[d] = plan.dims[d]; fresh->dims[d].T = 0; fresh->dims[d].M = 0; }
+    return fresh;
+}
+
 }  // namespace
 
 int build_plan(const rf_filter_desc *desc, rf_plan **out) {
@@ -845,28 +858,13 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
     };
     int rc = build(path);
     if (half && rc == RF_ERR_UNSUPPORTED && !plan->sharded()) {      // the fused builder refused the shape after all
-        std::unique_ptr<rf_plan> fresh(new rf_plan);
-        fresh->ndim = plan->ndim; fresh->dtype = plan->dtype; fresh->n_planes = plan->n_planes;
-        fresh->clamped = plan->clamped; fresh->device = plan->device; fresh->host_only = plan->host_only;
-        fresh->shard_rank = plan->shard_rank; fresh->shard_world = plan->shard_world; fresh->flags = plan->flags;
-        fresh->shard_extents = plan->shard_extents; fresh->shard_common = plan->shard_common;
-        fresh->scans = plan->scans; fresh->total = plan->total; fresh->pw = plan->pw;
-        for (int d = 0; d < RF_MAX_DIMS; d++) { fresh->dims[d] = plan->dims[d]; fresh->dims[d].T = 0; fresh->dims[d].M = 0; }
-        plan.swap(fresh);
+        plan = fresh_description(*plan);
         return finish_staged(build_staged_half(desc, plan.get()));
     }
     if (rc == RF_ERR_UNSUPPORTED && desc->path == RF_PATH_AUTO && path != RF_PATH_UNTILED && !plan->sharded() && !plan->mod_form) {
         // auto mode: a shape no tile fits falls back to the untiled recurrence (still on the GPU)
-        std::unique_ptr<rf_plan> fresh(new rf_plan);
-        // rebuild the description part
-        fresh->ndim = plan->ndim; fresh->dtype = plan->dtype; fresh->n_planes = plan->n_planes;
-        fresh->clamped = plan->clamped; fresh->device = plan->device; fresh->host_only = plan->host_only;
-        fresh->shard_rank = plan->shard_rank; fresh->shard_world = plan->shard_world; fresh->flags = plan->flags;
-        fresh->shard_extents = plan->shard_extents; fresh->shard_common = plan->shard_common;
-        fresh->scans = plan->scans; fresh->total = plan->total; fresh->pw = plan->pw;
-        fresh->pw.pre_fused = fresh->pw.post_fused = false;
-        for (int d = 0; d < RF_MAX_DIMS; d++) { fresh->dims[d] = plan->dims[d]; fresh->dims[d].T = 0; fresh->dims[d].M = 0; }
-        plan.swap(fresh);
+        plan = fresh_description(*plan);
+        plan->pw.pre_fused = plan->pw.post_fused = false;
         rc = build(RF_PATH_UNTILED);
     }
     if (rc != RF_OK) return rc;

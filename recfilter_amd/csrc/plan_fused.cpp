@@ -11,12 +11,14 @@
 //   carry_y          y carry recurrence, all y scans (one launch per scan around the exchanges when sharded); not run
 //                    where the y carries take the neighbour form
 //   fused_pass2      final correction pass
+// build_fused below is that list: geometry (fused_geometry) -> tables (fused_tables) -> buffers -> steps (FusedBuilder).
 #include <cmath>
 #include <cstring>
 #include <memory>
 
 #include "kernels_fused.h"
 #include "plan.h"
+#include "plan_carry.h"
 #include "plan_generic.h"
 #include "plan_strided.h"
 
@@ -102,16 +104,35 @@ double neighbour_carry_bound(const DimTables<S> &tab, const std::vector<int> &id
     return bound;
 }
 
-template <typename P, typename S>
-int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
+// ---- geometry ------------------------------------------------------------------------------------------------------
+// How the fused kernels tile the plan's image: decided from the description alone.  fused_geometry allocates nothing and
+// leaves the plan as it is.
+struct FusedGeometry {
+    const char *error = nullptr;         // non-null: a shape the kernels cannot tile (RF_ERR_UNSUPPORTED)
+    int K = 0;                           // feedback order the kernels run both dimensions at
+    bool chained = false;                // 1-D signal folded into chained rows
+    int64_t N1 = 0;                      // chained: the length the kernels see
+    bool in_place_tail = false, padded = false;
+    bool batch = false;                  // Tuple planes ride in one launch per step
+    int np = 1;                          // planes the steps run for (batched planes are inside Lx / Ly already, NZ)
+    bool rows_sharded = false, y_is_exchange_dim = false, y_sharded = false;
+    int64_t NX = 0, NY = 0, NZ = 1;
+    int nx = 0, ny = 0;                  // scans along x / y
+    int TY = 0, MX = 0, MY = 0;          // tile height, tiles per row / column
+    int TVx = 0, TVy = 0;                // samples / rows of the last tile
+    int64_t NXP = 0, NYP = 0;            // padded width / height
+    int64_t Lx = 0, Ly = 0;              // lines of the x / y carry stage
+};
+
+template <typename P>
+FusedGeometry fused_geometry(const rf_plan *plan) {
     using Acc = typename PixelTraits<P>::Acc;
-    int status = RF_OK;
-    plan->vector_access = true;                  // 16-byte chunks per lane in both passes
+    FusedGeometry g;
     const int K = fused_order(plan);
     const bool chained = plan->ndim == 1;        // 1-D signal folded into chained rows
-    DimInfo &dx = plan->dims[0];
-    DimInfo no_y;
-    DimInfo &dy = chained ? no_y : plan->dims[1];
+    const DimInfo &dx = plan->dims[0];
+    const DimInfo no_y;
+    const DimInfo &dy = chained ? no_y : plan->dims[1];
     const int64_t N1 = chained ? chained_padded_length(dx.N) : dx.N;     // chained: the length the kernels see
     // ... and whether they run on zero-padded COPIES (an epilogue that re-reads the input, RF_PAD_COPIES=1 for A/B runs) or on
     // the caller's buffers with the samples behind the signal's end masked (FusedArgs::lin_limit: no copy in, no copy out --
@@ -125,7 +146,6 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     const bool batch = plan->ndim == 2 && plan->n_planes > 1 && plan->n_planes <= kFusedMaxPlanes && !plan->sharded() &&
                        !(plan->flags & RF_PLAN_NO_PLANE_BATCH) && RF_KNOB("RF_NO_PLANE_BATCH") == nullptr;
     const int64_t NY = chained ? N1 / NX : dy.N, NZ = batch ? plan->n_planes : (plan->ndim > 2 ? plan->dims[2].N : 1);
-    const size_t first_begin_step = plan->begin_steps.size(), first_finish_step = plan->finish_steps.size();
     // tile height: 64 rows unless only 32 divides the height; any other height runs 64-row tiles (32 below 33 rows)
     // with a partial last tile row
     // (row shards: decided on the slabs' common divisor, so that every rank tiles alike)
@@ -177,7 +197,7 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         while (TY > 32 && NY % TY != 0) TY /= 2;
     // f64 pixels: a 256 x 32 tile is the 64 KiB of LDS a 256 x 64 tile of f32 takes (any height: partial last tile row)
     if (sizeof(Acc) == 8) {
-        if (rows_sharded && NYB % 32 != 0) { set_error("row-sharded f64 slabs must be multiples of 32 rows"); return RF_ERR_UNSUPPORTED; }
+        if (rows_sharded && NYB % 32 != 0) { g.error = "row-sharded f64 slabs must be multiples of 32 rows"; return g; }
         TY = 32;
     }
     const int nx = (int)dx.scan_ids.size(), ny = (int)dy.scan_ids.size();
@@ -191,65 +211,69 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     const int TVy = (int)(NY - (int64_t)(MY - 1) * TY);            // rows of the last tile row, (0, TY]
     const int64_t NXP = (int64_t)MX * kFusedTX;                     // padded width: pitch of everything indexed by column
     const int64_t NYP = (int64_t)MY * TY;                           // padded height: pitch of everything indexed by row
-    dx.T = kFusedTX; dx.M = chained ? N1 / kFusedTX : MX;
-    dy.T = TY;       dy.M = MY;
     const int64_t Lx = NYP * NZ, Ly = NXP * NZ;
     const int outer = plan->ndim - 1;
     const bool y_is_exchange_dim = (outer == 1);
     const bool y_sharded = y_is_exchange_dim && plan->sharded();
+    g.K = K; g.chained = chained; g.N1 = N1; g.in_place_tail = in_place_tail; g.padded = padded;
+    g.batch = batch; g.np = batch ? 1 : plan->n_planes;
+    g.rows_sharded = rows_sharded; g.y_is_exchange_dim = y_is_exchange_dim; g.y_sharded = y_sharded;
+    g.NX = NX; g.NY = NY; g.NZ = NZ; g.nx = nx; g.ny = ny;
+    g.TY = TY; g.MX = MX; g.MY = MY; g.TVx = TVx; g.TVy = TVy;
+    g.NXP = NXP; g.NYP = NYP; g.Lx = Lx; g.Ly = Ly;
+    return g;
+}
 
-    // ---- tables -------------------------------------------------------------------------
-    auto table_scans = [&](const std::vector<int> &ids) {
-        std::vector<ScanS<S>> v;
-        for (int id : ids) v.push_back(make_table_scan<S>(plan->scans[id]));
-        return v;
-    };
-    auto fused_scans = [&](const std::vector<int> &ids, bool with_segment_tables) {
-        std::vector<FusedScan<Acc>> v;
-        for (int id : ids) v.push_back(make_fused_scan<S, Acc>(plan->scans[id], K, with_segment_tables));
-        return v;
-    };
-    auto dev_scans = [&](const std::vector<int> &ids) {
-        std::vector<DevScan<Acc>> v;
-        for (int id : ids) {
-            DevScan<Acc> d = make_dev_scan<Acc>(plan->scans[id]);
-            d.order = K;
-            v.push_back(d);
-        }
-        return v;
-    };
-    auto flatten_W = [&](const DimTables<S> &tab, int n, std::vector<Acc> &hW, std::vector<Acc> &hA,
-                         const std::string &dn) {
-        hW.assign((size_t)4 * n * n * K * K, Acc(0));
-        hA.assign((size_t)n * K * K, Acc(0));
-        std::vector<double> dW(hW.size(), 0.0), dA(hA.size(), 0.0);
-        for (int v = 0; v < 4; v++)
-            for (int q = 0; q < n; q++)
-                for (int s = q + 1; s < n; s++)
-                    for (int e = 0; e < K * K; e++) {
-                        size_t idx = (((size_t)v * n + q) * n + s) * K * K + e;
-                        hW[idx] = table_to_acc<S, Acc>(tab.Wm(v, q, s)[e]);
-                        dW[idx] = table_to_double<S>(tab.Wm(v, q, s)[e]);
-                    }
-        for (int s = 0; s < n; s++)
-            for (int e = 0; e < K * K; e++) {
-                hA[(size_t)s * K * K + e] = table_to_acc<S, Acc>(tab.A[s][e]);
-                dA[(size_t)s * K * K + e] = table_to_double<S>(tab.A[s][e]);
-            }
-        plan->tables["W_" + dn] = dW;
-        plan->tables["A_" + dn] = dA;
-    };
+// ---- tables --------------------------------------------------------------------------------------------------------
+// Host tables of both dimensions, their uploads, and which dimensions take the neighbour form.
+template <typename S, typename Acc>
+struct FusedTables {
+    CarryStage<S, Acc> x, y;                         // W / A / A^C and the GenericDimArgs of the two carry stages
+    std::vector<FusedScan<Acc>> xs, ys;              // the scans as FusedArgs carries them
+    const Acc *G = nullptr;                          // G_x (device)
+    const Acc *Hx = nullptr, *Hy = nullptr;          // tail responses (device)
+    const Acc *AMx = nullptr, *AMSx = nullptr;       // per x scan A^MX and (A^MX)^chain_S (device): the row chain of chained rows
+    int chain_S = 1;                                 // rows per lane of the row-chain kernel
+    bool nb_x = false, nb_y = false;                 // neighbour-form carries (neighbour_carry_bound)
+    bool nb_x_pair() const { return nb_x && x.n == 2; }
+    bool nb_y_pair() const { return nb_y && y.n == 2; }
+};
 
+template <typename P, typename S>
+int fused_tables(rf_plan *plan, const FusedGeometry &g, FusedTables<S, typename PixelTraits<P>::Acc> &t) {
+    using Acc = typename PixelTraits<P>::Acc;
+    using Options = typename CarryStage<S, Acc>::Options;
+    int status = RF_OK;
+    const int K = g.K, nx = g.nx, ny = g.ny;
+    const DimInfo &dx = plan->dims[0];
+    const DimInfo no_y;
+    const DimInfo &dy = g.chained ? no_y : plan->dims[1];
+    auto up = [&](const auto &vec) {
+        using T = typename std::decay<decltype(vec)>::type::value_type;
+        return (const T *)plan->upload(vec.data(), vec.size() * sizeof(T), &status);
+    };
+    for (int id : dx.scan_ids) t.xs.push_back(make_fused_scan<S, Acc>(plan->scans[id], K, true));
+    for (int id : dy.scan_ids) t.ys.push_back(make_fused_scan<S, Acc>(plan->scans[id], K, false));
     // neighbour-form carries (neighbour_carry_bound): f32 images and batched Tuple planes, unsharded, not chained rows, not in
     // mod form (a 3-D plan's x/y stage keeps its scans); the bound is reported whatever RF_PLAN_FULL_CARRY_SCAN says
     // (f32 arithmetic: 16-bit float storage types take the same decision as the f32 plan of the same description)
-    const bool neighbour_plan = is_f32_arith<P>::value && plan->ndim == 2 && !plan->sharded() && !chained && !plan->mod_form;
+    const bool neighbour_plan = is_f32_arith<P>::value && plan->ndim == 2 && !plan->sharded() && !g.chained && !plan->mod_form;
     double nb_bound_x = -1.0, nb_bound_y = -1.0;
-    std::vector<FusedScan<Acc>> hxs = fused_scans(dx.scan_ids, true), hys = fused_scans(dy.scan_ids, false);
+    t.chain_S = (int)((g.NY + 63) / 64);
+    Options ox, oy;
+    ox.T_last = g.TVx;
+    ox.apply_powers = g.chained;                                     // (carry_apply runs for chained rows and row shards only)
+    oy.T_last = g.TVy;
+    oy.sharded = g.y_sharded;
+    oy.slab_powers = oy.apply_powers = g.y_sharded;                  // [j][slab][K x K], for the per-scan exchange
+    if (int rc = t.x.init(plan, dx.scan_ids, "x", K, kFusedTX, g.MX, LineGeom{g.NX, 1, g.Lx}, ox)) return rc;
+    if (int rc = t.y.init(plan, dy.scan_ids, "y", K, g.TY, g.MY, LineGeom{g.NY, g.NXP, g.Ly}, oy)) return rc;
+    std::vector<Acc> hHx, hHy, hG, hAMx, hAMSx;
     if (nx > 0) {
+        const DimTables<S> &tx = t.x.tab;
         // segment tables as the x phase reads them (float pixels: exact values of the kernel constants)
         std::vector<double> sr, sp;
-        for (const auto &f : hxs) {
+        for (const auto &f : t.xs) {
             for (int p = 0; p < kFusedSeg; p++)
                 for (int j = 0; j < K; j++) sr.push_back((double)f.R[j][f.causal ? p : kFusedSeg - 1 - p]);
             for (int step = 0; step < 4; step++)
@@ -258,31 +282,14 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         }
         plan->tables["seg_R_x"] = sr;
         plan->tables["seg_P_x"] = sp;
-    }
-    std::vector<DevScan<Acc>> hxd = dev_scans(dx.scan_ids), hyd = dev_scans(dy.scan_ids);
-    std::vector<Acc> hWx, hAx, hWy, hAy, hG, hAMy, hACx, hACy, hHx, hHy, hAMx, hAMSx, hApowX, hApowY;
-    const int chain_S = (int)((NY + 63) / 64);     // rows per lane of the row-chain kernel
-    const int Cx = carry_chunk_length(MX, Lx, K), Cy = carry_chunk_length(MY, Ly, K);
-    if (nx > 0) {
-        DimTables<S> tx = build_dim_tables<S>(table_scans(dx.scan_ids), K, kFusedTX, plan->clamped, TVx);
-        flatten_W(tx, nx, hWx, hAx, "x");
         if (neighbour_plan) nb_bound_x = neighbour_carry_bound<S>(tx, dx.scan_ids, plan);
-        if (chained) hApowX = carry_apply_powers<S, Acc>(tx.A, MX, K);
-        {
-            std::vector<S> H = build_tail_responses<S>(table_scans(dx.scan_ids), K, kFusedTX, plan->clamped, TVx);
-            std::vector<double> dH(H.size());
-            hHx.resize(H.size());
-            for (size_t e = 0; e < H.size(); e++) { hHx[e] = table_to_acc<S, Acc>(H[e]); dH[e] = table_to_double<S>(H[e]); }
-            plan->tables["H_x"] = dH;
-        }
-        hACx.assign((size_t)nx * K * K, Acc(0));
+        hHx = table_for_kernels<S, Acc>(plan, build_tail_responses<S>(tx.scans, K, kFusedTX, plan->clamped, g.TVx), "H_x");
         hAMx.assign((size_t)nx * K * K, Acc(0));
         hAMSx.assign((size_t)nx * K * K, Acc(0));
         for (int s = 0; s < nx; s++) {
-            std::vector<S> ac = mat_pow<S>(tx.A[s], Cx, K), am = mat_pow<S>(tx.A[s], MX, K);
-            std::vector<S> ams = mat_pow<S>(am, chain_S, K);
+            std::vector<S> am = mat_pow<S>(tx.A[s], g.MX, K);
+            std::vector<S> ams = mat_pow<S>(am, t.chain_S, K);
             for (int e = 0; e < K * K; e++) {
-                hACx[(size_t)s * K * K + e] = table_to_acc<S, Acc>(ac[e]);
                 hAMx[(size_t)s * K * K + e] = table_to_acc<S, Acc>(am[e]);
                 hAMSx[(size_t)s * K * K + e] = table_to_acc<S, Acc>(ams[e]);
             }
@@ -302,279 +309,288 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
             }
         plan->tables["G_x"] = dG;
     }
-    DimTables<S> ty;
     if (ny > 0) {
-        ty = build_dim_tables<S>(table_scans(dy.scan_ids), K, TY, plan->clamped, TVy);
-        flatten_W(ty, ny, hWy, hAy, "y");
-        if (neighbour_plan) nb_bound_y = neighbour_carry_bound<S>(ty, dy.scan_ids, plan);
-        if (y_sharded) hApowY = carry_apply_powers<S, Acc>(ty.A, MY, K);
-        {
-            std::vector<S> H = build_tail_responses<S>(table_scans(dy.scan_ids), K, TY, plan->clamped, TVy);
-            std::vector<double> dH(H.size());
-            hHy.resize(H.size());
-            for (size_t e = 0; e < H.size(); e++) { hHy[e] = table_to_acc<S, Acc>(H[e]); dH[e] = table_to_double<S>(H[e]); }
-            plan->tables["H_y"] = dH;
-        }
-        if (y_sharded) hAMy = slab_powers<S, Acc>(plan, ty.A, TY, K);          // [j][slab][K x K], for the per-scan exchange
-        hACy.assign((size_t)ny * K * K, Acc(0));
-        for (int j = 0; j < ny; j++) {
-            std::vector<S> ac = mat_pow<S>(ty.A[j], Cy, K);
-            for (int e = 0; e < K * K; e++) hACy[(size_t)j * K * K + e] = table_to_acc<S, Acc>(ac[e]);
-        }
+        if (neighbour_plan) nb_bound_y = neighbour_carry_bound<S>(t.y.tab, dy.scan_ids, plan);
+        hHy = table_for_kernels<S, Acc>(plan, build_tail_responses<S>(t.y.tab.scans, K, g.TY, plan->clamped, g.TVy), "H_y");
     }
+    t.G = up(hG); t.Hx = up(hHx); t.Hy = up(hHy); t.AMx = up(hAMx); t.AMSx = up(hAMSx);
 
     // Which dimensions take the neighbour form.  x: one scan needs nothing but the tails pass 1 left; a pair is completed by
     // xscan_rows (kernels_tails.hip, NB), which runs only with y scans in the filter.  y: one scan likewise; a pair needs the
     // final pass to add W * (the tile's own causal tail) to the anticausal carry it loads (FusedArgs::y_nb_W), which the
     // 128-row final pass does (kernels_fused_tall.hip).
     const bool full_scan = (plan->flags & RF_PLAN_FULL_CARRY_SCAN) != 0;
-    const bool nb_x = !full_scan && nb_bound_x >= 0.0 && nb_bound_x <= kNeighbourCarryBound && (nx == 1 || ny > 0);
-    const bool nb_y = !full_scan && nb_bound_y >= 0.0 && nb_bound_y <= kNeighbourCarryBound && (ny == 1 || TY == 128);
-    const bool nb_x_pair = nb_x && nx == 2, nb_y_pair = nb_y && ny == 2;
+    t.nb_x = !full_scan && nb_bound_x >= 0.0 && nb_bound_x <= kNeighbourCarryBound && (nx == 1 || ny > 0);
+    t.nb_y = !full_scan && nb_bound_y >= 0.0 && nb_bound_y <= kNeighbourCarryBound && (ny == 1 || g.TY == 128);
     // (every dropped transfer crosses a whole tile: neighbour_plan admits unsharded plans only, which hold both borders of both
     // dimensions, so the only partial tile is a last one and the causal carry leaving it is never consumed)
-    plan->tables["neighbour_carries"] = {nb_bound_x, nb_x ? 1.0 : 0.0, nb_bound_y, nb_y ? 1.0 : 0.0};
+    plan->tables["neighbour_carries"] = {nb_bound_x, t.nb_x ? 1.0 : 0.0, nb_bound_y, t.nb_y ? 1.0 : 0.0};
+    return status;
+}
 
-    // ---- device memory --------------------------------------------------------------------
-    auto up = [&](const auto &vec) {
-        using T = typename std::decay<decltype(vec)>::type::value_type;
-        return (const T *)plan->upload(vec.data(), vec.size() * sizeof(T), &status);
-    };
-    const DevScan<Acc> *d_xd = up(hxd);
-    const DevScan<Acc> *d_yd = up(hyd);
-    const Acc *d_Wx = up(hWx), *d_Ax = up(hAx), *d_Wy = up(hWy), *d_Ay = up(hAy), *d_G = up(hG), *d_AMy = up(hAMy);
-    const Acc *d_ACx = up(hACx), *d_ACy = up(hACy), *d_Hx = up(hHx), *d_Hy = up(hHy);
-    const Acc *d_AMx = up(hAMx), *d_AMSx = up(hAMSx);
-    const Acc *d_ApowX = up(hApowX), *d_ApowY = up(hApowY);      // only filled when carry_apply runs (chained rows, row shards)
+// ---- device memory -------------------------------------------------------------------------------------------------
+template <typename Acc>
+struct FusedBuffers {
+    Acc *xt = nullptr, *yt = nullptr;                // tile-local tails, completed in place by the carry stages
+    Acc *xt_done = nullptr;                          // the completed x tails where xscan_rows writes them (merged_cx, nb_x_pair)
+    Acc *xin = nullptr, *yin = nullptr;              // entering carries
+    Acc *row_exit = nullptr;                         // chained rows: the rows' exit states
+    size_t xt_pp = 0, yt_pp = 0, xin_pp = 0, yin_pp = 0;     // elements per plane
+    bool merged_cx = false;                          // xscan_rows completes the x tails itself (kernels_tails.hip, XC)
+};
 
-    const size_t xt_pp = (size_t)nx * MX * K * Lx, yt_pp = (size_t)ny * MY * K * Ly;
-    const size_t xin_pp = (size_t)nx * K * Lx, yin_pp = (size_t)ny * K * Ly;
-    const int np = batch ? 1 : plan->n_planes;         // batched planes are inside Lx / Ly already (NZ)
+template <typename S, typename Acc>
+int fused_buffers(rf_plan *plan, const FusedGeometry &g, FusedTables<S, Acc> &t, FusedBuffers<Acc> &b) {
+    int status = RF_OK;
+    const int K = g.K, np = g.np;
+    b.xt_pp = (size_t)g.nx * g.MX * K * g.Lx; b.yt_pp = (size_t)g.ny * g.MY * K * g.Ly;
+    b.xin_pp = (size_t)g.nx * K * g.Lx; b.yin_pp = (size_t)g.ny * K * g.Ly;
     // few tiles per row: xscan_rows completes the x tails itself, into a second array (kernels_tails.hip, XC)
     // (the neighbour form needs no recurrence at all: it takes such images too -- 2-4 µs per step ahead of XC on 1280^2 x 3 ...
     //  4096^2, orders 1-3, profiles/r7/xc_vs_nb.txt)
-    const bool merged_cx = !chained && !nb_x && xscan_completes_x_tails(K, TY, (int)MX, nx, ny, sizeof(Acc), (int64_t)MY * NZ);
-    Acc *xt = (Acc *)plan->alloc(xt_pp * np * sizeof(Acc), false, &status);
-    Acc *xt_done = (merged_cx || nb_x_pair) ? (Acc *)plan->alloc(xt_pp * np * sizeof(Acc), false, &status) : nullptr;
-    Acc *yt = (Acc *)plan->alloc(yt_pp * np * sizeof(Acc), false, &status);
-    Acc *xin = (Acc *)plan->alloc(xin_pp * np * sizeof(Acc), true, &status);
-    Acc *yin = (Acc *)plan->alloc(yin_pp * np * sizeof(Acc), true, &status);
+    b.merged_cx = !g.chained && !t.nb_x && xscan_completes_x_tails(K, g.TY, g.MX, g.nx, g.ny, sizeof(Acc), (int64_t)g.MY * g.NZ);
+    b.xt = (Acc *)plan->alloc(b.xt_pp * np * sizeof(Acc), false, &status);
+    b.xt_done = (b.merged_cx || t.nb_x_pair()) ? (Acc *)plan->alloc(b.xt_pp * np * sizeof(Acc), false, &status) : nullptr;
+    b.yt = (Acc *)plan->alloc(b.yt_pp * np * sizeof(Acc), false, &status);
+    b.xin = (Acc *)plan->alloc(b.xin_pp * np * sizeof(Acc), true, &status);
+    b.yin = (Acc *)plan->alloc(b.yin_pp * np * sizeof(Acc), true, &status);
     // (two of them: with the chain of scan s folded into the carry launch of scan s + 1 that launch reads one and writes the other)
-    Acc *row_exit = chained ? (Acc *)plan->alloc((size_t)2 * K * Lx * np * sizeof(Acc), true, &status) : nullptr;
-    if (status != RF_OK) return status;
+    b.row_exit = g.chained ? (Acc *)plan->alloc((size_t)2 * K * g.Lx * np * sizeof(Acc), true, &status) : nullptr;
+    t.x.use_buffers(b.xt, b.xt_pp, b.xin, b.xin_pp);
+    t.y.use_buffers(b.yt, b.yt_pp, b.yin, b.yin_pp);
+    return status;
+}
 
-    // ---- 3-D volumes: pass 1 in ONE read (kernels_tails_walk.hip) ------------------------------------
-    // The z tails are taken from the raw input by the pass that extracts the x/y tails (the z operators commute with the x/y
-    // filter: plan_strided.h); the z stage then has no first pass.  f32 volumes of whole tiles without a prologue (its bias is not
-    // linear) -- whole
-    // volumes, and z slabs that take the early exchange (the pass is then the slab's begin step) -- of at least one patch column (256 x 32 samples x one z tile: a workgroup of 1024 threads) per compute unit --
-    // measured, one read against two: 256^3 (32 patch columns) 0.214 against 0.124 ms, 512^3 (256) 0.645 against 0.680,
-    // 768^3 1.97 / 2.05, 1024^3 4.5 / 4.95, 2048^3 34.0 / 37.0 (profiles/r4/walk_tails_sizes.txt); RF_PLAN_WALK_PASS1: whatever
-    // the size; RF_PLAN_STAGED_PASS1 keeps the two first passes.
-    WalkArgs walk_args{};
-    std::shared_ptr<WalkHook> walk_hook;
-    std::unique_ptr<rf_plan> walk_child;             // F over the z carry planes (plan_strided.h), handed to the z stage below
+// ---- 3-D volumes: pass 1 in ONE read (kernels_tails_walk.hip) ------------------------------------
+// The z tails are taken from the raw input by the pass that extracts the x/y tails (the z operators commute with the x/y
+// filter: plan_strided.h); the z stage then has no first pass.  f32 volumes of whole tiles without a prologue (its bias is not
+// linear) -- whole
+// volumes, and z slabs that take the early exchange (the pass is then the slab's begin step) -- of at least one patch column (256 x 32 samples x one z tile: a workgroup of 1024 threads) per compute unit --
+// measured, one read against two: 256^3 (32 patch columns) 0.214 against 0.124 ms, 512^3 (256) 0.645 against 0.680,
+// 768^3 1.97 / 2.05, 1024^3 4.5 / 4.95, 2048^3 34.0 / 37.0 (profiles/r4/walk_tails_sizes.txt); RF_PLAN_WALK_PASS1: whatever
+// the size; RF_PLAN_STAGED_PASS1 keeps the two first passes.
+struct FusedWalk {
+    WalkArgs args{};
+    std::shared_ptr<WalkHook> hook;              // null: pass 1 does not walk
+    std::unique_ptr<rf_plan> child;              // F over the z carry planes (plan_strided.h), handed to the z stage
+};
+
+template <typename P, typename S>
+int plan_walk_pass1(rf_plan *plan, const rf_filter_desc *desc, const FusedGeometry &g,
+                    const FusedBuffers<typename PixelTraits<P>::Acc> &b, FusedWalk &w) {
+    using Acc = typename PixelTraits<P>::Acc;
+    int status = RF_OK;
     if constexpr (std::is_same<P, float>::value) {
+        const int K = g.K, TY = g.TY, nx = g.nx, ny = g.ny, np = g.np;
         static const char *walk_knob = RF_KNOB("RF_WALK");                        // A/B: 0 = never
         const bool wanted = !(plan->flags & RF_PLAN_STAGED_PASS1) && !(walk_knob && atoi(walk_knob) == 0);
         const bool z_slabs = plan->sharded();           // z slabs: with the early exchange (plan_strided.h), whose first step this pass then is
-        if (wanted && plan->ndim == 3 && (!z_slabs || early_exchange_possible<P>(plan, 2, desc)) && !batch && !chained && !plan->mod_form &&
-            !plan->pw.in_u8 && nx > 0 && ny > 0 && !plan->dims[2].scan_ids.empty() &&      // (a prologue x' = s x + b is applied as the samples arrive; an epilogue runs behind the z stage either way)
-            plan->dims[2].lines == NX * NY) {
-            const DimInfo &dz = plan->dims[2];
-            const int TZ = strided_tile(plan, 2), nz = (int)dz.scan_ids.size(), KZ = dz.k;
-            const int64_t patch_columns = TZ > 0 ? (int64_t)MX * ((NY + 31) / 32) * (dz.N / TZ) : 0;
-            // (widths that are not multiples of four: the pass takes them since round 6 -- 4-byte loads, kernels_tails_walk.hip U4 --
-            //  but loses to the two first passes there, 1024 x 1021 x 1021: walk 2.27 ms against 1.15 + 0.94, 1022 wide: 2.09 against
-            //  1.13 + 1.04 (profiles/r6/walk_odd_widths.txt); only RF_PLAN_WALK_PASS1 selects it for such volumes)
-            if (TZ > 0 && dz.N % TZ == 0 && walk_tails_applicable(K, TY, nx, ny, nz, KZ, TZ, TVx, TVy) &&
-                ((patch_columns >= 256 && NX % 4 == 0) || (plan->flags & RF_PLAN_WALK_PASS1))) {
-                const int MZ = (int)(dz.N / TZ);
-                walk_child.reset(build_carry_planes_plan(plan, desc, 2, (int64_t)nz * KZ * (MZ + (z_slabs ? 1 : 0))));
-                if (walk_child) {
-                    // impulse responses of the z tails, transposed: [variant][z][4]
-                    std::vector<S> H = build_tail_responses<S>(table_scans(dz.scan_ids), KZ, TZ, plan->clamped);
-                    std::vector<float> hHz((size_t)4 * TZ * 4, 0.0f);
-                    std::vector<double> dHz(H.size());
-                    for (size_t e = 0; e < H.size(); e++) dHz[e] = table_to_double<S>(H[e]);
-                    for (int v = 0; v < 4; v++)
-                        for (int j = 0; j < nz * KZ; j++)
-                            for (int z = 0; z < TZ; z++)
-                                hHz[((size_t)v * TZ + z) * 4 + j] = table_to_acc<S, Acc>(H[((size_t)v * nz * KZ + j) * TZ + z]);
-                    plan->tables["H_z"] = dHz;
-                    // tall patches (128 columns x 64 rows, round 6): 128-row y tiles, at most four x tails
-                    static const bool tall_off = RF_KNOB("RF_WALK_NO_TALL") != nullptr;       // A/B
-                    const bool tall = !tall_off && TY == 128 && K <= 2 && nx * K <= 4;
-                    const int parts = tall ? TY / 64 : TY / 32;
-                    walk_args.tall = tall ? 1 : 0;
-                    walk_args.xt2 = tall ? (float *)plan->alloc(xt_pp * np * sizeof(float), false, &status) : nullptr;      // (per Tuple plane)
-                    walk_args.HzT = (const float *)plan->upload(hHz.data(), hHz.size() * sizeof(float), &status);
-                    walk_args.TY = TY; walk_args.TZ = TZ; walk_args.MZ = MZ; walk_args.nzk = nz * KZ; walk_args.KZ = KZ;
-                    walk_args.parts_log2 = parts == 4 ? 2 : parts == 2 ? 1 : 0;
-                    walk_args.z_first_border = (!z_slabs || plan->shard_rank == 0) ? 1 : 0;
-                    walk_args.z_last_border = (!z_slabs || plan->shard_rank == plan->shard_world - 1) ? 1 : 0;
-                    walk_args.part_stride = (int64_t)yt_pp;
-                    walk_args.ytp = parts > 1 ? (float *)plan->alloc(yt_pp * parts * np * sizeof(float), false, &status) : nullptr;      // (per Tuple plane)
-                    walk_hook = std::make_shared<WalkHook>();
-                    if (status != RF_OK) return status;
-                }
-            }
-        }
+        if (!(wanted && plan->ndim == 3 && (!z_slabs || early_exchange_possible<P>(plan, 2, desc)) && !g.batch && !g.chained && !plan->mod_form &&
+              !plan->pw.in_u8 && nx > 0 && ny > 0 && !plan->dims[2].scan_ids.empty() &&      // (a prologue x' = s x + b is applied as the samples arrive; an epilogue runs behind the z stage either way)
+              plan->dims[2].lines == g.NX * g.NY))
+            return status;
+        const DimInfo &dz = plan->dims[2];
+        const int TZ = strided_tile(plan, 2), nz = (int)dz.scan_ids.size(), KZ = dz.k;
+        const int64_t patch_columns = TZ > 0 ? (int64_t)g.MX * ((g.NY + 31) / 32) * (dz.N / TZ) : 0;
+        // (widths that are not multiples of four: the pass takes them since round 6 -- 4-byte loads, kernels_tails_walk.hip U4 --
+        //  but loses to the two first passes there, 1024 x 1021 x 1021: walk 2.27 ms against 1.15 + 0.94, 1022 wide: 2.09 against
+        //  1.13 + 1.04 (profiles/r6/walk_odd_widths.txt); only RF_PLAN_WALK_PASS1 selects it for such volumes)
+        if (!(TZ > 0 && dz.N % TZ == 0 && walk_tails_applicable(K, TY, nx, ny, nz, KZ, TZ, g.TVx, g.TVy) &&
+              ((patch_columns >= 256 && g.NX % 4 == 0) || (plan->flags & RF_PLAN_WALK_PASS1))))
+            return status;
+        const int MZ = (int)(dz.N / TZ);
+        w.child.reset(build_carry_planes_plan(plan, desc, 2, (int64_t)nz * KZ * (MZ + (z_slabs ? 1 : 0))));
+        if (!w.child) return status;
+        // impulse responses of the z tails, transposed: [variant][z][4]
+        std::vector<ScanS<S>> zs;
+        for (int id : dz.scan_ids) zs.push_back(make_table_scan<S>(plan->scans[id]));
+        const std::vector<Acc> H = table_for_kernels<S, Acc>(plan, build_tail_responses<S>(zs, KZ, TZ, plan->clamped), "H_z");
+        std::vector<float> hHz((size_t)4 * TZ * 4, 0.0f);
+        for (int v = 0; v < 4; v++)
+            for (int j = 0; j < nz * KZ; j++)
+                for (int z = 0; z < TZ; z++)
+                    hHz[((size_t)v * TZ + z) * 4 + j] = H[((size_t)v * nz * KZ + j) * TZ + z];
+        // tall patches (128 columns x 64 rows, round 6): 128-row y tiles, at most four x tails
+        static const bool tall_off = RF_KNOB("RF_WALK_NO_TALL") != nullptr;       // A/B
+        const bool tall = !tall_off && TY == 128 && K <= 2 && nx * K <= 4;
+        const int parts = tall ? TY / 64 : TY / 32;
+        w.args.tall = tall ? 1 : 0;
+        w.args.xt2 = tall ? (float *)plan->alloc(b.xt_pp * np * sizeof(float), false, &status) : nullptr;      // (per Tuple plane)
+        w.args.HzT = (const float *)plan->upload(hHz.data(), hHz.size() * sizeof(float), &status);
+        w.args.TY = TY; w.args.TZ = TZ; w.args.MZ = MZ; w.args.nzk = nz * KZ; w.args.KZ = KZ;
+        w.args.parts_log2 = parts == 4 ? 2 : parts == 2 ? 1 : 0;
+        w.args.z_first_border = (!z_slabs || plan->shard_rank == 0) ? 1 : 0;
+        w.args.z_last_border = (!z_slabs || plan->shard_rank == plan->shard_world - 1) ? 1 : 0;
+        w.args.part_stride = (int64_t)b.yt_pp;
+        w.args.ytp = parts > 1 ? (float *)plan->alloc(b.yt_pp * parts * np * sizeof(float), false, &status) : nullptr;      // (per Tuple plane)
+        w.hook = std::make_shared<WalkHook>();
     }
-    const bool walk = (bool)walk_hook;
+    return status;
+}
 
-    FusedArgs<Acc> fbase{};
-    fbase.NX = NX; fbase.NY = NY; fbase.NZ = NZ; fbase.MX = MX; fbase.MY = MY; fbase.nx = nx; fbase.ny = ny;
-    fbase.NXP = NXP; fbase.last_lane = (TVx - 1) / kFusedSeg; fbase.last_cols = TVx;
-    fbase.NYP = NYP; fbase.last_rows = TVy;
-    fbase.row_bytes = (uint32_t)(NX * (int64_t)sizeof(P));
-    fbase.clamped = plan->clamped ? 1 : 0;
-    fbase.mod_form = plan->mod_form ? 1 : 0;
-    fbase.y_first_border = (!y_sharded || plan->shard_rank == 0) ? 1 : 0;
-    fbase.y_last_border = (!y_sharded || plan->shard_rank == plan->shard_world - 1) ? 1 : 0;
-    if constexpr (!PixelTraits<P>::is_integer) {
-        const bool z_follows = plan->ndim > 2 && !plan->dims[2].scan_ids.empty();
-        plan->pw.pre_fused = plan->pw.pre;
-        plan->pw.post_fused = plan->pw.post && !z_follows;     // with a z stage the epilogue runs after it
-        fbase.pw_flags = (plan->pw.pre_fused ? 1 : 0) | (plan->pw.post_fused ? 2 : 0);
-        fbase.pre_s = (Acc)plan->pw.pre_s; fbase.pre_b = (Acc)plan->pw.pre_b;
-        fbase.post_f = (Acc)plan->pw.post_f; fbase.post_i = (Acc)plan->pw.post_i; fbase.post_b = (Acc)plan->pw.post_b;
-    }
-    // The y tails of an unsharded plan are tile-major, [tile row][tile column][scan][r][256]: the rows pass 1 stores for
-    // one tile, and the ones pass 2 loads, are then one run of ny * K * 1 KiB instead of ny * K runs a whole image width
-    // apart (FusedArgs::yt_index).  Slabs keep [scan][tile row][r][line], which the exchange kernels address, and so do
-    // order-3 filters: measured on 16384^2, order 2 gains 0.005 ms of 0.62 ms and order 3 loses 0.01-0.03 ms of 1.98 ms
-    // (its carry scan reads six rows per tile and line), order 1 is unchanged either way.
-    static const bool yt_row_major = RF_KNOB("RF_YT_ROW_MAJOR") != nullptr;      // A/B runs
-    static const bool yt_force_tile = RF_KNOB("RF_YT_TILE_MAJOR") != nullptr;    // A/B runs: order 3 too
-    // (the one-read pass 1 of a volume stores a tile's combined rows as one run: tile-major for order 3 as well)
-    const bool yt_tile_major = !yt_row_major && !y_sharded && ny > 0 && (K <= 2 || yt_force_tile || walk) && Ly % kFusedTX == 0 &&
-                               Ly == NXP * (int64_t)NZ;
-    fbase.yt_tile_major = yt_tile_major ? 1 : 0;
-    fbase.lin_limit = in_place_tail ? dx.N : 0;
-    if constexpr (std::is_same<P, float>::value) {
-        // (pass 1 left the combined rows in parts: xscan_rows adds them up)
-        if (walk && walk_args.ytp) { fbase.yt_parts = walk_args.tall ? TY / 64 : TY / 32; fbase.yt_part_stride = walk_args.part_stride; fbase.ytp = walk_args.ytp; }
-    }
-    std::memset(fbase.xs, 0, sizeof(fbase.xs));
-    std::memset(fbase.ys, 0, sizeof(fbase.ys));
-    for (int s = 0; s < nx; s++) fbase.xs[s] = hxs[s];
-    for (int j = 0; j < ny; j++) {
-        fbase.ys[j].causal = hys[j].causal;
-        fbase.ys[j].b = hys[j].b;
-        for (int e = 0; e < kFusedMaxK; e++) fbase.ys[j].a[e] = hys[j].a[e];
-        fbase.ys[j].mod_n = hys[j].mod_n;
-        for (int e = 0; e < kFusedMaxMod; e++) fbase.ys[j].mod_g[e] = hys[j].mod_g[e];
-    }
-    auto fargs = [=](int pl) {
-        FusedArgs<Acc> a = fbase;
-        a.xt = xt + (size_t)pl * xt_pp;
-        a.yt = yt + (size_t)pl * yt_pp;
-        if (a.ytp != nullptr) a.ytp = a.ytp + (size_t)pl * yt_pp * (size_t)a.yt_parts;       // (the parts of the one-read pass 1)
-        a.y_incoming = yin + (size_t)pl * yin_pp;
-        a.x_incoming = xin + (size_t)pl * xin_pp;
+// ---- steps ---------------------------------------------------------------------------------------------------------
+// The FusedArgs of a plane.  Steps keep a copy (they outlive the builder).
+template <typename Acc>
+struct FusedPlaneArgs {
+    FusedArgs<Acc> base{};
+    FusedBuffers<Acc> b;
+    bool batch = false;
+    FusedArgs<Acc> operator()(const rf_plan *plan, int pl) const {
+        FusedArgs<Acc> a = base;
+        a.xt = b.xt + (size_t)pl * b.xt_pp;
+        a.yt = b.yt + (size_t)pl * b.yt_pp;
+        if (a.ytp != nullptr) a.ytp = a.ytp + (size_t)pl * b.yt_pp * (size_t)a.yt_parts;       // (the parts of the one-read pass 1)
+        a.y_incoming = b.yin + (size_t)pl * b.yin_pp;
+        a.x_incoming = b.xin + (size_t)pl * b.xin_pp;
         a.plane_batch = batch ? 1 : 0;
         if (batch)
             for (int i = 0; i < plan->n_planes; i++) { a.in_planes[i] = plan->in[i]; a.out_planes[i] = plan->xy_result(i); }
         return a;
-    };
-    GenericDimArgs<Acc> gx{};
-    gx.g = LineGeom{NX, 1, Lx};
-    gx.T = kFusedTX; gx.M = MX; gx.k = K; gx.n_scans = nx; gx.clamped = fbase.clamped;
-    gx.first_is_border = 1; gx.last_is_border = 1;
-    gx.scans = d_xd; gx.W = d_Wx; gx.A = d_Ax; gx.Apow = hApowX.empty() ? nullptr : d_ApowX;
-    auto gxargs = [=](int pl) {
-        GenericDimArgs<Acc> a = gx;
-        a.tails = xt + (size_t)pl * xt_pp;
-        a.incoming = xin + (size_t)pl * xin_pp;
-        if constexpr (std::is_same<P, float>::value) {
-            if (walk_args.xt2) a.tails_part2 = walk_args.xt2 + (size_t)pl * xt_pp;       // (tall patches: the x tails in two parts)
-        }
-        return a;
-    };
-    GenericDimArgs<Acc> gy{};
-    gy.g = LineGeom{NY, NXP, Ly};
-    gy.T = TY; gy.M = MY; gy.k = K; gy.n_scans = ny; gy.clamped = fbase.clamped;
-    gy.first_is_border = fbase.y_first_border; gy.last_is_border = fbase.y_last_border;
-    gy.scans = d_yd; gy.W = d_Wy; gy.A = d_Ay; gy.Apow = hApowY.empty() ? nullptr : d_ApowY;
-    gy.tile_major = fbase.yt_tile_major;
-    auto gyargs = [=](int pl) {
-        GenericDimArgs<Acc> a = gy;
-        a.tails = yt + (size_t)pl * yt_pp;
-        a.incoming = yin + (size_t)pl * yin_pp;
-        return a;
-    };
+    }
+};
 
-    uint32_t xmask = 0, ymask = 0;
-    for (int s = 0; s < nx; s++) if (hxs[s].causal) xmask |= 1u << s;
-    for (int j = 0; j < ny; j++) if (hys[j].causal) ymask |= 1u << j;
+// What pass 1 needs to choose its kernel
+template <typename Acc>
+struct Pass1Args {
+    int K = 0, TY = 0;
+    const Acc *Hx = nullptr, *Hy = nullptr;
+    bool padded = false;
+    int stream_mode = 0, mfma_mode = 0;
+    WalkArgs walk{};
+    std::shared_ptr<WalkHook> walk_hook;
+    size_t xt_pp = 0;
+};
 
-    // ---- steps -----------------------------------------------------------------------------
-    // pass 1: tail extraction by contraction with the impulse responses (kernels_tails.hip)
-    Step p1;
-    p1.name = "fused_tails";
-    const int stream_mode = (plan->flags & RF_PLAN_STREAM_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
-    const int mfma_mode = (plan->flags & RF_PLAN_MFMA_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
-    if (walk) p1.name = "walk_tails";
-    p1.run = [plan, fargs, K, TY, d_Hx, d_Hy, padded, stream_mode, mfma_mode, walk_args, walk_hook, xt_pp](int pl) {
-        (void)xt_pp;
-        const FusedArgs<Acc> a = fargs(pl);
-        (void)stream_mode;
-        (void)mfma_mode;
-        (void)walk_args;
-        if constexpr (std::is_same<P, float>::value) {
-            if (walk_hook) {
-                WalkArgs wa = walk_args;
-                wa.zt = walk_hook->zt + (size_t)pl * walk_hook->zt_stride;
-                if (wa.xt2) wa.xt2 += (size_t)pl * xt_pp;
-                if (wa.ytp) wa.ytp = const_cast<float *>(a.ytp);       // this plane's parts (fargs)
-                else wa.ytp = a.yt;                         // one patch per y tile: the combined rows go where they belong
-                return launch_walk_tails(K, (const float *)plan->in[pl], a, wa, d_Hx, d_Hy, plan->stream);
-            }
+// pass 1: tail extraction by contraction with the impulse responses (kernels_tails.hip)
+template <typename P>
+int launch_pass1(const rf_plan *plan, int pl, const FusedArgs<typename PixelTraits<P>::Acc> &a,
+                 const Pass1Args<typename PixelTraits<P>::Acc> &p) {
+    const int K = p.K, TY = p.TY;
+    const void *in = p.padded ? plan->pad_in[pl] : plan->in[pl];
+    if constexpr (std::is_same<P, float>::value) {
+        if (p.walk_hook) {
+            WalkArgs wa = p.walk;
+            wa.zt = p.walk_hook->zt + (size_t)pl * p.walk_hook->zt_stride;
+            if (wa.xt2) wa.xt2 += (size_t)pl * p.xt_pp;
+            if (wa.ytp) wa.ytp = const_cast<float *>(a.ytp);       // this plane's parts (FusedPlaneArgs)
+            else wa.ytp = a.yt;                         // one patch per y tile: the combined rows go where they belong
+            return launch_walk_tails(K, (const float *)plan->in[pl], a, wa, p.Hx, p.Hy, plan->stream);
         }
         // images of whole 256 x 64 tiles stream through the LDS-DMA ring (kernels_stream.hip)
+        if (a.lin_limit == 0 && stream_tails_applicable(K, TY, plan->pw.in_u8, a.pw_flags, a.last_cols, a.last_rows, (int64_t)a.MX * a.MY * a.NZ, a.MX,
+                                        a.NZ, a.nx * K, a.ny * K, p.stream_mode))
+            return launch_stream_tails(K, (const float *)in, a, p.Hx, p.Hy, plan->stream);
+        // ... other f32 images of whole tiles contract their x tails on the matrix cores (kernels_tails_mfma.hip)
+        if (mfma_tails_applicable(K, TY, plan->pw.in_u8, a.pw_flags, a.last_cols, a.last_rows, a.lin_limit, a.nx, a.ny, p.mfma_mode))
+            return launch_mfma_tails<float>(K, TY, (const float *)in, a, p.Hx, p.Hy, plan->stream);
+    }
+    // ... and so do images stored as 16-bit floats (the kernel widens the samples on their way into its f32 tile)
+    if constexpr (is_half_pixel<P>::value) {
+        if (mfma_tails_applicable(K, TY, false, a.pw_flags, a.last_cols, a.last_rows, a.lin_limit, a.nx, a.ny, p.mfma_mode, true))
+            return launch_mfma_tails<P>(K, TY, (const P *)in, a, p.Hx, p.Hy, plan->stream);
+    }
+    return launch_fused_tails<P>(K, TY, in, plan->pw.in_u8, a, p.Hx, p.Hy, plan->stream);
+}
+
+// The step adders of one fused plan.  Every step captures COPIES of what it needs (plain structs of pointers and integers),
+// never the builder: the steps run long after build_fused has returned.
+template <typename P, typename S>
+struct FusedBuilder {
+    using Acc = typename PixelTraits<P>::Acc;
+    rf_plan *plan = nullptr;
+    const rf_filter_desc *desc = nullptr;
+    FusedGeometry g;
+    FusedTables<S, Acc> t;
+    FusedBuffers<Acc> b;
+    FusedWalk walk;
+    FusedPlaneArgs<Acc> fargs;
+    const Acc *d_Yapply = nullptr;       // row shards: the merged exchange's correction, applied by pass 2 (FusedArgs::y_apply)
+
+    void set_plane_args() {
+        const int K = g.K, nx = g.nx, ny = g.ny, TY = g.TY;
+        const bool walks = (bool)walk.hook;
+        FusedArgs<Acc> &fbase = fargs.base;
+        fbase.NX = g.NX; fbase.NY = g.NY; fbase.NZ = g.NZ; fbase.MX = g.MX; fbase.MY = g.MY; fbase.nx = nx; fbase.ny = ny;
+        fbase.NXP = g.NXP; fbase.last_lane = (g.TVx - 1) / kFusedSeg; fbase.last_cols = g.TVx;
+        fbase.NYP = g.NYP; fbase.last_rows = g.TVy;
+        fbase.row_bytes = (uint32_t)(g.NX * (int64_t)sizeof(P));
+        fbase.clamped = plan->clamped ? 1 : 0;
+        fbase.mod_form = plan->mod_form ? 1 : 0;
+        fbase.y_first_border = (!g.y_sharded || plan->shard_rank == 0) ? 1 : 0;
+        fbase.y_last_border = (!g.y_sharded || plan->shard_rank == plan->shard_world - 1) ? 1 : 0;
+        if constexpr (!PixelTraits<P>::is_integer) {
+            const bool z_follows = plan->ndim > 2 && !plan->dims[2].scan_ids.empty();
+            plan->pw.pre_fused = plan->pw.pre;
+            plan->pw.post_fused = plan->pw.post && !z_follows;     // with a z stage the epilogue runs after it
+            fbase.pw_flags = (plan->pw.pre_fused ? 1 : 0) | (plan->pw.post_fused ? 2 : 0);
+            fbase.pre_s = (Acc)plan->pw.pre_s; fbase.pre_b = (Acc)plan->pw.pre_b;
+            fbase.post_f = (Acc)plan->pw.post_f; fbase.post_i = (Acc)plan->pw.post_i; fbase.post_b = (Acc)plan->pw.post_b;
+        }
+        // The y tails of an unsharded plan are tile-major, [tile row][tile column][scan][r][256]: the rows pass 1 stores for
+        // one tile, and the ones pass 2 loads, are then one run of ny * K * 1 KiB instead of ny * K runs a whole image width
+        // apart (FusedArgs::yt_index).  Slabs keep [scan][tile row][r][line], which the exchange kernels address, and so do
+        // order-3 filters: measured on 16384^2, order 2 gains 0.005 ms of 0.62 ms and order 3 loses 0.01-0.03 ms of 1.98 ms
+        // (its carry scan reads six rows per tile and line), order 1 is unchanged either way.
+        static const bool yt_row_major = RF_KNOB("RF_YT_ROW_MAJOR") != nullptr;      // A/B runs
+        static const bool yt_force_tile = RF_KNOB("RF_YT_TILE_MAJOR") != nullptr;    // A/B runs: order 3 too
+        // (the one-read pass 1 of a volume stores a tile's combined rows as one run: tile-major for order 3 as well)
+        const bool yt_tile_major = !yt_row_major && !g.y_sharded && ny > 0 && (K <= 2 || yt_force_tile || walks) && g.Ly % kFusedTX == 0 &&
+                                   g.Ly == g.NXP * (int64_t)g.NZ;
+        fbase.yt_tile_major = yt_tile_major ? 1 : 0;
+        fbase.lin_limit = g.in_place_tail ? plan->dims[0].N : 0;
         if constexpr (std::is_same<P, float>::value) {
-            if (a.lin_limit == 0 && stream_tails_applicable(K, TY, plan->pw.in_u8, a.pw_flags, a.last_cols, a.last_rows, (int64_t)a.MX * a.MY * a.NZ, a.MX,
-                                        a.NZ, a.nx * K, a.ny * K, stream_mode))
-                return launch_stream_tails(K, (const float *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
-            // ... other f32 images of whole tiles contract their x tails on the matrix cores (kernels_tails_mfma.hip)
-            if (mfma_tails_applicable(K, TY, plan->pw.in_u8, a.pw_flags, a.last_cols, a.last_rows, a.lin_limit, a.nx, a.ny, mfma_mode))
-                return launch_mfma_tails<float>(K, TY, (const float *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
+            // (pass 1 left the combined rows in parts: xscan_rows adds them up)
+            if (walks && walk.args.ytp) { fbase.yt_parts = walk.args.tall ? TY / 64 : TY / 32; fbase.yt_part_stride = walk.args.part_stride; fbase.ytp = walk.args.ytp; }
+            if (walk.args.xt2) t.x.dev.tails_part2 = walk.args.xt2;       // (tall patches: the x tails in two parts)
         }
-        // ... and so do images stored as 16-bit floats (the kernel widens the samples on their way into its f32 tile)
-        if constexpr (is_half_pixel<P>::value) {
-            if (mfma_tails_applicable(K, TY, false, a.pw_flags, a.last_cols, a.last_rows, a.lin_limit, a.nx, a.ny, mfma_mode, true))
-                return launch_mfma_tails<P>(K, TY, (const P *)(padded ? plan->pad_in[pl] : plan->in[pl]), a, d_Hx, d_Hy, plan->stream);
+        std::memset(fbase.xs, 0, sizeof(fbase.xs));
+        std::memset(fbase.ys, 0, sizeof(fbase.ys));
+        for (int s = 0; s < nx; s++) fbase.xs[s] = t.xs[s];
+        for (int j = 0; j < ny; j++) {
+            fbase.ys[j].causal = t.ys[j].causal;
+            fbase.ys[j].b = t.ys[j].b;
+            for (int e = 0; e < kFusedMaxK; e++) fbase.ys[j].a[e] = t.ys[j].a[e];
+            fbase.ys[j].mod_n = t.ys[j].mod_n;
+            for (int e = 0; e < kFusedMaxMod; e++) fbase.ys[j].mod_g[e] = t.ys[j].mod_g[e];
         }
-        return launch_fused_tails<P>(K, TY, padded ? plan->pad_in[pl] : plan->in[pl], plan->pw.in_u8, a, d_Hx, d_Hy, plan->stream);
-    };
-    if (padded) {
-        // the zero-padded copies the kernels run on (the padding of the input copy is written once, here, and never again)
-        plan->padded_len = N1;
-        const size_t user_bytes = (size_t)dx.N * sizeof(P);
-        for (int pl = 0; pl < plan->n_planes; pl++) {
-            plan->pad_in[pl] = plan->alloc((size_t)N1 * sizeof(P), true, &status);
-            plan->pad_out[pl] = plan->alloc((size_t)N1 * sizeof(P), false, &status);
-        }
-        if (status != RF_OK) return status;
-        Step ci;
-        ci.name = "pad_copy_in";
-        ci.run = [plan, user_bytes](int pl) -> int {
-            RF_HIP_CHECK(hipMemcpyAsync(plan->pad_in[pl], plan->in[pl], user_bytes, hipMemcpyDeviceToDevice, plan->stream));
-            return (int)RF_OK;
-        };
-        plan->begin_steps.push_back(ci);
+        fargs.b = b;
+        fargs.batch = g.batch;
+        t.y.dev.base.tile_major = fbase.yt_tile_major;
     }
-    plan->begin_steps.push_back(p1);
-    if (nx > 0 && !chained && !merged_cx && !nb_x) {
-        Step cx;
-        cx.name = "carry_x";
-        cx.run = [plan, gxargs, K, nx, d_ACx, Cx, xmask](int pl) {
-            return launch_carry_block<Acc>(K, gxargs(pl), xmask, 0, nx, (Acc *)nullptr, d_ACx, Cx, plan->stream);
-        };
-        plan->begin_steps.push_back(cx);
+
+    int add_pass1() {
+        int status = RF_OK;
+        rf_plan *const plan = this->plan;
+        Pass1Args<Acc> p1a;
+        p1a.K = g.K; p1a.TY = g.TY; p1a.Hx = t.Hx; p1a.Hy = t.Hy; p1a.padded = g.padded;
+        p1a.stream_mode = (plan->flags & RF_PLAN_STREAM_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
+        p1a.mfma_mode = (plan->flags & RF_PLAN_MFMA_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
+        p1a.walk = walk.args; p1a.walk_hook = walk.hook; p1a.xt_pp = b.xt_pp;
+        Step p1;
+        p1.name = walk.hook ? "walk_tails" : "fused_tails";
+        p1.run = [plan, fargs = this->fargs, p1a](int pl) { return launch_pass1<P>(plan, pl, fargs(plan, pl), p1a); };
+        if (g.padded) {
+            // the zero-padded copies the kernels run on (the padding of the input copy is written once, here, and never again)
+            plan->padded_len = g.N1;
+            const size_t user_bytes = (size_t)plan->dims[0].N * sizeof(P);
+            for (int pl = 0; pl < plan->n_planes; pl++) {
+                plan->pad_in[pl] = plan->alloc((size_t)g.N1 * sizeof(P), true, &status);
+                plan->pad_out[pl] = plan->alloc((size_t)g.N1 * sizeof(P), false, &status);
+            }
+            if (status != RF_OK) return status;
+            Step ci;
+            ci.name = "pad_copy_in";
+            ci.run = [plan, user_bytes](int pl) -> int {
+                RF_HIP_CHECK(hipMemcpyAsync(plan->pad_in[pl], plan->in[pl], user_bytes, hipMemcpyDeviceToDevice, plan->stream));
+                return (int)RF_OK;
+            };
+            plan->begin_steps.push_back(ci);
+        }
+        plan->begin_steps.push_back(p1);
+        return status;
     }
-    if (chained) {
+
+    void add_chained_row_carries() {
         // Chained rows: per scan, (1) the blocked carry scan of every row with a zero entering state, publishing the
         // rows' exit states, (2) the chain over the rows -> state entering every row, (3) that state propagated through
         // the row's tails.  The same three steps as a sharded dimension (exchange_local / gather / exchange_apply),
@@ -583,38 +599,44 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         // are done by the carry launch of scan s + 1 before its own scan (carry_block_kernel PRE), the last scan's by
         // chain_apply_kernel -- n + 1 launches for n scans.
         static const bool no_pre = RF_KNOB("RF_NO_CHAIN_PRE") != nullptr;        // A/B runs: chain_apply after every scan
-        const bool one_launch_chain = chain_apply_applies(K, Lx, sizeof(Acc)) && !hApowX.empty();
+        rf_plan *const plan = this->plan;
+        const CarryDev<Acc> cx = t.x.dev;               // (built with Options::apply_powers: chain_apply / carry_apply have their A^i)
+        const int K = g.K, nx = g.nx, MX = g.MX, chain_S = t.chain_S;
+        const int64_t Lx = g.Lx;
+        Acc *const row_exit = b.row_exit, *const xin = b.xin;
+        const size_t xin_pp = b.xin_pp;
+        const bool one_launch_chain = chain_apply_applies(K, Lx, sizeof(Acc));
         const size_t exit_pp = (size_t)K * Lx;            // one buffer of exit states (two per plane, by scan parity)
         for (int s = 0; s < nx; s++) {
-            const bool causal = hxs[s].causal != 0;
+            const bool causal = t.xs[s].causal != 0;
             const bool fold_prev = one_launch_chain && !no_pre && s > 0;
             Step cs;
             cs.name = "carry_x" + std::to_string(s);
             ChainPre<Acc> pre{};
             if (fold_prev) {
-                pre.AM = d_AMx + (size_t)(s - 1) * K * K; pre.AMS = d_AMSx + (size_t)(s - 1) * K * K;
-                pre.Apow = d_ApowX + (size_t)(s - 1) * MX * K * K;
-                pre.S = chain_S; pre.causal_prev = hxs[s - 1].causal != 0 ? 1 : 0;
+                pre.AM = t.AMx + (size_t)(s - 1) * K * K; pre.AMS = t.AMSx + (size_t)(s - 1) * K * K;
+                pre.Apow = cx.base.Apow + (size_t)(s - 1) * MX * K * K;
+                pre.S = chain_S; pre.causal_prev = t.xs[s - 1].causal != 0 ? 1 : 0;
             }
-            cs.run = [plan, gxargs, K, s, d_ACx, Cx, xmask, row_exit, exit_pp, xin, xin_pp, Lx, pre, fold_prev](int pl) {
+            cs.run = [plan, cx, K, s, row_exit, exit_pp, xin, xin_pp, Lx, pre, fold_prev](int pl) {
                 Acc *mine = row_exit + ((size_t)pl * 2 + (s & 1)) * exit_pp;
                 if (!fold_prev)
-                    return launch_carry_block<Acc>(K, gxargs(pl), xmask, s, s + 1, mine, d_ACx, Cx, plan->stream);
+                    return launch_carry_block<Acc>(K, cx.args(pl), cx.causal_mask, s, s + 1, mine, cx.AC, cx.C, plan->stream);
                 ChainPre<Acc> p = pre;
                 p.exit_states = row_exit + ((size_t)pl * 2 + ((s - 1) & 1)) * exit_pp;
                 p.incoming_prev = xin + (size_t)pl * xin_pp + (size_t)(s - 1) * K * Lx;
-                return launch_carry_block<Acc>(K, gxargs(pl), xmask, s, s + 1, mine, d_ACx, Cx, plan->stream, &p);
+                return launch_carry_block<Acc>(K, cx.args(pl), cx.causal_mask, s, s + 1, mine, cx.AC, cx.C, plan->stream, &p);
             };
             plan->begin_steps.push_back(cs);
+            const Acc *AMs = t.AMx + (size_t)s * K * K, *AMSs = t.AMSx + (size_t)s * K * K;
             if (one_launch_chain) {
                 if (!no_pre && s + 1 < nx) continue;          // the next scan's carry launch finishes this one
                 // the chain over the rows and the propagation through their tails in one launch (kernels_carry.hip)
                 Step ca;
                 ca.name = "chain_apply" + std::to_string(s);
-                const Acc *AMs = d_AMx + (size_t)s * K * K, *AMSs = d_AMSx + (size_t)s * K * K;
-                ca.run = [plan, gxargs, K, s, causal, row_exit, exit_pp, xin, xin_pp, Lx, AMs, AMSs, chain_S](int pl) {
+                ca.run = [plan, cx, K, s, causal, row_exit, exit_pp, xin, xin_pp, Lx, AMs, AMSs, chain_S](int pl) {
                     Acc *inc = xin + (size_t)pl * xin_pp + (size_t)s * K * Lx;
-                    return launch_chain_apply<Acc>(K, gxargs(pl), s, row_exit + ((size_t)pl * 2 + (s & 1)) * exit_pp, inc, causal, AMs,
+                    return launch_chain_apply<Acc>(K, cx.args(pl), s, row_exit + ((size_t)pl * 2 + (s & 1)) * exit_pp, inc, causal, AMs,
                                                    AMSs, chain_S, plan->stream);
                 };
                 plan->begin_steps.push_back(ca);
@@ -622,7 +644,6 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
             }
             Step rc;
             rc.name = "row_chain" + std::to_string(s);
-            const Acc *AMs = d_AMx + (size_t)s * K * K, *AMSs = d_AMSx + (size_t)s * K * K;
             rc.run = [plan, K, s, causal, row_exit, exit_pp, xin, xin_pp, Lx, AMs, AMSs, chain_S](int pl) {
                 Acc *inc = xin + (size_t)pl * xin_pp + (size_t)s * K * Lx;
                 return launch_row_chain<Acc>(K, row_exit + ((size_t)pl * 2 + (s & 1)) * exit_pp, inc, (int)Lx, causal, AMs, AMSs, chain_S,
@@ -631,105 +652,84 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
             plan->begin_steps.push_back(rc);
             Step ap;
             ap.name = "carry_x_apply" + std::to_string(s);
-            ap.run = [plan, gxargs, s](int pl) { return launch_generic_carry_apply<Acc>(gxargs(pl), s, plan->stream); };
+            ap.run = [plan, cx, s](int pl) { return launch_generic_carry_apply<Acc>(cx.args(pl), s, plan->stream); };
             plan->begin_steps.push_back(ap);
         }
     }
-    if (nx > 0 && ny > 0) {
+
+    void add_xscan_rows() {
         // finishes the y tails: tile-local x scans of the combined rows + the cross-dimension residual of the
         // completed x carries (lib/split.cpp:1215-1633)
+        rf_plan *const plan = this->plan;
+        const int K = g.K, TY = g.TY;
+        const bool merged_cx = b.merged_cx, nb_x_pair = t.nb_x_pair();
+        const Acc *d_Hy = t.Hy, *d_G = t.G, *d_Wx = t.x.dev.base.W, *d_Ax = t.x.dev.base.A;
+        Acc *const xt_done = b.xt_done;
+        const size_t xt_pp = b.xt_pp;
         Step xs;
         xs.name = "xscan_rows";
-        xs.run = [plan, fargs, K, TY, d_Hy, d_G, merged_cx, nb_x_pair, d_Wx, d_Ax, xt_done, xt_pp](int pl) {
+        xs.run = [plan, fargs = this->fargs, K, TY, d_Hy, d_G, merged_cx, nb_x_pair, d_Wx, d_Ax, xt_done, xt_pp](int pl) {
             if (merged_cx)
-                return launch_xscan_rows<Acc>(K, TY, fargs(pl), d_Hy, d_G, plan->stream, d_Wx, d_Ax, xt_done + (size_t)pl * xt_pp);
+                return launch_xscan_rows<Acc>(K, TY, fargs(plan, pl), d_Hy, d_G, plan->stream, d_Wx, d_Ax, xt_done + (size_t)pl * xt_pp);
             if (nb_x_pair)      // neighbour form: the x tails completed from the neighbours' (NB)
-                return launch_xscan_rows<Acc>(K, TY, fargs(pl), d_Hy, d_G, plan->stream, d_Wx, nullptr, xt_done + (size_t)pl * xt_pp, true);
-            return launch_xscan_rows<Acc>(K, TY, fargs(pl), d_Hy, d_G, plan->stream);
+                return launch_xscan_rows<Acc>(K, TY, fargs(plan, pl), d_Hy, d_G, plan->stream, d_Wx, nullptr, xt_done + (size_t)pl * xt_pp, true);
+            return launch_xscan_rows<Acc>(K, TY, fargs(plan, pl), d_Hy, d_G, plan->stream);
         };
         plan->begin_steps.push_back(xs);
     }
-    const Acc *d_Yapply = nullptr;
-    if (!y_sharded) {   // one launch for every y scan; per-scan launches only around the exchanges
-        if (ny > 0 && !nb_y) {
-            Step cy;
-            cy.name = "carry_y";
-            cy.run = [plan, gyargs, K, ny, d_ACy, Cy, ymask](int pl) {
-                return launch_carry_block<Acc>(K, gyargs(pl), ymask, 0, ny, (Acc *)nullptr, d_ACy, Cy, plan->stream);
-            };
-            plan->begin_steps.push_back(cy);
+
+    int add_y_carries() {
+        if (!g.y_sharded) {   // one launch for every y scan; per-scan launches only around the exchanges
+            if (g.ny > 0 && !t.nb_y) t.y.add_local_carry(plan, "carry_y");
+            return RF_OK;
         }
-    } else if (merged_exchange_applies(ny, K, plan->shard_world)) {
-        // one all-gather for all y scans (plan_generic.h, "merged exchange")
-        // ... whose correction of the tails is left to pass 2 (FusedArgs::y_apply): no launch between gather and pass 2
-        static const bool separate_apply = RF_KNOB("RF_SHARD_SEPARATE_APPLY") != nullptr;     // A/B runs
-        int rc = add_merged_exchange<S, Acc>(plan, ty, "y", MY, TY, Ly, ymask, gyargs, yin, yin_pp, d_ACy, Cy, "carry_y",
-                                             separate_apply ? nullptr : &d_Yapply);
-        if (rc != RF_OK) return rc;
-    } else {
-        for (int j = 0; j < ny; j++) {
-            const int64_t plane_stride = (int64_t)K * Ly;
-            const int ex_index = (int)plan->exchanges.size();
-            rf_plan::Exchange ex;
-            ex.bytes = (size_t)np * K * Ly * sizeof(Acc);
-            ex.scratch = plan->alloc(ex.bytes, true, &status);
-            if (status != RF_OK) return status;
-            ex.send = ex.scratch;
-            const Acc *AMj = d_AMy + (size_t)j * plan->shard_world * K * K;
-            const int64_t rank_stride = (int64_t)np * K * Ly;
-            ex.form_incoming = [plan, gyargs, j, rank_stride, plane_stride, AMj](const void *gathered) {
-                for (int pl = 0; pl < plan->n_planes; pl++) {
-                    int rc = launch_gather_incoming<Acc>(gyargs(pl), j, (const Acc *)gathered, rank_stride,
-                                                         pl * plane_stride, plan->shard_rank, plan->shard_world, AMj,
-                                                         plan->stream);
-                    if (rc) return rc;
-                }
+        if (merged_exchange_applies(g.ny, g.K, plan->shard_world)) {
+            // one all-gather for all y scans (plan_generic.h, "merged exchange")
+            // ... whose correction of the tails is left to pass 2 (FusedArgs::y_apply): no launch between gather and pass 2
+            static const bool separate_apply = RF_KNOB("RF_SHARD_SEPARATE_APPLY") != nullptr;     // A/B runs
+            return add_merged_exchange<S, Acc>(plan, t.y, "carry_y", separate_apply ? nullptr : &d_Yapply);
+        }
+        return t.y.add_per_scan_carries(plan, "carry_y", "carry_y_apply", true);
+    }
+
+    void add_pass2() {
+        rf_plan *const plan = this->plan;
+        const int K = g.K, TY = g.TY;
+        const bool padded = g.padded;
+        const Acc *d_Yapply = this->d_Yapply, *d_Ynb = t.nb_y_pair() ? t.y.dev.base.W : nullptr;
+        Acc *const xt_done = (b.merged_cx || t.nb_x_pair()) ? b.xt_done : nullptr;
+        const size_t xt_pp = b.xt_pp;
+        Step p2;
+        p2.name = "fused_pass2";
+        p2.run = [plan, fargs = this->fargs, K, TY, d_Yapply, d_Ynb, padded, xt_done, xt_pp](int pl) {
+            FusedArgs<Acc> a = fargs(plan, pl);
+            a.y_apply = d_Yapply;
+            a.y_nb_W = d_Ynb;
+            if (xt_done) a.xt = xt_done + (size_t)pl * xt_pp;
+            if constexpr (sizeof(Acc) == 4) {
+                if (TY == 128) return launch_fused_pass2_tall<P>(K, plan->in[pl], plan->pw.in_u8, (P *)plan->xy_result(pl), a, plan->stream);
+            }
+            return launch_fused_pass2<P>(K, TY, padded ? plan->pad_in[pl] : plan->in[pl], plan->pw.in_u8, (P *)(padded ? plan->pad_out[pl] : plan->xy_result(pl)), a,
+                                         plan->stream);
+        };
+        if (g.y_is_exchange_dim) plan->finish_steps.push_back(p2);
+        else plan->begin_steps.push_back(p2);
+        if (padded) {
+            const size_t user_bytes = (size_t)plan->dims[0].N * sizeof(P);
+            Step co;
+            co.name = "pad_copy_out";
+            co.run = [plan, user_bytes](int pl) -> int {
+                RF_HIP_CHECK(hipMemcpyAsync(plan->out[pl], plan->pad_out[pl], user_bytes, hipMemcpyDeviceToDevice, plan->stream));
                 return (int)RF_OK;
             };
-            plan->exchanges.push_back(ex);
-            Step cy;
-            cy.name = "carry_y" + std::to_string(j);
-            cy.run = [plan, gyargs, K, j, d_ACy, Cy, ex_index, plane_stride, ymask](int pl) {
-                Acc *send = (Acc *)plan->exchanges[ex_index].send;
-                return launch_carry_block<Acc>(K, gyargs(pl), ymask, j, j + 1, send ? send + pl * plane_stride : nullptr,
-                                               d_ACy, Cy, plan->stream);
-            };
-            plan->exchange_local_steps.push_back({cy});
-            Step ap;
-            ap.name = "carry_y_apply" + std::to_string(j);
-            ap.run = [plan, gyargs, j](int pl) { return launch_generic_carry_apply<Acc>(gyargs(pl), j, plan->stream); };
-            plan->exchange_apply_steps.push_back({ap});
+            plan->begin_steps.push_back(co);
         }
-    }
-    Step p2;
-    p2.name = "fused_pass2";
-    const Acc *d_Ynb = nb_y_pair ? d_Wy : nullptr;
-    p2.run = [plan, fargs, K, TY, d_Yapply, d_Ynb, padded, merged_cx, nb_x_pair, xt_done, xt_pp](int pl) {
-        FusedArgs<Acc> a = fargs(pl);
-        a.y_apply = d_Yapply;
-        a.y_nb_W = d_Ynb;
-        if (merged_cx || nb_x_pair) a.xt = xt_done + (size_t)pl * xt_pp;
-        if constexpr (sizeof(Acc) == 4) {
-            if (TY == 128) return launch_fused_pass2_tall<P>(K, plan->in[pl], plan->pw.in_u8, (P *)plan->xy_result(pl), a, plan->stream);
-        }
-        return launch_fused_pass2<P>(K, TY, padded ? plan->pad_in[pl] : plan->in[pl], plan->pw.in_u8, (P *)(padded ? plan->pad_out[pl] : plan->xy_result(pl)), a,
-                                     plan->stream);
-    };
-    if (y_is_exchange_dim) plan->finish_steps.push_back(p2);
-    else plan->begin_steps.push_back(p2);
-    if (padded) {
-        const size_t user_bytes = (size_t)dx.N * sizeof(P);
-        Step co;
-        co.name = "pad_copy_out";
-        co.run = [plan, user_bytes](int pl) -> int {
-            RF_HIP_CHECK(hipMemcpyAsync(plan->out[pl], plan->pad_out[pl], user_bytes, hipMemcpyDeviceToDevice, plan->stream));
-            return (int)RF_OK;
-        };
-        plan->begin_steps.push_back(co);
     }
 
     // ---- z (3-D): filtered after the fused x/y stage, reading and writing the output planes ----
-    if (plan->ndim > 2 && !plan->dims[2].scan_ids.empty()) {
+    int add_z_stage(size_t first_begin_step) {
+        int status = RF_OK;
+        const bool padded = g.padded;
         // Intermediate volume (RF_PLAN_INPLACE_Z forbids it): a final z pass that reads and writes the SAME addresses is 4 %
         // slower than one from one volume to another -- its write front follows its read front through the same DRAM banks
         // (tools/microbench/zpass_shape.hip: 2.95 against 2.82 ms per 512 planes of 2048^2; config 5 at 2048^3: 12.3 -> 11.8 ms).
@@ -754,12 +754,46 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         } else
         if constexpr (sizeof(Acc) == 4)
             rc = strided_tile(plan, 2) > 0 ? add_strided_dimension<P, S>(plan, 2, /*from_input=*/false, desc, first_begin_step,
-                                                                         walk_hook.get(), walk_hook ? walk_child.release() : nullptr)
+                                                                         walk.hook.get(), walk.hook ? walk.child.release() : nullptr)
                                            : add_generic_dimension<P, S>(plan, desc->tile[2], 2, /*from_input=*/false);
         else rc = add_generic_dimension<P, S>(plan, desc->tile[2], 2, /*from_input=*/false);      // (f64: no strided kernels)
-        if (rc != RF_OK) return rc;
+        return rc;
     }
-    if (batch) {
+};
+
+template <typename P, typename S>
+int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
+    plan->vector_access = true;                  // 16-byte chunks per lane in both passes
+    FusedBuilder<P, S> fb;
+    fb.plan = plan; fb.desc = desc;
+    const FusedGeometry &g = fb.g = fused_geometry<P>(plan);
+    if (g.error) { set_error("%s", g.error); return RF_ERR_UNSUPPORTED; }
+    plan->dims[0].T = kFusedTX; plan->dims[0].M = g.chained ? g.N1 / kFusedTX : g.MX;
+    if (!g.chained) { plan->dims[1].T = g.TY; plan->dims[1].M = g.MY; }
+    const size_t first_begin_step = plan->begin_steps.size(), first_finish_step = plan->finish_steps.size();
+
+    if (int rc = fused_tables<P, S>(plan, g, fb.t)) return rc;
+    if (int rc = fused_buffers<S>(plan, g, fb.t, fb.b)) return rc;
+    if (int rc = plan_walk_pass1<P, S>(plan, desc, g, fb.b, fb.walk)) return rc;
+    // The x tails of tall patches arrive in two parts (GenericDimArgs::tails_part2), which only the blocked carry scan carry_x
+    // adds up: a plan whose x carries are completed by xscan_rows (merged_cx, the neighbour form) or by the row chain of chained
+    // rows would drop the second part.  Unreachable today -- tall patches need a volume and 128-row tiles, merged_cx at most 64
+    // rows, the neighbour form a 2-D image, chained rows a 1-D signal -- but those are heuristics of three functions.
+    if (fb.walk.args.tall && (fb.b.merged_cx || fb.t.nb_x || g.chained)) {
+        set_error("fused path: tall walk patches need the carry_x scan (not merged_cx / neighbour form / chained rows)");
+        return RF_ERR_UNSUPPORTED;
+    }
+    fb.set_plane_args();
+
+    if (int rc = fb.add_pass1()) return rc;
+    if (g.nx > 0 && !g.chained && !fb.b.merged_cx && !fb.t.nb_x) fb.t.x.add_local_carry(plan, "carry_x");
+    if (g.chained) fb.add_chained_row_carries();
+    if (g.nx > 0 && g.ny > 0) fb.add_xscan_rows();
+    if (int rc = fb.add_y_carries()) return rc;
+    fb.add_pass2();
+    if (plan->ndim > 2 && !plan->dims[2].scan_ids.empty())
+        if (int rc = fb.add_z_stage(first_begin_step)) return rc;
+    if (g.batch) {
         // every step above covers all planes in its one launch: it runs for plane 0 and is skipped for the others
         auto once = [](std::vector<Step> &steps, size_t first) {
             for (size_t i = first; i < steps.size(); i++) {
@@ -770,7 +804,7 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
         once(plan->begin_steps, first_begin_step);
         once(plan->finish_steps, first_finish_step);
     }
-    return status;
+    return RF_OK;
 }
 
 }  // namespace

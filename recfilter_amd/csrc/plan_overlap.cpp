@@ -42,14 +42,7 @@ int build_overlap(rf_plan *plan, const rf_filter_desc *desc) {
     OvArgs<Acc> base{};
     base.ndim = plan->ndim;
     base.clamped = plan->clamped ? 1 : 0;
-    struct DimCarry {
-        GenericDimArgs<Acc> g{};
-        uint32_t causal_mask = 0;
-        const Acc *AC = nullptr;
-        int C = 1;
-        size_t tails_pp = 0, inc_pp = 0;
-        Acc *tails = nullptr, *incoming = nullptr;
-    } carry[3];
+    CarryStage<S, Acc> carry[3];
     for (int d = 0; d < 3; d++) {
         OvDim<Acc> &od = base.d[d];
         od.N = d < plan->ndim ? plan->dims[d].N : 1;
@@ -65,70 +58,28 @@ int build_overlap(rf_plan *plan, const rf_filter_desc *desc) {
         di.T = T; di.M = di.N / T;
         od.T = T; od.M = (int32_t)di.M; od.n = n; od.k = k;
 
-        std::vector<ScanS<S>> ts;
-        std::vector<DevScan<Acc>> ds;
-        for (int id : di.scan_ids) {
-            ts.push_back(make_table_scan<S>(plan->scans[id]));
-            DevScan<Acc> dv = make_dev_scan<Acc>(plan->scans[id]);
-            dv.order = k;            // shorter scans are zero padded to the dimension's order (lib/split.cpp:575-578)
-            ds.push_back(dv);
-        }
-        DimTables<S> tab = build_dim_tables<S>(ts, k, T, plan->clamped);
-        std::vector<Acc> hW((size_t)4 * n * n * k * k, Acc(0)), hA((size_t)n * k * k, Acc(0)), hG((size_t)4 * n * T * k, Acc(0));
-        std::vector<double> dW(hW.size(), 0.0), dA(hA.size(), 0.0), dG(hG.size(), 0.0);
+        CarryStage<S, Acc> &c = carry[d];
+        status = c.init(plan, di.scan_ids, std::string(1, "xyz"[d]), k, T, di.M, LineGeom{di.N, di.stride, di.lines}, {});
+        // G[v][q][pos][o]: what the carry entering scan q adds to the tile after ALL scans of the dimension
+        std::vector<S> G((size_t)4 * n * T * k, S(0));
         for (int v = 0; v < 4; v++)
             for (int q = 0; q < n; q++) {
-                for (int s = q + 1; s < n; s++)
-                    for (int e = 0; e < k * k; e++) {
-                        const size_t idx = (((size_t)v * n + q) * n + s) * k * k + e;
-                        hW[idx] = table_to_acc<S, Acc>(tab.Wm(v, q, s)[e]);
-                        dW[idx] = table_to_double<S>(tab.Wm(v, q, s)[e]);
-                    }
-                const std::vector<S> &Pm = tab.P(v, q, n - 1);          // [pos][o]: after ALL scans of the dimension
-                for (size_t e = 0; e < (size_t)T * k; e++) {
-                    hG[((size_t)v * n + q) * T * k + e] = table_to_acc<S, Acc>(Pm[e]);
-                    dG[((size_t)v * n + q) * T * k + e] = table_to_double<S>(Pm[e]);
-                }
+                const std::vector<S> &Pm = c.tab.P(v, q, n - 1);
+                std::copy(Pm.begin(), Pm.begin() + (std::ptrdiff_t)T * k, G.begin() + (std::ptrdiff_t)(((size_t)v * n + q) * T * k));
             }
-        for (int s = 0; s < n; s++)
-            for (int e = 0; e < k * k; e++) {
-                hA[(size_t)s * k * k + e] = table_to_acc<S, Acc>(tab.A[s][e]);
-                dA[(size_t)s * k * k + e] = table_to_double<S>(tab.A[s][e]);
-            }
-        const std::string dn(1, "xyz"[d]);
-        plan->tables["W_" + dn] = dW;
-        plan->tables["A_" + dn] = dA;
-        plan->tables["G_" + dn] = dG;
-
-        DimCarry &c = carry[d];
-        c.C = carry_chunk_length(di.M, di.lines, k);
-        std::vector<Acc> hAC((size_t)n * k * k, Acc(0));
-        for (int s = 0; s < n; s++) {
-            std::vector<S> ac = mat_pow<S>(tab.A[s], c.C, k);
-            for (int e = 0; e < k * k; e++) hAC[(size_t)s * k * k + e] = table_to_acc<S, Acc>(ac[e]);
-            if (ts[s].causal) c.causal_mask |= 1u << s;
-        }
-        const DevScan<Acc> *dScans = (const DevScan<Acc> *)plan->upload(ds.data(), ds.size() * sizeof(DevScan<Acc>), &status);
-        const Acc *dWp = (const Acc *)plan->upload(hW.data(), hW.size() * sizeof(Acc), &status);
-        const Acc *dAp = (const Acc *)plan->upload(hA.data(), hA.size() * sizeof(Acc), &status);
+        const std::vector<Acc> hG = table_for_kernels<S, Acc>(plan, G, "G_" + c.dn);
         od.G = (const Acc *)plan->upload(hG.data(), hG.size() * sizeof(Acc), &status);
-        c.AC = (const Acc *)plan->upload(hAC.data(), hAC.size() * sizeof(Acc), &status);
-        od.scans = dScans;
-        c.tails_pp = (size_t)n * di.M * k * di.lines;
-        c.inc_pp = (size_t)n * k * di.lines;
-        c.tails = (Acc *)plan->alloc(c.tails_pp * plan->n_planes * sizeof(Acc), false, &status);
-        c.incoming = (Acc *)plan->alloc(c.inc_pp * plan->n_planes * sizeof(Acc), true, &status);     // zeros: image borders
+        od.scans = c.dev.base.scans;
+        if (status == RF_OK) status = c.alloc_buffers(plan);
         if (status != RF_OK) return status;
-        c.g.g = LineGeom{di.N, di.stride, di.lines};
-        c.g.T = T; c.g.M = (int32_t)di.M; c.g.k = k; c.g.n_scans = n;
-        c.g.clamped = base.clamped; c.g.first_is_border = 1; c.g.last_is_border = 1;
-        c.g.scans = dScans; c.g.W = dWp; c.g.A = dAp; c.g.Apow = nullptr;
     }
     // (dimensions without scans are "tiled" one index at a time: check the tile count fits)
-    auto args_for = [base, carry](int pl) {
+    CarryDev<Acc> dev[3];
+    for (int d = 0; d < 3; d++) dev[d] = carry[d].dev;
+    auto args_for = [base, dev](int pl) {
         OvArgs<Acc> a = base;
         for (int d = 0; d < 3; d++)
-            if (a.d[d].n > 0) a.d[d].tails = carry[d].tails + (size_t)pl * carry[d].tails_pp;
+            if (a.d[d].n > 0) a.d[d].tails = dev[d].tails + (size_t)pl * dev[d].tails_stride;
         return a;
     };
 
@@ -146,16 +97,7 @@ int build_overlap(rf_plan *plan, const rf_filter_desc *desc) {
             rs.run = [plan, args_for, d](int pl) { return launch_overlap_residual<Acc>(args_for(pl), d, plan->stream); };
             plan->begin_steps.push_back(rs);
         }
-        const DimCarry c = carry[d];
-        Step cs;
-        cs.name = "carry_" + dn;
-        cs.run = [plan, c](int pl) {
-            GenericDimArgs<Acc> g = c.g;
-            g.tails = c.tails + (size_t)pl * c.tails_pp;
-            g.incoming = c.incoming + (size_t)pl * c.inc_pp;
-            return launch_carry_block<Acc>(g.k, g, c.causal_mask, 0, g.n_scans, (Acc *)nullptr, c.AC, c.C, plan->stream);
-        };
-        plan->begin_steps.push_back(cs);
+        carry[d].add_local_carry(plan, "carry_" + dn);
         earlier = true;
     }
     Step p2;
