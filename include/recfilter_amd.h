@@ -59,7 +59,13 @@ typedef enum {
  * planes hold 16-bit floats; every sample is widened exactly to f32 as it is loaded; coefficients, tails, carries, tables,
  * pointwise stages and every intermediate are those of an RF_F32 plan of the same description; the result is rounded ONCE,
  * to nearest even, at the final store (overflow to +-inf, NaN propagates):  out = round16(F_f32(widen(in))).
- * 2-D images (width a multiple of 4) and long 1-D signals run natively on RF_PATH_TILED_FUSED; every other plan is staged
+ * 2-D images (width a multiple of 4) and long 1-D signals run natively on RF_PATH_TILED_FUSED.  So do unsharded volumes
+ * filtered along z whose depth the strided z kernels tile (a multiple of 32) and whose width is a multiple of 4, without an
+ * epilogue: the x/y stage's result waits, unrounded, in a plan-owned f32 volume per plane (always allocated, counted in
+ * rf_plan_workspace_bytes), and the final z pass rounds as it stores; the launch list is that of the RF_F32 plan built with
+ * RF_PLAN_STAGED_PASS1.  RF_PATH_TILED_FUSED asks for that form at any size; RF_PATH_AUTO takes it from 2^23 samples per plane
+ * on (measured: 0.69 of the staged step there, 0.52 at 1024^3; at 2^21 samples the staged form, three launches of the line
+ * kernels between its conversions, is 1.27x ahead).  Every other plan is staged
  * through plan-owned f32 planes (steps "convert_in" / "convert_out", counted in rf_plan_workspace_bytes; rf_plan_path
  * reports the inner f32 plan's path).  RF_IN_U8 input and shards other than the row shards of a 2-D image on the fused
  * path: RF_ERR_UNSUPPORTED. */
@@ -168,15 +174,16 @@ typedef struct {
  *                           a final z pass that reads and writes the same addresses runs 4 % slower (its read and write
  *                           fronts chase each other through the same DRAM banks: tools/microbench/zpass_shape.hip) -- as
  *                           long as that volume is at most a third of the device memory free when the plan is built.
- *                           Same kernels, same results either way.
+ *                           Same kernels, same results either way.  (A native RF_F16 / RF_BF16 volume NEEDS that
+ *                           volume, in f32: with this flag such a plan is staged through f32 planes instead.)
  *   RF_PLAN_FULL_CARRY_SCAN the fused x/y stage runs its carry scans (carry_x / carry_y) for every filter.  Default: an f32
  *                           2-D image (or batched Tuple planes), unsharded, whose scans along a dimension are one scan or
  *                           a causal-then-anticausal pair, completes that dimension's carries from the neighbouring
  *                           tiles' tails alone where the filter decays within a tile -- the part that form drops is
  *                           at most 2^-32 of the largest carry (rf_plan_table("neighbour_carries")).
  *   RF_PLAN_STAGE_HALF      RF_F16 / RF_BF16 pixels: the plan is staged through f32 planes even where the fused kernels
- *                           would run it natively (same result to the last rounding; for comparisons).  Ignored for the
- *                           other pixel types. */
+ *                           would run it natively -- 2-D images, 1-D signals and volumes alike (same result to the last
+ *                           rounding; for comparisons).  Ignored for the other pixel types. */
 #define RF_PLAN_FORCE_EXCHANGE  0x01u
 #define RF_PLAN_TILED_ONLY      0x02u
 #define RF_PLAN_NO_CASCADE      0x04u

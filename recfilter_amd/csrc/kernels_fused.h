@@ -151,6 +151,9 @@ int launch_line_scans(int K, bool strided, const P *src, P *dst, const LineScanA
 template <typename P>
 int launch_strided_pass(bool final_pass, int K, int TZ, const P *src, P *dst,
                         const StridedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream);
+// the final pass of that dimension from an f32 volume to planes of a 16-bit float storage type (_Float16, __bf16), rounded once
+template <typename PD>
+int launch_strided_final_narrow(int K, int TZ, const float *src, PD *dst, const StridedArgs<float> &a, hipStream_t stream);
 
 // Blocked parallel carry scan over the tails of one dimension (kernels_carry.hip); scans
 // [s_begin, s_end) of the dimension in one launch.  AC[s] = A[s]^C, C = carry_chunk_length(M, lines).
@@ -182,14 +185,17 @@ int launch_chain_apply(int K, const GenericDimArgs<Acc> &a, int s, const Acc *ex
                        const Acc *AM, const Acc *AMS, int S, hipStream_t stream);
 
 // pass 2: the final correction pass (kernels_fused.hip)
-// (src_u8: the input plane holds unsigned bytes, rf_pointwise_desc.in_dtype == RF_IN_U8; float pixels only)
+// src_kind: what the input plane holds -- the pixel type P, or (float pixels only) unsigned bytes (rf_pointwise_desc.in_dtype ==
+// RF_IN_U8) or a 16-bit float storage type: the x/y stage of a 16-bit volume, which writes the f32 volume its z stage reads
+// (FusedArgs::row_bytes is then that of the f32 rows)
+enum { kSrcPixel = 0, kSrcU8 = 1, kSrcF16 = 2, kSrcBF16 = 3 };
 template <typename P>
-int launch_fused_pass2(int K, int TY, const void *src, bool src_u8, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
+int launch_fused_pass2(int K, int TY, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                        hipStream_t stream);
 // the same pass on 256 x 128 tiles: two 64-row halves through the LDS, the 128-sample column in registers
 // (kernels_fused_tall.hip); halves the y tails and every kernel that walks them
 template <typename P>
-int launch_fused_pass2_tall(int K, const void *src, bool src_u8, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
+int launch_fused_pass2_tall(int K, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                             hipStream_t stream);
 // pass 1 as a contraction with precomputed impulse responses (kernels_tails.hip)
 template <typename P>

@@ -504,23 +504,50 @@ static int launch_fused_pass2_typed(int K, int TY, const PI *src, P *dst, const 
     return RF_ERR_UNSUPPORTED;
 }
 
+// 16-bit float planes in, f32 out (the x/y stage of a 16-bit volume): the automatic choice of a volume's x/y stage -- whole
+// tiles with the usual pair of scans in both dimensions, fixed at compile time, rows leaving from inside the last scan -- plus
+// the general-pattern code for every other filter and for partial tiles
+template <typename PI>
+static int launch_fused_pass2_widen(int K, int TY, const PI *src, float *dst, const FusedArgs<float> &a, hipStream_t stream) {
+    if (a.lin_limit > 0 || a.mod_form || (a.pw_flags & 2) || a.plane_batch) {
+        set_error("fused pass 2: a 16-bit source with an f32 destination is the x/y stage of a volume (no epilogue, no sections)");
+        return RF_ERR_INVALID_ARG;
+    }
+    const bool edge = a.last_cols != kFusedTX || a.last_rows != TY;
+    const bool pair = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0 && a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
+#define RF_CASE(KK, TT)                                                                                         \
+    if (K == KK && TY == TT) {                                                                                  \
+        if (edge) return launch_fused_pass2_impl<float, KK, TT, false, true, PI>(src, dst, a, stream);          \
+        if (pair) return launch_fused_pass2_impl<float, KK, TT, false, false, PI, 4, true>(src, dst, a, stream); \
+        return launch_fused_pass2_impl<float, KK, TT, false, false, PI>(src, dst, a, stream);                   \
+    }
+    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
+    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
+#undef RF_CASE
+    set_error("fused path: unsupported order %d / tile height %d", K, TY);
+    return RF_ERR_UNSUPPORTED;
+}
+
 template <typename P>
-int launch_fused_pass2(int K, int TY, const void *src, bool src_u8, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
+int launch_fused_pass2(int K, int TY, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                        hipStream_t stream) {
     if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
     if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
     if (a.y_nb_W != nullptr) { set_error("fused pass 2: neighbour-form y carries need the 128-row final pass"); return RF_ERR_INVALID_ARG; }
     if constexpr (std::is_same<P, float>::value) {
-        if (src_u8) return launch_fused_pass2_typed<P, uint8_t>(K, TY, (const uint8_t *)src, dst, a, stream);
+        if (src_kind == kSrcU8) return launch_fused_pass2_typed<P, uint8_t>(K, TY, (const uint8_t *)src, dst, a, stream);
+        if (src_kind == kSrcF16) return launch_fused_pass2_widen<_Float16>(K, TY, (const _Float16 *)src, dst, a, stream);
+        if (src_kind == kSrcBF16) return launch_fused_pass2_widen<__bf16>(K, TY, (const __bf16 *)src, dst, a, stream);
     }
+    if (src_kind != kSrcPixel) { set_error("fused pass 2: only f32 pixels take a source of another type"); return RF_ERR_INVALID_ARG; }
     return launch_fused_pass2_typed<P, P>(K, TY, (const P *)src, dst, a, stream);
 }
 
-template int launch_fused_pass2<float>(int, int, const void *, bool, float *, const FusedArgs<float> &, hipStream_t);
-template int launch_fused_pass2<int32_t>(int, int, const void *, bool, int32_t *, const FusedArgs<uint32_t> &, hipStream_t);
-template int launch_fused_pass2<int16_t>(int, int, const void *, bool, int16_t *, const FusedArgs<uint32_t> &, hipStream_t);
-template int launch_fused_pass2<_Float16>(int, int, const void *, bool, _Float16 *, const FusedArgs<float> &, hipStream_t);
-template int launch_fused_pass2<__bf16>(int, int, const void *, bool, __bf16 *, const FusedArgs<float> &, hipStream_t);
-template int launch_fused_pass2<double>(int, int, const void *, bool, double *, const FusedArgs<double> &, hipStream_t);
+template int launch_fused_pass2<float>(int, int, const void *, int, float *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2<int32_t>(int, int, const void *, int, int32_t *, const FusedArgs<uint32_t> &, hipStream_t);
+template int launch_fused_pass2<int16_t>(int, int, const void *, int, int16_t *, const FusedArgs<uint32_t> &, hipStream_t);
+template int launch_fused_pass2<_Float16>(int, int, const void *, int, _Float16 *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2<__bf16>(int, int, const void *, int, __bf16 *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2<double>(int, int, const void *, int, double *, const FusedArgs<double> &, hipStream_t);
 
 }  // namespace rf

@@ -438,10 +438,28 @@ int launch_tall_impl(const PI *src, P *dst, const FusedArgs<typename PixelTraits
     return launch_tall_pat<P, K, EDGE, PI, 0, false>(src, dst, a, stream);
 }
 
+// 16-bit float planes in, f32 out (the x/y stage of a 16-bit volume, kernels_fused.hip launch_fused_pass2_widen): the usual pair
+// of scans in both dimensions on its compile-time variants, every other filter on the general-pattern code
+template <int K, bool EDGE, typename PI>
+int launch_tall_widen(const PI *src, float *dst, const FusedArgs<float> &a, hipStream_t stream) {
+    if (a.mod_form || (a.pw_flags & 2) || a.plane_batch || a.y_nb_W != nullptr || a.y_apply != nullptr) {
+        set_error("fused pass 2: a 16-bit source with an f32 destination is the x/y stage of an unsharded volume (no epilogue, no sections)");
+        return RF_ERR_INVALID_ARG;
+    }
+    const bool pair_y = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0;
+    const bool pair_x = a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
+    if constexpr (!EDGE) {
+        if (pair_y && pair_x) return launch_tall_pat<float, K, EDGE, PI, 2, true, true>(src, dst, a, stream);
+    } else {
+        if (pair_y) return launch_tall_pat<float, K, EDGE, PI, 2, false>(src, dst, a, stream);
+    }
+    return launch_tall_pat<float, K, EDGE, PI, 0, false>(src, dst, a, stream);
+}
+
 }  // namespace
 
 template <typename P>
-int launch_fused_pass2_tall(int K, const void *src, bool src_u8, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
+int launch_fused_pass2_tall(int K, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                             hipStream_t stream) {
     if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
     if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
@@ -451,9 +469,14 @@ int launch_fused_pass2_tall(int K, const void *src, bool src_u8, P *dst, const F
 #define RF_CASE(KK)                                                                                                     \
     if (K == KK) {                                                                                                      \
         if constexpr (std::is_same<P, float>::value) {                                                                  \
-            if (src_u8) return e ? launch_tall_impl<P, KK, true, uint8_t>((const uint8_t *)src, dst, aa, stream)         \
-                                 : launch_tall_impl<P, KK, false, uint8_t>((const uint8_t *)src, dst, aa, stream);       \
+            if (src_kind == kSrcU8) return e ? launch_tall_impl<P, KK, true, uint8_t>((const uint8_t *)src, dst, aa, stream)   \
+                                             : launch_tall_impl<P, KK, false, uint8_t>((const uint8_t *)src, dst, aa, stream); \
+            if (src_kind == kSrcF16) return e ? launch_tall_widen<KK, true, _Float16>((const _Float16 *)src, dst, aa, stream)  \
+                                              : launch_tall_widen<KK, false, _Float16>((const _Float16 *)src, dst, aa, stream); \
+            if (src_kind == kSrcBF16) return e ? launch_tall_widen<KK, true, __bf16>((const __bf16 *)src, dst, aa, stream)     \
+                                               : launch_tall_widen<KK, false, __bf16>((const __bf16 *)src, dst, aa, stream);   \
         }                                                                                                               \
+        if (src_kind != kSrcPixel) { set_error("fused pass 2: only f32 pixels take a source of another type"); return (int)RF_ERR_INVALID_ARG; } \
         return e ? launch_tall_impl<P, KK, true, P>((const P *)src, dst, aa, stream)                                    \
                  : launch_tall_impl<P, KK, false, P>((const P *)src, dst, aa, stream);                                  \
     }
@@ -480,10 +503,10 @@ int launch_fused_pass2_tall(int K, const void *src, bool src_u8, P *dst, const F
     return one(a, edge);
 }
 
-template int launch_fused_pass2_tall<float>(int, const void *, bool, float *, const FusedArgs<float> &, hipStream_t);
-template int launch_fused_pass2_tall<_Float16>(int, const void *, bool, _Float16 *, const FusedArgs<float> &, hipStream_t);
-template int launch_fused_pass2_tall<__bf16>(int, const void *, bool, __bf16 *, const FusedArgs<float> &, hipStream_t);
-template int launch_fused_pass2_tall<int32_t>(int, const void *, bool, int32_t *, const FusedArgs<uint32_t> &, hipStream_t);
-template int launch_fused_pass2_tall<int16_t>(int, const void *, bool, int16_t *, const FusedArgs<uint32_t> &, hipStream_t);
+template int launch_fused_pass2_tall<float>(int, const void *, int, float *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2_tall<_Float16>(int, const void *, int, _Float16 *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2_tall<__bf16>(int, const void *, int, __bf16 *, const FusedArgs<float> &, hipStream_t);
+template int launch_fused_pass2_tall<int32_t>(int, const void *, int, int32_t *, const FusedArgs<uint32_t> &, hipStream_t);
+template int launch_fused_pass2_tall<int16_t>(int, const void *, int, int16_t *, const FusedArgs<uint32_t> &, hipStream_t);
 
 }  // namespace rf

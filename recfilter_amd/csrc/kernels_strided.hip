@@ -119,6 +119,88 @@ strided_pass_kernel(const P *__restrict__ src, P *__restrict__ dst, StridedArgs<
     }
 }
 
+// The final pass of a 16-bit float volume's z stage (plan_fused.cpp, "native 16-bit volumes"): strided_pass_kernel<float, ...,
+// FINAL = true> reading the f32 volume the x/y stage left -- the same addresses, carries, scan patterns and recurrences --
+// with a destination type of its own: every sample is rounded once, to nearest even, as it is stored (pixel.h).  A lane owns
+// one x, so a wave stores 128 contiguous bytes per row.
+// (A kernel of its own, not a parameter of the one above: sharing the body through a device function, or a further template
+// parameter, changed the code of every existing instance.)
+template <typename PD, int K, int TZ, bool UNI, int PAT>
+__global__ void __launch_bounds__(256)
+strided_final_narrow_kernel(const float *__restrict__ src, PD *__restrict__ dst, StridedArgs<float> a) {
+    const int64_t line = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (line >= a.lines) return;
+    const int t = blockIdx.y;
+    const int64_t l0 = (int64_t)blockIdx.x * 256;                    // wave-uniform
+    const int64_t ubase = (l0 / a.inner) * a.n * a.inner + (l0 % a.inner) + (int64_t)t * TZ * a.inner;
+    const int64_t base = UNI ? ubase + threadIdx.x : (line / a.inner) * a.n * a.inner + (line % a.inner) + (int64_t)t * TZ * a.inner;
+    const uint32_t lane = threadIdx.x;
+    float col[TZ];
+#pragma unroll
+    for (int i = 0; i < TZ; i++) {
+        if constexpr (UNI) col[i] = __builtin_nontemporal_load(src + (ubase + (int64_t)i * a.inner) + lane);
+        else col[i] = __builtin_nontemporal_load(src + base + (int64_t)i * a.inner);
+    }
+    auto one_scan = [&](int s, auto causal_tag) __attribute__((always_inline)) {
+        constexpr bool causal = decltype(causal_tag)::value;
+        const FusedScanY<float> &sc = a.scans[s];
+        const bool tile_first = causal ? (t == 0) : (t == a.M - 1);
+        const bool border = causal ? (t == 0 && a.first_is_border) : (t == a.M - 1 && a.last_is_border);
+        float carry[K];
+        if (tile_first) {
+#pragma unroll
+            for (int r = 0; r < K; r++) carry[r] = a.incoming[((int64_t)s * K + r) * a.lines + line];
+        } else {
+            const int tp = causal ? t - 1 : t + 1;
+#pragma unroll
+            for (int r = 0; r < K; r++) carry[r] = a.tails[(((int64_t)s * a.M + tp) * K + r) * a.lines + line];
+        }
+        scan_regs<float, causal, K, TZ>(col, sc, a.clamped && border, carry);
+    };
+    if constexpr (PAT == 1) {
+        one_scan(0, std::true_type{});
+    } else if constexpr (PAT == 2) {
+        one_scan(0, std::true_type{});
+        one_scan(1, std::false_type{});
+    } else {
+#pragma unroll 1
+        for (int s = 0; s < a.n_scans; s++) {
+            if (a.scans[s].causal != 0) one_scan(s, std::true_type{});
+            else one_scan(s, std::false_type{});
+        }
+    }
+    // Every conversion takes the f32 value as the last scan left it in its register (the empty asm).  Left to itself the
+    // compiler folds the conversion to binary16 into the last scan's multiply-add (v_fma_mixlo_f16: no f32 rounding in front of
+    // the 16-bit one, and a second, 16-bit copy of the column alive beside the f32 one the recurrence needs): 129 registers
+    // against the f32 instance's 78 at 64 samples, 257 against 140 at 128, i.e. one wave per SIMD instead of three.
+#pragma unroll
+    for (int i = 0; i < TZ; i++) {
+        float v = col[i];
+        asm volatile("" : "+v"(v));
+        if constexpr (UNI) __builtin_nontemporal_store(PixelTraits<PD>::store(v), dst + (ubase + (int64_t)i * a.inner) + lane);
+        else __builtin_nontemporal_store(PixelTraits<PD>::store(v), dst + base + (int64_t)i * a.inner);
+    }
+}
+
+}  // namespace
+
+namespace {
+// the fast variants: whole runs of 256 lines per workgroup, the usual scan patterns (else the general one)
+template <typename Acc>
+inline bool strided_uniform(const StridedArgs<Acc> &a) { return a.inner % 256 == 0 && a.lines % 256 == 0; }
+template <typename Acc>
+inline int strided_pattern(const StridedArgs<Acc> &a) {
+    return a.mod_form ? 0 : (a.n_scans == 1 && a.scans[0].causal != 0) ? 1
+         : (a.n_scans == 2 && a.scans[0].causal != 0 && a.scans[1].causal == 0) ? 2 : 0;
+}
+// Workgroups per CU: these kernels stream 64 or 128 rows per wave that lie a whole plane apart; beyond three waves
+// per SIMD more rows in flight make the memory system slower, not faster (2048^3, 64 samples per thread: 5.7 ms at
+// three waves per SIMD, 6.9 ms at six).  An unused LDS allocation bounds the residency.
+inline size_t strided_residency_lds() {
+    static const int wgs_per_cu = RF_KNOB("RF_STRIDED_WGS") ? atoi(RF_KNOB("RF_STRIDED_WGS")) : 3;
+    const size_t pad_lds = wgs_per_cu >= 1 && wgs_per_cu <= 8 ? (size_t)(160 * 1024 / wgs_per_cu) & ~(size_t)1023 : 0;
+    return pad_lds > 64 * 1024 ? 64 * 1024 : pad_lds;      // (more than 64 KiB would need an opt-in per kernel)
+}
 }  // namespace
 
 template <typename P>
@@ -127,16 +209,9 @@ int launch_strided_pass(bool final_pass, int K, int TZ, const P *src, P *dst,
     if (a.lines <= 0 || a.M <= 0) return RF_OK;
     if (a.M > 65535) { set_error("strided path: too many tiles"); return RF_ERR_UNSUPPORTED; }
     dim3 grid((unsigned)((a.lines + 255) / 256), (unsigned)a.M);
-    // the fast variants: whole runs of 256 lines per workgroup, the usual scan patterns (else the general one)
-    const bool uni = a.inner % 256 == 0 && a.lines % 256 == 0;
-    const int pat = a.mod_form ? 0 : (a.n_scans == 1 && a.scans[0].causal != 0) ? 1
-                  : (a.n_scans == 2 && a.scans[0].causal != 0 && a.scans[1].causal == 0) ? 2 : 0;
-    // Workgroups per CU: these kernels stream 64 or 128 rows per wave that lie a whole plane apart; beyond three waves
-    // per SIMD more rows in flight make the memory system slower, not faster (2048^3, 64 samples per thread: 5.7 ms at
-    // three waves per SIMD, 6.9 ms at six).  An unused LDS allocation bounds the residency.
-    static const int wgs_per_cu = RF_KNOB("RF_STRIDED_WGS") ? atoi(RF_KNOB("RF_STRIDED_WGS")) : 3;
-    const size_t pad_lds = wgs_per_cu >= 1 && wgs_per_cu <= 8 ? (size_t)(160 * 1024 / wgs_per_cu) & ~(size_t)1023 : 0;
-    const size_t lds_bytes = pad_lds > 64 * 1024 ? 64 * 1024 : pad_lds;      // (more than 64 KiB would need an opt-in per kernel)
+    const bool uni = strided_uniform(a);
+    const int pat = strided_pattern(a);
+    const size_t lds_bytes = strided_residency_lds();
 #define RF_LAUNCH(KK, TT, FF, UU, PP)                                                                                \
     { hipLaunchKernelGGL((strided_pass_kernel<P, KK, TT, FF, UU, PP>), grid, dim3(256), UU ? lds_bytes : 0, stream, src, dst, a); \
       RF_HIP_CHECK(hipGetLastError()); return RF_OK; }
@@ -145,6 +220,34 @@ int launch_strided_pass(bool final_pass, int K, int TZ, const P *src, P *dst,
         if (uni && pat == 2) { if (final_pass) RF_LAUNCH(KK, TT, true, true, 2) else RF_LAUNCH(KK, TT, false, true, 2) } \
         if (uni && pat == 1) { if (final_pass) RF_LAUNCH(KK, TT, true, true, 1) else RF_LAUNCH(KK, TT, false, true, 1) } \
         if (final_pass) RF_LAUNCH(KK, TT, true, false, 0) else RF_LAUNCH(KK, TT, false, false, 0)                     \
+    }
+    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
+    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
+    RF_CASE(1, 128) RF_CASE(2, 128) RF_CASE(3, 128)
+#undef RF_CASE
+#undef RF_LAUNCH
+    set_error("strided path: unsupported order %d / tile %d", K, TZ);
+    return RF_ERR_UNSUPPORTED;
+}
+
+// the final pass from an f32 volume to 16-bit float planes: same grid, same variant choice, same residency
+template <typename PD>
+int launch_strided_final_narrow(int K, int TZ, const float *src, PD *dst, const StridedArgs<float> &a, hipStream_t stream) {
+    if (a.lines <= 0 || a.M <= 0) return RF_OK;
+    if (a.M > 65535) { set_error("strided path: too many tiles"); return RF_ERR_UNSUPPORTED; }
+    if (a.mod_form) { set_error("strided path: scans in mod form are those of f32 plans"); return RF_ERR_INVALID_ARG; }
+    dim3 grid((unsigned)((a.lines + 255) / 256), (unsigned)a.M);
+    const bool uni = strided_uniform(a);
+    const int pat = strided_pattern(a);
+    const size_t lds_bytes = strided_residency_lds();
+#define RF_LAUNCH(KK, TT, UU, PP)                                                                                    \
+    { hipLaunchKernelGGL((strided_final_narrow_kernel<PD, KK, TT, UU, PP>), grid, dim3(256), UU ? lds_bytes : 0, stream, src, dst, a); \
+      RF_HIP_CHECK(hipGetLastError()); return RF_OK; }
+#define RF_CASE(KK, TT)                                                                                              \
+    if (K == KK && TZ == TT) {                                                                                        \
+        if (uni && pat == 2) RF_LAUNCH(KK, TT, true, 2)                                                               \
+        if (uni && pat == 1) RF_LAUNCH(KK, TT, true, 1)                                                               \
+        RF_LAUNCH(KK, TT, false, 0)                                                                                   \
     }
     RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
     RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
@@ -188,5 +291,7 @@ int launch_stream_copy(const float *src, float *dst, int64_t width, int64_t rows
 template int launch_strided_pass<float>(bool, int, int, const float *, float *, const StridedArgs<float> &, hipStream_t);
 template int launch_strided_pass<int32_t>(bool, int, int, const int32_t *, int32_t *, const StridedArgs<uint32_t> &, hipStream_t);
 template int launch_strided_pass<int16_t>(bool, int, int, const int16_t *, int16_t *, const StridedArgs<uint32_t> &, hipStream_t);
+template int launch_strided_final_narrow<_Float16>(int, int, const float *, _Float16 *, const StridedArgs<float> &, hipStream_t);
+template int launch_strided_final_narrow<__bf16>(int, int, const float *, __bf16 *, const StridedArgs<float> &, hipStream_t);
 
 }  // namespace rf

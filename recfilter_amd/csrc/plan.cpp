@@ -386,6 +386,15 @@ int build_clamped_1d(const rf_filter_desc *desc, rf_plan *parent) {
 //     convert_in -> the f32 plan of the same description, in place in those planes -> convert_out
 // (an epilogue with an input operand needs out != in: a second f32 plane per image plane).  The steps carry those two
 // names, rf_plan_path reports the inner plan's path, rf_plan_workspace_bytes includes the planes.
+// Volumes whose z stage runs on the strided kernels are native as well (plan_fused.cpp, "native 16-bit volumes"): the x/y
+// stage's result waits in an f32 volume of the plan's own.  RF_PATH_TILED_FUSED asks for that form at any size; RF_PATH_AUTO
+// takes it from kHalfVolumeNativeSamples samples per plane on and stays staged below.
+// Measured, one MI355X, order-2 Gaussian along x, y and z, native / staged step (profiles/r9/half_volumes.txt): 64 x 96 x 128
+// 1.73 and 128^3 (2^21) 1.27 -- there the staged form's f32 plan is three launches of the line kernels, 29 / 43 us a step against
+// the native plan's seven launches, 51 / 55 us; 128 x 256 x 256 (2^23) 0.69, 256^3 0.71, 512^3 0.60, 2^28 0.54, 1024^3 0.52.
+// 2^23 is the smallest size measured with the native form ahead; nothing between 2^21 and 2^23 has been measured.
+constexpr int64_t kHalfVolumeNativeSamples = (int64_t)1 << 23;
+
 template <typename H>
 int build_staged_half_typed(const rf_filter_desc *desc, rf_plan *parent) {
     rf_filter_desc fd = *desc;
@@ -683,8 +692,10 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
     };
     if (half) {
         std::string unused;
+        // (volumes, RF_PATH_AUTO: native from kHalfVolumeNativeSamples samples per plane on -- above)
+        const bool small_volume = desc->ndim > 2 && desc->path == RF_PATH_AUTO && plan->total < kHalfVolumeNativeSamples;
         const bool native = (desc->path == RF_PATH_AUTO || desc->path == RF_PATH_TILED_FUSED) && !(desc->flags & RF_PLAN_STAGE_HALF) &&
-                            fused_plan_applicable(plan.get(), desc, &unused);
+                            !small_volume && fused_plan_applicable(plan.get(), desc, &unused);
         if (!native) return finish_staged(build_staged_half(desc, plan.get()));
     }
 

@@ -706,6 +706,16 @@ struct FusedBuilder {
             a.y_apply = d_Yapply;
             a.y_nb_W = d_Ynb;
             if (xt_done) a.xt = xt_done + (size_t)pl * xt_pp;
+            if constexpr (is_half_pixel<P>::value) {
+                // native 16-bit volume (add_z_stage gave the plan its f32 volume, which only such a plan has): the f32 instances
+                // with a 16-bit source, into the volume the z stage reads
+                if (plan->mid[pl] != nullptr) {
+                    const int kind = std::is_same<P, _Float16>::value ? kSrcF16 : kSrcBF16;
+                    a.row_bytes = (uint32_t)(a.NX * (int64_t)sizeof(float));
+                    if (TY == 128) return launch_fused_pass2_tall<float>(K, plan->in[pl], kind, (float *)plan->mid[pl], a, plan->stream);
+                    return launch_fused_pass2<float>(K, TY, plan->in[pl], kind, (float *)plan->mid[pl], a, plan->stream);
+                }
+            }
             if constexpr (sizeof(Acc) == 4) {
                 if (TY == 128) return launch_fused_pass2_tall<P>(K, plan->in[pl], plan->pw.in_u8, (P *)plan->xy_result(pl), a, plan->stream);
             }
@@ -736,7 +746,7 @@ struct FusedBuilder {
         // Large volumes on the strided kernels therefore get a plan-owned volume between the two stages, as long as it is at
         // most a third of the memory the device has free now.  The x/y stage writes it, the z stage reads it and writes the
         // output planes; nothing else looks at the x/y stage's result.
-        if constexpr (sizeof(Acc) == 4) {
+        if constexpr (sizeof(Acc) == 4 && !is_half_pixel<P>::value) {
             const size_t mid_bytes = (size_t)plan->total * sizeof(P);
             if (!(plan->flags & RF_PLAN_INPLACE_Z) && !plan->host_only && !padded && strided_tile(plan, 2) > 0 &&
                 plan->total >= ((int64_t)1 << 28)) {
@@ -748,9 +758,20 @@ struct FusedBuilder {
             }
         }
         int rc;
-        if constexpr (is_half_pixel<P>::value) {      // (fused_plan_applicable: no volumes of 16-bit float pixels)
-            set_error("fused path: volumes of 16-bit float pixels are staged through f32 planes");
-            return RF_ERR_UNSUPPORTED;
+        if constexpr (is_half_pixel<P>::value) {
+            // Native 16-bit volumes.  RF_F16 / RF_BF16 are storage types (pixel.h): nothing may be rounded before the last store,
+            // so the x/y stage's result cannot wait in the 16-bit output planes.  It waits in the intermediate volume above, here
+            // ALWAYS allocated and ALWAYS f32 (host-only plans count it in their workspace; the free memory is not consulted: the
+            // staged form would own an f32 plane of the same size): the final x/y pass reads the 16-bit input and writes it
+            // (f32 instances with a 16-bit source), pass 1 of z and the carry scan are the f32 plan's, and the final z pass
+            // rounds once as it stores (strided_final_narrow_kernel).  18 bytes per sample, against 32-36 staged.
+            if (strided_tile(plan, 2) == 0 || padded) {
+                set_error("fused path: a volume of 16-bit float pixels needs the strided z stage");
+                return RF_ERR_UNSUPPORTED;
+            }
+            for (int pl = 0; pl < plan->n_planes; pl++) plan->mid[pl] = plan->alloc((size_t)plan->total * sizeof(float), false, &status);
+            if (status != RF_OK) return status;
+            return add_strided_dimension<float, S, P>(plan, 2, /*from_input=*/false, desc, first_begin_step);
         } else
         if constexpr (sizeof(Acc) == 4)
             rc = strided_tile(plan, 2) > 0 ? add_strided_dimension<P, S>(plan, 2, /*from_input=*/false, desc, first_begin_step,
@@ -815,9 +836,16 @@ bool fused_plan_applicable(const rf_plan *plan, const rf_filter_desc *, std::str
     if (plan->dtype != RF_F32 && plan->dtype != RF_I32 && plan->dtype != RF_I16 && plan->dtype != RF_F64 && !half)
         return no("pixel type must be f32, f64, i32, i16, f16 or bf16");
     // 16-bit float storage types (pixel.h): 2-D images and 1-D signals run here natively -- no intermediate of theirs ever
-    // reaches a plane.  A volume's z stage would read the x/y stage's result back from the output planes, i.e. rounded to 16
-    // bits: volumes are staged through f32 planes (plan.cpp, "staged 16-bit plans").
-    if (half && plan->ndim > 2) return no("16-bit float pixels: 1-D signals and 2-D images");
+    // reaches a plane.  A volume's z stage must not read the x/y stage's result back from the 16-bit output planes: a volume is
+    // native where that result can wait in an f32 volume of the plan's own in front of the strided z kernels (add_z_stage,
+    // "native 16-bit volumes") and staged through f32 planes everywhere else (plan.cpp, "staged 16-bit plans").
+    if (half && plan->ndim > 2) {
+        if (plan->dims[2].scan_ids.empty() || strided_tile(plan, 2) == 0) return no("16-bit float volumes: scans along z on the strided kernels");
+        if (plan->sharded()) return no("16-bit float volumes cannot be sharded");
+        // (a volume's epilogue is a stand-alone step over the output planes, i.e. behind the rounding)
+        if (plan->pw.post) return no("16-bit float volumes: no epilogue");
+        if (plan->flags & (RF_PLAN_INPLACE_Z | RF_PLAN_WALK_PASS1)) return no("16-bit float volumes: the z stage reads an f32 volume of the plan's own, after two first passes");
+    }
     if (half && plan->pw.in_u8) return no("16-bit float pixels: no unsigned-byte input");
     if (plan->dtype == RF_F64 && (plan->ndim < 2 || plan->pw.in_u8)) return no("f64 pixels: 2-D / 3-D images of f64 samples");
     if (plan->ndim == 1) {

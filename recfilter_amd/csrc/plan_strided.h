@@ -15,7 +15,8 @@ namespace rf {
 inline int strided_tile(const rf_plan *plan, int d) {
     const DimInfo &di = plan->dims[d];
     if (di.scan_ids.empty() || di.k > kFusedMaxK || (int)di.scan_ids.size() > kFusedMaxScans) return 0;
-    if (plan->dtype != RF_F32 && plan->dtype != RF_I32 && plan->dtype != RF_I16) return 0;
+    // (RF_F16 / RF_BF16: the z stage of a native 16-bit volume, which reads an f32 volume -- plan_fused.cpp)
+    if (plan->dtype != RF_F32 && plan->dtype != RF_I32 && plan->dtype != RF_I16 && plan->dtype != RF_F16 && plan->dtype != RF_BF16) return 0;
     const int64_t basis = plan->tile_basis(d);       // sharded dimension: every rank's slab must tile alike
     if (const int want = plan->strided_tile_planes() ? plan->strided_tile_planes() : RF_KNOB("RF_STRIDED_TZ") ? atoi(RF_KNOB("RF_STRIDED_TZ")) : 0) {
         // RF_PLAN_TILE_PLANES(n): the caller's tile width of the strided stage, where it divides the extent
@@ -84,7 +85,9 @@ inline bool early_exchange_possible(const rf_plan *plan, int d, const rf_filter_
 // `walk` (unsharded volumes, kernels_tails_walk.hip): the same commutation without an exchange -- pass 1 of the x/y stage has
 // formed this dimension's tails from the raw input as it went, so the dimension is: carry scan, F over the scans * k * tiles
 // carry planes (`walk_child`, built by the caller), pass 2 on the x/y-filtered output.
-template <typename P, typename S>
+// PD (native 16-bit volumes, plan_fused.cpp): the type of the output planes where it is not P -- P = float is then the type of
+// the plan-owned volume the x/y stage wrote (rf_plan::mid), which both passes read; only the final pass's store knows PD.
+template <typename P, typename S, typename PD = P>
 int add_strided_dimension(rf_plan *plan, int d, bool from_input, const rf_filter_desc *desc = nullptr, size_t xy_begin = (size_t)-1,
                           WalkHook *walk = nullptr, rf_plan *walk_child = nullptr) {
     using Acc = typename PixelTraits<P>::Acc;
@@ -92,6 +95,10 @@ int add_strided_dimension(rf_plan *plan, int d, bool from_input, const rf_filter
     DimInfo &di = plan->dims[d];
     const int TZ = strided_tile(plan, d);
     if (TZ == 0) { set_error("strided path not applicable to dimension %d", d); return RF_ERR_UNSUPPORTED; }
+    if (!std::is_same<PD, P>::value && (from_input || walk != nullptr || plan->sharded() || (plan->mid[0] == nullptr && !plan->host_only))) {
+        set_error("strided path: a destination type of its own needs the unsharded z stage behind an intermediate volume");
+        return RF_ERR_INVALID_ARG;
+    }
     di.T = TZ;
     di.M = di.N / TZ;
     const int n = (int)di.scan_ids.size(), K = di.k, M = (int)di.M;
@@ -186,7 +193,8 @@ int add_strided_dimension(rf_plan *plan, int d, bool from_input, const rf_filter
     p2.name = "strided_pass2_" + dn;
     p2.run = [plan, sargs, K, TZ, from_input](int pl) {
         const P *src = from_input ? (const P *)plan->in[pl] : (const P *)plan->xy_result(pl);
-        return launch_strided_pass<P>(true, K, TZ, src, (P *)plan->out[pl], sargs(pl), plan->stream);
+        if constexpr (!std::is_same<PD, P>::value) return launch_strided_final_narrow<PD>(K, TZ, src, (PD *)plan->out[pl], sargs(pl), plan->stream);
+        else return launch_strided_pass<P>(true, K, TZ, src, (P *)plan->out[pl], sargs(pl), plan->stream);
     };
     if (d == outer) plan->finish_steps.push_back(p2);
     else plan->begin_steps.push_back(p2);
