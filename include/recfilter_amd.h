@@ -327,9 +327,20 @@ int rf_plan_abort(rf_plan *plan);
  * the plan runs it (RF_PLAN_FULL_CARRY_SCAN). */
 int rf_plan_table(const rf_plan *plan, const char *name, double *out, size_t capacity, size_t *n_out);
 
-/* Debugging aid: device pointer and size of the i-th buffer the plan owns (tables, tails, carries,
- * in allocation order); RF_ERR_INVALID_ARG past the last one. */
+/* Debugging aids.  rf_plan_debug_buffer: device pointer and size of the i-th device buffer an execute of the plan's first
+ * instance uses -- the plan's own (tables, tails, carries, staging planes; in allocation order), then those of the plans it
+ * drives as stages (cascade stages, the f32 plan inside a staged 16-bit plan, the zero-border plan of a clamped signal) and
+ * of its helper plans, depth first; RF_ERR_INVALID_ARG past the last one.  A host-only plan lists what it would have
+ * allocated, with null pointers.
+ * rf_plan_debug_buffer_kind: how the buffer was made.  RF_BUFFER_SCRATCH buffers hold samples, tails or carries in the plan's
+ * arithmetic type and are written by every execute before it reads them; they hold no index, count or flag.
+ * rf_plan_debug_fill: sets every byte of a zeroed or scratch buffer to `byte` (0..255), asynchronously on `stream`;
+ * RF_ERR_INVALID_ARG for a table.  Filling a ZEROED buffer with anything but 0 breaks the plan; filling SCRATCH with any
+ * byte must not change any result (tests/test_gpu_footprint.py). */
+enum rf_buffer_kind { RF_BUFFER_TABLE = 0, RF_BUFFER_ZEROED = 1, RF_BUFFER_SCRATCH = 2 };
 int rf_plan_debug_buffer(const rf_plan *plan, int index, void **ptr_out, size_t *bytes_out);
+int rf_plan_debug_buffer_kind(const rf_plan *plan, int index, int *kind_out);
+int rf_plan_debug_fill(rf_plan *plan, int index, int byte, void *stream);
 
 /* ---- coefficient design (lib/iir_coeff.cpp:162-177, 222-234, 236-263, 205-220) ------------ */
 int rf_gaussian_weights(float sigma, int order, float *coeff_out /* order+1 */);

@@ -27,6 +27,8 @@ RF_F32, RF_F64, RF_I32, RF_I16, RF_F16, RF_BF16 = range(6)      # RF_F16 / RF_BF
 RF_BORDER_ZERO, RF_BORDER_CLAMP = 0, 1
 RF_POINTWISE_PRE, RF_POINTWISE_POST = 1, 2
 RF_IN_PIXEL, RF_IN_U8 = 0, 1
+RF_BUFFER_TABLE, RF_BUFFER_ZEROED, RF_BUFFER_SCRATCH = range(3)      # rf_buffer_kind (rf_plan_debug_buffer_kind)
+BUFFER_KIND_NAMES = {RF_BUFFER_TABLE: "table", RF_BUFFER_ZEROED: "zeroed", RF_BUFFER_SCRATCH: "scratch"}
 RF_PATH_AUTO, RF_PATH_UNTILED, RF_PATH_TILED_GENERIC, RF_PATH_TILED_FUSED, RF_PATH_TILED_OVERLAPPED, RF_PATH_TILED_MATRIX = range(6)
 # rf_filter_desc.flags (plan options; the library reads no environment variable)
 RF_PLAN_FORCE_EXCHANGE, RF_PLAN_TILED_ONLY, RF_PLAN_NO_CASCADE, RF_PLAN_NO_SECTIONS = 0x01, 0x02, 0x04, 0x08
@@ -58,7 +60,7 @@ EXPORTED_SYMBOLS = [
     "rf_plan_num_kernels", "rf_plan_execute", "rf_plan_execute_timed", "rf_plan_num_exchanges",
     "rf_plan_exchange_bytes",
     "rf_plan_begin", "rf_plan_exchange_local", "rf_plan_exchange_apply", "rf_plan_has_interior", "rf_plan_interior", "rf_plan_finish", "rf_plan_abort",
-    "rf_plan_table", "rf_plan_debug_buffer", "rf_gaussian_weights", "rf_integral_image_coeff", "rf_overlap_feedback_coeff",
+    "rf_plan_table", "rf_plan_debug_buffer", "rf_plan_debug_buffer_kind", "rf_plan_debug_fill", "rf_gaussian_weights", "rf_integral_image_coeff", "rf_overlap_feedback_coeff",
     "rf_gaussian_box_filter", "rf_box_difference", "rf_tap_filter", "rf_stream_copy", "rf_last_error_string", "rf_version", "rf_device_count",
 ]
 
@@ -146,6 +148,8 @@ def lib() -> ctypes.CDLL:
     L.rf_plan_table.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.c_size_t,
                                 ctypes.POINTER(ctypes.c_size_t)]
     L.rf_plan_debug_buffer.argtypes = [vp, ctypes.c_int, vpp, ctypes.POINTER(ctypes.c_size_t)]
+    L.rf_plan_debug_buffer_kind.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    L.rf_plan_debug_fill.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
     L.rf_gaussian_weights.argtypes = [ctypes.c_float, ctypes.c_int, fp]
     L.rf_integral_image_coeff.argtypes = [ctypes.c_int, fp]
     L.rf_overlap_feedback_coeff.argtypes = [fp, ctypes.c_int, fp, ctypes.c_int, fp]

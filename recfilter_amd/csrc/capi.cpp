@@ -348,10 +348,38 @@ int rf_plan_table(const rf_plan *plan, const char *name, double *out, size_t cap
     return RF_OK;
 }
 
+namespace {
+const DeviceBuffer *debug_buffer_at(const rf_plan *plan, int index) {
+    std::vector<const DeviceBuffer *> all;
+    if (plan) plan->all_buffers(all);
+    if (!plan || index < 0 || index >= (int)all.size()) { set_error("no such buffer"); return nullptr; }
+    return all[(size_t)index];
+}
+}  // namespace
+
 int rf_plan_debug_buffer(const rf_plan *plan, int index, void **ptr_out, size_t *bytes_out) {
-    if (!plan || index < 0 || index >= (int)plan->buffers.size()) { set_error("no such buffer"); return RF_ERR_INVALID_ARG; }
-    if (ptr_out) *ptr_out = plan->buffers[index].ptr;
-    if (bytes_out) *bytes_out = plan->buffers[index].bytes;
+    const DeviceBuffer *b = debug_buffer_at(plan, index);
+    if (!b) return RF_ERR_INVALID_ARG;
+    if (ptr_out) *ptr_out = b->ptr;
+    if (bytes_out) *bytes_out = b->bytes;
+    return RF_OK;
+}
+
+int rf_plan_debug_buffer_kind(const rf_plan *plan, int index, int *kind_out) {
+    const DeviceBuffer *b = debug_buffer_at(plan, index);
+    if (!b || !kind_out) { if (b) set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    *kind_out = b->kind;
+    return RF_OK;
+}
+
+int rf_plan_debug_fill(rf_plan *plan, int index, int byte, void *stream) {
+    const DeviceBuffer *b = debug_buffer_at(plan, index);
+    if (!b) return RF_ERR_INVALID_ARG;
+    if (b->kind == RF_BUFFER_TABLE) { set_error("buffer %d is a table: not filled", index); return RF_ERR_INVALID_ARG; }
+    if (byte < 0 || byte > 255) { set_error("fill byte must be 0..255"); return RF_ERR_INVALID_ARG; }
+    if (plan->host_only || !b->ptr) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) has no device memory"); return RF_ERR_HIP; }
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    RF_HIP_CHECK(hipMemsetAsync(b->ptr, byte, b->bytes, (hipStream_t)stream));
     return RF_OK;
 }
 

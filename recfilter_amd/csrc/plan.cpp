@@ -933,17 +933,26 @@ hipStream_t build_stream(int device, int *status) {
 }
 }  // namespace
 
-void *rf_plan::alloc(size_t bytes, bool zero, int *status) {
+void rf_plan::all_buffers(std::vector<const rf::DeviceBuffer *> &into) const {
+    for (const auto &b : buffers) into.push_back(&b);
+    for (const auto &s : stages) s->all_buffers(into);
+    for (const auto &h : helpers) h->all_buffers(into);
+}
+
+void *rf_plan::alloc(size_t bytes, bool zero, int *status) { return alloc_kind(bytes, zero ? RF_BUFFER_ZEROED : RF_BUFFER_SCRATCH, status); }
+
+void *rf_plan::alloc_kind(size_t bytes, int kind, int *status) {
+    const bool zero = kind == RF_BUFFER_ZEROED;
     if (*status != RF_OK) return nullptr;
     if (bytes == 0) bytes = 16;
-    if (host_only) { workspace_bytes += bytes; return nullptr; }
+    if (host_only) { buffers.push_back({nullptr, bytes, kind}); workspace_bytes += bytes; return nullptr; }
     void *p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) {
         rf::set_error("hipMalloc of %zu bytes failed", bytes);
         *status = RF_ERR_NOMEM;
         return nullptr;
     }
-    buffers.push_back({p, bytes});
+    buffers.push_back({p, bytes, kind});
     workspace_bytes += bytes;
     if (zero) {
         hipStream_t bs = build_stream(device, status);
@@ -956,7 +965,7 @@ void *rf_plan::alloc(size_t bytes, bool zero, int *status) {
 }
 
 void *rf_plan::upload(const void *host, size_t bytes, int *status) {
-    void *p = alloc(bytes, false, status);
+    void *p = alloc_kind(bytes, RF_BUFFER_TABLE, status);
     if (!p) return nullptr;
     if (bytes) {
         // the host tables are temporaries of the build: the copy has left them when this returns

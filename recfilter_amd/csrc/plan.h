@@ -41,9 +41,12 @@ struct Pointwise {
     double pre_s = 1.0, pre_b = 0.0, post_f = 1.0, post_i = 0.0, post_b = 0.0;
 };
 
+// How a device buffer of a plan was made (rf_buffer_kind): a table uploaded at build, workspace zeroed at build and relied on
+// afterwards, or scratch that every execute writes before it reads it.
 struct DeviceBuffer {
-    void *ptr = nullptr;
+    void *ptr = nullptr;         // null in a host-only plan, which records what it would have allocated
     size_t bytes = 0;
+    int kind = RF_BUFFER_SCRATCH;
 };
 
 }  // namespace rf
@@ -154,8 +157,12 @@ struct rf_plan {
     hipEvent_t done = nullptr;
 
     ~rf_plan();
-    void *alloc(size_t bytes, bool zero, int *status);
-    void *upload(const void *host, size_t bytes, int *status);
+    void *alloc(size_t bytes, bool zero, int *status);                 // workspace: RF_BUFFER_ZEROED / RF_BUFFER_SCRATCH
+    void *upload(const void *host, size_t bytes, int *status);         // RF_BUFFER_TABLE
+    void *alloc_kind(size_t bytes, int kind, int *status);
+    // every device buffer an execute of this instance uses: its own, then those of its cascade / staging stages and of its
+    // helper plans, depth first (rf_plan_debug_buffer's index)
+    void all_buffers(std::vector<const rf::DeviceBuffer *> &into) const;
     int finish_build();      // waits for the uploads and zero fills (the build stream), creates `done`
 };
 

@@ -188,6 +188,26 @@ class Plan:
                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n.value, None))
         return out
 
+    # -- debugging aids ---------------------------------------------------------------------
+    def debug_buffers(self) -> List[Tuple[int, str, int]]:
+        """[(index, kind, bytes)] of every device buffer an execute of the plan's first instance uses, child plans included
+        (rf_plan_debug_buffer / rf_plan_debug_buffer_kind); kind is "table", "zeroed" or "scratch".  A host-only plan lists
+        what it would have allocated."""
+        L, out, i = capi.lib(), [], 0
+        n, kind = ctypes.c_size_t(), ctypes.c_int()
+        while L.rf_plan_debug_buffer(self._h, i, None, ctypes.byref(n)) == capi.RF_OK:
+            capi.check(L.rf_plan_debug_buffer_kind(self._h, i, ctypes.byref(kind)))
+            out.append((i, capi.BUFFER_KIND_NAMES[kind.value], int(n.value)))
+            i += 1
+        return out
+
+    def debug_fill(self, index: int, byte: int, stream=None) -> None:
+        """rf_plan_debug_fill: every byte of buffer `index` becomes `byte`, on `stream` (default: torch's current stream).
+        Raises for a table.  Scratch may hold anything before an execute; a zeroed buffer filled with non-zero bytes breaks
+        the plan."""
+        host_only = self._desc.device == capi.RF_DEVICE_HOST_ONLY       # (refused by the library; there is no stream to ask torch for)
+        capi.check(capi.lib().rf_plan_debug_fill(self._h, int(index), int(byte), ctypes.c_void_p() if host_only else self._stream(stream)))
+
     # -- execution --------------------------------------------------------------------------
     def _pointers(self, tensors, inputs: bool = False) -> ctypes.Array:
         if len(tensors) != self.planes:
