@@ -57,19 +57,6 @@ int set_context(rf_plan *plan, const void *const *in_planes, void *const *out_pl
     return RF_OK;
 }
 
-// every step of a single-device execute, in order
-std::vector<const Step *> flat_steps(const rf_plan *plan) {
-    std::vector<const Step *> v;
-    for (const Step &s : plan->begin_steps) v.push_back(&s);
-    for (const auto &ex : plan->exchange_local_steps)
-        for (const Step &s : ex) v.push_back(&s);
-    for (const Step &s : plan->interior_steps) v.push_back(&s);
-    for (const auto &ex : plan->exchange_apply_steps)         // (non-empty only for plans built with the exchange structure)
-        for (const Step &s : ex) v.push_back(&s);
-    for (const Step &s : plan->finish_steps) v.push_back(&s);
-    return v;
-}
-
 // ---- concurrent executions -------------------------------------------------------------------------------------------
 // The instance of `plan` an execution on `stream` runs on, OWNED by the calling thread (plan.h): the instance that last ran
 // on this stream (stream order separates the two executions); else one whose last execution has finished; else a new
@@ -198,7 +185,7 @@ int rf_plan_tiles(const rf_plan *plan, int32_t tile_out[RF_MAX_DIMS]) {
     return RF_OK;
 }
 
-int rf_plan_num_kernels(const rf_plan *plan) { return plan ? (int)flat_steps(plan).size() : 0; }
+int rf_plan_num_kernels(const rf_plan *plan) { return plan ? (int)single_device_steps(plan).size() : 0; }
 int rf_plan_num_exchanges(const rf_plan *plan) { return plan ? (int)plan->exchanges.size() : 0; }
 
 int rf_plan_execute(rf_plan *plan, const void *const *in_planes, void *const *out_planes, void *stream) {
@@ -211,7 +198,7 @@ int rf_plan_execute(rf_plan *plan, const void *const *in_planes, void *const *ou
     const bool context_set = rc == RF_OK;        // from here on launches are attempted on inst->stream
     if (rc == RF_OK) {
         for (auto &ex : inst->exchanges) ex.send = ex.scratch;
-        for (const Step *st : flat_steps(inst)) {
+        for (const Step *st : single_device_steps(inst)) {
             for (int pl = 0; pl < inst->n_planes && rc == RF_OK; pl++) rc = st->run(pl);
             if (rc != RF_OK) break;
         }
@@ -234,7 +221,7 @@ int rf_plan_execute_timed(rf_plan *plan, const void *const *in_planes, void *con
     int rc = set_context(inst, in_planes, out_planes, stream);
     if (rc) return rc;
     for (auto &ex : inst->exchanges) ex.send = ex.scratch;
-    auto steps = flat_steps(inst);
+    auto steps = single_device_steps(inst);
     if (capacity < (int)steps.size() || !ms_out) { set_error("ms_out too small: need %zu", steps.size()); return RF_ERR_INVALID_ARG; }
     // events are destroyed on every return path; outputs are fully written even when a step fails
     struct Events {
@@ -242,7 +229,7 @@ int rf_plan_execute_timed(rf_plan *plan, const void *const *in_planes, void *con
         ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
     } events;
     // (names: the primary's steps have the same names and live as long as the plan)
-    auto names = flat_steps(plan);
+    auto names = single_device_steps(plan);
     for (size_t i = 0; i < steps.size(); i++) {
         ms_out[i] = 0.0f;
         if (names_out) names_out[i] = names[i]->name.c_str();

@@ -168,4 +168,33 @@ struct rf_plan {
 
 namespace rf {
 int build_plan(const rf_filter_desc *desc, rf_plan **out);
+
+// every step of a single-device execute, in order: begin, exchange_local, interior, exchange_apply (plans built with the
+// exchange structure; left out where !with_apply), finish
+std::vector<const Step *> single_device_steps(const rf_plan *plan, bool with_apply = true);
+
+// ---- a plan driven by another plan (plan.cpp) --------------------------------------------------------------------------
+// A wrapper -- the in-plan cascade, the clamped 1-D form, a staged 16-bit plan, the carry-plane helper of a z stage -- builds an
+// unsharded child plan, owns it (rf_plan::stages / helpers) and runs the child's steps as steps of its own.  The child's Steps
+// are referenced BY POINTER into the child's step vectors: nothing touches those vectors once the child is built.
+//   child_steps         the step list of a child; a sharded child is refused (its steps need the stepping calls)
+//   bind_child          the child's per-execute context: planes(q) = plane q's {input, output}, and the parent's stream
+//   append_child_steps  `steps` as begin steps of the parent, named prefix + name; the first binds the context when it runs
+//                       for plane 0 (a batched child launches all its planes from plane 0)
+//   take_over_child     the child's workspace counts as the parent's and its exchanges send into their own scratch (single
+//                       device); `shown`: rf_plan_tiles / rf_plan_table of the parent report this child's
+struct ChildPlanes { const void *in; void *out; };
+int child_steps(const rf_plan *child, std::vector<const Step *> &steps);
+template <typename F>
+void bind_child(rf_plan *child, int n_planes, hipStream_t stream, F &&planes) {
+    for (int q = 0; q < n_planes; q++) {
+        const ChildPlanes p = planes(q);
+        child->in[q] = child->orig_in[q] = p.in;
+        child->out[q] = p.out;
+    }
+    child->stream = stream;
+}
+void append_child_steps(rf_plan *parent, rf_plan *child, const std::vector<const Step *> &steps, const std::string &prefix,
+                        std::function<ChildPlanes(int plane)> planes);
+void take_over_child(rf_plan *parent, rf_plan *child, bool shown);
 }

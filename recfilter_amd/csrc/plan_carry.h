@@ -284,32 +284,30 @@ struct CarryStage {
 };
 
 // The step "carry_planes_xy": a helper plan (the x/y filter F over carry planes, plan_strided.h) run on plane pl's carry
-// planes, `tails + pl * stride`, in place.  ONE step: the helper has one workspace, so its launches for a plane run back to
-// back (the steps of an execute run plane by plane inside every step).  The plan takes the helper over.
+// planes, `tails + pl * stride`, in place, appended to `into`.  ONE step: the helper has one workspace, so its launches for a
+// plane run back to back (the steps of an execute run plane by plane inside every step).  The plan takes the helper over
+// (plan.h, "a plan driven by another plan").
 template <typename Acc>
-Step adopt_carry_planes_plan(rf_plan *plan, std::unique_ptr<rf_plan> helper, Acc *tails, size_t stride) {
+int adopt_carry_planes_plan(rf_plan *plan, std::unique_ptr<rf_plan> helper, Acc *tails, size_t stride, std::vector<Step> &into) {
     rf_plan *child = helper.get();
-    plan->helpers.push_back(std::move(helper));
-    plan->workspace_bytes += child->workspace_bytes;
     std::vector<const Step *> steps;
-    for (const Step &s : child->begin_steps) steps.push_back(&s);
-    for (const auto &ex : child->exchange_local_steps)
-        for (const Step &s : ex) steps.push_back(&s);
-    for (const Step &s : child->finish_steps) steps.push_back(&s);
+    if (int rc = child_steps(child, steps)) return rc;
+    plan->helpers.push_back(std::move(helper));
+    take_over_child(plan, child, false);
     Step w;
     w.name = "carry_planes_xy";
     w.run = [plan, child, steps, tails, stride](int pl) {
         // the helper's context: this plane's run of carry planes, filtered in place
-        child->in[0] = child->orig_in[0] = tails + (size_t)pl * stride;
-        child->out[0] = tails + (size_t)pl * stride;
-        child->stream = plan->stream;
+        Acc *planes = tails + (size_t)pl * stride;
+        bind_child(child, 1, plan->stream, [planes](int) { return ChildPlanes{planes, planes}; });
         for (const Step *sp : steps) {
             const int rc = sp->run(0);
             if (rc != RF_OK) return rc;
         }
         return (int)RF_OK;
     };
-    return w;
+    into.push_back(w);
+    return RF_OK;
 }
 
 }  // namespace rf

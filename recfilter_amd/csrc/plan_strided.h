@@ -179,11 +179,12 @@ int add_strided_dimension(rf_plan *plan, int d, bool from_input, const rf_filter
 
     if (!sharded) {
         stage.add_local_carry(plan, "carry_" + dn);
-        if (walk) plan->begin_steps.push_back(adopt_carry_planes_plan<Acc>(plan, std::move(child), c.tails, c.tails_stride));
+        if (walk)
+            if (int rc = adopt_carry_planes_plan<Acc>(plan, std::move(child), c.tails, c.tails_stride, plan->begin_steps)) return rc;
     } else if (merged_exchange_applies(n, K, plan->shard_world)) {
         int rc = add_merged_exchange<S, Acc>(plan, stage, "carry_" + dn);
+        if (rc == RF_OK && early) rc = adopt_carry_planes_plan<Acc>(plan, std::move(child), c.tails, c.tails_stride, plan->exchange_apply_steps.back());
         if (rc != RF_OK) return rc;
-        if (early) plan->exchange_apply_steps.back().push_back(adopt_carry_planes_plan<Acc>(plan, std::move(child), c.tails, c.tails_stride));
     } else {
         int rc = stage.add_per_scan_carries(plan, "carry_" + dn, "carry_apply_" + dn, true);
         if (rc != RF_OK) return rc;

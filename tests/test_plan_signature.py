@@ -18,7 +18,7 @@ with open(os.path.join(HERE, "golden", "plan_signature.json")) as f:
 
 def test_the_golden_file_covers_the_case_list():
     assert sorted(GOLDEN) == sorted(name for name, _ in ps.CASES)
-    assert len(GOLDEN) >= 250
+    assert len(GOLDEN) >= 320
 
 
 @pytest.mark.parametrize("name,kw", ps.CASES, ids=[name for name, _ in ps.CASES])

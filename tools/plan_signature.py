@@ -191,6 +191,72 @@ def _cases():
     add("overlap_3d_tile8", (64, 64, 64), CFG5, path=OVERLAP, tile=(8, 8, 8))
     add("overlap_3d_tile16_clamped_f64", (64, 64, 64), CFG5, clamped=True, path=OVERLAP, tile=(16, 16, 16), dtype="float64")
     add("overlap_2d_i32", (256, 256), [(X, C, SUM1), (Y, C, SUM1)], path=OVERLAP, tile=(32, 32), dtype="int32")
+    # ---- the decisions of build_plan itself (plan.cpp): every stage, every wrapper, every refusal ------------------------
+    bq, first = [0.05, 1.6, -0.7], [0.5, 0.5]
+    NO_CASCADE, MATRIX, UNTILED = capi.RF_PLAN_NO_CASCADE, capi.RF_PATH_TILED_MATRIX, capi.RF_PATH_UNTILED
+    # the in-plan cascade
+    add("cascade1d_5_biquads_1000000", (1_000_000,), [(X, C, bq)] * 5, flags=TILED)
+    add("cascade1d_9_biquads_1000000", (1_000_000,), [(X, C, bq)] * 9, flags=TILED)
+    add("cascade1d_padded_pair_100000", (100_000,), [(X, C, bq), (X, A, bq)], flags=TILED)
+    add("cascade2d_six_x_one_y_clamped", (256, 512), [(X, C, first)] * 6 + [(Y, A, [0.6, 0.4])], clamped=True, flags=TILED)
+    add("cascade_refused_input_epilogue", (256, 512), [(X, C, first)] * 5, flags=TILED, epilogue=(1.0, 1.0, 0.0))
+    add("cascade_off_1000000", (1_000_000,), [(X, C, bq)] * 5, flags=TILED | NO_CASCADE)
+    add("cascade_off_forced_fused_refused", (1_000_000,), [(X, C, bq)] * 5, path=FUSED, flags=NO_CASCADE)
+    add("cascade_forced_fused_64sq", (64, 64), [(X, C, first)] * 5, path=FUSED)
+    add("cascade_forced_fused_stage_refused", (256, 512), [(X, C, ORDER9)] * 2, path=FUSED)
+    # clamped 1-D signals
+    add("clamped1d_over_cascade_100000", (100_000,), [(X, C, bq)] * 5, clamped=True, flags=TILED)
+    add("clamped1d_running_sum_refused", (100_000,), [(X, C, SUM1)], clamped=True, flags=TILED)
+    # merged runs
+    r, th = 0.9995, 0.01
+    slow = [1e-3, 2 * r * math.cos(th), -r * r]
+    mild = [(X, C, [0.5, 0.3, 0.1]), (X, C, [0.8, 0.2]), (X, C, [0.7, 0.2, -0.1]), (X, A, [0.6, 0.3]), (X, A, [0.9, 0.1, 0.05]),
+            (X, A, [0.6, 0.4])]
+    add("merged_five_fast_2p20", (1 << 20,), [(X, C, [1.0, 0.1, 0.1])] * 5)
+    add("merged_refused_slow_poles_2p20", (1 << 20,), [(X, C, slow)] * 2)
+    add("merged_kept_as_given_2p20", (1 << 20,), mild)
+    # the matrix path and the automatic choice
+    add("matrix1d_order15_2p16", (1 << 16,), [(X, C, [1.0] + [0.01] * 15)])
+    add("matrix1d_order5_one_scan_2p20", (1 << 20,), [(X, C, ORDER5)])
+    add("matrix1d_order5_one_scan_clamped_2p20", (1 << 20,), [(X, C, ORDER5)], clamped=True)
+    add("matrix2d_order9_y_96x160", (96, 160), [(Y, A, ORDER9)], clamped=True)
+    add("matrix_forced_refused_100x162", (100, 162), [(X, A, ORDER9)], path=MATRIX)
+    add("auto_order9_generic_100x162", (100, 162), [(X, A, ORDER9)])
+    add("auto_order9_untiled_101x103", (101, 103), [(X, C, ORDER9)])
+    add("auto_lines_512sq", (512, 512), xy_pm(GAUSS2), clamped=True)
+    add("auto_lines_order3_1920sq", (1920, 1920), xy_pm(GAUSS3), clamped=True)
+    add("auto_overlap_five_x_tile32", (512, 512), [(X, C, first)] * 5 + [(Y, C, first)], tile=(32, 32), flags=NO_CASCADE)
+    add("untiled_serial_100sq", (100, 100), xy_pm(GAUSS2), path=UNTILED, flags=capi.RF_PLAN_SERIAL_UNTILED)
+    add("untiled_no_scans_auto", (64, 64), [])
+    add("untiled_no_scans_forced", (64, 64), [], path=UNTILED)
+    add("untiled_1d_f64_10007", (10007,), [(X, C, GAUSS2)], dtype="float64")
+    add("forced_overlap_refused_no_tiles", (512, 512), xy_pm(GAUSS2), path=OVERLAP)
+    add("forced_fused_refused_f64_order9", (256, 512), [(X, C, ORDER9)], path=FUSED, dtype="float64")
+    # 16-bit pixels: staged and native
+    add("staged_f16_lines_1d_4099", (4099,), [(X, C, GAUSS2)], dtype="float16")
+    add("staged_f16_two_planes_300x1001", (300, 1001), xy_pm(GAUSS2), clamped=True, dtype="float16", flags=TILED,
+        epilogue=(-0.5, 1.5, 0.0))
+    add("staged_f16_width_302", (100, 302), xy_pm(GAUSS2), clamped=True, dtype="float16")
+    add("staged_bf16_over_cascade_1000000", (1_000_000,), [(X, C, bq)] * 5, dtype="bfloat16", flags=TILED)
+    add("staged_f16_over_generic_256x512", (256, 512), [(Y, C, first)] * 5, dtype="float16", flags=TILED, epilogue=(1.0, 1.0, 0.0))
+    add("staged_f16_vol_64x96x128", (64, 96, 128), CFG5, dtype="float16")
+    add("native_f16_vol_forced_64x96x128", (64, 96, 128), CFG5, dtype="float16", path=FUSED)
+    add("native_f16_vol_128x256x256", (128, 256, 256), CFG5, dtype="float16")
+    add("staged_f16_vol_fused_builder_refused", (100, 256, 256), CFG5, dtype="float16", path=FUSED)
+    add("staged_f16_vol_sharded_refused", (128, 256, 256), CFG5, dtype="float16", shard_rank=0, shard_world=2)
+    # clamped sections
+    add("sections_order5_256x512_x3", (256, 512), xy_pm(ORDER5), clamped=True, flags=TILED, planes=3)
+    add("sections_off_zero_2048sq", (2048, 2048), xy_pm(ORDER5), clamped=False, flags=TILED | capi.RF_PLAN_NO_SECTIONS)
+    # stand-alone pointwise steps
+    add("pointwise_generic_f64", (320, 480), xy_pm(GAUSS2), clamped=True, path=GENERIC, tile=(32, 32), dtype="float64",
+        prologue=(2.0, -0.5), epilogue=(1.0, 0.5, 0.25))
+    add("pointwise_generic_u8", (320, 480), xy_pm(GAUSS2), clamped=True, path=GENERIC, tile=(32, 32), input_dtype=np.uint8,
+        prologue=(1.0 / 255.0, 0.0), epilogue=(1.0, 0.5, 0.0))
+    # refusals of the validation
+    add("refused_tile_not_a_divisor", (100, 100), xy_pm(GAUSS2), tile=(32, 32))
+    add("refused_unknown_path", (64, 64), xy_pm(GAUSS2), path=9)
+    add("refused_stream_and_staged_pass1", (512, 512), xy_pm(GAUSS2), path=FUSED,
+        flags=capi.RF_PLAN_STREAM_PASS1 | capi.RF_PLAN_STAGED_PASS1)
     return cases
 
 
