@@ -97,6 +97,10 @@ struct RecFilterImageRef {
  *  own (scaled) input -- the unsharp mask `(1+w)*I - w*Blur` of apps/usm/unsharp_mask_optimized.cpp:57. */
 struct RecFilterPointwise {
     float w_filtered = 1.0f, w_input = 0.0f, bias = 0.0f;
+    /** the consumer is `cast<uint8_t>(...)` of that expression (a filter defined on a uint8 image only): realize() returns
+     *  planes of unsigned bytes, each min(max(rint(v), 0), 255) of the float value v, converted once as the final pass stores
+     *  it (rf_pointwise_desc.in_dtype = RF_IO_U8) */
+    bool to_bytes = false;
 };
 template <typename T>
 RecFilterImageRef RecFilterImage(const T *device_ptr) { return RecFilterImageRef{device_ptr, RecFilterPixel<T>::dtype}; }
@@ -114,6 +118,8 @@ struct RecFilterRealization {
     std::vector<int64_t> extent;   // x first
     int dtype = RF_F32;
     size_t bytes_per_plane = 0;
+    /** the planes hold unsigned bytes (a RecFilterPointwise::to_bytes consumer): read them with to_host<uint8_t>() */
+    bool bytes = false;
     /** copy plane i to host memory */
     template <typename T> std::vector<T> to_host(size_t i = 0) const {
         std::vector<T> h(bytes_per_plane / sizeof(T));
@@ -184,6 +190,7 @@ class RecFilter {
         std::vector<Scan> scans;
         std::map<std::string, int> tile;
         bool clamped = false, tiled = false, compiled = false, has_consumer = false;
+        bool out_bytes = false;        // the planes realize() returns hold unsigned bytes (RecFilterPointwise::to_bytes)
         bool merged = false;                     // the plan holds the scans of the whole cascade this stage ends (compile_jit)
         bool merge_at_compile = true;            // merge_cascades() when the plan was built (toggled since: execute_chain plans again)
         RecFilterPointwise consumer;
@@ -476,7 +483,10 @@ public:
         d.shard_extents = c->shard_extents.empty() ? nullptr : c->shard_extents.data();
         d.flags = c->plan_flags;
         // (the defining expression belongs to the stage that reads the image: this one, or the head of the merged cascade)
-        if (!head->source && !head->inputs.empty() && head->inputs[0].bytes) d.pointwise.in_dtype = RF_IN_U8;
+        const bool head_bytes = !head->source && !head->inputs.empty() && head->inputs[0].bytes;
+        c->out_bytes = c->has_consumer && c->consumer.to_bytes;
+        if (c->out_bytes && !head_bytes) fail("a consumer that stores bytes needs a filter defined on a uint8 image, run as one plan");
+        if (head_bytes) d.pointwise.in_dtype = c->out_bytes ? RF_IO_U8 : RF_IN_U8;
         if (!head->source && !head->inputs.empty() && (head->inputs[0].scale != 1.0f || head->inputs[0].bias != 0.0f)) {
             d.pointwise.flags |= RF_POINTWISE_PRE;
             d.pointwise.pre_scale = head->inputs[0].scale; d.pointwise.pre_bias = head->inputs[0].bias;
@@ -504,7 +514,7 @@ public:
             for (auto &i : head->inputs) in.push_back(i.ptr);
         } else if (c->source) { RecFilter up(c->source); up.execute_chain(); for (void *p : up.c->out) in.push_back(p); }
         else for (auto &i : c->inputs) in.push_back(i.ptr);
-        const size_t bytes = plane_elems() * dtype_size(dtype());
+        const size_t bytes = out_plane_bytes();
         if (c->out.size() != in.size()) {
             for (void *p : c->out) (void)hipFree(p);
             c->out.assign(in.size(), nullptr);
@@ -512,6 +522,8 @@ public:
         }
         if (rf_plan_execute(c->plan, in.data(), c->out.data(), c->stream) != RF_OK) fail(rf_last_error_string());
     }
+    /** bytes of one output plane: the pixel type's, or one per sample behind a to_bytes consumer */
+    size_t out_plane_bytes() const { return plane_elems() * (c->out_bytes ? 1 : dtype_size(dtype())); }
 
     /** Not in the reference (it has no multi-device path): this object filters ONE rank's slab of an image that is
      *  partitioned along its outermost dimension over `world` GPUs, one process (or thread) per GPU.  The extents of the
@@ -618,7 +630,7 @@ public:
     RecFilterRealization enqueue() {
         execute_chain();
         RecFilterRealization r;
-        r.planes = c->out; r.dtype = dtype(); r.bytes_per_plane = plane_elems() * dtype_size(dtype());
+        r.planes = c->out; r.dtype = dtype(); r.bytes_per_plane = out_plane_bytes(); r.bytes = c->out_bytes;
         for (auto &dm : c->dims) r.extent.push_back(dm.num_pixels());
         return r;
     }
@@ -628,7 +640,7 @@ public:
         execute_chain();
         if (hipDeviceSynchronize() != hipSuccess) fail("device synchronisation failed");
         RecFilterRealization r;
-        r.planes = c->out; r.dtype = dtype(); r.bytes_per_plane = plane_elems() * dtype_size(dtype());
+        r.planes = c->out; r.dtype = dtype(); r.bytes_per_plane = out_plane_bytes(); r.bytes = c->out_bytes;
         for (auto &dm : c->dims) r.extent.push_back(dm.num_pixels());
         return r;
     }

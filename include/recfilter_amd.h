@@ -117,8 +117,22 @@ typedef struct {
 #define RF_POINTWISE_POST  2
 /* element type of the INPUT planes: the pixel type (default), or unsigned bytes converted on load -- the
  * `cast<float>(input(x,y,c)) / 255.0f` of demo/demo_gaussian_filter.cpp:51-53 with the uint8 image read directly
- * (1 byte per sample instead of 4 in both passes).  RF_IN_U8 needs dtype RF_F32; outputs stay f32. */
-typedef enum { RF_IN_PIXEL = 0, RF_IN_U8 = 1 } rf_input_dtype;
+ * (1 byte per sample instead of 4 in both passes).  RF_IN_U8 needs dtype RF_F32; outputs stay f32.
+ *
+ * RF_IO_U8: input AND output planes hold unsigned bytes -- a STORAGE type under the contract of RF_F16 / RF_BF16 above.  dtype
+ * must be RF_F32; the filter is the RF_F32 plan of the same description with RF_IN_U8 (bytes widened on load; prologue, tails,
+ * carries, tables and epilogue are that plan's); no intermediate ever passes through a byte plane; the result is converted
+ * ONCE, at the final store:  out = sat8(v),  sat8(v) = (uint8) min(max(rint(v), 0), 255),  v the f32 value behind the epilogue
+ * (post_filtered * F(x') + post_input * x' + post_bias, or F(x') without one).  rint rounds to nearest, ties to even; values
+ * below 0 store 0, values above 255 store 255, NaN stores 0 -- the reference's consumer cast<uint8_t>(...) computed at the filter.
+ * 2-D images whose width is a multiple of 4, with orders <= 3 and at most four scans per dimension, run natively on
+ * RF_PATH_TILED_FUSED: the launch list is the RF_IN_U8 plan's, name for name, and its final pass stores the bytes (3 bytes of
+ * image traffic per sample instead of 6 and a conversion pass).  Every other plan the RF_IN_U8 plan can run is staged: that
+ * plan writes plan-owned f32 planes (counted in rf_plan_workspace_bytes, listed as scratch by rf_plan_debug_buffer), one step
+ * "convert_out" follows; rf_plan_path reports the inner plan's path.  in == out is allowed (an epilogue with post_input != 0
+ * needs out != in, as everywhere).  Planes on both sides must be 4-byte aligned.  Any other dtype, sharded plans and
+ * RF_PLAN_FORCE_EXCHANGE: RF_ERR_UNSUPPORTED. */
+typedef enum { RF_IN_PIXEL = 0, RF_IN_U8 = 1, RF_IO_U8 = 2 } rf_input_dtype;
 typedef struct {
     int32_t flags;                    /* RF_POINTWISE_PRE | RF_POINTWISE_POST */
     float   pre_scale, pre_bias;
@@ -183,7 +197,9 @@ typedef struct {
  *                           at most 2^-32 of the largest carry (rf_plan_table("neighbour_carries")).
  *   RF_PLAN_STAGE_HALF      RF_F16 / RF_BF16 pixels: the plan is staged through f32 planes even where the fused kernels
  *                           would run it natively -- 2-D images, 1-D signals and volumes alike (same result to the last
- *                           rounding; for comparisons).  Ignored for the other pixel types. */
+ *                           rounding; for comparisons).  RF_IO_U8 planes (rf_input_dtype): the plan is staged through f32
+ *                           planes and "convert_out" even where the fused final pass would store the bytes itself.  Ignored
+ *                           for every other plan. */
 #define RF_PLAN_FORCE_EXCHANGE  0x01u
 #define RF_PLAN_TILED_ONLY      0x02u
 #define RF_PLAN_NO_CASCADE      0x04u
@@ -264,7 +280,7 @@ int rf_plan_num_kernels(const rf_plan *plan);
  * in_planes/out_planes: n_planes device pointers each.  in == out (same pointers) is allowed.  A plan whose kernels
  * move 16 bytes per lane -- the fused path (rf_plan_path() == RF_PATH_TILED_FUSED) and the line-parallel untiled
  * kernels RF_PATH_AUTO / RF_PATH_UNTILED use for orders <= 3 with extents that are multiples of 16 -- needs 16-byte
- * aligned planes (4-byte for RF_IN_U8 input planes) and returns RF_ERR_INVALID_ARG otherwise (hipMalloc and torch
+ * aligned planes (4-byte for RF_IN_U8 input planes and for both sides of RF_IO_U8) and returns RF_ERR_INVALID_ARG otherwise (hipMalloc and torch
  * allocations are 256-byte aligned; only offset views are affected).  The generic and overlapped tiled paths take any
  * element-aligned pointer. */
 int rf_plan_execute(rf_plan *plan, const void *const *in_planes, void *const *out_planes,

@@ -26,7 +26,7 @@ RF_OK, RF_ERR_INVALID_ARG, RF_ERR_UNSUPPORTED, RF_ERR_HIP, RF_ERR_NOMEM, RF_ERR_
 RF_F32, RF_F64, RF_I32, RF_I16, RF_F16, RF_BF16 = range(6)      # RF_F16 / RF_BF16: 16-bit float STORAGE, f32 arithmetic
 RF_BORDER_ZERO, RF_BORDER_CLAMP = 0, 1
 RF_POINTWISE_PRE, RF_POINTWISE_POST = 1, 2
-RF_IN_PIXEL, RF_IN_U8 = 0, 1
+RF_IN_PIXEL, RF_IN_U8, RF_IO_U8 = 0, 1, 2      # rf_input_dtype; RF_IO_U8: byte planes on both sides, out = sat8(f32 result)
 RF_BUFFER_TABLE, RF_BUFFER_ZEROED, RF_BUFFER_SCRATCH = range(3)      # rf_buffer_kind (rf_plan_debug_buffer_kind)
 BUFFER_KIND_NAMES = {RF_BUFFER_TABLE: "table", RF_BUFFER_ZEROED: "zeroed", RF_BUFFER_SCRATCH: "scratch"}
 RF_PATH_AUTO, RF_PATH_UNTILED, RF_PATH_TILED_GENERIC, RF_PATH_TILED_FUSED, RF_PATH_TILED_OVERLAPPED, RF_PATH_TILED_MATRIX = range(6)

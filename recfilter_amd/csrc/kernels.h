@@ -42,6 +42,8 @@ int launch_pointwise_from(const P *f, const X *x, P *dst, int64_t n, double c0, 
 // ---- conversion of a plane between a 16-bit float storage type (_Float16, __bf16) and f32 (staged 16-bit plans) ----
 template <typename D, typename S>
 int launch_convert(const S *src, D *dst, int64_t n, hipStream_t stream);
+// f32 plane -> unsigned bytes, sat8 (pixel.h): the one conversion of a staged RF_IO_U8 plan; any element alignment
+int launch_convert_sat8(const float *src, uint8_t *dst, int64_t n, hipStream_t stream);
 
 // ---- finite differences of summed-area tables (rf_box_difference) ----
 struct BoxDiffArgs {

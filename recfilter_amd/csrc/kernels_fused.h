@@ -197,6 +197,11 @@ int launch_fused_pass2(int K, int TY, const void *src, int src_kind, P *dst, con
 template <typename P>
 int launch_fused_pass2_tall(int K, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                             hipStream_t stream);
+// the same two passes from unsigned-byte planes to unsigned-byte planes (rf_pointwise_desc.in_dtype == RF_IO_U8): the f32
+// arithmetic of the kSrcU8 instances, the result converted once as it is stored (sat8, pixel.h).  FusedArgs::row_bytes is that
+// of the byte rows (NX); unsharded 2-D images, no sections, no folded signals.
+int launch_fused_pass2_u8(int K, int TY, const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream);
+int launch_fused_pass2_tall_u8(int K, const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream);
 // pass 1 as a contraction with precomputed impulse responses (kernels_tails.hip)
 template <typename P>
 int launch_fused_tails(int K, int TY, const void *src, bool src_u8, const FusedArgs<typename PixelTraits<P>::Acc> &a,

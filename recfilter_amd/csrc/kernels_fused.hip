@@ -300,6 +300,8 @@ fused_pass2_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<ty
             constexpr bool EARLY = YPAT > 2;
             char *dpb_early = reinterpret_cast<char *>(dst + tile_off);
             // (with the pointwise epilogue applied on the way out: EPI has this thread's input column in registers)
+            Acc hq0 = Acc(0), hq1 = Acc(0), hq2 = Acc(0), hq3 = Acc(0);      // byte pixels, packed form: the rows of a block of four
+            (void)hq0; (void)hq1; (void)hq2; (void)hq3;
             Acc held = Acc(0);
             (void)held;
             auto row_out = [&](int m, Acc v) __attribute__((always_inline)) {
@@ -307,6 +309,12 @@ fused_pass2_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<ty
                     if constexpr (EPI) v = a.post_f * v + (a.post_i * orig[m] + a.post_b);
                     else if (a.pw_flags & 2) v = a.post_f * v + a.post_b;
                 }
+                if constexpr (packed_bytes<P>::value) {
+                    // byte pixels, packed form: four rows at a time, one dword per lane (scan_device.h, store_row_quad)
+                    if ((m & 3) == 0) hq0 = v; else if ((m & 3) == 1) hq1 = v; else if ((m & 3) == 2) hq2 = v; else hq3 = v;
+                    if ((m & 3) == (PAT == 2 ? 0 : 3))
+                        store_row_quad(dpb_early, (uint32_t)t, (uint32_t)(m & ~3), a.row_bytes, hq0, hq1, hq2, hq3, (uint32_t)TY);
+                } else
                 if constexpr (packed_stores<P>::value) {
                     // 16-bit float pixels: two rows at a time, one dword per lane (scan_device.h, store_row_pair); the scan
                     // hands the rows over in its own direction, so the first row of a pair waits for the second
@@ -394,6 +402,12 @@ fused_pass2_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<ty
                 my_rows = left < (int64_t)rows_here ? (int)left : rows_here;
             }
             if (t < last_cols) {
+                if constexpr (packed_bytes<P>::value && !LIN) {
+                    // (byte pixels, packed form: last_cols is a multiple of 4, so a quad of columns is stored or not as one)
+#pragma unroll
+                    for (int i = 0; i < TY; i += 4)
+                        store_row_quad(dpb, (uint32_t)t, (uint32_t)i, row_bytes, col[i], col[i + 1], col[i + 2], col[i + 3], (uint32_t)my_rows);
+                } else
                 if constexpr (packed_stores<P>::value && !LIN) {
                     // (16-bit float pixels, scan_device.h: last_cols is a multiple of 4, so a column pair is stored or not as one;
                     // rows_here is tile-uniform)
@@ -520,6 +534,34 @@ static int launch_fused_pass2_widen(int K, int TY, const PI *src, float *dst, co
         if (edge) return launch_fused_pass2_impl<float, KK, TT, false, true, PI>(src, dst, a, stream);          \
         if (pair) return launch_fused_pass2_impl<float, KK, TT, false, false, PI, 4, true>(src, dst, a, stream); \
         return launch_fused_pass2_impl<float, KK, TT, false, false, PI>(src, dst, a, stream);                   \
+    }
+    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
+    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
+#undef RF_CASE
+    set_error("fused path: unsupported order %d / tile height %d", K, TY);
+    return RF_ERR_UNSUPPORTED;
+}
+
+// Unsigned bytes in, unsigned bytes out (rf_pointwise_desc.in_dtype == RF_IO_U8): the f32 arithmetic of the RF_IN_U8 instances
+// with a byte destination -- PixelTraits<uint8_t>::store is sat8 (pixel.h), applied to the value behind the epilogue as a row
+// leaves.  Three instances per order and tile height: partial tiles; whole tiles with the usual pair of scans in both
+// dimensions and rows leaving from inside the last scan (an affine epilogue is applied on the way out); the general-pattern
+// code for everything else (an epilogue's input operand comes back through the caches, as for the 16-bit types).
+int launch_fused_pass2_u8(int K, int TY, const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream) {
+    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
+    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    if (a.lin_limit > 0 || a.mod_form || a.y_nb_W != nullptr || a.y_apply != nullptr || a.row_bytes != (uint32_t)a.NX) {
+        set_error("fused pass 2: byte planes on both sides are an unsharded 2-D image of orders <= 3 with a row pitch of NX bytes");
+        return RF_ERR_INVALID_ARG;
+    }
+    const bool edge = a.last_cols != kFusedTX || a.last_rows != TY;
+    const bool pair = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0 && a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
+    const bool early = (a.pw_flags & 2) == 0 || a.post_i == 0.0f;
+#define RF_CASE(KK, TT)                                                                                         \
+    if (K == KK && TY == TT) {                                                                                  \
+        if (edge) return launch_fused_pass2_impl<uint8_t, KK, TT, false, true, uint8_t>(src, dst, a, stream);   \
+        if (pair && early) return launch_fused_pass2_impl<uint8_t, KK, TT, false, false, uint8_t, 4, true>(src, dst, a, stream); \
+        return launch_fused_pass2_impl<uint8_t, KK, TT, false, false, uint8_t>(src, dst, a, stream);            \
     }
     RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
     RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)

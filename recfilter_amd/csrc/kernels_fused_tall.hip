@@ -25,7 +25,8 @@ constexpr int kHalfRows = 64;
 // YPAT: the directions of the y scans when they are the usual ones -- 1: one causal scan, 2: causal then anticausal; 0: any
 // (a run-time direction inside the loop over the scans makes every sample of the column a phi of two register
 // assignments: a hundred and more register copies per scan and, on a 128-sample column, spills).
-// EARLY (whole tiles, one of the fixed patterns, no epilogue): the rows are stored from inside the last scan.
+// EARLY (whole tiles, one of the fixed patterns, no epilogue -- byte planes: none with an input operand): the rows are stored from
+// inside the last scan.
 // XFIX: the x scans have the same pattern as the y scans (YPAT), fixed at compile time as well.
 template <typename P, int K, bool EDGE, typename PI, int YPAT, bool EARLY, bool XFIX>
 __global__ void __launch_bounds__(kFusedThreads, 2)
@@ -324,9 +325,22 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     // whole tiles without an epilogue: the rows are stored from inside the last scan, each as soon as it is final
     char *dpb_early = reinterpret_cast<char *>(dst + tile_off);
     static_assert(!EARLY || (!EDGE && YPAT > 0), "early stores: whole tiles, fixed scan pattern");
+    Acc hq0 = Acc(0), hq1 = Acc(0), hq2 = Acc(0), hq3 = Acc(0);      // byte pixels, packed form: the rows of a block of four
+    (void)hq0; (void)hq1; (void)hq2; (void)hq3;
     Acc held = Acc(0);
     (void)held;
     auto row_out = [&](int m, Acc v) __attribute__((always_inline)) {
+        // (byte planes only: an affine epilogue is applied on the way out, so the usual x' = in / 255, out = 255 F round trip
+        // of a byte image keeps the early stores; no other destination type launches EARLY with an epilogue)
+        if constexpr (std::is_same<P, uint8_t>::value) {
+            if (a.pw_flags & 2) v = a.post_f * v + a.post_b;
+        }
+        if constexpr (packed_bytes<P>::value) {
+            // byte pixels, packed form: four rows at a time, one dword per lane (scan_device.h, store_row_quad)
+            if ((m & 3) == 0) hq0 = v; else if ((m & 3) == 1) hq1 = v; else if ((m & 3) == 2) hq2 = v; else hq3 = v;
+            if ((m & 3) == (YPAT == 2 ? 0 : 3))
+                store_row_quad(dpb_early, (uint32_t)t, (uint32_t)(m & ~3), a.row_bytes, hq0, hq1, hq2, hq3, (uint32_t)TY);
+        } else
         if constexpr (packed_stores<P>::value) {
             // 16-bit float pixels: two rows at a time, one dword per lane (scan_device.h, store_row_pair); the scan hands the
             // rows over in its own direction, so the first row of a pair waits for the second
@@ -381,6 +395,12 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
         char *dpb = reinterpret_cast<char *>(dst + tile_off);
         const uint32_t row_bytes = a.row_bytes;
         if (t < last_cols) {
+            if constexpr (packed_bytes<P>::value) {
+                // (byte pixels, packed form: last_cols is a multiple of 4, so a quad of columns is stored or not as one)
+#pragma unroll
+                for (int i = 0; i < TY; i += 4)
+                    store_row_quad(dpb, (uint32_t)t, (uint32_t)i, row_bytes, col[i], col[i + 1], col[i + 2], col[i + 3], (uint32_t)(EDGE ? rows_here : TY));
+            } else
             if constexpr (packed_stores<P>::value) {
                 // (16-bit float pixels, scan_device.h: last_cols is a multiple of 4, so a column pair is stored or not as one)
 #pragma unroll
@@ -456,7 +476,50 @@ int launch_tall_widen(const PI *src, float *dst, const FusedArgs<float> &a, hipS
     return launch_tall_pat<float, K, EDGE, PI, 0, false>(src, dst, a, stream);
 }
 
+// Unsigned bytes in, unsigned bytes out (kernels_fused.hip, launch_fused_pass2_u8): the usual pair of y scans on its
+// compile-time variants -- rows leaving from inside the last scan where the tiles are whole, both dimensions have the pair and
+// the epilogue, if any, has no input operand -- every other filter on the general-pattern code
+template <int K, bool EDGE>
+int launch_tall_u8(const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream) {
+    const bool pair_y = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0;
+    const bool pair_x = a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
+    if constexpr (!EDGE) {
+        if (pair_y && pair_x && ((a.pw_flags & 2) == 0 || a.post_i == 0.0f)) return launch_tall_pat<uint8_t, K, EDGE, uint8_t, 2, true, true>(src, dst, a, stream);
+    }
+    if (pair_y) return launch_tall_pat<uint8_t, K, EDGE, uint8_t, 2, false>(src, dst, a, stream);
+    return launch_tall_pat<uint8_t, K, EDGE, uint8_t, 0, false>(src, dst, a, stream);
+}
+
 }  // namespace
+
+int launch_fused_pass2_tall_u8(int K, const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream) {
+    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
+    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    if (a.lin_limit > 0 || a.mod_form || a.y_apply != nullptr || a.row_bytes != (uint32_t)a.NX) {
+        set_error("fused pass 2: byte planes on both sides are an unsharded 2-D image of orders <= 3 with a row pitch of NX bytes");
+        return RF_ERR_INVALID_ARG;
+    }
+    auto one = [&](const FusedArgs<float> &aa, bool e) -> int {
+#define RF_CASE(KK) \
+    if (K == KK) return e ? launch_tall_u8<KK, true>(src, dst, aa, stream) : launch_tall_u8<KK, false>(src, dst, aa, stream);
+        RF_CASE(1) RF_CASE(2) RF_CASE(3)
+#undef RF_CASE
+        set_error("fused path: unsupported order %d", K);
+        return (int)RF_ERR_UNSUPPORTED;
+    };
+    // partial tiles: the whole tiles on the lean kernel, the last tile column and the last tile row on the EDGE variant, as below
+    const bool edge = a.last_cols != kFusedTX || a.last_rows != kTallTY;
+    if (edge) {
+        const int MXf = a.MX - (a.last_cols != kFusedTX ? 1 : 0), MYf = a.MY - (a.last_rows != kTallTY ? 1 : 0);
+        FusedArgs<float> part = a;
+        part.gx = MXf; part.gy = MYf;
+        int rc = (MXf > 0 && MYf > 0) ? one(part, false) : (int)RF_OK;
+        if (rc == RF_OK && MXf < a.MX) { part = a; part.tx0 = a.MX - 1; part.gx = 1; part.gy = a.MY; rc = one(part, true); }
+        if (rc == RF_OK && MYf < a.MY && MXf > 0) { part = a; part.ty0 = a.MY - 1; part.gy = 1; part.gx = MXf; rc = one(part, true); }
+        return rc;
+    }
+    return one(a, false);
+}
 
 template <typename P>
 int launch_fused_pass2_tall(int K, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,

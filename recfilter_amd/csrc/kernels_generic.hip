@@ -872,6 +872,31 @@ template int launch_convert<float, __bf16>(const __bf16 *, float *, int64_t, hip
 template int launch_convert<_Float16, float>(const float *, _Float16 *, int64_t, hipStream_t);
 template int launch_convert<__bf16, float>(const float *, __bf16 *, int64_t, hipStream_t);
 
+// ---- f32 planes -> unsigned bytes (staged RF_IO_U8 plans, plan.cpp): out = sat8(v), the plan's one conversion ----
+// Four samples per thread (one dword of bytes) where the source is 16-byte and the destination 4-byte aligned, sample by
+// sample otherwise and for the last n % 4.
+__global__ void __launch_bounds__(kBlock)
+convert_sat8_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, int64_t n, int64_t n4) {
+    typedef float F4 __attribute__((ext_vector_type(4)));
+    const int64_t step = (int64_t)gridDim.x * kBlock, first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    for (int64_t i = first; i < n4; i += step) {
+        const F4 v = reinterpret_cast<const F4 *>(src)[i];
+        reinterpret_cast<uint32_t *>(dst)[i] = (uint32_t)sat8(v.x) | ((uint32_t)sat8(v.y) << 8) | ((uint32_t)sat8(v.z) << 16) | ((uint32_t)sat8(v.w) << 24);
+    }
+    for (int64_t i = 4 * n4 + first; i < n; i += step) dst[i] = sat8(src[i]);
+}
+
+int launch_convert_sat8(const float *src, uint8_t *dst, int64_t n, hipStream_t stream) {
+    if (n <= 0) return RF_OK;
+    const bool aligned = ((uintptr_t)src & 15u) == 0 && ((uintptr_t)dst & 3u) == 0;
+    const int64_t n4 = aligned ? n / 4 : 0;
+    const int64_t want = ((aligned ? n4 + 4 : n) + kBlock - 1) / kBlock;
+    const unsigned blocks = (unsigned)(want < 256 * 64 ? want : 256 * 64);
+    hipLaunchKernelGGL(convert_sat8_kernel, dim3(blocks), dim3(kBlock), 0, stream, src, dst, n, n4);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
+}
+
 template <typename P>
 int launch_box_difference(const P *in, P *out, const BoxDiffArgs &a, hipStream_t stream) {
     if (a.n[0] <= 0 || a.n[1] <= 0 || a.n[2] <= 0) return RF_OK;

@@ -56,6 +56,21 @@ template <> struct PixelTraits<__bf16> {
     static inline Acc coef_from_double(double c) { return (float)c; }
     static constexpr bool is_integer = false;
 };
+// Unsigned-byte planes on both sides (rf_pointwise_desc.in_dtype == RF_IO_U8) are a storage type in the same sense: the plan is
+// the RF_F32 plan that reads the bytes (RF_IN_U8), and the f32 result is converted once, at the final store:
+//     sat8(v) = (uint8) min(max(rint(v), 0), 255)      rint: to nearest, ties to even; below 0 -> 0, above 255 -> 255, NaN -> 0
+// (fmaxf returns its other operand for a NaN).  Only the final-pass kernels of the fused path are instantiated with this
+// destination type; no plan has it as its pixel type.
+__host__ __device__ inline uint8_t sat8(float v) {
+    return (uint8_t)(int32_t)__builtin_fminf(__builtin_fmaxf(__builtin_rintf(v), 0.0f), 255.0f);
+}
+template <> struct PixelTraits<uint8_t> {
+    using Acc = float;
+    static __host__ __device__ inline Acc load(uint8_t v) { return (float)v; }
+    static __host__ __device__ inline uint8_t store(Acc v) { return sat8(v); }
+    static inline Acc coef_from_double(double c) { return (float)c; }
+    static constexpr bool is_integer = false;
+};
 template <> struct PixelTraits<int16_t> {
     using Acc = uint32_t;
     static __host__ __device__ inline Acc load(int16_t v) { return (uint32_t)(int32_t)v; }

@@ -455,6 +455,42 @@ int build_staged_half(const rf_filter_desc *desc, rf_plan *parent) {
     return desc->dtype == RF_F16 ? build_staged_half_typed<_Float16>(desc, parent) : build_staged_half_typed<__bf16>(desc, parent);
 }
 
+// ---- staged byte-output plans ---------------------------------------------------------------------------------------------
+// RF_IO_U8 (pixel.h, sat8): out = sat8(F_f32(widen(in))), no intermediate ever passes through a byte plane.  The final pass of the
+// fused x/y kernels keeps that contract for 2-D images (plan_fused.cpp, add_pass2).  Every other plan owns one f32 plane per
+// image plane and runs
+//     the RF_IN_U8 f32 plan of the same description, from the caller's bytes into those planes -> convert_out
+// (no convert_in: that plan reads the bytes itself; its epilogue's input operand is the caller's plane, never its output).
+// Same wrapper as the staged 16-bit plans above.
+int build_staged_u8(const rf_filter_desc *desc, rf_plan *parent) {
+    rf_filter_desc fd = *desc;
+    fd.pointwise.in_dtype = RF_IN_U8;
+    rf_plan *child = nullptr;
+    int rc = build_plan(&fd, &child);
+    if (rc != RF_OK) return rc;
+    std::unique_ptr<rf_plan> holder(child);
+    std::vector<const Step *> steps;
+    if ((rc = child_steps(child, steps)) != RF_OK) return rc;
+    // (the launch list is the RF_IN_U8 plan's, name for name: the apply steps the generic path keeps for an unsharded outermost
+    // dimension run here as rf_plan_execute runs them for that plan)
+    steps = single_device_steps(child, true);
+    int status = RF_OK;
+    std::vector<float *> pa((size_t)parent->n_planes, nullptr);
+    for (int pl = 0; pl < parent->n_planes; pl++) pa[(size_t)pl] = (float *)parent->alloc((size_t)parent->total * sizeof(float), false, &status);
+    if (status != RF_OK) return status;
+    const int64_t total = parent->total;
+    append_child_steps(parent, child, steps, "", [parent, pa](int q) { return ChildPlanes{parent->orig_in[q], pa[(size_t)q]}; });
+    Step co;
+    co.name = "convert_out";
+    co.run = [parent, pa, total](int pl) { return launch_convert_sat8(pa[(size_t)pl], (uint8_t *)parent->out[pl], total, parent->stream); };
+    parent->begin_steps.push_back(co);
+    parent->path = child->path;
+    parent->vector_access = false;           // (rf_plan_execute checks the 4-byte alignment of byte planes by itself)
+    take_over_child(parent, child, true);
+    parent->stages.push_back(std::move(holder));
+    return RF_OK;
+}
+
 // what a replica of this plan is built from (concurrent executions, capi.cpp)
 void save_desc(rf_plan *plan, const rf_filter_desc *desc) {
     plan->saved.d = *desc;
@@ -533,8 +569,12 @@ int validate_desc(const rf_filter_desc *desc) {
     }
     const rf_pointwise_desc &pwd = desc->pointwise;
     if (pwd.flags & ~(RF_POINTWISE_PRE | RF_POINTWISE_POST)) { set_error("unknown pointwise flags 0x%x", pwd.flags); return RF_ERR_INVALID_ARG; }
-    if (pwd.in_dtype != RF_IN_PIXEL && pwd.in_dtype != RF_IN_U8) { set_error("unknown pointwise input type %d", pwd.in_dtype); return RF_ERR_INVALID_ARG; }
-    if (pwd.in_dtype == RF_IN_U8 && desc->dtype != RF_F32) { set_error("unsigned-byte input needs f32 pixels"); return RF_ERR_UNSUPPORTED; }
+    if (pwd.in_dtype < RF_IN_PIXEL || pwd.in_dtype > RF_IO_U8) { set_error("unknown pointwise input type %d", pwd.in_dtype); return RF_ERR_INVALID_ARG; }
+    if (pwd.in_dtype != RF_IN_PIXEL && desc->dtype != RF_F32) { set_error("unsigned-byte planes need f32 pixels"); return RF_ERR_UNSUPPORTED; }
+    if (pwd.in_dtype == RF_IO_U8 && (desc->shard_world > 1 || (desc->flags & RF_PLAN_FORCE_EXCHANGE))) {
+        set_error("unsigned-byte output planes cannot be sharded");
+        return RF_ERR_UNSUPPORTED;
+    }
     if (pwd.flags != 0 && desc->dtype != RF_F32 && desc->dtype != RF_F64 && !is_half(desc->dtype)) {
         set_error("pointwise stages need a floating-point pixel type");
         return RF_ERR_UNSUPPORTED;
@@ -633,7 +673,8 @@ int describe(const rf_filter_desc *desc, rf_plan *plan) {
     plan->flags = desc->flags;
     plan->pw.pre = (pwd.flags & RF_POINTWISE_PRE) != 0;
     plan->pw.post = (pwd.flags & RF_POINTWISE_POST) != 0;
-    plan->pw.in_u8 = pwd.in_dtype == RF_IN_U8;
+    plan->pw.in_u8 = pwd.in_dtype == RF_IN_U8 || pwd.in_dtype == RF_IO_U8;
+    plan->pw.out_u8 = pwd.in_dtype == RF_IO_U8;
     if (plan->pw.pre) { plan->pw.pre_s = pwd.pre_scale; plan->pw.pre_b = pwd.pre_bias; }
     if (plan->pw.in_u8) plan->pw.pre = true;        // the conversion is a prologue (scale 1, bias 0 unless given)
     if (plan->pw.post) { plan->pw.post_f = pwd.post_filtered; plan->pw.post_i = pwd.post_input; plan->pw.post_b = pwd.post_bias; }
@@ -682,6 +723,14 @@ bool half_plan_is_native(const rf_filter_desc *desc, const rf_plan *plan) {
     // (volumes, RF_PATH_AUTO: native from kHalfVolumeNativeSamples samples per plane on -- above)
     const bool small_volume = desc->ndim > 2 && desc->path == RF_PATH_AUTO && plan->total < kHalfVolumeNativeSamples;
     return auto_or_fused(desc) && !(desc->flags & RF_PLAN_STAGE_HALF) && !small_volume && fused_plan_applicable(plan, desc, &unused);
+}
+
+// Byte planes on both sides: native where the fused kernels take the 2-D image as it is -- orders <= 3 (asked BEFORE the rewrite
+// into sections: no byte instance carries border modifications), a width that is a multiple of 4 -- staged everywhere else
+// ("staged byte-output plans" above).  RF_PLAN_STAGE_HALF forces the staged form.
+bool u8_plan_is_native(const rf_filter_desc *desc, const rf_plan *plan) {
+    std::string unused;
+    return auto_or_fused(desc) && !(desc->flags & RF_PLAN_STAGE_HALF) && desc->ndim == 2 && fused_plan_applicable(plan, desc, &unused);
 }
 
 // Orders above 3 (lib/split.cpp:575-578 pads any order; the fused kernels stop at 3): with a zero border and float
@@ -882,11 +931,13 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
     if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     *out = nullptr;
     if (int rc = validate_desc(desc)) return rc;
-    if (plan_merged_runs(desc, out)) return RF_OK;
+    const bool bytes_out = desc->pointwise.in_dtype == RF_IO_U8;       // (a staged plan: its RF_IN_U8 child merges its own runs)
+    if (!bytes_out && plan_merged_runs(desc, out)) return RF_OK;
     std::unique_ptr<rf_plan> plan(new rf_plan);
     if (int rc = describe(desc, plan.get())) return rc;
     const bool half = is_half(desc->dtype);
     if (half && !half_plan_is_native(desc, plan.get())) return finish(build_staged_half(desc, plan.get()), plan, desc, out);
+    if (bytes_out && !u8_plan_is_native(desc, plan.get())) return finish(build_staged_u8(desc, plan.get()), plan, desc, out);
     rewrite_into_sections(desc, plan.get());
     std::string fused_why;
     const bool fused_ok = fused_plan_applicable(plan.get(), desc, &fused_why);       // (of the final scan list: once)
@@ -896,7 +947,12 @@ int build_plan(const rf_filter_desc *desc, rf_plan **out) {
 
     const int path = desc->path == RF_PATH_AUTO ? choose_auto_path(desc, plan.get(), fused_ok) : desc->path;
     if ((rc = check_path(desc, plan.get(), path, fused_ok, fused_why)) != RF_OK) return rc;
-    rc = build_on_path(plan.get(), desc, path);
+    // (a native byte-output plan is a fused plan: no other builder knows byte planes)
+    rc = (bytes_out && path != RF_PATH_TILED_FUSED) ? (int)RF_ERR_UNSUPPORTED : build_on_path(plan.get(), desc, path);
+    if (bytes_out && rc == RF_ERR_UNSUPPORTED) {                     // the fused builder refused the shape after all
+        plan = fresh_description(*plan);
+        return finish(build_staged_u8(desc, plan.get()), plan, desc, out);
+    }
     if (half && rc == RF_ERR_UNSUPPORTED && !plan->sharded()) {      // the fused builder refused the shape after all
         plan = fresh_description(*plan);
         return finish(build_staged_half(desc, plan.get()), plan, desc, out);

@@ -37,6 +37,7 @@ struct Step {
 struct Pointwise {
     bool pre = false, post = false;
     bool in_u8 = false;            // input planes are unsigned bytes, converted on load (implies a prologue)
+    bool out_u8 = false;           // RF_IO_U8: the output planes are unsigned bytes too, out = sat8(f32 result) (pixel.h)
     bool pre_fused = false, post_fused = false;
     double pre_s = 1.0, pre_b = 0.0, post_f = 1.0, post_i = 0.0, post_b = 0.0;
 };

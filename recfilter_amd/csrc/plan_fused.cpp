@@ -716,6 +716,15 @@ struct FusedBuilder {
                     return launch_fused_pass2<float>(K, TY, plan->in[pl], kind, (float *)plan->mid[pl], a, plan->stream);
                 }
             }
+            if constexpr (std::is_same<P, float>::value) {
+                // byte planes on both sides (RF_IO_U8; plan.cpp, u8_plan_is_native: an unsharded 2-D image): everything up to
+                // here was the RF_IN_U8 plan's, the final pass stores bytes
+                if (plan->pw.out_u8) {
+                    a.row_bytes = (uint32_t)a.NX;
+                    if (TY == 128) return launch_fused_pass2_tall_u8(K, (const uint8_t *)plan->in[pl], (uint8_t *)plan->out[pl], a, plan->stream);
+                    return launch_fused_pass2_u8(K, TY, (const uint8_t *)plan->in[pl], (uint8_t *)plan->out[pl], a, plan->stream);
+                }
+            }
             if constexpr (sizeof(Acc) == 4) {
                 if (TY == 128) return launch_fused_pass2_tall<P>(K, plan->in[pl], plan->pw.in_u8, (P *)plan->xy_result(pl), a, plan->stream);
             }
@@ -789,6 +798,12 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     fb.plan = plan; fb.desc = desc;
     const FusedGeometry &g = fb.g = fused_geometry<P>(plan);
     if (g.error) { set_error("%s", g.error); return RF_ERR_UNSUPPORTED; }
+    // (byte output planes: only the final pass of such an image stores bytes -- nothing else here may ever write them)
+    if (plan->pw.out_u8 && (!std::is_same<P, float>::value || plan->ndim != 2 || plan->sharded() || plan->mod_form || g.chained || g.padded ||
+                            plan->dims[0].N % 4 != 0)) {
+        set_error("fused path: byte output planes need an unsharded 2-D f32 plan of orders <= 3 whose width is a multiple of 4");
+        return RF_ERR_UNSUPPORTED;
+    }
     plan->dims[0].T = kFusedTX; plan->dims[0].M = g.chained ? g.N1 / kFusedTX : g.MX;
     if (!g.chained) { plan->dims[1].T = g.TY; plan->dims[1].M = g.MY; }
     const size_t first_begin_step = plan->begin_steps.size(), first_finish_step = plan->finish_steps.size();

@@ -336,6 +336,34 @@ __device__ __forceinline__ void store_row_pair(char *tile_base, uint32_t t, uint
                                     reinterpret_cast<uint32_t *>(tile_base + ((t & ~1u) * 2u + row * row_bytes)));
 }
 
+// ---- final stores of unsigned-byte pixels (RF_IO_U8) --------------------------------------------------------------------------
+// The plain store of a byte pixel is one byte per lane and row (global_store_byte): as many store instructions as f32 pixels
+// need, for a quarter of the bytes.  The packed form -- built with -DRF_U8_PACKED_STORES for A/B runs -- issues a quarter of
+// them: the four lanes of a quad (columns 4c .. 4c+3) transpose a 4 x 4 block of converted bytes among themselves (three
+// v_mov_b32_dpp quad_perm exchanges) so that lane q holds the four columns of row q, and each stores one dword.  Which form
+// ships is decided by measurement (NOTES section 4, "byte output planes").
+// Call with the lanes of a quad either all active or all inactive (the callers' column bound is a multiple of 4).
+// row0: the first row of the block, a multiple of 4; rows: the rows that exist (a row >= rows is not stored).
+#ifdef RF_U8_PACKED_STORES
+template <typename P> struct packed_bytes { static constexpr bool value = std::is_same<P, uint8_t>::value; };
+#else
+template <typename P> struct packed_bytes { static constexpr bool value = false; };
+#endif
+__device__ __forceinline__ void store_row_quad(char *tile_base, uint32_t t, uint32_t row0, uint32_t row_bytes, float v0, float v1,
+                                               float v2, float v3, uint32_t rows) {
+    const uint32_t q = t & 3u;
+    const uint32_t b0 = sat8(v0), b1 = sat8(v1), b2 = sat8(v2), b3 = sat8(v3);      // this column's bytes of rows row0 .. row0 + 3
+    auto pick = [&](uint32_t r) { return r == 0u ? b0 : r == 1u ? b1 : r == 2u ? b2 : b3; };
+    // lane q hands lane q ^ k its byte of row q ^ k and receives that lane's byte of row q: column (q ^ k) of row q
+    const uint32_t g1 = dpp_move<0xB1>(pick(q ^ 1u));       // quad_perm:[1,0,3,2]
+    const uint32_t g2 = dpp_move<0x4E>(pick(q ^ 2u));       // quad_perm:[2,3,0,1]
+    const uint32_t g3 = dpp_move<0x1B>(pick(q ^ 3u));       // quad_perm:[3,2,1,0]
+    const uint32_t word = (pick(q) << (8u * q)) | (g1 << (8u * (q ^ 1u))) | (g2 << (8u * (q ^ 2u))) | (g3 << (8u * (q ^ 3u)));
+    const uint32_t row = row0 + q;
+    if (row < rows)
+        __builtin_nontemporal_store(word, reinterpret_cast<uint32_t *>(tile_base + ((t & ~3u) + row * row_bytes)));
+}
+
 template <typename Acc>
 struct Vec4 {
     typedef Acc type __attribute__((ext_vector_type(4)));

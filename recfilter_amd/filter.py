@@ -14,11 +14,17 @@ from __future__ import annotations
 import itertools
 from typing import Dict, List, Optional, Sequence, Union
 
+import numpy as np
+
 from . import capi
 from .capi import RecFilterError
 from .plan import Plan
 
 _counter = itertools.count()
+
+
+def _is_byte_tensor(t) -> bool:
+    return str(getattr(t, "dtype", "")) in ("torch.uint8", "uint8")
 
 
 class RecFilterUsageError(RuntimeError):
@@ -83,10 +89,14 @@ class RecFilterSchedule:
 class Pointwise:
     """A pointwise consumer of a filter, `w_filtered * F + w_input * I + bias` with I the filter's own
     (prologue-transformed) input -- e.g. the unsharp mask `(1+w)*I - w*Blur` of
-    apps/usm/unsharp_mask_optimized.cpp:57.  Passed to RecFilter.compute_at()."""
+    apps/usm/unsharp_mask_optimized.cpp:57.  Passed to RecFilter.compute_at().
+    to_bytes=True (a filter defined on torch.uint8 tensors only): the consumer is `cast<uint8_t>(...)` of that expression --
+    realize() returns torch.uint8 tensors, each sample min(max(rint(v), 0), 255) of the float value v, converted once as the
+    final pass stores it (rf_input_dtype RF_IO_U8)."""
 
-    def __init__(self, w_filtered: float = 1.0, w_input: float = 0.0, bias: float = 0.0):
+    def __init__(self, w_filtered: float = 1.0, w_input: float = 0.0, bias: float = 0.0, to_bytes: bool = False):
         self.w_filtered, self.w_input, self.bias = float(w_filtered), float(w_input), float(bias)
+        self.to_bytes = bool(to_bytes)
 
 
 class RecFilter:
@@ -103,7 +113,7 @@ class RecFilter:
         self._contents: Dict = dict(
             name=(name or "R") + f"_{next(_counter)}", dims=[], inputs=None, scans=[],
             clamped=False, tiled=False, tile={}, compiled=False, plan=None, schedule_log=[],
-            source=None, prologue=None, epilogue=None)
+            source=None, prologue=None, epilogue=None, to_bytes=False)
 
     # -- definition -----------------------------------------------------------------------------
     def name(self) -> str:
@@ -287,6 +297,11 @@ class RecFilter:
             raise RecFilterUsageError(f"Cannot compute {self.name()} at another consumer because it already has a consumer")
         if c["compiled"]:
             raise RecFilterUsageError("compute_at must be called before the filter is compiled or realized")
+        if getattr(consumer, "to_bytes", False):
+            inputs = self._root_inputs()
+            if not inputs or not _is_byte_tensor(inputs[0]):
+                raise RecFilterUsageError(f"A consumer that stores bytes needs {self.name()} to be defined on unsigned-byte tensors")
+            c["to_bytes"] = True
         c["epilogue"] = (consumer.w_filtered, consumer.w_input, consumer.bias)
 
     # -- schedules: accepted, recorded, not needed (lib/recfilter.cpp:396-870) -------------------
@@ -382,8 +397,15 @@ class RecFilter:
             path = capi.RF_PATH_AUTO if tiled else capi.RF_PATH_UNTILED
         kw = dict(dtype=inputs[0].dtype, clamped=c["clamped"], planes=len(inputs), tile=tile, device=inputs[0].device.index or 0,
                   epilogue=c["epilogue"])
+        # a definition on unsigned-byte tensors is a float32 filter that reads the bytes (rf_pointwise_desc.in_dtype); with a
+        # to_bytes consumer it stores bytes as well.  Only the plan that reads the head's tensors sees bytes: a stage of a
+        # cascade that runs as a plan of its own reads its source's float32 result.
+        byte_kw = {}
+        if _is_byte_tensor(inputs[0]):
+            kw["dtype"] = np.float32
+            byte_kw = dict(input_dtype=np.uint8, output_dtype=np.uint8 if c.get("to_bytes") else None)
         try:
-            c["plan"] = Plan(shape, scans, path=path, prologue=prologue, **kw)
+            c["plan"] = Plan(shape, scans, path=path, prologue=prologue, **kw, **(byte_kw if chain is not None or c["source"] is None else {}))
             c["merged_stages"] = len(chain) if chain is not None else 0
         except (RecFilterError, ValueError):
             # The merged plan of a cascade may not exist where every stage's own plan does -- more than RF_MAX_SCANS scans in
@@ -393,6 +415,8 @@ class RecFilter:
                 raise
             if asked_path is None:
                 path = capi.RF_PATH_AUTO if c["tiled"] else capi.RF_PATH_UNTILED
+            if c.get("to_bytes"):
+                raise RecFilterUsageError("a consumer that stores bytes needs the cascade to run as one plan")
             c["plan"] = Plan(shape, c["scans"], path=path, prologue=c["prologue"], **kw)
             c["merged_stages"] = 0
         c["merge_cascades_at_compile"] = RecFilter.merge_cascades

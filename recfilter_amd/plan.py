@@ -46,6 +46,16 @@ def _dtype_code(dtype) -> int:
     return _NP_DTYPES[dt]
 
 
+def _is_uint8(dtype) -> bool:
+    """np.uint8 / torch.uint8 (or anything numpy reads as an unsigned byte)"""
+    if dtype is None:
+        return False
+    try:
+        return np.dtype(str(dtype).replace("torch.", "") if hasattr(dtype, "is_floating_point") else dtype) == np.dtype(np.uint8)
+    except TypeError:
+        return False
+
+
 def _torch_dtype(code: int):
     import torch
     return {capi.RF_F32: torch.float32, capi.RF_F64: torch.float64, capi.RF_I32: torch.int32, capi.RF_I16: torch.int16,
@@ -59,11 +69,14 @@ class Plan:
                  planes: int = 1, tile: Optional[Sequence[int]] = None, path: int = capi.RF_PATH_AUTO,
                  device: int = -1, shard_rank: int = 0, shard_world: int = 1, shard_extents: Optional[Sequence[int]] = None,
                  prologue: Optional[Tuple[float, float]] = None,
-                 epilogue: Optional[Tuple[float, float, float]] = None, input_dtype=None, flags: Optional[int] = None):
+                 epilogue: Optional[Tuple[float, float, float]] = None, input_dtype=None, flags: Optional[int] = None,
+                 output_dtype=None):
         """prologue = (scale, bias): x' = scale*in + bias before the first scan;
         epilogue = (w_filtered, w_input, bias): out = w_filtered*F(x') + w_input*x' + bias
         (rf_pointwise_desc; fused into pass 1 / pass 2 on the fused path).  input_dtype=np.uint8 (with dtype float32):
         the input planes are unsigned bytes converted on load (rf_pointwise_desc.in_dtype = RF_IN_U8).
+        output_dtype=np.uint8 (with input_dtype=np.uint8 and dtype float32; np.uint8 or torch.uint8 for either): the output
+        planes are unsigned bytes too, out = sat8(f32 result), converted once at the final store (RF_IO_U8).
         flags: rf_filter_desc.flags (capi.RF_PLAN_*); None = recfilter_amd.plan.DEFAULT_FLAGS (0 as shipped)."""
         L = capi.lib()
         shape = tuple(int(s) for s in shape)
@@ -113,10 +126,15 @@ class Plan:
         if epilogue is not None:
             d.pointwise.flags |= capi.RF_POINTWISE_POST
             d.pointwise.post_filtered, d.pointwise.post_input, d.pointwise.post_bias = (float(v) for v in epilogue)
-        self.input_np_dtype = None
-        if input_dtype is not None and np.dtype(input_dtype if not hasattr(input_dtype, "is_floating_point") else
-                                                 str(input_dtype).replace("torch.", "")) == np.dtype(np.uint8):
-            d.pointwise.in_dtype = capi.RF_IN_U8
+        self.input_np_dtype = self.output_np_dtype = None
+        if output_dtype is not None:
+            if not _is_uint8(output_dtype):
+                raise TypeError(f"unsupported output type {output_dtype}: byte planes (uint8) or the pixel type")
+            if not _is_uint8(input_dtype) or d.dtype != capi.RF_F32:
+                raise TypeError("output_dtype=uint8 needs input_dtype=uint8 and dtype float32")
+            self.output_np_dtype = np.dtype(np.uint8)
+        if _is_uint8(input_dtype):
+            d.pointwise.in_dtype = capi.RF_IO_U8 if self.output_np_dtype is not None else capi.RF_IN_U8
             self.input_np_dtype = np.dtype(np.uint8)
         elif input_dtype is not None and _dtype_code(input_dtype) != d.dtype:
             raise TypeError(f"unsupported input type {input_dtype} for pixel type {dtype}")
@@ -222,6 +240,10 @@ class Plan:
                 import torch
                 if t.dtype != torch.uint8:
                     raise TypeError(f"plane {i}: the plan expects unsigned-byte input planes, got {t.dtype}")
+            elif not inputs and self.output_np_dtype is not None:
+                import torch
+                if t.dtype != torch.uint8:
+                    raise TypeError(f"plane {i}: the plan writes unsigned-byte output planes, got {t.dtype}")
             elif _dtype_code(t.dtype) != self._desc.dtype:
                 raise TypeError(f"plane {i}: dtype {t.dtype} does not match the plan")
             arr[i] = t.data_ptr()
@@ -229,7 +251,7 @@ class Plan:
 
     def _new_outputs(self, inputs):
         import torch
-        tdt = _torch_dtype(self.dtype_code)
+        tdt = torch.uint8 if self.output_np_dtype is not None else _torch_dtype(self.dtype_code)
         return [torch.empty(t.shape, dtype=tdt, device=t.device) for t in inputs]
 
     @staticmethod
