@@ -195,6 +195,13 @@ typedef struct {
  *                           a causal-then-anticausal pair, completes that dimension's carries from the neighbouring
  *                           tiles' tails alone where the filter decays within a tile -- the part that form drops is
  *                           at most 2^-32 of the largest carry (rf_plan_table("neighbour_carries")).
+ *   RF_PLAN_SEPARATE_ROW_SCANS a neighbour-form step keeps its three kernels as they are for every filter: the launch between
+ *                           the passes scans the y tails' combined rows, adds the cross-dimension residual and completes
+ *                           the x tails.  Default: an f32 image of whole 256 x 128 tiles under an order-2 causal + anticausal
+ *                           pair in x and in y, both in neighbour form and without pointwise stages, takes the row-scan
+ *                           form (rf_plan_table("row_scans") = 1): pass 1 scans the rows it holds, that launch only contracts
+ *                           the x tails into 64 bytes per tile, and the final pass forms the carries it loads.  Same step
+ *                           names, same workspace, the same result to the bit.
  *   RF_PLAN_STAGE_HALF      RF_F16 / RF_BF16 pixels: the plan is staged through f32 planes even where the fused kernels
  *                           would run it natively -- 2-D images, 1-D signals and volumes alike (same result to the last
  *                           rounding; for comparisons).  RF_IO_U8 planes (rf_input_dtype): the plan is staged through f32
@@ -215,7 +222,8 @@ typedef struct {
 #define RF_PLAN_INPLACE_Z       0x10000000u
 #define RF_PLAN_FULL_CARRY_SCAN 0x20000000u
 #define RF_PLAN_STAGE_HALF      0x40000000u
-#define RF_PLAN_ALL_FLAGS       0x7f0000ffu
+#define RF_PLAN_SEPARATE_ROW_SCANS 0x80000000u
+#define RF_PLAN_ALL_FLAGS       0xff0000ffu
 #define RF_PLAN_TILE_ROWS(n)    (((uint32_t)(n) & 0xffu) << 8)
 #define RF_PLAN_TILE_PLANES(n)  (((uint32_t)(n) & 0xffu) << 16)
 

@@ -40,6 +40,7 @@ RF_PLAN_NO_OVERLAP = 0x08000000
 RF_PLAN_INPLACE_Z = 0x10000000
 RF_PLAN_FULL_CARRY_SCAN = 0x20000000
 RF_PLAN_STAGE_HALF = 0x40000000       # 16-bit float pixels: staged through f32 planes even where the fused kernels run them
+RF_PLAN_SEPARATE_ROW_SCANS = 0x80000000       # a neighbour-form step keeps its three kernels (rf_plan_table("row_scans") = 0)
 
 
 def RF_PLAN_TILE_ROWS(n: int) -> int:

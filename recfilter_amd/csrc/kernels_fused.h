@@ -116,6 +116,14 @@ struct FusedArgs {
     // image the kernels see is the signal followed by zeros, but only its first lin_limit samples exist in the caller's
     // buffers -- loads beyond them yield zeros, stores beyond them are dropped.  0: every sample of the image exists.
     int64_t lin_limit;
+    // Row-scan form of the neighbour-form step (plan_fused.cpp, row_scans; kernels_tails_mfma.hip RS, xtau_kernel,
+    // kernels_fused_tall.hip RS): pass 1 leaves the y tails tile-locally scanned along x, the middle launch stores only
+    // rs_tau[z][ty][tx][j * K + r][q * K + o] -- the contraction of the completed x carry strips entering tile (tx, ty) with
+    // Hy -- and the final pass forms every carry itself: `xt` holds the RAW x tails, x_nb_W the chaining tables of the x scans
+    // (W[v][q][s][r][o], as y_nb_W), rs_G the table G[v][q][o][256] of the residual.  All null otherwise.
+    const Acc *x_nb_W;
+    const Acc *rs_tau;
+    const Acc *rs_G;
     // element index of y tail (j, ty, r) of column `line` (= x + NXP * z)
     __host__ __device__ int64_t yt_index(int j, int ty, int r, int K, int64_t line) const {
         if (yt_tile_major)
@@ -216,6 +224,11 @@ bool mfma_tails_applicable(int K, int TY, bool src_u8, int pw_flags, int last_co
                            int mode, bool narrow = false /* planes of a 16-bit float storage type */);
 template <typename PI>      // float, _Float16, __bf16
 int launch_mfma_tails(int K, int TY, const PI *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream);
+// Row-scan form (FusedArgs::rs_tau): order 2, 256 x 128 tiles, a causal + anticausal pair in x and in y, f32 planes of whole
+// tiles.  Pass 1 also runs the tile-local x scans of the combined rows it holds (one wave, through the free tile stage) ...
+int launch_mfma_tails_row_scans(const float *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream);
+// ... and the middle launch only contracts the neighbours' x tail strips with Hy, into tau (kernels_tails.hip, xtau_kernel)
+int launch_xtau(const FusedArgs<float> &a, const float *Hy, const float *Wx, float *tau, hipStream_t stream);
 // pass 1 of a 3-D plan in one read of the volume: x tails, the parts of the y tails' combined rows and the z tails
 // (kernels_tails_walk.hip)
 struct WalkArgs {

@@ -28,7 +28,14 @@ constexpr int kHalfRows = 64;
 // EARLY (whole tiles, one of the fixed patterns, no epilogue -- byte planes: none with an input operand): the rows are stored from
 // inside the last scan.
 // XFIX: the x scans have the same pattern as the y scans (YPAT), fixed at compile time as well.
-template <typename P, int K, bool EDGE, typename PI, int YPAT, bool EARLY, bool XFIX>
+// RS (row-scan form, FusedArgs::rs_tau; f32 whole tiles, the pair in both dimensions, both in neighbour form): nothing between
+// the passes has completed a carry.  x: FusedArgs::xt holds the raw tails, and the entry lane of the anticausal scan adds
+// W_v(tx+1)[0->1] * (this tile's own causal tail) to the tail it loads from tile tx + 1 -- what xscan_rows_kernel<NB> wrote to
+// xt_done.  y: the tails are tile-locally scanned along x (pass 1) but lack the cross-dimension residual, so each of the three
+// the kernel loads -- the causal one of tile ty - 1, the anticausal one of tile ty + 1, its own causal one -- first gets
+// sum_{q,o} G_vx[q][o][column] * tau(that tile)[j * K + r][q * K + o] (xtau_kernel).  Same terms in the same order as the
+// three-kernel form: the results are the same to the bit.
+template <typename P, int K, bool EDGE, typename PI, int YPAT, bool EARLY, bool XFIX, bool RS = false>
 __global__ void __launch_bounds__(kFusedThreads, 2)
 fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<typename PixelTraits<P>::Acc> a) {
     using Acc = typename PixelTraits<P>::Acc;
@@ -115,6 +122,26 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     // Neighbour-form y carries (FusedArgs::y_nb_W): the anticausal carry from tile ty + 1 is that tile's own tail plus
     // W_v(ty+1)[0->1] * this tile's causal tail -- the same shape, a k-vector requested here and a k x k product applied
     // after the pixels, with the tile's own scan-0 tail in the place of the slab's entering carries.
+    // RS: this column's G entries and the (workgroup-uniform) tau of the three tiles, requested with the carries
+    Acc rs_g[RS ? 2 * K : 1];
+    Acc rs_t[RS ? 3 : 1][K][RS ? 2 * K : 1];
+    if constexpr (RS) {
+        static_assert(!EDGE && YPAT == 2 && XFIX && std::is_same<Acc, float>::value, "row scans: whole tiles, the pair in x and in y");
+        const int vx = (tx == 0 ? 1 : 0) | (tx == a.MX - 1 ? 2 : 0);
+#pragma unroll
+        for (int qo = 0; qo < 2 * K; qo++) rs_g[qo] = a.rs_G[((size_t)vx * 2 * K + qo) * kFusedTX + t];
+        // [0]: tile ty - 1, scan 0; [1]: this tile, scan 0; [2]: tile ty + 1, scan 1
+        const int64_t tile_id = (z * a.MY + ty) * a.MX + tx;
+        const Acc *tp = a.rs_tau + tile_id * (4 * K * K);
+#pragma unroll
+        for (int r = 0; r < K; r++)
+#pragma unroll
+            for (int qo = 0; qo < 2 * K; qo++) {
+                rs_t[0][r][qo] = ty > 0 ? tp[-(int64_t)a.MX * (4 * K * K) + r * 2 * K + qo] : Acc(0);
+                rs_t[1][r][qo] = ty < a.MY - 1 ? tp[r * 2 * K + qo] : Acc(0);
+                rs_t[2][r][qo] = ty < a.MY - 1 ? tp[(int64_t)a.MX * (4 * K * K) + (K + r) * 2 * K + qo] : Acc(0);
+            }
+    }
     Acc yin[kFusedMaxScans][K];
     if (a.y_apply != nullptr) {
 #pragma unroll
@@ -126,6 +153,19 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
         for (int o = 0; o < K; o++) yin[0][o] = a.yt[a.yt_index(0, ty, o, K, line)];
     }
     auto apply_entering_carries = [&]() {
+        if constexpr (RS) {
+            // the residual of the three loaded tails, q then o onto the tail as xscan_rows_kernel adds it to a row
+#pragma unroll
+            for (int r = 0; r < K; r++)
+#pragma unroll
+                for (int qo = 0; qo < 2 * K; qo++) {
+                    if (ty > 0) CY[0][r] = CY[0][r] + rs_g[qo] * rs_t[0][r][qo];
+                    if (ty < a.MY - 1) {
+                        yin[0][r] = yin[0][r] + rs_g[qo] * rs_t[1][r][qo];
+                        CY[1][r] = CY[1][r] + rs_g[qo] * rs_t[2][r][qo];
+                    }
+                }
+        }
         if (a.y_nb_W != nullptr) {
             if (ty < a.MY - 1) {          // (the last tile row's anticausal carry enters at the border: nothing chains on it)
                 const int v = (ty + 1 == a.MY - 1) ? 2 : 0;
@@ -168,6 +208,7 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     // a prefetched half tile and the x phase leave no registers for them.
     Acc *cx_lds = tile + TL * kFusedTX;
     Acc CX[2][kFusedMaxScans][NR][K];
+    Acc XOWN[RS ? 2 : 1][RS ? NR : 1][K];      // RS: the tile's own causal tail, for the entry lane of the anticausal scan
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const int64_t line0 = (int64_t)ty * TY + TL * h + slot + a.NYP * z;
@@ -188,11 +229,35 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
                     for (int n = 0; n < NR; n++)
 #pragma unroll
                         for (int j = 0; j < K; j++) CX[h][s][n][j] = cp[j * Lx + line0 + 16 * n];
+                    if constexpr (RS) {
+                        if (s == 1 && !tile_first) {
+                            const Acc *op = a.xt + (int64_t)tx * K * Lx;
+#pragma unroll
+                            for (int n = 0; n < NR; n++)
+#pragma unroll
+                                for (int j = 0; j < K; j++) XOWN[h][n][j] = op[j * Lx + line0 + 16 * n];
+                        }
+                    }
                 }
             }
         }
     }
     auto park_carries = [&]() {
+        if constexpr (RS) {
+            // c_1(tx+1) = tau_1(tx+1) + W_v(tx+1)[0->1] tau_0(tx), term by term onto the loaded tail (xscan_rows_kernel<NB>)
+            if (l == last_lane && tx < a.MX - 1) {
+                const int vt = (tx + 1 == a.MX - 1) ? 2 : 0;
+                const Acc *Wm = a.x_nb_W + ((vt * 2 + 0) * 2 + 1) * K * K;
+#pragma unroll
+                for (int h = 0; h < 2; h++)
+#pragma unroll
+                    for (int n = 0; n < NR; n++)
+#pragma unroll
+                        for (int j = 0; j < K; j++)
+#pragma unroll
+                            for (int m = 0; m < K; m++) CX[h][1][n][j] = CX[h][1][n][j] + Wm[j * K + m] * XOWN[h][n][m];
+            }
+        }
 #pragma unroll
         for (int h = 0; h < 2; h++)
 #pragma unroll
@@ -416,7 +481,7 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     }
 }
 
-template <typename P, int K, bool EDGE, typename PI, int YPAT, bool EARLY, bool XFIX = false>
+template <typename P, int K, bool EDGE, typename PI, int YPAT, bool EARLY, bool XFIX = false, bool RS = false>
 int launch_tall_pat(const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
     using Acc = typename PixelTraits<P>::Acc;
     // the half tile + the x carries of both halves ([2][4 scans][4 rows][K][16 slots])
@@ -428,14 +493,14 @@ int launch_tall_pat(const PI *src, P *dst, const FusedArgs<typename PixelTraits<
     RF_HIP_CHECK(hipGetDevice(&dev));
     std::atomic<bool> &done = attr_set[dev & 63];
     if (!done.load(std::memory_order_acquire)) {
-        RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_pass2_tall_kernel<P, K, EDGE, PI, YPAT, EARLY, XFIX>),
+        RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_pass2_tall_kernel<P, K, EDGE, PI, YPAT, EARLY, XFIX, RS>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         done.store(true, std::memory_order_release);
     }
     dim3 grid((unsigned)(a.gx > 0 ? a.gx : a.MX), (unsigned)(a.gy > 0 ? a.gy : a.MY), (unsigned)a.NZ);
     FusedArgs<Acc> aa = a;
     aa.xcd_contig = (a.row_bytes % 128u != 0 && (grid.x * grid.y) % 8u == 0 && grid.x * grid.y >= 2048u) ? 1 : 0;
-    hipLaunchKernelGGL((fused_pass2_tall_kernel<P, K, EDGE, PI, YPAT, EARLY, XFIX>), grid, dim3(kFusedThreads), lds, stream, src, dst, aa);
+    hipLaunchKernelGGL((fused_pass2_tall_kernel<P, K, EDGE, PI, YPAT, EARLY, XFIX, RS>), grid, dim3(kFusedThreads), lds, stream, src, dst, aa);
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
 }
@@ -447,6 +512,14 @@ int launch_tall_impl(const PI *src, P *dst, const FusedArgs<typename PixelTraits
     bool early = !EDGE && pat > 0;
     if constexpr (!PixelTraits<P>::is_integer) early = early && (a.pw_flags & 2) == 0;
     const int xpat = a.mod_form ? 0 : (a.nx == 1 && a.xs[0].causal != 0) ? 1 : (a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0) ? 2 : 0;
+    if (a.rs_tau != nullptr) {      // the row-scan form (FusedArgs::rs_tau): one instance
+        if constexpr (!EDGE && K == 2 && std::is_same<P, float>::value && std::is_same<PI, float>::value) {
+            if (early && pat == 2 && xpat == 2 && a.y_nb_W != nullptr && a.x_nb_W != nullptr && a.rs_G != nullptr && a.y_apply == nullptr)
+                return launch_tall_pat<P, K, EDGE, PI, 2, true, true, true>(src, dst, a, stream);
+        }
+        set_error("fused pass 2: the row-scan form is misconfigured");
+        return RF_ERR_INVALID_ARG;
+    }
     if constexpr (!EDGE) {
         if (early && pat == 1 && xpat == 1) return launch_tall_pat<P, K, EDGE, PI, 1, true, true>(src, dst, a, stream);
         if (early && pat == 2 && xpat == 2) return launch_tall_pat<P, K, EDGE, PI, 2, true, true>(src, dst, a, stream);

@@ -736,6 +736,92 @@ xscan_rows_kernel(FusedArgs<Acc> a, int gj, int TY, const Acc *__restrict__ Hy, 
     }
 }
 
+// Row-scan form of the neighbour-form step (FusedArgs::rs_tau; order 2, 128-row tiles, a causal + anticausal pair in x and in
+// y): pass 1 has run the tile-local x scans of the combined rows itself (kernels_tails_mfma.hip, RS) and the final pass adds
+// the residual to the tails it loads and completes its x carries from the raw tails (kernels_fused_tall.hip, RS).  What is
+// left of xscan_rows_kernel<NB> is tau: per tile and combined row (j, r) the nx * K contractions of the completed x carry strips
+// entering the tile with Hy[vy][j][r] -- the same terms in the same order as there, stored instead of applied.  One 16-lane row
+// per tile fetches the strips once for all ny * K combined rows; 16 consecutive tiles of a tile row per workgroup.
+template <int K>
+__global__ void __launch_bounds__(256)
+xtau_kernel(FusedArgs<float> a, const float *__restrict__ Hy, const float *__restrict__ Wx, float *__restrict__ tau) {
+    typedef float A4 __attribute__((ext_vector_type(4)));
+    constexpr int TY = 128, NXK = 2 * K, NYK = 2 * K;
+    const int t = threadIdx.x;
+    const int l = t & 15, row = t >> 4;
+    const int n_xg = (a.MX + 15) / 16;
+    int b = blockIdx.x;
+    const int xg = b % n_xg; b /= n_xg;
+    const int64_t z = b % a.NZ;
+    const int ty = (int)(b / a.NZ);
+    const int tx = xg * 16 + row;
+    const bool row_ok = tx < a.MX;
+    float tv[NYK][NXK];
+#pragma unroll
+    for (int jr = 0; jr < NYK; jr++)
+#pragma unroll
+        for (int qo = 0; qo < NXK; qo++) tv[jr][qo] = 0.0f;
+    if (row_ok) {
+        const int vy = ((ty == 0 && a.y_first_border) ? 1 : 0) | ((ty == a.MY - 1 && a.y_last_border) ? 2 : 0);
+        const int64_t Lx = a.NYP * a.NZ;
+        const A4 zero4 = A4{0.0f, 0.0f, 0.0f, 0.0f};
+        // the row's 16 lanes split the 128-term sums: four consecutive rows per lane and 64-row block
+#pragma unroll
+        for (int blk = 0; blk < TY; blk += 64) {
+            A4 hy[NYK];
+#pragma unroll
+            for (int jr = 0; jr < NYK; jr++) hy[jr] = *reinterpret_cast<const A4 *>(Hy + (size_t)(vy * NYK + jr) * TY + blk + 4 * l);
+            const int64_t y0 = (int64_t)ty * TY + a.NYP * z + blk + 4 * l;
+            A4 own[K];                  // this tile's causal tail, which the anticausal carry entering it chains on
+#pragma unroll
+            for (int o = 0; o < K; o++)
+                own[o] = tx < a.MX - 1 ? *reinterpret_cast<const A4 *>(a.xt + ((int64_t)tx * K + o) * Lx + y0) : zero4;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                const bool qc = q == 0;
+                const bool q_first = qc ? (tx == 0) : (tx == a.MX - 1);
+                const int tp = qc ? tx - 1 : tx + 1;
+#pragma unroll
+                for (int o = 0; o < K; o++) {
+                    A4 c = zero4;
+                    if (!q_first) c = *reinterpret_cast<const A4 *>(a.xt + (((int64_t)q * a.MX + tp) * K + o) * Lx + y0);
+                    if (q == 1 && !q_first) {       // c_1(tx+1) = tau_1(tx+1) + W_v(tx+1)[0->1] tau_0(tx)
+                        const int vn = (tx + 1 == a.MX - 1) ? 2 : 0;
+                        const float *Wm = Wx + ((vn * 2 + 0) * 2 + 1) * K * K + o * K;
+#pragma unroll
+                        for (int m = 0; m < K; m++) {
+                            const float w = Wm[m];
+                            c.x = c.x + w * own[m].x; c.y = c.y + w * own[m].y;
+                            c.z = c.z + w * own[m].z; c.w = c.w + w * own[m].w;
+                        }
+                    }
+#pragma unroll
+                    for (int jr = 0; jr < NYK; jr++)
+                        tv[jr][q * K + o] = tv[jr][q * K + o] + (hy[jr].x * c.x + hy[jr].y * c.y + hy[jr].z * c.z + hy[jr].w * c.w);
+                }
+            }
+        }
+    }
+    // all-reduce over the 16 lanes of the row: xor 1, xor 2, half mirror, mirror
+#pragma unroll
+    for (int jr = 0; jr < NYK; jr++)
+#pragma unroll
+        for (int qo = 0; qo < NXK; qo++) {
+            tv[jr][qo] = tv[jr][qo] + dpp_move<0xB1>(tv[jr][qo]);
+            tv[jr][qo] = tv[jr][qo] + dpp_move<0x4E>(tv[jr][qo]);
+            tv[jr][qo] = tv[jr][qo] + dpp_move<0x141>(tv[jr][qo]);
+            tv[jr][qo] = tv[jr][qo] + dpp_move<0x140>(tv[jr][qo]);
+        }
+    if (row_ok && l == 0) {
+        float *dst = tau + ((z * a.MY + ty) * a.MX + tx) * (NYK * NXK);
+#pragma unroll
+        for (int jr = 0; jr < NYK; jr++)
+#pragma unroll
+            for (int qo = 0; qo < NXK; qo += 4)
+                *reinterpret_cast<A4 *>(dst + jr * NXK + qo) = A4{tv[jr][qo], tv[jr][qo + 1], tv[jr][qo + 2], tv[jr][qo + 3]};
+    }
+}
+
 }  // namespace
 
 template <typename P>
@@ -898,6 +984,20 @@ int launch_xscan_rows(int K, int TY, const FusedArgs<Acc> &a, const Acc *Hy, con
 #undef RF_CASE
     set_error("xscan rows: unsupported order %d", K);
     return RF_ERR_UNSUPPORTED;
+}
+
+int launch_xtau(const FusedArgs<float> &a, const float *Hy, const float *Wx, float *tau, hipStream_t stream) {
+    if (a.MY <= 0 || a.MX <= 0 || a.NZ <= 0) return RF_OK;
+    if (Hy == nullptr || Wx == nullptr || tau == nullptr || a.nx != 2 || a.ny != 2 || a.mod_form || a.xs[0].causal == 0 || a.xs[1].causal != 0 ||
+        a.last_rows != 128 || a.last_cols != kFusedTX) {
+        set_error("xtau: the row-scan form is misconfigured");
+        return RF_ERR_INVALID_ARG;
+    }
+    const int64_t blocks = (int64_t)a.MY * a.NZ * ((a.MX + 15) / 16);
+    if (blocks >= (1ll << 31)) { set_error("xtau: grid too large"); return RF_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL((xtau_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, stream, a, Hy, Wx, tau);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
 }
 
 template int launch_fused_tails<float>(int, int, const void *, bool, const FusedArgs<float> &, const float *, const float *, hipStream_t);

@@ -56,7 +56,10 @@ __device__ __forceinline__ int row_swz(int row, int c) { return c ^ (row & 15) ^
 // PI: what the planes hold -- float, or a 16-bit float storage type (pixel.h): a thread then fetches its four samples of a row
 // as 8 bytes, keeps them packed until the step's rows are written into the LDS tile, and widens them there; the tile, the
 // contraction and the tails are f32 either way
-template <int K, int TY, int NX, int NY, bool YM, typename PI = float>
+// RS (row-scan form, FusedArgs::rs_tau; f32 planes, YM = false): the kernel also runs the tile-local x scans of the combined
+// rows -- they depend on this tile alone, and the 32 KiB tile stage is free once the step loop is done -- so the y tails it
+// stores are finished but for the cross-dimension residual, which the final pass adds (kernels_fused_tall.hip, RS)
+template <int K, int TY, int NX, int NY, bool YM, typename PI = float, bool RS = false>
 __global__ void __launch_bounds__(kFusedThreads, 4)
 mfma_tails_kernel(const PI *__restrict__ src, FusedArgs<float> a,
                   const float *__restrict__ Hx,     // [vx][s][r][256]
@@ -248,6 +251,44 @@ mfma_tails_kernel(const PI *__restrict__ src, FusedArgs<float> a,
         __syncthreads();                                             // the last step's stage is complete
         flush_xtails(NH - 1);
     }
+    if constexpr (RS) {
+        static_assert(!YM && NX > 0 && NY > 0 && std::is_same<PI, float>::value, "row scans: f32 planes, both dimensions filtered");
+        // The combined rows (thread = column) go into the tile stage -- its last readers passed the barrier above -- as rows of
+        // 256 in the chunk swizzle of xscan_rows_kernel; after one barrier the first wave runs what that kernel runs on them:
+        // one 16-lane row per combined row, 16 samples per lane, every x scan from zero carries.
+        const int e = (swz_chunk(t >> 2) << 2) | (t & 3);
+#pragma unroll
+        for (int jr = 0; jr < NYK; jr++) tile[jr * kFusedTX + e] = comb[jr];
+        __syncthreads();
+        static_assert(NYK <= 4, "row scans: one wave holds the combined rows");
+        if (w == 0 && (lane >> 4) < NYK) {
+            const int l = lane & 15, row = lane >> 4, sw = (l >> 2) & 3;
+            float v[1][kFusedSeg];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const F4 q = tile4[row * 64 + 4 * l + (j ^ sw)];
+                v[0][4 * j + 0] = q.x; v[0][4 * j + 1] = q.y; v[0][4 * j + 2] = q.z; v[0][4 * j + 3] = q.w;
+            }
+            float zero[1][K];
+#pragma unroll
+            for (int j = 0; j < K; j++) zero[0][j] = 0.0f;
+#pragma unroll 1
+            for (int s = 0; s < NX; s++) {
+                const FusedScan<float> &sc = a.xs[s];
+                const bool causal = sc.causal != 0;
+                const bool tile_first = causal ? (tx == 0) : (tx == a.MX - 1);
+                const bool first_lane = causal ? (l == 0) : (l == 15);
+                const bool clamp_first = a.clamped && tile_first && first_lane;
+                if (causal) scan_rows16<float, true, K, 1>(v, sc, first_lane, clamp_first, zero);
+                else        scan_rows16<float, false, K, 1>(v, sc, first_lane, clamp_first, zero, false, kFusedSeg);
+            }
+            float *dst = a.yt + a.yt_index(row / K, ty, row % K, K, (int64_t)tx * kFusedTX + a.NXP * z) + 16 * l;
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                *reinterpret_cast<F4 *>(dst + 4 * j) = F4{v[0][4 * j + 0], v[0][4 * j + 1], v[0][4 * j + 2], v[0][4 * j + 3]};
+        }
+        return;
+    }
     // combined rows -> yt; with x scans in the filter xscan_rows_kernel finishes them in place
     if constexpr (YM) {
         if (nyk > 0) {
@@ -321,6 +362,21 @@ int launch_mfma_tails(int K, int TY, const PI *src, const FusedArgs<float> &a, c
 #undef RF_CASE
     set_error("mfma tails: unsupported order %d / tile height %d / %d + %d scans", K, TY, a.nx, a.ny);
     return RF_ERR_UNSUPPORTED;
+}
+
+int launch_mfma_tails_row_scans(const float *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream) {
+    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
+    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    if (a.nx != 2 || a.ny != 2 || a.last_cols != kFusedTX || a.last_rows != 128 || a.lin_limit != 0 || a.mod_form || (a.pw_flags & 1) ||
+        a.xs[0].causal == 0 || a.xs[1].causal != 0 || a.yt_parts > 1) {
+        set_error("mfma tails: the row-scan form is misconfigured");
+        return RF_ERR_INVALID_ARG;
+    }
+    dim3 grid((unsigned)a.MX, (unsigned)a.MY, (unsigned)a.NZ);
+    const size_t stage_bytes = (size_t)4 * 4 * kRows * sizeof(float);
+    hipLaunchKernelGGL((mfma_tails_kernel<2, 128, 2, 2, false, float, true>), grid, dim3(kFusedThreads), stage_bytes, stream, src, a, Hx, Hy);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
 }
 
 template int launch_mfma_tails<float>(int, int, const float *, const FusedArgs<float> &, const float *, const float *, hipStream_t);

@@ -235,6 +235,7 @@ struct FusedTables {
     const Acc *AMx = nullptr, *AMSx = nullptr;       // per x scan A^MX and (A^MX)^chain_S (device): the row chain of chained rows
     int chain_S = 1;                                 // rows per lane of the row-chain kernel
     bool nb_x = false, nb_y = false;                 // neighbour-form carries (neighbour_carry_bound)
+    bool row_scans = false;                          // the row-scan form of the neighbour-form step (fused_tables)
     bool nb_x_pair() const { return nb_x && x.n == 2; }
     bool nb_y_pair() const { return nb_y && y.n == 2; }
 };
@@ -325,6 +326,26 @@ int fused_tables(rf_plan *plan, const FusedGeometry &g, FusedTables<S, typename 
     // (every dropped transfer crosses a whole tile: neighbour_plan admits unsharded plans only, which hold both borders of both
     // dimensions, so the only partial tile is a last one and the causal carry leaving it is never consumed)
     plan->tables["neighbour_carries"] = {nb_bound_x, t.nb_x ? 1.0 : 0.0, nb_bound_y, t.nb_y ? 1.0 : 0.0};
+
+    // The row-scan form of the neighbour-form step.  With both dimensions in neighbour form nothing between the two passes runs a
+    // recurrence across tiles, and what xscan_rows still does needs no launch that walks the y tails: the tile-local x scans of a
+    // tile's combined rows depend on that tile alone -- pass 1 runs them while it holds the rows (kernels_tails_mfma.hip, RS) --
+    // and the residual is a rank nx * K update per tile, which the final pass adds to the three tails it loads, as it completes
+    // its x carries from the raw tails (kernels_fused_tall.hip, RS).  The middle launch shrinks to the contraction tau
+    // (kernels_tails.hip, xtau_kernel): it reads the x tails once and writes 64 bytes per tile, into the allocation that is
+    // xt_done otherwise.  Taken exactly where pass 1 is mfma_tails_kernel and the final pass the lean 128-row kernel on what the
+    // headline workload runs: f32 planes on both sides, order 2, the pair in x and in y, whole 256 x 128 tiles, no pointwise
+    // stage; RF_PLAN_SEPARATE_ROW_SCANS keeps the three kernels of the neighbour form.
+    if constexpr (std::is_same<P, float>::value) {
+        const int mfma_mode = (plan->flags & RF_PLAN_MFMA_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
+        const int stream_mode = (plan->flags & RF_PLAN_STREAM_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
+        t.row_scans = !(plan->flags & RF_PLAN_SEPARATE_ROW_SCANS) && t.nb_x_pair() && t.nb_y_pair() && K == 2 && g.TY == 128 &&
+                      g.TVx == kFusedTX && g.TVy == 128 && !plan->pw.in_u8 && !plan->pw.out_u8 && !plan->pw.pre && !plan->pw.post &&
+                      !g.padded && !g.in_place_tail && t.xs[0].causal != 0 && t.xs[1].causal == 0 && t.ys[0].causal != 0 && t.ys[1].causal == 0 &&
+                      !stream_tails_applicable(K, g.TY, false, 0, g.TVx, g.TVy, (int64_t)g.MX * g.MY * g.NZ, g.MX, g.NZ, nx * K, ny * K, stream_mode) &&
+                      mfma_tails_applicable(K, g.TY, false, 0, g.TVx, g.TVy, 0, nx, ny, mfma_mode);
+    }
+    plan->tables["row_scans"] = {t.row_scans ? 1.0 : 0.0};
     return status;
 }
 
@@ -459,6 +480,7 @@ struct Pass1Args {
     WalkArgs walk{};
     std::shared_ptr<WalkHook> walk_hook;
     size_t xt_pp = 0;
+    bool row_scans = false;      // FusedTables::row_scans: the instance that also scans the combined rows
 };
 
 // pass 1: tail extraction by contraction with the impulse responses (kernels_tails.hip)
@@ -468,6 +490,7 @@ int launch_pass1(const rf_plan *plan, int pl, const FusedArgs<typename PixelTrai
     const int K = p.K, TY = p.TY;
     const void *in = p.padded ? plan->pad_in[pl] : plan->in[pl];
     if constexpr (std::is_same<P, float>::value) {
+        if (p.row_scans) return launch_mfma_tails_row_scans((const float *)in, a, p.Hx, p.Hy, plan->stream);
         if (p.walk_hook) {
             WalkArgs wa = p.walk;
             wa.zt = p.walk_hook->zt + (size_t)pl * p.walk_hook->zt_stride;
@@ -566,6 +589,7 @@ struct FusedBuilder {
         p1a.stream_mode = (plan->flags & RF_PLAN_STREAM_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
         p1a.mfma_mode = (plan->flags & RF_PLAN_MFMA_PASS1) ? 1 : (plan->flags & RF_PLAN_STAGED_PASS1) ? -1 : 0;
         p1a.walk = walk.args; p1a.walk_hook = walk.hook; p1a.xt_pp = b.xt_pp;
+        p1a.row_scans = t.row_scans;
         Step p1;
         p1.name = walk.hook ? "walk_tails" : "fused_tails";
         p1.run = [plan, fargs = this->fargs, p1a](int pl) { return launch_pass1<P>(plan, pl, fargs(plan, pl), p1a); };
@@ -667,7 +691,18 @@ struct FusedBuilder {
         Acc *const xt_done = b.xt_done;
         const size_t xt_pp = b.xt_pp;
         Step xs;
+        // (the step keeps its name in the row-scan form, where it launches xtau_kernel and scans no row: the step names of a plan
+        //  are what its callers and the suite's launch lists know a neighbour-form step by)
         xs.name = "xscan_rows";
+        if constexpr (std::is_same<Acc, float>::value) {
+            if (t.row_scans) {
+                xs.run = [plan, fargs = this->fargs, d_Hy, d_Wx, xt_done, xt_pp](int pl) {
+                    return launch_xtau(fargs(plan, pl), d_Hy, d_Wx, xt_done + (size_t)pl * xt_pp, plan->stream);
+                };
+                plan->begin_steps.push_back(xs);
+                return;
+            }
+        }
         xs.run = [plan, fargs = this->fargs, K, TY, d_Hy, d_G, merged_cx, nb_x_pair, d_Wx, d_Ax, xt_done, xt_pp](int pl) {
             if (merged_cx)
                 return launch_xscan_rows<Acc>(K, TY, fargs(plan, pl), d_Hy, d_G, plan->stream, d_Wx, d_Ax, xt_done + (size_t)pl * xt_pp);
@@ -699,13 +734,17 @@ struct FusedBuilder {
         const Acc *d_Yapply = this->d_Yapply, *d_Ynb = t.nb_y_pair() ? t.y.dev.base.W : nullptr;
         Acc *const xt_done = (b.merged_cx || t.nb_x_pair()) ? b.xt_done : nullptr;
         const size_t xt_pp = b.xt_pp;
+        // the row-scan form: the allocation of xt_done holds tau, the x tails stay where pass 1 wrote them
+        const bool row_scans = t.row_scans;
+        const Acc *d_Xnb = row_scans ? t.x.dev.base.W : nullptr, *d_G = row_scans ? t.G : nullptr;
         Step p2;
         p2.name = "fused_pass2";
-        p2.run = [plan, fargs = this->fargs, K, TY, d_Yapply, d_Ynb, padded, xt_done, xt_pp](int pl) {
+        p2.run = [plan, fargs = this->fargs, K, TY, d_Yapply, d_Ynb, padded, xt_done, xt_pp, row_scans, d_Xnb, d_G](int pl) {
             FusedArgs<Acc> a = fargs(plan, pl);
             a.y_apply = d_Yapply;
             a.y_nb_W = d_Ynb;
-            if (xt_done) a.xt = xt_done + (size_t)pl * xt_pp;
+            if (row_scans) { a.x_nb_W = d_Xnb; a.rs_G = d_G; a.rs_tau = xt_done + (size_t)pl * xt_pp; }
+            else if (xt_done) a.xt = xt_done + (size_t)pl * xt_pp;
             if constexpr (is_half_pixel<P>::value) {
                 // native 16-bit volume (add_z_stage gave the plan its f32 volume, which only such a plan has): the f32 instances
                 // with a 16-bit source, into the volume the z stage reads
