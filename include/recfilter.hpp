@@ -674,6 +674,9 @@ public:
         return s.str();
     }
     const std::vector<std::string> &schedule_log() const { return *c->schedule_log; }
+    /** Not in the reference: the plan behind realize(), for the rf_plan_* queries of recfilter_amd.h (path, launches,
+     *  workspace); null before compile_jit() / realize(), owned by the filter */
+    const rf_plan *plan() const { return c->plan; }
 
     friend class RecFilterRefVar;
 };

@@ -127,7 +127,13 @@ typedef struct {
  * below 0 store 0, values above 255 store 255, NaN stores 0 -- the reference's consumer cast<uint8_t>(...) computed at the filter.
  * 2-D images whose width is a multiple of 4, with orders <= 3 and at most four scans per dimension, run natively on
  * RF_PATH_TILED_FUSED: the launch list is the RF_IN_U8 plan's, name for name, and its final pass stores the bytes (3 bytes of
- * image traffic per sample instead of 6 and a conversion pass).  Every other plan the RF_IN_U8 plan can run is staged: that
+ * image traffic per sample instead of 6 and a conversion pass).  Volumes (ndim == 3) with scans along z and along x and / or y run
+ * natively too where the depth is a multiple of 32 (the strided z kernels tile it), the width a multiple of 4, orders are <= 3
+ * with at most four scans per dimension, post_input == 0 and none of RF_PLAN_STAGE_HALF / RF_PLAN_INPLACE_Z / RF_PLAN_WALK_PASS1
+ * is set -- under RF_PATH_TILED_FUSED at any size, under RF_PATH_AUTO from 2^21 samples per plane on: the launch list is that of
+ * the RF_IN_U8 plan with RF_PLAN_STAGED_PASS1 without its "pointwise_post" step, the x/y result waits in one plan-owned f32
+ * volume per plane (counted in rf_plan_workspace_bytes, listed as scratch) and the final z pass stores
+ * sat8(post_filtered * v + post_bias).  Every other plan the RF_IN_U8 plan can run is staged: that
  * plan writes plan-owned f32 planes (counted in rf_plan_workspace_bytes, listed as scratch by rf_plan_debug_buffer), one step
  * "convert_out" follows; rf_plan_path reports the inner plan's path.  in == out is allowed (an epilogue with post_input != 0
  * needs out != in, as everywhere).  Planes on both sides must be 4-byte aligned.  Any other dtype, sharded plans and
@@ -188,8 +194,9 @@ typedef struct {
  *                           a final z pass that reads and writes the same addresses runs 4 % slower (its read and write
  *                           fronts chase each other through the same DRAM banks: tools/microbench/zpass_shape.hip) -- as
  *                           long as that volume is at most a third of the device memory free when the plan is built.
- *                           Same kernels, same results either way.  (A native RF_F16 / RF_BF16 volume NEEDS that
- *                           volume, in f32: with this flag such a plan is staged through f32 planes instead.)
+ *                           Same kernels, same results either way.  (A native RF_F16 / RF_BF16 volume and a native
+ *                           RF_IO_U8 byte volume NEED that volume, in f32: with this flag such a plan is staged through
+ *                           f32 planes instead.)
  *   RF_PLAN_FULL_CARRY_SCAN the fused x/y stage runs its carry scans (carry_x / carry_y) for every filter.  Default: an f32
  *                           2-D image (or batched Tuple planes), unsharded, whose scans along a dimension are one scan or
  *                           a causal-then-anticausal pair, completes that dimension's carries from the neighbouring
@@ -205,8 +212,8 @@ typedef struct {
  *   RF_PLAN_STAGE_HALF      RF_F16 / RF_BF16 pixels: the plan is staged through f32 planes even where the fused kernels
  *                           would run it natively -- 2-D images, 1-D signals and volumes alike (same result to the last
  *                           rounding; for comparisons).  RF_IO_U8 planes (rf_input_dtype): the plan is staged through f32
- *                           planes and "convert_out" even where the fused final pass would store the bytes itself.  Ignored
- *                           for every other plan. */
+ *                           planes and "convert_out" even where the fused final pass (2-D images) or the final z pass
+ *                           (volumes) would store the bytes itself.  Ignored for every other plan. */
 #define RF_PLAN_FORCE_EXCHANGE  0x01u
 #define RF_PLAN_TILED_ONLY      0x02u
 #define RF_PLAN_NO_CASCADE      0x04u

@@ -162,6 +162,10 @@ int launch_strided_pass(bool final_pass, int K, int TZ, const P *src, P *dst,
 // the final pass of that dimension from an f32 volume to planes of a 16-bit float storage type (_Float16, __bf16), rounded once
 template <typename PD>
 int launch_strided_final_narrow(int K, int TZ, const float *src, PD *dst, const StridedArgs<float> &a, hipStream_t stream);
+// the final pass of that dimension from an f32 volume to unsigned-byte planes (RF_IO_U8): out = sat8(post_f * v + post_b), converted
+// once (pixel.h); the width a multiple of 4, the planes 4-byte aligned
+int launch_strided_final_u8(int K, int TZ, const float *src, uint8_t *dst, const StridedArgs<float> &a, float post_f, float post_b,
+                            hipStream_t stream);
 
 // Blocked parallel carry scan over the tails of one dimension (kernels_carry.hip); scans
 // [s_begin, s_end) of the dimension in one launch.  AC[s] = A[s]^C, C = carry_chunk_length(M, lines).

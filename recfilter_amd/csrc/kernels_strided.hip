@@ -182,6 +182,97 @@ strided_final_narrow_kernel(const float *__restrict__ src, PD *__restrict__ dst,
     }
 }
 
+// The packed store of the kernel below (built with -DRF_U8_PACKED_STORES: make u8packed): store_row_quad of scan_device.h with
+// rows = z.  The four lanes of a quad own four consecutive x of one row (lines and inner are multiples of 4); they exchange the
+// converted bytes of four z planes (three v_mov_b32_dpp quad_perm) so that lane q holds the four x of plane q, and each stores
+// one dword at `quad_p0` (the quad's first x in plane 0 of the block: 4-byte aligned) + q planes.  64-bit plane offsets.
+__device__ __forceinline__ void store_plane_quad(uint8_t *quad_p0, uint32_t q, int64_t inner, float v0, float v1, float v2, float v3) {
+    const uint32_t b0 = sat8(v0), b1 = sat8(v1), b2 = sat8(v2), b3 = sat8(v3);      // this x's bytes of planes 0 .. 3 of the block
+    auto pick = [&](uint32_t r) { return r == 0u ? b0 : r == 1u ? b1 : r == 2u ? b2 : b3; };
+    const uint32_t g1 = dpp_move<0xB1>(pick(q ^ 1u));       // quad_perm:[1,0,3,2]
+    const uint32_t g2 = dpp_move<0x4E>(pick(q ^ 2u));       // quad_perm:[2,3,0,1]
+    const uint32_t g3 = dpp_move<0x1B>(pick(q ^ 3u));       // quad_perm:[3,2,1,0]
+    const uint32_t word = (pick(q) << (8u * q)) | (g1 << (8u * (q ^ 1u))) | (g2 << (8u * (q ^ 2u))) | (g3 << (8u * (q ^ 3u)));
+    __builtin_nontemporal_store(word, reinterpret_cast<uint32_t *>(quad_p0 + (int64_t)q * inner));
+}
+
+// The final pass of a byte volume's z stage (RF_IO_U8; plan_fused.cpp, "native byte volumes"): strided_final_narrow_kernel with a
+// byte destination -- the f32 volume the x/y stage left, the same addresses, carries, scan patterns and recurrences -- and the
+// affine part of an epilogue on the store: out = sat8(post_f * v + post_b) (pixel.h; 1 and 0 without an epilogue), converted once.
+// A lane owns one x, so a wave stores 64 contiguous bytes per row.  Needs inner % 4 == 0 and lines % 4 == 0 (the plan's rule:
+// the width is a multiple of 4), so that the lanes of a quad are all inside or all outside the volume.
+// (A kernel of its own, for the reason given above.)
+template <int K, int TZ, bool UNI, int PAT>
+__global__ void __launch_bounds__(256)
+strided_final_u8_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, StridedArgs<float> a, float post_f, float post_b) {
+    const int64_t line = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (line >= a.lines) return;
+    const int t = blockIdx.y;
+    const int64_t l0 = (int64_t)blockIdx.x * 256;                    // wave-uniform
+    const int64_t ubase = (l0 / a.inner) * a.n * a.inner + (l0 % a.inner) + (int64_t)t * TZ * a.inner;
+    const int64_t base = UNI ? ubase + threadIdx.x : (line / a.inner) * a.n * a.inner + (line % a.inner) + (int64_t)t * TZ * a.inner;
+    const uint32_t lane = threadIdx.x;
+    float col[TZ];
+#pragma unroll
+    for (int i = 0; i < TZ; i++) {
+        if constexpr (UNI) col[i] = __builtin_nontemporal_load(src + (ubase + (int64_t)i * a.inner) + lane);
+        else col[i] = __builtin_nontemporal_load(src + base + (int64_t)i * a.inner);
+    }
+    auto one_scan = [&](int s, auto causal_tag) __attribute__((always_inline)) {
+        constexpr bool causal = decltype(causal_tag)::value;
+        const FusedScanY<float> &sc = a.scans[s];
+        const bool tile_first = causal ? (t == 0) : (t == a.M - 1);
+        const bool border = causal ? (t == 0 && a.first_is_border) : (t == a.M - 1 && a.last_is_border);
+        float carry[K];
+        if (tile_first) {
+#pragma unroll
+            for (int r = 0; r < K; r++) carry[r] = a.incoming[((int64_t)s * K + r) * a.lines + line];
+        } else {
+            const int tp = causal ? t - 1 : t + 1;
+#pragma unroll
+            for (int r = 0; r < K; r++) carry[r] = a.tails[(((int64_t)s * a.M + tp) * K + r) * a.lines + line];
+        }
+        scan_regs<float, causal, K, TZ>(col, sc, a.clamped && border, carry);
+    };
+    if constexpr (PAT == 1) {
+        one_scan(0, std::true_type{});
+    } else if constexpr (PAT == 2) {
+        one_scan(0, std::true_type{});
+        one_scan(1, std::false_type{});
+    } else {
+#pragma unroll 1
+        for (int s = 0; s < a.n_scans; s++) {
+            if (a.scans[s].causal != 0) one_scan(s, std::true_type{});
+            else one_scan(s, std::false_type{});
+        }
+    }
+    // (the empty asm: every conversion takes the f32 value as the last scan left it in its register, as in the kernel above)
+#ifdef RF_U8_PACKED_STORES
+    const uint32_t q = lane & 3u;
+    uint8_t *const quad = dst + (UNI ? ubase + (int64_t)(lane & ~3u) : base - (int64_t)q);
+#pragma unroll
+    for (int i = 0; i < TZ; i += 4) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            v[j] = col[i + j];
+            asm volatile("" : "+v"(v[j]));
+            v[j] = post_f * v[j] + post_b;
+        }
+        store_plane_quad(quad + (int64_t)i * a.inner, q, a.inner, v[0], v[1], v[2], v[3]);
+    }
+#else
+#pragma unroll
+    for (int i = 0; i < TZ; i++) {
+        float v = col[i];
+        asm volatile("" : "+v"(v));
+        v = post_f * v + post_b;
+        if constexpr (UNI) __builtin_nontemporal_store(sat8(v), dst + (ubase + (int64_t)i * a.inner) + lane);
+        else __builtin_nontemporal_store(sat8(v), dst + base + (int64_t)i * a.inner);
+    }
+#endif
+}
+
 }  // namespace
 
 namespace {
@@ -242,6 +333,38 @@ int launch_strided_final_narrow(int K, int TZ, const float *src, PD *dst, const 
     const size_t lds_bytes = strided_residency_lds();
 #define RF_LAUNCH(KK, TT, UU, PP)                                                                                    \
     { hipLaunchKernelGGL((strided_final_narrow_kernel<PD, KK, TT, UU, PP>), grid, dim3(256), UU ? lds_bytes : 0, stream, src, dst, a); \
+      RF_HIP_CHECK(hipGetLastError()); return RF_OK; }
+#define RF_CASE(KK, TT)                                                                                              \
+    if (K == KK && TZ == TT) {                                                                                        \
+        if (uni && pat == 2) RF_LAUNCH(KK, TT, true, 2)                                                               \
+        if (uni && pat == 1) RF_LAUNCH(KK, TT, true, 1)                                                               \
+        RF_LAUNCH(KK, TT, false, 0)                                                                                   \
+    }
+    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
+    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
+    RF_CASE(1, 128) RF_CASE(2, 128) RF_CASE(3, 128)
+#undef RF_CASE
+#undef RF_LAUNCH
+    set_error("strided path: unsupported order %d / tile %d", K, TZ);
+    return RF_ERR_UNSUPPORTED;
+}
+
+// the final pass from an f32 volume to byte planes (RF_IO_U8): same grid, same variant choice, same residency
+int launch_strided_final_u8(int K, int TZ, const float *src, uint8_t *dst, const StridedArgs<float> &a, float post_f, float post_b,
+                            hipStream_t stream) {
+    if (a.lines <= 0 || a.M <= 0) return RF_OK;
+    if (a.M > 65535) { set_error("strided path: too many tiles"); return RF_ERR_UNSUPPORTED; }
+    if (a.mod_form) { set_error("strided path: scans in mod form are those of f32 plans"); return RF_ERR_INVALID_ARG; }
+    if (a.inner % 4 != 0 || a.lines % 4 != 0 || (reinterpret_cast<uintptr_t>(dst) & 3u) != 0) {
+        set_error("strided path: byte planes need a width that is a multiple of 4 and 4-byte aligned planes");
+        return RF_ERR_INVALID_ARG;
+    }
+    dim3 grid((unsigned)((a.lines + 255) / 256), (unsigned)a.M);
+    const bool uni = strided_uniform(a);
+    const int pat = strided_pattern(a);
+    const size_t lds_bytes = strided_residency_lds();
+#define RF_LAUNCH(KK, TT, UU, PP)                                                                                    \
+    { hipLaunchKernelGGL((strided_final_u8_kernel<KK, TT, UU, PP>), grid, dim3(256), UU ? lds_bytes : 0, stream, src, dst, a, post_f, post_b); \
       RF_HIP_CHECK(hipGetLastError()); return RF_OK; }
 #define RF_CASE(KK, TT)                                                                                              \
     if (K == KK && TZ == TT) {                                                                                        \

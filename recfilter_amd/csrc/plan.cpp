@@ -19,6 +19,7 @@
 #include "sections.h"
 #include "plan_generic.h"
 #include "plan_clamp1d.h"
+#include "plan_strided.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -406,6 +407,15 @@ int build_clamped_1d(const rf_filter_desc *desc, rf_plan *parent) {
 // 2^23 is the smallest size measured with the native form ahead; nothing between 2^21 and 2^23 has been measured.
 constexpr int64_t kHalfVolumeNativeSamples = (int64_t)1 << 23;
 
+// The threshold of native byte volumes (RF_IO_U8; u8_plan_is_native below) under RF_PATH_AUTO: the smallest measured size at which
+// the native step is ahead of the staged one by more than the staged plan's spread against a copy of itself.
+// Measured, one MI355X, order-2 Gaussian along x, y and z with the round trip in / 255, 255 F, native / staged step, two runs
+// (profiles/r14/u8_volume_probe.txt): 128^3 (2^21) 0.81 / 0.83 (56 against 69 us; spread 0.1 us), 128 x 256 x 256 (2^23) 0.60 / 0.59,
+// 256^3 0.60 / 0.60, 512^3 0.47 / 0.46, 1024^3 0.44 / 0.44 (3.54 against 8.08 ms; spread 0.3 ms).  The byte model says 15 / 23 = 0.65.
+// Unlike the 16-bit volumes the staged form runs the same seven launches plus two, so the native form is ahead at 2^21 already;
+// nothing below 2^21 has been measured.
+constexpr int64_t kByteVolumeNativeSamples = (int64_t)1 << 21;
+
 template <typename H>
 int build_staged_half_typed(const rf_filter_desc *desc, rf_plan *parent) {
     rf_filter_desc fd = *desc;
@@ -457,7 +467,8 @@ int build_staged_half(const rf_filter_desc *desc, rf_plan *parent) {
 
 // ---- staged byte-output plans ---------------------------------------------------------------------------------------------
 // RF_IO_U8 (pixel.h, sat8): out = sat8(F_f32(widen(in))), no intermediate ever passes through a byte plane.  The final pass of the
-// fused x/y kernels keeps that contract for 2-D images (plan_fused.cpp, add_pass2).  Every other plan owns one f32 plane per
+// fused x/y kernels keeps that contract for 2-D images (plan_fused.cpp, add_pass2), the final z pass for the volumes
+// u8_plan_is_native admits (add_z_stage, "native byte volumes").  Every other plan owns one f32 plane per
 // image plane and runs
 //     the RF_IN_U8 f32 plan of the same description, from the caller's bytes into those planes -> convert_out
 // (no convert_in: that plan reads the bytes itself; its epilogue's input operand is the caller's plane, never its output).
@@ -728,9 +739,15 @@ bool half_plan_is_native(const rf_filter_desc *desc, const rf_plan *plan) {
 // Byte planes on both sides: native where the fused kernels take the 2-D image as it is -- orders <= 3 (asked BEFORE the rewrite
 // into sections: no byte instance carries border modifications), a width that is a multiple of 4 -- staged everywhere else
 // ("staged byte-output plans" above).  RF_PLAN_STAGE_HALF forces the staged form.
+// A volume is native where its x/y result can wait in an f32 volume of the plan's own in front of the strided z kernels, whose final
+// pass then stores the bytes (plan_fused.cpp, "native byte volumes"): scans along z and along x and/or y, a depth the strided kernels
+// tile, no epilogue with an input operand, none of RF_PLAN_INPLACE_Z / RF_PLAN_WALK_PASS1.  RF_PATH_TILED_FUSED asks for that form
+// at any size, RF_PATH_AUTO takes it from kByteVolumeNativeSamples samples per plane on.
 bool u8_plan_is_native(const rf_filter_desc *desc, const rf_plan *plan) {
     std::string unused;
-    return auto_or_fused(desc) && !(desc->flags & RF_PLAN_STAGE_HALF) && desc->ndim == 2 && fused_plan_applicable(plan, desc, &unused);
+    if (!auto_or_fused(desc) || (desc->flags & RF_PLAN_STAGE_HALF) || !fused_plan_applicable(plan, desc, &unused)) return false;
+    if (desc->ndim == 2) return true;
+    return byte_volume_form(plan) && (desc->path == RF_PATH_TILED_FUSED || plan->total >= kByteVolumeNativeSamples);
 }
 
 // Orders above 3 (lib/split.cpp:575-578 pads any order; the fused kernels stop at 3): with a zero border and float

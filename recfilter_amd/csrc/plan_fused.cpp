@@ -758,7 +758,8 @@ struct FusedBuilder {
             if constexpr (std::is_same<P, float>::value) {
                 // byte planes on both sides (RF_IO_U8; plan.cpp, u8_plan_is_native: an unsharded 2-D image): everything up to
                 // here was the RF_IN_U8 plan's, the final pass stores bytes
-                if (plan->pw.out_u8) {
+                // (a byte VOLUME's final x/y pass is the f32 one below, into the plan's f32 volume: add_z_stage)
+                if (plan->pw.out_u8 && plan->ndim == 2) {
                     a.row_bytes = (uint32_t)a.NX;
                     if (TY == 128) return launch_fused_pass2_tall_u8(K, (const uint8_t *)plan->in[pl], (uint8_t *)plan->out[pl], a, plan->stream);
                     return launch_fused_pass2_u8(K, TY, (const uint8_t *)plan->in[pl], (uint8_t *)plan->out[pl], a, plan->stream);
@@ -806,6 +807,26 @@ struct FusedBuilder {
             }
         }
         int rc;
+        if constexpr (std::is_same<P, float>::value) {
+            // Native byte volumes (RF_IO_U8; plan.cpp, u8_plan_is_native).  The contract is that of the 16-bit storage types below:
+            // nothing may pass through a byte plane before the last store, so the x/y stage's result waits in the intermediate
+            // volume, ALWAYS allocated (host-only plans count it; the free memory is not consulted: the staged form would own an
+            // f32 plane of the same size).  Everything up to the final z pass is the RF_IN_U8 plan's -- the final x/y pass reads
+            // the bytes and writes the volume, pass 1 of z and the carry scan read it -- and the final z pass stores
+            // sat8(post_f * v + post_b) (strided_final_u8_kernel): the affine epilogue rides on the store, there is no
+            // pointwise_post step.  Bytes per sample: 1 + (1 + 4) + 4 + (4 + 1) = 15, against 23 staged.
+            // (build_fused has admitted byte planes for this form alone: plan_strided.h, byte_volume_form)
+            if (plan->pw.out_u8) {
+                for (int pl = 0; pl < plan->n_planes; pl++)
+                    if (plan->mid[pl] == nullptr) plan->mid[pl] = plan->alloc((size_t)plan->total * sizeof(float), false, &status);
+                if (status != RF_OK) return status;
+                const bool post = plan->pw.post;
+                rc = add_strided_dimension<float, S, uint8_t>(plan, 2, /*from_input=*/false, desc, first_begin_step, nullptr, nullptr,
+                                                              post ? (float)plan->pw.post_f : 1.0f, post ? (float)plan->pw.post_b : 0.0f);
+                plan->pw.post_fused = post;        // (no stand-alone step: plan.cpp, add_pointwise_steps)
+                return rc;
+            }
+        }
         if constexpr (is_half_pixel<P>::value) {
             // Native 16-bit volumes.  RF_F16 / RF_BF16 are storage types (pixel.h): nothing may be rounded before the last store,
             // so the x/y stage's result cannot wait in the 16-bit output planes.  It waits in the intermediate volume above, here
@@ -838,9 +859,12 @@ int build_fused(rf_plan *plan, const rf_filter_desc *desc) {
     const FusedGeometry &g = fb.g = fused_geometry<P>(plan);
     if (g.error) { set_error("%s", g.error); return RF_ERR_UNSUPPORTED; }
     // (byte output planes: only the final pass of such an image stores bytes -- nothing else here may ever write them)
-    if (plan->pw.out_u8 && (!std::is_same<P, float>::value || plan->ndim != 2 || plan->sharded() || plan->mod_form || g.chained || g.padded ||
-                            plan->dims[0].N % 4 != 0)) {
-        set_error("fused path: byte output planes need an unsharded 2-D f32 plan of orders <= 3 whose width is a multiple of 4");
+    // (... or the final z pass of a volume whose x/y result waits in an f32 volume of the plan's own: add_z_stage)
+    const bool byte_volume = byte_volume_form(plan);
+    if (plan->pw.out_u8 && (!std::is_same<P, float>::value || (plan->ndim != 2 && !byte_volume) || plan->sharded() || plan->mod_form || g.chained ||
+                            g.padded || plan->dims[0].N % 4 != 0)) {
+        set_error("fused path: byte output planes need an unsharded f32 plan of orders <= 3 whose width is a multiple of 4: a 2-D image, or a "
+                  "volume with scans along z on the strided kernels");
         return RF_ERR_UNSUPPORTED;
     }
     plan->dims[0].T = kFusedTX; plan->dims[0].M = g.chained ? g.N1 / kFusedTX : g.MX;

@@ -30,6 +30,16 @@ inline int strided_tile(const rf_plan *plan, int d) {
     return 0;
 }
 
+// The form of a native byte volume (RF_IO_U8; plan.cpp, u8_plan_is_native; plan_fused.cpp, "native byte volumes"), beyond what the
+// fused x/y stage asks of the RF_IN_U8 image: scans along z on the strided kernels behind an f32 volume of the plan's own, a width
+// that is a multiple of 4, one device, no input operand in the epilogue.  The one statement of the rule: the plan stage that
+// chooses the form and the builder that admits byte planes both ask here.
+inline bool byte_volume_form(const rf_plan *plan) {
+    return plan->ndim == 3 && !plan->dims[2].scan_ids.empty() && strided_tile(plan, 2) > 0 && plan->dims[0].N % 4 == 0 &&
+           !plan->sharded() && !(plan->flags & (RF_PLAN_FORCE_EXCHANGE | RF_PLAN_STAGE_HALF | RF_PLAN_INPLACE_Z | RF_PLAN_WALK_PASS1)) &&
+           !(plan->pw.post && plan->pw.post_i != 0.0);
+}
+
 // What pass 1 of the x/y stage needs to know when it also forms this dimension's tails (kernels_tails_walk.hip): the strided
 // dimension then has no first pass of its own.  Filled by add_strided_dimension.
 struct WalkHook {
@@ -87,9 +97,11 @@ inline bool early_exchange_possible(const rf_plan *plan, int d, const rf_filter_
 // carry planes (`walk_child`, built by the caller), pass 2 on the x/y-filtered output.
 // PD (native 16-bit volumes, plan_fused.cpp): the type of the output planes where it is not P -- P = float is then the type of
 // the plan-owned volume the x/y stage wrote (rf_plan::mid), which both passes read; only the final pass's store knows PD.
+// PD = uint8_t (native byte volumes, RF_IO_U8): the same, and the affine part of the plan's epilogue rides on that store
+// (`post_f`, `post_b`: out = sat8(post_f * v + post_b); no other destination type looks at them).
 template <typename P, typename S, typename PD = P>
 int add_strided_dimension(rf_plan *plan, int d, bool from_input, const rf_filter_desc *desc = nullptr, size_t xy_begin = (size_t)-1,
-                          WalkHook *walk = nullptr, rf_plan *walk_child = nullptr) {
+                          WalkHook *walk = nullptr, rf_plan *walk_child = nullptr, float post_f = 1.0f, float post_b = 0.0f) {
     using Acc = typename PixelTraits<P>::Acc;
     int status = RF_OK;
     DimInfo &di = plan->dims[d];
@@ -192,11 +204,17 @@ int add_strided_dimension(rf_plan *plan, int d, bool from_input, const rf_filter
 
     Step p2;
     p2.name = "strided_pass2_" + dn;
-    p2.run = [plan, sargs, K, TZ, from_input](int pl) {
-        const P *src = from_input ? (const P *)plan->in[pl] : (const P *)plan->xy_result(pl);
-        if constexpr (!std::is_same<PD, P>::value) return launch_strided_final_narrow<PD>(K, TZ, src, (PD *)plan->out[pl], sargs(pl), plan->stream);
-        else return launch_strided_pass<P>(true, K, TZ, src, (P *)plan->out[pl], sargs(pl), plan->stream);
-    };
+    if constexpr (std::is_same<PD, uint8_t>::value) {
+        p2.run = [plan, sargs, K, TZ, post_f, post_b](int pl) {
+            return launch_strided_final_u8(K, TZ, (const float *)plan->xy_result(pl), (uint8_t *)plan->out[pl], sargs(pl), post_f, post_b, plan->stream);
+        };
+    } else {
+        p2.run = [plan, sargs, K, TZ, from_input](int pl) {
+            const P *src = from_input ? (const P *)plan->in[pl] : (const P *)plan->xy_result(pl);
+            if constexpr (!std::is_same<PD, P>::value) return launch_strided_final_narrow<PD>(K, TZ, src, (PD *)plan->out[pl], sargs(pl), plan->stream);
+            else return launch_strided_pass<P>(true, K, TZ, src, (P *)plan->out[pl], sargs(pl), plan->stream);
+        };
+    }
     if (d == outer) plan->finish_steps.push_back(p2);
     else plan->begin_steps.push_back(p2);
     return status;
