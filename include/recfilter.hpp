@@ -736,3 +736,60 @@ inline void tap_filter(const std::vector<const void *> &in_planes, void *out, co
     if (rf_tap_filter(in_planes.data(), (int)in_planes.size(), out, (int)extent.size(), extent.data(), dtype, taps.data(),
                       (int)taps.size(), stream) != RF_OK) throw RecFilterError(rf_last_error_string());
 }
+
+/** Spatially varying first-order scans over 2-D f32 device planes (recfilter_amd.h, rf_var_plan_*): the edge-aware
+ *  counterpart of a recursive Gaussian -- the domain-transform recursive filter runs `+x, -x, +y, -y` with a per-pixel
+ *  feedback.  y[i] = (1 - w[i]) x[i] + w[i] y[i-1] along +dim; -dim couples sample i to i+1 through w[i+1]; element 0 of a weight
+ *  plane along the scanned dimension is never used.
+ *      RecFilterDim x("x", width), y("y", height);
+ *      RecFilterVarying F(x, y);            // extents; the first dimension is the fastest
+ *      F.add_scan(+x, 0); F.add_scan(-x, 0); F.add_scan(+y, 1); F.add_scan(-y, 1);
+ *      F.realize({in}, {wx, wy}, {out});    // device pointers; in == out is allowed
+ *  The plan is built on the first realize() and kept; it owns one workspace: order the realizations of one object. */
+class RecFilterVarying {
+    std::vector<RecFilterDim> dims;
+    std::vector<rf_var_scan_desc> scans;
+    int n_weights = 0;
+    rf_var_plan *plan = nullptr;
+    int plan_planes = 0;
+    void drop() { if (plan) { rf_var_plan_destroy(plan); plan = nullptr; } }
+public:
+    RecFilterVarying(RecFilterDim x, RecFilterDim y) : dims{std::move(x), std::move(y)} {}
+    RecFilterVarying(const RecFilterVarying &) = delete;
+    RecFilterVarying &operator=(const RecFilterVarying &) = delete;
+    ~RecFilterVarying() { drop(); }
+    /** one scan along +dim or -dim with the weight plane `weight_index` of realize() */
+    void add_scan(const RecFilterDimAndCausality &d, int weight_index) {
+        int dim = -1;
+        for (size_t i = 0; i < dims.size(); i++) if (dims[i].var() == d.var()) dim = (int)i;
+        if (dim < 0) throw RecFilterError("add_scan: '" + d.var() + "' is not a dimension of this filter");
+        if (weight_index < 0) throw RecFilterError("add_scan: negative weight index");
+        scans.push_back(rf_var_scan_desc{dim, d.causal() ? 1 : 0, weight_index});
+        n_weights = std::max(n_weights, weight_index + 1);
+        drop();
+    }
+    int num_kernels() const { return plan ? rf_var_plan_num_kernels(plan) : 0; }
+    /** in / out: one device plane per channel; weights: the planes add_scan indexed.  Asynchronous on `stream`. */
+    void realize(const std::vector<const void *> &in, const std::vector<const void *> &weights, const std::vector<void *> &out,
+                 void *stream = nullptr) {
+        if (in.empty() || in.size() != out.size()) throw RecFilterError("realize: as many output planes as input planes, at least one");
+        if ((int)weights.size() < n_weights) throw RecFilterError("realize: a scan indexes a weight plane that was not passed");
+        if (!plan || plan_planes != (int)in.size()) {
+            drop();
+            rf_var_desc d{};
+            d.ndim = 2;
+            d.abi = RF_ABI;
+            d.extent[0] = dims[0].num_pixels();
+            d.extent[1] = dims[1].num_pixels();
+            d.dtype = RF_F32;
+            d.n_planes = (int)in.size();
+            d.n_weights = std::max(n_weights, 1);
+            d.n_scans = (int)scans.size();
+            d.scans = scans.data();
+            d.device = -1;
+            if (rf_var_plan_create(&d, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
+            plan_planes = (int)in.size();
+        }
+        if (rf_var_plan_execute(plan, in.data(), weights.data(), out.data(), stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+};

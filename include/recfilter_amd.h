@@ -415,6 +415,62 @@ int rf_tap_filter(const void *const *in_planes, int n_in, void *out, int ndim, c
  * (roofline.copy_ceiling_gbps).  src != dst.  Nothing of the filter path calls it. */
 int rf_stream_copy(const float *src, float *dst, int64_t width, int64_t rows, void *stream);
 
+/* ---- spatially varying first-order scans (edge-aware smoothing) ------------------------------------------------------ */
+/* A recurrence whose feedback changes from sample to sample: what the domain-transform recursive filter (Gastal & Oliveira
+ * 2011) runs along x and along y with a per-pixel feedback a^d.  Nothing of rf_filter_desc can express it (a plan there turns
+ * CONSTANT coefficients into tables); this family stands beside it, with the same three-stage tiling (tile-local tails, the
+ * carry recurrence across tiles, a correction pass) whose carry operators are read from a weight plane.
+ *
+ * Planes are dense f32, x fastest, 2-D.  A weight plane has the image's extents; element i along the scanned dimension holds
+ * the coupling between sample i-1 and sample i; element 0 is NEVER USED (it is masked by a select: a NaN stored there reaches
+ * no output).  Values are expected in [0, 1]; anything else is the caller's business and NaN propagates.  With w~[0] = 0,
+ * w~[N] = 0 and w~[i] = w[i] otherwise, along a line x[0..N):
+ *     causal      (+d):  y[i] = (1 - w~[i])   * x[i] + w~[i]   * y[i-1]     i = 0 .. N-1   (y[0]   = x[0])
+ *     anticausal  (-d):  y[i] = (1 - w~[i+1]) * x[i] + w~[i+1] * y[i+1]     i = N-1 .. 0   (y[N-1] = x[N-1])
+ * A plan is a list of at most RF_VAR_MAX_SCANS scans (dim, causal, weights), applied in the order given; `weights` indexes the
+ * weight planes handed to execute.  All n_planes image planes share the weight planes (the channels of an RGB image see the
+ * same edges).  A +d scan directly followed by the -d scan of the same dimension and weight plane runs as ONE stage where
+ * the two are a run of their own (the scans before and behind them, if any, are along the other dimension); every other scan
+ * is a stage of its own (-d +d: two stages; +d -d +d along one dimension: three).  Every
+ * stage is three launches ("var_tails_x|y", "var_carry", "var_pass2_x|y": rf_var_plan_num_kernels = 3 per stage).  The first
+ * stage reads `in`, later stages filter `out` in place.  in == out is allowed; a weight plane must not overlap an output plane;
+ * image and weight planes must be 16-byte aligned (RF_ERR_INVALID_ARG otherwise).
+ * The plan owns ONE workspace (tails and carries, about 7/64 of the image planes): executes of one plan are ordered by the
+ * caller -- one stream, or the caller's own synchronisation; concurrent executes of one plan are not supported.
+ * Refused: ndim != 2, dtype != RF_F32, a width that is not a multiple of 4 (RF_ERR_UNSUPPORTED); abi != RF_ABI, n_scans outside
+ * 1..RF_VAR_MAX_SCANS, dim outside 0..1, weights outside 0..n_weights-1, n_planes outside 1..RF_MAX_PLANES, n_weights outside
+ * 1..RF_VAR_MAX_SCANS, extents below 1, nonzero flags (RF_ERR_INVALID_ARG).  A host-only plan (device = RF_DEVICE_HOST_ONLY)
+ * answers the queries and refuses to execute with RF_ERR_HIP. */
+#define RF_VAR_MAX_SCANS 8
+typedef struct {
+    int32_t dim;                      /* 0 = x (fastest), 1 = y                                  */
+    int32_t causal;                   /* 1 = +dim, 0 = -dim                                      */
+    int32_t weights;                  /* index into the weight planes                            */
+} rf_var_scan_desc;
+typedef struct {
+    int32_t  ndim;                    /* 2                                                       */
+    uint32_t abi;                     /* RF_ABI                                                  */
+    int64_t  extent[RF_MAX_DIMS];     /* extent[0] = width (x)                                   */
+    int32_t  dtype;                   /* RF_F32                                                  */
+    int32_t  n_planes;                /* 1..RF_MAX_PLANES                                        */
+    int32_t  n_weights;               /* 1..RF_VAR_MAX_SCANS                                     */
+    int32_t  n_scans;
+    const rf_var_scan_desc *scans;    /* in application order                                    */
+    int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
+    uint32_t flags;                   /* 0                                                       */
+} rf_var_desc;
+typedef struct rf_var_plan rf_var_plan;
+int    rf_var_plan_create(const rf_var_desc *desc, rf_var_plan **plan_out);
+int    rf_var_plan_destroy(rf_var_plan *plan);
+size_t rf_var_plan_workspace_bytes(const rf_var_plan *plan);
+int    rf_var_plan_num_kernels(const rf_var_plan *plan);
+/* in_planes / out_planes: n_planes device pointers each; weight_planes: n_weights device pointers.  Asynchronous on `stream`. */
+int    rf_var_plan_execute(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                           void *const *out_planes, void *stream);
+/* as rf_plan_execute_timed: per-kernel milliseconds and names (valid for the life of the plan); synchronises the stream */
+int    rf_var_plan_execute_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                                 void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);
 const char *rf_version(void);

@@ -20,6 +20,7 @@ RF_MAX_ORDER = 32
 RF_ABI = 3          # revision of include/recfilter_amd.h this module mirrors (rf_filter_desc.abi)
 RF_MAX_SCANS = 32
 RF_MAX_PLANES = 16
+RF_VAR_MAX_SCANS = 8     # scans (and weight planes) of a plan of spatially varying scans (rf_var_desc)
 RF_DEVICE_HOST_ONLY = -2
 
 RF_OK, RF_ERR_INVALID_ARG, RF_ERR_UNSUPPORTED, RF_ERR_HIP, RF_ERR_NOMEM, RF_ERR_STATE = range(6)
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "rf_plan_begin", "rf_plan_exchange_local", "rf_plan_exchange_apply", "rf_plan_has_interior", "rf_plan_interior", "rf_plan_finish", "rf_plan_abort",
     "rf_plan_table", "rf_plan_debug_buffer", "rf_plan_debug_buffer_kind", "rf_plan_debug_fill", "rf_gaussian_weights", "rf_integral_image_coeff", "rf_overlap_feedback_coeff",
     "rf_gaussian_box_filter", "rf_box_difference", "rf_tap_filter", "rf_stream_copy", "rf_last_error_string", "rf_version", "rf_device_count",
+    "rf_var_plan_create", "rf_var_plan_destroy", "rf_var_plan_workspace_bytes", "rf_var_plan_num_kernels", "rf_var_plan_execute",
+    "rf_var_plan_execute_timed",
 ]
 
 
@@ -89,6 +92,17 @@ class FilterDesc(ctypes.Structure):
 
 class Tap(ctypes.Structure):
     _fields_ = [("plane", ctypes.c_int32), ("offset", ctypes.c_int32 * RF_MAX_DIMS), ("weight", ctypes.c_float)]
+
+
+class VarScanDesc(ctypes.Structure):
+    _fields_ = [("dim", ctypes.c_int32), ("causal", ctypes.c_int32), ("weights", ctypes.c_int32)]
+
+
+class VarDesc(ctypes.Structure):
+    _fields_ = [("ndim", ctypes.c_int32), ("abi", ctypes.c_uint32), ("extent", ctypes.c_int64 * RF_MAX_DIMS),
+                ("dtype", ctypes.c_int32), ("n_planes", ctypes.c_int32), ("n_weights", ctypes.c_int32),
+                ("n_scans", ctypes.c_int32), ("scans", ctypes.POINTER(VarScanDesc)),
+                ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class RecFilterError(RuntimeError):
@@ -160,6 +174,13 @@ def lib() -> ctypes.CDLL:
     L.rf_stream_copy.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp]
     L.rf_tap_filter.argtypes = [vpp, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
                                 ctypes.POINTER(Tap), ctypes.c_int, vp]
+    L.rf_var_plan_create.argtypes = [ctypes.POINTER(VarDesc), vpp]
+    L.rf_var_plan_destroy.argtypes = [vp]
+    L.rf_var_plan_workspace_bytes.argtypes = [vp]
+    L.rf_var_plan_workspace_bytes.restype = ctypes.c_size_t
+    L.rf_var_plan_num_kernels.argtypes = [vp]
+    L.rf_var_plan_execute.argtypes = [vp, vpp, vpp, vpp, vp]
+    L.rf_var_plan_execute_timed.argtypes = [vp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

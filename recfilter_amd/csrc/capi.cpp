@@ -3,8 +3,11 @@
 #include <cmath>
 #include <complex>
 #include <cstring>
+#include <exception>
+#include <new>
 
 #include "plan.h"
+#include "plan_var.h"
 
 namespace rf {
 
@@ -154,6 +157,24 @@ int run_pending_interior(rf_plan *plan) {
     if (!plan->interior_pending) return RF_OK;
     plan->interior_pending = false;
     return run_steps(plan, plan->interior_steps);
+}
+
+
+// Fenced bodies: whatever the builder or the driver throws (std::bad_alloc of a host vector) becomes a status.
+template <typename F>
+int fenced(const char *what, F &&body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", what);
+        return RF_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        set_error("%s: %s", what, e.what());
+        return RF_ERR_INVALID_ARG;
+    } catch (...) {
+        set_error("%s: unknown exception", what);
+        return RF_ERR_INVALID_ARG;
+    }
 }
 
 }  // namespace
@@ -525,6 +546,40 @@ int rf_tap_filter(const void *const *in_planes, int n_in, void *out, int ndim, c
     if (dtype == RF_F64) return launch_tap_filter<double>((double *)out, a, (hipStream_t)stream);
     set_error("tap_filter needs a floating-point pixel type");
     return RF_ERR_UNSUPPORTED;
+}
+
+// ---- spatially varying first-order scans (plan_var.cpp) ---------------------------------------------------------------------
+int rf_var_plan_create(const rf_var_desc *desc, rf_var_plan **plan_out) {
+    return fenced("rf_var_plan_create", [&] { return build_var_plan(desc, plan_out); });
+}
+
+int rf_var_plan_destroy(rf_var_plan *plan) {
+    return fenced("rf_var_plan_destroy", [&] {
+        if (plan) {
+            if (!plan->host_only) (void)hipSetDevice(plan->device);
+            delete plan;
+        }
+        return (int)RF_OK;
+    });
+}
+
+size_t rf_var_plan_workspace_bytes(const rf_var_plan *plan) { return plan ? plan->workspace_bytes() : 0; }
+int rf_var_plan_num_kernels(const rf_var_plan *plan) { return plan ? (int)plan->names.size() : 0; }
+
+int rf_var_plan_execute(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, void *const *out_planes,
+                        void *stream) {
+    return fenced("rf_var_plan_execute", [&] { return run_var_plan(plan, in_planes, weight_planes, out_planes, (hipStream_t)stream, nullptr); });
+}
+
+int rf_var_plan_execute_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                              void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var_plan_execute_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
+        if (names_out)
+            for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
+        return run_var_plan(plan, in_planes, weight_planes, out_planes, (hipStream_t)stream, ms_out);
+    });
 }
 
 const char *rf_last_error_string(void) { return g_last_error.c_str(); }

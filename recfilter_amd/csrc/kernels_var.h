@@ -1,0 +1,38 @@
+// kernels_var.h -- launchers of the spatially varying first-order scans (kernels_var.hip; plan_var.cpp drives them).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "rf_internal.h"
+
+namespace rf {
+
+constexpr int kVarTile = 64;        // samples of a tile along the scanned dimension
+constexpr int kVarComponents = 5;   // tail slots per tile and line: E1, P1, E2, G, P2
+enum VarComponent { VAR_E1 = 0, VAR_P1 = 1, VAR_E2 = 2, VAR_G = 3, VAR_P2 = 4 };
+// what a stage runs: one causal scan, one anticausal scan, or a causal scan directly followed by the anticausal one
+enum VarMode { VAR_CAUSAL = 0, VAR_ANTICAUSAL = 1, VAR_PAIR = 2 };
+
+// One stage on all planes of an image.  `lines` lines of `n` samples along the scanned dimension, `tiles` tiles of kVarTile.
+//   tails [tile][component][plane][line]   E1 / E2 per image plane; P1 / G / P2 depend on the weights alone: plane 0 holds them
+//   carry [tile][c, d][plane][line]        what enters tile `tile` from the left (c) and from the right (d)
+struct VarArgs {
+    const float *src[RF_MAX_PLANES];
+    float *dst[RF_MAX_PLANES];
+    const float *weights;
+    float *tails;
+    float *carry;
+    int32_t width, height;          // x fastest
+    int32_t n_planes;
+    int32_t tiles;
+    int32_t lines;
+    int32_t mode;                   // VarMode
+};
+
+int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
+int launch_var_carry(const VarArgs &a, hipStream_t stream);
+int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream);
+
+}  // namespace rf

@@ -1,0 +1,324 @@
+// kernels_var.hip -- first-order scans whose feedback changes from sample to sample (edge-aware smoothing by the
+// domain-transform recursive filter, Gastal & Oliveira 2011).
+//
+//   causal (+d):      y[i] = (1 - w[i])   * x[i] + w[i]   * y[i-1]         w[0] and w[N] count as 0: a select, never a product
+//   anticausal (-d):  y[i] = (1 - w[i+1]) * x[i] + w[i+1] * y[i+1]
+//
+// The three-stage tiling of the constant-coefficient paths with the carry operators read from the weight plane instead of a
+// table.  A stage is one scan, or a causal scan directly followed by the anticausal scan on the same weights (VAR_PAIR).
+// Tile [t0, t1) of a line, zero entry:  u = local causal scan of x,  p[i] = w[t0] * ... * w[i]  (so y = u + p * c_t),
+// v_u / v_p = local anticausal scans of u / p,  q[t0] = w[t0+1] * ... * w[t1]:
+//   var_tails_x / var_tails_y   E1 = u[t1-1], P1 = p[t1-1], E2 = v_u[t0], G = v_p[t0], P2 = q[t0]   (a single scan: its two)
+//   var_carry                   c_0 = 0, c_{t+1} = E1_t + P1_t c_t;   d_{M-1} = 0, d_{t-1} = E2_t + G_t c_t + P2_t d_t
+//   var_pass2_x / var_pass2_y   reloads the tile, reruns the recurrence(s) from c_t and d_t, stores
+// The final pass RERUNS the recurrences (it does not superpose u + p c): weights of exactly 0 and 1 give exact results.
+//
+// One lane owns the 64 samples of a line's tile in registers, with the 65 weights that couple them (w[t1] belongs to the next
+// tile: the anticausal scan enters through it).  Along y the lane is a column: every access of a wave is 256 contiguous bytes,
+// no LDS.  Along x a workgroup of one wave takes 64 rows x 64 columns: 16-byte row loads, a transposition through LDS rows
+// padded to 68 dwords (ds_write_b128 and ds_read_b128 both conflict-free), the scan, the way back, 16-byte stores.
+// Samples a partial tile misses are loaded from a safe address inside the plane and selected away where they are consumed
+// (image 0, weight 0); they are never stored.  A workgroup has loaded its whole tile before it stores: in == out is legal.
+#include "kernels_var.h"
+
+namespace rf {
+
+namespace {
+
+constexpr int T = kVarTile;
+constexpr int LDS_PITCH = T + 4;      // dwords: rows stay 16-byte aligned, lane l starts on bank 4 l
+
+__device__ __forceinline__ float step(float w, float x, float prev) { return __builtin_fmaf(w, prev, (1.0f - w) * x); }
+
+// The anticausal scan needs 1 - w[i+1], the causal one 1 - w[i]: left alone, the compiler keeps the 64 differences of one scan
+// in registers for the next (and for the weight-only scans behind them) -- a wave less per SIMD.  Behind this fence it forms
+// them again, one instruction per sample.  (An empty statement: it emits nothing and touches no memory.)
+__device__ __forceinline__ void forget_differences(float (&w)[T + 1]) {
+#pragma unroll
+    for (int i = 0; i <= T; i++) asm volatile("" : "+v"(w[i]));
+}
+
+// tile-local tails; x: the tile's samples (destroyed), w: the masked weights w[t0 .. t1]
+template <int MODE>
+__device__ __forceinline__ void tile_tails(float (&x)[T], float (&w)[T + 1], bool weights_too, float (&out)[kVarComponents]) {
+    // One sweep for the three that depend on the weights alone (plane 0 forms them; wave-uniform).  G = v_p[t0] is the
+    // anticausal recurrence over p written out:  G = sum_i qq[i] * (1 - w[i+1]) * p[i],  qq[i] = w[t0+1] * ... * w[i]
+    // (no array of p; exact for weights of 0 and 1).
+    out[VAR_P1] = out[VAR_G] = out[VAR_P2] = 0.0f;
+    if (weights_too) {
+        float p = w[0], qq = 1.0f, g = 0.0f;
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            if (i > 0) { p *= w[i]; qq *= w[i]; }
+            if constexpr (MODE == VAR_PAIR) g = __builtin_fmaf(qq * (1.0f - w[i + 1]), p, g);
+        }
+        out[VAR_P1] = p;
+        out[VAR_G] = g;
+        out[VAR_P2] = qq * w[T];
+        if constexpr (MODE != VAR_CAUSAL) forget_differences(w);
+    }
+    if constexpr (MODE != VAR_ANTICAUSAL) {
+        float prev = 0.0f;
+#pragma unroll
+        for (int i = 0; i < T; i++) { x[i] = step(w[i], x[i], prev); prev = x[i]; }
+        out[VAR_E1] = prev;
+        if constexpr (MODE == VAR_PAIR) forget_differences(w);
+    }
+    if constexpr (MODE != VAR_CAUSAL) {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = T - 1; i >= 0; i--) v = step(w[i + 1], x[i], v);
+        out[VAR_E2] = v;
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void tile_final(float (&x)[T], float (&w)[T + 1], float c, float d) {
+    if constexpr (MODE != VAR_ANTICAUSAL) {
+        float prev = c;
+#pragma unroll
+        for (int i = 0; i < T; i++) { x[i] = step(w[i], x[i], prev); prev = x[i]; }
+        if constexpr (MODE == VAR_PAIR) forget_differences(w);
+    }
+    if constexpr (MODE != VAR_CAUSAL) {
+        float v = d;
+#pragma unroll
+        for (int i = T - 1; i >= 0; i--) { x[i] = step(w[i + 1], x[i], v); v = x[i]; }
+    }
+}
+
+// samples and weights beyond the line's end, and the weight of element 0, selected away
+__device__ __forceinline__ void mask_tile(float (&x)[T], float (&w)[T + 1], int t0, int n) {
+#pragma unroll
+    for (int i = 0; i < T; i++) x[i] = t0 + i < n ? x[i] : 0.0f;
+#pragma unroll
+    for (int i = 0; i <= T; i++) w[i] = (t0 + i == 0 || t0 + i >= n) ? 0.0f : w[i];
+}
+
+__device__ __forceinline__ int64_t tail_index(const VarArgs &a, int t, int comp, int pl, int line) {
+    return (((int64_t)t * kVarComponents + comp) * a.n_planes + pl) * a.lines + line;
+}
+__device__ __forceinline__ int64_t carry_index(const VarArgs &a, int t, int which, int pl, int line) {
+    return (((int64_t)t * 2 + which) * a.n_planes + pl) * a.lines + line;
+}
+
+template <int MODE>
+__device__ __forceinline__ void store_tails(const VarArgs &a, int t, int pl, int line, const float (&out)[kVarComponents]) {
+    if constexpr (MODE != VAR_ANTICAUSAL) a.tails[tail_index(a, t, VAR_E1, pl, line)] = out[VAR_E1];
+    if constexpr (MODE != VAR_CAUSAL) a.tails[tail_index(a, t, VAR_E2, pl, line)] = out[VAR_E2];
+    if (pl != 0) return;
+    if constexpr (MODE != VAR_ANTICAUSAL) a.tails[tail_index(a, t, VAR_P1, 0, line)] = out[VAR_P1];
+    if constexpr (MODE == VAR_PAIR) a.tails[tail_index(a, t, VAR_G, 0, line)] = out[VAR_G];
+    if constexpr (MODE != VAR_CAUSAL) a.tails[tail_index(a, t, VAR_P2, 0, line)] = out[VAR_P2];
+}
+
+// ---- along y: lane = column -------------------------------------------------------------------------------------------
+template <int MODE, bool FINAL>
+__global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
+    const int col = blockIdx.x * 64 + threadIdx.x;
+    if (col >= a.width) return;                       // (no barrier below: lanes are independent)
+    const int t = blockIdx.y, pl = blockIdx.z, t0 = t * T;
+    const int64_t pitch = a.width;
+    const float *src = a.src[pl];
+    float x[T], w[T + 1];
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int r = min(t0 + i, a.height - 1);      // wave-uniform row: a scalar base and the lane's column
+        x[i] = (src + r * pitch)[col];
+        w[i] = (a.weights + r * pitch)[col];
+    }
+    w[T] = 0.0f;
+    if constexpr (MODE != VAR_CAUSAL) w[T] = (a.weights + min(t0 + T, a.height - 1) * pitch)[col];
+    float c = 0.0f, d = 0.0f;
+    if constexpr (FINAL) {
+        if constexpr (MODE != VAR_ANTICAUSAL) c = a.carry[carry_index(a, t, 0, pl, col)];
+        if constexpr (MODE != VAR_CAUSAL) d = a.carry[carry_index(a, t, 1, pl, col)];
+    }
+    mask_tile(x, w, t0, a.height);
+    if constexpr (FINAL) {
+        tile_final<MODE>(x, w, c, d);
+        float *dst = a.dst[pl];
+#pragma unroll
+        for (int i = 0; i < T; i++)
+            if (t0 + i < a.height) (dst + (t0 + i) * pitch)[col] = x[i];
+    } else {
+        float out[kVarComponents];
+        tile_tails<MODE>(x, w, pl == 0, out);
+        store_tails<MODE>(a, t, pl, col, out);
+    }
+}
+
+// ---- along x: workgroup = one wave = 64 rows x 64 columns, lane = row after the transposition -----------------------------
+// request k of a lane: row (k * 64 + lane) / 16 of the tile, 16-byte chunk (k * 64 + lane) % 16 -- a wave instruction moves four
+// rows of 256 contiguous bytes
+__device__ __forceinline__ void request_tile(const float *plane, const VarArgs &a, int r0, int c0, float (&v)[T]) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < T / 4; k++) {
+        const int flat = k * 64 + lane;
+        const int r = min(r0 + (flat >> 4), a.height - 1);
+        const int c = min(c0 + (flat & 15) * 4, a.width - 4);      // (the width is a multiple of 4)
+        const float4 q = *reinterpret_cast<const float4 *>(plane + (int64_t)r * a.width + c);
+        v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+    }
+}
+
+// chunks as requested -> the lane's row of the tile
+__device__ __forceinline__ void transpose_in(const float (&v)[T], float *lds, float (&row)[T]) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < T / 4; k++) {
+        const int flat = k * 64 + lane;
+        *reinterpret_cast<float4 *>(lds + (flat >> 4) * LDS_PITCH + (flat & 15) * 4) = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < T / 4; k++) {
+        const float4 q = *reinterpret_cast<const float4 *>(lds + lane * LDS_PITCH + k * 4);
+        row[4 * k] = q.x; row[4 * k + 1] = q.y; row[4 * k + 2] = q.z; row[4 * k + 3] = q.w;
+    }
+    __syncthreads();
+}
+
+template <int MODE, bool FINAL>
+__global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int t = blockIdx.x, pl = blockIdx.z, t0 = t * T, r0 = blockIdx.y * 64;
+    const int row = r0 + lane;
+    const float *src = a.src[pl];
+    float vx[T], vw[T];
+    request_tile(src, a, r0, t0, vx);
+    request_tile(a.weights, a, r0, t0, vw);
+    float w_next = 0.0f;                             // w[t1], the next tile's first weight
+    if constexpr (MODE != VAR_CAUSAL) w_next = a.weights[(int64_t)min(row, a.height - 1) * a.width + min(t0 + T, a.width - 1)];
+    float c = 0.0f, d = 0.0f;
+    if constexpr (FINAL) {
+        const int line = min(row, a.height - 1);
+        if constexpr (MODE != VAR_ANTICAUSAL) c = a.carry[carry_index(a, t, 0, pl, line)];
+        if constexpr (MODE != VAR_CAUSAL) d = a.carry[carry_index(a, t, 1, pl, line)];
+    }
+    float x[T], wt[T], w[T + 1];
+    transpose_in(vx, lds, x);
+    transpose_in(vw, lds, wt);
+#pragma unroll
+    for (int i = 0; i < T; i++) w[i] = wt[i];
+    w[T] = w_next;
+    mask_tile(x, w, t0, a.width);
+    __builtin_amdgcn_sched_barrier(0);      // (the scans stay behind the transposition: they would hold its registers)
+    if constexpr (FINAL) {
+        tile_final<MODE>(x, w, c, d);
+#pragma unroll
+        for (int k = 0; k < T / 4; k++)
+            *reinterpret_cast<float4 *>(lds + lane * LDS_PITCH + k * 4) = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
+        __syncthreads();
+        float *dst = a.dst[pl];
+#pragma unroll
+        for (int k = 0; k < T / 4; k++) {
+            const int flat = k * 64 + lane;
+            const int r = r0 + (flat >> 4), col = t0 + (flat & 15) * 4;
+            const float4 q = *reinterpret_cast<const float4 *>(lds + (flat >> 4) * LDS_PITCH + (flat & 15) * 4);
+            if (r < a.height && col < a.width) *reinterpret_cast<float4 *>(dst + (int64_t)r * a.width + col) = q;
+        }
+    } else {
+        float out[kVarComponents];
+        tile_tails<MODE>(x, w, pl == 0, out);
+        if (row < a.height) store_tails<MODE>(a, t, pl, row, out);
+    }
+}
+
+// ---- carries: one lane per line and plane -----------------------------------------------------------------------------------
+// The tails of CHUNK tiles are requested together, ahead of the recurrence that consumes them (tiles past the end: the last
+// tile's, not consumed).
+template <int MODE>
+__global__ void __launch_bounds__(256) var_carry_kernel(VarArgs a) {
+    constexpr int CHUNK = 8;
+    const int line = blockIdx.x * 256 + threadIdx.x;
+    if (line >= a.lines) return;
+    const int pl = blockIdx.y, M = a.tiles;
+    if constexpr (MODE != VAR_ANTICAUSAL) {
+        float c = 0.0f;
+        for (int tb = 0; tb < M; tb += CHUNK) {
+            float e[CHUNK], p[CHUNK];
+#pragma unroll
+            for (int j = 0; j < CHUNK; j++) {
+                const int t = min(tb + j, M - 1);
+                e[j] = a.tails[tail_index(a, t, VAR_E1, pl, line)];
+                p[j] = a.tails[tail_index(a, t, VAR_P1, 0, line)];
+            }
+#pragma unroll
+            for (int j = 0; j < CHUNK; j++) {
+                if (tb + j < M) {
+                    a.carry[carry_index(a, tb + j, 0, pl, line)] = c;
+                    c = __builtin_fmaf(p[j], c, e[j]);
+                }
+            }
+        }
+    }
+    if constexpr (MODE != VAR_CAUSAL) {
+        float d = 0.0f;
+        for (int tb = M - 1; tb >= 0; tb -= CHUNK) {
+            float e[CHUNK], p[CHUNK], g[CHUNK], c[CHUNK];
+#pragma unroll
+            for (int j = 0; j < CHUNK; j++) {
+                const int t = max(tb - j, 0);
+                e[j] = a.tails[tail_index(a, t, VAR_E2, pl, line)];
+                p[j] = a.tails[tail_index(a, t, VAR_P2, 0, line)];
+                g[j] = 0.0f; c[j] = 0.0f;
+                if constexpr (MODE == VAR_PAIR) {
+                    g[j] = a.tails[tail_index(a, t, VAR_G, 0, line)];
+                    c[j] = a.carry[carry_index(a, t, 0, pl, line)];       // (this lane wrote it above)
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < CHUNK; j++) {
+                if (tb - j >= 0) {
+                    a.carry[carry_index(a, tb - j, 1, pl, line)] = d;
+                    d = __builtin_fmaf(p[j], d, e[j]);
+                    if constexpr (MODE == VAR_PAIR) d = __builtin_fmaf(g[j], c[j], d);
+                }
+            }
+        }
+    }
+}
+
+int launched(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
+    return RF_OK;
+}
+
+template <bool FINAL>
+int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
+    const int cross = dim == 0 ? a.height : a.width;          // lines, 64 per workgroup
+    const dim3 block(64);
+    const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)a.n_planes)
+                               : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)a.n_planes);
+#define RF_VAR_LAUNCH(MODE)                                                                        \
+    if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL>), grid, block, 0, stream, a);      \
+    else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL>), grid, block, 0, stream, a)
+    switch (a.mode) {
+        case VAR_CAUSAL: RF_VAR_LAUNCH(VAR_CAUSAL); break;
+        case VAR_ANTICAUSAL: RF_VAR_LAUNCH(VAR_ANTICAUSAL); break;
+        default: RF_VAR_LAUNCH(VAR_PAIR); break;
+    }
+#undef RF_VAR_LAUNCH
+    return launched(FINAL ? (dim == 0 ? "var_pass2_x" : "var_pass2_y") : (dim == 0 ? "var_tails_x" : "var_tails_y"));
+}
+
+}  // namespace
+
+int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream) { return launch_pass<false>(a, dim, stream); }
+int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream) { return launch_pass<true>(a, dim, stream); }
+
+int launch_var_carry(const VarArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.lines + 255) / 256), (unsigned)a.n_planes), block(256);
+    switch (a.mode) {
+        case VAR_CAUSAL: hipLaunchKernelGGL((var_carry_kernel<VAR_CAUSAL>), grid, block, 0, stream, a); break;
+        case VAR_ANTICAUSAL: hipLaunchKernelGGL((var_carry_kernel<VAR_ANTICAUSAL>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((var_carry_kernel<VAR_PAIR>), grid, block, 0, stream, a); break;
+    }
+    return launched("var_carry");
+}
+
+}  // namespace rf

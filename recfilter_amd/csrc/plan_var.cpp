@@ -1,0 +1,200 @@
+// plan_var.cpp -- plan builder and driver of the spatially varying first-order scans (kernels_var.hip).
+//
+// No tables: the carry operators are data.  The builder validates the description, groups the scans into stages (a causal scan
+// directly followed by the anticausal scan of the same dimension and weight plane is one stage where the two are all the plan
+// runs along that dimension at that point), and allocates one workspace:
+// tails [tile][component][plane][line] and carries [tile][c, d][plane][line], sized for the dimension that needs more.  Every
+// stage is three launches: tails, carry, final pass.  The first stage reads the input planes, later stages filter the output
+// planes in place.
+#include "plan_var.h"
+
+#include <algorithm>
+#include <memory>
+
+rf_var_plan::~rf_var_plan() {
+    if (tails) (void)hipFree(tails);
+    if (carry) (void)hipFree(carry);
+}
+
+namespace rf {
+
+namespace {
+
+constexpr int64_t kVarMaxExtent = int64_t(1) << 21;      // 64 lines or samples per workgroup along grid.y (65535 workgroups)
+
+int validate(const rf_var_desc *d) {
+    if (d->abi != RF_ABI) {
+        set_error("rf_var_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->flags != 0) { set_error("rf_var_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
+    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
+    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
+    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
+    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
+    if (d->ndim != 2) { set_error("varying scans take 2-D images (ndim = %d)", d->ndim); return RF_ERR_UNSUPPORTED; }
+    if (d->dtype != RF_F32) { set_error("varying scans take f32 planes (dtype = %d)", d->dtype); return RF_ERR_UNSUPPORTED; }
+    for (int s = 0; s < d->n_scans; s++) {
+        const rf_var_scan_desc &sc = d->scans[s];
+        if (sc.dim < 0 || sc.dim > 1) { set_error("scan %d: dim must be 0 or 1 (got %d)", s, sc.dim); return RF_ERR_INVALID_ARG; }
+        if (sc.weights < 0 || sc.weights >= d->n_weights) {
+            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    for (int k = 0; k < 2; k++)
+        if (d->extent[k] < 1) { set_error("extent[%d] must be positive", k); return RF_ERR_INVALID_ARG; }
+    for (int k = 0; k < 2; k++)
+        if (d->extent[k] > kVarMaxExtent) { set_error("extent[%d] = %lld is above %lld", k, (long long)d->extent[k], (long long)kVarMaxExtent); return RF_ERR_UNSUPPORTED; }
+    if (d->extent[0] % 4 != 0) {
+        set_error("varying scans move 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)d->extent[0]);
+        return RF_ERR_UNSUPPORTED;
+    }
+    return RF_OK;
+}
+
+int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
+
+}  // namespace
+
+int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
+    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    *out = nullptr;
+    int rc = validate(desc);
+    if (rc != RF_OK) return rc;
+    const bool host_only = desc->device == RF_DEVICE_HOST_ONLY;
+    int device = desc->device;
+    if (!host_only) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("no HIP device available (this library has no CPU fallback)"); return RF_ERR_HIP; }
+        if (device < 0) RF_HIP_CHECK(hipGetDevice(&device));
+        if (device >= ndev) { set_error("device %d out of range (%d visible)", device, ndev); return RF_ERR_INVALID_ARG; }
+    }
+    std::unique_ptr<rf_var_plan> plan(new rf_var_plan);
+    plan->width = desc->extent[0];
+    plan->height = desc->extent[1];
+    plan->n_planes = desc->n_planes;
+    plan->n_weights = desc->n_weights;
+    plan->device = host_only ? 0 : device;
+    plan->host_only = host_only;
+    // Stages: the scans are taken in runs along one dimension.  A run that is exactly {+d, -d} on one weight plane is ONE fused
+    // stage; every other run -- a single scan, -d +d, a pair on two weight planes, three or more scans along the dimension --
+    // goes scan by scan (longer runs are not searched for pairs).
+    bool used[2] = {false, false};
+    auto add_stage = [&](int dim, int mode, int weights) {
+        rf_var_stage st;
+        st.dim = dim; st.mode = mode; st.weights = weights;
+        used[dim] = true;
+        const char *axis = dim == 0 ? "x" : "y";
+        plan->names.push_back(std::string("var_tails_") + axis);
+        plan->names.push_back("var_carry");
+        plan->names.push_back(std::string("var_pass2_") + axis);
+        plan->stages.push_back(st);
+    };
+    for (int s = 0; s < desc->n_scans;) {
+        int e = s + 1;
+        while (e < desc->n_scans && desc->scans[e].dim == desc->scans[s].dim) e++;
+        const rf_var_scan_desc *run = desc->scans + s;
+        if (e - s == 2 && run[0].causal != 0 && run[1].causal == 0 && run[0].weights == run[1].weights) {
+            add_stage(run[0].dim, VAR_PAIR, run[0].weights);
+        } else {
+            for (int q = s; q < e; q++) add_stage(desc->scans[q].dim, desc->scans[q].causal != 0 ? VAR_CAUSAL : VAR_ANTICAUSAL, desc->scans[q].weights);
+        }
+        s = e;
+    }
+    // tiles x lines of the dimension that needs more: x scans have `height` lines, y scans `width`
+    int64_t slots = 0;
+    if (used[0]) slots = std::max(slots, tiles_of(plan->width) * plan->height);
+    if (used[1]) slots = std::max(slots, tiles_of(plan->height) * plan->width);
+    plan->tails_bytes = (size_t)(slots * kVarComponents * plan->n_planes) * sizeof(float);
+    plan->carry_bytes = (size_t)(slots * 2 * plan->n_planes) * sizeof(float);
+    if (!host_only) {
+        RF_HIP_CHECK(hipSetDevice(device));
+        if (hipMalloc((void **)&plan->tails, plan->tails_bytes) != hipSuccess || hipMalloc((void **)&plan->carry, plan->carry_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of %zu bytes of workspace failed", plan->workspace_bytes());
+            return RF_ERR_NOMEM;
+        }
+    }
+    *out = plan.release();
+    return RF_OK;
+}
+
+int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, void *const *out_planes,
+                 hipStream_t stream, float *ms_out) {
+    if (!plan || !in_planes || !weight_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
+    const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
+    for (int pl = 0; pl < plan->n_planes; pl++) {
+        if (!in_planes[pl] || !out_planes[pl]) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
+        if ((((uintptr_t)in_planes[pl] | (uintptr_t)out_planes[pl]) & 15u) != 0) {
+            set_error("plane %d: the varying scans need 16-byte aligned image pointers", pl);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    for (int k = 0; k < plan->n_weights; k++) {
+        if (!weight_planes[k]) { set_error("weight plane %d: null pointer", k); return RF_ERR_INVALID_ARG; }
+        if (((uintptr_t)weight_planes[k] & 15u) != 0) { set_error("weight plane %d: the varying scans need 16-byte aligned pointers", k); return RF_ERR_INVALID_ARG; }
+        const uintptr_t w0 = (uintptr_t)weight_planes[k];
+        for (int pl = 0; pl < plan->n_planes; pl++) {
+            const uintptr_t o0 = (uintptr_t)out_planes[pl];
+            if (w0 < o0 + plane_bytes && o0 < w0 + plane_bytes) {
+                set_error("weight plane %d overlaps output plane %d: every stage reads the weights after it has begun to store", k, pl);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    }
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    // events are destroyed on every return path
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } events;
+    const size_t n_kernels = plan->stages.size() * 3;
+    if (ms_out) {
+        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
+        for (size_t i = 0; i < n_kernels + 1; i++) {
+            hipEvent_t e;
+            RF_HIP_CHECK(hipEventCreate(&e));
+            events.ev.push_back(e);
+        }
+        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
+    }
+    size_t launch = 0;
+    auto mark = [&]() -> int {
+        launch++;
+        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
+        return RF_OK;
+    };
+    for (size_t s = 0; s < plan->stages.size(); s++) {
+        const rf_var_stage &st = plan->stages[s];
+        VarArgs a{};
+        for (int pl = 0; pl < plan->n_planes; pl++) {
+            a.src[pl] = (const float *)(s == 0 ? in_planes[pl] : out_planes[pl]);
+            a.dst[pl] = (float *)out_planes[pl];
+        }
+        a.weights = (const float *)weight_planes[st.weights];
+        a.tails = plan->tails;
+        a.carry = plan->carry;
+        a.width = (int32_t)plan->width;
+        a.height = (int32_t)plan->height;
+        a.n_planes = plan->n_planes;
+        a.tiles = (int32_t)tiles_of(st.dim == 0 ? plan->width : plan->height);
+        a.lines = (int32_t)(st.dim == 0 ? plan->height : plan->width);
+        a.mode = st.mode;
+        int rc = launch_var_tails(a, st.dim, stream);
+        if (rc == RF_OK) rc = mark();
+        if (rc == RF_OK) rc = launch_var_carry(a, stream);
+        if (rc == RF_OK) rc = mark();
+        if (rc == RF_OK) rc = launch_var_pass2(a, st.dim, stream);
+        if (rc == RF_OK) rc = mark();
+        if (rc != RF_OK) return rc;
+    }
+    if (ms_out) {
+        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
+        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
+    }
+    return RF_OK;
+}
+
+}  // namespace rf

@@ -1,0 +1,37 @@
+// plan_var.h -- the plan behind the rf_var_plan_* entry points: spatially varying first-order scans (plan_var.cpp).
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "kernels_var.h"
+#include "rf_internal.h"
+
+// One stage = one scan, or a causal scan directly followed by the anticausal scan of the same dimension and weight plane
+// (where the two are all of a run along that dimension: plan_var.cpp).
+struct rf_var_stage {
+    int dim = 0;
+    int mode = rf::VAR_CAUSAL;      // rf::VarMode
+    int weights = 0;
+};
+
+struct rf_var_plan {
+    int64_t width = 0, height = 0;
+    int n_planes = 1, n_weights = 1;
+    int device = 0;
+    bool host_only = false;
+    std::vector<rf_var_stage> stages;
+    std::vector<std::string> names;          // three per stage: what rf_var_plan_execute_timed reports
+    // the one workspace: every stage's tails and carries (sized for the larger dimension); written before it is read
+    float *tails = nullptr, *carry = nullptr;
+    size_t tails_bytes = 0, carry_bytes = 0;
+    size_t workspace_bytes() const { return tails_bytes + carry_bytes; }
+    ~rf_var_plan();
+};
+
+namespace rf {
+int build_var_plan(const rf_var_desc *desc, rf_var_plan **out);
+// ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
+int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, void *const *out_planes,
+                 hipStream_t stream, float *ms_out);
+}  // namespace rf

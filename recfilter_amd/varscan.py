@@ -1,0 +1,181 @@
+"""Spatially varying first-order scans: thin Python handle over rf_var_plan_* (include/recfilter_amd.h), and the
+edge-aware smoothing built on them (the domain-transform recursive filter of Gastal & Oliveira 2011).
+
+The scans run in the HIP kernels of kernels_var.hip; torch tensors are device memory.  Only the weight planes of
+`domain_transform_weights` are computed with torch (a pointwise expression of the guide image, on the guide's device).
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+from . import capi
+
+VarScan = Tuple[int, bool, int]      # (dim, causal, index of the weight plane); dim 0 = x
+
+
+class VarPlan:
+    """A list of at most capi.RF_VAR_MAX_SCANS scans  y[i] = (1 - w[i]) x[i] + w[i] y[i-1]  (causal; the anticausal one couples
+    sample i to i+1 through w[i+1]) over `planes` f32 planes of `shape` = (height, width) that share `n_weights` weight planes.
+    Element 0 of a weight plane along the scanned dimension is never used.  One plan owns one workspace: order its executes."""
+
+    def __init__(self, shape: Sequence[int], scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1):
+        L = capi.lib()
+        shape = tuple(int(s) for s in shape)
+        if not 1 <= len(shape) <= capi.RF_MAX_DIMS:
+            raise ValueError(f"1..{capi.RF_MAX_DIMS} dimensions, got shape {shape}")
+        scans = list(scans)
+        self._scan_arr = (capi.VarScanDesc * max(len(scans), 1))()
+        for i, (dim, causal, weights) in enumerate(scans):
+            s = self._scan_arr[i]
+            s.dim, s.causal, s.weights = int(dim), int(bool(causal)), int(weights)
+        d = capi.VarDesc()
+        d.abi = capi.RF_ABI
+        d.ndim = len(shape)
+        for i, e in enumerate(reversed(shape)):      # (y, x) -> extent[0] = x
+            d.extent[i] = e
+        d.dtype = capi.RF_F32
+        d.n_planes, d.n_weights = int(planes), int(n_weights)
+        d.n_scans = len(scans)
+        d.scans = ctypes.cast(self._scan_arr, ctypes.POINTER(capi.VarScanDesc))
+        d.device = int(device)
+        d.flags = 0
+        self._desc = d
+        self.shape, self.planes, self.n_weights = shape, int(planes), int(n_weights)
+        self._h = ctypes.c_void_p()
+        capi.check(L.rf_var_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
+
+    # -- lifetime ---------------------------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            capi.lib().rf_var_plan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- queries ----------------------------------------------------------------------------
+    @property
+    def workspace_bytes(self) -> int:
+        return int(capi.lib().rf_var_plan_workspace_bytes(self._h))
+
+    @property
+    def num_kernels(self) -> int:
+        return int(capi.lib().rf_var_plan_num_kernels(self._h))
+
+    # -- execution --------------------------------------------------------------------------
+    def _pointers(self, tensors, count: int, what: str) -> ctypes.Array:
+        import torch
+        if len(tensors) != count:
+            raise ValueError(f"expected {count} {what} planes, got {len(tensors)}")
+        arr = (ctypes.c_void_p * count)()
+        for i, t in enumerate(tensors):
+            if tuple(t.shape) != self.shape:
+                raise ValueError(f"{what} plane {i}: shape {tuple(t.shape)} != plan shape {self.shape}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{what} plane {i}: float32 planes only, got {t.dtype}")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("planes must be contiguous device tensors")
+            arr[i] = t.data_ptr()
+        return arr
+
+    @staticmethod
+    def _stream(stream) -> ctypes.c_void_p:
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return ctypes.c_void_p(s.cuda_stream)
+
+    def _arguments(self, ins, weights, outs):
+        import torch
+        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
+            # (the library refuses; there are no device tensors to take pointers from)
+            nulls = lambda n: (ctypes.c_void_p * n)()      # noqa: E731
+            return nulls(self.planes), nulls(self.n_weights), nulls(self.planes), None, ctypes.c_void_p()
+        if outs is None:
+            outs = [torch.empty_like(t) for t in ins]
+        return (self._pointers(ins, self.planes, "input"), self._pointers(weights, self.n_weights, "weight"),
+                self._pointers(outs, self.planes, "output"), outs, None)
+
+    def execute(self, ins, weights, outs=None, stream=None):
+        """rf_var_plan_execute: asynchronous on `stream` (default: torch's current stream).  outs=None allocates the outputs;
+        outs may be the inputs themselves (in place)."""
+        pin, pw, pout, outs, host_stream = self._arguments(ins, weights, outs)
+        capi.check(capi.lib().rf_var_plan_execute(self._h, pin, pw, pout, host_stream if host_stream is not None else self._stream(stream)))
+        return outs
+
+    def execute_timed(self, ins, weights, outs=None, stream=None):
+        """rf_var_plan_execute_timed: (outputs, [(kernel name, ms), ...]) measured with HIP events; synchronises the stream."""
+        pin, pw, pout, outs, host_stream = self._arguments(ins, weights, outs)
+        n = self.num_kernels
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_var_plan_execute_timed(self._h, pin, pw, pout,
+                                                        host_stream if host_stream is not None else self._stream(stream), ms, names, n))
+        return outs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+# ---- the domain-transform recursive filter ----------------------------------------------------------------------------------
+def domain_transform_weights(guide, sigma_s: float, sigma_r: float, iterations: int = 3):
+    """The feedback planes of the domain-transform recursive filter for a guide image (C, H, W) or (H, W), computed with torch on
+    the guide's device:  [(w_x, w_y) for iteration k = 0 .. iterations-1],  f32 planes of (H, W) with
+        d_x[i] = 1 + (sigma_s / sigma_r) * sum_c |g_c[i] - g_c[i-1]|     (the same along y; element 0, never used, holds a^1)
+        sigma_k = sigma_s * sqrt(3) * 2^(K-1-k) / sqrt(4^K - 1),   a_k = exp(-sqrt(2) / sigma_k),   w = a_k ** d."""
+    import torch
+    if iterations < 1:
+        raise ValueError("iterations must be >= 1")
+    g = guide if guide.dim() == 3 else guide.unsqueeze(0)
+    if g.dim() != 3:
+        raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
+    g = g.to(torch.float32)
+    ratio = float(sigma_s) / float(sigma_r)
+    dx = torch.ones(g.shape[1:], dtype=torch.float32, device=g.device)
+    dy = torch.ones(g.shape[1:], dtype=torch.float32, device=g.device)
+    dx[:, 1:] += ratio * (g[:, :, 1:] - g[:, :, :-1]).abs().sum(0)
+    dy[1:, :] += ratio * (g[:, 1:, :] - g[:, :-1, :]).abs().sum(0)
+    K = int(iterations)
+    out = []
+    for k in range(K):
+        sigma_k = float(sigma_s) * math.sqrt(3.0) * 2.0 ** (K - 1 - k) / math.sqrt(4.0 ** K - 1.0)
+        a_k = math.exp(-math.sqrt(2.0) / sigma_k)
+        out.append((torch.pow(a_k, dx).contiguous(), torch.pow(a_k, dy).contiguous()))
+    return out
+
+
+_SMOOTH_SCANS = [(0, True, 0), (0, False, 0), (1, True, 1), (1, False, 1)]      # +x -x on weights 0, +y -y on weights 1
+_smooth_plans: Dict[Tuple[int, int, int, int], VarPlan] = {}
+
+
+def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3):
+    """Edge-aware smoothing of a device image (C, H, W) or (H, W), f32, by the domain-transform recursive filter: per iteration
+    +x, -x on that iteration's x weights, then +y, -y on its y weights (two fused stages, six launches).  guide=None: the image
+    guides itself.  One plan per (shape, device), cached; calls on one shape are ordered by the caller (one stream)."""
+    import torch
+    img = image if image.dim() == 3 else image.unsqueeze(0)
+    if img.dim() != 3:
+        raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
+    img = img.to(torch.float32).contiguous()
+    weights = domain_transform_weights(image if guide is None else guide, sigma_s, sigma_r, iterations)
+    C, H, W = (int(s) for s in img.shape)
+    if tuple(weights[0][0].shape) != (H, W):
+        raise ValueError("guide and image must have the same height and width")
+    key = (C, H, W, img.device.index if img.device.index is not None else torch.cuda.current_device())
+    plan = _smooth_plans.get(key)
+    if plan is None:
+        plan = _smooth_plans[key] = VarPlan((H, W), _SMOOTH_SCANS, planes=C, n_weights=2, device=key[3])
+    out = torch.empty_like(img)
+    outs = [out[c] for c in range(C)]
+    src = [img[c] for c in range(C)]
+    for wx, wy in weights:
+        plan.execute(src, [wx.to(img.device), wy.to(img.device)], outs)
+        src = outs
+    return out if image.dim() == 3 else out[0]
