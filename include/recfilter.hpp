@@ -772,8 +772,22 @@ public:
     /** in / out: one device plane per channel; weights: the planes add_scan indexed.  Asynchronous on `stream`. */
     void realize(const std::vector<const void *> &in, const std::vector<const void *> &weights, const std::vector<void *> &out,
                  void *stream = nullptr) {
+        prepare(in, weights.size(), out);
+        if (rf_var_plan_execute(plan, in.data(), weights.data(), out.data(), stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+    /** The power form (rf_var_plan_execute_power): plane k of `exponents` holds d >= 0 and the scans that index it use
+     *  w = bases[k] ^ d, formed in the kernels; 0 < bases[k] < 1, one base per exponent plane.  The same plan as realize(). */
+    void realize_power(const std::vector<const void *> &in, const std::vector<const void *> &exponents, const std::vector<float> &bases,
+                       const std::vector<void *> &out, void *stream = nullptr) {
+        prepare(in, exponents.size(), out);
+        if ((int)bases.size() < n_weights) throw RecFilterError("realize_power: one base per exponent plane");
+        if (rf_var_plan_execute_power(plan, in.data(), exponents.data(), bases.data(), out.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+private:
+    void prepare(const std::vector<const void *> &in, size_t weight_planes, const std::vector<void *> &out) {
         if (in.empty() || in.size() != out.size()) throw RecFilterError("realize: as many output planes as input planes, at least one");
-        if ((int)weights.size() < n_weights) throw RecFilterError("realize: a scan indexes a weight plane that was not passed");
+        if ((int)weight_planes < n_weights) throw RecFilterError("realize: a scan indexes a weight plane that was not passed");
         if (!plan || plan_planes != (int)in.size()) {
             drop();
             rf_var_desc d{};
@@ -790,6 +804,15 @@ public:
             if (rf_var_plan_create(&d, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
             plan_planes = (int)in.size();
         }
-        if (rf_var_plan_execute(plan, in.data(), weights.data(), out.data(), stream) != RF_OK) throw RecFilterError(rf_last_error_string());
     }
 };
+
+/** The exponent planes of the domain-transform filter from a guide image (rf_var_distances): d_x = 1 + scale * sum over the
+ *  guide planes of |g - g one column to the left|, d_y the same with the row above; scale = sigma_s / sigma_r (over 255 for a
+ *  uint8 guide that stands for guide / 255).  One launch on `stream`, on the current device.  With
+ *  RecFilterVarying::realize_power and bases {a_k, a_k} per iteration this is the whole filter. */
+inline void domain_transform_distances(const std::vector<const void *> &guide_planes, bool guide_u8, int64_t width, int64_t height,
+                                       float scale, void *dx, void *dy, void *stream = nullptr) {
+    if (rf_var_distances(guide_planes.data(), (int32_t)guide_planes.size(), guide_u8 ? 1 : 0, width, height, scale, dx, dy, -1,
+                         stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+}

@@ -470,6 +470,32 @@ int    rf_var_plan_execute(rf_var_plan *plan, const void *const *in_planes, cons
 /* as rf_plan_execute_timed: per-kernel milliseconds and names (valid for the life of the plan); synchronises the stream */
 int    rf_var_plan_execute_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
                                  void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity);
+/* The power form.  As rf_var_plan_execute, but plane k of `exponent_planes` holds exponents d >= 0 (+inf allowed) and the weight
+ * a scan uses is
+ *     w[i] = exp2f(d[i] * l_k),   l_k = (float)log2((double)bases[k]),   0 < bases[k] < 1,
+ * formed in f32 as the kernels load the plane (one multiply, one hardware exp2 of 1 ulp whose denormal results flush to 0); no
+ * weight plane is ever stored.  d = 0 gives w = 1 exactly, d = +inf gives w = 0 exactly.  Element 0 along the scanned dimension
+ * is still never used (a select: NaN there reaches nothing).  Same plan object, workspace, stages, launch names and
+ * rf_var_plan_num_kernels as rf_var_plan_execute: a plan may be run either way, call by call.  What the domain-transform filter
+ * needs per iteration k is then two exponent planes (rf_var_distances) shared by all iterations and bases = {a_k, a_k}.
+ * Checked in this order: null arrays; a base that is not finite or not inside (0, 1) (RF_ERR_INVALID_ARG, the message names the
+ * plane); a host-only plan (RF_ERR_HIP); then the per-plane checks of rf_var_plan_execute. */
+int    rf_var_plan_execute_power(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                 const float *bases /* n_weights */, void *const *out_planes, void *stream);
+int    rf_var_plan_execute_power_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                       const float *bases, void *const *out_planes, void *stream, float *ms_out,
+                                       const char **names_out, int capacity);
+/* The distance planes of the domain-transform filter from a guide image of n_guide dense planes of width x height:
+ *     d_x[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r][c-1]|   (c >= 1;  d_x[r][0] = 1)
+ *     d_y[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r-1][c]|   (r >= 1;  d_y[0][c] = 1)
+ * channels summed in order in f32; guide planes f32 (guide_u8 = 0) or uint8 (guide_u8 = 1: the differences are exact).  One
+ * launch ("var_distances"), one read of the guide; asynchronous on `stream`; device -1 = the current one.  Decided before any
+ * HIP call: n_guide outside 1..RF_MAX_PLANES, extents below 1, null pointers, a scale that is negative or not finite
+ * (RF_ERR_INVALID_ARG); a width that is not a multiple of 4, extents above the varying plans' limit of 2^21 (RF_ERR_UNSUPPORTED);
+ * dx / dy / f32 guide planes not 16-byte aligned, uint8 guide planes not 4-byte aligned, dx or dy overlapping each other or a
+ * guide plane (RF_ERR_INVALID_ARG). */
+int    rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height,
+                        float scale, void *dx, void *dy, int32_t device, void *stream);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

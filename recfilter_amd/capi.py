@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
     "rf_plan_table", "rf_plan_debug_buffer", "rf_plan_debug_buffer_kind", "rf_plan_debug_fill", "rf_gaussian_weights", "rf_integral_image_coeff", "rf_overlap_feedback_coeff",
     "rf_gaussian_box_filter", "rf_box_difference", "rf_tap_filter", "rf_stream_copy", "rf_last_error_string", "rf_version", "rf_device_count",
     "rf_var_plan_create", "rf_var_plan_destroy", "rf_var_plan_workspace_bytes", "rf_var_plan_num_kernels", "rf_var_plan_execute",
-    "rf_var_plan_execute_timed",
+    "rf_var_plan_execute_timed", "rf_var_plan_execute_power", "rf_var_plan_execute_power_timed", "rf_var_distances",
 ]
 
 
@@ -181,6 +181,10 @@ def lib() -> ctypes.CDLL:
     L.rf_var_plan_num_kernels.argtypes = [vp]
     L.rf_var_plan_execute.argtypes = [vp, vpp, vpp, vpp, vp]
     L.rf_var_plan_execute_timed.argtypes = [vp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_plan_execute_power.argtypes = [vp, vpp, vpp, fp, vpp, vp]
+    L.rf_var_plan_execute_power_timed.argtypes = [vp, vpp, vpp, fp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_distances.argtypes = [vpp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, vp, vp,
+                                   ctypes.c_int32, vp]
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

@@ -568,7 +568,7 @@ int rf_var_plan_num_kernels(const rf_var_plan *plan) { return plan ? (int)plan->
 
 int rf_var_plan_execute(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, void *const *out_planes,
                         void *stream) {
-    return fenced("rf_var_plan_execute", [&] { return run_var_plan(plan, in_planes, weight_planes, out_planes, (hipStream_t)stream, nullptr); });
+    return fenced("rf_var_plan_execute", [&] { return run_var_plan(plan, in_planes, weight_planes, nullptr, out_planes, (hipStream_t)stream, nullptr); });
 }
 
 int rf_var_plan_execute_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
@@ -578,7 +578,34 @@ int rf_var_plan_execute_timed(rf_var_plan *plan, const void *const *in_planes, c
         if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
         if (names_out)
             for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
-        return run_var_plan(plan, in_planes, weight_planes, out_planes, (hipStream_t)stream, ms_out);
+        return run_var_plan(plan, in_planes, weight_planes, nullptr, out_planes, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var_plan_execute_power(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes, const float *bases,
+                              void *const *out_planes, void *stream) {
+    return fenced("rf_var_plan_execute_power", [&] {
+        if (!bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        return run_var_plan(plan, in_planes, exponent_planes, bases, out_planes, (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var_plan_execute_power_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                    const float *bases, void *const *out_planes, void *stream, float *ms_out, const char **names_out,
+                                    int capacity) {
+    return fenced("rf_var_plan_execute_power_timed", [&] {
+        if (!plan || !bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
+        if (names_out)
+            for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
+        return run_var_plan(plan, in_planes, exponent_planes, bases, out_planes, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
+                     void *dx, void *dy, int32_t device, void *stream) {
+    return fenced("rf_var_distances", [&] {
+        return run_var_distances(guide_planes, n_guide, guide_u8, width, height, scale, dx, dy, device, (hipStream_t)stream);
     });
 }
 

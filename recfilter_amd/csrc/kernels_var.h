@@ -29,10 +29,23 @@ struct VarArgs {
     int32_t tiles;
     int32_t lines;
     int32_t mode;                   // VarMode
+    // power form (rf_var_plan_execute_power): `weights` holds exponents d, the kernels form w = exp2(d * log2_base) as they load
+    int32_t power;
+    float log2_base;
+};
+
+// d_x = 1 + scale * sum_ch |g - g one column to the left|, d_y the same with the row above (kernels_var.hip, var_distances)
+struct VarDistArgs {
+    const void *guide[RF_MAX_PLANES];
+    float *dx, *dy;
+    int32_t width, height;          // x fastest; the width is a multiple of 4
+    int32_t n_guide;
+    float scale;
 };
 
 int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_carry(const VarArgs &a, hipStream_t stream);
 int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream);
+int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream);
 
 }  // namespace rf

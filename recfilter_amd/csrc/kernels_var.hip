@@ -19,7 +19,16 @@
 // padded to 68 dwords (ds_write_b128 and ds_read_b128 both conflict-free), the scan, the way back, 16-byte stores.
 // Samples a partial tile misses are loaded from a safe address inside the plane and selected away where they are consumed
 // (image 0, weight 0); they are never stored.  A workgroup has loaded its whole tile before it stores: in == out is legal.
+//
+// Power form (POWER, rf_var_plan_execute_power): the weight plane holds exponents d >= 0 and a stage carries l = log2(base);
+// the lane's 65 registers become w = exp2(d * l) in place, one multiply and one v_exp_f32 each, before mask_tile -- the scans
+// and var_carry see weights as before.  d = 0 gives 1 and d = +inf gives 0, exactly.  A separate instantiation: the plane-form
+// kernels hold no trace of it.
+//
+// var_distances: the two exponent planes of the domain-transform filter from a guide image, one streaming launch.
 #include "kernels_var.h"
+
+#include <algorithm>
 
 namespace rf {
 
@@ -95,6 +104,10 @@ __device__ __forceinline__ void mask_tile(float (&x)[T], float (&w)[T + 1], int 
     for (int i = 0; i <= T; i++) w[i] = (t0 + i == 0 || t0 + i >= n) ? 0.0f : w[i];
 }
 
+// exponents -> weights in place.  v_exp_f32: 1 ulp, exp2(-0) = 1, exp2(-inf) = 0; results below 2^-126 flush to 0 (such a
+// weight couples nothing at f32 precision).  The product is a plain f32 multiply: what the tests' numpy yardstick forms.
+__device__ __forceinline__ float power_weight(float d, float l) { return __builtin_amdgcn_exp2f(d * l); }
+
 __device__ __forceinline__ int64_t tail_index(const VarArgs &a, int t, int comp, int pl, int line) {
     return (((int64_t)t * kVarComponents + comp) * a.n_planes + pl) * a.lines + line;
 }
@@ -113,7 +126,7 @@ __device__ __forceinline__ void store_tails(const VarArgs &a, int t, int pl, int
 }
 
 // ---- along y: lane = column -------------------------------------------------------------------------------------------
-template <int MODE, bool FINAL>
+template <int MODE, bool FINAL, bool POWER>
 __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
     const int col = blockIdx.x * 64 + threadIdx.x;
     if (col >= a.width) return;                       // (no barrier below: lanes are independent)
@@ -129,6 +142,11 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
     }
     w[T] = 0.0f;
     if constexpr (MODE != VAR_CAUSAL) w[T] = (a.weights + min(t0 + T, a.height - 1) * pitch)[col];
+    if constexpr (POWER) {
+#pragma unroll
+        for (int i = 0; i < T; i++) w[i] = power_weight(w[i], a.log2_base);
+        if constexpr (MODE != VAR_CAUSAL) w[T] = power_weight(w[T], a.log2_base);
+    }
     float c = 0.0f, d = 0.0f;
     if constexpr (FINAL) {
         if constexpr (MODE != VAR_ANTICAUSAL) c = a.carry[carry_index(a, t, 0, pl, col)];
@@ -180,7 +198,7 @@ __device__ __forceinline__ void transpose_in(const float (&v)[T], float *lds, fl
     __syncthreads();
 }
 
-template <int MODE, bool FINAL>
+template <int MODE, bool FINAL, bool POWER>
 __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
@@ -204,6 +222,11 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
 #pragma unroll
     for (int i = 0; i < T; i++) w[i] = wt[i];
     w[T] = w_next;
+    if constexpr (POWER) {
+#pragma unroll
+        for (int i = 0; i < T; i++) w[i] = power_weight(w[i], a.log2_base);
+        if constexpr (MODE != VAR_CAUSAL) w[T] = power_weight(w[T], a.log2_base);
+    }
     mask_tile(x, w, t0, a.width);
     __builtin_amdgcn_sched_barrier(0);      // (the scans stay behind the transposition: they would hold its registers)
     if constexpr (FINAL) {
@@ -282,6 +305,50 @@ __global__ void __launch_bounds__(256) var_carry_kernel(VarArgs a) {
     }
 }
 
+// ---- var_distances: lane = 4 adjacent columns of one row -------------------------------------------------------------------
+// a lane's chunk of one guide channel as four floats; bytes convert exactly
+__device__ __forceinline__ void load_chunk(const float *g, int64_t at, float (&v)[4]) {
+    const float4 q = *reinterpret_cast<const float4 *>(g + at);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+__device__ __forceinline__ void load_chunk(const uint8_t *g, int64_t at, float (&v)[4]) {
+    const uint32_t q = *reinterpret_cast<const uint32_t *>(g + at);
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = (float)((q >> (8 * j)) & 255u);
+}
+
+// The element to the left of the chunk and the chunk of the row above come from clamped addresses (column 0: the chunk's own
+// first element; row 0: the row itself) and are selected away there.  Rows beyond gridDim.y are taken in a stride loop.
+template <typename G>
+__global__ void __launch_bounds__(256) var_distances_kernel(VarDistArgs a) {
+    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (c >= a.width) return;
+    for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
+        const int64_t own_at = (int64_t)r * a.width + c, up_at = (int64_t)max(r - 1, 0) * a.width + c;
+        float sx[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sy[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int ch = 0; ch < a.n_guide; ch++) {
+            const G *g = static_cast<const G *>(a.guide[ch]);
+            float own[4], up[4];
+            load_chunk(g, own_at, own);
+            load_chunk(g, up_at, up);
+            const float left = (float)g[own_at - (c > 0 ? 1 : 0)];
+            sx[0] += fabsf(own[0] - left);
+#pragma unroll
+            for (int j = 1; j < 4; j++) sx[j] += fabsf(own[j] - own[j - 1]);
+#pragma unroll
+            for (int j = 0; j < 4; j++) sy[j] += fabsf(own[j] - up[j]);
+        }
+        float dx[4], dy[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            dx[j] = (c + j == 0) ? 1.0f : 1.0f + a.scale * sx[j];
+            dy[j] = (r == 0) ? 1.0f : 1.0f + a.scale * sy[j];
+        }
+        *reinterpret_cast<float4 *>(a.dx + own_at) = make_float4(dx[0], dx[1], dx[2], dx[3]);
+        *reinterpret_cast<float4 *>(a.dy + own_at) = make_float4(dy[0], dy[1], dy[2], dy[3]);
+    }
+}
+
 int launched(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
@@ -294,15 +361,18 @@ int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
     const dim3 block(64);
     const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)a.n_planes)
                                : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)a.n_planes);
-#define RF_VAR_LAUNCH(MODE)                                                                        \
-    if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL>), grid, block, 0, stream, a);      \
-    else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL>), grid, block, 0, stream, a)
+#define RF_VAR_LAUNCH_FORM(MODE, POWER)                                                                   \
+    if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL, POWER>), grid, block, 0, stream, a);      \
+    else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL, POWER>), grid, block, 0, stream, a)
+#define RF_VAR_LAUNCH(MODE)                                                                               \
+    if (a.power) { RF_VAR_LAUNCH_FORM(MODE, true); } else { RF_VAR_LAUNCH_FORM(MODE, false); }
     switch (a.mode) {
         case VAR_CAUSAL: RF_VAR_LAUNCH(VAR_CAUSAL); break;
         case VAR_ANTICAUSAL: RF_VAR_LAUNCH(VAR_ANTICAUSAL); break;
         default: RF_VAR_LAUNCH(VAR_PAIR); break;
     }
 #undef RF_VAR_LAUNCH
+#undef RF_VAR_LAUNCH_FORM
     return launched(FINAL ? (dim == 0 ? "var_pass2_x" : "var_pass2_y") : (dim == 0 ? "var_tails_x" : "var_tails_y"));
 }
 
@@ -319,6 +389,13 @@ int launch_var_carry(const VarArgs &a, hipStream_t stream) {
         default: hipLaunchKernelGGL((var_carry_kernel<VAR_PAIR>), grid, block, 0, stream, a); break;
     }
     return launched("var_carry");
+}
+
+int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
+    if (guide_u8) hipLaunchKernelGGL((var_distances_kernel<uint8_t>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var_distances_kernel<float>), grid, block, 0, stream, a);
+    return launched("var_distances");
 }
 
 }  // namespace rf

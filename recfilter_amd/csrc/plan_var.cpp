@@ -5,10 +5,12 @@
 // runs along that dimension at that point), and allocates one workspace:
 // tails [tile][component][plane][line] and carries [tile][c, d][plane][line], sized for the dimension that needs more.  Every
 // stage is three launches: tails, carry, final pass.  The first stage reads the input planes, later stages filter the output
-// planes in place.
+// planes in place.  The power form (rf_var_plan_execute_power) runs the same stages on exponent planes: a stage carries
+// log2 of its plane's base and launches the kernels' POWER instances.
 #include "plan_var.h"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 
 rf_var_plan::~rf_var_plan() {
@@ -120,9 +122,19 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
     return RF_OK;
 }
 
-int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, void *const *out_planes,
-                 hipStream_t stream, float *ms_out) {
+int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
+                 void *const *out_planes, hipStream_t stream, float *ms_out) {
     if (!plan || !in_planes || !weight_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    float log2_base[RF_VAR_MAX_SCANS] = {};
+    if (bases) {
+        for (int k = 0; k < plan->n_weights; k++) {
+            if (!std::isfinite(bases[k]) || !(bases[k] > 0.0f && bases[k] < 1.0f)) {
+                set_error("exponent plane %d: the base must be inside (0, 1) (got %g)", k, (double)bases[k]);
+                return RF_ERR_INVALID_ARG;
+            }
+            log2_base[k] = (float)std::log2((double)bases[k]);
+        }
+    }
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
     const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
     for (int pl = 0; pl < plan->n_planes; pl++) {
@@ -182,6 +194,8 @@ int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *co
         a.tiles = (int32_t)tiles_of(st.dim == 0 ? plan->width : plan->height);
         a.lines = (int32_t)(st.dim == 0 ? plan->height : plan->width);
         a.mode = st.mode;
+        a.power = bases ? 1 : 0;
+        a.log2_base = log2_base[st.weights];
         int rc = launch_var_tails(a, st.dim, stream);
         if (rc == RF_OK) rc = mark();
         if (rc == RF_OK) rc = launch_var_carry(a, stream);
@@ -195,6 +209,50 @@ int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *co
         for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
     }
     return RF_OK;
+}
+
+int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
+                      void *dx, void *dy, int32_t device, hipStream_t stream) {
+    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
+    if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
+    if (!guide_planes || !dx || !dy) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (!guide_planes[ch]) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
+    if (!std::isfinite(scale) || scale < 0.0f) { set_error("scale must be finite and not negative (got %g)", (double)scale); return RF_ERR_INVALID_ARG; }
+    if (width % 4 != 0) {
+        set_error("var_distances moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)width);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (width > kVarMaxExtent || height > kVarMaxExtent) {
+        set_error("extents %lld x %lld are above %lld", (long long)width, (long long)height, (long long)kVarMaxExtent);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if ((((uintptr_t)dx | (uintptr_t)dy) & 15u) != 0) { set_error("dx and dy must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
+    const uintptr_t guide_align = guide_u8 ? 3u : 15u;
+    for (int ch = 0; ch < n_guide; ch++)
+        if (((uintptr_t)guide_planes[ch] & guide_align) != 0) {
+            set_error("guide plane %d: %s guide planes must be %u-byte aligned", ch, guide_u8 ? "uint8" : "f32", (unsigned)guide_align + 1);
+            return RF_ERR_INVALID_ARG;
+        }
+    const size_t samples = (size_t)(width * height), out_bytes = samples * sizeof(float), guide_bytes = samples * (guide_u8 ? 1 : sizeof(float));
+    auto overlap = [](uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; };
+    if (overlap((uintptr_t)dx, out_bytes, (uintptr_t)dy, out_bytes)) { set_error("dx overlaps dy"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (overlap((uintptr_t)dx, out_bytes, (uintptr_t)guide_planes[ch], guide_bytes) ||
+            overlap((uintptr_t)dy, out_bytes, (uintptr_t)guide_planes[ch], guide_bytes)) {
+            set_error("guide plane %d overlaps dx or dy: a lane reads its neighbours' samples", ch);
+            return RF_ERR_INVALID_ARG;
+        }
+    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
+    VarDistArgs a{};
+    for (int ch = 0; ch < n_guide; ch++) a.guide[ch] = guide_planes[ch];
+    a.dx = (float *)dx;
+    a.dy = (float *)dy;
+    a.width = (int32_t)width;
+    a.height = (int32_t)height;
+    a.n_guide = n_guide;
+    a.scale = scale;
+    return launch_var_distances(a, guide_u8 != 0, stream);
 }
 
 }  // namespace rf

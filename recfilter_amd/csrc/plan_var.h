@@ -32,6 +32,9 @@ struct rf_var_plan {
 namespace rf {
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out);
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
-int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, void *const *out_planes,
-                 hipStream_t stream, float *ms_out);
+// bases == nullptr: `weight_planes` hold weights; else they hold exponents and bases[k] is the base of plane k (the power form)
+int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
+                 void *const *out_planes, hipStream_t stream, float *ms_out);
+int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
+                      void *dx, void *dy, int32_t device, hipStream_t stream);
 }  // namespace rf

@@ -1,8 +1,11 @@
 """Spatially varying first-order scans: thin Python handle over rf_var_plan_* (include/recfilter_amd.h), and the
 edge-aware smoothing built on them (the domain-transform recursive filter of Gastal & Oliveira 2011).
 
-The scans run in the HIP kernels of kernels_var.hip; torch tensors are device memory.  Only the weight planes of
-`domain_transform_weights` are computed with torch (a pointwise expression of the guide image, on the guide's device).
+The scans run in the HIP kernels of kernels_var.hip; torch tensors are device memory.  Two forms of the filter:
+  planes   `domain_transform_weights` computes a pair of weight planes per iteration with torch (a pointwise expression of the
+           guide image, on the guide's device); `VarPlan.execute` reads them.
+  power    `domain_transform_distances` (rf_var_distances, one HIP launch) gives the two exponent planes all iterations share;
+           `VarPlan.execute_power` forms w = a_k ** d in the scan kernels.  Nothing but the scans' output is stored.
 """
 from __future__ import annotations
 
@@ -123,6 +126,33 @@ class VarPlan:
                                                         host_stream if host_stream is not None else self._stream(stream), ms, names, n))
         return outs, [(names[i].decode(), float(ms[i])) for i in range(n)]
 
+    def _bases(self, bases) -> ctypes.Array:
+        bases = [float(b) for b in bases]
+        if len(bases) != self.n_weights:
+            raise ValueError(f"expected {self.n_weights} bases, got {len(bases)}")
+        return (ctypes.c_float * self.n_weights)(*bases)
+
+    def execute_power(self, ins, exponents, bases, outs=None, stream=None):
+        """rf_var_plan_execute_power: as execute, but plane k of `exponents` holds d >= 0 and the scans use
+        w = exp2(d * log2(bases[k])), formed in the kernels; 0 < bases[k] < 1, one per exponent plane."""
+        pb = self._bases(bases)
+        pin, pd, pout, outs, host_stream = self._arguments(ins, exponents, outs)
+        capi.check(capi.lib().rf_var_plan_execute_power(self._h, pin, pd, pb, pout,
+                                                        host_stream if host_stream is not None else self._stream(stream)))
+        return outs
+
+    def execute_power_timed(self, ins, exponents, bases, outs=None, stream=None):
+        """rf_var_plan_execute_power_timed: (outputs, [(kernel name, ms), ...]); the launches execute_timed names."""
+        pb = self._bases(bases)
+        pin, pd, pout, outs, host_stream = self._arguments(ins, exponents, outs)
+        n = self.num_kernels
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_var_plan_execute_power_timed(self._h, pin, pd, pb, pout,
+                                                              host_stream if host_stream is not None else self._stream(stream),
+                                                              ms, names, n))
+        return outs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
 
 # ---- the domain-transform recursive filter ----------------------------------------------------------------------------------
 def domain_transform_weights(guide, sigma_s: float, sigma_r: float, iterations: int = 3):
@@ -142,31 +172,79 @@ def domain_transform_weights(guide, sigma_s: float, sigma_r: float, iterations: 
     dy = torch.ones(g.shape[1:], dtype=torch.float32, device=g.device)
     dx[:, 1:] += ratio * (g[:, :, 1:] - g[:, :, :-1]).abs().sum(0)
     dy[1:, :] += ratio * (g[:, 1:, :] - g[:, :-1, :]).abs().sum(0)
+    return [(torch.pow(a_k, dx).contiguous(), torch.pow(a_k, dy).contiguous()) for a_k in domain_transform_bases(sigma_s, iterations)]
+
+
+def domain_transform_bases(sigma_s: float, iterations: int = 3) -> List[float]:
+    """[a_0 .. a_{K-1}] of the domain-transform recursive filter:
+        sigma_k = sigma_s * sqrt(3) * 2^(K-1-k) / sqrt(4^K - 1),   a_k = exp(-sqrt(2) / sigma_k)."""
+    if iterations < 1:
+        raise ValueError("iterations must be >= 1")
     K = int(iterations)
     out = []
     for k in range(K):
         sigma_k = float(sigma_s) * math.sqrt(3.0) * 2.0 ** (K - 1 - k) / math.sqrt(4.0 ** K - 1.0)
-        a_k = math.exp(-math.sqrt(2.0) / sigma_k)
-        out.append((torch.pow(a_k, dx).contiguous(), torch.pow(a_k, dy).contiguous()))
+        out.append(math.exp(-math.sqrt(2.0) / sigma_k))
     return out
+
+
+def domain_transform_distances(guide, sigma_s: float, sigma_r: float, stream=None):
+    """(d_x, d_y): the exponent planes of the domain-transform filter for a device guide image (C, H, W) or (H, W), f32 or uint8,
+    by rf_var_distances (one HIP launch, one read of the guide):
+        d_x[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r][c-1]|     (the same along y; column 0 of d_x and row 0 of d_y hold 1)
+    scale = sigma_s / sigma_r, for a uint8 guide sigma_s / sigma_r / 255: a byte guide means that guide divided by 255.
+    W must be a multiple of 4.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    g = guide if guide.dim() == 3 else guide.unsqueeze(0)
+    if g.dim() != 3:
+        raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
+    if g.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"float32 or uint8 guides only, got {g.dtype}")
+    if not g.is_cuda:
+        raise ValueError("the guide must be a device tensor")
+    g = g.contiguous()
+    C, H, W = (int(s) for s in g.shape)
+    u8 = g.dtype == torch.uint8
+    scale = float(sigma_s) / float(sigma_r) / (255.0 if u8 else 1.0)
+    planes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
+    dx = torch.empty((H, W), dtype=torch.float32, device=g.device)
+    dy = torch.empty((H, W), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        capi.check(capi.lib().rf_var_distances(planes, C, int(u8), W, H, scale, dx.data_ptr(), dy.data_ptr(), g.device.index,
+                                               VarPlan._stream(stream)))
+    return dx, dy
 
 
 _SMOOTH_SCANS = [(0, True, 0), (0, False, 0), (1, True, 1), (1, False, 1)]      # +x -x on weights 0, +y -y on weights 1
 _smooth_plans: Dict[Tuple[int, int, int, int], VarPlan] = {}
 
 
-def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3):
+def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes"):
     """Edge-aware smoothing of a device image (C, H, W) or (H, W), f32, by the domain-transform recursive filter: per iteration
     +x, -x on that iteration's x weights, then +y, -y on its y weights (two fused stages, six launches).  guide=None: the image
-    guides itself.  One plan per (shape, device), cached; calls on one shape are ordered by the caller (one stream)."""
+    guides itself.  One plan per (shape, device), cached; calls on one shape are ordered by the caller (one stream).
+    form="planes": the weight planes of `domain_transform_weights`, 2 per iteration, read by `execute`.  form="power": the two
+    planes of `domain_transform_distances`, computed once, and `execute_power` with bases [a_k, a_k] per iteration -- no weight
+    plane is stored; the guide may be uint8 (taken as it is: guide / 255)."""
     import torch
+    if form not in ("planes", "power"):
+        raise ValueError(f"form must be 'planes' or 'power', got {form!r}")
     img = image if image.dim() == 3 else image.unsqueeze(0)
     if img.dim() != 3:
         raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
     img = img.to(torch.float32).contiguous()
-    weights = domain_transform_weights(image if guide is None else guide, sigma_s, sigma_r, iterations)
+    if form == "power":
+        g = img if guide is None else guide
+        if g.dtype != torch.uint8:
+            g = g.to(torch.float32)
+        distances = [d.to(img.device) for d in domain_transform_distances(g.to(img.device), sigma_s, sigma_r)]
+        weights = [(distances, [a_k, a_k]) for a_k in domain_transform_bases(sigma_s, iterations)]
+        shape_hw = tuple(distances[0].shape)
+    else:
+        weights = domain_transform_weights(image if guide is None else guide, sigma_s, sigma_r, iterations)
+        shape_hw = tuple(weights[0][0].shape)
     C, H, W = (int(s) for s in img.shape)
-    if tuple(weights[0][0].shape) != (H, W):
+    if shape_hw != (H, W):
         raise ValueError("guide and image must have the same height and width")
     key = (C, H, W, img.device.index if img.device.index is not None else torch.cuda.current_device())
     plan = _smooth_plans.get(key)
@@ -176,6 +254,9 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     outs = [out[c] for c in range(C)]
     src = [img[c] for c in range(C)]
     for wx, wy in weights:
-        plan.execute(src, [wx.to(img.device), wy.to(img.device)], outs)
+        if form == "power":
+            plan.execute_power(src, wx, wy, outs)      # (the distance planes, this iteration's bases)
+        else:
+            plan.execute(src, [wx.to(img.device), wy.to(img.device)], outs)
         src = outs
     return out if image.dim() == 3 else out[0]
