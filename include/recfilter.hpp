@@ -816,3 +816,55 @@ inline void domain_transform_distances(const std::vector<const void *> &guide_pl
     if (rf_var_distances(guide_planes.data(), (int32_t)guide_planes.size(), guide_u8 ? 1 : 0, width, height, scale, dx, dy, -1,
                          stream) != RF_OK) throw RecFilterError(rf_last_error_string());
 }
+
+/** Edge-aware smoothing as one object (recfilter_amd.h, rf_smooth_plan_*): the domain-transform recursive filter of `planes`
+ *  dense device planes of width x height, f32 or uint8 (bytes in AND out: sat8 of the f32 filter on the widened bytes, rounded
+ *  once, at the final store).  guide_planes = 0: the image guides itself; else that many separate guide planes, f32 or uint8 (a
+ *  byte guide means that guide divided by 255).  The library owns the distance planes and sequences 1 + 6 K launches.
+ *      RecFilterSmooth F(width, height, 3, 0, false, true, 3, 60.0, 0.4);      // an RGB byte image guiding itself
+ *      F.realize({r, g, b}, {}, {r, g, b});                                      // device pointers; in == out is allowed
+ *  The plan is built on first use and kept; it owns one workspace: order the realizations of one object. */
+class RecFilterSmooth {
+    rf_smooth_desc desc{};
+    rf_smooth_plan *plan = nullptr;
+    void prepare() {
+        if (!plan && rf_smooth_plan_create(&desc, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+public:
+    RecFilterSmooth(int64_t width, int64_t height, int planes, int guide_planes, bool guide_u8, bool image_u8, int iterations,
+                    double sigma_s, double sigma_r) {
+        desc.abi = RF_ABI;
+        desc.image_u8 = image_u8 ? 1 : 0;
+        desc.width = width;
+        desc.height = height;
+        desc.n_planes = planes;
+        desc.n_guide = guide_planes;
+        desc.guide_u8 = guide_u8 ? 1 : 0;
+        desc.iterations = iterations;
+        desc.sigma_s = sigma_s;
+        desc.sigma_r = sigma_r;
+        desc.device = -1;
+        desc.flags = 0;
+    }
+    RecFilterSmooth(const RecFilterSmooth &) = delete;
+    RecFilterSmooth &operator=(const RecFilterSmooth &) = delete;
+    ~RecFilterSmooth() { if (plan) rf_smooth_plan_destroy(plan); }
+    /** image / out: one device plane per channel; guide: the separate guide planes, empty when the image guides itself.
+     *  Asynchronous on `stream`. */
+    void realize(const std::vector<const void *> &image, const std::vector<const void *> &guide, const std::vector<void *> &out,
+                 void *stream = nullptr) {
+        prepare();
+        if ((int)image.size() != desc.n_planes || (int)out.size() != desc.n_planes || (int)guide.size() != desc.n_guide)
+            throw RecFilterError("realize: as many image, output and guide planes as the filter was built for");
+        if (rf_smooth_plan_execute(plan, image.data(), guide.empty() ? nullptr : guide.data(), out.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** a_0 .. a_{K-1}: the f32 bases of the iterations */
+    std::vector<float> bases() {
+        prepare();
+        std::vector<float> b((size_t)desc.iterations);
+        if (rf_smooth_plan_bases(plan, b.data()) != RF_OK) throw RecFilterError(rf_last_error_string());
+        return b;
+    }
+    int num_kernels() { prepare(); return rf_smooth_plan_num_kernels(plan); }
+};

@@ -497,6 +497,60 @@ int    rf_var_plan_execute_power_timed(rf_var_plan *plan, const void *const *in_
 int    rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height,
                         float scale, void *dx, void *dy, int32_t device, void *stream);
 
+/* ---- edge-aware smoothing as one plan ------------------------------------------------------------------------------------- */
+/* The domain-transform recursive filter (Gastal & Oliveira 2011) of an image of n_planes dense planes, f32 or uint8, that share
+ * their edges.  The edges come from the image itself (n_guide = 0) or from n_guide separate guide planes, f32 or uint8.  A byte
+ * guide means that guide divided by 255.  The plan owns the two distance planes and sequences every launch:
+ *     "var_distances"  once, as rf_var_distances with scale = (float)(sigma_s / sigma_r), over 255 where the guiding planes are bytes;
+ *     then for k = 0 .. K-1 the stages +x -x and +y -y of the power form on d_x, d_y with the bases {a_k, a_k}:
+ *     "var_tails_x", "var_carry", "var_pass2_x", "var_tails_y", "var_carry", "var_pass2_y"
+ *     sigma_k = sigma_s * sqrt(3) * 2^(K-1-k) / sqrt(4^K - 1)  (in double),   a_k = (float)exp(-sqrt(2) / sigma_k).
+ * The number of launches is 1 + 6 K.  No conversion launch exists.
+ * f32 images: the first stage reads image_planes, everything else runs in place on out_planes; the result is, bit for bit, that
+ * of rf_var_distances followed by K calls of rf_var_plan_execute_power.
+ * uint8 images (image_u8 = 1, input AND output; the storage contract of RF_IO_U8): the filter is the f32 filter on the widened
+ * bytes.  The plan owns n_planes f32 working planes; the first stage reads the caller's bytes and writes them, the stages between
+ * run in place on them, and the final pass of the last stage stores out = sat8(f32 result) to out_planes: to nearest, ties to
+ * even, clamped to [0, 255], NaN -> 0.  Nothing between two iterations is rounded to bytes.
+ * Workspace: two f32 distance planes + (uint8 images) n_planes f32 planes + the tails and carries of the varying scans.
+ * Create refuses, before any HIP call: abi != RF_ABI, nonzero flags, n_planes outside 1..RF_MAX_PLANES, n_guide outside
+ * 0..RF_MAX_PLANES, image_u8 or guide_u8 other than 0 or 1, guide_u8 = 1 with n_guide = 0, iterations outside
+ * 1..RF_SMOOTH_MAX_ITERATIONS, extents below 1, a sigma that is not finite and positive (RF_ERR_INVALID_ARG); a width that is
+ * not a multiple of 4, an extent above 2^21, an a_k that rounds to 1 or to 0 in f32 (RF_ERR_UNSUPPORTED; the message names k).
+ * Execute refuses: null arrays or pointers, guide_planes that does not match n_guide (NULL iff n_guide == 0), f32 planes that
+ * are not 16-byte aligned, uint8 planes that are not 4-byte aligned, an input plane that is neither the output plane of the same
+ * index nor disjoint from every output plane (RF_ERR_INVALID_ARG); a host-only plan (RF_ERR_HIP).  in == out is allowed in both
+ * image types; guide planes may overlap output planes (the distances are formed first, on the same stream).
+ * Executes of one plan are ordered by the caller, as for a plan of varying scans: one stream, or the caller's synchronisation.
+ * Every function returns a status and never throws. */
+#define RF_SMOOTH_MAX_ITERATIONS 8
+typedef struct {
+    uint32_t abi;                     /* RF_ABI                                                  */
+    int32_t  image_u8;                /* 0: f32 image planes; 1: uint8 image planes, in AND out  */
+    int64_t  width, height;
+    int32_t  n_planes;                /* 1..RF_MAX_PLANES image planes sharing the edges         */
+    int32_t  n_guide;                 /* 0: the image guides itself; else 1..RF_MAX_PLANES       */
+    int32_t  guide_u8;                /* type of the separate guide planes; 0 when n_guide == 0  */
+    int32_t  iterations;              /* K, 1..RF_SMOOTH_MAX_ITERATIONS                          */
+    double   sigma_s, sigma_r;        /* finite, > 0                                             */
+    int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
+    uint32_t flags;                   /* 0                                                       */
+} rf_smooth_desc;
+typedef struct rf_smooth_plan rf_smooth_plan;
+int    rf_smooth_plan_create(const rf_smooth_desc *desc, rf_smooth_plan **plan_out);
+int    rf_smooth_plan_destroy(rf_smooth_plan *plan);
+size_t rf_smooth_plan_workspace_bytes(const rf_smooth_plan *plan);
+int    rf_smooth_plan_num_kernels(const rf_smooth_plan *plan);
+/* a_0 .. a_{K-1}, the bases the plan runs with */
+int    rf_smooth_plan_bases(const rf_smooth_plan *plan, float *out /* iterations */);
+/* image_planes / out_planes: n_planes device pointers each; guide_planes: n_guide device pointers, NULL iff n_guide == 0.
+ * Asynchronous on `stream`. */
+int    rf_smooth_plan_execute(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                              void *const *out_planes, void *stream);
+/* per-kernel milliseconds and names (valid for the life of the plan); synchronises the stream */
+int    rf_smooth_plan_execute_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                    void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);
 const char *rf_version(void);

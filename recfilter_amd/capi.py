@@ -21,6 +21,7 @@ RF_ABI = 3          # revision of include/recfilter_amd.h this module mirrors (r
 RF_MAX_SCANS = 32
 RF_MAX_PLANES = 16
 RF_VAR_MAX_SCANS = 8     # scans (and weight planes) of a plan of spatially varying scans (rf_var_desc)
+RF_SMOOTH_MAX_ITERATIONS = 8     # iterations of a smoothing plan (rf_smooth_desc)
 RF_DEVICE_HOST_ONLY = -2
 
 RF_OK, RF_ERR_INVALID_ARG, RF_ERR_UNSUPPORTED, RF_ERR_HIP, RF_ERR_NOMEM, RF_ERR_STATE = range(6)
@@ -66,6 +67,8 @@ EXPORTED_SYMBOLS = [
     "rf_gaussian_box_filter", "rf_box_difference", "rf_tap_filter", "rf_stream_copy", "rf_last_error_string", "rf_version", "rf_device_count",
     "rf_var_plan_create", "rf_var_plan_destroy", "rf_var_plan_workspace_bytes", "rf_var_plan_num_kernels", "rf_var_plan_execute",
     "rf_var_plan_execute_timed", "rf_var_plan_execute_power", "rf_var_plan_execute_power_timed", "rf_var_distances",
+    "rf_smooth_plan_create", "rf_smooth_plan_destroy", "rf_smooth_plan_workspace_bytes", "rf_smooth_plan_num_kernels",
+    "rf_smooth_plan_bases", "rf_smooth_plan_execute", "rf_smooth_plan_execute_timed",
 ]
 
 
@@ -102,6 +105,13 @@ class VarDesc(ctypes.Structure):
     _fields_ = [("ndim", ctypes.c_int32), ("abi", ctypes.c_uint32), ("extent", ctypes.c_int64 * RF_MAX_DIMS),
                 ("dtype", ctypes.c_int32), ("n_planes", ctypes.c_int32), ("n_weights", ctypes.c_int32),
                 ("n_scans", ctypes.c_int32), ("scans", ctypes.POINTER(VarScanDesc)),
+                ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class SmoothDesc(ctypes.Structure):
+    _fields_ = [("abi", ctypes.c_uint32), ("image_u8", ctypes.c_int32), ("width", ctypes.c_int64), ("height", ctypes.c_int64),
+                ("n_planes", ctypes.c_int32), ("n_guide", ctypes.c_int32), ("guide_u8", ctypes.c_int32),
+                ("iterations", ctypes.c_int32), ("sigma_s", ctypes.c_double), ("sigma_r", ctypes.c_double),
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
@@ -185,6 +195,14 @@ def lib() -> ctypes.CDLL:
     L.rf_var_plan_execute_power_timed.argtypes = [vp, vpp, vpp, fp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
     L.rf_var_distances.argtypes = [vpp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, vp, vp,
                                    ctypes.c_int32, vp]
+    L.rf_smooth_plan_create.argtypes = [ctypes.POINTER(SmoothDesc), vpp]
+    L.rf_smooth_plan_destroy.argtypes = [vp]
+    L.rf_smooth_plan_workspace_bytes.argtypes = [vp]
+    L.rf_smooth_plan_workspace_bytes.restype = ctypes.c_size_t
+    L.rf_smooth_plan_num_kernels.argtypes = [vp]
+    L.rf_smooth_plan_bases.argtypes = [vp, fp]
+    L.rf_smooth_plan_execute.argtypes = [vp, vpp, vpp, vpp, vp]
+    L.rf_smooth_plan_execute_timed.argtypes = [vp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "plan.h"
+#include "plan_smooth.h"
 #include "plan_var.h"
 
 namespace rf {
@@ -606,6 +607,46 @@ int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t g
                      void *dx, void *dy, int32_t device, void *stream) {
     return fenced("rf_var_distances", [&] {
         return run_var_distances(guide_planes, n_guide, guide_u8, width, height, scale, dx, dy, device, (hipStream_t)stream);
+    });
+}
+
+// ---- edge-aware smoothing as one plan (plan_smooth.cpp) -----------------------------------------------------------------------
+int rf_smooth_plan_create(const rf_smooth_desc *desc, rf_smooth_plan **plan_out) {
+    return fenced("rf_smooth_plan_create", [&] { return build_smooth_plan(desc, plan_out); });
+}
+
+int rf_smooth_plan_destroy(rf_smooth_plan *plan) {
+    return fenced("rf_smooth_plan_destroy", [&] {
+        if (plan) {
+            if (!plan->host_only) (void)hipSetDevice(plan->device);
+            delete plan;
+        }
+        return (int)RF_OK;
+    });
+}
+
+size_t rf_smooth_plan_workspace_bytes(const rf_smooth_plan *plan) { return plan ? plan->workspace_bytes() : 0; }
+int rf_smooth_plan_num_kernels(const rf_smooth_plan *plan) { return plan ? (int)plan->names.size() : 0; }
+
+int rf_smooth_plan_bases(const rf_smooth_plan *plan, float *out) {
+    if (!plan || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (size_t k = 0; k < plan->bases.size(); k++) out[k] = plan->bases[k];
+    return RF_OK;
+}
+
+int rf_smooth_plan_execute(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
+                           void *stream) {
+    return fenced("rf_smooth_plan_execute", [&] { return run_smooth_plan(plan, image_planes, guide_planes, out_planes, (hipStream_t)stream, nullptr); });
+}
+
+int rf_smooth_plan_execute_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                 void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_smooth_plan_execute_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
+        if (names_out)
+            for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
+        return run_smooth_plan(plan, image_planes, guide_planes, out_planes, (hipStream_t)stream, ms_out);
     });
 }
 

@@ -19,8 +19,8 @@ enum VarMode { VAR_CAUSAL = 0, VAR_ANTICAUSAL = 1, VAR_PAIR = 2 };
 //   tails [tile][component][plane][line]   E1 / E2 per image plane; P1 / G / P2 depend on the weights alone: plane 0 holds them
 //   carry [tile][c, d][plane][line]        what enters tile `tile` from the left (c) and from the right (d)
 struct VarArgs {
-    const float *src[RF_MAX_PLANES];
-    float *dst[RF_MAX_PLANES];
+    const void *src[RF_MAX_PLANES];     // f32 planes, or bytes (src_u8)
+    void *dst[RF_MAX_PLANES];           // what the final pass stores: f32 planes, or bytes (dst_u8)
     const float *weights;
     float *tails;
     float *carry;
@@ -32,6 +32,9 @@ struct VarArgs {
     // power form (rf_var_plan_execute_power): `weights` holds exponents d, the kernels form w = exp2(d * log2_base) as they load
     int32_t power;
     float log2_base;
+    // byte planes (rf_smooth_plan; the pair mode in the power form only): the source of a stage along x, the destination of a final
+    // pass along y.  Separate kernel instances, chosen by the launchers; the f32 instances never look at these.
+    int32_t src_u8, dst_u8;
 };
 
 // d_x = 1 + scale * sum_ch |g - g one column to the left|, d_y the same with the row above (kernels_var.hip, var_distances)

@@ -25,8 +25,15 @@
 // and var_carry see weights as before.  d = 0 gives 1 and d = +inf gives 0, exactly.  A separate instantiation: the plane-form
 // kernels hold no trace of it.
 //
+// Byte planes (rf_smooth_plan, plan_smooth.cpp; the pair mode in the power form only): a stage along x may read uint8 planes -- a
+// 4-byte load per request where the f32 form loads 16, widened exactly, into the same transposition -- and a final pass along y
+// may store them, sat8 (pixel.h) of the f32 result, one byte per lane and row.  A trailing template TYPE argument with a default:
+// the f32 instances are what they were, register for register.
+//
 // var_distances: the two exponent planes of the domain-transform filter from a guide image, one streaming launch.
 #include "kernels_var.h"
+
+#include "pixel.h"
 
 #include <algorithm>
 
@@ -126,13 +133,15 @@ __device__ __forceinline__ void store_tails(const VarArgs &a, int t, int pl, int
 }
 
 // ---- along y: lane = column -------------------------------------------------------------------------------------------
-template <int MODE, bool FINAL, bool POWER>
+// DST: the samples the final pass stores -- float, or uint8_t (the last pass of a byte image, rf_smooth_plan: sat8 of pixel.h, one
+// byte per lane and row).  Instantiated for the pair mode in the power form only.
+template <int MODE, bool FINAL, bool POWER, typename DST = float>
 __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
     const int col = blockIdx.x * 64 + threadIdx.x;
     if (col >= a.width) return;                       // (no barrier below: lanes are independent)
     const int t = blockIdx.y, pl = blockIdx.z, t0 = t * T;
     const int64_t pitch = a.width;
-    const float *src = a.src[pl];
+    const float *src = static_cast<const float *>(a.src[pl]);
     float x[T], w[T + 1];
 #pragma unroll
     for (int i = 0; i < T; i++) {
@@ -155,10 +164,10 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
     mask_tile(x, w, t0, a.height);
     if constexpr (FINAL) {
         tile_final<MODE>(x, w, c, d);
-        float *dst = a.dst[pl];
+        DST *dst = static_cast<DST *>(a.dst[pl]);
 #pragma unroll
         for (int i = 0; i < T; i++)
-            if (t0 + i < a.height) (dst + (t0 + i) * pitch)[col] = x[i];
+            if (t0 + i < a.height) (dst + (t0 + i) * pitch)[col] = PixelTraits<DST>::store(x[i]);
     } else {
         float out[kVarComponents];
         tile_tails<MODE>(x, w, pl == 0, out);
@@ -181,6 +190,21 @@ __device__ __forceinline__ void request_tile(const float *plane, const VarArgs &
     }
 }
 
+// a byte plane: the same rows and chunks, 4 bytes where the f32 form moves 16, widened exactly -- a wave instruction moves four
+// rows of 64 contiguous bytes; everything behind the loads is the f32 kernel's
+__device__ __forceinline__ void request_tile(const uint8_t *plane, const VarArgs &a, int r0, int c0, float (&v)[T]) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < T / 4; k++) {
+        const int flat = k * 64 + lane;
+        const int r = min(r0 + (flat >> 4), a.height - 1);
+        const int c = min(c0 + (flat & 15) * 4, a.width - 4);      // (the width is a multiple of 4: a 4-byte aligned address)
+        const uint32_t q = *reinterpret_cast<const uint32_t *>(plane + (int64_t)r * a.width + c);
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[4 * k + j] = (float)((q >> (8 * j)) & 255u);
+    }
+}
+
 // chunks as requested -> the lane's row of the tile
 __device__ __forceinline__ void transpose_in(const float (&v)[T], float *lds, float (&row)[T]) {
     const int lane = threadIdx.x;
@@ -198,13 +222,15 @@ __device__ __forceinline__ void transpose_in(const float (&v)[T], float *lds, fl
     __syncthreads();
 }
 
-template <int MODE, bool FINAL, bool POWER>
+// SRC: the samples of the source planes -- float, or uint8_t (the first stage of a byte image, rf_smooth_plan; the destination
+// stays f32).  Instantiated for the pair mode in the power form only.
+template <int MODE, bool FINAL, bool POWER, typename SRC = float>
 __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
     const int t = blockIdx.x, pl = blockIdx.z, t0 = t * T, r0 = blockIdx.y * 64;
     const int row = r0 + lane;
-    const float *src = a.src[pl];
+    const SRC *src = static_cast<const SRC *>(a.src[pl]);
     float vx[T], vw[T];
     request_tile(src, a, r0, t0, vx);
     request_tile(a.weights, a, r0, t0, vw);
@@ -235,7 +261,7 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
         for (int k = 0; k < T / 4; k++)
             *reinterpret_cast<float4 *>(lds + lane * LDS_PITCH + k * 4) = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
         __syncthreads();
-        float *dst = a.dst[pl];
+        float *dst = static_cast<float *>(a.dst[pl]);
 #pragma unroll
         for (int k = 0; k < T / 4; k++) {
             const int flat = k * 64 + lane;
@@ -361,6 +387,18 @@ int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
     const dim3 block(64);
     const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)a.n_planes)
                                : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)a.n_planes);
+    // byte planes (rf_smooth_plan): the instances that exist, and nothing else -- there is no conversion to fall back on
+    if (a.src_u8 || a.dst_u8) {
+        const char *what = FINAL ? (dim == 0 ? "var_pass2_x" : "var_pass2_y") : (dim == 0 ? "var_tails_x" : "var_tails_y");
+        const bool x_src = dim == 0 && a.src_u8 && !a.dst_u8, y_dst = dim == 1 && FINAL && a.dst_u8 && !a.src_u8;
+        if (a.mode != VAR_PAIR || !a.power || !(x_src || y_dst)) {
+            set_error("%s: no kernel for byte planes here (source %s, destination %s)", what, a.src_u8 ? "uint8" : "f32", a.dst_u8 ? "uint8" : "f32");
+            return RF_ERR_UNSUPPORTED;
+        }
+        if (x_src) hipLaunchKernelGGL((var_x_kernel<VAR_PAIR, FINAL, true, uint8_t>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var_y_kernel<VAR_PAIR, true, true, uint8_t>), grid, block, 0, stream, a);
+        return launched(what);
+    }
 #define RF_VAR_LAUNCH_FORM(MODE, POWER)                                                                   \
     if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL, POWER>), grid, block, 0, stream, a);      \
     else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL, POWER>), grid, block, 0, stream, a)

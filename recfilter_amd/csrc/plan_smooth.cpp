@@ -1,0 +1,202 @@
+// plan_smooth.cpp -- edge-aware smoothing by the domain-transform recursive filter (Gastal & Oliveira 2011) as one plan.
+//
+// One var_distances launch forms the exponent planes d_x, d_y the plan owns; then K runs of an inner varying plan
+// (+x -x +y -y: two pair stages, power form) with bases {a_k, a_k}.  Nothing here is a kernel of its own: the launches are those
+// of rf_var_distances and rf_var_plan_execute_power, with the same arguments, so an f32 image gives their bits.
+// Byte images (the storage contract of RF_IO_U8): the first stage reads the caller's bytes into f32 working planes the plan
+// owns, everything between runs in place on those, and the final pass of the last stage stores sat8 (pixel.h) of its f32
+// result to the caller's bytes.  No conversion launch, and nothing between two iterations is rounded.
+#include "plan_smooth.h"
+
+#include <cmath>
+
+rf_smooth_plan::~rf_smooth_plan() {
+    if (planes) (void)hipFree(planes);
+}
+
+namespace rf {
+
+namespace {
+
+int validate(const rf_smooth_desc *d) {
+    if (d->abi != RF_ABI) {
+        set_error("rf_smooth_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->flags != 0) { set_error("rf_smooth_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
+    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
+    if (d->n_guide < 0 || d->n_guide > RF_MAX_PLANES) { set_error("n_guide must be 0..%d (got %d)", RF_MAX_PLANES, d->n_guide); return RF_ERR_INVALID_ARG; }
+    if (d->image_u8 != 0 && d->image_u8 != 1) { set_error("image_u8 must be 0 or 1 (got %d)", d->image_u8); return RF_ERR_INVALID_ARG; }
+    if (d->guide_u8 != 0 && d->guide_u8 != 1) { set_error("guide_u8 must be 0 or 1 (got %d)", d->guide_u8); return RF_ERR_INVALID_ARG; }
+    if (d->guide_u8 == 1 && d->n_guide == 0) { set_error("guide_u8 = 1 without guide planes (n_guide = 0: the image guides itself)"); return RF_ERR_INVALID_ARG; }
+    if (d->iterations < 1 || d->iterations > RF_SMOOTH_MAX_ITERATIONS) {
+        set_error("iterations must be 1..%d (got %d)", RF_SMOOTH_MAX_ITERATIONS, d->iterations);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->width < 1 || d->height < 1) { set_error("width and height must be positive (got %lld x %lld)", (long long)d->width, (long long)d->height); return RF_ERR_INVALID_ARG; }
+    if (!std::isfinite(d->sigma_s) || !(d->sigma_s > 0.0)) { set_error("sigma_s must be finite and positive (got %g)", d->sigma_s); return RF_ERR_INVALID_ARG; }
+    if (!std::isfinite(d->sigma_r) || !(d->sigma_r > 0.0)) { set_error("sigma_r must be finite and positive (got %g)", d->sigma_r); return RF_ERR_INVALID_ARG; }
+    if (d->width % 4 != 0) {
+        set_error("the varying scans move 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)d->width);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (d->width > var_max_extent() || d->height > var_max_extent()) {
+        set_error("extents %lld x %lld are above %lld", (long long)d->width, (long long)d->height, (long long)var_max_extent());
+        return RF_ERR_UNSUPPORTED;
+    }
+    return RF_OK;
+}
+
+bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
+
+}  // namespace
+
+int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out) {
+    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    *out = nullptr;
+    int rc = validate(desc);
+    if (rc != RF_OK) return rc;
+    std::unique_ptr<rf_smooth_plan> plan(new rf_smooth_plan);
+    plan->width = desc->width;
+    plan->height = desc->height;
+    plan->n_planes = desc->n_planes;
+    plan->n_guide = desc->n_guide;
+    plan->iterations = desc->iterations;
+    plan->image_u8 = desc->image_u8 != 0;
+    plan->guide_u8 = desc->guide_u8 != 0;
+    plan->host_only = desc->device == RF_DEVICE_HOST_ONLY;
+    // a byte guide means that guide divided by 255 (a separate uint8 guide, or a uint8 image guiding itself)
+    const bool bytes_guide = desc->n_guide > 0 ? plan->guide_u8 : plan->image_u8;
+    plan->scale = (float)(desc->sigma_s / desc->sigma_r / (bytes_guide ? 255.0 : 1.0));
+    if (!std::isfinite(plan->scale)) { set_error("sigma_s / sigma_r = %g is not an f32", desc->sigma_s / desc->sigma_r); return RF_ERR_UNSUPPORTED; }
+    const int K = desc->iterations;
+    for (int k = 0; k < K; k++) {
+        const double sigma_k = desc->sigma_s * std::sqrt(3.0) * std::ldexp(1.0, K - 1 - k) / std::sqrt(std::ldexp(1.0, 2 * K) - 1.0);
+        const float a_k = (float)std::exp(-std::sqrt(2.0) / sigma_k);
+        if (!(a_k > 0.0f && a_k < 1.0f)) {
+            set_error("iteration k = %d: the base a_k = exp(-sqrt(2) / %g) rounds to %g in f32", k, sigma_k, (double)a_k);
+            return RF_ERR_UNSUPPORTED;
+        }
+        plan->bases.push_back(a_k);
+        plan->log2_bases.push_back((float)std::log2((double)a_k));
+    }
+    const rf_var_scan_desc scans[4] = {{0, 1, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 1}};
+    rf_var_desc vd{};
+    vd.ndim = 2;
+    vd.abi = RF_ABI;
+    vd.extent[0] = desc->width;
+    vd.extent[1] = desc->height;
+    vd.dtype = RF_F32;
+    vd.n_planes = desc->n_planes;
+    vd.n_weights = 2;
+    vd.n_scans = 4;
+    vd.scans = scans;
+    vd.device = desc->device;
+    vd.flags = 0;
+    rf_var_plan *inner = nullptr;
+    rc = build_var_plan(&vd, &inner);      // (the device checks, and the tails and the carries)
+    if (rc != RF_OK) return rc;
+    plan->inner.reset(inner);
+    plan->device = inner->device;
+    const size_t plane_bytes = (size_t)(desc->width * desc->height) * sizeof(float);
+    plan->planes_bytes = plane_bytes * (size_t)(2 + (plan->image_u8 ? desc->n_planes : 0));
+    if (!plan->host_only) {
+        RF_HIP_CHECK(hipSetDevice(plan->device));
+        if (hipMalloc((void **)&plan->planes, plan->planes_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of %zu bytes of distance and working planes failed", plan->planes_bytes);
+            return RF_ERR_NOMEM;
+        }
+    }
+    plan->names.push_back("var_distances");
+    for (int k = 0; k < K; k++)
+        for (const std::string &n : inner->names) plan->names.push_back(n);
+    *out = plan.release();
+    return RF_OK;
+}
+
+int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
+                    hipStream_t stream, float *ms_out) {
+    if (!plan || !image_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    if (plan->n_guide > 0 && !guide_planes) { set_error("this plan takes %d separate guide planes: guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }
+    if (plan->n_guide == 0 && guide_planes) { set_error("this plan's image guides itself (n_guide = 0): guide_planes must be null"); return RF_ERR_INVALID_ARG; }
+    if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
+    const size_t samples = (size_t)(plan->width * plan->height);
+    const size_t image_bytes = samples * (plan->image_u8 ? 1 : sizeof(float));
+    const uintptr_t image_mask = plan->image_u8 ? 3u : 15u, guide_mask = plan->guide_u8 ? 3u : 15u;
+    for (int pl = 0; pl < plan->n_planes; pl++) {
+        if (!image_planes[pl] || !out_planes[pl]) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
+        if ((((uintptr_t)image_planes[pl] | (uintptr_t)out_planes[pl]) & image_mask) != 0) {
+            set_error("plane %d: %s image planes must be %u-byte aligned", pl, plan->image_u8 ? "uint8" : "f32", (unsigned)image_mask + 1);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    for (int ch = 0; ch < plan->n_guide; ch++) {
+        if (!guide_planes[ch]) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
+        if (((uintptr_t)guide_planes[ch] & guide_mask) != 0) {
+            set_error("guide plane %d: %s guide planes must be %u-byte aligned", ch, plan->guide_u8 ? "uint8" : "f32", (unsigned)guide_mask + 1);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    // a stage has loaded its tile before it stores, so a plane may be filtered in place; any other overlap of an input with an output
+    // is read after another workgroup's store
+    for (int pl = 0; pl < plan->n_planes; pl++)
+        for (int q = 0; q < plan->n_planes; q++) {
+            if (pl == q && image_planes[pl] == out_planes[q]) continue;
+            if (overlap((uintptr_t)image_planes[pl], image_bytes, (uintptr_t)out_planes[q], image_bytes)) {
+                set_error("input plane %d overlaps output plane %d: an input plane is its own output plane or disjoint from every output plane", pl, q);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    // events are destroyed on every return path
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } events;
+    const size_t n_kernels = plan->names.size();
+    if (ms_out) {
+        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
+        for (size_t i = 0; i < n_kernels + 1; i++) {
+            hipEvent_t e;
+            RF_HIP_CHECK(hipEventCreate(&e));
+            events.ev.push_back(e);
+        }
+        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
+    }
+    size_t launch = 0;
+    const std::function<int()> mark = [&]() -> int {
+        launch++;
+        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
+        return RF_OK;
+    };
+    float *dx = plan->planes, *dy = dx + samples;
+    // the distances first, on the same stream: guide planes may be output planes
+    const bool self = plan->n_guide == 0;
+    int rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
+                               plan->width, plan->height, plan->scale, dx, dy, plan->device, stream);
+    if (rc == RF_OK) rc = mark();
+    if (rc != RF_OK) return rc;
+    void *work[RF_MAX_PLANES] = {};
+    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(dy + samples * (size_t)(1 + pl)) : out_planes[pl];
+    const void *const weights[2] = {dx, dy};
+    const int K = plan->iterations;
+    for (int k = 0; k < K; k++) {
+        VarIo io{};
+        io.in = k == 0 ? image_planes : (const void *const *)work;
+        io.in_u8 = k == 0 && plan->image_u8;
+        io.work = work;
+        io.out = k == K - 1 ? out_planes : work;
+        io.out_u8 = k == K - 1 && plan->image_u8;
+        const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
+        rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, mark);
+        if (rc != RF_OK) return rc;
+    }
+    if (ms_out) {
+        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
+        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
+    }
+    return RF_OK;
+}
+
+}  // namespace rf

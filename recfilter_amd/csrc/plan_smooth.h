@@ -1,0 +1,34 @@
+// plan_smooth.h -- the plan behind the rf_smooth_plan_* entry points: the domain-transform recursive filter as one object
+// (plan_smooth.cpp).
+#pragma once
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "plan_var.h"
+
+struct rf_smooth_plan {
+    int64_t width = 0, height = 0;
+    int n_planes = 1, n_guide = 0, iterations = 1;
+    bool image_u8 = false, guide_u8 = false;
+    int device = 0;
+    bool host_only = false;
+    float scale = 0.0f;                      // of var_distances: sigma_s / sigma_r, over 255 where the planes that guide are bytes
+    std::vector<float> bases;                // a_k
+    std::vector<float> log2_bases;           // (float)log2((double)a_k): what rf_var_plan_execute_power forms from a_k
+    std::unique_ptr<rf_var_plan> inner;      // +x -x +y -y on two exponent planes: two pair stages, the tails and the carries
+    // one allocation: d_x, d_y, then (byte images) n_planes f32 working planes
+    float *planes = nullptr;
+    size_t planes_bytes = 0;
+    std::vector<std::string> names;          // "var_distances", then the inner plan's six per iteration
+    size_t workspace_bytes() const { return planes_bytes + inner->workspace_bytes(); }
+    ~rf_smooth_plan();
+};
+
+namespace rf {
+int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out);
+// ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
+int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
+                    hipStream_t stream, float *ms_out);
+}  // namespace rf

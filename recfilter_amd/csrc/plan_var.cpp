@@ -6,7 +6,8 @@
 // tails [tile][component][plane][line] and carries [tile][c, d][plane][line], sized for the dimension that needs more.  Every
 // stage is three launches: tails, carry, final pass.  The first stage reads the input planes, later stages filter the output
 // planes in place.  The power form (rf_var_plan_execute_power) runs the same stages on exponent planes: a stage carries
-// log2 of its plane's base and launches the kernels' POWER instances.
+// log2 of its plane's base and launches the kernels' POWER instances.  run_var_plan checks the arguments and owns the timing
+// events; launch_var_stages issues the launches of one run, and is what the smoothing plan (plan_smooth.cpp) calls per iteration.
 #include "plan_var.h"
 
 #include <algorithm>
@@ -58,6 +59,8 @@ int validate(const rf_var_desc *d) {
 int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
 
 }  // namespace
+
+int64_t var_max_extent() { return kVarMaxExtent; }
 
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
     if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
@@ -173,18 +176,34 @@ int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *co
         RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
     }
     size_t launch = 0;
-    auto mark = [&]() -> int {
+    const std::function<int()> mark = [&]() -> int {
         launch++;
         if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
         return RF_OK;
     };
-    for (size_t s = 0; s < plan->stages.size(); s++) {
+    VarIo io{};
+    io.in = in_planes;
+    io.work = io.out = out_planes;
+    int rc = launch_var_stages(plan, io, weight_planes, bases ? log2_base : nullptr, stream, mark);
+    if (rc != RF_OK) return rc;
+    if (ms_out) {
+        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
+        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
+    }
+    return RF_OK;
+}
+
+int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
+                      const std::function<int()> &mark) {
+    const size_t last = plan->stages.size() - 1;
+    for (size_t s = 0; s <= last; s++) {
         const rf_var_stage &st = plan->stages[s];
         VarArgs a{};
         for (int pl = 0; pl < plan->n_planes; pl++) {
-            a.src[pl] = (const float *)(s == 0 ? in_planes[pl] : out_planes[pl]);
-            a.dst[pl] = (float *)out_planes[pl];
+            a.src[pl] = s == 0 ? io.in[pl] : io.work[pl];
+            a.dst[pl] = s == last ? io.out[pl] : io.work[pl];
         }
+        a.src_u8 = s == 0 && io.in_u8;
         a.weights = (const float *)weight_planes[st.weights];
         a.tails = plan->tails;
         a.carry = plan->carry;
@@ -194,19 +213,16 @@ int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *co
         a.tiles = (int32_t)tiles_of(st.dim == 0 ? plan->width : plan->height);
         a.lines = (int32_t)(st.dim == 0 ? plan->height : plan->width);
         a.mode = st.mode;
-        a.power = bases ? 1 : 0;
-        a.log2_base = log2_base[st.weights];
+        a.power = log2_base ? 1 : 0;
+        a.log2_base = log2_base ? log2_base[st.weights] : 0.0f;
         int rc = launch_var_tails(a, st.dim, stream);
         if (rc == RF_OK) rc = mark();
         if (rc == RF_OK) rc = launch_var_carry(a, stream);
         if (rc == RF_OK) rc = mark();
+        a.dst_u8 = s == last && io.out_u8;        // (the tails pass stores no sample)
         if (rc == RF_OK) rc = launch_var_pass2(a, st.dim, stream);
         if (rc == RF_OK) rc = mark();
         if (rc != RF_OK) return rc;
-    }
-    if (ms_out) {
-        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
-        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
     }
     return RF_OK;
 }

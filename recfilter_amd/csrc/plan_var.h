@@ -1,6 +1,7 @@
 // plan_var.h -- the plan behind the rf_var_plan_* entry points: spatially varying first-order scans (plan_var.cpp).
 #pragma once
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -35,6 +36,18 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out);
 // bases == nullptr: `weight_planes` hold weights; else they hold exponents and bases[k] is the base of plane k (the power form)
 int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
                  void *const *out_planes, hipStream_t stream, float *ms_out);
+// The launches of one run of `plan`, nothing checked (run_var_plan and plan_smooth.cpp check first).  The first stage reads `in`
+// (f32, or bytes: in_u8); the stages write `work` (f32) and later stages filter it in place; the final pass of the last stage
+// stores to `out` (f32 -- then out is work -- or bytes: out_u8).  log2_base == nullptr: the plane form.  `mark` is called behind
+// every launch.
+struct VarIo {
+    const void *const *in = nullptr;
+    void *const *work = nullptr, *const *out = nullptr;
+    bool in_u8 = false, out_u8 = false;
+};
+int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
+                      const std::function<int()> &mark);
+int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                       void *dx, void *dy, int32_t device, hipStream_t stream);
 }  // namespace rf

@@ -6,6 +6,8 @@ The scans run in the HIP kernels of kernels_var.hip; torch tensors are device me
            guide image, on the guide's device); `VarPlan.execute` reads them.
   power    `domain_transform_distances` (rf_var_distances, one HIP launch) gives the two exponent planes all iterations share;
            `VarPlan.execute_power` forms w = a_k ** d in the scan kernels.  Nothing but the scans' output is stored.
+  plan     `SmoothPlan` (rf_smooth_plan_*): the power form as one object of the library, which owns the distance planes and
+           sequences every launch; f32 or uint8 images (bytes in, bytes out, no conversion pass).
 """
 from __future__ import annotations
 
@@ -215,8 +217,163 @@ def domain_transform_distances(guide, sigma_s: float, sigma_r: float, stream=Non
     return dx, dy
 
 
+class SmoothPlan:
+    """rf_smooth_plan_*: the domain-transform recursive filter of `planes` image planes of `shape_hw` = (height, width), f32 or
+    uint8 (uint8: input AND output; out = sat8 of the f32 filter on the widened bytes, rounded once, at the final store).
+    guide_planes = 0: the image guides itself; else that many separate guide planes of `guide_dtype`.  A byte guide means that
+    guide divided by 255.  One var_distances launch, then 6 launches per iteration.  One plan owns its distance planes, working
+    planes, tails and carries: order its executes."""
+
+    def __init__(self, shape_hw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
+                 iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, device: int = -1):
+        import torch
+        shape_hw = tuple(int(s) for s in shape_hw)
+        if len(shape_hw) != 2:
+            raise ValueError(f"shape_hw must be (height, width), got {shape_hw}")
+        image_dtype = torch.float32 if image_dtype is None else image_dtype
+        guide_dtype = torch.float32 if guide_dtype is None else guide_dtype
+        for what, dt in (("image", image_dtype), ("guide", guide_dtype)):
+            if dt not in (torch.float32, torch.uint8):
+                raise TypeError(f"{what}_dtype must be torch.float32 or torch.uint8, got {dt}")
+        d = capi.SmoothDesc()
+        d.abi = capi.RF_ABI
+        d.image_u8 = int(image_dtype == torch.uint8)
+        d.height, d.width = shape_hw
+        d.n_planes, d.n_guide = int(planes), int(guide_planes)
+        d.guide_u8 = int(guide_dtype == torch.uint8) if d.n_guide != 0 else 0
+        d.iterations = int(iterations)
+        d.sigma_s, d.sigma_r = float(sigma_s), float(sigma_r)
+        d.device = int(device)
+        d.flags = 0
+        self._desc = d
+        self.shape, self.planes, self.guide_planes, self.iterations = shape_hw, int(planes), int(guide_planes), int(iterations)
+        self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
+        self._h = ctypes.c_void_p()
+        capi.check(capi.lib().rf_smooth_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
+
+    # -- lifetime ---------------------------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            capi.lib().rf_smooth_plan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- queries ----------------------------------------------------------------------------
+    @property
+    def workspace_bytes(self) -> int:
+        return int(capi.lib().rf_smooth_plan_workspace_bytes(self._h))
+
+    @property
+    def num_kernels(self) -> int:
+        return int(capi.lib().rf_smooth_plan_num_kernels(self._h))
+
+    @property
+    def bases(self) -> List[float]:
+        """[a_0 .. a_{K-1}]: the f32 bases the plan runs with"""
+        out = (ctypes.c_float * self.iterations)()
+        capi.check(capi.lib().rf_smooth_plan_bases(self._h, out))
+        return [float(v) for v in out]
+
+    # -- execution --------------------------------------------------------------------------
+    def _pointers(self, tensor, count: int, dtype, what: str) -> ctypes.Array:
+        """the planes of a (C, H, W) or (H, W) device tensor, or of a list of (H, W) tensors; VarPlan._pointers' checks"""
+        if hasattr(tensor, "dim"):
+            tensor = [tensor] if tensor.dim() == 2 else [tensor[c] for c in range(tensor.shape[0])] if tensor.dim() == 3 else None
+            if tensor is None:
+                raise ValueError(f"{what} must be (C, H, W) or (H, W)")
+        if len(tensor) != count:
+            raise ValueError(f"expected {count} {what} planes, got {len(tensor)}")
+        arr = (ctypes.c_void_p * count)()
+        for i, t in enumerate(tensor):
+            if tuple(t.shape) != self.shape:
+                raise ValueError(f"{what} plane {i}: shape {tuple(t.shape)} != plan shape {self.shape}")
+            if t.dtype != dtype:
+                raise TypeError(f"{what} plane {i}: {dtype} planes only, got {t.dtype}")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("planes must be contiguous device tensors")
+            arr[i] = t.data_ptr()
+        return arr
+
+    def _arguments(self, image, guide, out):
+        import torch
+        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
+            # (the library refuses; there are no device tensors to take pointers from)
+            nulls = lambda n: (ctypes.c_void_p * max(n, 1))()      # noqa: E731
+            return nulls(self.planes), nulls(self.guide_planes) if self.guide_planes else None, nulls(self.planes), None, ctypes.c_void_p()
+        if out is None:
+            out = torch.empty_like(image) if hasattr(image, "dim") else [torch.empty_like(t) for t in image]
+        pg = None
+        if guide is not None:
+            if self.guide_planes == 0:
+                raise ValueError("this plan's image guides itself (guide_planes=0): no guide is taken")
+            pg = self._pointers(guide, self.guide_planes, self.guide_dtype, "guide")
+        elif self.guide_planes != 0:
+            raise ValueError(f"this plan takes {self.guide_planes} separate guide planes")
+        return self._pointers(image, self.planes, self.image_dtype, "image"), pg, self._pointers(out, self.planes, self.image_dtype, "output"), out, None
+
+    def execute(self, image, guide=None, out=None, stream=None):
+        """rf_smooth_plan_execute: asynchronous on `stream` (default: torch's current stream).  image, out: (C, H, W) or (H, W)
+        device tensors of the plan's image dtype (or lists of (H, W) planes); out=None allocates it; out may be the image."""
+        pi, pg, po, out, host_stream = self._arguments(image, guide, out)
+        capi.check(capi.lib().rf_smooth_plan_execute(self._h, pi, pg, po, host_stream if host_stream is not None else VarPlan._stream(stream)))
+        return out
+
+    def execute_timed(self, image, guide=None, out=None, stream=None):
+        """rf_smooth_plan_execute_timed: (output, [(kernel name, ms), ...]) measured with HIP events; synchronises the stream."""
+        pi, pg, po, out, host_stream = self._arguments(image, guide, out)
+        n = self.num_kernels
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_smooth_plan_execute_timed(self._h, pi, pg, po,
+                                                           host_stream if host_stream is not None else VarPlan._stream(stream), ms, names, n))
+        return out, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
 _SMOOTH_SCANS = [(0, True, 0), (0, False, 0), (1, True, 1), (1, False, 1)]      # +x -x on weights 0, +y -y on weights 1
 _smooth_plans: Dict[Tuple[int, int, int, int], VarPlan] = {}
+_smooth_plan_objects: Dict[tuple, SmoothPlan] = {}
+
+
+def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations):
+    import torch
+    img = (image if image.dim() == 3 else image.unsqueeze(0))
+    if img.dim() != 3:
+        raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
+    if img.dtype != torch.uint8:
+        img = img.to(torch.float32)
+    img = img.contiguous()
+    g = None
+    if guide is not None:
+        g = guide if guide.dim() == 3 else guide.unsqueeze(0)
+        if g.dim() != 3:
+            raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
+        if g.dtype != torch.uint8:
+            g = g.to(torch.float32)
+        g = g.to(img.device).contiguous()
+        if tuple(g.shape[1:]) != tuple(img.shape[1:]):
+            raise ValueError("guide and image must have the same height and width")
+    C, H, W = (int(s) for s in img.shape)
+    device = img.device.index if img.device.index is not None else torch.cuda.current_device()
+    key = (C, H, W, img.dtype, None if g is None else (int(g.shape[0]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), device)
+    plan = _smooth_plan_objects.get(key)
+    if plan is None:
+        plan = _smooth_plan_objects[key] = SmoothPlan((H, W), planes=C, guide_planes=0 if g is None else int(g.shape[0]), image_dtype=img.dtype,
+                                                      guide_dtype=None if g is None else g.dtype, iterations=iterations, sigma_s=sigma_s,
+                                                      sigma_r=sigma_r, device=device)
+    with torch.cuda.device(img.device):
+        out = plan.execute(img, g)
+    return out if image.dim() == 3 else out[0]
 
 
 def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes"):
@@ -225,10 +382,14 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     guides itself.  One plan per (shape, device), cached; calls on one shape are ordered by the caller (one stream).
     form="planes": the weight planes of `domain_transform_weights`, 2 per iteration, read by `execute`.  form="power": the two
     planes of `domain_transform_distances`, computed once, and `execute_power` with bases [a_k, a_k] per iteration -- no weight
-    plane is stored; the guide may be uint8 (taken as it is: guide / 255)."""
+    plane is stored; the guide may be uint8 (taken as it is: guide / 255).  form="plan": what "power" computes, by a cached
+    SmoothPlan (keyed by shape, dtypes, iterations, sigmas and device) that owns the distance planes; the result has the image's
+    dtype -- a uint8 image gives uint8 (sat8 of the f32 filter on the bytes, the byte image guiding itself as image / 255)."""
     import torch
-    if form not in ("planes", "power"):
-        raise ValueError(f"form must be 'planes' or 'power', got {form!r}")
+    if form not in ("planes", "power", "plan"):
+        raise ValueError(f"form must be 'planes', 'power' or 'plan', got {form!r}")
+    if form == "plan":
+        return _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations)
     img = image if image.dim() == 3 else image.unsqueeze(0)
     if img.dim() != 3:
         raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")

@@ -35,7 +35,8 @@ for f in files:
     o, n = parse(f"{tmp}/old.{f}.txt"), parse(f"{tmp}/new.{f}.txt")
     print(f"== {f}: {len(o)} kernels before, {len(n)} after")
     # a template parameter added at the end of a kernel's list shows in the names of the new tree: match on the old name's arguments
-    key = lambda name: re.sub(r", false>\(", ">(", name).replace("Lb0EEEv", "EEv", 1)
+    # (a trailing type parameter with a default shows as ", float>(")
+    key = lambda name: re.sub(r", (false|float)>\(", ">(", name).replace("Lb0EEEv", "EEv", 1)
     nk = {}
     for name in n:
         nk.setdefault(key(name), name)
