@@ -745,6 +745,7 @@ inline void tap_filter(const std::vector<const void *> &in_planes, void *out, co
  *      RecFilterVarying F(x, y);            // extents; the first dimension is the fastest
  *      F.add_scan(+x, 0); F.add_scan(-x, 0); F.add_scan(+y, 1); F.add_scan(-y, 1);
  *      F.realize({in}, {wx, wy}, {out});    // device pointers; in == out is allowed
+ *      F.gradient({in}, {wx, wy}, {grad_out}, {grad_in}, {grad_wx, grad_wy});      // the adjoint, weight gradients optional
  *  The plan is built on the first realize() and kept; it owns one workspace: order the realizations of one object. */
 class RecFilterVarying {
     std::vector<RecFilterDim> dims;
@@ -784,6 +785,19 @@ public:
         if (rf_var_plan_execute_power(plan, in.data(), exponents.data(), bases.data(), out.data(), stream) != RF_OK)
             throw RecFilterError(rf_last_error_string());
     }
+    /** The adjoint of realize() (rf_var_plan_backward): grad_in = dL/d(in) from grad_out = dL/d(out), and dL/d(weights[k]) into
+     *  grad_weights[k] where that entry is not null.  grad_weights empty: the image gradient alone, and `in` may be empty too.
+     *  grad_in[pl] == grad_out[pl] is allowed.  The same plan as realize(), on its workspace: order the calls. */
+    void gradient(const std::vector<const void *> &in, const std::vector<const void *> &weights, const std::vector<const void *> &grad_out,
+                  const std::vector<void *> &grad_in, const std::vector<void *> &grad_weights = {}, void *stream = nullptr) {
+        if (!in.empty() && in.size() != grad_out.size()) throw RecFilterError("gradient: as many input planes as grad_out planes, or none");
+        if (!grad_weights.empty() && grad_weights.size() != weights.size()) throw RecFilterError("gradient: one grad_weights entry per weight plane (null: no gradient), or none");
+        prepare(grad_out, weights.size(), grad_in);
+        if (rf_var_plan_backward(plan, in.empty() ? nullptr : in.data(), weights.data(), grad_out.data(), grad_in.data(),
+                                 grad_weights.empty() ? nullptr : grad_weights.data(), stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+    /** launches of gradient(): 3 per scan, 7 with weight gradients */
+    int gradient_num_kernels(bool with_weight_gradients) const { return plan ? rf_var_plan_backward_num_kernels(plan, with_weight_gradients ? 1 : 0) : 0; }
 private:
     void prepare(const std::vector<const void *> &in, size_t weight_planes, const std::vector<void *> &out) {
         if (in.empty() || in.size() != out.size()) throw RecFilterError("realize: as many output planes as input planes, at least one");

@@ -485,6 +485,37 @@ int    rf_var_plan_execute_power(rf_var_plan *plan, const void *const *in_planes
 int    rf_var_plan_execute_power_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
                                        const float *bases, void *const *out_planes, void *stream, float *ms_out,
                                        const char **names_out, int capacity);
+/* The adjoint of a plan run by rf_var_plan_execute (the plane form): given grad_out = dL/d(out), grad_in = dL/d(in) and, where
+ * asked for, dL/d(weight plane).  With g the gradient that enters a scan's adjoint, along a line:
+ *     causal scan       lam[i] = g[i] + w~[i+1] lam[i+1]   (anticausal, unit input gain)     dL/dx[i] = (1 - w~[i])   lam[i]
+ *                       dL/dw[i] = lam[i] (y[i-1] - x[i])      i = 1 .. N-1;  element 0: 0
+ *     anticausal scan   mu[i]  = g[i] + w~[i]   mu[i-1]    (causal, unit input gain)         dL/dx[i] = (1 - w~[i+1]) mu[i]
+ *                       dL/dw[i] = mu[i-1] (y[i] - x[i-1])     i = 1 .. N-1;  element 0: 0
+ * The scans' adjoints run in reverse order, always scan by scan (no fused pair).  The gradient of a weight plane is the sum over
+ * the scans that read it and over the image planes (planes in index order, in f32, in a register: no atomics -- two runs of one
+ * call agree bit for bit).
+ * grad_weight_planes = NULL or all entries NULL: 3 launches per scan ("var_adj_tails_x|y", "var_carry", "var_adj_pass2_x|y"); the
+ * first stage reads grad_out, later stages run in place on grad_in; grad_out[pl] == grad_in[pl] is allowed; in_planes may be NULL;
+ * no workspace beyond the plan's.
+ * Otherwise in_planes is needed: the forward is rerun scan by scan ("var_tails_*", "var_carry", "var_pass2_*", 3 per scan) with
+ * every scan's output kept, then per scan in reverse order the adjoint stage, which also stores lam, and one "var_grad_x|y"
+ * launch: 7 launches per scan.  A weight plane whose entry is NULL gets no gradient and its var_grad launches are skipped (the
+ * timed form reports 0 ms for them).  The (n_scans + 1) * n_planes extra planes are allocated by the first call that needs them
+ * and freed with the plan: rf_var_plan_backward_workspace_bytes(plan, 1); rf_var_plan_workspace_bytes does not count them.
+ * rf_var_plan_backward_num_kernels(plan, with_weight_gradients): 3 n_scans, or 7 n_scans.
+ * The plan's one workspace is used: order backward calls with the plan's executes.  Checked in this order, before any HIP call:
+ * null plan / weight_planes / grad_out_planes / grad_in_planes; a weight gradient asked for with in_planes NULL
+ * (RF_ERR_INVALID_ARG); a host-only plan (RF_ERR_HIP); null or not 16-byte aligned planes; a grad_in plane or a gradient plane
+ * that overlaps a weight plane, an input plane, another grad_in or gradient plane, or a grad_out plane -- except grad_in[pl]
+ * being exactly grad_out[pl] (RF_ERR_INVALID_ARG; the message names the planes). */
+int    rf_var_plan_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                            const void *const *grad_out_planes, void *const *grad_in_planes,
+                            void *const *grad_weight_planes /* NULL, or n_weights entries each NULL or a plane */, void *stream);
+int    rf_var_plan_backward_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                                  const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes,
+                                  void *stream, float *ms_out, const char **names_out, int capacity);
+int    rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gradients);
+size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_weight_gradients);
 /* The distance planes of the domain-transform filter from a guide image of n_guide dense planes of width x height:
  *     d_x[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r][c-1]|   (c >= 1;  d_x[r][0] = 1)
  *     d_y[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r-1][c]|   (r >= 1;  d_y[0][c] = 1)

@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "rf_gaussian_box_filter", "rf_box_difference", "rf_tap_filter", "rf_stream_copy", "rf_last_error_string", "rf_version", "rf_device_count",
     "rf_var_plan_create", "rf_var_plan_destroy", "rf_var_plan_workspace_bytes", "rf_var_plan_num_kernels", "rf_var_plan_execute",
     "rf_var_plan_execute_timed", "rf_var_plan_execute_power", "rf_var_plan_execute_power_timed", "rf_var_distances",
+    "rf_var_plan_backward", "rf_var_plan_backward_timed", "rf_var_plan_backward_num_kernels", "rf_var_plan_backward_workspace_bytes",
     "rf_smooth_plan_create", "rf_smooth_plan_destroy", "rf_smooth_plan_workspace_bytes", "rf_smooth_plan_num_kernels",
     "rf_smooth_plan_bases", "rf_smooth_plan_execute", "rf_smooth_plan_execute_timed",
 ]
@@ -193,6 +194,11 @@ def lib() -> ctypes.CDLL:
     L.rf_var_plan_execute_timed.argtypes = [vp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
     L.rf_var_plan_execute_power.argtypes = [vp, vpp, vpp, fp, vpp, vp]
     L.rf_var_plan_execute_power_timed.argtypes = [vp, vpp, vpp, fp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_plan_backward.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, vp]
+    L.rf_var_plan_backward_timed.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_plan_backward_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var_plan_backward_workspace_bytes.argtypes = [vp, ctypes.c_int]
+    L.rf_var_plan_backward_workspace_bytes.restype = ctypes.c_size_t
     L.rf_var_distances.argtypes = [vpp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, vp, vp,
                                    ctypes.c_int32, vp]
     L.rf_smooth_plan_create.argtypes = [ctypes.POINTER(SmoothDesc), vpp]

@@ -603,6 +603,42 @@ int rf_var_plan_execute_power_timed(rf_var_plan *plan, const void *const *in_pla
     });
 }
 
+// the adjoint (run_var_backward)
+static bool wants_weight_gradients(const rf_var_plan *plan, void *const *grad_weight_planes) {
+    if (!plan || !grad_weight_planes) return false;
+    for (int k = 0; k < plan->n_weights; k++)
+        if (grad_weight_planes[k]) return true;
+    return false;
+}
+
+int rf_var_plan_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                         const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, void *stream) {
+    return fenced("rf_var_plan_backward", [&] {
+        return run_var_backward(plan, in_planes, weight_planes, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var_plan_backward_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
+                               const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes,
+                               void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var_plan_backward_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        const std::vector<std::string> &names = plan->backward_names[wants_weight_gradients(plan, grad_weight_planes) ? 1 : 0];
+        if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
+        if (names_out)
+            for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+        return run_var_backward(plan, in_planes, weight_planes, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gradients) {
+    return plan ? (int)plan->backward_names[with_weight_gradients ? 1 : 0].size() : 0;
+}
+
+size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_weight_gradients) {
+    return plan ? plan->backward_workspace_bytes(with_weight_gradients != 0) : 0;
+}
+
 int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                      void *dx, void *dy, int32_t device, void *stream) {
     return fenced("rf_var_distances", [&] {

@@ -35,6 +35,25 @@ struct VarArgs {
     // byte planes (rf_smooth_plan; the pair mode in the power form only): the source of a stage along x, the destination of a final
     // pass along y.  Separate kernel instances, chosen by the launchers; the f32 instances never look at these.
     int32_t src_u8, dst_u8;
+    // adjoint stages (rf_var_plan_backward; single scans, plane form, f32 only): `mode` is the direction of the ADJOINT recurrence
+    // (VAR_ANTICAUSAL: the adjoint of a causal scan), which has unit input gain; the final pass stores (1 - w~) * lam to dst and,
+    // where lam[pl] is not null, the unscaled lam to it.  The other instances never look at these.
+    int32_t adjoint;
+    void *lam[RF_MAX_PLANES];
+};
+
+// The weight gradient of ONE scan (kernels_var.hip, var_grad): lam = that scan's adjoint state, x / y = its saved input and output.
+//   causal      grad[i] = sum_planes lam[i]   * (y[i-1] - x[i])        anticausal  grad[i] = sum_planes lam[i-1] * (y[i] - x[i-1])
+// along `dim`, planes summed in index order in f32; element 0 along the scanned dimension is 0.  accumulate: added to what `grad`
+// holds (a later scan on the same weight plane), else stored.
+struct VarGradArgs {
+    const float *lam[RF_MAX_PLANES];
+    const float *x[RF_MAX_PLANES];
+    const float *y[RF_MAX_PLANES];
+    float *grad;
+    int32_t width, height;          // x fastest; the width is a multiple of 4
+    int32_t n_planes;
+    int32_t accumulate;
 };
 
 // d_x = 1 + scale * sum_ch |g - g one column to the left|, d_y the same with the row above (kernels_var.hip, var_distances)
@@ -50,5 +69,6 @@ int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_carry(const VarArgs &a, hipStream_t stream);
 int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream);
+int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream);
 
 }  // namespace rf

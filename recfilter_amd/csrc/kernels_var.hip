@@ -31,6 +31,16 @@
 // the f32 instances are what they were, register for register.
 //
 // var_distances: the two exponent planes of the domain-transform filter from a guide image, one streaming launch.
+//
+// Adjoint stages (ADJ, rf_var_plan_backward): the adjoint of a causal scan is the ANTICAUSAL recurrence with unit input gain
+//   lam[i] = g[i] + w[i+1] * lam[i+1]        dL/dx[i] = (1 - w[i]) * lam[i]
+// and the adjoint of an anticausal scan the causal one,  mu[i] = g[i] + w[i] * mu[i-1],  dL/dx[i] = (1 - w[i+1]) * mu[i].  The same
+// tiling: the tails are E = the local scan's last value and the P the forward scan of that direction stores, var_carry is
+// unchanged, the final pass reruns the recurrence from the carry and stores the scaled state -- and, where VarArgs names planes
+// for it, the unscaled one.  Single scans, plane form, f32.  A trailing template argument with a default, as the byte planes'.
+//
+// var_grad: the weight gradient of one scan from its adjoint state and its saved input and output, one streaming launch; the
+// planes are summed in a register, in index order (no atomics: a backward call is reproducible bit for bit).
 #include "kernels_var.h"
 
 #include "pixel.h"
@@ -103,6 +113,55 @@ __device__ __forceinline__ void tile_final(float (&x)[T], float (&w)[T + 1], flo
     }
 }
 
+// ---- adjoint stages: MODE is the direction of the adjoint recurrence itself -----------------------------------------------------
+__device__ __forceinline__ float adjoint_step(float w, float x, float prev) { return __builtin_fmaf(w, prev, x); }
+
+// tile-local tails, zero entry: E and the product that carries the entry across the tile (the forward scans' P1 / P2, formed in
+// their order of multiplication)
+template <int MODE>
+__device__ __forceinline__ void tile_tails_adjoint(const float (&x)[T], const float (&w)[T + 1], bool weights_too, float (&out)[kVarComponents]) {
+    out[VAR_E1] = out[VAR_P1] = out[VAR_E2] = out[VAR_G] = out[VAR_P2] = 0.0f;
+    if (weights_too) {
+        float p = MODE == VAR_CAUSAL ? w[0] : 1.0f;
+#pragma unroll
+        for (int i = 1; i < T; i++) p *= w[i];
+        if constexpr (MODE == VAR_CAUSAL) out[VAR_P1] = p;
+        else out[VAR_P2] = p * w[T];
+    }
+    if constexpr (MODE == VAR_CAUSAL) {
+        float prev = 0.0f;
+#pragma unroll
+        for (int i = 0; i < T; i++) prev = adjoint_step(w[i], x[i], prev);
+        out[VAR_E1] = prev;
+    } else {
+        float v = 0.0f;
+#pragma unroll
+        for (int i = T - 1; i >= 0; i--) v = adjoint_step(w[i + 1], x[i], v);
+        out[VAR_E2] = v;
+    }
+}
+
+// x: the gradient that enters, replaced by the adjoint state (lam or mu)
+template <int MODE>
+__device__ __forceinline__ void tile_final_adjoint(float (&x)[T], const float (&w)[T + 1], float c, float d) {
+    if constexpr (MODE == VAR_CAUSAL) {
+        float prev = c;
+#pragma unroll
+        for (int i = 0; i < T; i++) { x[i] = adjoint_step(w[i], x[i], prev); prev = x[i]; }
+    } else {
+        float v = d;
+#pragma unroll
+        for (int i = T - 1; i >= 0; i--) { x[i] = adjoint_step(w[i + 1], x[i], v); v = x[i]; }
+    }
+}
+
+// what the final pass stores for sample i: the state times the input gain of the FORWARD scan (the adjoint of a causal scan
+// runs anticausally and scales by 1 - w[i]; the adjoint of an anticausal scan by 1 - w[i+1])
+template <int MODE>
+__device__ __forceinline__ float adjoint_result(const float (&x)[T], const float (&w)[T + 1], int i) {
+    return (1.0f - w[MODE == VAR_ANTICAUSAL ? i : i + 1]) * x[i];
+}
+
 // samples and weights beyond the line's end, and the weight of element 0, selected away
 __device__ __forceinline__ void mask_tile(float (&x)[T], float (&w)[T + 1], int t0, int n) {
 #pragma unroll
@@ -135,8 +194,9 @@ __device__ __forceinline__ void store_tails(const VarArgs &a, int t, int pl, int
 // ---- along y: lane = column -------------------------------------------------------------------------------------------
 // DST: the samples the final pass stores -- float, or uint8_t (the last pass of a byte image, rf_smooth_plan: sat8 of pixel.h, one
 // byte per lane and row).  Instantiated for the pair mode in the power form only.
-template <int MODE, bool FINAL, bool POWER, typename DST = float>
+template <int MODE, bool FINAL, bool POWER, typename DST = float, bool ADJ = false>
 __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
+    static_assert(!ADJ || (MODE != VAR_PAIR && !POWER), "adjoint stages: single scans in the plane form");
     const int col = blockIdx.x * 64 + threadIdx.x;
     if (col >= a.width) return;                       // (no barrier below: lanes are independent)
     const int t = blockIdx.y, pl = blockIdx.z, t0 = t * T;
@@ -150,7 +210,7 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
         w[i] = (a.weights + r * pitch)[col];
     }
     w[T] = 0.0f;
-    if constexpr (MODE != VAR_CAUSAL) w[T] = (a.weights + min(t0 + T, a.height - 1) * pitch)[col];
+    if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w[T] = (a.weights + min(t0 + T, a.height - 1) * pitch)[col];
     if constexpr (POWER) {
 #pragma unroll
         for (int i = 0; i < T; i++) w[i] = power_weight(w[i], a.log2_base);
@@ -162,7 +222,24 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
         if constexpr (MODE != VAR_CAUSAL) d = a.carry[carry_index(a, t, 1, pl, col)];
     }
     mask_tile(x, w, t0, a.height);
-    if constexpr (FINAL) {
+    if constexpr (ADJ) {
+        if constexpr (FINAL) {
+            tile_final_adjoint<MODE>(x, w, c, d);
+            float *dst = static_cast<float *>(a.dst[pl]), *lam = static_cast<float *>(a.lam[pl]);
+#pragma unroll
+            for (int i = 0; i < T; i++)
+                if (t0 + i < a.height) (dst + (t0 + i) * pitch)[col] = adjoint_result<MODE>(x, w, i);
+            if (lam) {
+#pragma unroll
+                for (int i = 0; i < T; i++)
+                    if (t0 + i < a.height) (lam + (t0 + i) * pitch)[col] = x[i];
+            }
+        } else {
+            float out[kVarComponents];
+            tile_tails_adjoint<MODE>(x, w, pl == 0, out);
+            store_tails<MODE>(a, t, pl, col, out);
+        }
+    } else if constexpr (FINAL) {
         tile_final<MODE>(x, w, c, d);
         DST *dst = static_cast<DST *>(a.dst[pl]);
 #pragma unroll
@@ -224,8 +301,9 @@ __device__ __forceinline__ void transpose_in(const float (&v)[T], float *lds, fl
 
 // SRC: the samples of the source planes -- float, or uint8_t (the first stage of a byte image, rf_smooth_plan; the destination
 // stays f32).  Instantiated for the pair mode in the power form only.
-template <int MODE, bool FINAL, bool POWER, typename SRC = float>
+template <int MODE, bool FINAL, bool POWER, typename SRC = float, bool ADJ = false>
 __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
+    static_assert(!ADJ || (MODE != VAR_PAIR && !POWER), "adjoint stages: single scans in the plane form");
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
     const int t = blockIdx.x, pl = blockIdx.z, t0 = t * T, r0 = blockIdx.y * 64;
@@ -235,7 +313,7 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     request_tile(src, a, r0, t0, vx);
     request_tile(a.weights, a, r0, t0, vw);
     float w_next = 0.0f;                             // w[t1], the next tile's first weight
-    if constexpr (MODE != VAR_CAUSAL) w_next = a.weights[(int64_t)min(row, a.height - 1) * a.width + min(t0 + T, a.width - 1)];
+    if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w_next = a.weights[(int64_t)min(row, a.height - 1) * a.width + min(t0 + T, a.width - 1)];
     float c = 0.0f, d = 0.0f;
     if constexpr (FINAL) {
         const int line = min(row, a.height - 1);
@@ -255,7 +333,37 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     }
     mask_tile(x, w, t0, a.width);
     __builtin_amdgcn_sched_barrier(0);      // (the scans stay behind the transposition: they would hold its registers)
-    if constexpr (FINAL) {
+    if constexpr (ADJ) {
+        if constexpr (FINAL) {
+            tile_final_adjoint<MODE>(x, w, c, d);
+            // the way back twice: the scaled state to dst, then (where the plan wants it) the state itself to lam
+            float *planes[2] = {static_cast<float *>(a.dst[pl]), static_cast<float *>(a.lam[pl])};
+#pragma unroll
+            for (int which = 0; which < 2; which++) {
+                if (which == 1 && !planes[1]) break;      // (uniform)
+                if (which == 1) __syncthreads();
+#pragma unroll
+                for (int k = 0; k < T / 4; k++) {
+                    const float4 q = which == 0 ? make_float4(adjoint_result<MODE>(x, w, 4 * k), adjoint_result<MODE>(x, w, 4 * k + 1),
+                                                              adjoint_result<MODE>(x, w, 4 * k + 2), adjoint_result<MODE>(x, w, 4 * k + 3))
+                                                : make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
+                    *reinterpret_cast<float4 *>(lds + lane * LDS_PITCH + k * 4) = q;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < T / 4; k++) {
+                    const int flat = k * 64 + lane;
+                    const int r = r0 + (flat >> 4), col = t0 + (flat & 15) * 4;
+                    const float4 q = *reinterpret_cast<const float4 *>(lds + (flat >> 4) * LDS_PITCH + (flat & 15) * 4);
+                    if (r < a.height && col < a.width) *reinterpret_cast<float4 *>(planes[which] + (int64_t)r * a.width + col) = q;
+                }
+            }
+        } else {
+            float out[kVarComponents];
+            tile_tails_adjoint<MODE>(x, w, pl == 0, out);
+            if (row < a.height) store_tails<MODE>(a, t, pl, row, out);
+        }
+    } else if constexpr (FINAL) {
         tile_final<MODE>(x, w, c, d);
 #pragma unroll
         for (int k = 0; k < T / 4; k++)
@@ -375,6 +483,62 @@ __global__ void __launch_bounds__(256) var_distances_kernel(VarDistArgs a) {
     }
 }
 
+// ---- var_grad: lane = 4 adjacent columns of one row, as var_distances ---------------------------------------------------------
+// The sample before the chunk along the scanned dimension comes from a clamped address (dim 0: the element to the left of the
+// chunk, column 0: the chunk's own first element; dim 1: the chunk of the row above, row 0: the row itself); element 0 of the
+// gradient is 0 by a select, whatever was read for it.
+template <int DIM>
+__device__ __forceinline__ void load_previous(const float *p, int64_t own_at, int64_t before_at, const float (&own)[4], float (&prev)[4]) {
+    if constexpr (DIM == 0) {
+        prev[0] = p[before_at];
+#pragma unroll
+        for (int j = 1; j < 4; j++) prev[j] = own[j - 1];
+    } else {
+        load_chunk(p, before_at, prev);
+    }
+}
+
+template <int DIM, bool CAUSAL>
+__global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
+    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (c >= a.width) return;
+    for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
+        const int64_t own_at = (int64_t)r * a.width + c;
+        const int64_t before_at = DIM == 0 ? own_at - (c > 0 ? 1 : 0) : (int64_t)max(r - 1, 0) * a.width + c;
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int pl = 0; pl < a.n_planes; pl++) {
+            float lam[4], x[4], y[4], before[4], term[4];
+            if constexpr (CAUSAL) {              // lam[i] * (y[i-1] - x[i])
+                load_chunk(a.lam[pl], own_at, lam);
+                load_chunk(a.x[pl], own_at, x);
+                if constexpr (DIM == 0) load_chunk(a.y[pl], own_at, y);
+                load_previous<DIM>(a.y[pl], own_at, before_at, y, before);
+#pragma unroll
+                for (int j = 0; j < 4; j++) term[j] = lam[j] * (before[j] - x[j]);
+            } else {                             // lam[i-1] * (y[i] - x[i-1])
+                load_chunk(a.y[pl], own_at, y);
+                if constexpr (DIM == 0) { load_chunk(a.lam[pl], own_at, lam); load_chunk(a.x[pl], own_at, x); }
+                load_previous<DIM>(a.lam[pl], own_at, before_at, lam, before);
+                float x_before[4];
+                load_previous<DIM>(a.x[pl], own_at, before_at, x, x_before);
+#pragma unroll
+                for (int j = 0; j < 4; j++) term[j] = before[j] * (y[j] - x_before[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) s[j] = pl == 0 ? term[j] : s[j] + term[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[j] = (DIM == 0 ? c + j == 0 : r == 0) ? 0.0f : s[j];
+        if (a.accumulate) {
+            float old[4];
+            load_chunk(a.grad, own_at, old);
+#pragma unroll
+            for (int j = 0; j < 4; j++) s[j] = old[j] + s[j];
+        }
+        *reinterpret_cast<float4 *>(a.grad + own_at) = make_float4(s[0], s[1], s[2], s[3]);
+    }
+}
+
 int launched(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
@@ -387,6 +551,19 @@ int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
     const dim3 block(64);
     const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)a.n_planes)
                                : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)a.n_planes);
+    if (a.adjoint) {
+        const char *what = FINAL ? (dim == 0 ? "var_adj_pass2_x" : "var_adj_pass2_y") : (dim == 0 ? "var_adj_tails_x" : "var_adj_tails_y");
+        if (a.src_u8 || a.dst_u8 || a.power || a.mode == VAR_PAIR) {
+            set_error("%s: adjoint stages are single scans on f32 planes in the plane form", what);
+            return RF_ERR_UNSUPPORTED;
+        }
+#define RF_VAR_LAUNCH_ADJOINT(MODE)                                                                                      \
+        if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL, false, float, true>), grid, block, 0, stream, a);    \
+        else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL, false, float, true>), grid, block, 0, stream, a)
+        if (a.mode == VAR_CAUSAL) { RF_VAR_LAUNCH_ADJOINT(VAR_CAUSAL); } else { RF_VAR_LAUNCH_ADJOINT(VAR_ANTICAUSAL); }
+#undef RF_VAR_LAUNCH_ADJOINT
+        return launched(what);
+    }
     // byte planes (rf_smooth_plan): the instances that exist, and nothing else -- there is no conversion to fall back on
     if (a.src_u8 || a.dst_u8) {
         const char *what = FINAL ? (dim == 0 ? "var_pass2_x" : "var_pass2_y") : (dim == 0 ? "var_tails_x" : "var_tails_y");
@@ -434,6 +611,18 @@ int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream
     if (guide_u8) hipLaunchKernelGGL((var_distances_kernel<uint8_t>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var_distances_kernel<float>), grid, block, 0, stream, a);
     return launched("var_distances");
+}
+
+int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
+    if (dim == 0) {
+        if (causal) hipLaunchKernelGGL((var_grad_kernel<0, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var_grad_kernel<0, false>), grid, block, 0, stream, a);
+    } else {
+        if (causal) hipLaunchKernelGGL((var_grad_kernel<1, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var_grad_kernel<1, false>), grid, block, 0, stream, a);
+    }
+    return launched(dim == 0 ? "var_grad_x" : "var_grad_y");
 }
 
 }  // namespace rf

@@ -8,14 +8,23 @@
 // planes in place.  The power form (rf_var_plan_execute_power) runs the same stages on exponent planes: a stage carries
 // log2 of its plane's base and launches the kernels' POWER instances.  run_var_plan checks the arguments and owns the timing
 // events; launch_var_stages issues the launches of one run, and is what the smoothing plan (plan_smooth.cpp) calls per iteration.
+//
+// run_var_backward is the adjoint of a plan (rf_var_plan_backward): per scan in reverse order an adjoint stage -- a unit-gain scan
+// in the opposite direction, tails / var_carry / final pass like a forward stage, always scan by scan.  The image gradient needs
+// nothing else.  Weight gradients need every scan's input and output: the forward is rerun scan by scan into plan-owned planes
+// (n_scans * n_planes, allocated by the first call that needs them), every adjoint stage also stores its unscaled state to
+// n_planes more, and one var_grad launch per scan forms the gradient from the three -- stored by the first launch that touches a
+// weight plane, added by the later ones; the host knows which is which, so there are no atomics and no zero-fill.
 #include "plan_var.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <memory>
 
 rf_var_plan::~rf_var_plan() {
     if (tails) (void)hipFree(tails);
+    if (grad_planes) (void)hipFree(grad_planes);
     if (carry) (void)hipFree(carry);
 }
 
@@ -107,6 +116,22 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
         }
         s = e;
     }
+    // the adjoint's launch lists: [1] reruns the forward scan by scan first, and has one var_grad behind every adjoint stage
+    plan->scans.assign(desc->scans, desc->scans + desc->n_scans);
+    for (const rf_var_scan_desc &sc : plan->scans) {
+        const char *axis = sc.dim == 0 ? "x" : "y";
+        plan->backward_names[1].push_back(std::string("var_tails_") + axis);
+        plan->backward_names[1].push_back("var_carry");
+        plan->backward_names[1].push_back(std::string("var_pass2_") + axis);
+    }
+    for (int with = 0; with < 2; with++)
+        for (int q = desc->n_scans - 1; q >= 0; q--) {
+            const char *axis = desc->scans[q].dim == 0 ? "x" : "y";
+            plan->backward_names[with].push_back(std::string("var_adj_tails_") + axis);
+            plan->backward_names[with].push_back("var_carry");
+            plan->backward_names[with].push_back(std::string("var_adj_pass2_") + axis);
+            if (with) plan->backward_names[with].push_back(std::string("var_grad_") + axis);
+        }
     // tiles x lines of the dimension that needs more: x scans have `height` lines, y scans `width`
     int64_t slots = 0;
     if (used[0]) slots = std::max(slots, tiles_of(plan->width) * plan->height);
@@ -223,6 +248,189 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
         if (rc == RF_OK) rc = launch_var_pass2(a, st.dim, stream);
         if (rc == RF_OK) rc = mark();
         if (rc != RF_OK) return rc;
+    }
+    return RF_OK;
+}
+
+namespace {
+
+// one single-scan stage's arguments, planes aside
+VarArgs scan_args(const rf_var_plan *plan, const rf_var_scan_desc &sc, const void *const *weight_planes, int mode) {
+    VarArgs a{};
+    a.weights = (const float *)weight_planes[sc.weights];
+    a.tails = plan->tails;
+    a.carry = plan->carry;
+    a.width = (int32_t)plan->width;
+    a.height = (int32_t)plan->height;
+    a.n_planes = plan->n_planes;
+    a.tiles = (int32_t)tiles_of(sc.dim == 0 ? plan->width : plan->height);
+    a.lines = (int32_t)(sc.dim == 0 ? plan->height : plan->width);
+    a.mode = mode;
+    return a;
+}
+
+bool overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+
+}  // namespace
+
+int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const void *const *grad_out_planes,
+                     void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream, float *ms_out) {
+    // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
+    if (!plan || !weight_planes || !grad_out_planes || !grad_in_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    bool with_weights = false;
+    if (grad_weight_planes)
+        for (int k = 0; k < plan->n_weights; k++) with_weights = with_weights || grad_weight_planes[k] != nullptr;
+    if (with_weights && !in_planes) { set_error("weight gradients need the input planes (in_planes is null)"); return RF_ERR_INVALID_ARG; }
+    if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
+    const int P = plan->n_planes, K = plan->n_weights;
+    const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
+    for (int pl = 0; pl < P; pl++) {
+        if (!grad_out_planes[pl] || !grad_in_planes[pl] || (with_weights && !in_planes[pl])) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
+        if ((((uintptr_t)grad_out_planes[pl] | (uintptr_t)grad_in_planes[pl] | (uintptr_t)(with_weights ? in_planes[pl] : nullptr)) & 15u) != 0) {
+            set_error("plane %d: the varying scans need 16-byte aligned image pointers", pl);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    for (int k = 0; k < K; k++) {
+        if (!weight_planes[k]) { set_error("weight plane %d: null pointer", k); return RF_ERR_INVALID_ARG; }
+        if ((((uintptr_t)weight_planes[k] | (uintptr_t)(with_weights ? grad_weight_planes[k] : nullptr)) & 15u) != 0) {
+            set_error("weight plane %d: the varying scans need 16-byte aligned pointers (the plane and its gradient)", k);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    // what is written (grad_in planes, weight-gradient planes) against everything that is read and everything else that is written
+    const int n_written = P + (with_weights ? K : 0);
+    auto written = [&](int i) -> const void * { return i < P ? grad_in_planes[i] : grad_weight_planes[i - P]; };
+    auto written_name = [&](int i, char *buf, size_t n) {
+        if (i < P) std::snprintf(buf, n, "grad_in plane %d", i);
+        else std::snprintf(buf, n, "gradient of weight plane %d", i - P);
+    };
+    for (int i = 0; i < n_written; i++) {
+        const void *o = written(i);
+        if (!o) continue;
+        char name[64];
+        written_name(i, name, sizeof name);
+        for (int k = 0; k < K; k++)
+            if (overlap(o, plane_bytes, weight_planes[k], plane_bytes)) {
+                set_error("%s overlaps weight plane %d: every stage reads the weights after it has begun to store", name, k);
+                return RF_ERR_INVALID_ARG;
+            }
+        if (in_planes)
+            for (int pl = 0; pl < P; pl++)
+                if (in_planes[pl] && overlap(o, plane_bytes, in_planes[pl], plane_bytes)) {
+                    set_error("%s overlaps input plane %d", name, pl);
+                    return RF_ERR_INVALID_ARG;
+                }
+        for (int j = i + 1; j < n_written; j++)
+            if (written(j) && overlap(o, plane_bytes, written(j), plane_bytes)) {
+                char other[64];
+                written_name(j, other, sizeof other);
+                set_error("%s overlaps %s", name, other);
+                return RF_ERR_INVALID_ARG;
+            }
+        for (int pl = 0; pl < P; pl++) {
+            if (i == pl && o == grad_out_planes[pl]) continue;      // in place: a plane and its own gradient, exactly
+            if (overlap(o, plane_bytes, grad_out_planes[pl], plane_bytes)) {
+                set_error("%s overlaps grad_out plane %d (only grad_in plane %d may, and then exactly)", name, pl, pl);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    }
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    const int S = (int)plan->scans.size();
+    if (with_weights && !plan->grad_planes) {
+        if (hipMalloc((void **)&plan->grad_planes, plan->backward_workspace_bytes(true)) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->grad_planes = nullptr;
+            set_error("hipMalloc of %zu bytes for the weight gradients' planes failed", plan->backward_workspace_bytes(true));
+            return RF_ERR_NOMEM;
+        }
+    }
+    // events are destroyed on every return path
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } events;
+    const size_t n_kernels = plan->backward_names[with_weights ? 1 : 0].size();
+    if (ms_out) {
+        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
+        for (size_t i = 0; i < n_kernels + 1; i++) {
+            hipEvent_t e;
+            RF_HIP_CHECK(hipEventCreate(&e));
+            events.ev.push_back(e);
+        }
+        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
+    }
+    size_t launch = 0;
+    auto mark = [&]() -> int {
+        launch++;
+        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
+        return RF_OK;
+    };
+    const size_t plane_floats = plane_bytes / sizeof(float);
+    auto saved = [&](int scan, int pl) { return plan->grad_planes + ((size_t)scan * P + pl) * plane_floats; };      // scan == S: the state
+    int rc = RF_OK;
+    if (with_weights) {
+        // the forward again, scan by scan, every output kept: scan q reads scan q-1's planes
+        for (int q = 0; q < S && rc == RF_OK; q++) {
+            const rf_var_scan_desc &sc = plan->scans[q];
+            VarArgs a = scan_args(plan, sc, weight_planes, sc.causal != 0 ? VAR_CAUSAL : VAR_ANTICAUSAL);
+            for (int pl = 0; pl < P; pl++) {
+                a.src[pl] = q == 0 ? in_planes[pl] : saved(q - 1, pl);
+                a.dst[pl] = saved(q, pl);
+            }
+            rc = launch_var_tails(a, sc.dim, stream);
+            if (rc == RF_OK) rc = mark();
+            if (rc == RF_OK) rc = launch_var_carry(a, stream);
+            if (rc == RF_OK) rc = mark();
+            if (rc == RF_OK) rc = launch_var_pass2(a, sc.dim, stream);
+            if (rc == RF_OK) rc = mark();
+        }
+    }
+    bool touched[RF_VAR_MAX_SCANS] = {};
+    std::vector<size_t> skipped;      // slots of var_grad launches that were not issued
+    for (int q = S - 1; q >= 0 && rc == RF_OK; q--) {
+        const rf_var_scan_desc &sc = plan->scans[q];
+        float *const grad = with_weights ? (float *)grad_weight_planes[sc.weights] : nullptr;
+        // the adjoint of a causal scan runs anticausally, and the other way round
+        VarArgs a = scan_args(plan, sc, weight_planes, sc.causal != 0 ? VAR_ANTICAUSAL : VAR_CAUSAL);
+        a.adjoint = 1;
+        for (int pl = 0; pl < P; pl++) {
+            a.src[pl] = q == S - 1 ? grad_out_planes[pl] : grad_in_planes[pl];
+            a.dst[pl] = grad_in_planes[pl];
+            a.lam[pl] = grad ? saved(S, pl) : nullptr;
+        }
+        rc = launch_var_tails(a, sc.dim, stream);
+        if (rc == RF_OK) rc = mark();
+        if (rc == RF_OK) rc = launch_var_carry(a, stream);
+        if (rc == RF_OK) rc = mark();
+        if (rc == RF_OK) rc = launch_var_pass2(a, sc.dim, stream);
+        if (rc == RF_OK) rc = mark();
+        if (rc != RF_OK || !with_weights) continue;
+        if (grad) {                                   // (a weight plane without a gradient: no launch, its slot reports 0 ms)
+            VarGradArgs g{};
+            for (int pl = 0; pl < P; pl++) {
+                g.lam[pl] = saved(S, pl);
+                g.x[pl] = q == 0 ? (const float *)in_planes[pl] : saved(q - 1, pl);
+                g.y[pl] = saved(q, pl);
+            }
+            g.grad = grad;
+            g.width = (int32_t)plan->width;
+            g.height = (int32_t)plan->height;
+            g.n_planes = P;
+            g.accumulate = touched[sc.weights] ? 1 : 0;
+            touched[sc.weights] = true;
+            rc = launch_var_grad(g, sc.dim, sc.causal != 0, stream);
+        } else {
+            skipped.push_back(launch);
+        }
+        if (rc == RF_OK) rc = mark();
+    }
+    if (rc != RF_OK) return rc;
+    if (ms_out) {
+        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
+        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
+        for (size_t i : skipped) ms_out[i] = 0.0f;
     }
     return RF_OK;
 }

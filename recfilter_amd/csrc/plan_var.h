@@ -27,6 +27,15 @@ struct rf_var_plan {
     float *tails = nullptr, *carry = nullptr;
     size_t tails_bytes = 0, carry_bytes = 0;
     size_t workspace_bytes() const { return tails_bytes + carry_bytes; }
+    // rf_var_plan_backward: the scans as described (adjoint stages are single scans), the launch names without ([0]) and with
+    // ([1]) weight gradients, and the planes the weight gradients need -- every scan's output (n_scans * n_planes) and one
+    // scan's adjoint state (n_planes) -- allocated by the first call that asks for a weight gradient
+    std::vector<rf_var_scan_desc> scans;
+    std::vector<std::string> backward_names[2];
+    float *grad_planes = nullptr;
+    size_t backward_workspace_bytes(bool with_weight_gradients) const {
+        return with_weight_gradients ? (scans.size() + 1) * (size_t)n_planes * (size_t)(width * height) * sizeof(float) : 0;
+    }
     ~rf_var_plan();
 };
 
@@ -47,6 +56,10 @@ struct VarIo {
 };
 int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
                       const std::function<int()> &mark);
+// The adjoint of the plan (rf_var_plan_backward in recfilter_amd.h).  grad_weight_planes: nullptr, or n_weights entries, each nullptr
+// (no gradient for that plane) or a plane.  ms_out as in run_var_plan, one slot per name of backward_names[with weight gradients].
+int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const void *const *grad_out_planes,
+                     void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream, float *ms_out);
 int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                       void *dx, void *dy, int32_t device, hipStream_t stream);

@@ -8,6 +8,10 @@ The scans run in the HIP kernels of kernels_var.hip; torch tensors are device me
            `VarPlan.execute_power` forms w = a_k ** d in the scan kernels.  Nothing but the scans' output is stored.
   plan     `SmoothPlan` (rf_smooth_plan_*): the power form as one object of the library, which owns the distance planes and
            sequences every launch; f32 or uint8 images (bytes in, bytes out, no conversion pass).
+
+The plane form is differentiable: `VarPlan.backward` (rf_var_plan_backward) is the adjoint of `VarPlan.execute` in the same HIP
+kernels' adjoint instances -- gradients with respect to the image planes and, where asked for, the weight planes -- and
+`VarPlan.apply` / `var_scan` put it behind torch.autograd.
 """
 from __future__ import annotations
 
@@ -48,6 +52,7 @@ class VarPlan:
         d.flags = 0
         self._desc = d
         self.shape, self.planes, self.n_weights = shape, int(planes), int(n_weights)
+        self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
         self._h = ctypes.c_void_p()
         capi.check(L.rf_var_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
 
@@ -154,6 +159,130 @@ class VarPlan:
                                                               host_stream if host_stream is not None else self._stream(stream),
                                                               ms, names, n))
         return outs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    # -- the adjoint ------------------------------------------------------------------------
+    def backward_num_kernels(self, with_weights: bool = False) -> int:
+        """rf_var_plan_backward_num_kernels: 3 launches per scan, 7 with weight gradients"""
+        return int(capi.lib().rf_var_plan_backward_num_kernels(self._h, int(bool(with_weights))))
+
+    def backward_workspace_bytes(self, with_weights: bool = False) -> int:
+        """rf_var_plan_backward_workspace_bytes: what the first backward call with weight gradients allocates, beyond
+        workspace_bytes: (scans + 1) * planes f32 planes; 0 without weight gradients"""
+        return int(capi.lib().rf_var_plan_backward_workspace_bytes(self._h, int(bool(with_weights))))
+
+    def _backward_arguments(self, ins, weights, grad_outs, grad_ins, grad_weights):
+        import torch
+        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
+            # (the library refuses; there are no device tensors to take pointers from)
+            nulls = lambda n: (ctypes.c_void_p * n)()      # noqa: E731
+            return (nulls(self.planes) if ins is not None else None, nulls(self.n_weights), nulls(self.planes), nulls(self.planes),
+                    nulls(self.n_weights) if grad_weights is not None else None, None, None, ctypes.c_void_p())
+        if grad_ins is None:
+            grad_ins = [torch.empty_like(t) for t in grad_outs]
+        pgw = None
+        if grad_weights is not None:
+            if len(grad_weights) != self.n_weights:
+                raise ValueError(f"expected {self.n_weights} entries in grad_weights (None: no gradient for that plane), got {len(grad_weights)}")
+            pgw = (ctypes.c_void_p * self.n_weights)()
+            for k, t in enumerate(grad_weights):
+                if t is not None:
+                    pgw[k] = self._pointers([t], 1, f"gradient of weight plane {k}:")[0]
+        return (self._pointers(ins, self.planes, "input") if ins is not None else None, self._pointers(weights, self.n_weights, "weight"),
+                self._pointers(grad_outs, self.planes, "grad_out"), self._pointers(grad_ins, self.planes, "grad_in"), pgw,
+                grad_ins, grad_weights, None)
+
+    def backward(self, ins, weights, grad_outs, grad_ins=None, grad_weights=None, stream=None):
+        """rf_var_plan_backward, the adjoint of execute: (grad_ins, grad_weights) from grad_outs = dL/d(outs).  grad_ins=None
+        allocates them; grad_ins may be grad_outs themselves (in place).  grad_weights: None (no weight gradient; `ins` may then
+        be None too), or a list of n_weights entries, each a plane to be WRITTEN or None for a plane that needs no gradient; a
+        plane no scan reads is left as it is.  Asynchronous on `stream` (default: torch's current stream); uses the plan's
+        workspace like an execute."""
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_weights, host_stream = self._backward_arguments(ins, weights, grad_outs, grad_ins, grad_weights)
+        capi.check(capi.lib().rf_var_plan_backward(self._h, pin, pw, pgo, pgi, pgw,
+                                                   host_stream if host_stream is not None else self._stream(stream)))
+        return grad_ins, grad_weights
+
+    def backward_timed(self, ins, weights, grad_outs, grad_ins=None, grad_weights=None, stream=None):
+        """rf_var_plan_backward_timed: (grad_ins, grad_weights, [(kernel name, ms), ...]); synchronises the stream.  The var_grad
+        launch of a weight plane without a gradient is skipped and reports 0 ms."""
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_weights, host_stream = self._backward_arguments(ins, weights, grad_outs, grad_ins, grad_weights)
+        n = self.backward_num_kernels(grad_weights is not None and any(t is not None for t in grad_weights))
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_var_plan_backward_timed(self._h, pin, pw, pgo, pgi, pgw,
+                                                         host_stream if host_stream is not None else self._stream(stream), ms, names, n))
+        return grad_ins, grad_weights, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    def apply(self, ins, weights):
+        """execute, out of place, as a differentiable torch operation: a tuple of `planes` output planes whose values are bit for
+        bit execute's.  Backward is `backward` -- the image gradient always, the gradient of a weight plane where that plane
+        requires one.  Only the inputs and the weights are saved; no double backward."""
+        if len(ins) != self.planes or len(weights) != self.n_weights:
+            raise ValueError(f"expected {self.planes} input planes and {self.n_weights} weight planes, got {len(ins)} and {len(weights)}")
+        return _var_scan_function().apply(self, *ins, *weights)
+
+
+_function = None
+
+
+def _var_scan_function():
+    """the torch.autograd.Function behind VarPlan.apply (torch is imported when it is first needed)"""
+    global _function
+    if _function is not None:
+        return _function
+    import torch
+
+    def plane(t):      # what the library takes: contiguous, 16-byte aligned
+        t = t.contiguous()
+        return t.clone() if t.data_ptr() % 16 else t
+
+    class VarScanFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, *tensors):
+            ins = [plane(t) for t in tensors[:plan.planes]]
+            weights = [plane(t) for t in tensors[plan.planes:]]
+            ctx.plan = plan
+            ctx.save_for_backward(*ins, *weights)
+            return tuple(plan.execute(ins, weights))
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, *grad_outs):
+            plan = ctx.plan
+            saved = ctx.saved_tensors
+            ins, weights = list(saved[:plan.planes]), list(saved[plan.planes:])
+            need_in = ctx.needs_input_grad[1:1 + plan.planes]
+            need_w = ctx.needs_input_grad[1 + plan.planes:]
+            read = {k for _, _, k in plan.scans}
+            grad_weights = None
+            if any(n and k in read for k, n in enumerate(need_w)):
+                grad_weights = [torch.empty_like(w) if n and k in read else None for k, (w, n) in enumerate(zip(weights, need_w))]
+            with torch.cuda.device(ins[0].device):
+                grad_ins, grad_weights = plan.backward(ins, weights, [plane(g) for g in grad_outs], None, grad_weights)
+            grad_weights = grad_weights or [None] * plan.n_weights
+            # (a weight plane that no scan reads has a gradient of zero)
+            grad_weights = [torch.zeros_like(w) if n and k not in read else g for k, (w, n, g) in enumerate(zip(weights, need_w, grad_weights))]
+            return (None, *[g if n else None for g, n in zip(grad_ins, need_in)], *grad_weights)
+
+    _function = VarScanFunction
+    return _function
+
+
+_scan_plans: Dict[tuple, VarPlan] = {}
+
+
+def var_scan(ins, weights, scans):
+    """`VarPlan.apply` without the plan: `scans` [(dim, causal, weight index), ...] on the device planes `ins` with the weight
+    planes `weights`, differentiable with respect to both.  Plans are cached by shape, scans, plane counts and device; calls that
+    share a plan are ordered by the caller (one stream)."""
+    import torch
+    ins, weights = list(ins), list(weights)
+    device = ins[0].device.index if ins[0].device.index is not None else torch.cuda.current_device()
+    key = (tuple(ins[0].shape), tuple((int(d), bool(c), int(k)) for d, c, k in scans), len(ins), len(weights), device)
+    plan = _scan_plans.get(key)
+    if plan is None:
+        plan = _scan_plans[key] = VarPlan(key[0], key[1], planes=len(ins), n_weights=len(weights), device=device)
+    return plan.apply(ins, weights)
 
 
 # ---- the domain-transform recursive filter ----------------------------------------------------------------------------------
@@ -384,7 +513,11 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     planes of `domain_transform_distances`, computed once, and `execute_power` with bases [a_k, a_k] per iteration -- no weight
     plane is stored; the guide may be uint8 (taken as it is: guide / 255).  form="plan": what "power" computes, by a cached
     SmoothPlan (keyed by shape, dtypes, iterations, sigmas and device) that owns the distance planes; the result has the image's
-    dtype -- a uint8 image gives uint8 (sat8 of the f32 filter on the bytes, the byte image guiding itself as image / 255)."""
+    dtype -- a uint8 image gives uint8 (sat8 of the f32 filter on the bytes, the byte image guiding itself as image / 255).
+    Gradients: with form="planes", torch's grad mode on and an image or a guide that requires a gradient, the scans go through
+    `var_scan` (same values, bit for bit) and the result is differentiable with respect to both -- the guide through the torch
+    expression `domain_transform_weights` is.  form="power" and form="plan" are not differentiable: their result carries no
+    grad_fn whatever the inputs require."""
     import torch
     if form not in ("planes", "power", "plan"):
         raise ValueError(f"form must be 'planes', 'power' or 'plan', got {form!r}")
@@ -394,6 +527,16 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     if img.dim() != 3:
         raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
     img = img.to(torch.float32).contiguous()
+    if form == "planes" and torch.is_grad_enabled() and (image.requires_grad or (guide is not None and guide.requires_grad)):
+        weights = domain_transform_weights(image if guide is None else guide, sigma_s, sigma_r, iterations)
+        if tuple(weights[0][0].shape) != tuple(img.shape[1:]):
+            raise ValueError("guide and image must have the same height and width")
+        planes = [img[c] for c in range(img.shape[0])]
+        with torch.cuda.device(img.device):
+            for wx, wy in weights:
+                planes = var_scan(planes, [wx.to(img.device), wy.to(img.device)], _SMOOTH_SCANS)
+        out = torch.stack(list(planes))
+        return out if image.dim() == 3 else out[0]
     if form == "power":
         g = img if guide is None else guide
         if g.dtype != torch.uint8:
