@@ -796,7 +796,21 @@ public:
         if (rf_var_plan_backward(plan, in.empty() ? nullptr : in.data(), weights.data(), grad_out.data(), grad_in.data(),
                                  grad_weights.empty() ? nullptr : grad_weights.data(), stream) != RF_OK) throw RecFilterError(rf_last_error_string());
     }
-    /** launches of gradient(): 3 per scan, 7 with weight gradients */
+    /** The adjoint of realize_power() (rf_var_plan_backward_power): as gradient(), with the exponent planes and their bases in the
+     *  place of the weights; grad_exponents[k], where not null, receives dL/d(exponents[k]) = (w ln bases[k]) dL/dw. */
+    void gradient_power(const std::vector<const void *> &in, const std::vector<const void *> &exponents, const std::vector<float> &bases,
+                        const std::vector<const void *> &grad_out, const std::vector<void *> &grad_in,
+                        const std::vector<void *> &grad_exponents = {}, void *stream = nullptr) {
+        if (!in.empty() && in.size() != grad_out.size()) throw RecFilterError("gradient_power: as many input planes as grad_out planes, or none");
+        if (!grad_exponents.empty() && grad_exponents.size() != exponents.size())
+            throw RecFilterError("gradient_power: one grad_exponents entry per exponent plane (null: no gradient), or none");
+        prepare(grad_out, exponents.size(), grad_in);
+        if ((int)bases.size() < n_weights) throw RecFilterError("gradient_power: one base per exponent plane");
+        if (rf_var_plan_backward_power(plan, in.empty() ? nullptr : in.data(), exponents.data(), bases.data(), grad_out.data(), grad_in.data(),
+                                       grad_exponents.empty() ? nullptr : grad_exponents.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** launches of gradient() and gradient_power(): 3 per scan, 7 with weight gradients */
     int gradient_num_kernels(bool with_weight_gradients) const { return plan ? rf_var_plan_backward_num_kernels(plan, with_weight_gradients ? 1 : 0) : 0; }
 private:
     void prepare(const std::vector<const void *> &in, size_t weight_planes, const std::vector<void *> &out) {
@@ -831,12 +845,23 @@ inline void domain_transform_distances(const std::vector<const void *> &guide_pl
                          stream) != RF_OK) throw RecFilterError(rf_last_error_string());
 }
 
+/** The adjoint of domain_transform_distances for f32 guide planes (rf_var_distances_backward): the guide's gradient from those of
+ *  d_x and d_y, stored to grad_guide_planes or (accumulate) added to what they hold.  One launch on `stream`. */
+inline void domain_transform_distances_gradient(const std::vector<const void *> &guide_planes, int64_t width, int64_t height, float scale,
+                                                const void *grad_dx, const void *grad_dy, const std::vector<void *> &grad_guide_planes,
+                                                bool accumulate = false, void *stream = nullptr) {
+    if (guide_planes.size() != grad_guide_planes.size()) throw RecFilterError("domain_transform_distances_gradient: one gradient plane per guide plane");
+    if (rf_var_distances_backward(guide_planes.data(), (int32_t)guide_planes.size(), width, height, scale, grad_dx, grad_dy,
+                                  grad_guide_planes.data(), accumulate ? 1 : 0, -1, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+}
+
 /** Edge-aware smoothing as one object (recfilter_amd.h, rf_smooth_plan_*): the domain-transform recursive filter of `planes`
  *  dense device planes of width x height, f32 or uint8 (bytes in AND out: sat8 of the f32 filter on the widened bytes, rounded
  *  once, at the final store).  guide_planes = 0: the image guides itself; else that many separate guide planes, f32 or uint8 (a
  *  byte guide means that guide divided by 255).  The library owns the distance planes and sequences 1 + 6 K launches.
  *      RecFilterSmooth F(width, height, 3, 0, false, true, 3, 60.0, 0.4);      // an RGB byte image guiding itself
  *      F.realize({r, g, b}, {}, {r, g, b});                                      // device pointers; in == out is allowed
+ *  f32 images are differentiable: F.gradient(image, guide, grad_out, grad_image, grad_guide, edges) (rf_smooth_plan_backward).
  *  The plan is built on first use and kept; it owns one workspace: order the realizations of one object. */
 class RecFilterSmooth {
     rf_smooth_desc desc{};
@@ -881,4 +906,21 @@ public:
         return b;
     }
     int num_kernels() { prepare(); return rf_smooth_plan_num_kernels(plan); }
+    /** The adjoint of realize() for f32 images (rf_smooth_plan_backward): grad_image = dL/d(image) from grad_out = dL/d(out).
+     *  edges = false holds the distances constant (grad_guide empty; `image` may be empty unless the image guides itself).
+     *  edges = true differentiates through them: with separate f32 guide planes grad_guide receives the guide's gradient; where
+     *  the image guides itself grad_guide stays empty and that gradient is added into grad_image.  grad_image[pl] == grad_out[pl]
+     *  is allowed.  On the plan's workspace: order the calls. */
+    void gradient(const std::vector<const void *> &image, const std::vector<const void *> &guide, const std::vector<const void *> &grad_out,
+                  const std::vector<void *> &grad_image, const std::vector<void *> &grad_guide = {}, bool edges = false, void *stream = nullptr) {
+        prepare();
+        if ((!image.empty() && (int)image.size() != desc.n_planes) || (int)grad_out.size() != desc.n_planes ||
+            (int)grad_image.size() != desc.n_planes || (int)guide.size() != desc.n_guide || (!grad_guide.empty() && grad_guide.size() != guide.size()))
+            throw RecFilterError("gradient: as many image, gradient and guide planes as the filter was built for");
+        if (rf_smooth_plan_backward(plan, image.empty() ? nullptr : image.data(), guide.empty() ? nullptr : guide.data(), grad_out.data(),
+                                    grad_image.data(), grad_guide.empty() ? nullptr : grad_guide.data(), edges ? 1 : 0, stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** launches of gradient(): 1 + 12 K, or 34 K - 4 with edges */
+    int gradient_num_kernels(bool edges) { prepare(); return rf_smooth_plan_backward_num_kernels(plan, edges ? 1 : 0); }
 };

@@ -514,6 +514,26 @@ int    rf_var_plan_backward(rf_var_plan *plan, const void *const *in_planes, con
 int    rf_var_plan_backward_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
                                   const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes,
                                   void *stream, float *ms_out, const char **names_out, int capacity);
+/* The adjoint of a plan run by rf_var_plan_execute_power (the power form).  As rf_var_plan_backward, with exponent_planes and bases
+ * in the place of weight_planes and grad_exponent_planes in the place of grad_weight_planes.  A scan uses
+ *     w[i] = exp2f(d[i] * l_k),   l_k = (float)log2((double)bases[k])
+ * formed in the kernels exactly as rf_var_plan_execute_power forms it; the image gradient is the plane form's adjoint on those
+ * weights, and the gradient of an exponent plane is
+ *     dL/dd[i] = (w[i] * c_k) * dL/dw[i],   c_k = (float)log((double)bases[k]),
+ * dL/dw the quantity rf_var_plan_backward forms and w recomputed from d by the same hardware exp2.  d is never a factor: d = +inf
+ * gives w = 0 and a gradient of exactly 0, d = 0 gives c_k * dL/dw.  Element 0 along the scanned dimension is 0 by a select (a NaN
+ * exponent there reaches nothing).  Launch lists, names, workspace, rf_var_plan_backward_num_kernels and
+ * rf_var_plan_backward_workspace_bytes are those of rf_var_plan_backward; one plan runs either form, call by call; the first
+ * var_grad launch that touches a gradient plane stores, later ones add: no atomics, bit-reproducible.  Checked in the order of
+ * rf_var_plan_backward, with the base check of rf_var_plan_execute_power (each base finite and inside (0, 1), RF_ERR_INVALID_ARG,
+ * the message names the plane) directly before the host-only check. */
+int    rf_var_plan_backward_power(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                  const float *bases /* n_weights */, const void *const *grad_out_planes, void *const *grad_in_planes,
+                                  void *const *grad_exponent_planes /* NULL, or n_weights entries each NULL or a plane */, void *stream);
+int    rf_var_plan_backward_power_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                        const float *bases, const void *const *grad_out_planes, void *const *grad_in_planes,
+                                        void *const *grad_exponent_planes, void *stream, float *ms_out, const char **names_out,
+                                        int capacity);
 int    rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gradients);
 size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_weight_gradients);
 /* The distance planes of the domain-transform filter from a guide image of n_guide dense planes of width x height:
@@ -527,6 +547,18 @@ size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_we
  * guide plane (RF_ERR_INVALID_ARG). */
 int    rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height,
                         float scale, void *dx, void *dy, int32_t device, void *stream);
+/* The adjoint of rf_var_distances for f32 guide planes: from grad_dx = dL/d(d_x) and grad_dy = dL/d(d_y), per channel, in f32 with
+ * the terms in this order,
+ *     gg[ch][r][c] = scale * (  sx(r,c) * gdx[r][c] - sx(r,c+1) * gdx[r][c+1] + sy(r,c) * gdy[r][c] - sy(r+1,c) * gdy[r+1][c] )
+ *     sx(r,c) = sgn(g[r][c] - g[r][c-1]) for 1 <= c < W, else 0;   sy likewise along rows;   sgn(0) = 0
+ * (a constant guide gets a gradient of exactly 0).  accumulate = 0: stored to grad_guide_planes; 1: added to what they hold.  One
+ * launch ("var_distances_grad"), a gather: no atomics, two runs agree bit for bit.  There is no entry point for byte guides.
+ * Decided before any HIP call: the refusals of rf_var_distances (null pointers include grad_guide_planes and its entries); then
+ * accumulate other than 0 or 1, planes not 16-byte aligned, a gradient plane that overlaps grad_dx, grad_dy, a guide plane or
+ * another gradient plane (RF_ERR_INVALID_ARG). */
+int    rf_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale,
+                                 const void *grad_dx, const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate,
+                                 int32_t device, void *stream);
 
 /* ---- edge-aware smoothing as one plan ------------------------------------------------------------------------------------- */
 /* The domain-transform recursive filter (Gastal & Oliveira 2011) of an image of n_planes dense planes, f32 or uint8, that share
@@ -581,6 +613,37 @@ int    rf_smooth_plan_execute(rf_smooth_plan *plan, const void *const *image_pla
 /* per-kernel milliseconds and names (valid for the life of the plan); synchronises the stream */
 int    rf_smooth_plan_execute_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
                                     void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity);
+/* The adjoint of rf_smooth_plan_execute for f32 images (a uint8-image plan: RF_ERR_UNSUPPORTED): grad_image = dL/d(image) from
+ * grad_out = dL/d(out) and, with edges = 1, the gradient through the distances as well.
+ * edges = 0 (distances held constant): "var_distances", then for k = K-1 .. 0 the adjoint stages of -y +y -x +x in the power form
+ * with the bases {a_k, a_k} -- the launches of rf_var_plan_backward_power without exponent gradients, 1 + 12 K in all.  The first
+ * stage reads grad_out, the rest run in place on grad_image; grad_out[pl] == grad_image[pl] is allowed; image_planes is needed only
+ * where the image guides itself; a uint8 guide is allowed; grad_guide_planes must be NULL; no workspace beyond the plan's.  The
+ * result is, bit for bit, that of K calls of rf_var_plan_backward_power in reverse order.
+ * edges = 1: "var_distances"; the forward of iterations 0 .. K-2 (the six launches of an execute each), every output kept; for
+ * k = K-1 .. 0 the launches of rf_var_plan_backward_power WITH both exponent gradients on iteration k's input (28), whose
+ * var_grad launches store into two plan-owned planes the first time each is touched and add afterwards; one "var_distances_grad"
+ * with the plan's scale.  34 K - 4 launches.  n_guide > 0: grad_guide_planes (n_guide planes) is required and stored, and
+ * grad_image is bit for bit that of edges = 0.  n_guide = 0: grad_guide_planes must be NULL and the last launch ADDS the guide's
+ * gradient into grad_image_planes.  A uint8 guide is refused (RF_ERR_UNSUPPORTED).  Workspace, allocated by the first call that
+ * needs it and freed with the plan: 2 + (K - 1 + 5) * n_planes f32 planes = rf_smooth_plan_backward_workspace_bytes(plan, 1)
+ * (0 for edges = 0; rf_smooth_plan_workspace_bytes does not count it).
+ * No atomics: two runs of one call agree bit for bit.  A plan keeps no state across calls; order executes and backward calls of
+ * one plan on one stream.  Checked in this order, before any HIP call: null plan / grad_out_planes / grad_image_planes; edges other
+ * than 0 or 1 (RF_ERR_INVALID_ARG); a uint8-image plan (RF_ERR_UNSUPPORTED); guide_planes that does not match n_guide; image_planes
+ * NULL where it is needed (RF_ERR_INVALID_ARG); edges = 1 with a uint8 guide (RF_ERR_UNSUPPORTED); grad_guide_planes NULL where it
+ * is required or given where it must be NULL (RF_ERR_INVALID_ARG); a host-only plan (RF_ERR_HIP); null or misaligned planes; a
+ * grad_image or guide-gradient plane that overlaps a guide plane, an image plane, another written plane, or a grad_out plane --
+ * except grad_image[pl] being exactly grad_out[pl] (RF_ERR_INVALID_ARG; the message names the planes). */
+int    rf_smooth_plan_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                               const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes,
+                               int32_t edges, void *stream);
+int    rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                     const void *const *grad_out_planes, void *const *grad_image_planes,
+                                     void *const *grad_guide_planes, int32_t edges, void *stream, float *ms_out,
+                                     const char **names_out, int capacity);
+int    rf_smooth_plan_backward_num_kernels(const rf_smooth_plan *plan, int edges);
+size_t rf_smooth_plan_backward_workspace_bytes(const rf_smooth_plan *plan, int edges);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

@@ -70,6 +70,9 @@ EXPORTED_SYMBOLS = [
     "rf_var_plan_backward", "rf_var_plan_backward_timed", "rf_var_plan_backward_num_kernels", "rf_var_plan_backward_workspace_bytes",
     "rf_smooth_plan_create", "rf_smooth_plan_destroy", "rf_smooth_plan_workspace_bytes", "rf_smooth_plan_num_kernels",
     "rf_smooth_plan_bases", "rf_smooth_plan_execute", "rf_smooth_plan_execute_timed",
+    "rf_var_plan_backward_power", "rf_var_plan_backward_power_timed", "rf_var_distances_backward",
+    "rf_smooth_plan_backward", "rf_smooth_plan_backward_timed", "rf_smooth_plan_backward_num_kernels",
+    "rf_smooth_plan_backward_workspace_bytes",
 ]
 
 
@@ -209,6 +212,16 @@ def lib() -> ctypes.CDLL:
     L.rf_smooth_plan_bases.argtypes = [vp, fp]
     L.rf_smooth_plan_execute.argtypes = [vp, vpp, vpp, vpp, vp]
     L.rf_smooth_plan_execute_timed.argtypes = [vp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_plan_backward_power.argtypes = [vp, vpp, vpp, fp, vpp, vpp, vpp, vp]
+    L.rf_var_plan_backward_power_timed.argtypes = [vp, vpp, vpp, fp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_distances_backward.argtypes = [vpp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, vp, vp, vpp,
+                                            ctypes.c_int32, ctypes.c_int32, vp]
+    L.rf_smooth_plan_backward.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, ctypes.c_int32, vp]
+    L.rf_smooth_plan_backward_timed.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, ctypes.c_int32, vp, fp, ctypes.POINTER(ctypes.c_char_p),
+                                                ctypes.c_int]
+    L.rf_smooth_plan_backward_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_smooth_plan_backward_workspace_bytes.argtypes = [vp, ctypes.c_int]
+    L.rf_smooth_plan_backward_workspace_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

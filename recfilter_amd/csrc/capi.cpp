@@ -614,7 +614,7 @@ static bool wants_weight_gradients(const rf_var_plan *plan, void *const *grad_we
 int rf_var_plan_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes,
                          const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, void *stream) {
     return fenced("rf_var_plan_backward", [&] {
-        return run_var_backward(plan, in_planes, weight_planes, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, nullptr);
+        return run_var_backward(plan, in_planes, weight_planes, nullptr, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, nullptr);
     });
 }
 
@@ -627,7 +627,29 @@ int rf_var_plan_backward_timed(rf_var_plan *plan, const void *const *in_planes, 
         if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
         if (names_out)
             for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
-        return run_var_backward(plan, in_planes, weight_planes, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, ms_out);
+        return run_var_backward(plan, in_planes, weight_planes, nullptr, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var_plan_backward_power(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes, const float *bases,
+                               const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_exponent_planes,
+                               void *stream) {
+    return fenced("rf_var_plan_backward_power", [&] {
+        if (!bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        return run_var_backward(plan, in_planes, exponent_planes, bases, grad_out_planes, grad_in_planes, grad_exponent_planes, (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var_plan_backward_power_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes, const float *bases,
+                                     const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_exponent_planes,
+                                     void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var_plan_backward_power_timed", [&] {
+        if (!plan || !bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        const std::vector<std::string> &names = plan->backward_names[wants_weight_gradients(plan, grad_exponent_planes) ? 1 : 0];
+        if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
+        if (names_out)
+            for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+        return run_var_backward(plan, in_planes, exponent_planes, bases, grad_out_planes, grad_in_planes, grad_exponent_planes, (hipStream_t)stream, ms_out);
     });
 }
 
@@ -643,6 +665,14 @@ int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t g
                      void *dx, void *dy, int32_t device, void *stream) {
     return fenced("rf_var_distances", [&] {
         return run_var_distances(guide_planes, n_guide, guide_u8, width, height, scale, dx, dy, device, (hipStream_t)stream);
+    });
+}
+
+int rf_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
+                              const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, void *stream) {
+    return fenced("rf_var_distances_backward", [&] {
+        return run_var_distances_backward(guide_planes, n_guide, width, height, scale, grad_dx, grad_dy, grad_guide_planes, accumulate, device,
+                                          (hipStream_t)stream);
     });
 }
 
@@ -684,6 +714,36 @@ int rf_smooth_plan_execute_timed(rf_smooth_plan *plan, const void *const *image_
             for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
         return run_smooth_plan(plan, image_planes, guide_planes, out_planes, (hipStream_t)stream, ms_out);
     });
+}
+
+int rf_smooth_plan_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                            const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes, int32_t edges,
+                            void *stream) {
+    return fenced("rf_smooth_plan_backward", [&] {
+        return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                  const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes,
+                                  int32_t edges, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_smooth_plan_backward_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return (int)RF_ERR_INVALID_ARG; }
+        const std::vector<std::string> &names = plan->backward_names[edges];
+        if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
+        if (names_out)
+            for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+        return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_smooth_plan_backward_num_kernels(const rf_smooth_plan *plan, int edges) {
+    return plan ? (int)plan->backward_names[edges ? 1 : 0].size() : 0;
+}
+
+size_t rf_smooth_plan_backward_workspace_bytes(const rf_smooth_plan *plan, int edges) {
+    return plan ? plan->backward_workspace_bytes(edges != 0) : 0;
 }
 
 const char *rf_last_error_string(void) { return g_last_error.c_str(); }

@@ -35,7 +35,7 @@ struct VarArgs {
     // byte planes (rf_smooth_plan; the pair mode in the power form only): the source of a stage along x, the destination of a final
     // pass along y.  Separate kernel instances, chosen by the launchers; the f32 instances never look at these.
     int32_t src_u8, dst_u8;
-    // adjoint stages (rf_var_plan_backward; single scans, plane form, f32 only): `mode` is the direction of the ADJOINT recurrence
+    // adjoint stages (rf_var_plan_backward, rf_var_plan_backward_power; single scans, f32 only): `mode` is the direction of the ADJOINT recurrence
     // (VAR_ANTICAUSAL: the adjoint of a causal scan), which has unit input gain; the final pass stores (1 - w~) * lam to dst and,
     // where lam[pl] is not null, the unscaled lam to it.  The other instances never look at these.
     int32_t adjoint;
@@ -54,6 +54,10 @@ struct VarGradArgs {
     int32_t width, height;          // x fastest; the width is a multiple of 4
     int32_t n_planes;
     int32_t accumulate;
+    // the gradient of an EXPONENT plane (rf_var_plan_backward_power): not null -> the sum above times w * ln_base,
+    // w = exp2(exponents[i] * log2_base) as the scans form it
+    const float *exponents;
+    float log2_base, ln_base;
 };
 
 // d_x = 1 + scale * sum_ch |g - g one column to the left|, d_y the same with the row above (kernels_var.hip, var_distances)
@@ -65,10 +69,25 @@ struct VarDistArgs {
     float scale;
 };
 
+// The adjoint of var_distances (kernels_var.hip, var_distances_grad), f32 guides:
+//   grad_guide[ch][r][c] = scale * (sx(r,c) gdx[r][c] - sx(r,c+1) gdx[r][c+1] + sy(r,c) gdy[r][c] - sy(r+1,c) gdy[r+1][c])
+// sx / sy: the sign of the guide's difference to the left / above (0 for a difference of 0 and outside the plane).  accumulate:
+// added to what the planes hold, else stored.
+struct VarDistGradArgs {
+    const float *guide[RF_MAX_PLANES];
+    float *grad_guide[RF_MAX_PLANES];
+    const float *gdx, *gdy;
+    int32_t width, height;          // x fastest; the width is a multiple of 4
+    int32_t n_guide;
+    int32_t accumulate;
+    float scale;
+};
+
 int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_carry(const VarArgs &a, hipStream_t stream);
 int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream);
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream);
+int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream);
 
 }  // namespace rf

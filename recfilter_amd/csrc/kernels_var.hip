@@ -37,10 +37,17 @@
 // and the adjoint of an anticausal scan the causal one,  mu[i] = g[i] + w[i] * mu[i-1],  dL/dx[i] = (1 - w[i+1]) * mu[i].  The same
 // tiling: the tails are E = the local scan's last value and the P the forward scan of that direction stores, var_carry is
 // unchanged, the final pass reruns the recurrence from the carry and stores the scaled state -- and, where VarArgs names planes
-// for it, the unscaled one.  Single scans, plane form, f32.  A trailing template argument with a default, as the byte planes'.
+// for it, the unscaled one.  Single scans, f32.  A trailing template argument with a default, as the byte planes'.  With POWER
+// (rf_var_plan_backward_power) the exponents become weights where the forward instances convert them: the adjoint recurrences see
+// weights as before.
 //
 // var_grad: the weight gradient of one scan from its adjoint state and its saved input and output, one streaming launch; the
-// planes are summed in a register, in index order (no atomics: a backward call is reproducible bit for bit).
+// planes are summed in a register, in index order (no atomics: a backward call is reproducible bit for bit).  Its POWER instances
+// give the gradient of an EXPONENT plane: d/dd exp2(d l) = w ln(base), so the register sum is multiplied by w * ln_base, w formed
+// from d as the scans form it -- never by d itself (d = +inf: w = 0, a gradient of exactly 0).
+//
+// var_distances_grad (rf_var_distances_backward): the adjoint of var_distances, a gather -- a guide sample collects from the (at
+// most) four differences it takes part in, with the sign of each; one streaming launch, no atomics.
 #include "kernels_var.h"
 
 #include "pixel.h"
@@ -196,7 +203,7 @@ __device__ __forceinline__ void store_tails(const VarArgs &a, int t, int pl, int
 // byte per lane and row).  Instantiated for the pair mode in the power form only.
 template <int MODE, bool FINAL, bool POWER, typename DST = float, bool ADJ = false>
 __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
-    static_assert(!ADJ || (MODE != VAR_PAIR && !POWER), "adjoint stages: single scans in the plane form");
+    static_assert(!ADJ || MODE != VAR_PAIR, "adjoint stages: single scans");
     const int col = blockIdx.x * 64 + threadIdx.x;
     if (col >= a.width) return;                       // (no barrier below: lanes are independent)
     const int t = blockIdx.y, pl = blockIdx.z, t0 = t * T;
@@ -214,7 +221,7 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
     if constexpr (POWER) {
 #pragma unroll
         for (int i = 0; i < T; i++) w[i] = power_weight(w[i], a.log2_base);
-        if constexpr (MODE != VAR_CAUSAL) w[T] = power_weight(w[T], a.log2_base);
+        if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w[T] = power_weight(w[T], a.log2_base);
     }
     float c = 0.0f, d = 0.0f;
     if constexpr (FINAL) {
@@ -303,7 +310,7 @@ __device__ __forceinline__ void transpose_in(const float (&v)[T], float *lds, fl
 // stays f32).  Instantiated for the pair mode in the power form only.
 template <int MODE, bool FINAL, bool POWER, typename SRC = float, bool ADJ = false>
 __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
-    static_assert(!ADJ || (MODE != VAR_PAIR && !POWER), "adjoint stages: single scans in the plane form");
+    static_assert(!ADJ || MODE != VAR_PAIR, "adjoint stages: single scans");
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
     const int t = blockIdx.x, pl = blockIdx.z, t0 = t * T, r0 = blockIdx.y * 64;
@@ -329,7 +336,7 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     if constexpr (POWER) {
 #pragma unroll
         for (int i = 0; i < T; i++) w[i] = power_weight(w[i], a.log2_base);
-        if constexpr (MODE != VAR_CAUSAL) w[T] = power_weight(w[T], a.log2_base);
+        if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w[T] = power_weight(w[T], a.log2_base);
     }
     mask_tile(x, w, t0, a.width);
     __builtin_amdgcn_sched_barrier(0);      // (the scans stay behind the transposition: they would hold its registers)
@@ -498,7 +505,7 @@ __device__ __forceinline__ void load_previous(const float *p, int64_t own_at, in
     }
 }
 
-template <int DIM, bool CAUSAL>
+template <int DIM, bool CAUSAL, bool POWER = false>
 __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
     const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (c >= a.width) return;
@@ -527,6 +534,12 @@ __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; j++) s[j] = pl == 0 ? term[j] : s[j] + term[j];
         }
+        if constexpr (POWER) {                   // dL/dd = (w * ln base) * dL/dw, w as the scans form it
+            float d[4];
+            load_chunk(a.exponents, own_at, d);
+#pragma unroll
+            for (int j = 0; j < 4; j++) s[j] = (power_weight(d[j], a.log2_base) * a.ln_base) * s[j] + 0.0f;      // (w = 0: +0, not -0)
+        }
 #pragma unroll
         for (int j = 0; j < 4; j++) s[j] = (DIM == 0 ? c + j == 0 : r == 0) ? 0.0f : s[j];
         if (a.accumulate) {
@@ -536,6 +549,60 @@ __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
             for (int j = 0; j < 4; j++) s[j] = old[j] + s[j];
         }
         *reinterpret_cast<float4 *>(a.grad + own_at) = make_float4(s[0], s[1], s[2], s[3]);
+    }
+}
+
+// ---- var_distances_grad: lane = 4 adjacent columns of one row, as var_distances ---------------------------------------------------
+// the sign of a difference applied to the gradient that difference received: a select, sgn(0) = 0 (what the derivative of |.| is
+// taken to be), so no product of a sign with a gradient is ever formed
+__device__ __forceinline__ float signed_by(float difference, float g) { return difference > 0.0f ? g : (difference < 0.0f ? -g : 0.0f); }
+
+// A guide sample takes part in the difference to its left (+), the one to its right (-), the one above (+) and the one below (-).
+// The neighbours come from clamped addresses (column 0 / W-1: the chunk's own end element; row 0 / H-1: the row itself) and the
+// terms they feed are selected away at the borders.  Rows beyond gridDim.y are taken in a stride loop.
+__global__ void __launch_bounds__(256) var_distances_grad_kernel(VarDistGradArgs a) {
+    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (c >= a.width) return;
+    const bool has_right = c + 4 < a.width;
+    for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
+        const int64_t own_at = (int64_t)r * a.width + c, up_at = (int64_t)max(r - 1, 0) * a.width + c;
+        const int64_t down_at = (int64_t)min(r + 1, a.height - 1) * a.width + c;
+        const int64_t left_at = own_at - (c > 0 ? 1 : 0), right_at = own_at + (has_right ? 4 : 3);
+        const bool has_down = r + 1 < a.height;
+        float gx_own[4], gx[5], gy[4], gy_down[4];      // gx[4]: the gradient of the difference to the right of the chunk
+        load_chunk(a.gdx, own_at, gx_own);
+#pragma unroll
+        for (int j = 0; j < 4; j++) gx[j] = gx_own[j];
+        gx[4] = a.gdx[right_at];
+        load_chunk(a.gdy, own_at, gy);
+        load_chunk(a.gdy, down_at, gy_down);
+        for (int ch = 0; ch < a.n_guide; ch++) {
+            const float *g = a.guide[ch];
+            float chunk[4], own[6], up[4], down[4], out[4];      // own[0]: the element to the left, own[5]: the one to the right
+            load_chunk(g, own_at, chunk);
+#pragma unroll
+            for (int j = 0; j < 4; j++) own[j + 1] = chunk[j];
+            own[0] = g[left_at];
+            own[5] = g[right_at];
+            load_chunk(g, up_at, up);
+            load_chunk(g, down_at, down);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float from_left = c + j > 0 ? signed_by(own[j + 1] - own[j], gx[j]) : 0.0f;
+                const float from_right = (j < 3 || has_right) ? signed_by(own[j + 2] - own[j + 1], gx[j + 1]) : 0.0f;
+                const float from_up = r > 0 ? signed_by(own[j + 1] - up[j], gy[j]) : 0.0f;
+                const float from_down = has_down ? signed_by(down[j] - own[j + 1], gy_down[j]) : 0.0f;
+                out[j] = a.scale * (((from_left - from_right) + from_up) - from_down);
+            }
+            float *dst = a.grad_guide[ch];
+            if (a.accumulate) {
+                float old[4];
+                load_chunk(dst, own_at, old);
+#pragma unroll
+                for (int j = 0; j < 4; j++) out[j] = old[j] + out[j];
+            }
+            *reinterpret_cast<float4 *>(dst + own_at) = make_float4(out[0], out[1], out[2], out[3]);
+        }
     }
 }
 
@@ -553,15 +620,18 @@ int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
                                : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)a.n_planes);
     if (a.adjoint) {
         const char *what = FINAL ? (dim == 0 ? "var_adj_pass2_x" : "var_adj_pass2_y") : (dim == 0 ? "var_adj_tails_x" : "var_adj_tails_y");
-        if (a.src_u8 || a.dst_u8 || a.power || a.mode == VAR_PAIR) {
-            set_error("%s: adjoint stages are single scans on f32 planes in the plane form", what);
+        if (a.src_u8 || a.dst_u8 || a.mode == VAR_PAIR) {
+            set_error("%s: adjoint stages are single scans on f32 planes", what);
             return RF_ERR_UNSUPPORTED;
         }
+#define RF_VAR_LAUNCH_ADJOINT_FORM(MODE, POWER)                                                                          \
+        if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL, POWER, float, true>), grid, block, 0, stream, a);    \
+        else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL, POWER, float, true>), grid, block, 0, stream, a)
 #define RF_VAR_LAUNCH_ADJOINT(MODE)                                                                                      \
-        if (dim == 0) hipLaunchKernelGGL((var_x_kernel<MODE, FINAL, false, float, true>), grid, block, 0, stream, a);    \
-        else hipLaunchKernelGGL((var_y_kernel<MODE, FINAL, false, float, true>), grid, block, 0, stream, a)
+        if (a.power) { RF_VAR_LAUNCH_ADJOINT_FORM(MODE, true); } else { RF_VAR_LAUNCH_ADJOINT_FORM(MODE, false); }
         if (a.mode == VAR_CAUSAL) { RF_VAR_LAUNCH_ADJOINT(VAR_CAUSAL); } else { RF_VAR_LAUNCH_ADJOINT(VAR_ANTICAUSAL); }
 #undef RF_VAR_LAUNCH_ADJOINT
+#undef RF_VAR_LAUNCH_ADJOINT_FORM
         return launched(what);
     }
     // byte planes (rf_smooth_plan): the instances that exist, and nothing else -- there is no conversion to fall back on
@@ -615,14 +685,23 @@ int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream
 
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream) {
     const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
-    if (dim == 0) {
-        if (causal) hipLaunchKernelGGL((var_grad_kernel<0, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((var_grad_kernel<0, false>), grid, block, 0, stream, a);
-    } else {
-        if (causal) hipLaunchKernelGGL((var_grad_kernel<1, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((var_grad_kernel<1, false>), grid, block, 0, stream, a);
+#define RF_VAR_LAUNCH_GRAD(POWER)                                                                                   \
+    if (dim == 0) {                                                                                                 \
+        if (causal) hipLaunchKernelGGL((var_grad_kernel<0, true, POWER>), grid, block, 0, stream, a);               \
+        else hipLaunchKernelGGL((var_grad_kernel<0, false, POWER>), grid, block, 0, stream, a);                     \
+    } else {                                                                                                        \
+        if (causal) hipLaunchKernelGGL((var_grad_kernel<1, true, POWER>), grid, block, 0, stream, a);               \
+        else hipLaunchKernelGGL((var_grad_kernel<1, false, POWER>), grid, block, 0, stream, a);                     \
     }
+    if (a.exponents) { RF_VAR_LAUNCH_GRAD(true) } else { RF_VAR_LAUNCH_GRAD(false) }
+#undef RF_VAR_LAUNCH_GRAD
     return launched(dim == 0 ? "var_grad_x" : "var_grad_y");
+}
+
+int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
+    hipLaunchKernelGGL(var_distances_grad_kernel, grid, block, 0, stream, a);
+    return launched("var_distances_grad");
 }
 
 }  // namespace rf

@@ -6,12 +6,20 @@
 // Byte images (the storage contract of RF_IO_U8): the first stage reads the caller's bytes into f32 working planes the plan
 // owns, everything between runs in place on those, and the final pass of the last stage stores sat8 (pixel.h) of its f32
 // result to the caller's bytes.  No conversion launch, and nothing between two iterations is rounded.
+//
+// run_smooth_backward is the adjoint for f32 images.  With the distances held constant it is var_distances and, per iteration in
+// reverse order, the inner plan's power-form adjoint without exponent gradients: the launches of rf_var_plan_backward_power.  To
+// differentiate through the distances it first reruns iterations 0 .. K-2 into checkpoint planes (the fused pair stages), then
+// per iteration in reverse order the inner plan's adjoint WITH both exponent gradients on that iteration's input -- the first
+// stores into gd_x, gd_y, the later ones add -- and one var_distances_grad launch takes gd_x, gd_y to the guide.
 #include "plan_smooth.h"
 
 #include <cmath>
+#include <cstdio>
 
 rf_smooth_plan::~rf_smooth_plan() {
     if (planes) (void)hipFree(planes);
+    if (grad_planes) (void)hipFree(grad_planes);
 }
 
 namespace rf {
@@ -48,6 +56,7 @@ int validate(const rf_smooth_desc *d) {
 }
 
 bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
+bool overlap(const void *a, const void *b, size_t n) { return overlap((uintptr_t)a, n, (uintptr_t)b, n); }
 
 }  // namespace
 
@@ -111,6 +120,17 @@ int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out) {
     plan->names.push_back("var_distances");
     for (int k = 0; k < K; k++)
         for (const std::string &n : inner->names) plan->names.push_back(n);
+    // the adjoint's launch lists
+    for (int edges = 0; edges < 2; edges++) {
+        std::vector<std::string> &names = plan->backward_names[edges];
+        names.push_back("var_distances");
+        if (edges)
+            for (int k = 0; k + 1 < K; k++)
+                for (const std::string &n : inner->names) names.push_back(n);
+        for (int k = 0; k < K; k++)
+            for (const std::string &n : inner->backward_names[edges]) names.push_back(n);
+        if (edges) names.push_back("var_distances_grad");
+    }
     *out = plan.release();
     return RF_OK;
 }
@@ -190,6 +210,172 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         io.out_u8 = k == K - 1 && plan->image_u8;
         const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
         rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, mark);
+        if (rc != RF_OK) return rc;
+    }
+    if (ms_out) {
+        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
+        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
+    }
+    return RF_OK;
+}
+
+int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                        const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes, int32_t edges,
+                        hipStream_t stream, float *ms_out) {
+    // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
+    if (!plan || !grad_out_planes || !grad_image_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return RF_ERR_INVALID_ARG; }
+    if (plan->image_u8) { set_error("the backward of a smoothing plan takes f32 images (this plan's are uint8)"); return RF_ERR_UNSUPPORTED; }
+    const bool self = plan->n_guide == 0;
+    if (!self && !guide_planes) { set_error("this plan takes %d separate guide planes: guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }
+    if (self && guide_planes) { set_error("this plan's image guides itself (n_guide = 0): guide_planes must be null"); return RF_ERR_INVALID_ARG; }
+    const bool need_image = self || edges == 1;
+    if (need_image && !image_planes) {
+        set_error(self ? "this plan's image guides itself: the backward needs the image planes (image_planes is null)"
+                       : "gradients through the distances need the image planes (image_planes is null)");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (edges == 1 && plan->guide_u8) { set_error("no gradient with respect to a uint8 guide: edges = 1 takes f32 guide planes"); return RF_ERR_UNSUPPORTED; }
+    if (edges == 1 && !self && !grad_guide_planes) { set_error("edges = 1 with %d separate guide planes: grad_guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }
+    if ((edges == 0 || self) && grad_guide_planes) {
+        set_error(edges == 0 ? "edges = 0 forms no guide gradient: grad_guide_planes must be null"
+                             : "this plan's image guides itself (n_guide = 0): its guide gradient is added to grad_image_planes and grad_guide_planes must be null");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
+    const int P = plan->n_planes, G = plan->n_guide, K = plan->iterations;
+    const bool with_guide_grad = edges == 1 && !self;
+    const size_t samples = (size_t)(plan->width * plan->height), plane_bytes = samples * sizeof(float);
+    const size_t guide_bytes = samples * (plan->guide_u8 ? 1 : sizeof(float));
+    for (int pl = 0; pl < P; pl++) {
+        if (!grad_out_planes[pl] || !grad_image_planes[pl] || (need_image && !image_planes[pl])) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
+        if ((((uintptr_t)grad_out_planes[pl] | (uintptr_t)grad_image_planes[pl] | (uintptr_t)(need_image ? image_planes[pl] : nullptr)) & 15u) != 0) {
+            set_error("plane %d: the varying scans need 16-byte aligned image pointers", pl);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    const uintptr_t guide_mask = plan->guide_u8 ? 3u : 15u;
+    for (int ch = 0; ch < G; ch++) {
+        if (!guide_planes[ch] || (with_guide_grad && !grad_guide_planes[ch])) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
+        if (((uintptr_t)guide_planes[ch] & guide_mask) != 0 || (with_guide_grad && ((uintptr_t)grad_guide_planes[ch] & 15u) != 0)) {
+            set_error("guide plane %d: %s guide planes must be %u-byte aligned (the plane and its gradient)", ch, plan->guide_u8 ? "uint8" : "f32", (unsigned)guide_mask + 1);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    // what is written (grad_image planes, guide-gradient planes) against everything that is read and everything else that is written
+    const int n_written = P + (with_guide_grad ? G : 0);
+    auto written = [&](int i) -> const void * { return i < P ? grad_image_planes[i] : grad_guide_planes[i - P]; };
+    auto written_name = [&](int i, char *buf, size_t n) {
+        if (i < P) std::snprintf(buf, n, "grad_image plane %d", i);
+        else std::snprintf(buf, n, "gradient of guide plane %d", i - P);
+    };
+    for (int i = 0; i < n_written; i++) {
+        const void *o = written(i);
+        char name[64];
+        written_name(i, name, sizeof name);
+        for (int ch = 0; ch < G; ch++)
+            if (overlap((uintptr_t)o, plane_bytes, (uintptr_t)guide_planes[ch], guide_bytes)) {
+                set_error("%s overlaps guide plane %d", name, ch);
+                return RF_ERR_INVALID_ARG;
+            }
+        if (need_image)
+            for (int pl = 0; pl < P; pl++)
+                if (overlap(o, image_planes[pl], plane_bytes)) {
+                    set_error("%s overlaps image plane %d", name, pl);
+                    return RF_ERR_INVALID_ARG;
+                }
+        for (int j = i + 1; j < n_written; j++)
+            if (overlap(o, written(j), plane_bytes)) {
+                char other[64];
+                written_name(j, other, sizeof other);
+                set_error("%s overlaps %s", name, other);
+                return RF_ERR_INVALID_ARG;
+            }
+        for (int pl = 0; pl < P; pl++) {
+            if (i == pl && o == grad_out_planes[pl]) continue;      // in place: a plane and its own gradient, exactly
+            if (overlap(o, grad_out_planes[pl], plane_bytes)) {
+                set_error("%s overlaps grad_out plane %d (only grad_image plane %d may, and then exactly)", name, pl, pl);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    }
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    rf_var_plan *inner = plan->inner.get();
+    if (edges == 1) {
+        int rc = ensure_var_grad_planes(inner);
+        if (rc != RF_OK) return rc;
+        if (!plan->grad_planes && hipMalloc((void **)&plan->grad_planes, plan->own_backward_bytes()) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->grad_planes = nullptr;
+            set_error("hipMalloc of %zu bytes for the distance gradients and the checkpoint planes failed", plan->own_backward_bytes());
+            return RF_ERR_NOMEM;
+        }
+    }
+    // events are destroyed on every return path
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } events;
+    const size_t n_kernels = plan->backward_names[edges].size();
+    if (ms_out) {
+        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
+        for (size_t i = 0; i < n_kernels + 1; i++) {
+            hipEvent_t e;
+            RF_HIP_CHECK(hipEventCreate(&e));
+            events.ev.push_back(e);
+        }
+        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
+    }
+    size_t launch = 0;
+    const std::function<int()> mark = [&]() -> int {
+        launch++;
+        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
+        return RF_OK;
+    };
+    const std::function<void()> skip = [] {};      // (both exponent gradients are always formed: nothing is skipped)
+    float *dx = plan->planes, *dy = dx + samples;
+    int rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
+                               dx, dy, plan->device, stream);
+    if (rc == RF_OK) rc = mark();
+    if (rc != RF_OK) return rc;
+    const void *const exponents[2] = {dx, dy};
+    float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples : nullptr;
+    // the output of iteration k, k = 0 .. K-2
+    void *checkpoints[RF_SMOOTH_MAX_ITERATIONS][RF_MAX_PLANES] = {};
+    if (edges == 1) {
+        for (int k = 0; k + 1 < K; k++) {
+            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = gdy + samples * (size_t)(1 + k * P + pl);
+            VarIo io{};
+            io.in = k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
+            io.work = io.out = checkpoints[k];
+            const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
+            rc = launch_var_stages(inner, io, exponents, l, stream, mark);
+            if (rc != RF_OK) return rc;
+        }
+    }
+    void *const grad_exponents[2] = {gdx, gdy};
+    for (int k = K - 1; k >= 0; k--) {
+        const float a_k = plan->bases[(size_t)k];
+        const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
+        const float ln = (float)std::log((double)a_k), c[2] = {ln, ln};
+        const bool holds_sum[2] = {k < K - 1, k < K - 1};
+        VarBackwardIo io{};
+        io.in = edges == 0 ? nullptr : k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
+        io.weights = exponents;
+        io.grad_out = k == K - 1 ? grad_out_planes : (const void *const *)grad_image_planes;
+        io.grad_in = grad_image_planes;
+        io.grad_weights = edges == 1 ? grad_exponents : nullptr;
+        io.log2_base = l;
+        io.ln_base = c;
+        io.holds_sum = holds_sum;
+        rc = launch_var_backward(inner, io, stream, mark, skip);
+        if (rc != RF_OK) return rc;
+    }
+    if (edges == 1) {
+        // a separate guide: stored; the image guiding itself: added to the image gradient the scans have just left there
+        rc = run_var_distances_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->scale, gdx, gdy,
+                                        self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream);
+        if (rc == RF_OK) rc = mark();
         if (rc != RF_OK) return rc;
     }
     if (ms_out) {

@@ -23,6 +23,13 @@ struct rf_smooth_plan {
     size_t planes_bytes = 0;
     std::vector<std::string> names;          // "var_distances", then the inner plan's six per iteration
     size_t workspace_bytes() const { return planes_bytes + inner->workspace_bytes(); }
+    // rf_smooth_plan_backward: the launch names with the distances held constant ([0]) and differentiated ([1]); [1] needs the
+    // gradients of d_x and d_y and the outputs of iterations 0 .. K-2 -- 2 + (K - 1) * n_planes f32 planes, allocated by the first
+    // call that needs them -- and the inner plan's (4 + 1) * n_planes
+    std::vector<std::string> backward_names[2];
+    float *grad_planes = nullptr;
+    size_t own_backward_bytes() const { return (size_t)(2 + (iterations - 1) * n_planes) * (size_t)(width * height) * sizeof(float); }
+    size_t backward_workspace_bytes(bool edges) const { return edges ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
     ~rf_smooth_plan();
 };
 
@@ -31,4 +38,8 @@ int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out);
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
 int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
                     hipStream_t stream, float *ms_out);
+// The adjoint (rf_smooth_plan_backward in recfilter_amd.h); ms_out: one slot per name of backward_names[edges].
+int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                        const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes, int32_t edges,
+                        hipStream_t stream, float *ms_out);
 }  // namespace rf

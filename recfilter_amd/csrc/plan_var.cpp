@@ -15,6 +15,12 @@
 // (n_scans * n_planes, allocated by the first call that needs them), every adjoint stage also stores its unscaled state to
 // n_planes more, and one var_grad launch per scan forms the gradient from the three -- stored by the first launch that touches a
 // weight plane, added by the later ones; the host knows which is which, so there are no atomics and no zero-fill.
+// The power form (rf_var_plan_backward_power) is the same list on the kernels' POWER instances: the stages carry log2 of their
+// plane's base, var_grad also its natural logarithm and the exponent plane, and what it stores is the gradient of the exponents.
+// run_var_backward checks and owns the events; launch_var_backward issues the launches, and is what the smoothing plan's backward
+// (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
+//
+// run_var_distances_backward: the adjoint of run_var_distances, one launch.
 #include "plan_var.h"
 
 #include <algorithm>
@@ -273,14 +279,26 @@ bool overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintp
 
 }  // namespace
 
-int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const void *const *grad_out_planes,
-                     void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream, float *ms_out) {
+int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
+                     const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream,
+                     float *ms_out) {
     // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
     if (!plan || !weight_planes || !grad_out_planes || !grad_in_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     bool with_weights = false;
     if (grad_weight_planes)
         for (int k = 0; k < plan->n_weights; k++) with_weights = with_weights || grad_weight_planes[k] != nullptr;
     if (with_weights && !in_planes) { set_error("weight gradients need the input planes (in_planes is null)"); return RF_ERR_INVALID_ARG; }
+    float log2_base[RF_VAR_MAX_SCANS] = {}, ln_base[RF_VAR_MAX_SCANS] = {};
+    if (bases) {
+        for (int k = 0; k < plan->n_weights; k++) {
+            if (!std::isfinite(bases[k]) || !(bases[k] > 0.0f && bases[k] < 1.0f)) {
+                set_error("exponent plane %d: the base must be inside (0, 1) (got %g)", k, (double)bases[k]);
+                return RF_ERR_INVALID_ARG;
+            }
+            log2_base[k] = (float)std::log2((double)bases[k]);
+            ln_base[k] = (float)std::log((double)bases[k]);
+        }
+    }
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
     const int P = plan->n_planes, K = plan->n_weights;
     const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
@@ -337,14 +355,9 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
         }
     }
     RF_HIP_CHECK(hipSetDevice(plan->device));
-    const int S = (int)plan->scans.size();
-    if (with_weights && !plan->grad_planes) {
-        if (hipMalloc((void **)&plan->grad_planes, plan->backward_workspace_bytes(true)) != hipSuccess) {
-            (void)hipGetLastError();
-            plan->grad_planes = nullptr;
-            set_error("hipMalloc of %zu bytes for the weight gradients' planes failed", plan->backward_workspace_bytes(true));
-            return RF_ERR_NOMEM;
-        }
+    if (with_weights) {
+        int rc = ensure_var_grad_planes(plan);
+        if (rc != RF_OK) return rc;
     }
     // events are destroyed on every return path
     struct Events {
@@ -362,21 +375,61 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
         RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
     }
     size_t launch = 0;
-    auto mark = [&]() -> int {
+    const std::function<int()> mark = [&]() -> int {
         launch++;
         if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
         return RF_OK;
     };
-    const size_t plane_floats = plane_bytes / sizeof(float);
+    std::vector<size_t> skipped;      // slots of var_grad launches that were not issued
+    const std::function<void()> skip = [&]() { skipped.push_back(launch); };
+    VarBackwardIo io{};
+    io.in = in_planes;
+    io.weights = weight_planes;
+    io.grad_out = grad_out_planes;
+    io.grad_in = grad_in_planes;
+    io.grad_weights = with_weights ? grad_weight_planes : nullptr;
+    io.log2_base = bases ? log2_base : nullptr;
+    io.ln_base = bases ? ln_base : nullptr;
+    int rc = launch_var_backward(plan, io, stream, mark, skip);
+    if (rc != RF_OK) return rc;
+    if (ms_out) {
+        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
+        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
+        for (size_t i : skipped) ms_out[i] = 0.0f;
+    }
+    return RF_OK;
+}
+
+int ensure_var_grad_planes(rf_var_plan *plan) {
+    if (plan->grad_planes) return RF_OK;
+    if (hipMalloc((void **)&plan->grad_planes, plan->backward_workspace_bytes(true)) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->grad_planes = nullptr;
+        set_error("hipMalloc of %zu bytes for the weight gradients' planes failed", plan->backward_workspace_bytes(true));
+        return RF_ERR_NOMEM;
+    }
+    return RF_OK;
+}
+
+int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, const std::function<int()> &mark,
+                        const std::function<void()> &skip) {
+    const int P = plan->n_planes, S = (int)plan->scans.size();
+    const bool with_weights = io.grad_weights != nullptr, power = io.log2_base != nullptr;
+    const size_t plane_floats = (size_t)(plan->width * plan->height);
     auto saved = [&](int scan, int pl) { return plan->grad_planes + ((size_t)scan * P + pl) * plane_floats; };      // scan == S: the state
+    auto form = [&](VarArgs &a, const rf_var_scan_desc &sc) {
+        a.power = power ? 1 : 0;
+        a.log2_base = power ? io.log2_base[sc.weights] : 0.0f;
+    };
     int rc = RF_OK;
     if (with_weights) {
         // the forward again, scan by scan, every output kept: scan q reads scan q-1's planes
         for (int q = 0; q < S && rc == RF_OK; q++) {
             const rf_var_scan_desc &sc = plan->scans[q];
-            VarArgs a = scan_args(plan, sc, weight_planes, sc.causal != 0 ? VAR_CAUSAL : VAR_ANTICAUSAL);
+            VarArgs a = scan_args(plan, sc, io.weights, sc.causal != 0 ? VAR_CAUSAL : VAR_ANTICAUSAL);
+            form(a, sc);
             for (int pl = 0; pl < P; pl++) {
-                a.src[pl] = q == 0 ? in_planes[pl] : saved(q - 1, pl);
+                a.src[pl] = q == 0 ? io.in[pl] : saved(q - 1, pl);
                 a.dst[pl] = saved(q, pl);
             }
             rc = launch_var_tails(a, sc.dim, stream);
@@ -388,16 +441,18 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
         }
     }
     bool touched[RF_VAR_MAX_SCANS] = {};
-    std::vector<size_t> skipped;      // slots of var_grad launches that were not issued
+    if (io.holds_sum)
+        for (int k = 0; k < plan->n_weights; k++) touched[k] = io.holds_sum[k];
     for (int q = S - 1; q >= 0 && rc == RF_OK; q--) {
         const rf_var_scan_desc &sc = plan->scans[q];
-        float *const grad = with_weights ? (float *)grad_weight_planes[sc.weights] : nullptr;
+        float *const grad = with_weights ? (float *)io.grad_weights[sc.weights] : nullptr;
         // the adjoint of a causal scan runs anticausally, and the other way round
-        VarArgs a = scan_args(plan, sc, weight_planes, sc.causal != 0 ? VAR_ANTICAUSAL : VAR_CAUSAL);
+        VarArgs a = scan_args(plan, sc, io.weights, sc.causal != 0 ? VAR_ANTICAUSAL : VAR_CAUSAL);
+        form(a, sc);
         a.adjoint = 1;
         for (int pl = 0; pl < P; pl++) {
-            a.src[pl] = q == S - 1 ? grad_out_planes[pl] : grad_in_planes[pl];
-            a.dst[pl] = grad_in_planes[pl];
+            a.src[pl] = q == S - 1 ? io.grad_out[pl] : io.grad_in[pl];
+            a.dst[pl] = io.grad_in[pl];
             a.lam[pl] = grad ? saved(S, pl) : nullptr;
         }
         rc = launch_var_tails(a, sc.dim, stream);
@@ -411,7 +466,7 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
             VarGradArgs g{};
             for (int pl = 0; pl < P; pl++) {
                 g.lam[pl] = saved(S, pl);
-                g.x[pl] = q == 0 ? (const float *)in_planes[pl] : saved(q - 1, pl);
+                g.x[pl] = q == 0 ? (const float *)io.in[pl] : saved(q - 1, pl);
                 g.y[pl] = saved(q, pl);
             }
             g.grad = grad;
@@ -419,20 +474,19 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
             g.height = (int32_t)plan->height;
             g.n_planes = P;
             g.accumulate = touched[sc.weights] ? 1 : 0;
+            if (power) {
+                g.exponents = (const float *)io.weights[sc.weights];
+                g.log2_base = io.log2_base[sc.weights];
+                g.ln_base = io.ln_base[sc.weights];
+            }
             touched[sc.weights] = true;
             rc = launch_var_grad(g, sc.dim, sc.causal != 0, stream);
         } else {
-            skipped.push_back(launch);
+            skip();
         }
         if (rc == RF_OK) rc = mark();
     }
-    if (rc != RF_OK) return rc;
-    if (ms_out) {
-        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
-        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
-        for (size_t i : skipped) ms_out[i] = 0.0f;
-    }
-    return RF_OK;
+    return rc;
 }
 
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
@@ -477,6 +531,64 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
     a.n_guide = n_guide;
     a.scale = scale;
     return launch_var_distances(a, guide_u8 != 0, stream);
+}
+
+int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
+                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream) {
+    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
+    if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
+    if (!guide_planes || !grad_dx || !grad_dy || !grad_guide_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (!guide_planes[ch] || !grad_guide_planes[ch]) { set_error("guide plane %d: null pointer (the plane or its gradient)", ch); return RF_ERR_INVALID_ARG; }
+    if (!std::isfinite(scale) || scale < 0.0f) { set_error("scale must be finite and not negative (got %g)", (double)scale); return RF_ERR_INVALID_ARG; }
+    if (accumulate != 0 && accumulate != 1) { set_error("accumulate must be 0 or 1 (got %d)", accumulate); return RF_ERR_INVALID_ARG; }
+    if (width % 4 != 0) {
+        set_error("var_distances_grad moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)width);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (width > kVarMaxExtent || height > kVarMaxExtent) {
+        set_error("extents %lld x %lld are above %lld", (long long)width, (long long)height, (long long)kVarMaxExtent);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if ((((uintptr_t)grad_dx | (uintptr_t)grad_dy) & 15u) != 0) { set_error("grad_dx and grad_dy must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if ((((uintptr_t)guide_planes[ch] | (uintptr_t)grad_guide_planes[ch]) & 15u) != 0) {
+            set_error("guide plane %d: f32 guide planes and their gradients must be 16-byte aligned", ch);
+            return RF_ERR_INVALID_ARG;
+        }
+    // a gradient plane is written while other lanes still read: it overlaps nothing that is read and no other gradient plane
+    const size_t bytes = (size_t)(width * height) * sizeof(float);
+    for (int ch = 0; ch < n_guide; ch++) {
+        const void *o = grad_guide_planes[ch];
+        if (overlap(o, bytes, grad_dx, bytes) || overlap(o, bytes, grad_dy, bytes)) {
+            set_error("gradient of guide plane %d overlaps grad_dx or grad_dy: a lane reads its neighbours' samples", ch);
+            return RF_ERR_INVALID_ARG;
+        }
+        for (int q = 0; q < n_guide; q++) {
+            if (overlap(o, bytes, guide_planes[q], bytes)) {
+                set_error("gradient of guide plane %d overlaps guide plane %d: a lane reads its neighbours' samples", ch, q);
+                return RF_ERR_INVALID_ARG;
+            }
+            if (q > ch && overlap(o, bytes, grad_guide_planes[q], bytes)) {
+                set_error("gradient of guide plane %d overlaps gradient of guide plane %d", ch, q);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    }
+    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
+    VarDistGradArgs a{};
+    for (int ch = 0; ch < n_guide; ch++) {
+        a.guide[ch] = (const float *)guide_planes[ch];
+        a.grad_guide[ch] = (float *)grad_guide_planes[ch];
+    }
+    a.gdx = (const float *)grad_dx;
+    a.gdy = (const float *)grad_dy;
+    a.width = (int32_t)width;
+    a.height = (int32_t)height;
+    a.n_guide = n_guide;
+    a.accumulate = accumulate;
+    a.scale = scale;
+    return launch_var_distances_grad(a, stream);
 }
 
 }  // namespace rf

@@ -58,9 +58,28 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
                       const std::function<int()> &mark);
 // The adjoint of the plan (rf_var_plan_backward in recfilter_amd.h).  grad_weight_planes: nullptr, or n_weights entries, each nullptr
 // (no gradient for that plane) or a plane.  ms_out as in run_var_plan, one slot per name of backward_names[with weight gradients].
-int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const void *const *grad_out_planes,
-                     void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream, float *ms_out);
+// bases == nullptr: the plane form; else the power form (rf_var_plan_backward_power): `weight_planes` hold exponents and the
+// gradient planes receive the gradient of the exponents.
+int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
+                     const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream,
+                     float *ms_out);
+// The launches of one backward run of `plan`, nothing checked (run_var_backward and plan_smooth.cpp check first, and call
+// ensure_var_grad_planes where grad_weights is not null).  grad_weights: nullptr (3 launches per scan), or n_weights entries.
+// log2_base / ln_base: nullptr for the plane form, else per weight plane.  holds_sum: nullptr, or per weight plane whether its
+// gradient plane already holds a sum this run adds to (else the first var_grad launch that touches a plane stores).  `mark` is
+// called behind every launch and behind every var_grad slot that was not issued; `skip` just before mark for such a slot.
+struct VarBackwardIo {
+    const void *const *in = nullptr, *const *weights = nullptr, *const *grad_out = nullptr;
+    void *const *grad_in = nullptr, *const *grad_weights = nullptr;
+    const float *log2_base = nullptr, *ln_base = nullptr;
+    const bool *holds_sum = nullptr;
+};
+int ensure_var_grad_planes(rf_var_plan *plan);
+int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, const std::function<int()> &mark,
+                        const std::function<void()> &skip);
 int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                       void *dx, void *dy, int32_t device, hipStream_t stream);
+int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
+                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream);
 }  // namespace rf

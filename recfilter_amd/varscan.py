@@ -11,7 +11,11 @@ The scans run in the HIP kernels of kernels_var.hip; torch tensors are device me
 
 The plane form is differentiable: `VarPlan.backward` (rf_var_plan_backward) is the adjoint of `VarPlan.execute` in the same HIP
 kernels' adjoint instances -- gradients with respect to the image planes and, where asked for, the weight planes -- and
-`VarPlan.apply` / `var_scan` put it behind torch.autograd.
+`VarPlan.apply` / `var_scan` put it behind torch.autograd.  So are the power form and the plan: `VarPlan.backward_power`
+(rf_var_plan_backward_power; gradients with respect to the image planes and the exponent planes), `domain_transform_distances_backward`
+(rf_var_distances_backward; the guide's gradient from those of the two distance planes) and `SmoothPlan.backward`
+(rf_smooth_plan_backward: both, sequenced by the library), behind `VarPlan.apply_power`, `SmoothPlan.apply` and
+`edge_aware_smooth(form="plan", differentiable=True)`.  f32 planes only; no byte-guide gradient; no double backward.
 """
 from __future__ import annotations
 
@@ -213,13 +217,44 @@ class VarPlan:
                                                          host_stream if host_stream is not None else self._stream(stream), ms, names, n))
         return grad_ins, grad_weights, [(names[i].decode(), float(ms[i])) for i in range(n)]
 
+    def backward_power(self, ins, exponents, bases, grad_outs, grad_ins=None, grad_exponents=None, stream=None):
+        """rf_var_plan_backward_power, the adjoint of execute_power: (grad_ins, grad_exponents).  As backward, with the exponent
+        planes and their bases in the place of the weights; a gradient plane receives dL/dd = (w ln base) dL/dw."""
+        pb = self._bases(bases)
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, host_stream = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents)
+        capi.check(capi.lib().rf_var_plan_backward_power(self._h, pin, pw, pb, pgo, pgi, pgw,
+                                                         host_stream if host_stream is not None else self._stream(stream)))
+        return grad_ins, grad_exponents
+
+    def backward_power_timed(self, ins, exponents, bases, grad_outs, grad_ins=None, grad_exponents=None, stream=None):
+        """rf_var_plan_backward_power_timed: (grad_ins, grad_exponents, [(kernel name, ms), ...]); the launches backward_timed names"""
+        pb = self._bases(bases)
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, host_stream = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents)
+        n = self.backward_num_kernels(grad_exponents is not None and any(t is not None for t in grad_exponents))
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_var_plan_backward_power_timed(self._h, pin, pw, pb, pgo, pgi, pgw,
+                                                               host_stream if host_stream is not None else self._stream(stream), ms, names, n))
+        return grad_ins, grad_exponents, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    def apply_power(self, ins, exponents, bases):
+        """execute_power, out of place, as a differentiable torch operation: values bit for bit execute_power's.  Backward is
+        `backward_power` -- the image gradient always, the gradient of an exponent plane where that plane requires one.  The
+        bases are constants.  No double backward."""
+        if len(ins) != self.planes or len(exponents) != self.n_weights:
+            raise ValueError(f"expected {self.planes} input planes and {self.n_weights} exponent planes, got {len(ins)} and {len(exponents)}")
+        bases = [float(b) for b in bases]
+        if len(bases) != self.n_weights:
+            raise ValueError(f"expected {self.n_weights} bases, got {len(bases)}")
+        return _var_scan_function().apply((self, bases), *ins, *exponents)
+
     def apply(self, ins, weights):
         """execute, out of place, as a differentiable torch operation: a tuple of `planes` output planes whose values are bit for
         bit execute's.  Backward is `backward` -- the image gradient always, the gradient of a weight plane where that plane
         requires one.  Only the inputs and the weights are saved; no double backward."""
         if len(ins) != self.planes or len(weights) != self.n_weights:
             raise ValueError(f"expected {self.planes} input planes and {self.n_weights} weight planes, got {len(ins)} and {len(weights)}")
-        return _var_scan_function().apply(self, *ins, *weights)
+        return _var_scan_function().apply((self, None), *ins, *weights)
 
 
 _function = None
@@ -238,12 +273,13 @@ def _var_scan_function():
 
     class VarScanFunction(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, plan, *tensors):
+        def forward(ctx, plan_and_bases, *tensors):      # bases None: the plane form; else the power form
+            plan, bases = plan_and_bases
             ins = [plane(t) for t in tensors[:plan.planes]]
             weights = [plane(t) for t in tensors[plan.planes:]]
-            ctx.plan = plan
+            ctx.plan, ctx.bases = plan, bases
             ctx.save_for_backward(*ins, *weights)
-            return tuple(plan.execute(ins, weights))
+            return tuple(plan.execute(ins, weights) if bases is None else plan.execute_power(ins, weights, bases))
 
         @staticmethod
         @torch.autograd.function.once_differentiable
@@ -258,7 +294,10 @@ def _var_scan_function():
             if any(n and k in read for k, n in enumerate(need_w)):
                 grad_weights = [torch.empty_like(w) if n and k in read else None for k, (w, n) in enumerate(zip(weights, need_w))]
             with torch.cuda.device(ins[0].device):
-                grad_ins, grad_weights = plan.backward(ins, weights, [plane(g) for g in grad_outs], None, grad_weights)
+                if ctx.bases is None:
+                    grad_ins, grad_weights = plan.backward(ins, weights, [plane(g) for g in grad_outs], None, grad_weights)
+                else:
+                    grad_ins, grad_weights = plan.backward_power(ins, weights, ctx.bases, [plane(g) for g in grad_outs], None, grad_weights)
             grad_weights = grad_weights or [None] * plan.n_weights
             # (a weight plane that no scan reads has a gradient of zero)
             grad_weights = [torch.zeros_like(w) if n and k not in read else g for k, (w, n, g) in enumerate(zip(weights, need_w, grad_weights))]
@@ -344,6 +383,38 @@ def domain_transform_distances(guide, sigma_s: float, sigma_r: float, stream=Non
         capi.check(capi.lib().rf_var_distances(planes, C, int(u8), W, H, scale, dx.data_ptr(), dy.data_ptr(), g.device.index,
                                                VarPlan._stream(stream)))
     return dx, dy
+
+
+def domain_transform_distances_backward(guide, sigma_s: float, sigma_r: float, grad_dx, grad_dy, grad_guide=None, accumulate: bool = False,
+                                        stream=None):
+    """rf_var_distances_backward: the gradient of an f32 device guide (C, H, W) or (H, W) from the gradients of the two planes of
+    `domain_transform_distances` (one HIP launch, a gather).  grad_guide=None allocates it (then accumulate must be False);
+    accumulate=True adds to what grad_guide holds.  Returned in the guide's shape."""
+    import torch
+    g = guide if guide.dim() == 3 else guide.unsqueeze(0)
+    if g.dim() != 3:
+        raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
+    if g.dtype != torch.float32:
+        raise TypeError(f"float32 guides only (there is no gradient with respect to a byte guide), got {g.dtype}")
+    if not g.is_cuda:
+        raise ValueError("the guide must be a device tensor")
+    g = g.contiguous()
+    C, H, W = (int(s) for s in g.shape)
+    if grad_guide is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs grad_guide")
+        grad_guide = torch.empty_like(g)
+    gg = grad_guide if grad_guide.dim() == 3 else grad_guide.unsqueeze(0)
+    for what, t, shape in (("grad_dx", grad_dx, (H, W)), ("grad_dy", grad_dy, (H, W)), ("grad_guide", gg, (C, H, W))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {shape}")
+    planes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
+    grads = (ctypes.c_void_p * C)(*[gg[c].data_ptr() for c in range(C)])
+    scale = float(sigma_s) / float(sigma_r)
+    with torch.cuda.device(g.device):
+        capi.check(capi.lib().rf_var_distances_backward(planes, C, W, H, scale, grad_dx.data_ptr(), grad_dy.data_ptr(), grads,
+                                                        int(bool(accumulate)), g.device.index, VarPlan._stream(stream)))
+    return grad_guide
 
 
 class SmoothPlan:
@@ -469,12 +540,109 @@ class SmoothPlan:
         return out, [(names[i].decode(), float(ms[i])) for i in range(n)]
 
 
+    # -- the adjoint ------------------------------------------------------------------------
+    def backward_num_kernels(self, edges: bool = False) -> int:
+        """rf_smooth_plan_backward_num_kernels: 1 + 12 K launches with the distances held constant, 34 K - 4 through them"""
+        return int(capi.lib().rf_smooth_plan_backward_num_kernels(self._h, int(bool(edges))))
+
+    def backward_workspace_bytes(self, edges: bool = False) -> int:
+        """rf_smooth_plan_backward_workspace_bytes: what the first backward call with edges allocates beyond workspace_bytes,
+        2 + (K - 1 + 5) * planes f32 planes; 0 without edges"""
+        return int(capi.lib().rf_smooth_plan_backward_workspace_bytes(self._h, int(bool(edges))))
+
+    def _backward_arguments(self, image, guide, grad_out, grad_image, grad_guide, edges):
+        import torch
+        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
+            # (the library refuses; there are no device tensors to take pointers from)
+            nulls = lambda n: (ctypes.c_void_p * max(n, 1))()      # noqa: E731
+            return (nulls(self.planes) if image is not None else None, nulls(self.guide_planes) if guide is not None else None,
+                    nulls(self.planes), nulls(self.planes), nulls(self.guide_planes) if grad_guide is not None else None,
+                    None, None, ctypes.c_void_p())
+        f32 = torch.float32
+        if grad_image is None:
+            grad_image = torch.empty_like(grad_out) if hasattr(grad_out, "dim") else [torch.empty_like(t) for t in grad_out]
+        if edges and self.guide_planes and grad_guide is None and guide is not None and self.guide_dtype == f32:
+            grad_guide = torch.empty_like(guide) if hasattr(guide, "dim") else [torch.empty_like(t) for t in guide]
+        return (self._pointers(image, self.planes, f32, "image") if image is not None else None,
+                self._pointers(guide, self.guide_planes, self.guide_dtype, "guide") if guide is not None else None,
+                self._pointers(grad_out, self.planes, f32, "grad_out"), self._pointers(grad_image, self.planes, f32, "grad_image"),
+                self._pointers(grad_guide, self.guide_planes, f32, "grad_guide") if grad_guide is not None else None,
+                grad_image, grad_guide, None)
+
+    def backward(self, image, guide, grad_out, grad_image=None, grad_guide=None, edges: bool = False, stream=None):
+        """rf_smooth_plan_backward, the adjoint of execute for f32 images: (grad_image, grad_guide) from grad_out = dL/d(out).
+        edges=False holds the distances constant (grad_guide is None; `image` is needed only where the image guides itself).
+        edges=True differentiates through them: with separate f32 guide planes grad_guide is written (allocated when None); where
+        the image guides itself that gradient is added into grad_image.  grad_image=None allocates it; it may be grad_out (in
+        place).  Asynchronous on `stream`; uses the plan's workspace like an execute."""
+        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, host_stream = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges)
+        capi.check(capi.lib().rf_smooth_plan_backward(self._h, pi, pg, pgo, pgi, pgg, int(edges),
+                                                      host_stream if host_stream is not None else VarPlan._stream(stream)))
+        return grad_image, grad_guide
+
+    def backward_timed(self, image, guide, grad_out, grad_image=None, grad_guide=None, edges: bool = False, stream=None):
+        """rf_smooth_plan_backward_timed: (grad_image, grad_guide, [(kernel name, ms), ...]); synchronises the stream"""
+        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, host_stream = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges)
+        n = self.backward_num_kernels(edges)
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_smooth_plan_backward_timed(self._h, pi, pg, pgo, pgi, pgg, int(edges),
+                                                            host_stream if host_stream is not None else VarPlan._stream(stream), ms, names, n))
+        return grad_image, grad_guide, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    def apply(self, image, guide=None):
+        """execute, out of place, as a differentiable torch operation on f32 tensors (C, H, W) or (H, W): values bit for bit
+        execute's.  Backward is `backward`; it goes through the distances (edges) where the guide requires a gradient, or the
+        image does and guides itself.  Only the image and the guide are saved; no double backward."""
+        return _smooth_function().apply(self, image, guide)
+
+
+_smooth_fn = None
+
+
+def _smooth_function():
+    """the torch.autograd.Function behind SmoothPlan.apply (torch is imported when it is first needed)"""
+    global _smooth_fn
+    if _smooth_fn is not None:
+        return _smooth_fn
+    import torch
+
+    def planes(t):      # what the library takes: contiguous, 16-byte aligned
+        t = t.contiguous()
+        return t.clone() if t.data_ptr() % 16 else t
+
+    class SmoothFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, image, guide):
+            image = planes(image)
+            guide = planes(guide) if guide is not None else None
+            ctx.plan = plan
+            ctx.save_for_backward(image, *([guide] if guide is not None else []))
+            with torch.cuda.device(image.device):
+                return plan.execute(image, guide)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            image = ctx.saved_tensors[0]
+            guide = ctx.saved_tensors[1] if len(ctx.saved_tensors) > 1 else None
+            need_image, need_guide = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+            edges = need_guide if guide is not None else need_image
+            with torch.cuda.device(image.device):
+                grad_image, grad_guide = plan.backward(image, guide, planes(grad_out), None, None, edges=bool(edges))
+            return None, grad_image if need_image else None, grad_guide if need_guide else None
+
+    _smooth_fn = SmoothFunction
+    return _smooth_fn
+
+
 _SMOOTH_SCANS = [(0, True, 0), (0, False, 0), (1, True, 1), (1, False, 1)]      # +x -x on weights 0, +y -y on weights 1
 _smooth_plans: Dict[Tuple[int, int, int, int], VarPlan] = {}
 _smooth_plan_objects: Dict[tuple, SmoothPlan] = {}
 
 
-def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations):
+def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=False):
     import torch
     img = (image if image.dim() == 3 else image.unsqueeze(0))
     if img.dim() != 3:
@@ -500,12 +668,18 @@ def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations):
         plan = _smooth_plan_objects[key] = SmoothPlan((H, W), planes=C, guide_planes=0 if g is None else int(g.shape[0]), image_dtype=img.dtype,
                                                       guide_dtype=None if g is None else g.dtype, iterations=iterations, sigma_s=sigma_s,
                                                       sigma_r=sigma_r, device=device)
+    if differentiable and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad)):
+        if img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad):
+            raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
+        out = plan.apply(img, g)
+        return out if image.dim() == 3 else out[0]
     with torch.cuda.device(img.device):
         out = plan.execute(img, g)
     return out if image.dim() == 3 else out[0]
 
 
-def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes"):
+def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes",
+                      differentiable: bool = False):
     """Edge-aware smoothing of a device image (C, H, W) or (H, W), f32, by the domain-transform recursive filter: per iteration
     +x, -x on that iteration's x weights, then +y, -y on its y weights (two fused stages, six launches).  guide=None: the image
     guides itself.  One plan per (shape, device), cached; calls on one shape are ordered by the caller (one stream).
@@ -516,13 +690,18 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     dtype -- a uint8 image gives uint8 (sat8 of the f32 filter on the bytes, the byte image guiding itself as image / 255).
     Gradients: with form="planes", torch's grad mode on and an image or a guide that requires a gradient, the scans go through
     `var_scan` (same values, bit for bit) and the result is differentiable with respect to both -- the guide through the torch
-    expression `domain_transform_weights` is.  form="power" and form="plan" are not differentiable: their result carries no
-    grad_fn whatever the inputs require."""
+    expression `domain_transform_weights` is.  form="plan" with differentiable=True goes through `SmoothPlan.apply` (same values,
+    bit for bit): f32 images, gradients with respect to the image and an f32 guide, all of it in the library (through the
+    distances where the guide, or a self-guiding image, requires a gradient).  Without the flag form="plan" carries no grad_fn
+    whatever the inputs require, and form="power" never does: differentiable=True with form="power" raises ValueError (use
+    "plan"); with form="planes" the flag changes nothing."""
     import torch
     if form not in ("planes", "power", "plan"):
         raise ValueError(f"form must be 'planes', 'power' or 'plan', got {form!r}")
+    if differentiable and form == "power":
+        raise ValueError('form="power" is not differentiable: use form="plan" with differentiable=True (or form="planes")')
     if form == "plan":
-        return _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations)
+        return _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable)
     img = image if image.dim() == 3 else image.unsqueeze(0)
     if img.dim() != 3:
         raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
