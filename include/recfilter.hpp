@@ -866,8 +866,12 @@ inline void domain_transform_distances_gradient(const std::vector<const void *> 
 class RecFilterSmooth {
     rf_smooth_desc desc{};
     rf_smooth_plan *plan = nullptr;
+    rf_smooth_batch_desc batch_desc{};
+    bool batched = false;
     void prepare() {
-        if (!plan && rf_smooth_plan_create(&desc, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
+        if (plan) return;
+        const int rc = batched ? rf_smooth_plan_create_batched(&desc, &batch_desc, &plan) : rf_smooth_plan_create(&desc, &plan);
+        if (rc != RF_OK) throw RecFilterError(rf_last_error_string());
     }
 public:
     RecFilterSmooth(int64_t width, int64_t height, int planes, int guide_planes, bool guide_u8, bool image_u8, int iterations,
@@ -888,6 +892,18 @@ public:
     RecFilterSmooth(const RecFilterSmooth &) = delete;
     RecFilterSmooth &operator=(const RecFilterSmooth &) = delete;
     ~RecFilterSmooth() { if (plan) rf_smooth_plan_destroy(plan); }
+    /** Before first use: `n` images per realize() / gradient() call, every launch taking all of them (rf_smooth_plan_create_batched).
+     *  The plane vectors then name image 0's planes; image b's are image_stride samples further per b (guide planes and their
+     *  gradients: guide_stride; 0 where the image guides itself).  Contiguous NCHW: image_stride = C*H*W, guide_stride = G*H*W.
+     *  Each image is filtered with its own edges, bit for bit as a filter without a batch filters it. */
+    RecFilterSmooth &batch(int n, int64_t image_stride, int64_t guide_stride = 0) {
+        if (plan) throw RecFilterError("batch: set before the first realize, gradient or query");
+        batch_desc.batch = n;
+        batch_desc.image_stride = image_stride;
+        batch_desc.guide_stride = guide_stride;
+        batched = true;
+        return *this;
+    }
     /** image / out: one device plane per channel; guide: the separate guide planes, empty when the image guides itself.
      *  Asynchronous on `stream`. */
     void realize(const std::vector<const void *> &image, const std::vector<const void *> &guide, const std::vector<void *> &out,

@@ -645,6 +645,43 @@ int    rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *im
 int    rf_smooth_plan_backward_num_kernels(const rf_smooth_plan *plan, int edges);
 size_t rf_smooth_plan_backward_workspace_bytes(const rf_smooth_plan *plan, int edges);
 
+/* A batch: `batch` images of the description per call, forward and backward, every launch taking all of them (the batch is a
+ * grid dimension of every kernel, never a loop on the host).  The result is an ordinary rf_smooth_plan: execute, execute_timed,
+ * backward, backward_timed, bases, the queries and destroy take it with their signatures above.
+ * The pointer arrays of those calls name image 0's planes.  Plane pl of image b is  planes[pl] + b * image_stride  samples in
+ * image_planes, out_planes, grad_out_planes and grad_image_planes, and  planes[ch] + b * guide_stride  in guide_planes and
+ * grad_guide_planes.  A contiguous NCHW tensor: image_stride = C*H*W, guide_stride = G*H*W.
+ * Every image is filtered with its own edges -- its own distance planes, from its own guide or from itself -- in its own tile
+ * grid, with its own tails and carries: out[b] and the gradients of image b are, bit for bit, those of a single-image plan of the
+ * same description on image b, whatever its position in the batch and whatever the other images hold (NaN included).
+ * rf_smooth_plan_num_kernels and rf_smooth_plan_backward_num_kernels return what they return for one image (1 + 6 K, 1 + 12 K,
+ * 34 K - 4; the same names in the same order): launches do not grow with the batch.  rf_smooth_plan_workspace_bytes and
+ * rf_smooth_plan_backward_workspace_bytes(plan, 1) are exactly `batch` times the single-image plan's: 2 * batch distance planes,
+ * batch * n_planes working planes for byte images, tails and carries per image in the single-image layout, and per image the
+ * planes of the backward.  An allocation that fails: RF_ERR_NOMEM, the message carries the byte count, *plan_out stays NULL.
+ * batch = 1 behaves as rf_smooth_plan_create in every respect, bit for bit.
+ * Create refuses, before any HIP call and in this order: a null batch; a null desc or plan_out; batch outside
+ * 1..RF_SMOOTH_MAX_BATCH; a stride that is not a multiple of 4 samples (every plane of every image stays 16-byte aligned for f32
+ * and 4-byte aligned for bytes); image_stride < width * height; guide_stride != 0 with n_guide == 0; guide_stride < width * height
+ * with n_guide > 0 -- a guide shared by the whole batch (stride 0) is not supported: its gradient would be a sum across images
+ * (all RF_ERR_INVALID_ARG); then everything rf_smooth_plan_create refuses, with its status.
+ * Execute and backward keep their checks and their order.  With batch > 1 the aliasing rules hold per (image, plane) extent
+ * [planes[pl] + b * stride, + width * height samples): a written plane (out; grad_image, grad_guide) is disjoint from every other
+ * extent of the call, read or written -- except that out[b][pl] may be exactly image[b][pl], and grad_image[b][pl] exactly
+ * grad_out[b][pl] (in place).  Guide planes may still overlap the output planes of an execute.  A stride that makes planes of
+ * different images overlap is refused by the same rule (RF_ERR_INVALID_ARG; the message names both planes and their images).  The
+ * extents are sorted, not paired: E log E steps for the E = batch * (planes of the arrays involved) extents of a call.
+ * Not supported: a guide shared across the batch, images of different sizes in one batch, 16-bit planes, widths that are not
+ * multiples of 4, byte images in the backward. */
+#define RF_SMOOTH_MAX_BATCH 1024
+typedef struct {
+    int32_t batch;          /* 1..RF_SMOOTH_MAX_BATCH images per call                                                   */
+    int64_t image_stride;   /* samples from image b to image b+1 in image_planes, out_planes, grad_out_planes,
+                               grad_image_planes: plane pl of image b is  planes[pl] + b * image_stride                 */
+    int64_t guide_stride;   /* the same for guide_planes and grad_guide_planes; must be 0 when n_guide == 0             */
+} rf_smooth_batch_desc;
+int    rf_smooth_plan_create_batched(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **plan_out);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);
 const char *rf_version(void);

@@ -22,6 +22,7 @@ RF_MAX_SCANS = 32
 RF_MAX_PLANES = 16
 RF_VAR_MAX_SCANS = 8     # scans (and weight planes) of a plan of spatially varying scans (rf_var_desc)
 RF_SMOOTH_MAX_ITERATIONS = 8     # iterations of a smoothing plan (rf_smooth_desc)
+RF_SMOOTH_MAX_BATCH = 1024       # images of a batched smoothing plan (rf_smooth_batch_desc)
 RF_DEVICE_HOST_ONLY = -2
 
 RF_OK, RF_ERR_INVALID_ARG, RF_ERR_UNSUPPORTED, RF_ERR_HIP, RF_ERR_NOMEM, RF_ERR_STATE = range(6)
@@ -72,7 +73,7 @@ EXPORTED_SYMBOLS = [
     "rf_smooth_plan_bases", "rf_smooth_plan_execute", "rf_smooth_plan_execute_timed",
     "rf_var_plan_backward_power", "rf_var_plan_backward_power_timed", "rf_var_distances_backward",
     "rf_smooth_plan_backward", "rf_smooth_plan_backward_timed", "rf_smooth_plan_backward_num_kernels",
-    "rf_smooth_plan_backward_workspace_bytes",
+    "rf_smooth_plan_backward_workspace_bytes", "rf_smooth_plan_create_batched",
 ]
 
 
@@ -117,6 +118,10 @@ class SmoothDesc(ctypes.Structure):
                 ("n_planes", ctypes.c_int32), ("n_guide", ctypes.c_int32), ("guide_u8", ctypes.c_int32),
                 ("iterations", ctypes.c_int32), ("sigma_s", ctypes.c_double), ("sigma_r", ctypes.c_double),
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class SmoothBatchDesc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("image_stride", ctypes.c_int64), ("guide_stride", ctypes.c_int64)]
 
 
 class RecFilterError(RuntimeError):
@@ -205,6 +210,7 @@ def lib() -> ctypes.CDLL:
     L.rf_var_distances.argtypes = [vpp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, vp, vp,
                                    ctypes.c_int32, vp]
     L.rf_smooth_plan_create.argtypes = [ctypes.POINTER(SmoothDesc), vpp]
+    L.rf_smooth_plan_create_batched.argtypes = [ctypes.POINTER(SmoothDesc), ctypes.POINTER(SmoothBatchDesc), vpp]
     L.rf_smooth_plan_destroy.argtypes = [vp]
     L.rf_smooth_plan_workspace_bytes.argtypes = [vp]
     L.rf_smooth_plan_workspace_bytes.restype = ctypes.c_size_t

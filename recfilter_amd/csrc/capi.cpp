@@ -678,7 +678,15 @@ int rf_var_distances_backward(const void *const *guide_planes, int32_t n_guide, 
 
 // ---- edge-aware smoothing as one plan (plan_smooth.cpp) -----------------------------------------------------------------------
 int rf_smooth_plan_create(const rf_smooth_desc *desc, rf_smooth_plan **plan_out) {
-    return fenced("rf_smooth_plan_create", [&] { return build_smooth_plan(desc, plan_out); });
+    return fenced("rf_smooth_plan_create", [&] { return build_smooth_plan(desc, nullptr, plan_out); });
+}
+
+int rf_smooth_plan_create_batched(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **plan_out) {
+    return fenced("rf_smooth_plan_create_batched", [&] {
+        if (plan_out) *plan_out = nullptr;
+        if (!batch) { set_error("null batch description (rf_smooth_plan_create takes one image)"); return (int)RF_ERR_INVALID_ARG; }
+        return build_smooth_plan(desc, batch, plan_out);
+    });
 }
 
 int rf_smooth_plan_destroy(rf_smooth_plan *plan) {

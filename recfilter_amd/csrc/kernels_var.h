@@ -40,6 +40,11 @@ struct VarArgs {
     // where lam[pl] is not null, the unscaled lam to it.  The other instances never look at these.
     int32_t adjoint;
     void *lam[RF_MAX_PLANES];
+    // the batch (rf_smooth_plan_create_batched): `batch` images per launch on gridDim.z = batch * n_planes.  The pointers above name
+    // image 0's planes; image b's are `stride` SAMPLES further per b (0 with batch 1), its weight plane weights_stride floats, its
+    // tails and carries -- one image's worth each, in the layout above -- tails_stride / carry_stride floats.
+    int32_t batch;
+    int64_t src_stride, dst_stride, lam_stride, weights_stride, tails_stride, carry_stride;
 };
 
 // The weight gradient of ONE scan (kernels_var.hip, var_grad): lam = that scan's adjoint state, x / y = its saved input and output.
@@ -58,6 +63,9 @@ struct VarGradArgs {
     // w = exp2(exponents[i] * log2_base) as the scans form it
     const float *exponents;
     float log2_base, ln_base;
+    // the batch, on gridDim.z: image b's planes are these strides (samples) behind image 0's
+    int32_t batch;
+    int64_t lam_stride, x_stride, y_stride, grad_stride, exponents_stride;
 };
 
 // d_x = 1 + scale * sum_ch |g - g one column to the left|, d_y the same with the row above (kernels_var.hip, var_distances)
@@ -67,6 +75,9 @@ struct VarDistArgs {
     int32_t width, height;          // x fastest; the width is a multiple of 4
     int32_t n_guide;
     float scale;
+    // the batch, on gridDim.z: image b's guide planes are guide_stride samples behind image 0's; dx and dy hold `batch` dense planes
+    int32_t batch;
+    int64_t guide_stride;
 };
 
 // The adjoint of var_distances (kernels_var.hip, var_distances_grad), f32 guides:
@@ -81,6 +92,9 @@ struct VarDistGradArgs {
     int32_t n_guide;
     int32_t accumulate;
     float scale;
+    // the batch, on gridDim.z: strides in samples per image; gdx and gdy hold `batch` dense planes
+    int32_t batch;
+    int64_t guide_stride, grad_guide_stride;
 };
 
 int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);

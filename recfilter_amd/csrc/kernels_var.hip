@@ -48,6 +48,11 @@
 //
 // var_distances_grad (rf_var_distances_backward): the adjoint of var_distances, a gather -- a guide sample collects from the (at
 // most) four differences it takes part in, with the sign of each; one streaming launch, no atomics.
+//
+// The batch (rf_smooth_plan_create_batched): every kernel takes `batch` images in one launch, the image index on gridDim.z (beside
+// the plane in the pass kernels: z = b * n_planes + pl).  Image b's planes, weight plane, tails and carries are image 0's plus a
+// wave-uniform 64-bit offset; an image keeps its own tile grid from its row 0 and column 0 and its own borders, so its result is
+// what a launch of that image alone gives, bit for bit, and no sample of one image meets a sample of another.
 #include "kernels_var.h"
 
 #include "pixel.h"
@@ -188,36 +193,58 @@ __device__ __forceinline__ int64_t carry_index(const VarArgs &a, int t, int whic
     return (((int64_t)t * 2 + which) * a.n_planes + pl) * a.lines + line;
 }
 
+// the batch (rf_smooth_plan_create_batched): gridDim.z = batch * n_planes, image b = z / n_planes.  Everything that depends on b
+// is a wave-uniform 64-bit offset added to a base pointer once; behind that an image is tiled, and its tails and carries laid
+// out, as the only image of a launch would be (batch 1: every offset is 0).
+struct VarImage {
+    int pl;
+    int64_t b;
+};
+__device__ __forceinline__ VarImage image_of(const VarArgs &a, unsigned z) {
+    const unsigned b = z / (unsigned)a.n_planes;
+    return {(int)(z - b * (unsigned)a.n_planes), (int64_t)b};
+}
+
 template <int MODE>
-__device__ __forceinline__ void store_tails(const VarArgs &a, int t, int pl, int line, const float (&out)[kVarComponents]) {
-    if constexpr (MODE != VAR_ANTICAUSAL) a.tails[tail_index(a, t, VAR_E1, pl, line)] = out[VAR_E1];
-    if constexpr (MODE != VAR_CAUSAL) a.tails[tail_index(a, t, VAR_E2, pl, line)] = out[VAR_E2];
+__device__ __forceinline__ void store_tails(const VarArgs &a, float *tails, int t, int pl, int line, const float (&out)[kVarComponents]) {
+    if constexpr (MODE != VAR_ANTICAUSAL) tails[tail_index(a, t, VAR_E1, pl, line)] = out[VAR_E1];
+    if constexpr (MODE != VAR_CAUSAL) tails[tail_index(a, t, VAR_E2, pl, line)] = out[VAR_E2];
     if (pl != 0) return;
-    if constexpr (MODE != VAR_ANTICAUSAL) a.tails[tail_index(a, t, VAR_P1, 0, line)] = out[VAR_P1];
-    if constexpr (MODE == VAR_PAIR) a.tails[tail_index(a, t, VAR_G, 0, line)] = out[VAR_G];
-    if constexpr (MODE != VAR_CAUSAL) a.tails[tail_index(a, t, VAR_P2, 0, line)] = out[VAR_P2];
+    if constexpr (MODE != VAR_ANTICAUSAL) tails[tail_index(a, t, VAR_P1, 0, line)] = out[VAR_P1];
+    if constexpr (MODE == VAR_PAIR) tails[tail_index(a, t, VAR_G, 0, line)] = out[VAR_G];
+    if constexpr (MODE != VAR_CAUSAL) tails[tail_index(a, t, VAR_P2, 0, line)] = out[VAR_P2];
 }
 
 // ---- along y: lane = column -------------------------------------------------------------------------------------------
 // DST: the samples the final pass stores -- float, or uint8_t (the last pass of a byte image, rf_smooth_plan: sat8 of pixel.h, one
 // byte per lane and row).  Instantiated for the pair mode in the power form only.
+// The anticausal final pass sits just under the 168 registers of three waves per SIMD; with the batch offsets in its scalar
+// registers the allocator, left alone, lands just above.  Asked for three waves it stays there (no scratch: profiles/r20).
+template <int MODE, bool FINAL, bool ADJ>
+constexpr int y_waves() { return MODE == VAR_ANTICAUSAL && FINAL && !ADJ ? 3 : 1; }
+
 template <int MODE, bool FINAL, bool POWER, typename DST = float, bool ADJ = false>
-__global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(y_waves<MODE, FINAL, ADJ>()))) var_y_kernel(VarArgs a) {
     static_assert(!ADJ || MODE != VAR_PAIR, "adjoint stages: single scans");
     const int col = blockIdx.x * 64 + threadIdx.x;
     if (col >= a.width) return;                       // (no barrier below: lanes are independent)
-    const int t = blockIdx.y, pl = blockIdx.z, t0 = t * T;
+    const int t = blockIdx.y, t0 = t * T;
+    const VarImage im = image_of(a, blockIdx.z);
+    const int pl = im.pl;
     const int64_t pitch = a.width;
-    const float *src = static_cast<const float *>(a.src[pl]);
+    const float *src = static_cast<const float *>(a.src[pl]) + im.b * a.src_stride;
+    const float *weights = a.weights + im.b * a.weights_stride;
+    float *tails = a.tails + im.b * a.tails_stride;
+    const float *carry = a.carry + im.b * a.carry_stride;
     float x[T], w[T + 1];
 #pragma unroll
     for (int i = 0; i < T; i++) {
         const int r = min(t0 + i, a.height - 1);      // wave-uniform row: a scalar base and the lane's column
         x[i] = (src + r * pitch)[col];
-        w[i] = (a.weights + r * pitch)[col];
+        w[i] = (weights + r * pitch)[col];
     }
     w[T] = 0.0f;
-    if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w[T] = (a.weights + min(t0 + T, a.height - 1) * pitch)[col];
+    if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w[T] = (weights + min(t0 + T, a.height - 1) * pitch)[col];
     if constexpr (POWER) {
 #pragma unroll
         for (int i = 0; i < T; i++) w[i] = power_weight(w[i], a.log2_base);
@@ -225,14 +252,15 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
     }
     float c = 0.0f, d = 0.0f;
     if constexpr (FINAL) {
-        if constexpr (MODE != VAR_ANTICAUSAL) c = a.carry[carry_index(a, t, 0, pl, col)];
-        if constexpr (MODE != VAR_CAUSAL) d = a.carry[carry_index(a, t, 1, pl, col)];
+        if constexpr (MODE != VAR_ANTICAUSAL) c = carry[carry_index(a, t, 0, pl, col)];
+        if constexpr (MODE != VAR_CAUSAL) d = carry[carry_index(a, t, 1, pl, col)];
     }
     mask_tile(x, w, t0, a.height);
     if constexpr (ADJ) {
         if constexpr (FINAL) {
             tile_final_adjoint<MODE>(x, w, c, d);
-            float *dst = static_cast<float *>(a.dst[pl]), *lam = static_cast<float *>(a.lam[pl]);
+            float *dst = static_cast<float *>(a.dst[pl]) + im.b * a.dst_stride;
+            float *lam = a.lam[pl] ? static_cast<float *>(a.lam[pl]) + im.b * a.lam_stride : nullptr;
 #pragma unroll
             for (int i = 0; i < T; i++)
                 if (t0 + i < a.height) (dst + (t0 + i) * pitch)[col] = adjoint_result<MODE>(x, w, i);
@@ -244,18 +272,18 @@ __global__ void __launch_bounds__(64) var_y_kernel(VarArgs a) {
         } else {
             float out[kVarComponents];
             tile_tails_adjoint<MODE>(x, w, pl == 0, out);
-            store_tails<MODE>(a, t, pl, col, out);
+            store_tails<MODE>(a, tails, t, pl, col, out);
         }
     } else if constexpr (FINAL) {
         tile_final<MODE>(x, w, c, d);
-        DST *dst = static_cast<DST *>(a.dst[pl]);
+        DST *dst = static_cast<DST *>(a.dst[pl]) + im.b * a.dst_stride;
 #pragma unroll
         for (int i = 0; i < T; i++)
             if (t0 + i < a.height) (dst + (t0 + i) * pitch)[col] = PixelTraits<DST>::store(x[i]);
     } else {
         float out[kVarComponents];
         tile_tails<MODE>(x, w, pl == 0, out);
-        store_tails<MODE>(a, t, pl, col, out);
+        store_tails<MODE>(a, tails, t, pl, col, out);
     }
 }
 
@@ -313,19 +341,24 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     static_assert(!ADJ || MODE != VAR_PAIR, "adjoint stages: single scans");
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
-    const int t = blockIdx.x, pl = blockIdx.z, t0 = t * T, r0 = blockIdx.y * 64;
+    const int t = blockIdx.x, t0 = t * T, r0 = blockIdx.y * 64;
+    const VarImage im = image_of(a, blockIdx.z);
+    const int pl = im.pl;
     const int row = r0 + lane;
-    const SRC *src = static_cast<const SRC *>(a.src[pl]);
+    const SRC *src = static_cast<const SRC *>(a.src[pl]) + im.b * a.src_stride;
+    const float *weights = a.weights + im.b * a.weights_stride;
+    float *tails = a.tails + im.b * a.tails_stride;
+    const float *carry = a.carry + im.b * a.carry_stride;
     float vx[T], vw[T];
     request_tile(src, a, r0, t0, vx);
-    request_tile(a.weights, a, r0, t0, vw);
+    request_tile(weights, a, r0, t0, vw);
     float w_next = 0.0f;                             // w[t1], the next tile's first weight
-    if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w_next = a.weights[(int64_t)min(row, a.height - 1) * a.width + min(t0 + T, a.width - 1)];
+    if constexpr (MODE != VAR_CAUSAL || (ADJ && FINAL)) w_next = weights[(int64_t)min(row, a.height - 1) * a.width + min(t0 + T, a.width - 1)];
     float c = 0.0f, d = 0.0f;
     if constexpr (FINAL) {
         const int line = min(row, a.height - 1);
-        if constexpr (MODE != VAR_ANTICAUSAL) c = a.carry[carry_index(a, t, 0, pl, line)];
-        if constexpr (MODE != VAR_CAUSAL) d = a.carry[carry_index(a, t, 1, pl, line)];
+        if constexpr (MODE != VAR_ANTICAUSAL) c = carry[carry_index(a, t, 0, pl, line)];
+        if constexpr (MODE != VAR_CAUSAL) d = carry[carry_index(a, t, 1, pl, line)];
     }
     float x[T], wt[T], w[T + 1];
     transpose_in(vx, lds, x);
@@ -344,7 +377,8 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
         if constexpr (FINAL) {
             tile_final_adjoint<MODE>(x, w, c, d);
             // the way back twice: the scaled state to dst, then (where the plan wants it) the state itself to lam
-            float *planes[2] = {static_cast<float *>(a.dst[pl]), static_cast<float *>(a.lam[pl])};
+            float *planes[2] = {static_cast<float *>(a.dst[pl]) + im.b * a.dst_stride,
+                                a.lam[pl] ? static_cast<float *>(a.lam[pl]) + im.b * a.lam_stride : nullptr};
 #pragma unroll
             for (int which = 0; which < 2; which++) {
                 if (which == 1 && !planes[1]) break;      // (uniform)
@@ -368,7 +402,7 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
         } else {
             float out[kVarComponents];
             tile_tails_adjoint<MODE>(x, w, pl == 0, out);
-            if (row < a.height) store_tails<MODE>(a, t, pl, row, out);
+            if (row < a.height) store_tails<MODE>(a, tails, t, pl, row, out);
         }
     } else if constexpr (FINAL) {
         tile_final<MODE>(x, w, c, d);
@@ -376,7 +410,7 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
         for (int k = 0; k < T / 4; k++)
             *reinterpret_cast<float4 *>(lds + lane * LDS_PITCH + k * 4) = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
         __syncthreads();
-        float *dst = static_cast<float *>(a.dst[pl]);
+        float *dst = static_cast<float *>(a.dst[pl]) + im.b * a.dst_stride;
 #pragma unroll
         for (int k = 0; k < T / 4; k++) {
             const int flat = k * 64 + lane;
@@ -387,7 +421,7 @@ __global__ void __launch_bounds__(64) var_x_kernel(VarArgs a) {
     } else {
         float out[kVarComponents];
         tile_tails<MODE>(x, w, pl == 0, out);
-        if (row < a.height) store_tails<MODE>(a, t, pl, row, out);
+        if (row < a.height) store_tails<MODE>(a, tails, t, pl, row, out);
     }
 }
 
@@ -400,6 +434,8 @@ __global__ void __launch_bounds__(256) var_carry_kernel(VarArgs a) {
     const int line = blockIdx.x * 256 + threadIdx.x;
     if (line >= a.lines) return;
     const int pl = blockIdx.y, M = a.tiles;
+    const float *tails = a.tails + (int64_t)blockIdx.z * a.tails_stride;      // blockIdx.z: the image of the batch
+    float *carry = a.carry + (int64_t)blockIdx.z * a.carry_stride;
     if constexpr (MODE != VAR_ANTICAUSAL) {
         float c = 0.0f;
         for (int tb = 0; tb < M; tb += CHUNK) {
@@ -407,13 +443,13 @@ __global__ void __launch_bounds__(256) var_carry_kernel(VarArgs a) {
 #pragma unroll
             for (int j = 0; j < CHUNK; j++) {
                 const int t = min(tb + j, M - 1);
-                e[j] = a.tails[tail_index(a, t, VAR_E1, pl, line)];
-                p[j] = a.tails[tail_index(a, t, VAR_P1, 0, line)];
+                e[j] = tails[tail_index(a, t, VAR_E1, pl, line)];
+                p[j] = tails[tail_index(a, t, VAR_P1, 0, line)];
             }
 #pragma unroll
             for (int j = 0; j < CHUNK; j++) {
                 if (tb + j < M) {
-                    a.carry[carry_index(a, tb + j, 0, pl, line)] = c;
+                    carry[carry_index(a, tb + j, 0, pl, line)] = c;
                     c = __builtin_fmaf(p[j], c, e[j]);
                 }
             }
@@ -426,18 +462,18 @@ __global__ void __launch_bounds__(256) var_carry_kernel(VarArgs a) {
 #pragma unroll
             for (int j = 0; j < CHUNK; j++) {
                 const int t = max(tb - j, 0);
-                e[j] = a.tails[tail_index(a, t, VAR_E2, pl, line)];
-                p[j] = a.tails[tail_index(a, t, VAR_P2, 0, line)];
+                e[j] = tails[tail_index(a, t, VAR_E2, pl, line)];
+                p[j] = tails[tail_index(a, t, VAR_P2, 0, line)];
                 g[j] = 0.0f; c[j] = 0.0f;
                 if constexpr (MODE == VAR_PAIR) {
-                    g[j] = a.tails[tail_index(a, t, VAR_G, 0, line)];
-                    c[j] = a.carry[carry_index(a, t, 0, pl, line)];       // (this lane wrote it above)
+                    g[j] = tails[tail_index(a, t, VAR_G, 0, line)];
+                    c[j] = carry[carry_index(a, t, 0, pl, line)];       // (this lane wrote it above)
                 }
             }
 #pragma unroll
             for (int j = 0; j < CHUNK; j++) {
                 if (tb - j >= 0) {
-                    a.carry[carry_index(a, tb - j, 1, pl, line)] = d;
+                    carry[carry_index(a, tb - j, 1, pl, line)] = d;
                     d = __builtin_fmaf(p[j], d, e[j]);
                     if constexpr (MODE == VAR_PAIR) d = __builtin_fmaf(g[j], c[j], d);
                 }
@@ -464,11 +500,13 @@ template <typename G>
 __global__ void __launch_bounds__(256) var_distances_kernel(VarDistArgs a) {
     const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (c >= a.width) return;
+    const int64_t b = blockIdx.z;                    // the image of the batch: its own row 0 and column 0
+    float *const out_dx = a.dx + b * ((int64_t)a.width * a.height), *const out_dy = a.dy + b * ((int64_t)a.width * a.height);
     for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
         const int64_t own_at = (int64_t)r * a.width + c, up_at = (int64_t)max(r - 1, 0) * a.width + c;
         float sx[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sy[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int ch = 0; ch < a.n_guide; ch++) {
-            const G *g = static_cast<const G *>(a.guide[ch]);
+            const G *g = static_cast<const G *>(a.guide[ch]) + b * a.guide_stride;
             float own[4], up[4];
             load_chunk(g, own_at, own);
             load_chunk(g, up_at, up);
@@ -485,8 +523,8 @@ __global__ void __launch_bounds__(256) var_distances_kernel(VarDistArgs a) {
             dx[j] = (c + j == 0) ? 1.0f : 1.0f + a.scale * sx[j];
             dy[j] = (r == 0) ? 1.0f : 1.0f + a.scale * sy[j];
         }
-        *reinterpret_cast<float4 *>(a.dx + own_at) = make_float4(dx[0], dx[1], dx[2], dx[3]);
-        *reinterpret_cast<float4 *>(a.dy + own_at) = make_float4(dy[0], dy[1], dy[2], dy[3]);
+        *reinterpret_cast<float4 *>(out_dx + own_at) = make_float4(dx[0], dx[1], dx[2], dx[3]);
+        *reinterpret_cast<float4 *>(out_dy + own_at) = make_float4(dy[0], dy[1], dy[2], dy[3]);
     }
 }
 
@@ -509,25 +547,28 @@ template <int DIM, bool CAUSAL, bool POWER = false>
 __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
     const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (c >= a.width) return;
+    const int64_t b = blockIdx.z;                    // the image of the batch
+    float *const grad = a.grad + b * a.grad_stride;
     for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
         const int64_t own_at = (int64_t)r * a.width + c;
         const int64_t before_at = DIM == 0 ? own_at - (c > 0 ? 1 : 0) : (int64_t)max(r - 1, 0) * a.width + c;
         float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int pl = 0; pl < a.n_planes; pl++) {
+            const float *const p_lam = a.lam[pl] + b * a.lam_stride, *const p_x = a.x[pl] + b * a.x_stride, *const p_y = a.y[pl] + b * a.y_stride;
             float lam[4], x[4], y[4], before[4], term[4];
             if constexpr (CAUSAL) {              // lam[i] * (y[i-1] - x[i])
-                load_chunk(a.lam[pl], own_at, lam);
-                load_chunk(a.x[pl], own_at, x);
-                if constexpr (DIM == 0) load_chunk(a.y[pl], own_at, y);
-                load_previous<DIM>(a.y[pl], own_at, before_at, y, before);
+                load_chunk(p_lam, own_at, lam);
+                load_chunk(p_x, own_at, x);
+                if constexpr (DIM == 0) load_chunk(p_y, own_at, y);
+                load_previous<DIM>(p_y, own_at, before_at, y, before);
 #pragma unroll
                 for (int j = 0; j < 4; j++) term[j] = lam[j] * (before[j] - x[j]);
             } else {                             // lam[i-1] * (y[i] - x[i-1])
-                load_chunk(a.y[pl], own_at, y);
-                if constexpr (DIM == 0) { load_chunk(a.lam[pl], own_at, lam); load_chunk(a.x[pl], own_at, x); }
-                load_previous<DIM>(a.lam[pl], own_at, before_at, lam, before);
+                load_chunk(p_y, own_at, y);
+                if constexpr (DIM == 0) { load_chunk(p_lam, own_at, lam); load_chunk(p_x, own_at, x); }
+                load_previous<DIM>(p_lam, own_at, before_at, lam, before);
                 float x_before[4];
-                load_previous<DIM>(a.x[pl], own_at, before_at, x, x_before);
+                load_previous<DIM>(p_x, own_at, before_at, x, x_before);
 #pragma unroll
                 for (int j = 0; j < 4; j++) term[j] = before[j] * (y[j] - x_before[j]);
             }
@@ -536,7 +577,7 @@ __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
         }
         if constexpr (POWER) {                   // dL/dd = (w * ln base) * dL/dw, w as the scans form it
             float d[4];
-            load_chunk(a.exponents, own_at, d);
+            load_chunk(a.exponents + b * a.exponents_stride, own_at, d);
 #pragma unroll
             for (int j = 0; j < 4; j++) s[j] = (power_weight(d[j], a.log2_base) * a.ln_base) * s[j] + 0.0f;      // (w = 0: +0, not -0)
         }
@@ -544,11 +585,11 @@ __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
         for (int j = 0; j < 4; j++) s[j] = (DIM == 0 ? c + j == 0 : r == 0) ? 0.0f : s[j];
         if (a.accumulate) {
             float old[4];
-            load_chunk(a.grad, own_at, old);
+            load_chunk(grad, own_at, old);
 #pragma unroll
             for (int j = 0; j < 4; j++) s[j] = old[j] + s[j];
         }
-        *reinterpret_cast<float4 *>(a.grad + own_at) = make_float4(s[0], s[1], s[2], s[3]);
+        *reinterpret_cast<float4 *>(grad + own_at) = make_float4(s[0], s[1], s[2], s[3]);
     }
 }
 
@@ -564,20 +605,22 @@ __global__ void __launch_bounds__(256) var_distances_grad_kernel(VarDistGradArgs
     const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (c >= a.width) return;
     const bool has_right = c + 4 < a.width;
+    const int64_t b = blockIdx.z;                    // the image of the batch: its own borders
+    const float *const gdx = a.gdx + b * ((int64_t)a.width * a.height), *const gdy = a.gdy + b * ((int64_t)a.width * a.height);
     for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
         const int64_t own_at = (int64_t)r * a.width + c, up_at = (int64_t)max(r - 1, 0) * a.width + c;
         const int64_t down_at = (int64_t)min(r + 1, a.height - 1) * a.width + c;
         const int64_t left_at = own_at - (c > 0 ? 1 : 0), right_at = own_at + (has_right ? 4 : 3);
         const bool has_down = r + 1 < a.height;
         float gx_own[4], gx[5], gy[4], gy_down[4];      // gx[4]: the gradient of the difference to the right of the chunk
-        load_chunk(a.gdx, own_at, gx_own);
+        load_chunk(gdx, own_at, gx_own);
 #pragma unroll
         for (int j = 0; j < 4; j++) gx[j] = gx_own[j];
-        gx[4] = a.gdx[right_at];
-        load_chunk(a.gdy, own_at, gy);
-        load_chunk(a.gdy, down_at, gy_down);
+        gx[4] = gdx[right_at];
+        load_chunk(gdy, own_at, gy);
+        load_chunk(gdy, down_at, gy_down);
         for (int ch = 0; ch < a.n_guide; ch++) {
-            const float *g = a.guide[ch];
+            const float *g = a.guide[ch] + b * a.guide_stride;
             float chunk[4], own[6], up[4], down[4], out[4];      // own[0]: the element to the left, own[5]: the one to the right
             load_chunk(g, own_at, chunk);
 #pragma unroll
@@ -594,7 +637,7 @@ __global__ void __launch_bounds__(256) var_distances_grad_kernel(VarDistGradArgs
                 const float from_down = has_down ? signed_by(down[j] - own[j + 1], gy_down[j]) : 0.0f;
                 out[j] = a.scale * (((from_left - from_right) + from_up) - from_down);
             }
-            float *dst = a.grad_guide[ch];
+            float *dst = a.grad_guide[ch] + b * a.grad_guide_stride;
             if (a.accumulate) {
                 float old[4];
                 load_chunk(dst, own_at, old);
@@ -616,8 +659,8 @@ template <bool FINAL>
 int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
     const int cross = dim == 0 ? a.height : a.width;          // lines, 64 per workgroup
     const dim3 block(64);
-    const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)a.n_planes)
-                               : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)a.n_planes);
+    const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)(a.batch * a.n_planes))
+                               : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)(a.batch * a.n_planes));
     if (a.adjoint) {
         const char *what = FINAL ? (dim == 0 ? "var_adj_pass2_x" : "var_adj_pass2_y") : (dim == 0 ? "var_adj_tails_x" : "var_adj_tails_y");
         if (a.src_u8 || a.dst_u8 || a.mode == VAR_PAIR) {
@@ -667,7 +710,7 @@ int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream) { return lau
 int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream) { return launch_pass<true>(a, dim, stream); }
 
 int launch_var_carry(const VarArgs &a, hipStream_t stream) {
-    const dim3 grid((unsigned)((a.lines + 255) / 256), (unsigned)a.n_planes), block(256);
+    const dim3 grid((unsigned)((a.lines + 255) / 256), (unsigned)a.n_planes, (unsigned)a.batch), block(256);
     switch (a.mode) {
         case VAR_CAUSAL: hipLaunchKernelGGL((var_carry_kernel<VAR_CAUSAL>), grid, block, 0, stream, a); break;
         case VAR_ANTICAUSAL: hipLaunchKernelGGL((var_carry_kernel<VAR_ANTICAUSAL>), grid, block, 0, stream, a); break;
@@ -677,14 +720,14 @@ int launch_var_carry(const VarArgs &a, hipStream_t stream) {
 }
 
 int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream) {
-    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)a.batch), block(256);
     if (guide_u8) hipLaunchKernelGGL((var_distances_kernel<uint8_t>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var_distances_kernel<float>), grid, block, 0, stream, a);
     return launched("var_distances");
 }
 
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream) {
-    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)a.batch), block(256);
 #define RF_VAR_LAUNCH_GRAD(POWER)                                                                                   \
     if (dim == 0) {                                                                                                 \
         if (causal) hipLaunchKernelGGL((var_grad_kernel<0, true, POWER>), grid, block, 0, stream, a);               \
@@ -699,7 +742,7 @@ int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stre
 }
 
 int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream) {
-    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535)), block(256);
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)a.batch), block(256);
     hipLaunchKernelGGL(var_distances_grad_kernel, grid, block, 0, stream, a);
     return launched("var_distances_grad");
 }

@@ -12,8 +12,13 @@
 // differentiate through the distances it first reruns iterations 0 .. K-2 into checkpoint planes (the fused pair stages), then
 // per iteration in reverse order the inner plan's adjoint WITH both exponent gradients on that iteration's input -- the first
 // stores into gd_x, gd_y, the later ones add -- and one var_distances_grad launch takes gd_x, gd_y to the guide.
+//
+// A batched plan (rf_smooth_plan_create_batched) is the same sequence: every launch takes all the images on gridDim.z, each image
+// with its own distance planes, tails, carries and working planes, laid out image after image as a single-image plan lays out
+// its one.  The launch count does not depend on the batch.  The caller's planes are checked per (image, plane) extent, sorted.
 #include "plan_smooth.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 
@@ -58,12 +63,94 @@ int validate(const rf_smooth_desc *d) {
 bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
 bool overlap(const void *a, const void *b, size_t n) { return overlap((uintptr_t)a, n, (uintptr_t)b, n); }
 
+// the refusals of rf_smooth_plan_create_batched that concern the batch alone, in the order recfilter_amd.h documents
+int validate_batch(const rf_smooth_desc *d, const rf_smooth_batch_desc *b) {
+    if (b->batch < 1 || b->batch > RF_SMOOTH_MAX_BATCH) { set_error("batch must be 1..%d (got %d)", RF_SMOOTH_MAX_BATCH, b->batch); return RF_ERR_INVALID_ARG; }
+    if (b->image_stride % 4 != 0 || b->guide_stride % 4 != 0) {
+        set_error("image_stride = %lld and guide_stride = %lld must be multiples of 4 samples: every image's planes keep the alignment of image 0's",
+                  (long long)b->image_stride, (long long)b->guide_stride);
+        return RF_ERR_INVALID_ARG;
+    }
+    // (extents the plain validation refuses anyway form no product here)
+    const bool sane = d->width >= 1 && d->height >= 1 && d->width <= var_max_extent() && d->height <= var_max_extent();
+    const int64_t samples = sane ? d->width * d->height : 0;
+    if (b->image_stride < samples || b->image_stride < 0) {
+        set_error("image_stride = %lld is below one plane's %lld samples", (long long)b->image_stride, (long long)samples);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->n_guide == 0 && b->guide_stride != 0) {
+        set_error("guide_stride must be 0 where the image guides itself (n_guide = 0; got %lld)", (long long)b->guide_stride);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->n_guide > 0 && b->guide_stride < std::max<int64_t>(samples, 1)) {
+        set_error("guide_stride = %lld is below one plane's %lld samples (every image has its own guide: a guide shared by the batch is not supported)",
+                  (long long)b->guide_stride, (long long)samples);
+        return RF_ERR_INVALID_ARG;
+    }
+    return RF_OK;
+}
+
+// ---- the aliasing rules of a batched call, per (image, plane) extent ------------------------------------------------------------
+// The planes of NCHW tensors interleave (image b's plane 1 lies between image b's plane 0 and image b+1's plane 0), so an array is
+// not one span.  Every extent [planes[pl] + b * stride, + one plane) of every array goes into one list, sorted by its start;
+// one sweep then holds, for the read and for the written extents seen so far, the two that end last.  An extent overlaps an
+// earlier one of a class exactly when the one ending last does -- or, where that is the one extent it may be (in place: the same
+// (image, plane) of the partner array, the same address), the second.  E extents: O(E log E), no pair is formed.
+struct ExtentArray {
+    const char *name;
+    const void *const *planes;
+    int n;
+    int64_t stride_bytes;
+    size_t bytes;            // of one plane
+    bool written;
+    int partner;             // the array whose extent of the same (image, plane) may be this one exactly, or -1
+};
+struct Extent {
+    uintptr_t lo, hi;
+    int32_t array, b, pl;
+};
+
+int check_extents(const ExtentArray *arrays, int n_arrays, int batch) {
+    std::vector<Extent> ext;
+    for (int k = 0; k < n_arrays; k++)
+        for (int b = 0; b < batch; b++)
+            for (int pl = 0; pl < arrays[k].n; pl++) {
+                const uintptr_t lo = (uintptr_t)arrays[k].planes[pl] + (uintptr_t)((int64_t)b * arrays[k].stride_bytes);
+                ext.push_back({lo, lo + arrays[k].bytes, k, b, pl});
+            }
+    std::sort(ext.begin(), ext.end(), [](const Extent &x, const Extent &y) { return x.lo < y.lo; });
+    const Extent *last[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // [written][0: ends last, 1: the next]
+    auto in_place = [&](const Extent &x, const Extent &y) {
+        return arrays[x.array].partner == y.array && x.b == y.b && x.pl == y.pl && x.lo == y.lo && x.hi == y.hi;
+    };
+    for (const Extent &x : ext) {
+        const bool w = arrays[x.array].written;
+        for (int cls = 0; cls < 2; cls++) {
+            if (!w && cls == 0) continue;                  // (two read extents may overlap)
+            const Extent *y = last[cls][0];
+            if (y && in_place(x, *y)) y = last[cls][1];
+            if (y && y->hi > x.lo) {
+                const Extent &rd = w ? *y : x, &wr = w ? x : *y;      // (both written: in the order met)
+                set_error("%s plane %d of image %d overlaps %s plane %d of image %d: a plane that is written is disjoint from every other plane of the call, "
+                          "or is exactly the same plane of the same image it is computed from",
+                          arrays[wr.array].name, wr.pl, wr.b, arrays[rd.array].name, rd.pl, rd.b);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+        const Extent **slot = last[w ? 1 : 0];
+        if (!slot[0] || x.hi > slot[0]->hi) { slot[1] = slot[0]; slot[0] = &x; }
+        else if (!slot[1] || x.hi > slot[1]->hi) slot[1] = &x;
+    }
+    return RF_OK;
+}
+
 }  // namespace
 
-int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out) {
+int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out) {
     if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     *out = nullptr;
-    int rc = validate(desc);
+    int rc = batch ? validate_batch(desc, batch) : RF_OK;
+    if (rc == RF_OK) rc = validate(desc);
     if (rc != RF_OK) return rc;
     std::unique_ptr<rf_smooth_plan> plan(new rf_smooth_plan);
     plan->width = desc->width;
@@ -74,6 +161,11 @@ int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out) {
     plan->image_u8 = desc->image_u8 != 0;
     plan->guide_u8 = desc->guide_u8 != 0;
     plan->host_only = desc->device == RF_DEVICE_HOST_ONLY;
+    if (batch) {
+        plan->batch = batch->batch;
+        plan->image_stride = batch->image_stride;
+        plan->guide_stride = batch->guide_stride;
+    }
     // a byte guide means that guide divided by 255 (a separate uint8 guide, or a uint8 image guiding itself)
     const bool bytes_guide = desc->n_guide > 0 ? plan->guide_u8 : plan->image_u8;
     plan->scale = (float)(desc->sigma_s / desc->sigma_r / (bytes_guide ? 255.0 : 1.0));
@@ -103,12 +195,12 @@ int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out) {
     vd.device = desc->device;
     vd.flags = 0;
     rf_var_plan *inner = nullptr;
-    rc = build_var_plan(&vd, &inner);      // (the device checks, and the tails and the carries)
+    rc = build_var_plan(&vd, &inner, plan->batch);      // (the device checks, and the tails and the carries)
     if (rc != RF_OK) return rc;
     plan->inner.reset(inner);
     plan->device = inner->device;
     const size_t plane_bytes = (size_t)(desc->width * desc->height) * sizeof(float);
-    plan->planes_bytes = plane_bytes * (size_t)(2 + (plan->image_u8 ? desc->n_planes : 0));
+    plan->planes_bytes = plane_bytes * (size_t)(2 + (plan->image_u8 ? desc->n_planes : 0)) * (size_t)plan->batch;
     if (!plan->host_only) {
         RF_HIP_CHECK(hipSetDevice(plan->device));
         if (hipMalloc((void **)&plan->planes, plan->planes_bytes) != hipSuccess) {
@@ -160,7 +252,16 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
     }
     // a stage has loaded its tile before it stores, so a plane may be filtered in place; any other overlap of an input with an output
     // is read after another workgroup's store
-    for (int pl = 0; pl < plan->n_planes; pl++)
+    const int B = plan->batch;
+    const int64_t image_stride = plan->image_stride, guide_stride = plan->guide_stride;
+    if (B > 1) {
+        const int64_t stride_bytes = image_stride * (int64_t)(plan->image_u8 ? 1 : sizeof(float));
+        const ExtentArray arrays[2] = {{"input", image_planes, plan->n_planes, stride_bytes, image_bytes, false, 1},
+                                       {"output", (const void *const *)out_planes, plan->n_planes, stride_bytes, image_bytes, true, 0}};
+        int rc = check_extents(arrays, 2, B);
+        if (rc != RF_OK) return rc;
+    }
+    for (int pl = 0; pl < plan->n_planes && B == 1; pl++)
         for (int q = 0; q < plan->n_planes; q++) {
             if (pl == q && image_planes[pl] == out_planes[q]) continue;
             if (overlap((uintptr_t)image_planes[pl], image_bytes, (uintptr_t)out_planes[q], image_bytes)) {
@@ -190,15 +291,17 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
         return RF_OK;
     };
-    float *dx = plan->planes, *dy = dx + samples;
+    float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each
     // the distances first, on the same stream: guide planes may be output planes
     const bool self = plan->n_guide == 0;
     int rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
-                               plan->width, plan->height, plan->scale, dx, dy, plan->device, stream);
+                               plan->width, plan->height, plan->scale, dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
     if (rc == RF_OK) rc = mark();
     if (rc != RF_OK) return rc;
     void *work[RF_MAX_PLANES] = {};
-    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(dy + samples * (size_t)(1 + pl)) : out_planes[pl];
+    // byte images: [image][plane] behind the distance planes
+    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(dy + samples * (size_t)(B + pl)) : out_planes[pl];
+    const int64_t work_stride = plan->image_u8 ? (int64_t)samples * plan->n_planes : image_stride;
     const void *const weights[2] = {dx, dy};
     const int K = plan->iterations;
     for (int k = 0; k < K; k++) {
@@ -208,6 +311,10 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         io.work = work;
         io.out = k == K - 1 ? out_planes : work;
         io.out_u8 = k == K - 1 && plan->image_u8;
+        io.in_stride = k == 0 ? image_stride : work_stride;
+        io.work_stride = work_stride;
+        io.out_stride = k == K - 1 ? image_stride : work_stride;
+        io.weights_stride = (int64_t)samples;
         const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
         rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, mark);
         if (rc != RF_OK) return rc;
@@ -269,7 +376,23 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         if (i < P) std::snprintf(buf, n, "grad_image plane %d", i);
         else std::snprintf(buf, n, "gradient of guide plane %d", i - P);
     };
-    for (int i = 0; i < n_written; i++) {
+    const int B = plan->batch;
+    const int64_t image_stride = plan->image_stride, guide_stride = plan->guide_stride;
+    if (B > 1) {
+        const int64_t image_stride_bytes = image_stride * (int64_t)sizeof(float), guide_stride_bytes = guide_stride * (int64_t)(plan->guide_u8 ? 1 : sizeof(float));
+        ExtentArray arrays[5];
+        int n = 0, grad_out_at, grad_image_at;
+        if (G > 0) arrays[n++] = {"guide", guide_planes, G, guide_stride_bytes, guide_bytes, false, -1};
+        if (need_image) arrays[n++] = {"image", image_planes, P, image_stride_bytes, plane_bytes, false, -1};
+        grad_out_at = n;
+        grad_image_at = n + 1;
+        arrays[n++] = {"grad_out", grad_out_planes, P, image_stride_bytes, plane_bytes, false, grad_image_at};
+        arrays[n++] = {"grad_image", (const void *const *)grad_image_planes, P, image_stride_bytes, plane_bytes, true, grad_out_at};
+        if (with_guide_grad) arrays[n++] = {"gradient of guide", (const void *const *)grad_guide_planes, G, guide_stride_bytes, plane_bytes, true, -1};
+        int rc = check_extents(arrays, n, B);
+        if (rc != RF_OK) return rc;
+    }
+    for (int i = 0; i < n_written && B == 1; i++) {
         const void *o = written(i);
         char name[64];
         written_name(i, name, sizeof name);
@@ -333,21 +456,25 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         return RF_OK;
     };
     const std::function<void()> skip = [] {};      // (both exponent gradients are always formed: nothing is skipped)
-    float *dx = plan->planes, *dy = dx + samples;
+    float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each, as the gradients' gd_x, gd_y below
     int rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
-                               dx, dy, plan->device, stream);
+                               dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
     if (rc == RF_OK) rc = mark();
     if (rc != RF_OK) return rc;
     const void *const exponents[2] = {dx, dy};
-    float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples : nullptr;
-    // the output of iteration k, k = 0 .. K-2
+    float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples * (size_t)B : nullptr;
+    // the output of iteration k, k = 0 .. K-2: [iteration][image][plane]
+    const int64_t checkpoint_stride = (int64_t)samples * P;
     void *checkpoints[RF_SMOOTH_MAX_ITERATIONS][RF_MAX_PLANES] = {};
     if (edges == 1) {
         for (int k = 0; k + 1 < K; k++) {
-            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = gdy + samples * (size_t)(1 + k * P + pl);
+            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = gdy + samples * ((size_t)B + (size_t)k * (size_t)B * P + pl);
             VarIo io{};
             io.in = k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
             io.work = io.out = checkpoints[k];
+            io.in_stride = k == 0 ? image_stride : checkpoint_stride;
+            io.work_stride = io.out_stride = checkpoint_stride;
+            io.weights_stride = (int64_t)samples;
             const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
             rc = launch_var_stages(inner, io, exponents, l, stream, mark);
             if (rc != RF_OK) return rc;
@@ -368,13 +495,17 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         io.log2_base = l;
         io.ln_base = c;
         io.holds_sum = holds_sum;
+        io.in_stride = k == 0 ? image_stride : checkpoint_stride;
+        io.weights_stride = io.grad_weights_stride = (int64_t)samples;
+        io.grad_out_stride = io.grad_in_stride = image_stride;
         rc = launch_var_backward(inner, io, stream, mark, skip);
         if (rc != RF_OK) return rc;
     }
     if (edges == 1) {
         // a separate guide: stored; the image guiding itself: added to the image gradient the scans have just left there
         rc = run_var_distances_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->scale, gdx, gdy,
-                                        self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream);
+                                        self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream, B,
+                                        self ? image_stride : guide_stride, self ? image_stride : guide_stride);
         if (rc == RF_OK) rc = mark();
         if (rc != RF_OK) return rc;
     }

@@ -11,6 +11,10 @@
 struct rf_smooth_plan {
     int64_t width = 0, height = 0;
     int n_planes = 1, n_guide = 0, iterations = 1;
+    // rf_smooth_plan_create_batched: `batch` images per call, every launch taking all of them (gridDim.z).  The callers' arrays name
+    // image 0's planes; image b's are image_stride / guide_stride samples further per b.  rf_smooth_plan_create: 1, strides unused.
+    int batch = 1;
+    int64_t image_stride = 0, guide_stride = 0;
     bool image_u8 = false, guide_u8 = false;
     int device = 0;
     bool host_only = false;
@@ -18,23 +22,25 @@ struct rf_smooth_plan {
     std::vector<float> bases;                // a_k
     std::vector<float> log2_bases;           // (float)log2((double)a_k): what rf_var_plan_execute_power forms from a_k
     std::unique_ptr<rf_var_plan> inner;      // +x -x +y -y on two exponent planes: two pair stages, the tails and the carries
-    // one allocation: d_x, d_y, then (byte images) n_planes f32 working planes
+    // one allocation: d_x (one plane per image), d_y (the same), then (byte images) n_planes f32 working planes per image
     float *planes = nullptr;
     size_t planes_bytes = 0;
     std::vector<std::string> names;          // "var_distances", then the inner plan's six per iteration
     size_t workspace_bytes() const { return planes_bytes + inner->workspace_bytes(); }
     // rf_smooth_plan_backward: the launch names with the distances held constant ([0]) and differentiated ([1]); [1] needs the
     // gradients of d_x and d_y and the outputs of iterations 0 .. K-2 -- 2 + (K - 1) * n_planes f32 planes, allocated by the first
-    // call that needs them -- and the inner plan's (4 + 1) * n_planes
+    // call that needs them -- and the inner plan's (4 + 1) * n_planes; all of it per image: gd_x [image], gd_y [image], then
+    // [iteration][image][plane]
     std::vector<std::string> backward_names[2];
     float *grad_planes = nullptr;
-    size_t own_backward_bytes() const { return (size_t)(2 + (iterations - 1) * n_planes) * (size_t)(width * height) * sizeof(float); }
+    size_t own_backward_bytes() const { return (size_t)batch * (size_t)(2 + (iterations - 1) * n_planes) * (size_t)(width * height) * sizeof(float); }
     size_t backward_workspace_bytes(bool edges) const { return edges ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
     ~rf_smooth_plan();
 };
 
 namespace rf {
-int build_smooth_plan(const rf_smooth_desc *desc, rf_smooth_plan **out);
+// batch == nullptr: rf_smooth_plan_create; else rf_smooth_plan_create_batched (which has refused a null one)
+int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out);
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
 int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
                     hipStream_t stream, float *ms_out);

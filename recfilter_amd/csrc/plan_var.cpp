@@ -21,6 +21,10 @@
 // (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
 //
 // run_var_distances_backward: the adjoint of run_var_distances, one launch.
+//
+// A plan may hold a batch (build_var_plan's third argument; plan_smooth.cpp only, the public entry points build 1): tails,
+// carries and the backward's planes are then `batch` images' worth, image after image, and the launchers above carry the batch
+// and the strides from image to image (VarIo, VarBackwardIo) to the kernels, whose grids take all images at once.
 #include "plan_var.h"
 
 #include <algorithm>
@@ -77,7 +81,7 @@ int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
 
 int64_t var_max_extent() { return kVarMaxExtent; }
 
-int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
+int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     *out = nullptr;
     int rc = validate(desc);
@@ -95,6 +99,7 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
     plan->height = desc->extent[1];
     plan->n_planes = desc->n_planes;
     plan->n_weights = desc->n_weights;
+    plan->batch = batch;
     plan->device = host_only ? 0 : device;
     plan->host_only = host_only;
     // Stages: the scans are taken in runs along one dimension.  A run that is exactly {+d, -d} on one weight plane is ONE fused
@@ -142,8 +147,8 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out) {
     int64_t slots = 0;
     if (used[0]) slots = std::max(slots, tiles_of(plan->width) * plan->height);
     if (used[1]) slots = std::max(slots, tiles_of(plan->height) * plan->width);
-    plan->tails_bytes = (size_t)(slots * kVarComponents * plan->n_planes) * sizeof(float);
-    plan->carry_bytes = (size_t)(slots * 2 * plan->n_planes) * sizeof(float);
+    plan->tails_bytes = (size_t)(slots * kVarComponents * plan->n_planes) * sizeof(float) * (size_t)batch;
+    plan->carry_bytes = (size_t)(slots * 2 * plan->n_planes) * sizeof(float) * (size_t)batch;
     if (!host_only) {
         RF_HIP_CHECK(hipSetDevice(device));
         if (hipMalloc((void **)&plan->tails, plan->tails_bytes) != hipSuccess || hipMalloc((void **)&plan->carry, plan->carry_bytes) != hipSuccess) {
@@ -238,6 +243,12 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
         a.weights = (const float *)weight_planes[st.weights];
         a.tails = plan->tails;
         a.carry = plan->carry;
+        a.batch = plan->batch;
+        a.src_stride = s == 0 ? io.in_stride : io.work_stride;
+        a.dst_stride = s == last ? io.out_stride : io.work_stride;
+        a.weights_stride = io.weights_stride;
+        a.tails_stride = plan->image_tails_floats();
+        a.carry_stride = plan->image_carry_floats();
         a.width = (int32_t)plan->width;
         a.height = (int32_t)plan->height;
         a.n_planes = plan->n_planes;
@@ -272,6 +283,9 @@ VarArgs scan_args(const rf_var_plan *plan, const rf_var_scan_desc &sc, const voi
     a.tiles = (int32_t)tiles_of(sc.dim == 0 ? plan->width : plan->height);
     a.lines = (int32_t)(sc.dim == 0 ? plan->height : plan->width);
     a.mode = mode;
+    a.batch = plan->batch;
+    a.tails_stride = plan->image_tails_floats();
+    a.carry_stride = plan->image_carry_floats();
     return a;
 }
 
@@ -416,10 +430,13 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
     const int P = plan->n_planes, S = (int)plan->scans.size();
     const bool with_weights = io.grad_weights != nullptr, power = io.log2_base != nullptr;
     const size_t plane_floats = (size_t)(plan->width * plan->height);
-    auto saved = [&](int scan, int pl) { return plan->grad_planes + ((size_t)scan * P + pl) * plane_floats; };      // scan == S: the state
+    // [scan][image][plane]; scan == S: the state
+    auto saved = [&](int scan, int pl) { return plan->grad_planes + ((size_t)scan * (size_t)plan->batch * P + pl) * plane_floats; };
+    const int64_t saved_stride = (int64_t)P * (int64_t)plane_floats;
     auto form = [&](VarArgs &a, const rf_var_scan_desc &sc) {
         a.power = power ? 1 : 0;
         a.log2_base = power ? io.log2_base[sc.weights] : 0.0f;
+        a.weights_stride = io.weights_stride;
     };
     int rc = RF_OK;
     if (with_weights) {
@@ -432,6 +449,8 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
                 a.src[pl] = q == 0 ? io.in[pl] : saved(q - 1, pl);
                 a.dst[pl] = saved(q, pl);
             }
+            a.src_stride = q == 0 ? io.in_stride : saved_stride;
+            a.dst_stride = saved_stride;
             rc = launch_var_tails(a, sc.dim, stream);
             if (rc == RF_OK) rc = mark();
             if (rc == RF_OK) rc = launch_var_carry(a, stream);
@@ -455,6 +474,9 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
             a.dst[pl] = io.grad_in[pl];
             a.lam[pl] = grad ? saved(S, pl) : nullptr;
         }
+        a.src_stride = q == S - 1 ? io.grad_out_stride : io.grad_in_stride;
+        a.dst_stride = io.grad_in_stride;
+        a.lam_stride = saved_stride;
         rc = launch_var_tails(a, sc.dim, stream);
         if (rc == RF_OK) rc = mark();
         if (rc == RF_OK) rc = launch_var_carry(a, stream);
@@ -473,6 +495,11 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
             g.width = (int32_t)plan->width;
             g.height = (int32_t)plan->height;
             g.n_planes = P;
+            g.batch = plan->batch;
+            g.lam_stride = g.y_stride = saved_stride;
+            g.x_stride = q == 0 ? io.in_stride : saved_stride;
+            g.grad_stride = io.grad_weights_stride;
+            g.exponents_stride = io.weights_stride;
             g.accumulate = touched[sc.weights] ? 1 : 0;
             if (power) {
                 g.exponents = (const float *)io.weights[sc.weights];
@@ -490,7 +517,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
 }
 
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
-                      void *dx, void *dy, int32_t device, hipStream_t stream) {
+                      void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch, int64_t guide_stride) {
     if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
     if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
     if (!guide_planes || !dx || !dy) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
@@ -514,8 +541,9 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
         }
     const size_t samples = (size_t)(width * height), out_bytes = samples * sizeof(float), guide_bytes = samples * (guide_u8 ? 1 : sizeof(float));
     auto overlap = [](uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; };
-    if (overlap((uintptr_t)dx, out_bytes, (uintptr_t)dy, out_bytes)) { set_error("dx overlaps dy"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
+    if (overlap((uintptr_t)dx, out_bytes * (size_t)batch, (uintptr_t)dy, out_bytes * (size_t)batch)) { set_error("dx overlaps dy"); return RF_ERR_INVALID_ARG; }
+    // (a batch comes from plan_smooth.cpp: dx and dy are the plan's own planes, which no plane of a caller overlaps)
+    for (int ch = 0; ch < n_guide && batch == 1; ch++)
         if (overlap((uintptr_t)dx, out_bytes, (uintptr_t)guide_planes[ch], guide_bytes) ||
             overlap((uintptr_t)dy, out_bytes, (uintptr_t)guide_planes[ch], guide_bytes)) {
             set_error("guide plane %d overlaps dx or dy: a lane reads its neighbours' samples", ch);
@@ -530,11 +558,14 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
     a.height = (int32_t)height;
     a.n_guide = n_guide;
     a.scale = scale;
+    a.batch = batch;
+    a.guide_stride = guide_stride;
     return launch_var_distances(a, guide_u8 != 0, stream);
 }
 
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
-                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream) {
+                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
+                               int32_t batch, int64_t guide_stride, int64_t grad_guide_stride) {
     if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
     if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
     if (!guide_planes || !grad_dx || !grad_dy || !grad_guide_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
@@ -557,8 +588,10 @@ int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide,
             return RF_ERR_INVALID_ARG;
         }
     // a gradient plane is written while other lanes still read: it overlaps nothing that is read and no other gradient plane
+    // (a batch comes from plan_smooth.cpp, which has checked every extent of the caller's against every other, sorted; grad_dx and
+    // grad_dy are then the plan's own planes)
     const size_t bytes = (size_t)(width * height) * sizeof(float);
-    for (int ch = 0; ch < n_guide; ch++) {
+    for (int ch = 0; ch < n_guide && batch == 1; ch++) {
         const void *o = grad_guide_planes[ch];
         if (overlap(o, bytes, grad_dx, bytes) || overlap(o, bytes, grad_dy, bytes)) {
             set_error("gradient of guide plane %d overlaps grad_dx or grad_dy: a lane reads its neighbours' samples", ch);
@@ -588,6 +621,9 @@ int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide,
     a.n_guide = n_guide;
     a.accumulate = accumulate;
     a.scale = scale;
+    a.batch = batch;
+    a.guide_stride = guide_stride;
+    a.grad_guide_stride = grad_guide_stride;
     return launch_var_distances_grad(a, stream);
 }
 

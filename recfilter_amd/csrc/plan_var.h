@@ -19,6 +19,9 @@ struct rf_var_stage {
 struct rf_var_plan {
     int64_t width = 0, height = 0;
     int n_planes = 1, n_weights = 1;
+    // images per launch (internal: rf_smooth_plan_create_batched; the public rf_var_plan_* entry points build 1).  Every workspace
+    // below is `batch` times one image's, image after image, each in the single-image layout.
+    int batch = 1;
     int device = 0;
     bool host_only = false;
     std::vector<rf_var_stage> stages;
@@ -27,20 +30,23 @@ struct rf_var_plan {
     float *tails = nullptr, *carry = nullptr;
     size_t tails_bytes = 0, carry_bytes = 0;
     size_t workspace_bytes() const { return tails_bytes + carry_bytes; }
+    int64_t image_tails_floats() const { return (int64_t)(tails_bytes / sizeof(float)) / batch; }
+    int64_t image_carry_floats() const { return (int64_t)(carry_bytes / sizeof(float)) / batch; }
     // rf_var_plan_backward: the scans as described (adjoint stages are single scans), the launch names without ([0]) and with
     // ([1]) weight gradients, and the planes the weight gradients need -- every scan's output (n_scans * n_planes) and one
-    // scan's adjoint state (n_planes) -- allocated by the first call that asks for a weight gradient
+    // scan's adjoint state (n_planes) -- allocated by the first call that asks for a weight gradient.  [scan][image][plane]: the
+    // planes of one scan are n_planes * width * height samples from image to image.
     std::vector<rf_var_scan_desc> scans;
     std::vector<std::string> backward_names[2];
     float *grad_planes = nullptr;
     size_t backward_workspace_bytes(bool with_weight_gradients) const {
-        return with_weight_gradients ? (scans.size() + 1) * (size_t)n_planes * (size_t)(width * height) * sizeof(float) : 0;
+        return with_weight_gradients ? (scans.size() + 1) * (size_t)batch * (size_t)n_planes * (size_t)(width * height) * sizeof(float) : 0;
     }
     ~rf_var_plan();
 };
 
 namespace rf {
-int build_var_plan(const rf_var_desc *desc, rf_var_plan **out);
+int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch = 1);
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
 // bases == nullptr: `weight_planes` hold weights; else they hold exponents and bases[k] is the base of plane k (the power form)
 int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
@@ -48,11 +54,12 @@ int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *co
 // The launches of one run of `plan`, nothing checked (run_var_plan and plan_smooth.cpp check first).  The first stage reads `in`
 // (f32, or bytes: in_u8); the stages write `work` (f32) and later stages filter it in place; the final pass of the last stage
 // stores to `out` (f32 -- then out is work -- or bytes: out_u8).  log2_base == nullptr: the plane form.  `mark` is called behind
-// every launch.
+// every launch.  A batched plan: the arrays name image 0's planes and the strides are samples from image to image.
 struct VarIo {
     const void *const *in = nullptr;
     void *const *work = nullptr, *const *out = nullptr;
     bool in_u8 = false, out_u8 = false;
+    int64_t in_stride = 0, work_stride = 0, out_stride = 0, weights_stride = 0;
 };
 int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
                       const std::function<int()> &mark);
@@ -73,13 +80,16 @@ struct VarBackwardIo {
     void *const *grad_in = nullptr, *const *grad_weights = nullptr;
     const float *log2_base = nullptr, *ln_base = nullptr;
     const bool *holds_sum = nullptr;
+    int64_t in_stride = 0, weights_stride = 0, grad_out_stride = 0, grad_in_stride = 0, grad_weights_stride = 0;      // a batched plan
 };
 int ensure_var_grad_planes(rf_var_plan *plan);
 int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, const std::function<int()> &mark,
                         const std::function<void()> &skip);
 int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
+// batch > 1 (plan_smooth.cpp): image b's guide planes are guide_stride samples behind image 0's, dx and dy hold `batch` dense planes
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
-                      void *dx, void *dy, int32_t device, hipStream_t stream);
+                      void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch = 1, int64_t guide_stride = 0);
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
-                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream);
+                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
+                               int32_t batch = 1, int64_t guide_stride = 0, int64_t grad_guide_stride = 0);
 }  // namespace rf

@@ -422,10 +422,14 @@ class SmoothPlan:
     uint8 (uint8: input AND output; out = sat8 of the f32 filter on the widened bytes, rounded once, at the final store).
     guide_planes = 0: the image guides itself; else that many separate guide planes of `guide_dtype`.  A byte guide means that
     guide divided by 255.  One var_distances launch, then 6 launches per iteration.  One plan owns its distance planes, working
-    planes, tails and carries: order its executes."""
+    planes, tails and carries: order its executes.
+    batch=N (rf_smooth_plan_create_batched): N images per call, every launch taking all of them -- the launch counts are those of
+    one image.  Image, output and gradient tensors are then contiguous (N, planes, H, W) device tensors and the guide
+    (N, guide_planes, H, W); every image is filtered with its own edges, bit for bit as a plan without a batch filters it.
+    batch=None: one image, through rf_smooth_plan_create."""
 
     def __init__(self, shape_hw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
-                 iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, device: int = -1):
+                 iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, device: int = -1, batch: Optional[int] = None):
         import torch
         shape_hw = tuple(int(s) for s in shape_hw)
         if len(shape_hw) != 2:
@@ -448,8 +452,16 @@ class SmoothPlan:
         self._desc = d
         self.shape, self.planes, self.guide_planes, self.iterations = shape_hw, int(planes), int(guide_planes), int(iterations)
         self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
+        self.batch = None if batch is None else int(batch)
         self._h = ctypes.c_void_p()
-        capi.check(capi.lib().rf_smooth_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
+        if self.batch is None:
+            capi.check(capi.lib().rf_smooth_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
+        else:
+            b = capi.SmoothBatchDesc()      # contiguous NCHW
+            b.batch = self.batch
+            b.image_stride = d.n_planes * d.height * d.width
+            b.guide_stride = d.n_guide * d.height * d.width
+            capi.check(capi.lib().rf_smooth_plan_create_batched(ctypes.byref(d), ctypes.byref(b), ctypes.byref(self._h)))
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self) -> None:
@@ -487,7 +499,19 @@ class SmoothPlan:
 
     # -- execution --------------------------------------------------------------------------
     def _pointers(self, tensor, count: int, dtype, what: str) -> ctypes.Array:
-        """the planes of a (C, H, W) or (H, W) device tensor, or of a list of (H, W) tensors; VarPlan._pointers' checks"""
+        """the planes of a (C, H, W) or (H, W) device tensor, or of a list of (H, W) tensors; VarPlan._pointers' checks.
+        A batched plan: image 0's planes of a contiguous (N, C, H, W) device tensor (the plan holds the strides)."""
+        if self.batch is not None:
+            shape = (self.batch, count) + self.shape
+            if not hasattr(tensor, "dim") or tensor.dim() != 4:
+                raise ValueError(f"{what} must be one (N, C, H, W) tensor for a batched plan")
+            if tuple(tensor.shape) != shape:
+                raise ValueError(f"{what}: shape {tuple(tensor.shape)} != the batched plan's {shape}")
+            if tensor.dtype != dtype:
+                raise TypeError(f"{what}: {dtype} planes only, got {tensor.dtype}")
+            if not tensor.is_cuda or not tensor.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device tensor")
+            return (ctypes.c_void_p * count)(*[tensor[0, c].data_ptr() for c in range(count)])
         if hasattr(tensor, "dim"):
             tensor = [tensor] if tensor.dim() == 2 else [tensor[c] for c in range(tensor.shape[0])] if tensor.dim() == 3 else None
             if tensor is None:
@@ -644,6 +668,8 @@ _smooth_plan_objects: Dict[tuple, SmoothPlan] = {}
 
 def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=False):
     import torch
+    if image.dim() == 4:
+        return _smooth_by_batched_plan(image, guide, sigma_s, sigma_r, iterations, differentiable)
     img = (image if image.dim() == 3 else image.unsqueeze(0))
     if img.dim() != 3:
         raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
@@ -678,11 +704,42 @@ def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=F
     return out if image.dim() == 3 else out[0]
 
 
+def _smooth_by_batched_plan(image, guide, sigma_s, sigma_r, iterations, differentiable):
+    """form="plan" on (N, C, H, W): one cached SmoothPlan(batch=N), the rules of the 3-D call"""
+    import torch
+    img = image if image.dtype == torch.uint8 else image.to(torch.float32)
+    img = img.contiguous()
+    g = None
+    if guide is not None:
+        if guide.dim() != 4:
+            raise ValueError(f"a batched image (N, C, H, W) takes a guide (N, G, H, W), got {tuple(guide.shape)}")
+        g = guide if guide.dtype == torch.uint8 else guide.to(torch.float32)
+        g = g.to(img.device).contiguous()
+        if int(g.shape[0]) != int(img.shape[0]) or tuple(g.shape[2:]) != tuple(img.shape[2:]):
+            raise ValueError("guide and image must have the same batch size, height and width")
+    N, C, H, W = (int(s) for s in img.shape)
+    device = img.device.index if img.device.index is not None else torch.cuda.current_device()
+    key = (N, C, H, W, img.dtype, None if g is None else (int(g.shape[1]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), device)
+    plan = _smooth_plan_objects.get(key)
+    if plan is None:
+        plan = _smooth_plan_objects[key] = SmoothPlan((H, W), planes=C, guide_planes=0 if g is None else int(g.shape[1]), image_dtype=img.dtype,
+                                                      guide_dtype=None if g is None else g.dtype, iterations=iterations, sigma_s=sigma_s,
+                                                      sigma_r=sigma_r, device=device, batch=N)
+    if differentiable and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad)):
+        if img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad):
+            raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
+        return plan.apply(img, g)
+    with torch.cuda.device(img.device):
+        return plan.execute(img, g)
+
+
 def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes",
                       differentiable: bool = False):
     """Edge-aware smoothing of a device image (C, H, W) or (H, W), f32, by the domain-transform recursive filter: per iteration
     +x, -x on that iteration's x weights, then +y, -y on its y weights (two fused stages, six launches).  guide=None: the image
     guides itself.  One plan per (shape, device), cached; calls on one shape are ordered by the caller (one stream).
+    form="plan" also takes a batch: image (N, C, H, W) with guide (N, G, H, W) or None, through a cached SmoothPlan(batch=N) -- every
+    launch takes all N images, each filtered with its own edges, bit for bit as the 3-D call filters it; the other forms refuse 4-D.
     form="planes": the weight planes of `domain_transform_weights`, 2 per iteration, read by `execute`.  form="power": the two
     planes of `domain_transform_distances`, computed once, and `execute_power` with bases [a_k, a_k] per iteration -- no weight
     plane is stored; the guide may be uint8 (taken as it is: guide / 255).  form="plan": what "power" computes, by a cached
