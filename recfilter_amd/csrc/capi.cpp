@@ -550,6 +550,15 @@ int rf_tap_filter(const void *const *in_planes, int n_in, void *out, int ndim, c
 }
 
 // ---- spatially varying first-order scans (plan_var.cpp) ---------------------------------------------------------------------
+// what the *_timed entry points of the varying scans and the smoothing plan do before they run: ms_out has a slot per launch,
+// and names_out (where given) receives the launches' names
+static int timed_names(const std::vector<std::string> &names, float *ms_out, const char **names_out, int capacity) {
+    if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return RF_ERR_INVALID_ARG; }
+    if (names_out)
+        for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+    return RF_OK;
+}
+
 int rf_var_plan_create(const rf_var_desc *desc, rf_var_plan **plan_out) {
     return fenced("rf_var_plan_create", [&] { return build_var_plan(desc, plan_out); });
 }
@@ -576,9 +585,7 @@ int rf_var_plan_execute_timed(rf_var_plan *plan, const void *const *in_planes, c
                               void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity) {
     return fenced("rf_var_plan_execute_timed", [&] {
         if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
-        if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
-        if (names_out)
-            for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
+        if (int rc = timed_names(plan->names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_var_plan(plan, in_planes, weight_planes, nullptr, out_planes, (hipStream_t)stream, ms_out);
     });
 }
@@ -596,9 +603,7 @@ int rf_var_plan_execute_power_timed(rf_var_plan *plan, const void *const *in_pla
                                     int capacity) {
     return fenced("rf_var_plan_execute_power_timed", [&] {
         if (!plan || !bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
-        if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
-        if (names_out)
-            for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
+        if (int rc = timed_names(plan->names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_var_plan(plan, in_planes, exponent_planes, bases, out_planes, (hipStream_t)stream, ms_out);
     });
 }
@@ -624,9 +629,7 @@ int rf_var_plan_backward_timed(rf_var_plan *plan, const void *const *in_planes, 
     return fenced("rf_var_plan_backward_timed", [&] {
         if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
         const std::vector<std::string> &names = plan->backward_names[wants_weight_gradients(plan, grad_weight_planes) ? 1 : 0];
-        if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
-        if (names_out)
-            for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+        if (int rc = timed_names(names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_var_backward(plan, in_planes, weight_planes, nullptr, grad_out_planes, grad_in_planes, grad_weight_planes, (hipStream_t)stream, ms_out);
     });
 }
@@ -646,9 +649,7 @@ int rf_var_plan_backward_power_timed(rf_var_plan *plan, const void *const *in_pl
     return fenced("rf_var_plan_backward_power_timed", [&] {
         if (!plan || !bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
         const std::vector<std::string> &names = plan->backward_names[wants_weight_gradients(plan, grad_exponent_planes) ? 1 : 0];
-        if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
-        if (names_out)
-            for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+        if (int rc = timed_names(names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_var_backward(plan, in_planes, exponent_planes, bases, grad_out_planes, grad_in_planes, grad_exponent_planes, (hipStream_t)stream, ms_out);
     });
 }
@@ -717,9 +718,7 @@ int rf_smooth_plan_execute_timed(rf_smooth_plan *plan, const void *const *image_
                                  void *const *out_planes, void *stream, float *ms_out, const char **names_out, int capacity) {
     return fenced("rf_smooth_plan_execute_timed", [&] {
         if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
-        if (!ms_out || capacity < (int)plan->names.size()) { set_error("ms_out too small: need %zu", plan->names.size()); return (int)RF_ERR_INVALID_ARG; }
-        if (names_out)
-            for (size_t i = 0; i < plan->names.size(); i++) names_out[i] = plan->names[i].c_str();
+        if (int rc = timed_names(plan->names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_smooth_plan(plan, image_planes, guide_planes, out_planes, (hipStream_t)stream, ms_out);
     });
 }
@@ -739,9 +738,7 @@ int rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *image
         if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
         if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return (int)RF_ERR_INVALID_ARG; }
         const std::vector<std::string> &names = plan->backward_names[edges];
-        if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return (int)RF_ERR_INVALID_ARG; }
-        if (names_out)
-            for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
+        if (int rc = timed_names(names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, ms_out);
     });
 }

@@ -15,7 +15,11 @@
 //
 // A batched plan (rf_smooth_plan_create_batched) is the same sequence: every launch takes all the images on gridDim.z, each image
 // with its own distance planes, tails, carries and working planes, laid out image after image as a single-image plan lays out
-// its one.  The launch count does not depend on the batch.  The caller's planes are checked per (image, plane) extent, sorted.
+// its one.  The launch count does not depend on the batch.  The caller's planes are checked per (image, plane) extent, sorted
+// (check_extents); a single image's by the checks plan_var.h shares with the varying plan (check_plane, check_written_planes).
+//
+// Both run functions construct one LaunchTimer (plan_var.h) and hand it to every launcher they call, so the slots of a timed run
+// follow the plan's name lists; the constants of the power form, log2 and ln of every a_k, are the plan's from its construction.
 #include "plan_smooth.h"
 
 #include <algorithm>
@@ -59,9 +63,6 @@ int validate(const rf_smooth_desc *d) {
     }
     return RF_OK;
 }
-
-bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
-bool overlap(const void *a, const void *b, size_t n) { return overlap((uintptr_t)a, n, (uintptr_t)b, n); }
 
 // the refusals of rf_smooth_plan_create_batched that concern the batch alone, in the order recfilter_amd.h documents
 int validate_batch(const rf_smooth_desc *d, const rf_smooth_batch_desc *b) {
@@ -180,6 +181,7 @@ int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *ba
         }
         plan->bases.push_back(a_k);
         plan->log2_bases.push_back((float)std::log2((double)a_k));
+        plan->ln_bases.push_back((float)std::log((double)a_k));
     }
     const rf_var_scan_desc scans[4] = {{0, 1, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 1}};
     rf_var_desc vd{};
@@ -235,21 +237,14 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
     const size_t samples = (size_t)(plan->width * plan->height);
     const size_t image_bytes = samples * (plan->image_u8 ? 1 : sizeof(float));
-    const uintptr_t image_mask = plan->image_u8 ? 3u : 15u, guide_mask = plan->guide_u8 ? 3u : 15u;
-    for (int pl = 0; pl < plan->n_planes; pl++) {
-        if (!image_planes[pl] || !out_planes[pl]) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
-        if ((((uintptr_t)image_planes[pl] | (uintptr_t)out_planes[pl]) & image_mask) != 0) {
-            set_error("plane %d: %s image planes must be %u-byte aligned", pl, plan->image_u8 ? "uint8" : "f32", (unsigned)image_mask + 1);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    for (int ch = 0; ch < plan->n_guide; ch++) {
-        if (!guide_planes[ch]) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
-        if (((uintptr_t)guide_planes[ch] & guide_mask) != 0) {
-            set_error("guide plane %d: %s guide planes must be %u-byte aligned", ch, plan->guide_u8 ? "uint8" : "f32", (unsigned)guide_mask + 1);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
+    int rc = RF_OK;
+    for (int pl = 0; pl < plan->n_planes && rc == RF_OK; pl++)
+        rc = check_plane("plane", pl, {{image_planes[pl]}, {out_planes[pl]}}, plan->image_u8 ? 3u : 15u, "null image pointer",
+                         plan->image_u8 ? "uint8 image planes must be 4-byte aligned" : "f32 image planes must be 16-byte aligned");
+    for (int ch = 0; ch < plan->n_guide && rc == RF_OK; ch++)
+        rc = check_plane("guide plane", ch, {{guide_planes[ch]}}, plan->guide_u8 ? 3u : 15u, "null pointer",
+                         plan->guide_u8 ? "uint8 guide planes must be 4-byte aligned" : "f32 guide planes must be 16-byte aligned");
+    if (rc != RF_OK) return rc;
     // a stage has loaded its tile before it stores, so a plane may be filtered in place; any other overlap of an input with an output
     // is read after another workgroup's store
     const int B = plan->batch;
@@ -258,45 +253,26 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         const int64_t stride_bytes = image_stride * (int64_t)(plan->image_u8 ? 1 : sizeof(float));
         const ExtentArray arrays[2] = {{"input", image_planes, plan->n_planes, stride_bytes, image_bytes, false, 1},
                                        {"output", (const void *const *)out_planes, plan->n_planes, stride_bytes, image_bytes, true, 0}};
-        int rc = check_extents(arrays, 2, B);
+        rc = check_extents(arrays, 2, B);
         if (rc != RF_OK) return rc;
     }
     for (int pl = 0; pl < plan->n_planes && B == 1; pl++)
         for (int q = 0; q < plan->n_planes; q++) {
             if (pl == q && image_planes[pl] == out_planes[q]) continue;
-            if (overlap((uintptr_t)image_planes[pl], image_bytes, (uintptr_t)out_planes[q], image_bytes)) {
+            if (overlap(image_planes[pl], image_bytes, out_planes[q], image_bytes)) {
                 set_error("input plane %d overlaps output plane %d: an input plane is its own output plane or disjoint from every output plane", pl, q);
                 return RF_ERR_INVALID_ARG;
             }
         }
     RF_HIP_CHECK(hipSetDevice(plan->device));
-    // events are destroyed on every return path
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } events;
-    const size_t n_kernels = plan->names.size();
-    if (ms_out) {
-        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
-        for (size_t i = 0; i < n_kernels + 1; i++) {
-            hipEvent_t e;
-            RF_HIP_CHECK(hipEventCreate(&e));
-            events.ev.push_back(e);
-        }
-        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
-    }
-    size_t launch = 0;
-    const std::function<int()> mark = [&]() -> int {
-        launch++;
-        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
-        return RF_OK;
-    };
+    LaunchTimer timer(stream, ms_out, plan->names.size());
+    if (timer.status() != RF_OK) return timer.status();
     float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each
     // the distances first, on the same stream: guide planes may be output planes
     const bool self = plan->n_guide == 0;
-    int rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
-                               plan->width, plan->height, plan->scale, dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
-    if (rc == RF_OK) rc = mark();
+    rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
+                           plan->width, plan->height, plan->scale, dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
+    if (rc == RF_OK) rc = timer.mark();
     if (rc != RF_OK) return rc;
     void *work[RF_MAX_PLANES] = {};
     // byte images: [image][plane] behind the distance planes
@@ -316,14 +292,10 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         io.out_stride = k == K - 1 ? image_stride : work_stride;
         io.weights_stride = (int64_t)samples;
         const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-        rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, mark);
+        rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, timer);
         if (rc != RF_OK) return rc;
     }
-    if (ms_out) {
-        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
-        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
-    }
-    return RF_OK;
+    return timer.finish();
 }
 
 int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
@@ -354,28 +326,18 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     const bool with_guide_grad = edges == 1 && !self;
     const size_t samples = (size_t)(plan->width * plan->height), plane_bytes = samples * sizeof(float);
     const size_t guide_bytes = samples * (plan->guide_u8 ? 1 : sizeof(float));
-    for (int pl = 0; pl < P; pl++) {
-        if (!grad_out_planes[pl] || !grad_image_planes[pl] || (need_image && !image_planes[pl])) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
-        if ((((uintptr_t)grad_out_planes[pl] | (uintptr_t)grad_image_planes[pl] | (uintptr_t)(need_image ? image_planes[pl] : nullptr)) & 15u) != 0) {
-            set_error("plane %d: the varying scans need 16-byte aligned image pointers", pl);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    const uintptr_t guide_mask = plan->guide_u8 ? 3u : 15u;
-    for (int ch = 0; ch < G; ch++) {
-        if (!guide_planes[ch] || (with_guide_grad && !grad_guide_planes[ch])) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
-        if (((uintptr_t)guide_planes[ch] & guide_mask) != 0 || (with_guide_grad && ((uintptr_t)grad_guide_planes[ch] & 15u) != 0)) {
-            set_error("guide plane %d: %s guide planes must be %u-byte aligned (the plane and its gradient)", ch, plan->guide_u8 ? "uint8" : "f32", (unsigned)guide_mask + 1);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
+    int rc = RF_OK;
+    for (int pl = 0; pl < P && rc == RF_OK; pl++)
+        rc = check_plane("plane", pl, {{grad_out_planes[pl]}, {grad_image_planes[pl]}, {need_image ? image_planes[pl] : nullptr, need_image}}, 15u,
+                         "null image pointer", "the varying scans need 16-byte aligned image pointers");
+    // (a guide with a gradient is f32: one mask for the plane and its gradient)
+    for (int ch = 0; ch < G && rc == RF_OK; ch++)
+        rc = check_plane("guide plane", ch, {{guide_planes[ch]}, {with_guide_grad ? grad_guide_planes[ch] : nullptr, with_guide_grad}},
+                         plan->guide_u8 ? 3u : 15u, "null pointer",
+                         plan->guide_u8 ? "uint8 guide planes must be 4-byte aligned (the plane and its gradient)"
+                                        : "f32 guide planes must be 16-byte aligned (the plane and its gradient)");
+    if (rc != RF_OK) return rc;
     // what is written (grad_image planes, guide-gradient planes) against everything that is read and everything else that is written
-    const int n_written = P + (with_guide_grad ? G : 0);
-    auto written = [&](int i) -> const void * { return i < P ? grad_image_planes[i] : grad_guide_planes[i - P]; };
-    auto written_name = [&](int i, char *buf, size_t n) {
-        if (i < P) std::snprintf(buf, n, "grad_image plane %d", i);
-        else std::snprintf(buf, n, "gradient of guide plane %d", i - P);
-    };
     const int B = plan->batch;
     const int64_t image_stride = plan->image_stride, guide_stride = plan->guide_stride;
     if (B > 1) {
@@ -389,43 +351,18 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         arrays[n++] = {"grad_out", grad_out_planes, P, image_stride_bytes, plane_bytes, false, grad_image_at};
         arrays[n++] = {"grad_image", (const void *const *)grad_image_planes, P, image_stride_bytes, plane_bytes, true, grad_out_at};
         if (with_guide_grad) arrays[n++] = {"gradient of guide", (const void *const *)grad_guide_planes, G, guide_stride_bytes, plane_bytes, true, -1};
-        int rc = check_extents(arrays, n, B);
-        if (rc != RF_OK) return rc;
+        rc = check_extents(arrays, n, B);
+    } else {
+        const PlaneList written[2] = {{"grad_image", (const void *const *)grad_image_planes, P, plane_bytes},
+                                      {"gradient of guide", (const void *const *)grad_guide_planes, with_guide_grad ? G : 0, plane_bytes}};
+        const PlaneList read[2] = {{"guide", guide_planes, G, guide_bytes}, {"image", image_planes, need_image ? P : 0, plane_bytes}};
+        rc = check_written_planes(written, 2, read, 2, {"grad_out", grad_out_planes, P, plane_bytes});
     }
-    for (int i = 0; i < n_written && B == 1; i++) {
-        const void *o = written(i);
-        char name[64];
-        written_name(i, name, sizeof name);
-        for (int ch = 0; ch < G; ch++)
-            if (overlap((uintptr_t)o, plane_bytes, (uintptr_t)guide_planes[ch], guide_bytes)) {
-                set_error("%s overlaps guide plane %d", name, ch);
-                return RF_ERR_INVALID_ARG;
-            }
-        if (need_image)
-            for (int pl = 0; pl < P; pl++)
-                if (overlap(o, image_planes[pl], plane_bytes)) {
-                    set_error("%s overlaps image plane %d", name, pl);
-                    return RF_ERR_INVALID_ARG;
-                }
-        for (int j = i + 1; j < n_written; j++)
-            if (overlap(o, written(j), plane_bytes)) {
-                char other[64];
-                written_name(j, other, sizeof other);
-                set_error("%s overlaps %s", name, other);
-                return RF_ERR_INVALID_ARG;
-            }
-        for (int pl = 0; pl < P; pl++) {
-            if (i == pl && o == grad_out_planes[pl]) continue;      // in place: a plane and its own gradient, exactly
-            if (overlap(o, grad_out_planes[pl], plane_bytes)) {
-                set_error("%s overlaps grad_out plane %d (only grad_image plane %d may, and then exactly)", name, pl, pl);
-                return RF_ERR_INVALID_ARG;
-            }
-        }
-    }
+    if (rc != RF_OK) return rc;
     RF_HIP_CHECK(hipSetDevice(plan->device));
     rf_var_plan *inner = plan->inner.get();
     if (edges == 1) {
-        int rc = ensure_var_grad_planes(inner);
+        rc = ensure_var_grad_planes(inner);
         if (rc != RF_OK) return rc;
         if (!plan->grad_planes && hipMalloc((void **)&plan->grad_planes, plan->own_backward_bytes()) != hipSuccess) {
             (void)hipGetLastError();
@@ -434,32 +371,12 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
             return RF_ERR_NOMEM;
         }
     }
-    // events are destroyed on every return path
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } events;
-    const size_t n_kernels = plan->backward_names[edges].size();
-    if (ms_out) {
-        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
-        for (size_t i = 0; i < n_kernels + 1; i++) {
-            hipEvent_t e;
-            RF_HIP_CHECK(hipEventCreate(&e));
-            events.ev.push_back(e);
-        }
-        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
-    }
-    size_t launch = 0;
-    const std::function<int()> mark = [&]() -> int {
-        launch++;
-        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
-        return RF_OK;
-    };
-    const std::function<void()> skip = [] {};      // (both exponent gradients are always formed: nothing is skipped)
+    LaunchTimer timer(stream, ms_out, plan->backward_names[edges].size());
+    if (timer.status() != RF_OK) return timer.status();
     float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each, as the gradients' gd_x, gd_y below
-    int rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
-                               dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
-    if (rc == RF_OK) rc = mark();
+    rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
+                           dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
+    if (rc == RF_OK) rc = timer.mark();
     if (rc != RF_OK) return rc;
     const void *const exponents[2] = {dx, dy};
     float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples * (size_t)B : nullptr;
@@ -476,15 +393,14 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
             io.work_stride = io.out_stride = checkpoint_stride;
             io.weights_stride = (int64_t)samples;
             const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-            rc = launch_var_stages(inner, io, exponents, l, stream, mark);
+            rc = launch_var_stages(inner, io, exponents, l, stream, timer);
             if (rc != RF_OK) return rc;
         }
     }
     void *const grad_exponents[2] = {gdx, gdy};
     for (int k = K - 1; k >= 0; k--) {
-        const float a_k = plan->bases[(size_t)k];
         const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-        const float ln = (float)std::log((double)a_k), c[2] = {ln, ln};
+        const float c[2] = {plan->ln_bases[(size_t)k], plan->ln_bases[(size_t)k]};
         const bool holds_sum[2] = {k < K - 1, k < K - 1};
         VarBackwardIo io{};
         io.in = edges == 0 ? nullptr : k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
@@ -498,7 +414,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         io.in_stride = k == 0 ? image_stride : checkpoint_stride;
         io.weights_stride = io.grad_weights_stride = (int64_t)samples;
         io.grad_out_stride = io.grad_in_stride = image_stride;
-        rc = launch_var_backward(inner, io, stream, mark, skip);
+        rc = launch_var_backward(inner, io, stream, timer);      // (both exponent gradients are always formed: nothing is skipped)
         if (rc != RF_OK) return rc;
     }
     if (edges == 1) {
@@ -506,14 +422,10 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         rc = run_var_distances_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->scale, gdx, gdy,
                                         self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream, B,
                                         self ? image_stride : guide_stride, self ? image_stride : guide_stride);
-        if (rc == RF_OK) rc = mark();
+        if (rc == RF_OK) rc = timer.mark();
         if (rc != RF_OK) return rc;
     }
-    if (ms_out) {
-        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
-        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
-    }
-    return RF_OK;
+    return timer.finish();
 }
 
 }  // namespace rf

@@ -21,6 +21,7 @@ struct rf_smooth_plan {
     float scale = 0.0f;                      // of var_distances: sigma_s / sigma_r, over 255 where the planes that guide are bytes
     std::vector<float> bases;                // a_k
     std::vector<float> log2_bases;           // (float)log2((double)a_k): what rf_var_plan_execute_power forms from a_k
+    std::vector<float> ln_bases;             // (float)log((double)a_k): what rf_var_plan_backward_power forms beside it
     std::unique_ptr<rf_var_plan> inner;      // +x -x +y -y on two exponent planes: two pair stages, the tails and the carries
     // one allocation: d_x (one plane per image), d_y (the same), then (byte images) n_planes f32 working planes per image
     float *planes = nullptr;

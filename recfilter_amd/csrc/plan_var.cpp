@@ -6,8 +6,14 @@
 // tails [tile][component][plane][line] and carries [tile][c, d][plane][line], sized for the dimension that needs more.  Every
 // stage is three launches: tails, carry, final pass.  The first stage reads the input planes, later stages filter the output
 // planes in place.  The power form (rf_var_plan_execute_power) runs the same stages on exponent planes: a stage carries
-// log2 of its plane's base and launches the kernels' POWER instances.  run_var_plan checks the arguments and owns the timing
-// events; launch_var_stages issues the launches of one run, and is what the smoothing plan (plan_smooth.cpp) calls per iteration.
+// log2 of its plane's base and launches the kernels' POWER instances.  run_var_plan checks the arguments and constructs the run's
+// LaunchTimer; launch_var_stages issues the launches of one run, and is what the smoothing plan (plan_smooth.cpp) calls per
+// iteration.
+//
+// What every run shares lives here once: LaunchTimer (the events of a timed run: a mark behind every launch, nothing at all where
+// no times are asked for), scan_args (the fields of VarArgs a plan determines) and launch_stage (tails, carry, final pass, a mark
+// behind each), and the checks plan_var.h declares -- check_plane (null and alignment, per plane index), check_written_planes (the
+// aliasing rules of a single-image backward) and power_constants (the bases of the power form, log2 and ln of each).
 //
 // run_var_backward is the adjoint of a plan (rf_var_plan_backward): per scan in reverse order an adjoint stage -- a unit-gain scan
 // in the opposite direction, tails / var_carry / final pass like a forward stage, always scan by scan.  The image gradient needs
@@ -17,10 +23,10 @@
 // weight plane, added by the later ones; the host knows which is which, so there are no atomics and no zero-fill.
 // The power form (rf_var_plan_backward_power) is the same list on the kernels' POWER instances: the stages carry log2 of their
 // plane's base, var_grad also its natural logarithm and the exponent plane, and what it stores is the gradient of the exponents.
-// run_var_backward checks and owns the events; launch_var_backward issues the launches, and is what the smoothing plan's backward
-// (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
+// run_var_backward checks and constructs the timer; launch_var_backward issues the launches, and is what the smoothing plan's
+// backward (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
 //
-// run_var_distances_backward: the adjoint of run_var_distances, one launch.
+// run_var_distances_backward: the adjoint of run_var_distances, one launch; the two share their checks of counts, scale and extents.
 //
 // A plan may hold a batch (build_var_plan's third argument; plan_smooth.cpp only, the public entry points build 1): tails,
 // carries and the backward's planes are then `batch` images' worth, image after image, and the launchers above carry the batch
@@ -77,6 +83,14 @@ int validate(const rf_var_desc *d) {
 
 int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
 
+// the three launches of a stage along `dim`; prefix: "var_", or "var_adj_" for an adjoint stage
+void push_stage_names(std::vector<std::string> &names, const char *prefix, int dim) {
+    const char *axis = dim == 0 ? "x" : "y";
+    names.push_back(std::string(prefix) + "tails_" + axis);
+    names.push_back("var_carry");
+    names.push_back(std::string(prefix) + "pass2_" + axis);
+}
+
 }  // namespace
 
 int64_t var_max_extent() { return kVarMaxExtent; }
@@ -110,10 +124,7 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
         rf_var_stage st;
         st.dim = dim; st.mode = mode; st.weights = weights;
         used[dim] = true;
-        const char *axis = dim == 0 ? "x" : "y";
-        plan->names.push_back(std::string("var_tails_") + axis);
-        plan->names.push_back("var_carry");
-        plan->names.push_back(std::string("var_pass2_") + axis);
+        push_stage_names(plan->names, "var_", dim);
         plan->stages.push_back(st);
     };
     for (int s = 0; s < desc->n_scans;) {
@@ -129,19 +140,11 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     }
     // the adjoint's launch lists: [1] reruns the forward scan by scan first, and has one var_grad behind every adjoint stage
     plan->scans.assign(desc->scans, desc->scans + desc->n_scans);
-    for (const rf_var_scan_desc &sc : plan->scans) {
-        const char *axis = sc.dim == 0 ? "x" : "y";
-        plan->backward_names[1].push_back(std::string("var_tails_") + axis);
-        plan->backward_names[1].push_back("var_carry");
-        plan->backward_names[1].push_back(std::string("var_pass2_") + axis);
-    }
+    for (const rf_var_scan_desc &sc : plan->scans) push_stage_names(plan->backward_names[1], "var_", sc.dim);
     for (int with = 0; with < 2; with++)
         for (int q = desc->n_scans - 1; q >= 0; q--) {
-            const char *axis = desc->scans[q].dim == 0 ? "x" : "y";
-            plan->backward_names[with].push_back(std::string("var_adj_tails_") + axis);
-            plan->backward_names[with].push_back("var_carry");
-            plan->backward_names[with].push_back(std::string("var_adj_pass2_") + axis);
-            if (with) plan->backward_names[with].push_back(std::string("var_grad_") + axis);
+            push_stage_names(plan->backward_names[with], "var_adj_", desc->scans[q].dim);
+            if (with) plan->backward_names[with].push_back(desc->scans[q].dim == 0 ? "var_grad_x" : "var_grad_y");
         }
     // tiles x lines of the dimension that needs more: x scans have `height` lines, y scans `width`
     int64_t slots = 0;
@@ -161,137 +164,189 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     return RF_OK;
 }
 
-int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
-                 void *const *out_planes, hipStream_t stream, float *ms_out) {
-    if (!plan || !in_planes || !weight_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    float log2_base[RF_VAR_MAX_SCANS] = {};
-    if (bases) {
-        for (int k = 0; k < plan->n_weights; k++) {
-            if (!std::isfinite(bases[k]) || !(bases[k] > 0.0f && bases[k] < 1.0f)) {
-                set_error("exponent plane %d: the base must be inside (0, 1) (got %g)", k, (double)bases[k]);
-                return RF_ERR_INVALID_ARG;
-            }
-            log2_base[k] = (float)std::log2((double)bases[k]);
-        }
+// ---- the launch timer -----------------------------------------------------------------------------------------------------------
+LaunchTimer::LaunchTimer(hipStream_t stream, float *ms_out, size_t n_slots) : stream_(stream), ms_out_(ms_out), n_slots_(n_slots) {
+    if (ms_out_) status_ = create();
+}
+
+LaunchTimer::~LaunchTimer() {
+    for (hipEvent_t e : events_) (void)hipEventDestroy(e);
+}
+
+int LaunchTimer::create() {
+    for (size_t i = 0; i < n_slots_; i++) ms_out_[i] = 0.0f;
+    for (size_t i = 0; i < n_slots_ + 1; i++) {
+        hipEvent_t e;
+        RF_HIP_CHECK(hipEventCreate(&e));
+        events_.push_back(e);
     }
-    if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
-    const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
-    for (int pl = 0; pl < plan->n_planes; pl++) {
-        if (!in_planes[pl] || !out_planes[pl]) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
-        if ((((uintptr_t)in_planes[pl] | (uintptr_t)out_planes[pl]) & 15u) != 0) {
-            set_error("plane %d: the varying scans need 16-byte aligned image pointers", pl);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    for (int k = 0; k < plan->n_weights; k++) {
-        if (!weight_planes[k]) { set_error("weight plane %d: null pointer", k); return RF_ERR_INVALID_ARG; }
-        if (((uintptr_t)weight_planes[k] & 15u) != 0) { set_error("weight plane %d: the varying scans need 16-byte aligned pointers", k); return RF_ERR_INVALID_ARG; }
-        const uintptr_t w0 = (uintptr_t)weight_planes[k];
-        for (int pl = 0; pl < plan->n_planes; pl++) {
-            const uintptr_t o0 = (uintptr_t)out_planes[pl];
-            if (w0 < o0 + plane_bytes && o0 < w0 + plane_bytes) {
-                set_error("weight plane %d overlaps output plane %d: every stage reads the weights after it has begun to store", k, pl);
-                return RF_ERR_INVALID_ARG;
-            }
-        }
-    }
-    RF_HIP_CHECK(hipSetDevice(plan->device));
-    // events are destroyed on every return path
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } events;
-    const size_t n_kernels = plan->stages.size() * 3;
-    if (ms_out) {
-        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
-        for (size_t i = 0; i < n_kernels + 1; i++) {
-            hipEvent_t e;
-            RF_HIP_CHECK(hipEventCreate(&e));
-            events.ev.push_back(e);
-        }
-        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
-    }
-    size_t launch = 0;
-    const std::function<int()> mark = [&]() -> int {
-        launch++;
-        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
-        return RF_OK;
-    };
-    VarIo io{};
-    io.in = in_planes;
-    io.work = io.out = out_planes;
-    int rc = launch_var_stages(plan, io, weight_planes, bases ? log2_base : nullptr, stream, mark);
-    if (rc != RF_OK) return rc;
-    if (ms_out) {
-        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
-        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
-    }
+    RF_HIP_CHECK(hipEventRecord(events_[0], stream_));
     return RF_OK;
 }
 
-int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
-                      const std::function<int()> &mark) {
-    const size_t last = plan->stages.size() - 1;
-    for (size_t s = 0; s <= last; s++) {
-        const rf_var_stage &st = plan->stages[s];
-        VarArgs a{};
-        for (int pl = 0; pl < plan->n_planes; pl++) {
-            a.src[pl] = s == 0 ? io.in[pl] : io.work[pl];
-            a.dst[pl] = s == last ? io.out[pl] : io.work[pl];
+int LaunchTimer::mark() {
+    if (!ms_out_) return RF_OK;
+    marks_++;
+    RF_HIP_CHECK(hipEventRecord(events_[marks_], stream_));
+    return RF_OK;
+}
+
+void LaunchTimer::skip() {
+    if (ms_out_) skipped_.push_back(marks_);
+}
+
+int LaunchTimer::finish() {
+    if (!ms_out_) return RF_OK;
+    RF_HIP_CHECK(hipEventSynchronize(events_.back()));
+    for (size_t i = 0; i < n_slots_; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out_[i], events_[i], events_[i + 1]));
+    for (size_t i : skipped_) ms_out_[i] = 0.0f;
+    return RF_OK;
+}
+
+// ---- the shared checks ------------------------------------------------------------------------------------------------------------
+int check_plane(const char *what, int index, std::initializer_list<PlanePointer> pointers, uintptr_t mask, const char *null_text, const char *align_text) {
+    uintptr_t bits = 0;
+    for (const PlanePointer &q : pointers) {
+        if (q.required && !q.p) { set_error("%s %d: %s", what, index, null_text); return RF_ERR_INVALID_ARG; }
+        bits |= (uintptr_t)q.p;
+    }
+    if ((bits & mask) != 0) { set_error("%s %d: %s", what, index, align_text); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
+int check_written_planes(const PlaneList *written, int n_written, const PlaneList *read, int n_read, const PlaneList &grad_out) {
+    for (int w = 0; w < n_written; w++)
+        for (int i = 0; i < written[w].n; i++) {
+            const void *o = written[w].planes[i];
+            if (!o) continue;
+            const size_t bytes = written[w].bytes;
+            char name[64];
+            std::snprintf(name, sizeof name, "%s plane %d", written[w].noun, i);
+            for (int r = 0; r < n_read; r++)
+                for (int q = 0; q < read[r].n; q++)
+                    if (read[r].planes[q] && overlap(o, bytes, read[r].planes[q], read[r].bytes)) {
+                        set_error("%s overlaps %s plane %d%s", name, read[r].noun, q, read[r].why);
+                        return RF_ERR_INVALID_ARG;
+                    }
+            for (int v = w; v < n_written; v++)      // every written plane behind this one
+                for (int j = v == w ? i + 1 : 0; j < written[v].n; j++)
+                    if (written[v].planes[j] && overlap(o, bytes, written[v].planes[j], written[v].bytes)) {
+                        set_error("%s overlaps %s plane %d", name, written[v].noun, j);
+                        return RF_ERR_INVALID_ARG;
+                    }
+            for (int pl = 0; pl < grad_out.n; pl++) {
+                if (w == 0 && i == pl && o == grad_out.planes[pl]) continue;      // in place: a plane and its own gradient, exactly
+                if (overlap(o, bytes, grad_out.planes[pl], grad_out.bytes)) {
+                    set_error("%s overlaps %s plane %d (only %s plane %d may, and then exactly)", name, grad_out.noun, pl, written[0].noun, pl);
+                    return RF_ERR_INVALID_ARG;
+                }
+            }
         }
-        a.src_u8 = s == 0 && io.in_u8;
-        a.weights = (const float *)weight_planes[st.weights];
-        a.tails = plan->tails;
-        a.carry = plan->carry;
-        a.batch = plan->batch;
-        a.src_stride = s == 0 ? io.in_stride : io.work_stride;
-        a.dst_stride = s == last ? io.out_stride : io.work_stride;
-        a.weights_stride = io.weights_stride;
-        a.tails_stride = plan->image_tails_floats();
-        a.carry_stride = plan->image_carry_floats();
-        a.width = (int32_t)plan->width;
-        a.height = (int32_t)plan->height;
-        a.n_planes = plan->n_planes;
-        a.tiles = (int32_t)tiles_of(st.dim == 0 ? plan->width : plan->height);
-        a.lines = (int32_t)(st.dim == 0 ? plan->height : plan->width);
-        a.mode = st.mode;
-        a.power = log2_base ? 1 : 0;
-        a.log2_base = log2_base ? log2_base[st.weights] : 0.0f;
-        int rc = launch_var_tails(a, st.dim, stream);
-        if (rc == RF_OK) rc = mark();
-        if (rc == RF_OK) rc = launch_var_carry(a, stream);
-        if (rc == RF_OK) rc = mark();
-        a.dst_u8 = s == last && io.out_u8;        // (the tails pass stores no sample)
-        if (rc == RF_OK) rc = launch_var_pass2(a, st.dim, stream);
-        if (rc == RF_OK) rc = mark();
-        if (rc != RF_OK) return rc;
+    return RF_OK;
+}
+
+int power_constants(const float *bases, int n_weights, float *log2_base, float *ln_base) {
+    for (int k = 0; k < n_weights; k++) {
+        if (!std::isfinite(bases[k]) || !(bases[k] > 0.0f && bases[k] < 1.0f)) {
+            set_error("exponent plane %d: the base must be inside (0, 1) (got %g)", k, (double)bases[k]);
+            return RF_ERR_INVALID_ARG;
+        }
+        log2_base[k] = (float)std::log2((double)bases[k]);
+        ln_base[k] = (float)std::log((double)bases[k]);
     }
     return RF_OK;
 }
 
 namespace {
 
-// one single-scan stage's arguments, planes aside
-VarArgs scan_args(const rf_var_plan *plan, const rf_var_scan_desc &sc, const void *const *weight_planes, int mode) {
+// The fields of a stage's arguments that the plan determines -- the workspace, the batch, the extents, the tiling along `dim` --
+// with the stage's weight plane and mode.  The planes, their strides and the power form are the caller's.
+VarArgs scan_args(const rf_var_plan *plan, int dim, const void *weights, int mode) {
     VarArgs a{};
-    a.weights = (const float *)weight_planes[sc.weights];
+    a.weights = (const float *)weights;
     a.tails = plan->tails;
     a.carry = plan->carry;
-    a.width = (int32_t)plan->width;
-    a.height = (int32_t)plan->height;
-    a.n_planes = plan->n_planes;
-    a.tiles = (int32_t)tiles_of(sc.dim == 0 ? plan->width : plan->height);
-    a.lines = (int32_t)(sc.dim == 0 ? plan->height : plan->width);
-    a.mode = mode;
     a.batch = plan->batch;
     a.tails_stride = plan->image_tails_floats();
     a.carry_stride = plan->image_carry_floats();
+    a.width = (int32_t)plan->width;
+    a.height = (int32_t)plan->height;
+    a.n_planes = plan->n_planes;
+    a.tiles = (int32_t)tiles_of(dim == 0 ? plan->width : plan->height);
+    a.lines = (int32_t)(dim == 0 ? plan->height : plan->width);
+    a.mode = mode;
     return a;
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+// The three launches of a stage, a mark behind each.  a.dst_u8 is held back until the final pass: the tails pass stores no sample.
+int launch_stage(VarArgs &a, int dim, hipStream_t stream, LaunchTimer &timer) {
+    const int32_t dst_u8 = a.dst_u8;
+    a.dst_u8 = 0;
+    int rc = launch_var_tails(a, dim, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK) rc = launch_var_carry(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    a.dst_u8 = dst_u8;
+    if (rc == RF_OK) rc = launch_var_pass2(a, dim, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    return rc;
+}
 
 }  // namespace
+
+int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
+                 void *const *out_planes, hipStream_t stream, float *ms_out) {
+    if (!plan || !in_planes || !weight_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    float log2_base[RF_VAR_MAX_SCANS] = {}, ln_base[RF_VAR_MAX_SCANS] = {};
+    int rc = bases ? power_constants(bases, plan->n_weights, log2_base, ln_base) : RF_OK;
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
+    const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
+    for (int pl = 0; pl < plan->n_planes; pl++) {
+        rc = check_plane("plane", pl, {{in_planes[pl]}, {out_planes[pl]}}, 15u, "null image pointer", "the varying scans need 16-byte aligned image pointers");
+        if (rc != RF_OK) return rc;
+    }
+    for (int k = 0; k < plan->n_weights; k++) {
+        rc = check_plane("weight plane", k, {{weight_planes[k]}}, 15u, "null pointer", "the varying scans need 16-byte aligned pointers");
+        if (rc != RF_OK) return rc;
+        for (int pl = 0; pl < plan->n_planes; pl++)
+            if (overlap(weight_planes[k], plane_bytes, out_planes[pl], plane_bytes)) {
+                set_error("weight plane %d overlaps output plane %d: every stage reads the weights after it has begun to store", k, pl);
+                return RF_ERR_INVALID_ARG;
+            }
+    }
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    LaunchTimer timer(stream, ms_out, plan->names.size());
+    if (timer.status() != RF_OK) return timer.status();
+    VarIo io{};
+    io.in = in_planes;
+    io.work = io.out = out_planes;
+    rc = launch_var_stages(plan, io, weight_planes, bases ? log2_base : nullptr, stream, timer);
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
+                      LaunchTimer &timer) {
+    const size_t last = plan->stages.size() - 1;
+    for (size_t s = 0; s <= last; s++) {
+        const rf_var_stage &st = plan->stages[s];
+        VarArgs a = scan_args(plan, st.dim, weight_planes[st.weights], st.mode);
+        for (int pl = 0; pl < plan->n_planes; pl++) {
+            a.src[pl] = s == 0 ? io.in[pl] : io.work[pl];
+            a.dst[pl] = s == last ? io.out[pl] : io.work[pl];
+        }
+        a.src_u8 = s == 0 && io.in_u8;
+        a.dst_u8 = s == last && io.out_u8;
+        a.src_stride = s == 0 ? io.in_stride : io.work_stride;
+        a.dst_stride = s == last ? io.out_stride : io.work_stride;
+        a.weights_stride = io.weights_stride;
+        a.power = log2_base ? 1 : 0;
+        a.log2_base = log2_base ? log2_base[st.weights] : 0.0f;
+        int rc = launch_stage(a, st.dim, stream, timer);
+        if (rc != RF_OK) return rc;
+    }
+    return RF_OK;
+}
 
 int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
                      const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream,
@@ -303,99 +358,35 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
         for (int k = 0; k < plan->n_weights; k++) with_weights = with_weights || grad_weight_planes[k] != nullptr;
     if (with_weights && !in_planes) { set_error("weight gradients need the input planes (in_planes is null)"); return RF_ERR_INVALID_ARG; }
     float log2_base[RF_VAR_MAX_SCANS] = {}, ln_base[RF_VAR_MAX_SCANS] = {};
-    if (bases) {
-        for (int k = 0; k < plan->n_weights; k++) {
-            if (!std::isfinite(bases[k]) || !(bases[k] > 0.0f && bases[k] < 1.0f)) {
-                set_error("exponent plane %d: the base must be inside (0, 1) (got %g)", k, (double)bases[k]);
-                return RF_ERR_INVALID_ARG;
-            }
-            log2_base[k] = (float)std::log2((double)bases[k]);
-            ln_base[k] = (float)std::log((double)bases[k]);
-        }
-    }
+    int rc = bases ? power_constants(bases, plan->n_weights, log2_base, ln_base) : RF_OK;
+    if (rc != RF_OK) return rc;
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
     const int P = plan->n_planes, K = plan->n_weights;
     const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
     for (int pl = 0; pl < P; pl++) {
-        if (!grad_out_planes[pl] || !grad_in_planes[pl] || (with_weights && !in_planes[pl])) { set_error("plane %d: null image pointer", pl); return RF_ERR_INVALID_ARG; }
-        if ((((uintptr_t)grad_out_planes[pl] | (uintptr_t)grad_in_planes[pl] | (uintptr_t)(with_weights ? in_planes[pl] : nullptr)) & 15u) != 0) {
-            set_error("plane %d: the varying scans need 16-byte aligned image pointers", pl);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    for (int k = 0; k < K; k++) {
-        if (!weight_planes[k]) { set_error("weight plane %d: null pointer", k); return RF_ERR_INVALID_ARG; }
-        if ((((uintptr_t)weight_planes[k] | (uintptr_t)(with_weights ? grad_weight_planes[k] : nullptr)) & 15u) != 0) {
-            set_error("weight plane %d: the varying scans need 16-byte aligned pointers (the plane and its gradient)", k);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    // what is written (grad_in planes, weight-gradient planes) against everything that is read and everything else that is written
-    const int n_written = P + (with_weights ? K : 0);
-    auto written = [&](int i) -> const void * { return i < P ? grad_in_planes[i] : grad_weight_planes[i - P]; };
-    auto written_name = [&](int i, char *buf, size_t n) {
-        if (i < P) std::snprintf(buf, n, "grad_in plane %d", i);
-        else std::snprintf(buf, n, "gradient of weight plane %d", i - P);
-    };
-    for (int i = 0; i < n_written; i++) {
-        const void *o = written(i);
-        if (!o) continue;
-        char name[64];
-        written_name(i, name, sizeof name);
-        for (int k = 0; k < K; k++)
-            if (overlap(o, plane_bytes, weight_planes[k], plane_bytes)) {
-                set_error("%s overlaps weight plane %d: every stage reads the weights after it has begun to store", name, k);
-                return RF_ERR_INVALID_ARG;
-            }
-        if (in_planes)
-            for (int pl = 0; pl < P; pl++)
-                if (in_planes[pl] && overlap(o, plane_bytes, in_planes[pl], plane_bytes)) {
-                    set_error("%s overlaps input plane %d", name, pl);
-                    return RF_ERR_INVALID_ARG;
-                }
-        for (int j = i + 1; j < n_written; j++)
-            if (written(j) && overlap(o, plane_bytes, written(j), plane_bytes)) {
-                char other[64];
-                written_name(j, other, sizeof other);
-                set_error("%s overlaps %s", name, other);
-                return RF_ERR_INVALID_ARG;
-            }
-        for (int pl = 0; pl < P; pl++) {
-            if (i == pl && o == grad_out_planes[pl]) continue;      // in place: a plane and its own gradient, exactly
-            if (overlap(o, plane_bytes, grad_out_planes[pl], plane_bytes)) {
-                set_error("%s overlaps grad_out plane %d (only grad_in plane %d may, and then exactly)", name, pl, pl);
-                return RF_ERR_INVALID_ARG;
-            }
-        }
-    }
-    RF_HIP_CHECK(hipSetDevice(plan->device));
-    if (with_weights) {
-        int rc = ensure_var_grad_planes(plan);
+        rc = check_plane("plane", pl, {{grad_out_planes[pl]}, {grad_in_planes[pl]}, {with_weights ? in_planes[pl] : nullptr, with_weights}}, 15u,
+                         "null image pointer", "the varying scans need 16-byte aligned image pointers");
         if (rc != RF_OK) return rc;
     }
-    // events are destroyed on every return path
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } events;
-    const size_t n_kernels = plan->backward_names[with_weights ? 1 : 0].size();
-    if (ms_out) {
-        for (size_t i = 0; i < n_kernels; i++) ms_out[i] = 0.0f;
-        for (size_t i = 0; i < n_kernels + 1; i++) {
-            hipEvent_t e;
-            RF_HIP_CHECK(hipEventCreate(&e));
-            events.ev.push_back(e);
-        }
-        RF_HIP_CHECK(hipEventRecord(events.ev[0], stream));
+    for (int k = 0; k < K; k++) {
+        rc = check_plane("weight plane", k, {{weight_planes[k]}, {with_weights ? grad_weight_planes[k] : nullptr, false}}, 15u, "null pointer",
+                         "the varying scans need 16-byte aligned pointers (the plane and its gradient)");
+        if (rc != RF_OK) return rc;
     }
-    size_t launch = 0;
-    const std::function<int()> mark = [&]() -> int {
-        launch++;
-        if (ms_out) RF_HIP_CHECK(hipEventRecord(events.ev[launch], stream));
-        return RF_OK;
-    };
-    std::vector<size_t> skipped;      // slots of var_grad launches that were not issued
-    const std::function<void()> skip = [&]() { skipped.push_back(launch); };
+    // what is written (grad_in planes, weight-gradient planes) against everything that is read and everything else that is written
+    const PlaneList written[2] = {{"grad_in", (const void *const *)grad_in_planes, P, plane_bytes},
+                                  {"gradient of weight", (const void *const *)grad_weight_planes, with_weights ? K : 0, plane_bytes}};
+    const PlaneList read[2] = {{"weight", weight_planes, K, plane_bytes, ": every stage reads the weights after it has begun to store"},
+                               {"input", in_planes, in_planes ? P : 0, plane_bytes}};
+    rc = check_written_planes(written, 2, read, 2, {"grad_out", grad_out_planes, P, plane_bytes});
+    if (rc != RF_OK) return rc;
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    if (with_weights) {
+        rc = ensure_var_grad_planes(plan);
+        if (rc != RF_OK) return rc;
+    }
+    LaunchTimer timer(stream, ms_out, plan->backward_names[with_weights ? 1 : 0].size());
+    if (timer.status() != RF_OK) return timer.status();
     VarBackwardIo io{};
     io.in = in_planes;
     io.weights = weight_planes;
@@ -404,14 +395,8 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
     io.grad_weights = with_weights ? grad_weight_planes : nullptr;
     io.log2_base = bases ? log2_base : nullptr;
     io.ln_base = bases ? ln_base : nullptr;
-    int rc = launch_var_backward(plan, io, stream, mark, skip);
-    if (rc != RF_OK) return rc;
-    if (ms_out) {
-        RF_HIP_CHECK(hipEventSynchronize(events.ev.back()));
-        for (size_t i = 0; i < n_kernels; i++) RF_HIP_CHECK(hipEventElapsedTime(&ms_out[i], events.ev[i], events.ev[i + 1]));
-        for (size_t i : skipped) ms_out[i] = 0.0f;
-    }
-    return RF_OK;
+    rc = launch_var_backward(plan, io, stream, timer);
+    return rc == RF_OK ? timer.finish() : rc;
 }
 
 int ensure_var_grad_planes(rf_var_plan *plan) {
@@ -425,38 +410,34 @@ int ensure_var_grad_planes(rf_var_plan *plan) {
     return RF_OK;
 }
 
-int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, const std::function<int()> &mark,
-                        const std::function<void()> &skip) {
+int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, LaunchTimer &timer) {
     const int P = plan->n_planes, S = (int)plan->scans.size();
     const bool with_weights = io.grad_weights != nullptr, power = io.log2_base != nullptr;
     const size_t plane_floats = (size_t)(plan->width * plan->height);
     // [scan][image][plane]; scan == S: the state
     auto saved = [&](int scan, int pl) { return plan->grad_planes + ((size_t)scan * (size_t)plan->batch * P + pl) * plane_floats; };
     const int64_t saved_stride = (int64_t)P * (int64_t)plane_floats;
-    auto form = [&](VarArgs &a, const rf_var_scan_desc &sc) {
+    // one single-scan stage's arguments, planes aside
+    auto stage_args = [&](const rf_var_scan_desc &sc, int mode) {
+        VarArgs a = scan_args(plan, sc.dim, io.weights[sc.weights], mode);
         a.power = power ? 1 : 0;
         a.log2_base = power ? io.log2_base[sc.weights] : 0.0f;
         a.weights_stride = io.weights_stride;
+        return a;
     };
     int rc = RF_OK;
     if (with_weights) {
         // the forward again, scan by scan, every output kept: scan q reads scan q-1's planes
         for (int q = 0; q < S && rc == RF_OK; q++) {
             const rf_var_scan_desc &sc = plan->scans[q];
-            VarArgs a = scan_args(plan, sc, io.weights, sc.causal != 0 ? VAR_CAUSAL : VAR_ANTICAUSAL);
-            form(a, sc);
+            VarArgs a = stage_args(sc, sc.causal != 0 ? VAR_CAUSAL : VAR_ANTICAUSAL);
             for (int pl = 0; pl < P; pl++) {
                 a.src[pl] = q == 0 ? io.in[pl] : saved(q - 1, pl);
                 a.dst[pl] = saved(q, pl);
             }
             a.src_stride = q == 0 ? io.in_stride : saved_stride;
             a.dst_stride = saved_stride;
-            rc = launch_var_tails(a, sc.dim, stream);
-            if (rc == RF_OK) rc = mark();
-            if (rc == RF_OK) rc = launch_var_carry(a, stream);
-            if (rc == RF_OK) rc = mark();
-            if (rc == RF_OK) rc = launch_var_pass2(a, sc.dim, stream);
-            if (rc == RF_OK) rc = mark();
+            rc = launch_stage(a, sc.dim, stream, timer);
         }
     }
     bool touched[RF_VAR_MAX_SCANS] = {};
@@ -466,8 +447,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
         const rf_var_scan_desc &sc = plan->scans[q];
         float *const grad = with_weights ? (float *)io.grad_weights[sc.weights] : nullptr;
         // the adjoint of a causal scan runs anticausally, and the other way round
-        VarArgs a = scan_args(plan, sc, io.weights, sc.causal != 0 ? VAR_ANTICAUSAL : VAR_CAUSAL);
-        form(a, sc);
+        VarArgs a = stage_args(sc, sc.causal != 0 ? VAR_ANTICAUSAL : VAR_CAUSAL);
         a.adjoint = 1;
         for (int pl = 0; pl < P; pl++) {
             a.src[pl] = q == S - 1 ? io.grad_out[pl] : io.grad_in[pl];
@@ -477,12 +457,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
         a.src_stride = q == S - 1 ? io.grad_out_stride : io.grad_in_stride;
         a.dst_stride = io.grad_in_stride;
         a.lam_stride = saved_stride;
-        rc = launch_var_tails(a, sc.dim, stream);
-        if (rc == RF_OK) rc = mark();
-        if (rc == RF_OK) rc = launch_var_carry(a, stream);
-        if (rc == RF_OK) rc = mark();
-        if (rc == RF_OK) rc = launch_var_pass2(a, sc.dim, stream);
-        if (rc == RF_OK) rc = mark();
+        rc = launch_stage(a, sc.dim, stream, timer);
         if (rc != RF_OK || !with_weights) continue;
         if (grad) {                                   // (a weight plane without a gradient: no launch, its slot reports 0 ms)
             VarGradArgs g{};
@@ -509,29 +484,52 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
             touched[sc.weights] = true;
             rc = launch_var_grad(g, sc.dim, sc.causal != 0, stream);
         } else {
-            skip();
+            timer.skip();
         }
-        if (rc == RF_OK) rc = mark();
+        if (rc == RF_OK) rc = timer.mark();
     }
     return rc;
 }
 
-int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
-                      void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch, int64_t guide_stride) {
+namespace {
+
+// What run_var_distances and run_var_distances_backward refuse alike, in three parts: each checks pointers of its own (and the
+// backward `accumulate`) between them.  `kernel` names the launch in the message.
+int check_distance_counts(int32_t n_guide, int64_t width, int64_t height) {
     if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
     if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
-    if (!guide_planes || !dx || !dy) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if (!guide_planes[ch]) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
+int check_distance_scale(float scale) {
     if (!std::isfinite(scale) || scale < 0.0f) { set_error("scale must be finite and not negative (got %g)", (double)scale); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
+int check_distance_extents(const char *kernel, int64_t width, int64_t height) {
     if (width % 4 != 0) {
-        set_error("var_distances moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)width);
+        set_error("%s moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", kernel, (long long)width);
         return RF_ERR_UNSUPPORTED;
     }
     if (width > kVarMaxExtent || height > kVarMaxExtent) {
         set_error("extents %lld x %lld are above %lld", (long long)width, (long long)height, (long long)kVarMaxExtent);
         return RF_ERR_UNSUPPORTED;
     }
+    return RF_OK;
+}
+
+}  // namespace
+
+int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
+                      void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch, int64_t guide_stride) {
+    int rc = check_distance_counts(n_guide, width, height);
+    if (rc != RF_OK) return rc;
+    if (!guide_planes || !dx || !dy) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (!guide_planes[ch]) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
+    rc = check_distance_scale(scale);
+    if (rc == RF_OK) rc = check_distance_extents("var_distances", width, height);
+    if (rc != RF_OK) return rc;
     if ((((uintptr_t)dx | (uintptr_t)dy) & 15u) != 0) { set_error("dx and dy must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
     const uintptr_t guide_align = guide_u8 ? 3u : 15u;
     for (int ch = 0; ch < n_guide; ch++)
@@ -540,12 +538,10 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
             return RF_ERR_INVALID_ARG;
         }
     const size_t samples = (size_t)(width * height), out_bytes = samples * sizeof(float), guide_bytes = samples * (guide_u8 ? 1 : sizeof(float));
-    auto overlap = [](uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; };
-    if (overlap((uintptr_t)dx, out_bytes * (size_t)batch, (uintptr_t)dy, out_bytes * (size_t)batch)) { set_error("dx overlaps dy"); return RF_ERR_INVALID_ARG; }
+    if (overlap(dx, out_bytes * (size_t)batch, dy, out_bytes * (size_t)batch)) { set_error("dx overlaps dy"); return RF_ERR_INVALID_ARG; }
     // (a batch comes from plan_smooth.cpp: dx and dy are the plan's own planes, which no plane of a caller overlaps)
     for (int ch = 0; ch < n_guide && batch == 1; ch++)
-        if (overlap((uintptr_t)dx, out_bytes, (uintptr_t)guide_planes[ch], guide_bytes) ||
-            overlap((uintptr_t)dy, out_bytes, (uintptr_t)guide_planes[ch], guide_bytes)) {
+        if (overlap(dx, out_bytes, guide_planes[ch], guide_bytes) || overlap(dy, out_bytes, guide_planes[ch], guide_bytes)) {
             set_error("guide plane %d overlaps dx or dy: a lane reads its neighbours' samples", ch);
             return RF_ERR_INVALID_ARG;
         }
@@ -566,21 +562,16 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
                                const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
                                int32_t batch, int64_t guide_stride, int64_t grad_guide_stride) {
-    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
-    if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
+    int rc = check_distance_counts(n_guide, width, height);
+    if (rc != RF_OK) return rc;
     if (!guide_planes || !grad_dx || !grad_dy || !grad_guide_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     for (int ch = 0; ch < n_guide; ch++)
         if (!guide_planes[ch] || !grad_guide_planes[ch]) { set_error("guide plane %d: null pointer (the plane or its gradient)", ch); return RF_ERR_INVALID_ARG; }
-    if (!std::isfinite(scale) || scale < 0.0f) { set_error("scale must be finite and not negative (got %g)", (double)scale); return RF_ERR_INVALID_ARG; }
+    rc = check_distance_scale(scale);
+    if (rc != RF_OK) return rc;
     if (accumulate != 0 && accumulate != 1) { set_error("accumulate must be 0 or 1 (got %d)", accumulate); return RF_ERR_INVALID_ARG; }
-    if (width % 4 != 0) {
-        set_error("var_distances_grad moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)width);
-        return RF_ERR_UNSUPPORTED;
-    }
-    if (width > kVarMaxExtent || height > kVarMaxExtent) {
-        set_error("extents %lld x %lld are above %lld", (long long)width, (long long)height, (long long)kVarMaxExtent);
-        return RF_ERR_UNSUPPORTED;
-    }
+    rc = check_distance_extents("var_distances_grad", width, height);
+    if (rc != RF_OK) return rc;
     if ((((uintptr_t)grad_dx | (uintptr_t)grad_dy) & 15u) != 0) { set_error("grad_dx and grad_dy must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
     for (int ch = 0; ch < n_guide; ch++)
         if ((((uintptr_t)guide_planes[ch] | (uintptr_t)grad_guide_planes[ch]) & 15u) != 0) {

@@ -1,7 +1,7 @@
 // plan_var.h -- the plan behind the rf_var_plan_* entry points: spatially varying first-order scans (plan_var.cpp).
 #pragma once
 
-#include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -47,13 +47,64 @@ struct rf_var_plan {
 
 namespace rf {
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch = 1);
+
+// The events of one timed run: slot i of ms_out receives the time from the i-th mark (the construction is mark 0) to the next.
+// ms_out == nullptr: a plain asynchronous run -- no event is created and every method returns RF_OK.  The events are destroyed
+// on every path.  n_slots: the launches of the run, one name each (the caller of the run function has checked the capacity).
+class LaunchTimer {
+public:
+    LaunchTimer(hipStream_t stream, float *ms_out, size_t n_slots);      // zero-fills ms_out; look at status() before launching
+    ~LaunchTimer();
+    LaunchTimer(const LaunchTimer &) = delete;
+    LaunchTimer &operator=(const LaunchTimer &) = delete;
+    int status() const { return status_; }
+    int mark();         // behind every launch, and behind every slot whose launch was not issued
+    void skip();        // just before mark(), for a slot whose launch was not issued: it reports 0 ms
+    int finish();       // synchronises with the last mark and fills ms_out
+private:
+    int create();
+    hipStream_t stream_;
+    float *ms_out_;
+    size_t n_slots_, marks_ = 0;
+    int status_ = RF_OK;
+    std::vector<hipEvent_t> events_;
+    std::vector<size_t> skipped_;
+};
+
+// ---- checks the run functions of plan_var.cpp and plan_smooth.cpp share ---------------------------------------------------------
+inline bool overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+
+// Plane `index` of one or more arrays of a call: no pointer that is `required` is null, and every pointer (a null one passes) is
+// aligned to mask + 1 bytes.  The refusals read "<what> <index>: <null_text>" and "<what> <index>: <align_text>".
+struct PlanePointer {
+    const void *p;
+    bool required = true;
+};
+int check_plane(const char *what, int index, std::initializer_list<PlanePointer> pointers, uintptr_t mask, const char *null_text, const char *align_text);
+
+// The aliasing rules of a single-image backward call: every plane that is written against every plane that is read, every other
+// plane that is written, and the gradient it is computed from -- which alone it may be, plane for plane and exactly, and only
+// written[0] (the image gradient: in place).  `noun` is how the messages name a plane of the array ("<noun> plane <index>"),
+// `why` what follows where a written plane overlaps one of a read array.  Null planes are passed over.
+struct PlaneList {
+    const char *noun;
+    const void *const *planes;
+    int n;
+    size_t bytes;            // of one plane
+    const char *why = "";
+};
+int check_written_planes(const PlaneList *written, int n_written, const PlaneList *read, int n_read, const PlaneList &grad_out);
+
+// The power form's constants: bases[k] inside (0, 1) for each of the n_weights planes, or a refusal; log2 and ln of each.
+int power_constants(const float *bases, int n_weights, float *log2_base, float *ln_base);
+
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
 // bases == nullptr: `weight_planes` hold weights; else they hold exponents and bases[k] is the base of plane k (the power form)
 int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
                  void *const *out_planes, hipStream_t stream, float *ms_out);
 // The launches of one run of `plan`, nothing checked (run_var_plan and plan_smooth.cpp check first).  The first stage reads `in`
 // (f32, or bytes: in_u8); the stages write `work` (f32) and later stages filter it in place; the final pass of the last stage
-// stores to `out` (f32 -- then out is work -- or bytes: out_u8).  log2_base == nullptr: the plane form.  `mark` is called behind
+// stores to `out` (f32 -- then out is work -- or bytes: out_u8).  log2_base == nullptr: the plane form.  `timer` is marked behind
 // every launch.  A batched plan: the arrays name image 0's planes and the strides are samples from image to image.
 struct VarIo {
     const void *const *in = nullptr;
@@ -62,7 +113,7 @@ struct VarIo {
     int64_t in_stride = 0, work_stride = 0, out_stride = 0, weights_stride = 0;
 };
 int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *weight_planes, const float *log2_base, hipStream_t stream,
-                      const std::function<int()> &mark);
+                      LaunchTimer &timer);
 // The adjoint of the plan (rf_var_plan_backward in recfilter_amd.h).  grad_weight_planes: nullptr, or n_weights entries, each nullptr
 // (no gradient for that plane) or a plane.  ms_out as in run_var_plan, one slot per name of backward_names[with weight gradients].
 // bases == nullptr: the plane form; else the power form (rf_var_plan_backward_power): `weight_planes` hold exponents and the
@@ -73,8 +124,8 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
 // The launches of one backward run of `plan`, nothing checked (run_var_backward and plan_smooth.cpp check first, and call
 // ensure_var_grad_planes where grad_weights is not null).  grad_weights: nullptr (3 launches per scan), or n_weights entries.
 // log2_base / ln_base: nullptr for the plane form, else per weight plane.  holds_sum: nullptr, or per weight plane whether its
-// gradient plane already holds a sum this run adds to (else the first var_grad launch that touches a plane stores).  `mark` is
-// called behind every launch and behind every var_grad slot that was not issued; `skip` just before mark for such a slot.
+// gradient plane already holds a sum this run adds to (else the first var_grad launch that touches a plane stores).  `timer` is
+// marked behind every launch and behind every var_grad slot that was not issued, which is skipped first.
 struct VarBackwardIo {
     const void *const *in = nullptr, *const *weights = nullptr, *const *grad_out = nullptr;
     void *const *grad_in = nullptr, *const *grad_weights = nullptr;
@@ -83,8 +134,7 @@ struct VarBackwardIo {
     int64_t in_stride = 0, weights_stride = 0, grad_out_stride = 0, grad_in_stride = 0, grad_weights_stride = 0;      // a batched plan
 };
 int ensure_var_grad_planes(rf_var_plan *plan);
-int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, const std::function<int()> &mark,
-                        const std::function<void()> &skip);
+int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, LaunchTimer &timer);
 int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
 // batch > 1 (plan_smooth.cpp): image b's guide planes are guide_stride samples behind image 0's, dx and dy hold `batch` dense planes
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,

@@ -28,10 +28,64 @@ from . import capi
 VarScan = Tuple[int, bool, int]      # (dim, causal, index of the weight plane); dim 0 = x
 
 
-class VarPlan:
+def _aligned_contiguous(t):
+    """what the library takes: contiguous, 16-byte aligned"""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _plane_pointer(t, shape, dtype, dtype_text: str, what: str) -> int:
+    """the address of one plane, after the checks every plane of a call gets"""
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what}: shape {tuple(t.shape)} != plan shape {shape}")
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: {dtype_text} planes only, got {t.dtype}")
+    if not t.is_cuda or not t.is_contiguous():
+        raise ValueError("planes must be contiguous device tensors")
+    return t.data_ptr()
+
+
+def _timed(call, n: int):
+    """[(kernel name, ms), ...] of a *_timed entry point with `n` launches: call(ms, names, n) returns its status"""
+    ms = (ctypes.c_float * max(n, 1))()
+    names = (ctypes.c_char_p * max(n, 1))()
+    capi.check(call(ms, names, n))
+    return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+class _PlanHandle:
+    """the lifetime of the library's plan behind self._h; `_destroy` names the entry point that frees it"""
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(capi.lib(), self._destroy)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _stream(stream) -> ctypes.c_void_p:
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return ctypes.c_void_p(s.cuda_stream)
+
+
+class VarPlan(_PlanHandle):
     """A list of at most capi.RF_VAR_MAX_SCANS scans  y[i] = (1 - w[i]) x[i] + w[i] y[i-1]  (causal; the anticausal one couples
     sample i to i+1 through w[i+1]) over `planes` f32 planes of `shape` = (height, width) that share `n_weights` weight planes.
     Element 0 of a weight plane along the scanned dimension is never used.  One plan owns one workspace: order its executes."""
+    _destroy = "rf_var_plan_destroy"
 
     def __init__(self, shape: Sequence[int], scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1):
         L = capi.lib()
@@ -60,24 +114,6 @@ class VarPlan:
         self._h = ctypes.c_void_p()
         capi.check(L.rf_var_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
 
-    # -- lifetime ---------------------------------------------------------------------------
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            capi.lib().rf_var_plan_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     # -- queries ----------------------------------------------------------------------------
     @property
     def workspace_bytes(self) -> int:
@@ -94,48 +130,32 @@ class VarPlan:
             raise ValueError(f"expected {count} {what} planes, got {len(tensors)}")
         arr = (ctypes.c_void_p * count)()
         for i, t in enumerate(tensors):
-            if tuple(t.shape) != self.shape:
-                raise ValueError(f"{what} plane {i}: shape {tuple(t.shape)} != plan shape {self.shape}")
-            if t.dtype != torch.float32:
-                raise TypeError(f"{what} plane {i}: float32 planes only, got {t.dtype}")
-            if not t.is_cuda or not t.is_contiguous():
-                raise ValueError("planes must be contiguous device tensors")
-            arr[i] = t.data_ptr()
+            arr[i] = _plane_pointer(t, self.shape, torch.float32, "float32", f"{what} plane {i}")
         return arr
 
-    @staticmethod
-    def _stream(stream) -> ctypes.c_void_p:
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return ctypes.c_void_p(s.cuda_stream)
-
-    def _arguments(self, ins, weights, outs):
+    def _arguments(self, ins, weights, outs, stream):
+        """(input, weight and output pointers, the outputs, the stream's handle)"""
         import torch
         if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from)
+            # (the library refuses; there are no device tensors to take pointers from, and no stream)
             nulls = lambda n: (ctypes.c_void_p * n)()      # noqa: E731
             return nulls(self.planes), nulls(self.n_weights), nulls(self.planes), None, ctypes.c_void_p()
         if outs is None:
             outs = [torch.empty_like(t) for t in ins]
         return (self._pointers(ins, self.planes, "input"), self._pointers(weights, self.n_weights, "weight"),
-                self._pointers(outs, self.planes, "output"), outs, None)
+                self._pointers(outs, self.planes, "output"), outs, self._stream(stream))
 
     def execute(self, ins, weights, outs=None, stream=None):
         """rf_var_plan_execute: asynchronous on `stream` (default: torch's current stream).  outs=None allocates the outputs;
         outs may be the inputs themselves (in place)."""
-        pin, pw, pout, outs, host_stream = self._arguments(ins, weights, outs)
-        capi.check(capi.lib().rf_var_plan_execute(self._h, pin, pw, pout, host_stream if host_stream is not None else self._stream(stream)))
+        pin, pw, pout, outs, s = self._arguments(ins, weights, outs, stream)
+        capi.check(capi.lib().rf_var_plan_execute(self._h, pin, pw, pout, s))
         return outs
 
     def execute_timed(self, ins, weights, outs=None, stream=None):
         """rf_var_plan_execute_timed: (outputs, [(kernel name, ms), ...]) measured with HIP events; synchronises the stream."""
-        pin, pw, pout, outs, host_stream = self._arguments(ins, weights, outs)
-        n = self.num_kernels
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_var_plan_execute_timed(self._h, pin, pw, pout,
-                                                        host_stream if host_stream is not None else self._stream(stream), ms, names, n))
-        return outs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        pin, pw, pout, outs, s = self._arguments(ins, weights, outs, stream)
+        return outs, _timed(lambda *report: capi.lib().rf_var_plan_execute_timed(self._h, pin, pw, pout, s, *report), self.num_kernels)
 
     def _bases(self, bases) -> ctypes.Array:
         bases = [float(b) for b in bases]
@@ -147,22 +167,15 @@ class VarPlan:
         """rf_var_plan_execute_power: as execute, but plane k of `exponents` holds d >= 0 and the scans use
         w = exp2(d * log2(bases[k])), formed in the kernels; 0 < bases[k] < 1, one per exponent plane."""
         pb = self._bases(bases)
-        pin, pd, pout, outs, host_stream = self._arguments(ins, exponents, outs)
-        capi.check(capi.lib().rf_var_plan_execute_power(self._h, pin, pd, pb, pout,
-                                                        host_stream if host_stream is not None else self._stream(stream)))
+        pin, pd, pout, outs, s = self._arguments(ins, exponents, outs, stream)
+        capi.check(capi.lib().rf_var_plan_execute_power(self._h, pin, pd, pb, pout, s))
         return outs
 
     def execute_power_timed(self, ins, exponents, bases, outs=None, stream=None):
         """rf_var_plan_execute_power_timed: (outputs, [(kernel name, ms), ...]); the launches execute_timed names."""
         pb = self._bases(bases)
-        pin, pd, pout, outs, host_stream = self._arguments(ins, exponents, outs)
-        n = self.num_kernels
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_var_plan_execute_power_timed(self._h, pin, pd, pb, pout,
-                                                              host_stream if host_stream is not None else self._stream(stream),
-                                                              ms, names, n))
-        return outs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        pin, pd, pout, outs, s = self._arguments(ins, exponents, outs, stream)
+        return outs, _timed(lambda *report: capi.lib().rf_var_plan_execute_power_timed(self._h, pin, pd, pb, pout, s, *report), self.num_kernels)
 
     # -- the adjoint ------------------------------------------------------------------------
     def backward_num_kernels(self, with_weights: bool = False) -> int:
@@ -174,10 +187,11 @@ class VarPlan:
         workspace_bytes: (scans + 1) * planes f32 planes; 0 without weight gradients"""
         return int(capi.lib().rf_var_plan_backward_workspace_bytes(self._h, int(bool(with_weights))))
 
-    def _backward_arguments(self, ins, weights, grad_outs, grad_ins, grad_weights):
+    def _backward_arguments(self, ins, weights, grad_outs, grad_ins, grad_weights, stream):
+        """(the five pointer arrays, grad_ins, grad_weights, the stream's handle)"""
         import torch
         if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from)
+            # (the library refuses; there are no device tensors to take pointers from, and no stream)
             nulls = lambda n: (ctypes.c_void_p * n)()      # noqa: E731
             return (nulls(self.planes) if ins is not None else None, nulls(self.n_weights), nulls(self.planes), nulls(self.planes),
                     nulls(self.n_weights) if grad_weights is not None else None, None, None, ctypes.c_void_p())
@@ -193,7 +207,7 @@ class VarPlan:
                     pgw[k] = self._pointers([t], 1, f"gradient of weight plane {k}:")[0]
         return (self._pointers(ins, self.planes, "input") if ins is not None else None, self._pointers(weights, self.n_weights, "weight"),
                 self._pointers(grad_outs, self.planes, "grad_out"), self._pointers(grad_ins, self.planes, "grad_in"), pgw,
-                grad_ins, grad_weights, None)
+                grad_ins, grad_weights, self._stream(stream))
 
     def backward(self, ins, weights, grad_outs, grad_ins=None, grad_weights=None, stream=None):
         """rf_var_plan_backward, the adjoint of execute: (grad_ins, grad_weights) from grad_outs = dL/d(outs).  grad_ins=None
@@ -201,41 +215,31 @@ class VarPlan:
         be None too), or a list of n_weights entries, each a plane to be WRITTEN or None for a plane that needs no gradient; a
         plane no scan reads is left as it is.  Asynchronous on `stream` (default: torch's current stream); uses the plan's
         workspace like an execute."""
-        pin, pw, pgo, pgi, pgw, grad_ins, grad_weights, host_stream = self._backward_arguments(ins, weights, grad_outs, grad_ins, grad_weights)
-        capi.check(capi.lib().rf_var_plan_backward(self._h, pin, pw, pgo, pgi, pgw,
-                                                   host_stream if host_stream is not None else self._stream(stream)))
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_weights, s = self._backward_arguments(ins, weights, grad_outs, grad_ins, grad_weights, stream)
+        capi.check(capi.lib().rf_var_plan_backward(self._h, pin, pw, pgo, pgi, pgw, s))
         return grad_ins, grad_weights
 
     def backward_timed(self, ins, weights, grad_outs, grad_ins=None, grad_weights=None, stream=None):
         """rf_var_plan_backward_timed: (grad_ins, grad_weights, [(kernel name, ms), ...]); synchronises the stream.  The var_grad
         launch of a weight plane without a gradient is skipped and reports 0 ms."""
-        pin, pw, pgo, pgi, pgw, grad_ins, grad_weights, host_stream = self._backward_arguments(ins, weights, grad_outs, grad_ins, grad_weights)
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_weights, s = self._backward_arguments(ins, weights, grad_outs, grad_ins, grad_weights, stream)
         n = self.backward_num_kernels(grad_weights is not None and any(t is not None for t in grad_weights))
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_var_plan_backward_timed(self._h, pin, pw, pgo, pgi, pgw,
-                                                         host_stream if host_stream is not None else self._stream(stream), ms, names, n))
-        return grad_ins, grad_weights, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        return grad_ins, grad_weights, _timed(lambda *report: capi.lib().rf_var_plan_backward_timed(self._h, pin, pw, pgo, pgi, pgw, s, *report), n)
 
     def backward_power(self, ins, exponents, bases, grad_outs, grad_ins=None, grad_exponents=None, stream=None):
         """rf_var_plan_backward_power, the adjoint of execute_power: (grad_ins, grad_exponents).  As backward, with the exponent
         planes and their bases in the place of the weights; a gradient plane receives dL/dd = (w ln base) dL/dw."""
         pb = self._bases(bases)
-        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, host_stream = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents)
-        capi.check(capi.lib().rf_var_plan_backward_power(self._h, pin, pw, pb, pgo, pgi, pgw,
-                                                         host_stream if host_stream is not None else self._stream(stream)))
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, s = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents, stream)
+        capi.check(capi.lib().rf_var_plan_backward_power(self._h, pin, pw, pb, pgo, pgi, pgw, s))
         return grad_ins, grad_exponents
 
     def backward_power_timed(self, ins, exponents, bases, grad_outs, grad_ins=None, grad_exponents=None, stream=None):
         """rf_var_plan_backward_power_timed: (grad_ins, grad_exponents, [(kernel name, ms), ...]); the launches backward_timed names"""
         pb = self._bases(bases)
-        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, host_stream = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents)
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, s = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents, stream)
         n = self.backward_num_kernels(grad_exponents is not None and any(t is not None for t in grad_exponents))
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_var_plan_backward_power_timed(self._h, pin, pw, pb, pgo, pgi, pgw,
-                                                               host_stream if host_stream is not None else self._stream(stream), ms, names, n))
-        return grad_ins, grad_exponents, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        return grad_ins, grad_exponents, _timed(lambda *report: capi.lib().rf_var_plan_backward_power_timed(self._h, pin, pw, pb, pgo, pgi, pgw, s, *report), n)
 
     def apply_power(self, ins, exponents, bases):
         """execute_power, out of place, as a differentiable torch operation: values bit for bit execute_power's.  Backward is
@@ -266,10 +270,7 @@ def _var_scan_function():
     if _function is not None:
         return _function
     import torch
-
-    def plane(t):      # what the library takes: contiguous, 16-byte aligned
-        t = t.contiguous()
-        return t.clone() if t.data_ptr() % 16 else t
+    plane = _aligned_contiguous
 
     class VarScanFunction(torch.autograd.Function):
         @staticmethod
@@ -417,7 +418,7 @@ def domain_transform_distances_backward(guide, sigma_s: float, sigma_r: float, g
     return grad_guide
 
 
-class SmoothPlan:
+class SmoothPlan(_PlanHandle):
     """rf_smooth_plan_*: the domain-transform recursive filter of `planes` image planes of `shape_hw` = (height, width), f32 or
     uint8 (uint8: input AND output; out = sat8 of the f32 filter on the widened bytes, rounded once, at the final store).
     guide_planes = 0: the image guides itself; else that many separate guide planes of `guide_dtype`.  A byte guide means that
@@ -427,6 +428,7 @@ class SmoothPlan:
     one image.  Image, output and gradient tensors are then contiguous (N, planes, H, W) device tensors and the guide
     (N, guide_planes, H, W); every image is filtered with its own edges, bit for bit as a plan without a batch filters it.
     batch=None: one image, through rf_smooth_plan_create."""
+    _destroy = "rf_smooth_plan_destroy"
 
     def __init__(self, shape_hw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
                  iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, device: int = -1, batch: Optional[int] = None):
@@ -462,24 +464,6 @@ class SmoothPlan:
             b.image_stride = d.n_planes * d.height * d.width
             b.guide_stride = d.n_guide * d.height * d.width
             capi.check(capi.lib().rf_smooth_plan_create_batched(ctypes.byref(d), ctypes.byref(b), ctypes.byref(self._h)))
-
-    # -- lifetime ---------------------------------------------------------------------------
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            capi.lib().rf_smooth_plan_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # -- queries ----------------------------------------------------------------------------
     @property
@@ -520,19 +504,14 @@ class SmoothPlan:
             raise ValueError(f"expected {count} {what} planes, got {len(tensor)}")
         arr = (ctypes.c_void_p * count)()
         for i, t in enumerate(tensor):
-            if tuple(t.shape) != self.shape:
-                raise ValueError(f"{what} plane {i}: shape {tuple(t.shape)} != plan shape {self.shape}")
-            if t.dtype != dtype:
-                raise TypeError(f"{what} plane {i}: {dtype} planes only, got {t.dtype}")
-            if not t.is_cuda or not t.is_contiguous():
-                raise ValueError("planes must be contiguous device tensors")
-            arr[i] = t.data_ptr()
+            arr[i] = _plane_pointer(t, self.shape, dtype, str(dtype), f"{what} plane {i}")
         return arr
 
-    def _arguments(self, image, guide, out):
+    def _arguments(self, image, guide, out, stream):
+        """(image, guide and output pointers, the output, the stream's handle)"""
         import torch
         if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from)
+            # (the library refuses; there are no device tensors to take pointers from, and no stream)
             nulls = lambda n: (ctypes.c_void_p * max(n, 1))()      # noqa: E731
             return nulls(self.planes), nulls(self.guide_planes) if self.guide_planes else None, nulls(self.planes), None, ctypes.c_void_p()
         if out is None:
@@ -544,25 +523,19 @@ class SmoothPlan:
             pg = self._pointers(guide, self.guide_planes, self.guide_dtype, "guide")
         elif self.guide_planes != 0:
             raise ValueError(f"this plan takes {self.guide_planes} separate guide planes")
-        return self._pointers(image, self.planes, self.image_dtype, "image"), pg, self._pointers(out, self.planes, self.image_dtype, "output"), out, None
+        return self._pointers(image, self.planes, self.image_dtype, "image"), pg, self._pointers(out, self.planes, self.image_dtype, "output"), out, self._stream(stream)
 
     def execute(self, image, guide=None, out=None, stream=None):
         """rf_smooth_plan_execute: asynchronous on `stream` (default: torch's current stream).  image, out: (C, H, W) or (H, W)
         device tensors of the plan's image dtype (or lists of (H, W) planes); out=None allocates it; out may be the image."""
-        pi, pg, po, out, host_stream = self._arguments(image, guide, out)
-        capi.check(capi.lib().rf_smooth_plan_execute(self._h, pi, pg, po, host_stream if host_stream is not None else VarPlan._stream(stream)))
+        pi, pg, po, out, s = self._arguments(image, guide, out, stream)
+        capi.check(capi.lib().rf_smooth_plan_execute(self._h, pi, pg, po, s))
         return out
 
     def execute_timed(self, image, guide=None, out=None, stream=None):
         """rf_smooth_plan_execute_timed: (output, [(kernel name, ms), ...]) measured with HIP events; synchronises the stream."""
-        pi, pg, po, out, host_stream = self._arguments(image, guide, out)
-        n = self.num_kernels
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_smooth_plan_execute_timed(self._h, pi, pg, po,
-                                                           host_stream if host_stream is not None else VarPlan._stream(stream), ms, names, n))
-        return out, [(names[i].decode(), float(ms[i])) for i in range(n)]
-
+        pi, pg, po, out, s = self._arguments(image, guide, out, stream)
+        return out, _timed(lambda *report: capi.lib().rf_smooth_plan_execute_timed(self._h, pi, pg, po, s, *report), self.num_kernels)
 
     # -- the adjoint ------------------------------------------------------------------------
     def backward_num_kernels(self, edges: bool = False) -> int:
@@ -574,10 +547,11 @@ class SmoothPlan:
         2 + (K - 1 + 5) * planes f32 planes; 0 without edges"""
         return int(capi.lib().rf_smooth_plan_backward_workspace_bytes(self._h, int(bool(edges))))
 
-    def _backward_arguments(self, image, guide, grad_out, grad_image, grad_guide, edges):
+    def _backward_arguments(self, image, guide, grad_out, grad_image, grad_guide, edges, stream):
+        """(the five pointer arrays, grad_image, grad_guide, the stream's handle)"""
         import torch
         if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from)
+            # (the library refuses; there are no device tensors to take pointers from, and no stream)
             nulls = lambda n: (ctypes.c_void_p * max(n, 1))()      # noqa: E731
             return (nulls(self.planes) if image is not None else None, nulls(self.guide_planes) if guide is not None else None,
                     nulls(self.planes), nulls(self.planes), nulls(self.guide_planes) if grad_guide is not None else None,
@@ -591,7 +565,7 @@ class SmoothPlan:
                 self._pointers(guide, self.guide_planes, self.guide_dtype, "guide") if guide is not None else None,
                 self._pointers(grad_out, self.planes, f32, "grad_out"), self._pointers(grad_image, self.planes, f32, "grad_image"),
                 self._pointers(grad_guide, self.guide_planes, f32, "grad_guide") if grad_guide is not None else None,
-                grad_image, grad_guide, None)
+                grad_image, grad_guide, self._stream(stream))
 
     def backward(self, image, guide, grad_out, grad_image=None, grad_guide=None, edges: bool = False, stream=None):
         """rf_smooth_plan_backward, the adjoint of execute for f32 images: (grad_image, grad_guide) from grad_out = dL/d(out).
@@ -599,20 +573,15 @@ class SmoothPlan:
         edges=True differentiates through them: with separate f32 guide planes grad_guide is written (allocated when None); where
         the image guides itself that gradient is added into grad_image.  grad_image=None allocates it; it may be grad_out (in
         place).  Asynchronous on `stream`; uses the plan's workspace like an execute."""
-        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, host_stream = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges)
-        capi.check(capi.lib().rf_smooth_plan_backward(self._h, pi, pg, pgo, pgi, pgg, int(edges),
-                                                      host_stream if host_stream is not None else VarPlan._stream(stream)))
+        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, s = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges, stream)
+        capi.check(capi.lib().rf_smooth_plan_backward(self._h, pi, pg, pgo, pgi, pgg, int(edges), s))
         return grad_image, grad_guide
 
     def backward_timed(self, image, guide, grad_out, grad_image=None, grad_guide=None, edges: bool = False, stream=None):
         """rf_smooth_plan_backward_timed: (grad_image, grad_guide, [(kernel name, ms), ...]); synchronises the stream"""
-        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, host_stream = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges)
-        n = self.backward_num_kernels(edges)
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_smooth_plan_backward_timed(self._h, pi, pg, pgo, pgi, pgg, int(edges),
-                                                            host_stream if host_stream is not None else VarPlan._stream(stream), ms, names, n))
-        return grad_image, grad_guide, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, s = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges, stream)
+        return grad_image, grad_guide, _timed(lambda *report: capi.lib().rf_smooth_plan_backward_timed(self._h, pi, pg, pgo, pgi, pgg, int(edges), s, *report),
+                                              self.backward_num_kernels(edges))
 
     def apply(self, image, guide=None):
         """execute, out of place, as a differentiable torch operation on f32 tensors (C, H, W) or (H, W): values bit for bit
@@ -630,10 +599,7 @@ def _smooth_function():
     if _smooth_fn is not None:
         return _smooth_fn
     import torch
-
-    def planes(t):      # what the library takes: contiguous, 16-byte aligned
-        t = t.contiguous()
-        return t.clone() if t.data_ptr() % 16 else t
+    planes = _aligned_contiguous
 
     class SmoothFunction(torch.autograd.Function):
         @staticmethod
@@ -667,70 +633,44 @@ _smooth_plan_objects: Dict[tuple, SmoothPlan] = {}
 
 
 def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=False):
+    """form="plan": one cached SmoothPlan on (C, H, W) or (H, W); on (N, C, H, W) one cached SmoothPlan(batch=N), by the same rules"""
     import torch
-    if image.dim() == 4:
-        return _smooth_by_batched_plan(image, guide, sigma_s, sigma_r, iterations, differentiable)
-    img = (image if image.dim() == 3 else image.unsqueeze(0))
-    if img.dim() != 3:
+    batched = image.dim() == 4
+    at = 1 if batched else 0      # where the planes are counted
+    img = image if batched or image.dim() == 3 else image.unsqueeze(0)
+    if img.dim() != 3 + at:
         raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
     if img.dtype != torch.uint8:
         img = img.to(torch.float32)
     img = img.contiguous()
     g = None
     if guide is not None:
-        g = guide if guide.dim() == 3 else guide.unsqueeze(0)
-        if g.dim() != 3:
+        if batched and guide.dim() != 4:
+            raise ValueError(f"a batched image (N, C, H, W) takes a guide (N, G, H, W), got {tuple(guide.shape)}")
+        g = guide if batched or guide.dim() == 3 else guide.unsqueeze(0)
+        if g.dim() != 3 + at:
             raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
         if g.dtype != torch.uint8:
             g = g.to(torch.float32)
         g = g.to(img.device).contiguous()
-        if tuple(g.shape[1:]) != tuple(img.shape[1:]):
-            raise ValueError("guide and image must have the same height and width")
-    C, H, W = (int(s) for s in img.shape)
+        if tuple(g.shape[:at]) != tuple(img.shape[:at]) or tuple(g.shape[at + 1:]) != tuple(img.shape[at + 1:]):
+            raise ValueError("guide and image must have the same " + ("batch size, height and width" if batched else "height and width"))
+    shape = tuple(int(s) for s in img.shape)      # (C, H, W), or (N, C, H, W)
     device = img.device.index if img.device.index is not None else torch.cuda.current_device()
-    key = (C, H, W, img.dtype, None if g is None else (int(g.shape[0]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), device)
+    key = shape + (img.dtype, None if g is None else (int(g.shape[at]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), device)
     plan = _smooth_plan_objects.get(key)
     if plan is None:
-        plan = _smooth_plan_objects[key] = SmoothPlan((H, W), planes=C, guide_planes=0 if g is None else int(g.shape[0]), image_dtype=img.dtype,
-                                                      guide_dtype=None if g is None else g.dtype, iterations=iterations, sigma_s=sigma_s,
-                                                      sigma_r=sigma_r, device=device)
+        plan = _smooth_plan_objects[key] = SmoothPlan(shape[-2:], planes=shape[at], guide_planes=0 if g is None else int(g.shape[at]),
+                                                      image_dtype=img.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
+                                                      sigma_s=sigma_s, sigma_r=sigma_r, device=device, batch=shape[0] if batched else None)
     if differentiable and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad)):
         if img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad):
             raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
         out = plan.apply(img, g)
-        return out if image.dim() == 3 else out[0]
-    with torch.cuda.device(img.device):
-        out = plan.execute(img, g)
-    return out if image.dim() == 3 else out[0]
-
-
-def _smooth_by_batched_plan(image, guide, sigma_s, sigma_r, iterations, differentiable):
-    """form="plan" on (N, C, H, W): one cached SmoothPlan(batch=N), the rules of the 3-D call"""
-    import torch
-    img = image if image.dtype == torch.uint8 else image.to(torch.float32)
-    img = img.contiguous()
-    g = None
-    if guide is not None:
-        if guide.dim() != 4:
-            raise ValueError(f"a batched image (N, C, H, W) takes a guide (N, G, H, W), got {tuple(guide.shape)}")
-        g = guide if guide.dtype == torch.uint8 else guide.to(torch.float32)
-        g = g.to(img.device).contiguous()
-        if int(g.shape[0]) != int(img.shape[0]) or tuple(g.shape[2:]) != tuple(img.shape[2:]):
-            raise ValueError("guide and image must have the same batch size, height and width")
-    N, C, H, W = (int(s) for s in img.shape)
-    device = img.device.index if img.device.index is not None else torch.cuda.current_device()
-    key = (N, C, H, W, img.dtype, None if g is None else (int(g.shape[1]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), device)
-    plan = _smooth_plan_objects.get(key)
-    if plan is None:
-        plan = _smooth_plan_objects[key] = SmoothPlan((H, W), planes=C, guide_planes=0 if g is None else int(g.shape[1]), image_dtype=img.dtype,
-                                                      guide_dtype=None if g is None else g.dtype, iterations=iterations, sigma_s=sigma_s,
-                                                      sigma_r=sigma_r, device=device, batch=N)
-    if differentiable and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad)):
-        if img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad):
-            raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
-        return plan.apply(img, g)
-    with torch.cuda.device(img.device):
-        return plan.execute(img, g)
+    else:
+        with torch.cuda.device(img.device):
+            out = plan.execute(img, g)
+    return out if image.dim() >= 3 else out[0]
 
 
 def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes",
