@@ -3,9 +3,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 
 #include "kernels.h"
+#include "pass2_select.h"
 #include "pixel.h"
 #include "rf_internal.h"
 
@@ -132,6 +136,95 @@ struct FusedArgs {
     }
 };
 
+// What every launcher of the fused path that puts MY and NZ into its grid does first.  *launch = false with RF_OK: no tiles,
+// nothing to do.
+template <typename Acc>
+inline int fused_grid_guard(const FusedArgs<Acc> &a, bool *launch) {
+    *launch = false;
+    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
+    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    *launch = true;
+    return RF_OK;
+}
+
+// More than 64 KiB of dynamic LDS has to be opted into once per kernel and device; every instance (Kernel) has its own flags.
+// (Concurrent plan creators / executors on different host threads may race to set it: the flag is atomic and the attribute call
+// itself is idempotent.)
+template <auto Kernel>
+inline int opt_in_dynamic_lds(size_t bytes) {
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    RF_HIP_CHECK(hipGetDevice(&dev));
+    std::atomic<bool> &done = attr_set[dev & 63];
+    if (!done.load(std::memory_order_acquire)) {
+        RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        done.store(true, std::memory_order_release);
+    }
+    return RF_OK;
+}
+
+// ---- the final pass's launchers and select_pass2 (pass2_select.h) ----
+template <typename T>
+constexpr int pass2_pixel() {
+    return std::is_same<T, float>::value ? kP2F32 : std::is_same<T, _Float16>::value ? kP2F16 : std::is_same<T, __bf16>::value ? kP2BF16 :
+           std::is_same<T, int32_t>::value ? kP2I32 : std::is_same<T, int16_t>::value ? kP2I16 : std::is_same<T, double>::value ? kP2F64 :
+           std::is_same<T, uint8_t>::value ? kP2U8 : kP2Other;
+}
+// the facts of a launch the rule reads
+template <typename Acc>
+inline Pass2Query pass2_query(bool tall, int dst, int src, int K, int TY, const FusedArgs<Acc> &a, bool edge_everywhere) {
+    Pass2Query q{};
+    q.tall = tall; q.dst = dst; q.src = src; q.K = K; q.TY = TY;
+    q.last_cols = a.last_cols; q.last_rows = a.last_rows; q.MX = a.MX; q.MY = a.MY; q.NX = a.NX; q.NZ = a.NZ; q.row_bytes = a.row_bytes;
+    q.nx = a.nx; q.ny = a.ny;
+    for (int s = 0; s < 2; s++) { q.x_causal[s] = a.xs[s].causal != 0; q.y_causal[s] = a.ys[s].causal != 0; }
+    q.mod_form = a.mod_form != 0; q.lin = a.lin_limit > 0; q.plane_batch = a.plane_batch != 0;
+    q.pw_flags = a.pw_flags; q.post_input = a.post_i != Acc(0);
+    q.y_apply = a.y_apply != nullptr; q.y_nb_W = a.y_nb_W != nullptr; q.x_nb_W = a.x_nb_W != nullptr;
+    q.rs_tau = a.rs_tau != nullptr; q.rs_G = a.rs_G != nullptr;
+    q.edge_everywhere = edge_everywhere;
+    return q;
+}
+// the arguments of one of its launches
+template <typename Acc>
+inline FusedArgs<Acc> pass2_strip(const FusedArgs<Acc> &a, const Pass2Launch &l) {
+    FusedArgs<Acc> part = a;
+    part.tx0 = l.tx0; part.ty0 = l.ty0; part.gx = l.gx; part.gy = l.gy;
+    part.xcd_contig = l.xcd_contig;
+    return part;
+}
+// What a launcher of the final pass does: grid guard, query, select, then launch_one(launch, its arguments) for the launches in order.
+template <typename Acc, typename F>
+inline int pass2_run(bool tall, int dst, int src, int K, int TY, const FusedArgs<Acc> &a, bool edge_everywhere, F launch_one) {
+    bool launch;
+    if (int rc = fused_grid_guard(a, &launch); rc != RF_OK || !launch) return rc;
+    const Pass2Choice c = select_pass2(pass2_query(tall, dst, src, K, TY, a, edge_everywhere));
+    for (int n = 0; n < c.n; n++)
+        if (int rc = launch_one(c.launch[n], pass2_strip(a, c.launch[n])); rc != RF_OK) return rc;
+    if (c.refusal != RF_OK) set_error("%s", c.text);
+    return c.refusal;
+}
+// Walks kPass2Instances: row(std::integral_constant<size_t, ROW>) launches row ROW if it is the wanted instance and compiled for the
+// caller's kernel and types, and returns kPass2NotThisRow otherwise.  A choice the list does not hold is an error of its own.
+constexpr int kPass2NotThisRow = -1;
+template <typename F, size_t... ROW>
+inline int pass2_walk(const Pass2Launch &l, int K, int TY, F row, std::index_sequence<ROW...>) {
+    int rc = kPass2NotThisRow;
+    if ((((rc = row(std::integral_constant<size_t, ROW>())) != kPass2NotThisRow) || ...)) return rc;
+    set_error("fused pass 2: no instance EPI %d EDGE %d YPAT %d XFIX %d EARLY %d LIN %d MOD %d RS %d of order %d on %d-row tiles for these pixel types",
+              l.inst.EPI, l.inst.EDGE, l.inst.YPAT, l.inst.XFIX, l.inst.EARLY, l.inst.LIN, l.inst.MOD, l.inst.RS, K, TY);
+    return RF_ERR_UNSUPPORTED;
+}
+// ... one row's launch: the opt-in (lds_opt_in: the most the kernel may be launched with), the grid of the strip
+template <auto Kernel, typename PI, typename P, typename Acc>
+inline int pass2_launch(size_t lds_opt_in, size_t lds, const PI *src, P *dst, const FusedArgs<Acc> &a, hipStream_t stream) {
+    if (int rc = opt_in_dynamic_lds<Kernel>(lds_opt_in); rc != RF_OK) return rc;
+    dim3 grid((unsigned)(a.gx > 0 ? a.gx : a.MX), (unsigned)(a.gy > 0 ? a.gy : a.MY), (unsigned)a.NZ);
+    hipLaunchKernelGGL(Kernel, grid, dim3(kFusedThreads), lds, stream, src, dst, a);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
+}
+
 // Register-column scans along a strided dimension (kernels_strided.hip), by value like FusedArgs.
 template <typename Acc>
 struct StridedArgs {
@@ -201,6 +294,12 @@ int launch_chain_apply(int K, const GenericDimArgs<Acc> &a, int s, const Acc *ex
 // RF_IN_U8) or a 16-bit float storage type: the x/y stage of a 16-bit volume, which writes the f32 volume its z stage reads
 // (FusedArgs::row_bytes is then that of the f32 rows)
 enum { kSrcPixel = 0, kSrcU8 = 1, kSrcF16 = 2, kSrcBF16 = 3 };
+// ... as Pass2Query::src (only f32 pixels take a source of another type: anything else is kP2Other, which the rule refuses)
+inline int pass2_source(int dst, int src_kind) {
+    if (src_kind == kSrcPixel) return dst;
+    if (dst != kP2F32) return kP2Other;
+    return src_kind == kSrcU8 ? kP2U8 : src_kind == kSrcF16 ? kP2F16 : src_kind == kSrcBF16 ? kP2BF16 : kP2Other;
+}
 template <typename P>
 int launch_fused_pass2(int K, int TY, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                        hipStream_t stream);

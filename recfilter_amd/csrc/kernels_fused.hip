@@ -20,8 +20,9 @@
 // This file holds pass 2, the final correction pass (lib/split.cpp:1008-1130, 1647-1780).  Pass 1 (tail extraction as
 // a contraction) and the completion of the y tails are in kernels_tails.hip, the carry recurrences in
 // kernels_carry.hip; plan_fused.cpp strings them together.
-#include <atomic>
+#include <iterator>
 #include <type_traits>
+#include <utility>
 
 #include "kernels.h"
 #include "kernels_fused.h"
@@ -432,157 +433,52 @@ fused_pass2_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedArgs<ty
     }
 }
 
-template <typename P, int K, int TY, bool EPI, bool EDGE, typename PI, int YPAT = 0, bool XFIX = false, bool LIN = false, bool MOD = false>
-int launch_fused_pass2_impl(const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
-    using Acc = typename PixelTraits<P>::Acc;
-    const size_t lds = (size_t)TY * kFusedTX * sizeof(Acc);
-    // the 64 KiB of dynamic LDS has to be opted into once per device
-    // (concurrent plan creators/executors on different host threads may race to set it: the flag is atomic and the
-    // attribute call itself is idempotent)
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    RF_HIP_CHECK(hipGetDevice(&dev));
-    std::atomic<bool> &done = attr_set[dev & 63];
-    if (!done.load(std::memory_order_acquire)) {
-        RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_pass2_kernel<P, K, TY, EPI, EDGE, PI, YPAT, XFIX, LIN, MOD>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        done.store(true, std::memory_order_release);
-    }
-    dim3 grid((unsigned)(a.gx > 0 ? a.gx : a.MX), (unsigned)(a.gy > 0 ? a.gy : a.MY), (unsigned)a.NZ);
-    hipLaunchKernelGGL((fused_pass2_kernel<P, K, TY, EPI, EDGE, PI, YPAT, XFIX, LIN, MOD>), grid, dim3(kFusedThreads), lds, stream, src, dst, a);
-    RF_HIP_CHECK(hipGetLastError());
-    return RF_OK;
+// (pixel types, K, TY, instance) -> the template instance, launched: the flat list kPass2Instances under its guard (pass2_select.h)
+template <typename P, typename PI, int K, int TY>
+int launch_instance(const Pass2Launch &l, const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
+    return pass2_walk(l, K, TY, [&](auto row) -> int {
+        constexpr Pass2Instance I = kPass2Instances[decltype(row)::value];
+        if constexpr (pass2_has(false, pass2_pixel<P>(), pass2_pixel<PI>(), K, TY, I)) {
+            // (the 64 KiB tile -- 128 KiB of f64 -- is opted into, whatever TY)
+            if (l.inst == I) return pass2_launch<&fused_pass2_kernel<P, K, TY, I.EPI, I.EDGE, PI, I.YPAT, I.XFIX, I.LIN, I.MOD>>(l.lds, l.lds, src, dst, a, stream);
+        }
+        return kPass2NotThisRow;
+    }, std::make_index_sequence<std::size(kPass2Instances)>());
 }
 
 }  // namespace
 
 template <typename P, typename PI>
-static int launch_fused_pass2_typed(int K, int TY, const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
-                                    hipStream_t stream) {
-    // the epilogue variant that keeps the input column in registers exists for float pixels only
-    bool epi = false;
-    const bool edge = a.last_cols != kFusedTX || a.last_rows != TY;
-    // (three launches like the 128-row final pass's -- whole tiles lean, edge strips on the EDGE variant -- gain nothing here:
-    // the 64-row EDGE variant costs 20-35 % per tile, what the two extra strips cost: 8192 x 8188, 0.134 / 0.135 ms)
-    // (16-bit float pixels: no such instances -- their input operand comes back through the caches, as at order 3)
-    if constexpr (!PixelTraits<P>::is_integer && !is_half_pixel<P>::value) epi = (a.pw_flags & 2) && a.post_i != typename PixelTraits<P>::Acc(0) && K <= 2;
-    if (a.lin_limit > 0 && (a.ny != 0 || a.NZ != 1 || a.plane_batch || epi || edge)) {
-        set_error("fused pass 2: a signal that ends inside the image needs a 1-D plan of whole tiles without an input-operand epilogue");
-        return RF_ERR_INVALID_ARG;
-    }
-    // (a plan in mod form -- FusedArgs::mod_form -- takes the general-pattern code, which applies its border modifications)
-    const int ypat = a.mod_form ? 0 : (a.ny == 1 && a.ys[0].causal != 0) ? 1 : (a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0) ? 2 : 0;
-    const int xpat = a.mod_form ? 0 : (a.nx == 1 && a.xs[0].causal != 0) ? 1 : (a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0) ? 2 : 0;
-    bool early = true;        // rows can leave from inside the last scan (an affine epilogue is applied on the way out; one with
-                              // an input operand only where the column is in registers, i.e. the EPI variants)
-    if constexpr (!PixelTraits<P>::is_integer) early = (a.pw_flags & 2) == 0 || a.post_i == typename PixelTraits<P>::Acc(0);
-#define RF_CASE(KK, TT)                                                                                         \
-    if (K == KK && TY == TT) {                                                                                  \
-        if constexpr (std::is_same<P, float>::value && std::is_same<P, PI>::value) {                            \
-            if (a.mod_form) {                                                                                   \
-                if (epi) { set_error("fused pass 2: clamped sections cannot take an epilogue with an input operand"); return RF_ERR_UNSUPPORTED; } \
-                return edge ? launch_fused_pass2_impl<P, KK, TT, false, true, PI, 0, false, false, true>(src, dst, a, stream)   \
-                            : launch_fused_pass2_impl<P, KK, TT, false, false, PI, 0, false, false, true>(src, dst, a, stream); \
-            }                                                                                                   \
-        }                                                                                                       \
-        if constexpr (std::is_same<P, PI>::value) {                                                             \
-            if (a.lin_limit > 0) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 0, false, true>(src, dst, a, stream); \
-        }                                                                                                       \
-        if constexpr (!PixelTraits<P>::is_integer && !is_half_pixel<P>::value) {                                \
-            if (epi && edge) return launch_fused_pass2_impl<P, KK, TT, true, true, PI>(src, dst, a, stream);    \
-            if constexpr (TT == 64 && std::is_same<P, PI>::value) {                                             \
-                if (epi && ypat == 1) return launch_fused_pass2_impl<P, KK, TT, true, false, PI, 3>(src, dst, a, stream); \
-                if (epi && ypat == 2) return launch_fused_pass2_impl<P, KK, TT, true, false, PI, 4>(src, dst, a, stream); \
-            }                                                                                                   \
-            if (epi) return launch_fused_pass2_impl<P, KK, TT, true, false, PI>(src, dst, a, stream);           \
-        }                                                                                                       \
-        if constexpr (std::is_same<P, float>::value && std::is_same<P, PI>::value) {   /* partial tiles, the usual y scans */ \
-            if (edge && ypat == 1) return launch_fused_pass2_impl<P, KK, TT, false, true, PI, 1>(src, dst, a, stream); \
-            if (edge && ypat == 2) return launch_fused_pass2_impl<P, KK, TT, false, true, PI, 2>(src, dst, a, stream); \
-        }                                                                                                       \
-        if (edge) return launch_fused_pass2_impl<P, KK, TT, false, true, PI>(src, dst, a, stream);              \
-        if constexpr ((TT == 64 || std::is_same<P, float>::value) && std::is_same<P, PI>::value) {   /* the usual y scans, directions fixed at compile time */ \
-            if (ypat == 1 && early && xpat == 1) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 3, true>(src, dst, a, stream); \
-            if (ypat == 2 && early && xpat == 2) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 4, true>(src, dst, a, stream); \
-            if (ypat == 1 && early) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 3>(src, dst, a, stream); \
-            if (ypat == 2 && early) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 4>(src, dst, a, stream); \
-            if (ypat == 1) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 1>(src, dst, a, stream); \
-            if (ypat == 2) return launch_fused_pass2_impl<P, KK, TT, false, false, PI, 2>(src, dst, a, stream); \
-        }                                                                                                       \
-        return launch_fused_pass2_impl<P, KK, TT, false, false, PI>(src, dst, a, stream);                       \
-    }
-    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
-    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
-#undef RF_CASE
-    set_error("fused path: unsupported order %d / tile height %d", K, TY);
-    return RF_ERR_UNSUPPORTED;
+static int run(int K, int TY, int src_pixel, const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
+    using Args = FusedArgs<typename PixelTraits<P>::Acc>;
+    return pass2_run(false, pass2_pixel<P>(), src_pixel, K, TY, a, false, [&](const Pass2Launch &l, const Args &part) -> int {
+        switch (TY == 64 || TY == 32 ? K : 0) {
+        case 1: return TY == 64 ? launch_instance<P, PI, 1, 64>(l, src, dst, part, stream) : launch_instance<P, PI, 1, 32>(l, src, dst, part, stream);
+        case 2: return TY == 64 ? launch_instance<P, PI, 2, 64>(l, src, dst, part, stream) : launch_instance<P, PI, 2, 32>(l, src, dst, part, stream);
+        case 3: return TY == 64 ? launch_instance<P, PI, 3, 64>(l, src, dst, part, stream) : launch_instance<P, PI, 3, 32>(l, src, dst, part, stream);
+        }
+        set_error("fused pass 2: no instances of order %d on %d-row tiles", K, TY);
+        return RF_ERR_UNSUPPORTED;
+    });
 }
 
-// 16-bit float planes in, f32 out (the x/y stage of a 16-bit volume): the automatic choice of a volume's x/y stage -- whole
-// tiles with the usual pair of scans in both dimensions, fixed at compile time, rows leaving from inside the last scan -- plus
-// the general-pattern code for every other filter and for partial tiles
-template <typename PI>
-static int launch_fused_pass2_widen(int K, int TY, const PI *src, float *dst, const FusedArgs<float> &a, hipStream_t stream) {
-    if (a.lin_limit > 0 || a.mod_form || (a.pw_flags & 2) || a.plane_batch) {
-        set_error("fused pass 2: a 16-bit source with an f32 destination is the x/y stage of a volume (no epilogue, no sections)");
-        return RF_ERR_INVALID_ARG;
-    }
-    const bool edge = a.last_cols != kFusedTX || a.last_rows != TY;
-    const bool pair = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0 && a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
-#define RF_CASE(KK, TT)                                                                                         \
-    if (K == KK && TY == TT) {                                                                                  \
-        if (edge) return launch_fused_pass2_impl<float, KK, TT, false, true, PI>(src, dst, a, stream);          \
-        if (pair) return launch_fused_pass2_impl<float, KK, TT, false, false, PI, 4, true>(src, dst, a, stream); \
-        return launch_fused_pass2_impl<float, KK, TT, false, false, PI>(src, dst, a, stream);                   \
-    }
-    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
-    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
-#undef RF_CASE
-    set_error("fused path: unsupported order %d / tile height %d", K, TY);
-    return RF_ERR_UNSUPPORTED;
-}
-
-// Unsigned bytes in, unsigned bytes out (rf_pointwise_desc.in_dtype == RF_IO_U8): the f32 arithmetic of the RF_IN_U8 instances
-// with a byte destination -- PixelTraits<uint8_t>::store is sat8 (pixel.h), applied to the value behind the epilogue as a row
-// leaves.  Three instances per order and tile height: partial tiles; whole tiles with the usual pair of scans in both
-// dimensions and rows leaving from inside the last scan (an affine epilogue is applied on the way out); the general-pattern
-// code for everything else (an epilogue's input operand comes back through the caches, as for the 16-bit types).
+// Unsigned bytes in, unsigned bytes out (rf_pointwise_desc.in_dtype == RF_IO_U8): the f32 arithmetic of the RF_IN_U8 instances with
+// a byte destination -- PixelTraits<uint8_t>::store is sat8 (pixel.h), applied to the value behind the epilogue as a row leaves.
 int launch_fused_pass2_u8(int K, int TY, const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
-    if (a.lin_limit > 0 || a.mod_form || a.y_nb_W != nullptr || a.y_apply != nullptr || a.row_bytes != (uint32_t)a.NX) {
-        set_error("fused pass 2: byte planes on both sides are an unsharded 2-D image of orders <= 3 with a row pitch of NX bytes");
-        return RF_ERR_INVALID_ARG;
-    }
-    const bool edge = a.last_cols != kFusedTX || a.last_rows != TY;
-    const bool pair = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0 && a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
-    const bool early = (a.pw_flags & 2) == 0 || a.post_i == 0.0f;
-#define RF_CASE(KK, TT)                                                                                         \
-    if (K == KK && TY == TT) {                                                                                  \
-        if (edge) return launch_fused_pass2_impl<uint8_t, KK, TT, false, true, uint8_t>(src, dst, a, stream);   \
-        if (pair && early) return launch_fused_pass2_impl<uint8_t, KK, TT, false, false, uint8_t, 4, true>(src, dst, a, stream); \
-        return launch_fused_pass2_impl<uint8_t, KK, TT, false, false, uint8_t>(src, dst, a, stream);            \
-    }
-    RF_CASE(1, 64) RF_CASE(2, 64) RF_CASE(3, 64)
-    RF_CASE(1, 32) RF_CASE(2, 32) RF_CASE(3, 32)
-#undef RF_CASE
-    set_error("fused path: unsupported order %d / tile height %d", K, TY);
-    return RF_ERR_UNSUPPORTED;
+    return run<uint8_t, uint8_t>(K, TY, kP2U8, src, dst, a, stream);
 }
 
 template <typename P>
 int launch_fused_pass2(int K, int TY, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                        hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
-    if (a.y_nb_W != nullptr) { set_error("fused pass 2: neighbour-form y carries need the 128-row final pass"); return RF_ERR_INVALID_ARG; }
+    const int src_pixel = pass2_source(pass2_pixel<P>(), src_kind);
     if constexpr (std::is_same<P, float>::value) {
-        if (src_kind == kSrcU8) return launch_fused_pass2_typed<P, uint8_t>(K, TY, (const uint8_t *)src, dst, a, stream);
-        if (src_kind == kSrcF16) return launch_fused_pass2_widen<_Float16>(K, TY, (const _Float16 *)src, dst, a, stream);
-        if (src_kind == kSrcBF16) return launch_fused_pass2_widen<__bf16>(K, TY, (const __bf16 *)src, dst, a, stream);
+        // unsigned-byte input planes (RF_IN_U8); 16-bit float planes in, f32 out: the x/y stage of a 16-bit volume
+        if (src_pixel == kP2U8) return run<P, uint8_t>(K, TY, src_pixel, (const uint8_t *)src, dst, a, stream);
+        if (src_pixel == kP2F16) return run<P, _Float16>(K, TY, src_pixel, (const _Float16 *)src, dst, a, stream);
+        if (src_pixel == kP2BF16) return run<P, __bf16>(K, TY, src_pixel, (const __bf16 *)src, dst, a, stream);
     }
-    if (src_kind != kSrcPixel) { set_error("fused pass 2: only f32 pixels take a source of another type"); return RF_ERR_INVALID_ARG; }
-    return launch_fused_pass2_typed<P, P>(K, TY, (const P *)src, dst, a, stream);
+    return run<P, P>(K, TY, src_pixel, (const P *)src, dst, a, stream);
 }
 
 template int launch_fused_pass2<float>(int, int, const void *, int, float *, const FusedArgs<float> &, hipStream_t);

@@ -8,8 +8,9 @@
 // LDS as two halves of 64 rows (load, x phase, columns out), the thread keeps its 128-sample column in registers, runs all
 // y scans on it and stores.  Everything else is fused_pass2_kernel (kernels_fused.hip): same carries, same tables, same
 // arithmetic per sample.
-#include <atomic>
+#include <iterator>
 #include <type_traits>
+#include <utility>
 
 #include "kernels.h"
 #include "kernels_fused.h"
@@ -481,162 +482,54 @@ fused_pass2_tall_kernel(const PI *__restrict__ src, P *__restrict__ dst, FusedAr
     }
 }
 
-template <typename P, int K, bool EDGE, typename PI, int YPAT, bool EARLY, bool XFIX = false, bool RS = false>
-int launch_tall_pat(const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
+// (pixel types, K, instance) -> the template instance, launched: the flat list kPass2Instances under its guard (pass2_select.h)
+template <typename P, typename PI, int K>
+int launch_instance(const Pass2Launch &l, const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
     using Acc = typename PixelTraits<P>::Acc;
-    // the half tile + the x carries of both halves ([2][4 scans][4 rows][K][16 slots])
-    // ... and the y carries of the columns ([ny * K][256])
-    const size_t lds = ((size_t)kHalfRows * kFusedTX + 2 * kFusedMaxScans * (kHalfRows / 16) * K * 16 + (size_t)a.ny * K * kFusedTX) * sizeof(Acc);
-    const size_t lds_max = ((size_t)kHalfRows * kFusedTX + 2 * kFusedMaxScans * (kHalfRows / 16) * K * 16 + (size_t)kFusedMaxScans * K * kFusedTX) * sizeof(Acc);
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    RF_HIP_CHECK(hipGetDevice(&dev));
-    std::atomic<bool> &done = attr_set[dev & 63];
-    if (!done.load(std::memory_order_acquire)) {
-        RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_pass2_tall_kernel<P, K, EDGE, PI, YPAT, EARLY, XFIX, RS>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        done.store(true, std::memory_order_release);
-    }
-    dim3 grid((unsigned)(a.gx > 0 ? a.gx : a.MX), (unsigned)(a.gy > 0 ? a.gy : a.MY), (unsigned)a.NZ);
-    FusedArgs<Acc> aa = a;
-    aa.xcd_contig = (a.row_bytes % 128u != 0 && (grid.x * grid.y) % 8u == 0 && grid.x * grid.y >= 2048u) ? 1 : 0;
-    hipLaunchKernelGGL((fused_pass2_tall_kernel<P, K, EDGE, PI, YPAT, EARLY, XFIX, RS>), grid, dim3(kFusedThreads), lds, stream, src, dst, aa);
-    RF_HIP_CHECK(hipGetLastError());
-    return RF_OK;
-}
-
-template <typename P, int K, bool EDGE, typename PI>
-int launch_tall_impl(const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
-    // (a plan in mod form -- FusedArgs::mod_form -- takes the general-pattern code, which applies its border modifications)
-    const int pat = a.mod_form ? 0 : (a.ny == 1 && a.ys[0].causal != 0) ? 1 : (a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0) ? 2 : 0;
-    bool early = !EDGE && pat > 0;
-    if constexpr (!PixelTraits<P>::is_integer) early = early && (a.pw_flags & 2) == 0;
-    const int xpat = a.mod_form ? 0 : (a.nx == 1 && a.xs[0].causal != 0) ? 1 : (a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0) ? 2 : 0;
-    if (a.rs_tau != nullptr) {      // the row-scan form (FusedArgs::rs_tau): one instance
-        if constexpr (!EDGE && K == 2 && std::is_same<P, float>::value && std::is_same<PI, float>::value) {
-            if (early && pat == 2 && xpat == 2 && a.y_nb_W != nullptr && a.x_nb_W != nullptr && a.rs_G != nullptr && a.y_apply == nullptr)
-                return launch_tall_pat<P, K, EDGE, PI, 2, true, true, true>(src, dst, a, stream);
+    return pass2_walk(l, K, kTallTY, [&](auto row) -> int {
+        constexpr Pass2Instance I = kPass2Instances[decltype(row)::value];
+        if constexpr (pass2_has(true, pass2_pixel<P>(), pass2_pixel<PI>(), K, kTallTY, I)) {
+            // (opted into for the most y scans a plan can have: Pass2Launch::lds counts the plan's)
+            constexpr size_t lds_max = ((size_t)kHalfRows * kFusedTX + 2 * kFusedMaxScans * (kHalfRows / 16) * K * 16 + (size_t)kFusedMaxScans * K * kFusedTX) * sizeof(Acc);
+            if (l.inst == I) return pass2_launch<&fused_pass2_tall_kernel<P, K, I.EDGE, PI, I.YPAT, I.EARLY, I.XFIX, I.RS>>(lds_max, l.lds, src, dst, a, stream);
         }
-        set_error("fused pass 2: the row-scan form is misconfigured");
-        return RF_ERR_INVALID_ARG;
-    }
-    if constexpr (!EDGE) {
-        if (early && pat == 1 && xpat == 1) return launch_tall_pat<P, K, EDGE, PI, 1, true, true>(src, dst, a, stream);
-        if (early && pat == 2 && xpat == 2) return launch_tall_pat<P, K, EDGE, PI, 2, true, true>(src, dst, a, stream);
-        if (early && pat == 1) return launch_tall_pat<P, K, EDGE, PI, 1, true>(src, dst, a, stream);
-        if (early && pat == 2) return launch_tall_pat<P, K, EDGE, PI, 2, true>(src, dst, a, stream);
-    }
-    if (pat == 1) return launch_tall_pat<P, K, EDGE, PI, 1, false>(src, dst, a, stream);
-    if (pat == 2) return launch_tall_pat<P, K, EDGE, PI, 2, false>(src, dst, a, stream);
-    return launch_tall_pat<P, K, EDGE, PI, 0, false>(src, dst, a, stream);
-}
-
-// 16-bit float planes in, f32 out (the x/y stage of a 16-bit volume, kernels_fused.hip launch_fused_pass2_widen): the usual pair
-// of scans in both dimensions on its compile-time variants, every other filter on the general-pattern code
-template <int K, bool EDGE, typename PI>
-int launch_tall_widen(const PI *src, float *dst, const FusedArgs<float> &a, hipStream_t stream) {
-    if (a.mod_form || (a.pw_flags & 2) || a.plane_batch || a.y_nb_W != nullptr || a.y_apply != nullptr) {
-        set_error("fused pass 2: a 16-bit source with an f32 destination is the x/y stage of an unsharded volume (no epilogue, no sections)");
-        return RF_ERR_INVALID_ARG;
-    }
-    const bool pair_y = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0;
-    const bool pair_x = a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
-    if constexpr (!EDGE) {
-        if (pair_y && pair_x) return launch_tall_pat<float, K, EDGE, PI, 2, true, true>(src, dst, a, stream);
-    } else {
-        if (pair_y) return launch_tall_pat<float, K, EDGE, PI, 2, false>(src, dst, a, stream);
-    }
-    return launch_tall_pat<float, K, EDGE, PI, 0, false>(src, dst, a, stream);
-}
-
-// Unsigned bytes in, unsigned bytes out (kernels_fused.hip, launch_fused_pass2_u8): the usual pair of y scans on its
-// compile-time variants -- rows leaving from inside the last scan where the tiles are whole, both dimensions have the pair and
-// the epilogue, if any, has no input operand -- every other filter on the general-pattern code
-template <int K, bool EDGE>
-int launch_tall_u8(const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream) {
-    const bool pair_y = a.ny == 2 && a.ys[0].causal != 0 && a.ys[1].causal == 0;
-    const bool pair_x = a.nx == 2 && a.xs[0].causal != 0 && a.xs[1].causal == 0;
-    if constexpr (!EDGE) {
-        if (pair_y && pair_x && ((a.pw_flags & 2) == 0 || a.post_i == 0.0f)) return launch_tall_pat<uint8_t, K, EDGE, uint8_t, 2, true, true>(src, dst, a, stream);
-    }
-    if (pair_y) return launch_tall_pat<uint8_t, K, EDGE, uint8_t, 2, false>(src, dst, a, stream);
-    return launch_tall_pat<uint8_t, K, EDGE, uint8_t, 0, false>(src, dst, a, stream);
+        return kPass2NotThisRow;
+    }, std::make_index_sequence<std::size(kPass2Instances)>());
 }
 
 }  // namespace
 
+template <typename P, typename PI>
+static int run(int K, int src_pixel, const PI *src, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a, hipStream_t stream) {
+    using Args = FusedArgs<typename PixelTraits<P>::Acc>;
+    static const bool edge_everywhere = RF_KNOB("RF_TALL_EDGE_EVERYWHERE") != nullptr;      // A/B runs
+    // (partial tiles make up to three launches: pass2_select.h)
+    return pass2_run(true, pass2_pixel<P>(), src_pixel, K, kTallTY, a, edge_everywhere, [&](const Pass2Launch &l, const Args &part) -> int {
+        switch (K) {
+        case 1: return launch_instance<P, PI, 1>(l, src, dst, part, stream);
+        case 2: return launch_instance<P, PI, 2>(l, src, dst, part, stream);
+        case 3: return launch_instance<P, PI, 3>(l, src, dst, part, stream);
+        }
+        set_error("fused pass 2: no 128-row instances of order %d", K);
+        return RF_ERR_UNSUPPORTED;
+    });
+}
+
+// unsigned bytes in, unsigned bytes out (kernels_fused.hip, launch_fused_pass2_u8)
 int launch_fused_pass2_tall_u8(int K, const uint8_t *src, uint8_t *dst, const FusedArgs<float> &a, hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
-    if (a.lin_limit > 0 || a.mod_form || a.y_apply != nullptr || a.row_bytes != (uint32_t)a.NX) {
-        set_error("fused pass 2: byte planes on both sides are an unsharded 2-D image of orders <= 3 with a row pitch of NX bytes");
-        return RF_ERR_INVALID_ARG;
-    }
-    auto one = [&](const FusedArgs<float> &aa, bool e) -> int {
-#define RF_CASE(KK) \
-    if (K == KK) return e ? launch_tall_u8<KK, true>(src, dst, aa, stream) : launch_tall_u8<KK, false>(src, dst, aa, stream);
-        RF_CASE(1) RF_CASE(2) RF_CASE(3)
-#undef RF_CASE
-        set_error("fused path: unsupported order %d", K);
-        return (int)RF_ERR_UNSUPPORTED;
-    };
-    // partial tiles: the whole tiles on the lean kernel, the last tile column and the last tile row on the EDGE variant, as below
-    const bool edge = a.last_cols != kFusedTX || a.last_rows != kTallTY;
-    if (edge) {
-        const int MXf = a.MX - (a.last_cols != kFusedTX ? 1 : 0), MYf = a.MY - (a.last_rows != kTallTY ? 1 : 0);
-        FusedArgs<float> part = a;
-        part.gx = MXf; part.gy = MYf;
-        int rc = (MXf > 0 && MYf > 0) ? one(part, false) : (int)RF_OK;
-        if (rc == RF_OK && MXf < a.MX) { part = a; part.tx0 = a.MX - 1; part.gx = 1; part.gy = a.MY; rc = one(part, true); }
-        if (rc == RF_OK && MYf < a.MY && MXf > 0) { part = a; part.ty0 = a.MY - 1; part.gy = 1; part.gx = MXf; rc = one(part, true); }
-        return rc;
-    }
-    return one(a, false);
+    return run<uint8_t, uint8_t>(K, kP2U8, src, dst, a, stream);
 }
 
 template <typename P>
 int launch_fused_pass2_tall(int K, const void *src, int src_kind, P *dst, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                             hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
-    const bool edge = a.last_cols != kFusedTX || a.last_rows != kTallTY;
-    // one launch of `aa`'s tiles on the lean (edge = false) or the EDGE variant
-    auto one = [&](const FusedArgs<typename PixelTraits<P>::Acc> &aa, bool e) -> int {
-#define RF_CASE(KK)                                                                                                     \
-    if (K == KK) {                                                                                                      \
-        if constexpr (std::is_same<P, float>::value) {                                                                  \
-            if (src_kind == kSrcU8) return e ? launch_tall_impl<P, KK, true, uint8_t>((const uint8_t *)src, dst, aa, stream)   \
-                                             : launch_tall_impl<P, KK, false, uint8_t>((const uint8_t *)src, dst, aa, stream); \
-            if (src_kind == kSrcF16) return e ? launch_tall_widen<KK, true, _Float16>((const _Float16 *)src, dst, aa, stream)  \
-                                              : launch_tall_widen<KK, false, _Float16>((const _Float16 *)src, dst, aa, stream); \
-            if (src_kind == kSrcBF16) return e ? launch_tall_widen<KK, true, __bf16>((const __bf16 *)src, dst, aa, stream)     \
-                                               : launch_tall_widen<KK, false, __bf16>((const __bf16 *)src, dst, aa, stream);   \
-        }                                                                                                               \
-        if (src_kind != kSrcPixel) { set_error("fused pass 2: only f32 pixels take a source of another type"); return (int)RF_ERR_INVALID_ARG; } \
-        return e ? launch_tall_impl<P, KK, true, P>((const P *)src, dst, aa, stream)                                    \
-                 : launch_tall_impl<P, KK, false, P>((const P *)src, dst, aa, stream);                                  \
+    const int src_pixel = pass2_source(pass2_pixel<P>(), src_kind);
+    if constexpr (std::is_same<P, float>::value) {      // (as launch_fused_pass2, kernels_fused.hip)
+        if (src_pixel == kP2U8) return run<P, uint8_t>(K, src_pixel, (const uint8_t *)src, dst, a, stream);
+        if (src_pixel == kP2F16) return run<P, _Float16>(K, src_pixel, (const _Float16 *)src, dst, a, stream);
+        if (src_pixel == kP2BF16) return run<P, __bf16>(K, src_pixel, (const __bf16 *)src, dst, a, stream);
     }
-        RF_CASE(1) RF_CASE(2) RF_CASE(3)
-#undef RF_CASE
-        set_error("fused path: unsupported order %d", K);
-        return (int)RF_ERR_UNSUPPORTED;
-    };
-    // Partial tiles.  The EDGE variant costs the final pass almost twice its time per tile (no rows leave from inside the last
-    // scan, a bound and a select per access, 24-144 bytes of scratch: 16384 x 16256, 0.662 ms against 0.366 ms for 16384^2),
-    // and only the last tile column / row needs it: the whole tiles run on the lean kernel, the two strips as launches of
-    // their own on the EDGE variant (FusedArgs::tx0 ..): 0.386 + 0.042 ms.  (One launch with a per-workgroup branch between
-    // the two bodies was slower than the three launches: 0.531 ms.)
-    static const bool edge_everywhere = RF_KNOB("RF_TALL_EDGE_EVERYWHERE") != nullptr;      // A/B runs
-    if (edge && !edge_everywhere) {
-        const int MXf = a.MX - (a.last_cols != kFusedTX ? 1 : 0), MYf = a.MY - (a.last_rows != kTallTY ? 1 : 0);
-        FusedArgs<typename PixelTraits<P>::Acc> part = a;
-        part.gx = MXf; part.gy = MYf;
-        int rc = (MXf > 0 && MYf > 0) ? one(part, false) : (int)RF_OK;
-        if (rc == RF_OK && MXf < a.MX) { part = a; part.tx0 = a.MX - 1; part.gx = 1; part.gy = a.MY; rc = one(part, true); }
-        if (rc == RF_OK && MYf < a.MY && MXf > 0) { part = a; part.ty0 = a.MY - 1; part.gy = 1; part.gx = MXf; rc = one(part, true); }
-        return rc;
-    }
-    return one(a, edge);
+    return run<P, P>(K, src_pixel, (const P *)src, dst, a, stream);
 }
 
 template int launch_fused_pass2_tall<float>(int, const void *, int, float *, const FusedArgs<float> &, hipStream_t);

@@ -14,7 +14,6 @@
 // this kernel finish a 512^2 image in a fraction of that.  It also is what RF_PATH_UNTILED runs whenever the shape
 // admits it (f32 / i32 / i16 pixels, orders <= 3, <= 4 scans per dimension, extents that are multiples of 16).
 // Larger images stay on the tiled paths: this one moves 8 bytes per sample and SCAN (every scan re-reads the line).
-#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -294,14 +293,8 @@ int launch_line_scans(int K, bool strided, const P *src, P *dst, const LineScanA
         const size_t lds = strided ? (size_t)MTT * kLineTile * (kLinesPerWG + 1) * sizeof(typename PixelTraits<P>::Acc) : 0; \
         if (strided) {                                                                                                \
             if (lds > 64 * 1024) {                                                                                    \
-                static std::atomic<bool> attr_set[64];                                                                \
-                int dev = 0;                                                                                          \
-                RF_HIP_CHECK(hipGetDevice(&dev));                                                                     \
-                if (!attr_set[dev & 63].load(std::memory_order_acquire)) {                                            \
-                    RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&line_scans_short_kernel<P, KK, MTT, true>), \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
-                    attr_set[dev & 63].store(true, std::memory_order_release);                                        \
-                }                                                                                                     \
+                const int rc = opt_in_dynamic_lds<&line_scans_short_kernel<P, KK, MTT, true>>(lds);                    \
+                if (rc != RF_OK) return rc;                                                                           \
             }                                                                                                         \
             hipLaunchKernelGGL((line_scans_short_kernel<P, KK, MTT, true>), grid, blk, lds, stream, src, dst, a);     \
         } else hipLaunchKernelGGL((line_scans_short_kernel<P, KK, MTT, false>), grid, blk, 0, stream, src, dst, a);   \

@@ -19,7 +19,6 @@
 // The arithmetic is that of fused_tails_kernel (same tables, same summation order inside a quarter); images made of
 // whole 256 x 64 tiles with pixel-typed planes take this kernel, everything else (partial tiles, 32-row tiles,
 // unsigned-byte planes, a fused prologue) stays on fused_tails_kernel.
-#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -354,15 +353,9 @@ int launch_stream_tails(int K, const float *src, const FusedArgs<float> &a, cons
     const int ngx = nxk > 0 ? (nxk + 3) / 4 : 1, ngy = a.ny * K > 0 ? (a.ny * K + 3) / 4 : 1;
 #define RF_CASE(GX, GY, SLOTS, AHEAD)                                                                                    \
     if (ngx == GX && ngy == GY && ring == SLOTS) {                                                                       \
-        auto kern = &stream_tails_kernel<GX, GY, SLOTS, AHEAD>;                                                          \
-        static std::atomic<bool> attr_set[64];                                                                           \
-        int dev = 0;                                                                                                     \
-        RF_HIP_CHECK(hipGetDevice(&dev));                                                                                \
-        if (!attr_set[dev & 63].load(std::memory_order_acquire)) {                                                       \
-            RF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                             (int)(SLOTS * kSlotBytes + (8 * 4 * GX + 4 * 4 * GY) * kHyPitch * sizeof(float)))); \
-            attr_set[dev & 63].store(true, std::memory_order_release);                                                   \
-        }                                                                                                                \
+        constexpr auto kern = &stream_tails_kernel<GX, GY, SLOTS, AHEAD>;                                                \
+        const int rc = opt_in_dynamic_lds<kern>(SLOTS * kSlotBytes + (8 * 4 * GX + 4 * 4 * GY) * kHyPitch * sizeof(float)); \
+        if (rc != RF_OK) return rc;                                                                                      \
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kStreamThreads), (size_t)SLOTS * kSlotBytes + lds_rest, stream, src, a, Hx, \
                            Hy, (uint32_t)n_tiles, K);                                                                    \
         RF_HIP_CHECK(hipGetLastError());                                                                                 \

@@ -828,8 +828,8 @@ template <typename P>
 int launch_fused_tails(int K, int TY, const void *src, bool src_u8, const FusedArgs<typename PixelTraits<P>::Acc> &a,
                        const typename PixelTraits<P>::Acc *Hx, const typename PixelTraits<P>::Acc *Hy,
                        hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    bool launch;
+    if (int rc = fused_grid_guard(a, &launch); rc != RF_OK || !launch) return rc;
     dim3 grid((unsigned)a.MX, (unsigned)a.MY, (unsigned)a.NZ);
     static const size_t pad_bytes = RF_KNOB("RF_TAILS_PAD_LDS") ? (size_t)atoi(RF_KNOB("RF_TAILS_PAD_LDS")) : 0;     // A/B: bounds the residency
     const size_t hx_bytes = (size_t)(a.nx > 0 ? a.nx : 1) * K * kFusedTX * sizeof(typename PixelTraits<P>::Acc) + pad_bytes;

@@ -331,8 +331,8 @@ bool mfma_tails_applicable(int K, int TY, bool src_u8, int pw_flags, int last_co
 
 template <typename PI>
 int launch_mfma_tails(int K, int TY, const PI *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    bool launch;
+    if (int rc = fused_grid_guard(a, &launch); rc != RF_OK || !launch) return rc;
     dim3 grid((unsigned)a.MX, (unsigned)a.MY, (unsigned)a.NZ);
     const int nxk = a.nx * K, nyk = a.ny * K;
     // (YM = false: with the y tails on the matrix cores too -- the template's other form -- every instance needs more than
@@ -365,8 +365,8 @@ int launch_mfma_tails(int K, int TY, const PI *src, const FusedArgs<float> &a, c
 }
 
 int launch_mfma_tails_row_scans(const float *src, const FusedArgs<float> &a, const float *Hx, const float *Hy, hipStream_t stream) {
-    if (a.MX <= 0 || a.MY <= 0 || a.NZ <= 0) return RF_OK;
-    if (a.NZ > 65535 || a.MY > 65535) { set_error("fused path: grid too large"); return RF_ERR_UNSUPPORTED; }
+    bool launch;
+    if (int rc = fused_grid_guard(a, &launch); rc != RF_OK || !launch) return rc;
     if (a.nx != 2 || a.ny != 2 || a.last_cols != kFusedTX || a.last_rows != 128 || a.lin_limit != 0 || a.mod_form || (a.pw_flags & 1) ||
         a.xs[0].causal == 0 || a.xs[1].causal != 0 || a.yt_parts > 1) {
         set_error("mfma tails: the row-scan form is misconfigured");

@@ -11,11 +11,12 @@ import ref_cases as rc
 cfgname = sys.argv[1] if len(sys.argv) > 1 else "cfg3_gaussian2_xy"
 c = rc.BASELINE_CONFIGS[cfgname]
 shape = c["shape"]; planes = c.get("planes", 1)
-if len(sys.argv) > 2:
-    shape = tuple(int(sys.argv[2]) for _ in shape)
+if len(sys.argv) > 2:       # N: every extent; HxW: the shape
+    shape = tuple(int(v) for v in sys.argv[2].split("x")) if "x" in sys.argv[2] else tuple(int(sys.argv[2]) for _ in shape)
+flags = rfa.capi.RF_PLAN_TILED_ONLY if "tiled" in sys.argv[3:] else None      # (small images: the tiled kernels, not the line-parallel ones)
 imgs = [torch.rand(shape, device="cuda") for _ in range(planes)]
 outs = [torch.empty_like(i) for i in imgs]
-with rfa.Plan(shape, c["scans"], clamped=c["clamped"], planes=planes) as plan:
+with rfa.Plan(shape, c["scans"], clamped=c["clamped"], planes=planes, flags=flags) as plan:
     for _ in range(3):
         plan.execute(imgs, outs)
     acc = {}
