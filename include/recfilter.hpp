@@ -645,6 +645,33 @@ public:
         return r;
     }
 
+    /** Not in the reference: the gradient of a loss through the filter (rf_plan_backward).  grad_out / grad_in: one device plane
+     *  per Tuple element, f32; grad_in[p] may be grad_out[p].  The filter must run as ONE plan (a single stage, or a cascade
+     *  compile_jit merged); it is compiled if it has not been.  Asynchronous on the filter's stream. */
+    void gradient(const std::vector<const void *> &grad_out, const std::vector<void *> &grad_in) {
+        backward_call(nullptr, grad_out, grad_in, nullptr);
+    }
+    /** ... and with respect to every coefficient: `input` = the planes the realization read, `grad_coeffs` = a DEVICE buffer of
+     *  n_scans * (1 + RF_MAX_ORDER) doubles, row s = dL/dfeedfwd, dL/dfeedback[0..] of the s-th add_filter call */
+    void gradient(const std::vector<const void *> &input, const std::vector<const void *> &grad_out, const std::vector<void *> &grad_in,
+                  double *grad_coeffs) {
+        if (!grad_coeffs) fail("gradient: null coefficient-gradient buffer");
+        backward_call(&input, grad_out, grad_in, grad_coeffs);
+    }
+
+private:
+    void backward_call(const std::vector<const void *> *input, const std::vector<const void *> &grad_out, const std::vector<void *> &grad_in,
+                       double *grad_coeffs) {
+        if (c->compiled && c->merge_at_compile != merge_cascades()) c->compiled = false;
+        if (!c->compiled) compile_jit();
+        if (c->source && !c->merged) fail("gradient: a cascade that is not merged into one plan has no single backward");
+        const size_t n = n_planes();
+        if (grad_out.size() != n || grad_in.size() != n || (input && input->size() != n)) fail("gradient: one plane per Tuple element is needed");
+        if (rf_plan_backward(c->plan, input ? input->data() : nullptr, grad_out.data(), grad_in.data(), grad_coeffs, c->stream) != RF_OK)
+            fail(rf_last_error_string());
+    }
+
+public:
     /** lib/recfilter.cpp:991-1016: one warm-up, then the mean time of `iterations` runs in ms, every run including the
      *  upstream stages of a cascade (unlike the reference the device is synchronised before the clock is read) */
     float profile(int iterations) {

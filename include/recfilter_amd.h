@@ -373,6 +373,71 @@ int rf_plan_debug_buffer(const rf_plan *plan, int index, void **ptr_out, size_t 
 int rf_plan_debug_buffer_kind(const rf_plan *plan, int index, int *kind_out);
 int rf_plan_debug_fill(rf_plan *plan, int index, int byte, void *stream);
 
+/* ---- backward: the gradient of a loss through a plan ---------------------------------------------------------------------- */
+/* Given grad_out = dL/d(out) of an execute, grad_in = dL/d(in) and, where asked for, the gradient with respect to every
+ * coefficient of every scan.  Per line, in scan order r = 0 .. n-1 (an anticausal scan: the reversed line), a scan with input u,
+ * output y, feed-forward c0 and feedback a_0 .. a_{k-1} is
+ *     y[r] = c0 u[r] + sum_{j < r} a_j y[r-j-1]                                   zero border
+ *          + t_r (r == 0 ? u[0] : y[0])  for r < k,   t_r = sum_{j >= r} a_j       clamped border
+ * With g = dL/dy and mu the unit-gain zero-border scan of g in the OPPOSITE direction (same feedback, feed-forward 1):
+ *     dL/du = c0 mu;    clamped: dL/du[0] += t_0 mu[0] + gamma sum_{1 <= r < k} t_r mu[r],   gamma = c0 + t_0
+ *     dL/da_j = sum_{r > j} mu[r] y[r-j-1];    clamped: + beta + mu[0] u[0] + y[0] sum_{1 <= r <= j} mu[r]
+ *     dL/dc0  = sum_r mu[r] u[r];              clamped: + beta,    beta = u[0] sum_{1 <= r < k} t_r mu[r]
+ * summed over all lines and all planes (the planes share the coefficients); the scans' adjoints run in reverse order.  The
+ * affine stages compose: out = pf F(ps in + pb) + pi (ps in + pb) + po gives grad_in = pf F^T(ps g) + pi ps g.
+ *
+ * grad_coeffs: NULL, or a DEVICE buffer of n_scans * (1 + RF_MAX_ORDER) doubles; row s holds dL/dfeedfwd and then
+ * dL/dfeedback[j] of the caller's scan s, entries past the order are 0.  It lives on the device so that a backward call never
+ * synchronises and can be captured into a graph like an execute (the FIRST call of each kind builds child plans and, with
+ * grad_coeffs, allocates: make it outside a capture).  in_planes is needed exactly when grad_coeffs is given and must be NULL
+ * otherwise.  grad_in[p] == grad_out[p] is allowed.
+ *
+ * Three routes, built by the first call that needs them (plan creation costs what it did) and freed with the plan:
+ *   1. zero border, no grad_coeffs: ONE adjoint plan -- the caller's description with the scans reversed and every direction
+ *      flipped, the same path, tiles and flags, prologue (ps, 0) and epilogue (pf, pi, 0).  The launch list is that plan's.
+ *   2. clamped border, no grad_coeffs: per scan in reverse order a single-scan zero-border plan (feed-forward c0) and one
+ *      "adjoint_border" launch that touches the first k samples of every line; in place on grad_in behind the first scan.
+ *   3. with grad_coeffs: the forward rerun scan by scan (single-scan plans with the caller's border) into plan-owned planes, every
+ *      scan's output kept; then per scan in reverse order a unit-gain single-scan plan (mu), "coeff_grad" (one streaming pass
+ *      over mu, u and y, 16-byte loads, f64 sums, one slab of 1 + k doubles per workgroup; it also stores c0 mu, the next
+ *      gradient: 16 bytes per sample in all; under a clamped border its lanes then add the clamp terms, one line per lane),
+ *      "coeff_grad_sum" (one workgroup: the slabs in index order) and, clamped, "adjoint_border".  No atomics anywhere: two calls agree bit for bit, whatever else runs.  grad_in of route 3
+ *      equals that of routes 1 / 2 up to rounding and is NOT bit-identical: it is formed scan by scan as fl(c0 * mu) behind a
+ *      unit-gain scan, where routes 1 / 2 run the fused plan / scans with feed-forward c0.
+ * rf_plan_backward_timed lists the launches in execution order -- the child plans' own step names, "coeff_grad",
+ * "coeff_grad_sum", "adjoint_border" -- and synchronises the stream; rf_plan_backward_num_kernels(plan, with_coeffs) is the
+ * length of that list (0 for a plan the backward refuses).  rf_plan_backward_workspace_bytes(plan, with_coeffs): 0 without
+ * coefficients; with them (n_scans + 1) image sets of n_planes f32 planes and the slabs (1024 * (1 + RF_MAX_ORDER) doubles),
+ * allocated by the first call that needs them.  The child plans' own tails and carries come on top and are not counted;
+ * rf_plan_workspace_bytes, rf_plan_debug_buffer*, rf_plan_num_kernels and the plan tables do not change.
+ * Backward calls of one plan are ordered by the caller (one stream, or the caller's synchronisation), as for
+ * rf_var_plan_backward; forward executes keep their instance pool and may run beside them.
+ *
+ * Refused, before any HIP call and in this order:
+ *   null plan / grad_out_planes / grad_in_planes or a null plane; in_planes NULL with grad_coeffs or given without it
+ *                                                                                        RF_ERR_INVALID_ARG
+ *   planes that are not aligned as rf_plan_execute asks for the plan's path (16 bytes on the fused path and the line-parallel
+ *   kernels, except images whose width is not a multiple of 4); grad_coeffs not 8-byte aligned   RF_ERR_INVALID_ARG
+ *   a written plane (grad_in, grad_coeffs) that overlaps any other plane of the call, except grad_in[p] being exactly
+ *   grad_out[p] (which an epilogue with post_input != 0 does not allow either)              RF_ERR_INVALID_ARG
+ *   dtype != RF_F32                                                                          RF_ERR_UNSUPPORTED
+ *   in_dtype != RF_IN_PIXEL                                                                  RF_ERR_UNSUPPORTED
+ *   shard_world > 1 or RF_PLAN_FORCE_EXCHANGE                                                RF_ERR_UNSUPPORTED
+ *   grad_coeffs on a plan with pointwise stages                                              RF_ERR_UNSUPPORTED
+ *   clamped border with an extent <= the order of a scan along that dimension, or with feedfwd == 0 (route 2 divides by it);
+ *   clamped border with pointwise stages; grad_coeffs on a plan without scans                RF_ERR_UNSUPPORTED
+ *   a host-only plan                                                                         RF_ERR_HIP
+ * Out of scope: f64, integer, 16-bit and byte pixels; sharded plans; coefficient gradients through pointwise stages; pointwise
+ * stages on a clamped plan; a derivative with respect to the sigma of rf_gaussian_weights; second derivatives; fusing the
+ * clamped route's scans.  Routes 2 and 3 are not tuned for time. */
+int    rf_plan_backward(rf_plan *plan, const void *const *in_planes, const void *const *grad_out_planes,
+                        void *const *grad_in_planes, double *grad_coeffs, void *stream);
+int    rf_plan_backward_timed(rf_plan *plan, const void *const *in_planes, const void *const *grad_out_planes,
+                              void *const *grad_in_planes, double *grad_coeffs, void *stream, float *ms_out,
+                              const char **names_out, int capacity);
+int    rf_plan_backward_num_kernels(rf_plan *plan, int with_coeffs);
+size_t rf_plan_backward_workspace_bytes(rf_plan *plan, int with_coeffs);
+
 /* ---- coefficient design (lib/iir_coeff.cpp:162-177, 222-234, 236-263, 205-220) ------------ */
 int rf_gaussian_weights(float sigma, int order, float *coeff_out /* order+1 */);
 int rf_integral_image_coeff(int n, float *coeff_out /* n+1 */);

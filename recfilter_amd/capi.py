@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = [
     "rf_var_plan_backward_power", "rf_var_plan_backward_power_timed", "rf_var_distances_backward",
     "rf_smooth_plan_backward", "rf_smooth_plan_backward_timed", "rf_smooth_plan_backward_num_kernels",
     "rf_smooth_plan_backward_workspace_bytes", "rf_smooth_plan_create_batched",
+    "rf_plan_backward", "rf_plan_backward_timed", "rf_plan_backward_num_kernels", "rf_plan_backward_workspace_bytes",
 ]
 
 
@@ -184,6 +185,11 @@ def lib() -> ctypes.CDLL:
     L.rf_plan_debug_buffer.argtypes = [vp, ctypes.c_int, vpp, ctypes.POINTER(ctypes.c_size_t)]
     L.rf_plan_debug_buffer_kind.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     L.rf_plan_debug_fill.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
+    L.rf_plan_backward.argtypes = [vp, vpp, vpp, vpp, vp, vp]
+    L.rf_plan_backward_timed.argtypes = [vp, vpp, vpp, vpp, vp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_plan_backward_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_plan_backward_workspace_bytes.argtypes = [vp, ctypes.c_int]
+    L.rf_plan_backward_workspace_bytes.restype = ctypes.c_size_t
     L.rf_gaussian_weights.argtypes = [ctypes.c_float, ctypes.c_int, fp]
     L.rf_integral_image_coeff.argtypes = [ctypes.c_int, fp]
     L.rf_overlap_feedback_coeff.argtypes = [fp, ctypes.c_int, fp, ctypes.c_int, fp]

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "plan.h"
+#include "plan_adjoint.h"
 #include "plan_smooth.h"
 #include "plan_var.h"
 
@@ -396,6 +397,29 @@ int rf_plan_debug_fill(rf_plan *plan, int index, int byte, void *stream) {
     RF_HIP_CHECK(hipMemsetAsync(b->ptr, byte, b->bytes, (hipStream_t)stream));
     return RF_OK;
 }
+
+// ---- backward of a plan (plan_adjoint.cpp) ------------------------------------------------
+int rf_plan_backward(rf_plan *plan, const void *const *in_planes, const void *const *grad_out_planes, void *const *grad_in_planes,
+                     double *grad_coeffs, void *stream) {
+    return fenced("rf_plan_backward", [&] {
+        return plan_backward(plan, in_planes, grad_out_planes, grad_in_planes, grad_coeffs, stream, false, nullptr, nullptr, 0);
+    });
+}
+
+int rf_plan_backward_timed(rf_plan *plan, const void *const *in_planes, const void *const *grad_out_planes, void *const *grad_in_planes,
+                           double *grad_coeffs, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_plan_backward_timed", [&] {
+        return plan_backward(plan, in_planes, grad_out_planes, grad_in_planes, grad_coeffs, stream, true, ms_out, names_out, capacity);
+    });
+}
+
+int rf_plan_backward_num_kernels(rf_plan *plan, int with_coeffs) {
+    int n = 0;
+    (void)fenced("rf_plan_backward_num_kernels", [&] { n = plan_backward_num_kernels(plan, with_coeffs); return (int)RF_OK; });
+    return n;
+}
+
+size_t rf_plan_backward_workspace_bytes(rf_plan *plan, int with_coeffs) { return plan_backward_workspace_bytes(plan, with_coeffs); }
 
 // ---- coefficient design ------------------------------------------------------------------
 // Recursive Gaussian of van Vliet, Young and Verbeek: the poles of a fixed prototype are

@@ -44,6 +44,8 @@ struct Pointwise {
 
 // How a device buffer of a plan was made (rf_buffer_kind): a table uploaded at build, workspace zeroed at build and relied on
 // afterwards, or scratch that every execute writes before it reads it.
+struct Adjoint;      // plan_adjoint.h: what rf_plan_backward built for a plan
+
 struct DeviceBuffer {
     void *ptr = nullptr;         // null in a host-only plan, which records what it would have allocated
     size_t bytes = 0;
@@ -156,6 +158,11 @@ struct rf_plan {
     // recorded behind every execution; created once when the plan is built (never rewritten), queried only while the
     // instance is not owned -- i.e. never while another thread may be about to record it
     hipEvent_t done = nullptr;
+
+    // rf_plan_backward (plan_adjoint.cpp): the child plans, launch lists and workspace of the backward, built by the first call
+    // that needs them and freed with the plan.  Nothing of the forward side -- workspace_bytes, buffers, steps, tables, the
+    // instance pool -- knows about it.
+    std::shared_ptr<rf::Adjoint> adjoint;
 
     ~rf_plan();
     void *alloc(size_t bytes, bool zero, int *status);                 // workspace: RF_BUFFER_ZEROED / RF_BUFFER_SCRATCH

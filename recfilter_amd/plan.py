@@ -6,6 +6,7 @@ Images are torch CUDA(HIP) tensors used purely as device memory: a tensor of sha
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import List, Optional, Sequence, Tuple
 
@@ -141,6 +142,7 @@ class Plan:
         d.flags = int(DEFAULT_FLAGS if flags is None else flags)
         self._desc = d
         self.shape = shape
+        self.n_scans = len(scans)
         self.planes = int(planes)
         self.np_dtype = _CODE_NP.get(d.dtype)        # None for bfloat16, which numpy does not have
         self.dtype_code = int(d.dtype)
@@ -281,6 +283,60 @@ class Plan:
         names = (ctypes.c_char_p * max(n, 1))()
         capi.check(capi.lib().rf_plan_execute_timed(self._h, pin, pout, self._stream(stream), ms, names, n))
         return outputs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    # -- backward (rf_plan_backward) ------------------------------------------------------------
+    def _backward_arguments(self, grad_outs, grad_ins, inputs, coeff_grads, stream):
+        import torch
+        grad_outs = list(grad_outs)
+        if coeff_grads and inputs is None:
+            raise ValueError("coefficient gradients need the inputs of the execute (inputs=...)")
+        if not coeff_grads and inputs is not None:
+            raise ValueError("inputs are read only for coefficient gradients: pass coeff_grads=True, or leave inputs out")
+        if grad_ins is None:
+            grad_ins = [torch.empty_like(g) for g in grad_outs]
+        pgo, pgi = self._pointers(grad_outs), self._pointers(grad_ins)
+        pin = self._pointers(list(inputs)) if coeff_grads else None
+        coeffs = None
+        if coeff_grads:
+            coeffs = torch.empty((self.n_scans, 1 + capi.RF_MAX_ORDER), dtype=torch.float64, device=grad_outs[0].device)
+        pc = ctypes.c_void_p(coeffs.data_ptr()) if coeffs is not None else None
+        return pin, pgo, pgi, pc, grad_ins, coeffs, self._stream(stream)
+
+    def backward(self, grad_outs, grad_ins=None, inputs=None, coeff_grads=False, stream=None):
+        """rf_plan_backward: (grad_ins, coeffs) from grad_outs = dL/d(outputs) of an execute.  grad_ins = dL/d(inputs) (new
+        tensors unless given; grad_ins[p] may be grad_outs[p]).  coeff_grads=True also returns `coeffs`, a device f64 tensor of
+        shape (n_scans, 1 + RF_MAX_ORDER): row s = [dL/dfeedfwd, dL/dfeedback...] of scan s summed over the planes, zeros past
+        the order; it needs `inputs`, the planes the execute read.  Otherwise coeffs is None and inputs must be left out.
+        Asynchronous on `stream` (default: torch's current stream); nothing synchronises.  f32 planes, unsharded plans."""
+        pin, pgo, pgi, pc, grad_ins, coeffs, s = self._backward_arguments(grad_outs, grad_ins, inputs, coeff_grads, stream)
+        capi.check(capi.lib().rf_plan_backward(self._h, pin, pgo, pgi, pc, s))
+        return grad_ins, coeffs
+
+    def backward_timed(self, grad_outs, grad_ins=None, inputs=None, coeff_grads=False, stream=None):
+        """rf_plan_backward_timed: (grad_ins, coeffs, [(launch name, ms), ...]) in execution order; synchronises the stream."""
+        pin, pgo, pgi, pc, grad_ins, coeffs, s = self._backward_arguments(grad_outs, grad_ins, inputs, coeff_grads, stream)
+        n = self.backward_num_kernels(coeff_grads)
+        ms = (ctypes.c_float * max(n, 1))()
+        names = (ctypes.c_char_p * max(n, 1))()
+        capi.check(capi.lib().rf_plan_backward_timed(self._h, pin, pgo, pgi, pc, s, ms, names, n))
+        return grad_ins, coeffs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    def backward_num_kernels(self, coeff_grads: bool = False) -> int:
+        """launches of one backward call (0 for a plan the backward refuses); the first query builds the child plans"""
+        return int(capi.lib().rf_plan_backward_num_kernels(self._h, int(bool(coeff_grads))))
+
+    def backward_workspace_bytes(self, coeff_grads: bool = False) -> int:
+        """device memory the backward allocates on first need beyond its child plans' own tails and carries: 0 without
+        coefficient gradients, (n_scans + 1) image sets and the reduction's slabs with them"""
+        return int(capi.lib().rf_plan_backward_workspace_bytes(self._h, int(bool(coeff_grads))))
+
+    def apply(self, inputs):
+        """execute, out of place, as a differentiable torch operation: a tuple of `planes` output planes whose values are bit
+        for bit execute's, differentiable with respect to the inputs (backward is `backward`).  No double backward."""
+        inputs = list(inputs)
+        if len(inputs) != self.planes:
+            raise ValueError(f"expected {self.planes} planes, got {len(inputs)}")
+        return _plan_function().apply(self, *inputs)
 
     # stepping API (sharded execution) ---------------------------------------------------------
     def begin(self, inputs, outputs, stream=None):
@@ -435,3 +491,114 @@ def second_order_sections(coeff: Sequence[float]) -> List[List[float]]:
         sections.append([1.0, float(real[0])])
     sections[0][0] = coeff[0]
     return sections
+
+
+# ---- torch.autograd ---------------------------------------------------------------------------
+_function = None
+_filter_function = None
+
+
+def _plan_function():
+    """the torch.autograd.Function behind Plan.apply (torch is imported when it is first needed)"""
+    global _function
+    if _function is not None:
+        return _function
+    import torch
+
+    class PlanFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, *inputs):
+            ctx.plan = plan
+            return tuple(plan.execute([t.contiguous() for t in inputs]))
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, *grad_outs):
+            with torch.cuda.device(grad_outs[0].device):
+                grad_ins, _ = ctx.plan.backward([g.contiguous() for g in grad_outs])
+            return (None, *[g if n else None for g, n in zip(grad_ins, ctx.needs_input_grad[1:])])
+
+    _function = PlanFunction
+    return _function
+
+
+FILTER_PLAN_CACHE = 16       # plans recursive_filter keeps (least recently used first out)
+_filter_plans: "collections.OrderedDict[tuple, Plan]" = collections.OrderedDict()
+
+
+def _filter_plan(key) -> Plan:
+    """the cached plan of `key` = (shape, device index, clamped, ((dim, causal, (coefficients...)), ...)); a plan that falls
+    out of the cache is destroyed"""
+    plan = _filter_plans.get(key)
+    if plan is not None and plan._h:
+        _filter_plans.move_to_end(key)
+        return plan
+    shape, device, clamped, scans = key
+    plan = Plan(shape, [(d, c, list(w)) for d, c, w in scans], clamped=clamped, device=device)
+    _filter_plans[key] = plan
+    while len(_filter_plans) > FILTER_PLAN_CACHE:
+        _, old = _filter_plans.popitem(last=False)
+        old.close()
+    return plan
+
+
+def _recursive_filter_function():
+    global _filter_function
+    if _filter_function is not None:
+        return _filter_function
+    import torch
+
+    class RecursiveFilterFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, key, image, *coeffs):
+            image = image.contiguous()
+            ctx.key = key
+            ctx.coeffs = [(c.shape, c.dtype, c.device) for c in coeffs]
+            ctx.save_for_backward(image)
+            with torch.cuda.device(image.device):
+                return _filter_plan(key).execute([image])[0]
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            (image,) = ctx.saved_tensors
+            want = any(ctx.needs_input_grad[2:])
+            with torch.cuda.device(image.device):
+                plan = _filter_plan(ctx.key)           # (built again if the cache dropped it meanwhile)
+                if want:
+                    grad_ins, rows = plan.backward([grad_out.contiguous()], inputs=[image], coeff_grads=True)
+                else:
+                    grad_ins, rows = plan.backward([grad_out.contiguous()])
+            grads = [None] * len(ctx.coeffs)
+            for s, ((shape, dtype, device), need) in enumerate(zip(ctx.coeffs, ctx.needs_input_grad[2:])):
+                if need:
+                    grads[s] = rows[s, :shape[0]].to(device=device, dtype=dtype)
+            return (None, grad_ins[0] if ctx.needs_input_grad[1] else None, *grads)
+
+    _filter_function = RecursiveFilterFunction
+    return _filter_function
+
+
+def recursive_filter(image, scans, coeffs, clamped: bool = False):
+    """The recursive filter `scans` = [(dim, causal), ...] (dim 0 = x, the last axis) of the f32 device tensor `image` (1 to 3
+    dimensions), scan s with the coefficients coeffs[s] = a 1-D tensor [feedfwd, fb1 .. fbk]: differentiable with respect to
+    the image and to every coefficient tensor.  One tensor object may appear several times in `coeffs` (the four scans of a
+    Gaussian): autograd sums its rows.  The values are a Plan's execute; backward is Plan.backward (no double backward).
+    Plans are cached by shape, device, border and coefficient VALUES in a least-recently-used cache of FILTER_PLAN_CACHE plans;
+    a plan that falls out is destroyed.  Reading the coefficient values from device tensors SYNCHRONISES with the device on
+    every call (a plan turns its coefficients into tables on the host); keep the coefficients on the host where that matters.
+    Calls that share a plan are ordered by the caller (one stream)."""
+    import torch
+    scans, coeffs = list(scans), list(coeffs)
+    if len(scans) != len(coeffs):
+        raise ValueError(f"{len(scans)} scans need {len(scans)} coefficient tensors, got {len(coeffs)}")
+    if not image.is_cuda or image.dtype != torch.float32:
+        raise TypeError("recursive_filter takes an f32 device tensor")
+    values = []
+    for s, c in enumerate(coeffs):
+        if not torch.is_tensor(c) or c.dim() != 1 or c.numel() < 2 or not c.is_floating_point():
+            raise ValueError(f"coeffs[{s}]: a 1-D floating-point tensor [feedfwd, fb1 .. fbk] is needed")
+        values.append(tuple(float(np.float32(v)) for v in c.detach().cpu().tolist()))
+    key = (tuple(image.shape), image.device.index, bool(clamped),
+           tuple((int(d), bool(c), v) for (d, c), v in zip(scans, values)))
+    return _recursive_filter_function().apply(key, image, *coeffs)
