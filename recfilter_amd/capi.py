@@ -243,3 +243,39 @@ def lib() -> ctypes.CDLL:
 def check(status: int) -> None:
     if status != RF_OK:
         raise RecFilterError(status, lib().rf_last_error_string().decode())
+
+
+def _timed(call, n: int):
+    """[(kernel name, ms), ...] of a *_timed entry point with `n` launches: call(ms, names, n) returns its status"""
+    ms = (ctypes.c_float * max(n, 1))()
+    names = (ctypes.c_char_p * max(n, 1))()
+    check(call(ms, names, n))
+    return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+class _PlanHandle:
+    """the lifetime of the library's plan behind self._h; `_destroy` names the entry point that frees it"""
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _stream(stream) -> ctypes.c_void_p:
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        return ctypes.c_void_p(s.cuda_stream)

@@ -10,6 +10,7 @@
 #include "plan_adjoint.h"
 #include "plan_smooth.h"
 #include "plan_var.h"
+#include "run_support.h"
 
 namespace rf {
 
@@ -45,8 +46,7 @@ int set_context(rf_plan *plan, const void *const *in_planes, void *const *out_pl
             return RF_ERR_INVALID_ARG;
         }
         // the fused kernels and the line-parallel untiled kernels move 16 bytes per lane (4 for unsigned-byte input planes)
-        // (an image whose width is not a multiple of 4 has element-aligned rows anyway: any element-aligned plane)
-        if (plan->vector_access && !(plan->path == RF_PATH_TILED_FUSED && plan->ndim >= 2 && plan->dims[0].N % 4 != 0)) {
+        if (wants_aligned_planes(plan)) {
             const uintptr_t in_mask = plan->pw.in_u8 ? 3u : 15u, out_mask = plan->pw.out_u8 ? 3u : 15u;
             if (((uintptr_t)in_planes[pl] & in_mask) != 0 || ((uintptr_t)out_planes[pl] & out_mask) != 0) {
                 set_error("plane %d: this plan's kernels (%s) need 16-byte aligned image pointers (4-byte for uint8 inputs)", pl,
@@ -161,6 +161,37 @@ int run_pending_interior(rf_plan *plan) {
     return run_steps(plan, plan->interior_steps);
 }
 
+// rf_plan_execute (timed == false: ms_out is unused, no event is created, the call can be captured into a graph) and
+// rf_plan_execute_timed: every step of a single-device execute on an instance of the plan, a mark of the timer behind each.
+int execute_plan(rf_plan *plan, const void *const *in_planes, void *const *out_planes, void *stream, bool timed, float *ms_out,
+                 const char **names_out, int capacity) {
+    if (!plan) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    if (plan->sharded()) { set_error("a sharded plan must be driven through rf_plan_begin/exchange/finish"); return RF_ERR_STATE; }
+    if (stepping_instance(plan) != nullptr) { set_error("rf_plan_execute between this thread's rf_plan_begin and rf_plan_finish"); return RF_ERR_STATE; }
+    rf_plan *inst = acquire_instance(plan, (hipStream_t)stream);
+    if (!inst) return RF_ERR_NOMEM;
+    struct Release {
+        rf_plan *plan, *inst; bool enqueued = false;
+        ~Release() { release_instance(plan, inst, enqueued); }
+    } guard{plan, inst};
+    if (int rc = set_context(inst, in_planes, out_planes, stream)) return rc;
+    for (auto &ex : inst->exchanges) ex.send = ex.scratch;
+    const auto steps = single_device_steps(inst);
+    if (timed) {
+        // (names: the primary's steps have the same names and live as long as the plan)
+        const auto names = single_device_steps(plan);
+        if (int rc = timed_names(steps.size(), [&](size_t i) { return names[i]->name.c_str(); }, ms_out, names_out, capacity)) return rc;
+    }
+    LaunchTimer timer(inst->stream, timed ? ms_out : nullptr, steps.size());      // (destroyed before the instance is released)
+    if (timer.status() != RF_OK) return timer.status();
+    guard.enqueued = true;                       // from here on launches are attempted on inst->stream
+    for (const Step *st : steps) {
+        for (int pl = 0; pl < inst->n_planes; pl++)
+            if (int rc = st->run(pl)) return rc;
+        if (int rc = timer.mark()) return rc;
+    }
+    return timer.finish();
+}
 
 // Fenced bodies: whatever the builder or the driver throws (std::bad_alloc of a host vector) becomes a status.
 template <typename F>
@@ -217,68 +248,12 @@ int rf_plan_num_kernels(const rf_plan *plan) { return plan ? (int)single_device_
 int rf_plan_num_exchanges(const rf_plan *plan) { return plan ? (int)plan->exchanges.size() : 0; }
 
 int rf_plan_execute(rf_plan *plan, const void *const *in_planes, void *const *out_planes, void *stream) {
-    if (!plan) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    if (plan->sharded()) { set_error("a sharded plan must be driven through rf_plan_begin/exchange/finish"); return RF_ERR_STATE; }
-    if (stepping_instance(plan) != nullptr) { set_error("rf_plan_execute between this thread's rf_plan_begin and rf_plan_finish"); return RF_ERR_STATE; }
-    rf_plan *inst = acquire_instance(plan, (hipStream_t)stream);
-    if (!inst) return RF_ERR_NOMEM;
-    int rc = set_context(inst, in_planes, out_planes, stream);
-    const bool context_set = rc == RF_OK;        // from here on launches are attempted on inst->stream
-    if (rc == RF_OK) {
-        for (auto &ex : inst->exchanges) ex.send = ex.scratch;
-        for (const Step *st : single_device_steps(inst)) {
-            for (int pl = 0; pl < inst->n_planes && rc == RF_OK; pl++) rc = st->run(pl);
-            if (rc != RF_OK) break;
-        }
-    }
-    release_instance(plan, inst, context_set);
-    return rc;
+    return execute_plan(plan, in_planes, out_planes, stream, false, nullptr, nullptr, 0);
 }
 
 int rf_plan_execute_timed(rf_plan *plan, const void *const *in_planes, void *const *out_planes, void *stream,
                           float *ms_out, const char **names_out, int capacity) {
-    if (!plan) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    if (plan->sharded()) { set_error("a sharded plan must be driven through rf_plan_begin/exchange/finish"); return RF_ERR_STATE; }
-    if (stepping_instance(plan) != nullptr) { set_error("rf_plan_execute between this thread's rf_plan_begin and rf_plan_finish"); return RF_ERR_STATE; }
-    rf_plan *inst = acquire_instance(plan, (hipStream_t)stream);
-    if (!inst) return RF_ERR_NOMEM;
-    struct Release {
-        rf_plan *plan, *inst; bool ran = false;
-        ~Release() { release_instance(plan, inst, ran); }
-    } guard{plan, inst};
-    int rc = set_context(inst, in_planes, out_planes, stream);
-    if (rc) return rc;
-    for (auto &ex : inst->exchanges) ex.send = ex.scratch;
-    auto steps = single_device_steps(inst);
-    if (capacity < (int)steps.size() || !ms_out) { set_error("ms_out too small: need %zu", steps.size()); return RF_ERR_INVALID_ARG; }
-    // events are destroyed on every return path; outputs are fully written even when a step fails
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } events;
-    // (names: the primary's steps have the same names and live as long as the plan)
-    auto names = single_device_steps(plan);
-    for (size_t i = 0; i < steps.size(); i++) {
-        ms_out[i] = 0.0f;
-        if (names_out) names_out[i] = names[i]->name.c_str();
-    }
-    for (size_t i = 0; i < steps.size() + 1; i++) {
-        hipEvent_t e;
-        RF_HIP_CHECK(hipEventCreate(&e));
-        events.ev.push_back(e);
-    }
-    std::vector<hipEvent_t> &ev = events.ev;
-    RF_HIP_CHECK(hipEventRecord(ev[0], inst->stream));
-    guard.ran = true;
-    for (size_t i = 0; i < steps.size() && rc == RF_OK; i++) {
-        for (int pl = 0; pl < inst->n_planes && rc == RF_OK; pl++) rc = steps[i]->run(pl);
-        if (rc == RF_OK && hipEventRecord(ev[i + 1], inst->stream) != hipSuccess) rc = RF_ERR_HIP;
-    }
-    if (rc == RF_OK && hipEventSynchronize(ev.back()) != hipSuccess) rc = RF_ERR_HIP;
-    for (size_t i = 0; i < steps.size() && rc == RF_OK; i++)
-        if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = RF_ERR_HIP;
-    if (rc == RF_ERR_HIP) set_error("HIP event timing failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return execute_plan(plan, in_planes, out_planes, stream, true, ms_out, names_out, capacity);
 }
 
 int rf_plan_begin(rf_plan *plan, const void *const *in_planes, void *const *out_planes, void *stream) {
@@ -574,15 +549,7 @@ int rf_tap_filter(const void *const *in_planes, int n_in, void *out, int ndim, c
 }
 
 // ---- spatially varying first-order scans (plan_var.cpp) ---------------------------------------------------------------------
-// what the *_timed entry points of the varying scans and the smoothing plan do before they run: ms_out has a slot per launch,
-// and names_out (where given) receives the launches' names
-static int timed_names(const std::vector<std::string> &names, float *ms_out, const char **names_out, int capacity) {
-    if (!ms_out || capacity < (int)names.size()) { set_error("ms_out too small: need %zu", names.size()); return RF_ERR_INVALID_ARG; }
-    if (names_out)
-        for (size_t i = 0; i < names.size(); i++) names_out[i] = names[i].c_str();
-    return RF_OK;
-}
-
+// (the *_timed entry points of the varying scans and the smoothing plan check ms_out and fill names_out before they run)
 int rf_var_plan_create(const rf_var_desc *desc, rf_var_plan **plan_out) {
     return fenced("rf_var_plan_create", [&] { return build_var_plan(desc, plan_out); });
 }

@@ -177,6 +177,13 @@ struct rf_plan {
 namespace rf {
 int build_plan(const rf_filter_desc *desc, rf_plan **out);
 
+// Which plans need 16-byte aligned planes (rf_plan_execute, rf_plan_begin, rf_plan_backward): those whose kernels move 16 bytes
+// per lane (rf_plan::vector_access) -- except that an image whose width is not a multiple of 4 has element-aligned rows anyway,
+// and the fused path then takes any element-aligned plane.
+inline bool wants_aligned_planes(const rf_plan *p) {
+    return p->vector_access && !(p->path == RF_PATH_TILED_FUSED && p->ndim >= 2 && p->dims[0].N % 4 != 0);
+}
+
 // every step of a single-device execute, in order: begin, exchange_local, interior, exchange_apply (plans built with the
 // exchange structure; left out where !with_apply), finish
 std::vector<const Step *> single_device_steps(const rf_plan *plan, bool with_apply = true);

@@ -16,6 +16,8 @@
 #include <algorithm>
 #include <cstring>
 
+#include "run_support.h"
+
 namespace rf {
 
 Adjoint::~Adjoint() {
@@ -318,15 +320,6 @@ int ensure_built(rf_plan *plan, bool with_coeffs) {
     return rc;
 }
 
-// rf_plan_execute's rule: these kernels move 16 bytes per lane (an image whose width is not a multiple of 4 has element-aligned
-// rows anyway)
-bool wants_aligned_planes(const rf_plan *p) {
-    return p->vector_access && !(p->path == RF_PATH_TILED_FUSED && p->ndim >= 2 && p->dims[0].N % 4 != 0);
-}
-
-struct Extent { uintptr_t lo, hi; const char *what; int index; };
-bool overlap(const Extent &a, const Extent &b) { return a.lo < b.hi && b.lo < a.hi; }
-
 }  // namespace
 
 int plan_backward(rf_plan *plan, const void *const *in_planes, const void *const *grad_out_planes, void *const *grad_in_planes,
@@ -338,56 +331,32 @@ int plan_backward(rf_plan *plan, const void *const *in_planes, const void *const
     if (!with_coeffs && in_planes) { set_error("rf_plan_backward: in_planes must be NULL without grad_coeffs"); return RF_ERR_INVALID_ARG; }
     const rf_filter_desc &d = plan->saved.d;
     const int P = d.n_planes;
-    for (int pl = 0; pl < P; pl++)
-        if (!grad_out_planes[pl] || !grad_in_planes[pl] || (with_coeffs && !in_planes[pl])) {
-            set_error("rf_plan_backward: plane %d: null image pointer", pl);
-            return RF_ERR_INVALID_ARG;
-        }
-    auto misaligned = [&]() {
-        for (int pl = 0; pl < P; pl++) {
-            uintptr_t bits = (uintptr_t)grad_out_planes[pl] | (uintptr_t)grad_in_planes[pl];
-            if (with_coeffs) bits |= (uintptr_t)in_planes[pl];
-            if (bits & 15u) {
-                set_error("rf_plan_backward: plane %d: this plan's kernels need 16-byte aligned image pointers", pl);
-                return true;
-            }
-        }
-        return false;
+    // null planes first, then (mask 15) every plane's alignment
+    auto check_planes = [&](uintptr_t mask) {
+        for (int pl = 0; pl < P; pl++)
+            if (int rc = check_plane("rf_plan_backward: plane", pl, {{grad_out_planes[pl]}, {grad_in_planes[pl]}, {with_coeffs ? in_planes[pl] : nullptr, with_coeffs}},
+                                     mask, "null image pointer", "this plan's kernels need 16-byte aligned image pointers"))
+                return rc;
+        return (int)RF_OK;
     };
-    if (wants_aligned_planes(plan) && misaligned()) return RF_ERR_INVALID_ARG;
+    if (int rc = check_planes(0)) return rc;
+    if (wants_aligned_planes(plan))
+        if (int rc = check_planes(15u)) return rc;
     if (with_coeffs && ((uintptr_t)grad_coeffs & 7u)) { set_error("rf_plan_backward: grad_coeffs must be 8-byte aligned"); return RF_ERR_INVALID_ARG; }
-    {
-        size_t plane_bytes = dtype_bytes(d.dtype);
-        for (int i = 0; i < d.ndim; i++) plane_bytes *= (size_t)d.extent[i];
-        std::vector<Extent> read, written;
-        for (int pl = 0; pl < P; pl++) {
-            written.push_back({(uintptr_t)grad_in_planes[pl], (uintptr_t)grad_in_planes[pl] + plane_bytes, "grad_in", pl});
-            read.push_back({(uintptr_t)grad_out_planes[pl], (uintptr_t)grad_out_planes[pl] + plane_bytes, "grad_out", pl});
-            if (with_coeffs) read.push_back({(uintptr_t)in_planes[pl], (uintptr_t)in_planes[pl] + plane_bytes, "in", pl});
-        }
-        if (with_coeffs)
-            written.push_back({(uintptr_t)grad_coeffs, (uintptr_t)grad_coeffs + (size_t)std::max(d.n_scans, 1) * kAdjSlabDoubles * sizeof(double),
-                               "grad_coeffs", 0});
-        for (size_t i = 0; i < written.size(); i++) {
-            const Extent &w = written[i];
-            for (size_t j = i + 1; j < written.size(); j++)
-                if (overlap(w, written[j])) {
-                    set_error("rf_plan_backward: %s[%d] overlaps %s[%d]", w.what, w.index, written[j].what, written[j].index);
-                    return RF_ERR_INVALID_ARG;
-                }
-            for (const Extent &r : read) {
-                const bool in_place = std::strcmp(w.what, "grad_in") == 0 && std::strcmp(r.what, "grad_out") == 0 && w.index == r.index && w.lo == r.lo;
-                if (!in_place && overlap(w, r)) {
-                    set_error("rf_plan_backward: %s[%d] overlaps %s[%d]", w.what, w.index, r.what, r.index);
-                    return RF_ERR_INVALID_ARG;
-                }
-                if (in_place && (d.pointwise.flags & RF_POINTWISE_POST) && d.pointwise.post_input != 0.0f) {
-                    set_error("rf_plan_backward: plane %d: an epilogue that reads the input needs grad_in != grad_out", w.index);
-                    return RF_ERR_INVALID_ARG;
-                }
+    // what is written (grad_in planes, the rows of grad_coeffs) against everything that is read and everything else that is written
+    size_t plane_bytes = dtype_bytes(d.dtype);
+    for (int i = 0; i < d.ndim; i++) plane_bytes *= (size_t)d.extent[i];
+    const void *const coeff_rows = grad_coeffs;
+    const PlaneList written[2] = {{"grad_in", (const void *const *)grad_in_planes, P, plane_bytes},
+                                  {"grad_coeffs", &coeff_rows, with_coeffs ? 1 : 0, (size_t)std::max(d.n_scans, 1) * kAdjSlabDoubles * sizeof(double)}};
+    const PlaneList read = {"in", in_planes, with_coeffs ? P : 0, plane_bytes};
+    if (int rc = check_written_planes(written, 2, &read, 1, {"grad_out", grad_out_planes, P, plane_bytes})) return rc;
+    if ((d.pointwise.flags & RF_POINTWISE_POST) && d.pointwise.post_input != 0.0f)
+        for (int pl = 0; pl < P; pl++)
+            if (grad_in_planes[pl] == grad_out_planes[pl]) {
+                set_error("rf_plan_backward: plane %d: an epilogue that reads the input needs grad_in != grad_out", pl);
+                return RF_ERR_INVALID_ARG;
             }
-        }
-    }
     if (int rc = refuse_description(plan, with_coeffs)) return rc;
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot run a backward"); return RF_ERR_HIP; }
 
@@ -397,7 +366,8 @@ int plan_backward(rf_plan *plan, const void *const *in_planes, const void *const
     Adjoint *a = plan->adjoint.get();
     // (a single scan of a filter may run on a path that moves 16 bytes per lane where the whole filter's plan does not)
     for (const auto &child : a->children)
-        if (wants_aligned_planes(child.get()) && misaligned()) return RF_ERR_INVALID_ARG;
+        if (wants_aligned_planes(child.get()))
+            if (int rc = check_planes(15u)) return rc;
     if (with_coeffs)
         if (int rc = ensure_workspace(plan, a)) return rc;
     for (int pl = 0; pl < P; pl++) {
@@ -408,37 +378,15 @@ int plan_backward(rf_plan *plan, const void *const *in_planes, const void *const
     a->gcoeff = grad_coeffs;
     a->stream = (hipStream_t)stream;
     const std::vector<AdjLaunch> &list = with_coeffs ? a->coeff : a->plain;
-    if (!timed) {
-        for (const AdjLaunch &l : list)
-            if (int rc = l.run()) return rc;
-        return RF_OK;
+    if (timed)
+        if (int rc = timed_names(list.size(), [&](size_t i) { return list[i].name.c_str(); }, ms_out, names_out, capacity)) return rc;
+    LaunchTimer timer(a->stream, timed ? ms_out : nullptr, list.size());
+    if (timer.status() != RF_OK) return timer.status();
+    for (const AdjLaunch &l : list) {
+        if (int rc = l.run()) return rc;
+        if (int rc = timer.mark()) return rc;
     }
-    if (capacity < (int)list.size() || !ms_out) { set_error("ms_out too small: need %zu", list.size()); return RF_ERR_INVALID_ARG; }
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } events;
-    for (size_t i = 0; i < list.size(); i++) {
-        ms_out[i] = 0.0f;
-        if (names_out) names_out[i] = list[i].name.c_str();
-    }
-    for (size_t i = 0; i < list.size() + 1; i++) {
-        hipEvent_t e;
-        RF_HIP_CHECK(hipEventCreate(&e));
-        events.ev.push_back(e);
-    }
-    std::vector<hipEvent_t> &ev = events.ev;
-    RF_HIP_CHECK(hipEventRecord(ev[0], a->stream));
-    int rc = RF_OK;
-    for (size_t i = 0; i < list.size() && rc == RF_OK; i++) {
-        rc = list[i].run();
-        if (rc == RF_OK && hipEventRecord(ev[i + 1], a->stream) != hipSuccess) rc = RF_ERR_HIP;
-    }
-    if (rc == RF_OK && hipEventSynchronize(ev.back()) != hipSuccess) rc = RF_ERR_HIP;
-    for (size_t i = 0; i < list.size() && rc == RF_OK; i++)
-        if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = RF_ERR_HIP;
-    if (rc == RF_ERR_HIP) set_error("HIP event timing failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
+    return timer.finish();
 }
 
 int plan_backward_num_kernels(rf_plan *plan, int with_coeffs) {

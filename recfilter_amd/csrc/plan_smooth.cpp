@@ -16,9 +16,9 @@
 // A batched plan (rf_smooth_plan_create_batched) is the same sequence: every launch takes all the images on gridDim.z, each image
 // with its own distance planes, tails, carries and working planes, laid out image after image as a single-image plan lays out
 // its one.  The launch count does not depend on the batch.  The caller's planes are checked per (image, plane) extent, sorted
-// (check_extents); a single image's by the checks plan_var.h shares with the varying plan (check_plane, check_written_planes).
+// (check_extents); a single image's by the checks every plan family shares (run_support.h: check_plane, check_written_planes).
 //
-// Both run functions construct one LaunchTimer (plan_var.h) and hand it to every launcher they call, so the slots of a timed run
+// Both run functions construct one LaunchTimer (run_support.h) and hand it to every launcher they call, so the slots of a timed run
 // follow the plan's name lists; the constants of the power form, log2 and ln of every a_k, are the plan's from its construction.
 #include "plan_smooth.h"
 

@@ -1,12 +1,11 @@
 // plan_var.h -- the plan behind the rf_var_plan_* entry points: spatially varying first-order scans (plan_var.cpp).
 #pragma once
 
-#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "kernels_var.h"
-#include "rf_internal.h"
+#include "run_support.h"
 
 // One stage = one scan, or a causal scan directly followed by the anticausal scan of the same dimension and weight plane
 // (where the two are all of a run along that dimension: plan_var.cpp).
@@ -47,53 +46,6 @@ struct rf_var_plan {
 
 namespace rf {
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch = 1);
-
-// The events of one timed run: slot i of ms_out receives the time from the i-th mark (the construction is mark 0) to the next.
-// ms_out == nullptr: a plain asynchronous run -- no event is created and every method returns RF_OK.  The events are destroyed
-// on every path.  n_slots: the launches of the run, one name each (the caller of the run function has checked the capacity).
-class LaunchTimer {
-public:
-    LaunchTimer(hipStream_t stream, float *ms_out, size_t n_slots);      // zero-fills ms_out; look at status() before launching
-    ~LaunchTimer();
-    LaunchTimer(const LaunchTimer &) = delete;
-    LaunchTimer &operator=(const LaunchTimer &) = delete;
-    int status() const { return status_; }
-    int mark();         // behind every launch, and behind every slot whose launch was not issued
-    void skip();        // just before mark(), for a slot whose launch was not issued: it reports 0 ms
-    int finish();       // synchronises with the last mark and fills ms_out
-private:
-    int create();
-    hipStream_t stream_;
-    float *ms_out_;
-    size_t n_slots_, marks_ = 0;
-    int status_ = RF_OK;
-    std::vector<hipEvent_t> events_;
-    std::vector<size_t> skipped_;
-};
-
-// ---- checks the run functions of plan_var.cpp and plan_smooth.cpp share ---------------------------------------------------------
-inline bool overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
-
-// Plane `index` of one or more arrays of a call: no pointer that is `required` is null, and every pointer (a null one passes) is
-// aligned to mask + 1 bytes.  The refusals read "<what> <index>: <null_text>" and "<what> <index>: <align_text>".
-struct PlanePointer {
-    const void *p;
-    bool required = true;
-};
-int check_plane(const char *what, int index, std::initializer_list<PlanePointer> pointers, uintptr_t mask, const char *null_text, const char *align_text);
-
-// The aliasing rules of a single-image backward call: every plane that is written against every plane that is read, every other
-// plane that is written, and the gradient it is computed from -- which alone it may be, plane for plane and exactly, and only
-// written[0] (the image gradient: in place).  `noun` is how the messages name a plane of the array ("<noun> plane <index>"),
-// `why` what follows where a written plane overlaps one of a read array.  Null planes are passed over.
-struct PlaneList {
-    const char *noun;
-    const void *const *planes;
-    int n;
-    size_t bytes;            // of one plane
-    const char *why = "";
-};
-int check_written_planes(const PlaneList *written, int n_written, const PlaneList *read, int n_read, const PlaneList &grad_out);
 
 // The power form's constants: bases[k] inside (0, 1) for each of the n_weights planes, or a refusal; log2 and ln of each.
 int power_constants(const float *bases, int n_weights, float *log2_base, float *ln_base);

@@ -63,8 +63,9 @@ def _torch_dtype(code: int):
             capi.RF_F16: torch.float16, capi.RF_BF16: torch.bfloat16}[code]
 
 
-class Plan:
+class Plan(capi._PlanHandle):
     """One tiled (or untiled) recursive filter on one device: rf_plan_create .. rf_plan_destroy."""
+    _destroy = "rf_plan_destroy"
 
     def __init__(self, shape: Sequence[int], scans: Sequence[Scan], dtype=np.float32, clamped: bool = False,
                  planes: int = 1, tile: Optional[Sequence[int]] = None, path: int = capi.RF_PATH_AUTO,
@@ -149,24 +150,6 @@ class Plan:
         self.shard_world = int(shard_world)
         self._h = ctypes.c_void_p()
         capi.check(L.rf_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
-
-    # -- lifetime ---------------------------------------------------------------------------
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            capi.lib().rf_plan_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # -- queries ----------------------------------------------------------------------------
     @property
@@ -256,12 +239,6 @@ class Plan:
         tdt = torch.uint8 if self.output_np_dtype is not None else _torch_dtype(self.dtype_code)
         return [torch.empty(t.shape, dtype=tdt, device=t.device) for t in inputs]
 
-    @staticmethod
-    def _stream(stream) -> ctypes.c_void_p:
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return ctypes.c_void_p(s.cuda_stream)
-
     def execute(self, inputs, outputs=None, stream=None):
         """rf_plan_execute: asynchronous on `stream` (default: torch's current stream).  Executes on distinct streams may
         overlap: the plan runs them on replicas of itself with their own workspaces (include/recfilter_amd.h)."""
@@ -277,12 +254,8 @@ class Plan:
         import torch
         if outputs is None:
             outputs = self._new_outputs(inputs)
-        pin, pout = self._pointers(inputs, True), self._pointers(outputs)
-        n = self.num_kernels
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_plan_execute_timed(self._h, pin, pout, self._stream(stream), ms, names, n))
-        return outputs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        pin, pout, s = self._pointers(inputs, True), self._pointers(outputs), self._stream(stream)
+        return outputs, capi._timed(lambda *report: capi.lib().rf_plan_execute_timed(self._h, pin, pout, s, *report), self.num_kernels)
 
     # -- backward (rf_plan_backward) ------------------------------------------------------------
     def _backward_arguments(self, grad_outs, grad_ins, inputs, coeff_grads, stream):
@@ -316,10 +289,7 @@ class Plan:
         """rf_plan_backward_timed: (grad_ins, coeffs, [(launch name, ms), ...]) in execution order; synchronises the stream."""
         pin, pgo, pgi, pc, grad_ins, coeffs, s = self._backward_arguments(grad_outs, grad_ins, inputs, coeff_grads, stream)
         n = self.backward_num_kernels(coeff_grads)
-        ms = (ctypes.c_float * max(n, 1))()
-        names = (ctypes.c_char_p * max(n, 1))()
-        capi.check(capi.lib().rf_plan_backward_timed(self._h, pin, pgo, pgi, pc, s, ms, names, n))
-        return grad_ins, coeffs, [(names[i].decode(), float(ms[i])) for i in range(n)]
+        return grad_ins, coeffs, capi._timed(lambda *report: capi.lib().rf_plan_backward_timed(self._h, pin, pgo, pgi, pc, s, *report), n)
 
     def backward_num_kernels(self, coeff_grads: bool = False) -> int:
         """launches of one backward call (0 for a plan the backward refuses); the first query builds the child plans"""

@@ -24,6 +24,7 @@ import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import capi
+from .capi import _PlanHandle, _timed
 
 VarScan = Tuple[int, bool, int]      # (dim, causal, index of the weight plane); dim 0 = x
 
@@ -43,42 +44,6 @@ def _plane_pointer(t, shape, dtype, dtype_text: str, what: str) -> int:
     if not t.is_cuda or not t.is_contiguous():
         raise ValueError("planes must be contiguous device tensors")
     return t.data_ptr()
-
-
-def _timed(call, n: int):
-    """[(kernel name, ms), ...] of a *_timed entry point with `n` launches: call(ms, names, n) returns its status"""
-    ms = (ctypes.c_float * max(n, 1))()
-    names = (ctypes.c_char_p * max(n, 1))()
-    capi.check(call(ms, names, n))
-    return [(names[i].decode(), float(ms[i])) for i in range(n)]
-
-
-class _PlanHandle:
-    """the lifetime of the library's plan behind self._h; `_destroy` names the entry point that frees it"""
-    _destroy = ""
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            getattr(capi.lib(), self._destroy)(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @staticmethod
-    def _stream(stream) -> ctypes.c_void_p:
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return ctypes.c_void_p(s.cuda_stream)
 
 
 class VarPlan(_PlanHandle):

@@ -158,6 +158,50 @@ def test_refusals_in_order():
         assert "overlaps" in _refusal(plan, capi.RF_ERR_INVALID_ARG, pgi=both)
 
 
+@pytest.mark.parametrize("n", [1, 2], ids=["one_plane", "two_planes"])
+def test_aliasing_rule_names_both_planes(n):
+    """a written plane (grad_in, grad_coeffs) is disjoint from every other plane of the call, except that grad_in[p] may be
+    exactly grad_out[p]: every refusal names both arrays and both plane indices"""
+    shape = (64, 64)
+    plane_bytes, coeff_bytes = 64 * 64 * 4, len(GAUSS2_XY) * (1 + capi.RF_MAX_ORDER) * 8
+    gout, gin, inp = (lambda: _planes(n, shape, 0)), (lambda: _planes(n, shape, FAR)), (lambda: _planes(n, shape, 2 * FAR))
+    coeffs = BASE + 3 * FAR
+    last = n - 1
+
+    def moved(planes, index, address):
+        planes[index] = address
+        return planes
+
+    def refused(a, i, b, j, **call):
+        message = _refusal(plan, capi.RF_ERR_INVALID_ARG, shape=shape, **call)
+        one, other = f"{a} plane {i}", f"{b} plane {j}"
+        assert message.startswith(f"{one} overlaps {other}") or message.startswith(f"{other} overlaps {one}"), message
+
+    with _host_plan(shape=shape, planes=n) as plan:
+        # grad_in against grad_out: its own plane unless exactly, another plane even exactly
+        refused("grad_in", last, "grad_out", last, pgi=moved(gin(), last, gout()[last] + 64))
+        refused("grad_in", 0, "grad_out", 0, pgi=moved(gin(), 0, gout()[0] - plane_bytes + 16))
+        if n == 2:
+            refused("grad_in", 0, "grad_out", 1, pgi=moved(gin(), 0, gout()[1]))
+            refused("grad_in", 1, "grad_out", 0, pgi=moved(gin(), 1, gout()[0] - plane_bytes + 16))
+            # grad_in against grad_in
+            refused("grad_in", 0, "grad_in", 1, pgi=moved(gin(), 1, gin()[0]))
+            refused("grad_in", 0, "grad_in", 1, pgi=moved(gin(), 1, gin()[0] + 1024))
+        # grad_in against in (read only with the coefficients)
+        refused("grad_in", last, "in", 0, pin=inp(), coeffs=coeffs, pgi=moved(gin(), last, inp()[0] - 256))
+        refused("grad_in", 0, "in", last, pin=inp(), coeffs=coeffs, pgi=moved(gin(), 0, inp()[last]))
+        # grad_coeffs, n_scans rows of 1 + RF_MAX_ORDER doubles, against each of the three: its first and its last byte
+        for array, noun in ((gout(), "grad_out"), (gin(), "grad_in"), (inp(), "in")):
+            refused("grad_coeffs", 0, noun, last, pin=inp(), coeffs=array[last] + plane_bytes - 8)
+            refused("grad_coeffs", 0, noun, 0, pin=inp(), coeffs=array[0] - coeff_bytes + 8)
+            _refusal(plan, capi.RF_ERR_HIP, shape=shape, pin=inp(), coeffs=array[0] - coeff_bytes)
+            _refusal(plan, capi.RF_ERR_HIP, shape=shape, pin=inp(), coeffs=array[last] + plane_bytes)
+        # in place, plane for plane and exactly, is accepted as far as the host-only refusal
+        _refusal(plan, capi.RF_ERR_HIP, shape=shape, pgo=gout(), pgi=gout())
+        _refusal(plan, capi.RF_ERR_HIP, shape=shape, pgo=gout(), pgi=gout(), pin=inp(), coeffs=coeffs)
+        _refusal(plan, capi.RF_ERR_HIP, shape=shape, pgo=gout(), pgi=moved(gin(), last, gout()[last]))
+
+
 def test_refusals_of_the_description():
     shape = (64, 256)
     inp, coeffs = _planes(1, shape, 2 * FAR), BASE + 3 * FAR
