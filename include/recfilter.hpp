@@ -773,7 +773,12 @@ inline void tap_filter(const std::vector<const void *> &in_planes, void *out, co
  *      F.add_scan(+x, 0); F.add_scan(-x, 0); F.add_scan(+y, 1); F.add_scan(-y, 1);
  *      F.realize({in}, {wx, wy}, {out});    // device pointers; in == out is allowed
  *      F.gradient({in}, {wx, wy}, {grad_out}, {grad_in}, {grad_wx, grad_wy});      // the adjoint, weight gradients optional
- *  The plan is built on the first realize() and kept; it owns one workspace: order the realizations of one object. */
+ *  The plan is built on the first realize() and kept; it owns one workspace: order the realizations of one object.
+ *  A long 1-D signal (rf_var_plan_create_signal; a multiple of 4 samples, up to 2^30):
+ *      RecFilterDim x("x", length);
+ *      RecFilterVarying F(x);               // a "plane" is a dense f32 signal; scans are +x and -x
+ *      F.add_scan(+x, 0); F.add_scan(-x, 0);
+ *      F.realize({in}, {w}, {out});         // realize_power, gradient and gradient_power likewise */
 class RecFilterVarying {
     std::vector<RecFilterDim> dims;
     std::vector<rf_var_scan_desc> scans;
@@ -783,6 +788,8 @@ class RecFilterVarying {
     void drop() { if (plan) { rf_var_plan_destroy(plan); plan = nullptr; } }
 public:
     RecFilterVarying(RecFilterDim x, RecFilterDim y) : dims{std::move(x), std::move(y)} {}
+    /** one long 1-D signal of x.num_pixels() samples (rf_var_plan_create_signal) */
+    explicit RecFilterVarying(RecFilterDim x) : dims{std::move(x)} {}
     RecFilterVarying(const RecFilterVarying &) = delete;
     RecFilterVarying &operator=(const RecFilterVarying &) = delete;
     ~RecFilterVarying() { drop(); }
@@ -845,6 +852,20 @@ private:
         if ((int)weight_planes < n_weights) throw RecFilterError("realize: a scan indexes a weight plane that was not passed");
         if (!plan || plan_planes != (int)in.size()) {
             drop();
+            if (dims.size() == 1) {
+                rf_var_signal_desc sd{};
+                sd.abi = RF_ABI;
+                sd.length = dims[0].num_pixels();
+                sd.dtype = RF_F32;
+                sd.n_planes = (int)in.size();
+                sd.n_weights = std::max(n_weights, 1);
+                sd.n_scans = (int)scans.size();
+                sd.scans = scans.data();
+                sd.device = -1;
+                if (rf_var_plan_create_signal(&sd, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
+                plan_planes = (int)in.size();
+                return;
+            }
             rf_var_desc d{};
             d.ndim = 2;
             d.abi = RF_ABI;

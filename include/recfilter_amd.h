@@ -601,6 +601,40 @@ int    rf_var_plan_backward_power_timed(rf_var_plan *plan, const void *const *in
                                         int capacity);
 int    rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gradients);
 size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_weight_gradients);
+/* The varying scans on long 1-D SIGNALS.  rf_var_plan_create refuses ndim = 1, and a (1, N) image fills one lane of a wave; this
+ * entry point builds an ordinary rf_var_plan whose "plane" is a dense f32 signal of `length` samples: execute, execute_power,
+ * backward, backward_power, their timed forms, the four queries and destroy work on it as above.  The operator is the one above
+ * with N = length: w~[0] = w~[N] = 0 by selects, element 0 of a weight signal is never used (a NaN there reaches nothing), every
+ * scan has dim 0, and a +x scan directly followed by -x on one weight signal, where the two are the whole list, is one stage.
+ * in == out is allowed; a weight signal must not overlap an output; signals are 16-byte aligned.
+ * Tiling: a lane owns 64 consecutive samples, a wave a group of 64 such tiles (4096 samples).  A stage is three launches,
+ * "var_tails_1d" (tile tails, then a scan of them across the wave: every lane stores the affine map from the carries that enter
+ * its group to those that enter its tile, one lane the group's aggregate), "var_carry_1d" (the carry recurrences over groups, one
+ * workgroup per plane sweeping 1024 groups at a time) and "var_pass2_1d" (reruns the recurrences from the carries; weights of
+ * exactly 0 and 1 stay exact).  No kernel waits on another workgroup; results are reproducible bit for bit.
+ * rf_var_plan_num_kernels = 3 per stage; rf_var_plan_backward_num_kernels = 3 n_scans ("var_adj_tails_1d", "var_carry_1d",
+ * "var_adj_pass2_1d") or 7 n_scans (with the forward's three and "var_grad_x").  rf_var_plan_workspace_bytes is exact:
+ * 4 * n_planes * (5 * (tiles + groups) + 2 * groups) bytes, tiles = ceil(length / 64), groups = ceil(tiles / 64) -- below 1/8 of
+ * the signal planes from one full group (4096 samples) on.
+ * Refused before any HIP call, the message naming the field: length not a multiple of 4 or above 2^30, dtype != RF_F32
+ * (RF_ERR_UNSUPPORTED); abi != RF_ABI, nonzero flags, n_planes / n_weights / n_scans outside their ranges, null scans, a scan
+ * with dim != 0 or weights outside 0..n_weights-1, length below 1 (RF_ERR_INVALID_ARG).  A host-only plan answers the queries and
+ * refuses to run with RF_ERR_HIP.
+ * Out of scope: lengths that are not multiples of 4 (pad with zero samples and zero weights: a weight of 0 decouples exactly);
+ * batches of long signals with weights of their own (many short lines are the x scans of a 2-D plan); byte and 16-bit signals;
+ * rf_smooth_plan and rf_var_distances on signals (their extent limit of 2^21 stays); orders above 1; sharding. */
+typedef struct {
+    uint32_t abi;                     /* RF_ABI                                                  */
+    int64_t  length;                  /* samples per signal: a multiple of 4, 4 .. 2^30          */
+    int32_t  dtype;                   /* RF_F32                                                  */
+    int32_t  n_planes;                /* signals that share the weight signals, 1..RF_MAX_PLANES */
+    int32_t  n_weights;               /* 1..RF_VAR_MAX_SCANS                                     */
+    int32_t  n_scans;                 /* 1..RF_VAR_MAX_SCANS                                     */
+    const rf_var_scan_desc *scans;    /* dim must be 0                                           */
+    int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
+    uint32_t flags;                   /* 0                                                       */
+} rf_var_signal_desc;
+int    rf_var_plan_create_signal(const rf_var_signal_desc *desc, rf_var_plan **plan_out);
 /* The distance planes of the domain-transform filter from a guide image of n_guide dense planes of width x height:
  *     d_x[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r][c-1]|   (c >= 1;  d_x[r][0] = 1)
  *     d_y[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r-1][c]|   (r >= 1;  d_y[0][c] = 1)

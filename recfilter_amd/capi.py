@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = [
     "rf_smooth_plan_backward", "rf_smooth_plan_backward_timed", "rf_smooth_plan_backward_num_kernels",
     "rf_smooth_plan_backward_workspace_bytes", "rf_smooth_plan_create_batched",
     "rf_plan_backward", "rf_plan_backward_timed", "rf_plan_backward_num_kernels", "rf_plan_backward_workspace_bytes",
+    "rf_var_plan_create_signal",
 ]
 
 
@@ -111,6 +112,12 @@ class VarDesc(ctypes.Structure):
     _fields_ = [("ndim", ctypes.c_int32), ("abi", ctypes.c_uint32), ("extent", ctypes.c_int64 * RF_MAX_DIMS),
                 ("dtype", ctypes.c_int32), ("n_planes", ctypes.c_int32), ("n_weights", ctypes.c_int32),
                 ("n_scans", ctypes.c_int32), ("scans", ctypes.POINTER(VarScanDesc)),
+                ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class VarSignalDesc(ctypes.Structure):
+    _fields_ = [("abi", ctypes.c_uint32), ("length", ctypes.c_int64), ("dtype", ctypes.c_int32), ("n_planes", ctypes.c_int32),
+                ("n_weights", ctypes.c_int32), ("n_scans", ctypes.c_int32), ("scans", ctypes.POINTER(VarScanDesc)),
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
@@ -200,6 +207,7 @@ def lib() -> ctypes.CDLL:
     L.rf_tap_filter.argtypes = [vpp, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
                                 ctypes.POINTER(Tap), ctypes.c_int, vp]
     L.rf_var_plan_create.argtypes = [ctypes.POINTER(VarDesc), vpp]
+    L.rf_var_plan_create_signal.argtypes = [ctypes.POINTER(VarSignalDesc), vpp]
     L.rf_var_plan_destroy.argtypes = [vp]
     L.rf_var_plan_workspace_bytes.argtypes = [vp]
     L.rf_var_plan_workspace_bytes.restype = ctypes.c_size_t

@@ -554,6 +554,10 @@ int rf_var_plan_create(const rf_var_desc *desc, rf_var_plan **plan_out) {
     return fenced("rf_var_plan_create", [&] { return build_var_plan(desc, plan_out); });
 }
 
+int rf_var_plan_create_signal(const rf_var_signal_desc *desc, rf_var_plan **plan_out) {
+    return fenced("rf_var_plan_create_signal", [&] { return build_var_signal_plan(desc, plan_out); });
+}
+
 int rf_var_plan_destroy(rf_var_plan *plan) {
     return fenced("rf_var_plan_destroy", [&] {
         if (plan) {

@@ -100,6 +100,13 @@ struct VarDistGradArgs {
 int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_carry(const VarArgs &a, hipStream_t stream);
 int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream);
+// One long line (kernels_var_signal.hip; rf_var_plan_create_signal): width = the signal's length, height = lines = 1, tiles =
+// ceil(width / kVarTile); 64 tiles are a group.  tails: 5 * n_planes * (tiles + groups) floats, carry: 2 * n_planes * groups (the
+// layouts: kernels_var_signal.hip).  f32, batch 1; no byte planes.
+constexpr int kVarGroupTiles = 64;
+int launch_var_signal_tails(const VarArgs &a, hipStream_t stream);
+int launch_var_signal_carry(const VarArgs &a, hipStream_t stream);
+int launch_var_signal_pass2(const VarArgs &a, hipStream_t stream);
 int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream);
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream);
 int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream);

@@ -27,6 +27,10 @@
 //
 // run_var_distances_backward: the adjoint of run_var_distances, one launch; the two share their checks of counts, scale and extents.
 //
+// A signal plan (build_var_signal_plan, rf_var_plan_create_signal) is the plan of a 1 x length image whose stages run the three
+// kernels of kernels_var_signal.hip (launch_stage's `signal`): width = length, height = 1, every scan along dim 0, the workspace
+// sized for tiles plus groups of 64 tiles.  Runs, the backward and var_grad are the code above, unchanged.
+//
 // A plan may hold a batch (build_var_plan's third argument; plan_smooth.cpp only, the public entry points build 1): tails,
 // carries and the backward's planes are then `batch` images' worth, image after image, and the launchers above carry the batch
 // and the strides from image to image (VarIo, VarBackwardIo) to the kernels, whose grids take all images at once.
@@ -81,13 +85,45 @@ int validate(const rf_var_desc *d) {
 
 int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
 
-// the three launches of a stage along `dim`; prefix: "var_", or "var_adj_" for an adjoint stage
-void push_stage_names(std::vector<std::string> &names, const char *prefix, int dim) {
-    const char *axis = dim == 0 ? "x" : "y";
+// the three launches of a stage along `dim` (a signal plan: "1d"); prefix: "var_", or "var_adj_" for an adjoint stage
+void push_stage_names(std::vector<std::string> &names, const char *prefix, int dim, bool signal) {
+    const char *axis = signal ? "1d" : dim == 0 ? "x" : "y";
     names.push_back(std::string(prefix) + "tails_" + axis);
-    names.push_back("var_carry");
+    names.push_back(signal ? "var_carry_1d" : "var_carry");
     names.push_back(std::string(prefix) + "pass2_" + axis);
 }
+
+constexpr int64_t kVarMaxSignal = int64_t(1) << 30;      // samples of a signal: indices and 4096-sample groups stay inside int32
+
+int validate_signal(const rf_var_signal_desc *d) {
+    if (d->abi != RF_ABI) {
+        set_error("rf_var_signal_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->flags != 0) { set_error("rf_var_signal_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
+    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
+    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
+    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
+    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
+    if (d->dtype != RF_F32) { set_error("varying scans take f32 signals (dtype = %d)", d->dtype); return RF_ERR_UNSUPPORTED; }
+    for (int s = 0; s < d->n_scans; s++) {
+        const rf_var_scan_desc &sc = d->scans[s];
+        if (sc.dim != 0) { set_error("scan %d: dim must be 0 on a signal (got %d)", s, sc.dim); return RF_ERR_INVALID_ARG; }
+        if (sc.weights < 0 || sc.weights >= d->n_weights) {
+            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    if (d->length < 1) { set_error("length must be positive (got %lld)", (long long)d->length); return RF_ERR_INVALID_ARG; }
+    if (d->length > kVarMaxSignal) { set_error("length = %lld is above %lld", (long long)d->length, (long long)kVarMaxSignal); return RF_ERR_UNSUPPORTED; }
+    if (d->length % 4 != 0) {
+        set_error("varying scans move 16 bytes per lane: length must be a multiple of 4 (got %lld)", (long long)d->length);
+        return RF_ERR_UNSUPPORTED;
+    }
+    return RF_OK;
+}
+
+int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool signal);
 
 }  // namespace
 
@@ -98,6 +134,33 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     *out = nullptr;
     int rc = validate(desc);
     if (rc != RF_OK) return rc;
+    return build_checked(desc, out, batch, false);
+}
+
+int build_var_signal_plan(const rf_var_signal_desc *desc, rf_var_plan **out) {
+    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    *out = nullptr;
+    int rc = validate_signal(desc);
+    if (rc != RF_OK) return rc;
+    // the plan of a 1 x length image, whose stages run the signal kernels
+    rf_var_desc d{};
+    d.ndim = 2;
+    d.abi = desc->abi;
+    d.extent[0] = desc->length;
+    d.extent[1] = 1;
+    d.dtype = desc->dtype;
+    d.n_planes = desc->n_planes;
+    d.n_weights = desc->n_weights;
+    d.n_scans = desc->n_scans;
+    d.scans = desc->scans;
+    d.device = desc->device;
+    return build_checked(&d, out, 1, true);
+}
+
+namespace {
+
+// the plan of a description that has passed its checks
+int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool signal) {
     const bool host_only = desc->device == RF_DEVICE_HOST_ONLY;
     int device = desc->device;
     if (!host_only) {
@@ -114,6 +177,7 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     plan->batch = batch;
     plan->device = host_only ? 0 : device;
     plan->host_only = host_only;
+    plan->signal = signal;
     // Stages: the scans are taken in runs along one dimension.  A run that is exactly {+d, -d} on one weight plane is ONE fused
     // stage; every other run -- a single scan, -d +d, a pair on two weight planes, three or more scans along the dimension --
     // goes scan by scan (longer runs are not searched for pairs).
@@ -122,7 +186,7 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
         rf_var_stage st;
         st.dim = dim; st.mode = mode; st.weights = weights;
         used[dim] = true;
-        push_stage_names(plan->names, "var_", dim);
+        push_stage_names(plan->names, "var_", dim, signal);
         plan->stages.push_back(st);
     };
     for (int s = 0; s < desc->n_scans;) {
@@ -138,18 +202,24 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     }
     // the adjoint's launch lists: [1] reruns the forward scan by scan first, and has one var_grad behind every adjoint stage
     plan->scans.assign(desc->scans, desc->scans + desc->n_scans);
-    for (const rf_var_scan_desc &sc : plan->scans) push_stage_names(plan->backward_names[1], "var_", sc.dim);
+    for (const rf_var_scan_desc &sc : plan->scans) push_stage_names(plan->backward_names[1], "var_", sc.dim, signal);
     for (int with = 0; with < 2; with++)
         for (int q = desc->n_scans - 1; q >= 0; q--) {
-            push_stage_names(plan->backward_names[with], "var_adj_", desc->scans[q].dim);
+            push_stage_names(plan->backward_names[with], "var_adj_", desc->scans[q].dim, signal);
             if (with) plan->backward_names[with].push_back(desc->scans[q].dim == 0 ? "var_grad_x" : "var_grad_y");
         }
     // tiles x lines of the dimension that needs more: x scans have `height` lines, y scans `width`
     int64_t slots = 0;
     if (used[0]) slots = std::max(slots, tiles_of(plan->width) * plan->height);
     if (used[1]) slots = std::max(slots, tiles_of(plan->height) * plan->width);
+    int64_t carry_slots = slots;
+    if (signal) {
+        // a lane's map per tile and an aggregate per group of 64 tiles; carries per group
+        carry_slots = (tiles_of(plan->width) + kVarGroupTiles - 1) / kVarGroupTiles;
+        slots = tiles_of(plan->width) + carry_slots;
+    }
     plan->tails_bytes = (size_t)(slots * kVarComponents * plan->n_planes) * sizeof(float) * (size_t)batch;
-    plan->carry_bytes = (size_t)(slots * 2 * plan->n_planes) * sizeof(float) * (size_t)batch;
+    plan->carry_bytes = (size_t)(carry_slots * 2 * plan->n_planes) * sizeof(float) * (size_t)batch;
     if (!host_only) {
         RF_HIP_CHECK(hipSetDevice(device));
         if (hipMalloc((void **)&plan->tails, plan->tails_bytes) != hipSuccess || hipMalloc((void **)&plan->carry, plan->carry_bytes) != hipSuccess) {
@@ -161,6 +231,8 @@ int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
     *out = plan.release();
     return RF_OK;
 }
+
+}  // namespace
 
 int power_constants(const float *bases, int n_weights, float *log2_base, float *ln_base) {
     for (int k = 0; k < n_weights; k++) {
@@ -196,15 +268,16 @@ VarArgs scan_args(const rf_var_plan *plan, int dim, const void *weights, int mod
 }
 
 // The three launches of a stage, a mark behind each.  a.dst_u8 is held back until the final pass: the tails pass stores no sample.
-int launch_stage(VarArgs &a, int dim, hipStream_t stream, LaunchTimer &timer) {
+// signal: the plan of one long line (rf_var_plan_create_signal), whose three launches are kernels_var_signal.hip's.
+int launch_stage(VarArgs &a, int dim, bool signal, hipStream_t stream, LaunchTimer &timer) {
     const int32_t dst_u8 = a.dst_u8;
     a.dst_u8 = 0;
-    int rc = launch_var_tails(a, dim, stream);
+    int rc = signal ? launch_var_signal_tails(a, stream) : launch_var_tails(a, dim, stream);
     if (rc == RF_OK) rc = timer.mark();
-    if (rc == RF_OK) rc = launch_var_carry(a, stream);
+    if (rc == RF_OK) rc = signal ? launch_var_signal_carry(a, stream) : launch_var_carry(a, stream);
     if (rc == RF_OK) rc = timer.mark();
     a.dst_u8 = dst_u8;
-    if (rc == RF_OK) rc = launch_var_pass2(a, dim, stream);
+    if (rc == RF_OK) rc = signal ? launch_var_signal_pass2(a, stream) : launch_var_pass2(a, dim, stream);
     if (rc == RF_OK) rc = timer.mark();
     return rc;
 }
@@ -259,7 +332,7 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
         a.weights_stride = io.weights_stride;
         a.power = log2_base ? 1 : 0;
         a.log2_base = log2_base ? log2_base[st.weights] : 0.0f;
-        int rc = launch_stage(a, st.dim, stream, timer);
+        int rc = launch_stage(a, st.dim, plan->signal, stream, timer);
         if (rc != RF_OK) return rc;
     }
     return RF_OK;
@@ -354,7 +427,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
             }
             a.src_stride = q == 0 ? io.in_stride : saved_stride;
             a.dst_stride = saved_stride;
-            rc = launch_stage(a, sc.dim, stream, timer);
+            rc = launch_stage(a, sc.dim, plan->signal, stream, timer);
         }
     }
     bool touched[RF_VAR_MAX_SCANS] = {};
@@ -374,7 +447,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
         a.src_stride = q == S - 1 ? io.grad_out_stride : io.grad_in_stride;
         a.dst_stride = io.grad_in_stride;
         a.lam_stride = saved_stride;
-        rc = launch_stage(a, sc.dim, stream, timer);
+        rc = launch_stage(a, sc.dim, plan->signal, stream, timer);
         if (rc != RF_OK || !with_weights) continue;
         if (grad) {                                   // (a weight plane without a gradient: no launch, its slot reports 0 ms)
             VarGradArgs g{};

@@ -23,6 +23,9 @@ struct rf_var_plan {
     int batch = 1;
     int device = 0;
     bool host_only = false;
+    // one long 1-D signal (rf_var_plan_create_signal): width = its length, height = 1, every scan along dim 0; the stages run the
+    // kernels of kernels_var_signal.hip and the workspace is sized for tiles plus groups of 64 tiles
+    bool signal = false;
     std::vector<rf_var_stage> stages;
     std::vector<std::string> names;          // three per stage: what rf_var_plan_execute_timed reports
     // the one workspace: every stage's tails and carries (sized for the larger dimension); written before it is read
@@ -46,6 +49,8 @@ struct rf_var_plan {
 
 namespace rf {
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch = 1);
+// rf_var_plan_create_signal: an ordinary plan whose planes are dense f32 signals of desc->length samples
+int build_var_signal_plan(const rf_var_signal_desc *desc, rf_var_plan **out);
 
 // The power form's constants: bases[k] inside (0, 1) for each of the n_weights planes, or a refusal; log2 and ln of each.
 int power_constants(const float *bases, int n_weights, float *log2_base, float *ln_base);

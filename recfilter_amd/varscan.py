@@ -79,6 +79,35 @@ class VarPlan(_PlanHandle):
         self._h = ctypes.c_void_p()
         capi.check(L.rf_var_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
 
+    @classmethod
+    def signal(cls, length: int, scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1) -> "VarPlan":
+        """rf_var_plan_create_signal: the plan of long 1-D signals -- `planes` dense f32 signals of `length` samples (a multiple
+        of 4, up to 2**30) that share `n_weights` weight signals; every scan has dim 0.  `shape` is (length,), and every method
+        works as on an image plan, a plane being a 1-D tensor.  A lane owns 64 samples, a wave 4096; the launches are
+        var_tails_1d, var_carry_1d, var_pass2_1d per stage."""
+        L = capi.lib()
+        self = cls.__new__(cls)
+        scans = list(scans)
+        self._scan_arr = (capi.VarScanDesc * max(len(scans), 1))()
+        for i, (dim, causal, weights) in enumerate(scans):
+            s = self._scan_arr[i]
+            s.dim, s.causal, s.weights = int(dim), int(bool(causal)), int(weights)
+        d = capi.VarSignalDesc()
+        d.abi = capi.RF_ABI
+        d.length = int(length)
+        d.dtype = capi.RF_F32
+        d.n_planes, d.n_weights = int(planes), int(n_weights)
+        d.n_scans = len(scans)
+        d.scans = ctypes.cast(self._scan_arr, ctypes.POINTER(capi.VarScanDesc))
+        d.device = int(device)
+        d.flags = 0
+        self._desc = d
+        self.shape, self.planes, self.n_weights = (int(length),), int(planes), int(n_weights)
+        self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
+        self._h = ctypes.c_void_p()
+        capi.check(L.rf_var_plan_create_signal(ctypes.byref(d), ctypes.byref(self._h)))
+        return self
+
     # -- queries ----------------------------------------------------------------------------
     @property
     def workspace_bytes(self) -> int:
@@ -288,6 +317,68 @@ def var_scan(ins, weights, scans):
     if plan is None:
         plan = _scan_plans[key] = VarPlan(key[0], key[1], planes=len(ins), n_weights=len(weights), device=device)
     return plan.apply(ins, weights)
+
+
+_signal_plans: Dict[tuple, VarPlan] = {}
+
+
+def _signal_plan(length: int, scans, planes: int, n_weights: int, device) -> VarPlan:
+    key = (int(length), tuple((int(d), bool(c), int(k)) for d, c, k in scans), int(planes), int(n_weights), device)
+    plan = _signal_plans.get(key)
+    if plan is None:
+        plan = _signal_plans[key] = VarPlan.signal(key[0], key[1], planes=planes, n_weights=n_weights, device=device)
+    return plan
+
+
+def _padded(t, pad: int, value: float):
+    """`pad` more elements of `value` behind a 1-D tensor (differentiable: the gradient is the slice)"""
+    import torch
+    return t if pad == 0 else torch.nn.functional.pad(t, (0, pad), value=value)
+
+
+def var_scan_signal(ins, weights, scans):
+    """`scans` [(0, causal, weight index), ...] on the 1-D device signals `ins` (f32, one length N) with the weight signals
+    `weights`, through a cached `VarPlan.signal`; differentiable with respect to both, like `var_scan`.  Element 0 of a weight
+    signal is never used.  The library takes lengths that are multiples of 4: any other length is padded up to the next one --
+    the inputs with 0 and the weights with 0, and a weight of 0 decouples exactly, so the N real samples are what an unpadded
+    scan gives -- and the result is sliced back.  The padding costs one copy of every signal (none where N % 4 == 0).  Calls that
+    share a plan are ordered by the caller (one stream).  Returns a tuple of len(ins) signals."""
+    import torch
+    ins, weights = list(ins), list(weights)
+    n = int(ins[0].shape[0])
+    if any(t.dim() != 1 or int(t.shape[0]) != n for t in ins + weights):
+        raise ValueError("var_scan_signal takes 1-D signals of one length")
+    pad = -n % 4
+    device = ins[0].device.index if ins[0].device.index is not None else torch.cuda.current_device()
+    plan = _signal_plan(n + pad, scans, len(ins), len(weights), device)
+    with torch.cuda.device(ins[0].device):
+        outs = plan.apply([_padded(t, pad, 0.0) for t in ins], [_padded(w, pad, 0.0) for w in weights])
+    return tuple(o[:n] for o in outs) if pad else tuple(outs)
+
+
+def smooth_samples(x, gaps, time_constant: float, zero_phase: bool = True):
+    """The exponential moving average of an irregularly sampled series: x (N,) or (C, N), f32 on the device, sampled at times t
+    with gaps[i] = t[i] - t[i-1] >= 0 (gaps[0] is unused):
+        y[i] = (1 - w[i]) x[i] + w[i] y[i-1],   w[i] = exp(-gaps[i] / time_constant)
+    and, with zero_phase, the same recurrence backwards over the result (+x -x, one fused stage).  It runs through the power form
+    of a cached `VarPlan.signal`: the weights are formed in the kernels as base ** gaps with base = exp(-1 / time_constant), and no
+    weight signal is stored.  Differentiable with respect to x and gaps.  A time constant whose base rounds to 0 or 1 in f32 is
+    refused by the library (RecFilterError).  Lengths that are not multiples of 4 are padded as in `var_scan_signal` (the gaps with
+    +inf: a weight of exactly 0), at the cost of one copy."""
+    import torch
+    if x.dim() not in (1, 2) or gaps.dim() != 1 or int(gaps.shape[0]) != int(x.shape[-1]):
+        raise ValueError(f"x must be (N,) or (C, N) and gaps (N,), got {tuple(x.shape)} and {tuple(gaps.shape)}")
+    signals = [x] if x.dim() == 1 else [x[c] for c in range(x.shape[0])]
+    n = int(gaps.shape[0])
+    pad = -n % 4
+    base = math.exp(-1.0 / float(time_constant))
+    scans = [(0, True, 0), (0, False, 0)] if zero_phase else [(0, True, 0)]
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    plan = _signal_plan(n + pad, scans, len(signals), 1, device)
+    with torch.cuda.device(x.device):
+        outs = plan.apply_power([_padded(t.to(torch.float32), pad, 0.0) for t in signals], [_padded(gaps.to(torch.float32), pad, math.inf)], [base])
+    outs = [o[:n] for o in outs] if pad else list(outs)
+    return outs[0] if x.dim() == 1 else torch.stack(outs)
 
 
 # ---- the domain-transform recursive filter ----------------------------------------------------------------------------------
