@@ -790,6 +790,9 @@ public:
     RecFilterVarying(RecFilterDim x, RecFilterDim y) : dims{std::move(x), std::move(y)} {}
     /** one long 1-D signal of x.num_pixels() samples (rf_var_plan_create_signal) */
     explicit RecFilterVarying(RecFilterDim x) : dims{std::move(x)} {}
+    /** volumes [z][y][x] of x.num_pixels() x y.num_pixels() x z.num_pixels() samples (rf_var_plan_create_volume): a "plane" of
+     *  realize() and gradient() is a dense f32 volume, a weight plane a volume of the same size, and scans run along x, y or z */
+    RecFilterVarying(RecFilterDim x, RecFilterDim y, RecFilterDim z) : dims{std::move(x), std::move(y), std::move(z)} {}
     RecFilterVarying(const RecFilterVarying &) = delete;
     RecFilterVarying &operator=(const RecFilterVarying &) = delete;
     ~RecFilterVarying() { drop(); }
@@ -866,6 +869,22 @@ private:
                 plan_planes = (int)in.size();
                 return;
             }
+            if (dims.size() == 3) {
+                rf_var_volume_desc vd{};
+                vd.abi = RF_ABI;
+                vd.width = dims[0].num_pixels();
+                vd.height = dims[1].num_pixels();
+                vd.depth = dims[2].num_pixels();
+                vd.dtype = RF_F32;
+                vd.n_planes = (int)in.size();
+                vd.n_weights = std::max(n_weights, 1);
+                vd.n_scans = (int)scans.size();
+                vd.scans = scans.data();
+                vd.device = -1;
+                if (rf_var_plan_create_volume(&vd, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
+                plan_planes = (int)in.size();
+                return;
+            }
             rf_var_desc d{};
             d.ndim = 2;
             d.abi = RF_ABI;
@@ -893,6 +912,15 @@ inline void domain_transform_distances(const std::vector<const void *> &guide_pl
                          stream) != RF_OK) throw RecFilterError(rf_last_error_string());
 }
 
+/** The exponent volumes of the filter on volumes [z][y][x] (rf_var_distances_volume): d_x and d_y slice by slice as
+ *  domain_transform_distances forms them, d_z = spacing_z + scale * sum over the guide volumes of |g - g one slice before| (slice
+ *  0: spacing_z).  spacing_z > 0 is the sample distance along z in units of the x/y pitch.  One launch on `stream`. */
+inline void domain_transform_distances_volume(const std::vector<const void *> &guide_volumes, bool guide_u8, int64_t width, int64_t height,
+                                              int64_t depth, float scale, float spacing_z, void *dx, void *dy, void *dz, void *stream = nullptr) {
+    if (rf_var_distances_volume(guide_volumes.data(), (int32_t)guide_volumes.size(), guide_u8 ? 1 : 0, width, height, depth, scale, spacing_z,
+                                dx, dy, dz, -1, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+}
+
 /** The adjoint of domain_transform_distances for f32 guide planes (rf_var_distances_backward): the guide's gradient from those of
  *  d_x and d_y, stored to grad_guide_planes or (accumulate) added to what they hold.  One launch on `stream`. */
 inline void domain_transform_distances_gradient(const std::vector<const void *> &guide_planes, int64_t width, int64_t height, float scale,
@@ -916,12 +944,45 @@ class RecFilterSmooth {
     rf_smooth_plan *plan = nullptr;
     rf_smooth_batch_desc batch_desc{};
     bool batched = false;
+    int64_t depth = 0;             // > 0: a volume (rf_smooth_plan_create_volume)
+    double spacing_z = 1.0;
     void prepare() {
         if (plan) return;
-        const int rc = batched ? rf_smooth_plan_create_batched(&desc, &batch_desc, &plan) : rf_smooth_plan_create(&desc, &plan);
+        int rc;
+        if (depth > 0) {
+            if (batched) throw RecFilterError("a volume filter takes no batch");
+            rf_smooth_volume_desc vd{};
+            vd.abi = desc.abi;
+            vd.image_u8 = desc.image_u8;
+            vd.width = desc.width;
+            vd.height = desc.height;
+            vd.depth = depth;
+            vd.n_planes = desc.n_planes;
+            vd.n_guide = desc.n_guide;
+            vd.guide_u8 = desc.guide_u8;
+            vd.iterations = desc.iterations;
+            vd.sigma_s = desc.sigma_s;
+            vd.sigma_r = desc.sigma_r;
+            vd.spacing_z = spacing_z;
+            vd.device = desc.device;
+            vd.flags = desc.flags;
+            rc = rf_smooth_plan_create_volume(&vd, &plan);
+        } else {
+            rc = batched ? rf_smooth_plan_create_batched(&desc, &batch_desc, &plan) : rf_smooth_plan_create(&desc, &plan);
+        }
         if (rc != RF_OK) throw RecFilterError(rf_last_error_string());
     }
 public:
+    /** The filter along x, y and z of volumes [z][y][x] (rf_smooth_plan_create_volume): a "plane" of realize() is a dense volume,
+     *  f32 or uint8; spacing_z > 0 is the sample distance along z in units of the x/y pitch.  1 + 9 K launches; gradient() is
+     *  refused by the library; no batch. */
+    RecFilterSmooth(int64_t width, int64_t height, int64_t depth_, int planes, int guide_planes, bool guide_u8, bool image_u8, int iterations,
+                    double sigma_s, double sigma_r, double spacing_z_)
+        : RecFilterSmooth(width, height, planes, guide_planes, guide_u8, image_u8, iterations, sigma_s, sigma_r) {
+        if (depth_ < 1) throw RecFilterError("RecFilterSmooth: the depth of a volume must be positive");
+        depth = depth_;
+        spacing_z = spacing_z_;
+    }
     RecFilterSmooth(int64_t width, int64_t height, int planes, int guide_planes, bool guide_u8, bool image_u8, int iterations,
                     double sigma_s, double sigma_r) {
         desc.abi = RF_ABI;

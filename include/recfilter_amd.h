@@ -635,6 +635,51 @@ typedef struct {
     uint32_t flags;                   /* 0                                                       */
 } rf_var_signal_desc;
 int    rf_var_plan_create_signal(const rf_var_signal_desc *desc, rf_var_plan **plan_out);
+/* The varying scans on VOLUMES.  rf_var_plan_create refuses ndim = 3; this entry point builds an ordinary rf_var_plan whose
+ * "plane" is a dense f32 volume [z][y][x] of width x height x depth samples, 16-byte aligned: execute, execute_power, backward,
+ * backward_power, their timed forms, the four queries and destroy work on it as above.  A weight plane is a volume of the same
+ * size; dim is 0 (x), 1 (y) or 2 (z).  The operator is the one above along the chosen axis: w~[0] = w~[N] = 0 by selects, and
+ * element 0 along the scanned axis -- column 0, row 0 or slice 0 -- is never used (a NaN there reaches nothing).  Stages form as
+ * above: a run {+d, -d} on one weight volume, alone along d, is one pair stage; every other run goes scan by scan.
+ * The arithmetic of a line does not depend on its container.  An x or y stage takes the `depth` slices as a batch on gridDim.z
+ * beside the planes (slice strides of width * height samples; tails and carries slice after slice in the single-image layout):
+ * every slice is, bit for bit, what the 2-D plan of width x height gives on it.  A z stage runs the y kernels on the
+ * (width * height) x depth view, one voxel column per lane, rows width * height samples apart: bit for bit the y scans of a 2-D
+ * plan on that image.  Three launches per stage whatever the depth: "var_tails_x|y|z", "var_carry", "var_pass2_x|y|z"; the
+ * backward adds "var_adj_tails_z", "var_adj_pass2_z" and "var_grad_z" to the names above.
+ * rf_var_plan_workspace_bytes is exact: 4 * n_planes * (5 + 2) * slots bytes, slots = max over the dimensions d the plan scans of
+ * ceil(n_d / 64) * (width * height * depth / n_d).  rf_var_plan_backward_workspace_bytes(plan, 1) is (n_scans + 1) * n_planes
+ * volumes.
+ * Refused before any HIP call, the message naming the limit: a width that is not a multiple of 4; an extent above 2^21;
+ * width * height above 2^30 (a z scan indexes its lines in 32 bits); depth * n_planes above 65535 (the slices ride on gridDim.z);
+ * dtype != RF_F32 (RF_ERR_UNSUPPORTED); abi != RF_ABI, nonzero flags, n_planes / n_weights / n_scans outside their ranges, null
+ * scans, a scan with dim outside 0..2 or weights outside 0..n_weights-1, an extent below 1 (RF_ERR_INVALID_ARG).  A host-only
+ * plan answers the queries and refuses to run with RF_ERR_HIP.
+ * Out of scope: batches of volumes; byte and 16-bit volumes here (rf_smooth_plan_create_volume takes bytes); widths that are not
+ * multiples of 4; orders above 1; sharding. */
+typedef struct {
+    uint32_t abi;                     /* RF_ABI                                                  */
+    int64_t  width, height, depth;    /* x fastest; each 1 .. 2^21, width a multiple of 4        */
+    int32_t  dtype;                   /* RF_F32                                                  */
+    int32_t  n_planes;                /* volumes that share the weight volumes, 1..RF_MAX_PLANES */
+    int32_t  n_weights;               /* 1..RF_VAR_MAX_SCANS                                     */
+    int32_t  n_scans;                 /* 1..RF_VAR_MAX_SCANS                                     */
+    const rf_var_scan_desc *scans;    /* dim 0, 1 or 2                                           */
+    int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
+    uint32_t flags;                   /* 0                                                       */
+} rf_var_volume_desc;
+int    rf_var_plan_create_volume(const rf_var_volume_desc *desc, rf_var_plan **plan_out);
+/* The three exponent volumes of the domain-transform filter from n_guide guide volumes [z][y][x], f32 or uint8, in one launch
+ * ("var_distances_volume") that reads the guide once (a lane walks z with the slice before in registers):
+ *     d_x, d_y      slice by slice what rf_var_distances gives on that slice, bit for bit
+ *     d_z[z][r][c] = spacing_z + scale * sum_ch |g_ch[z][r][c] - g_ch[z-1][r][c]|   (z >= 1;  slice 0 holds spacing_z)
+ * spacing_z, finite and > 0, is the sample distance along z in units of the x/y pitch (slice thickness; how far apart two frames
+ * count); 1 = isotropic.  Refusals as rf_var_distances, with the volume domain of rf_var_plan_create_volume (n_planes = 1) in the
+ * place of the 2-D extent check, a spacing_z that is not finite and positive (RF_ERR_INVALID_ARG, behind the scale check), and dz
+ * in every alignment and overlap check.  There is no adjoint of this launch. */
+int    rf_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height,
+                               int64_t depth, float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device,
+                               void *stream);
 /* The distance planes of the domain-transform filter from a guide image of n_guide dense planes of width x height:
  *     d_x[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r][c-1]|   (c >= 1;  d_x[r][0] = 1)
  *     d_y[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r-1][c]|   (r >= 1;  d_y[0][c] = 1)
@@ -780,6 +825,33 @@ typedef struct {
     int64_t guide_stride;   /* the same for guide_planes and grad_guide_planes; must be 0 when n_guide == 0             */
 } rf_smooth_batch_desc;
 int    rf_smooth_plan_create_batched(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **plan_out);
+
+/* A volume: the filter along x, y and z of n_planes dense volumes [z][y][x], f32 or uint8.  The result is an ordinary
+ * rf_smooth_plan that owns THREE distance volumes: execute, execute_timed, bases, the queries and destroy take it with their
+ * signatures above, a "plane" being a volume.  One "var_distances_volume" launch (rf_var_distances_volume with the plan's scale
+ * and spacing_z), then for k = 0 .. K-1 the pair stages +x -x, +y -y, +z -z of the power form on d_x, d_y, d_z with the bases
+ * {a_k, a_k, a_k}: 1 + 9 K launches, a_k as above.  f32 volumes: bit for bit rf_var_distances_volume followed by K calls of
+ * rf_var_plan_execute_power on the volume plan.  uint8 volumes: the storage contract above -- the first x stage reads the
+ * caller's bytes, the iterations run on n_planes plan-owned f32 volumes, the last z pass stores sat8; no conversion launch.
+ * spacing_z: the sample distance along z in units of the x/y pitch, finite and > 0 (1 = isotropic).
+ * Create refuses what rf_smooth_plan_create refuses, with the domain of rf_var_plan_create_volume in the place of the 2-D extent
+ * checks and a spacing_z that is not finite and positive (RF_ERR_INVALID_ARG).  rf_smooth_plan_backward and _backward_timed on a
+ * volume plan return RF_ERR_UNSUPPORTED (the distances of a volume have no adjoint); rf_smooth_plan_backward_num_kernels and
+ * _backward_workspace_bytes return 0.  There is no batch of volumes. */
+typedef struct {
+    uint32_t abi;                     /* RF_ABI                                                  */
+    int32_t  image_u8;                /* 0: f32 volumes; 1: uint8 volumes, in AND out            */
+    int64_t  width, height, depth;
+    int32_t  n_planes;                /* 1..RF_MAX_PLANES volumes sharing the edges              */
+    int32_t  n_guide;                 /* 0: the volume guides itself; else 1..RF_MAX_PLANES      */
+    int32_t  guide_u8;                /* type of the separate guide volumes; 0 when n_guide == 0 */
+    int32_t  iterations;              /* K, 1..RF_SMOOTH_MAX_ITERATIONS                          */
+    double   sigma_s, sigma_r;        /* finite, > 0                                             */
+    double   spacing_z;               /* finite, > 0; 1 = isotropic                              */
+    int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
+    uint32_t flags;                   /* 0                                                       */
+} rf_smooth_volume_desc;
+int    rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth_plan **plan_out);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = [
     "rf_smooth_plan_backward_workspace_bytes", "rf_smooth_plan_create_batched",
     "rf_plan_backward", "rf_plan_backward_timed", "rf_plan_backward_num_kernels", "rf_plan_backward_workspace_bytes",
     "rf_var_plan_create_signal",
+    "rf_var_plan_create_volume", "rf_var_distances_volume", "rf_smooth_plan_create_volume",
 ]
 
 
@@ -121,11 +122,24 @@ class VarSignalDesc(ctypes.Structure):
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
+class VarVolumeDesc(ctypes.Structure):
+    _fields_ = [("abi", ctypes.c_uint32), ("width", ctypes.c_int64), ("height", ctypes.c_int64), ("depth", ctypes.c_int64),
+                ("dtype", ctypes.c_int32), ("n_planes", ctypes.c_int32), ("n_weights", ctypes.c_int32), ("n_scans", ctypes.c_int32),
+                ("scans", ctypes.POINTER(VarScanDesc)), ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
 class SmoothDesc(ctypes.Structure):
     _fields_ = [("abi", ctypes.c_uint32), ("image_u8", ctypes.c_int32), ("width", ctypes.c_int64), ("height", ctypes.c_int64),
                 ("n_planes", ctypes.c_int32), ("n_guide", ctypes.c_int32), ("guide_u8", ctypes.c_int32),
                 ("iterations", ctypes.c_int32), ("sigma_s", ctypes.c_double), ("sigma_r", ctypes.c_double),
                 ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class SmoothVolumeDesc(ctypes.Structure):
+    _fields_ = [("abi", ctypes.c_uint32), ("image_u8", ctypes.c_int32), ("width", ctypes.c_int64), ("height", ctypes.c_int64),
+                ("depth", ctypes.c_int64), ("n_planes", ctypes.c_int32), ("n_guide", ctypes.c_int32), ("guide_u8", ctypes.c_int32),
+                ("iterations", ctypes.c_int32), ("sigma_s", ctypes.c_double), ("sigma_r", ctypes.c_double),
+                ("spacing_z", ctypes.c_double), ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class SmoothBatchDesc(ctypes.Structure):
@@ -208,6 +222,10 @@ def lib() -> ctypes.CDLL:
                                 ctypes.POINTER(Tap), ctypes.c_int, vp]
     L.rf_var_plan_create.argtypes = [ctypes.POINTER(VarDesc), vpp]
     L.rf_var_plan_create_signal.argtypes = [ctypes.POINTER(VarSignalDesc), vpp]
+    L.rf_var_plan_create_volume.argtypes = [ctypes.POINTER(VarVolumeDesc), vpp]
+    L.rf_var_distances_volume.argtypes = [vpp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_float, ctypes.c_float, vp, vp, vp, ctypes.c_int32, vp]
+    L.rf_smooth_plan_create_volume.argtypes = [ctypes.POINTER(SmoothVolumeDesc), vpp]
     L.rf_var_plan_destroy.argtypes = [vp]
     L.rf_var_plan_workspace_bytes.argtypes = [vp]
     L.rf_var_plan_workspace_bytes.restype = ctypes.c_size_t

@@ -558,6 +558,10 @@ int rf_var_plan_create_signal(const rf_var_signal_desc *desc, rf_var_plan **plan
     return fenced("rf_var_plan_create_signal", [&] { return build_var_signal_plan(desc, plan_out); });
 }
 
+int rf_var_plan_create_volume(const rf_var_volume_desc *desc, rf_var_plan **plan_out) {
+    return fenced("rf_var_plan_create_volume", [&] { return build_var_volume_plan(desc, plan_out); });
+}
+
 int rf_var_plan_destroy(rf_var_plan *plan) {
     return fenced("rf_var_plan_destroy", [&] {
         if (plan) {
@@ -664,6 +668,14 @@ int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t g
     });
 }
 
+int rf_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
+                            float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, void *stream) {
+    return fenced("rf_var_distances_volume", [&] {
+        return run_var_distances_volume(guide_volumes, n_guide, guide_u8, width, height, depth, scale, spacing_z, dx, dy, dz, device,
+                                        (hipStream_t)stream);
+    });
+}
+
 int rf_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
                               const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, void *stream) {
     return fenced("rf_var_distances_backward", [&] {
@@ -683,6 +695,10 @@ int rf_smooth_plan_create_batched(const rf_smooth_desc *desc, const rf_smooth_ba
         if (!batch) { set_error("null batch description (rf_smooth_plan_create takes one image)"); return (int)RF_ERR_INVALID_ARG; }
         return build_smooth_plan(desc, batch, plan_out);
     });
+}
+
+int rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth_plan **plan_out) {
+    return fenced("rf_smooth_plan_create_volume", [&] { return build_smooth_volume_plan(desc, plan_out); });
 }
 
 int rf_smooth_plan_destroy(rf_smooth_plan *plan) {
@@ -732,6 +748,7 @@ int rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *image
     return fenced("rf_smooth_plan_backward_timed", [&] {
         if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
         if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return (int)RF_ERR_INVALID_ARG; }
+        if (plan->volume) return refuse_volume_backward();
         const std::vector<std::string> &names = plan->backward_names[edges];
         if (int rc = timed_names(names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, ms_out);

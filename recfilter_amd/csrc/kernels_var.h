@@ -80,6 +80,18 @@ struct VarDistArgs {
     int64_t guide_stride;
 };
 
+// The three exponent volumes of a guide volume [z][y][x] (kernels_var.hip, var_distances_volume): d_x and d_y slice by slice as
+// var_distances forms them, d_z = spacing_z + scale * sum_ch |g - g one slice before| (slice 0: spacing_z).  One launch: a lane owns
+// four adjacent columns of one row and walks kVarDistSlices slices with the slice before in registers.
+constexpr int kVarDistSlices = 16;
+struct VarDistVolumeArgs {
+    const void *guide[RF_MAX_PLANES];
+    float *dx, *dy, *dz;
+    int32_t width, height, depth;   // x fastest; the width is a multiple of 4
+    int32_t n_guide;
+    float scale, spacing_z;
+};
+
 // The adjoint of var_distances (kernels_var.hip, var_distances_grad), f32 guides:
 //   grad_guide[ch][r][c] = scale * (sx(r,c) gdx[r][c] - sx(r,c+1) gdx[r][c+1] + sy(r,c) gdy[r][c] - sy(r+1,c) gdy[r+1][c])
 // sx / sy: the sign of the guide's difference to the left / above (0 for a difference of 0 and outside the plane).  accumulate:
@@ -97,6 +109,8 @@ struct VarDistGradArgs {
     int64_t guide_stride, grad_guide_stride;
 };
 
+// dim 2 (a z stage of a volume plan, plan_var.cpp): the y kernels on the view the arguments describe -- width = lines = the voxel
+// columns, height = the depth -- under the names "var_*_z"
 int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
 int launch_var_carry(const VarArgs &a, hipStream_t stream);
 int launch_var_pass2(const VarArgs &a, int dim, hipStream_t stream);
@@ -108,6 +122,7 @@ int launch_var_signal_tails(const VarArgs &a, hipStream_t stream);
 int launch_var_signal_carry(const VarArgs &a, hipStream_t stream);
 int launch_var_signal_pass2(const VarArgs &a, hipStream_t stream);
 int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream);
+int launch_var_distances_volume(const VarDistVolumeArgs &a, bool guide_u8, hipStream_t stream);
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream);
 int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream);
 

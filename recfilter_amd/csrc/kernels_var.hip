@@ -53,12 +53,17 @@
 // the plane in the pass kernels: z = b * n_planes + pl).  Image b's planes, weight plane, tails and carries are image 0's plus a
 // wave-uniform 64-bit offset; an image keeps its own tile grid from its row 0 and column 0 and its own borders, so its result is
 // what a launch of that image alone gives, bit for bit, and no sample of one image meets a sample of another.
+//
+// Volumes (rf_var_plan_create_volume, plan_var.cpp) run these kernels as they are: the slices of an x or y stage are the batch, and
+// a z stage is var_y_kernel / var_grad_kernel<1, ...> on the (width * height) x depth view -- the launchers take dim = 2 for it and
+// differ in the name they report.  var_distances_volume is the one kernel volumes add.
 #include "kernels_var.h"
 
 #include "pixel.h"
 #include "var_device.h"
 
 #include <algorithm>
+#include <string>
 
 namespace rf {
 
@@ -377,6 +382,59 @@ __global__ void __launch_bounds__(256) var_distances_kernel(VarDistArgs a) {
     }
 }
 
+// ---- var_distances_volume: lane = 4 adjacent columns of one row, walking z ------------------------------------------------------
+// d_x and d_y of a slice are var_distances' expressions on that slice, term for term.  The lanes are the (row, chunk) pairs of a
+// slice, flat on gridDim.x (a narrow volume still fills its waves); gridDim.y takes segments of kVarDistSlices slices.  A lane
+// keeps its chunk of the slice before, per channel, in registers: the guide is read once, plus one slice per segment.  NG: the
+// channels the registers are laid out for (1, 4 or RF_MAX_PLANES; n_guide <= NG).
+template <typename G, int NG>
+__global__ void __launch_bounds__(256) var_distances_volume_kernel(VarDistVolumeArgs a) {
+    const int chunks = a.width / 4;
+    const int64_t flat = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (flat >= (int64_t)chunks * a.height) return;
+    const int r = (int)(flat / chunks), c = (int)(flat - (int64_t)r * chunks) * 4;
+    const int64_t slice = (int64_t)a.width * a.height;
+    const int64_t own_row = (int64_t)r * a.width + c, up_row = (int64_t)max(r - 1, 0) * a.width + c;
+    const int z0 = blockIdx.y * kVarDistSlices, z1 = min(z0 + kVarDistSlices, a.depth);
+    float before[NG][4];
+#pragma unroll
+    for (int ch = 0; ch < NG; ch++)
+        if (ch < a.n_guide) load_chunk(static_cast<const G *>(a.guide[ch]), (int64_t)max(z0 - 1, 0) * slice + own_row, before[ch]);
+    for (int z = z0; z < z1; z++) {
+        const int64_t own_at = z * slice + own_row, up_at = z * slice + up_row;
+        float sx[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sy[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int ch = 0; ch < NG; ch++) {
+            if (ch >= a.n_guide) continue;
+            const G *g = static_cast<const G *>(a.guide[ch]);
+            float own[4], up[4];
+            load_chunk(g, own_at, own);
+            load_chunk(g, up_at, up);
+            const float left = (float)g[own_at - (c > 0 ? 1 : 0)];
+            sx[0] += fabsf(own[0] - left);
+#pragma unroll
+            for (int j = 1; j < 4; j++) sx[j] += fabsf(own[j] - own[j - 1]);
+#pragma unroll
+            for (int j = 0; j < 4; j++) sy[j] += fabsf(own[j] - up[j]);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                sz[j] += fabsf(own[j] - before[ch][j]);
+                before[ch][j] = own[j];
+            }
+        }
+        float dx[4], dy[4], dz[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            dx[j] = (c + j == 0) ? 1.0f : 1.0f + a.scale * sx[j];
+            dy[j] = (r == 0) ? 1.0f : 1.0f + a.scale * sy[j];
+            dz[j] = (z == 0) ? a.spacing_z : a.spacing_z + a.scale * sz[j];
+        }
+        *reinterpret_cast<float4 *>(a.dx + own_at) = make_float4(dx[0], dx[1], dx[2], dx[3]);
+        *reinterpret_cast<float4 *>(a.dy + own_at) = make_float4(dy[0], dy[1], dy[2], dy[3]);
+        *reinterpret_cast<float4 *>(a.dz + own_at) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+    }
+}
+
 // ---- var_grad: lane = 4 adjacent columns of one row, as var_distances ---------------------------------------------------------
 // The sample before the chunk along the scanned dimension comes from a clamped address (dim 0: the element to the left of the
 // chunk, column 0: the chunk's own first element; dim 1: the chunk of the row above, row 0: the row itself); element 0 of the
@@ -506,12 +564,17 @@ int launched(const char *what) {
 
 template <bool FINAL>
 int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
+    static const char *const kAxis[3] = {"x", "y", "z"};
+    const char *const axis = kAxis[dim];
+    // a z stage of a volume plan is the y kernels on the view plan_var.cpp describes: only its name differs
+    if (dim == 2) dim = 1;
     const int cross = dim == 0 ? a.height : a.width;          // lines, 64 per workgroup
     const dim3 block(64);
     const dim3 grid = dim == 0 ? dim3((unsigned)a.tiles, (unsigned)((cross + 63) / 64), (unsigned)(a.batch * a.n_planes))
                                : dim3((unsigned)((cross + 63) / 64), (unsigned)a.tiles, (unsigned)(a.batch * a.n_planes));
     if (a.adjoint) {
-        const char *what = FINAL ? (dim == 0 ? "var_adj_pass2_x" : "var_adj_pass2_y") : (dim == 0 ? "var_adj_tails_x" : "var_adj_tails_y");
+        const std::string name = std::string(FINAL ? "var_adj_pass2_" : "var_adj_tails_") + axis;
+        const char *what = name.c_str();
         if (a.src_u8 || a.dst_u8 || a.mode == VAR_PAIR) {
             set_error("%s: adjoint stages are single scans on f32 planes", what);
             return RF_ERR_UNSUPPORTED;
@@ -528,7 +591,8 @@ int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
     }
     // byte planes (rf_smooth_plan): the instances that exist, and nothing else -- there is no conversion to fall back on
     if (a.src_u8 || a.dst_u8) {
-        const char *what = FINAL ? (dim == 0 ? "var_pass2_x" : "var_pass2_y") : (dim == 0 ? "var_tails_x" : "var_tails_y");
+        const std::string name = std::string(FINAL ? "var_pass2_" : "var_tails_") + axis;
+        const char *what = name.c_str();
         const bool x_src = dim == 0 && a.src_u8 && !a.dst_u8, y_dst = dim == 1 && FINAL && a.dst_u8 && !a.src_u8;
         if (a.mode != VAR_PAIR || !a.power || !(x_src || y_dst)) {
             set_error("%s: no kernel for byte planes here (source %s, destination %s)", what, a.src_u8 ? "uint8" : "f32", a.dst_u8 ? "uint8" : "f32");
@@ -550,7 +614,7 @@ int launch_pass(const VarArgs &a, int dim, hipStream_t stream) {
     }
 #undef RF_VAR_LAUNCH
 #undef RF_VAR_LAUNCH_FORM
-    return launched(FINAL ? (dim == 0 ? "var_pass2_x" : "var_pass2_y") : (dim == 0 ? "var_tails_x" : "var_tails_y"));
+    return launched((std::string(FINAL ? "var_pass2_" : "var_tails_") + axis).c_str());
 }
 
 }  // namespace
@@ -575,7 +639,23 @@ int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream
     return launched("var_distances");
 }
 
+int launch_var_distances_volume(const VarDistVolumeArgs &a, bool guide_u8, hipStream_t stream) {
+    const int64_t lanes = (int64_t)(a.width / 4) * a.height;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)((a.depth + kVarDistSlices - 1) / kVarDistSlices)), block(256);
+#define RF_VAR_LAUNCH_DISTANCES(NG)                                                                                    \
+    if (guide_u8) hipLaunchKernelGGL((var_distances_volume_kernel<uint8_t, NG>), grid, block, 0, stream, a);            \
+    else hipLaunchKernelGGL((var_distances_volume_kernel<float, NG>), grid, block, 0, stream, a)
+    if (a.n_guide <= 1) { RF_VAR_LAUNCH_DISTANCES(1); }
+    else if (a.n_guide <= 4) { RF_VAR_LAUNCH_DISTANCES(4); }
+    else { RF_VAR_LAUNCH_DISTANCES(RF_MAX_PLANES); }
+#undef RF_VAR_LAUNCH_DISTANCES
+    return launched("var_distances_volume");
+}
+
+// dim 2 (a z stage of a volume plan): the dim 1 instances on the view the arguments describe
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream) {
+    const char *const what = dim == 0 ? "var_grad_x" : dim == 1 ? "var_grad_y" : "var_grad_z";
+    if (dim == 2) dim = 1;
     const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)a.batch), block(256);
 #define RF_VAR_LAUNCH_GRAD(POWER)                                                                                   \
     if (dim == 0) {                                                                                                 \
@@ -587,7 +667,7 @@ int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stre
     }
     if (a.exponents) { RF_VAR_LAUNCH_GRAD(true) } else { RF_VAR_LAUNCH_GRAD(false) }
 #undef RF_VAR_LAUNCH_GRAD
-    return launched(dim == 0 ? "var_grad_x" : "var_grad_y");
+    return launched(what);
 }
 
 int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream) {

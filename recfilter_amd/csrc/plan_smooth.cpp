@@ -20,6 +20,10 @@
 //
 // Both run functions construct one LaunchTimer (run_support.h) and hand it to every launcher they call, so the slots of a timed run
 // follow the plan's name lists; the constants of the power form, log2 and ln of every a_k, are the plan's from its construction.
+//
+// A volume plan (build_smooth_volume_plan, rf_smooth_plan_create_volume) is the same sequence one dimension up: three distance
+// volumes from one var_distances_volume launch (d_z from spacing_z), an inner volume plan +x -x +y -y +z -z with {a_k, a_k, a_k},
+// 1 + 9 K launches; bytes enter at the first x stage and leave at the last z pass.  No batch, and its backward is refused.
 #include "plan_smooth.h"
 
 #include <algorithm>
@@ -147,13 +151,62 @@ int check_extents(const ExtentArray *arrays, int n_arrays, int batch) {
 
 }  // namespace
 
+namespace {
+int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, rf_smooth_plan **out);
+}
+
 int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out) {
     if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     *out = nullptr;
     int rc = batch ? validate_batch(desc, batch) : RF_OK;
     if (rc == RF_OK) rc = validate(desc);
     if (rc != RF_OK) return rc;
+    return build_checked(desc, batch, 0, 1.0f, out);
+}
+
+int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan **out) {
+    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    *out = nullptr;
+    // the description of a slice, checked as an image's; then the volume's own domain and spacing_z
+    rf_smooth_desc d{};
+    d.abi = desc->abi;
+    d.image_u8 = desc->image_u8;
+    d.width = desc->width;
+    d.height = desc->height;
+    d.n_planes = desc->n_planes;
+    d.n_guide = desc->n_guide;
+    d.guide_u8 = desc->guide_u8;
+    d.iterations = desc->iterations;
+    d.sigma_s = desc->sigma_s;
+    d.sigma_r = desc->sigma_r;
+    d.device = desc->device;
+    d.flags = desc->flags;
+    int rc = validate(&d);
+    if (rc != RF_OK) return rc;
+    const float spacing_z = (float)desc->spacing_z;
+    if (!std::isfinite(desc->spacing_z) || !std::isfinite(spacing_z) || !(spacing_z > 0.0f)) {
+        set_error("spacing_z must be finite and positive in f32 (got %g)", desc->spacing_z);
+        return RF_ERR_INVALID_ARG;
+    }
+    rc = check_volume_extents(desc->width, desc->height, desc->depth, desc->n_planes);
+    if (rc != RF_OK) return rc;
+    return build_checked(&d, nullptr, desc->depth, spacing_z, out);
+}
+
+int refuse_volume_backward() {
+    set_error("the backward of a smoothing plan takes images: the distances of a volume (var_distances_volume) have no adjoint");
+    return RF_ERR_UNSUPPORTED;
+}
+
+namespace {
+
+// the plan of a description that has passed its checks; depth = 0: an image, else a volume
+int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, rf_smooth_plan **out) {
+    int rc = RF_OK;
     std::unique_ptr<rf_smooth_plan> plan(new rf_smooth_plan);
+    plan->volume = depth > 0;
+    plan->depth = plan->volume ? depth : 1;
+    plan->spacing_z = spacing_z;
     plan->width = desc->width;
     plan->height = desc->height;
     plan->n_planes = desc->n_planes;
@@ -183,7 +236,7 @@ int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *ba
         plan->log2_bases.push_back((float)std::log2((double)a_k));
         plan->ln_bases.push_back((float)std::log((double)a_k));
     }
-    const rf_var_scan_desc scans[4] = {{0, 1, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 1}};
+    const rf_var_scan_desc scans[6] = {{0, 1, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 1}, {2, 1, 2}, {2, 0, 2}};
     rf_var_desc vd{};
     vd.ndim = 2;
     vd.abi = RF_ABI;
@@ -197,12 +250,27 @@ int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *ba
     vd.device = desc->device;
     vd.flags = 0;
     rf_var_plan *inner = nullptr;
-    rc = build_var_plan(&vd, &inner, plan->batch);      // (the device checks, and the tails and the carries)
+    if (plan->volume) {
+        rf_var_volume_desc vv{};
+        vv.abi = RF_ABI;
+        vv.width = desc->width;
+        vv.height = desc->height;
+        vv.depth = depth;
+        vv.dtype = RF_F32;
+        vv.n_planes = desc->n_planes;
+        vv.n_weights = 3;
+        vv.n_scans = 6;
+        vv.scans = scans;
+        vv.device = desc->device;
+        rc = build_var_volume_plan(&vv, &inner);
+    } else {
+        rc = build_var_plan(&vd, &inner, plan->batch);      // (the device checks, and the tails and the carries)
+    }
     if (rc != RF_OK) return rc;
     plan->inner.reset(inner);
     plan->device = inner->device;
-    const size_t plane_bytes = (size_t)(desc->width * desc->height) * sizeof(float);
-    plan->planes_bytes = plane_bytes * (size_t)(2 + (plan->image_u8 ? desc->n_planes : 0)) * (size_t)plan->batch;
+    const size_t plane_bytes = (size_t)plan->samples() * sizeof(float);
+    plan->planes_bytes = plane_bytes * (size_t)((plan->volume ? 3 : 2) + (plan->image_u8 ? desc->n_planes : 0)) * (size_t)plan->batch;
     if (!plan->host_only) {
         RF_HIP_CHECK(hipSetDevice(plan->device));
         if (hipMalloc((void **)&plan->planes, plan->planes_bytes) != hipSuccess) {
@@ -211,11 +279,11 @@ int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *ba
             return RF_ERR_NOMEM;
         }
     }
-    plan->names.push_back("var_distances");
+    plan->names.push_back(plan->volume ? "var_distances_volume" : "var_distances");
     for (int k = 0; k < K; k++)
         for (const std::string &n : inner->names) plan->names.push_back(n);
-    // the adjoint's launch lists
-    for (int edges = 0; edges < 2; edges++) {
+    // the adjoint's launch lists (a volume plan has none: its backward is refused)
+    for (int edges = 0; edges < 2 && !plan->volume; edges++) {
         std::vector<std::string> &names = plan->backward_names[edges];
         names.push_back("var_distances");
         if (edges)
@@ -229,13 +297,15 @@ int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *ba
     return RF_OK;
 }
 
+}  // namespace
+
 int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
                     hipStream_t stream, float *ms_out) {
     if (!plan || !image_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     if (plan->n_guide > 0 && !guide_planes) { set_error("this plan takes %d separate guide planes: guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }
     if (plan->n_guide == 0 && guide_planes) { set_error("this plan's image guides itself (n_guide = 0): guide_planes must be null"); return RF_ERR_INVALID_ARG; }
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
-    const size_t samples = (size_t)(plan->width * plan->height);
+    const size_t samples = (size_t)plan->samples();
     const size_t image_bytes = samples * (plan->image_u8 ? 1 : sizeof(float));
     int rc = RF_OK;
     for (int pl = 0; pl < plan->n_planes && rc == RF_OK; pl++)
@@ -268,17 +338,23 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
     LaunchTimer timer(stream, ms_out, plan->names.size());
     if (timer.status() != RF_OK) return timer.status();
     float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each
+    float *dz = plan->volume ? dy + samples : nullptr;             // (a volume: B is 1)
+    float *const own = plan->volume ? dz + samples : dy + samples * (size_t)B;      // what follows the distances
     // the distances first, on the same stream: guide planes may be output planes
     const bool self = plan->n_guide == 0;
-    rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
-                           plan->width, plan->height, plan->scale, dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
+    if (plan->volume)
+        rc = run_var_distances_volume(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
+                                      plan->width, plan->height, plan->depth, plan->scale, plan->spacing_z, dx, dy, dz, plan->device, stream);
+    else
+        rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
+                               plan->width, plan->height, plan->scale, dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
     if (rc == RF_OK) rc = timer.mark();
     if (rc != RF_OK) return rc;
     void *work[RF_MAX_PLANES] = {};
     // byte images: [image][plane] behind the distance planes
-    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(dy + samples * (size_t)(B + pl)) : out_planes[pl];
+    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(own + samples * (size_t)pl) : out_planes[pl];
     const int64_t work_stride = plan->image_u8 ? (int64_t)samples * plan->n_planes : image_stride;
-    const void *const weights[2] = {dx, dy};
+    const void *const weights[3] = {dx, dy, dz};
     const int K = plan->iterations;
     for (int k = 0; k < K; k++) {
         VarIo io{};
@@ -291,7 +367,7 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         io.work_stride = work_stride;
         io.out_stride = k == K - 1 ? image_stride : work_stride;
         io.weights_stride = (int64_t)samples;
-        const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
+        const float l[3] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
         rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, timer);
         if (rc != RF_OK) return rc;
     }
@@ -304,6 +380,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
     if (!plan || !grad_out_planes || !grad_image_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return RF_ERR_INVALID_ARG; }
+    if (plan->volume) return refuse_volume_backward();
     if (plan->image_u8) { set_error("the backward of a smoothing plan takes f32 images (this plan's are uint8)"); return RF_ERR_UNSUPPORTED; }
     const bool self = plan->n_guide == 0;
     if (!self && !guide_planes) { set_error("this plan takes %d separate guide planes: guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }

@@ -16,6 +16,12 @@ struct rf_smooth_plan {
     int batch = 1;
     int64_t image_stride = 0, guide_stride = 0;
     bool image_u8 = false, guide_u8 = false;
+    // rf_smooth_plan_create_volume: planes are [z][y][x] volumes of width x height x depth samples, the inner plan is a volume plan
+    // (+x -x +y -y +z -z on three exponent volumes) and there is a third distance volume d_z, formed from spacing_z.  batch stays 1.
+    bool volume = false;
+    int64_t depth = 1;
+    float spacing_z = 1.0f;
+    int64_t samples() const { return width * height * depth; }      // of one plane
     int device = 0;
     bool host_only = false;
     float scale = 0.0f;                      // of var_distances: sigma_s / sigma_r, over 255 where the planes that guide are bytes
@@ -23,7 +29,7 @@ struct rf_smooth_plan {
     std::vector<float> log2_bases;           // (float)log2((double)a_k): what rf_var_plan_execute_power forms from a_k
     std::vector<float> ln_bases;             // (float)log((double)a_k): what rf_var_plan_backward_power forms beside it
     std::unique_ptr<rf_var_plan> inner;      // +x -x +y -y on two exponent planes: two pair stages, the tails and the carries
-    // one allocation: d_x (one plane per image), d_y (the same), then (byte images) n_planes f32 working planes per image
+    // one allocation: d_x (one plane per image), d_y (the same), (a volume: d_z,) then (byte images) n_planes f32 working planes per image
     float *planes = nullptr;
     size_t planes_bytes = 0;
     std::vector<std::string> names;          // "var_distances", then the inner plan's six per iteration
@@ -35,13 +41,17 @@ struct rf_smooth_plan {
     std::vector<std::string> backward_names[2];
     float *grad_planes = nullptr;
     size_t own_backward_bytes() const { return (size_t)batch * (size_t)(2 + (iterations - 1) * n_planes) * (size_t)(width * height) * sizeof(float); }
-    size_t backward_workspace_bytes(bool edges) const { return edges ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
+    size_t backward_workspace_bytes(bool edges) const { return edges && !volume ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
     ~rf_smooth_plan();
 };
 
 namespace rf {
 // batch == nullptr: rf_smooth_plan_create; else rf_smooth_plan_create_batched (which has refused a null one)
 int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out);
+// rf_smooth_plan_create_volume
+int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan **out);
+// what the backward entry points answer for a volume plan: RF_ERR_UNSUPPORTED
+int refuse_volume_backward();
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
 int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
                     hipStream_t stream, float *ms_out);

@@ -34,6 +34,12 @@
 // A plan may hold a batch (build_var_plan's third argument; plan_smooth.cpp only, the public entry points build 1): tails,
 // carries and the backward's planes are then `batch` images' worth, image after image, and the launchers above carry the batch
 // and the strides from image to image (VarIo, VarBackwardIo) to the kernels, whose grids take all images at once.
+//
+// A volume plan (build_var_volume_plan, rf_var_plan_create_volume) runs the same kernels on dense [z][y][x] volumes: scan_args
+// gives an x or y stage the `depth` slices as its batch (slice strides of width * height samples: stage_stride; tails and carries
+// slice after slice in the single-image layout) and a z stage the (width * height) x depth view of the y kernels, a voxel column
+// per lane.  plan->batch stays 1 and the backward's planes are volumes.  check_volume_extents is the accepted domain, shared with
+// run_var_distances_volume (the three exponent volumes, one launch) and plan_smooth.cpp.
 #include "plan_var.h"
 
 #include <algorithm>
@@ -87,7 +93,7 @@ int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
 
 // the three launches of a stage along `dim` (a signal plan: "1d"); prefix: "var_", or "var_adj_" for an adjoint stage
 void push_stage_names(std::vector<std::string> &names, const char *prefix, int dim, bool signal) {
-    const char *axis = signal ? "1d" : dim == 0 ? "x" : "y";
+    const char *axis = signal ? "1d" : dim == 0 ? "x" : dim == 1 ? "y" : "z";
     names.push_back(std::string(prefix) + "tails_" + axis);
     names.push_back(signal ? "var_carry_1d" : "var_carry");
     names.push_back(std::string(prefix) + "pass2_" + axis);
@@ -123,9 +129,59 @@ int validate_signal(const rf_var_signal_desc *d) {
     return RF_OK;
 }
 
+constexpr int64_t kVarMaxVolumeLines = int64_t(1) << 30;      // width * height: the z view's line index is an int32
+constexpr int64_t kVarMaxGridZ = 65535;                        // depth * n_planes: the slices ride on gridDim.z beside the planes
+
+int validate_volume(const rf_var_volume_desc *d) {
+    if (d->abi != RF_ABI) {
+        set_error("rf_var_volume_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->flags != 0) { set_error("rf_var_volume_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
+    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
+    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
+    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
+    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
+    if (d->dtype != RF_F32) { set_error("varying scans take f32 volumes (dtype = %d)", d->dtype); return RF_ERR_UNSUPPORTED; }
+    for (int s = 0; s < d->n_scans; s++) {
+        const rf_var_scan_desc &sc = d->scans[s];
+        if (sc.dim < 0 || sc.dim > 2) { set_error("scan %d: dim must be 0, 1 or 2 on a volume (got %d)", s, sc.dim); return RF_ERR_INVALID_ARG; }
+        if (sc.weights < 0 || sc.weights >= d->n_weights) {
+            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    return check_volume_extents(d->width, d->height, d->depth, d->n_planes);
+}
+
 int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool signal);
 
 }  // namespace
+
+int check_volume_extents(int64_t width, int64_t height, int64_t depth, int32_t n_planes) {
+    if (width < 1 || height < 1 || depth < 1) {
+        set_error("width, height and depth must be positive (got %lld x %lld x %lld)", (long long)width, (long long)height, (long long)depth);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (width > kVarMaxExtent || height > kVarMaxExtent || depth > kVarMaxExtent) {
+        set_error("extents %lld x %lld x %lld are above %lld", (long long)width, (long long)height, (long long)depth, (long long)kVarMaxExtent);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (width % 4 != 0) {
+        set_error("varying scans move 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", (long long)width);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (width * height > kVarMaxVolumeLines) {
+        set_error("width * height = %lld is above %lld: a z scan indexes its lines in 32 bits", (long long)(width * height), (long long)kVarMaxVolumeLines);
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (depth * n_planes > kVarMaxGridZ) {
+        set_error("depth * n_planes = %lld is above %lld: the slices of an x or y stage ride on gridDim.z beside the planes",
+                  (long long)(depth * n_planes), (long long)kVarMaxGridZ);
+        return RF_ERR_UNSUPPORTED;
+    }
+    return RF_OK;
+}
 
 int64_t var_max_extent() { return kVarMaxExtent; }
 
@@ -157,6 +213,27 @@ int build_var_signal_plan(const rf_var_signal_desc *desc, rf_var_plan **out) {
     return build_checked(&d, out, 1, true);
 }
 
+int build_var_volume_plan(const rf_var_volume_desc *desc, rf_var_plan **out) {
+    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    *out = nullptr;
+    int rc = validate_volume(desc);
+    if (rc != RF_OK) return rc;
+    // (ndim = 3 reaches build_checked from here alone: rf_var_plan_create refuses it)
+    rf_var_desc d{};
+    d.ndim = 3;
+    d.abi = desc->abi;
+    d.extent[0] = desc->width;
+    d.extent[1] = desc->height;
+    d.extent[2] = desc->depth;
+    d.dtype = desc->dtype;
+    d.n_planes = desc->n_planes;
+    d.n_weights = desc->n_weights;
+    d.n_scans = desc->n_scans;
+    d.scans = desc->scans;
+    d.device = desc->device;
+    return build_checked(&d, out, 1, false);
+}
+
 namespace {
 
 // the plan of a description that has passed its checks
@@ -178,10 +255,12 @@ int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool si
     plan->device = host_only ? 0 : device;
     plan->host_only = host_only;
     plan->signal = signal;
+    plan->volume = desc->ndim == 3;
+    plan->depth = plan->volume ? desc->extent[2] : 1;
     // Stages: the scans are taken in runs along one dimension.  A run that is exactly {+d, -d} on one weight plane is ONE fused
     // stage; every other run -- a single scan, -d +d, a pair on two weight planes, three or more scans along the dimension --
     // goes scan by scan (longer runs are not searched for pairs).
-    bool used[2] = {false, false};
+    bool used[3] = {false, false, false};
     auto add_stage = [&](int dim, int mode, int weights) {
         rf_var_stage st;
         st.dim = dim; st.mode = mode; st.weights = weights;
@@ -206,12 +285,14 @@ int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool si
     for (int with = 0; with < 2; with++)
         for (int q = desc->n_scans - 1; q >= 0; q--) {
             push_stage_names(plan->backward_names[with], "var_adj_", desc->scans[q].dim, signal);
-            if (with) plan->backward_names[with].push_back(desc->scans[q].dim == 0 ? "var_grad_x" : "var_grad_y");
+            if (with) plan->backward_names[with].push_back(desc->scans[q].dim == 0 ? "var_grad_x" : desc->scans[q].dim == 1 ? "var_grad_y" : "var_grad_z");
         }
-    // tiles x lines of the dimension that needs more: x scans have `height` lines, y scans `width`
+    // tiles x lines of the dimension that needs more: x scans have `height` lines (per slice of a volume), y scans `width`, z
+    // scans width * height
     int64_t slots = 0;
-    if (used[0]) slots = std::max(slots, tiles_of(plan->width) * plan->height);
-    if (used[1]) slots = std::max(slots, tiles_of(plan->height) * plan->width);
+    if (used[0]) slots = std::max(slots, tiles_of(plan->width) * plan->height * plan->depth);
+    if (used[1]) slots = std::max(slots, tiles_of(plan->height) * plan->width * plan->depth);
+    if (used[2]) slots = std::max(slots, tiles_of(plan->depth) * plan->width * plan->height);
     int64_t carry_slots = slots;
     if (signal) {
         // a lane's map per tile and an aggregate per group of 64 tiles; carries per group
@@ -264,7 +345,24 @@ VarArgs scan_args(const rf_var_plan *plan, int dim, const void *weights, int mod
     a.tiles = (int32_t)tiles_of(dim == 0 ? plan->width : plan->height);
     a.lines = (int32_t)(dim == 0 ? plan->height : plan->width);
     a.mode = mode;
+    if (plan->volume && dim == 2) {
+        // the (width * height) x depth view: a voxel column per lane, rows width * height samples apart
+        a.width = a.lines = (int32_t)(plan->width * plan->height);
+        a.height = (int32_t)plan->depth;
+        a.tiles = (int32_t)tiles_of(plan->depth);
+    } else if (plan->volume) {
+        // the slices as a batch, each with a slice's tails and carries in the single-image layout
+        a.batch = (int32_t)plan->depth;
+        a.tails_stride = (int64_t)a.tiles * kVarComponents * a.n_planes * a.lines;
+        a.carry_stride = (int64_t)a.tiles * 2 * a.n_planes * a.lines;
+    }
     return a;
+}
+
+// Samples from image to image of a stage's planes: the caller's stride -- or, in a volume plan, the slice stride of an x / y stage
+// and nothing for a z stage, whose one image is the whole view.
+int64_t stage_stride(const rf_var_plan *plan, int dim, int64_t callers) {
+    return plan->volume ? (dim == 2 ? 0 : plan->width * plan->height) : callers;
 }
 
 // The three launches of a stage, a mark behind each.  a.dst_u8 is held back until the final pass: the tails pass stores no sample.
@@ -291,7 +389,7 @@ int run_var_plan(rf_var_plan *plan, const void *const *in_planes, const void *co
     int rc = bases ? power_constants(bases, plan->n_weights, log2_base, ln_base) : RF_OK;
     if (rc != RF_OK) return rc;
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
-    const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
+    const size_t plane_bytes = (size_t)plan->plane_samples() * sizeof(float);
     for (int pl = 0; pl < plan->n_planes; pl++) {
         rc = check_plane("plane", pl, {{in_planes[pl]}, {out_planes[pl]}}, 15u, "null image pointer", "the varying scans need 16-byte aligned image pointers");
         if (rc != RF_OK) return rc;
@@ -327,9 +425,9 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
         }
         a.src_u8 = s == 0 && io.in_u8;
         a.dst_u8 = s == last && io.out_u8;
-        a.src_stride = s == 0 ? io.in_stride : io.work_stride;
-        a.dst_stride = s == last ? io.out_stride : io.work_stride;
-        a.weights_stride = io.weights_stride;
+        a.src_stride = stage_stride(plan, st.dim, s == 0 ? io.in_stride : io.work_stride);
+        a.dst_stride = stage_stride(plan, st.dim, s == last ? io.out_stride : io.work_stride);
+        a.weights_stride = stage_stride(plan, st.dim, io.weights_stride);
         a.power = log2_base ? 1 : 0;
         a.log2_base = log2_base ? log2_base[st.weights] : 0.0f;
         int rc = launch_stage(a, st.dim, plan->signal, stream, timer);
@@ -352,7 +450,7 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
     if (rc != RF_OK) return rc;
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
     const int P = plan->n_planes, K = plan->n_weights;
-    const size_t plane_bytes = (size_t)(plan->width * plan->height) * sizeof(float);
+    const size_t plane_bytes = (size_t)plan->plane_samples() * sizeof(float);
     for (int pl = 0; pl < P; pl++) {
         rc = check_plane("plane", pl, {{grad_out_planes[pl]}, {grad_in_planes[pl]}, {with_weights ? in_planes[pl] : nullptr, with_weights}}, 15u,
                          "null image pointer", "the varying scans need 16-byte aligned image pointers");
@@ -403,7 +501,7 @@ int ensure_var_grad_planes(rf_var_plan *plan) {
 int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, LaunchTimer &timer) {
     const int P = plan->n_planes, S = (int)plan->scans.size();
     const bool with_weights = io.grad_weights != nullptr, power = io.log2_base != nullptr;
-    const size_t plane_floats = (size_t)(plan->width * plan->height);
+    const size_t plane_floats = (size_t)plan->plane_samples();
     // [scan][image][plane]; scan == S: the state
     auto saved = [&](int scan, int pl) { return plan->grad_planes + ((size_t)scan * (size_t)plan->batch * P + pl) * plane_floats; };
     const int64_t saved_stride = (int64_t)P * (int64_t)plane_floats;
@@ -412,7 +510,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
         VarArgs a = scan_args(plan, sc.dim, io.weights[sc.weights], mode);
         a.power = power ? 1 : 0;
         a.log2_base = power ? io.log2_base[sc.weights] : 0.0f;
-        a.weights_stride = io.weights_stride;
+        a.weights_stride = stage_stride(plan, sc.dim, io.weights_stride);
         return a;
     };
     int rc = RF_OK;
@@ -425,8 +523,8 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
                 a.src[pl] = q == 0 ? io.in[pl] : saved(q - 1, pl);
                 a.dst[pl] = saved(q, pl);
             }
-            a.src_stride = q == 0 ? io.in_stride : saved_stride;
-            a.dst_stride = saved_stride;
+            a.src_stride = stage_stride(plan, sc.dim, q == 0 ? io.in_stride : saved_stride);
+            a.dst_stride = stage_stride(plan, sc.dim, saved_stride);
             rc = launch_stage(a, sc.dim, plan->signal, stream, timer);
         }
     }
@@ -444,9 +542,9 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
             a.dst[pl] = io.grad_in[pl];
             a.lam[pl] = grad ? saved(S, pl) : nullptr;
         }
-        a.src_stride = q == S - 1 ? io.grad_out_stride : io.grad_in_stride;
-        a.dst_stride = io.grad_in_stride;
-        a.lam_stride = saved_stride;
+        a.src_stride = stage_stride(plan, sc.dim, q == S - 1 ? io.grad_out_stride : io.grad_in_stride);
+        a.dst_stride = stage_stride(plan, sc.dim, io.grad_in_stride);
+        a.lam_stride = stage_stride(plan, sc.dim, saved_stride);
         rc = launch_stage(a, sc.dim, plan->signal, stream, timer);
         if (rc != RF_OK || !with_weights) continue;
         if (grad) {                                   // (a weight plane without a gradient: no launch, its slot reports 0 ms)
@@ -457,14 +555,14 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
                 g.y[pl] = saved(q, pl);
             }
             g.grad = grad;
-            g.width = (int32_t)plan->width;
-            g.height = (int32_t)plan->height;
+            g.width = a.width;                  // (a volume: the stage's view and its batch of slices)
+            g.height = a.height;
             g.n_planes = P;
-            g.batch = plan->batch;
-            g.lam_stride = g.y_stride = saved_stride;
-            g.x_stride = q == 0 ? io.in_stride : saved_stride;
-            g.grad_stride = io.grad_weights_stride;
-            g.exponents_stride = io.weights_stride;
+            g.batch = a.batch;
+            g.lam_stride = g.y_stride = stage_stride(plan, sc.dim, saved_stride);
+            g.x_stride = stage_stride(plan, sc.dim, q == 0 ? io.in_stride : saved_stride);
+            g.grad_stride = stage_stride(plan, sc.dim, io.grad_weights_stride);
+            g.exponents_stride = stage_stride(plan, sc.dim, io.weights_stride);
             g.accumulate = touched[sc.weights] ? 1 : 0;
             if (power) {
                 g.exponents = (const float *)io.weights[sc.weights];
@@ -547,6 +645,51 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
     a.batch = batch;
     a.guide_stride = guide_stride;
     return launch_var_distances(a, guide_u8 != 0, stream);
+}
+
+int run_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
+                             float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, hipStream_t stream) {
+    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
+    if (width < 1 || height < 1 || depth < 1) { set_error("width, height and depth must be positive"); return RF_ERR_INVALID_ARG; }
+    if (!guide_volumes || !dx || !dy || !dz) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (!guide_volumes[ch]) { set_error("guide volume %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
+    int rc = check_distance_scale(scale);
+    if (rc != RF_OK) return rc;
+    if (!std::isfinite(spacing_z) || !(spacing_z > 0.0f)) { set_error("spacing_z must be finite and positive (got %g)", (double)spacing_z); return RF_ERR_INVALID_ARG; }
+    rc = check_volume_extents(width, height, depth, 1);
+    if (rc != RF_OK) return rc;
+    if ((((uintptr_t)dx | (uintptr_t)dy | (uintptr_t)dz) & 15u) != 0) { set_error("dx, dy and dz must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
+    const uintptr_t guide_align = guide_u8 ? 3u : 15u;
+    for (int ch = 0; ch < n_guide; ch++)
+        if (((uintptr_t)guide_volumes[ch] & guide_align) != 0) {
+            set_error("guide volume %d: %s guide volumes must be %u-byte aligned", ch, guide_u8 ? "uint8" : "f32", (unsigned)guide_align + 1);
+            return RF_ERR_INVALID_ARG;
+        }
+    const size_t samples = (size_t)(width * height * depth), out_bytes = samples * sizeof(float), guide_bytes = samples * (guide_u8 ? 1 : sizeof(float));
+    if (overlap(dx, out_bytes, dy, out_bytes) || overlap(dx, out_bytes, dz, out_bytes) || overlap(dy, out_bytes, dz, out_bytes)) {
+        set_error("dx, dy and dz overlap each other");
+        return RF_ERR_INVALID_ARG;
+    }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (overlap(dx, out_bytes, guide_volumes[ch], guide_bytes) || overlap(dy, out_bytes, guide_volumes[ch], guide_bytes) ||
+            overlap(dz, out_bytes, guide_volumes[ch], guide_bytes)) {
+            set_error("guide volume %d overlaps dx, dy or dz: a lane reads its neighbours' samples", ch);
+            return RF_ERR_INVALID_ARG;
+        }
+    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
+    VarDistVolumeArgs a{};
+    for (int ch = 0; ch < n_guide; ch++) a.guide[ch] = guide_volumes[ch];
+    a.dx = (float *)dx;
+    a.dy = (float *)dy;
+    a.dz = (float *)dz;
+    a.width = (int32_t)width;
+    a.height = (int32_t)height;
+    a.depth = (int32_t)depth;
+    a.n_guide = n_guide;
+    a.scale = scale;
+    a.spacing_z = spacing_z;
+    return launch_var_distances_volume(a, guide_u8 != 0, stream);
 }
 
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,

@@ -26,6 +26,13 @@ struct rf_var_plan {
     // one long 1-D signal (rf_var_plan_create_signal): width = its length, height = 1, every scan along dim 0; the stages run the
     // kernels of kernels_var_signal.hip and the workspace is sized for tiles plus groups of 64 tiles
     bool signal = false;
+    // a volume (rf_var_plan_create_volume): planes are dense [z][y][x] volumes of width x height x depth samples and dim 2 scans
+    // along z.  An x / y stage takes the `depth` slices as a batch (gridDim.z, slice strides of width * height samples, tails and
+    // carries slice after slice in the single-image layout); a z stage runs the y kernels on the (width * height) x depth view,
+    // one voxel column per lane.  `batch` stays 1: there is no batch of volumes.
+    bool volume = false;
+    int64_t depth = 1;
+    int64_t plane_samples() const { return width * height * depth; }
     std::vector<rf_var_stage> stages;
     std::vector<std::string> names;          // three per stage: what rf_var_plan_execute_timed reports
     // the one workspace: every stage's tails and carries (sized for the larger dimension); written before it is read
@@ -42,7 +49,7 @@ struct rf_var_plan {
     std::vector<std::string> backward_names[2];
     float *grad_planes = nullptr;
     size_t backward_workspace_bytes(bool with_weight_gradients) const {
-        return with_weight_gradients ? (scans.size() + 1) * (size_t)batch * (size_t)n_planes * (size_t)(width * height) * sizeof(float) : 0;
+        return with_weight_gradients ? (scans.size() + 1) * (size_t)batch * (size_t)n_planes * (size_t)plane_samples() * sizeof(float) : 0;
     }
     ~rf_var_plan();
 };
@@ -51,6 +58,12 @@ namespace rf {
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch = 1);
 // rf_var_plan_create_signal: an ordinary plan whose planes are dense f32 signals of desc->length samples
 int build_var_signal_plan(const rf_var_signal_desc *desc, rf_var_plan **out);
+// rf_var_plan_create_volume: an ordinary plan whose planes are dense f32 volumes
+int build_var_volume_plan(const rf_var_volume_desc *desc, rf_var_plan **out);
+// what rf_var_plan_create_volume, rf_var_distances_volume and rf_smooth_plan_create_volume refuse alike (the message names the limit):
+// extents below 1 (RF_ERR_INVALID_ARG); a width that is no multiple of 4, an extent above 2^21, width * height above 2^30,
+// depth * n_planes above 65535 (RF_ERR_UNSUPPORTED)
+int check_volume_extents(int64_t width, int64_t height, int64_t depth, int32_t n_planes);
 
 // The power form's constants: bases[k] inside (0, 1) for each of the n_weights planes, or a refusal; log2 and ln of each.
 int power_constants(const float *bases, int n_weights, float *log2_base, float *ln_base);
@@ -96,6 +109,9 @@ int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORT
 // batch > 1 (plan_smooth.cpp): image b's guide planes are guide_stride samples behind image 0's, dx and dy hold `batch` dense planes
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                       void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch = 1, int64_t guide_stride = 0);
+// rf_var_distances_volume: d_x, d_y slice by slice as run_var_distances forms them, d_z along z from spacing_z; one launch
+int run_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
+                             float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, hipStream_t stream);
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
                                const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
                                int32_t batch = 1, int64_t guide_stride = 0, int64_t grad_guide_stride = 0);

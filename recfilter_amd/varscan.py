@@ -9,6 +9,10 @@ The scans run in the HIP kernels of kernels_var.hip; torch tensors are device me
   plan     `SmoothPlan` (rf_smooth_plan_*): the power form as one object of the library, which owns the distance planes and
            sequences every launch; f32 or uint8 images (bytes in, bytes out, no conversion pass).
 
+Volumes: `VarPlan.volume`, `var_scan_volume`, `domain_transform_distances_volume`, `SmoothPlan.volume` and
+`edge_aware_smooth_volume` are the same on (D, H, W) volumes with scans along x, y and z (rf_var_plan_create_volume,
+rf_var_distances_volume, rf_smooth_plan_create_volume); the smoothing plan of a volume has no backward.
+
 The plane form is differentiable: `VarPlan.backward` (rf_var_plan_backward) is the adjoint of `VarPlan.execute` in the same HIP
 kernels' adjoint instances -- gradients with respect to the image planes and, where asked for, the weight planes -- and
 `VarPlan.apply` / `var_scan` put it behind torch.autograd.  So are the power form and the plan: `VarPlan.backward_power`
@@ -106,6 +110,40 @@ class VarPlan(_PlanHandle):
         self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
         self._h = ctypes.c_void_p()
         capi.check(L.rf_var_plan_create_signal(ctypes.byref(d), ctypes.byref(self._h)))
+        return self
+
+    @classmethod
+    def volume(cls, shape: Sequence[int], scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1) -> "VarPlan":
+        """rf_var_plan_create_volume: the plan of `planes` dense f32 volumes of `shape` = (depth, height, width) that share
+        `n_weights` weight volumes; dim 0 = x, 1 = y, 2 = z, and element 0 of a weight volume along the scanned axis is never
+        used.  Every method works as on an image plan, a plane being a 3-D tensor.  An x or y stage takes all slices in one
+        launch, each bit for bit what VarPlan((height, width)) gives on it; a z stage is bit for bit the y stage of the 2-D plan
+        on the (depth, height * width) reshaped volume.  Three launches per stage whatever the depth (var_tails_z, var_carry,
+        var_pass2_z for z).  width % 4 == 0, extents up to 2**21, height * width <= 2**30, depth * planes <= 65535."""
+        L = capi.lib()
+        self = cls.__new__(cls)
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 3:
+            raise ValueError(f"shape must be (depth, height, width), got {shape}")
+        scans = list(scans)
+        self._scan_arr = (capi.VarScanDesc * max(len(scans), 1))()
+        for i, (dim, causal, weights) in enumerate(scans):
+            s = self._scan_arr[i]
+            s.dim, s.causal, s.weights = int(dim), int(bool(causal)), int(weights)
+        d = capi.VarVolumeDesc()
+        d.abi = capi.RF_ABI
+        d.depth, d.height, d.width = shape
+        d.dtype = capi.RF_F32
+        d.n_planes, d.n_weights = int(planes), int(n_weights)
+        d.n_scans = len(scans)
+        d.scans = ctypes.cast(self._scan_arr, ctypes.POINTER(capi.VarScanDesc))
+        d.device = int(device)
+        d.flags = 0
+        self._desc = d
+        self.shape, self.planes, self.n_weights = shape, int(planes), int(n_weights)
+        self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
+        self._h = ctypes.c_void_p()
+        capi.check(L.rf_var_plan_create_volume(ctypes.byref(d), ctypes.byref(self._h)))
         return self
 
     # -- queries ----------------------------------------------------------------------------
@@ -319,6 +357,28 @@ def var_scan(ins, weights, scans):
     return plan.apply(ins, weights)
 
 
+_volume_plans: Dict[tuple, VarPlan] = {}
+
+
+def var_scan_volume(ins, weights, scans):
+    """`scans` [(dim, causal, weight index), ...] with dim 0 = x, 1 = y, 2 = z on the device volumes `ins` (f32, one shape
+    (D, H, W)) with the weight volumes `weights`, through a cached `VarPlan.volume`; differentiable with respect to both, like
+    `var_scan`.  Element 0 of a weight volume along the scanned axis is never used.  Calls that share a plan are ordered by the
+    caller (one stream).  Returns a tuple of len(ins) volumes."""
+    import torch
+    ins, weights = list(ins), list(weights)
+    shape = tuple(int(s) for s in ins[0].shape)
+    if len(shape) != 3 or any(tuple(t.shape) != shape for t in ins + weights):
+        raise ValueError("var_scan_volume takes 3-D volumes (D, H, W) of one shape")
+    device = ins[0].device.index if ins[0].device.index is not None else torch.cuda.current_device()
+    key = (shape, tuple((int(d), bool(c), int(k)) for d, c, k in scans), len(ins), len(weights), device)
+    plan = _volume_plans.get(key)
+    if plan is None:
+        plan = _volume_plans[key] = VarPlan.volume(key[0], key[1], planes=len(ins), n_weights=len(weights), device=device)
+    with torch.cuda.device(ins[0].device):
+        return plan.apply(ins, weights)
+
+
 _signal_plans: Dict[tuple, VarPlan] = {}
 
 
@@ -442,6 +502,33 @@ def domain_transform_distances(guide, sigma_s: float, sigma_r: float, stream=Non
     return dx, dy
 
 
+def domain_transform_distances_volume(guide, sigma_s: float, sigma_r: float, spacing_z: float = 1.0, stream=None):
+    """(d_x, d_y, d_z): the exponent volumes of the domain-transform filter for a device guide volume (C, D, H, W) or (D, H, W),
+    f32 or uint8, by rf_var_distances_volume (one HIP launch, one read of the guide).  d_x and d_y are, slice by slice, what
+    `domain_transform_distances` gives;
+        d_z[z][r][c] = spacing_z + scale * sum_ch |g_ch[z][r][c] - g_ch[z-1][r][c]|     (slice 0 holds spacing_z)
+    with scale as there.  spacing_z > 0 is the sample distance along z in units of the x/y pitch (slice thickness, or how far
+    apart two frames count); 1 = isotropic.  W must be a multiple of 4.  Asynchronous on `stream`."""
+    import torch
+    g = guide if guide.dim() == 4 else guide.unsqueeze(0)
+    if g.dim() != 4:
+        raise ValueError(f"guide must be (C, D, H, W) or (D, H, W), got {tuple(guide.shape)}")
+    if g.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"float32 or uint8 guides only, got {g.dtype}")
+    if not g.is_cuda:
+        raise ValueError("the guide must be a device tensor")
+    g = g.contiguous()
+    C, D, H, W = (int(s) for s in g.shape)
+    u8 = g.dtype == torch.uint8
+    scale = float(sigma_s) / float(sigma_r) / (255.0 if u8 else 1.0)
+    volumes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
+    dx, dy, dz = (torch.empty((D, H, W), dtype=torch.float32, device=g.device) for _ in range(3))
+    with torch.cuda.device(g.device):
+        capi.check(capi.lib().rf_var_distances_volume(volumes, C, int(u8), W, H, D, scale, float(spacing_z), dx.data_ptr(), dy.data_ptr(),
+                                                      dz.data_ptr(), g.device.index, VarPlan._stream(stream)))
+    return dx, dy, dz
+
+
 def domain_transform_distances_backward(guide, sigma_s: float, sigma_r: float, grad_dx, grad_dy, grad_guide=None, accumulate: bool = False,
                                         stream=None):
     """rf_var_distances_backward: the gradient of an f32 device guide (C, H, W) or (H, W) from the gradients of the two planes of
@@ -521,6 +608,42 @@ class SmoothPlan(_PlanHandle):
             b.guide_stride = d.n_guide * d.height * d.width
             capi.check(capi.lib().rf_smooth_plan_create_batched(ctypes.byref(d), ctypes.byref(b), ctypes.byref(self._h)))
 
+    @classmethod
+    def volume(cls, shape_dhw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
+               iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, spacing_z: float = 1.0, device: int = -1) -> "SmoothPlan":
+        """rf_smooth_plan_create_volume: the filter along x, y and z of `planes` volumes of `shape_dhw` = (depth, height, width),
+        f32 or uint8 (bytes in, bytes out, as for images).  The plan owns three distance volumes: one var_distances_volume
+        launch, then 9 launches per iteration (+x -x, +y -y, +z -z).  spacing_z > 0: the sample distance along z in units of the
+        x/y pitch.  execute / execute_timed take (C, D, H, W) or (D, H, W) tensors (or lists of (D, H, W) volumes); backward is
+        refused by the library (RF_ERR_UNSUPPORTED); there is no batch of volumes."""
+        import torch
+        self = cls.__new__(cls)
+        shape_dhw = tuple(int(s) for s in shape_dhw)
+        if len(shape_dhw) != 3:
+            raise ValueError(f"shape_dhw must be (depth, height, width), got {shape_dhw}")
+        image_dtype = torch.float32 if image_dtype is None else image_dtype
+        guide_dtype = torch.float32 if guide_dtype is None else guide_dtype
+        for what, dt in (("image", image_dtype), ("guide", guide_dtype)):
+            if dt not in (torch.float32, torch.uint8):
+                raise TypeError(f"{what}_dtype must be torch.float32 or torch.uint8, got {dt}")
+        d = capi.SmoothVolumeDesc()
+        d.abi = capi.RF_ABI
+        d.image_u8 = int(image_dtype == torch.uint8)
+        d.depth, d.height, d.width = shape_dhw
+        d.n_planes, d.n_guide = int(planes), int(guide_planes)
+        d.guide_u8 = int(guide_dtype == torch.uint8) if d.n_guide != 0 else 0
+        d.iterations = int(iterations)
+        d.sigma_s, d.sigma_r, d.spacing_z = float(sigma_s), float(sigma_r), float(spacing_z)
+        d.device = int(device)
+        d.flags = 0
+        self._desc = d
+        self.shape, self.planes, self.guide_planes, self.iterations = shape_dhw, int(planes), int(guide_planes), int(iterations)
+        self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
+        self.batch = None
+        self._h = ctypes.c_void_p()
+        capi.check(capi.lib().rf_smooth_plan_create_volume(ctypes.byref(d), ctypes.byref(self._h)))
+        return self
+
     # -- queries ----------------------------------------------------------------------------
     @property
     def workspace_bytes(self) -> int:
@@ -553,9 +676,10 @@ class SmoothPlan(_PlanHandle):
                 raise ValueError(f"{what} must be a contiguous device tensor")
             return (ctypes.c_void_p * count)(*[tensor[0, c].data_ptr() for c in range(count)])
         if hasattr(tensor, "dim"):
-            tensor = [tensor] if tensor.dim() == 2 else [tensor[c] for c in range(tensor.shape[0])] if tensor.dim() == 3 else None
+            nd = len(self.shape)      # 2, or 3 for a volume plan: one plane, or a stack of planes
+            tensor = [tensor] if tensor.dim() == nd else [tensor[c] for c in range(tensor.shape[0])] if tensor.dim() == nd + 1 else None
             if tensor is None:
-                raise ValueError(f"{what} must be (C, H, W) or (H, W)")
+                raise ValueError(f"{what} must be (C, H, W) or (H, W)" if nd == 2 else f"{what} must be (C, D, H, W) or (D, H, W)")
         if len(tensor) != count:
             raise ValueError(f"expected {count} {what} planes, got {len(tensor)}")
         arr = (ctypes.c_void_p * count)()
@@ -681,6 +805,47 @@ def _smooth_function():
 
     _smooth_fn = SmoothFunction
     return _smooth_fn
+
+
+_smooth_volume_plans: Dict[tuple, SmoothPlan] = {}
+
+
+def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, spacing_z: float = 1.0):
+    """Edge-aware smoothing of a device volume (C, D, H, W) or (D, H, W), f32 or uint8, by the domain-transform recursive filter
+    along x, y and z, through a cached `SmoothPlan.volume` (keyed by shape, dtypes, iterations, sigmas, spacing_z and device): per
+    iteration +x -x, +y -y, +z -z on the three exponent volumes of `domain_transform_distances_volume`.  guide=None: the volume
+    guides itself; else a guide (G, D, H, W) or (D, H, W), f32 or uint8.  spacing_z > 0 is the sample distance along z in units
+    of the x/y pitch -- slice thickness of a CT/MR stack, or how far apart two video frames count; 1 = isotropic.  The result
+    has the volume's dtype (uint8: sat8 of the f32 filter on the bytes).  Not differentiable.  W must be a multiple of 4; calls
+    that share a plan are ordered by the caller (one stream)."""
+    import torch
+    vol = volume if volume.dim() == 4 else volume.unsqueeze(0)
+    if vol.dim() != 4:
+        raise ValueError(f"volume must be (C, D, H, W) or (D, H, W), got {tuple(volume.shape)}")
+    if vol.dtype != torch.uint8:
+        vol = vol.to(torch.float32)
+    vol = vol.contiguous()
+    g = None
+    if guide is not None:
+        g = guide if guide.dim() == 4 else guide.unsqueeze(0)
+        if g.dim() != 4:
+            raise ValueError(f"guide must be (G, D, H, W) or (D, H, W), got {tuple(guide.shape)}")
+        if g.dtype != torch.uint8:
+            g = g.to(torch.float32)
+        g = g.to(vol.device).contiguous()
+        if tuple(g.shape[1:]) != tuple(vol.shape[1:]):
+            raise ValueError("guide and volume must have the same depth, height and width")
+    shape = tuple(int(s) for s in vol.shape)
+    device = vol.device.index if vol.device.index is not None else torch.cuda.current_device()
+    key = shape + (vol.dtype, None if g is None else (int(g.shape[0]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), float(spacing_z), device)
+    plan = _smooth_volume_plans.get(key)
+    if plan is None:
+        plan = _smooth_volume_plans[key] = SmoothPlan.volume(shape[1:], planes=shape[0], guide_planes=0 if g is None else int(g.shape[0]),
+                                                             image_dtype=vol.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
+                                                             sigma_s=sigma_s, sigma_r=sigma_r, spacing_z=spacing_z, device=device)
+    with torch.cuda.device(vol.device):
+        out = plan.execute(vol, g)
+    return out if volume.dim() == 4 else out[0]
 
 
 _SMOOTH_SCANS = [(0, True, 0), (0, False, 0), (1, True, 1), (1, False, 1)]      # +x -x on weights 0, +y -y on weights 1
