@@ -931,13 +931,28 @@ inline void domain_transform_distances_gradient(const std::vector<const void *> 
                                   grad_guide_planes.data(), accumulate ? 1 : 0, -1, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
 }
 
+/** The adjoint of domain_transform_distances_volume for f32 guide volumes (rf_var_distances_volume_backward): the guide's gradient
+ *  from those of d_x, d_y and d_z (spacing_z does not enter), stored to grad_guide_volumes or (accumulate) added to what they hold.
+ *  One launch on `stream`. */
+inline void domain_transform_distances_volume_gradient(const std::vector<const void *> &guide_volumes, int64_t width, int64_t height, int64_t depth,
+                                                       float scale, const void *grad_dx, const void *grad_dy, const void *grad_dz,
+                                                       const std::vector<void *> &grad_guide_volumes, bool accumulate = false,
+                                                       void *stream = nullptr) {
+    if (guide_volumes.size() != grad_guide_volumes.size())
+        throw RecFilterError("domain_transform_distances_volume_gradient: one gradient volume per guide volume");
+    if (rf_var_distances_volume_backward(guide_volumes.data(), (int32_t)guide_volumes.size(), width, height, depth, scale, grad_dx, grad_dy, grad_dz,
+                                         grad_guide_volumes.data(), accumulate ? 1 : 0, -1, stream) != RF_OK)
+        throw RecFilterError(rf_last_error_string());
+}
+
 /** Edge-aware smoothing as one object (recfilter_amd.h, rf_smooth_plan_*): the domain-transform recursive filter of `planes`
  *  dense device planes of width x height, f32 or uint8 (bytes in AND out: sat8 of the f32 filter on the widened bytes, rounded
  *  once, at the final store).  guide_planes = 0: the image guides itself; else that many separate guide planes, f32 or uint8 (a
  *  byte guide means that guide divided by 255).  The library owns the distance planes and sequences 1 + 6 K launches.
  *      RecFilterSmooth F(width, height, 3, 0, false, true, 3, 60.0, 0.4);      // an RGB byte image guiding itself
  *      F.realize({r, g, b}, {}, {r, g, b});                                      // device pointers; in == out is allowed
- *  f32 images are differentiable: F.gradient(image, guide, grad_out, grad_image, grad_guide, edges) (rf_smooth_plan_backward).
+ *  f32 images are differentiable: F.gradient(image, guide, grad_out, grad_image, grad_guide, edges) (rf_smooth_plan_backward);
+ *  f32 volumes are where differentiable() was called before first use.
  *  The plan is built on first use and kept; it owns one workspace: order the realizations of one object. */
 class RecFilterSmooth {
     rf_smooth_desc desc{};
@@ -946,6 +961,7 @@ class RecFilterSmooth {
     bool batched = false;
     int64_t depth = 0;             // > 0: a volume (rf_smooth_plan_create_volume)
     double spacing_z = 1.0;
+    bool volume_backward = false;  // differentiable(): RF_SMOOTH_VOLUME_BACKWARD
     void prepare() {
         if (plan) return;
         int rc;
@@ -965,7 +981,7 @@ class RecFilterSmooth {
             vd.sigma_r = desc.sigma_r;
             vd.spacing_z = spacing_z;
             vd.device = desc.device;
-            vd.flags = desc.flags;
+            vd.flags = volume_backward ? RF_SMOOTH_VOLUME_BACKWARD : 0;
             rc = rf_smooth_plan_create_volume(&vd, &plan);
         } else {
             rc = batched ? rf_smooth_plan_create_batched(&desc, &batch_desc, &plan) : rf_smooth_plan_create(&desc, &plan);
@@ -974,8 +990,8 @@ class RecFilterSmooth {
     }
 public:
     /** The filter along x, y and z of volumes [z][y][x] (rf_smooth_plan_create_volume): a "plane" of realize() is a dense volume,
-     *  f32 or uint8; spacing_z > 0 is the sample distance along z in units of the x/y pitch.  1 + 9 K launches; gradient() is
-     *  refused by the library; no batch. */
+     *  f32 or uint8; spacing_z > 0 is the sample distance along z in units of the x/y pitch.  1 + 9 K launches; no batch.
+     *  gradient() is refused by the library unless differentiable() was called before first use. */
     RecFilterSmooth(int64_t width, int64_t height, int64_t depth_, int planes, int guide_planes, bool guide_u8, bool image_u8, int iterations,
                     double sigma_s, double sigma_r, double spacing_z_)
         : RecFilterSmooth(width, height, planes, guide_planes, guide_u8, image_u8, iterations, sigma_s, sigma_r) {
@@ -1013,6 +1029,15 @@ public:
         batched = true;
         return *this;
     }
+    /** Before first use, on a volume filter of f32 volumes: the plan is created with RF_SMOOTH_VOLUME_BACKWARD, so gradient() and
+     *  gradient_num_kernels() work on it (1 + 18 K launches, 51 K - 7 with edges; the workspace of edges is allocated by the first
+     *  such call).  realize() is unchanged, bit for bit.  The library refuses the flag for uint8 volumes. */
+    RecFilterSmooth &differentiable() {
+        if (plan) throw RecFilterError("differentiable: set before the first realize, gradient or query");
+        if (depth < 1) throw RecFilterError("differentiable: an image filter has its gradient already; this is for the volume constructor");
+        volume_backward = true;
+        return *this;
+    }
     /** image / out: one device plane per channel; guide: the separate guide planes, empty when the image guides itself.
      *  Asynchronous on `stream`. */
     void realize(const std::vector<const void *> &image, const std::vector<const void *> &guide, const std::vector<void *> &out,
@@ -1046,6 +1071,7 @@ public:
                                     grad_image.data(), grad_guide.empty() ? nullptr : grad_guide.data(), edges ? 1 : 0, stream) != RF_OK)
             throw RecFilterError(rf_last_error_string());
     }
-    /** launches of gradient(): 1 + 12 K, or 34 K - 4 with edges */
+    /** launches of gradient(): 1 + 12 K, or 34 K - 4 with edges; a differentiable() volume filter: 1 + 18 K, or 51 K - 7; a volume
+     *  filter without it: 0 */
     int gradient_num_kernels(bool edges) { prepare(); return rf_smooth_plan_backward_num_kernels(plan, edges ? 1 : 0); }
 };

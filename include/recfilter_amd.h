@@ -676,10 +676,29 @@ int    rf_var_plan_create_volume(const rf_var_volume_desc *desc, rf_var_plan **p
  * spacing_z, finite and > 0, is the sample distance along z in units of the x/y pitch (slice thickness; how far apart two frames
  * count); 1 = isotropic.  Refusals as rf_var_distances, with the volume domain of rf_var_plan_create_volume (n_planes = 1) in the
  * place of the 2-D extent check, a spacing_z that is not finite and positive (RF_ERR_INVALID_ARG, behind the scale check), and dz
- * in every alignment and overlap check.  There is no adjoint of this launch. */
+ * in every alignment and overlap check.  Its adjoint for f32 guides is rf_var_distances_volume_backward. */
 int    rf_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height,
                                int64_t depth, float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device,
                                void *stream);
+/* The adjoint of rf_var_distances_volume for f32 guide volumes: from grad_dx, grad_dy, grad_dz = dL/d(d_x), dL/d(d_y), dL/d(d_z), per
+ * channel, in f32 with the six terms in this order,
+ *     gg[ch][z][r][c] = scale * ( ((((L - R) + U) - Dn) + B) - A )
+ *     L  = sx(z,r,c) * gdx[z][r][c]        R  = sx(z,r,c+1) * gdx[z][r][c+1]
+ *     U  = sy(z,r,c) * gdy[z][r][c]        Dn = sy(z,r+1,c) * gdy[z][r+1][c]
+ *     B  = sz(z,r,c) * gdz[z][r][c]        A  = sz(z+1,r,c) * gdz[z+1][r][c]
+ *     sx(z,r,c) = sgn(g[z][r][c] - g[z][r][c-1]) for 1 <= c < W, else 0;   sy, sz likewise along rows and slices;   sgn(0) = 0
+ * (a constant guide gets a gradient of exactly 0; spacing_z is an additive constant of d_z and does not enter).  The signs are
+ * applied by selects and the terms outside the volume are selected away: gdx[..][..][0], gdy[..][0][..] and gdz[0] are never part
+ * of a result (a NaN there reaches nothing).  With grad_dz = 0 a slice receives the values rf_var_distances_backward gives on it.
+ * accumulate = 0: stored to grad_guide_volumes; 1: added to what they hold.  One launch ("var_distances_volume_grad"), a gather: no
+ * atomics, two runs agree bit for bit.  There is no entry point for byte guides.
+ * Decided before any HIP call: the refusals of rf_var_distances_volume for f32 guides (n_guide, extents below 1, null pointers --
+ * the three gradient inputs, grad_guide_volumes and its entries included --, the scale, the volume domain with n_planes = 1); then
+ * accumulate other than 0 or 1, volumes not 16-byte aligned, a gradient volume that overlaps grad_dx, grad_dy, grad_dz, a guide
+ * volume or another gradient volume (RF_ERR_INVALID_ARG; the message names the volumes). */
+int    rf_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth,
+                                        float scale, const void *grad_dx, const void *grad_dy, const void *grad_dz,
+                                        void *const *grad_guide_volumes, int32_t accumulate, int32_t device, void *stream);
 /* The distance planes of the domain-transform filter from a guide image of n_guide dense planes of width x height:
  *     d_x[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r][c-1]|   (c >= 1;  d_x[r][0] = 1)
  *     d_y[r][c] = 1 + scale * sum_ch |g_ch[r][c] - g_ch[r-1][c]|   (r >= 1;  d_y[0][c] = 1)
@@ -835,9 +854,28 @@ int    rf_smooth_plan_create_batched(const rf_smooth_desc *desc, const rf_smooth
  * caller's bytes, the iterations run on n_planes plan-owned f32 volumes, the last z pass stores sat8; no conversion launch.
  * spacing_z: the sample distance along z in units of the x/y pitch, finite and > 0 (1 = isotropic).
  * Create refuses what rf_smooth_plan_create refuses, with the domain of rf_var_plan_create_volume in the place of the 2-D extent
- * checks and a spacing_z that is not finite and positive (RF_ERR_INVALID_ARG).  rf_smooth_plan_backward and _backward_timed on a
- * volume plan return RF_ERR_UNSUPPORTED (the distances of a volume have no adjoint); rf_smooth_plan_backward_num_kernels and
- * _backward_workspace_bytes return 0.  There is no batch of volumes. */
+ * checks and a spacing_z that is not finite and positive (RF_ERR_INVALID_ARG).  Without RF_SMOOTH_VOLUME_BACKWARD in flags,
+ * rf_smooth_plan_backward and _backward_timed on a volume plan return RF_ERR_UNSUPPORTED, and rf_smooth_plan_backward_num_kernels
+ * and _backward_workspace_bytes return 0.  There is no batch of volumes.
+ * flags = RF_SMOOTH_VOLUME_BACKWARD (f32 volumes; with image_u8 = 1 create returns RF_ERR_UNSUPPORTED; any other bit is
+ * RF_ERR_INVALID_ARG): the plan has a backward.  Its forward is the unflagged plan's -- the same launches, the same
+ * rf_smooth_plan_workspace_bytes, the same bits -- and nothing more is allocated at create.  rf_smooth_plan_backward and
+ * _backward_timed then run the sequence documented above one dimension up, with the same rules, refusals and order of refusals:
+ *     edges = 0   "var_distances_volume", then for k = K-1 .. 0 the adjoint stages of -z +z -y +y -x +x in the power form with
+ *                 {a_k, a_k, a_k}: 1 + 18 K launches; bit for bit K calls of rf_var_plan_backward_power on the volume plan in
+ *                 reverse order.  grad_out[pl] == grad_image[pl] is allowed, a uint8 guide is allowed, no extra workspace.
+ *     edges = 1   "var_distances_volume"; the forward of iterations 0 .. K-2 (nine launches each), every output kept; for
+ *                 k = K-1 .. 0 the launches of rf_var_plan_backward_power with all three exponent gradients (7 * 6 = 42), the
+ *                 first touch of gd_x / gd_y / gd_z storing and the later ones adding; one "var_distances_volume_grad"
+ *                 (rf_var_distances_volume_backward) with the plan's scale: 51 K - 7 launches.  n_guide > 0: the gradient is
+ *                 stored to grad_guide_planes and grad_image has the bits of edges = 0; n_guide = 0: the last launch adds into
+ *                 grad_image_planes.  A uint8 guide is refused at the call (RF_ERR_UNSUPPORTED).
+ * Workspace at edges = 1, allocated by the first call that needs it (RF_ERR_NOMEM with the byte count in the message if that
+ * fails): 3 + (K - 1 + 7) * n_planes f32 volumes = rf_smooth_plan_backward_workspace_bytes(plan, 1) -- gd_x, gd_y, gd_z, K - 1
+ * checkpoints per plane, and the inner plan's (6 + 1) * n_planes; 0 for edges = 0.  A plan keeps no state across calls.
+ * Out of scope: byte and 16-bit volumes in the backward, byte-guide gradients, gradients of the sigmas, the bases or spacing_z,
+ * batches of volumes, sharding, double backward; the flag is not the default. */
+#define RF_SMOOTH_VOLUME_BACKWARD 1u   /* rf_smooth_volume_desc.flags: the plan has a backward (f32 volumes) */
 typedef struct {
     uint32_t abi;                     /* RF_ABI                                                  */
     int32_t  image_u8;                /* 0: f32 volumes; 1: uint8 volumes, in AND out            */
@@ -849,7 +887,7 @@ typedef struct {
     double   sigma_s, sigma_r;        /* finite, > 0                                             */
     double   spacing_z;               /* finite, > 0; 1 = isotropic                              */
     int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
-    uint32_t flags;                   /* 0                                                       */
+    uint32_t flags;                   /* 0, or RF_SMOOTH_VOLUME_BACKWARD                         */
 } rf_smooth_volume_desc;
 int    rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth_plan **plan_out);
 

@@ -12,7 +12,7 @@ from .filter import (Pointwise, RecFilter, RecFilterDim, RecFilterDimAndCausalit
 from .plan import (Plan, box_difference, tap_filter, stream_copy_ms, gaussian_box_filter, second_order_sections, gaussian_weights, integral_image_coeff,
                    overlap_feedback_coeff, recursive_filter)
 from .varscan import (SmoothPlan, VarPlan, domain_transform_bases, domain_transform_distances, domain_transform_distances_backward,
-                      domain_transform_distances_volume, domain_transform_weights, edge_aware_smooth, edge_aware_smooth_volume, smooth_samples,
+                      domain_transform_distances_volume, domain_transform_distances_volume_backward, domain_transform_weights, edge_aware_smooth, edge_aware_smooth_volume, smooth_samples,
                       var_scan, var_scan_signal, var_scan_volume)
 
 __all__ = [
@@ -21,5 +21,5 @@ __all__ = [
     "integral_image_coeff", "overlap_feedback_coeff", "VarPlan", "domain_transform_weights", "edge_aware_smooth",
     "domain_transform_bases", "domain_transform_distances", "SmoothPlan", "var_scan", "var_scan_signal", "smooth_samples",
     "domain_transform_distances_backward", "recursive_filter", "var_scan_volume", "domain_transform_distances_volume",
-    "edge_aware_smooth_volume",
+    "edge_aware_smooth_volume", "domain_transform_distances_volume_backward",
 ]

@@ -24,6 +24,7 @@ RF_VAR_MAX_SCANS = 8     # scans (and weight planes) of a plan of spatially vary
 RF_SMOOTH_MAX_ITERATIONS = 8     # iterations of a smoothing plan (rf_smooth_desc)
 RF_SMOOTH_MAX_BATCH = 1024       # images of a batched smoothing plan (rf_smooth_batch_desc)
 RF_DEVICE_HOST_ONLY = -2
+RF_SMOOTH_VOLUME_BACKWARD = 1    # rf_smooth_volume_desc.flags: the volume plan has a backward (f32 volumes)
 
 RF_OK, RF_ERR_INVALID_ARG, RF_ERR_UNSUPPORTED, RF_ERR_HIP, RF_ERR_NOMEM, RF_ERR_STATE = range(6)
 RF_F32, RF_F64, RF_I32, RF_I16, RF_F16, RF_BF16 = range(6)      # RF_F16 / RF_BF16: 16-bit float STORAGE, f32 arithmetic
@@ -77,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "rf_plan_backward", "rf_plan_backward_timed", "rf_plan_backward_num_kernels", "rf_plan_backward_workspace_bytes",
     "rf_var_plan_create_signal",
     "rf_var_plan_create_volume", "rf_var_distances_volume", "rf_smooth_plan_create_volume",
+    "rf_var_distances_volume_backward",
 ]
 
 
@@ -226,6 +228,8 @@ def lib() -> ctypes.CDLL:
     L.rf_var_distances_volume.argtypes = [vpp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                           ctypes.c_float, ctypes.c_float, vp, vp, vp, ctypes.c_int32, vp]
     L.rf_smooth_plan_create_volume.argtypes = [ctypes.POINTER(SmoothVolumeDesc), vpp]
+    L.rf_var_distances_volume_backward.argtypes = [vpp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
+                                                   vp, vp, vp, vpp, ctypes.c_int32, ctypes.c_int32, vp]
     L.rf_var_plan_destroy.argtypes = [vp]
     L.rf_var_plan_workspace_bytes.argtypes = [vp]
     L.rf_var_plan_workspace_bytes.restype = ctypes.c_size_t

@@ -684,6 +684,15 @@ int rf_var_distances_backward(const void *const *guide_planes, int32_t n_guide, 
     });
 }
 
+int rf_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth,
+                                     float scale, const void *grad_dx, const void *grad_dy, const void *grad_dz,
+                                     void *const *grad_guide_volumes, int32_t accumulate, int32_t device, void *stream) {
+    return fenced("rf_var_distances_volume_backward", [&] {
+        return run_var_distances_volume_backward(guide_volumes, n_guide, width, height, depth, scale, grad_dx, grad_dy, grad_dz, grad_guide_volumes,
+                                                 accumulate, device, (hipStream_t)stream);
+    });
+}
+
 // ---- edge-aware smoothing as one plan (plan_smooth.cpp) -----------------------------------------------------------------------
 int rf_smooth_plan_create(const rf_smooth_desc *desc, rf_smooth_plan **plan_out) {
     return fenced("rf_smooth_plan_create", [&] { return build_smooth_plan(desc, nullptr, plan_out); });
@@ -748,7 +757,7 @@ int rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *image
     return fenced("rf_smooth_plan_backward_timed", [&] {
         if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
         if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return (int)RF_ERR_INVALID_ARG; }
-        if (plan->volume) return refuse_volume_backward();
+        if (!plan->has_backward()) return refuse_volume_backward();
         const std::vector<std::string> &names = plan->backward_names[edges];
         if (int rc = timed_names(names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, ms_out);

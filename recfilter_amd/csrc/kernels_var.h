@@ -109,6 +109,24 @@ struct VarDistGradArgs {
     int64_t guide_stride, grad_guide_stride;
 };
 
+// The adjoint of var_distances_volume (kernels_var.hip, var_distances_volume_grad), f32 guides: per channel, the six terms in this
+// order,
+//   grad_guide[ch][z][r][c] = scale * (((((L - R) + U) - Dn) + B) - A)
+//   L = sx(z,r,c) gdx[z][r][c]   R = sx(z,r,c+1) gdx[z][r][c+1]   U = sy(z,r,c) gdy[z][r][c]   Dn = sy(z,r+1,c) gdy[z][r+1][c]
+//   B = sz(z,r,c) gdz[z][r][c]   A = sz(z+1,r,c) gdz[z+1][r][c]
+// sx / sy / sz: the sign of the guide's difference to the left / above / one slice before (0 for a difference of 0 and outside
+// the volume).  spacing_z is an additive constant of d_z and does not enter.  accumulate: added to what the volumes hold, else
+// stored.  The grid is var_distances_volume's: a lane owns four adjacent columns of one row and walks kVarDistSlices slices.
+struct VarDistVolumeGradArgs {
+    const float *guide[RF_MAX_PLANES];
+    float *grad_guide[RF_MAX_PLANES];
+    const float *gdx, *gdy, *gdz;
+    int32_t width, height, depth;   // x fastest; the width is a multiple of 4
+    int32_t n_guide;
+    int32_t accumulate;
+    float scale;
+};
+
 // dim 2 (a z stage of a volume plan, plan_var.cpp): the y kernels on the view the arguments describe -- width = lines = the voxel
 // columns, height = the depth -- under the names "var_*_z"
 int launch_var_tails(const VarArgs &a, int dim, hipStream_t stream);
@@ -125,5 +143,6 @@ int launch_var_distances(const VarDistArgs &a, bool guide_u8, hipStream_t stream
 int launch_var_distances_volume(const VarDistVolumeArgs &a, bool guide_u8, hipStream_t stream);
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream);
 int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream);
+int launch_var_distances_volume_grad(const VarDistVolumeGradArgs &a, hipStream_t stream);
 
 }  // namespace rf

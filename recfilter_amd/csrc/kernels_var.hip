@@ -56,7 +56,8 @@
 //
 // Volumes (rf_var_plan_create_volume, plan_var.cpp) run these kernels as they are: the slices of an x or y stage are the batch, and
 // a z stage is var_y_kernel / var_grad_kernel<1, ...> on the (width * height) x depth view -- the launchers take dim = 2 for it and
-// differ in the name they report.  var_distances_volume is the one kernel volumes add.
+// differ in the name they report.  var_distances_volume and its adjoint var_distances_volume_grad
+// (rf_var_distances_volume_backward) are the two kernels volumes add.
 #include "kernels_var.h"
 
 #include "pixel.h"
@@ -556,6 +557,136 @@ __global__ void __launch_bounds__(256) var_distances_grad_kernel(VarDistGradArgs
     }
 }
 
+// ---- var_distances_volume_grad: lane = 4 adjacent columns of one row, walking z, as var_distances_volume -------------------------
+// A guide sample takes part in six differences: var_distances_grad's four in its slice, the one to the slice before (+) and the one
+// to the slice after (-).  Neighbours come from clamped addresses (the slice before slice 0 and after slice D-1: the slice itself)
+// and the terms they feed are selected away at the six faces.  The channels are independent and no array is indexed by the
+// channel, so nothing goes to scratch whatever n_guide is.  Two forms of the walk, one arithmetic (guide_gradient_chunk):
+//   ROLLING  the channel loop AROUND the walk: a lane keeps one channel's chunk of the slice before, its own and the slice after in
+//            registers, so the guide is read once (plus one slice per segment and the row neighbours) -- and gdx, gdy, gdz once
+//            PER CHANNEL.  One guide volume: every volume is read once.
+//   else     the channel loop INSIDE the walk: gdx, gdy and gdz of a slice are loaded once for all channels (gdz rolls along z in
+//            registers) and a channel's chunks of the slices before and after are read again from their clamped addresses, as
+//            var_distances_grad reads the rows above and below -- the second and third touch of a slice follow the first by one
+//            and two steps of the walk.  More than one guide volume.
+struct VolumeLane {
+    int r, c;
+    bool has_right, has_down;
+    int64_t slice, own_row, up_row, down_row, left_row, right_row;
+};
+__device__ __forceinline__ bool volume_lane(const VarDistVolumeGradArgs &a, VolumeLane &l) {
+    const int chunks = a.width / 4;
+    const int64_t flat = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (flat >= (int64_t)chunks * a.height) return false;
+    l.r = (int)(flat / chunks);
+    l.c = (int)(flat - (int64_t)l.r * chunks) * 4;
+    l.has_right = l.c + 4 < a.width;
+    l.has_down = l.r + 1 < a.height;
+    l.slice = (int64_t)a.width * a.height;
+    l.own_row = (int64_t)l.r * a.width + l.c;
+    l.up_row = (int64_t)max(l.r - 1, 0) * a.width + l.c;
+    l.down_row = (int64_t)min(l.r + 1, a.height - 1) * a.width + l.c;
+    l.left_row = l.own_row - (l.c > 0 ? 1 : 0);
+    l.right_row = l.own_row + (l.has_right ? 4 : 3);
+    return true;
+}
+
+// the gradients a slice's differences received, of the lane's chunk: gx[4] belongs to the difference to the right of the chunk
+struct SliceGradients {
+    float gx[5], gy[4], gy_down[4];
+};
+__device__ __forceinline__ void load_slice_gradients(const VarDistVolumeGradArgs &a, const VolumeLane &l, int64_t at, SliceGradients &s) {
+    float gx_own[4];
+    load_chunk(a.gdx, at + l.own_row, gx_own);
+#pragma unroll
+    for (int j = 0; j < 4; j++) s.gx[j] = gx_own[j];
+    s.gx[4] = a.gdx[at + l.right_row];
+    load_chunk(a.gdy, at + l.own_row, s.gy);
+    load_chunk(a.gdy, at + l.down_row, s.gy_down);
+}
+
+// one channel's chunk of slice z (at = z * slice): the six terms in the header's order, stored or added
+__device__ __forceinline__ void guide_gradient_chunk(const VarDistVolumeGradArgs &a, const VolumeLane &l, const float *g, float *dst, int z, int64_t at,
+                                                     const float (&before)[4], const float (&chunk)[4], const float (&after)[4],
+                                                     const SliceGradients &s, const float (&gz)[4], const float (&gz_after)[4]) {
+    const bool has_after = z + 1 < a.depth;
+    float own[6], up[4], down[4], out[4];      // own[0]: the element to the left, own[5]: the one to the right
+#pragma unroll
+    for (int j = 0; j < 4; j++) own[j + 1] = chunk[j];
+    own[0] = g[at + l.left_row];
+    own[5] = g[at + l.right_row];
+    load_chunk(g, at + l.up_row, up);
+    load_chunk(g, at + l.down_row, down);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float from_left = l.c + j > 0 ? signed_by(own[j + 1] - own[j], s.gx[j]) : 0.0f;
+        const float from_right = (j < 3 || l.has_right) ? signed_by(own[j + 2] - own[j + 1], s.gx[j + 1]) : 0.0f;
+        const float from_up = l.r > 0 ? signed_by(own[j + 1] - up[j], s.gy[j]) : 0.0f;
+        const float from_down = l.has_down ? signed_by(down[j] - own[j + 1], s.gy_down[j]) : 0.0f;
+        const float from_before = z > 0 ? signed_by(chunk[j] - before[j], gz[j]) : 0.0f;
+        const float from_after = has_after ? signed_by(after[j] - chunk[j], gz_after[j]) : 0.0f;
+        out[j] = a.scale * (((((from_left - from_right) + from_up) - from_down) + from_before) - from_after);
+    }
+    if (a.accumulate) {
+        float old[4];
+        load_chunk(dst, at + l.own_row, old);
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[j] = old[j] + out[j];
+    }
+    *reinterpret_cast<float4 *>(dst + at + l.own_row) = make_float4(out[0], out[1], out[2], out[3]);
+}
+
+template <bool ROLLING>
+__global__ void __launch_bounds__(256) var_distances_volume_grad_kernel(VarDistVolumeGradArgs a) {
+    VolumeLane l;
+    if (!volume_lane(a, l)) return;
+    const int z0 = blockIdx.y * kVarDistSlices, z1 = min(z0 + kVarDistSlices, a.depth);
+    if constexpr (ROLLING) {
+        for (int ch = 0; ch < a.n_guide; ch++) {
+            const float *const g = a.guide[ch];
+            float before[4], chunk[4], gz[4];
+            load_chunk(g, (int64_t)max(z0 - 1, 0) * l.slice + l.own_row, before);
+            load_chunk(g, (int64_t)z0 * l.slice + l.own_row, chunk);
+            load_chunk(a.gdz, (int64_t)z0 * l.slice + l.own_row, gz);
+            for (int z = z0; z < z1; z++) {
+                const int64_t at = (int64_t)z * l.slice, after_at = (int64_t)min(z + 1, a.depth - 1) * l.slice;
+                float after[4], gz_after[4];
+                SliceGradients s;
+                load_chunk(g, after_at + l.own_row, after);
+                load_chunk(a.gdz, after_at + l.own_row, gz_after);
+                load_slice_gradients(a, l, at, s);
+                guide_gradient_chunk(a, l, g, a.grad_guide[ch], z, at, before, chunk, after, s, gz, gz_after);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    before[j] = chunk[j];
+                    chunk[j] = after[j];
+                    gz[j] = gz_after[j];
+                }
+            }
+        }
+    } else {
+        float gz[4];
+        load_chunk(a.gdz, (int64_t)z0 * l.slice + l.own_row, gz);
+        for (int z = z0; z < z1; z++) {
+            const int64_t at = (int64_t)z * l.slice, before_at = (int64_t)max(z - 1, 0) * l.slice, after_at = (int64_t)min(z + 1, a.depth - 1) * l.slice;
+            float gz_after[4];
+            SliceGradients s;
+            load_chunk(a.gdz, after_at + l.own_row, gz_after);
+            load_slice_gradients(a, l, at, s);
+            for (int ch = 0; ch < a.n_guide; ch++) {
+                const float *const g = a.guide[ch];
+                float before[4], chunk[4], after[4];
+                load_chunk(g, before_at + l.own_row, before);
+                load_chunk(g, at + l.own_row, chunk);
+                load_chunk(g, after_at + l.own_row, after);
+                guide_gradient_chunk(a, l, g, a.grad_guide[ch], z, at, before, chunk, after, s, gz, gz_after);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) gz[j] = gz_after[j];
+        }
+    }
+}
+
 int launched(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
@@ -674,6 +805,16 @@ int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)a.batch), block(256);
     hipLaunchKernelGGL(var_distances_grad_kernel, grid, block, 0, stream, a);
     return launched("var_distances_grad");
+}
+
+int launch_var_distances_volume_grad(const VarDistVolumeGradArgs &a, hipStream_t stream) {
+    const int64_t lanes = (int64_t)(a.width / 4) * a.height;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)((a.depth + kVarDistSlices - 1) / kVarDistSlices)), block(256);
+    // one guide volume: the rolling window reads every volume once; more: gdx, gdy, gdz once for all channels (each form forced on
+    // every case: profiles/r27/smooth_volume_grad.txt)
+    if (a.n_guide == 1) hipLaunchKernelGGL(var_distances_volume_grad_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(var_distances_volume_grad_kernel<false>, grid, block, 0, stream, a);
+    return launched("var_distances_volume_grad");
 }
 
 }  // namespace rf

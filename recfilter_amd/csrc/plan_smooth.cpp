@@ -23,7 +23,10 @@
 //
 // A volume plan (build_smooth_volume_plan, rf_smooth_plan_create_volume) is the same sequence one dimension up: three distance
 // volumes from one var_distances_volume launch (d_z from spacing_z), an inner volume plan +x -x +y -y +z -z with {a_k, a_k, a_k},
-// 1 + 9 K launches; bytes enter at the first x stage and leave at the last z pass.  No batch, and its backward is refused.
+// 1 + 9 K launches; bytes enter at the first x stage and leave at the last z pass.  No batch.  Created with
+// RF_SMOOTH_VOLUME_BACKWARD (f32 volumes) it has the backward too, run_smooth_backward one dimension up: three exponent volumes and
+// their gradients, the inner volume plan's adjoint with {a_k, a_k, a_k}, var_distances_volume_grad at the end -- 1 + 18 K launches
+// with the distances held constant, 51 K - 7 through them.  Without the flag its backward is refused.
 #include "plan_smooth.h"
 
 #include <algorithm>
@@ -152,7 +155,8 @@ int check_extents(const ExtentArray *arrays, int n_arrays, int batch) {
 }  // namespace
 
 namespace {
-int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, rf_smooth_plan **out);
+int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, bool volume_backward,
+                  rf_smooth_plan **out);
 }
 
 int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out) {
@@ -161,7 +165,7 @@ int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *ba
     int rc = batch ? validate_batch(desc, batch) : RF_OK;
     if (rc == RF_OK) rc = validate(desc);
     if (rc != RF_OK) return rc;
-    return build_checked(desc, batch, 0, 1.0f, out);
+    return build_checked(desc, batch, 0, 1.0f, false, out);
 }
 
 int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan **out) {
@@ -180,9 +184,19 @@ int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan *
     d.sigma_s = desc->sigma_s;
     d.sigma_r = desc->sigma_r;
     d.device = desc->device;
-    d.flags = desc->flags;
+    d.flags = 0;
+    // (any bit but the one flag a volume plan has: refused where an image's flags are, behind the revision check)
+    if (desc->abi == RF_ABI && (desc->flags & ~(uint32_t)RF_SMOOTH_VOLUME_BACKWARD) != 0) {
+        set_error("rf_smooth_volume_desc.flags must be 0 or RF_SMOOTH_VOLUME_BACKWARD (got %#x)", desc->flags);
+        return RF_ERR_INVALID_ARG;
+    }
     int rc = validate(&d);
     if (rc != RF_OK) return rc;
+    const bool backward = (desc->flags & RF_SMOOTH_VOLUME_BACKWARD) != 0;
+    if (backward && desc->image_u8) {
+        set_error("RF_SMOOTH_VOLUME_BACKWARD: the backward of a smoothing plan takes f32 volumes (image_u8 = 1)");
+        return RF_ERR_UNSUPPORTED;
+    }
     const float spacing_z = (float)desc->spacing_z;
     if (!std::isfinite(desc->spacing_z) || !std::isfinite(spacing_z) || !(spacing_z > 0.0f)) {
         set_error("spacing_z must be finite and positive in f32 (got %g)", desc->spacing_z);
@@ -190,21 +204,23 @@ int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan *
     }
     rc = check_volume_extents(desc->width, desc->height, desc->depth, desc->n_planes);
     if (rc != RF_OK) return rc;
-    return build_checked(&d, nullptr, desc->depth, spacing_z, out);
+    return build_checked(&d, nullptr, desc->depth, spacing_z, backward, out);
 }
 
 int refuse_volume_backward() {
-    set_error("the backward of a smoothing plan takes images: the distances of a volume (var_distances_volume) have no adjoint");
+    set_error("this volume plan has no backward: create it with RF_SMOOTH_VOLUME_BACKWARD in rf_smooth_volume_desc.flags");
     return RF_ERR_UNSUPPORTED;
 }
 
 namespace {
 
 // the plan of a description that has passed its checks; depth = 0: an image, else a volume
-int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, rf_smooth_plan **out) {
+int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, bool volume_backward,
+                  rf_smooth_plan **out) {
     int rc = RF_OK;
     std::unique_ptr<rf_smooth_plan> plan(new rf_smooth_plan);
     plan->volume = depth > 0;
+    plan->volume_backward = plan->volume && volume_backward;
     plan->depth = plan->volume ? depth : 1;
     plan->spacing_z = spacing_z;
     plan->width = desc->width;
@@ -282,16 +298,16 @@ int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch,
     plan->names.push_back(plan->volume ? "var_distances_volume" : "var_distances");
     for (int k = 0; k < K; k++)
         for (const std::string &n : inner->names) plan->names.push_back(n);
-    // the adjoint's launch lists (a volume plan has none: its backward is refused)
-    for (int edges = 0; edges < 2 && !plan->volume; edges++) {
+    // the adjoint's launch lists (a volume plan without RF_SMOOTH_VOLUME_BACKWARD has none: its backward is refused)
+    for (int edges = 0; edges < 2 && plan->has_backward(); edges++) {
         std::vector<std::string> &names = plan->backward_names[edges];
-        names.push_back("var_distances");
+        names.push_back(plan->names[0]);
         if (edges)
             for (int k = 0; k + 1 < K; k++)
                 for (const std::string &n : inner->names) names.push_back(n);
         for (int k = 0; k < K; k++)
             for (const std::string &n : inner->backward_names[edges]) names.push_back(n);
-        if (edges) names.push_back("var_distances_grad");
+        if (edges) names.push_back(plan->volume ? "var_distances_volume_grad" : "var_distances_grad");
     }
     *out = plan.release();
     return RF_OK;
@@ -380,7 +396,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
     if (!plan || !grad_out_planes || !grad_image_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return RF_ERR_INVALID_ARG; }
-    if (plan->volume) return refuse_volume_backward();
+    if (!plan->has_backward()) return refuse_volume_backward();
     if (plan->image_u8) { set_error("the backward of a smoothing plan takes f32 images (this plan's are uint8)"); return RF_ERR_UNSUPPORTED; }
     const bool self = plan->n_guide == 0;
     if (!self && !guide_planes) { set_error("this plan takes %d separate guide planes: guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }
@@ -401,7 +417,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     if (plan->host_only) { set_error("host-only plan (RF_DEVICE_HOST_ONLY) cannot execute"); return RF_ERR_HIP; }
     const int P = plan->n_planes, G = plan->n_guide, K = plan->iterations;
     const bool with_guide_grad = edges == 1 && !self;
-    const size_t samples = (size_t)(plan->width * plan->height), plane_bytes = samples * sizeof(float);
+    const size_t samples = (size_t)plan->samples(), plane_bytes = samples * sizeof(float);
     const size_t guide_bytes = samples * (plan->guide_u8 ? 1 : sizeof(float));
     int rc = RF_OK;
     for (int pl = 0; pl < P && rc == RF_OK; pl++)
@@ -450,35 +466,42 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     }
     LaunchTimer timer(stream, ms_out, plan->backward_names[edges].size());
     if (timer.status() != RF_OK) return timer.status();
-    float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each, as the gradients' gd_x, gd_y below
-    rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
-                           dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
+    // one plane per image each (a volume: B is 1, and a third, d_z), as the gradients' gd_x, gd_y (, gd_z) below
+    const int nd = plan->n_distances();
+    float *dx = plan->planes, *dy = dx + samples * (size_t)B, *dz = plan->volume ? dy + samples : nullptr;
+    if (plan->volume)
+        rc = run_var_distances_volume(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height,
+                                      plan->depth, plan->scale, plan->spacing_z, dx, dy, dz, plan->device, stream);
+    else
+        rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
+                               dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
     if (rc == RF_OK) rc = timer.mark();
     if (rc != RF_OK) return rc;
-    const void *const exponents[2] = {dx, dy};
-    float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples * (size_t)B : nullptr;
+    const void *const exponents[3] = {dx, dy, dz};
+    float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples * (size_t)B : nullptr, *gdz = gdx && plan->volume ? gdy + samples : nullptr;
+    float *const own = gdx ? gdx + samples * (size_t)B * (size_t)nd : nullptr;      // what follows the distance gradients
     // the output of iteration k, k = 0 .. K-2: [iteration][image][plane]
     const int64_t checkpoint_stride = (int64_t)samples * P;
     void *checkpoints[RF_SMOOTH_MAX_ITERATIONS][RF_MAX_PLANES] = {};
     if (edges == 1) {
         for (int k = 0; k + 1 < K; k++) {
-            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = gdy + samples * ((size_t)B + (size_t)k * (size_t)B * P + pl);
+            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = own + samples * ((size_t)k * (size_t)B * P + pl);
             VarIo io{};
             io.in = k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
             io.work = io.out = checkpoints[k];
             io.in_stride = k == 0 ? image_stride : checkpoint_stride;
             io.work_stride = io.out_stride = checkpoint_stride;
             io.weights_stride = (int64_t)samples;
-            const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
+            const float l[3] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
             rc = launch_var_stages(inner, io, exponents, l, stream, timer);
             if (rc != RF_OK) return rc;
         }
     }
-    void *const grad_exponents[2] = {gdx, gdy};
+    void *const grad_exponents[3] = {gdx, gdy, gdz};
     for (int k = K - 1; k >= 0; k--) {
-        const float l[2] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-        const float c[2] = {plan->ln_bases[(size_t)k], plan->ln_bases[(size_t)k]};
-        const bool holds_sum[2] = {k < K - 1, k < K - 1};
+        const float l[3] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
+        const float c[3] = {plan->ln_bases[(size_t)k], plan->ln_bases[(size_t)k], plan->ln_bases[(size_t)k]};
+        const bool holds_sum[3] = {k < K - 1, k < K - 1, k < K - 1};
         VarBackwardIo io{};
         io.in = edges == 0 ? nullptr : k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
         io.weights = exponents;
@@ -491,14 +514,18 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         io.in_stride = k == 0 ? image_stride : checkpoint_stride;
         io.weights_stride = io.grad_weights_stride = (int64_t)samples;
         io.grad_out_stride = io.grad_in_stride = image_stride;
-        rc = launch_var_backward(inner, io, stream, timer);      // (both exponent gradients are always formed: nothing is skipped)
+        rc = launch_var_backward(inner, io, stream, timer);      // (every exponent gradient is always formed: nothing is skipped)
         if (rc != RF_OK) return rc;
     }
     if (edges == 1) {
         // a separate guide: stored; the image guiding itself: added to the image gradient the scans have just left there
-        rc = run_var_distances_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->scale, gdx, gdy,
-                                        self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream, B,
-                                        self ? image_stride : guide_stride, self ? image_stride : guide_stride);
+        if (plan->volume)
+            rc = run_var_distances_volume_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->depth, plan->scale,
+                                                   gdx, gdy, gdz, self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream);
+        else
+            rc = run_var_distances_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->scale, gdx, gdy,
+                                            self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream, B,
+                                            self ? image_stride : guide_stride, self ? image_stride : guide_stride);
         if (rc == RF_OK) rc = timer.mark();
         if (rc != RF_OK) return rc;
     }

@@ -21,6 +21,10 @@ struct rf_smooth_plan {
     bool volume = false;
     int64_t depth = 1;
     float spacing_z = 1.0f;
+    // RF_SMOOTH_VOLUME_BACKWARD: a volume plan with a backward (f32 volumes).  An image plan always has one.
+    bool volume_backward = false;
+    bool has_backward() const { return !volume || volume_backward; }
+    int n_distances() const { return volume ? 3 : 2; }
     int64_t samples() const { return width * height * depth; }      // of one plane
     int device = 0;
     bool host_only = false;
@@ -37,11 +41,13 @@ struct rf_smooth_plan {
     // rf_smooth_plan_backward: the launch names with the distances held constant ([0]) and differentiated ([1]); [1] needs the
     // gradients of d_x and d_y and the outputs of iterations 0 .. K-2 -- 2 + (K - 1) * n_planes f32 planes, allocated by the first
     // call that needs them -- and the inner plan's (4 + 1) * n_planes; all of it per image: gd_x [image], gd_y [image], then
-    // [iteration][image][plane]
+    // [iteration][image][plane].  A volume plan with a backward: the same one dimension up -- gd_x, gd_y, gd_z, then
+    // [iteration][plane], 3 + (K - 1) * n_planes f32 volumes, and the inner plan's (6 + 1) * n_planes.  A volume plan without one has
+    // no names and no workspace.
     std::vector<std::string> backward_names[2];
     float *grad_planes = nullptr;
-    size_t own_backward_bytes() const { return (size_t)batch * (size_t)(2 + (iterations - 1) * n_planes) * (size_t)(width * height) * sizeof(float); }
-    size_t backward_workspace_bytes(bool edges) const { return edges && !volume ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
+    size_t own_backward_bytes() const { return (size_t)batch * (size_t)(n_distances() + (iterations - 1) * n_planes) * (size_t)samples() * sizeof(float); }
+    size_t backward_workspace_bytes(bool edges) const { return edges && has_backward() ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
     ~rf_smooth_plan();
 };
 
@@ -50,7 +56,7 @@ namespace rf {
 int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out);
 // rf_smooth_plan_create_volume
 int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan **out);
-// what the backward entry points answer for a volume plan: RF_ERR_UNSUPPORTED
+// what the backward entry points answer for a volume plan without RF_SMOOTH_VOLUME_BACKWARD: RF_ERR_UNSUPPORTED
 int refuse_volume_backward();
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
 int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,

@@ -26,6 +26,8 @@
 // backward (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
 //
 // run_var_distances_backward: the adjoint of run_var_distances, one launch; the two share their checks of counts, scale and extents.
+// run_var_distances_volume_backward is the same for run_var_distances_volume (check_volume_distance_counts, check_distance_scale,
+// check_volume_extents).
 //
 // A signal plan (build_var_signal_plan, rf_var_plan_create_signal) is the plan of a 1 x length image whose stages run the three
 // kernels of kernels_var_signal.hip (launch_stage's `signal`): width = length, height = 1, every scan along dim 0, the workspace
@@ -606,6 +608,14 @@ int check_distance_extents(const char *kernel, int64_t width, int64_t height) {
     return RF_OK;
 }
 
+// the first refusals of run_var_distances_volume and run_var_distances_volume_backward; both go on to check_distance_scale and
+// check_volume_extents (n_planes = 1) behind pointer checks of their own
+int check_volume_distance_counts(int32_t n_guide, int64_t width, int64_t height, int64_t depth) {
+    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
+    if (width < 1 || height < 1 || depth < 1) { set_error("width, height and depth must be positive"); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
 }  // namespace
 
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
@@ -649,12 +659,12 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
 
 int run_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
                              float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, hipStream_t stream) {
-    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
-    if (width < 1 || height < 1 || depth < 1) { set_error("width, height and depth must be positive"); return RF_ERR_INVALID_ARG; }
+    int rc = check_volume_distance_counts(n_guide, width, height, depth);
+    if (rc != RF_OK) return rc;
     if (!guide_volumes || !dx || !dy || !dz) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
     for (int ch = 0; ch < n_guide; ch++)
         if (!guide_volumes[ch]) { set_error("guide volume %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
-    int rc = check_distance_scale(scale);
+    rc = check_distance_scale(scale);
     if (rc != RF_OK) return rc;
     if (!std::isfinite(spacing_z) || !(spacing_z > 0.0f)) { set_error("spacing_z must be finite and positive (got %g)", (double)spacing_z); return RF_ERR_INVALID_ARG; }
     rc = check_volume_extents(width, height, depth, 1);
@@ -749,6 +759,61 @@ int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide,
     a.guide_stride = guide_stride;
     a.grad_guide_stride = grad_guide_stride;
     return launch_var_distances_grad(a, stream);
+}
+
+int run_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth, float scale,
+                                      const void *grad_dx, const void *grad_dy, const void *grad_dz, void *const *grad_guide_volumes,
+                                      int32_t accumulate, int32_t device, hipStream_t stream) {
+    int rc = check_volume_distance_counts(n_guide, width, height, depth);
+    if (rc != RF_OK) return rc;
+    if (!guide_volumes || !grad_dx || !grad_dy || !grad_dz || !grad_guide_volumes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if (!guide_volumes[ch] || !grad_guide_volumes[ch]) { set_error("guide volume %d: null pointer (the volume or its gradient)", ch); return RF_ERR_INVALID_ARG; }
+    rc = check_distance_scale(scale);
+    if (rc == RF_OK) rc = check_volume_extents(width, height, depth, 1);
+    if (rc != RF_OK) return rc;
+    if (accumulate != 0 && accumulate != 1) { set_error("accumulate must be 0 or 1 (got %d)", accumulate); return RF_ERR_INVALID_ARG; }
+    if ((((uintptr_t)grad_dx | (uintptr_t)grad_dy | (uintptr_t)grad_dz) & 15u) != 0) { set_error("grad_dx, grad_dy and grad_dz must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < n_guide; ch++)
+        if ((((uintptr_t)guide_volumes[ch] | (uintptr_t)grad_guide_volumes[ch]) & 15u) != 0) {
+            set_error("guide volume %d: f32 guide volumes and their gradients must be 16-byte aligned", ch);
+            return RF_ERR_INVALID_ARG;
+        }
+    // a gradient volume is written while other lanes still read: it overlaps nothing that is read and no other gradient volume
+    const size_t bytes = (size_t)(width * height * depth) * sizeof(float);
+    for (int ch = 0; ch < n_guide; ch++) {
+        const void *o = grad_guide_volumes[ch];
+        if (overlap(o, bytes, grad_dx, bytes) || overlap(o, bytes, grad_dy, bytes) || overlap(o, bytes, grad_dz, bytes)) {
+            set_error("gradient of guide volume %d overlaps grad_dx, grad_dy or grad_dz: a lane reads its neighbours' samples", ch);
+            return RF_ERR_INVALID_ARG;
+        }
+        for (int q = 0; q < n_guide; q++) {
+            if (overlap(o, bytes, guide_volumes[q], bytes)) {
+                set_error("gradient of guide volume %d overlaps guide volume %d: a lane reads its neighbours' samples", ch, q);
+                return RF_ERR_INVALID_ARG;
+            }
+            if (q > ch && overlap(o, bytes, grad_guide_volumes[q], bytes)) {
+                set_error("gradient of guide volume %d overlaps gradient of guide volume %d", ch, q);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    }
+    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
+    VarDistVolumeGradArgs a{};
+    for (int ch = 0; ch < n_guide; ch++) {
+        a.guide[ch] = (const float *)guide_volumes[ch];
+        a.grad_guide[ch] = (float *)grad_guide_volumes[ch];
+    }
+    a.gdx = (const float *)grad_dx;
+    a.gdy = (const float *)grad_dy;
+    a.gdz = (const float *)grad_dz;
+    a.width = (int32_t)width;
+    a.height = (int32_t)height;
+    a.depth = (int32_t)depth;
+    a.n_guide = n_guide;
+    a.accumulate = accumulate;
+    a.scale = scale;
+    return launch_var_distances_volume_grad(a, stream);
 }
 
 }  // namespace rf

@@ -112,6 +112,11 @@ int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t 
 // rf_var_distances_volume: d_x, d_y slice by slice as run_var_distances forms them, d_z along z from spacing_z; one launch
 int run_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
                              float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, hipStream_t stream);
+// rf_var_distances_volume_backward: the adjoint of run_var_distances_volume for f32 guides, one launch; accumulate: added to what the
+// gradient volumes hold
+int run_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth, float scale,
+                                      const void *grad_dx, const void *grad_dy, const void *grad_dz, void *const *grad_guide_volumes,
+                                      int32_t accumulate, int32_t device, hipStream_t stream);
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
                                const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
                                int32_t batch = 1, int64_t guide_stride = 0, int64_t grad_guide_stride = 0);

@@ -11,7 +11,11 @@ The scans run in the HIP kernels of kernels_var.hip; torch tensors are device me
 
 Volumes: `VarPlan.volume`, `var_scan_volume`, `domain_transform_distances_volume`, `SmoothPlan.volume` and
 `edge_aware_smooth_volume` are the same on (D, H, W) volumes with scans along x, y and z (rf_var_plan_create_volume,
-rf_var_distances_volume, rf_smooth_plan_create_volume); the smoothing plan of a volume has no backward.
+rf_var_distances_volume, rf_smooth_plan_create_volume).  `domain_transform_distances_volume_backward`
+(rf_var_distances_volume_backward) is the adjoint of the volume distances for f32 guides.  The smoothing plan of a volume has a
+backward where it is asked for: `SmoothPlan.volume(..., differentiable=True)` (RF_SMOOTH_VOLUME_BACKWARD, f32 volumes) gives
+`backward`, `backward_timed` and `apply` -- 1 + 18 K launches with the distances held constant, 51 K - 7 through them -- and
+`edge_aware_smooth_volume(..., differentiable=True)` goes through it; without the flag the backward is refused as before.
 
 The plane form is differentiable: `VarPlan.backward` (rf_var_plan_backward) is the adjoint of `VarPlan.execute` in the same HIP
 kernels' adjoint instances -- gradients with respect to the image planes and, where asked for, the weight planes -- and
@@ -561,6 +565,41 @@ def domain_transform_distances_backward(guide, sigma_s: float, sigma_r: float, g
     return grad_guide
 
 
+def domain_transform_distances_volume_backward(guide, sigma_s: float, sigma_r: float, grad_dx, grad_dy, grad_dz, grad_guide=None,
+                                               accumulate: bool = False, stream=None):
+    """rf_var_distances_volume_backward: the gradient of an f32 device guide volume (C, D, H, W) or (D, H, W) from the gradients of
+    the three volumes of `domain_transform_distances_volume` (one HIP launch, var_distances_volume_grad, a gather; spacing_z does
+    not enter).  grad_guide=None allocates it (then accumulate must be False); accumulate=True adds to what grad_guide holds.
+    Returned in the guide's shape."""
+    import torch
+    g = guide if guide.dim() == 4 else guide.unsqueeze(0)
+    if g.dim() != 4:
+        raise ValueError(f"guide must be (C, D, H, W) or (D, H, W), got {tuple(guide.shape)}")
+    if g.dtype != torch.float32:
+        raise TypeError(f"float32 guides only (there is no gradient with respect to a byte guide), got {g.dtype}")
+    if not g.is_cuda:
+        raise ValueError("the guide must be a device tensor")
+    g = g.contiguous()
+    C, D, H, W = (int(s) for s in g.shape)
+    if grad_guide is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs grad_guide")
+        grad_guide = torch.empty_like(g)
+    gg = grad_guide if grad_guide.dim() == 4 else grad_guide.unsqueeze(0)
+    for what, t, shape in (("grad_dx", grad_dx, (D, H, W)), ("grad_dy", grad_dy, (D, H, W)), ("grad_dz", grad_dz, (D, H, W)),
+                           ("grad_guide", gg, (C, D, H, W))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {shape}")
+    volumes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
+    grads = (ctypes.c_void_p * C)(*[gg[c].data_ptr() for c in range(C)])
+    scale = float(sigma_s) / float(sigma_r)
+    with torch.cuda.device(g.device):
+        capi.check(capi.lib().rf_var_distances_volume_backward(volumes, C, W, H, D, scale, grad_dx.data_ptr(), grad_dy.data_ptr(),
+                                                               grad_dz.data_ptr(), grads, int(bool(accumulate)), g.device.index,
+                                                               VarPlan._stream(stream)))
+    return grad_guide
+
+
 class SmoothPlan(_PlanHandle):
     """rf_smooth_plan_*: the domain-transform recursive filter of `planes` image planes of `shape_hw` = (height, width), f32 or
     uint8 (uint8: input AND output; out = sat8 of the f32 filter on the widened bytes, rounded once, at the final store).
@@ -610,12 +649,18 @@ class SmoothPlan(_PlanHandle):
 
     @classmethod
     def volume(cls, shape_dhw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
-               iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, spacing_z: float = 1.0, device: int = -1) -> "SmoothPlan":
+               iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, spacing_z: float = 1.0, device: int = -1,
+               differentiable: bool = False) -> "SmoothPlan":
         """rf_smooth_plan_create_volume: the filter along x, y and z of `planes` volumes of `shape_dhw` = (depth, height, width),
         f32 or uint8 (bytes in, bytes out, as for images).  The plan owns three distance volumes: one var_distances_volume
         launch, then 9 launches per iteration (+x -x, +y -y, +z -z).  spacing_z > 0: the sample distance along z in units of the
-        x/y pitch.  execute / execute_timed take (C, D, H, W) or (D, H, W) tensors (or lists of (D, H, W) volumes); backward is
-        refused by the library (RF_ERR_UNSUPPORTED); there is no batch of volumes."""
+        x/y pitch.  execute / execute_timed take (C, D, H, W) or (D, H, W) tensors (or lists of (D, H, W) volumes); there is no
+        batch of volumes.
+        differentiable=False: backward is refused by the library (RF_ERR_UNSUPPORTED) and its queries return 0.
+        differentiable=True (RF_SMOOTH_VOLUME_BACKWARD; f32 volumes, the library refuses uint8 ones at create): the same forward,
+        bit for bit, and `backward`, `backward_timed` and `apply` work as on an image plan -- 1 + 18 K launches with the
+        distances held constant, 51 K - 7 through them (the last one var_distances_volume_grad), and
+        3 + (K - 1 + 7) * planes f32 volumes of workspace allocated by the first edges=True call."""
         import torch
         self = cls.__new__(cls)
         shape_dhw = tuple(int(s) for s in shape_dhw)
@@ -635,7 +680,7 @@ class SmoothPlan(_PlanHandle):
         d.iterations = int(iterations)
         d.sigma_s, d.sigma_r, d.spacing_z = float(sigma_s), float(sigma_r), float(spacing_z)
         d.device = int(device)
-        d.flags = 0
+        d.flags = capi.RF_SMOOTH_VOLUME_BACKWARD if differentiable else 0
         self._desc = d
         self.shape, self.planes, self.guide_planes, self.iterations = shape_dhw, int(planes), int(guide_planes), int(iterations)
         self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
@@ -719,12 +764,13 @@ class SmoothPlan(_PlanHandle):
 
     # -- the adjoint ------------------------------------------------------------------------
     def backward_num_kernels(self, edges: bool = False) -> int:
-        """rf_smooth_plan_backward_num_kernels: 1 + 12 K launches with the distances held constant, 34 K - 4 through them"""
+        """rf_smooth_plan_backward_num_kernels: 1 + 12 K launches with the distances held constant, 34 K - 4 through them (a
+        differentiable volume plan: 1 + 18 K and 51 K - 7; a volume plan without the flag: 0)"""
         return int(capi.lib().rf_smooth_plan_backward_num_kernels(self._h, int(bool(edges))))
 
     def backward_workspace_bytes(self, edges: bool = False) -> int:
         """rf_smooth_plan_backward_workspace_bytes: what the first backward call with edges allocates beyond workspace_bytes,
-        2 + (K - 1 + 5) * planes f32 planes; 0 without edges"""
+        2 + (K - 1 + 5) * planes f32 planes (a differentiable volume plan: 3 + (K - 1 + 7) * planes f32 volumes); 0 without edges"""
         return int(capi.lib().rf_smooth_plan_backward_workspace_bytes(self._h, int(bool(edges))))
 
     def _backward_arguments(self, image, guide, grad_out, grad_image, grad_guide, edges, stream):
@@ -764,8 +810,8 @@ class SmoothPlan(_PlanHandle):
                                               self.backward_num_kernels(edges))
 
     def apply(self, image, guide=None):
-        """execute, out of place, as a differentiable torch operation on f32 tensors (C, H, W) or (H, W): values bit for bit
-        execute's.  Backward is `backward`; it goes through the distances (edges) where the guide requires a gradient, or the
+        """execute, out of place, as a differentiable torch operation on f32 tensors (C, H, W) or (H, W) -- on a volume plan made
+        with differentiable=True, (C, D, H, W) or (D, H, W): values bit for bit execute's.  Backward is `backward`; it goes through the distances (edges) where the guide requires a gradient, or the
         image does and guides itself.  Only the image and the guide are saved; no double backward."""
         return _smooth_function().apply(self, image, guide)
 
@@ -810,14 +856,20 @@ def _smooth_function():
 _smooth_volume_plans: Dict[tuple, SmoothPlan] = {}
 
 
-def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, spacing_z: float = 1.0):
+def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, spacing_z: float = 1.0,
+                             differentiable: bool = False):
     """Edge-aware smoothing of a device volume (C, D, H, W) or (D, H, W), f32 or uint8, by the domain-transform recursive filter
     along x, y and z, through a cached `SmoothPlan.volume` (keyed by shape, dtypes, iterations, sigmas, spacing_z and device): per
     iteration +x -x, +y -y, +z -z on the three exponent volumes of `domain_transform_distances_volume`.  guide=None: the volume
     guides itself; else a guide (G, D, H, W) or (D, H, W), f32 or uint8.  spacing_z > 0 is the sample distance along z in units
     of the x/y pitch -- slice thickness of a CT/MR stack, or how far apart two video frames count; 1 = isotropic.  The result
-    has the volume's dtype (uint8: sat8 of the f32 filter on the bytes).  Not differentiable.  W must be a multiple of 4; calls
-    that share a plan are ordered by the caller (one stream)."""
+    has the volume's dtype (uint8: sat8 of the f32 filter on the bytes).  W must be a multiple of 4; calls that share a plan are
+    ordered by the caller (one stream).
+    differentiable=False (the default): the result carries no grad_fn whatever the inputs require.  differentiable=True, with
+    torch's grad mode on and a volume or a guide that requires a gradient: the call goes through `SmoothPlan.apply` on a cached
+    `SmoothPlan.volume(..., differentiable=True)` -- same values, bit for bit; f32 volumes, and an f32 guide where the guide requires
+    a gradient (TypeError otherwise); gradients with respect to the volume and the guide, all of it in the library, through the
+    distances where the guide, or a self-guiding volume, requires one.  No gradient of the sigmas or spacing_z; no double backward."""
     import torch
     vol = volume if volume.dim() == 4 else volume.unsqueeze(0)
     if vol.dim() != 4:
@@ -837,14 +889,23 @@ def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r:
             raise ValueError("guide and volume must have the same depth, height and width")
     shape = tuple(int(s) for s in vol.shape)
     device = vol.device.index if vol.device.index is not None else torch.cuda.current_device()
-    key = shape + (vol.dtype, None if g is None else (int(g.shape[0]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), float(spacing_z), device)
+    wants_grad = bool(differentiable) and torch.is_grad_enabled() and (vol.requires_grad or (g is not None and g.requires_grad))
+    if wants_grad and (vol.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad)):
+        raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
+    # (a plan with a backward is built only where one is needed: the default call keeps the plans it had)
+    key = shape + (vol.dtype, None if g is None else (int(g.shape[0]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), float(spacing_z), device,
+                   wants_grad)
     plan = _smooth_volume_plans.get(key)
     if plan is None:
         plan = _smooth_volume_plans[key] = SmoothPlan.volume(shape[1:], planes=shape[0], guide_planes=0 if g is None else int(g.shape[0]),
                                                              image_dtype=vol.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
-                                                             sigma_s=sigma_s, sigma_r=sigma_r, spacing_z=spacing_z, device=device)
-    with torch.cuda.device(vol.device):
-        out = plan.execute(vol, g)
+                                                             sigma_s=sigma_s, sigma_r=sigma_r, spacing_z=spacing_z, device=device,
+                                                             differentiable=wants_grad)
+    if wants_grad:
+        out = plan.apply(vol, g)
+    else:
+        with torch.cuda.device(vol.device):
+            out = plan.execute(vol, g)
     return out if volume.dim() == 4 else out[0]
 
 
