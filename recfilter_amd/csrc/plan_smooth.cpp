@@ -20,6 +20,9 @@
 //
 // Both run functions construct one LaunchTimer (run_support.h) and hand it to every launcher they call, so the slots of a timed run
 // follow the plan's name lists; the constants of the power form, log2 and ln of every a_k, are the plan's from its construction.
+// What the two share is here once: distance_planes (where d_x, d_y(, d_z) and their gradients lie), iteration_constants (the inner
+// plan's triples of iteration k), form_distances and form_guide_gradient -- the one place per direction that chooses between the
+// image's and the volume's distance runner, and between the guide and a self-guiding image.
 //
 // A volume plan (build_smooth_volume_plan, rf_smooth_plan_create_volume) is the same sequence one dimension up: three distance
 // volumes from one var_distances_volume launch (d_z from spacing_z), an inner volume plan +x -x +y -y +z -z with {a_k, a_k, a_k},
@@ -253,34 +256,31 @@ int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch,
         plan->ln_bases.push_back((float)std::log((double)a_k));
     }
     const rf_var_scan_desc scans[6] = {{0, 1, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 1}, {2, 1, 2}, {2, 0, 2}};
-    rf_var_desc vd{};
-    vd.ndim = 2;
-    vd.abi = RF_ABI;
-    vd.extent[0] = desc->width;
-    vd.extent[1] = desc->height;
-    vd.dtype = RF_F32;
-    vd.n_planes = desc->n_planes;
-    vd.n_weights = 2;
-    vd.n_scans = 4;
-    vd.scans = scans;
-    vd.device = desc->device;
-    vd.flags = 0;
+    // the inner plan: +x -x +y -y(, +z -z), a weight plane per dimension (the device checks, and the tails and the carries)
     rf_var_plan *inner = nullptr;
+    auto describe = [&](auto &d, int dims) {
+        d.abi = RF_ABI;
+        d.dtype = RF_F32;
+        d.n_planes = desc->n_planes;
+        d.n_weights = dims;
+        d.n_scans = 2 * dims;
+        d.scans = scans;
+        d.device = desc->device;
+    };
     if (plan->volume) {
         rf_var_volume_desc vv{};
-        vv.abi = RF_ABI;
+        describe(vv, 3);
         vv.width = desc->width;
         vv.height = desc->height;
         vv.depth = depth;
-        vv.dtype = RF_F32;
-        vv.n_planes = desc->n_planes;
-        vv.n_weights = 3;
-        vv.n_scans = 6;
-        vv.scans = scans;
-        vv.device = desc->device;
         rc = build_var_volume_plan(&vv, &inner);
     } else {
-        rc = build_var_plan(&vd, &inner, plan->batch);      // (the device checks, and the tails and the carries)
+        rf_var_desc vd{};
+        describe(vd, 2);
+        vd.ndim = 2;
+        vd.extent[0] = desc->width;
+        vd.extent[1] = desc->height;
+        rc = build_var_plan(&vd, &inner, plan->batch);
     }
     if (rc != RF_OK) return rc;
     plan->inner.reset(inner);
@@ -315,6 +315,71 @@ int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch,
 
 }  // namespace
 
+namespace {
+
+// The plan's distance planes d_x, d_y(, d_z) at `base` -- or their gradients, laid out alike -- one plane per image each (a volume:
+// the batch is 1), and what follows them: `own`.  base == nullptr (no gradient planes yet, or none needed): all null.
+struct DistancePlanes {
+    float *d[3] = {nullptr, nullptr, nullptr};
+    float *own = nullptr;
+};
+DistancePlanes distance_planes(const rf_smooth_plan *plan, float *base) {
+    DistancePlanes p;
+    if (!base) return p;
+    const size_t each = (size_t)plan->samples() * (size_t)plan->batch;
+    for (int k = 0; k < plan->n_distances(); k++) p.d[k] = base + each * (size_t)k;
+    p.own = base + each * (size_t)plan->n_distances();
+    return p;
+}
+
+// The constants of iteration k for the inner plan, whose exponent planes all share the base a_k; holds_sum: the backward's
+// exponent gradients already hold the sum of the iterations behind k.
+struct IterationConstants {
+    float log2_base[3], ln_base[3];
+    bool holds_sum[3];
+};
+IterationConstants iteration_constants(const rf_smooth_plan *plan, int k) {
+    IterationConstants c;
+    for (int q = 0; q < 3; q++) {
+        c.log2_base[q] = plan->log2_bases[(size_t)k];
+        c.ln_base[q] = plan->ln_bases[(size_t)k];
+        c.holds_sum[q] = k < plan->iterations - 1;
+    }
+    return c;
+}
+
+// The distances of a call, one launch: an image's or a volume's, from the guide planes or -- where the image guides itself -- from
+// the image planes, with that array's stride from image to image.
+int form_distances(const rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, const DistancePlanes &p,
+                   hipStream_t stream) {
+    const bool self = plan->n_guide == 0;
+    const void *const *guide = self ? image_planes : guide_planes;
+    const int n_guide = self ? plan->n_planes : plan->n_guide, guide_u8 = self ? plan->image_u8 : plan->guide_u8;
+    if (plan->volume)
+        return run_var_distances_volume(guide, n_guide, guide_u8, plan->width, plan->height, plan->depth, plan->scale, plan->spacing_z, p.d[0], p.d[1],
+                                        p.d[2], plan->device, stream);
+    return run_var_distances(guide, n_guide, guide_u8, plan->width, plan->height, plan->scale, p.d[0], p.d[1], plan->device, stream, plan->batch,
+                             self ? plan->image_stride : plan->guide_stride);
+}
+
+// The adjoint of form_distances, one launch, from the distance gradients `g`.  A separate guide: its gradient is stored; the image
+// guiding itself: added to the image gradient the scans have just left there.
+int form_guide_gradient(const rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, const DistancePlanes &g,
+                        void *const *grad_image_planes, void *const *grad_guide_planes, hipStream_t stream) {
+    const bool self = plan->n_guide == 0;
+    const void *const *guide = self ? image_planes : guide_planes;
+    void *const *grad = self ? grad_image_planes : grad_guide_planes;
+    const int n_guide = self ? plan->n_planes : plan->n_guide, accumulate = self ? 1 : 0;
+    const int64_t stride = self ? plan->image_stride : plan->guide_stride;
+    if (plan->volume)
+        return run_var_distances_volume_backward(guide, n_guide, plan->width, plan->height, plan->depth, plan->scale, g.d[0], g.d[1], g.d[2], grad,
+                                                 accumulate, plan->device, stream);
+    return run_var_distances_backward(guide, n_guide, plan->width, plan->height, plan->scale, g.d[0], g.d[1], grad, accumulate, plan->device, stream,
+                                      plan->batch, stride, stride);
+}
+
+}  // namespace
+
 int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
                     hipStream_t stream, float *ms_out) {
     if (!plan || !image_planes || !out_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
@@ -334,7 +399,7 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
     // a stage has loaded its tile before it stores, so a plane may be filtered in place; any other overlap of an input with an output
     // is read after another workgroup's store
     const int B = plan->batch;
-    const int64_t image_stride = plan->image_stride, guide_stride = plan->guide_stride;
+    const int64_t image_stride = plan->image_stride;
     if (B > 1) {
         const int64_t stride_bytes = image_stride * (int64_t)(plan->image_u8 ? 1 : sizeof(float));
         const ExtentArray arrays[2] = {{"input", image_planes, plan->n_planes, stride_bytes, image_bytes, false, 1},
@@ -353,24 +418,16 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
     RF_HIP_CHECK(hipSetDevice(plan->device));
     LaunchTimer timer(stream, ms_out, plan->names.size());
     if (timer.status() != RF_OK) return timer.status();
-    float *dx = plan->planes, *dy = dx + samples * (size_t)B;      // one plane per image each
-    float *dz = plan->volume ? dy + samples : nullptr;             // (a volume: B is 1)
-    float *const own = plan->volume ? dz + samples : dy + samples * (size_t)B;      // what follows the distances
     // the distances first, on the same stream: guide planes may be output planes
-    const bool self = plan->n_guide == 0;
-    if (plan->volume)
-        rc = run_var_distances_volume(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
-                                      plan->width, plan->height, plan->depth, plan->scale, plan->spacing_z, dx, dy, dz, plan->device, stream);
-    else
-        rc = run_var_distances(self ? image_planes : guide_planes, self ? plan->n_planes : plan->n_guide, self ? plan->image_u8 : plan->guide_u8,
-                               plan->width, plan->height, plan->scale, dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
+    const DistancePlanes d = distance_planes(plan, plan->planes);
+    rc = form_distances(plan, image_planes, guide_planes, d, stream);
     if (rc == RF_OK) rc = timer.mark();
     if (rc != RF_OK) return rc;
     void *work[RF_MAX_PLANES] = {};
     // byte images: [image][plane] behind the distance planes
-    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(own + samples * (size_t)pl) : out_planes[pl];
+    for (int pl = 0; pl < plan->n_planes; pl++) work[pl] = plan->image_u8 ? (void *)(d.own + samples * (size_t)pl) : out_planes[pl];
     const int64_t work_stride = plan->image_u8 ? (int64_t)samples * plan->n_planes : image_stride;
-    const void *const weights[3] = {dx, dy, dz};
+    const void *const weights[3] = {d.d[0], d.d[1], d.d[2]};
     const int K = plan->iterations;
     for (int k = 0; k < K; k++) {
         VarIo io{};
@@ -383,8 +440,7 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
         io.work_stride = work_stride;
         io.out_stride = k == K - 1 ? image_stride : work_stride;
         io.weights_stride = (int64_t)samples;
-        const float l[3] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-        rc = launch_var_stages(plan->inner.get(), io, weights, l, stream, timer);
+        rc = launch_var_stages(plan->inner.get(), io, weights, iteration_constants(plan, k).log2_base, stream, timer);
         if (rc != RF_OK) return rc;
     }
     return timer.finish();
@@ -466,51 +522,39 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     }
     LaunchTimer timer(stream, ms_out, plan->backward_names[edges].size());
     if (timer.status() != RF_OK) return timer.status();
-    // one plane per image each (a volume: B is 1, and a third, d_z), as the gradients' gd_x, gd_y (, gd_z) below
-    const int nd = plan->n_distances();
-    float *dx = plan->planes, *dy = dx + samples * (size_t)B, *dz = plan->volume ? dy + samples : nullptr;
-    if (plan->volume)
-        rc = run_var_distances_volume(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height,
-                                      plan->depth, plan->scale, plan->spacing_z, dx, dy, dz, plan->device, stream);
-    else
-        rc = run_var_distances(self ? image_planes : guide_planes, self ? P : G, self ? 0 : plan->guide_u8, plan->width, plan->height, plan->scale,
-                               dx, dy, plan->device, stream, B, self ? image_stride : guide_stride);
+    const DistancePlanes d = distance_planes(plan, plan->planes), g = distance_planes(plan, plan->grad_planes);
+    rc = form_distances(plan, image_planes, guide_planes, d, stream);
     if (rc == RF_OK) rc = timer.mark();
     if (rc != RF_OK) return rc;
-    const void *const exponents[3] = {dx, dy, dz};
-    float *gdx = plan->grad_planes, *gdy = gdx ? gdx + samples * (size_t)B : nullptr, *gdz = gdx && plan->volume ? gdy + samples : nullptr;
-    float *const own = gdx ? gdx + samples * (size_t)B * (size_t)nd : nullptr;      // what follows the distance gradients
+    const void *const exponents[3] = {d.d[0], d.d[1], d.d[2]};
     // the output of iteration k, k = 0 .. K-2: [iteration][image][plane]
     const int64_t checkpoint_stride = (int64_t)samples * P;
     void *checkpoints[RF_SMOOTH_MAX_ITERATIONS][RF_MAX_PLANES] = {};
     if (edges == 1) {
         for (int k = 0; k + 1 < K; k++) {
-            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = own + samples * ((size_t)k * (size_t)B * P + pl);
+            for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = g.own + samples * ((size_t)k * (size_t)B * P + pl);
             VarIo io{};
             io.in = k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
             io.work = io.out = checkpoints[k];
             io.in_stride = k == 0 ? image_stride : checkpoint_stride;
             io.work_stride = io.out_stride = checkpoint_stride;
             io.weights_stride = (int64_t)samples;
-            const float l[3] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-            rc = launch_var_stages(inner, io, exponents, l, stream, timer);
+            rc = launch_var_stages(inner, io, exponents, iteration_constants(plan, k).log2_base, stream, timer);
             if (rc != RF_OK) return rc;
         }
     }
-    void *const grad_exponents[3] = {gdx, gdy, gdz};
+    void *const grad_exponents[3] = {g.d[0], g.d[1], g.d[2]};
     for (int k = K - 1; k >= 0; k--) {
-        const float l[3] = {plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k], plan->log2_bases[(size_t)k]};
-        const float c[3] = {plan->ln_bases[(size_t)k], plan->ln_bases[(size_t)k], plan->ln_bases[(size_t)k]};
-        const bool holds_sum[3] = {k < K - 1, k < K - 1, k < K - 1};
+        const IterationConstants c = iteration_constants(plan, k);
         VarBackwardIo io{};
         io.in = edges == 0 ? nullptr : k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
         io.weights = exponents;
         io.grad_out = k == K - 1 ? grad_out_planes : (const void *const *)grad_image_planes;
         io.grad_in = grad_image_planes;
         io.grad_weights = edges == 1 ? grad_exponents : nullptr;
-        io.log2_base = l;
-        io.ln_base = c;
-        io.holds_sum = holds_sum;
+        io.log2_base = c.log2_base;
+        io.ln_base = c.ln_base;
+        io.holds_sum = c.holds_sum;
         io.in_stride = k == 0 ? image_stride : checkpoint_stride;
         io.weights_stride = io.grad_weights_stride = (int64_t)samples;
         io.grad_out_stride = io.grad_in_stride = image_stride;
@@ -518,14 +562,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
         if (rc != RF_OK) return rc;
     }
     if (edges == 1) {
-        // a separate guide: stored; the image guiding itself: added to the image gradient the scans have just left there
-        if (plan->volume)
-            rc = run_var_distances_volume_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->depth, plan->scale,
-                                                   gdx, gdy, gdz, self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream);
-        else
-            rc = run_var_distances_backward(self ? image_planes : guide_planes, self ? P : G, plan->width, plan->height, plan->scale, gdx, gdy,
-                                            self ? grad_image_planes : grad_guide_planes, self ? 1 : 0, plan->device, stream, B,
-                                            self ? image_stride : guide_stride, self ? image_stride : guide_stride);
+        rc = form_guide_gradient(plan, image_planes, guide_planes, g, grad_image_planes, grad_guide_planes, stream);
         if (rc == RF_OK) rc = timer.mark();
         if (rc != RF_OK) return rc;
     }

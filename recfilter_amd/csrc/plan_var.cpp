@@ -25,9 +25,9 @@
 // run_var_backward checks and constructs the timer; launch_var_backward issues the launches, and is what the smoothing plan's
 // backward (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
 //
-// run_var_distances_backward: the adjoint of run_var_distances, one launch; the two share their checks of counts, scale and extents.
-// run_var_distances_volume_backward is the same for run_var_distances_volume (check_volume_distance_counts, check_distance_scale,
-// check_volume_extents).
+// The three public descriptions (rf_var_desc, rf_var_signal_desc, rf_var_volume_desc) are lowered to one form, an rf_var_desc
+// (`lowered`), and checked by one validator: what differs between the kinds -- the struct's name in the messages, the noun, the
+// highest dim, the accepted domain -- is a VarKind record.  build_checked builds the plan of a lowered description.
 //
 // A signal plan (build_var_signal_plan, rf_var_plan_create_signal) is the plan of a 1 x length image whose stages run the three
 // kernels of kernels_var_signal.hip (launch_stage's `signal`): width = length, height = 1, every scan along dim 0, the workspace
@@ -41,11 +41,17 @@
 // gives an x or y stage the `depth` slices as its batch (slice strides of width * height samples: stage_stride; tails and carries
 // slice after slice in the single-image layout) and a z stage the (width * height) x depth view of the y kernels, a voxel column
 // per lane.  plan->batch stays 1 and the backward's planes are volumes.  check_volume_extents is the accepted domain, shared with
-// run_var_distances_volume (the three exponent volumes, one launch) and plan_smooth.cpp.
+// the distances of a volume and plan_smooth.cpp.
+//
+// The distances (rf_var_distances, rf_var_distances_volume) and their adjoints, one launch each, take one argument record,
+// DistanceCall: two planes or three, written or read.  The refusals are small steps over that record; each of the four entry points
+// lists its steps in its own documented order (run_distance_steps) and ends in run_distances_forward or run_distances_backward,
+// which hold the alignment and overlap checks -- loops over the two or three planes -- and fill the kernels' argument structs.
 #include "plan_var.h"
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <memory>
 
 rf_var_plan::~rf_var_plan() {
@@ -60,26 +66,10 @@ namespace {
 
 constexpr int64_t kVarMaxExtent = int64_t(1) << 21;      // 64 lines or samples per workgroup along grid.y (65535 workgroups)
 
-int validate(const rf_var_desc *d) {
-    if (d->abi != RF_ABI) {
-        set_error("rf_var_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
-        return RF_ERR_INVALID_ARG;
-    }
-    if (d->flags != 0) { set_error("rf_var_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
-    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
-    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
-    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
-    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
-    if (d->ndim != 2) { set_error("varying scans take 2-D images (ndim = %d)", d->ndim); return RF_ERR_UNSUPPORTED; }
-    if (d->dtype != RF_F32) { set_error("varying scans take f32 planes (dtype = %d)", d->dtype); return RF_ERR_UNSUPPORTED; }
-    for (int s = 0; s < d->n_scans; s++) {
-        const rf_var_scan_desc &sc = d->scans[s];
-        if (sc.dim < 0 || sc.dim > 1) { set_error("scan %d: dim must be 0 or 1 (got %d)", s, sc.dim); return RF_ERR_INVALID_ARG; }
-        if (sc.weights < 0 || sc.weights >= d->n_weights) {
-            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
+constexpr int64_t kVarMaxSignal = int64_t(1) << 30;      // samples of a signal: indices and 4096-sample groups stay inside int32
+
+// The accepted domain of each kind of description, on its lowered form (rf_var_desc: see lowered below).
+int check_image_domain(const rf_var_desc *d) {
     for (int k = 0; k < 2; k++)
         if (d->extent[k] < 1) { set_error("extent[%d] must be positive", k); return RF_ERR_INVALID_ARG; }
     for (int k = 0; k < 2; k++)
@@ -89,6 +79,72 @@ int validate(const rf_var_desc *d) {
         return RF_ERR_UNSUPPORTED;
     }
     return RF_OK;
+}
+
+int check_signal_domain(const rf_var_desc *d) {
+    const long long length = (long long)d->extent[0];
+    if (length < 1) { set_error("length must be positive (got %lld)", length); return RF_ERR_INVALID_ARG; }
+    if (length > kVarMaxSignal) { set_error("length = %lld is above %lld", length, (long long)kVarMaxSignal); return RF_ERR_UNSUPPORTED; }
+    if (length % 4 != 0) { set_error("varying scans move 16 bytes per lane: length must be a multiple of 4 (got %lld)", length); return RF_ERR_UNSUPPORTED; }
+    return RF_OK;
+}
+
+int check_volume_domain(const rf_var_desc *d) { return check_volume_extents(d->extent[0], d->extent[1], d->extent[2], d->n_planes); }
+
+// What the three kinds of description differ in, to the one validator: the public struct's name (the abi and flags messages), the
+// noun of the dtype message, the ndim of the lowered form, the highest dim of a scan with its message, and the domain.
+struct VarKind {
+    const char *struct_name, *noun;
+    int ndim, max_dim;
+    const char *dim_message;
+    int (*check_domain)(const rf_var_desc *);
+    bool signal;
+};
+const VarKind kImageKind = {"rf_var_desc", "planes", 2, 1, "scan %d: dim must be 0 or 1 (got %d)", check_image_domain, false};
+const VarKind kSignalKind = {"rf_var_signal_desc", "signals", 2, 0, "scan %d: dim must be 0 on a signal (got %d)", check_signal_domain, true};
+const VarKind kVolumeKind = {"rf_var_volume_desc", "volumes", 3, 2, "scan %d: dim must be 0, 1 or 2 on a volume (got %d)", check_volume_domain, false};
+
+int validate(const rf_var_desc *d, const VarKind &kind) {
+    if (d->abi != RF_ABI) {
+        set_error("%s.abi is %u, this library speaks revision %u of recfilter_amd.h", kind.struct_name, d->abi, RF_ABI);
+        return RF_ERR_INVALID_ARG;
+    }
+    if (d->flags != 0) { set_error("%s.flags must be 0 (got %#x)", kind.struct_name, d->flags); return RF_ERR_INVALID_ARG; }
+    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
+    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
+    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
+    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
+    // (only rf_var_desc has an ndim of its caller's: rf_var_plan_create takes images, and ndim = 3 comes from a volume description alone)
+    if (d->ndim != kind.ndim) { set_error("varying scans take 2-D images (ndim = %d)", d->ndim); return RF_ERR_UNSUPPORTED; }
+    if (d->dtype != RF_F32) { set_error("varying scans take f32 %s (dtype = %d)", kind.noun, d->dtype); return RF_ERR_UNSUPPORTED; }
+    for (int s = 0; s < d->n_scans; s++) {
+        const rf_var_scan_desc &sc = d->scans[s];
+        if (sc.dim < 0 || sc.dim > kind.max_dim) { set_error(kind.dim_message, s, sc.dim); return RF_ERR_INVALID_ARG; }
+        if (sc.weights < 0 || sc.weights >= d->n_weights) {
+            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    return kind.check_domain(d);
+}
+
+// The canonical form of a signal or volume description: an rf_var_desc of `ndim` dimensions with the fields all three share.
+template <class Desc>
+rf_var_desc lowered(const Desc &p, int ndim, int64_t width, int64_t height, int64_t depth) {
+    rf_var_desc d{};
+    d.ndim = ndim;
+    d.abi = p.abi;
+    d.extent[0] = width;
+    d.extent[1] = height;
+    d.extent[2] = depth;
+    d.dtype = p.dtype;
+    d.n_planes = p.n_planes;
+    d.n_weights = p.n_weights;
+    d.n_scans = p.n_scans;
+    d.scans = p.scans;
+    d.device = p.device;
+    d.flags = p.flags;
+    return d;
 }
 
 int64_t tiles_of(int64_t n) { return (n + kVarTile - 1) / kVarTile; }
@@ -101,60 +157,8 @@ void push_stage_names(std::vector<std::string> &names, const char *prefix, int d
     names.push_back(std::string(prefix) + "pass2_" + axis);
 }
 
-constexpr int64_t kVarMaxSignal = int64_t(1) << 30;      // samples of a signal: indices and 4096-sample groups stay inside int32
-
-int validate_signal(const rf_var_signal_desc *d) {
-    if (d->abi != RF_ABI) {
-        set_error("rf_var_signal_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
-        return RF_ERR_INVALID_ARG;
-    }
-    if (d->flags != 0) { set_error("rf_var_signal_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
-    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
-    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
-    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
-    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
-    if (d->dtype != RF_F32) { set_error("varying scans take f32 signals (dtype = %d)", d->dtype); return RF_ERR_UNSUPPORTED; }
-    for (int s = 0; s < d->n_scans; s++) {
-        const rf_var_scan_desc &sc = d->scans[s];
-        if (sc.dim != 0) { set_error("scan %d: dim must be 0 on a signal (got %d)", s, sc.dim); return RF_ERR_INVALID_ARG; }
-        if (sc.weights < 0 || sc.weights >= d->n_weights) {
-            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    if (d->length < 1) { set_error("length must be positive (got %lld)", (long long)d->length); return RF_ERR_INVALID_ARG; }
-    if (d->length > kVarMaxSignal) { set_error("length = %lld is above %lld", (long long)d->length, (long long)kVarMaxSignal); return RF_ERR_UNSUPPORTED; }
-    if (d->length % 4 != 0) {
-        set_error("varying scans move 16 bytes per lane: length must be a multiple of 4 (got %lld)", (long long)d->length);
-        return RF_ERR_UNSUPPORTED;
-    }
-    return RF_OK;
-}
-
 constexpr int64_t kVarMaxVolumeLines = int64_t(1) << 30;      // width * height: the z view's line index is an int32
 constexpr int64_t kVarMaxGridZ = 65535;                        // depth * n_planes: the slices ride on gridDim.z beside the planes
-
-int validate_volume(const rf_var_volume_desc *d) {
-    if (d->abi != RF_ABI) {
-        set_error("rf_var_volume_desc.abi is %u, this library speaks revision %u of recfilter_amd.h", d->abi, RF_ABI);
-        return RF_ERR_INVALID_ARG;
-    }
-    if (d->flags != 0) { set_error("rf_var_volume_desc.flags must be 0 (got %#x)", d->flags); return RF_ERR_INVALID_ARG; }
-    if (d->n_planes < 1 || d->n_planes > RF_MAX_PLANES) { set_error("n_planes must be 1..%d (got %d)", RF_MAX_PLANES, d->n_planes); return RF_ERR_INVALID_ARG; }
-    if (d->n_weights < 1 || d->n_weights > RF_VAR_MAX_SCANS) { set_error("n_weights must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_weights); return RF_ERR_INVALID_ARG; }
-    if (d->n_scans < 1 || d->n_scans > RF_VAR_MAX_SCANS) { set_error("n_scans must be 1..%d (got %d)", RF_VAR_MAX_SCANS, d->n_scans); return RF_ERR_INVALID_ARG; }
-    if (!d->scans) { set_error("null scans"); return RF_ERR_INVALID_ARG; }
-    if (d->dtype != RF_F32) { set_error("varying scans take f32 volumes (dtype = %d)", d->dtype); return RF_ERR_UNSUPPORTED; }
-    for (int s = 0; s < d->n_scans; s++) {
-        const rf_var_scan_desc &sc = d->scans[s];
-        if (sc.dim < 0 || sc.dim > 2) { set_error("scan %d: dim must be 0, 1 or 2 on a volume (got %d)", s, sc.dim); return RF_ERR_INVALID_ARG; }
-        if (sc.weights < 0 || sc.weights >= d->n_weights) {
-            set_error("scan %d: weights must be 0..%d (got %d)", s, d->n_weights - 1, sc.weights);
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    return check_volume_extents(d->width, d->height, d->depth, d->n_planes);
-}
 
 int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool signal);
 
@@ -187,53 +191,27 @@ int check_volume_extents(int64_t width, int64_t height, int64_t depth, int32_t n
 
 int64_t var_max_extent() { return kVarMaxExtent; }
 
-int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
-    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+namespace {
+// every build_var_*_plan behind its null check: the lowered description validated as its kind, then built
+int build_lowered(const rf_var_desc &d, const VarKind &kind, rf_var_plan **out, int batch) {
     *out = nullptr;
-    int rc = validate(desc);
-    if (rc != RF_OK) return rc;
-    return build_checked(desc, out, batch, false);
+    const int rc = validate(&d, kind);
+    return rc == RF_OK ? build_checked(&d, out, batch, kind.signal) : rc;
+}
+int refuse_null() { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+}  // namespace
+
+int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch) {
+    return desc && out ? build_lowered(*desc, kImageKind, out, batch) : refuse_null();
 }
 
+// the plan of a 1 x length image, whose stages run the signal kernels
 int build_var_signal_plan(const rf_var_signal_desc *desc, rf_var_plan **out) {
-    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    *out = nullptr;
-    int rc = validate_signal(desc);
-    if (rc != RF_OK) return rc;
-    // the plan of a 1 x length image, whose stages run the signal kernels
-    rf_var_desc d{};
-    d.ndim = 2;
-    d.abi = desc->abi;
-    d.extent[0] = desc->length;
-    d.extent[1] = 1;
-    d.dtype = desc->dtype;
-    d.n_planes = desc->n_planes;
-    d.n_weights = desc->n_weights;
-    d.n_scans = desc->n_scans;
-    d.scans = desc->scans;
-    d.device = desc->device;
-    return build_checked(&d, out, 1, true);
+    return desc && out ? build_lowered(lowered(*desc, 2, desc->length, 1, 0), kSignalKind, out, 1) : refuse_null();
 }
 
 int build_var_volume_plan(const rf_var_volume_desc *desc, rf_var_plan **out) {
-    if (!desc || !out) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    *out = nullptr;
-    int rc = validate_volume(desc);
-    if (rc != RF_OK) return rc;
-    // (ndim = 3 reaches build_checked from here alone: rf_var_plan_create refuses it)
-    rf_var_desc d{};
-    d.ndim = 3;
-    d.abi = desc->abi;
-    d.extent[0] = desc->width;
-    d.extent[1] = desc->height;
-    d.extent[2] = desc->depth;
-    d.dtype = desc->dtype;
-    d.n_planes = desc->n_planes;
-    d.n_weights = desc->n_weights;
-    d.n_scans = desc->n_scans;
-    d.scans = desc->scans;
-    d.device = desc->device;
-    return build_checked(&d, out, 1, false);
+    return desc && out ? build_lowered(lowered(*desc, 3, desc->width, desc->height, desc->depth), kVolumeKind, out, 1) : refuse_null();
 }
 
 namespace {
@@ -583,237 +561,253 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
 
 namespace {
 
-// What run_var_distances and run_var_distances_backward refuse alike, in three parts: each checks pointers of its own (and the
-// backward `accumulate`) between them.  `kernel` names the launch in the message.
-int check_distance_counts(int32_t n_guide, int64_t width, int64_t height) {
-    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
-    if (width < 1 || height < 1) { set_error("width and height must be positive"); return RF_ERR_INVALID_ARG; }
+// One call of the distances or of their adjoint, on an image or on a volume: what the four entry points below hand to the shared
+// steps.  Each entry point sequences the refusals in its own documented order (they differ: see the four functions) around
+// check_distance_pointers and one of the two runners, which hold the alignment and overlap checks and the launch.
+struct DistanceCall {
+    bool volume, backward;
+    const void *const *guide;
+    int32_t n_guide, guide_u8;
+    int64_t width, height, depth;      // depth: a volume's, else 1
+    float scale, spacing_z;
+    const void *planes[3];             // dx, dy(, dz): written by the forward; or their gradients, read by the backward
+    void *const *grad_guide;           // the backward's
+    int32_t accumulate, device;
+    hipStream_t stream;
+    int32_t batch;                     // an image's (plan_smooth.cpp); a volume has none
+    int64_t guide_stride, grad_guide_stride;
+    int n() const { return volume ? 3 : 2; }
+    const char *noun() const { return volume ? "volume" : "plane"; }
+    size_t bytes() const { return (size_t)(width * height * depth) * sizeof(float); }      // of one f32 plane
+    // "dx and dy", "grad_dx, grad_dy or grad_dz", ...
+    std::string list(const char *conjunction) const {
+        const std::string p(backward ? "grad_" : "");
+        return volume ? p + "dx, " + p + "dy " + conjunction + " " + p + "dz" : p + "dx " + conjunction + " " + p + "dy";
+    }
+};
+
+int check_distance_counts(const DistanceCall &c) {
+    if (c.n_guide < 1 || c.n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, c.n_guide); return RF_ERR_INVALID_ARG; }
+    if (c.width < 1 || c.height < 1 || c.depth < 1) {
+        set_error("%s must be positive", c.volume ? "width, height and depth" : "width and height");
+        return RF_ERR_INVALID_ARG;
+    }
     return RF_OK;
 }
 
-int check_distance_scale(float scale) {
-    if (!std::isfinite(scale) || scale < 0.0f) { set_error("scale must be finite and not negative (got %g)", (double)scale); return RF_ERR_INVALID_ARG; }
+int check_distance_pointers(const DistanceCall &c) {
+    bool null = !c.guide || (c.backward && !c.grad_guide);
+    for (int k = 0; k < c.n(); k++) null = null || !c.planes[k];
+    if (null) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    for (int ch = 0; ch < c.n_guide; ch++) {
+        if (c.guide[ch] && (!c.backward || c.grad_guide[ch])) continue;
+        if (c.backward) set_error("guide %s %d: null pointer (the %s or its gradient)", c.noun(), ch, c.noun());
+        else set_error("guide %s %d: null pointer", c.noun(), ch);
+        return RF_ERR_INVALID_ARG;
+    }
     return RF_OK;
 }
 
-int check_distance_extents(const char *kernel, int64_t width, int64_t height) {
-    if (width % 4 != 0) {
-        set_error("%s moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", kernel, (long long)width);
+int check_distance_scale(const DistanceCall &c) {
+    if (!std::isfinite(c.scale) || c.scale < 0.0f) { set_error("scale must be finite and not negative (got %g)", (double)c.scale); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
+int check_distance_spacing(const DistanceCall &c) {
+    if (!std::isfinite(c.spacing_z) || !(c.spacing_z > 0.0f)) { set_error("spacing_z must be finite and positive (got %g)", (double)c.spacing_z); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
+int check_distance_accumulate(const DistanceCall &c) {
+    if (c.accumulate != 0 && c.accumulate != 1) { set_error("accumulate must be 0 or 1 (got %d)", c.accumulate); return RF_ERR_INVALID_ARG; }
+    return RF_OK;
+}
+
+// the accepted domain: a volume's is check_volume_extents with one plane
+int check_distance_extents(const DistanceCall &c) {
+    if (c.volume) return check_volume_extents(c.width, c.height, c.depth, 1);
+    if (c.width % 4 != 0) {
+        set_error("%s moves 16 bytes per lane along x: the width must be a multiple of 4 (got %lld)", c.backward ? "var_distances_grad" : "var_distances",
+                  (long long)c.width);
         return RF_ERR_UNSUPPORTED;
     }
-    if (width > kVarMaxExtent || height > kVarMaxExtent) {
-        set_error("extents %lld x %lld are above %lld", (long long)width, (long long)height, (long long)kVarMaxExtent);
+    if (c.width > kVarMaxExtent || c.height > kVarMaxExtent) {
+        set_error("extents %lld x %lld are above %lld", (long long)c.width, (long long)c.height, (long long)kVarMaxExtent);
         return RF_ERR_UNSUPPORTED;
     }
     return RF_OK;
 }
 
-// the first refusals of run_var_distances_volume and run_var_distances_volume_backward; both go on to check_distance_scale and
-// check_volume_extents (n_planes = 1) behind pointer checks of their own
-int check_volume_distance_counts(int32_t n_guide, int64_t width, int64_t height, int64_t depth) {
-    if (n_guide < 1 || n_guide > RF_MAX_PLANES) { set_error("n_guide must be 1..%d (got %d)", RF_MAX_PLANES, n_guide); return RF_ERR_INVALID_ARG; }
-    if (width < 1 || height < 1 || depth < 1) { set_error("width, height and depth must be positive"); return RF_ERR_INVALID_ARG; }
+int check_distance_planes_aligned(const DistanceCall &c) {
+    uintptr_t bits = 0;
+    for (int k = 0; k < c.n(); k++) bits |= (uintptr_t)c.planes[k];
+    if ((bits & 15u) != 0) { set_error("%s must be 16-byte aligned", c.list("and").c_str()); return RF_ERR_INVALID_ARG; }
     return RF_OK;
+}
+
+// The forward behind its entry point's refusals: alignment, overlaps, one launch.
+int run_distances_forward(const DistanceCall &c) {
+    int rc = check_distance_planes_aligned(c);
+    if (rc != RF_OK) return rc;
+    const uintptr_t guide_align = c.guide_u8 ? 3u : 15u;
+    for (int ch = 0; ch < c.n_guide; ch++)
+        if (((uintptr_t)c.guide[ch] & guide_align) != 0) {
+            set_error("guide %s %d: %s guide %ss must be %u-byte aligned", c.noun(), ch, c.guide_u8 ? "uint8" : "f32", c.noun(), (unsigned)guide_align + 1);
+            return RF_ERR_INVALID_ARG;
+        }
+    const size_t out_bytes = c.bytes(), guide_bytes = c.guide_u8 ? out_bytes / sizeof(float) : out_bytes;
+    for (int k = 0; k < c.n(); k++)
+        for (int q = k + 1; q < c.n(); q++)
+            if (overlap(c.planes[k], out_bytes * (size_t)c.batch, c.planes[q], out_bytes * (size_t)c.batch)) {
+                set_error("%s", c.volume ? "dx, dy and dz overlap each other" : "dx overlaps dy");
+                return RF_ERR_INVALID_ARG;
+            }
+    // (a batch comes from plan_smooth.cpp: the distance planes are the plan's own, which no plane of a caller overlaps)
+    for (int ch = 0; ch < c.n_guide && c.batch == 1; ch++)
+        for (int k = 0; k < c.n(); k++)
+            if (overlap(c.planes[k], out_bytes, c.guide[ch], guide_bytes)) {
+                set_error("guide %s %d overlaps %s: a lane reads its neighbours' samples", c.noun(), ch, c.list("or").c_str());
+                return RF_ERR_INVALID_ARG;
+            }
+    if (c.device >= 0) RF_HIP_CHECK(hipSetDevice(c.device));
+    if (c.volume) {
+        VarDistVolumeArgs a{};
+        for (int ch = 0; ch < c.n_guide; ch++) a.guide[ch] = c.guide[ch];
+        a.dx = (float *)c.planes[0];
+        a.dy = (float *)c.planes[1];
+        a.dz = (float *)c.planes[2];
+        a.width = (int32_t)c.width;
+        a.height = (int32_t)c.height;
+        a.depth = (int32_t)c.depth;
+        a.n_guide = c.n_guide;
+        a.scale = c.scale;
+        a.spacing_z = c.spacing_z;
+        return launch_var_distances_volume(a, c.guide_u8 != 0, c.stream);
+    }
+    VarDistArgs a{};
+    for (int ch = 0; ch < c.n_guide; ch++) a.guide[ch] = c.guide[ch];
+    a.dx = (float *)c.planes[0];
+    a.dy = (float *)c.planes[1];
+    a.width = (int32_t)c.width;
+    a.height = (int32_t)c.height;
+    a.n_guide = c.n_guide;
+    a.scale = c.scale;
+    a.batch = c.batch;
+    a.guide_stride = c.guide_stride;
+    return launch_var_distances(a, c.guide_u8 != 0, c.stream);
+}
+
+// The adjoint behind its entry point's refusals: alignment, overlaps, one launch.
+int run_distances_backward(const DistanceCall &c) {
+    int rc = check_distance_planes_aligned(c);
+    if (rc != RF_OK) return rc;
+    for (int ch = 0; ch < c.n_guide; ch++)
+        if ((((uintptr_t)c.guide[ch] | (uintptr_t)c.grad_guide[ch]) & 15u) != 0) {
+            set_error("guide %s %d: f32 guide %ss and their gradients must be 16-byte aligned", c.noun(), ch, c.noun());
+            return RF_ERR_INVALID_ARG;
+        }
+    // a gradient plane is written while other lanes still read: it overlaps nothing that is read and no other gradient plane
+    // (a batch comes from plan_smooth.cpp, which has checked every extent of the caller's against every other, sorted; the distance
+    // gradients are then the plan's own planes)
+    const size_t bytes = c.bytes();
+    for (int ch = 0; ch < c.n_guide && c.batch == 1; ch++) {
+        const void *o = c.grad_guide[ch];
+        for (int k = 0; k < c.n(); k++)
+            if (overlap(o, bytes, c.planes[k], bytes)) {
+                set_error("gradient of guide %s %d overlaps %s: a lane reads its neighbours' samples", c.noun(), ch, c.list("or").c_str());
+                return RF_ERR_INVALID_ARG;
+            }
+        for (int q = 0; q < c.n_guide; q++) {
+            if (overlap(o, bytes, c.guide[q], bytes)) {
+                set_error("gradient of guide %s %d overlaps guide %s %d: a lane reads its neighbours' samples", c.noun(), ch, c.noun(), q);
+                return RF_ERR_INVALID_ARG;
+            }
+            if (q > ch && overlap(o, bytes, c.grad_guide[q], bytes)) {
+                set_error("gradient of guide %s %d overlaps gradient of guide %s %d", c.noun(), ch, c.noun(), q);
+                return RF_ERR_INVALID_ARG;
+            }
+        }
+    }
+    if (c.device >= 0) RF_HIP_CHECK(hipSetDevice(c.device));
+    if (c.volume) {
+        VarDistVolumeGradArgs a{};
+        for (int ch = 0; ch < c.n_guide; ch++) {
+            a.guide[ch] = (const float *)c.guide[ch];
+            a.grad_guide[ch] = (float *)c.grad_guide[ch];
+        }
+        a.gdx = (const float *)c.planes[0];
+        a.gdy = (const float *)c.planes[1];
+        a.gdz = (const float *)c.planes[2];
+        a.width = (int32_t)c.width;
+        a.height = (int32_t)c.height;
+        a.depth = (int32_t)c.depth;
+        a.n_guide = c.n_guide;
+        a.accumulate = c.accumulate;
+        a.scale = c.scale;
+        return launch_var_distances_volume_grad(a, c.stream);
+    }
+    VarDistGradArgs a{};
+    for (int ch = 0; ch < c.n_guide; ch++) {
+        a.guide[ch] = (const float *)c.guide[ch];
+        a.grad_guide[ch] = (float *)c.grad_guide[ch];
+    }
+    a.gdx = (const float *)c.planes[0];
+    a.gdy = (const float *)c.planes[1];
+    a.width = (int32_t)c.width;
+    a.height = (int32_t)c.height;
+    a.n_guide = c.n_guide;
+    a.accumulate = c.accumulate;
+    a.scale = c.scale;
+    a.batch = c.batch;
+    a.guide_stride = c.guide_stride;
+    a.grad_guide_stride = c.grad_guide_stride;
+    return launch_var_distances_grad(a, c.stream);
+}
+
+// the first refusal of `steps`, in their order; else what `run` answers
+using DistanceStep = int (*)(const DistanceCall &);
+int run_distance_steps(const DistanceCall &c, std::initializer_list<DistanceStep> steps, DistanceStep run) {
+    for (DistanceStep step : steps)
+        if (int rc = step(c); rc != RF_OK) return rc;
+    return run(c);
 }
 
 }  // namespace
 
+// The four entry points: each its own order of refusals, as recfilter_amd.h documents it.  The image backward decides `accumulate`
+// before the extents, the volume backward the volume's domain before `accumulate`; the volume forward has spacing_z between the
+// scale and the domain.
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                       void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch, int64_t guide_stride) {
-    int rc = check_distance_counts(n_guide, width, height);
-    if (rc != RF_OK) return rc;
-    if (!guide_planes || !dx || !dy) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if (!guide_planes[ch]) { set_error("guide plane %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
-    rc = check_distance_scale(scale);
-    if (rc == RF_OK) rc = check_distance_extents("var_distances", width, height);
-    if (rc != RF_OK) return rc;
-    if ((((uintptr_t)dx | (uintptr_t)dy) & 15u) != 0) { set_error("dx and dy must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
-    const uintptr_t guide_align = guide_u8 ? 3u : 15u;
-    for (int ch = 0; ch < n_guide; ch++)
-        if (((uintptr_t)guide_planes[ch] & guide_align) != 0) {
-            set_error("guide plane %d: %s guide planes must be %u-byte aligned", ch, guide_u8 ? "uint8" : "f32", (unsigned)guide_align + 1);
-            return RF_ERR_INVALID_ARG;
-        }
-    const size_t samples = (size_t)(width * height), out_bytes = samples * sizeof(float), guide_bytes = samples * (guide_u8 ? 1 : sizeof(float));
-    if (overlap(dx, out_bytes * (size_t)batch, dy, out_bytes * (size_t)batch)) { set_error("dx overlaps dy"); return RF_ERR_INVALID_ARG; }
-    // (a batch comes from plan_smooth.cpp: dx and dy are the plan's own planes, which no plane of a caller overlaps)
-    for (int ch = 0; ch < n_guide && batch == 1; ch++)
-        if (overlap(dx, out_bytes, guide_planes[ch], guide_bytes) || overlap(dy, out_bytes, guide_planes[ch], guide_bytes)) {
-            set_error("guide plane %d overlaps dx or dy: a lane reads its neighbours' samples", ch);
-            return RF_ERR_INVALID_ARG;
-        }
-    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
-    VarDistArgs a{};
-    for (int ch = 0; ch < n_guide; ch++) a.guide[ch] = guide_planes[ch];
-    a.dx = (float *)dx;
-    a.dy = (float *)dy;
-    a.width = (int32_t)width;
-    a.height = (int32_t)height;
-    a.n_guide = n_guide;
-    a.scale = scale;
-    a.batch = batch;
-    a.guide_stride = guide_stride;
-    return launch_var_distances(a, guide_u8 != 0, stream);
+    const DistanceCall c{false, false, guide_planes, n_guide, guide_u8, width, height, 1, scale, 1.0f, {dx, dy, nullptr}, nullptr, 0, device, stream,
+                         batch, guide_stride, 0};
+    return run_distance_steps(c, {check_distance_counts, check_distance_pointers, check_distance_scale, check_distance_extents}, run_distances_forward);
 }
 
 int run_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
                              float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, hipStream_t stream) {
-    int rc = check_volume_distance_counts(n_guide, width, height, depth);
-    if (rc != RF_OK) return rc;
-    if (!guide_volumes || !dx || !dy || !dz) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if (!guide_volumes[ch]) { set_error("guide volume %d: null pointer", ch); return RF_ERR_INVALID_ARG; }
-    rc = check_distance_scale(scale);
-    if (rc != RF_OK) return rc;
-    if (!std::isfinite(spacing_z) || !(spacing_z > 0.0f)) { set_error("spacing_z must be finite and positive (got %g)", (double)spacing_z); return RF_ERR_INVALID_ARG; }
-    rc = check_volume_extents(width, height, depth, 1);
-    if (rc != RF_OK) return rc;
-    if ((((uintptr_t)dx | (uintptr_t)dy | (uintptr_t)dz) & 15u) != 0) { set_error("dx, dy and dz must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
-    const uintptr_t guide_align = guide_u8 ? 3u : 15u;
-    for (int ch = 0; ch < n_guide; ch++)
-        if (((uintptr_t)guide_volumes[ch] & guide_align) != 0) {
-            set_error("guide volume %d: %s guide volumes must be %u-byte aligned", ch, guide_u8 ? "uint8" : "f32", (unsigned)guide_align + 1);
-            return RF_ERR_INVALID_ARG;
-        }
-    const size_t samples = (size_t)(width * height * depth), out_bytes = samples * sizeof(float), guide_bytes = samples * (guide_u8 ? 1 : sizeof(float));
-    if (overlap(dx, out_bytes, dy, out_bytes) || overlap(dx, out_bytes, dz, out_bytes) || overlap(dy, out_bytes, dz, out_bytes)) {
-        set_error("dx, dy and dz overlap each other");
-        return RF_ERR_INVALID_ARG;
-    }
-    for (int ch = 0; ch < n_guide; ch++)
-        if (overlap(dx, out_bytes, guide_volumes[ch], guide_bytes) || overlap(dy, out_bytes, guide_volumes[ch], guide_bytes) ||
-            overlap(dz, out_bytes, guide_volumes[ch], guide_bytes)) {
-            set_error("guide volume %d overlaps dx, dy or dz: a lane reads its neighbours' samples", ch);
-            return RF_ERR_INVALID_ARG;
-        }
-    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
-    VarDistVolumeArgs a{};
-    for (int ch = 0; ch < n_guide; ch++) a.guide[ch] = guide_volumes[ch];
-    a.dx = (float *)dx;
-    a.dy = (float *)dy;
-    a.dz = (float *)dz;
-    a.width = (int32_t)width;
-    a.height = (int32_t)height;
-    a.depth = (int32_t)depth;
-    a.n_guide = n_guide;
-    a.scale = scale;
-    a.spacing_z = spacing_z;
-    return launch_var_distances_volume(a, guide_u8 != 0, stream);
+    const DistanceCall c{true, false, guide_volumes, n_guide, guide_u8, width, height, depth, scale, spacing_z, {dx, dy, dz}, nullptr, 0, device, stream,
+                         1, 0, 0};
+    return run_distance_steps(c, {check_distance_counts, check_distance_pointers, check_distance_scale, check_distance_spacing, check_distance_extents},
+                              run_distances_forward);
 }
 
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
                                const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
                                int32_t batch, int64_t guide_stride, int64_t grad_guide_stride) {
-    int rc = check_distance_counts(n_guide, width, height);
-    if (rc != RF_OK) return rc;
-    if (!guide_planes || !grad_dx || !grad_dy || !grad_guide_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if (!guide_planes[ch] || !grad_guide_planes[ch]) { set_error("guide plane %d: null pointer (the plane or its gradient)", ch); return RF_ERR_INVALID_ARG; }
-    rc = check_distance_scale(scale);
-    if (rc != RF_OK) return rc;
-    if (accumulate != 0 && accumulate != 1) { set_error("accumulate must be 0 or 1 (got %d)", accumulate); return RF_ERR_INVALID_ARG; }
-    rc = check_distance_extents("var_distances_grad", width, height);
-    if (rc != RF_OK) return rc;
-    if ((((uintptr_t)grad_dx | (uintptr_t)grad_dy) & 15u) != 0) { set_error("grad_dx and grad_dy must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if ((((uintptr_t)guide_planes[ch] | (uintptr_t)grad_guide_planes[ch]) & 15u) != 0) {
-            set_error("guide plane %d: f32 guide planes and their gradients must be 16-byte aligned", ch);
-            return RF_ERR_INVALID_ARG;
-        }
-    // a gradient plane is written while other lanes still read: it overlaps nothing that is read and no other gradient plane
-    // (a batch comes from plan_smooth.cpp, which has checked every extent of the caller's against every other, sorted; grad_dx and
-    // grad_dy are then the plan's own planes)
-    const size_t bytes = (size_t)(width * height) * sizeof(float);
-    for (int ch = 0; ch < n_guide && batch == 1; ch++) {
-        const void *o = grad_guide_planes[ch];
-        if (overlap(o, bytes, grad_dx, bytes) || overlap(o, bytes, grad_dy, bytes)) {
-            set_error("gradient of guide plane %d overlaps grad_dx or grad_dy: a lane reads its neighbours' samples", ch);
-            return RF_ERR_INVALID_ARG;
-        }
-        for (int q = 0; q < n_guide; q++) {
-            if (overlap(o, bytes, guide_planes[q], bytes)) {
-                set_error("gradient of guide plane %d overlaps guide plane %d: a lane reads its neighbours' samples", ch, q);
-                return RF_ERR_INVALID_ARG;
-            }
-            if (q > ch && overlap(o, bytes, grad_guide_planes[q], bytes)) {
-                set_error("gradient of guide plane %d overlaps gradient of guide plane %d", ch, q);
-                return RF_ERR_INVALID_ARG;
-            }
-        }
-    }
-    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
-    VarDistGradArgs a{};
-    for (int ch = 0; ch < n_guide; ch++) {
-        a.guide[ch] = (const float *)guide_planes[ch];
-        a.grad_guide[ch] = (float *)grad_guide_planes[ch];
-    }
-    a.gdx = (const float *)grad_dx;
-    a.gdy = (const float *)grad_dy;
-    a.width = (int32_t)width;
-    a.height = (int32_t)height;
-    a.n_guide = n_guide;
-    a.accumulate = accumulate;
-    a.scale = scale;
-    a.batch = batch;
-    a.guide_stride = guide_stride;
-    a.grad_guide_stride = grad_guide_stride;
-    return launch_var_distances_grad(a, stream);
+    const DistanceCall c{false, true, guide_planes, n_guide, 0, width, height, 1, scale, 1.0f, {grad_dx, grad_dy, nullptr}, grad_guide_planes, accumulate,
+                         device, stream, batch, guide_stride, grad_guide_stride};
+    return run_distance_steps(c, {check_distance_counts, check_distance_pointers, check_distance_scale, check_distance_accumulate, check_distance_extents},
+                              run_distances_backward);
 }
 
 int run_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth, float scale,
                                       const void *grad_dx, const void *grad_dy, const void *grad_dz, void *const *grad_guide_volumes,
                                       int32_t accumulate, int32_t device, hipStream_t stream) {
-    int rc = check_volume_distance_counts(n_guide, width, height, depth);
-    if (rc != RF_OK) return rc;
-    if (!guide_volumes || !grad_dx || !grad_dy || !grad_dz || !grad_guide_volumes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if (!guide_volumes[ch] || !grad_guide_volumes[ch]) { set_error("guide volume %d: null pointer (the volume or its gradient)", ch); return RF_ERR_INVALID_ARG; }
-    rc = check_distance_scale(scale);
-    if (rc == RF_OK) rc = check_volume_extents(width, height, depth, 1);
-    if (rc != RF_OK) return rc;
-    if (accumulate != 0 && accumulate != 1) { set_error("accumulate must be 0 or 1 (got %d)", accumulate); return RF_ERR_INVALID_ARG; }
-    if ((((uintptr_t)grad_dx | (uintptr_t)grad_dy | (uintptr_t)grad_dz) & 15u) != 0) { set_error("grad_dx, grad_dy and grad_dz must be 16-byte aligned"); return RF_ERR_INVALID_ARG; }
-    for (int ch = 0; ch < n_guide; ch++)
-        if ((((uintptr_t)guide_volumes[ch] | (uintptr_t)grad_guide_volumes[ch]) & 15u) != 0) {
-            set_error("guide volume %d: f32 guide volumes and their gradients must be 16-byte aligned", ch);
-            return RF_ERR_INVALID_ARG;
-        }
-    // a gradient volume is written while other lanes still read: it overlaps nothing that is read and no other gradient volume
-    const size_t bytes = (size_t)(width * height * depth) * sizeof(float);
-    for (int ch = 0; ch < n_guide; ch++) {
-        const void *o = grad_guide_volumes[ch];
-        if (overlap(o, bytes, grad_dx, bytes) || overlap(o, bytes, grad_dy, bytes) || overlap(o, bytes, grad_dz, bytes)) {
-            set_error("gradient of guide volume %d overlaps grad_dx, grad_dy or grad_dz: a lane reads its neighbours' samples", ch);
-            return RF_ERR_INVALID_ARG;
-        }
-        for (int q = 0; q < n_guide; q++) {
-            if (overlap(o, bytes, guide_volumes[q], bytes)) {
-                set_error("gradient of guide volume %d overlaps guide volume %d: a lane reads its neighbours' samples", ch, q);
-                return RF_ERR_INVALID_ARG;
-            }
-            if (q > ch && overlap(o, bytes, grad_guide_volumes[q], bytes)) {
-                set_error("gradient of guide volume %d overlaps gradient of guide volume %d", ch, q);
-                return RF_ERR_INVALID_ARG;
-            }
-        }
-    }
-    if (device >= 0) RF_HIP_CHECK(hipSetDevice(device));
-    VarDistVolumeGradArgs a{};
-    for (int ch = 0; ch < n_guide; ch++) {
-        a.guide[ch] = (const float *)guide_volumes[ch];
-        a.grad_guide[ch] = (float *)grad_guide_volumes[ch];
-    }
-    a.gdx = (const float *)grad_dx;
-    a.gdy = (const float *)grad_dy;
-    a.gdz = (const float *)grad_dz;
-    a.width = (int32_t)width;
-    a.height = (int32_t)height;
-    a.depth = (int32_t)depth;
-    a.n_guide = n_guide;
-    a.accumulate = accumulate;
-    a.scale = scale;
-    return launch_var_distances_volume_grad(a, stream);
+    const DistanceCall c{true, true, guide_volumes, n_guide, 0, width, height, depth, scale, 1.0f, {grad_dx, grad_dy, grad_dz}, grad_guide_volumes,
+                         accumulate, device, stream, 1, 0, 0};
+    return run_distance_steps(c, {check_distance_counts, check_distance_pointers, check_distance_scale, check_distance_extents, check_distance_accumulate},
+                              run_distances_backward);
 }
 
 }  // namespace rf

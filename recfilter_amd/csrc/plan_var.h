@@ -55,12 +55,12 @@ struct rf_var_plan {
 };
 
 namespace rf {
+// rf_var_plan_create, _create_signal (planes are dense f32 signals of desc->length samples) and _create_volume (dense f32 volumes): each
+// description is lowered to an rf_var_desc and checked by the one validator as its kind
 int build_var_plan(const rf_var_desc *desc, rf_var_plan **out, int batch = 1);
-// rf_var_plan_create_signal: an ordinary plan whose planes are dense f32 signals of desc->length samples
 int build_var_signal_plan(const rf_var_signal_desc *desc, rf_var_plan **out);
-// rf_var_plan_create_volume: an ordinary plan whose planes are dense f32 volumes
 int build_var_volume_plan(const rf_var_volume_desc *desc, rf_var_plan **out);
-// what rf_var_plan_create_volume, rf_var_distances_volume and rf_smooth_plan_create_volume refuse alike (the message names the limit):
+// what rf_var_plan_create_volume, the distances of a volume and rf_smooth_plan_create_volume refuse alike (the message names the limit):
 // extents below 1 (RF_ERR_INVALID_ARG); a width that is no multiple of 4, an extent above 2^21, width * height above 2^30,
 // depth * n_planes above 65535 (RF_ERR_UNSUPPORTED)
 int check_volume_extents(int64_t width, int64_t height, int64_t depth, int32_t n_planes);
@@ -106,18 +106,18 @@ struct VarBackwardIo {
 int ensure_var_grad_planes(rf_var_plan *plan);
 int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, LaunchTimer &timer);
 int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
-// batch > 1 (plan_smooth.cpp): image b's guide planes are guide_stride samples behind image 0's, dx and dy hold `batch` dense planes
+// The distances and their adjoints, one launch each (plan_var.cpp: one argument record, one runner per direction).  The image forms
+// take a batch (plan_smooth.cpp): image b's guide planes are guide_stride samples behind image 0's -- their gradients
+// grad_guide_stride -- and dx, dy (grad_dx, grad_dy) hold `batch` dense planes.  The volume forms: d_x, d_y slice by slice as the image
+// form gives them, d_z along z from spacing_z; no batch.  accumulate: added to what the gradient planes hold.
 int run_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                       void *dx, void *dy, int32_t device, hipStream_t stream, int32_t batch = 1, int64_t guide_stride = 0);
-// rf_var_distances_volume: d_x, d_y slice by slice as run_var_distances forms them, d_z along z from spacing_z; one launch
 int run_var_distances_volume(const void *const *guide_volumes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, int64_t depth,
                              float scale, float spacing_z, void *dx, void *dy, void *dz, int32_t device, hipStream_t stream);
-// rf_var_distances_volume_backward: the adjoint of run_var_distances_volume for f32 guides, one launch; accumulate: added to what the
-// gradient volumes hold
-int run_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth, float scale,
-                                      const void *grad_dx, const void *grad_dy, const void *grad_dz, void *const *grad_guide_volumes,
-                                      int32_t accumulate, int32_t device, hipStream_t stream);
 int run_var_distances_backward(const void *const *guide_planes, int32_t n_guide, int64_t width, int64_t height, float scale, const void *grad_dx,
                                const void *grad_dy, void *const *grad_guide_planes, int32_t accumulate, int32_t device, hipStream_t stream,
                                int32_t batch = 1, int64_t guide_stride = 0, int64_t grad_guide_stride = 0);
+int run_var_distances_volume_backward(const void *const *guide_volumes, int32_t n_guide, int64_t width, int64_t height, int64_t depth, float scale,
+                                      const void *grad_dx, const void *grad_dy, const void *grad_dz, void *const *grad_guide_volumes,
+                                      int32_t accumulate, int32_t device, hipStream_t stream);
 }  // namespace rf

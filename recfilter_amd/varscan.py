@@ -54,6 +54,19 @@ def _plane_pointer(t, shape, dtype, dtype_text: str, what: str) -> int:
     return t.data_ptr()
 
 
+def _host_only_nulls(plan, *counts):
+    """None -- or, for a host-only plan, which the library refuses to run (there are no device tensors to take pointers from, and no
+    stream): a null pointer array for every count, None where the count is None"""
+    if plan._desc.device != capi.RF_DEVICE_HOST_ONLY:
+        return None
+    return [None if n is None else (ctypes.c_void_p * max(n, 1))() for n in counts]
+
+
+def _device_index(t) -> int:
+    import torch
+    return t.device.index if t.device.index is not None else torch.cuda.current_device()
+
+
 class VarPlan(_PlanHandle):
     """A list of at most capi.RF_VAR_MAX_SCANS scans  y[i] = (1 - w[i]) x[i] + w[i] y[i-1]  (causal; the anticausal one couples
     sample i to i+1 through w[i+1]) over `planes` f32 planes of `shape` = (height, width) that share `n_weights` weight planes.
@@ -61,20 +74,24 @@ class VarPlan(_PlanHandle):
     _destroy = "rf_var_plan_destroy"
 
     def __init__(self, shape: Sequence[int], scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1):
-        L = capi.lib()
         shape = tuple(int(s) for s in shape)
         if not 1 <= len(shape) <= capi.RF_MAX_DIMS:
             raise ValueError(f"1..{capi.RF_MAX_DIMS} dimensions, got shape {shape}")
+        d = capi.VarDesc()
+        d.ndim = len(shape)
+        for i, e in enumerate(reversed(shape)):      # (y, x) -> extent[0] = x
+            d.extent[i] = e
+        self._create("rf_var_plan_create", d, shape, scans, planes, n_weights, device)
+
+    def _create(self, create: str, d, shape, scans, planes, n_weights, device) -> "VarPlan":
+        """what the three kinds of plan share: the scan array, the common fields of the description `d` (which holds its kind's own
+        already), the attributes, and the call of the library's `create`"""
         scans = list(scans)
         self._scan_arr = (capi.VarScanDesc * max(len(scans), 1))()
         for i, (dim, causal, weights) in enumerate(scans):
             s = self._scan_arr[i]
             s.dim, s.causal, s.weights = int(dim), int(bool(causal)), int(weights)
-        d = capi.VarDesc()
         d.abi = capi.RF_ABI
-        d.ndim = len(shape)
-        for i, e in enumerate(reversed(shape)):      # (y, x) -> extent[0] = x
-            d.extent[i] = e
         d.dtype = capi.RF_F32
         d.n_planes, d.n_weights = int(planes), int(n_weights)
         d.n_scans = len(scans)
@@ -85,7 +102,8 @@ class VarPlan(_PlanHandle):
         self.shape, self.planes, self.n_weights = shape, int(planes), int(n_weights)
         self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
         self._h = ctypes.c_void_p()
-        capi.check(L.rf_var_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
+        capi.check(getattr(capi.lib(), create)(ctypes.byref(d), ctypes.byref(self._h)))
+        return self
 
     @classmethod
     def signal(cls, length: int, scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1) -> "VarPlan":
@@ -93,28 +111,9 @@ class VarPlan(_PlanHandle):
         of 4, up to 2**30) that share `n_weights` weight signals; every scan has dim 0.  `shape` is (length,), and every method
         works as on an image plan, a plane being a 1-D tensor.  A lane owns 64 samples, a wave 4096; the launches are
         var_tails_1d, var_carry_1d, var_pass2_1d per stage."""
-        L = capi.lib()
-        self = cls.__new__(cls)
-        scans = list(scans)
-        self._scan_arr = (capi.VarScanDesc * max(len(scans), 1))()
-        for i, (dim, causal, weights) in enumerate(scans):
-            s = self._scan_arr[i]
-            s.dim, s.causal, s.weights = int(dim), int(bool(causal)), int(weights)
         d = capi.VarSignalDesc()
-        d.abi = capi.RF_ABI
         d.length = int(length)
-        d.dtype = capi.RF_F32
-        d.n_planes, d.n_weights = int(planes), int(n_weights)
-        d.n_scans = len(scans)
-        d.scans = ctypes.cast(self._scan_arr, ctypes.POINTER(capi.VarScanDesc))
-        d.device = int(device)
-        d.flags = 0
-        self._desc = d
-        self.shape, self.planes, self.n_weights = (int(length),), int(planes), int(n_weights)
-        self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
-        self._h = ctypes.c_void_p()
-        capi.check(L.rf_var_plan_create_signal(ctypes.byref(d), ctypes.byref(self._h)))
-        return self
+        return cls.__new__(cls)._create("rf_var_plan_create_signal", d, (int(length),), scans, planes, n_weights, device)
 
     @classmethod
     def volume(cls, shape: Sequence[int], scans: Sequence[VarScan], planes: int = 1, n_weights: int = 1, device: int = -1) -> "VarPlan":
@@ -124,31 +123,12 @@ class VarPlan(_PlanHandle):
         launch, each bit for bit what VarPlan((height, width)) gives on it; a z stage is bit for bit the y stage of the 2-D plan
         on the (depth, height * width) reshaped volume.  Three launches per stage whatever the depth (var_tails_z, var_carry,
         var_pass2_z for z).  width % 4 == 0, extents up to 2**21, height * width <= 2**30, depth * planes <= 65535."""
-        L = capi.lib()
-        self = cls.__new__(cls)
         shape = tuple(int(s) for s in shape)
         if len(shape) != 3:
             raise ValueError(f"shape must be (depth, height, width), got {shape}")
-        scans = list(scans)
-        self._scan_arr = (capi.VarScanDesc * max(len(scans), 1))()
-        for i, (dim, causal, weights) in enumerate(scans):
-            s = self._scan_arr[i]
-            s.dim, s.causal, s.weights = int(dim), int(bool(causal)), int(weights)
         d = capi.VarVolumeDesc()
-        d.abi = capi.RF_ABI
         d.depth, d.height, d.width = shape
-        d.dtype = capi.RF_F32
-        d.n_planes, d.n_weights = int(planes), int(n_weights)
-        d.n_scans = len(scans)
-        d.scans = ctypes.cast(self._scan_arr, ctypes.POINTER(capi.VarScanDesc))
-        d.device = int(device)
-        d.flags = 0
-        self._desc = d
-        self.shape, self.planes, self.n_weights = shape, int(planes), int(n_weights)
-        self.scans = [(int(dim), bool(causal), int(weights)) for dim, causal, weights in scans]
-        self._h = ctypes.c_void_p()
-        capi.check(L.rf_var_plan_create_volume(ctypes.byref(d), ctypes.byref(self._h)))
-        return self
+        return cls.__new__(cls)._create("rf_var_plan_create_volume", d, shape, scans, planes, n_weights, device)
 
     # -- queries ----------------------------------------------------------------------------
     @property
@@ -172,10 +152,9 @@ class VarPlan(_PlanHandle):
     def _arguments(self, ins, weights, outs, stream):
         """(input, weight and output pointers, the outputs, the stream's handle)"""
         import torch
-        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from, and no stream)
-            nulls = lambda n: (ctypes.c_void_p * n)()      # noqa: E731
-            return nulls(self.planes), nulls(self.n_weights), nulls(self.planes), None, ctypes.c_void_p()
+        nulls = _host_only_nulls(self, self.planes, self.n_weights, self.planes)
+        if nulls:
+            return (*nulls, None, ctypes.c_void_p())
         if outs is None:
             outs = [torch.empty_like(t) for t in ins]
         return (self._pointers(ins, self.planes, "input"), self._pointers(weights, self.n_weights, "weight"),
@@ -226,11 +205,10 @@ class VarPlan(_PlanHandle):
     def _backward_arguments(self, ins, weights, grad_outs, grad_ins, grad_weights, stream):
         """(the five pointer arrays, grad_ins, grad_weights, the stream's handle)"""
         import torch
-        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from, and no stream)
-            nulls = lambda n: (ctypes.c_void_p * n)()      # noqa: E731
-            return (nulls(self.planes) if ins is not None else None, nulls(self.n_weights), nulls(self.planes), nulls(self.planes),
-                    nulls(self.n_weights) if grad_weights is not None else None, None, None, ctypes.c_void_p())
+        nulls = _host_only_nulls(self, self.planes if ins is not None else None, self.n_weights, self.planes, self.planes,
+                                 self.n_weights if grad_weights is not None else None)
+        if nulls:
+            return (*nulls, None, None, ctypes.c_void_p())
         if grad_ins is None:
             grad_ins = [torch.empty_like(t) for t in grad_outs]
         pgw = None
@@ -344,24 +322,28 @@ def _var_scan_function():
     return _function
 
 
+# plans of the functional front ends, one cache per kind of plan, every one keyed (shape, scans, planes, n_weights, device)
 _scan_plans: Dict[tuple, VarPlan] = {}
+_volume_plans: Dict[tuple, VarPlan] = {}
+_signal_plans: Dict[tuple, VarPlan] = {}
+_smooth_plans: Dict[tuple, VarPlan] = {}      # edge_aware_smooth, forms "planes" and "power"
+
+
+def _cached_plan(cache: Dict[tuple, VarPlan], create, shape, scans, planes: int, n_weights: int, device) -> VarPlan:
+    """the plan of `cache` for these arguments, made by `create` (VarPlan, VarPlan.signal or VarPlan.volume) where there is none yet"""
+    key = (shape, tuple((int(d), bool(c), int(k)) for d, c, k in scans), int(planes), int(n_weights), device)
+    plan = cache.get(key)
+    if plan is None:
+        plan = cache[key] = create(key[0], key[1], planes=key[2], n_weights=key[3], device=device)
+    return plan
 
 
 def var_scan(ins, weights, scans):
     """`VarPlan.apply` without the plan: `scans` [(dim, causal, weight index), ...] on the device planes `ins` with the weight
     planes `weights`, differentiable with respect to both.  Plans are cached by shape, scans, plane counts and device; calls that
     share a plan are ordered by the caller (one stream)."""
-    import torch
     ins, weights = list(ins), list(weights)
-    device = ins[0].device.index if ins[0].device.index is not None else torch.cuda.current_device()
-    key = (tuple(ins[0].shape), tuple((int(d), bool(c), int(k)) for d, c, k in scans), len(ins), len(weights), device)
-    plan = _scan_plans.get(key)
-    if plan is None:
-        plan = _scan_plans[key] = VarPlan(key[0], key[1], planes=len(ins), n_weights=len(weights), device=device)
-    return plan.apply(ins, weights)
-
-
-_volume_plans: Dict[tuple, VarPlan] = {}
+    return _cached_plan(_scan_plans, VarPlan, tuple(ins[0].shape), scans, len(ins), len(weights), _device_index(ins[0])).apply(ins, weights)
 
 
 def var_scan_volume(ins, weights, scans):
@@ -374,24 +356,9 @@ def var_scan_volume(ins, weights, scans):
     shape = tuple(int(s) for s in ins[0].shape)
     if len(shape) != 3 or any(tuple(t.shape) != shape for t in ins + weights):
         raise ValueError("var_scan_volume takes 3-D volumes (D, H, W) of one shape")
-    device = ins[0].device.index if ins[0].device.index is not None else torch.cuda.current_device()
-    key = (shape, tuple((int(d), bool(c), int(k)) for d, c, k in scans), len(ins), len(weights), device)
-    plan = _volume_plans.get(key)
-    if plan is None:
-        plan = _volume_plans[key] = VarPlan.volume(key[0], key[1], planes=len(ins), n_weights=len(weights), device=device)
+    plan = _cached_plan(_volume_plans, VarPlan.volume, shape, scans, len(ins), len(weights), _device_index(ins[0]))
     with torch.cuda.device(ins[0].device):
         return plan.apply(ins, weights)
-
-
-_signal_plans: Dict[tuple, VarPlan] = {}
-
-
-def _signal_plan(length: int, scans, planes: int, n_weights: int, device) -> VarPlan:
-    key = (int(length), tuple((int(d), bool(c), int(k)) for d, c, k in scans), int(planes), int(n_weights), device)
-    plan = _signal_plans.get(key)
-    if plan is None:
-        plan = _signal_plans[key] = VarPlan.signal(key[0], key[1], planes=planes, n_weights=n_weights, device=device)
-    return plan
 
 
 def _padded(t, pad: int, value: float):
@@ -413,8 +380,7 @@ def var_scan_signal(ins, weights, scans):
     if any(t.dim() != 1 or int(t.shape[0]) != n for t in ins + weights):
         raise ValueError("var_scan_signal takes 1-D signals of one length")
     pad = -n % 4
-    device = ins[0].device.index if ins[0].device.index is not None else torch.cuda.current_device()
-    plan = _signal_plan(n + pad, scans, len(ins), len(weights), device)
+    plan = _cached_plan(_signal_plans, VarPlan.signal, n + pad, scans, len(ins), len(weights), _device_index(ins[0]))
     with torch.cuda.device(ins[0].device):
         outs = plan.apply([_padded(t, pad, 0.0) for t in ins], [_padded(w, pad, 0.0) for w in weights])
     return tuple(o[:n] for o in outs) if pad else tuple(outs)
@@ -437,8 +403,7 @@ def smooth_samples(x, gaps, time_constant: float, zero_phase: bool = True):
     pad = -n % 4
     base = math.exp(-1.0 / float(time_constant))
     scans = [(0, True, 0), (0, False, 0)] if zero_phase else [(0, True, 0)]
-    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    plan = _signal_plan(n + pad, scans, len(signals), 1, device)
+    plan = _cached_plan(_signal_plans, VarPlan.signal, n + pad, scans, len(signals), 1, _device_index(x))
     with torch.cuda.device(x.device):
         outs = plan.apply_power([_padded(t.to(torch.float32), pad, 0.0) for t in signals], [_padded(gaps.to(torch.float32), pad, math.inf)], [base])
     outs = [o[:n] for o in outs] if pad else list(outs)
@@ -479,6 +444,40 @@ def domain_transform_bases(sigma_s: float, iterations: int = 3) -> List[float]:
     return out
 
 
+def _distance_guide(guide, nd: int, sigma_s: float, sigma_r: float, backward: bool = False):
+    """(the guide with its channel axis, contiguous; its planes' pointer array; the scale) for the distance calls on `nd` spatial
+    dimensions, after the checks they share; backward: f32 guides only"""
+    import torch
+    g = guide if guide.dim() == nd + 1 else guide.unsqueeze(0)
+    if g.dim() != nd + 1:
+        raise ValueError(f"guide must be {'(C, H, W) or (H, W)' if nd == 2 else '(C, D, H, W) or (D, H, W)'}, got {tuple(guide.shape)}")
+    if backward and g.dtype != torch.float32:
+        raise TypeError(f"float32 guides only (there is no gradient with respect to a byte guide), got {g.dtype}")
+    if g.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"float32 or uint8 guides only, got {g.dtype}")
+    if not g.is_cuda:
+        raise ValueError("the guide must be a device tensor")
+    g = g.contiguous()
+    scale = float(sigma_s) / float(sigma_r) / (255.0 if g.dtype == torch.uint8 else 1.0)
+    return g, (ctypes.c_void_p * g.shape[0])(*[g[c].data_ptr() for c in range(g.shape[0])]), scale
+
+
+def _distance_gradients(g, grads, grad_guide, accumulate: bool):
+    """(grad_guide, allocated where it is None; its planes' pointer array) for the distance adjoints of the guide `g`, after the
+    checks of the gradient tensors: `grads` are those of d_x, d_y(, d_z)"""
+    import torch
+    if grad_guide is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs grad_guide")
+        grad_guide = torch.empty_like(g)
+    gg = grad_guide if grad_guide.dim() == g.dim() else grad_guide.unsqueeze(0)
+    shape = tuple(int(s) for s in g.shape)
+    for what, t, want in [(f"grad_d{axis}", t, shape[1:]) for axis, t in zip("xyz", grads)] + [("grad_guide", gg, shape)]:
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {want}")
+    return grad_guide, (ctypes.c_void_p * shape[0])(*[gg[c].data_ptr() for c in range(shape[0])])
+
+
 def domain_transform_distances(guide, sigma_s: float, sigma_r: float, stream=None):
     """(d_x, d_y): the exponent planes of the domain-transform filter for a device guide image (C, H, W) or (H, W), f32 or uint8,
     by rf_var_distances (one HIP launch, one read of the guide):
@@ -486,22 +485,11 @@ def domain_transform_distances(guide, sigma_s: float, sigma_r: float, stream=Non
     scale = sigma_s / sigma_r, for a uint8 guide sigma_s / sigma_r / 255: a byte guide means that guide divided by 255.
     W must be a multiple of 4.  Asynchronous on `stream` (default: torch's current stream)."""
     import torch
-    g = guide if guide.dim() == 3 else guide.unsqueeze(0)
-    if g.dim() != 3:
-        raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
-    if g.dtype not in (torch.float32, torch.uint8):
-        raise TypeError(f"float32 or uint8 guides only, got {g.dtype}")
-    if not g.is_cuda:
-        raise ValueError("the guide must be a device tensor")
-    g = g.contiguous()
+    g, planes, scale = _distance_guide(guide, 2, sigma_s, sigma_r)
     C, H, W = (int(s) for s in g.shape)
-    u8 = g.dtype == torch.uint8
-    scale = float(sigma_s) / float(sigma_r) / (255.0 if u8 else 1.0)
-    planes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
-    dx = torch.empty((H, W), dtype=torch.float32, device=g.device)
-    dy = torch.empty((H, W), dtype=torch.float32, device=g.device)
+    dx, dy = (torch.empty((H, W), dtype=torch.float32, device=g.device) for _ in range(2))
     with torch.cuda.device(g.device):
-        capi.check(capi.lib().rf_var_distances(planes, C, int(u8), W, H, scale, dx.data_ptr(), dy.data_ptr(), g.device.index,
+        capi.check(capi.lib().rf_var_distances(planes, C, int(g.dtype == torch.uint8), W, H, scale, dx.data_ptr(), dy.data_ptr(), g.device.index,
                                                VarPlan._stream(stream)))
     return dx, dy
 
@@ -514,22 +502,12 @@ def domain_transform_distances_volume(guide, sigma_s: float, sigma_r: float, spa
     with scale as there.  spacing_z > 0 is the sample distance along z in units of the x/y pitch (slice thickness, or how far
     apart two frames count); 1 = isotropic.  W must be a multiple of 4.  Asynchronous on `stream`."""
     import torch
-    g = guide if guide.dim() == 4 else guide.unsqueeze(0)
-    if g.dim() != 4:
-        raise ValueError(f"guide must be (C, D, H, W) or (D, H, W), got {tuple(guide.shape)}")
-    if g.dtype not in (torch.float32, torch.uint8):
-        raise TypeError(f"float32 or uint8 guides only, got {g.dtype}")
-    if not g.is_cuda:
-        raise ValueError("the guide must be a device tensor")
-    g = g.contiguous()
+    g, volumes, scale = _distance_guide(guide, 3, sigma_s, sigma_r)
     C, D, H, W = (int(s) for s in g.shape)
-    u8 = g.dtype == torch.uint8
-    scale = float(sigma_s) / float(sigma_r) / (255.0 if u8 else 1.0)
-    volumes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
     dx, dy, dz = (torch.empty((D, H, W), dtype=torch.float32, device=g.device) for _ in range(3))
     with torch.cuda.device(g.device):
-        capi.check(capi.lib().rf_var_distances_volume(volumes, C, int(u8), W, H, D, scale, float(spacing_z), dx.data_ptr(), dy.data_ptr(),
-                                                      dz.data_ptr(), g.device.index, VarPlan._stream(stream)))
+        capi.check(capi.lib().rf_var_distances_volume(volumes, C, int(g.dtype == torch.uint8), W, H, D, scale, float(spacing_z), dx.data_ptr(),
+                                                      dy.data_ptr(), dz.data_ptr(), g.device.index, VarPlan._stream(stream)))
     return dx, dy, dz
 
 
@@ -539,26 +517,9 @@ def domain_transform_distances_backward(guide, sigma_s: float, sigma_r: float, g
     `domain_transform_distances` (one HIP launch, a gather).  grad_guide=None allocates it (then accumulate must be False);
     accumulate=True adds to what grad_guide holds.  Returned in the guide's shape."""
     import torch
-    g = guide if guide.dim() == 3 else guide.unsqueeze(0)
-    if g.dim() != 3:
-        raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
-    if g.dtype != torch.float32:
-        raise TypeError(f"float32 guides only (there is no gradient with respect to a byte guide), got {g.dtype}")
-    if not g.is_cuda:
-        raise ValueError("the guide must be a device tensor")
-    g = g.contiguous()
+    g, planes, scale = _distance_guide(guide, 2, sigma_s, sigma_r, backward=True)
     C, H, W = (int(s) for s in g.shape)
-    if grad_guide is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs grad_guide")
-        grad_guide = torch.empty_like(g)
-    gg = grad_guide if grad_guide.dim() == 3 else grad_guide.unsqueeze(0)
-    for what, t, shape in (("grad_dx", grad_dx, (H, W)), ("grad_dy", grad_dy, (H, W)), ("grad_guide", gg, (C, H, W))):
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {shape}")
-    planes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
-    grads = (ctypes.c_void_p * C)(*[gg[c].data_ptr() for c in range(C)])
-    scale = float(sigma_s) / float(sigma_r)
+    grad_guide, grads = _distance_gradients(g, (grad_dx, grad_dy), grad_guide, accumulate)
     with torch.cuda.device(g.device):
         capi.check(capi.lib().rf_var_distances_backward(planes, C, W, H, scale, grad_dx.data_ptr(), grad_dy.data_ptr(), grads,
                                                         int(bool(accumulate)), g.device.index, VarPlan._stream(stream)))
@@ -572,27 +533,9 @@ def domain_transform_distances_volume_backward(guide, sigma_s: float, sigma_r: f
     not enter).  grad_guide=None allocates it (then accumulate must be False); accumulate=True adds to what grad_guide holds.
     Returned in the guide's shape."""
     import torch
-    g = guide if guide.dim() == 4 else guide.unsqueeze(0)
-    if g.dim() != 4:
-        raise ValueError(f"guide must be (C, D, H, W) or (D, H, W), got {tuple(guide.shape)}")
-    if g.dtype != torch.float32:
-        raise TypeError(f"float32 guides only (there is no gradient with respect to a byte guide), got {g.dtype}")
-    if not g.is_cuda:
-        raise ValueError("the guide must be a device tensor")
-    g = g.contiguous()
+    g, volumes, scale = _distance_guide(guide, 3, sigma_s, sigma_r, backward=True)
     C, D, H, W = (int(s) for s in g.shape)
-    if grad_guide is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs grad_guide")
-        grad_guide = torch.empty_like(g)
-    gg = grad_guide if grad_guide.dim() == 4 else grad_guide.unsqueeze(0)
-    for what, t, shape in (("grad_dx", grad_dx, (D, H, W)), ("grad_dy", grad_dy, (D, H, W)), ("grad_dz", grad_dz, (D, H, W)),
-                           ("grad_guide", gg, (C, D, H, W))):
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {shape}")
-    volumes = (ctypes.c_void_p * C)(*[g[c].data_ptr() for c in range(C)])
-    grads = (ctypes.c_void_p * C)(*[gg[c].data_ptr() for c in range(C)])
-    scale = float(sigma_s) / float(sigma_r)
+    grad_guide, grads = _distance_gradients(g, (grad_dx, grad_dy, grad_dz), grad_guide, accumulate)
     with torch.cuda.device(g.device):
         capi.check(capi.lib().rf_var_distances_volume_backward(volumes, C, W, H, D, scale, grad_dx.data_ptr(), grad_dy.data_ptr(),
                                                                grad_dz.data_ptr(), grads, int(bool(accumulate)), g.device.index,
@@ -614,30 +557,12 @@ class SmoothPlan(_PlanHandle):
 
     def __init__(self, shape_hw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
                  iterations: int = 3, sigma_s: float = 60.0, sigma_r: float = 0.4, device: int = -1, batch: Optional[int] = None):
-        import torch
         shape_hw = tuple(int(s) for s in shape_hw)
         if len(shape_hw) != 2:
             raise ValueError(f"shape_hw must be (height, width), got {shape_hw}")
-        image_dtype = torch.float32 if image_dtype is None else image_dtype
-        guide_dtype = torch.float32 if guide_dtype is None else guide_dtype
-        for what, dt in (("image", image_dtype), ("guide", guide_dtype)):
-            if dt not in (torch.float32, torch.uint8):
-                raise TypeError(f"{what}_dtype must be torch.float32 or torch.uint8, got {dt}")
-        d = capi.SmoothDesc()
-        d.abi = capi.RF_ABI
-        d.image_u8 = int(image_dtype == torch.uint8)
+        d = self._describe(capi.SmoothDesc(), shape_hw, planes, guide_planes, image_dtype, guide_dtype, iterations, sigma_s, sigma_r, device)
         d.height, d.width = shape_hw
-        d.n_planes, d.n_guide = int(planes), int(guide_planes)
-        d.guide_u8 = int(guide_dtype == torch.uint8) if d.n_guide != 0 else 0
-        d.iterations = int(iterations)
-        d.sigma_s, d.sigma_r = float(sigma_s), float(sigma_r)
-        d.device = int(device)
-        d.flags = 0
-        self._desc = d
-        self.shape, self.planes, self.guide_planes, self.iterations = shape_hw, int(planes), int(guide_planes), int(iterations)
-        self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
         self.batch = None if batch is None else int(batch)
-        self._h = ctypes.c_void_p()
         if self.batch is None:
             capi.check(capi.lib().rf_smooth_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
         else:
@@ -646,6 +571,30 @@ class SmoothPlan(_PlanHandle):
             b.image_stride = d.n_planes * d.height * d.width
             b.guide_stride = d.n_guide * d.height * d.width
             capi.check(capi.lib().rf_smooth_plan_create_batched(ctypes.byref(d), ctypes.byref(b), ctypes.byref(self._h)))
+
+    def _describe(self, d, shape, planes, guide_planes, image_dtype, guide_dtype, iterations, sigma_s, sigma_r, device):
+        """what an image plan and a volume plan share: the dtype checks, the common fields of the description `d` (flags 0, no
+        extents) and the attributes (batch None, no handle yet); returns d"""
+        import torch
+        image_dtype = torch.float32 if image_dtype is None else image_dtype
+        guide_dtype = torch.float32 if guide_dtype is None else guide_dtype
+        for what, dt in (("image", image_dtype), ("guide", guide_dtype)):
+            if dt not in (torch.float32, torch.uint8):
+                raise TypeError(f"{what}_dtype must be torch.float32 or torch.uint8, got {dt}")
+        d.abi = capi.RF_ABI
+        d.image_u8 = int(image_dtype == torch.uint8)
+        d.n_planes, d.n_guide = int(planes), int(guide_planes)
+        d.guide_u8 = int(guide_dtype == torch.uint8) if d.n_guide != 0 else 0
+        d.iterations = int(iterations)
+        d.sigma_s, d.sigma_r = float(sigma_s), float(sigma_r)
+        d.device = int(device)
+        d.flags = 0
+        self._desc = d
+        self.shape, self.planes, self.guide_planes, self.iterations = shape, int(planes), int(guide_planes), int(iterations)
+        self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
+        self.batch = None
+        self._h = ctypes.c_void_p()
+        return d
 
     @classmethod
     def volume(cls, shape_dhw: Sequence[int], planes: int = 1, guide_planes: int = 0, image_dtype=None, guide_dtype=None,
@@ -661,31 +610,14 @@ class SmoothPlan(_PlanHandle):
         bit for bit, and `backward`, `backward_timed` and `apply` work as on an image plan -- 1 + 18 K launches with the
         distances held constant, 51 K - 7 through them (the last one var_distances_volume_grad), and
         3 + (K - 1 + 7) * planes f32 volumes of workspace allocated by the first edges=True call."""
-        import torch
         self = cls.__new__(cls)
         shape_dhw = tuple(int(s) for s in shape_dhw)
         if len(shape_dhw) != 3:
             raise ValueError(f"shape_dhw must be (depth, height, width), got {shape_dhw}")
-        image_dtype = torch.float32 if image_dtype is None else image_dtype
-        guide_dtype = torch.float32 if guide_dtype is None else guide_dtype
-        for what, dt in (("image", image_dtype), ("guide", guide_dtype)):
-            if dt not in (torch.float32, torch.uint8):
-                raise TypeError(f"{what}_dtype must be torch.float32 or torch.uint8, got {dt}")
-        d = capi.SmoothVolumeDesc()
-        d.abi = capi.RF_ABI
-        d.image_u8 = int(image_dtype == torch.uint8)
+        d = self._describe(capi.SmoothVolumeDesc(), shape_dhw, planes, guide_planes, image_dtype, guide_dtype, iterations, sigma_s, sigma_r, device)
         d.depth, d.height, d.width = shape_dhw
-        d.n_planes, d.n_guide = int(planes), int(guide_planes)
-        d.guide_u8 = int(guide_dtype == torch.uint8) if d.n_guide != 0 else 0
-        d.iterations = int(iterations)
-        d.sigma_s, d.sigma_r, d.spacing_z = float(sigma_s), float(sigma_r), float(spacing_z)
-        d.device = int(device)
+        d.spacing_z = float(spacing_z)
         d.flags = capi.RF_SMOOTH_VOLUME_BACKWARD if differentiable else 0
-        self._desc = d
-        self.shape, self.planes, self.guide_planes, self.iterations = shape_dhw, int(planes), int(guide_planes), int(iterations)
-        self.image_dtype, self.guide_dtype = image_dtype, guide_dtype if d.n_guide != 0 else None
-        self.batch = None
-        self._h = ctypes.c_void_p()
         capi.check(capi.lib().rf_smooth_plan_create_volume(ctypes.byref(d), ctypes.byref(self._h)))
         return self
 
@@ -735,10 +667,9 @@ class SmoothPlan(_PlanHandle):
     def _arguments(self, image, guide, out, stream):
         """(image, guide and output pointers, the output, the stream's handle)"""
         import torch
-        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from, and no stream)
-            nulls = lambda n: (ctypes.c_void_p * max(n, 1))()      # noqa: E731
-            return nulls(self.planes), nulls(self.guide_planes) if self.guide_planes else None, nulls(self.planes), None, ctypes.c_void_p()
+        nulls = _host_only_nulls(self, self.planes, self.guide_planes or None, self.planes)
+        if nulls:
+            return (*nulls, None, ctypes.c_void_p())
         if out is None:
             out = torch.empty_like(image) if hasattr(image, "dim") else [torch.empty_like(t) for t in image]
         pg = None
@@ -776,12 +707,10 @@ class SmoothPlan(_PlanHandle):
     def _backward_arguments(self, image, guide, grad_out, grad_image, grad_guide, edges, stream):
         """(the five pointer arrays, grad_image, grad_guide, the stream's handle)"""
         import torch
-        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
-            # (the library refuses; there are no device tensors to take pointers from, and no stream)
-            nulls = lambda n: (ctypes.c_void_p * max(n, 1))()      # noqa: E731
-            return (nulls(self.planes) if image is not None else None, nulls(self.guide_planes) if guide is not None else None,
-                    nulls(self.planes), nulls(self.planes), nulls(self.guide_planes) if grad_guide is not None else None,
-                    None, None, ctypes.c_void_p())
+        nulls = _host_only_nulls(self, self.planes if image is not None else None, self.guide_planes if guide is not None else None, self.planes,
+                                 self.planes, self.guide_planes if grad_guide is not None else None)
+        if nulls:
+            return (*nulls, None, None, ctypes.c_void_p())
         f32 = torch.float32
         if grad_image is None:
             grad_image = torch.empty_like(grad_out) if hasattr(grad_out, "dim") else [torch.empty_like(t) for t in grad_out]
@@ -853,7 +782,60 @@ def _smooth_function():
     return _smooth_fn
 
 
-_smooth_volume_plans: Dict[tuple, SmoothPlan] = {}
+_smooth_plan_objects: Dict[tuple, SmoothPlan] = {}      # form="plan": keyed by shape, dtypes, iterations, sigmas and device
+_smooth_volume_plans: Dict[tuple, SmoothPlan] = {}      # the same with spacing_z, and whether the plan has a backward
+
+
+def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=False, nd: int = 2, spacing_z: float = 1.0):
+    """form="plan" (nd = 2): one cached SmoothPlan on (C, H, W) or (H, W), on (N, C, H, W) one cached SmoothPlan(batch=N) by the same
+    rules; and edge_aware_smooth_volume (nd = 3): one cached SmoothPlan.volume on (C, D, H, W) or (D, H, W), which has no batch"""
+    import torch
+    what, dims, guide_dims, extents = (("image", "(C, H, W) or (H, W)", "(C, H, W) or (H, W)", "height and width") if nd == 2 else
+                                       ("volume", "(C, D, H, W) or (D, H, W)", "(G, D, H, W) or (D, H, W)", "depth, height and width"))
+    batched = nd == 2 and image.dim() == 4
+    at = 1 if batched else 0      # where the planes are counted
+    img = image if batched or image.dim() == nd + 1 else image.unsqueeze(0)
+    if img.dim() != nd + 1 + at:
+        raise ValueError(f"{what} must be {dims}, got {tuple(image.shape)}")
+    if img.dtype != torch.uint8:
+        img = img.to(torch.float32)
+    img = img.contiguous()
+    g = None
+    if guide is not None:
+        if batched and guide.dim() != 4:
+            raise ValueError(f"a batched image (N, C, H, W) takes a guide (N, G, H, W), got {tuple(guide.shape)}")
+        g = guide if batched or guide.dim() == nd + 1 else guide.unsqueeze(0)
+        if g.dim() != nd + 1 + at:
+            raise ValueError(f"guide must be {guide_dims}, got {tuple(guide.shape)}")
+        if g.dtype != torch.uint8:
+            g = g.to(torch.float32)
+        g = g.to(img.device).contiguous()
+        if tuple(g.shape[:at]) != tuple(img.shape[:at]) or tuple(g.shape[at + 1:]) != tuple(img.shape[at + 1:]):
+            raise ValueError(f"guide and {what} must have the same " + ("batch size, " if batched else "") + extents)
+    shape = tuple(int(s) for s in img.shape)      # (C, H, W), (N, C, H, W) or (C, D, H, W)
+    device = _device_index(img)
+    wants_grad = bool(differentiable) and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad))
+    if wants_grad and (img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad)):
+        raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
+    n_guide = 0 if g is None else int(g.shape[at])
+    common = dict(planes=shape[at], guide_planes=n_guide, image_dtype=img.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
+                  sigma_s=sigma_s, sigma_r=sigma_r, device=device)
+    key = shape + (img.dtype, None if g is None else (n_guide, g.dtype), int(iterations), float(sigma_s), float(sigma_r))
+    if nd == 2:
+        cache, key = _smooth_plan_objects, key + (device,)
+    else:      # (a plan with a backward is built only where one is needed: the default call keeps the plans it had)
+        cache, key = _smooth_volume_plans, key + (float(spacing_z), device, wants_grad)
+    plan = cache.get(key)
+    if plan is None and nd == 2:
+        plan = cache[key] = SmoothPlan(shape[-2:], batch=shape[0] if batched else None, **common)
+    elif plan is None:
+        plan = cache[key] = SmoothPlan.volume(shape[1:], spacing_z=spacing_z, differentiable=wants_grad, **common)
+    if wants_grad:
+        out = plan.apply(img, g)
+    else:
+        with torch.cuda.device(img.device):
+            out = plan.execute(img, g)
+    return out if image.dim() >= nd + 1 else out[0]
 
 
 def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, spacing_z: float = 1.0,
@@ -870,89 +852,10 @@ def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r:
     `SmoothPlan.volume(..., differentiable=True)` -- same values, bit for bit; f32 volumes, and an f32 guide where the guide requires
     a gradient (TypeError otherwise); gradients with respect to the volume and the guide, all of it in the library, through the
     distances where the guide, or a self-guiding volume, requires one.  No gradient of the sigmas or spacing_z; no double backward."""
-    import torch
-    vol = volume if volume.dim() == 4 else volume.unsqueeze(0)
-    if vol.dim() != 4:
-        raise ValueError(f"volume must be (C, D, H, W) or (D, H, W), got {tuple(volume.shape)}")
-    if vol.dtype != torch.uint8:
-        vol = vol.to(torch.float32)
-    vol = vol.contiguous()
-    g = None
-    if guide is not None:
-        g = guide if guide.dim() == 4 else guide.unsqueeze(0)
-        if g.dim() != 4:
-            raise ValueError(f"guide must be (G, D, H, W) or (D, H, W), got {tuple(guide.shape)}")
-        if g.dtype != torch.uint8:
-            g = g.to(torch.float32)
-        g = g.to(vol.device).contiguous()
-        if tuple(g.shape[1:]) != tuple(vol.shape[1:]):
-            raise ValueError("guide and volume must have the same depth, height and width")
-    shape = tuple(int(s) for s in vol.shape)
-    device = vol.device.index if vol.device.index is not None else torch.cuda.current_device()
-    wants_grad = bool(differentiable) and torch.is_grad_enabled() and (vol.requires_grad or (g is not None and g.requires_grad))
-    if wants_grad and (vol.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad)):
-        raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
-    # (a plan with a backward is built only where one is needed: the default call keeps the plans it had)
-    key = shape + (vol.dtype, None if g is None else (int(g.shape[0]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), float(spacing_z), device,
-                   wants_grad)
-    plan = _smooth_volume_plans.get(key)
-    if plan is None:
-        plan = _smooth_volume_plans[key] = SmoothPlan.volume(shape[1:], planes=shape[0], guide_planes=0 if g is None else int(g.shape[0]),
-                                                             image_dtype=vol.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
-                                                             sigma_s=sigma_s, sigma_r=sigma_r, spacing_z=spacing_z, device=device,
-                                                             differentiable=wants_grad)
-    if wants_grad:
-        out = plan.apply(vol, g)
-    else:
-        with torch.cuda.device(vol.device):
-            out = plan.execute(vol, g)
-    return out if volume.dim() == 4 else out[0]
+    return _smooth_by_plan(volume, guide, sigma_s, sigma_r, iterations, differentiable, nd=3, spacing_z=spacing_z)
 
 
 _SMOOTH_SCANS = [(0, True, 0), (0, False, 0), (1, True, 1), (1, False, 1)]      # +x -x on weights 0, +y -y on weights 1
-_smooth_plans: Dict[Tuple[int, int, int, int], VarPlan] = {}
-_smooth_plan_objects: Dict[tuple, SmoothPlan] = {}
-
-
-def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=False):
-    """form="plan": one cached SmoothPlan on (C, H, W) or (H, W); on (N, C, H, W) one cached SmoothPlan(batch=N), by the same rules"""
-    import torch
-    batched = image.dim() == 4
-    at = 1 if batched else 0      # where the planes are counted
-    img = image if batched or image.dim() == 3 else image.unsqueeze(0)
-    if img.dim() != 3 + at:
-        raise ValueError(f"image must be (C, H, W) or (H, W), got {tuple(image.shape)}")
-    if img.dtype != torch.uint8:
-        img = img.to(torch.float32)
-    img = img.contiguous()
-    g = None
-    if guide is not None:
-        if batched and guide.dim() != 4:
-            raise ValueError(f"a batched image (N, C, H, W) takes a guide (N, G, H, W), got {tuple(guide.shape)}")
-        g = guide if batched or guide.dim() == 3 else guide.unsqueeze(0)
-        if g.dim() != 3 + at:
-            raise ValueError(f"guide must be (C, H, W) or (H, W), got {tuple(guide.shape)}")
-        if g.dtype != torch.uint8:
-            g = g.to(torch.float32)
-        g = g.to(img.device).contiguous()
-        if tuple(g.shape[:at]) != tuple(img.shape[:at]) or tuple(g.shape[at + 1:]) != tuple(img.shape[at + 1:]):
-            raise ValueError("guide and image must have the same " + ("batch size, height and width" if batched else "height and width"))
-    shape = tuple(int(s) for s in img.shape)      # (C, H, W), or (N, C, H, W)
-    device = img.device.index if img.device.index is not None else torch.cuda.current_device()
-    key = shape + (img.dtype, None if g is None else (int(g.shape[at]), g.dtype), int(iterations), float(sigma_s), float(sigma_r), device)
-    plan = _smooth_plan_objects.get(key)
-    if plan is None:
-        plan = _smooth_plan_objects[key] = SmoothPlan(shape[-2:], planes=shape[at], guide_planes=0 if g is None else int(g.shape[at]),
-                                                      image_dtype=img.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
-                                                      sigma_s=sigma_s, sigma_r=sigma_r, device=device, batch=shape[0] if batched else None)
-    if differentiable and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad)):
-        if img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad):
-            raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
-        out = plan.apply(img, g)
-    else:
-        with torch.cuda.device(img.device):
-            out = plan.execute(img, g)
-    return out if image.dim() >= 3 else out[0]
 
 
 def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float = 0.4, iterations: int = 3, form: str = "planes",
@@ -1008,10 +911,7 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     C, H, W = (int(s) for s in img.shape)
     if shape_hw != (H, W):
         raise ValueError("guide and image must have the same height and width")
-    key = (C, H, W, img.device.index if img.device.index is not None else torch.cuda.current_device())
-    plan = _smooth_plans.get(key)
-    if plan is None:
-        plan = _smooth_plans[key] = VarPlan((H, W), _SMOOTH_SCANS, planes=C, n_weights=2, device=key[3])
+    plan = _cached_plan(_smooth_plans, VarPlan, (H, W), _SMOOTH_SCANS, C, 2, _device_index(img))
     out = torch.empty_like(img)
     outs = [out[c] for c in range(C)]
     src = [img[c] for c in range(C)]
