@@ -847,6 +847,22 @@ public:
                                        grad_exponents.empty() ? nullptr : grad_exponents.data(), stream) != RF_OK)
             throw RecFilterError(rf_last_error_string());
     }
+    /** gradient_power() with the gradient of the bases (rf_var_plan_backward_power_bases): grad_bases, a DEVICE buffer of one
+     *  double per exponent plane (8-byte aligned), receives dL/d(bases[k]); grad_exponents may be empty or hold null entries. */
+    void gradient_power_bases(const std::vector<const void *> &in, const std::vector<const void *> &exponents, const std::vector<float> &bases,
+                              const std::vector<const void *> &grad_out, const std::vector<void *> &grad_in,
+                              const std::vector<void *> &grad_exponents, double *grad_bases, void *stream = nullptr) {
+        if (in.size() != grad_out.size()) throw RecFilterError("gradient_power_bases: as many input planes as grad_out planes");
+        if (!grad_exponents.empty() && grad_exponents.size() != exponents.size())
+            throw RecFilterError("gradient_power_bases: one grad_exponents entry per exponent plane (null: no gradient), or none");
+        prepare(grad_out, exponents.size(), grad_in);
+        if ((int)bases.size() < n_weights) throw RecFilterError("gradient_power_bases: one base per exponent plane");
+        if (rf_var_plan_backward_power_bases(plan, in.data(), exponents.data(), bases.data(), grad_out.data(), grad_in.data(),
+                                             grad_exponents.empty() ? nullptr : grad_exponents.data(), grad_bases, stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** launches of gradient_power_bases(): 7 per scan and one */
+    int gradient_bases_num_kernels() const { return plan ? rf_var_plan_backward_bases_num_kernels(plan) : 0; }
     /** launches of gradient() and gradient_power(): 3 per scan, 7 with weight gradients */
     int gradient_num_kernels(bool with_weight_gradients) const { return plan ? rf_var_plan_backward_num_kernels(plan, with_weight_gradients ? 1 : 0) : 0; }
 private:
@@ -1055,6 +1071,29 @@ public:
         if (rf_smooth_plan_bases(plan, b.data()) != RF_OK) throw RecFilterError(rf_last_error_string());
         return b;
     }
+    /** New sigmas for the same plan (rf_smooth_plan_set_sigmas): the scale and the bases are recomputed as create computes them,
+     *  nothing is allocated, and every later realize() and gradient() runs with them.  A refusal leaves the filter as it was. */
+    void set_sigmas(double sigma_s, double sigma_r) {
+        prepare();
+        if (rf_smooth_plan_set_sigmas(plan, sigma_s, sigma_r) != RF_OK) throw RecFilterError(rf_last_error_string());
+        desc.sigma_s = sigma_s;
+        desc.sigma_r = sigma_r;
+    }
+    /** gradient() with the gradients of the scalars (rf_smooth_plan_backward_sigmas): grad_params, a DEVICE buffer of
+     *  3 + iterations doubles (8-byte aligned), receives dL/dsigma_s, dL/dsigma_r, dL/dspacing_z, dL/da_0 .. dL/da_{K-1}, summed over
+     *  the batch.  `image` is always needed; grad_image and grad_guide are bit for bit gradient()'s with the same `edges`. */
+    void gradient_sigmas(const std::vector<const void *> &image, const std::vector<const void *> &guide, const std::vector<const void *> &grad_out,
+                         const std::vector<void *> &grad_image, const std::vector<void *> &grad_guide, bool edges, double *grad_params,
+                         void *stream = nullptr) {
+        prepare();
+        if ((int)image.size() != desc.n_planes || (int)grad_out.size() != desc.n_planes || (int)grad_image.size() != desc.n_planes ||
+            (int)guide.size() != desc.n_guide || (!grad_guide.empty() && grad_guide.size() != guide.size()))
+            throw RecFilterError("gradient_sigmas: as many image, gradient and guide planes as the filter was built for");
+        if (rf_smooth_plan_backward_sigmas(plan, image.data(), guide.empty() ? nullptr : guide.data(), grad_out.data(), grad_image.data(),
+                                           grad_guide.empty() ? nullptr : grad_guide.data(), edges ? 1 : 0, grad_params, stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    int gradient_sigmas_num_kernels(bool edges) { prepare(); return rf_smooth_plan_backward_sigmas_num_kernels(plan, edges ? 1 : 0); }
     int num_kernels() { prepare(); return rf_smooth_plan_num_kernels(plan); }
     /** The adjoint of realize() for f32 images (rf_smooth_plan_backward): grad_image = dL/d(image) from grad_out = dL/d(out).
      *  edges = false holds the distances constant (grad_guide empty; `image` may be empty unless the image guides itself).

@@ -601,6 +601,39 @@ int    rf_var_plan_backward_power_timed(rf_var_plan *plan, const void *const *in
                                         int capacity);
 int    rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gradients);
 size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_weight_gradients);
+/* rf_var_plan_backward_power with the gradient of the BASES: the weight-gradient route of rf_var_plan_backward_power, whose var_grad
+ * launches also reduce, and one more launch.  grad_bases is a DEVICE buffer of n_weights doubles, 8-byte aligned; entry k receives
+ *     dL/dbases[k] = (1 / bases[k]) * sum over the scans that read plane k, over the image planes and over i, of t[i],
+ *     t[i] = (w[i] == 0 ? 0 : d[i] * w[i] * dL/dw[i]),
+ * dL/dw the register sum over the image planes that rf_var_plan_backward_power multiplies by w ln(base).  d is never a factor
+ * where w is 0 (d = +inf contributes exactly 0, the rule dL/dd follows) and element 0 along the scanned dimension contributes 0 by
+ * the same select as there.  The roundings of log2(bases[k]) to f32 are treated as the identity.  An entry whose plane no scan
+ * reads is 0.  The sum is a streaming f64 reduction without atomics: a lane adds its t in the order it visits its rows, a workgroup
+ * folds its lanes by a fixed tree and stores one f64 slab entry at an index that depends on (its block, the scan) alone, and the
+ * last launch, one workgroup, sums the slabs in index order and multiplies by 1 / bases[k], formed on the host in double.  Nothing
+ * synchronises; two runs of one call agree bit for bit.
+ * Entries of grad_exponent_planes, or the whole array, may be NULL: the reduction still runs and that plane's store is left out
+ * (no var_grad launch is skipped here).  grad_in and every exponent gradient asked for are bit for bit rf_var_plan_backward_power's.
+ * Image, signal and volume plans alike.
+ * Launches, in order: the 7 n_scans of rf_var_plan_backward_power with exponent gradients, then "var_param_sum":
+ * rf_var_plan_backward_bases_num_kernels(plan) = 7 n_scans + 1.  The slabs are the plan's, one double per workgroup of every
+ * var_grad launch, allocated by the first call that needs them and freed with the plan;
+ * rf_var_plan_backward_bases_workspace_bytes(plan) is exact: rf_var_plan_backward_workspace_bytes(plan, 1) plus 8 bytes per slab
+ * entry (a var_grad launch of w x h samples on b images or slices has ceil(w / 1024) * min(h, 65535) * b workgroups).
+ * Checked in the order of rf_var_plan_backward_power: null plan / exponent_planes / bases / grad_out_planes / grad_in_planes; null
+ * in_planes; directly behind these null grad_bases, then a grad_bases that is not 8-byte aligned (RF_ERR_INVALID_ARG); then the
+ * base check, the host-only plan (RF_ERR_HIP) and the per-plane checks.  grad_bases must not overlap any plane of the call (not
+ * checked). */
+int    rf_var_plan_backward_power_bases(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                        const float *bases /* n_weights */, const void *const *grad_out_planes, void *const *grad_in_planes,
+                                        void *const *grad_exponent_planes /* NULL, or n_weights entries each NULL or a plane */,
+                                        double *grad_bases /* device, n_weights doubles */, void *stream);
+int    rf_var_plan_backward_power_bases_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes,
+                                              const float *bases, const void *const *grad_out_planes, void *const *grad_in_planes,
+                                              void *const *grad_exponent_planes, double *grad_bases, void *stream, float *ms_out,
+                                              const char **names_out, int capacity);
+int    rf_var_plan_backward_bases_num_kernels(const rf_var_plan *plan);
+size_t rf_var_plan_backward_bases_workspace_bytes(const rf_var_plan *plan);
 /* The varying scans on long 1-D SIGNALS.  rf_var_plan_create refuses ndim = 1, and a (1, N) image fills one lane of a wave; this
  * entry point builds an ordinary rf_var_plan whose "plane" is a dense f32 signal of `length` samples: execute, execute_power,
  * backward, backward_power, their timed forms, the four queries and destroy work on it as above.  The operator is the one above
@@ -769,6 +802,14 @@ size_t rf_smooth_plan_workspace_bytes(const rf_smooth_plan *plan);
 int    rf_smooth_plan_num_kernels(const rf_smooth_plan *plan);
 /* a_0 .. a_{K-1}, the bases the plan runs with */
 int    rf_smooth_plan_bases(const rf_smooth_plan *plan, float *out /* iterations */);
+/* New sigmas for an existing plan: the scale of var_distances and a_0 .. a_{K-1} are recomputed exactly as create computes them, so
+ * rf_smooth_plan_bases afterwards returns, bit for bit, what a fresh plan created with these sigmas returns, and every later
+ * execute and backward runs with them.  Nothing is allocated and no HIP call is made: it works on host-only plans, and a caller who
+ * tunes the sigmas keeps one plan and its workspace.  Refused as create refuses them, the plan left unchanged: a sigma that is not
+ * finite and positive (RF_ERR_INVALID_ARG); sigma_s / sigma_r that is no f32, an a_k that rounds to 0 or 1 in f32
+ * (RF_ERR_UNSUPPORTED).  The values are read by the host when a call is issued: order it against the plan's executes and backwards as
+ * an execute is ordered (work already issued keeps the sigmas it was issued with). */
+int    rf_smooth_plan_set_sigmas(rf_smooth_plan *plan, double sigma_s, double sigma_r);
 /* image_planes / out_planes: n_planes device pointers each; guide_planes: n_guide device pointers, NULL iff n_guide == 0.
  * Asynchronous on `stream`. */
 int    rf_smooth_plan_execute(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
@@ -806,6 +847,34 @@ int    rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *im
                                      void *const *grad_guide_planes, int32_t edges, void *stream, float *ms_out,
                                      const char **names_out, int capacity);
 int    rf_smooth_plan_backward_num_kernels(const rf_smooth_plan *plan, int edges);
+/* rf_smooth_plan_backward with the gradients of the scalars that shape the filter.  grad_params is a DEVICE buffer of 3 + K doubles,
+ * 8-byte aligned: dL/dsigma_s, dL/dsigma_r, dL/dspacing_z (0 on an image plan), then dL/da_0 .. dL/da_{K-1}, all summed over the
+ * batch (the sigmas are shared).  With gd the exponent gradients the edges = 1 route accumulates, A_k = dL/da_k summed over the
+ * dimensions (rf_var_plan_backward_power_bases' sum per iteration) and Q = sum over the dimensions and samples of gd (d - d0), d0 = 1
+ * along x and y and spacing_z along z:
+ *     dL/dsigma_s = (sum_k A_k a_k (-ln a_k) + Q) / sigma_s,   dL/dsigma_r = -Q / sigma_r,   dL/dspacing_z = sum gd_z.
+ * A byte guide's 255 cancels; the roundings of a_k and of the scale to f32 are treated as the identity; the sigmas are those of
+ * create or of the last rf_smooth_plan_set_sigmas.  The host forms the factors in double and the device multiplies: no call
+ * synchronises, there are no atomics, and two runs agree bit for bit.
+ * Launches: those of rf_smooth_plan_backward(edges = 1) with the base-reducing var_grad instances -- edges = 0 leaves out the final
+ * var_distances[_volume]_grad -- then "var_dot" (one streaming launch over the (gd, d) pairs: f64 slabs of sum gd (d - d0), the term
+ * 0 by a select where gd is 0, and of sum gd) and "var_param_sum": rf_smooth_plan_backward_sigmas_num_kernels(plan, edges) =
+ * rf_smooth_plan_backward_num_kernels(plan, 1) + 2, one less at edges = 0.  grad_image and grad_guide are bit for bit what
+ * rf_smooth_plan_backward gives with the same edges.  The workspace is that of edges = 1 plus plan-owned f64 slabs (8 bytes per
+ * workgroup of every reducing launch and of var_dot), allocated by the first call.
+ * image_planes is always needed (the forward is rerun); a uint8 guide is allowed with edges = 0.  Image plans, batched plans and
+ * volume plans created with RF_SMOOTH_VOLUME_BACKWARD; unflagged volume plans and byte-image plans are refused as in
+ * rf_smooth_plan_backward.  Checked in this order: null plan / grad_out_planes / grad_image_planes; null grad_params, then a
+ * grad_params that is not 8-byte aligned (RF_ERR_INVALID_ARG); then the checks of rf_smooth_plan_backward in their order, the
+ * host-only plan (RF_ERR_HIP) last before the per-plane checks. */
+int    rf_smooth_plan_backward_sigmas(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                      const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes,
+                                      int32_t edges, double *grad_params /* device, 3 + iterations doubles */, void *stream);
+int    rf_smooth_plan_backward_sigmas_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                            const void *const *grad_out_planes, void *const *grad_image_planes,
+                                            void *const *grad_guide_planes, int32_t edges, double *grad_params, void *stream,
+                                            float *ms_out, const char **names_out, int capacity);
+int    rf_smooth_plan_backward_sigmas_num_kernels(const rf_smooth_plan *plan, int edges);
 size_t rf_smooth_plan_backward_workspace_bytes(const rf_smooth_plan *plan, int edges);
 
 /* A batch: `batch` images of the description per call, forward and backward, every launch taking all of them (the batch is a

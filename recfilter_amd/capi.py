@@ -79,6 +79,9 @@ EXPORTED_SYMBOLS = [
     "rf_var_plan_create_signal",
     "rf_var_plan_create_volume", "rf_var_distances_volume", "rf_smooth_plan_create_volume",
     "rf_var_distances_volume_backward",
+    "rf_var_plan_backward_power_bases", "rf_var_plan_backward_power_bases_timed", "rf_var_plan_backward_bases_num_kernels",
+    "rf_var_plan_backward_bases_workspace_bytes", "rf_smooth_plan_set_sigmas",
+    "rf_smooth_plan_backward_sigmas", "rf_smooth_plan_backward_sigmas_timed", "rf_smooth_plan_backward_sigmas_num_kernels",
 ]
 
 
@@ -252,16 +255,26 @@ def lib() -> ctypes.CDLL:
     L.rf_smooth_plan_workspace_bytes.restype = ctypes.c_size_t
     L.rf_smooth_plan_num_kernels.argtypes = [vp]
     L.rf_smooth_plan_bases.argtypes = [vp, fp]
+    L.rf_smooth_plan_set_sigmas.argtypes = [vp, ctypes.c_double, ctypes.c_double]
     L.rf_smooth_plan_execute.argtypes = [vp, vpp, vpp, vpp, vp]
     L.rf_smooth_plan_execute_timed.argtypes = [vp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
     L.rf_var_plan_backward_power.argtypes = [vp, vpp, vpp, fp, vpp, vpp, vpp, vp]
     L.rf_var_plan_backward_power_timed.argtypes = [vp, vpp, vpp, fp, vpp, vpp, vpp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_plan_backward_power_bases.argtypes = [vp, vpp, vpp, fp, vpp, vpp, vpp, vp, vp]
+    L.rf_var_plan_backward_power_bases_timed.argtypes = [vp, vpp, vpp, fp, vpp, vpp, vpp, vp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var_plan_backward_bases_num_kernels.argtypes = [vp]
+    L.rf_var_plan_backward_bases_workspace_bytes.argtypes = [vp]
+    L.rf_var_plan_backward_bases_workspace_bytes.restype = ctypes.c_size_t
     L.rf_var_distances_backward.argtypes = [vpp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, vp, vp, vpp,
                                             ctypes.c_int32, ctypes.c_int32, vp]
     L.rf_smooth_plan_backward.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, ctypes.c_int32, vp]
     L.rf_smooth_plan_backward_timed.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, ctypes.c_int32, vp, fp, ctypes.POINTER(ctypes.c_char_p),
                                                 ctypes.c_int]
     L.rf_smooth_plan_backward_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_smooth_plan_backward_sigmas.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, ctypes.c_int32, vp, vp]
+    L.rf_smooth_plan_backward_sigmas_timed.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, ctypes.c_int32, vp, vp, fp, ctypes.POINTER(ctypes.c_char_p),
+                                                       ctypes.c_int]
+    L.rf_smooth_plan_backward_sigmas_num_kernels.argtypes = [vp, ctypes.c_int]
     L.rf_smooth_plan_backward_workspace_bytes.argtypes = [vp, ctypes.c_int]
     L.rf_smooth_plan_backward_workspace_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p

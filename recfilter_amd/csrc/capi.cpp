@@ -653,6 +653,33 @@ int rf_var_plan_backward_power_timed(rf_var_plan *plan, const void *const *in_pl
     });
 }
 
+int rf_var_plan_backward_power_bases(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes, const float *bases,
+                                     const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_exponent_planes,
+                                     double *grad_bases, void *stream) {
+    return fenced("rf_var_plan_backward_power_bases", [&] {
+        if (!bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        return run_var_backward(plan, in_planes, exponent_planes, bases, grad_out_planes, grad_in_planes, grad_exponent_planes, (hipStream_t)stream, nullptr,
+                                true, grad_bases);
+    });
+}
+
+int rf_var_plan_backward_power_bases_timed(rf_var_plan *plan, const void *const *in_planes, const void *const *exponent_planes, const float *bases,
+                                           const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_exponent_planes,
+                                           double *grad_bases, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var_plan_backward_power_bases_timed", [&] {
+        if (!plan || !bases) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (int rc = timed_names(plan->backward_bases_names, ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var_backward(plan, in_planes, exponent_planes, bases, grad_out_planes, grad_in_planes, grad_exponent_planes, (hipStream_t)stream, ms_out,
+                                true, grad_bases);
+    });
+}
+
+int rf_var_plan_backward_bases_num_kernels(const rf_var_plan *plan) { return plan ? (int)plan->backward_bases_names.size() : 0; }
+
+size_t rf_var_plan_backward_bases_workspace_bytes(const rf_var_plan *plan) {
+    return plan ? plan->backward_workspace_bytes(true) + plan->bases_slab_bytes() : 0;
+}
+
 int rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gradients) {
     return plan ? (int)plan->backward_names[with_weight_gradients ? 1 : 0].size() : 0;
 }
@@ -729,6 +756,10 @@ int rf_smooth_plan_bases(const rf_smooth_plan *plan, float *out) {
     return RF_OK;
 }
 
+int rf_smooth_plan_set_sigmas(rf_smooth_plan *plan, double sigma_s, double sigma_r) {
+    return fenced("rf_smooth_plan_set_sigmas", [&] { return set_smooth_sigmas(plan, sigma_s, sigma_r); });
+}
+
 int rf_smooth_plan_execute(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes, void *const *out_planes,
                            void *stream) {
     return fenced("rf_smooth_plan_execute", [&] { return run_smooth_plan(plan, image_planes, guide_planes, out_planes, (hipStream_t)stream, nullptr); });
@@ -762,6 +793,32 @@ int rf_smooth_plan_backward_timed(rf_smooth_plan *plan, const void *const *image
         if (int rc = timed_names(names, ms_out, names_out, capacity); rc != RF_OK) return rc;
         return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, ms_out);
     });
+}
+
+int rf_smooth_plan_backward_sigmas(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                   const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes, int32_t edges,
+                                   double *grad_params, void *stream) {
+    return fenced("rf_smooth_plan_backward_sigmas", [&] {
+        return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, nullptr,
+                                   true, grad_params);
+    });
+}
+
+int rf_smooth_plan_backward_sigmas_timed(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
+                                         const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes,
+                                         int32_t edges, double *grad_params, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_smooth_plan_backward_sigmas_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return (int)RF_ERR_INVALID_ARG; }
+        if (!plan->has_backward()) return refuse_volume_backward();
+        if (int rc = timed_names(plan->sigma_names[edges], ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_smooth_backward(plan, image_planes, guide_planes, grad_out_planes, grad_image_planes, grad_guide_planes, edges, (hipStream_t)stream, ms_out,
+                                   true, grad_params);
+    });
+}
+
+int rf_smooth_plan_backward_sigmas_num_kernels(const rf_smooth_plan *plan, int edges) {
+    return plan ? (int)plan->sigma_names[edges ? 1 : 0].size() : 0;
 }
 
 int rf_smooth_plan_backward_num_kernels(const rf_smooth_plan *plan, int edges) {

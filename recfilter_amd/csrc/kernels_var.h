@@ -66,7 +66,46 @@ struct VarGradArgs {
     // the batch, on gridDim.z: image b's planes are these strides (samples) behind image 0's
     int32_t batch;
     int64_t lam_stride, x_stride, y_stride, grad_stride, exponents_stride;
+    // the base-reducing form (rf_var_plan_backward_power_bases; exponents != nullptr): not null -> every workgroup also stores
+    //   slabs[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum over its samples of (w == 0 ? 0 : d * w * dL/dw)
+    // in f64, var_grad_blocks(a) entries in all; `grad` may then be null (nothing is stored to it).  Only these instances look at it.
+    double *slabs;
 };
+// the workgroups of a base-reducing var_grad launch, whose grid walks at most kVarReduceRows rows at once (the rest in the stride
+// loop): the slab entries it writes
+constexpr int kVarReduceRows = 1024;
+int64_t var_grad_blocks(int32_t width, int32_t height, int32_t batch);
+
+// var_dot (rf_smooth_plan_backward_sigmas): one streaming launch over up to three pairs (gd, d) of dense f32 arrays of n samples (a
+// multiple of 4; the images of a batch lie one behind the other).  Workgroup w of var_dot_blocks(n) stores, per pair p, in f64,
+//   slabs[(2 * p) * blocks + w]     = its share of sum gd * (d - d0[p])      (gd == 0: the term is 0 by a select, whatever d holds)
+//   slabs[(2 * p + 1) * blocks + w] = its share of sum gd
+// lanes in the order of their grid-stride walk, the workgroup by var_grad's fixed tree.  No atomics.
+struct VarDotArgs {
+    const float *gd[3], *d[3];
+    float d0[3];
+    int32_t n_pairs;
+    int64_t n;
+    double *slabs;
+};
+int64_t var_dot_blocks(int64_t n);
+int launch_var_dot(const VarDotArgs &a, hipStream_t stream);
+
+// var_param_sum, one workgroup: with S_s = slabs[offset[s]] + ... + slabs[offset[s] + count[s] - 1], summed lane-strided and then by
+// a fixed tree in f64,  out[j] = sum over the segments s, in index order, of (target[s] == j ? factor[s] * S_s : 0) +
+// (target2[s] == j ? factor2[s] * S_s : 0);  target2 < 0: none.  An out entry no segment names is stored as 0.  No atomics: two runs
+// agree bit for bit.
+constexpr int kVarParamSegments = 64, kVarParamOutputs = 16;
+struct VarParamSumArgs {
+    const double *slabs;
+    double *out;
+    int32_t n_out;                  // at most kVarParamOutputs
+    int32_t n_segments;             // at most kVarParamSegments
+    int64_t offset[kVarParamSegments], count[kVarParamSegments];
+    int32_t target[kVarParamSegments], target2[kVarParamSegments];
+    double factor[kVarParamSegments], factor2[kVarParamSegments];
+};
+int launch_var_param_sum(const VarParamSumArgs &a, hipStream_t stream);
 
 // d_x = 1 + scale * sum_ch |g - g one column to the left|, d_y the same with the row above (kernels_var.hip, var_distances)
 struct VarDistArgs {

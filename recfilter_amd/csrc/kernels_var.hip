@@ -46,6 +46,9 @@
 // give the gradient of an EXPONENT plane: d/dd exp2(d l) = w ln(base), so the register sum is multiplied by w * ln_base, w formed
 // from d as the scans form it -- never by d itself (d = +inf: w = 0, a gradient of exactly 0).
 //
+// Its BASES instances (rf_var_plan_backward_power_bases) also reduce d * w * dL/dw -- base * dL/dbase -- in f64 to one slab entry
+// per workgroup, and var_param_sum, one workgroup, sums the slabs in index order: no atomics there either.
+//
 // var_distances_grad (rf_var_distances_backward): the adjoint of var_distances, a gather -- a guide sample collects from the (at
 // most) four differences it takes part in, with the sign of each; one streaming launch, no atomics.
 //
@@ -451,13 +454,29 @@ __device__ __forceinline__ void load_previous(const float *p, int64_t own_at, in
     }
 }
 
-template <int DIM, bool CAUSAL, bool POWER = false>
+// BASES (rf_var_plan_backward_power_bases; POWER only): the launch also reduces t[i] = (w[i] == 0 ? 0 : d[i] * w[i] * dL/dw[i]), whose sum
+// over the plane is base * dL/dbase.  A lane adds its t in f64, in the order it visits its rows; the workgroup folds its lanes by a
+// fixed tree (shuffles down the wave, then the four waves in index order through LDS) and stores ONE slab entry at the index of
+// its block: no atomics, and a second run gives the same bits.  Lanes past the width stay alive for the barrier and contribute 0;
+// a null `grad` switches the plane's store off.  d is never a factor where w is 0 (d = +inf: exactly 0).
+__device__ __forceinline__ double var_wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+template <int DIM, bool CAUSAL, bool POWER = false, bool BASES = false>
 __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
+    static_assert(!BASES || POWER, "the base gradient belongs to the power form");
     const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (c >= a.width) return;
+    if constexpr (!BASES) {
+        if (c >= a.width) return;
+    }
     const int64_t b = blockIdx.z;                    // the image of the batch
-    float *const grad = a.grad + b * a.grad_stride;
-    for (int r = blockIdx.y; r < a.height; r += gridDim.y) {
+    [[maybe_unused]] double acc = 0.0;
+    [[maybe_unused]] const bool store = !BASES || a.grad != nullptr;      // (uniform)
+    float *const grad = store ? a.grad + b * a.grad_stride : nullptr;
+    const int rows = BASES && c >= a.width ? 0 : a.height;      // (BASES: a lane past the width walks no row)
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
         const int64_t own_at = (int64_t)r * a.width + c;
         const int64_t before_at = DIM == 0 ? own_at - (c > 0 ? 1 : 0) : (int64_t)max(r - 1, 0) * a.width + c;
         float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -486,8 +505,19 @@ __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
         if constexpr (POWER) {                   // dL/dd = (w * ln base) * dL/dw, w as the scans form it
             float d[4];
             load_chunk(a.exponents + b * a.exponents_stride, own_at, d);
+            if constexpr (BASES) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float w = power_weight(d[j], a.log2_base);
+                    const double t = w == 0.0f ? 0.0 : ((double)d[j] * (double)w) * (double)s[j];
+                    acc += (DIM == 0 ? c + j == 0 : r == 0) ? 0.0 : t;
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 4; j++) s[j] = (power_weight(d[j], a.log2_base) * a.ln_base) * s[j] + 0.0f;      // (w = 0: +0, not -0)
+        }
+        if constexpr (BASES) {
+            if (!store) continue;
         }
 #pragma unroll
         for (int j = 0; j < 4; j++) s[j] = (DIM == 0 ? c + j == 0 : r == 0) ? 0.0f : s[j];
@@ -498,6 +528,82 @@ __global__ void __launch_bounds__(256) var_grad_kernel(VarGradArgs a) {
             for (int j = 0; j < 4; j++) s[j] = old[j] + s[j];
         }
         *reinterpret_cast<float4 *>(grad + own_at) = make_float4(s[0], s[1], s[2], s[3]);
+    }
+    if constexpr (BASES) {
+        __shared__ double red[4];
+        const double wave = var_wave_sum(acc);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wave;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            a.slabs[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    }
+}
+
+// ---- var_param_sum: one workgroup, the f64 sibling of coeff_grad_sum (kernels_adjoint.hip) ------------------------------------------
+// Every segment of slabs is summed lane-strided, folded down each wave and left in LDS, wave by wave; behind ONE barrier lane j sums
+// the waves of the segments that name out[j], in index order, each times its host-formed factor.
+constexpr int kParamSumThreads = 1024;
+__global__ void __launch_bounds__(kParamSumThreads) var_param_sum_kernel(VarParamSumArgs a) {
+    __shared__ double red[kVarParamSegments][kParamSumThreads / 64];
+    const int tid = threadIdx.x;
+    for (int s = 0; s < a.n_segments; s++) {
+        const double *seg = a.slabs + a.offset[s];
+        double v = 0.0;
+        // eight loads in flight per lane, added in index order: the sum's bits do not depend on the unrolling
+        int64_t i = tid;
+        for (; i + 7 * kParamSumThreads < a.count[s]; i += 8 * kParamSumThreads) {
+            double e[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) e[j] = seg[i + j * kParamSumThreads];
+#pragma unroll
+            for (int j = 0; j < 8; j++) v += e[j];
+        }
+        for (; i < a.count[s]; i += kParamSumThreads) v += seg[i];
+        v = var_wave_sum(v);
+        if ((tid & 63) == 0) red[s][tid >> 6] = v;
+    }
+    __syncthreads();
+    if (tid < a.n_out) {
+        double total = 0.0;
+        for (int s = 0; s < a.n_segments; s++) {
+            if (a.target[s] != tid && a.target2[s] != tid) continue;
+            double v = 0.0;
+            for (int w = 0; w < kParamSumThreads / 64; w++) v += red[s][w];
+            if (a.target[s] == tid) total += a.factor[s] * v;
+            if (a.target2[s] == tid) total += a.factor2[s] * v;
+        }
+        a.out[tid] = total;
+    }
+}
+
+// ---- var_dot: lane = 4 adjacent samples, a grid-stride walk -----------------------------------------------------------------------
+constexpr int kDotMaxBlocks = 1024;
+__global__ void __launch_bounds__(256) var_dot_kernel(VarDotArgs a) {
+    __shared__ double red[6][4];
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; e < a.n; e += (int64_t)gridDim.x * 1024) {
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            if (p >= a.n_pairs) continue;          // (uniform)
+            float g[4], d[4];
+            load_chunk(a.gd[p], e, g);
+            load_chunk(a.d[p], e, d);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                acc[2 * p] += g[j] == 0.0f ? 0.0 : (double)g[j] * ((double)d[j] - (double)a.d0[p]);      // (d = +inf beside gd = 0: 0, not NaN)
+                acc[2 * p + 1] += (double)g[j];
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        const double wave = var_wave_sum(acc[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = wave;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * a.n_pairs) {
+        const int q = threadIdx.x;
+        a.slabs[(int64_t)q * gridDim.x + blockIdx.x] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
     }
 }
 
@@ -787,18 +893,43 @@ int launch_var_distances_volume(const VarDistVolumeArgs &a, bool guide_u8, hipSt
 int launch_var_grad(const VarGradArgs &a, int dim, bool causal, hipStream_t stream) {
     const char *const what = dim == 0 ? "var_grad_x" : dim == 1 ? "var_grad_y" : "var_grad_z";
     if (dim == 2) dim = 1;
-    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)a.batch), block(256);
-#define RF_VAR_LAUNCH_GRAD(POWER)                                                                                   \
+    // the base-reducing form walks at most kVarReduceRows rows at once: fewer, larger slabs for var_param_sum
+    const dim3 grid((unsigned)((a.width / 4 + 255) / 256), (unsigned)std::min(a.height, a.slabs ? kVarReduceRows : 65535), (unsigned)a.batch), block(256);
+#define RF_VAR_LAUNCH_GRAD(POWER, BASES)                                                                            \
     if (dim == 0) {                                                                                                 \
-        if (causal) hipLaunchKernelGGL((var_grad_kernel<0, true, POWER>), grid, block, 0, stream, a);               \
-        else hipLaunchKernelGGL((var_grad_kernel<0, false, POWER>), grid, block, 0, stream, a);                     \
+        if (causal) hipLaunchKernelGGL((var_grad_kernel<0, true, POWER, BASES>), grid, block, 0, stream, a);        \
+        else hipLaunchKernelGGL((var_grad_kernel<0, false, POWER, BASES>), grid, block, 0, stream, a);              \
     } else {                                                                                                        \
-        if (causal) hipLaunchKernelGGL((var_grad_kernel<1, true, POWER>), grid, block, 0, stream, a);               \
-        else hipLaunchKernelGGL((var_grad_kernel<1, false, POWER>), grid, block, 0, stream, a);                     \
+        if (causal) hipLaunchKernelGGL((var_grad_kernel<1, true, POWER, BASES>), grid, block, 0, stream, a);        \
+        else hipLaunchKernelGGL((var_grad_kernel<1, false, POWER, BASES>), grid, block, 0, stream, a);              \
     }
-    if (a.exponents) { RF_VAR_LAUNCH_GRAD(true) } else { RF_VAR_LAUNCH_GRAD(false) }
+    if (a.slabs) {                                   // the base-reducing form: POWER instances only
+        if (!a.exponents) { set_error("%s: the base gradient needs the exponent plane", what); return RF_ERR_INVALID_ARG; }
+        RF_VAR_LAUNCH_GRAD(true, true)
+    } else if (a.exponents) { RF_VAR_LAUNCH_GRAD(true, false) } else { RF_VAR_LAUNCH_GRAD(false, false) }
 #undef RF_VAR_LAUNCH_GRAD
     return launched(what);
+}
+
+int64_t var_grad_blocks(int32_t width, int32_t height, int32_t batch) {
+    return (int64_t)((width / 4 + 255) / 256) * std::min(height, kVarReduceRows) * batch;
+}
+
+int64_t var_dot_blocks(int64_t n) { return std::min<int64_t>((n / 4 + 255) / 256, kDotMaxBlocks); }
+
+int launch_var_dot(const VarDotArgs &a, hipStream_t stream) {
+    if (a.n_pairs < 1 || a.n_pairs > 3 || a.n < 4 || a.n % 4 != 0) { set_error("var_dot: bad arguments"); return RF_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(var_dot_kernel, dim3((unsigned)var_dot_blocks(a.n)), dim3(256), 0, stream, a);
+    return launched("var_dot");
+}
+
+int launch_var_param_sum(const VarParamSumArgs &a, hipStream_t stream) {
+    if (a.n_out < 1 || a.n_out > kVarParamOutputs || a.n_segments < 0 || a.n_segments > kVarParamSegments) {
+        set_error("var_param_sum: bad argument counts");
+        return RF_ERR_INVALID_ARG;
+    }
+    hipLaunchKernelGGL(var_param_sum_kernel, dim3(1), dim3(kParamSumThreads), 0, stream, a);
+    return launched("var_param_sum");
 }
 
 int launch_var_distances_grad(const VarDistGradArgs &a, hipStream_t stream) {

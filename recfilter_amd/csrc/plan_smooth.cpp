@@ -13,6 +13,11 @@
 // per iteration in reverse order the inner plan's adjoint WITH both exponent gradients on that iteration's input -- the first
 // stores into gd_x, gd_y, the later ones add -- and one var_distances_grad launch takes gd_x, gd_y to the guide.
 //
+// With the sigma gradients (rf_smooth_plan_backward_sigmas) it runs the list through the distances at either setting of `edges` (edges = 0
+// leaves out the distances' adjoint), every inner backward on the base-reducing var_grad instances with its own segment of plan-owned
+// f64 slabs, then one var_dot launch (sum gd (d - d0) and sum gd) and one var_param_sum launch that stores dL/dsigma_s, dL/dsigma_r,
+// dL/dspacing_z and dL/da_k with factors the host formed in double.  rf_smooth_plan_set_sigmas recomputes the constants as create does.
+//
 // A batched plan (rf_smooth_plan_create_batched) is the same sequence: every launch takes all the images on gridDim.z, each image
 // with its own distance planes, tails, carries and working planes, laid out image after image as a single-image plan lays out
 // its one.  The launch count does not depend on the batch.  The caller's planes are checked per (image, plane) extent, sorted
@@ -39,6 +44,7 @@
 rf_smooth_plan::~rf_smooth_plan() {
     if (planes) (void)hipFree(planes);
     if (grad_planes) (void)hipFree(grad_planes);
+    if (sigma_slabs) (void)hipFree(sigma_slabs);
 }
 
 namespace rf {
@@ -160,6 +166,44 @@ int check_extents(const ExtentArray *arrays, int n_arrays, int batch) {
 namespace {
 int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, int64_t depth, float spacing_z, bool volume_backward,
                   rf_smooth_plan **out);
+
+// What the sigmas determine, for a plan whose guide kind and iteration count are set: the scale of var_distances and, per iteration,
+// a_k with its log2 and ln -- or the refusal of a scale that is no f32 or of an a_k that rounds to 0 or 1.  The outputs are written
+// only where nothing is refused.  Shared by create and rf_smooth_plan_set_sigmas: the two form the same bits.
+int smooth_constants(const rf_smooth_plan *plan, double sigma_s, double sigma_r, float &scale_out, std::vector<float> &bases,
+                     std::vector<float> &log2_bases, std::vector<float> &ln_bases) {
+    // a byte guide means that guide divided by 255 (a separate uint8 guide, or a uint8 image guiding itself)
+    const bool bytes_guide = plan->n_guide > 0 ? plan->guide_u8 : plan->image_u8;
+    const float scale = (float)(sigma_s / sigma_r / (bytes_guide ? 255.0 : 1.0));
+    if (!std::isfinite(scale)) { set_error("sigma_s / sigma_r = %g is not an f32", sigma_s / sigma_r); return RF_ERR_UNSUPPORTED; }
+    const int K = plan->iterations;
+    std::vector<float> a, l2, ln;
+    for (int k = 0; k < K; k++) {
+        const double sigma_k = sigma_s * std::sqrt(3.0) * std::ldexp(1.0, K - 1 - k) / std::sqrt(std::ldexp(1.0, 2 * K) - 1.0);
+        const float a_k = (float)std::exp(-std::sqrt(2.0) / sigma_k);
+        if (!(a_k > 0.0f && a_k < 1.0f)) {
+            set_error("iteration k = %d: the base a_k = exp(-sqrt(2) / %g) rounds to %g in f32", k, sigma_k, (double)a_k);
+            return RF_ERR_UNSUPPORTED;
+        }
+        a.push_back(a_k);
+        l2.push_back((float)std::log2((double)a_k));
+        ln.push_back((float)std::log((double)a_k));
+    }
+    scale_out = scale;
+    bases.swap(a);
+    log2_bases.swap(l2);
+    ln_bases.swap(ln);
+    return RF_OK;
+}
+}
+
+int set_smooth_sigmas(rf_smooth_plan *plan, double sigma_s, double sigma_r) {
+    if (!plan) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    if (!std::isfinite(sigma_s) || !(sigma_s > 0.0)) { set_error("sigma_s must be finite and positive (got %g)", sigma_s); return RF_ERR_INVALID_ARG; }
+    if (!std::isfinite(sigma_r) || !(sigma_r > 0.0)) { set_error("sigma_r must be finite and positive (got %g)", sigma_r); return RF_ERR_INVALID_ARG; }
+    const int rc = smooth_constants(plan, sigma_s, sigma_r, plan->scale, plan->bases, plan->log2_bases, plan->ln_bases);
+    if (rc == RF_OK) { plan->sigma_s = sigma_s; plan->sigma_r = sigma_r; }
+    return rc;
 }
 
 int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out) {
@@ -239,22 +283,11 @@ int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch,
         plan->image_stride = batch->image_stride;
         plan->guide_stride = batch->guide_stride;
     }
-    // a byte guide means that guide divided by 255 (a separate uint8 guide, or a uint8 image guiding itself)
-    const bool bytes_guide = desc->n_guide > 0 ? plan->guide_u8 : plan->image_u8;
-    plan->scale = (float)(desc->sigma_s / desc->sigma_r / (bytes_guide ? 255.0 : 1.0));
-    if (!std::isfinite(plan->scale)) { set_error("sigma_s / sigma_r = %g is not an f32", desc->sigma_s / desc->sigma_r); return RF_ERR_UNSUPPORTED; }
+    rc = smooth_constants(plan.get(), desc->sigma_s, desc->sigma_r, plan->scale, plan->bases, plan->log2_bases, plan->ln_bases);
+    if (rc != RF_OK) return rc;
+    plan->sigma_s = desc->sigma_s;
+    plan->sigma_r = desc->sigma_r;
     const int K = desc->iterations;
-    for (int k = 0; k < K; k++) {
-        const double sigma_k = desc->sigma_s * std::sqrt(3.0) * std::ldexp(1.0, K - 1 - k) / std::sqrt(std::ldexp(1.0, 2 * K) - 1.0);
-        const float a_k = (float)std::exp(-std::sqrt(2.0) / sigma_k);
-        if (!(a_k > 0.0f && a_k < 1.0f)) {
-            set_error("iteration k = %d: the base a_k = exp(-sqrt(2) / %g) rounds to %g in f32", k, sigma_k, (double)a_k);
-            return RF_ERR_UNSUPPORTED;
-        }
-        plan->bases.push_back(a_k);
-        plan->log2_bases.push_back((float)std::log2((double)a_k));
-        plan->ln_bases.push_back((float)std::log((double)a_k));
-    }
     const rf_var_scan_desc scans[6] = {{0, 1, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 1}, {2, 1, 2}, {2, 0, 2}};
     // the inner plan: +x -x +y -y(, +z -z), a weight plane per dimension (the device checks, and the tails and the carries)
     rf_var_plan *inner = nullptr;
@@ -308,6 +341,14 @@ int build_checked(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch,
         for (int k = 0; k < K; k++)
             for (const std::string &n : inner->backward_names[edges]) names.push_back(n);
         if (edges) names.push_back(plan->volume ? "var_distances_volume_grad" : "var_distances_grad");
+    }
+    // the sigma gradients: the list through the distances with the reducing var_grad launches (same names), then the two sums
+    for (int edges = 0; edges < 2 && plan->has_backward(); edges++) {
+        std::vector<std::string> &names = plan->sigma_names[edges];
+        names = plan->backward_names[1];
+        if (!edges) names.pop_back();
+        names.push_back("var_dot");
+        names.push_back("var_param_sum");
     }
     *out = plan.release();
     return RF_OK;
@@ -448,18 +489,20 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
 
 int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
                         const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes, int32_t edges,
-                        hipStream_t stream, float *ms_out) {
+                        hipStream_t stream, float *ms_out, bool sigmas, double *grad_params) {
     // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
     if (!plan || !grad_out_planes || !grad_image_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    if (sigmas && !grad_params) { set_error("null grad_params"); return RF_ERR_INVALID_ARG; }
+    if (sigmas && ((uintptr_t)grad_params & 7u) != 0) { set_error("grad_params must be 8-byte aligned: it receives 3 + iterations doubles"); return RF_ERR_INVALID_ARG; }
     if (edges != 0 && edges != 1) { set_error("edges must be 0 or 1 (got %d)", edges); return RF_ERR_INVALID_ARG; }
     if (!plan->has_backward()) return refuse_volume_backward();
     if (plan->image_u8) { set_error("the backward of a smoothing plan takes f32 images (this plan's are uint8)"); return RF_ERR_UNSUPPORTED; }
     const bool self = plan->n_guide == 0;
     if (!self && !guide_planes) { set_error("this plan takes %d separate guide planes: guide_planes is null", plan->n_guide); return RF_ERR_INVALID_ARG; }
     if (self && guide_planes) { set_error("this plan's image guides itself (n_guide = 0): guide_planes must be null"); return RF_ERR_INVALID_ARG; }
-    const bool need_image = self || edges == 1;
+    const bool need_image = self || edges == 1 || sigmas;      // (the sigma gradients rerun the forward)
     if (need_image && !image_planes) {
-        set_error(self ? "this plan's image guides itself: the backward needs the image planes (image_planes is null)"
+        set_error(sigmas ? "the sigma gradients need the image planes (image_planes is null)" : self ? "this plan's image guides itself: the backward needs the image planes (image_planes is null)"
                        : "gradients through the distances need the image planes (image_planes is null)");
         return RF_ERR_INVALID_ARG;
     }
@@ -510,7 +553,14 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     if (rc != RF_OK) return rc;
     RF_HIP_CHECK(hipSetDevice(plan->device));
     rf_var_plan *inner = plan->inner.get();
-    if (edges == 1) {
+    const bool through = edges == 1 || sigmas;       // the launch list through the distances: checkpoints and exponent gradients
+    if (sigmas && !plan->sigma_slabs && hipMalloc((void **)&plan->sigma_slabs, (size_t)plan->sigma_slab_count() * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->sigma_slabs = nullptr;
+        set_error("hipMalloc of %zu bytes for the sigma gradients' slabs failed", (size_t)plan->sigma_slab_count() * sizeof(double));
+        return RF_ERR_NOMEM;
+    }
+    if (through) {
         rc = ensure_var_grad_planes(inner);
         if (rc != RF_OK) return rc;
         if (!plan->grad_planes && hipMalloc((void **)&plan->grad_planes, plan->own_backward_bytes()) != hipSuccess) {
@@ -520,7 +570,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
             return RF_ERR_NOMEM;
         }
     }
-    LaunchTimer timer(stream, ms_out, plan->backward_names[edges].size());
+    LaunchTimer timer(stream, ms_out, sigmas ? plan->sigma_names[edges].size() : plan->backward_names[edges].size());
     if (timer.status() != RF_OK) return timer.status();
     const DistancePlanes d = distance_planes(plan, plan->planes), g = distance_planes(plan, plan->grad_planes);
     rc = form_distances(plan, image_planes, guide_planes, d, stream);
@@ -530,7 +580,7 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     // the output of iteration k, k = 0 .. K-2: [iteration][image][plane]
     const int64_t checkpoint_stride = (int64_t)samples * P;
     void *checkpoints[RF_SMOOTH_MAX_ITERATIONS][RF_MAX_PLANES] = {};
-    if (edges == 1) {
+    if (through) {
         for (int k = 0; k + 1 < K; k++) {
             for (int pl = 0; pl < P; pl++) checkpoints[k][pl] = g.own + samples * ((size_t)k * (size_t)B * P + pl);
             VarIo io{};
@@ -547,11 +597,12 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     for (int k = K - 1; k >= 0; k--) {
         const IterationConstants c = iteration_constants(plan, k);
         VarBackwardIo io{};
-        io.in = edges == 0 ? nullptr : k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
+        io.in = !through ? nullptr : k == 0 ? image_planes : (const void *const *)checkpoints[k - 1];
         io.weights = exponents;
         io.grad_out = k == K - 1 ? grad_out_planes : (const void *const *)grad_image_planes;
         io.grad_in = grad_image_planes;
-        io.grad_weights = edges == 1 ? grad_exponents : nullptr;
+        io.grad_weights = through ? grad_exponents : nullptr;
+        io.slabs = sigmas ? plan->sigma_slabs + (int64_t)k * inner->bases_slab_offset.back() : nullptr;
         io.log2_base = c.log2_base;
         io.ln_base = c.ln_base;
         io.holds_sum = c.holds_sum;
@@ -563,6 +614,64 @@ int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, c
     }
     if (edges == 1) {
         rc = form_guide_gradient(plan, image_planes, guide_planes, g, grad_image_planes, grad_guide_planes, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        if (rc != RF_OK) return rc;
+    }
+    if (sigmas) {
+        // Q and the sum of gd_z from one var_dot launch, then every scalar from one var_param_sum launch: the host forms the factors
+        // in double, the device multiplies -- nothing synchronises
+        const int n_dist = plan->n_distances(), n_scans = (int)inner->scans.size();
+        const int64_t per_iteration = inner->bases_slab_offset.back(), blocks = plan->dot_blocks();
+        double *const dot_slabs = plan->sigma_slabs + (int64_t)K * per_iteration;
+        VarDotArgs dot{};
+        for (int q = 0; q < n_dist; q++) {
+            dot.gd[q] = g.d[q];
+            dot.d[q] = d.d[q];
+            dot.d0[q] = q == 2 ? plan->spacing_z : 1.0f;
+        }
+        dot.n_pairs = n_dist;
+        dot.n = plan->samples() * plan->batch;
+        dot.slabs = dot_slabs;
+        rc = launch_var_dot(dot, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        if (rc != RF_OK) return rc;
+        // out: dL/dsigma_s, dL/dsigma_r, dL/dspacing_z, dL/da_0 .. dL/da_{K-1}.  With T the slabs of iteration k (sum of d w dL/dw):
+        // dL/da_k = T / a_k, and da_k/dsigma_s = a_k (-ln a_k) / sigma_s gives sigma_s its share T (-ln a_k) / sigma_s
+        VarParamSumArgs p{};
+        p.slabs = plan->sigma_slabs;
+        p.out = grad_params;
+        p.n_out = 3 + K;
+        int n = 0;
+        for (int k = 0; k < K; k++)
+            for (int q = 0; q < n_scans; q++, n++) {
+                const double a = (double)plan->bases[(size_t)k];
+                p.offset[n] = (int64_t)k * per_iteration + inner->bases_slab_offset[(size_t)q];
+                p.count[n] = inner->bases_slab_offset[(size_t)q + 1] - inner->bases_slab_offset[(size_t)q];
+                p.target[n] = 3 + k;
+                p.factor[n] = 1.0 / a;
+                p.target2[n] = 0;
+                p.factor2[n] = -std::log(a) / plan->sigma_s;
+            }
+        for (int q = 0; q < n_dist; q++) {
+            // sum gd (d - d0) = Q's share of dimension q: Q / sigma_s to sigma_s, -Q / sigma_r to sigma_r (a byte guide's 255 cancels)
+            p.offset[n] = (int64_t)K * per_iteration + (2 * q) * blocks;
+            p.count[n] = blocks;
+            p.target[n] = 0;
+            p.factor[n] = 1.0 / plan->sigma_s;
+            p.target2[n] = 1;
+            p.factor2[n] = -1.0 / plan->sigma_r;
+            n++;
+            if (q == 2) {      // sum gd_z: dL/dspacing_z
+                p.offset[n] = (int64_t)K * per_iteration + (2 * q + 1) * blocks;
+                p.count[n] = blocks;
+                p.target[n] = 2;
+                p.factor[n] = 1.0;
+                p.target2[n] = -1;
+                n++;
+            }
+        }
+        p.n_segments = n;
+        rc = launch_var_param_sum(p, stream);
         if (rc == RF_OK) rc = timer.mark();
         if (rc != RF_OK) return rc;
     }

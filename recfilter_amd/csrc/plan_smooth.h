@@ -28,6 +28,7 @@ struct rf_smooth_plan {
     int64_t samples() const { return width * height * depth; }      // of one plane
     int device = 0;
     bool host_only = false;
+    double sigma_s = 0.0, sigma_r = 0.0;     // as given to create or to rf_smooth_plan_set_sigmas: the factors of the sigma gradients
     float scale = 0.0f;                      // of var_distances: sigma_s / sigma_r, over 255 where the planes that guide are bytes
     std::vector<float> bases;                // a_k
     std::vector<float> log2_bases;           // (float)log2((double)a_k): what rf_var_plan_execute_power forms from a_k
@@ -48,6 +49,13 @@ struct rf_smooth_plan {
     float *grad_planes = nullptr;
     size_t own_backward_bytes() const { return (size_t)batch * (size_t)(n_distances() + (iterations - 1) * n_planes) * (size_t)samples() * sizeof(float); }
     size_t backward_workspace_bytes(bool edges) const { return edges && has_backward() ? own_backward_bytes() + inner->backward_workspace_bytes(true) : 0; }
+    // rf_smooth_plan_backward_sigmas: the names of [1] (edges = 0: without the final distances' adjoint), "var_dot", "var_param_sum";
+    // f64 slabs the plan owns -- per iteration the inner plan's bases slabs (iteration k's at k * inner->bases_slab_offset.back()),
+    // then var_dot's 2 * n_distances * var_dot_blocks entries -- allocated by the first call that needs them.
+    std::vector<std::string> sigma_names[2];
+    double *sigma_slabs = nullptr;
+    int64_t dot_blocks() const { return rf::var_dot_blocks(samples() * batch); }
+    int64_t sigma_slab_count() const { return (int64_t)iterations * inner->bases_slab_offset.back() + 2 * n_distances() * dot_blocks(); }
     ~rf_smooth_plan();
 };
 
@@ -56,6 +64,8 @@ namespace rf {
 int build_smooth_plan(const rf_smooth_desc *desc, const rf_smooth_batch_desc *batch, rf_smooth_plan **out);
 // rf_smooth_plan_create_volume
 int build_smooth_volume_plan(const rf_smooth_volume_desc *desc, rf_smooth_plan **out);
+// rf_smooth_plan_set_sigmas: the scale and the bases of new sigmas, formed as create forms them; a refusal leaves the plan as it was
+int set_smooth_sigmas(rf_smooth_plan *plan, double sigma_s, double sigma_r);
 // what the backward entry points answer for a volume plan without RF_SMOOTH_VOLUME_BACKWARD: RF_ERR_UNSUPPORTED
 int refuse_volume_backward();
 // ms_out == nullptr: plain asynchronous execute; else every launch bracketed by events (capacity checked by the caller)
@@ -64,5 +74,5 @@ int run_smooth_plan(rf_smooth_plan *plan, const void *const *image_planes, const
 // The adjoint (rf_smooth_plan_backward in recfilter_amd.h); ms_out: one slot per name of backward_names[edges].
 int run_smooth_backward(rf_smooth_plan *plan, const void *const *image_planes, const void *const *guide_planes,
                         const void *const *grad_out_planes, void *const *grad_image_planes, void *const *grad_guide_planes, int32_t edges,
-                        hipStream_t stream, float *ms_out);
+                        hipStream_t stream, float *ms_out, bool sigmas = false, double *grad_params = nullptr);
 }  // namespace rf

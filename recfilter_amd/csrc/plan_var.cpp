@@ -22,6 +22,8 @@
 // weight plane, added by the later ones; the host knows which is which, so there are no atomics and no zero-fill.
 // The power form (rf_var_plan_backward_power) is the same list on the kernels' POWER instances: the stages carry log2 of their
 // plane's base, var_grad also its natural logarithm and the exponent plane, and what it stores is the gradient of the exponents.
+// With the gradient of the bases (rf_var_plan_backward_power_bases) the var_grad launches are the base-reducing ones, each on its own
+// segment of plan-owned f64 slabs, and one var_param_sum launch behind them stores dL/dbases to the caller's device buffer.
 // run_var_backward checks and constructs the timer; launch_var_backward issues the launches, and is what the smoothing plan's
 // backward (plan_smooth.cpp) calls per iteration -- with planes that already hold a sum after the first.
 //
@@ -57,6 +59,7 @@
 rf_var_plan::~rf_var_plan() {
     if (tails) (void)hipFree(tails);
     if (grad_planes) (void)hipFree(grad_planes);
+    if (bases_slabs) (void)hipFree(bases_slabs);
     if (carry) (void)hipFree(carry);
 }
 
@@ -161,6 +164,7 @@ constexpr int64_t kVarMaxVolumeLines = int64_t(1) << 30;      // width * height:
 constexpr int64_t kVarMaxGridZ = 65535;                        // depth * n_planes: the slices ride on gridDim.z beside the planes
 
 int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool signal);
+VarArgs scan_args(const rf_var_plan *plan, int dim, const void *weights, int mode);
 
 }  // namespace
 
@@ -267,6 +271,15 @@ int build_checked(const rf_var_desc *desc, rf_var_plan **out, int batch, bool si
             push_stage_names(plan->backward_names[with], "var_adj_", desc->scans[q].dim, signal);
             if (with) plan->backward_names[with].push_back(desc->scans[q].dim == 0 ? "var_grad_x" : desc->scans[q].dim == 1 ? "var_grad_y" : "var_grad_z");
         }
+    // the base-reducing route: the names above and the sum; a slab entry per workgroup of every scan's var_grad launch, whose
+    // grid is that of the scan's stage (a volume: the view of a z stage, the slices of an x / y stage as its batch)
+    plan->backward_bases_names = plan->backward_names[1];
+    plan->backward_bases_names.push_back("var_param_sum");
+    plan->bases_slab_offset.assign(1, 0);
+    for (const rf_var_scan_desc &sc : plan->scans) {
+        const VarArgs a = scan_args(plan.get(), sc.dim, nullptr, VAR_CAUSAL);
+        plan->bases_slab_offset.push_back(plan->bases_slab_offset.back() + var_grad_blocks(a.width, a.height, a.batch));
+    }
     // tiles x lines of the dimension that needs more: x scans have `height` lines (per slice of a volume), y scans `width`, z
     // scans width * height
     int64_t slots = 0;
@@ -418,13 +431,20 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
 
 int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
                      const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream,
-                     float *ms_out) {
+                     float *ms_out, bool with_bases, double *grad_bases) {
     // refusals, in the order recfilter_amd.h documents; nothing of HIP is called before the last of them
     if (!plan || !weight_planes || !grad_out_planes || !grad_in_planes) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
-    bool with_weights = false;
+    if (with_bases && !bases) { set_error("null argument"); return RF_ERR_INVALID_ARG; }
+    bool with_weights = with_bases;                   // (the base gradient takes the weight-gradient route, planes or none)
+    void *const no_planes[RF_VAR_MAX_SCANS] = {};
+    if (!grad_weight_planes && with_bases) grad_weight_planes = no_planes;
     if (grad_weight_planes)
         for (int k = 0; k < plan->n_weights; k++) with_weights = with_weights || grad_weight_planes[k] != nullptr;
     if (with_weights && !in_planes) { set_error("weight gradients need the input planes (in_planes is null)"); return RF_ERR_INVALID_ARG; }
+    if (with_bases) {
+        if (!grad_bases) { set_error("null grad_bases"); return RF_ERR_INVALID_ARG; }
+        if (((uintptr_t)grad_bases & 7u) != 0) { set_error("grad_bases must be 8-byte aligned: it receives n_weights doubles"); return RF_ERR_INVALID_ARG; }
+    }
     float log2_base[RF_VAR_MAX_SCANS] = {}, ln_base[RF_VAR_MAX_SCANS] = {};
     int rc = bases ? power_constants(bases, plan->n_weights, log2_base, ln_base) : RF_OK;
     if (rc != RF_OK) return rc;
@@ -453,7 +473,11 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
         rc = ensure_var_grad_planes(plan);
         if (rc != RF_OK) return rc;
     }
-    LaunchTimer timer(stream, ms_out, plan->backward_names[with_weights ? 1 : 0].size());
+    if (with_bases) {
+        rc = ensure_var_bases_slabs(plan);
+        if (rc != RF_OK) return rc;
+    }
+    LaunchTimer timer(stream, ms_out, with_bases ? plan->backward_bases_names.size() : plan->backward_names[with_weights ? 1 : 0].size());
     if (timer.status() != RF_OK) return timer.status();
     VarBackwardIo io{};
     io.in = in_planes;
@@ -463,8 +487,37 @@ int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void
     io.grad_weights = with_weights ? grad_weight_planes : nullptr;
     io.log2_base = bases ? log2_base : nullptr;
     io.ln_base = bases ? ln_base : nullptr;
+    io.slabs = with_bases ? plan->bases_slabs : nullptr;
     rc = launch_var_backward(plan, io, stream, timer);
+    if (rc == RF_OK && with_bases) {
+        // dL/dbase_k = (1 / base_k) * the slabs of the scans that read plane k, scan by scan in index order
+        VarParamSumArgs p{};
+        p.slabs = plan->bases_slabs;
+        p.out = grad_bases;
+        p.n_out = K;
+        p.n_segments = (int32_t)plan->scans.size();
+        for (int q = 0; q < p.n_segments; q++) {
+            p.offset[q] = plan->bases_slab_offset[q];
+            p.count[q] = plan->bases_slab_offset[q + 1] - plan->bases_slab_offset[q];
+            p.target[q] = plan->scans[q].weights;
+            p.target2[q] = -1;
+            p.factor[q] = 1.0 / (double)bases[p.target[q]];
+        }
+        rc = launch_var_param_sum(p, stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
     return rc == RF_OK ? timer.finish() : rc;
+}
+
+int ensure_var_bases_slabs(rf_var_plan *plan) {
+    if (plan->bases_slabs) return RF_OK;
+    if (hipMalloc((void **)&plan->bases_slabs, plan->bases_slab_bytes()) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->bases_slabs = nullptr;
+        set_error("hipMalloc of %zu bytes for the base gradients' slabs failed", plan->bases_slab_bytes());
+        return RF_ERR_NOMEM;
+    }
+    return RF_OK;
 }
 
 int ensure_var_grad_planes(rf_var_plan *plan) {
@@ -520,14 +573,14 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
         for (int pl = 0; pl < P; pl++) {
             a.src[pl] = q == S - 1 ? io.grad_out[pl] : io.grad_in[pl];
             a.dst[pl] = io.grad_in[pl];
-            a.lam[pl] = grad ? saved(S, pl) : nullptr;
+            a.lam[pl] = grad || io.slabs ? saved(S, pl) : nullptr;
         }
         a.src_stride = stage_stride(plan, sc.dim, q == S - 1 ? io.grad_out_stride : io.grad_in_stride);
         a.dst_stride = stage_stride(plan, sc.dim, io.grad_in_stride);
         a.lam_stride = stage_stride(plan, sc.dim, saved_stride);
         rc = launch_stage(a, sc.dim, plan->signal, stream, timer);
         if (rc != RF_OK || !with_weights) continue;
-        if (grad) {                                   // (a weight plane without a gradient: no launch, its slot reports 0 ms)
+        if (grad || io.slabs) {                       // (a weight plane without a gradient: no launch, its slot reports 0 ms)
             VarGradArgs g{};
             for (int pl = 0; pl < P; pl++) {
                 g.lam[pl] = saved(S, pl);
@@ -549,6 +602,7 @@ int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t 
                 g.log2_base = io.log2_base[sc.weights];
                 g.ln_base = io.ln_base[sc.weights];
             }
+            g.slabs = io.slabs ? io.slabs + plan->bases_slab_offset[q] : nullptr;
             touched[sc.weights] = true;
             rc = launch_var_grad(g, sc.dim, sc.causal != 0, stream);
         } else {

@@ -51,6 +51,13 @@ struct rf_var_plan {
     size_t backward_workspace_bytes(bool with_weight_gradients) const {
         return with_weight_gradients ? (scans.size() + 1) * (size_t)batch * (size_t)n_planes * (size_t)plane_samples() * sizeof(float) : 0;
     }
+    // rf_var_plan_backward_power_bases: backward_names[1] and "var_param_sum"; the f64 slabs of the base-reducing var_grad launches,
+    // one entry per workgroup, scan q's at bases_slab_offset[q] (bases_slab_offset[n_scans]: their number) -- no two launches of a
+    // call share an entry.  Allocated by the first call that needs them, freed with the plan.
+    std::vector<std::string> backward_bases_names;
+    std::vector<int64_t> bases_slab_offset;
+    double *bases_slabs = nullptr;
+    size_t bases_slab_bytes() const { return bases_slab_offset.empty() ? 0 : (size_t)bases_slab_offset.back() * sizeof(double); }
     ~rf_var_plan();
 };
 
@@ -88,9 +95,12 @@ int launch_var_stages(rf_var_plan *plan, const VarIo &io, const void *const *wei
 // (no gradient for that plane) or a plane.  ms_out as in run_var_plan, one slot per name of backward_names[with weight gradients].
 // bases == nullptr: the plane form; else the power form (rf_var_plan_backward_power): `weight_planes` hold exponents and the
 // gradient planes receive the gradient of the exponents.
+// with_bases (rf_var_plan_backward_power_bases; the power form): the weight-gradient route whatever grad_weight_planes holds (it
+// may be null), on the base-reducing var_grad instances, and one var_param_sum that stores dL/dbases[k] to grad_bases (device,
+// n_weights doubles); ms_out then has one slot per name of backward_bases_names.
 int run_var_backward(rf_var_plan *plan, const void *const *in_planes, const void *const *weight_planes, const float *bases,
                      const void *const *grad_out_planes, void *const *grad_in_planes, void *const *grad_weight_planes, hipStream_t stream,
-                     float *ms_out);
+                     float *ms_out, bool with_bases = false, double *grad_bases = nullptr);
 // The launches of one backward run of `plan`, nothing checked (run_var_backward and plan_smooth.cpp check first, and call
 // ensure_var_grad_planes where grad_weights is not null).  grad_weights: nullptr (3 launches per scan), or n_weights entries.
 // log2_base / ln_base: nullptr for the plane form, else per weight plane.  holds_sum: nullptr, or per weight plane whether its
@@ -101,9 +111,13 @@ struct VarBackwardIo {
     void *const *grad_in = nullptr, *const *grad_weights = nullptr;
     const float *log2_base = nullptr, *ln_base = nullptr;
     const bool *holds_sum = nullptr;
+    // not null (the power form, grad_weights not null): the var_grad launches are the base-reducing ones, scan q's slabs at
+    // slabs + plan->bases_slab_offset[q]; an entry of grad_weights may then be null (its launch still runs, nothing is stored)
+    double *slabs = nullptr;
     int64_t in_stride = 0, weights_stride = 0, grad_out_stride = 0, grad_in_stride = 0, grad_weights_stride = 0;      // a batched plan
 };
 int ensure_var_grad_planes(rf_var_plan *plan);
+int ensure_var_bases_slabs(rf_var_plan *plan);
 int launch_var_backward(rf_var_plan *plan, const VarBackwardIo &io, hipStream_t stream, LaunchTimer &timer);
 int64_t var_max_extent();      // extents above it are refused (RF_ERR_UNSUPPORTED)
 // The distances and their adjoints, one launch each (plan_var.cpp: one argument record, one runner per direction).  The image forms

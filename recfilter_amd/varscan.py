@@ -255,12 +255,61 @@ class VarPlan(_PlanHandle):
         n = self.backward_num_kernels(grad_exponents is not None and any(t is not None for t in grad_exponents))
         return grad_ins, grad_exponents, _timed(lambda *report: capi.lib().rf_var_plan_backward_power_timed(self._h, pin, pw, pb, pgo, pgi, pgw, s, *report), n)
 
+    # -- the gradient of the bases ---------------------------------------------------------------
+    def backward_bases_num_kernels(self) -> int:
+        """rf_var_plan_backward_bases_num_kernels: 7 launches per scan and one var_param_sum"""
+        return int(capi.lib().rf_var_plan_backward_bases_num_kernels(self._h))
+
+    def backward_bases_workspace_bytes(self) -> int:
+        """rf_var_plan_backward_bases_workspace_bytes: backward_workspace_bytes(True) and the f64 slabs, one entry per workgroup of
+        every var_grad launch"""
+        return int(capi.lib().rf_var_plan_backward_bases_workspace_bytes(self._h))
+
+    def _grad_bases(self, grad_bases, like):
+        """(the buffer dL/dbases goes to -- a float64 device tensor of n_weights entries -- and its address)"""
+        import torch
+        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
+            return None, ctypes.c_void_p()
+        if grad_bases is None:
+            grad_bases = torch.empty(self.n_weights, dtype=torch.float64, device=like.device)
+        if grad_bases.dtype != torch.float64 or tuple(grad_bases.shape) != (self.n_weights,) or not grad_bases.is_cuda or not grad_bases.is_contiguous():
+            raise ValueError(f"grad_bases must be a contiguous float64 device tensor of {self.n_weights} entries")
+        return grad_bases, ctypes.c_void_p(grad_bases.data_ptr())
+
+    def backward_power_bases(self, ins, exponents, bases, grad_outs, grad_ins=None, grad_exponents=None, grad_bases=None, stream=None):
+        """rf_var_plan_backward_power_bases: (grad_ins, grad_exponents, grad_bases).  backward_power on its weight-gradient route --
+        grad_exponents may be None or hold None entries, the planes that are given receive backward_power's bits -- and
+        grad_bases, a float64 DEVICE tensor of n_weights entries (None allocates it), receives dL/dbases[k]: a streaming f64
+        reduction without atomics, reproducible bit for bit.  Asynchronous: reading grad_bases on the host synchronises."""
+        pb = self._bases(bases)
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, s = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents, stream)
+        grad_bases, pgb = self._grad_bases(grad_bases, grad_ins[0] if grad_ins else None)
+        capi.check(capi.lib().rf_var_plan_backward_power_bases(self._h, pin, pw, pb, pgo, pgi, pgw, pgb, s))
+        return grad_ins, grad_exponents, grad_bases
+
+    def backward_power_bases_timed(self, ins, exponents, bases, grad_outs, grad_ins=None, grad_exponents=None, grad_bases=None, stream=None):
+        """rf_var_plan_backward_power_bases_timed: (grad_ins, grad_exponents, grad_bases, [(kernel name, ms), ...])"""
+        pb = self._bases(bases)
+        pin, pw, pgo, pgi, pgw, grad_ins, grad_exponents, s = self._backward_arguments(ins, exponents, grad_outs, grad_ins, grad_exponents, stream)
+        grad_bases, pgb = self._grad_bases(grad_bases, grad_ins[0] if grad_ins else None)
+        timings = _timed(lambda *report: capi.lib().rf_var_plan_backward_power_bases_timed(self._h, pin, pw, pb, pgo, pgi, pgw, pgb, s, *report),
+                         self.backward_bases_num_kernels())
+        return grad_ins, grad_exponents, grad_bases, timings
+
     def apply_power(self, ins, exponents, bases):
         """execute_power, out of place, as a differentiable torch operation: values bit for bit execute_power's.  Backward is
-        `backward_power` -- the image gradient always, the gradient of an exponent plane where that plane requires one.  The
-        bases are constants.  No double backward."""
+        `backward_power` -- the image gradient always, the gradient of an exponent plane where that plane requires one.  `bases`:
+        a list of floats, which are constants -- or a float tensor of n_weights entries (any device), which receives a gradient
+        where it requires one: backward is then `backward_power_bases`, and reading the tensor's values costs one host read per
+        call.  No double backward."""
+        import torch
         if len(ins) != self.planes or len(exponents) != self.n_weights:
             raise ValueError(f"expected {self.planes} input planes and {self.n_weights} exponent planes, got {len(ins)} and {len(exponents)}")
+        if isinstance(bases, torch.Tensor):
+            if not bases.is_floating_point() or bases.numel() != self.n_weights:
+                raise ValueError(f"bases must be a float tensor of {self.n_weights} entries, got {bases.dtype} {tuple(bases.shape)}")
+            values = [float(b) for b in bases.detach().reshape(-1).to(torch.float64).cpu().tolist()]
+            return _var_scan_function().apply((self, values), *ins, *exponents, bases)
         bases = [float(b) for b in bases]
         if len(bases) != self.n_weights:
             raise ValueError(f"expected {self.n_weights} bases, got {len(bases)}")
@@ -291,8 +340,11 @@ def _var_scan_function():
         def forward(ctx, plan_and_bases, *tensors):      # bases None: the plane form; else the power form
             plan, bases = plan_and_bases
             ins = [plane(t) for t in tensors[:plan.planes]]
-            weights = [plane(t) for t in tensors[plan.planes:]]
+            weights = [plane(t) for t in tensors[plan.planes:plan.planes + plan.n_weights]]
             ctx.plan, ctx.bases = plan, bases
+            # apply_power's bases tensor, where there is one: backward needs what its gradient looks like, not the tensor
+            t = tensors[plan.planes + plan.n_weights] if len(tensors) > plan.planes + plan.n_weights else None
+            ctx.bases_like = None if t is None else (t.shape, t.dtype, t.device)
             ctx.save_for_backward(*ins, *weights)
             return tuple(plan.execute(ins, weights) if bases is None else plan.execute_power(ins, weights, bases))
 
@@ -303,20 +355,28 @@ def _var_scan_function():
             saved = ctx.saved_tensors
             ins, weights = list(saved[:plan.planes]), list(saved[plan.planes:])
             need_in = ctx.needs_input_grad[1:1 + plan.planes]
-            need_w = ctx.needs_input_grad[1 + plan.planes:]
+            need_w = ctx.needs_input_grad[1 + plan.planes:1 + plan.planes + plan.n_weights]
+            need_bases = ctx.bases_like is not None and ctx.needs_input_grad[1 + plan.planes + plan.n_weights]
             read = {k for _, _, k in plan.scans}
             grad_weights = None
             if any(n and k in read for k, n in enumerate(need_w)):
                 grad_weights = [torch.empty_like(w) if n and k in read else None for k, (w, n) in enumerate(zip(weights, need_w))]
             with torch.cuda.device(ins[0].device):
+                grad_bases = None
                 if ctx.bases is None:
                     grad_ins, grad_weights = plan.backward(ins, weights, [plane(g) for g in grad_outs], None, grad_weights)
+                elif need_bases:
+                    grad_ins, grad_weights, grad_bases = plan.backward_power_bases(ins, weights, ctx.bases, [plane(g) for g in grad_outs], None, grad_weights)
                 else:
                     grad_ins, grad_weights = plan.backward_power(ins, weights, ctx.bases, [plane(g) for g in grad_outs], None, grad_weights)
             grad_weights = grad_weights or [None] * plan.n_weights
             # (a weight plane that no scan reads has a gradient of zero)
             grad_weights = [torch.zeros_like(w) if n and k not in read else g for k, (w, n, g) in enumerate(zip(weights, need_w, grad_weights))]
-            return (None, *[g if n else None for g, n in zip(grad_ins, need_in)], *grad_weights)
+            grads = (None, *[g if n else None for g, n in zip(grad_ins, need_in)], *grad_weights)
+            if ctx.bases_like is None:
+                return grads
+            shape, dtype, device = ctx.bases_like
+            return (*grads, grad_bases.to(device=device, dtype=dtype).reshape(shape) if need_bases else None)
 
     _function = VarScanFunction
     return _function
@@ -386,13 +446,15 @@ def var_scan_signal(ins, weights, scans):
     return tuple(o[:n] for o in outs) if pad else tuple(outs)
 
 
-def smooth_samples(x, gaps, time_constant: float, zero_phase: bool = True):
+def smooth_samples(x, gaps, time_constant, zero_phase: bool = True):
     """The exponential moving average of an irregularly sampled series: x (N,) or (C, N), f32 on the device, sampled at times t
     with gaps[i] = t[i] - t[i-1] >= 0 (gaps[0] is unused):
         y[i] = (1 - w[i]) x[i] + w[i] y[i-1],   w[i] = exp(-gaps[i] / time_constant)
     and, with zero_phase, the same recurrence backwards over the result (+x -x, one fused stage).  It runs through the power form
     of a cached `VarPlan.signal`: the weights are formed in the kernels as base ** gaps with base = exp(-1 / time_constant), and no
-    weight signal is stored.  Differentiable with respect to x and gaps.  A time constant whose base rounds to 0 or 1 in f32 is
+    weight signal is stored.  Differentiable with respect to x and gaps -- and with respect to the time constant where that is a
+    float tensor of one element (dL/dtau = dL/dbase * base / tau^2, dL/dbase from `VarPlan.backward_power_bases`; reading its value
+    costs one host read per call).  A time constant whose base rounds to 0 or 1 in f32 is
     refused by the library (RecFilterError).  Lengths that are not multiples of 4 are padded as in `var_scan_signal` (the gaps with
     +inf: a weight of exactly 0), at the cost of one copy."""
     import torch
@@ -401,11 +463,16 @@ def smooth_samples(x, gaps, time_constant: float, zero_phase: bool = True):
     signals = [x] if x.dim() == 1 else [x[c] for c in range(x.shape[0])]
     n = int(gaps.shape[0])
     pad = -n % 4
-    base = math.exp(-1.0 / float(time_constant))
+    if isinstance(time_constant, torch.Tensor):
+        if not time_constant.is_floating_point() or time_constant.numel() != 1:
+            raise ValueError("a tensor time_constant must be a float tensor of one element")
+        base = torch.exp(-1.0 / time_constant.reshape(1).to(torch.float64))      # (autograd: d base / d tau = base / tau^2)
+    else:
+        base = [math.exp(-1.0 / float(time_constant))]
     scans = [(0, True, 0), (0, False, 0)] if zero_phase else [(0, True, 0)]
     plan = _cached_plan(_signal_plans, VarPlan.signal, n + pad, scans, len(signals), 1, _device_index(x))
     with torch.cuda.device(x.device):
-        outs = plan.apply_power([_padded(t.to(torch.float32), pad, 0.0) for t in signals], [_padded(gaps.to(torch.float32), pad, math.inf)], [base])
+        outs = plan.apply_power([_padded(t.to(torch.float32), pad, 0.0) for t in signals], [_padded(gaps.to(torch.float32), pad, math.inf)], base)
     outs = [o[:n] for o in outs] if pad else list(outs)
     return outs[0] if x.dim() == 1 else torch.stack(outs)
 
@@ -637,6 +704,14 @@ class SmoothPlan(_PlanHandle):
         capi.check(capi.lib().rf_smooth_plan_bases(self._h, out))
         return [float(v) for v in out]
 
+    def set_sigmas(self, sigma_s: float, sigma_r: float) -> None:
+        """rf_smooth_plan_set_sigmas: new sigmas for this plan -- the scale of the distances and the bases are recomputed as create
+        computes them (`bases` afterwards is a fresh plan's, bit for bit), nothing is allocated, and every later execute and
+        backward runs with them.  Refused like create's sigmas, the plan left unchanged.  Works on host-only plans.  Order it
+        against the plan's executes as an execute is ordered."""
+        capi.check(capi.lib().rf_smooth_plan_set_sigmas(self._h, float(sigma_s), float(sigma_r)))
+        self._desc.sigma_s, self._desc.sigma_r = float(sigma_s), float(sigma_r)
+
     # -- execution --------------------------------------------------------------------------
     def _pointers(self, tensor, count: int, dtype, what: str) -> ctypes.Array:
         """the planes of a (C, H, W) or (H, W) device tensor, or of a list of (H, W) tensors; VarPlan._pointers' checks.
@@ -738,11 +813,52 @@ class SmoothPlan(_PlanHandle):
         return grad_image, grad_guide, _timed(lambda *report: capi.lib().rf_smooth_plan_backward_timed(self._h, pi, pg, pgo, pgi, pgg, int(edges), s, *report),
                                               self.backward_num_kernels(edges))
 
-    def apply(self, image, guide=None):
+    def backward_sigmas_num_kernels(self, edges: bool = False) -> int:
+        """rf_smooth_plan_backward_sigmas_num_kernels: backward_num_kernels(True), less the distances' adjoint without edges, and two"""
+        return int(capi.lib().rf_smooth_plan_backward_sigmas_num_kernels(self._h, int(bool(edges))))
+
+    def _grad_params(self, grad_params, like):
+        import torch
+        if self._desc.device == capi.RF_DEVICE_HOST_ONLY:
+            return None, ctypes.c_void_p()
+        n = 3 + self.iterations
+        if grad_params is None:
+            grad_params = torch.empty(n, dtype=torch.float64, device=like.device)
+        if grad_params.dtype != torch.float64 or tuple(grad_params.shape) != (n,) or not grad_params.is_cuda or not grad_params.is_contiguous():
+            raise ValueError(f"grad_params must be a contiguous float64 device tensor of {n} entries")
+        return grad_params, ctypes.c_void_p(grad_params.data_ptr())
+
+    def backward_sigmas(self, image, guide, grad_out, grad_image=None, grad_guide=None, edges: bool = False, grad_params=None, stream=None):
+        """rf_smooth_plan_backward_sigmas: (grad_image, grad_guide, grad_params).  `backward` with the same `edges` -- grad_image and
+        grad_guide are its bits -- and grad_params, a float64 DEVICE tensor of 3 + iterations entries (None allocates it):
+        dL/dsigma_s, dL/dsigma_r, dL/dspacing_z (0 on an image plan), dL/da_0 .. dL/da_{K-1}, summed over the batch.  `image` is
+        always needed; a uint8 guide is allowed without edges.  Asynchronous: reading grad_params on the host synchronises."""
+        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, s = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges, stream)
+        grad_params, pgp = self._grad_params(grad_params, grad_image if hasattr(grad_image, "device") else (grad_image[0] if grad_image else None))
+        capi.check(capi.lib().rf_smooth_plan_backward_sigmas(self._h, pi, pg, pgo, pgi, pgg, int(edges), pgp, s))
+        return grad_image, grad_guide, grad_params
+
+    def backward_sigmas_timed(self, image, guide, grad_out, grad_image=None, grad_guide=None, edges: bool = False, grad_params=None, stream=None):
+        """rf_smooth_plan_backward_sigmas_timed: (grad_image, grad_guide, grad_params, [(kernel name, ms), ...])"""
+        pi, pg, pgo, pgi, pgg, grad_image, grad_guide, s = self._backward_arguments(image, guide, grad_out, grad_image, grad_guide, edges, stream)
+        grad_params, pgp = self._grad_params(grad_params, grad_image if hasattr(grad_image, "device") else (grad_image[0] if grad_image else None))
+        timings = _timed(lambda *report: capi.lib().rf_smooth_plan_backward_sigmas_timed(self._h, pi, pg, pgo, pgi, pgg, int(edges), pgp, s, *report),
+                         self.backward_sigmas_num_kernels(edges))
+        return grad_image, grad_guide, grad_params, timings
+
+    def apply(self, image, guide=None, sigma_s=None, sigma_r=None):
         """execute, out of place, as a differentiable torch operation on f32 tensors (C, H, W) or (H, W) -- on a volume plan made
         with differentiable=True, (C, D, H, W) or (D, H, W): values bit for bit execute's.  Backward is `backward`; it goes through the distances (edges) where the guide requires a gradient, or the
-        image does and guides itself.  Only the image and the guide are saved; no double backward."""
-        return _smooth_function().apply(self, image, guide)
+        image does and guides itself.  Only the image and the guide are saved; no double backward.
+        sigma_s, sigma_r: None (the plan's sigmas, constants) -- or both given, floats or float tensors of one element: the
+        plan is given these sigmas (`set_sigmas`) before the forward AND again before the backward, so calls with different
+        sigmas may share one plan, and a tensor that requires a gradient receives one (backward is then `backward_sigmas`).
+        Reading a sigma tensor costs one host read per call."""
+        if (sigma_s is None) != (sigma_r is None):
+            raise ValueError("sigma_s and sigma_r: both or neither")
+        if sigma_s is None:
+            return _smooth_function().apply(self, image, guide)
+        return _smooth_function().apply(self, image, guide, sigma_s, sigma_r)
 
 
 _smooth_fn = None
@@ -756,12 +872,25 @@ def _smooth_function():
     import torch
     planes = _aligned_contiguous
 
+    def scalar(v):
+        """(the value, what a gradient for it looks like or None) of a sigma given as a float or as a tensor of one element"""
+        if isinstance(v, torch.Tensor):
+            if not v.is_floating_point() or v.numel() != 1:
+                raise ValueError("a tensor sigma must be a float tensor of one element")
+            return float(v.detach().to(torch.float64).cpu().item()), (v.shape, v.dtype, v.device)      # (the one host read)
+        return float(v), None
+
     class SmoothFunction(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, plan, image, guide):
+        def forward(ctx, plan, image, guide, sigma_s=None, sigma_r=None):
             image = planes(image)
             guide = planes(guide) if guide is not None else None
             ctx.plan = plan
+            ctx.sigmas = None
+            if sigma_s is not None:
+                (vs, like_s), (vr, like_r) = scalar(sigma_s), scalar(sigma_r)
+                ctx.sigmas = (vs, vr, like_s, like_r)
+                plan.set_sigmas(vs, vr)
             ctx.save_for_backward(image, *([guide] if guide is not None else []))
             with torch.cuda.device(image.device):
                 return plan.execute(image, guide)
@@ -774,9 +903,21 @@ def _smooth_function():
             guide = ctx.saved_tensors[1] if len(ctx.saved_tensors) > 1 else None
             need_image, need_guide = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
             edges = need_guide if guide is not None else need_image
+            if ctx.sigmas is None:
+                with torch.cuda.device(image.device):
+                    grad_image, grad_guide = plan.backward(image, guide, planes(grad_out), None, None, edges=bool(edges))
+                return None, grad_image if need_image else None, grad_guide if need_guide else None
+            vs, vr, like_s, like_r = ctx.sigmas
+            need_s, need_r = like_s is not None and ctx.needs_input_grad[3], like_r is not None and ctx.needs_input_grad[4]
+            plan.set_sigmas(vs, vr)      # (another call may have given the shared plan other sigmas since the forward)
             with torch.cuda.device(image.device):
-                grad_image, grad_guide = plan.backward(image, guide, planes(grad_out), None, None, edges=bool(edges))
-            return None, grad_image if need_image else None, grad_guide if need_guide else None
+                if need_s or need_r:
+                    grad_image, grad_guide, gp = plan.backward_sigmas(image, guide, planes(grad_out), None, None, edges=bool(edges))
+                else:
+                    grad_image, grad_guide = plan.backward(image, guide, planes(grad_out), None, None, edges=bool(edges))
+            like = lambda g, l: g.to(device=l[2], dtype=l[1]).reshape(l[0])      # noqa: E731
+            return (None, grad_image if need_image else None, grad_guide if need_guide else None,
+                    like(gp[0], like_s) if need_s else None, like(gp[1], like_r) if need_r else None)
 
     _smooth_fn = SmoothFunction
     return _smooth_fn
@@ -814,13 +955,20 @@ def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=F
             raise ValueError(f"guide and {what} must have the same " + ("batch size, " if batched else "") + extents)
     shape = tuple(int(s) for s in img.shape)      # (C, H, W), (N, C, H, W) or (C, D, H, W)
     device = _device_index(img)
-    wants_grad = bool(differentiable) and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad))
+    tensor_sigmas = isinstance(sigma_s, torch.Tensor) or isinstance(sigma_r, torch.Tensor)
+    if tensor_sigmas and not differentiable:
+        raise TypeError("tensor sigmas are taken with differentiable=True")
+    wants_grad = bool(differentiable) and torch.is_grad_enabled() and (img.requires_grad or (g is not None and g.requires_grad) or
+                                                                      any(isinstance(v, torch.Tensor) and v.requires_grad for v in (sigma_s, sigma_r)))
     if wants_grad and (img.dtype != torch.float32 or (g is not None and g.dtype != torch.float32 and g.requires_grad)):
         raise TypeError("differentiable=True takes f32 images, and f32 guides where the guide requires a gradient")
     n_guide = 0 if g is None else int(g.shape[at])
+    # tensor sigmas: one plan for every value (the key leaves them out; SmoothPlan.apply sets them before forward and backward), at
+    # the cost of one host read per sigma tensor and call
+    first_s, first_r = (float(v.detach().cpu()) if isinstance(v, torch.Tensor) else float(v) for v in (sigma_s, sigma_r))
     common = dict(planes=shape[at], guide_planes=n_guide, image_dtype=img.dtype, guide_dtype=None if g is None else g.dtype, iterations=iterations,
-                  sigma_s=sigma_s, sigma_r=sigma_r, device=device)
-    key = shape + (img.dtype, None if g is None else (n_guide, g.dtype), int(iterations), float(sigma_s), float(sigma_r))
+                  sigma_s=first_s, sigma_r=first_r, device=device)
+    key = shape + (img.dtype, None if g is None else (n_guide, g.dtype), int(iterations)) + (("tensor sigmas",) if tensor_sigmas else (first_s, first_r))
     if nd == 2:
         cache, key = _smooth_plan_objects, key + (device,)
     else:      # (a plan with a backward is built only where one is needed: the default call keeps the plans it had)
@@ -830,7 +978,11 @@ def _smooth_by_plan(image, guide, sigma_s, sigma_r, iterations, differentiable=F
         plan = cache[key] = SmoothPlan(shape[-2:], batch=shape[0] if batched else None, **common)
     elif plan is None:
         plan = cache[key] = SmoothPlan.volume(shape[1:], spacing_z=spacing_z, differentiable=wants_grad, **common)
-    if wants_grad:
+    if tensor_sigmas:
+        if img.dtype != torch.float32:
+            raise TypeError("tensor sigmas take f32 images")
+        out = plan.apply(img, g, sigma_s, sigma_r)      # (also without a gradient: the shared plan needs this call's sigmas)
+    elif wants_grad:
         out = plan.apply(img, g)
     else:
         with torch.cuda.device(img.device):
@@ -851,7 +1003,9 @@ def edge_aware_smooth_volume(volume, guide=None, sigma_s: float = 60.0, sigma_r:
     torch's grad mode on and a volume or a guide that requires a gradient: the call goes through `SmoothPlan.apply` on a cached
     `SmoothPlan.volume(..., differentiable=True)` -- same values, bit for bit; f32 volumes, and an f32 guide where the guide requires
     a gradient (TypeError otherwise); gradients with respect to the volume and the guide, all of it in the library, through the
-    distances where the guide, or a self-guiding volume, requires one.  No gradient of the sigmas or spacing_z; no double backward."""
+    distances where the guide, or a self-guiding volume, requires one.  sigma_s and sigma_r may then be float tensors of one element,
+    which receive gradients (one cached plan for every value; reading a sigma tensor costs one host read per call).  No gradient of
+    spacing_z here; no double backward."""
     return _smooth_by_plan(volume, guide, sigma_s, sigma_r, iterations, differentiable, nd=3, spacing_z=spacing_z)
 
 
@@ -876,7 +1030,9 @@ def edge_aware_smooth(image, guide=None, sigma_s: float = 60.0, sigma_r: float =
     bit for bit): f32 images, gradients with respect to the image and an f32 guide, all of it in the library (through the
     distances where the guide, or a self-guiding image, requires a gradient).  Without the flag form="plan" carries no grad_fn
     whatever the inputs require, and form="power" never does: differentiable=True with form="power" raises ValueError (use
-    "plan"); with form="planes" the flag changes nothing."""
+    "plan"); with form="planes" the flag changes nothing.  With form="plan" and differentiable=True, sigma_s and sigma_r may be float
+    tensors of one element: they receive gradients (`SmoothPlan.backward_sigmas`), the plan cache key leaves the sigmas out, and
+    reading a sigma tensor costs one host read per call.  Float sigmas take exactly the path they took."""
     import torch
     if form not in ("planes", "power", "plan"):
         raise ValueError(f"form must be 'planes', 'power' or 'plan', got {form!r}")
