@@ -1114,3 +1114,51 @@ public:
      *  filter without it: 0 */
     int gradient_num_kernels(bool edges) { prepare(); return rf_smooth_plan_backward_num_kernels(plan, edges ? 1 : 0); }
 };
+
+/** One time-varying second-order all-pole scan on dense f32 device signals (recfilter_amd.h, rf_var2_plan_*):
+ *      y[n] = x[n] - a1[n] y[n-1] - a2[n] y[n-2]            (-x: y[n+1], y[n+2])
+ *  with coefficient signals as long as the input; a coefficient that would multiply a sample outside the line is never used.
+ *      RecFilterDim x("x", length);             // a multiple of 4, up to 2^30
+ *      RecFilterVarying2 F(+x);                 // or -x; F(+x, lines, stride): `lines` signals `stride` samples apart
+ *      F.realize(in, a1, a2, out);              // device pointers; in == out is allowed
+ *      F.gradient(a1, a2, out, grad_out, grad_in, grad_a1, grad_a2);      // the adjoint; grad_a1 = grad_a2 = nullptr: grad_in only
+ *  The plan is built on the first call and kept; it owns one workspace: order the calls of one object.  Zero-phase filtering is
+ *  two objects, +x then -x.  Refusals arrive as RecFilterError with the library's text. */
+class RecFilterVarying2 {
+    rf_var2_signal_desc desc{};
+    rf_var2_plan *plan = nullptr;
+    void prepare() {
+        if (!plan && rf_var2_plan_create_signal(&desc, &plan) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+public:
+    explicit RecFilterVarying2(const RecFilterDimAndCausality &x, int lines = 1, int64_t stride = 0) {
+        desc.abi = RF_ABI;
+        desc.length = x.num_pixels();
+        desc.n_lines = lines;
+        desc.stride = stride > 0 ? stride : desc.length;
+        desc.causal = x.causal() ? 1 : 0;
+        desc.device = -1;
+        desc.flags = 0;
+    }
+    RecFilterVarying2(const RecFilterVarying2 &) = delete;
+    RecFilterVarying2 &operator=(const RecFilterVarying2 &) = delete;
+    ~RecFilterVarying2() { if (plan) rf_var2_plan_destroy(plan); }
+    /** 3 */
+    int num_kernels() { prepare(); return rf_var2_plan_num_kernels(plan); }
+    /** 3, or 4 with coefficient gradients */
+    int gradient_num_kernels(bool with_coefficients) { prepare(); return rf_var2_plan_backward_num_kernels(plan, with_coefficients ? 1 : 0); }
+    size_t workspace_bytes() { prepare(); return rf_var2_plan_workspace_bytes(plan); }
+    /** Asynchronous on `stream`. */
+    void realize(const void *in, const void *a1, const void *a2, void *out, void *stream = nullptr) {
+        prepare();
+        if (rf_var2_plan_execute(plan, in, a1, a2, out, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize() (rf_var2_plan_backward): grad_in = dL/d(in) from grad_out = dL/d(out); `out` is realize()'s result.
+     *  grad_a1 and grad_a2: both null (no coefficient gradients; `out` may then be null) or both signals to be written.
+     *  grad_in == grad_out is allowed. */
+    void gradient(const void *a1, const void *a2, const void *out, const void *grad_out, void *grad_in, void *grad_a1 = nullptr,
+                  void *grad_a2 = nullptr, void *stream = nullptr) {
+        prepare();
+        if (rf_var2_plan_backward(plan, a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+};

@@ -655,7 +655,8 @@ size_t rf_var_plan_backward_bases_workspace_bytes(const rf_var_plan *plan);
  * refuses to run with RF_ERR_HIP.
  * Out of scope: lengths that are not multiples of 4 (pad with zero samples and zero weights: a weight of 0 decouples exactly);
  * batches of long signals with weights of their own (many short lines are the x scans of a 2-D plan); byte and 16-bit signals;
- * rf_smooth_plan and rf_var_distances on signals (their extent limit of 2^21 stays); orders above 1; sharding. */
+ * rf_smooth_plan and rf_var_distances on signals (their extent limit of 2^21 stays); orders above 1 (order 2: rf_var2_plan_*
+ * below); sharding. */
 typedef struct {
     uint32_t abi;                     /* RF_ABI                                                  */
     int64_t  length;                  /* samples per signal: a multiple of 4, 4 .. 2^30          */
@@ -959,6 +960,68 @@ typedef struct {
     uint32_t flags;                   /* 0, or RF_SMOOTH_VOLUME_BACKWARD                         */
 } rf_smooth_volume_desc;
 int    rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth_plan **plan_out);
+
+/* ---- time-varying second-order all-pole scans on signals ("var2") ---------------------------
+ * One scan per plan on n_lines dense f32 signals of `length` samples, line l beginning l * stride samples behind the pointer of
+ * a call.  Every line has coefficient signals a1 and a2 of its own, laid out like the input:
+ *     causal      y[n] = x[n] - a1~[n] y[n-1] - a2~[n] y[n-2]        y[-1] = y[-2] = 0
+ *     anticausal  y[n] = x[n] - a1~[n] y[n+1] - a2~[n] y[n+2]        y[N] = y[N+1] = 0
+ * The anticausal scan is the causal one on the three signals reversed.  a~ is a with every coefficient that would multiply a
+ * sample outside the line replaced by 0 through a select: a1[0], a2[0], a2[1] of a causal scan, a1[N-1], a2[N-1], a2[N-2] of an
+ * anticausal one -- a NaN stored there reaches no output.  Nothing restricts the coefficients: an unstable filter is the
+ * caller's business, NaN propagates.  A resonator whose centre frequency and bandwidth move, an LPC synthesis filter, a swept
+ * biquad's feedback half; zero-phase filtering is two plans, causal then anticausal, composed by the caller.
+ * in == out is allowed; no other overlap of out with in, and none with a coefficient signal; all pointers 16-byte aligned.
+ * Tiling (kernels_var2_signal.hip): the state is the 2-vector (y[n], y[n-1]); a lane owns 64 consecutive samples, a wave a group
+ * of 64 such tiles (4096 samples).  Three launches: "var2_tails_1d" (per tile the state it leaves from zero entry and the 2 x 2
+ * matrix that carries an entering state across it, then a scan of these across the wave: every lane stores the map from the
+ * state that enters its group to the state that enters its tile, one lane the group's aggregate), "var2_carry_1d" (the
+ * recurrence over groups, one workgroup per line sweeping 1024 groups at a time) and "var2_pass2_1d" (reruns the recurrence
+ * from the entering state and stores: coefficients of exactly 0 give out == in bit for bit).  No kernel waits on another
+ * workgroup, there are no atomics, and a result is reproducible bit for bit.  rf_var2_plan_num_kernels = 3.
+ * rf_var2_plan_workspace_bytes is exact: 4 * n_lines * (6 * (tiles + groups) + 2 * groups) bytes, tiles = ceil(length / 64),
+ * groups = ceil(tiles / 64).
+ * The adjoint: rf_var2_plan_backward takes the coefficients, `out` = the forward's result and grad_out = dL/d(out), and stores
+ * grad_in = dL/d(in) = lam, for a causal plan
+ *     lam[n] = grad_out[n] - a1~[n+1] lam[n+1] - a2~[n+2] lam[n+2]
+ * (the mirror image for an anticausal one), in three launches "var2_adj_tails_1d", "var2_carry_1d", "var2_adj_pass2_1d" on the
+ * plan's workspace.  grad_a1 and grad_a2 both given: a fourth launch "var2_grad_1d" stores
+ *     grad_a1[n] = -lam[n] y[n-1]    grad_a2[n] = -lam[n] y[n-2]          (anticausal: y[n+1], y[n+2])
+ * with 0 at the masked entries.  Both null: no coefficient gradients, and `out` may be null.  One null and one not is refused.
+ * grad_in == grad_out is allowed; a gradient that is written overlaps nothing else.  rf_var2_plan_backward_num_kernels = 3
+ * without and 4 with coefficient gradients.  A plan keeps no state across calls; order the calls of one plan (one workspace).
+ * Create refuses, in this order and before any HIP call: null arguments, abi != RF_ABI, nonzero flags, length < 1, n_lines
+ * outside 1..65535, a stride below the length, not a multiple of 4 or above 2^40 (RF_ERR_INVALID_ARG); a length that is not a
+ * multiple of 4, then one above 2^30 (RF_ERR_UNSUPPORTED).  A call refuses, in this order and before any HIP call: a null plan;
+ * backward: exactly one of grad_a1, grad_a2 null; a null pointer; a pointer that is not 16-byte aligned; an overlap named above
+ * (RF_ERR_INVALID_ARG); then a host-only plan (RF_ERR_HIP).  A *_timed call checks ms_out's capacity first.  A host-only plan
+ * (device = RF_DEVICE_HOST_ONLY) answers the queries and checks the arguments of a call, which it never dereferences.
+ * Out of scope: orders above 2; time-varying feed-forward taps; images and volumes; lists of scans inside one plan; 16-bit
+ * signals; second derivatives; sharding; lengths that are not multiples of 4 (pad the three signals with zeros behind the end
+ * of a causal scan, before the start of an anticausal one: the real samples are what an unpadded scan gives). */
+typedef struct rf_var2_plan rf_var2_plan;
+typedef struct {
+    uint32_t abi;                     /* RF_ABI                                                  */
+    int64_t  length;                  /* samples per line: a multiple of 4, 4 .. 2^30            */
+    int32_t  n_lines;                 /* 1..65535                                                */
+    int64_t  stride;                  /* samples from line to line: a multiple of 4, >= length   */
+    int32_t  causal;                  /* nonzero: causal; 0: anticausal                          */
+    int32_t  device;                  /* HIP device ordinal, -1 = current, RF_DEVICE_HOST_ONLY   */
+    uint32_t flags;                   /* 0                                                       */
+} rf_var2_signal_desc;
+int    rf_var2_plan_create_signal(const rf_var2_signal_desc *desc, rf_var2_plan **plan_out);
+int    rf_var2_plan_destroy(rf_var2_plan *plan);
+size_t rf_var2_plan_workspace_bytes(const rf_var2_plan *plan);
+int    rf_var2_plan_num_kernels(const rf_var2_plan *plan);
+int    rf_var2_plan_execute(rf_var2_plan *plan, const void *in, const void *a1, const void *a2, void *out, void *stream);
+int    rf_var2_plan_execute_timed(rf_var2_plan *plan, const void *in, const void *a1, const void *a2, void *out, void *stream,
+                                  float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_backward(rf_var2_plan *plan, const void *a1, const void *a2, const void *out, const void *grad_out, void *grad_in,
+                             void *grad_a1, void *grad_a2, void *stream);
+int    rf_var2_plan_backward_timed(rf_var2_plan *plan, const void *a1, const void *a2, const void *out, const void *grad_out,
+                                   void *grad_in, void *grad_a1, void *grad_a2, void *stream, float *ms_out, const char **names_out,
+                                   int capacity);
+int    rf_var2_plan_backward_num_kernels(const rf_var2_plan *plan, int with_coefficient_gradients);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

@@ -82,6 +82,9 @@ EXPORTED_SYMBOLS = [
     "rf_var_plan_backward_power_bases", "rf_var_plan_backward_power_bases_timed", "rf_var_plan_backward_bases_num_kernels",
     "rf_var_plan_backward_bases_workspace_bytes", "rf_smooth_plan_set_sigmas",
     "rf_smooth_plan_backward_sigmas", "rf_smooth_plan_backward_sigmas_timed", "rf_smooth_plan_backward_sigmas_num_kernels",
+    "rf_var2_plan_create_signal", "rf_var2_plan_destroy", "rf_var2_plan_workspace_bytes", "rf_var2_plan_num_kernels",
+    "rf_var2_plan_execute", "rf_var2_plan_execute_timed", "rf_var2_plan_backward", "rf_var2_plan_backward_timed",
+    "rf_var2_plan_backward_num_kernels",
 ]
 
 
@@ -131,6 +134,11 @@ class VarVolumeDesc(ctypes.Structure):
     _fields_ = [("abi", ctypes.c_uint32), ("width", ctypes.c_int64), ("height", ctypes.c_int64), ("depth", ctypes.c_int64),
                 ("dtype", ctypes.c_int32), ("n_planes", ctypes.c_int32), ("n_weights", ctypes.c_int32), ("n_scans", ctypes.c_int32),
                 ("scans", ctypes.POINTER(VarScanDesc)), ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class Var2SignalDesc(ctypes.Structure):
+    _fields_ = [("abi", ctypes.c_uint32), ("length", ctypes.c_int64), ("n_lines", ctypes.c_int32), ("stride", ctypes.c_int64),
+                ("causal", ctypes.c_int32), ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class SmoothDesc(ctypes.Structure):
@@ -277,6 +285,16 @@ def lib() -> ctypes.CDLL:
     L.rf_smooth_plan_backward_sigmas_num_kernels.argtypes = [vp, ctypes.c_int]
     L.rf_smooth_plan_backward_workspace_bytes.argtypes = [vp, ctypes.c_int]
     L.rf_smooth_plan_backward_workspace_bytes.restype = ctypes.c_size_t
+    L.rf_var2_plan_create_signal.argtypes = [ctypes.POINTER(Var2SignalDesc), vpp]
+    L.rf_var2_plan_destroy.argtypes = [vp]
+    L.rf_var2_plan_workspace_bytes.argtypes = [vp]
+    L.rf_var2_plan_workspace_bytes.restype = ctypes.c_size_t
+    L.rf_var2_plan_num_kernels.argtypes = [vp]
+    L.rf_var2_plan_execute.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rf_var2_plan_execute_timed.argtypes = [vp, vp, vp, vp, vp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var2_plan_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rf_var2_plan_backward_timed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var2_plan_backward_num_kernels.argtypes = [vp, ctypes.c_int]
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

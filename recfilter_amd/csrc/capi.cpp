@@ -10,6 +10,7 @@
 #include "plan_adjoint.h"
 #include "plan_smooth.h"
 #include "plan_var.h"
+#include "plan_var2.h"
 #include "run_support.h"
 
 namespace rf {
@@ -686,6 +687,57 @@ int rf_var_plan_backward_num_kernels(const rf_var_plan *plan, int with_weight_gr
 
 size_t rf_var_plan_backward_workspace_bytes(const rf_var_plan *plan, int with_weight_gradients) {
     return plan ? plan->backward_workspace_bytes(with_weight_gradients != 0) : 0;
+}
+
+// ---- time-varying second-order all-pole scans on signals (plan_var2.cpp) ----------------------------------------------------
+int rf_var2_plan_create_signal(const rf_var2_signal_desc *desc, rf_var2_plan **plan_out) {
+    return fenced("rf_var2_plan_create_signal", [&] { return build_var2_signal_plan(desc, plan_out); });
+}
+
+int rf_var2_plan_destroy(rf_var2_plan *plan) {
+    return fenced("rf_var2_plan_destroy", [&] {
+        if (plan) {
+            if (!plan->host_only) (void)hipSetDevice(plan->device);
+            delete plan;
+        }
+        return (int)RF_OK;
+    });
+}
+
+size_t rf_var2_plan_workspace_bytes(const rf_var2_plan *plan) { return plan ? plan->workspace_bytes() : 0; }
+int rf_var2_plan_num_kernels(const rf_var2_plan *plan) { return plan ? (int)plan->names.size() : 0; }
+
+int rf_var2_plan_backward_num_kernels(const rf_var2_plan *plan, int with_coefficient_gradients) {
+    return plan ? (int)plan->backward_names[with_coefficient_gradients ? 1 : 0].size() : 0;
+}
+
+int rf_var2_plan_execute(rf_var2_plan *plan, const void *in, const void *a1, const void *a2, void *out, void *stream) {
+    return fenced("rf_var2_plan_execute", [&] { return run_var2_plan(plan, in, a1, a2, out, (hipStream_t)stream, nullptr); });
+}
+
+int rf_var2_plan_execute_timed(rf_var2_plan *plan, const void *in, const void *a1, const void *a2, void *out, void *stream, float *ms_out,
+                               const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_execute_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (int rc = timed_names(plan->names, ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var2_plan(plan, in, a1, a2, out, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var2_plan_backward(rf_var2_plan *plan, const void *a1, const void *a2, const void *out, const void *grad_out, void *grad_in,
+                          void *grad_a1, void *grad_a2, void *stream) {
+    return fenced("rf_var2_plan_backward", [&] {
+        return run_var2_backward(plan, a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var2_plan_backward_timed(rf_var2_plan *plan, const void *a1, const void *a2, const void *out, const void *grad_out, void *grad_in,
+                                void *grad_a1, void *grad_a2, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_backward_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (int rc = timed_names(plan->backward_names[grad_a1 || grad_a2 ? 1 : 0], ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var2_backward(plan, a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, (hipStream_t)stream, ms_out);
+    });
 }
 
 int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,

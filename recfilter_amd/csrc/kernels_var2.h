@@ -1,0 +1,59 @@
+// kernels_var2.h -- launchers of the time-varying second-order all-pole scans on 1-D signals (kernels_var2_signal.hip;
+// plan_var2.cpp drives them).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "rf_internal.h"
+
+namespace rf {
+
+// tail slots per tile (and per group): E = (e0, e1), the state after the tile from zero entry, and the 2 x 2 matrix P that
+// carries the entering state across it
+constexpr int kVar2Components = 6;
+enum Var2Component { VAR2_E0 = 0, VAR2_E1 = 1, VAR2_P00 = 2, VAR2_P01 = 3, VAR2_P10 = 4, VAR2_P11 = 5 };
+
+// One scan on all lines.  Line l of every signal begins l * stride samples behind the pointer.  tiles = ceil(n / 64), groups =
+// ceil(tiles / 64).
+//   tails   [component][line][tile]     the lanes' maps: what enters tile t = E + P * (what enters its group)
+//           [component][line][group]    behind them, the groups' aggregates
+//   carry   [2][line][group]            the state that enters group g
+// causal: the direction of THIS recurrence (an adjoint stage runs against its forward).  adjoint: the coefficients are read
+// shifted by one (a1) and two (a2) samples against the direction of the recurrence -- lam[n] couples to lam[n+1] through a1[n+1].
+struct Var2Args {
+    const float *x;
+    const float *a1, *a2;
+    float *dst;
+    float *tails;
+    float *carry;
+    int32_t n;                      // samples per line: a multiple of 4
+    int32_t tiles, groups;
+    int32_t n_lines;
+    int32_t causal;
+    int32_t adjoint;
+    int64_t stride;
+};
+
+// The coefficient gradients of one scan (var2_grad_1d): lam = its adjoint state, y = its output.
+//   causal      grad_a1[n] = -lam[n] y[n-1]   grad_a2[n] = -lam[n] y[n-2]
+//   anticausal  grad_a1[n] = -lam[n] y[n+1]   grad_a2[n] = -lam[n] y[n+2]
+// and 0, by a select, where the neighbour lies outside the line.
+struct Var2GradArgs {
+    const float *lam, *y;
+    float *grad_a1, *grad_a2;
+    int32_t n;
+    int32_t n_lines;
+    int32_t causal;                 // the direction of the FORWARD scan
+    int64_t stride;
+};
+
+constexpr int kVar2Tile = 64;            // samples of a tile: one lane
+constexpr int kVar2GroupTiles = 64;      // tiles of a group: one wave
+int launch_var2_tails(const Var2Args &a, hipStream_t stream);      // "var2_tails_1d", "var2_adj_tails_1d"
+int launch_var2_carry(const Var2Args &a, hipStream_t stream);      // "var2_carry_1d"
+int launch_var2_pass2(const Var2Args &a, hipStream_t stream);      // "var2_pass2_1d", "var2_adj_pass2_1d"
+int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream);   // "var2_grad_1d"
+
+}  // namespace rf

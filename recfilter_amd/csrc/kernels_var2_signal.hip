@@ -1,0 +1,360 @@
+// kernels_var2_signal.hip -- time-varying second-order all-pole scans on dense f32 signals (rf_var2_plan_*):
+//   causal      y[n] = x[n] - a1~[n] y[n-1] - a2~[n] y[n-2]          anticausal: the same on the three signals reversed
+// with a coefficient that would multiply a sample outside the line selected to 0 (a~).  N a multiple of 4 up to 2^30; every line
+// has its own coefficient signals; lines ride on gridDim.y.
+//
+// The tiling is kernels_var_signal.hip's with a 2-vector where that file has a scalar.  The state behind sample n is
+// s[n] = (y[n], y[n-1]),  s[n] = M[n] s[n-1] + (x[n], 0),  M[n] = [[-a1~[n], -a2~[n]], [1, 0]].  A lane owns a TILE of 64
+// consecutive samples and forms six numbers: E, the state behind the tile from zero entry, and P = M[t1-1] ... M[t0], from two more
+// recurrences started at (1, 0) and (0, 1) in the same sweep.  For a sub-line A followed by B
+//   E = E_B + P_B E_A          P = P_B P_A                    identity (0, I)
+// A workgroup of one wave owns a GROUP of 64 tiles, 4096 contiguous samples.
+//
+//   var2_tails_1d   tile tails per lane, then a Kogge-Stone scan of (E, P) across the 64 lanes with __shfl_up (an anticausal scan:
+//                   __shfl_down, the lanes taken from the right).  A lane stores the map from the state that enters its group to the
+//                   state that enters its tile, one lane the group's aggregate.
+//   var2_carry_1d   the recurrence over GROUPS: one workgroup per line, up to 1024 lanes, sweeping the groups 1024 at a time in the
+//                   order of the recurrence -- a wave scan, the waves' totals folded through LDS, the running 2-vector kept in
+//                   registers between sweeps.
+//   var2_pass2_1d   reloads the group, forms the state that enters each tile from the stored map and the group's carry, RERUNS the
+//                   recurrence from it and stores.  Nothing is superposed: coefficients of exactly 0 give out == in.
+// No kernel waits on another workgroup, there are no atomics, every sum has a fixed order: results are reproducible bit for bit.
+//
+// The loads are var_tails_1d's -- a wave instruction moves 1024 contiguous bytes, the chunks go through LDS to the lanes' tiles
+// (transpose_in, var_device.h) -- for three signals.  request_tile of that header clamps rows and columns of a 2-D plane apart: on a
+// line whose length is no multiple of 64 it would read past the end, so the request here clamps the flat address.  Samples past
+// the end come from a clamped address inside the line and are selected away (input 0, coefficients 0): such a sample leaves the
+// state (0, 0) behind it after two steps and passes nothing on.  A workgroup has loaded its whole group before it stores: in == out
+// is legal.
+//
+// The adjoint of a causal scan is  lam[n] = g[n] - a1~[n+1] lam[n+1] - a2~[n+2] lam[n+2]:  an anticausal scan whose coefficients are
+// read one (a1) and two (a2) samples further on.  The ADJ instances form them from the tile's own coefficients and the first three
+// of the neighbouring tile (a1[t1], a2[t1], a2[t1+1]; the 65th weight of the first-order kernels), loaded from clamped addresses;
+// the masks by position are those of the scan's own direction.  The adjoint of an anticausal scan is the mirror image.
+#include "kernels_var2.h"
+
+#include "var_device.h"
+
+#include <algorithm>
+
+namespace rf {
+
+namespace {
+
+static_assert(kVar2Tile == T, "the tile of var_device.h");
+constexpr int kGroupTiles = kVar2GroupTiles;       // tiles of a group: one per lane
+constexpr int kGroupSamples = kGroupTiles * T;     // 4096
+constexpr int kCarryLanes = 1024;                  // groups of a sweep of var2_carry_1d
+constexpr int kGradLanes = 256;                    // lanes of a workgroup of var2_grad_1d, four samples each
+
+__device__ __forceinline__ int64_t map_index(const Var2Args &a, int comp, int line, int t) { return ((int64_t)comp * a.n_lines + line) * a.tiles + t; }
+__device__ __forceinline__ int64_t aggregate_index(const Var2Args &a, int comp, int line, int g) {
+    return (int64_t)kVar2Components * a.n_lines * a.tiles + ((int64_t)comp * a.n_lines + line) * a.groups + g;
+}
+__device__ __forceinline__ int64_t group_carry_index(const Var2Args &a, int comp, int line, int g) { return ((int64_t)comp * a.n_lines + line) * a.groups + g; }
+
+// one step of the recurrence: the new y from the two before it
+__device__ __forceinline__ float step2(float c1, float c2, float x, float y1, float y2) { return __builtin_fmaf(-c1, y1, __builtin_fmaf(-c2, y2, x)); }
+
+// sub-line A followed by B
+__device__ __forceinline__ void compose(const float (&A)[kVar2Components], const float (&B)[kVar2Components], float (&r)[kVar2Components]) {
+    r[VAR2_E0] = __builtin_fmaf(B[VAR2_P00], A[VAR2_E0], __builtin_fmaf(B[VAR2_P01], A[VAR2_E1], B[VAR2_E0]));
+    r[VAR2_E1] = __builtin_fmaf(B[VAR2_P10], A[VAR2_E0], __builtin_fmaf(B[VAR2_P11], A[VAR2_E1], B[VAR2_E1]));
+    r[VAR2_P00] = __builtin_fmaf(B[VAR2_P00], A[VAR2_P00], B[VAR2_P01] * A[VAR2_P10]);
+    r[VAR2_P01] = __builtin_fmaf(B[VAR2_P00], A[VAR2_P01], B[VAR2_P01] * A[VAR2_P11]);
+    r[VAR2_P10] = __builtin_fmaf(B[VAR2_P10], A[VAR2_P00], B[VAR2_P11] * A[VAR2_P10]);
+    r[VAR2_P11] = __builtin_fmaf(B[VAR2_P10], A[VAR2_P01], B[VAR2_P11] * A[VAR2_P11]);
+}
+
+__device__ __forceinline__ void identity(float (&r)[kVar2Components]) {
+    r[VAR2_E0] = 0.0f; r[VAR2_E1] = 0.0f; r[VAR2_P00] = 1.0f; r[VAR2_P01] = 0.0f; r[VAR2_P10] = 0.0f; r[VAR2_P11] = 1.0f;
+}
+
+// the map m applied to the state (s0, s1)
+__device__ __forceinline__ void apply_map(const float (&m)[kVar2Components], float s0, float s1, float &r0, float &r1) {
+    r0 = __builtin_fmaf(m[VAR2_P00], s0, __builtin_fmaf(m[VAR2_P01], s1, m[VAR2_E0]));
+    r1 = __builtin_fmaf(m[VAR2_P10], s0, __builtin_fmaf(m[VAR2_P11], s1, m[VAR2_E1]));
+}
+
+// the value of the lane k places earlier in the order of the recurrence
+template <bool REV>
+__device__ __forceinline__ float from_before(float v, int k) { return REV ? __shfl_down(v, k) : __shfl_up(v, k); }
+
+// From a lane's tile tails to its map and the group's aggregate.  pos: the lane's place in the order of the recurrence.
+//   map: the inclusive scan of the lane before (the identity at place 0);   whole: valid at place 63
+template <bool REV>
+__device__ __forceinline__ void scan_group(const float (&own)[kVar2Components], float (&map)[kVar2Components], float (&whole)[kVar2Components]) {
+    const int lane = threadIdx.x, pos = REV ? 63 - lane : lane;
+    float other[kVar2Components], next[kVar2Components];
+#pragma unroll
+    for (int i = 0; i < kVar2Components; i++) whole[i] = own[i];
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) other[i] = from_before<REV>(whole[i], k);
+        compose(other, whole, next);
+        if (pos >= k) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) whole[i] = next[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kVar2Components; i++) other[i] = from_before<REV>(whole[i], 1);
+    identity(map);
+    if (pos > 0) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) map[i] = other[i];
+    }
+}
+
+// request k of a lane: the 16-byte chunk k * 64 + lane of the group, from a flat address clamped into the line
+__device__ __forceinline__ void request_group(const float *signal, int n, int s0, float (&v)[T]) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < T / 4; k++) {
+        const int at = min(s0 + (k * 64 + lane) * 4, n - 4);      // (n is a multiple of 4, at least 4)
+        const float4 q = *reinterpret_cast<const float4 *>(signal + at);
+        v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+    }
+}
+
+// the lanes' tiles back through LDS to the group's chunks; a chunk is inside the line or beyond it (n is a multiple of 4)
+__device__ __forceinline__ void store_group(float *lds, float *signal, int n, int s0, const float (&y)[T]) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < T / 4; k++)
+        *reinterpret_cast<float4 *>(lds + lane * LDS_PITCH + k * 4) = make_float4(y[4 * k], y[4 * k + 1], y[4 * k + 2], y[4 * k + 3]);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < T / 4; k++) {
+        const int flat = k * 64 + lane;
+        const int at = s0 + flat * 4;
+        const float4 q = *reinterpret_cast<const float4 *>(lds + (flat >> 4) * LDS_PITCH + (flat & 15) * 4);
+        if (at < n) *reinterpret_cast<float4 *>(signal + at) = q;
+    }
+}
+
+// REV: the recurrence runs from the line's end to its start.  ADJ: the shifted coefficients of an adjoint stage.
+template <bool REV, bool ADJ, bool FINAL>
+__global__ void __launch_bounds__(64) var2_signal_kernel(Var2Args a) {
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x, line = blockIdx.y;
+    const int n = a.n;
+    const int s0 = g * kGroupSamples;                 // below 2^30 + 4096
+    const int t = g * kGroupTiles + lane, t0 = t * T;
+    const int64_t first = (int64_t)line * a.stride;
+    const float *px = a.x + first, *p1 = a.a1 + first, *p2 = a.a2 + first;
+    float vx[T], v1[T], v2[T];
+    request_group(px, n, s0, vx);
+    request_group(p1, n, s0, v1);
+    request_group(p2, n, s0, v2);
+    // an adjoint stage: the three coefficients of the neighbouring tile its shifted reads reach (clamped; masked below by position)
+    float nb1 = 0.0f, nb2_near = 0.0f, nb2_far = 0.0f;
+    if constexpr (ADJ) {
+        const int near = REV ? t0 + T : t0 - 1, far = REV ? t0 + T + 1 : t0 - 2;
+        const int at_near = max(min(near, n - 1), 0), at_far = max(min(far, n - 1), 0);
+        nb1 = p1[at_near];
+        nb2_near = p2[at_near];
+        nb2_far = p2[at_far];
+    }
+    float y1 = 0.0f, y2 = 0.0f;                       // the state that enters the tile
+    if constexpr (FINAL) {
+        const int tt = min(t, a.tiles - 1);
+        float m[kVar2Components];
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index(a, i, line, tt)];
+        apply_map(m, a.carry[group_carry_index(a, 0, line, g)], a.carry[group_carry_index(a, 1, line, g)], y1, y2);
+    }
+    float x[T], c1[T], c2[T];
+    transpose_in(vx, lds, x);
+    {
+        float r1[T], r2[T];
+        transpose_in(v1, lds, r1);
+        transpose_in(v2, lds, r2);
+        // the coefficients of step i: the tile's own, or (ADJ) those one and two samples further along the forward's direction
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            if constexpr (!ADJ) {
+                c1[i] = r1[i];
+                c2[i] = r2[i];
+            } else if constexpr (REV) {
+                c1[i] = i + 1 < T ? r1[i + 1 < T ? i + 1 : 0] : nb1;
+                c2[i] = i + 2 < T ? r2[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? nb2_near : nb2_far);
+            } else {
+                c1[i] = i >= 1 ? r1[i >= 1 ? i - 1 : 0] : nb1;
+                c2[i] = i >= 2 ? r2[i >= 2 ? i - 2 : 0] : (i == 1 ? nb2_near : nb2_far);
+            }
+        }
+    }
+    // the masks, by position in the line: everything from n on, and the coefficients that would reach outside the line
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        x[i] = at < n ? x[i] : 0.0f;
+        if constexpr (REV) {
+            c1[i] = at >= n - 1 ? 0.0f : c1[i];
+            c2[i] = at >= n - 2 ? 0.0f : c2[i];
+        } else {
+            c1[i] = (at < 1 || at >= n) ? 0.0f : c1[i];
+            c2[i] = (at < 2 || at >= n) ? 0.0f : c2[i];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);      // (the recurrences stay behind the transposition: they would hold its registers)
+    if constexpr (FINAL) {
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const int i = REV ? T - 1 - j : j;
+            const float y = step2(c1[i], c2[i], x[i], y1, y2);
+            x[i] = y; y2 = y1; y1 = y;
+        }
+        store_group(lds, a.dst + first, n, s0, x);
+    } else {
+        float u1 = 1.0f, u2 = 0.0f, w1 = 0.0f, w2 = 1.0f;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const int i = REV ? T - 1 - j : j;
+            const float y = step2(c1[i], c2[i], x[i], y1, y2);
+            const float u = step2(c1[i], c2[i], 0.0f, u1, u2);
+            const float w = step2(c1[i], c2[i], 0.0f, w1, w2);
+            y2 = y1; y1 = y; u2 = u1; u1 = u; w2 = w1; w1 = w;
+        }
+        float own[kVar2Components], map[kVar2Components], whole[kVar2Components];
+        own[VAR2_E0] = y1; own[VAR2_E1] = y2;
+        own[VAR2_P00] = u1; own[VAR2_P10] = u2;       // the column the state (1, 0) becomes
+        own[VAR2_P01] = w1; own[VAR2_P11] = w2;       // and the column of (0, 1)
+        scan_group<REV>(own, map, whole);
+        if (t < a.tiles) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) a.tails[map_index(a, i, line, t)] = map[i];
+        }
+        if (lane == (REV ? 0 : 63)) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) a.tails[aggregate_index(a, i, line, g)] = whole[i];
+        }
+    }
+}
+
+// ---- the recurrence over groups: one workgroup per line ---------------------------------------------------------------------------
+// A sweep takes blockDim.x groups in the order of the recurrence (REV: from the last group down), lane i the i-th of them.  Within a
+// sweep: an inclusive wave scan of the aggregates, the waves' totals through LDS, every lane folding the totals of the waves before
+// it onto the running state -- at most 16 steps -- and all of them onto the next sweep's.  Lanes past the last group hold the identity.
+template <bool REV>
+__global__ void __launch_bounds__(kCarryLanes) var2_carry_kernel(Var2Args a) {
+    __shared__ float totals[kCarryLanes / 64][kVar2Components];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6, span = blockDim.x;
+    const int line = blockIdx.x, G = a.groups;
+    float run0 = 0.0f, run1 = 0.0f;                   // the state that enters the sweep's first group
+    for (int base = 0; base < G; base += span) {
+        const int j = base + tid, jj = min(j, G - 1), g = REV ? G - 1 - jj : jj;
+        float m[kVar2Components], other[kVar2Components], next[kVar2Components];
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[aggregate_index(a, i, line, g)];
+        if (j >= G) identity(m);
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) other[i] = __shfl_up(m[i], k);
+            compose(other, m, next);
+            if (lane >= k) {
+#pragma unroll
+                for (int i = 0; i < kVar2Components; i++) m[i] = next[i];
+            }
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) totals[wave][i] = m[i];
+        }
+        __syncthreads();
+        float enter0 = run0, enter1 = run1, next0 = run0, next1 = run1;      // enter: what enters this wave's first group
+        for (int w = 0; w < waves; w++) {
+            float tw[kVar2Components], r0, r1;
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) tw[i] = totals[w][i];
+            apply_map(tw, next0, next1, r0, r1);
+            next0 = r0; next1 = r1;
+            if (w + 1 == wave) { enter0 = next0; enter1 = next1; }
+        }
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) other[i] = __shfl_up(m[i], 1);
+        if (lane == 0) identity(other);
+        float c0, c1;
+        apply_map(other, enter0, enter1, c0, c1);
+        if (j < G) {
+            a.carry[group_carry_index(a, 0, line, g)] = c0;
+            a.carry[group_carry_index(a, 1, line, g)] = c1;
+        }
+        run0 = next0; run1 = next1;
+        __syncthreads();
+    }
+}
+
+// ---- the coefficient gradients: one streaming launch, four samples per lane -------------------------------------------------------
+template <bool CAUSAL>
+__global__ void __launch_bounds__(kGradLanes) var2_grad_kernel(Var2GradArgs a) {
+    const int n = a.n;
+    const int at = (blockIdx.x * kGradLanes + threadIdx.x) * 4;      // below 2^30 + 1024
+    if (at >= n) return;
+    const int64_t first = (int64_t)blockIdx.y * a.stride;
+    const float *lam = a.lam + first, *y = a.y + first;
+    const float4 l = *reinterpret_cast<const float4 *>(lam + at);
+    const float4 v = *reinterpret_cast<const float4 *>(y + at);
+    // the two neighbours beyond the lane's four samples, from clamped addresses; selected away at the line's end
+    const int near = CAUSAL ? at - 1 : at + 4, far = CAUSAL ? at - 2 : at + 5;
+    const float y_near = y[max(min(near, n - 1), 0)], y_far = y[max(min(far, n - 1), 0)];
+    const float ls[4] = {l.x, l.y, l.z, l.w};
+    // six consecutive samples: y[at - 2 .. at + 3] (causal: sample at + k is ys[k + 2]) or y[at .. at + 5] (sample at + k is ys[k])
+    const float ys[6] = {CAUSAL ? y_far : v.x, CAUSAL ? y_near : v.y, CAUSAL ? v.x : v.z, CAUSAL ? v.y : v.w,
+                         CAUSAL ? v.z : y_near, CAUSAL ? v.w : y_far};
+    float g1[4], g2[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float one = ys[k + 1], two = CAUSAL ? ys[k] : ys[k + 2];      // one and two samples against the forward's direction
+        const bool no_one = CAUSAL ? at + k < 1 : at + k >= n - 1, no_two = CAUSAL ? at + k < 2 : at + k >= n - 2;
+        g1[k] = no_one ? 0.0f : -ls[k] * one;
+        g2[k] = no_two ? 0.0f : -ls[k] * two;
+    }
+    *reinterpret_cast<float4 *>(a.grad_a1 + first + at) = make_float4(g1[0], g1[1], g1[2], g1[3]);
+    *reinterpret_cast<float4 *>(a.grad_a2 + first + at) = make_float4(g2[0], g2[1], g2[2], g2[3]);
+}
+
+int launched(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
+    return RF_OK;
+}
+
+template <bool FINAL>
+int launch_pass(const Var2Args &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.adjoint) {
+        if (a.causal) hipLaunchKernelGGL((var2_signal_kernel<false, true, FINAL>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_signal_kernel<true, true, FINAL>), grid, block, 0, stream, a);
+        return launched(FINAL ? "var2_adj_pass2_1d" : "var2_adj_tails_1d");
+    }
+    if (a.causal) hipLaunchKernelGGL((var2_signal_kernel<false, false, FINAL>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_signal_kernel<true, false, FINAL>), grid, block, 0, stream, a);
+    return launched(FINAL ? "var2_pass2_1d" : "var2_tails_1d");
+}
+
+}  // namespace
+
+int launch_var2_tails(const Var2Args &a, hipStream_t stream) { return launch_pass<false>(a, stream); }
+int launch_var2_pass2(const Var2Args &a, hipStream_t stream) { return launch_pass<true>(a, stream); }
+
+int launch_var2_carry(const Var2Args &a, hipStream_t stream) {
+    const int lanes = std::min(kCarryLanes, (a.groups + 63) / 64 * 64);
+    const dim3 grid((unsigned)a.n_lines), block((unsigned)lanes);
+    if (a.causal) hipLaunchKernelGGL((var2_carry_kernel<false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_carry_kernel<true>), grid, block, 0, stream, a);
+    return launched("var2_carry_1d");
+}
+
+int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.causal) hipLaunchKernelGGL((var2_grad_kernel<true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_grad_kernel<false>), grid, block, 0, stream, a);
+    return launched("var2_grad_1d");
+}
+
+}  // namespace rf

@@ -1,0 +1,214 @@
+"""Time-varying second-order all-pole scans on signals: thin Python handle over rf_var2_plan_* (include/recfilter_amd.h).
+
+    causal      y[n] = x[n] - a1[n] y[n-1] - a2[n] y[n-2]          anticausal: the same on the three signals reversed
+
+with coefficient signals as long as the input -- a resonator whose centre frequency and bandwidth move, an LPC synthesis filter,
+the feedback half of a swept biquad.  The scans run in the HIP kernels of kernels_var2_signal.hip; torch tensors are device
+memory.  `Var2Plan.backward` (rf_var2_plan_backward) is the adjoint in the same kernels' adjoint instances -- the gradient of the
+input and, where asked for, of both coefficient signals -- and `Var2Plan.apply` / `allpole_scan` put it behind torch.autograd.
+f32 only; no double backward.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict
+
+from . import capi
+from .capi import _PlanHandle, _timed
+
+
+class Var2Plan(_PlanHandle):
+    """One scan over `lines` f32 signals of `length` samples (a multiple of 4, up to 2**30), every line with coefficient signals of
+    its own.  A signal argument is a device tensor of shape (length,) (lines == 1) or (lines, length) whose rows lie `stride`
+    samples apart (default: length, a contiguous tensor; a wider stride is a [:, :length] view of a wider buffer).  Coefficients
+    that would multiply a sample outside the line -- a1[0], a2[0], a2[1] of a causal scan, their mirror images of an anticausal
+    one -- are never used.  One plan owns one workspace: order its calls."""
+    _destroy = "rf_var2_plan_destroy"
+
+    def __init__(self, length: int, lines: int = 1, causal: bool = True, device: int = -1, stride: int = None):
+        d = capi.Var2SignalDesc()
+        d.abi = capi.RF_ABI
+        d.length, d.n_lines = int(length), int(lines)
+        d.stride = int(length if stride is None else stride)
+        d.causal = int(bool(causal))
+        d.device, d.flags = int(device), 0
+        self._desc = d
+        self.length, self.lines, self.stride, self.causal = int(d.length), int(d.n_lines), int(d.stride), bool(causal)
+        self._h = ctypes.c_void_p()
+        capi.check(capi.lib().rf_var2_plan_create_signal(ctypes.byref(d), ctypes.byref(self._h)))
+
+    # -- queries ----------------------------------------------------------------------------
+    @property
+    def workspace_bytes(self) -> int:
+        """4 * lines * (6 * (tiles + groups) + 2 * groups), tiles = ceil(length / 64), groups = ceil(tiles / 64)"""
+        return int(capi.lib().rf_var2_plan_workspace_bytes(self._h))
+
+    @property
+    def num_kernels(self) -> int:
+        return int(capi.lib().rf_var2_plan_num_kernels(self._h))
+
+    def backward_num_kernels(self, with_coefficients: bool = False) -> int:
+        """3 launches, 4 with coefficient gradients"""
+        return int(capi.lib().rf_var2_plan_backward_num_kernels(self._h, int(bool(with_coefficients))))
+
+    # -- arguments ----------------------------------------------------------------------------
+    @property
+    def _host_only(self) -> bool:
+        return self._desc.device == capi.RF_DEVICE_HOST_ONLY
+
+    def _pointer(self, t, what: str) -> ctypes.c_void_p:
+        """the address of a signal argument after its checks (None: a null pointer)"""
+        import torch
+        if t is None:
+            return ctypes.c_void_p()
+        shapes = [(self.lines, self.length)] + ([(self.length,)] if self.lines == 1 else [])
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{what}: shape {tuple(t.shape)}, the plan takes {' or '.join(str(s) for s in shapes)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: float32 signals only, got {t.dtype}")
+        if not t.is_cuda or t.stride(-1) != 1 or (t.dim() == 2 and self.lines > 1 and t.stride(0) != self.stride):
+            raise ValueError(f"{what}: a device tensor with dense rows {self.stride} samples apart")
+        return ctypes.c_void_p(t.data_ptr())
+
+    def _placeholders(self, count: int):
+        """what a call on a host-only plan passes: there are no device tensors to take pointers from.  Addresses that pass the
+        library's argument checks (16-byte aligned, apart) and are never dereferenced: the library refuses to run, RF_ERR_HIP"""
+        span = ((self.lines - 1) * self.stride + self.length) * 4 + 4096
+        return tuple(ctypes.c_void_p(4096 + i * span) for i in range(count))
+
+    def _like(self, t):
+        """a new tensor with the layout of `t` as this plan takes it"""
+        import torch
+        if self.lines > 1 and self.stride != self.length:
+            return torch.empty((self.lines, self.stride), dtype=torch.float32, device=t.device)[:, :self.length]
+        return torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device)
+
+    # -- execution --------------------------------------------------------------------------
+    def _arguments(self, x, a1, a2, out, stream):
+        if self._host_only:
+            return self._placeholders(4) + (None, ctypes.c_void_p())
+        if out is None:
+            out = self._like(x)
+        return (self._pointer(x, "x"), self._pointer(a1, "a1"), self._pointer(a2, "a2"), self._pointer(out, "out"), out, self._stream(stream))
+
+    def execute(self, x, a1, a2, out=None, stream=None):
+        """rf_var2_plan_execute: asynchronous on `stream` (default: torch's current stream).  out=None allocates the output; out may
+        be x itself (in place)."""
+        px, p1, p2, po, out, s = self._arguments(x, a1, a2, out, stream)
+        capi.check(capi.lib().rf_var2_plan_execute(self._h, px, p1, p2, po, s))
+        return out
+
+    def execute_timed(self, x, a1, a2, out=None, stream=None):
+        """rf_var2_plan_execute_timed: (output, [(kernel name, ms), ...]) measured with HIP events; synchronises the stream."""
+        px, p1, p2, po, out, s = self._arguments(x, a1, a2, out, stream)
+        return out, _timed(lambda *report: capi.lib().rf_var2_plan_execute_timed(self._h, px, p1, p2, po, s, *report), self.num_kernels)
+
+    # -- the adjoint ------------------------------------------------------------------------
+    def _backward_arguments(self, a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, stream):
+        if self._host_only:
+            return self._placeholders(5) + (ctypes.c_void_p(), ctypes.c_void_p(), None, ctypes.c_void_p())
+        if grad_in is None:
+            grad_in = self._like(grad_out)
+        return (self._pointer(a1, "a1"), self._pointer(a2, "a2"), self._pointer(out, "out"), self._pointer(grad_out, "grad_out"),
+                self._pointer(grad_in, "grad_in"), self._pointer(grad_a1, "grad_a1"), self._pointer(grad_a2, "grad_a2"), grad_in,
+                self._stream(stream))
+
+    def backward(self, a1, a2, out, grad_out, grad_in=None, grad_a1=None, grad_a2=None, stream=None):
+        """rf_var2_plan_backward, the adjoint of execute: grad_in = dL/dx from grad_out = dL/d(out); `out` is execute's result.
+        grad_in=None allocates it; it may be grad_out itself (in place).  grad_a1 and grad_a2: both None (no coefficient gradients;
+        `out` may then be None too) or both tensors to be WRITTEN.  Returns (grad_in, grad_a1, grad_a2).  Asynchronous; uses the
+        plan's workspace like an execute."""
+        p1, p2, po, pgo, pgi, pg1, pg2, grad_in, s = self._backward_arguments(a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, stream)
+        capi.check(capi.lib().rf_var2_plan_backward(self._h, p1, p2, po, pgo, pgi, pg1, pg2, s))
+        return grad_in, grad_a1, grad_a2
+
+    def backward_timed(self, a1, a2, out, grad_out, grad_in=None, grad_a1=None, grad_a2=None, stream=None):
+        """rf_var2_plan_backward_timed: (grad_in, grad_a1, grad_a2, [(kernel name, ms), ...]); synchronises the stream."""
+        p1, p2, po, pgo, pgi, pg1, pg2, grad_in, s = self._backward_arguments(a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, stream)
+        n = self.backward_num_kernels(grad_a1 is not None or grad_a2 is not None)
+        times = _timed(lambda *report: capi.lib().rf_var2_plan_backward_timed(self._h, p1, p2, po, pgo, pgi, pg1, pg2, s, *report), n)
+        return grad_in, grad_a1, grad_a2, times
+
+    def apply(self, x, a1, a2):
+        """execute, out of place, as a differentiable torch operation: the values are bit for bit execute's.  Backward is `backward`
+        -- the input's gradient always, both coefficient gradients where either coefficient signal requires one.  The coefficients
+        and the result are saved; no double backward."""
+        return _function().apply(self, x, a1, a2)
+
+
+_var2_function = None
+
+
+def _function():
+    """the torch.autograd.Function behind Var2Plan.apply (torch is imported when it is first needed)"""
+    global _var2_function
+    if _var2_function is not None:
+        return _var2_function
+    import torch
+
+    class Var2ScanFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, x, a1, a2):
+            ctx.plan = plan
+            with torch.cuda.device(x.device):
+                out = plan.execute(x, a1, a2)
+            ctx.save_for_backward(a1, a2, out)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            a1, a2, out = ctx.saved_tensors
+            need_x, need_1, need_2 = ctx.needs_input_grad[1:4]
+            g = _plan_layout(plan, grad_out)
+            g1 = plan._like(g) if need_1 or need_2 else None
+            g2 = plan._like(g) if need_1 or need_2 else None
+            with torch.cuda.device(g.device):
+                gin, g1, g2 = plan.backward(a1, a2, out, g, None, g1, g2)
+            return None, gin if need_x else None, g1 if need_1 else None, g2 if need_2 else None
+
+    _var2_function = Var2ScanFunction
+    return _var2_function
+
+
+def _plan_layout(plan, t):
+    """`t` as the plan takes a signal: f32, dense rows `stride` apart, 16-byte aligned (a copy only where it is not)"""
+    import torch
+    t = t.to(torch.float32)
+    ok = t.stride(-1) == 1 and (t.dim() == 1 or plan.lines == 1 and t.is_contiguous() or plan.lines > 1 and t.stride(0) == plan.stride)
+    if ok and t.data_ptr() % 16 == 0:
+        return t
+    fresh = plan._like(t)
+    fresh.copy_(t)
+    return fresh
+
+
+_plans: Dict[tuple, Var2Plan] = {}
+
+
+def allpole_scan(x, a1, a2, causal: bool = True):
+    """y[n] = x[n] - a1[n] y[n-1] - a2[n] y[n-2]  (causal=False: y[n+1], y[n+2]) on device tensors of one shape, (N,) or (L, N),
+    f32; every line has its own coefficients.  Differentiable in all three.  Plans are cached by length, lines, direction and
+    device; calls that share a plan are ordered by the caller (one stream).  The library takes lengths that are multiples of 4:
+    any other length is padded up to the next one with zeros in x, a1 and a2 -- behind the end for a causal scan, before the
+    start for an anticausal one: the recurrence reaches the padding last and the masked coefficients stay where they were, so the
+    N real samples are what an unpadded scan gives -- and the result is sliced back.  The padding costs one copy of every signal."""
+    import torch
+    if x.dim() not in (1, 2) or tuple(a1.shape) != tuple(x.shape) or tuple(a2.shape) != tuple(x.shape):
+        raise ValueError(f"x, a1 and a2 must share one shape (N,) or (L, N), got {tuple(x.shape)}, {tuple(a1.shape)}, {tuple(a2.shape)}")
+    n = int(x.shape[-1])
+    lines = 1 if x.dim() == 1 else int(x.shape[0])
+    pad = -n % 4
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (n + pad, lines, bool(causal), device)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = Var2Plan(n + pad, lines=lines, causal=causal, device=device)
+    if pad:
+        where = (0, pad) if causal else (pad, 0)
+        x, a1, a2 = (torch.nn.functional.pad(t, where) for t in (x, a1, a2))
+    out = plan.apply(*(_plan_layout(plan, t) for t in (x, a1, a2)))
+    if pad:
+        out = out[..., :n] if causal else out[..., pad:]
+    return out
