@@ -1161,4 +1161,28 @@ public:
         prepare();
         if (rf_var2_plan_backward(plan, a1, a2, out, grad_out, grad_in, grad_a1, grad_a2, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
     }
+    /** The whole section in direct form I (rf_var2_plan_execute_biquad), five coefficient signals as long as the input:
+     *      v[n] = b0[n] in[n] + b1[n] in[n-1] + b2[n] in[n-2]        out[n] = v[n] - a1[n] out[n-1] - a2[n] out[n-2]
+     *  (-x: the samples after n).  3 launches.  out overlaps none of the six inputs: in == out is refused. */
+    void realize_biquad(const void *in, const void *b0, const void *b1, const void *b2, const void *a1, const void *a2, void *out,
+                        void *stream = nullptr) {
+        prepare();
+        if (rf_var2_plan_execute_biquad(plan, in, b0, b1, b2, a1, a2, out, stream) != RF_OK) throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize_biquad() (rf_var2_plan_backward_biquad), 4 launches: grad_in from grad_out; `out` is realize_biquad()'s
+     *  result.  The five coefficient gradients: all null (`out` may then be null) or all signals to be written.  grad_in == grad_out
+     *  is allowed.  The plan allocates one signal for the adjoint state in the first call (biquad_gradient_bytes()). */
+    void gradient_biquad(const void *in, const void *b0, const void *b1, const void *b2, const void *a1, const void *a2, const void *out,
+                         const void *grad_out, void *grad_in, void *grad_b0 = nullptr, void *grad_b1 = nullptr, void *grad_b2 = nullptr,
+                         void *grad_a1 = nullptr, void *grad_a2 = nullptr, void *stream = nullptr) {
+        prepare();
+        if (rf_var2_plan_backward_biquad(plan, in, b0, b1, b2, a1, a2, out, grad_out, grad_in, grad_b0, grad_b1, grad_b2, grad_a1, grad_a2,
+                                         stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** 3 */
+    int biquad_num_kernels() { prepare(); return rf_var2_plan_biquad_num_kernels(plan); }
+    /** 4 */
+    int biquad_gradient_num_kernels() { prepare(); return rf_var2_plan_backward_biquad_num_kernels(plan); }
+    size_t biquad_gradient_bytes() { prepare(); return rf_var2_plan_backward_biquad_bytes(plan); }
 };

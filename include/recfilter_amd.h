@@ -996,9 +996,34 @@ int    rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth
  * backward: exactly one of grad_a1, grad_a2 null; a null pointer; a pointer that is not 16-byte aligned; an overlap named above
  * (RF_ERR_INVALID_ARG); then a host-only plan (RF_ERR_HIP).  A *_timed call checks ms_out's capacity first.  A host-only plan
  * (device = RF_DEVICE_HOST_ONLY) answers the queries and checks the arguments of a call, which it never dereferences.
- * Out of scope: orders above 2; time-varying feed-forward taps; images and volumes; lists of scans inside one plan; 16-bit
- * signals; second derivatives; sharding; lengths that are not multiples of 4 (pad the three signals with zeros behind the end
- * of a causal scan, before the start of an anticausal one: the real samples are what an unpadded scan gives). */
+ * Out of scope: orders above 2; images and volumes; lists of scans inside one plan; 16-bit signals; second derivatives;
+ * sharding; lengths that are not multiples of 4 (pad the signals with zeros behind the end of a causal scan, before the start
+ * of an anticausal one: the real samples are what an unpadded scan gives).
+ *
+ * The whole section, direct form I (rf_var2_plan_execute_biquad), on the same plan: five coefficient signals laid out like in,
+ *     causal      v[n] = b0[n] in[n] + b1~[n] in[n-1] + b2~[n] in[n-2]      y[n] = v[n] - a1~[n] y[n-1] - a2~[n] y[n-2]
+ * (anticausal: the same on all six signals reversed).  The masked slots are b1[0], b2[0], b2[1], a1[0], a2[0], a2[1] of a causal
+ * plan and their mirror images of an anticausal one; b0 has none.  The order of operations is fixed,
+ * v = fma(b2~, in[n-2], fma(b1~, in[n-1], b0 * in[n])): b = (1, 0, 0) gives rf_var2_plan_execute's bits for finite input.
+ * Three launches: "var2_biquad_tails_1d" forms v over a lane's tile in registers, STORES v to out and runs the tails stage on
+ * it; "var2_carry_1d" and "var2_pass2_1d" then run on out in place.  rf_var2_plan_biquad_num_kernels = 3.  out overlaps none of
+ * the six inputs: in == out is refused, because the first launch stores v while neighbouring groups still read in.
+ * rf_var2_plan_backward_biquad takes the six inputs, out = the forward's result and grad_out, and stores, for a causal plan,
+ *     grad_in[n] = b0[n] lam[n] + b1~[n+1] lam[n+1] + b2~[n+2] lam[n+2]       lam: the adjoint state above, from grad_out
+ *     grad_b0[n] = lam[n] in[n]   grad_b1[n] = lam[n] in[n-1]   grad_b2[n] = lam[n] in[n-2]
+ *     grad_a1[n] = -lam[n] y[n-1]   grad_a2[n] = -lam[n] y[n-2]
+ * (the mirror image for an anticausal one; +0 at the masked slots) in four launches, "var2_adj_tails_1d", "var2_carry_1d",
+ * "var2_adj_pass2_1d" and "var2_biquad_grad_1d", with or without coefficient gradients:
+ * rf_var2_plan_backward_biquad_num_kernels = 4.  lam lives in one f32 signal of the plan's span that the plan allocates in its
+ * first such call; rf_var2_plan_backward_biquad_bytes reports its size, 4 * ((n_lines - 1) * stride + length), and
+ * rf_var2_plan_workspace_bytes is unchanged.  The five coefficient gradients are all given or all null; all null: out may be null.
+ * grad_in == grad_out is allowed; a gradient that is written overlaps nothing else.  A call refuses, in this order and before
+ * any HIP call: a null plan; backward: some but not all of the five coefficient gradients null; a null pointer; a pointer that
+ * is not 16-byte aligned; execute: out overlapping a coefficient signal, then out overlapping in (in == out included); backward:
+ * a written gradient overlapping a coefficient signal, in, out, another written gradient, or grad_out other than grad_in exactly
+ * (RF_ERR_INVALID_ARG); then a host-only plan (RF_ERR_HIP).  A *_timed call checks ms_out's capacity first.
+ * Out of scope for the section: orders above 2; cascades of sections inside one plan; the direct-form-II ordering; images and
+ * volumes; 16-bit signals; second derivatives; sharding. */
 typedef struct rf_var2_plan rf_var2_plan;
 typedef struct {
     uint32_t abi;                     /* RF_ABI                                                  */
@@ -1022,6 +1047,21 @@ int    rf_var2_plan_backward_timed(rf_var2_plan *plan, const void *a1, const voi
                                    void *grad_in, void *grad_a1, void *grad_a2, void *stream, float *ms_out, const char **names_out,
                                    int capacity);
 int    rf_var2_plan_backward_num_kernels(const rf_var2_plan *plan, int with_coefficient_gradients);
+int    rf_var2_plan_execute_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
+                                   const void *a2, void *out, void *stream);
+int    rf_var2_plan_execute_biquad_timed(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2,
+                                         const void *a1, const void *a2, void *out, void *stream, float *ms_out, const char **names_out,
+                                         int capacity);
+int    rf_var2_plan_backward_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
+                                    const void *a2, const void *out, const void *grad_out, void *grad_in, void *grad_b0, void *grad_b1,
+                                    void *grad_b2, void *grad_a1, void *grad_a2, void *stream);
+int    rf_var2_plan_backward_biquad_timed(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2,
+                                          const void *a1, const void *a2, const void *out, const void *grad_out, void *grad_in,
+                                          void *grad_b0, void *grad_b1, void *grad_b2, void *grad_a1, void *grad_a2, void *stream,
+                                          float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_biquad_num_kernels(const rf_var2_plan *plan);
+int    rf_var2_plan_backward_biquad_num_kernels(const rf_var2_plan *plan);
+size_t rf_var2_plan_backward_biquad_bytes(const rf_var2_plan *plan);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

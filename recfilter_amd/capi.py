@@ -85,6 +85,8 @@ EXPORTED_SYMBOLS = [
     "rf_var2_plan_create_signal", "rf_var2_plan_destroy", "rf_var2_plan_workspace_bytes", "rf_var2_plan_num_kernels",
     "rf_var2_plan_execute", "rf_var2_plan_execute_timed", "rf_var2_plan_backward", "rf_var2_plan_backward_timed",
     "rf_var2_plan_backward_num_kernels",
+    "rf_var2_plan_execute_biquad", "rf_var2_plan_execute_biquad_timed", "rf_var2_plan_backward_biquad", "rf_var2_plan_backward_biquad_timed",
+    "rf_var2_plan_biquad_num_kernels", "rf_var2_plan_backward_biquad_num_kernels", "rf_var2_plan_backward_biquad_bytes",
 ]
 
 
@@ -295,6 +297,14 @@ def lib() -> ctypes.CDLL:
     L.rf_var2_plan_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rf_var2_plan_backward_timed.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
     L.rf_var2_plan_backward_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_execute_biquad.argtypes = [vp] * 9
+    L.rf_var2_plan_execute_biquad_timed.argtypes = [vp] * 9 + [fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var2_plan_backward_biquad.argtypes = [vp] * 16
+    L.rf_var2_plan_backward_biquad_timed.argtypes = [vp] * 16 + [fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var2_plan_biquad_num_kernels.argtypes = [vp]
+    L.rf_var2_plan_backward_biquad_num_kernels.argtypes = [vp]
+    L.rf_var2_plan_backward_biquad_bytes.argtypes = [vp]
+    L.rf_var2_plan_backward_biquad_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

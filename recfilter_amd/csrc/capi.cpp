@@ -740,6 +740,46 @@ int rf_var2_plan_backward_timed(rf_var2_plan *plan, const void *a1, const void *
     });
 }
 
+// the direct-form-I section on the same plan
+int rf_var2_plan_biquad_num_kernels(const rf_var2_plan *plan) { return plan ? (int)plan->biquad_names.size() : 0; }
+int rf_var2_plan_backward_biquad_num_kernels(const rf_var2_plan *plan) { return plan ? (int)plan->biquad_backward_names.size() : 0; }
+size_t rf_var2_plan_backward_biquad_bytes(const rf_var2_plan *plan) { return plan ? plan->span_bytes() : 0; }
+
+int rf_var2_plan_execute_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
+                                const void *a2, void *out, void *stream) {
+    return fenced("rf_var2_plan_execute_biquad", [&] { return run_var2_biquad(plan, in, b0, b1, b2, a1, a2, out, (hipStream_t)stream, nullptr); });
+}
+
+int rf_var2_plan_execute_biquad_timed(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
+                                      const void *a2, void *out, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_execute_biquad_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (int rc = timed_names(plan->biquad_names, ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var2_biquad(plan, in, b0, b1, b2, a1, a2, out, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var2_plan_backward_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
+                                 const void *a2, const void *out, const void *grad_out, void *grad_in, void *grad_b0, void *grad_b1,
+                                 void *grad_b2, void *grad_a1, void *grad_a2, void *stream) {
+    return fenced("rf_var2_plan_backward_biquad", [&] {
+        return run_var2_biquad_backward(plan, in, b0, b1, b2, a1, a2, out, grad_out, grad_in, grad_b0, grad_b1, grad_b2, grad_a1, grad_a2,
+                                        (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var2_plan_backward_biquad_timed(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
+                                       const void *a2, const void *out, const void *grad_out, void *grad_in, void *grad_b0, void *grad_b1,
+                                       void *grad_b2, void *grad_a1, void *grad_a2, void *stream, float *ms_out, const char **names_out,
+                                       int capacity) {
+    return fenced("rf_var2_plan_backward_biquad_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (int rc = timed_names(plan->biquad_backward_names, ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var2_biquad_backward(plan, in, b0, b1, b2, a1, a2, out, grad_out, grad_in, grad_b0, grad_b1, grad_b2, grad_a1, grad_a2,
+                                        (hipStream_t)stream, ms_out);
+    });
+}
+
 int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                      void *dx, void *dy, int32_t device, void *stream) {
     return fenced("rf_var_distances", [&] {

@@ -34,6 +34,7 @@ struct Var2Args {
     int32_t causal;
     int32_t adjoint;
     int64_t stride;
+    const float *b0, *b1, *b2;      // var2_biquad_tails_1d alone: the feed-forward taps, laid out like x
 };
 
 // The coefficient gradients of one scan (var2_grad_1d): lam = its adjoint state, y = its output.
@@ -49,11 +50,33 @@ struct Var2GradArgs {
     int64_t stride;
 };
 
+// The gradients of one direct-form-I section behind its adjoint scan (var2_biquad_grad_1d): lam = the adjoint state of the
+// all-pole half, x = the section's input, y = its output.  For a causal section
+//   grad_in[n] = fma(b2~[n+2], lam[n+2], fma(b1~[n+1], lam[n+1], b0[n] * lam[n]))          (lam outside the line is 0)
+//   grad_b0[n] = lam[n] x[n]   grad_b1[n] = lam[n] x[n-1]   grad_b2[n] = lam[n] x[n-2]   grad_a1[n] = -lam[n] y[n-1]   grad_a2[n] = -lam[n] y[n-2]
+// the mirror image for an anticausal one; +0, by a select, where the neighbour lies outside the line.  with_coefficients == 0:
+// grad_in alone; x, y and the five coefficient gradients are not touched.
+struct Var2BiquadGradArgs {
+    const float *lam, *x, *y;
+    const float *b0, *b1, *b2;
+    float *grad_in;
+    float *grad_b0, *grad_b1, *grad_b2, *grad_a1, *grad_a2;
+    int32_t n;
+    int32_t n_lines;
+    int32_t causal;                 // the direction of the FORWARD section
+    int32_t with_coefficients;
+    int64_t stride;
+};
+
 constexpr int kVar2Tile = 64;            // samples of a tile: one lane
 constexpr int kVar2GroupTiles = 64;      // tiles of a group: one wave
 int launch_var2_tails(const Var2Args &a, hipStream_t stream);      // "var2_tails_1d", "var2_adj_tails_1d"
 int launch_var2_carry(const Var2Args &a, hipStream_t stream);      // "var2_carry_1d"
 int launch_var2_pass2(const Var2Args &a, hipStream_t stream);      // "var2_pass2_1d", "var2_adj_pass2_1d"
 int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream);   // "var2_grad_1d"
+// the tails launch of a direct-form-I section: v = b0 x + b1~ x[n-1] + b2~ x[n-2] formed in registers and STORED to a.dst, the
+// tails of the all-pole scan on v stored as launch_var2_tails stores them (a.adjoint == 0; a.dst overlaps none of the inputs)
+int launch_var2_biquad_tails(const Var2Args &a, hipStream_t stream);             // "var2_biquad_tails_1d"
+int launch_var2_biquad_grad(const Var2BiquadGradArgs &a, hipStream_t stream);    // "var2_biquad_grad_1d"
 
 }  // namespace rf

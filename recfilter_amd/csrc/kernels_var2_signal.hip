@@ -31,6 +31,14 @@
 // read one (a1) and two (a2) samples further on.  The ADJ instances form them from the tile's own coefficients and the first three
 // of the neighbouring tile (a1[t1], a2[t1], a2[t1+1]; the 65th weight of the first-order kernels), loaded from clamped addresses;
 // the masks by position are those of the scan's own direction.  The adjoint of an anticausal scan is the mirror image.
+//
+// The direct-form-I section (rf_var2_plan_execute_biquad): v[n] = b0[n] x[n] + b1~[n] x[n-1] + b2~[n] x[n-2] in front of the scan.
+//   var2_biquad_tails_1d   the FF instance of the tails stage: the lane forms v over its tile in registers (feed_forward: the
+//                          six signals one at a time through the transposition), stores v to `out` and runs the tails on it;
+//                          var2_carry_1d and var2_pass2_1d then run on out, in place.  Neighbouring groups read x while this one
+//                          stores v: out overlaps no input.
+//   var2_biquad_grad_1d    behind the adjoint scan (lam in a signal of the plan's): grad_in and, where asked for, the five
+//                          coefficient gradients, pointwise in lam, x, y and the taps with neighbours from clamped addresses.
 #include "kernels_var2.h"
 
 #include "var_device.h"
@@ -134,9 +142,53 @@ __device__ __forceinline__ void store_group(float *lds, float *signal, int n, in
     }
 }
 
-// REV: the recurrence runs from the line's end to its start.  ADJ: the shifted coefficients of an adjoint stage.
-template <bool REV, bool ADJ, bool FINAL>
+// The feed-forward part of a direct-form-I section over the lane's tile (var2_biquad_tails_1d):
+//   v[i] = fma(b2~, x two samples before, fma(b1~, x one sample before, b0 * x[i]))          (REV: the samples after)
+// The signals come through the transposition one at a time -- x, then b0, b1, b2, each accumulated into v -- so three tiles are
+// live at most.  The two samples of x beyond the tile come from clamped addresses and are selected to 0 outside the line; the
+// taps are masked by position like the feedback coefficients, and everything from n on is 0: v is 0 there.
+template <bool REV>
+__device__ __forceinline__ void feed_forward(const Var2Args &a, float *lds, int64_t first, int n, int s0, int t0, float (&v)[T]) {
+    const float *px = a.x + first;
+    float raw[T], x[T], b[T];
+    request_group(px, n, s0, raw);
+    const int near = REV ? t0 + T : t0 - 1, far = REV ? t0 + T + 1 : t0 - 2;
+    float x_near = px[max(min(near, n - 1), 0)], x_far = px[max(min(far, n - 1), 0)];
+    x_near = (near < 0 || near >= n) ? 0.0f : x_near;
+    x_far = (far < 0 || far >= n) ? 0.0f : x_far;
+    transpose_in(raw, lds, x);
+#pragma unroll
+    for (int i = 0; i < T; i++) x[i] = t0 + i < n ? x[i] : 0.0f;
+    request_group(a.b0 + first, n, s0, raw);
+    transpose_in(raw, lds, b);
+#pragma unroll
+    for (int i = 0; i < T; i++) v[i] = (t0 + i < n ? b[i] : 0.0f) * x[i];
+    request_group(a.b1 + first, n, s0, raw);
+    transpose_in(raw, lds, b);
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        const float one = REV ? (i + 1 < T ? x[i + 1 < T ? i + 1 : 0] : x_near) : (i >= 1 ? x[i >= 1 ? i - 1 : 0] : x_near);
+        const bool masked = REV ? at >= n - 1 : (at < 1 || at >= n);
+        v[i] = __builtin_fmaf(masked ? 0.0f : b[i], one, v[i]);
+    }
+    request_group(a.b2 + first, n, s0, raw);
+    transpose_in(raw, lds, b);
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        const float two = REV ? (i + 2 < T ? x[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? x_near : x_far))
+                              : (i >= 2 ? x[i >= 2 ? i - 2 : 0] : (i == 1 ? x_near : x_far));
+        const bool masked = REV ? at >= n - 2 : (at < 2 || at >= n);
+        v[i] = __builtin_fmaf(masked ? 0.0f : b[i], two, v[i]);
+    }
+}
+
+// REV: the recurrence runs from the line's end to its start.  ADJ: the shifted coefficients of an adjoint stage.  FF: the tails
+// stage of a direct-form-I section -- the recurrences run on v = the feed-forward part of x, which is stored to dst.
+template <bool REV, bool ADJ, bool FINAL, bool FF = false>
 __global__ void __launch_bounds__(64) var2_signal_kernel(Var2Args a) {
+    static_assert(!FF || (!ADJ && !FINAL), "the feed-forward part stands in front of a forward tails stage");
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
     const int g = blockIdx.x, line = blockIdx.y;
@@ -146,9 +198,17 @@ __global__ void __launch_bounds__(64) var2_signal_kernel(Var2Args a) {
     const int64_t first = (int64_t)line * a.stride;
     const float *px = a.x + first, *p1 = a.a1 + first, *p2 = a.a2 + first;
     float vx[T], v1[T], v2[T];
-    request_group(px, n, s0, vx);
-    request_group(p1, n, s0, v1);
-    request_group(p2, n, s0, v2);
+    float x[T], c1[T], c2[T];
+    if constexpr (FF) {
+        feed_forward<REV>(a, lds, first, n, s0, t0, x);
+        request_group(p1, n, s0, v1);
+        request_group(p2, n, s0, v2);
+        store_group(lds, a.dst + first, n, s0, x);      // v: what var2_pass2_1d reads, in place
+    } else {
+        request_group(px, n, s0, vx);
+        request_group(p1, n, s0, v1);
+        request_group(p2, n, s0, v2);
+    }
     // an adjoint stage: the three coefficients of the neighbouring tile its shifted reads reach (clamped; masked below by position)
     float nb1 = 0.0f, nb2_near = 0.0f, nb2_far = 0.0f;
     if constexpr (ADJ) {
@@ -166,8 +226,7 @@ __global__ void __launch_bounds__(64) var2_signal_kernel(Var2Args a) {
         for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index(a, i, line, tt)];
         apply_map(m, a.carry[group_carry_index(a, 0, line, g)], a.carry[group_carry_index(a, 1, line, g)], y1, y2);
     }
-    float x[T], c1[T], c2[T];
-    transpose_in(vx, lds, x);
+    if constexpr (!FF) transpose_in(vx, lds, x);
     {
         float r1[T], r2[T];
         transpose_in(v1, lds, r1);
@@ -318,6 +377,70 @@ __global__ void __launch_bounds__(kGradLanes) var2_grad_kernel(Var2GradArgs a) {
     *reinterpret_cast<float4 *>(a.grad_a2 + first + at) = make_float4(g2[0], g2[1], g2[2], g2[3]);
 }
 
+// ---- the gradients of a direct-form-I section behind its adjoint scan: one streaming launch, four samples per lane ---------------
+// Six consecutive samples of a signal around the lane's four, the two beyond them from clamped addresses and 0 outside the line.
+//   AHEAD   p[at .. at + 5]:      sample at + k is w[k]
+//   else    p[at - 2 .. at + 3]:  sample at + k is w[k + 2]
+template <bool AHEAD>
+__device__ __forceinline__ void load_six(const float *p, int at, int n, float (&w)[6]) {
+    const float4 q = *reinterpret_cast<const float4 *>(p + at);
+    const int near = AHEAD ? at + 4 : at - 1, far = AHEAD ? at + 5 : at - 2;
+    float p_near = p[max(min(near, n - 1), 0)], p_far = p[max(min(far, n - 1), 0)];
+    p_near = (near < 0 || near >= n) ? 0.0f : p_near;
+    p_far = (far < 0 || far >= n) ? 0.0f : p_far;
+    w[0] = AHEAD ? q.x : p_far; w[1] = AHEAD ? q.y : p_near; w[2] = AHEAD ? q.z : q.x; w[3] = AHEAD ? q.w : q.y;
+    w[4] = AHEAD ? p_near : q.z; w[5] = AHEAD ? p_far : q.w;
+}
+
+// CAUSAL: the direction of the forward section -- its adjoint looks ahead (lam, b1, b2), its coefficient gradients look back (x, y)
+template <bool CAUSAL, bool COEF>
+__global__ void __launch_bounds__(kGradLanes) var2_biquad_grad_kernel(Var2BiquadGradArgs a) {
+    const int n = a.n;
+    const int at = (blockIdx.x * kGradLanes + threadIdx.x) * 4;      // below 2^30 + 1024
+    if (at >= n) return;
+    const int64_t first = (int64_t)blockIdx.y * a.stride;
+    constexpr int L0 = CAUSAL ? 0 : 2;      // sample at + k in a window that looks where the adjoint looks
+    constexpr int X0 = CAUSAL ? 2 : 0;      // and in one that looks where the forward looked
+    float lam[6], t1[6], t2[6];
+    load_six<CAUSAL>(a.lam + first, at, n, lam);
+    load_six<CAUSAL>(a.b1 + first, at, n, t1);
+    load_six<CAUSAL>(a.b2 + first, at, n, t2);
+    const float4 q0 = *reinterpret_cast<const float4 *>(a.b0 + first + at);
+    const float t0[4] = {q0.x, q0.y, q0.z, q0.w};
+    float gx[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        // the taps one and two samples along the forward's direction: inside the line they are never ones the forward masked
+        const int one = CAUSAL ? at + k + 1 : at + k - 1, two = CAUSAL ? at + k + 2 : at + k - 2;
+        const int i1 = CAUSAL ? L0 + k + 1 : L0 + k - 1, i2 = CAUSAL ? L0 + k + 2 : L0 + k - 2;
+        const float c1 = (one < 0 || one >= n) ? 0.0f : t1[i1], c2 = (two < 0 || two >= n) ? 0.0f : t2[i2];
+        gx[k] = __builtin_fmaf(c2, lam[i2], __builtin_fmaf(c1, lam[i1], t0[k] * lam[L0 + k]));
+    }
+    if constexpr (COEF) {
+        float xs[6], ys[6];
+        load_six<!CAUSAL>(a.x + first, at, n, xs);
+        load_six<!CAUSAL>(a.y + first, at, n, ys);
+        float g0[4], g1[4], g2[4], h1[4], h2[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i1 = CAUSAL ? X0 + k - 1 : X0 + k + 1, i2 = CAUSAL ? X0 + k - 2 : X0 + k + 2;
+            const bool no_one = CAUSAL ? at + k < 1 : at + k >= n - 1, no_two = CAUSAL ? at + k < 2 : at + k >= n - 2;
+            const float l = lam[L0 + k];
+            g0[k] = l * xs[X0 + k];
+            g1[k] = no_one ? 0.0f : l * xs[i1];
+            g2[k] = no_two ? 0.0f : l * xs[i2];
+            h1[k] = no_one ? 0.0f : -l * ys[i1];
+            h2[k] = no_two ? 0.0f : -l * ys[i2];
+        }
+        *reinterpret_cast<float4 *>(a.grad_b0 + first + at) = make_float4(g0[0], g0[1], g0[2], g0[3]);
+        *reinterpret_cast<float4 *>(a.grad_b1 + first + at) = make_float4(g1[0], g1[1], g1[2], g1[3]);
+        *reinterpret_cast<float4 *>(a.grad_b2 + first + at) = make_float4(g2[0], g2[1], g2[2], g2[3]);
+        *reinterpret_cast<float4 *>(a.grad_a1 + first + at) = make_float4(h1[0], h1[1], h1[2], h1[3]);
+        *reinterpret_cast<float4 *>(a.grad_a2 + first + at) = make_float4(h2[0], h2[1], h2[2], h2[3]);
+    }
+    *reinterpret_cast<float4 *>(a.grad_in + first + at) = make_float4(gx[0], gx[1], gx[2], gx[3]);
+}
+
 int launched(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
@@ -348,6 +471,25 @@ int launch_var2_carry(const Var2Args &a, hipStream_t stream) {
     if (a.causal) hipLaunchKernelGGL((var2_carry_kernel<false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var2_carry_kernel<true>), grid, block, 0, stream, a);
     return launched("var2_carry_1d");
+}
+
+int launch_var2_biquad_tails(const Var2Args &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.causal) hipLaunchKernelGGL((var2_signal_kernel<false, false, false, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_signal_kernel<true, false, false, true>), grid, block, 0, stream, a);
+    return launched("var2_biquad_tails_1d");
+}
+
+int launch_var2_biquad_grad(const Var2BiquadGradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.causal) {
+        if (a.with_coefficients) hipLaunchKernelGGL((var2_biquad_grad_kernel<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_biquad_grad_kernel<true, false>), grid, block, 0, stream, a);
+    } else {
+        if (a.with_coefficients) hipLaunchKernelGGL((var2_biquad_grad_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_biquad_grad_kernel<false, false>), grid, block, 0, stream, a);
+    }
+    return launched("var2_biquad_grad_1d");
 }
 
 int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream) {

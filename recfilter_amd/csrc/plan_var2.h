@@ -24,6 +24,10 @@ struct rf_var2_plan {
     size_t span_bytes() const { return (size_t)((int64_t)(n_lines - 1) * stride + length) * sizeof(float); }
     std::vector<std::string> names;                  // rf_var2_plan_execute_timed
     std::vector<std::string> backward_names[2];      // without ([0]) and with ([1]) coefficient gradients
+    // the direct-form-I section (rf_var2_plan_execute_biquad, rf_var2_plan_backward_biquad): the adjoint state of its all-pole half
+    // lives in one signal of the plan's span, allocated by the first backward call
+    float *lam = nullptr;
+    std::vector<std::string> biquad_names, biquad_backward_names;
     ~rf_var2_plan();
 };
 
@@ -33,4 +37,9 @@ int build_var2_signal_plan(const rf_var2_signal_desc *desc, rf_var2_plan **out);
 int run_var2_plan(rf_var2_plan *plan, const void *in, const void *a1, const void *a2, void *out, hipStream_t stream, float *ms_out);
 int run_var2_backward(rf_var2_plan *plan, const void *a1, const void *a2, const void *out, const void *grad_out, void *grad_in, void *grad_a1,
                       void *grad_a2, hipStream_t stream, float *ms_out);
+int run_var2_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1, const void *a2, void *out,
+                    hipStream_t stream, float *ms_out);
+int run_var2_biquad_backward(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1, const void *a2,
+                             const void *out, const void *grad_out, void *grad_in, void *grad_b0, void *grad_b1, void *grad_b2, void *grad_a1,
+                             void *grad_a2, hipStream_t stream, float *ms_out);
 }  // namespace rf

@@ -7,6 +7,13 @@ the feedback half of a swept biquad.  The scans run in the HIP kernels of kernel
 memory.  `Var2Plan.backward` (rf_var2_plan_backward) is the adjoint in the same kernels' adjoint instances -- the gradient of the
 input and, where asked for, of both coefficient signals -- and `Var2Plan.apply` / `allpole_scan` put it behind torch.autograd.
 f32 only; no double backward.
+
+The whole direct-form-I section runs on the same plans (rf_var2_plan_execute_biquad / _backward_biquad):
+
+    v[n] = b0[n] x[n] + b1[n] x[n-1] + b2[n] x[n-2]          y[n] = v[n] - a1[n] y[n-1] - a2[n] y[n-2]
+
+`Var2Plan.execute_biquad`, `backward_biquad` (the input's gradient and, where asked for, all five coefficient gradients),
+`apply_biquad` and `biquad_scan` behind torch.autograd.
 """
 from __future__ import annotations
 
@@ -135,8 +142,110 @@ class Var2Plan(_PlanHandle):
         and the result are saved; no double backward."""
         return _function().apply(self, x, a1, a2)
 
+    # -- the whole section, direct form I ---------------------------------------------------------
+    #     v[n] = b0[n] x[n] + b1[n] x[n-1] + b2[n] x[n-2]        y[n] = v[n] - a1[n] y[n-1] - a2[n] y[n-2]
+    @property
+    def biquad_num_kernels(self) -> int:
+        return int(capi.lib().rf_var2_plan_biquad_num_kernels(self._h))
+
+    @property
+    def backward_biquad_num_kernels(self) -> int:
+        """4 launches, with or without coefficient gradients"""
+        return int(capi.lib().rf_var2_plan_backward_biquad_num_kernels(self._h))
+
+    @property
+    def backward_biquad_bytes(self) -> int:
+        """the adjoint state's signal the plan allocates in its first backward_biquad: 4 * ((lines - 1) * stride + length)"""
+        return int(capi.lib().rf_var2_plan_backward_biquad_bytes(self._h))
+
+    def _biquad_arguments(self, x, b0, b1, b2, a1, a2, out, stream):
+        if self._host_only:
+            return self._placeholders(7) + (None, ctypes.c_void_p())
+        if out is None:
+            out = self._like(x)
+        names = ("x", "b0", "b1", "b2", "a1", "a2", "out")
+        return tuple(self._pointer(t, w) for t, w in zip((x, b0, b1, b2, a1, a2, out), names)) + (out, self._stream(stream))
+
+    def execute_biquad(self, x, b0, b1, b2, a1, a2, out=None, stream=None):
+        """rf_var2_plan_execute_biquad: asynchronous on `stream` (default: torch's current stream).  out=None allocates the output;
+        out may NOT be x (the first launch stores the feed-forward part while neighbouring groups still read x)."""
+        *p, out, s = self._biquad_arguments(x, b0, b1, b2, a1, a2, out, stream)
+        capi.check(capi.lib().rf_var2_plan_execute_biquad(self._h, *p, s))
+        return out
+
+    def execute_biquad_timed(self, x, b0, b1, b2, a1, a2, out=None, stream=None):
+        """rf_var2_plan_execute_biquad_timed: (output, [(kernel name, ms), ...]); synchronises the stream."""
+        *p, out, s = self._biquad_arguments(x, b0, b1, b2, a1, a2, out, stream)
+        return out, _timed(lambda *report: capi.lib().rf_var2_plan_execute_biquad_timed(self._h, *p, s, *report), self.biquad_num_kernels)
+
+    def _backward_biquad_arguments(self, x, b0, b1, b2, a1, a2, out, grad_out, grad_in, grads, stream):
+        if grads is not None and len(grads) != 5:
+            raise ValueError("grads: the five coefficient gradients (grad_b0, grad_b1, grad_b2, grad_a1, grad_a2) or None")
+        if self._host_only:
+            return self._placeholders(9) + (ctypes.c_void_p(),) * 5 + (None, grads, ctypes.c_void_p())
+        if grad_in is None:
+            grad_in = self._like(grad_out)
+        names = ("x", "b0", "b1", "b2", "a1", "a2", "out", "grad_out", "grad_in", "grad_b0", "grad_b1", "grad_b2", "grad_a1", "grad_a2")
+        tensors = (x, b0, b1, b2, a1, a2, out, grad_out, grad_in) + (tuple(grads) if grads is not None else (None,) * 5)
+        return tuple(self._pointer(t, w) for t, w in zip(tensors, names)) + (grad_in, grads, self._stream(stream))
+
+    def backward_biquad(self, x, b0, b1, b2, a1, a2, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_biquad, the adjoint of execute_biquad: grad_in = dL/dx from grad_out = dL/d(out); `out` is
+        execute_biquad's result.  grad_in=None allocates it; it may be grad_out itself.  grads: None (no coefficient gradients; `out`
+        may then be None too) or the five tensors (grad_b0, grad_b1, grad_b2, grad_a1, grad_a2) to be WRITTEN.  Returns
+        (grad_in, grads).  Asynchronous; uses the plan's workspace and its adjoint-state signal (allocated by the first call)."""
+        *p, grad_in, grads, s = self._backward_biquad_arguments(x, b0, b1, b2, a1, a2, out, grad_out, grad_in, grads, stream)
+        capi.check(capi.lib().rf_var2_plan_backward_biquad(self._h, *p, s))
+        return grad_in, grads
+
+    def backward_biquad_timed(self, x, b0, b1, b2, a1, a2, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_biquad_timed: (grad_in, grads, [(kernel name, ms), ...]); synchronises the stream."""
+        *p, grad_in, grads, s = self._backward_biquad_arguments(x, b0, b1, b2, a1, a2, out, grad_out, grad_in, grads, stream)
+        times = _timed(lambda *report: capi.lib().rf_var2_plan_backward_biquad_timed(self._h, *p, s, *report), self.backward_biquad_num_kernels)
+        return grad_in, grads, times
+
+    def apply_biquad(self, x, b0, b1, b2, a1, a2):
+        """execute_biquad as a differentiable torch operation: the values are bit for bit execute_biquad's.  Backward is
+        backward_biquad -- the input's gradient always, the five coefficient gradients where any coefficient signal requires one.
+        x, the five coefficients and the result are saved (no intermediate is); no double backward."""
+        return _biquad_function().apply(self, x, b0, b1, b2, a1, a2)
+
 
 _var2_function = None
+_var2_biquad_function = None
+
+
+def _biquad_function():
+    """the torch.autograd.Function behind Var2Plan.apply_biquad"""
+    global _var2_biquad_function
+    if _var2_biquad_function is not None:
+        return _var2_biquad_function
+    import torch
+
+    class Var2BiquadFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, x, b0, b1, b2, a1, a2):
+            ctx.plan = plan
+            with torch.cuda.device(x.device):
+                out = plan.execute_biquad(x, b0, b1, b2, a1, a2)
+            ctx.save_for_backward(x, b0, b1, b2, a1, a2, out)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            *inputs, out = ctx.saved_tensors
+            need_x, *need = ctx.needs_input_grad[1:7]
+            g = _plan_layout(plan, grad_out)
+            grads = tuple(plan._like(g) for _ in range(5)) if any(need) else None
+            with torch.cuda.device(g.device):
+                gin, grads = plan.backward_biquad(*inputs, out, g, None, grads)
+            grads = grads if grads is not None else (None,) * 5
+            return (None, gin if need_x else None) + tuple(t if wanted else None for t, wanted in zip(grads, need))
+
+    _var2_biquad_function = Var2BiquadFunction
+    return _var2_biquad_function
 
 
 def _function():
@@ -209,6 +318,33 @@ def allpole_scan(x, a1, a2, causal: bool = True):
         where = (0, pad) if causal else (pad, 0)
         x, a1, a2 = (torch.nn.functional.pad(t, where) for t in (x, a1, a2))
     out = plan.apply(*(_plan_layout(plan, t) for t in (x, a1, a2)))
+    if pad:
+        out = out[..., :n] if causal else out[..., pad:]
+    return out
+
+
+def biquad_scan(x, b0, b1, b2, a1, a2, causal: bool = True):
+    """The direct-form-I section with time-varying coefficients,
+        v[n] = b0[n] x[n] + b1[n] x[n-1] + b2[n] x[n-2]        y[n] = v[n] - a1[n] y[n-1] - a2[n] y[n-2]
+    (causal=False: the samples after n) on device tensors of one shape, (N,) or (L, N), f32; every line has its own coefficients.
+    Differentiable in all six.  It shares allpole_scan's plan cache and its padding rule: a length that is no multiple of 4 is
+    padded with zeros in all six signals, behind the end for a causal section, before the start for an anticausal one."""
+    import torch
+    signals = (x, b0, b1, b2, a1, a2)
+    if x.dim() not in (1, 2) or any(tuple(t.shape) != tuple(x.shape) for t in signals):
+        raise ValueError(f"x, b0, b1, b2, a1 and a2 must share one shape (N,) or (L, N), got {[tuple(t.shape) for t in signals]}")
+    n = int(x.shape[-1])
+    lines = 1 if x.dim() == 1 else int(x.shape[0])
+    pad = -n % 4
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (n + pad, lines, bool(causal), device)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = Var2Plan(n + pad, lines=lines, causal=causal, device=device)
+    if pad:
+        where = (0, pad) if causal else (pad, 0)
+        signals = tuple(torch.nn.functional.pad(t, where) for t in signals)
+    out = plan.apply_biquad(*(_plan_layout(plan, t) for t in signals))
     if pad:
         out = out[..., :n] if causal else out[..., pad:]
     return out
