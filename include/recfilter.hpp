@@ -1185,4 +1185,30 @@ public:
     /** 4 */
     int biquad_gradient_num_kernels() { prepare(); return rf_var2_plan_backward_biquad_num_kernels(plan); }
     size_t biquad_gradient_bytes() { prepare(); return rf_var2_plan_backward_biquad_bytes(plan); }
+    /** A cascade of 1 .. RF_VAR2_MAX_SECTIONS such sections in this object's direction (rf_var2_plan_execute_cascade), section
+     *  k + 1 on the result of section k, each with five coefficient signals of its own: 2 K + 1 launches, one link launch per
+     *  boundary between two sections.  out overlaps neither in nor any coefficient signal. */
+    void realize_cascade(const void *in, const std::vector<rf_var2_section> &sections, void *out, void *stream = nullptr) {
+        prepare();
+        if (rf_var2_plan_execute_cascade(plan, in, sections.data(), (int)sections.size(), out, stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize_cascade() (rf_var2_plan_backward_cascade): grad_in from grad_out; `out` is realize_cascade()'s result.
+     *  grads: empty (no coefficient gradients; `out` may then be null) or one rf_var2_section_grad per section, every pointer a
+     *  signal to be written.  grad_in == grad_out is allowed.  Nothing is kept from the forward: the call reruns all sections but
+     *  the last into signals the plan owns (cascade_gradient_bytes()). */
+    void gradient_cascade(const void *in, const std::vector<rf_var2_section> &sections, const void *out, const void *grad_out, void *grad_in,
+                          const std::vector<rf_var2_section_grad> &grads = {}, void *stream = nullptr) {
+        prepare();
+        if (!grads.empty() && grads.size() != sections.size())
+            throw RecFilterError("gradient_cascade: grads is empty or holds one rf_var2_section_grad per section");
+        if (rf_var2_plan_backward_cascade(plan, in, sections.data(), (int)sections.size(), out, grad_out, grad_in,
+                                          grads.empty() ? nullptr : grads.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** 2 K + 1 */
+    int cascade_num_kernels(int sections) { prepare(); return rf_var2_plan_cascade_num_kernels(plan, sections); }
+    /** 4 at K = 1, 6 K - 1 above */
+    int cascade_gradient_num_kernels(int sections) { prepare(); return rf_var2_plan_backward_cascade_num_kernels(plan, sections); }
+    size_t cascade_gradient_bytes(int sections) { prepare(); return rf_var2_plan_backward_cascade_bytes(plan, sections); }
 };

@@ -1022,8 +1022,35 @@ int    rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth
  * is not 16-byte aligned; execute: out overlapping a coefficient signal, then out overlapping in (in == out included); backward:
  * a written gradient overlapping a coefficient signal, in, out, another written gradient, or grad_out other than grad_in exactly
  * (RF_ERR_INVALID_ARG); then a host-only plan (RF_ERR_HIP).  A *_timed call checks ms_out's capacity first.
- * Out of scope for the section: orders above 2; cascades of sections inside one plan; the direct-form-II ordering; images and
- * volumes; 16-bit signals; second derivatives; sharding. */
+ * Out of scope for the section: orders above 2; the direct-form-II ordering; images and volumes; 16-bit signals; second
+ * derivatives; sharding.
+ *
+ * A cascade of sections (rf_var2_plan_execute_cascade): n_sections direct-form-I sections, 1 .. RF_VAR2_MAX_SECTIONS, run one
+ * behind the other in the plan's direction, section k + 1 on the result of section k; every section has five coefficient
+ * signals of its own (rf_var2_section), masked and evaluated as above.  Launches: "var2_biquad_tails_1d", then, per boundary
+ * between two sections, "var2_carry_1d" and "var2_link_1d" -- the final stage of section k, the feed-forward part of section
+ * k + 1 on the tile in registers and the tails stage of section k + 1, v stored in place on out -- then "var2_carry_1d" and
+ * "var2_pass2_1d": rf_var2_plan_cascade_num_kernels(plan, K) = 2 K + 1, and K = 1 is rf_var2_plan_execute_biquad's launches and
+ * bits.  The two samples a link's feed-forward taps reach beyond a tile are the state that enters the tile in section k's final
+ * stage (what its recurrence takes for y[t0-1], y[t0-2]), not a reload: equal to the stored samples up to the rounding of the
+ * carry algebra, exactly where the feedback coefficients are 0.  in == out is refused as for one section; out overlaps no
+ * coefficient signal of any section.
+ * rf_var2_plan_backward_cascade keeps nothing from the forward: for K >= 2 it reruns sections 0 .. K-2 into K - 1 signals of the
+ * plan's ("var2_biquad_tails_1d", K - 2 times "var2_carry_1d" and "var2_link_keep_1d", "var2_carry_1d", "var2_pass2_1d"), then
+ * runs, from the last section to the first, the four launches of rf_var2_plan_backward_biquad, the gradient between two sections
+ * in one more signal of the plan's: rf_var2_plan_backward_cascade_num_kernels(plan, K) = 4 at K = 1 and 6 K - 1 above.  The plan
+ * owns 1 span (K = 1) or K + 1 spans (lam, the gradient between sections, K - 1 results) of 4 * ((n_lines - 1) * stride +
+ * length) bytes, allocated by the first call and regrown when a later call asks for more sections:
+ * rf_var2_plan_backward_cascade_bytes(plan, K); rf_var2_plan_workspace_bytes is unchanged.  grads is null (no coefficient
+ * gradients; out may then be null) or an array of n_sections rf_var2_section_grad with every pointer given.  grad_in == grad_out
+ * is allowed; a written gradient overlaps nothing else.  A call refuses, in this order and before any HIP call: a null plan;
+ * n_sections outside 1 .. 16; null sections; backward: a section of grads with a null pointer ("section k: ..."); a null or
+ * misaligned in, out, grad_out, grad_in ("signal 0: ..."); a null or misaligned coefficient pointer ("section k: ..."); backward: a
+ * misaligned gradient pointer ("section k: ..."); execute: out overlapping a coefficient signal ("coefficient of section k plane
+ * j", j = 0..4 for b0, b1, b2, a1, a2), then in; backward: a written gradient overlapping a coefficient signal, in, out, another
+ * written gradient, or grad_out other than grad_in exactly (RF_ERR_INVALID_ARG); then a host-only plan (RF_ERR_HIP).  A *_timed
+ * call checks ms_out's capacity after the plan and n_sections.  Out of scope: mixed directions inside one cascade (zero-phase
+ * filtering stays two plans); keeping the forward's intermediates for the backward; concurrent calls on one plan. */
 typedef struct rf_var2_plan rf_var2_plan;
 typedef struct {
     uint32_t abi;                     /* RF_ABI                                                  */
@@ -1062,6 +1089,22 @@ int    rf_var2_plan_backward_biquad_timed(rf_var2_plan *plan, const void *in, co
 int    rf_var2_plan_biquad_num_kernels(const rf_var2_plan *plan);
 int    rf_var2_plan_backward_biquad_num_kernels(const rf_var2_plan *plan);
 size_t rf_var2_plan_backward_biquad_bytes(const rf_var2_plan *plan);
+#define RF_VAR2_MAX_SECTIONS 16
+typedef struct { const void *b0, *b1, *b2, *a1, *a2; } rf_var2_section;
+typedef struct { void *b0, *b1, *b2, *a1, *a2; } rf_var2_section_grad;
+int    rf_var2_plan_execute_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out,
+                                    void *stream);
+int    rf_var2_plan_execute_cascade_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                          void *out, void *stream, float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_backward_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                     const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *grads,
+                                     void *stream);
+int    rf_var2_plan_backward_cascade_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                           const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *grads,
+                                           void *stream, float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_cascade_num_kernels(const rf_var2_plan *plan, int n_sections);             /* 0: n_sections out of range */
+int    rf_var2_plan_backward_cascade_num_kernels(const rf_var2_plan *plan, int n_sections);
+size_t rf_var2_plan_backward_cascade_bytes(const rf_var2_plan *plan, int n_sections);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

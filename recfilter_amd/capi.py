@@ -87,6 +87,9 @@ EXPORTED_SYMBOLS = [
     "rf_var2_plan_backward_num_kernels",
     "rf_var2_plan_execute_biquad", "rf_var2_plan_execute_biquad_timed", "rf_var2_plan_backward_biquad", "rf_var2_plan_backward_biquad_timed",
     "rf_var2_plan_biquad_num_kernels", "rf_var2_plan_backward_biquad_num_kernels", "rf_var2_plan_backward_biquad_bytes",
+    "rf_var2_plan_execute_cascade", "rf_var2_plan_execute_cascade_timed", "rf_var2_plan_backward_cascade",
+    "rf_var2_plan_backward_cascade_timed", "rf_var2_plan_cascade_num_kernels", "rf_var2_plan_backward_cascade_num_kernels",
+    "rf_var2_plan_backward_cascade_bytes",
 ]
 
 
@@ -141,6 +144,14 @@ class VarVolumeDesc(ctypes.Structure):
 class Var2SignalDesc(ctypes.Structure):
     _fields_ = [("abi", ctypes.c_uint32), ("length", ctypes.c_int64), ("n_lines", ctypes.c_int32), ("stride", ctypes.c_int64),
                 ("causal", ctypes.c_int32), ("device", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+RF_VAR2_MAX_SECTIONS = 16
+
+
+class Var2Section(ctypes.Structure):
+    """rf_var2_section, and rf_var2_section_grad: five addresses"""
+    _fields_ = [("b0", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("a1", ctypes.c_void_p), ("a2", ctypes.c_void_p)]
 
 
 class SmoothDesc(ctypes.Structure):
@@ -305,6 +316,15 @@ def lib() -> ctypes.CDLL:
     L.rf_var2_plan_backward_biquad_num_kernels.argtypes = [vp]
     L.rf_var2_plan_backward_biquad_bytes.argtypes = [vp]
     L.rf_var2_plan_backward_biquad_bytes.restype = ctypes.c_size_t
+    sp, report = ctypes.POINTER(Var2Section), [fp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
+    L.rf_var2_plan_execute_cascade.argtypes = [vp, vp, sp, ctypes.c_int, vp, vp]
+    L.rf_var2_plan_execute_cascade_timed.argtypes = [vp, vp, sp, ctypes.c_int, vp, vp] + report
+    L.rf_var2_plan_backward_cascade.argtypes = [vp, vp, sp, ctypes.c_int, vp, vp, vp, sp, vp]
+    L.rf_var2_plan_backward_cascade_timed.argtypes = [vp, vp, sp, ctypes.c_int, vp, vp, vp, sp, vp] + report
+    L.rf_var2_plan_cascade_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_bytes.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

@@ -745,6 +745,45 @@ int rf_var2_plan_biquad_num_kernels(const rf_var2_plan *plan) { return plan ? (i
 int rf_var2_plan_backward_biquad_num_kernels(const rf_var2_plan *plan) { return plan ? (int)plan->biquad_backward_names.size() : 0; }
 size_t rf_var2_plan_backward_biquad_bytes(const rf_var2_plan *plan) { return plan ? plan->span_bytes() : 0; }
 
+int rf_var2_plan_cascade_num_kernels(const rf_var2_plan *plan, int n_sections) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_launches(n_sections) : 0;
+}
+int rf_var2_plan_backward_cascade_num_kernels(const rf_var2_plan *plan, int n_sections) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_backward_launches(n_sections) : 0;
+}
+size_t rf_var2_plan_backward_cascade_bytes(const rf_var2_plan *plan, int n_sections) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_backward_bytes(plan, n_sections) : 0;
+}
+
+int rf_var2_plan_execute_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out, void *stream) {
+    return fenced("rf_var2_plan_execute_cascade", [&] {
+        return run_var2_cascade(plan, in, sections, n_sections, out, (hipStream_t)stream, nullptr, nullptr, 0, false);
+    });
+}
+
+int rf_var2_plan_execute_cascade_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out,
+                                       void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_execute_cascade_timed", [&] {
+        return run_var2_cascade(plan, in, sections, n_sections, out, (hipStream_t)stream, ms_out, names_out, capacity, true);
+    });
+}
+
+int rf_var2_plan_backward_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *out,
+                                  const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, void *stream) {
+    return fenced("rf_var2_plan_backward_cascade", [&] {
+        return run_var2_cascade_backward(plan, in, sections, n_sections, out, grad_out, grad_in, grads, (hipStream_t)stream, nullptr, nullptr, 0, false);
+    });
+}
+
+int rf_var2_plan_backward_cascade_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *out,
+                                        const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, void *stream, float *ms_out,
+                                        const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_backward_cascade_timed", [&] {
+        return run_var2_cascade_backward(plan, in, sections, n_sections, out, grad_out, grad_in, grads, (hipStream_t)stream, ms_out, names_out,
+                                         capacity, true);
+    });
+}
+
 int rf_var2_plan_execute_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
                                 const void *a2, void *out, void *stream) {
     return fenced("rf_var2_plan_execute_biquad", [&] { return run_var2_biquad(plan, in, b0, b1, b2, a1, a2, out, (hipStream_t)stream, nullptr); });

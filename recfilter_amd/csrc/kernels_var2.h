@@ -68,6 +68,26 @@ struct Var2BiquadGradArgs {
     int64_t stride;
 };
 
+// The boundary between sections k and k + 1 of a cascade (var2_link_1d, var2_link_keep_1d): x = v_k, what section k's first launch
+// or the link before this one stored; a1, a2 = section k's feedback coefficients; tails and carry hold section k's maps and
+// carries on entry and section k + 1's maps and aggregates on return (a workgroup reads its own slots before it writes them).
+// next_* = section k + 1's five coefficient signals.  dst receives v_{k+1} and may be x (no workgroup reads another's samples);
+// keep, where not null, receives y_k and may be x too.  dst and keep are apart.
+struct Var2LinkArgs {
+    const float *x;
+    const float *a1, *a2;
+    const float *next_b0, *next_b1, *next_b2, *next_a1, *next_a2;
+    float *dst;
+    float *keep;
+    float *tails;
+    const float *carry;
+    int32_t n;
+    int32_t tiles, groups;
+    int32_t n_lines;
+    int32_t causal;
+    int64_t stride;
+};
+
 constexpr int kVar2Tile = 64;            // samples of a tile: one lane
 constexpr int kVar2GroupTiles = 64;      // tiles of a group: one wave
 int launch_var2_tails(const Var2Args &a, hipStream_t stream);      // "var2_tails_1d", "var2_adj_tails_1d"
@@ -77,6 +97,7 @@ int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream);   // "var2_grad
 // the tails launch of a direct-form-I section: v = b0 x + b1~ x[n-1] + b2~ x[n-2] formed in registers and STORED to a.dst, the
 // tails of the all-pole scan on v stored as launch_var2_tails stores them (a.adjoint == 0; a.dst overlaps none of the inputs)
 int launch_var2_biquad_tails(const Var2Args &a, hipStream_t stream);             // "var2_biquad_tails_1d"
+int launch_var2_link(const Var2LinkArgs &a, hipStream_t stream);                 // "var2_link_1d", "var2_link_keep_1d" (a.keep != null)
 int launch_var2_biquad_grad(const Var2BiquadGradArgs &a, hipStream_t stream);    // "var2_biquad_grad_1d"
 
 }  // namespace rf

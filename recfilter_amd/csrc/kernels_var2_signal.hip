@@ -39,6 +39,14 @@
 //                          stores v: out overlaps no input.
 //   var2_biquad_grad_1d    behind the adjoint scan (lam in a signal of the plan's): grad_in and, where asked for, the five
 //                          coefficient gradients, pointwise in lam, x, y and the taps with neighbours from clamped addresses.
+//
+// A cascade of K sections in one plan (rf_var2_plan_execute_cascade): section k + 1 reads what section k stores, and the two
+// samples its feed-forward taps reach beyond a tile are the state that enters the tile in section k's final stage.
+//   var2_link_1d           one launch per boundary between sections: the final stage of section k as var2_pass2_1d runs it (y_k of
+//                          the tile in registers), the feed-forward part of section k + 1 on y_k with the tile's entering state
+//                          (y1, y2) for the near and the far sample beyond the tile, v_{k+1} stored -- in place: no workgroup reads
+//                          another's samples -- and the tails of section k + 1 on it, into the slots the workgroup has just read.
+//   var2_link_keep_1d      the same with y_k stored too (the backward's rerun of the forward keeps every section's output).
 #include "kernels_var2.h"
 
 #include "var_device.h"
@@ -56,6 +64,7 @@ constexpr int kCarryLanes = 1024;                  // groups of a sweep of var2_
 constexpr int kGradLanes = 256;                    // lanes of a workgroup of var2_grad_1d, four samples each
 
 __device__ __forceinline__ int64_t map_index(const Var2Args &a, int comp, int line, int t) { return ((int64_t)comp * a.n_lines + line) * a.tiles + t; }
+__device__ __forceinline__ int64_t map_index_of(int n_lines, int tiles, int comp, int line, int t) { return ((int64_t)comp * n_lines + line) * tiles + t; }
 __device__ __forceinline__ int64_t aggregate_index(const Var2Args &a, int comp, int line, int g) {
     return (int64_t)kVar2Components * a.n_lines * a.tiles + ((int64_t)comp * a.n_lines + line) * a.groups + g;
 }
@@ -294,6 +303,133 @@ __global__ void __launch_bounds__(64) var2_signal_kernel(Var2Args a) {
     }
 }
 
+// ---- the boundary between two sections of a cascade ---------------------------------------------------------------------------------
+// The feed-forward part of the next section on y, the finished tile of this one: feed_forward's arithmetic, order and masks, with
+// the two samples beyond the tile handed in (the state that entered the tile: it is 0 where they lie outside the line).
+template <bool REV>
+__device__ __forceinline__ void link_feed_forward(const Var2LinkArgs &a, float *lds, int64_t first, int n, int s0, int t0, const float (&y)[T],
+                                                  float y_near, float y_far, float (&v)[T]) {
+    float raw[T], b[T];
+    request_group(a.next_b0 + first, n, s0, raw);
+    transpose_in(raw, lds, b);
+#pragma unroll
+    for (int i = 0; i < T; i++) v[i] = (t0 + i < n ? b[i] : 0.0f) * y[i];
+    request_group(a.next_b1 + first, n, s0, raw);
+    transpose_in(raw, lds, b);
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        const float one = REV ? (i + 1 < T ? y[i + 1 < T ? i + 1 : 0] : y_near) : (i >= 1 ? y[i >= 1 ? i - 1 : 0] : y_near);
+        const bool masked = REV ? at >= n - 1 : (at < 1 || at >= n);
+        v[i] = __builtin_fmaf(masked ? 0.0f : b[i], one, v[i]);
+    }
+    request_group(a.next_b2 + first, n, s0, raw);
+    transpose_in(raw, lds, b);
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        const float two = REV ? (i + 2 < T ? y[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? y_near : y_far))
+                              : (i >= 2 ? y[i >= 2 ? i - 2 : 0] : (i == 1 ? y_near : y_far));
+        const bool masked = REV ? at >= n - 2 : (at < 2 || at >= n);
+        v[i] = __builtin_fmaf(masked ? 0.0f : b[i], two, v[i]);
+    }
+}
+
+// the feedback coefficients of a forward stage over the lane's tile, masked by position
+template <bool REV>
+__device__ __forceinline__ void feedback_tiles(const float (&v1)[T], const float (&v2)[T], float *lds, int n, int t0, float (&c1)[T], float (&c2)[T]) {
+    transpose_in(v1, lds, c1);
+    transpose_in(v2, lds, c2);
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        if constexpr (REV) {
+            c1[i] = at >= n - 1 ? 0.0f : c1[i];
+            c2[i] = at >= n - 2 ? 0.0f : c2[i];
+        } else {
+            c1[i] = (at < 1 || at >= n) ? 0.0f : c1[i];
+            c2[i] = (at < 2 || at >= n) ? 0.0f : c2[i];
+        }
+    }
+}
+
+// KEEP: y of the finished section is stored to a.keep (it may be a.x: the group has loaded all of it)
+template <bool REV, bool KEEP>
+__global__ void __launch_bounds__(64) var2_link_kernel(Var2LinkArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x, line = blockIdx.y;
+    const int n = a.n;
+    const int s0 = g * kGroupSamples;                 // below 2^30 + 4096
+    const int t = g * kGroupTiles + lane, t0 = t * T;
+    const int64_t first = (int64_t)line * a.stride;
+    float y[T], v[T];
+    float y_near, y_far;
+    // the final stage of the section behind the boundary: var2_pass2_1d's, y kept in registers
+    {
+        float vx[T], v1[T], v2[T], c1[T], c2[T];
+        request_group(a.x + first, n, s0, vx);
+        request_group(a.a1 + first, n, s0, v1);
+        request_group(a.a2 + first, n, s0, v2);
+        const int tt = min(t, a.tiles - 1);
+        float m[kVar2Components], y1, y2;
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index_of(a.n_lines, a.tiles, i, line, tt)];
+        apply_map(m, a.carry[((int64_t)0 * a.n_lines + line) * a.groups + g], a.carry[((int64_t)1 * a.n_lines + line) * a.groups + g], y1, y2);
+        y_near = y1; y_far = y2;                      // y one and two samples before the tile, in the order of the recurrence
+        transpose_in(vx, lds, y);
+        feedback_tiles<REV>(v1, v2, lds, n, t0, c1, c2);
+#pragma unroll
+        for (int i = 0; i < T; i++) y[i] = t0 + i < n ? y[i] : 0.0f;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const int i = REV ? T - 1 - j : j;
+            const float r = step2(c1[i], c2[i], y[i], y1, y2);
+            y[i] = r; y2 = y1; y1 = r;
+        }
+    }
+    if constexpr (KEEP) {
+        store_group(lds, a.keep + first, n, s0, y);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < T; i++) y[i] = t0 + i < n ? y[i] : 0.0f;
+    __builtin_amdgcn_sched_barrier(0);
+    // the section in front of the boundary: its feed-forward part on y, then its tails stage
+    link_feed_forward<REV>(a, lds, first, n, s0, t0, y, y_near, y_far, v);
+    float v1[T], v2[T], c1[T], c2[T];
+    request_group(a.next_a1 + first, n, s0, v1);
+    request_group(a.next_a2 + first, n, s0, v2);
+    store_group(lds, a.dst + first, n, s0, v);
+    __syncthreads();
+    feedback_tiles<REV>(v1, v2, lds, n, t0, c1, c2);
+    __builtin_amdgcn_sched_barrier(0);
+    float y1 = 0.0f, y2 = 0.0f, u1 = 1.0f, u2 = 0.0f, w1 = 0.0f, w2 = 1.0f;
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        const int i = REV ? T - 1 - j : j;
+        const float r = step2(c1[i], c2[i], v[i], y1, y2);
+        const float u = step2(c1[i], c2[i], 0.0f, u1, u2);
+        const float w = step2(c1[i], c2[i], 0.0f, w1, w2);
+        y2 = y1; y1 = r; u2 = u1; u1 = u; w2 = w1; w1 = w;
+    }
+    float own[kVar2Components], map[kVar2Components], whole[kVar2Components];
+    own[VAR2_E0] = y1; own[VAR2_E1] = y2;
+    own[VAR2_P00] = u1; own[VAR2_P10] = u2;
+    own[VAR2_P01] = w1; own[VAR2_P11] = w2;
+    scan_group<REV>(own, map, whole);
+    if (t < a.tiles) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) a.tails[map_index_of(a.n_lines, a.tiles, i, line, t)] = map[i];
+    }
+    if (lane == (REV ? 0 : 63)) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++)
+            a.tails[(int64_t)kVar2Components * a.n_lines * a.tiles + ((int64_t)i * a.n_lines + line) * a.groups + g] = whole[i];
+    }
+}
+
 // ---- the recurrence over groups: one workgroup per line ---------------------------------------------------------------------------
 // A sweep takes blockDim.x groups in the order of the recurrence (REV: from the last group down), lane i the i-th of them.  Within a
 // sweep: an inclusive wave scan of the aggregates, the waves' totals through LDS, every lane folding the totals of the waves before
@@ -478,6 +614,18 @@ int launch_var2_biquad_tails(const Var2Args &a, hipStream_t stream) {
     if (a.causal) hipLaunchKernelGGL((var2_signal_kernel<false, false, false, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var2_signal_kernel<true, false, false, true>), grid, block, 0, stream, a);
     return launched("var2_biquad_tails_1d");
+}
+
+int launch_var2_link(const Var2LinkArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.keep) {
+        if (a.causal) hipLaunchKernelGGL((var2_link_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_link_kernel<true, true>), grid, block, 0, stream, a);
+        return launched("var2_link_keep_1d");
+    }
+    if (a.causal) hipLaunchKernelGGL((var2_link_kernel<false, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_link_kernel<true, false>), grid, block, 0, stream, a);
+    return launched("var2_link_1d");
 }
 
 int launch_var2_biquad_grad(const Var2BiquadGradArgs &a, hipStream_t stream) {

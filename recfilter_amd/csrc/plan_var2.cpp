@@ -10,7 +10,8 @@
 //              read shifted: grad_in = lam.  With coefficient gradients, var2_grad_1d then reads lam from grad_in and y from `out`.
 // The adjoint uses the forward's workspace and nothing else: the caller hands back the forward's result.
 // The direct-form-I section (run_var2_biquad, run_var2_biquad_backward: the feed-forward taps in front of the scan) stands at the
-// end of the file; its backward keeps the adjoint state in one signal the plan allocates in the first such call.
+// end of the file; its backward keeps the adjoint state in one signal the plan allocates in the first such call.  Behind it, the
+// cascade of sections (run_var2_cascade, run_var2_cascade_backward): one link launch per boundary between two sections.
 #include "plan_var2.h"
 
 #include <memory>
@@ -18,6 +19,7 @@
 rf_var2_plan::~rf_var2_plan() {
     if (workspace) (void)hipFree(workspace);
     if (lam) (void)hipFree(lam);
+    if (cascade) (void)hipFree(cascade);
 }
 
 namespace rf {
@@ -269,6 +271,247 @@ int run_var2_biquad_backward(rf_var2_plan *plan, const void *in, const void *b0,
         g.grad_b2 = (float *)grad_b2;
         g.grad_a1 = (float *)grad_a1;
         g.grad_a2 = (float *)grad_a2;
+        g.n = (int32_t)plan->length;
+        g.n_lines = plan->n_lines;
+        g.causal = plan->causal ? 1 : 0;
+        g.with_coefficients = with_coefficients ? 1 : 0;
+        g.stride = plan->stride;
+        rc = launch_var2_biquad_grad(g, stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+// ---- a cascade of direct-form-I sections -------------------------------------------------------------------------------------------
+//   forward    var2_biquad_tails_1d (v_0 to out), then per boundary var2_carry_1d and var2_link_1d (the final stage of section k,
+//              the feed-forward part and the tails of section k + 1, v_{k+1} to out in place), then var2_carry_1d, var2_pass2_1d.
+//   backward   keeps nothing from the forward.  K >= 2: sections 0 .. K-2 are rerun into the plan's signals I_0 .. I_{K-2} (the
+//              link's KEEP instance stores y_k over v_k in I_k and v_{k+1} to I_{k+1}); then, from the last section to the first,
+//              the three adjoint launches on g_k into lam and var2_biquad_grad_1d with x = y_{k-1}, y = y_k, the gradient
+//              between two sections in one more signal of the plan's (the grad launch reads lam, never g_k: one buffer serves).
+namespace {
+
+constexpr const char *kSectionCount = "n_sections must be 1..%lld (got %lld)";
+
+Var2LinkArgs link_args(const rf_var2_plan *plan, const float *x, const rf_var2_section &done, const rf_var2_section &next, float *dst, float *keep) {
+    Var2LinkArgs l{};
+    l.x = x;
+    l.a1 = (const float *)done.a1;
+    l.a2 = (const float *)done.a2;
+    l.next_b0 = (const float *)next.b0;
+    l.next_b1 = (const float *)next.b1;
+    l.next_b2 = (const float *)next.b2;
+    l.next_a1 = (const float *)next.a1;
+    l.next_a2 = (const float *)next.a2;
+    l.dst = dst;
+    l.keep = keep;
+    l.tails = plan->workspace;
+    l.carry = plan->workspace + plan->tails_floats();
+    l.n = (int32_t)plan->length;
+    l.tiles = (int32_t)plan->tiles;
+    l.groups = (int32_t)plan->groups;
+    l.n_lines = plan->n_lines;
+    l.causal = plan->causal ? 1 : 0;
+    l.stride = plan->stride;
+    return l;
+}
+
+// Sections 0 .. count-1 on `in`.  signals == nullptr: every v and the result in `out`, in place.  Else section k's v, then its
+// result, in signals[k] (count of them).
+int launch_sections(const rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int count, float *out, float *const *signals,
+                    hipStream_t stream, LaunchTimer &timer) {
+    Var2Args a = scan_args(plan, plan->causal, false);
+    a.x = (const float *)in;
+    a.b0 = (const float *)sections[0].b0;
+    a.b1 = (const float *)sections[0].b1;
+    a.b2 = (const float *)sections[0].b2;
+    a.a1 = (const float *)sections[0].a1;
+    a.a2 = (const float *)sections[0].a2;
+    a.dst = signals ? signals[0] : out;
+    int rc = launch_var2_biquad_tails(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    for (int k = 1; k < count && rc == RF_OK; k++) {
+        rc = launch_var2_carry(a, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        float *from = signals ? signals[k - 1] : out, *to = signals ? signals[k] : out;
+        if (rc == RF_OK) rc = launch_var2_link(link_args(plan, from, sections[k - 1], sections[k], to, signals ? from : nullptr), stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
+    a.x = a.dst = signals ? signals[count - 1] : out;
+    a.a1 = (const float *)sections[count - 1].a1;
+    a.a2 = (const float *)sections[count - 1].a2;
+    if (rc == RF_OK) rc = launch_var2_carry(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK) rc = launch_var2_pass2(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    return rc;
+}
+
+int check_sections(const rf_var2_section *sections, int n_sections) {
+    for (int k = 0; k < n_sections; k++) {
+        const rf_var2_section &s = sections[k];
+        int rc = check_plane("section", k, {{s.b0}, {s.b1}, {s.b2}, {s.a1}, {s.a2}}, 15u, "null pointer (b0, b1, b2, a1, a2)",
+                             "the var2 scans need 16-byte aligned pointers");
+        if (rc != RF_OK) return rc;
+    }
+    return RF_OK;
+}
+
+// the coefficient signals of every section as lists of read planes: "coefficient of section k plane j"
+struct SectionLists {
+    std::vector<std::string> nouns;
+    std::vector<const void *> planes;
+    SectionLists(const char *what, int n) {
+        nouns.reserve(n);
+        planes.reserve((size_t)5 * n);
+        for (int k = 0; k < n; k++) nouns.push_back(std::string(what) + " of section " + std::to_string(k));
+    }
+    PlaneList list(int k, int count, size_t bytes, const char *why = "") const { return {nouns[k].c_str(), planes.data() + 5 * k, count, bytes, why}; }
+};
+
+}  // namespace
+
+const char *var2_cascade_name(int n_sections, size_t i) {
+    if (i == 0) return "var2_biquad_tails_1d";
+    if (i + 1 == (size_t)var2_cascade_launches(n_sections)) return "var2_pass2_1d";
+    return i % 2 == 1 ? "var2_carry_1d" : "var2_link_1d";
+}
+
+const char *var2_cascade_backward_name(int n_sections, size_t i) {
+    static const char *const section[4] = {"var2_adj_tails_1d", "var2_carry_1d", "var2_adj_pass2_1d", "var2_biquad_grad_1d"};
+    const size_t rerun = n_sections == 1 ? 0 : (size_t)var2_cascade_launches(n_sections - 1);
+    if (i >= rerun) return section[(i - rerun) % 4];
+    if (i == 0) return "var2_biquad_tails_1d";
+    if (i + 1 == rerun) return "var2_pass2_1d";
+    return i % 2 == 1 ? "var2_carry_1d" : "var2_link_keep_1d";
+}
+
+int run_var2_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out, hipStream_t stream,
+                     float *ms_out, const char **names_out, int capacity, bool timed) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
+    const size_t launches = (size_t)var2_cascade_launches(n_sections);
+    if (timed) {
+        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_name(n_sections, i); }, ms_out, names_out, capacity);
+        if (rc != RF_OK) return rc;
+    }
+    if (!sections) return refuse(RF_ERR_INVALID_ARG, "null sections");
+    int rc = check_plane("signal", 0, {{in}, {out}}, 15u, "null pointer (in, out)", "the var2 scans need 16-byte aligned pointers");
+    if (rc == RF_OK) rc = check_sections(sections, n_sections);
+    if (rc != RF_OK) return rc;
+    const size_t bytes = plan->span_bytes();
+    SectionLists coefficients("coefficient", n_sections);
+    for (int k = 0; k < n_sections; k++)
+        coefficients.planes.insert(coefficients.planes.end(), {sections[k].b0, sections[k].b1, sections[k].b2, sections[k].a1, sections[k].a2});
+    std::vector<PlaneList> read;
+    for (int k = 0; k < n_sections; k++) read.push_back(coefficients.list(k, 5, bytes, ": a coefficient signal is read while outputs are stored"));
+    const void *const written[1] = {out}, *const input[1] = {in};
+    read.push_back({"in", input, 1, bytes,
+                    ": in == out is not allowed for a biquad (the first launch stores the feed-forward part while neighbouring groups still read in)"});
+    const PlaneList w = {"out", written, 1, bytes};
+    rc = check_written_planes(&w, 1, read.data(), (int)read.size(), {"grad_out", nullptr, 0, bytes});
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    LaunchTimer timer(stream, ms_out, launches);
+    if (timer.status() != RF_OK) return timer.status();
+    rc = launch_sections(plan, in, sections, n_sections, (float *)out, nullptr, stream, timer);
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+int run_var2_cascade_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *out,
+                              const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, hipStream_t stream, float *ms_out,
+                              const char **names_out, int capacity, bool timed) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
+    const int K = n_sections;
+    const size_t launches = (size_t)var2_cascade_backward_launches(K);
+    if (timed) {
+        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_backward_name(K, i); }, ms_out, names_out, capacity);
+        if (rc != RF_OK) return rc;
+    }
+    if (!sections) return refuse(RF_ERR_INVALID_ARG, "null sections");
+    const bool with_coefficients = grads != nullptr;
+    for (int k = 0; with_coefficients && k < K; k++) {
+        const rf_var2_section_grad &g = grads[k];
+        const int given = (g.b0 != nullptr) + (g.b1 != nullptr) + (g.b2 != nullptr) + (g.a1 != nullptr) + (g.a2 != nullptr);
+        if (given != 5)
+            return refuse(RF_ERR_INVALID_ARG, "section %lld: the five coefficient gradients are all given, or grads is null (%lld given)", k, given);
+    }
+    int rc = check_plane("signal", 0, {{in}, {grad_out}, {grad_in}, {out, with_coefficients}}, 15u,
+                         "null pointer (in, grad_out, grad_in; out where coefficient gradients are asked for)",
+                         "the var2 scans need 16-byte aligned pointers");
+    if (rc == RF_OK) rc = check_sections(sections, K);
+    for (int k = 0; rc == RF_OK && with_coefficients && k < K; k++)
+        rc = check_plane("section", k, {{grads[k].b0}, {grads[k].b1}, {grads[k].b2}, {grads[k].a1}, {grads[k].a2}}, 15u,
+                         "null gradient pointer", "the var2 scans need 16-byte aligned pointers (a coefficient gradient)");
+    if (rc != RF_OK) return rc;
+    const size_t bytes = plan->span_bytes();
+    SectionLists coefficients("coefficient", K), gradients("gradient", K);
+    for (int k = 0; k < K; k++) {
+        coefficients.planes.insert(coefficients.planes.end(), {sections[k].b0, sections[k].b1, sections[k].b2, sections[k].a1, sections[k].a2});
+        if (with_coefficients) gradients.planes.insert(gradients.planes.end(), {grads[k].b0, grads[k].b1, grads[k].b2, grads[k].a1, grads[k].a2});
+    }
+    const void *const gin[1] = {grad_in}, *const input[1] = {in}, *const result[1] = {out}, *const gout[1] = {grad_out};
+    std::vector<PlaneList> written, read;
+    written.push_back({"grad_in", gin, 1, bytes});
+    for (int k = 0; with_coefficients && k < K; k++) written.push_back(gradients.list(k, 5, bytes));
+    for (int k = 0; k < K; k++) read.push_back(coefficients.list(k, 5, bytes, ": a coefficient signal is read while outputs are stored"));
+    read.push_back({"in", input, 1, bytes});
+    read.push_back({"out", result, with_coefficients ? 1 : 0, bytes});
+    rc = check_written_planes(written.data(), (int)written.size(), read.data(), (int)read.size(), {"grad_out", gout, 1, bytes});
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    if (!plan->lam && hipMalloc((void **)&plan->lam, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->lam = nullptr;
+        set_error("hipMalloc of %zu bytes for the adjoint state of the cascade's backward failed", bytes);
+        return RF_ERR_NOMEM;
+    }
+    if (K >= 2 && plan->cascade_spans < K) {
+        // (hipFree waits for the device: no earlier call on this plan still uses the signals)
+        if (plan->cascade) (void)hipFree(plan->cascade);
+        plan->cascade = nullptr;
+        plan->cascade_spans = 0;
+        if (hipMalloc((void **)&plan->cascade, bytes * (size_t)K) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->cascade = nullptr;
+            set_error("hipMalloc of %zu bytes for the signals of the cascade's backward failed", bytes * (size_t)K);
+            return RF_ERR_NOMEM;
+        }
+        plan->cascade_spans = K;
+    }
+    LaunchTimer timer(stream, ms_out, launches);
+    if (timer.status() != RF_OK) return timer.status();
+    const size_t span_floats = bytes / sizeof(float);
+    float *between = plan->cascade;                   // g_{k-1}, K >= 2
+    float *results[RF_VAR2_MAX_SECTIONS] = {};        // y_0 .. y_{K-2}
+    for (int k = 0; k + 1 < K; k++) results[k] = plan->cascade + (size_t)(k + 1) * span_floats;
+    if (K >= 2) rc = launch_sections(plan, in, sections, K - 1, nullptr, results, stream, timer);
+    for (int k = K - 1; k >= 0 && rc == RF_OK; k--) {
+        Var2Args a = scan_args(plan, !plan->causal, true);
+        a.x = k == K - 1 ? (const float *)grad_out : between;
+        a.a1 = (const float *)sections[k].a1;
+        a.a2 = (const float *)sections[k].a2;
+        a.dst = plan->lam;
+        rc = launch_scan(a, stream, timer);
+        if (rc != RF_OK) break;
+        Var2BiquadGradArgs g{};
+        g.lam = plan->lam;
+        g.x = k == 0 ? (const float *)in : results[k - 1];
+        g.y = k == K - 1 ? (const float *)out : results[k];
+        g.b0 = (const float *)sections[k].b0;
+        g.b1 = (const float *)sections[k].b1;
+        g.b2 = (const float *)sections[k].b2;
+        g.grad_in = k == 0 ? (float *)grad_in : between;
+        if (with_coefficients) {
+            g.grad_b0 = (float *)grads[k].b0;
+            g.grad_b1 = (float *)grads[k].b1;
+            g.grad_b2 = (float *)grads[k].b2;
+            g.grad_a1 = (float *)grads[k].a1;
+            g.grad_a2 = (float *)grads[k].a2;
+        }
         g.n = (int32_t)plan->length;
         g.n_lines = plan->n_lines;
         g.causal = plan->causal ? 1 : 0;

@@ -28,6 +28,11 @@ struct rf_var2_plan {
     // lives in one signal of the plan's span, allocated by the first backward call
     float *lam = nullptr;
     std::vector<std::string> biquad_names, biquad_backward_names;
+    // a cascade's backward (rf_var2_plan_backward_cascade) with two sections or more: `cascade_spans` further signals of the
+    // plan's span in one allocation -- the gradient between two sections, then the results of all sections but the last --
+    // allocated by the first such call and regrown when a later one asks for more sections
+    float *cascade = nullptr;
+    int cascade_spans = 0;
     ~rf_var2_plan();
 };
 
@@ -42,4 +47,17 @@ int run_var2_biquad(rf_var2_plan *plan, const void *in, const void *b0, const vo
 int run_var2_biquad_backward(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1, const void *a2,
                              const void *out, const void *grad_out, void *grad_in, void *grad_b0, void *grad_b1, void *grad_b2, void *grad_a1,
                              void *grad_a2, hipStream_t stream, float *ms_out);
+// a cascade of n_sections direct-form-I sections: the launches' names (string literals), counts and the backward's memory
+const char *var2_cascade_name(int n_sections, size_t i);
+const char *var2_cascade_backward_name(int n_sections, size_t i);
+inline int var2_cascade_launches(int n_sections) { return 2 * n_sections + 1; }
+inline int var2_cascade_backward_launches(int n_sections) { return n_sections == 1 ? 4 : 6 * n_sections - 1; }
+inline size_t var2_cascade_backward_bytes(const rf_var2_plan *plan, int n_sections) {
+    return plan->span_bytes() * (size_t)(n_sections == 1 ? 1 : n_sections + 1);
+}
+int run_var2_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out, hipStream_t stream,
+                     float *ms_out, const char **names_out, int capacity, bool timed);
+int run_var2_cascade_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *out,
+                              const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, hipStream_t stream, float *ms_out,
+                              const char **names_out, int capacity, bool timed);
 }  // namespace rf

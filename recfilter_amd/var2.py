@@ -14,11 +14,16 @@ The whole direct-form-I section runs on the same plans (rf_var2_plan_execute_biq
 
 `Var2Plan.execute_biquad`, `backward_biquad` (the input's gradient and, where asked for, all five coefficient gradients),
 `apply_biquad` and `biquad_scan` behind torch.autograd.
+
+A cascade of K such sections, each with five coefficient signals of its own, runs in 2 K + 1 launches on one plan
+(rf_var2_plan_execute_cascade / _backward_cascade): `Var2Plan.execute_cascade`, `backward_cascade`, `apply_cascade` and
+`biquad_cascade`.  Autograd saves x, the coefficients and the result -- no intermediate signal: the backward reruns the sections
+into signals the plan owns.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict
+from typing import Dict, Sequence
 
 from . import capi
 from .capi import _PlanHandle, _timed
@@ -211,8 +216,132 @@ class Var2Plan(_PlanHandle):
         return _biquad_function().apply(self, x, b0, b1, b2, a1, a2)
 
 
+    # -- a cascade of sections ------------------------------------------------------------------
+    #     sections: K tuples (b0, b1, b2, a1, a2), 1 <= K <= 16; section k + 1 runs on the result of section k, all in the plan's direction
+    def cascade_num_kernels(self, sections: int) -> int:
+        """2 K + 1 launches"""
+        return int(capi.lib().rf_var2_plan_cascade_num_kernels(self._h, int(sections)))
+
+    def backward_cascade_num_kernels(self, sections: int) -> int:
+        """4 launches at K = 1, 6 K - 1 above: the rerun of K - 1 sections, then four launches per section"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_num_kernels(self._h, int(sections)))
+
+    def backward_cascade_bytes(self, sections: int) -> int:
+        """what the plan owns behind a backward_cascade of K sections: 1 span at K = 1, K + 1 above, of 4 * ((lines - 1) * stride + length)"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_bytes(self._h, int(sections)))
+
+    def _section_array(self, sections, what: str):
+        """(the rf_var2_section array or None, K).  Host-only: addresses that pass the library's checks, never dereferenced"""
+        if sections is None:
+            return None, 0
+        K = len(sections)
+        array = (capi.Var2Section * max(K, 1))()
+        for k, s in enumerate(sections):
+            if len(s) != 5:
+                raise ValueError(f"{what}[{k}]: the five signals (b0, b1, b2, a1, a2)")
+            for name, t in zip(("b0", "b1", "b2", "a1", "a2"), s):
+                setattr(array[k], name, self._pointer(t, f"{what}[{k}].{name}").value)
+        return array, K
+
+    def _cascade_arguments(self, x, sections, out, stream):
+        if self._host_only:
+            K = len(sections)
+            p = self._placeholders(2 + 5 * K)
+            array = (capi.Var2Section * max(K, 1))(*(capi.Var2Section(*(q.value for q in p[2 + 5 * k:7 + 5 * k])) for k in range(K)))
+            return p[0], array, K, p[1], None, ctypes.c_void_p()
+        if out is None:
+            out = self._like(x)
+        array, K = self._section_array(sections, "sections")
+        return self._pointer(x, "x"), array, K, self._pointer(out, "out"), out, self._stream(stream)
+
+    def execute_cascade(self, x, sections: Sequence, out=None, stream=None):
+        """rf_var2_plan_execute_cascade: asynchronous on `stream` (default: torch's current stream).  out=None allocates the output;
+        out may NOT be x.  One section is execute_biquad's launches and bits."""
+        px, array, K, po, out, s = self._cascade_arguments(x, sections, out, stream)
+        capi.check(capi.lib().rf_var2_plan_execute_cascade(self._h, px, array, K, po, s))
+        return out
+
+    def execute_cascade_timed(self, x, sections: Sequence, out=None, stream=None):
+        """rf_var2_plan_execute_cascade_timed: (output, [(kernel name, ms), ...]); synchronises the stream."""
+        px, array, K, po, out, s = self._cascade_arguments(x, sections, out, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_execute_cascade_timed(self._h, px, array, K, po, s, *report)      # noqa: E731
+        return out, _timed(call, self.cascade_num_kernels(K))
+
+    def _backward_cascade_arguments(self, x, sections, out, grad_out, grad_in, grads, stream):
+        if grads is not None and len(grads) != len(sections):
+            raise ValueError("grads: one tuple (grad_b0, grad_b1, grad_b2, grad_a1, grad_a2) per section, or None")
+        if self._host_only:
+            K = len(sections)
+            p = self._placeholders(4 + 5 * K)
+            array = (capi.Var2Section * max(K, 1))(*(capi.Var2Section(*(q.value for q in p[4 + 5 * k:9 + 5 * k])) for k in range(K)))
+            return p[0], array, K, p[1], p[2], p[3], None, None, grads, ctypes.c_void_p()
+        if grad_in is None:
+            grad_in = self._like(grad_out)
+        array, K = self._section_array(sections, "sections")
+        garray, _ = self._section_array(grads, "grads")
+        return (self._pointer(x, "x"), array, K, self._pointer(out, "out"), self._pointer(grad_out, "grad_out"),
+                self._pointer(grad_in, "grad_in"), garray, grad_in, grads, self._stream(stream))
+
+    def backward_cascade(self, x, sections: Sequence, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_cascade, the adjoint of execute_cascade: grad_in = dL/dx from grad_out = dL/d(out); `out` is
+        execute_cascade's result.  grad_in=None allocates it; it may be grad_out itself.  grads: None (no coefficient gradients;
+        `out` may then be None too) or K tuples of five tensors to be WRITTEN.  Returns (grad_in, grads).  Asynchronous; nothing is
+        kept from the forward: the call reruns all sections but the last into signals of the plan's (backward_cascade_bytes)."""
+        px, array, K, po, pgo, pgi, garray, grad_in, grads, s = self._backward_cascade_arguments(x, sections, out, grad_out, grad_in, grads, stream)
+        capi.check(capi.lib().rf_var2_plan_backward_cascade(self._h, px, array, K, po, pgo, pgi, garray, s))
+        return grad_in, grads
+
+    def backward_cascade_timed(self, x, sections: Sequence, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_cascade_timed: (grad_in, grads, [(kernel name, ms), ...]); synchronises the stream."""
+        px, array, K, po, pgo, pgi, garray, grad_in, grads, s = self._backward_cascade_arguments(x, sections, out, grad_out, grad_in, grads, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_backward_cascade_timed(self._h, px, array, K, po, pgo, pgi, garray, s, *report)      # noqa: E731
+        return grad_in, grads, _timed(call, self.backward_cascade_num_kernels(K))
+
+    def apply_cascade(self, x, sections: Sequence):
+        """execute_cascade as a differentiable torch operation: the values are bit for bit execute_cascade's.  Backward is
+        backward_cascade -- the input's gradient always, all 5 K coefficient gradients where any coefficient signal requires one.
+        x, the coefficients and the result are saved, no intermediate signal; no double backward."""
+        return _cascade_function().apply(self, x, *(t for s in sections for t in s))
+
+
 _var2_function = None
 _var2_biquad_function = None
+_var2_cascade_function = None
+
+
+def _cascade_function():
+    """the torch.autograd.Function behind Var2Plan.apply_cascade: (plan, x, then the 5 K coefficient signals section by section)"""
+    global _var2_cascade_function
+    if _var2_cascade_function is not None:
+        return _var2_cascade_function
+    import torch
+
+    class Var2CascadeFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, x, *coefficients):
+            ctx.plan = plan
+            sections = [coefficients[i:i + 5] for i in range(0, len(coefficients), 5)]
+            with torch.cuda.device(x.device):
+                out = plan.execute_cascade(x, sections)
+            ctx.save_for_backward(x, *coefficients, out)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            x, *coefficients, out = ctx.saved_tensors
+            sections = [coefficients[i:i + 5] for i in range(0, len(coefficients), 5)]
+            need_x, *need = ctx.needs_input_grad[1:]
+            g = _plan_layout(plan, grad_out)
+            grads = [tuple(plan._like(g) for _ in range(5)) for _ in sections] if any(need) else None
+            with torch.cuda.device(g.device):
+                gin, grads = plan.backward_cascade(x, sections, out, g, None, grads)
+            given = [t for s in grads for t in s] if grads is not None else [None] * len(coefficients)
+            return (None, gin if need_x else None) + tuple(t if wanted else None for t, wanted in zip(given, need))
+
+    _var2_cascade_function = Var2CascadeFunction
+    return _var2_cascade_function
 
 
 def _biquad_function():
@@ -345,6 +474,38 @@ def biquad_scan(x, b0, b1, b2, a1, a2, causal: bool = True):
         where = (0, pad) if causal else (pad, 0)
         signals = tuple(torch.nn.functional.pad(t, where) for t in signals)
     out = plan.apply_biquad(*(_plan_layout(plan, t) for t in signals))
+    if pad:
+        out = out[..., :n] if causal else out[..., pad:]
+    return out
+
+
+def biquad_cascade(x, sections: Sequence, causal: bool = True):
+    """K direct-form-I sections with time-varying coefficients, one behind the other in one direction, in 2 K + 1 launches:
+    `sections` is a sequence of K tuples (b0, b1, b2, a1, a2), 1 <= K <= 16, every signal a device tensor shaped like x, (N,) or
+    (L, N), f32.  Differentiable in x and all 5 K coefficient signals; autograd keeps no signal between the sections.  It shares
+    biquad_scan's plan cache and padding rule: a length that is no multiple of 4 is padded with zeros in every signal, behind the
+    end for causal sections, before the start for anticausal ones (a padded section maps zeros to zeros and the recurrence
+    reaches the padding last, so the real samples are the unpadded cascade's)."""
+    import torch
+    sections = [tuple(s) for s in sections]
+    if not 1 <= len(sections) <= capi.RF_VAR2_MAX_SECTIONS or any(len(s) != 5 for s in sections):
+        raise ValueError(f"sections: 1..{capi.RF_VAR2_MAX_SECTIONS} tuples (b0, b1, b2, a1, a2)")
+    signals = (x,) + tuple(t for s in sections for t in s)
+    if x.dim() not in (1, 2) or any(tuple(t.shape) != tuple(x.shape) for t in signals):
+        raise ValueError(f"x and every coefficient signal must share one shape (N,) or (L, N), got {sorted({tuple(t.shape) for t in signals})}")
+    n = int(x.shape[-1])
+    lines = 1 if x.dim() == 1 else int(x.shape[0])
+    pad = -n % 4
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (n + pad, lines, bool(causal), device)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = Var2Plan(n + pad, lines=lines, causal=causal, device=device)
+    if pad:
+        where = (0, pad) if causal else (pad, 0)
+        signals = tuple(torch.nn.functional.pad(t, where) for t in signals)
+    signals = [_plan_layout(plan, t) for t in signals]
+    out = plan.apply_cascade(signals[0], [signals[1 + 5 * k:6 + 5 * k] for k in range(len(sections))])
     if pad:
         out = out[..., :n] if causal else out[..., pad:]
     return out
