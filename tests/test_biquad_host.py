@@ -12,7 +12,9 @@ import pytest
 import biquad_cases as cases
 import biquad_emulator as emu
 import biquad_loops as loops
+import var2_cases
 import var2_emulator
+import var2_exact as exact
 import recfilter_amd as rfa
 from recfilter_amd import capi
 
@@ -114,23 +116,52 @@ def test_padding_rule_of_biquad_scan(n, causal):
 
 # ---- the emulator ---------------------------------------------------------------------------------------------------------------
 GPU_CASES = ([(n, 1, kind) for n in cases.LENGTHS for kind in cases.KINDS] + [(n, lines, "resonator") for lines, n, _ in cases.LINE_CASES]
-             + [(cases.LONG, 1, "sprinkled")])
+             + [(cases.LONG, 1, "sprinkled")] + cases.LONG_MEMORY_CASES)
 
 
-@pytest.mark.parametrize("causal", DIRECTIONS)
-@pytest.mark.parametrize("n,lines,kind", GPU_CASES)
-def test_emulator_under_the_bar_on_every_gpu_case(n, lines, kind, causal):
-    """what makes the GPU tests ones the algebra itself passes: forward and all six gradients of the numpy f32 replay"""
-    signals = cases.case(n, lines, kind, causal)
-    want = cases.expected(n, lines, kind, causal)
+def replay(signals, causal):
+    lines, n = signals[0].shape
     got = {name: np.empty((lines, n), np.float32) for name in cases.NAMES}
     for l in range(lines):
         one = [s[l] for s in signals]
         y = emu.tiled_forward(*one[:6], causal)
         for name, r in zip(cases.NAMES, (y, *emu.tiled_adjoint(*one[:6], y, one[6], causal))):
             got[name][l] = r
+    return got
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n,lines,kind", GPU_CASES)
+def test_emulator_under_the_bar_on_every_gpu_case(n, lines, kind, causal):
+    """what makes the GPU tests ones the algebra itself passes: forward and all six gradients of the numpy f32 replay"""
+    want = cases.expected(n, lines, kind, causal)
+    got = replay(cases.case(n, lines, kind, causal), causal)
     for name in cases.NAMES:
         cases.assert_under_bar(got[name], want[name], f"emulator {n} x {lines} {kind} {name_of(causal)} {name}")
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n,lines,kind", cases.LONG_MEMORY_CASES)
+def test_emulator_under_half_the_bar_on_every_long_memory_case(n, lines, kind, causal):
+    """the condition the seeds of cases.LONG_MEMORY_SEEDS were chosen by"""
+    assert set(cases.LONG_MEMORY_SEEDS) == {(n, kind, c) for n, _, kind in cases.LONG_MEMORY_CASES for c in DIRECTIONS}
+    want = cases.expected(n, lines, kind, causal)
+    got = replay(cases.case(n, lines, kind, causal), causal)
+    for name in cases.NAMES:
+        var2_cases.assert_under_half_the_bar(got[name], want[name], f"emulator {n} x {lines} {kind} {name_of(causal)} {name}")
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("family", list(exact.FAMILIES))
+@pytest.mark.parametrize("n", exact.LENGTHS[:2])
+def test_emulator_is_exact_on_every_exact_gpu_case(n, family, causal):
+    """integer taps in front of the integer rotations of tests/var2_exact.py: the replay gives the integers, forward and all six
+    gradients, no tolerance (the closed form itself is pinned against the loops in tests/test_var2_host.py)"""
+    want = exact.biquad_expected(n, family, causal)
+    got = replay(exact.biquad_case(n, family, causal), causal)
+    assert tuple(want) == cases.NAMES
+    for name in cases.NAMES:
+        np.testing.assert_array_equal(got[name], want[name], name)
 
 
 @pytest.mark.parametrize("causal", DIRECTIONS)

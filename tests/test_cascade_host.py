@@ -14,6 +14,7 @@ import biquad_emulator
 import cascade_cases as cases
 import cascade_emulator as emu
 import cascade_loops as loops
+import var2_exact as exact
 import recfilter_amd as rfa
 from recfilter_amd import capi
 
@@ -102,7 +103,11 @@ def test_padding_rule_of_biquad_cascade(n, causal):
 
 # ---- the numpy replay -----------------------------------------------------------------------------------------------------------
 def replay(n, lines, kind, causal, K):
-    x, sections, g = cases.case(n, lines, kind, causal, K)
+    return replay_of(*cases.case(n, lines, kind, causal, K), causal)
+
+
+def replay_of(x, sections, g, causal):
+    (lines, n), K = x.shape, len(sections)
     got = {name: np.empty((lines, n), np.float32) for name in cases.names(K)}
     for l in range(lines):
         one = line(sections, l)
@@ -113,13 +118,29 @@ def replay(n, lines, kind, causal, K):
 
 
 @pytest.mark.parametrize("causal", DIRECTIONS)
-@pytest.mark.parametrize("n,lines,kind,K", cases.GPU_CASES)
+@pytest.mark.parametrize("n,lines,kind,K", cases.GPU_CASES + cases.LONG_MEMORY_CASES)
 def test_replay_meets_the_condition_on_every_gpu_case(n, lines, kind, K, causal):
     """forward and all 1 + 5 K gradients of the numpy f32 replay: at most 2 x the f32 serial cascade's error, or under 1e-6"""
     want = cases.expected(n, lines, kind, causal, K)
     got = replay(n, lines, kind, causal, K)
     for name in cases.names(K):
         cases.assert_under_bar(got[name], want[name], f"replay {n} x {lines} {kind} K={K} {name_of(causal)} {name}", factor=2)
+
+
+def test_every_long_memory_case_has_its_seed():
+    assert set(cases.LONG_MEMORY_SEEDS) == {(n, kind, c, K) for n, _, kind, K in cases.LONG_MEMORY_CASES for c in DIRECTIONS}
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n", exact.LENGTHS[:2])
+def test_replay_is_exact_on_every_exact_gpu_case(n, causal):
+    """a section of period 6 into one of period 3, integer taps (tests/var2_exact.py; the closed form is pinned against the loops
+    in tests/test_var2_host.py): the replay, the link included, gives the integers -- forward and all 11 gradients"""
+    want, left_out = exact.cascade_expected(n, causal)
+    assert not left_out and tuple(sorted(want)) == tuple(sorted(cases.names(2)))
+    got = replay_of(*exact.cascade_case(n, causal), causal)
+    for name in cases.names(2):
+        np.testing.assert_array_equal(got[name], want[name], name)
 
 
 @pytest.mark.parametrize("causal", DIRECTIONS)

@@ -18,6 +18,7 @@ import pytest
 import biquad_cases as cases
 import biquad_emulator as emu
 import guarded
+import var2_exact as exact
 import recfilter_amd as rfa
 
 pytestmark = pytest.mark.gpu
@@ -116,7 +117,36 @@ def test_long_signal_against_segmented_loops(causal):
     check_all(cases.LONG, 1, "sprinkled", causal)
 
 
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n,lines,kind", cases.LONG_MEMORY_CASES)
+def test_long_memory_against_f64_loops(n, lines, kind, causal):
+    """r inside [0.998, 0.9995] at four groups: a group's P reaches the result (tests/var2_cases.py); the seeds are the ones under
+    which the numpy replay is at or below half the bar (cases.LONG_MEMORY_SEEDS)"""
+    assert cases.LONG_MEMORY_CASES == [(12292, 1, "long memory")]      # the ones tests/test_biquad_host.py holds the replay on
+    check_all(n, lines, kind, causal)
+
+
 # ---- exact cases ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("family", list(exact.FAMILIES))
+@pytest.mark.parametrize("n", exact.LENGTHS[:2])
+def test_integer_rotations_with_integer_taps_are_exact(n, family, causal):
+    """tests/var2_exact.py: constant integer taps in front of a companion matrix of period 6 or 3 or the running sum's, inputs in
+    {-1, 0, 1} -- the output and all six gradients are the integers, bit for bit, at four groups and at 66"""
+    signals = exact.biquad_case(n, family, causal)
+    want = exact.biquad_expected(n, family, causal)
+    what = f"{n} {family} {name_of(causal)}"
+    with rfa.Var2Plan(n, causal=causal) as plan:
+        y = run_forward(plan, signals[:6])
+        exact.assert_equal(y, want["out"], f"{what} out", causal)
+        only_x = run_backward(plan, signals[:6], y, signals[6], False)
+        full = run_backward(plan, signals[:6], y, signals[6], True)
+    np.testing.assert_array_equal(bits(only_x[0]), bits(full[0]))
+    for got, name in zip(full, GRADS):
+        exact.assert_equal(got, want[name], f"{what} {name}", causal)
+    assert_masked_gradients_are_zero(full, causal, what)
+
+
 @pytest.mark.parametrize("causal", DIRECTIONS)
 @pytest.mark.parametrize("n", [68, 8196])
 def test_unit_taps_give_the_bits_of_the_all_pole_scan(n, causal):

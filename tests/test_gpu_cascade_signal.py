@@ -18,6 +18,7 @@ import pytest
 
 import cascade_cases as cases
 import guarded
+import var2_exact as exact
 import recfilter_amd as rfa
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +138,38 @@ def test_the_accuracy_cases_are_the_host_tests():
             + [(n, 1, kind, 8) for n in (4100, 8196) for kind in ("resonator", "sprinkled")]
             + [(n, lines, "resonator", 2) for lines, n, _ in cases.LINE_CASES] + [(cases.LONG, 1, "sprinkled", 2)])
     assert here == cases.GPU_CASES
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n,lines,kind,K", cases.LONG_MEMORY_CASES)
+def test_long_memory_against_f64_loops(n, lines, kind, K, causal):
+    """r inside [0.998, 0.9995] at four groups, K = 2: a group's P reaches the result through var2_link_1d and var2_link_keep_1d
+    (tests/var2_cases.py); the seeds are the ones under which the numpy replay meets the host test's condition"""
+    assert cases.LONG_MEMORY_CASES == [(12292, 1, "long memory", 2)]      # the ones tests/test_cascade_host.py holds the replay on
+    check_all(n, lines, kind, causal, K)
+
+
+# ---- exact cases ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n", exact.LENGTHS[:2])
+def test_integer_rotations_of_two_periods_are_exact(n, causal):
+    """tests/var2_exact.py: a section of period 6 into one of period 3 (two of one period would resonate and grow), integer taps,
+    inputs in {-1, 0, 1}: the state that enters every tile of the link is an integer that never decayed, and the output and the
+    gradients are the integers bit for bit, at four groups and at 66.  Every one of the 11 gradients is checked: all stay below
+    2^24 at these lengths (the reference says which do not, and none may be left out silently)"""
+    x, sections, g = exact.cascade_case(n, causal)
+    want, left_out = exact.cascade_expected(n, causal)
+    assert not left_out, f"gradients that reach 2^24 and could not be compared: {left_out}"
+    what = f"{n} period 6 into period 3 {name_of(causal)}"
+    with rfa.Var2Plan(n, causal=causal) as plan:
+        y = run_forward(plan, x, sections)
+        exact.assert_equal(y, want["out"], f"{what} out", causal)
+        only_x = run_backward(plan, x, sections, y, g, False)
+        full = run_backward(plan, x, sections, y, g, True)
+    np.testing.assert_array_equal(bits(only_x[0]), bits(full[0]))
+    for got, name in zip(full, cases.names(2)[1:]):
+        exact.assert_equal(got, want[name], f"{what} {name}", causal)
+    assert_masked_gradients_are_zero(full, causal, 2, what)
 
 
 # ---- exact identities -------------------------------------------------------------------------------------------------------------

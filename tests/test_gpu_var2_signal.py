@@ -7,7 +7,12 @@ gradients.  tests/test_var2_host.py holds the numpy replay of the kernels' algeb
 coefficients a scan masks hold NaN; inputs are seeded, signed, in [-1, 1].
 
 The long case, 4,198,404 samples, is 1026 groups: var2_carry_1d takes two sweeps.  It is of the sprinkled family, whose zeros cut
-the line every 200..600 samples, and is checked against the segmented loops."""
+the line every 200..600 samples, and is checked against the segmented loops.
+
+With a pole radius of at most 0.98 a group's 2 x 2 matrix P is 0.98^4096 = 1e-36: those families cannot see the matrix half of
+var2_carry_1d.  Two families can: the integer rotations of tests/var2_exact.py, compared without tolerance, and the long-memory
+family (r inside [0.998, 0.9995]) under the bar; tests/test_var2_carry_seen_host.py shows on the CPU that a wrong carry stage
+fails every one of their cases."""
 import os
 import subprocess
 import sys
@@ -17,6 +22,7 @@ import pytest
 
 import guarded
 import var2_cases as cases
+import var2_exact as exact
 import recfilter_amd as rfa
 
 pytestmark = pytest.mark.gpu
@@ -108,7 +114,59 @@ def test_long_signal_against_segmented_loops(causal):
     check_all(cases.LONG, 1, "sprinkled", causal)
 
 
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("n,lines,kind", cases.LONG_MEMORY_CASES)
+def test_long_memory_against_f64_loops(n, lines, kind, causal):
+    """r inside [0.998, 0.9995]: a group's P is 3e-4 .. 0.13, so the matrix half of var2_carry_1d reaches the result -- four groups,
+    66 groups (a second wave), and 1026 (a second sweep; cuts 20,000 .. 40,000 samples apart, none near a sweep boundary).  The seeds
+    are the ones under which the numpy replay is at or below half the bar (cases.LONG_MEMORY_SEEDS)"""
+    check_all(n, lines, kind, causal)
+
+
+def test_the_long_memory_cases_are_the_host_tests():
+    """the cases above are the ones tests/test_var2_host.py holds the numpy replay to half the bar on and
+    tests/test_var2_carry_seen_host.py shows a wrong carry stage on"""
+    assert cases.LONG_MEMORY_CASES == [(12292, 1, "long memory"), (266244, 1, "long memory"), (cases.LONG, 1, "long memory, cut")]
+    assert exact.LENGTHS == [12292, 266244, cases.LONG] and list(exact.FAMILIES) == ["period 6", "period 3", "running sum"]
+
+
 # ---- exact cases ----------------------------------------------------------------------------------------------------------------
+def check_exact(n, signals, want, causal, what, stride=None):
+    """execute and backward on integer signals (lines, n) against the integers of tests/var2_exact.py: no tolerance"""
+    x, a1, a2, g = signals
+    lines = x.shape[0]
+    y = run_forward(n, lines, causal, x, a1, a2, stride)
+    exact.assert_equal(y, want["out"], f"{what} out", causal)
+    with rfa.Var2Plan(n, lines=lines, causal=causal, stride=stride) as plan:
+        only_x = run_backward(plan, a1, a2, y, g, False, stride)
+        full = run_backward(plan, a1, a2, y, g, True, stride)
+    np.testing.assert_array_equal(bits(only_x[0]), bits(full[0]))
+    for got, name in zip(full, ("grad_x", "grad_a1", "grad_a2")):
+        exact.assert_equal(got, want[name], f"{what} {name}", causal)
+    first, second = (np.s_[:, :1], np.s_[:, :2]) if causal else (np.s_[:, -1:], np.s_[:, -2:])
+    assert np.all(bits(full[1][first]) == 0) and np.all(bits(full[2][second]) == 0), f"{what}: the masked coefficients' gradients are not +0"
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+@pytest.mark.parametrize("family", list(exact.FAMILIES))
+@pytest.mark.parametrize("n", exact.LENGTHS)
+def test_integer_rotations_are_exact(n, family, causal):
+    """constant coefficients whose companion matrix has period 6 or 3, or is the running sum's, on inputs in {-1, 0, 1}: every
+    state and every entry of a group's P is a small integer that never decays, so the result is the integer one bit for bit
+    whatever the order of operations -- at four groups (the first P_B E_A of either direction), 66 (the fold of the waves'
+    totals) and 1026 (the state kept between two sweeps)"""
+    check_exact(n, exact.case(n, family, causal), exact.expected(n, family, causal), causal, f"{n} {family} {name_of(causal)}")
+
+
+@pytest.mark.parametrize("causal", DIRECTIONS)
+def test_integer_rotations_on_lines_with_a_stride_above_the_length(causal):
+    """one line per family, rows further apart than they are long"""
+    n = exact.LENGTHS[0]
+    signals = [np.concatenate(s) for s in zip(*(exact.case(n, family, causal) for family in exact.FAMILIES))]
+    want = {name: np.concatenate([exact.expected(n, family, causal)[name] for family in exact.FAMILIES]) for name in ("out", "grad_x", "grad_a1", "grad_a2")}
+    check_exact(n, signals, want, causal, f"{n} x 3 {name_of(causal)}", stride=n + 12)
+
+
 @pytest.mark.parametrize("causal", DIRECTIONS)
 @pytest.mark.parametrize("n", [68, 8196, cases.LONG])
 def test_coefficients_of_zero_leave_the_signal(n, causal):

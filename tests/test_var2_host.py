@@ -1,7 +1,8 @@
 """CPU tests of the time-varying second-order all-pole scans (rf_var2_plan_*): host-only plans -- creation, launch counts, the
 workspace formula, every refusal with its status and text -- the loops of tests/var2_loops.py pinned by central differences, and
 the tiled algebra of kernels_var2_signal.hip replayed in numpy f32 (tests/var2_emulator.py) under the GPU tests' bar on every
-case the GPU tests use.  No kernel is launched."""
+case the GPU tests use -- at or below half of it on the long-memory cases, whose seeds are chosen by that, and exact on the integer
+rotations of tests/var2_exact.py, whose closed form is pinned against the loops here.  No kernel is launched."""
 import ctypes
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 import var2_cases as cases
 import var2_emulator as emu
+import var2_exact as exact
 import var2_loops as loops
 import recfilter_amd as rfa
 from recfilter_amd import capi
@@ -287,22 +289,124 @@ def test_tile_tails_and_carries_are_the_serial_states(causal):
 
 
 GPU_CASES = ([(n, 1, kind) for n in cases.LENGTHS for kind in cases.KINDS] + [(n, lines, "resonator") for lines, n, _ in cases.LINE_CASES]
-             + [(cases.LONG, 1, "sprinkled")])
+             + [(cases.LONG, 1, "sprinkled")] + cases.LONG_MEMORY_CASES)
+
+
+def replay(n, lines, kind, causal):
+    x, a1, a2, g = cases.case(n, lines, kind, causal)
+    got = {name: np.empty((lines, n), np.float32) for name in ("out", "grad_x", "grad_a1", "grad_a2")}
+    for l in range(lines):
+        y = emu.tiled_forward(x[l], a1[l], a2[l], causal)
+        got["out"][l] = y
+        got["grad_x"][l], got["grad_a1"][l], got["grad_a2"][l] = emu.tiled_adjoint(a1[l], a2[l], y, g[l], causal)
+    return got
 
 
 @pytest.mark.parametrize("causal", [True, False])
 @pytest.mark.parametrize("n,lines,kind", GPU_CASES)
 def test_emulator_under_the_bar_on_every_gpu_case(n, lines, kind, causal):
     """what makes the GPU tests ones the algebra itself passes: forward and all three gradients of the numpy f32 replay"""
-    x, a1, a2, g = cases.case(n, lines, kind, causal)
     want = cases.expected(n, lines, kind, causal)
-    got = {name: np.empty((lines, n), np.float32) for name in want}
-    for l in range(lines):
-        y = emu.tiled_forward(x[l], a1[l], a2[l], causal)
-        got["out"][l] = y
-        got["grad_x"][l], got["grad_a1"][l], got["grad_a2"][l] = emu.tiled_adjoint(a1[l], a2[l], y, g[l], causal)
+    got = replay(n, lines, kind, causal)
     for name in want:
         cases.assert_under_bar(got[name], want[name], f"emulator {n} x {lines} {kind} {'causal' if causal else 'anticausal'} {name}")
+
+
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("n,lines,kind", cases.LONG_MEMORY_CASES)
+def test_emulator_under_half_the_bar_on_every_long_memory_case(n, lines, kind, causal):
+    """the condition the seeds of cases.LONG_MEMORY_SEEDS were chosen by: a kernel result above the bar on one of these cases is
+    then a finding about the kernel, not about the draw"""
+    assert set(cases.LONG_MEMORY_SEEDS) == {(n, kind, c) for n, _, kind in cases.LONG_MEMORY_CASES for c in (True, False)}
+    want = cases.expected(n, lines, kind, causal)
+    got = replay(n, lines, kind, causal)
+    for name in want:
+        cases.assert_under_half_the_bar(got[name], want[name], f"emulator {n} x {lines} {kind} {'causal' if causal else 'anticausal'} {name}")
+
+
+def test_long_memory_family_keeps_its_memory():
+    """r inside [0.998, 0.9995], and the long case's cuts 20,000 .. 40,000 samples apart, none near a sweep boundary (the case
+    itself asserts the latter): about 140 lines for the segmented loops"""
+    for n, _, kind in cases.LONG_MEMORY_CASES:
+        _, a1, a2, _ = cases.case(n, 1, kind, True)
+        r = np.sqrt(a2[0][2:].astype(np.float64))
+        live = r > 0
+        assert r[live].min() >= 0.998 - 1e-6 and r[live].max() <= 0.9995 + 1e-6
+        if kind == "long memory, cut":
+            starts = loops.segment_starts(*loops.masked(a1[0], a2[0], np.float64))
+            gaps = np.diff(starts)
+            gaps = gaps[gaps > 1]      # (a cut decouples at two neighbouring samples: a segment of one sample before each long one)
+            assert 100 <= len(gaps) <= 220 and gaps.min() >= 20000 - 1 and gaps.max() <= 40000
+        else:
+            assert live.all()
+
+
+# ---- the exact cases ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("family", list(exact.FAMILIES))
+@pytest.mark.parametrize("n", [4, 68, 4100, 12292])
+def test_integer_closed_forms_are_the_serial_loops(n, family, causal):
+    """tests/var2_exact.py against the f64 loops, ends included: the all-pole scan, the section with integer taps, and (period 6
+    into period 3) the cascade of two"""
+    import biquad_loops
+    import cascade_loops
+    x, a1, a2, g = exact.case(n, family, causal)
+    want = exact.expected(n, family, causal)
+    y = loops.forward(x, a1, a2, causal)
+    np.testing.assert_array_equal(y, want["out"])
+    for got, name in zip(loops.adjoint(a1, a2, y, g, causal), ("grad_x", "grad_a1", "grad_a2")):
+        np.testing.assert_array_equal(got, want[name], name)
+    if n > 4:
+        assert all(np.any(want[name] != 0) for name in want)
+    signals = exact.biquad_case(n, family, causal)
+    want = exact.biquad_expected(n, family, causal)
+    y = biquad_loops.forward(*signals[:6], causal)
+    for got, name in zip((y, *biquad_loops.adjoint(*signals[:6], y, signals[6], causal)), want):
+        np.testing.assert_array_equal(got, want[name], name)
+    if family == "period 6":
+        x, sections, g = exact.cascade_case(n, causal)
+        want, left_out = exact.cascade_expected(n, causal)
+        assert not left_out
+        ys = cascade_loops.forward(x, sections, causal)
+        got = dict(zip(cascade_names(2), cascade_flat(ys[-1], cascade_loops.adjoint(x, sections, ys, g, causal))))
+        assert set(got) == set(want)
+        for name in want:
+            np.testing.assert_array_equal(got[name], want[name], name)
+
+
+def cascade_names(K):
+    return ("out", "grad_x") + tuple(f"grad_{c}_{k}" for k in range(K) for c in exact.COEFFICIENTS)
+
+
+def cascade_flat(result, grads):
+    return [result, grads[0]] + [c for s in grads[1] for c in s]
+
+
+@pytest.mark.parametrize("causal", [True, False])
+@pytest.mark.parametrize("family", list(exact.FAMILIES))
+@pytest.mark.parametrize("n", exact.LENGTHS)
+def test_emulator_is_exact_on_every_exact_gpu_case(n, family, causal):
+    """the numpy f32 replay gives the integers: forward and all three gradients, no tolerance"""
+    x, a1, a2, g = exact.case(n, family, causal)
+    want = exact.expected(n, family, causal)
+    y = emu.tiled_forward(x[0], a1[0], a2[0], causal)
+    for got, name in zip((y, *emu.tiled_adjoint(a1[0], a2[0], y, g[0], causal)), ("out", "grad_x", "grad_a1", "grad_a2")):
+        np.testing.assert_array_equal(got, want[name][0], name)
+
+
+def test_exact_families_are_the_integer_rotations():
+    """the companion matrices: period 6 and 3 (no power of two: M^64 and M^4096 are not the identity and not symmetric), and the
+    running sum's singular one"""
+    for family, period in (("period 6", 6), ("period 3", 3), ("running sum", None)):
+        a1, a2 = exact.FAMILIES[family]
+        M = np.array([[-a1, -a2], [1, 0]], dtype=np.int64)
+        for power in (64, 4096):
+            P = np.linalg.matrix_power(M, power)
+            assert not np.array_equal(P, P.T) and not np.array_equal(P, np.eye(2, dtype=np.int64)), (family, power)
+        if period:
+            assert np.array_equal(np.linalg.matrix_power(M, period), np.eye(2, dtype=np.int64))
+        else:
+            assert np.array_equal(np.linalg.matrix_power(M, 4096), [[1, 0], [1, 0]])
 
 
 @pytest.mark.parametrize("causal", [True, False])

@@ -40,7 +40,7 @@ def apply_map(m, s0, s1):
     return fma(p00, s0, fma(p01, s1, e0)), fma(p10, s0, fma(p11, s1, e1))
 
 
-def lane_scan(own):
+def lane_scan(own, compose=compose):
     """inclusive Kogge-Stone scan along the last axis (64 lanes)"""
     whole = tuple(c.copy() for c in own)
     lanes = whole[0].shape[-1]
@@ -80,9 +80,10 @@ def scan_coefficients(a1, a2, causal, adjoint):
     return c1, c2
 
 
-def tiled_scan(x, a1, a2, causal=True, adjoint=False, parts=None):
+def tiled_scan(x, a1, a2, causal=True, adjoint=False, parts=None, mutate_aggregate=None, carry_compose=compose):
     """the three launches on one line (N,), N a multiple of 4.  `causal`: the direction of THIS recurrence.  parts: a dict that
-    receives the intermediate values (tests)"""
+    receives the intermediate values (tests).  mutate_aggregate, carry_compose: what tests/test_var2_carry_seen_host.py hands the
+    carry stage in place of the groups' aggregates and of `compose` in its lane scan; left alone, no bit changes"""
     n = x.shape[0]
     c1, c2 = scan_coefficients(a1, a2, causal, adjoint)
     groups = -(-n // (T * GROUP))
@@ -108,6 +109,8 @@ def tiled_scan(x, a1, a2, causal=True, adjoint=False, parts=None):
     whole = lane_scan(own)
     maps = exclusive(whole)
     aggregate = tuple(c[:, -1] for c in whole)
+    if mutate_aggregate is not None:
+        aggregate = tuple(np.asarray(c, dtype=F) for c in mutate_aggregate(aggregate))
     # var2_carry_1d: sweeps of up to 1024 groups
     span = min(SWEEP, -(-groups // 64) * 64)
     carry0, carry1 = np.zeros(groups, F), np.zeros(groups, F)
@@ -118,7 +121,7 @@ def tiled_scan(x, a1, a2, causal=True, adjoint=False, parts=None):
         for c, a in zip(m, aggregate):
             c[:take] = a[base:base + take]
         m = tuple(c.reshape(span // 64, 64) for c in m)
-        scanned = lane_scan(m)
+        scanned = lane_scan(m, carry_compose)
         totals = tuple(c[:, -1] for c in scanned)
         enter0, enter1 = np.zeros(span // 64, F), np.zeros(span // 64, F)
         nxt0, nxt1 = np.array(run0, F), np.array(run1, F)
