@@ -1211,4 +1211,38 @@ public:
     /** 4 at K = 1, 6 K - 1 above */
     int cascade_gradient_num_kernels(int sections) { prepare(); return rf_var2_plan_backward_cascade_num_kernels(plan, sections); }
     size_t cascade_gradient_bytes(int sections) { prepare(); return rf_var2_plan_backward_cascade_bytes(plan, sections); }
+    /** realize_cascade() with every section's result kept, for training (rf_var2_plan_execute_cascade_keep): kept holds one
+     *  signal per section but the last, laid out like in, and receives section k's result in kept[k]; out is realize_cascade()'s
+     *  bit for bit.  The signals are the caller's; a kept signal overlaps nothing else in the call. */
+    void realize_cascade_keep(const void *in, const std::vector<rf_var2_section> &sections, void *out, const std::vector<void *> &kept,
+                              void *stream = nullptr) {
+        prepare();
+        if (kept.size() + 1 != sections.size())
+            throw RecFilterError("realize_cascade_keep: kept holds one signal per section but the last");
+        if (rf_var2_plan_execute_cascade_keep(plan, in, sections.data(), (int)sections.size(), out, kept.empty() ? nullptr : kept.data(),
+                                              stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize_cascade_keep() on what it kept (rf_var2_plan_backward_cascade_kept): nothing is rerun, one adjoint
+     *  link launch per boundary between two sections.  grads: empty (no coefficient gradients: in, out and kept may then be null
+     *  and empty, nothing of the forward is read) or one rf_var2_section_grad per section.  grad_in == grad_out is allowed.  The
+     *  plan owns one signal, two for two sections or more (cascade_kept_gradient_bytes()). */
+    void gradient_cascade_kept(const void *in, const std::vector<rf_var2_section> &sections, const std::vector<const void *> &kept,
+                               const void *out, const void *grad_out, void *grad_in, const std::vector<rf_var2_section_grad> &grads = {},
+                               void *stream = nullptr) {
+        prepare();
+        if (!grads.empty() && grads.size() != sections.size())
+            throw RecFilterError("gradient_cascade_kept: grads is empty or holds one rf_var2_section_grad per section");
+        if (!kept.empty() && kept.size() + 1 != sections.size())
+            throw RecFilterError("gradient_cascade_kept: kept is empty or holds one signal per section but the last");
+        if (rf_var2_plan_backward_cascade_kept(plan, in, sections.data(), (int)sections.size(), kept.empty() ? nullptr : kept.data(), out,
+                                               grad_out, grad_in, grads.empty() ? nullptr : grads.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** 2 K + 2 without coefficient gradients, 3 K + 1 with them */
+    int cascade_kept_gradient_num_kernels(int sections, bool with_coefficients) {
+        prepare();
+        return rf_var2_plan_backward_cascade_kept_num_kernels(plan, sections, with_coefficients ? 1 : 0);
+    }
+    size_t cascade_kept_gradient_bytes(int sections) { prepare(); return rf_var2_plan_backward_cascade_kept_bytes(plan, sections); }
 };

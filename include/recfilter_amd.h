@@ -1049,8 +1049,34 @@ int    rf_smooth_plan_create_volume(const rf_smooth_volume_desc *desc, rf_smooth
  * misaligned gradient pointer ("section k: ..."); execute: out overlapping a coefficient signal ("coefficient of section k plane
  * j", j = 0..4 for b0, b1, b2, a1, a2), then in; backward: a written gradient overlapping a coefficient signal, in, out, another
  * written gradient, or grad_out other than grad_in exactly (RF_ERR_INVALID_ARG); then a host-only plan (RF_ERR_HIP).  A *_timed
- * call checks ms_out's capacity after the plan and n_sections.  Out of scope: mixed directions inside one cascade (zero-phase
- * filtering stays two plans); keeping the forward's intermediates for the backward; concurrent calls on one plan. */
+ * call checks ms_out's capacity after the plan and n_sections.
+ *
+ * The cascade for training (rf_var2_plan_execute_cascade_keep, rf_var2_plan_backward_cascade_kept): the forward keeps every
+ * section's result, in signals the CALLER owns -- the plan still keeps no state between calls -- and the backward reruns nothing.
+ * kept is an array of n_sections - 1 pointers to signals laid out like in (it may be null at K = 1); kept[k] receives section
+ * k's result, out the last section's.  The launches are rf_var2_plan_execute_cascade's with "var2_link_keep_1d" for
+ * "var2_link_1d" -- rf_var2_plan_cascade_num_kernels serves -- and out is that call's bit for bit; K = 1 is
+ * rf_var2_plan_execute_biquad's launches and bits.  A kept signal overlaps nothing else in the call; in == out is refused.
+ * rf_var2_plan_backward_cascade_kept takes them back.  Launches, from the last section down: "var2_adj_tails_1d" on grad_out;
+ * per boundary between sections k and k - 1, "var2_carry_1d" and "var2_adj_link_1d" -- the final stage of section k's adjoint
+ * scan, the gradient that enters section k - 1,
+ *     g[n] = fma(b2~[n+2], lam[n+2], fma(b1~[n+1], lam[n+1], b0[n] lam[n]))          (causal; lam = section k's adjoint state)
+ * formed on the tile in registers and stored to a signal of the plan's, and the adjoint tails stage of section k - 1 on it --
+ * then "var2_carry_1d", "var2_adj_pass2_1d" and "var2_biquad_grad_1d" for section 0.  The two samples of lam the transposed taps
+ * reach beyond a tile are the state that enters the tile in the adjoint scan's final stage, not a reload: with feedback the
+ * gradients differ from rf_var2_plan_backward_cascade's in the last bits of a few samples, with all feedback coefficients 0 they
+ * are its bits.  With coefficient gradients the link is "var2_adj_link_keep_1d" (lam stored too) and "var2_biquad_coef_1d"
+ * follows it: the section's five gradients from lam, kept[k-1] and kept[k] (out for the last section).
+ * rf_var2_plan_backward_cascade_kept_num_kernels(plan, K, with) = 2 K + 2 without coefficient gradients and 3 K + 1 with them;
+ * both are 4 at K = 1, where launches and bits are rf_var2_plan_backward_biquad's.  The plan owns lam (K = 1) or lam and the
+ * gradient between sections (K >= 2), whatever K: rf_var2_plan_backward_cascade_kept_bytes(plan, K) = 1 or 2 spans, shared with
+ * rf_var2_plan_backward_cascade's allocation -- calls of both kinds mix on one plan in any order.  grads null: in, out and kept
+ * may be null (nothing of the forward is read).  grads given: every pointer of every section, in, out and, for K >= 2, all of
+ * kept are required.  grad_in == grad_out is allowed.  Refusals are those of the cascade calls above, in their order, with the
+ * kept pointers checked behind in, out, grad_out, grad_in ("kept k: ...", null or misaligned) and before the coefficient
+ * pointers; execute_cascade_keep: out, then a kept signal, overlapping a coefficient signal, in, or another written signal
+ * ("kept plane k"); backward_cascade_kept: a written gradient overlapping a kept signal, beside the overlaps above.
+ * Out of scope: mixed directions inside one cascade (zero-phase filtering stays two plans); concurrent calls on one plan. */
 typedef struct rf_var2_plan rf_var2_plan;
 typedef struct {
     uint32_t abi;                     /* RF_ABI                                                  */
@@ -1105,6 +1131,21 @@ int    rf_var2_plan_backward_cascade_timed(rf_var2_plan *plan, const void *in, c
 int    rf_var2_plan_cascade_num_kernels(const rf_var2_plan *plan, int n_sections);             /* 0: n_sections out of range */
 int    rf_var2_plan_backward_cascade_num_kernels(const rf_var2_plan *plan, int n_sections);
 size_t rf_var2_plan_backward_cascade_bytes(const rf_var2_plan *plan, int n_sections);
+/* kept: n_sections - 1 signals laid out like in (null at n_sections == 1) */
+int    rf_var2_plan_execute_cascade_keep(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                         void *out, void *const *kept, void *stream);
+int    rf_var2_plan_execute_cascade_keep_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                               void *out, void *const *kept, void *stream, float *ms_out, const char **names_out,
+                                               int capacity);
+int    rf_var2_plan_backward_cascade_kept(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                          const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                          const rf_var2_section_grad *grads, void *stream);
+int    rf_var2_plan_backward_cascade_kept_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                                const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                                const rf_var2_section_grad *grads, void *stream, float *ms_out,
+                                                const char **names_out, int capacity);
+int    rf_var2_plan_backward_cascade_kept_num_kernels(const rf_var2_plan *plan, int n_sections, int with_coefficient_gradients);
+size_t rf_var2_plan_backward_cascade_kept_bytes(const rf_var2_plan *plan, int n_sections);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

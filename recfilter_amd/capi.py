@@ -90,6 +90,9 @@ EXPORTED_SYMBOLS = [
     "rf_var2_plan_execute_cascade", "rf_var2_plan_execute_cascade_timed", "rf_var2_plan_backward_cascade",
     "rf_var2_plan_backward_cascade_timed", "rf_var2_plan_cascade_num_kernels", "rf_var2_plan_backward_cascade_num_kernels",
     "rf_var2_plan_backward_cascade_bytes",
+    "rf_var2_plan_execute_cascade_keep", "rf_var2_plan_execute_cascade_keep_timed", "rf_var2_plan_backward_cascade_kept",
+    "rf_var2_plan_backward_cascade_kept_timed", "rf_var2_plan_backward_cascade_kept_num_kernels",
+    "rf_var2_plan_backward_cascade_kept_bytes",
 ]
 
 
@@ -325,6 +328,14 @@ def lib() -> ctypes.CDLL:
     L.rf_var2_plan_backward_cascade_num_kernels.argtypes = [vp, ctypes.c_int]
     L.rf_var2_plan_backward_cascade_bytes.argtypes = [vp, ctypes.c_int]
     L.rf_var2_plan_backward_cascade_bytes.restype = ctypes.c_size_t
+    kp = ctypes.POINTER(ctypes.c_void_p)      # the kept signals: an array of addresses
+    L.rf_var2_plan_execute_cascade_keep.argtypes = [vp, vp, sp, ctypes.c_int, vp, kp, vp]
+    L.rf_var2_plan_execute_cascade_keep_timed.argtypes = [vp, vp, sp, ctypes.c_int, vp, kp, vp] + report
+    L.rf_var2_plan_backward_cascade_kept.argtypes = [vp, vp, sp, ctypes.c_int, kp, vp, vp, vp, sp, vp]
+    L.rf_var2_plan_backward_cascade_kept_timed.argtypes = [vp, vp, sp, ctypes.c_int, kp, vp, vp, vp, sp, vp] + report
+    L.rf_var2_plan_backward_cascade_kept_num_kernels.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_kept_bytes.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_kept_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

@@ -784,6 +784,48 @@ int rf_var2_plan_backward_cascade_timed(rf_var2_plan *plan, const void *in, cons
     });
 }
 
+// the cascade whose forward keeps every section's result in signals of the caller's, and the backward without a rerun
+int rf_var2_plan_backward_cascade_kept_num_kernels(const rf_var2_plan *plan, int n_sections, int with_coefficient_gradients) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS
+               ? var2_cascade_kept_backward_launches(n_sections, with_coefficient_gradients != 0) : 0;
+}
+size_t rf_var2_plan_backward_cascade_kept_bytes(const rf_var2_plan *plan, int n_sections) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_kept_backward_bytes(plan, n_sections) : 0;
+}
+
+int rf_var2_plan_execute_cascade_keep(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out,
+                                      void *const *kept, void *stream) {
+    return fenced("rf_var2_plan_execute_cascade_keep", [&] {
+        return run_var2_cascade_keep(plan, in, sections, n_sections, out, kept, (hipStream_t)stream, nullptr, nullptr, 0, false);
+    });
+}
+
+int rf_var2_plan_execute_cascade_keep_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out,
+                                            void *const *kept, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_execute_cascade_keep_timed", [&] {
+        return run_var2_cascade_keep(plan, in, sections, n_sections, out, kept, (hipStream_t)stream, ms_out, names_out, capacity, true);
+    });
+}
+
+int rf_var2_plan_backward_cascade_kept(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                       const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                       const rf_var2_section_grad *grads, void *stream) {
+    return fenced("rf_var2_plan_backward_cascade_kept", [&] {
+        return run_var2_cascade_kept_backward(plan, in, sections, n_sections, kept, out, grad_out, grad_in, grads, (hipStream_t)stream, nullptr,
+                                              nullptr, 0, false);
+    });
+}
+
+int rf_var2_plan_backward_cascade_kept_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections,
+                                             const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                             const rf_var2_section_grad *grads, void *stream, float *ms_out, const char **names_out,
+                                             int capacity) {
+    return fenced("rf_var2_plan_backward_cascade_kept_timed", [&] {
+        return run_var2_cascade_kept_backward(plan, in, sections, n_sections, kept, out, grad_out, grad_in, grads, (hipStream_t)stream, ms_out,
+                                              names_out, capacity, true);
+    });
+}
+
 int rf_var2_plan_execute_biquad(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1,
                                 const void *a2, void *out, void *stream) {
     return fenced("rf_var2_plan_execute_biquad", [&] { return run_var2_biquad(plan, in, b0, b1, b2, a1, a2, out, (hipStream_t)stream, nullptr); });

@@ -88,6 +88,27 @@ struct Var2LinkArgs {
     int64_t stride;
 };
 
+// The boundary between sections k and k - 1 of a cascade, backward (var2_adj_link_1d, var2_adj_link_keep_1d): x = g_k, the
+// gradient that enters section k's adjoint scan (grad_out, or what the link before this one stored); a1, a2, b0, b1, b2 = section
+// k's coefficient signals; tails and carry hold that scan's maps and carries on entry and, on return, the maps and aggregates of
+// section k - 1's adjoint scan (prev_a1, prev_a2: its feedback coefficients).  dst receives g_{k-1} and may be x; keep, where not
+// null, receives lam_k and may be x too.  dst and keep are apart.  causal: the direction of the ADJOINT recurrence.
+struct Var2AdjLinkArgs {
+    const float *x;
+    const float *a1, *a2;
+    const float *b0, *b1, *b2;
+    const float *prev_a1, *prev_a2;
+    float *dst;
+    float *keep;
+    float *tails;
+    const float *carry;
+    int32_t n;
+    int32_t tiles, groups;
+    int32_t n_lines;
+    int32_t causal;
+    int64_t stride;
+};
+
 constexpr int kVar2Tile = 64;            // samples of a tile: one lane
 constexpr int kVar2GroupTiles = 64;      // tiles of a group: one wave
 int launch_var2_tails(const Var2Args &a, hipStream_t stream);      // "var2_tails_1d", "var2_adj_tails_1d"
@@ -99,5 +120,8 @@ int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream);   // "var2_grad
 int launch_var2_biquad_tails(const Var2Args &a, hipStream_t stream);             // "var2_biquad_tails_1d"
 int launch_var2_link(const Var2LinkArgs &a, hipStream_t stream);                 // "var2_link_1d", "var2_link_keep_1d" (a.keep != null)
 int launch_var2_biquad_grad(const Var2BiquadGradArgs &a, hipStream_t stream);    // "var2_biquad_grad_1d"
+int launch_var2_adj_link(const Var2AdjLinkArgs &a, hipStream_t stream);          // "var2_adj_link_1d", "var2_adj_link_keep_1d" (a.keep != null)
+// the five coefficient gradients without grad_in: a.b0, a.b1, a.b2, a.grad_in and a.with_coefficients are not looked at
+int launch_var2_biquad_coef(const Var2BiquadGradArgs &a, hipStream_t stream);    // "var2_biquad_coef_1d"
 
 }  // namespace rf

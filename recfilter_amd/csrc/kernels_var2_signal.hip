@@ -46,7 +46,17 @@
 //                          the tile in registers), the feed-forward part of section k + 1 on y_k with the tile's entering state
 //                          (y1, y2) for the near and the far sample beyond the tile, v_{k+1} stored -- in place: no workgroup reads
 //                          another's samples -- and the tails of section k + 1 on it, into the slots the workgroup has just read.
-//   var2_link_keep_1d      the same with y_k stored too (the backward's rerun of the forward keeps every section's output).
+//   var2_link_keep_1d      the same with y_k stored too (the backward's rerun of the forward keeps every section's output; so
+//                          does rf_var2_plan_execute_cascade_keep, into signals of the caller's).
+//
+// The backward of a cascade whose forward kept every section's result (rf_var2_plan_backward_cascade_kept) mirrors the link: the
+// gradient that enters section k - 1 is the transposed feed-forward part of section k on lam_k, and the two samples of lam_k its
+// taps reach beyond a tile are the state that enters the tile in the adjoint scan's final stage.
+//   var2_adj_link_1d       one launch per boundary: the final stage of section k's adjoint scan as var2_adj_pass2_1d runs it (lam_k
+//                          of the tile in registers), g_{k-1} = fma(b2~ two along, lam_k two along, fma(b1~ one along, lam_k one
+//                          along, b0 lam_k)) stored -- in place -- and the adjoint tails of section k - 1 on it.
+//   var2_adj_link_keep_1d  the same with lam_k stored too, for
+//   var2_biquad_coef_1d    the five coefficient gradients of a section from lam, x and y: the COEF half of var2_biquad_grad_1d.
 #include "kernels_var2.h"
 
 #include "var_device.h"
@@ -430,6 +440,155 @@ __global__ void __launch_bounds__(64) var2_link_kernel(Var2LinkArgs a) {
     }
 }
 
+// ---- the boundary between two sections of a cascade, backward ------------------------------------------------------------------------
+// One coefficient signal over the lane's tile as an adjoint stage reads it, from the tile as transposed: the values SHIFT samples
+// further along the forward's direction (REV: toward the line's end) -- those beyond the tile handed in, read from clamped
+// addresses -- then the mask by position of the scan's own direction.  The shifted feedback coefficients of var2_adj_tails_1d and
+// the transposed taps of var2_biquad_grad_1d are both this: a tap that would multiply lam outside the line sits where the scan
+// masks its coefficient.
+template <bool REV, int SHIFT>
+__device__ __forceinline__ void shift_and_mask(float (&c)[T], float beyond_near, float beyond_far, int n, int t0) {
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        const int i = REV ? j : T - 1 - j;            // in place: a value is read before it is overwritten
+        const int from = REV ? i + SHIFT : i - SHIFT;
+        const bool inside = from >= 0 && from < T;
+        const bool nearest = REV ? from == T : from == -1;
+        c[i] = inside ? c[inside ? from : 0] : (nearest ? beyond_near : beyond_far);
+    }
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        const int at = t0 + i;
+        c[i] = (REV ? at >= n - SHIFT : (at < SHIFT || at >= n)) ? 0.0f : c[i];
+    }
+}
+
+// the two samples of a signal just beyond the lane's tile in the direction an adjoint stage looks, from clamped addresses
+template <bool REV>
+__device__ __forceinline__ void beyond_tile(const float *p, int n, int t0, float &near_value, float &far_value) {
+    const int near = REV ? t0 + T : t0 - 1, far = REV ? t0 + T + 1 : t0 - 2;
+    near_value = p[max(min(near, n - 1), 0)];
+    far_value = p[max(min(far, n - 1), 0)];
+}
+
+// REV: the direction of the adjoint recurrence (the adjoint of a causal section runs REV).  KEEP: lam of the finished section is
+// stored to a.keep.
+template <bool REV, bool KEEP>
+__global__ void __launch_bounds__(64) var2_adj_link_kernel(Var2AdjLinkArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x, line = blockIdx.y;
+    const int n = a.n;
+    const int s0 = g * kGroupSamples;                 // below 2^30 + 4096
+    const int t = g * kGroupTiles + lane, t0 = t * T;
+    const int64_t first = (int64_t)line * a.stride;
+    float lam[T], v[T];
+    float lam_near, lam_far;
+    // the final stage of section k's adjoint scan: var2_adj_pass2_1d's, lam kept in registers
+    {
+        float vx[T], v1[T], v2[T], c1[T], c2[T];
+        request_group(a.x + first, n, s0, vx);
+        request_group(a.a1 + first, n, s0, v1);
+        request_group(a.a2 + first, n, s0, v2);
+        float nb1, nb1_far, nb2_near, nb2_far;
+        beyond_tile<REV>(a.a1 + first, n, t0, nb1, nb1_far);
+        beyond_tile<REV>(a.a2 + first, n, t0, nb2_near, nb2_far);
+        const int tt = min(t, a.tiles - 1);
+        float m[kVar2Components], y1, y2;
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index_of(a.n_lines, a.tiles, i, line, tt)];
+        apply_map(m, a.carry[((int64_t)0 * a.n_lines + line) * a.groups + g], a.carry[((int64_t)1 * a.n_lines + line) * a.groups + g], y1, y2);
+        lam_near = y1; lam_far = y2;                  // lam one and two samples before the tile, in the order of the recurrence
+        transpose_in(vx, lds, lam);
+        transpose_in(v1, lds, c1);
+        transpose_in(v2, lds, c2);
+        shift_and_mask<REV, 1>(c1, nb1, nb1_far, n, t0);
+        shift_and_mask<REV, 2>(c2, nb2_near, nb2_far, n, t0);
+#pragma unroll
+        for (int i = 0; i < T; i++) lam[i] = t0 + i < n ? lam[i] : 0.0f;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            const int i = REV ? T - 1 - j : j;
+            const float r = step2(c1[i], c2[i], lam[i], y1, y2);
+            lam[i] = r; y2 = y1; y1 = r;
+        }
+    }
+    if constexpr (KEEP) {
+        store_group(lds, a.keep + first, n, s0, lam);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < T; i++) lam[i] = t0 + i < n ? lam[i] : 0.0f;
+    __builtin_amdgcn_sched_barrier(0);
+    // the transposed feed-forward part of section k on lam: var2_biquad_grad_1d's order, the taps one at a time
+    {
+        float raw[T], b[T], b_near, b_far;
+        request_group(a.b0 + first, n, s0, raw);
+        transpose_in(raw, lds, b);
+#pragma unroll
+        for (int i = 0; i < T; i++) v[i] = (t0 + i < n ? b[i] : 0.0f) * lam[i];
+        request_group(a.b1 + first, n, s0, raw);
+        beyond_tile<REV>(a.b1 + first, n, t0, b_near, b_far);
+        transpose_in(raw, lds, b);
+        shift_and_mask<REV, 1>(b, b_near, b_far, n, t0);
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            const float one = REV ? (i + 1 < T ? lam[i + 1 < T ? i + 1 : 0] : lam_near) : (i >= 1 ? lam[i >= 1 ? i - 1 : 0] : lam_near);
+            v[i] = __builtin_fmaf(b[i], one, v[i]);
+        }
+        request_group(a.b2 + first, n, s0, raw);
+        beyond_tile<REV>(a.b2 + first, n, t0, b_near, b_far);
+        transpose_in(raw, lds, b);
+        shift_and_mask<REV, 2>(b, b_near, b_far, n, t0);
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            const float two = REV ? (i + 2 < T ? lam[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? lam_near : lam_far))
+                                  : (i >= 2 ? lam[i >= 2 ? i - 2 : 0] : (i == 1 ? lam_near : lam_far));
+            v[i] = __builtin_fmaf(b[i], two, v[i]);
+        }
+    }
+    // the adjoint tails stage of section k - 1 on v, the gradient that enters it
+    float v1[T], v2[T], c1[T], c2[T];
+    request_group(a.prev_a1 + first, n, s0, v1);
+    request_group(a.prev_a2 + first, n, s0, v2);
+    float nb1, nb1_far, nb2_near, nb2_far;
+    beyond_tile<REV>(a.prev_a1 + first, n, t0, nb1, nb1_far);
+    beyond_tile<REV>(a.prev_a2 + first, n, t0, nb2_near, nb2_far);
+    store_group(lds, a.dst + first, n, s0, v);
+    __syncthreads();
+    transpose_in(v1, lds, c1);
+    transpose_in(v2, lds, c2);
+    shift_and_mask<REV, 1>(c1, nb1, nb1_far, n, t0);
+    shift_and_mask<REV, 2>(c2, nb2_near, nb2_far, n, t0);
+#pragma unroll
+    for (int i = 0; i < T; i++) v[i] = t0 + i < n ? v[i] : 0.0f;
+    __builtin_amdgcn_sched_barrier(0);
+    float y1 = 0.0f, y2 = 0.0f, u1 = 1.0f, u2 = 0.0f, w1 = 0.0f, w2 = 1.0f;
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        const int i = REV ? T - 1 - j : j;
+        const float r = step2(c1[i], c2[i], v[i], y1, y2);
+        const float u = step2(c1[i], c2[i], 0.0f, u1, u2);
+        const float w = step2(c1[i], c2[i], 0.0f, w1, w2);
+        y2 = y1; y1 = r; u2 = u1; u1 = u; w2 = w1; w1 = w;
+    }
+    float own[kVar2Components], map[kVar2Components], whole[kVar2Components];
+    own[VAR2_E0] = y1; own[VAR2_E1] = y2;
+    own[VAR2_P00] = u1; own[VAR2_P10] = u2;
+    own[VAR2_P01] = w1; own[VAR2_P11] = w2;
+    scan_group<REV>(own, map, whole);
+    if (t < a.tiles) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) a.tails[map_index_of(a.n_lines, a.tiles, i, line, t)] = map[i];
+    }
+    if (lane == (REV ? 0 : 63)) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++)
+            a.tails[(int64_t)kVar2Components * a.n_lines * a.tiles + ((int64_t)i * a.n_lines + line) * a.groups + g] = whole[i];
+    }
+}
+
 // ---- the recurrence over groups: one workgroup per line ---------------------------------------------------------------------------
 // A sweep takes blockDim.x groups in the order of the recurrence (REV: from the last group down), lane i the i-th of them.  Within a
 // sweep: an inclusive wave scan of the aggregates, the waves' totals through LDS, every lane folding the totals of the waves before
@@ -577,6 +736,39 @@ __global__ void __launch_bounds__(kGradLanes) var2_biquad_grad_kernel(Var2Biquad
     *reinterpret_cast<float4 *>(a.grad_in + first + at) = make_float4(gx[0], gx[1], gx[2], gx[3]);
 }
 
+// The five coefficient gradients alone (var2_biquad_coef_1d), for a section whose input gradient var2_adj_link_keep_1d has formed:
+// the COEF half above -- the same products, selects and +0 at the masked slots -- from lam, x and y; no tap is read.
+template <bool CAUSAL>
+__global__ void __launch_bounds__(kGradLanes) var2_biquad_coef_kernel(Var2BiquadGradArgs a) {
+    const int n = a.n;
+    const int at = (blockIdx.x * kGradLanes + threadIdx.x) * 4;      // below 2^30 + 1024
+    if (at >= n) return;
+    const int64_t first = (int64_t)blockIdx.y * a.stride;
+    constexpr int X0 = CAUSAL ? 2 : 0;
+    const float4 q = *reinterpret_cast<const float4 *>(a.lam + first + at);
+    const float lam[4] = {q.x, q.y, q.z, q.w};
+    float xs[6], ys[6];
+    load_six<!CAUSAL>(a.x + first, at, n, xs);
+    load_six<!CAUSAL>(a.y + first, at, n, ys);
+    float g0[4], g1[4], g2[4], h1[4], h2[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i1 = CAUSAL ? X0 + k - 1 : X0 + k + 1, i2 = CAUSAL ? X0 + k - 2 : X0 + k + 2;
+        const bool no_one = CAUSAL ? at + k < 1 : at + k >= n - 1, no_two = CAUSAL ? at + k < 2 : at + k >= n - 2;
+        const float l = lam[k];
+        g0[k] = l * xs[X0 + k];
+        g1[k] = no_one ? 0.0f : l * xs[i1];
+        g2[k] = no_two ? 0.0f : l * xs[i2];
+        h1[k] = no_one ? 0.0f : -l * ys[i1];
+        h2[k] = no_two ? 0.0f : -l * ys[i2];
+    }
+    *reinterpret_cast<float4 *>(a.grad_b0 + first + at) = make_float4(g0[0], g0[1], g0[2], g0[3]);
+    *reinterpret_cast<float4 *>(a.grad_b1 + first + at) = make_float4(g1[0], g1[1], g1[2], g1[3]);
+    *reinterpret_cast<float4 *>(a.grad_b2 + first + at) = make_float4(g2[0], g2[1], g2[2], g2[3]);
+    *reinterpret_cast<float4 *>(a.grad_a1 + first + at) = make_float4(h1[0], h1[1], h1[2], h1[3]);
+    *reinterpret_cast<float4 *>(a.grad_a2 + first + at) = make_float4(h2[0], h2[1], h2[2], h2[3]);
+}
+
 int launched(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
@@ -626,6 +818,25 @@ int launch_var2_link(const Var2LinkArgs &a, hipStream_t stream) {
     if (a.causal) hipLaunchKernelGGL((var2_link_kernel<false, false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var2_link_kernel<true, false>), grid, block, 0, stream, a);
     return launched("var2_link_1d");
+}
+
+int launch_var2_adj_link(const Var2AdjLinkArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.keep) {
+        if (a.causal) hipLaunchKernelGGL((var2_adj_link_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_adj_link_kernel<true, true>), grid, block, 0, stream, a);
+        return launched("var2_adj_link_keep_1d");
+    }
+    if (a.causal) hipLaunchKernelGGL((var2_adj_link_kernel<false, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_adj_link_kernel<true, false>), grid, block, 0, stream, a);
+    return launched("var2_adj_link_1d");
+}
+
+int launch_var2_biquad_coef(const Var2BiquadGradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.causal) hipLaunchKernelGGL((var2_biquad_coef_kernel<true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_biquad_coef_kernel<false>), grid, block, 0, stream, a);
+    return launched("var2_biquad_coef_1d");
 }
 
 int launch_var2_biquad_grad(const Var2BiquadGradArgs &a, hipStream_t stream) {

@@ -523,4 +523,225 @@ int run_var2_cascade_backward(rf_var2_plan *plan, const void *in, const rf_var2_
     return rc == RF_OK ? timer.finish() : rc;
 }
 
+// ---- the cascade that keeps every section's result ---------------------------------------------------------------------------------
+//   forward    run_var2_cascade's launches with the link's KEEP instance: section k's v, then its result, in kept[k] (the caller's;
+//              K - 1 of them), the last section's in out.  The values of out are run_var2_cascade's.
+//   backward   no rerun.  var2_adj_tails_1d on grad_out with the last section's coefficients; then, per boundary from the last one
+//              down, var2_carry_1d and var2_adj_link_1d -- the final stage of section k's adjoint scan, the gradient that enters
+//              section k - 1 formed on lam_k in registers and stored to the plan's signal G (plan->cascade, its first span), in
+//              place from the second boundary on, and the adjoint tails of section k - 1 -- with, where coefficient gradients are
+//              asked for, lam_k stored to the plan's lam (var2_adj_link_keep_1d) and var2_biquad_coef_1d on it; then
+//              var2_carry_1d, var2_adj_pass2_1d into lam and var2_biquad_grad_1d for section 0.
+const char *var2_cascade_keep_name(int n_sections, size_t i) {
+    if (i == 0) return "var2_biquad_tails_1d";
+    if (i + 1 == (size_t)var2_cascade_launches(n_sections)) return "var2_pass2_1d";
+    return i % 2 == 1 ? "var2_carry_1d" : "var2_link_keep_1d";
+}
+
+const char *var2_cascade_kept_backward_name(int n_sections, bool with_coefficients, size_t i) {
+    static const char *const last[3] = {"var2_carry_1d", "var2_adj_pass2_1d", "var2_biquad_grad_1d"};
+    const size_t launches = (size_t)var2_cascade_kept_backward_launches(n_sections, with_coefficients);
+    if (i == 0) return "var2_adj_tails_1d";
+    if (i + 3 >= launches) return last[i + 3 - launches];
+    const size_t at = (i - 1) % (with_coefficients ? 3 : 2);      // within the launches of one boundary
+    return at == 0 ? "var2_carry_1d" : at == 2 ? "var2_biquad_coef_1d" : with_coefficients ? "var2_adj_link_keep_1d" : "var2_adj_link_1d";
+}
+
+namespace {
+
+// the kept signals of a call, one "kept k" check each: required or, where not, aligned if given
+int check_kept(const void *const *kept, int count, bool required) {
+    for (int k = 0; k < count; k++) {
+        int rc = check_plane("kept", k, {{kept ? kept[k] : nullptr, required}}, 15u, "null pointer (a kept signal)",
+                             "the var2 scans need 16-byte aligned pointers");
+        if (rc != RF_OK) return rc;
+    }
+    return RF_OK;
+}
+
+Var2BiquadGradArgs grad_args(const rf_var2_plan *plan, const rf_var2_section &s, const rf_var2_section_grad *g, const float *x, const float *y,
+                             float *grad_in) {
+    Var2BiquadGradArgs a{};
+    a.lam = plan->lam;
+    a.x = x;
+    a.y = y;
+    a.b0 = (const float *)s.b0;
+    a.b1 = (const float *)s.b1;
+    a.b2 = (const float *)s.b2;
+    a.grad_in = grad_in;
+    if (g) {
+        a.grad_b0 = (float *)g->b0;
+        a.grad_b1 = (float *)g->b1;
+        a.grad_b2 = (float *)g->b2;
+        a.grad_a1 = (float *)g->a1;
+        a.grad_a2 = (float *)g->a2;
+    }
+    a.n = (int32_t)plan->length;
+    a.n_lines = plan->n_lines;
+    a.causal = plan->causal ? 1 : 0;
+    a.with_coefficients = g ? 1 : 0;
+    a.stride = plan->stride;
+    return a;
+}
+
+}  // namespace
+
+int run_var2_cascade_keep(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out, void *const *kept,
+                          hipStream_t stream, float *ms_out, const char **names_out, int capacity, bool timed) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
+    const int K = n_sections;
+    const size_t launches = (size_t)var2_cascade_launches(K);
+    if (timed) {
+        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_keep_name(K, i); }, ms_out, names_out, capacity);
+        if (rc != RF_OK) return rc;
+    }
+    if (!sections) return refuse(RF_ERR_INVALID_ARG, "null sections");
+    int rc = check_plane("signal", 0, {{in}, {out}}, 15u, "null pointer (in, out)", "the var2 scans need 16-byte aligned pointers");
+    if (rc == RF_OK) rc = check_kept(kept, K - 1, true);
+    if (rc == RF_OK) rc = check_sections(sections, K);
+    if (rc != RF_OK) return rc;
+    const size_t bytes = plan->span_bytes();
+    SectionLists coefficients("coefficient", K);
+    for (int k = 0; k < K; k++)
+        coefficients.planes.insert(coefficients.planes.end(), {sections[k].b0, sections[k].b1, sections[k].b2, sections[k].a1, sections[k].a2});
+    std::vector<PlaneList> read;
+    for (int k = 0; k < K; k++) read.push_back(coefficients.list(k, 5, bytes, ": a coefficient signal is read while outputs are stored"));
+    const void *const result[1] = {out}, *const input[1] = {in};
+    read.push_back({"in", input, 1, bytes,
+                    ": in == out is not allowed for a biquad (the first launch stores the feed-forward part while neighbouring groups still read in)"});
+    const PlaneList written[2] = {{"out", result, 1, bytes}, {"kept", (const void *const *)kept, K - 1, bytes}};
+    rc = check_written_planes(written, 1, read.data(), (int)read.size(), {"grad_out", nullptr, 0, bytes});      // out, as run_var2_cascade refuses it
+    if (rc != RF_OK) return rc;
+    read.back().why = ": a kept signal is stored while neighbouring groups still read in";
+    rc = check_written_planes(written, 2, read.data(), (int)read.size(), {"grad_out", nullptr, 0, bytes});      // then the kept signals
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    LaunchTimer timer(stream, ms_out, launches);
+    if (timer.status() != RF_OK) return timer.status();
+    float *signals[RF_VAR2_MAX_SECTIONS] = {};
+    for (int k = 0; k + 1 < K; k++) signals[k] = (float *)kept[k];
+    signals[K - 1] = (float *)out;
+    rc = launch_sections(plan, in, sections, K, nullptr, signals, stream, timer);
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+int run_var2_cascade_kept_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *const *kept,
+                                   const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, hipStream_t stream,
+                                   float *ms_out, const char **names_out, int capacity, bool timed) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
+    const int K = n_sections;
+    const bool with_coefficients = grads != nullptr;
+    const size_t launches = (size_t)var2_cascade_kept_backward_launches(K, with_coefficients);
+    if (timed) {
+        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_kept_backward_name(K, with_coefficients, i); }, ms_out, names_out, capacity);
+        if (rc != RF_OK) return rc;
+    }
+    if (!sections) return refuse(RF_ERR_INVALID_ARG, "null sections");
+    for (int k = 0; with_coefficients && k < K; k++) {
+        const rf_var2_section_grad &g = grads[k];
+        const int given = (g.b0 != nullptr) + (g.b1 != nullptr) + (g.b2 != nullptr) + (g.a1 != nullptr) + (g.a2 != nullptr);
+        if (given != 5)
+            return refuse(RF_ERR_INVALID_ARG, "section %lld: the five coefficient gradients are all given, or grads is null (%lld given)", k, given);
+    }
+    // without coefficient gradients nothing of the forward is read: in, out and kept may be null
+    int rc = check_plane("signal", 0, {{in, with_coefficients}, {grad_out}, {grad_in}, {out, with_coefficients}}, 15u,
+                         "null pointer (grad_out, grad_in; in and out where coefficient gradients are asked for)",
+                         "the var2 scans need 16-byte aligned pointers");
+    if (rc == RF_OK) rc = check_kept(kept, K - 1, with_coefficients);
+    if (rc == RF_OK) rc = check_sections(sections, K);
+    for (int k = 0; rc == RF_OK && with_coefficients && k < K; k++)
+        rc = check_plane("section", k, {{grads[k].b0}, {grads[k].b1}, {grads[k].b2}, {grads[k].a1}, {grads[k].a2}}, 15u,
+                         "null gradient pointer", "the var2 scans need 16-byte aligned pointers (a coefficient gradient)");
+    if (rc != RF_OK) return rc;
+    const size_t bytes = plan->span_bytes();
+    SectionLists coefficients("coefficient", K), gradients("gradient", K);
+    for (int k = 0; k < K; k++) {
+        coefficients.planes.insert(coefficients.planes.end(), {sections[k].b0, sections[k].b1, sections[k].b2, sections[k].a1, sections[k].a2});
+        if (with_coefficients) gradients.planes.insert(gradients.planes.end(), {grads[k].b0, grads[k].b1, grads[k].b2, grads[k].a1, grads[k].a2});
+    }
+    const void *const gin[1] = {grad_in}, *const input[1] = {in}, *const result[1] = {out}, *const gout[1] = {grad_out};
+    std::vector<PlaneList> written, read;
+    written.push_back({"grad_in", gin, 1, bytes});
+    for (int k = 0; with_coefficients && k < K; k++) written.push_back(gradients.list(k, 5, bytes));
+    for (int k = 0; k < K; k++) read.push_back(coefficients.list(k, 5, bytes, ": a coefficient signal is read while outputs are stored"));
+    read.push_back({"in", input, with_coefficients ? 1 : 0, bytes});
+    read.push_back({"out", result, with_coefficients ? 1 : 0, bytes});
+    read.push_back({"kept", kept, with_coefficients ? K - 1 : 0, bytes});
+    rc = check_written_planes(written.data(), (int)written.size(), read.data(), (int)read.size(), {"grad_out", gout, 1, bytes});
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    if (!plan->lam && hipMalloc((void **)&plan->lam, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->lam = nullptr;
+        set_error("hipMalloc of %zu bytes for the adjoint state of the cascade's backward failed", bytes);
+        return RF_ERR_NOMEM;
+    }
+    if (K >= 2 && plan->cascade_spans < 1) {
+        if (hipMalloc((void **)&plan->cascade, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->cascade = nullptr;
+            set_error("hipMalloc of %zu bytes for the gradient between the sections of the cascade's backward failed", bytes);
+            return RF_ERR_NOMEM;
+        }
+        plan->cascade_spans = 1;
+    }
+    LaunchTimer timer(stream, ms_out, launches);
+    if (timer.status() != RF_OK) return timer.status();
+    float *between = plan->cascade;                   // G: g_{k-1}, K >= 2
+    Var2Args a = scan_args(plan, !plan->causal, true);
+    a.x = (const float *)grad_out;
+    a.a1 = (const float *)sections[K - 1].a1;
+    a.a2 = (const float *)sections[K - 1].a2;
+    a.dst = plan->lam;
+    rc = launch_var2_tails(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    for (int k = K - 1; k >= 1 && rc == RF_OK; k--) {
+        rc = launch_var2_carry(a, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        Var2AdjLinkArgs l{};
+        l.x = k == K - 1 ? (const float *)grad_out : between;
+        l.a1 = (const float *)sections[k].a1;
+        l.a2 = (const float *)sections[k].a2;
+        l.b0 = (const float *)sections[k].b0;
+        l.b1 = (const float *)sections[k].b1;
+        l.b2 = (const float *)sections[k].b2;
+        l.prev_a1 = (const float *)sections[k - 1].a1;
+        l.prev_a2 = (const float *)sections[k - 1].a2;
+        l.dst = between;
+        l.keep = with_coefficients ? plan->lam : nullptr;
+        l.tails = a.tails;
+        l.carry = a.carry;
+        l.n = a.n;
+        l.tiles = a.tiles;
+        l.groups = a.groups;
+        l.n_lines = a.n_lines;
+        l.causal = a.causal;
+        l.stride = a.stride;
+        if (rc == RF_OK) rc = launch_var2_adj_link(l, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        if (rc == RF_OK && with_coefficients) {
+            rc = launch_var2_biquad_coef(grad_args(plan, sections[k], &grads[k], (const float *)kept[k - 1],
+                                                   k == K - 1 ? (const float *)out : (const float *)kept[k], nullptr), stream);
+            if (rc == RF_OK) rc = timer.mark();
+        }
+    }
+    a.x = K == 1 ? (const float *)grad_out : between;
+    a.a1 = (const float *)sections[0].a1;
+    a.a2 = (const float *)sections[0].a2;
+    if (rc == RF_OK) rc = launch_var2_carry(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK) rc = launch_var2_pass2(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK) {
+        const float *y = !with_coefficients ? nullptr : K == 1 ? (const float *)out : (const float *)kept[0];
+        rc = launch_var2_biquad_grad(grad_args(plan, sections[0], with_coefficients ? &grads[0] : nullptr, (const float *)in, y, (float *)grad_in), stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
 }  // namespace rf

@@ -30,7 +30,8 @@ struct rf_var2_plan {
     std::vector<std::string> biquad_names, biquad_backward_names;
     // a cascade's backward (rf_var2_plan_backward_cascade) with two sections or more: `cascade_spans` further signals of the
     // plan's span in one allocation -- the gradient between two sections, then the results of all sections but the last --
-    // allocated by the first such call and regrown when a later one asks for more sections
+    // allocated by the first such call and regrown when a later one asks for more sections.  rf_var2_plan_backward_cascade_kept
+    // uses the first span alone (the gradient between two sections) and allocates one span where there is none
     float *cascade = nullptr;
     int cascade_spans = 0;
     ~rf_var2_plan();
@@ -60,4 +61,20 @@ int run_var2_cascade(rf_var2_plan *plan, const void *in, const rf_var2_section *
 int run_var2_cascade_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *out,
                               const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, hipStream_t stream, float *ms_out,
                               const char **names_out, int capacity, bool timed);
+// the cascade whose forward keeps every section's result in signals of the caller's (kept: n_sections - 1 of them), and the
+// backward on them: no rerun, one adjoint link launch per boundary; the plan owns lam and, for two sections or more, the first
+// span of `cascade` (the gradient between two sections)
+const char *var2_cascade_keep_name(int n_sections, size_t i);
+const char *var2_cascade_kept_backward_name(int n_sections, bool with_coefficients, size_t i);
+inline int var2_cascade_kept_backward_launches(int n_sections, bool with_coefficients) {
+    return with_coefficients ? 3 * n_sections + 1 : 2 * n_sections + 2;
+}
+inline size_t var2_cascade_kept_backward_bytes(const rf_var2_plan *plan, int n_sections) {
+    return plan->span_bytes() * (size_t)(n_sections == 1 ? 1 : 2);
+}
+int run_var2_cascade_keep(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, void *out, void *const *kept,
+                          hipStream_t stream, float *ms_out, const char **names_out, int capacity, bool timed);
+int run_var2_cascade_kept_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *const *kept,
+                                   const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, hipStream_t stream,
+                                   float *ms_out, const char **names_out, int capacity, bool timed);
 }  // namespace rf

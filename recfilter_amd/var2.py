@@ -18,7 +18,9 @@ The whole direct-form-I section runs on the same plans (rf_var2_plan_execute_biq
 A cascade of K such sections, each with five coefficient signals of its own, runs in 2 K + 1 launches on one plan
 (rf_var2_plan_execute_cascade / _backward_cascade): `Var2Plan.execute_cascade`, `backward_cascade`, `apply_cascade` and
 `biquad_cascade`.  Autograd saves x, the coefficients and the result -- no intermediate signal: the backward reruns the sections
-into signals the plan owns.
+into signals the plan owns.  With keep=True the forward keeps every section's result in tensors autograd saves
+(rf_var2_plan_execute_cascade_keep) and the backward reruns nothing (rf_var2_plan_backward_cascade_kept: one adjoint link launch
+per boundary between two sections): `Var2Plan.execute_cascade_keep`, `backward_cascade_kept`.
 """
 from __future__ import annotations
 
@@ -297,16 +299,143 @@ class Var2Plan(_PlanHandle):
         call = lambda *report: capi.lib().rf_var2_plan_backward_cascade_timed(self._h, px, array, K, po, pgo, pgi, garray, s, *report)      # noqa: E731
         return grad_in, grads, _timed(call, self.backward_cascade_num_kernels(K))
 
-    def apply_cascade(self, x, sections: Sequence):
+    # -- the cascade for training: the forward keeps every section's result, the backward reruns nothing ----------------------
+    def backward_cascade_kept_num_kernels(self, sections: int, with_coefficients: bool = False) -> int:
+        """2 K + 2 launches without coefficient gradients, 3 K + 1 with them (4 at K = 1 either way)"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_kept_num_kernels(self._h, int(sections), int(bool(with_coefficients))))
+
+    def backward_cascade_kept_bytes(self, sections: int) -> int:
+        """what the plan owns behind a backward_cascade_kept: 1 span at K = 1 (lam), 2 above (lam and the gradient between
+        sections), whatever K"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_kept_bytes(self._h, int(sections)))
+
+    def _kept_array(self, kept, count: int):
+        """the array of the kept signals' addresses (None: a null pointer)"""
+        if kept is None:
+            return None
+        if len(kept) != count:
+            raise ValueError(f"kept: one signal per section but the last ({count}), got {len(kept)}")
+        return (ctypes.c_void_p * max(count, 1))(*(self._pointer(t, f"kept[{k}]").value for k, t in enumerate(kept)))
+
+    def _cascade_keep_arguments(self, x, sections, out, kept, stream):
+        K = len(sections)
+        if self._host_only:
+            p = self._placeholders(2 + 5 * K + K - 1)
+            array = (capi.Var2Section * max(K, 1))(*(capi.Var2Section(*(q.value for q in p[2 + 5 * k:7 + 5 * k])) for k in range(K)))
+            return p[0], array, K, p[1], (ctypes.c_void_p * max(K - 1, 1))(*(q.value for q in p[2 + 5 * K:])), None, None, ctypes.c_void_p()
+        if out is None:
+            out = self._like(x)
+        if kept is None:
+            kept = [self._like(x) for _ in range(K - 1)]
+        array, K = self._section_array(sections, "sections")
+        return self._pointer(x, "x"), array, K, self._pointer(out, "out"), self._kept_array(kept, max(K - 1, 0)), out, list(kept), self._stream(stream)
+
+    def execute_cascade_keep(self, x, sections: Sequence, out=None, kept=None, stream=None):
+        """rf_var2_plan_execute_cascade_keep: execute_cascade with every section's result kept.  Returns (out, kept): kept[k] is
+        section k's result, K - 1 tensors laid out like x (kept=None allocates them); out is execute_cascade's bit for bit.  The
+        kept signals are the caller's: the plan keeps no state between calls."""
+        px, array, K, po, pk, out, kept, s = self._cascade_keep_arguments(x, sections, out, kept, stream)
+        capi.check(capi.lib().rf_var2_plan_execute_cascade_keep(self._h, px, array, K, po, pk, s))
+        return out, kept
+
+    def execute_cascade_keep_timed(self, x, sections: Sequence, out=None, kept=None, stream=None):
+        """rf_var2_plan_execute_cascade_keep_timed: (out, kept, [(kernel name, ms), ...]); synchronises the stream."""
+        px, array, K, po, pk, out, kept, s = self._cascade_keep_arguments(x, sections, out, kept, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_execute_cascade_keep_timed(self._h, px, array, K, po, pk, s, *report)      # noqa: E731
+        return out, kept, _timed(call, self.cascade_num_kernels(K))
+
+    def _backward_cascade_kept_arguments(self, x, sections, kept, out, grad_out, grad_in, grads, stream):
+        K = len(sections)
+        if grads is not None and len(grads) != K:
+            raise ValueError("grads: one tuple (grad_b0, grad_b1, grad_b2, grad_a1, grad_a2) per section, or None")
+        if self._host_only:
+            p = self._placeholders(4 + 5 * K + K - 1)
+            array = (capi.Var2Section * max(K, 1))(*(capi.Var2Section(*(q.value for q in p[4 + 5 * k:9 + 5 * k])) for k in range(K)))
+            pk = (ctypes.c_void_p * max(K - 1, 1))(*(q.value for q in p[4 + 5 * K:]))
+            return p[0], array, K, pk, p[1], p[2], p[3], None, None, grads, ctypes.c_void_p()
+        if grad_in is None:
+            grad_in = self._like(grad_out)
+        array, K = self._section_array(sections, "sections")
+        garray, _ = self._section_array(grads, "grads")
+        return (self._pointer(x, "x"), array, K, self._kept_array(kept, max(K - 1, 0)), self._pointer(out, "out"), self._pointer(grad_out, "grad_out"),
+                self._pointer(grad_in, "grad_in"), garray, grad_in, grads, self._stream(stream))
+
+    def backward_cascade_kept(self, x, sections: Sequence, kept, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_cascade_kept, the adjoint of execute_cascade_keep on what it kept: nothing is rerun -- one adjoint
+        link launch per boundary forms the gradient that enters the section before on the adjoint state in registers.  grads:
+        None (no coefficient gradients: x, kept and out may then be None, nothing of the forward is read) or K tuples of five
+        tensors to be WRITTEN.  grad_in=None allocates it; it may be grad_out itself.  Returns (grad_in, grads).  Asynchronous;
+        uses the plan's workspace and one or two signals of its own (backward_cascade_kept_bytes)."""
+        px, array, K, pk, po, pgo, pgi, garray, grad_in, grads, s = self._backward_cascade_kept_arguments(x, sections, kept, out, grad_out, grad_in, grads, stream)
+        capi.check(capi.lib().rf_var2_plan_backward_cascade_kept(self._h, px, array, K, pk, po, pgo, pgi, garray, s))
+        return grad_in, grads
+
+    def backward_cascade_kept_timed(self, x, sections: Sequence, kept, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_cascade_kept_timed: (grad_in, grads, [(kernel name, ms), ...]); synchronises the stream."""
+        px, array, K, pk, po, pgo, pgi, garray, grad_in, grads, s = self._backward_cascade_kept_arguments(x, sections, kept, out, grad_out, grad_in, grads, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_backward_cascade_kept_timed(self._h, px, array, K, pk, po, pgo, pgi, garray, s, *report)      # noqa: E731
+        return grad_in, grads, _timed(call, self.backward_cascade_kept_num_kernels(K, grads is not None))
+
+    def apply_cascade(self, x, sections: Sequence, keep: bool = False):
         """execute_cascade as a differentiable torch operation: the values are bit for bit execute_cascade's.  Backward is
         backward_cascade -- the input's gradient always, all 5 K coefficient gradients where any coefficient signal requires one.
-        x, the coefficients and the result are saved, no intermediate signal; no double backward."""
-        return _cascade_function().apply(self, x, *(t for s in sections for t in s))
+        x, the coefficients and the result are saved, no intermediate signal; no double backward.
+        keep=True: the same values, and the backward is backward_cascade_kept.  Where a coefficient signal requires a gradient
+        the forward is execute_cascade_keep and the K - 1 kept signals are saved beside x, the coefficients and the result; where
+        only x does, the forward is execute_cascade and the coefficients alone are saved."""
+        function = _cascade_kept_function() if keep else _cascade_function()
+        return function.apply(self, x, *(t for s in sections for t in s))
 
 
 _var2_function = None
 _var2_biquad_function = None
 _var2_cascade_function = None
+_var2_cascade_kept_function = None
+
+
+def _cascade_kept_function():
+    """the torch.autograd.Function behind Var2Plan.apply_cascade(keep=True): (plan, x, then the 5 K coefficient signals)"""
+    global _var2_cascade_kept_function
+    if _var2_cascade_kept_function is not None:
+        return _var2_cascade_kept_function
+    import torch
+
+    class Var2CascadeKeptFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, x, *coefficients):
+            ctx.plan = plan
+            sections = [coefficients[i:i + 5] for i in range(0, len(coefficients), 5)]
+            ctx.with_coefficients = any(ctx.needs_input_grad[2:])
+            with torch.cuda.device(x.device):
+                if ctx.with_coefficients:
+                    out, kept = plan.execute_cascade_keep(x, sections)
+                    ctx.save_for_backward(x, *coefficients, out, *kept)
+                else:      # the backward reads nothing of the forward
+                    out = plan.execute_cascade(x, sections)
+                    ctx.save_for_backward(*coefficients)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            need_x, *need = ctx.needs_input_grad[1:]
+            count = len(need)
+            if ctx.with_coefficients:
+                x, *rest = ctx.saved_tensors
+                coefficients, out, kept = rest[:count], rest[count], rest[count + 1:]
+            else:
+                x, coefficients, out, kept = None, ctx.saved_tensors, None, None
+            sections = [coefficients[i:i + 5] for i in range(0, count, 5)]
+            g = _plan_layout(plan, grad_out)
+            grads = [tuple(plan._like(g) for _ in range(5)) for _ in sections] if ctx.with_coefficients else None
+            with torch.cuda.device(g.device):
+                gin, grads = plan.backward_cascade_kept(x, sections, kept, out, g, None, grads)
+            given = [t for s in grads for t in s] if grads is not None else [None] * count
+            return (None, gin if need_x else None) + tuple(t if wanted else None for t, wanted in zip(given, need))
+
+    _var2_cascade_kept_function = Var2CascadeKeptFunction
+    return _var2_cascade_kept_function
 
 
 def _cascade_function():
@@ -479,10 +608,13 @@ def biquad_scan(x, b0, b1, b2, a1, a2, causal: bool = True):
     return out
 
 
-def biquad_cascade(x, sections: Sequence, causal: bool = True):
+def biquad_cascade(x, sections: Sequence, causal: bool = True, keep: bool = False):
     """K direct-form-I sections with time-varying coefficients, one behind the other in one direction, in 2 K + 1 launches:
     `sections` is a sequence of K tuples (b0, b1, b2, a1, a2), 1 <= K <= 16, every signal a device tensor shaped like x, (N,) or
-    (L, N), f32.  Differentiable in x and all 5 K coefficient signals; autograd keeps no signal between the sections.  It shares
+    (L, N), f32.  Differentiable in x and all 5 K coefficient signals; autograd keeps no signal between the sections.
+    keep=True, the route for training: the values are the same bit for bit; where a coefficient signal requires a gradient the
+    forward keeps every section's result (K - 1 more signals saved for the backward) and the backward reruns nothing
+    (Var2Plan.backward_cascade_kept: 3 K + 1 launches for 6 K - 1).  The gradients of the two routes agree to rounding.  It shares
     biquad_scan's plan cache and padding rule: a length that is no multiple of 4 is padded with zeros in every signal, behind the
     end for causal sections, before the start for anticausal ones (a padded section maps zeros to zeros and the recurrence
     reaches the padding last, so the real samples are the unpadded cascade's)."""
@@ -505,7 +637,7 @@ def biquad_cascade(x, sections: Sequence, causal: bool = True):
         where = (0, pad) if causal else (pad, 0)
         signals = tuple(torch.nn.functional.pad(t, where) for t in signals)
     signals = [_plan_layout(plan, t) for t in signals]
-    out = plan.apply_cascade(signals[0], [signals[1 + 5 * k:6 + 5 * k] for k in range(len(sections))])
+    out = plan.apply_cascade(signals[0], [signals[1 + 5 * k:6 + 5 * k] for k in range(len(sections))], keep=keep)
     if pad:
         out = out[..., :n] if causal else out[..., pad:]
     return out
