@@ -1185,6 +1185,35 @@ public:
     /** 4 */
     int biquad_gradient_num_kernels() { prepare(); return rf_var2_plan_backward_biquad_num_kernels(plan); }
     size_t biquad_gradient_bytes() { prepare(); return rf_var2_plan_backward_biquad_bytes(plan); }
+    /** The section with its coefficients at a control rate (rf_var2_plan_execute_biquad_frames): every member of `frames` is
+     *  frames_count(hop) f32 values per line, frame j at sample j * hop, lines frame_stride values apart (0: dense); between two
+     *  frames the kernels interpolate linearly in registers -- bit for bit realize_biquad() on the expanded signals.  hop: a
+     *  power of two, 64 .. 65536.  3 launches.  out overlaps neither in nor a frame array. */
+    void realize_biquad_frames(const void *in, const rf_var2_section &frames, int hop, void *out, int64_t frame_stride = 0,
+                               void *stream = nullptr) {
+        prepare();
+        const int count = frames_count(hop);
+        if (rf_var2_plan_execute_biquad_frames(plan, in, &frames, hop, count, frame_stride > 0 ? frame_stride : count, out, stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize_biquad_frames() (rf_var2_plan_backward_biquad_frames), 4 launches, or 5 with frame gradients:
+     *  frame_grads null (`out` may then be null) or five arrays laid out like the frames, to be written -- the per-sample
+     *  gradients contracted in f64 and rounded once.  grad_in == grad_out is allowed. */
+    void gradient_biquad_frames(const void *in, const rf_var2_section &frames, int hop, const void *out, const void *grad_out, void *grad_in,
+                                const rf_var2_section_grad *frame_grads = nullptr, int64_t frame_stride = 0, void *stream = nullptr) {
+        prepare();
+        const int count = frames_count(hop);
+        if (rf_var2_plan_backward_biquad_frames(plan, in, &frames, hop, count, frame_stride > 0 ? frame_stride : count, out, grad_out, grad_in,
+                                                frame_grads, stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** ceil(length / hop) + 1; 0 for a hop the library refuses */
+    int frames_count(int hop) const { return rf_var2_frames_count((int)desc.length, hop); }
+    /** 3 */
+    int biquad_frames_num_kernels() { prepare(); return rf_var2_plan_biquad_frames_num_kernels(plan); }
+    /** 4, or 5 with frame gradients */
+    int biquad_frames_gradient_num_kernels(bool with_frames) { prepare(); return rf_var2_plan_backward_biquad_frames_num_kernels(plan, with_frames ? 1 : 0); }
+    size_t biquad_frames_gradient_bytes(int hop) { prepare(); return rf_var2_plan_backward_biquad_frames_bytes(plan, hop); }
     /** A cascade of 1 .. RF_VAR2_MAX_SECTIONS such sections in this object's direction (rf_var2_plan_execute_cascade), section
      *  k + 1 on the result of section k, each with five coefficient signals of its own: 2 K + 1 launches, one link launch per
      *  boundary between two sections.  out overlaps neither in nor any coefficient signal. */

@@ -1147,6 +1147,55 @@ int    rf_var2_plan_backward_cascade_kept_timed(rf_var2_plan *plan, const void *
 int    rf_var2_plan_backward_cascade_kept_num_kernels(const rf_var2_plan *plan, int n_sections, int with_coefficient_gradients);
 size_t rf_var2_plan_backward_cascade_kept_bytes(const rf_var2_plan *plan, int n_sections);
 
+/* The section with its coefficients at a control rate (rf_var2_plan_execute_biquad_frames): each of b0, b1, b2, a1, a2 is
+ * n_frames = ceil(length / hop) + 1 f32 FRAMES per line, frame j at sample j * hop, line l frame_stride >= n_frames values
+ * behind the pointer (4-byte aligned).  hop is a power of two, 64 .. 65536.  At n = j * hop + k, 0 <= k < hop, by absolute
+ * position whatever the plan's direction,
+ *     c[n] = fma(k / hop, c[j+1] - c[j], c[j])          (f32; the difference rounded once; c[j * hop] == c[j] exactly)
+ * and on these c[n] the section is rf_var2_plan_execute_biquad's: the same masks by position, the same arithmetic, the same
+ * bits as that call on the expanded signals (rf_var2_expand_frames writes them, one coefficient per call).  Frames have no
+ * masked slots: all of them must be finite.  The kernels read the frames and interpolate in registers: the forward moves 16
+ * bytes per sample for 44.  Launches: "var2_biquad_frames_tails_1d", "var2_carry_1d", "var2_frames_pass2_1d"
+ * (rf_var2_plan_biquad_frames_num_kernels = 3); out overlaps neither in nor a frame array.
+ * rf_var2_plan_backward_biquad_frames: "var2_adj_frames_tails_1d", "var2_carry_1d", "var2_adj_frames_pass2_1d" on grad_out into
+ * the plan's lam, then "var2_biquad_frames_grad_1d": grad_in, rf_var2_plan_backward_biquad's bits on the expanded signals.
+ * With frame gradients (frame_grads: five arrays laid out like the frames, all given; or all null, or frame_grads null, and
+ * out may then be null) that launch also forms the five per-sample gradients of rf_var2_plan_backward_biquad, rounded to f32,
+ * and contracts them with the interpolation's transpose in f64 -- per piece of min(hop, 1024) samples S0 = sum (1 - k / hop) g
+ * and S1 = sum (k / hop) g, every product exact, a lane in the order of its samples, the lanes of a piece by a fixed tree --
+ * into a slab of doubles the plan owns; "var2_frames_fold_1d" adds the pieces of interval j (S0) and of interval j - 1 (S1) in
+ * order and rounds once: dL/dc_j.  No atomics; two calls give the same bits.
+ * rf_var2_plan_backward_biquad_frames_num_kernels(plan, with) = 4 or 5.  rf_var2_plan_backward_biquad_frames_bytes(plan, hop):
+ * lam, 4 * ((n_lines - 1) * stride + length), shared with the other backward calls, plus the slab, 80 * n_lines * ceil(length /
+ * min(hop, 1024)); 0 for a refused hop.  Both are allocated by the first call that needs them (the slab regrown by a call with a
+ * smaller hop); rf_var2_plan_workspace_bytes is unchanged and the plan keeps no state between calls.
+ * Refusals, before any HIP call, in this order: a hop that is no power of two in 64 .. 65536 (RF_ERR_UNSUPPORTED); n_frames !=
+ * rf_var2_frames_count(length, hop); frame_stride < n_frames; a null or misaligned pointer (frames, in, out, grad_out, grad_in);
+ * in == out or out overlapping a frame array; frame gradients neither all given nor all null; a written gradient overlapping
+ * anything else (grad_in == grad_out is allowed); last, a host-only plan (RF_ERR_HIP).
+ * rf_var2_expand_frames: out[l * stride + n] = c[n] for one coefficient on `lines` lines of `length` samples (a multiple of 4;
+ * out 16-byte aligned, apart from the frames), on the current device: "var2_expand_frames_1d".
+ * Out of scope: hops below 64 or not powers of two (480, for example); hold or cubic interpolation; frames for cascades;
+ * frames for rf_var_plan; 16-bit signals, second derivatives, sharding. */
+int    rf_var2_frames_count(int length, int hop);                        /* ceil(length / hop) + 1; 0: hop refused */
+int    rf_var2_expand_frames(const void *frames, int hop, int n_frames, int64_t frame_stride, int length, int lines, int64_t stride,
+                             void *out, void *stream);
+int    rf_var2_plan_execute_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames,
+                                          int64_t frame_stride, void *out, void *stream);
+int    rf_var2_plan_execute_biquad_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop,
+                                                int n_frames, int64_t frame_stride, void *out, void *stream, float *ms_out,
+                                                const char **names_out, int capacity);
+int    rf_var2_plan_backward_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames,
+                                           int64_t frame_stride, const void *out, const void *grad_out, void *grad_in,
+                                           const rf_var2_section_grad *frame_grads, void *stream);
+int    rf_var2_plan_backward_biquad_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop,
+                                                 int n_frames, int64_t frame_stride, const void *out, const void *grad_out,
+                                                 void *grad_in, const rf_var2_section_grad *frame_grads, void *stream, float *ms_out,
+                                                 const char **names_out, int capacity);
+int    rf_var2_plan_biquad_frames_num_kernels(const rf_var2_plan *plan);
+int    rf_var2_plan_backward_biquad_frames_num_kernels(const rf_var2_plan *plan, int with_frame_gradients);
+size_t rf_var2_plan_backward_biquad_frames_bytes(const rf_var2_plan *plan, int hop);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);
 const char *rf_version(void);

@@ -93,6 +93,9 @@ EXPORTED_SYMBOLS = [
     "rf_var2_plan_execute_cascade_keep", "rf_var2_plan_execute_cascade_keep_timed", "rf_var2_plan_backward_cascade_kept",
     "rf_var2_plan_backward_cascade_kept_timed", "rf_var2_plan_backward_cascade_kept_num_kernels",
     "rf_var2_plan_backward_cascade_kept_bytes",
+    "rf_var2_frames_count", "rf_var2_expand_frames", "rf_var2_plan_execute_biquad_frames", "rf_var2_plan_execute_biquad_frames_timed",
+    "rf_var2_plan_backward_biquad_frames", "rf_var2_plan_backward_biquad_frames_timed", "rf_var2_plan_biquad_frames_num_kernels",
+    "rf_var2_plan_backward_biquad_frames_num_kernels", "rf_var2_plan_backward_biquad_frames_bytes",
 ]
 
 
@@ -336,6 +339,17 @@ def lib() -> ctypes.CDLL:
     L.rf_var2_plan_backward_cascade_kept_num_kernels.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.rf_var2_plan_backward_cascade_kept_bytes.argtypes = [vp, ctypes.c_int]
     L.rf_var2_plan_backward_cascade_kept_bytes.restype = ctypes.c_size_t
+    L.rf_var2_frames_count.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.rf_var2_expand_frames.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, vp, vp]
+    frames = [vp, vp, sp, ctypes.c_int, ctypes.c_int, ctypes.c_int64]      # plan, in, the frames, hop, n_frames, frame_stride
+    L.rf_var2_plan_execute_biquad_frames.argtypes = frames + [vp, vp]
+    L.rf_var2_plan_execute_biquad_frames_timed.argtypes = frames + [vp, vp] + report
+    L.rf_var2_plan_backward_biquad_frames.argtypes = frames + [vp, vp, vp, sp, vp]
+    L.rf_var2_plan_backward_biquad_frames_timed.argtypes = frames + [vp, vp, vp, sp, vp] + report
+    L.rf_var2_plan_biquad_frames_num_kernels.argtypes = [vp]
+    L.rf_var2_plan_backward_biquad_frames_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_biquad_frames_bytes.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_biquad_frames_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

@@ -861,6 +861,62 @@ int rf_var2_plan_backward_biquad_timed(rf_var2_plan *plan, const void *in, const
     });
 }
 
+// ---- the section on control-rate frames ---------------------------------------------------------------------------------------------
+int rf_var2_frames_count(int length, int hop) { return var2_frames_count(length, hop); }
+
+int rf_var2_expand_frames(const void *frames, int hop, int n_frames, int64_t frame_stride, int length, int lines, int64_t stride, void *out,
+                          void *stream) {
+    return fenced("rf_var2_expand_frames", [&] {
+        return run_var2_expand_frames(frames, hop, n_frames, frame_stride, length, lines, stride, out, (hipStream_t)stream);
+    });
+}
+
+int rf_var2_plan_biquad_frames_num_kernels(const rf_var2_plan *plan) { return plan ? (int)plan->frames_names.size() : 0; }
+int rf_var2_plan_backward_biquad_frames_num_kernels(const rf_var2_plan *plan, int with_frame_gradients) {
+    return plan ? (int)plan->frames_backward_names[with_frame_gradients ? 1 : 0].size() : 0;
+}
+size_t rf_var2_plan_backward_biquad_frames_bytes(const rf_var2_plan *plan, int hop) {
+    return plan && var2_hop_ok(hop) ? plan->span_bytes() + plan->frames_slab_needed(hop) : 0;
+}
+
+int rf_var2_plan_execute_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames,
+                                       int64_t frame_stride, void *out, void *stream) {
+    return fenced("rf_var2_plan_execute_biquad_frames", [&] {
+        return run_var2_biquad_frames(plan, in, frames, hop, n_frames, frame_stride, out, (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var2_plan_execute_biquad_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames,
+                                             int64_t frame_stride, void *out, void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_execute_biquad_frames_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        if (int rc = timed_names(plan->frames_names, ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var2_biquad_frames(plan, in, frames, hop, n_frames, frame_stride, out, (hipStream_t)stream, ms_out);
+    });
+}
+
+int rf_var2_plan_backward_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames,
+                                        int64_t frame_stride, const void *out, const void *grad_out, void *grad_in,
+                                        const rf_var2_section_grad *frame_grads, void *stream) {
+    return fenced("rf_var2_plan_backward_biquad_frames", [&] {
+        return run_var2_biquad_frames_backward(plan, in, frames, hop, n_frames, frame_stride, out, grad_out, grad_in, frame_grads,
+                                               (hipStream_t)stream, nullptr);
+    });
+}
+
+int rf_var2_plan_backward_biquad_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames,
+                                              int64_t frame_stride, const void *out, const void *grad_out, void *grad_in,
+                                              const rf_var2_section_grad *frame_grads, void *stream, float *ms_out, const char **names_out,
+                                              int capacity) {
+    return fenced("rf_var2_plan_backward_biquad_frames_timed", [&] {
+        if (!plan) { set_error("null argument"); return (int)RF_ERR_INVALID_ARG; }
+        const bool with = frame_grads && frame_grads->b0 && frame_grads->b1 && frame_grads->b2 && frame_grads->a1 && frame_grads->a2;
+        if (int rc = timed_names(plan->frames_backward_names[with ? 1 : 0], ms_out, names_out, capacity); rc != RF_OK) return rc;
+        return run_var2_biquad_frames_backward(plan, in, frames, hop, n_frames, frame_stride, out, grad_out, grad_in, frame_grads,
+                                               (hipStream_t)stream, ms_out);
+    });
+}
+
 int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                      void *dx, void *dy, int32_t device, void *stream) {
     return fenced("rf_var_distances", [&] {

@@ -109,6 +109,68 @@ struct Var2AdjLinkArgs {
     int64_t stride;
 };
 
+// ---- coefficients from control-rate frames (rf_var2_plan_execute_biquad_frames) -----------------------------------------------------
+// A coefficient of line l is n_frames f32 values, frame j at sample j * hop, l * frame_stride values behind the pointer; hop =
+// 1 << hop_shift, 64 .. 65536, inv_hop = 1 / hop.  At n = j * hop + k the coefficient is fma(k * inv_hop, c[j+1] - c[j], c[j]).
+// One stage of the section on all lines: the FF tails stage (x = in, dst = v, all five coefficients), its final stage (x = dst = v;
+// a1, a2) or a stage of the adjoint scan (adjoint = 1; a1, a2 read one and two samples along the forward's direction).
+struct Var2FramesArgs {
+    const float *x;
+    const float *b0, *b1, *b2, *a1, *a2;      // frames
+    float *dst;
+    float *tails;
+    float *carry;
+    int32_t n;
+    int32_t tiles, groups;
+    int32_t n_lines;
+    int32_t causal;                 // the direction of THIS recurrence
+    int32_t adjoint;
+    int32_t hop_shift, n_frames;
+    float inv_hop;
+    int64_t stride, frame_stride;
+};
+
+constexpr int kVar2FrameSums = 10;           // per piece of an interval: S0 and S1 of b0, b1, b2, a1, a2
+constexpr int kVar2GradBlock = 1024;         // samples of a workgroup of var2_biquad_frames_grad_1d
+// The gradients of the section behind its adjoint scan (var2_biquad_frames_grad_1d): grad_in as var2_biquad_grad_1d forms it, the
+// taps interpolated; with_frames: the five per-sample coefficient gradients of that kernel, rounded to f32, contracted in f64 over
+// pieces of min(hop, 1024) samples -- S0 = sum (1 - k / hop) g, S1 = sum (k / hop) g -- into
+//   slab   [line][piece][10] doubles, pieces = ceil(n / min(hop, 1024)) per line
+// var2_frames_fold_1d adds the pieces of the two intervals that meet at a frame, in order, and rounds once: grad[line][frame].
+struct Var2FramesGradArgs {
+    const float *lam, *x, *y;
+    const float *b0, *b1, *b2;      // frames
+    float *grad_in;
+    double *slab;
+    float *grad_b0, *grad_b1, *grad_b2, *grad_a1, *grad_a2;      // the fold's: [line][frame]
+    int32_t n;
+    int32_t n_lines;
+    int32_t causal;                 // the direction of the FORWARD section
+    int32_t with_frames;
+    int32_t hop_shift, n_frames;
+    int32_t pieces;                 // per line
+    float inv_hop;
+    int64_t stride, frame_stride;
+};
+inline int64_t var2_frames_pieces(int64_t n, int hop) { const int64_t piece = hop < kVar2GradBlock ? hop : kVar2GradBlock; return (n + piece - 1) / piece; }
+
+// One coefficient expanded to audio rate on all lines (var2_expand_frames_1d): out[line * stride + n], n a multiple of 4.
+struct Var2ExpandArgs {
+    const float *frames;
+    float *out;
+    int32_t n;
+    int32_t n_lines;
+    int32_t hop_shift, n_frames;
+    float inv_hop;
+    int64_t stride, frame_stride;
+};
+int launch_var2_expand_frames(const Var2ExpandArgs &a, hipStream_t stream);      // "var2_expand_frames_1d"
+// "var2_biquad_frames_tails_1d" (a.adjoint == 0), "var2_adj_frames_tails_1d"
+int launch_var2_frames_tails(const Var2FramesArgs &a, hipStream_t stream);
+int launch_var2_frames_pass2(const Var2FramesArgs &a, hipStream_t stream);       // "var2_frames_pass2_1d", "var2_adj_frames_pass2_1d"
+int launch_var2_frames_grad(const Var2FramesGradArgs &a, hipStream_t stream);    // "var2_biquad_frames_grad_1d"
+int launch_var2_frames_fold(const Var2FramesGradArgs &a, hipStream_t stream);    // "var2_frames_fold_1d"
+
 constexpr int kVar2Tile = 64;            // samples of a tile: one lane
 constexpr int kVar2GroupTiles = 64;      // tiles of a group: one wave
 int launch_var2_tails(const Var2Args &a, hipStream_t stream);      // "var2_tails_1d", "var2_adj_tails_1d"

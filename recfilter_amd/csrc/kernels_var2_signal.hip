@@ -57,6 +57,16 @@
 //                          along, b0 lam_k)) stored -- in place -- and the adjoint tails of section k - 1 on it.
 //   var2_adj_link_keep_1d  the same with lam_k stored too, for
 //   var2_biquad_coef_1d    the five coefficient gradients of a section from lam, x and y: the COEF half of var2_biquad_grad_1d.
+//
+// The section with its coefficients as control-rate frames (rf_var2_plan_execute_biquad_frames): frame j of a coefficient at sample
+// j * hop, hop a power of two >= 64, linear interpolation in registers -- no coefficient signal is read.
+//   var2_expand_frames_1d          c[n] of one coefficient at audio rate: what the kernels below form, bit for bit
+//   var2_biquad_frames_tails_1d    var2_biquad_tails_1d reading x and the frames; var2_frames_pass2_1d, var2_adj_frames_tails_1d and
+//                                  var2_adj_frames_pass2_1d are the other stages (var2_frames_kernel); var2_carry_1d serves unchanged
+//   var2_biquad_frames_grad_1d     grad_in as var2_biquad_grad_1d forms it and, where asked for, that kernel's five per-sample
+//                                  gradients contracted in f64 with the interpolation's transpose, per piece of min(hop, 1024)
+//                                  samples, into a slab of the plan's
+//   var2_frames_fold_1d            the pieces that meet at a frame added in order, rounded once: the five frame gradients
 #include "kernels_var2.h"
 
 #include "var_device.h"
@@ -769,6 +779,272 @@ __global__ void __launch_bounds__(kGradLanes) var2_biquad_coef_kernel(Var2Biquad
     *reinterpret_cast<float4 *>(a.grad_a2 + first + at) = make_float4(h2[0], h2[1], h2[2], h2[3]);
 }
 
+// ---- coefficients from control-rate frames ---------------------------------------------------------------------------------------
+// Frame j of a coefficient sits at sample j * hop, hop = 1 << shift >= 64: a tile lies inside one interval.  At n = j * hop + k
+//   c[n] = fma(k / hop, c[j+1] - c[j], c[j])          (k / hop exact; the difference rounded once; c[j * hop] == c[j])
+// and every kernel below forms it with frame_lerp, so all of them see one value per sample.
+struct FramePair {
+    float c, d;      // c[j] and c[j+1] - c[j]
+};
+__device__ __forceinline__ FramePair frame_pair(const float *frames, int j) {
+    const float c = frames[j];
+    return {c, frames[j + 1] - c};
+}
+__device__ __forceinline__ float frame_lerp(const FramePair &p, int k, float inv_hop) { return __builtin_fmaf((float)k * inv_hop, p.d, p.c); }
+// the coefficient at sample `at` of the line, 0 <= at < n: its interval has both frames (n_frames = ceil(n / hop) + 1)
+__device__ __forceinline__ float frame_at(const float *frames, int at, int shift, float inv_hop) {
+    return frame_lerp(frame_pair(frames, at >> shift), at & ((1 << shift) - 1), inv_hop);
+}
+
+// var2_signal_kernel with the coefficient signals formed in registers: the same masks by position, the same order of the
+// feed-forward part, the same recurrences, scan and stores.  Nothing but x goes through the transposition, and a coefficient
+// lives for one step.  ADJ: the three coefficients its shifted reads reach beyond the tile come from frame_at at a position
+// clamped into the line -- the next interval's where the tile ends at a frame -- and are masked by position like the rest.
+template <bool REV, bool ADJ, bool FINAL, bool FF = false>
+__global__ void __launch_bounds__(64) var2_frames_kernel(Var2FramesArgs a) {
+    static_assert(!FF || (!ADJ && !FINAL), "the feed-forward part stands in front of a forward tails stage");
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x, line = blockIdx.y;
+    const int n = a.n;
+    const int s0 = g * kGroupSamples;                 // below 2^30 + 4096
+    const int t = g * kGroupTiles + lane, t0 = t * T;
+    const int64_t first = (int64_t)line * a.stride, frame0 = (int64_t)line * a.frame_stride;
+    const int shift = a.hop_shift;
+    const float inv_hop = a.inv_hop;
+    // the tile's interval; a tile beyond the line takes the last one (everything in it is masked)
+    const int j = min(t0 >> shift, a.n_frames - 2), k0 = t0 & ((1 << shift) - 1);
+    const float *px = a.x + first;
+    float raw[T], x[T];
+    request_group(px, n, s0, raw);
+    const FramePair f1 = frame_pair(a.a1 + frame0, j), f2 = frame_pair(a.a2 + frame0, j);
+    const int near = REV ? t0 + T : t0 - 1, far = REV ? t0 + T + 1 : t0 - 2;      // beyond the tile, against the recurrence
+    const int at_near = max(min(near, n - 1), 0), at_far = max(min(far, n - 1), 0);
+    float nb1 = 0.0f, nb2_near = 0.0f, nb2_far = 0.0f;
+    if constexpr (ADJ) {
+        nb1 = frame_at(a.a1 + frame0, at_near, shift, inv_hop);
+        nb2_near = frame_at(a.a2 + frame0, at_near, shift, inv_hop);
+        nb2_far = frame_at(a.a2 + frame0, at_far, shift, inv_hop);
+    }
+    float y1 = 0.0f, y2 = 0.0f;                       // the state that enters the tile
+    if constexpr (FINAL) {
+        const int tt = min(t, a.tiles - 1);
+        float m[kVar2Components];
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index_of(a.n_lines, a.tiles, i, line, tt)];
+        apply_map(m, a.carry[((int64_t)0 * a.n_lines + line) * a.groups + g], a.carry[((int64_t)1 * a.n_lines + line) * a.groups + g], y1, y2);
+    }
+    if constexpr (FF) {
+        float x_near = px[at_near], x_far = px[at_far];
+        x_near = (near < 0 || near >= n) ? 0.0f : x_near;
+        x_far = (far < 0 || far >= n) ? 0.0f : x_far;
+        const FramePair f0 = frame_pair(a.b0 + frame0, j), g1 = frame_pair(a.b1 + frame0, j), g2 = frame_pair(a.b2 + frame0, j);
+        float u[T];
+        transpose_in(raw, lds, u);
+#pragma unroll
+        for (int i = 0; i < T; i++) u[i] = t0 + i < n ? u[i] : 0.0f;
+        // feed_forward's arithmetic: b0 x, then b1~ on the sample before, then b2~ on the one before that
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            const int at = t0 + i;
+            const float one = REV ? (i + 1 < T ? u[i + 1 < T ? i + 1 : 0] : x_near) : (i >= 1 ? u[i >= 1 ? i - 1 : 0] : x_near);
+            const float two = REV ? (i + 2 < T ? u[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? x_near : x_far))
+                                  : (i >= 2 ? u[i >= 2 ? i - 2 : 0] : (i == 1 ? x_near : x_far));
+            const bool no_one = REV ? at >= n - 1 : (at < 1 || at >= n), no_two = REV ? at >= n - 2 : (at < 2 || at >= n);
+            float v = (at < n ? frame_lerp(f0, k0 + i, inv_hop) : 0.0f) * u[i];
+            v = __builtin_fmaf(no_one ? 0.0f : frame_lerp(g1, k0 + i, inv_hop), one, v);
+            x[i] = __builtin_fmaf(no_two ? 0.0f : frame_lerp(g2, k0 + i, inv_hop), two, v);
+        }
+        store_group(lds, a.dst + first, n, s0, x);      // v: what var2_frames_pass2_1d reads, in place
+#pragma unroll
+        for (int i = 0; i < T; i++) x[i] = t0 + i < n ? x[i] : 0.0f;
+    } else {
+        transpose_in(raw, lds, x);
+#pragma unroll
+        for (int i = 0; i < T; i++) x[i] = t0 + i < n ? x[i] : 0.0f;
+    }
+    // the coefficients of step i, masked by position: the tile's own, or (ADJ) those one and two samples further along the
+    // forward's direction
+    auto coefficients = [&](int i, float &c1, float &c2) {
+        const int at = t0 + i;
+        if constexpr (!ADJ) {
+            c1 = frame_lerp(f1, k0 + i, inv_hop);
+            c2 = frame_lerp(f2, k0 + i, inv_hop);
+        } else if constexpr (REV) {
+            c1 = i + 1 < T ? frame_lerp(f1, k0 + i + 1, inv_hop) : nb1;
+            c2 = i + 2 < T ? frame_lerp(f2, k0 + i + 2, inv_hop) : (i + 2 == T ? nb2_near : nb2_far);
+        } else {
+            c1 = i >= 1 ? frame_lerp(f1, k0 + i - 1, inv_hop) : nb1;
+            c2 = i >= 2 ? frame_lerp(f2, k0 + i - 2, inv_hop) : (i == 1 ? nb2_near : nb2_far);
+        }
+        if constexpr (REV) {
+            c1 = at >= n - 1 ? 0.0f : c1;
+            c2 = at >= n - 2 ? 0.0f : c2;
+        } else {
+            c1 = (at < 1 || at >= n) ? 0.0f : c1;
+            c2 = (at < 2 || at >= n) ? 0.0f : c2;
+        }
+    };
+    if constexpr (FINAL) {
+#pragma unroll
+        for (int s = 0; s < T; s++) {
+            const int i = REV ? T - 1 - s : s;
+            float c1, c2;
+            coefficients(i, c1, c2);
+            const float y = step2(c1, c2, x[i], y1, y2);
+            x[i] = y; y2 = y1; y1 = y;
+        }
+        store_group(lds, a.dst + first, n, s0, x);
+    } else {
+        float u1 = 1.0f, u2 = 0.0f, w1 = 0.0f, w2 = 1.0f;
+#pragma unroll
+        for (int s = 0; s < T; s++) {
+            const int i = REV ? T - 1 - s : s;
+            float c1, c2;
+            coefficients(i, c1, c2);
+            const float y = step2(c1, c2, x[i], y1, y2);
+            const float u = step2(c1, c2, 0.0f, u1, u2);
+            const float w = step2(c1, c2, 0.0f, w1, w2);
+            y2 = y1; y1 = y; u2 = u1; u1 = u; w2 = w1; w1 = w;
+        }
+        float own[kVar2Components], map[kVar2Components], whole[kVar2Components];
+        own[VAR2_E0] = y1; own[VAR2_E1] = y2;
+        own[VAR2_P00] = u1; own[VAR2_P10] = u2;
+        own[VAR2_P01] = w1; own[VAR2_P11] = w2;
+        scan_group<REV>(own, map, whole);
+        if (t < a.tiles) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++) a.tails[map_index_of(a.n_lines, a.tiles, i, line, t)] = map[i];
+        }
+        if (lane == (REV ? 0 : 63)) {
+#pragma unroll
+            for (int i = 0; i < kVar2Components; i++)
+                a.tails[(int64_t)kVar2Components * a.n_lines * a.tiles + ((int64_t)i * a.n_lines + line) * a.groups + g] = whole[i];
+        }
+    }
+}
+
+// one coefficient at audio rate: four samples per lane, which share an interval (hop is a multiple of 4)
+__global__ void __launch_bounds__(kGradLanes) var2_expand_frames_kernel(Var2ExpandArgs a) {
+    const int at = (blockIdx.x * kGradLanes + threadIdx.x) * 4;      // below 2^30 + 1024
+    if (at >= a.n) return;
+    const FramePair p = frame_pair(a.frames + (int64_t)blockIdx.y * a.frame_stride, at >> a.hop_shift);
+    const int k = at & ((1 << a.hop_shift) - 1);
+    *reinterpret_cast<float4 *>(a.out + (int64_t)blockIdx.y * a.stride + at) =
+        make_float4(frame_lerp(p, k, a.inv_hop), frame_lerp(p, k + 1, a.inv_hop), frame_lerp(p, k + 2, a.inv_hop), frame_lerp(p, k + 3, a.inv_hop));
+}
+
+// The gradients of the section behind its adjoint scan.  grad_in: var2_biquad_grad_kernel's expression, the taps one and two
+// samples along the forward's direction from frame_at.  FRAMES: that kernel's five per-sample coefficient gradients -- the same
+// products and selects, rounded to f32 -- weighted by 1 - k / hop (S0, to the interval's first frame) and k / hop (S1, to its
+// second) and summed in f64, where every product is exact: a lane in the order of its four samples, the lanes of a piece of
+// min(hop, 1024) samples by a fixed tree -- shuffles within a wave, then the piece's first lane over its waves' sums in order.
+template <bool CAUSAL, bool FRAMES>
+__global__ void __launch_bounds__(kGradLanes) var2_frames_grad_kernel(Var2FramesGradArgs a) {
+    static_assert(kGradLanes * 4 == kVar2GradBlock, "a workgroup's samples");
+    __shared__ double sums[kGradLanes / 64][kVar2FrameSums];
+    const int n = a.n;
+    const int at = (blockIdx.x * kGradLanes + threadIdx.x) * 4;      // below 2^30 + 1024
+    const bool inside = at < n;
+    if (!FRAMES && !inside) return;
+    const int64_t first = (int64_t)blockIdx.y * a.stride, frame0 = (int64_t)blockIdx.y * a.frame_stride;
+    const int shift = a.hop_shift;
+    const float inv_hop = a.inv_hop;
+    constexpr int L0 = CAUSAL ? 0 : 2;      // sample at + k in a window that looks where the adjoint looks
+    constexpr int X0 = CAUSAL ? 2 : 0;      // and in one that looks where the forward looked
+    float lam[6] = {};
+    double s[kVar2FrameSums] = {};
+    if (inside) {
+        load_six<CAUSAL>(a.lam + first, at, n, lam);
+        float gx[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int one = CAUSAL ? at + k + 1 : at + k - 1, two = CAUSAL ? at + k + 2 : at + k - 2;
+            const int i1 = CAUSAL ? L0 + k + 1 : L0 + k - 1, i2 = CAUSAL ? L0 + k + 2 : L0 + k - 2;
+            const float t0 = frame_at(a.b0 + frame0, at + k, shift, inv_hop);
+            const float t1 = frame_at(a.b1 + frame0, max(min(one, n - 1), 0), shift, inv_hop);
+            const float t2 = frame_at(a.b2 + frame0, max(min(two, n - 1), 0), shift, inv_hop);
+            const float c1 = (one < 0 || one >= n) ? 0.0f : t1, c2 = (two < 0 || two >= n) ? 0.0f : t2;
+            gx[k] = __builtin_fmaf(c2, lam[i2], __builtin_fmaf(c1, lam[i1], t0 * lam[L0 + k]));
+        }
+        *reinterpret_cast<float4 *>(a.grad_in + first + at) = make_float4(gx[0], gx[1], gx[2], gx[3]);
+        if constexpr (FRAMES) {
+            float xs[6], ys[6];
+            load_six<!CAUSAL>(a.x + first, at, n, xs);
+            load_six<!CAUSAL>(a.y + first, at, n, ys);
+            const int k0 = at & ((1 << shift) - 1), hop = 1 << shift;
+            const double scale = (double)inv_hop;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int i1 = CAUSAL ? X0 + k - 1 : X0 + k + 1, i2 = CAUSAL ? X0 + k - 2 : X0 + k + 2;
+                const bool no_one = CAUSAL ? at + k < 1 : at + k >= n - 1, no_two = CAUSAL ? at + k < 2 : at + k >= n - 2;
+                const float l = lam[L0 + k];
+                const float gc[5] = {l * xs[X0 + k], no_one ? 0.0f : l * xs[i1], no_two ? 0.0f : l * xs[i2],
+                                     no_one ? 0.0f : -l * ys[i1], no_two ? 0.0f : -l * ys[i2]};
+                const double w1 = (double)(k0 + k) * scale, w0 = (double)(hop - k0 - k) * scale;      // exact
+#pragma unroll
+                for (int c = 0; c < 5; c++) {
+                    s[2 * c] += w0 * (double)gc[c];
+                    s[2 * c + 1] += w1 * (double)gc[c];
+                }
+            }
+        }
+    }
+    if constexpr (FRAMES) {
+        const int piece_lanes = min(1 << shift, kVar2GradBlock) / 4;      // 16 .. 256, a power of two
+        const int wave_lanes = min(piece_lanes, 64);
+        for (int off = wave_lanes >> 1; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int q = 0; q < kVar2FrameSums; q++) s[q] += __shfl_down(s[q], off);
+        }
+        const int tid = threadIdx.x;
+        if (piece_lanes > 64) {
+            if ((tid & 63) == 0) {
+#pragma unroll
+                for (int q = 0; q < kVar2FrameSums; q++) sums[tid >> 6][q] = s[q];
+            }
+            __syncthreads();
+        }
+        if ((tid & (piece_lanes - 1)) == 0 && inside) {
+            if (piece_lanes > 64) {
+                for (int w = 1; w < piece_lanes / 64; w++) {
+#pragma unroll
+                    for (int q = 0; q < kVar2FrameSums; q++) s[q] += sums[(tid >> 6) + w][q];
+                }
+            }
+            const int piece = at / (piece_lanes * 4);
+            double *dst = a.slab + ((int64_t)blockIdx.y * a.pieces + piece) * kVar2FrameSums;
+#pragma unroll
+            for (int q = 0; q < kVar2FrameSums; q++) dst[q] = s[q];
+        }
+    }
+}
+
+// dL/dc_j = (the S0 of interval j's pieces, in order) + (the S1 of interval j - 1's pieces, in order), rounded once to f32.
+// One lane per frame; a piece that begins beyond the line does not exist.
+__global__ void __launch_bounds__(kGradLanes) var2_frames_fold_kernel(Var2FramesGradArgs a) {
+    const int j = blockIdx.x * kGradLanes + threadIdx.x, line = blockIdx.y;
+    if (j >= a.n_frames) return;
+    const int per_interval = max(1, (1 << a.hop_shift) / kVar2GradBlock);
+    const double *slab = a.slab + (int64_t)line * a.pieces * kVar2FrameSums;
+    float *const grads[5] = {a.grad_b0, a.grad_b1, a.grad_b2, a.grad_a1, a.grad_a2};
+    double own[5] = {}, before[5] = {};
+    if (j + 1 < a.n_frames) {
+        for (int p = j * per_interval; p < min((j + 1) * per_interval, a.pieces); p++) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) own[c] += slab[(int64_t)p * kVar2FrameSums + 2 * c];
+        }
+    }
+    if (j >= 1) {
+        for (int p = (j - 1) * per_interval; p < min(j * per_interval, a.pieces); p++) {
+#pragma unroll
+            for (int c = 0; c < 5; c++) before[c] += slab[(int64_t)p * kVar2FrameSums + 2 * c + 1];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 5; c++) grads[c][(int64_t)line * a.frame_stride + j] = (float)(own[c] + before[c]);
+}
+
 int launched(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("launch of %s failed: %s", what, hipGetErrorString(e)); return RF_ERR_HIP; }
@@ -856,6 +1132,54 @@ int launch_var2_grad(const Var2GradArgs &a, hipStream_t stream) {
     if (a.causal) hipLaunchKernelGGL((var2_grad_kernel<true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var2_grad_kernel<false>), grid, block, 0, stream, a);
     return launched("var2_grad_1d");
+}
+
+int launch_var2_expand_frames(const Var2ExpandArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    hipLaunchKernelGGL(var2_expand_frames_kernel, grid, block, 0, stream, a);
+    return launched("var2_expand_frames_1d");
+}
+
+namespace {
+template <bool FINAL>
+int launch_frames_pass(const Var2FramesArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.adjoint) {
+        if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, true, FINAL>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_kernel<true, true, FINAL>), grid, block, 0, stream, a);
+        return launched(FINAL ? "var2_adj_frames_pass2_1d" : "var2_adj_frames_tails_1d");
+    }
+    if constexpr (FINAL) {
+        if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_kernel<true, false, true>), grid, block, 0, stream, a);
+        return launched("var2_frames_pass2_1d");
+    } else {
+        if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, false, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_kernel<true, false, false, true>), grid, block, 0, stream, a);
+        return launched("var2_biquad_frames_tails_1d");
+    }
+}
+}  // namespace
+
+int launch_var2_frames_tails(const Var2FramesArgs &a, hipStream_t stream) { return launch_frames_pass<false>(a, stream); }
+int launch_var2_frames_pass2(const Var2FramesArgs &a, hipStream_t stream) { return launch_frames_pass<true>(a, stream); }
+
+int launch_var2_frames_grad(const Var2FramesGradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.causal) {
+        if (a.with_frames) hipLaunchKernelGGL((var2_frames_grad_kernel<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_grad_kernel<true, false>), grid, block, 0, stream, a);
+    } else {
+        if (a.with_frames) hipLaunchKernelGGL((var2_frames_grad_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_grad_kernel<false, false>), grid, block, 0, stream, a);
+    }
+    return launched("var2_biquad_frames_grad_1d");
+}
+
+int launch_var2_frames_fold(const Var2FramesGradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n_frames + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    hipLaunchKernelGGL(var2_frames_fold_kernel, grid, block, 0, stream, a);
+    return launched("var2_frames_fold_1d");
 }
 
 }  // namespace rf

@@ -20,6 +20,7 @@ rf_var2_plan::~rf_var2_plan() {
     if (workspace) (void)hipFree(workspace);
     if (lam) (void)hipFree(lam);
     if (cascade) (void)hipFree(cascade);
+    if (frames_slab) (void)hipFree(frames_slab);
 }
 
 namespace rf {
@@ -97,6 +98,10 @@ int build_var2_signal_plan(const rf_var2_signal_desc *d, rf_var2_plan **out) {
     plan->backward_names[1] = {"var2_adj_tails_1d", "var2_carry_1d", "var2_adj_pass2_1d", "var2_grad_1d"};
     plan->biquad_names = {"var2_biquad_tails_1d", "var2_carry_1d", "var2_pass2_1d"};
     plan->biquad_backward_names = {"var2_adj_tails_1d", "var2_carry_1d", "var2_adj_pass2_1d", "var2_biquad_grad_1d"};
+    plan->frames_names = {"var2_biquad_frames_tails_1d", "var2_carry_1d", "var2_frames_pass2_1d"};
+    plan->frames_backward_names[0] = {"var2_adj_frames_tails_1d", "var2_carry_1d", "var2_adj_frames_pass2_1d", "var2_biquad_frames_grad_1d"};
+    plan->frames_backward_names[1] = plan->frames_backward_names[0];
+    plan->frames_backward_names[1].push_back("var2_frames_fold_1d");
     if (!host_only) {
         RF_HIP_CHECK(hipSetDevice(device));
         if (hipMalloc((void **)&plan->workspace, plan->workspace_bytes()) != hipSuccess) {
@@ -739,6 +744,216 @@ int run_var2_cascade_kept_backward(rf_var2_plan *plan, const void *in, const rf_
     if (rc == RF_OK) {
         const float *y = !with_coefficients ? nullptr : K == 1 ? (const float *)out : (const float *)kept[0];
         rc = launch_var2_biquad_grad(grad_args(plan, sections[0], with_coefficients ? &grads[0] : nullptr, (const float *)in, y, (float *)grad_in), stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+// ---- the section on control-rate frames -------------------------------------------------------------------------------------------
+//   forward    var2_biquad_frames_tails_1d (reads in and the frames, stores v to out), var2_carry_1d, var2_frames_pass2_1d on out.
+//   backward   var2_adj_frames_tails_1d, var2_carry_1d, var2_adj_frames_pass2_1d on grad_out into the plan's lam, then
+//              var2_biquad_frames_grad_1d: grad_in and, where frame gradients are asked for, the f64 sums of every piece into the
+//              plan's slab, which var2_frames_fold_1d folds into the five [line][frame] gradients.
+// The checks common to the calls come first, in the header's order: the hop, the frame count, the frame stride.
+namespace {
+
+int hop_shift_of(int hop) {
+    int shift = 0;
+    while ((1 << shift) < hop) shift++;
+    return shift;
+}
+
+int check_frames_layout(int64_t length, int hop, int n_frames, int64_t frame_stride) {
+    if (!var2_hop_ok(hop)) return refuse(RF_ERR_UNSUPPORTED, "hop must be a power of two in 64..65536 (got %lld)", hop);
+    if (n_frames != var2_frames_count(length, hop))
+        return refuse(RF_ERR_INVALID_ARG, "n_frames must be ceil(length / hop) + 1 = %lld (got %lld)", var2_frames_count(length, hop), n_frames);
+    if (frame_stride < n_frames) return refuse(RF_ERR_INVALID_ARG, "frame_stride must be at least n_frames = %lld (got %lld)", n_frames, frame_stride);
+    return RF_OK;
+}
+
+constexpr const char *kFrameAlign = "signals need 16-byte aligned pointers, frame arrays 4-byte aligned ones";
+
+Var2FramesArgs frames_args(const rf_var2_plan *plan, const rf_var2_section &f, int hop, int n_frames, int64_t frame_stride, bool causal, bool adjoint) {
+    Var2FramesArgs a{};
+    a.b0 = (const float *)f.b0;
+    a.b1 = (const float *)f.b1;
+    a.b2 = (const float *)f.b2;
+    a.a1 = (const float *)f.a1;
+    a.a2 = (const float *)f.a2;
+    a.tails = plan->workspace;
+    a.carry = plan->workspace + plan->tails_floats();
+    a.n = (int32_t)plan->length;
+    a.tiles = (int32_t)plan->tiles;
+    a.groups = (int32_t)plan->groups;
+    a.n_lines = plan->n_lines;
+    a.causal = causal ? 1 : 0;
+    a.adjoint = adjoint ? 1 : 0;
+    a.hop_shift = hop_shift_of(hop);
+    a.n_frames = n_frames;
+    a.inv_hop = 1.0f / (float)hop;
+    a.stride = plan->stride;
+    a.frame_stride = frame_stride;
+    return a;
+}
+
+// tails, carry, final stage: the three launches of a scan on frames, a mark behind each
+int launch_frames_scan(const rf_var2_plan *plan, const Var2FramesArgs &a, hipStream_t stream, LaunchTimer &timer) {
+    int rc = launch_var2_frames_tails(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK) rc = launch_var2_carry(scan_args(plan, a.causal != 0, a.adjoint != 0), stream);
+    if (rc == RF_OK) rc = timer.mark();
+    Var2FramesArgs last = a;
+    if (!a.adjoint) last.x = a.dst;      // v; the scan finishes on it in place
+    if (rc == RF_OK) rc = launch_var2_frames_pass2(last, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    return rc;
+}
+
+size_t frames_span_bytes(int n_lines, int n_frames, int64_t frame_stride) { return (size_t)((int64_t)(n_lines - 1) * frame_stride + n_frames) * sizeof(float); }
+
+}  // namespace
+
+int run_var2_expand_frames(const void *frames, int hop, int n_frames, int64_t frame_stride, int64_t length, int lines, int64_t stride, void *out,
+                           hipStream_t stream) {
+    if (length < 1 || length % 4 != 0 || length > kVar2MaxLength)
+        return refuse(RF_ERR_INVALID_ARG, "length must be a positive multiple of 4, at most 2^30 (got %lld)", length);
+    if (lines < 1 || lines > kVar2MaxLines) return refuse(RF_ERR_INVALID_ARG, "lines must be 1..%lld (got %lld)", kVar2MaxLines, lines);
+    if (stride < length || stride % 4 != 0 || stride > kVar2MaxStride)
+        return refuse(RF_ERR_INVALID_ARG, "stride must be a multiple of 4, at least the length and at most 2^40 (got %lld for a length of %lld)", stride, length);
+    int rc = check_frames_layout(length, hop, n_frames, frame_stride);
+    if (rc != RF_OK) return rc;
+    if (!frames || !out) return refuse(RF_ERR_INVALID_ARG, "null pointer (frames, out)");
+    if (((uintptr_t)out & 15u) != 0 || ((uintptr_t)frames & 3u) != 0) { set_error("%s", kFrameAlign); return RF_ERR_INVALID_ARG; }
+    if (overlap(out, (size_t)((int64_t)(lines - 1) * stride + length) * sizeof(float), frames, frames_span_bytes(lines, n_frames, frame_stride)))
+        return refuse(RF_ERR_INVALID_ARG, "out overlaps the frames");
+    Var2ExpandArgs a{};
+    a.frames = (const float *)frames;
+    a.out = (float *)out;
+    a.n = (int32_t)length;
+    a.n_lines = lines;
+    a.hop_shift = hop_shift_of(hop);
+    a.n_frames = n_frames;
+    a.inv_hop = 1.0f / (float)hop;
+    a.stride = stride;
+    a.frame_stride = frame_stride;
+    return launch_var2_expand_frames(a, stream);
+}
+
+int run_var2_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames, int64_t frame_stride, void *out,
+                           hipStream_t stream, float *ms_out) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
+    if (rc != RF_OK) return rc;
+    if (!frames) return refuse(RF_ERR_INVALID_ARG, "null frames");
+    rc = check_plane("signal", 0, {{in}, {out}}, 15u, "null pointer (in, out)", kFrameAlign);
+    if (rc == RF_OK) rc = check_plane("frames", 0, {{frames->b0}, {frames->b1}, {frames->b2}, {frames->a1}, {frames->a2}}, 3u,
+                                      "null pointer (b0, b1, b2, a1, a2)", kFrameAlign);
+    if (rc != RF_OK) return rc;
+    const size_t bytes = plan->span_bytes(), frame_bytes = frames_span_bytes(plan->n_lines, n_frames, frame_stride);
+    const void *const written[1] = {out}, *const coefficients[5] = {frames->b0, frames->b1, frames->b2, frames->a1, frames->a2}, *const input[1] = {in};
+    const PlaneList w = {"out", written, 1, bytes};
+    const PlaneList r[2] = {{"in", input, 1, bytes,
+                             ": in == out is not allowed for a biquad (the first launch stores the feed-forward part while neighbouring groups still read in)"},
+                            {"frames", coefficients, 5, frame_bytes, ": a frame array is read while outputs are stored"}};
+    rc = check_written_planes(&w, 1, r, 2, {"grad_out", nullptr, 0, bytes});
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    LaunchTimer timer(stream, ms_out, plan->frames_names.size());
+    if (timer.status() != RF_OK) return timer.status();
+    Var2FramesArgs a = frames_args(plan, *frames, hop, n_frames, frame_stride, plan->causal, false);
+    a.x = (const float *)in;
+    a.dst = (float *)out;
+    rc = launch_frames_scan(plan, a, stream, timer);
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames, int64_t frame_stride,
+                                    const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
+                                    hipStream_t stream, float *ms_out) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
+    if (rc != RF_OK) return rc;
+    if (!frames) return refuse(RF_ERR_INVALID_ARG, "null frames");
+    const rf_var2_section_grad none{};
+    const rf_var2_section_grad &fg = frame_grads ? *frame_grads : none;
+    const int given = (fg.b0 != nullptr) + (fg.b1 != nullptr) + (fg.b2 != nullptr) + (fg.a1 != nullptr) + (fg.a2 != nullptr);
+    const bool with_frames = given == 5;
+    // (null pointers are refused first; the count of the frame gradients behind them, as the header orders the refusals)
+    rc = check_plane("signal", 0, {{in}, {grad_out}, {grad_in}, {out, with_frames}}, 15u,
+                     "null pointer (in, grad_out, grad_in; out where frame gradients are asked for)", kFrameAlign);
+    if (rc == RF_OK) rc = check_plane("frames", 0, {{frames->b0}, {frames->b1}, {frames->b2}, {frames->a1}, {frames->a2}, {fg.b0, false}, {fg.b1, false},
+                                                    {fg.b2, false}, {fg.a1, false}, {fg.a2, false}}, 3u, "null pointer (b0, b1, b2, a1, a2)", kFrameAlign);
+    if (rc != RF_OK) return rc;
+    if (given != 0 && given != 5)
+        return refuse(RF_ERR_INVALID_ARG, "the five frame gradients are all given or all null (the fold forms the five; %lld given)", given);
+    const size_t bytes = plan->span_bytes(), frame_bytes = frames_span_bytes(plan->n_lines, n_frames, frame_stride);
+    const void *const gin[1] = {grad_in}, *const gframes[5] = {fg.b0, fg.b1, fg.b2, fg.a1, fg.a2},
+                      *const coefficients[5] = {frames->b0, frames->b1, frames->b2, frames->a1, frames->a2}, *const input[1] = {in},
+                      *const result[1] = {out}, *const gout[1] = {grad_out};
+    const PlaneList written[2] = {{"grad_in", gin, 1, bytes}, {"gradient of frames", gframes, with_frames ? 5 : 0, frame_bytes}};
+    const PlaneList read[3] = {{"frames", coefficients, 5, frame_bytes, ": a frame array is read while outputs are stored"},
+                               {"in", input, 1, bytes},
+                               {"out", result, with_frames ? 1 : 0, bytes}};
+    rc = check_written_planes(written, 2, read, 3, {"grad_out", gout, 1, bytes});
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    if (!plan->lam && hipMalloc((void **)&plan->lam, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        plan->lam = nullptr;
+        set_error("hipMalloc of %zu bytes for the adjoint state of the biquad's backward failed", bytes);
+        return RF_ERR_NOMEM;
+    }
+    const size_t slab_bytes = plan->frames_slab_needed(hop);
+    if (with_frames && plan->frames_slab_bytes < slab_bytes) {
+        // (hipFree waits for the device: no earlier call on this plan still uses the slab)
+        if (plan->frames_slab) (void)hipFree(plan->frames_slab);
+        plan->frames_slab = nullptr;
+        plan->frames_slab_bytes = 0;
+        if (hipMalloc((void **)&plan->frames_slab, slab_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->frames_slab = nullptr;
+            set_error("hipMalloc of %zu bytes for the partial sums of the frame gradients failed", slab_bytes);
+            return RF_ERR_NOMEM;
+        }
+        plan->frames_slab_bytes = slab_bytes;
+    }
+    LaunchTimer timer(stream, ms_out, plan->frames_backward_names[with_frames ? 1 : 0].size());
+    if (timer.status() != RF_OK) return timer.status();
+    Var2FramesArgs a = frames_args(plan, *frames, hop, n_frames, frame_stride, !plan->causal, true);
+    a.x = (const float *)grad_out;
+    a.dst = plan->lam;
+    rc = launch_frames_scan(plan, a, stream, timer);
+    if (rc != RF_OK) return rc;
+    Var2FramesGradArgs g{};
+    g.lam = plan->lam;
+    g.x = (const float *)in;
+    g.y = (const float *)out;
+    g.b0 = (const float *)frames->b0;
+    g.b1 = (const float *)frames->b1;
+    g.b2 = (const float *)frames->b2;
+    g.grad_in = (float *)grad_in;
+    g.slab = plan->frames_slab;
+    g.grad_b0 = (float *)fg.b0;
+    g.grad_b1 = (float *)fg.b1;
+    g.grad_b2 = (float *)fg.b2;
+    g.grad_a1 = (float *)fg.a1;
+    g.grad_a2 = (float *)fg.a2;
+    g.n = (int32_t)plan->length;
+    g.n_lines = plan->n_lines;
+    g.causal = plan->causal ? 1 : 0;
+    g.with_frames = with_frames ? 1 : 0;
+    g.hop_shift = a.hop_shift;
+    g.n_frames = n_frames;
+    g.pieces = (int32_t)var2_frames_pieces(plan->length, hop);
+    g.inv_hop = a.inv_hop;
+    g.stride = plan->stride;
+    g.frame_stride = frame_stride;
+    rc = launch_var2_frames_grad(g, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK && with_frames) {
+        rc = launch_var2_frames_fold(g, stream);
         if (rc == RF_OK) rc = timer.mark();
     }
     return rc == RF_OK ? timer.finish() : rc;

@@ -34,6 +34,13 @@ struct rf_var2_plan {
     // uses the first span alone (the gradient between two sections) and allocates one span where there is none
     float *cascade = nullptr;
     int cascade_spans = 0;
+    // the section on control-rate frames (rf_var2_plan_backward_biquad_frames): lam above, and the slab of f64 partial sums its
+    // frame gradients are folded from -- 10 doubles per piece of min(hop, 1024) samples -- allocated by the first call that
+    // asks for frame gradients and regrown when a later one has a smaller hop
+    double *frames_slab = nullptr;
+    size_t frames_slab_bytes = 0;
+    size_t frames_slab_needed(int hop) const { return (size_t)n_lines * (size_t)rf::var2_frames_pieces(length, hop) * rf::kVar2FrameSums * sizeof(double); }
+    std::vector<std::string> frames_names, frames_backward_names[2];      // [1]: with frame gradients
     ~rf_var2_plan();
 };
 
@@ -48,6 +55,16 @@ int run_var2_biquad(rf_var2_plan *plan, const void *in, const void *b0, const vo
 int run_var2_biquad_backward(rf_var2_plan *plan, const void *in, const void *b0, const void *b1, const void *b2, const void *a1, const void *a2,
                              const void *out, const void *grad_out, void *grad_in, void *grad_b0, void *grad_b1, void *grad_b2, void *grad_a1,
                              void *grad_a2, hipStream_t stream, float *ms_out);
+// the section with its five coefficients as control-rate frames: [line][n_frames] f32, frame j at sample j * hop
+inline bool var2_hop_ok(int hop) { return hop >= 64 && hop <= 65536 && (hop & (hop - 1)) == 0; }
+inline int var2_frames_count(int64_t length, int hop) { return var2_hop_ok(hop) && length >= 1 ? (int)((length + hop - 1) / hop) + 1 : 0; }
+int run_var2_expand_frames(const void *frames, int hop, int n_frames, int64_t frame_stride, int64_t length, int lines, int64_t stride, void *out,
+                           hipStream_t stream);
+int run_var2_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames, int64_t frame_stride, void *out,
+                           hipStream_t stream, float *ms_out);
+int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames, int64_t frame_stride,
+                                    const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
+                                    hipStream_t stream, float *ms_out);
 // a cascade of n_sections direct-form-I sections: the launches' names (string literals), counts and the backward's memory
 const char *var2_cascade_name(int n_sections, size_t i);
 const char *var2_cascade_backward_name(int n_sections, size_t i);

@@ -21,6 +21,11 @@ A cascade of K such sections, each with five coefficient signals of its own, run
 into signals the plan owns.  With keep=True the forward keeps every section's result in tensors autograd saves
 (rf_var2_plan_execute_cascade_keep) and the backward reruns nothing (rf_var2_plan_backward_cascade_kept: one adjoint link launch
 per boundary between two sections): `Var2Plan.execute_cascade_keep`, `backward_cascade_kept`.
+
+The section also takes its coefficients at a control rate (rf_var2_plan_execute_biquad_frames / _backward_biquad_frames): one frame
+every `hop` samples, a power of two from 64 to 65536, interpolated linearly in the kernels' registers -- `frames_count`,
+`expand_frames`, `Var2Plan.execute_biquad_frames`, `backward_biquad_frames` (the input's gradient and, where asked for, the five
+frame gradients, contracted in f64), `apply_biquad_frames` and `biquad_scan_frames` behind torch.autograd.
 """
 from __future__ import annotations
 
@@ -216,6 +221,107 @@ class Var2Plan(_PlanHandle):
         backward_biquad -- the input's gradient always, the five coefficient gradients where any coefficient signal requires one.
         x, the five coefficients and the result are saved (no intermediate is); no double backward."""
         return _biquad_function().apply(self, x, b0, b1, b2, a1, a2)
+
+    # -- the section on control-rate frames ---------------------------------------------------------
+    #     frames: (b0, b1, b2, a1, a2), each (F,) (lines == 1) or (lines, F), F = frames_count(length, hop), frame j at sample
+    #     j * hop; between two frames the coefficient is fma(k / hop, c[j+1] - c[j], c[j]), formed in the kernels' registers
+    @property
+    def biquad_frames_num_kernels(self) -> int:
+        return int(capi.lib().rf_var2_plan_biquad_frames_num_kernels(self._h))
+
+    def backward_biquad_frames_num_kernels(self, with_frames: bool = False) -> int:
+        """4 launches, 5 with frame gradients (the fold)"""
+        return int(capi.lib().rf_var2_plan_backward_biquad_frames_num_kernels(self._h, int(bool(with_frames))))
+
+    def backward_biquad_frames_bytes(self, hop: int) -> int:
+        """what the plan owns behind a backward_biquad_frames: lam and the slab of f64 partial sums, 80 bytes per piece of
+        min(hop, 1024) samples"""
+        return int(capi.lib().rf_var2_plan_backward_biquad_frames_bytes(self._h, int(hop)))
+
+    def _frames_array(self, frames, hop: int, what: str, like=None):
+        """(a one-element rf_var2_section array, n_frames, frame_stride) of five frame tensors after their checks; `like`: the
+        frame stride they must share with (the gradients with the frames: the library takes one stride)"""
+        import torch
+        if frames is None:
+            return None, 0, 0
+        if len(frames) != 5:
+            raise ValueError(f"{what}: the five frame tensors (b0, b1, b2, a1, a2)")
+        count = frames_count(self.length, hop)
+        shapes = [(self.lines, count)] + ([(count,)] if self.lines == 1 else [])
+        array = (capi.Var2Section * 1)()
+        stride = like
+        for name, t in zip(("b0", "b1", "b2", "a1", "a2"), frames):
+            if tuple(t.shape) not in shapes:
+                raise ValueError(f"{what}.{name}: shape {tuple(t.shape)}, hop {hop} on this plan takes {' or '.join(str(s) for s in shapes)}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{what}.{name}: float32 frames only, got {t.dtype}")
+            own = t.stride(0) if t.dim() == 2 and self.lines > 1 else count
+            stride = own if stride is None else stride
+            if not t.is_cuda or t.stride(-1) != 1 or own != stride:
+                raise ValueError(f"{what}.{name}: a device tensor with dense rows, all five the same distance apart")
+            setattr(array[0], name, t.data_ptr())
+        return array, count, stride
+
+    def _host_frames(self, hop: int, first: int):
+        count = int(capi.lib().rf_var2_frames_count(self.length, int(hop)))
+        p = self._placeholders(first + 5)
+        return p[:first], (capi.Var2Section * 1)(capi.Var2Section(*(q.value for q in p[first:]))), count, count
+
+    def _biquad_frames_arguments(self, x, frames, hop, out, stream):
+        if self._host_only:
+            (px, po), array, count, stride = self._host_frames(hop, 2)
+            return px, array, int(hop), count, stride, po, None, ctypes.c_void_p()
+        if out is None:
+            out = self._like(x)
+        array, count, stride = self._frames_array(frames, hop, "frames")
+        return self._pointer(x, "x"), array, int(hop), count, stride, self._pointer(out, "out"), out, self._stream(stream)
+
+    def execute_biquad_frames(self, x, frames, hop: int, out=None, stream=None):
+        """rf_var2_plan_execute_biquad_frames: execute_biquad with the five coefficients as frames every `hop` samples (a power of
+        two, 64..65536), bit for bit what execute_biquad gives on expand_frames of each.  out=None allocates the output; out may
+        NOT be x.  Asynchronous on `stream` (default: torch's current stream)."""
+        *p, out, s = self._biquad_frames_arguments(x, frames, hop, out, stream)
+        capi.check(capi.lib().rf_var2_plan_execute_biquad_frames(self._h, *p, s))
+        return out
+
+    def execute_biquad_frames_timed(self, x, frames, hop: int, out=None, stream=None):
+        """rf_var2_plan_execute_biquad_frames_timed: (output, [(kernel name, ms), ...]); synchronises the stream."""
+        *p, out, s = self._biquad_frames_arguments(x, frames, hop, out, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_execute_biquad_frames_timed(self._h, *p, s, *report)      # noqa: E731
+        return out, _timed(call, self.biquad_frames_num_kernels)
+
+    def _backward_biquad_frames_arguments(self, x, frames, hop, out, grad_out, grad_in, grads, stream):
+        if self._host_only:
+            (px, po, pgo, pgi), array, count, stride = self._host_frames(hop, 4)
+            return px, array, int(hop), count, stride, po, pgo, pgi, None, None, grads, ctypes.c_void_p()
+        if grad_in is None:
+            grad_in = self._like(grad_out)
+        array, count, stride = self._frames_array(frames, hop, "frames")
+        garray, _, _ = self._frames_array(grads, hop, "grads", like=stride)
+        return (self._pointer(x, "x"), array, int(hop), count, stride, self._pointer(out, "out"), self._pointer(grad_out, "grad_out"),
+                self._pointer(grad_in, "grad_in"), garray, grad_in, grads, self._stream(stream))
+
+    def backward_biquad_frames(self, x, frames, hop: int, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_biquad_frames, the adjoint of execute_biquad_frames: grad_in = dL/dx from grad_out; `out` is the
+        forward's result.  grads: None (no frame gradients; `out` may then be None too) or five tensors laid out like the frames
+        (the same distance between rows) to be WRITTEN: dL/d(frame), the per-sample gradients contracted in f64 with the
+        interpolation's transpose and rounded once.  Returns (grad_in, grads).  Asynchronous; the plan allocates the adjoint
+        state and the slab of partial sums in its first call (backward_biquad_frames_bytes)."""
+        *p, grad_in, grads, s = self._backward_biquad_frames_arguments(x, frames, hop, out, grad_out, grad_in, grads, stream)
+        capi.check(capi.lib().rf_var2_plan_backward_biquad_frames(self._h, *p, s))
+        return grad_in, grads
+
+    def backward_biquad_frames_timed(self, x, frames, hop: int, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_biquad_frames_timed: (grad_in, grads, [(kernel name, ms), ...]); synchronises the stream."""
+        *p, grad_in, grads, s = self._backward_biquad_frames_arguments(x, frames, hop, out, grad_out, grad_in, grads, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_backward_biquad_frames_timed(self._h, *p, s, *report)      # noqa: E731
+        return grad_in, grads, _timed(call, self.backward_biquad_frames_num_kernels(grads is not None))
+
+    def apply_biquad_frames(self, x, frames, hop: int):
+        """execute_biquad_frames as a differentiable torch operation: the values are bit for bit execute_biquad_frames'.  Backward
+        is backward_biquad_frames -- the input's gradient always, the five frame gradients where any frame tensor requires one.
+        x, the frames and the result are saved; no double backward."""
+        return _biquad_frames_function().apply(self, int(hop), x, *frames)
 
 
     # -- a cascade of sections ------------------------------------------------------------------
@@ -473,6 +579,42 @@ def _cascade_function():
     return _var2_cascade_function
 
 
+_var2_biquad_frames_function = None
+
+
+def _biquad_frames_function():
+    """the torch.autograd.Function behind Var2Plan.apply_biquad_frames: (plan, hop, x, then the five frame tensors)"""
+    global _var2_biquad_frames_function
+    if _var2_biquad_frames_function is not None:
+        return _var2_biquad_frames_function
+    import torch
+
+    class Var2BiquadFramesFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, hop, x, b0, b1, b2, a1, a2):
+            ctx.plan, ctx.hop = plan, hop
+            with torch.cuda.device(x.device):
+                out = plan.execute_biquad_frames(x, (b0, b1, b2, a1, a2), hop)
+            ctx.save_for_backward(x, b0, b1, b2, a1, a2, out)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            x, *frames, out = ctx.saved_tensors
+            need_x, *need = ctx.needs_input_grad[2:8]
+            g = _plan_layout(plan, grad_out)
+            grads = tuple(torch.empty_like(t) for t in frames) if any(need) else None
+            with torch.cuda.device(g.device):
+                gin, grads = plan.backward_biquad_frames(x, frames, ctx.hop, out, g, None, grads)
+            grads = grads if grads is not None else (None,) * 5
+            return (None, None, gin if need_x else None) + tuple(t if wanted else None for t, wanted in zip(grads, need))
+
+    _var2_biquad_frames_function = Var2BiquadFramesFunction
+    return _var2_biquad_frames_function
+
+
 def _biquad_function():
     """the torch.autograd.Function behind Var2Plan.apply_biquad"""
     global _var2_biquad_function
@@ -641,3 +783,70 @@ def biquad_cascade(x, sections: Sequence, causal: bool = True, keep: bool = Fals
     if pad:
         out = out[..., :n] if causal else out[..., pad:]
     return out
+
+
+def frames_count(length: int, hop: int) -> int:
+    """rf_var2_frames_count: the frames per coefficient and line that `length` samples take at one frame every `hop` samples,
+    ceil(length / hop) + 1 -- frame j sits at sample j * hop and the last interval has both its ends.  hop: a power of two,
+    64..65536 (anything else raises ValueError)."""
+    count = int(capi.lib().rf_var2_frames_count(int(length), int(hop))) if 1 <= int(length) <= 2 ** 30 else 0
+    if count == 0:
+        raise ValueError(f"hop must be a power of two in 64..65536 and length 1..2**30 (got hop {hop}, length {length})")
+    return count
+
+
+def expand_frames(frames, hop: int, length: int, out=None, stream=None):
+    """rf_var2_expand_frames: the coefficient signal the frames kernels form in registers, at audio rate.  frames: a device tensor
+    (F,) or (L, F), f32, F = frames_count(length, hop), dense rows (a [:, :F] view of a wider buffer is taken as it is); the
+    result is (length,) or (L, length):  c[j * hop + k] = fma(k / hop, c[j+1] - c[j], c[j]).  out: a tensor to be written, rows a
+    multiple of 4 samples apart (then length is a multiple of 4 too); None allocates it."""
+    import torch
+    count = frames_count(length, hop)
+    if frames.dim() not in (1, 2) or int(frames.shape[-1]) != count:
+        raise ValueError(f"frames: shape {tuple(frames.shape)}, {length} samples at hop {hop} take (..., {count})")
+    if frames.dtype != torch.float32 or not frames.is_cuda or frames.stride(-1) != 1:
+        raise ValueError("frames: a float32 device tensor with dense rows")
+    lines = 1 if frames.dim() == 1 else int(frames.shape[0])
+    frame_stride = int(frames.stride(0)) if frames.dim() == 2 and lines > 1 else count
+    padded = length + (-length % 4)
+    if out is None:
+        result = torch.empty(frames.shape[:-1] + (padded,), dtype=torch.float32, device=frames.device)
+    else:
+        result = out
+        if tuple(out.shape) != tuple(frames.shape[:-1]) + (length,) or out.dtype != torch.float32 or not out.is_cuda or out.stride(-1) != 1 or padded != length:
+            raise ValueError(f"out: a float32 device tensor {tuple(frames.shape[:-1]) + (length,)} with dense rows, length a multiple of 4")
+    stride = int(result.stride(0)) if result.dim() == 2 and lines > 1 else padded
+    with torch.cuda.device(frames.device):
+        s = _PlanHandle._stream(stream)
+        capi.check(capi.lib().rf_var2_expand_frames(ctypes.c_void_p(frames.data_ptr()), int(hop), count, frame_stride, padded, lines, stride,
+                                                    ctypes.c_void_p(result.data_ptr()), s))
+    return result if out is not None else result[..., :length]
+
+
+def biquad_scan_frames(x, b0, b1, b2, a1, a2, hop: int, causal: bool = True):
+    """biquad_scan with the five coefficients at a control rate: x is (N,) or (L, N), every coefficient (F,) or (L, F) with
+    F = frames_count(N, hop), frame j at sample j * hop and linear interpolation between two frames (expand_frames), by absolute
+    position for either direction.  hop: a power of two, 64..65536.  The kernels read the frames and interpolate in registers: no
+    audio-rate coefficient signal exists, forward or backward.  Differentiable in x and all five frame tensors -- the frame
+    gradients are the per-sample gradients contracted in f64; x, the frames and the result are saved, no double backward.
+    b = (1, 0, 0) frames is the all-pole scan.  Frames must be finite.  It shares biquad_scan's plan cache; a length that is no
+    multiple of 4 is padded with zeros in x behind the END for either direction (hop is a multiple of 4: F does not change, and
+    zero input on zero state stays zero)."""
+    import torch
+    frames = (b0, b1, b2, a1, a2)
+    n = int(x.shape[-1])
+    count = frames_count(n, hop)
+    shape = tuple(x.shape[:-1]) + (count,)
+    if x.dim() not in (1, 2) or any(tuple(t.shape) != shape for t in frames):
+        raise ValueError(f"x is (N,) or (L, N) and every frame tensor {shape} at hop {hop}, got {tuple(x.shape)} and {[tuple(t.shape) for t in frames]}")
+    lines = 1 if x.dim() == 1 else int(x.shape[0])
+    pad = -n % 4
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (n + pad, lines, bool(causal), device)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = Var2Plan(n + pad, lines=lines, causal=causal, device=device)
+    if pad:
+        x = torch.nn.functional.pad(x, (0, pad))
+    out = plan.apply_biquad_frames(_plan_layout(plan, x), tuple(t.to(torch.float32).contiguous() for t in frames), hop)
+    return out[..., :n] if pad else out
