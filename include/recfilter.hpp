@@ -1274,4 +1274,45 @@ public:
         return rf_var2_plan_backward_cascade_kept_num_kernels(plan, sections, with_coefficients ? 1 : 0);
     }
     size_t cascade_kept_gradient_bytes(int sections) { prepare(); return rf_var2_plan_backward_cascade_kept_bytes(plan, sections); }
+    /** realize_cascade() with every section's coefficients at a control rate (rf_var2_plan_execute_cascade_frames): frames[k]
+     *  holds section k's five frame arrays as realize_biquad_frames() takes them, one hop and one frame_stride (0: dense) for all
+     *  sections.  2 K + 1 launches that read no coefficient signal; bit for bit realize_cascade() on the expanded signals.  kept:
+     *  empty (v and the result in out, in place) or one signal per section but the last, which receives section k's result in
+     *  kept[k] -- out has the same bits either way. */
+    void realize_cascade_frames(const void *in, const std::vector<rf_var2_section> &frames, int hop, void *out,
+                                const std::vector<void *> &kept = {}, int64_t frame_stride = 0, void *stream = nullptr) {
+        prepare();
+        if (!kept.empty() && kept.size() + 1 != frames.size())
+            throw RecFilterError("realize_cascade_frames: kept is empty or holds one signal per section but the last");
+        const int count = frames_count(hop);
+        if (rf_var2_plan_execute_cascade_frames(plan, in, frames.data(), (int)frames.size(), hop, count, frame_stride > 0 ? frame_stride : count,
+                                                out, kept.empty() ? nullptr : kept.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize_cascade_frames() on what it kept (rf_var2_plan_backward_cascade_frames): nothing is rerun.
+     *  frame_grads: empty (no frame gradients: in, out and kept may then be null and empty) or one rf_var2_section_grad per
+     *  section, five arrays laid out like the frames, to be written -- the per-sample gradients contracted in f64 and rounded
+     *  once.  grad_in == grad_out is allowed.  The plan owns two signals and the slab (cascade_frames_gradient_bytes()). */
+    void gradient_cascade_frames(const void *in, const std::vector<rf_var2_section> &frames, int hop, const std::vector<const void *> &kept,
+                                 const void *out, const void *grad_out, void *grad_in, const std::vector<rf_var2_section_grad> &frame_grads = {},
+                                 int64_t frame_stride = 0, void *stream = nullptr) {
+        prepare();
+        if (!frame_grads.empty() && frame_grads.size() != frames.size())
+            throw RecFilterError("gradient_cascade_frames: frame_grads is empty or holds one rf_var2_section_grad per section");
+        if (!kept.empty() && kept.size() + 1 != frames.size())
+            throw RecFilterError("gradient_cascade_frames: kept is empty or holds one signal per section but the last");
+        const int count = frames_count(hop);
+        if (rf_var2_plan_backward_cascade_frames(plan, in, frames.data(), (int)frames.size(), hop, count, frame_stride > 0 ? frame_stride : count,
+                                                 kept.empty() ? nullptr : kept.data(), out, grad_out, grad_in,
+                                                 frame_grads.empty() ? nullptr : frame_grads.data(), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** 2 K + 1 (3 at K = 1) */
+    int cascade_frames_num_kernels(int sections) { prepare(); return rf_var2_plan_cascade_frames_num_kernels(plan, sections); }
+    /** 2 K + 2 without frame gradients, 3 K + 2 with them; 4 and 5 at K = 1 */
+    int cascade_frames_gradient_num_kernels(int sections, bool with_frames) {
+        prepare();
+        return rf_var2_plan_backward_cascade_frames_num_kernels(plan, sections, with_frames ? 1 : 0);
+    }
+    size_t cascade_frames_gradient_bytes(int sections, int hop) { prepare(); return rf_var2_plan_backward_cascade_frames_bytes(plan, sections, hop); }
 };

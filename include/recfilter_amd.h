@@ -1175,8 +1175,8 @@ size_t rf_var2_plan_backward_cascade_kept_bytes(const rf_var2_plan *plan, int n_
  * anything else (grad_in == grad_out is allowed); last, a host-only plan (RF_ERR_HIP).
  * rf_var2_expand_frames: out[l * stride + n] = c[n] for one coefficient on `lines` lines of `length` samples (a multiple of 4;
  * out 16-byte aligned, apart from the frames), on the current device: "var2_expand_frames_1d".
- * Out of scope: hops below 64 or not powers of two (480, for example); hold or cubic interpolation; frames for cascades;
- * frames for rf_var_plan; 16-bit signals, second derivatives, sharding. */
+ * Out of scope: hops below 64 or not powers of two (480, for example); hold or cubic interpolation; frames for
+ * rf_var_plan; 16-bit signals, second derivatives, sharding.  (Cascades on frames: rf_var2_plan_execute_cascade_frames, below.) */
 int    rf_var2_frames_count(int length, int hop);                        /* ceil(length / hop) + 1; 0: hop refused */
 int    rf_var2_expand_frames(const void *frames, int hop, int n_frames, int64_t frame_stride, int length, int lines, int64_t stride,
                              void *out, void *stream);
@@ -1195,6 +1195,60 @@ int    rf_var2_plan_backward_biquad_frames_timed(rf_var2_plan *plan, const void 
 int    rf_var2_plan_biquad_frames_num_kernels(const rf_var2_plan *plan);
 int    rf_var2_plan_backward_biquad_frames_num_kernels(const rf_var2_plan *plan, int with_frame_gradients);
 size_t rf_var2_plan_backward_biquad_frames_bytes(const rf_var2_plan *plan, int hop);
+
+/* A cascade of sections on control-rate frames (rf_var2_plan_execute_cascade_frames): n_sections sections, 1 ..
+ * RF_VAR2_MAX_SECTIONS, all in the plan's direction, section k with its five coefficients as frames -- frames[k], an
+ * rf_var2_section of frame pointers -- as rf_var2_plan_execute_biquad_frames defines them; one hop, one n_frames =
+ * rf_var2_frames_count(length, hop) and one frame_stride serve all sections.  The result is rf_var2_plan_execute_cascade's on the
+ * expanded signals bit for bit: c[n] by absolute position, the same masks, the same fma order of the feed-forward part, and the
+ * two samples beyond a tile are the state that enters the tile.  No coefficient signal exists: 8 K + 8 bytes per sample move
+ * where K calls of rf_var2_plan_execute_biquad_frames move 16 K and rf_var2_plan_execute_cascade 36 K + 8.
+ * Launches: "var2_biquad_frames_tails_1d"; per boundary between two sections "var2_carry_1d" and "var2_frames_link_1d" -- the
+ * final stage of section k, the feed-forward part and the tails stage of section k + 1 on the tile in registers, every
+ * coefficient interpolated in the step that uses it -- then "var2_carry_1d" and "var2_frames_pass2_1d":
+ * rf_var2_plan_cascade_frames_num_kernels(plan, K) = 2 K + 1.  kept null: v and the result in out, in place.  kept given (K - 1
+ * signals laid out like in, the CALLER's): kept[k] receives section k's result ("var2_frames_link_keep_1d" for the link); out
+ * has the same bits either way.  K = 1 is rf_var2_plan_execute_biquad_frames: its launches, names and bits; kept is not read.
+ * rf_var2_plan_backward_cascade_frames runs on the kept signals and reruns nothing: "var2_adj_frames_tails_1d" on grad_out; per
+ * boundary from the last one down "var2_carry_1d" and "var2_adj_frames_link_1d" -- rf_var2_plan_backward_cascade_kept's
+ * "var2_adj_link_1d" on frames, grad_in that call's bits on the expanded signals -- then "var2_carry_1d",
+ * "var2_adj_frames_pass2_1d" and "var2_biquad_frames_grad_1d" for section 0.  With frame gradients (frame_grads: n_sections
+ * rf_var2_section_grad laid out like the frames, every pointer given) the link is "var2_adj_frames_link_keep_1d", lam to the
+ * plan's signal, and "var2_frames_coef_1d" follows it: the per-sample gradients of section k from lam, kept[k-1] and kept[k]
+ * (out for the last section), rounded to f32 and contracted in f64 as "var2_biquad_frames_grad_1d" contracts them -- the same
+ * lane order, the same tree -- into section k's part of the slab; "var2_frames_fold_cascade_1d" is last and folds every
+ * section in one launch, the additions per frame in rf_var2_plan_backward_biquad_frames' order.
+ * rf_var2_plan_backward_cascade_frames_num_kernels(plan, K, with) = 2 K + 2 without frame gradients and 3 K + 2 with them; 4
+ * and 5 at K = 1, where launches and bits are rf_var2_plan_backward_biquad_frames'.  The plan owns lam, the gradient between
+ * sections (K >= 2) and a slab of K * 80 * n_lines * ceil(length / min(hop, 1024)) bytes, shared with the other backward calls
+ * -- calls of every kind mix on one plan in any order, a call with a larger need regrows the slab:
+ * rf_var2_plan_backward_cascade_frames_bytes(plan, K, hop), 0 for a refused K or hop.  rf_var2_plan_workspace_bytes is
+ * unchanged and the plan keeps no state between calls.  Without frame gradients (frame_grads null, or every pointer null) in,
+ * out and kept may be null; with them all are required.  grad_in == grad_out is allowed.
+ * Refusals, before any HIP call, in this order: n_sections out of range (a *_timed call checks ms_out's capacity next); a hop
+ * that is no power of two in 64 .. 65536 (RF_ERR_UNSUPPORTED); n_frames != rf_var2_frames_count(length, hop); frame_stride <
+ * n_frames; a null or misaligned pointer (frames, then in, out, grad_out, grad_in, "kept k", "frames k", "frame gradients k");
+ * execute: in == out, out overlapping a frame array, then a kept signal overlapping in, a frame array, out or another kept
+ * signal; backward: the frame gradients of a section neither all given nor all null, or the sections not alike; a written
+ * array (grad_in, a frame gradient) overlapping a frame array, in, out, a kept signal, another written array, or grad_out other
+ * than grad_in exactly; last, a host-only plan (RF_ERR_HIP).
+ * Out of scope: a backward that reruns instead of keeping; a hop or a direction per section; the contraction folded into the
+ * adjoint link; and what is out of scope for one section on frames. */
+int    rf_var2_plan_execute_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                           int n_frames, int64_t frame_stride, void *out, void *const *kept, void *stream);
+int    rf_var2_plan_execute_cascade_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections,
+                                                 int hop, int n_frames, int64_t frame_stride, void *out, void *const *kept, void *stream,
+                                                 float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_backward_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                            int n_frames, int64_t frame_stride, const void *const *kept, const void *out,
+                                            const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads, void *stream);
+int    rf_var2_plan_backward_cascade_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections,
+                                                  int hop, int n_frames, int64_t frame_stride, const void *const *kept, const void *out,
+                                                  const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
+                                                  void *stream, float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_cascade_frames_num_kernels(const rf_var2_plan *plan, int n_sections);      /* 0: n_sections out of range */
+int    rf_var2_plan_backward_cascade_frames_num_kernels(const rf_var2_plan *plan, int n_sections, int with_frame_gradients);
+size_t rf_var2_plan_backward_cascade_frames_bytes(const rf_var2_plan *plan, int n_sections, int hop);
 
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);

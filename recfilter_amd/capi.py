@@ -96,6 +96,9 @@ EXPORTED_SYMBOLS = [
     "rf_var2_frames_count", "rf_var2_expand_frames", "rf_var2_plan_execute_biquad_frames", "rf_var2_plan_execute_biquad_frames_timed",
     "rf_var2_plan_backward_biquad_frames", "rf_var2_plan_backward_biquad_frames_timed", "rf_var2_plan_biquad_frames_num_kernels",
     "rf_var2_plan_backward_biquad_frames_num_kernels", "rf_var2_plan_backward_biquad_frames_bytes",
+    "rf_var2_plan_execute_cascade_frames", "rf_var2_plan_execute_cascade_frames_timed", "rf_var2_plan_backward_cascade_frames",
+    "rf_var2_plan_backward_cascade_frames_timed", "rf_var2_plan_cascade_frames_num_kernels",
+    "rf_var2_plan_backward_cascade_frames_num_kernels", "rf_var2_plan_backward_cascade_frames_bytes",
 ]
 
 
@@ -350,6 +353,16 @@ def lib() -> ctypes.CDLL:
     L.rf_var2_plan_backward_biquad_frames_num_kernels.argtypes = [vp, ctypes.c_int]
     L.rf_var2_plan_backward_biquad_frames_bytes.argtypes = [vp, ctypes.c_int]
     L.rf_var2_plan_backward_biquad_frames_bytes.restype = ctypes.c_size_t
+    # plan, in, the sections' frames, K, hop, n_frames, frame_stride
+    cascade_frames = [vp, vp, sp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]
+    L.rf_var2_plan_execute_cascade_frames.argtypes = cascade_frames + [vp, kp, vp]
+    L.rf_var2_plan_execute_cascade_frames_timed.argtypes = cascade_frames + [vp, kp, vp] + report
+    L.rf_var2_plan_backward_cascade_frames.argtypes = cascade_frames + [kp, vp, vp, vp, sp, vp]
+    L.rf_var2_plan_backward_cascade_frames_timed.argtypes = cascade_frames + [kp, vp, vp, vp, sp, vp] + report
+    L.rf_var2_plan_cascade_frames_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_frames_num_kernels.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_frames_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    L.rf_var2_plan_backward_cascade_frames_bytes.restype = ctypes.c_size_t
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

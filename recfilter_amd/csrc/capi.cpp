@@ -917,6 +917,53 @@ int rf_var2_plan_backward_biquad_frames_timed(rf_var2_plan *plan, const void *in
     });
 }
 
+// ---- a cascade of sections on control-rate frames -------------------------------------------------------------------------------------
+int rf_var2_plan_cascade_frames_num_kernels(const rf_var2_plan *plan, int n_sections) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_frames_launches(n_sections) : 0;
+}
+int rf_var2_plan_backward_cascade_frames_num_kernels(const rf_var2_plan *plan, int n_sections, int with_frame_gradients) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_frames_backward_launches(n_sections, with_frame_gradients != 0) : 0;
+}
+size_t rf_var2_plan_backward_cascade_frames_bytes(const rf_var2_plan *plan, int n_sections, int hop) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS && var2_hop_ok(hop) ? var2_cascade_frames_backward_bytes(plan, n_sections, hop) : 0;
+}
+
+int rf_var2_plan_execute_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
+                                        int64_t frame_stride, void *out, void *const *kept, void *stream) {
+    return fenced("rf_var2_plan_execute_cascade_frames", [&] {
+        return run_var2_cascade_frames(plan, in, frames, n_sections, hop, n_frames, frame_stride, out, kept, (hipStream_t)stream, nullptr, nullptr, 0,
+                                       false);
+    });
+}
+
+int rf_var2_plan_execute_cascade_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                              int n_frames, int64_t frame_stride, void *out, void *const *kept, void *stream, float *ms_out,
+                                              const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_execute_cascade_frames_timed", [&] {
+        return run_var2_cascade_frames(plan, in, frames, n_sections, hop, n_frames, frame_stride, out, kept, (hipStream_t)stream, ms_out, names_out,
+                                       capacity, true);
+    });
+}
+
+int rf_var2_plan_backward_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
+                                         int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                         const rf_var2_section_grad *frame_grads, void *stream) {
+    return fenced("rf_var2_plan_backward_cascade_frames", [&] {
+        return run_var2_cascade_frames_backward(plan, in, frames, n_sections, hop, n_frames, frame_stride, kept, out, grad_out, grad_in, frame_grads,
+                                                (hipStream_t)stream, nullptr, nullptr, 0, false);
+    });
+}
+
+int rf_var2_plan_backward_cascade_frames_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                               int n_frames, int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out,
+                                               void *grad_in, const rf_var2_section_grad *frame_grads, void *stream, float *ms_out,
+                                               const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_backward_cascade_frames_timed", [&] {
+        return run_var2_cascade_frames_backward(plan, in, frames, n_sections, hop, n_frames, frame_stride, kept, out, grad_out, grad_in, frame_grads,
+                                                (hipStream_t)stream, ms_out, names_out, capacity, true);
+    });
+}
+
 int rf_var_distances(const void *const *guide_planes, int32_t n_guide, int32_t guide_u8, int64_t width, int64_t height, float scale,
                      void *dx, void *dy, int32_t device, void *stream) {
     return fenced("rf_var_distances", [&] {

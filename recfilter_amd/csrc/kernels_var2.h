@@ -171,6 +171,61 @@ int launch_var2_frames_pass2(const Var2FramesArgs &a, hipStream_t stream);      
 int launch_var2_frames_grad(const Var2FramesGradArgs &a, hipStream_t stream);    // "var2_biquad_frames_grad_1d"
 int launch_var2_frames_fold(const Var2FramesGradArgs &a, hipStream_t stream);    // "var2_frames_fold_1d"
 
+// ---- a cascade of sections on control-rate frames (rf_var2_plan_execute_cascade_frames) ---------------------------------------------
+// One hop, one n_frames and one frame_stride serve every section; a1 .. next_a2 (b0 .. prev_a2) are FRAMES.  Otherwise the two
+// structs are Var2LinkArgs and Var2AdjLinkArgs: the same x, dst, keep, tails and carry, the same rules for what may be what.
+struct Var2FramesLinkArgs {
+    const float *x;
+    const float *a1, *a2;
+    const float *next_b0, *next_b1, *next_b2, *next_a1, *next_a2;
+    float *dst;
+    float *keep;
+    float *tails;
+    const float *carry;
+    int32_t n;
+    int32_t tiles, groups;
+    int32_t n_lines;
+    int32_t causal;
+    int32_t hop_shift, n_frames;
+    float inv_hop;
+    int64_t stride, frame_stride;
+};
+struct Var2AdjFramesLinkArgs {
+    const float *x;
+    const float *a1, *a2;
+    const float *b0, *b1, *b2;
+    const float *prev_a1, *prev_a2;
+    float *dst;
+    float *keep;
+    float *tails;
+    const float *carry;
+    int32_t n;
+    int32_t tiles, groups;
+    int32_t n_lines;
+    int32_t causal;                 // the direction of the ADJOINT recurrence
+    int32_t hop_shift, n_frames;
+    float inv_hop;
+    int64_t stride, frame_stride;
+};
+// The fold of all sections in one launch (var2_frames_fold_cascade_1d): section k's sums lie k * section_doubles behind slab, laid
+// out as Var2FramesGradArgs::slab; grads[k] = its five [line][frame] gradients (b0, b1, b2, a1, a2).  The sections ride on gridDim.z.
+constexpr int kVar2MaxSections = 16;         // RF_VAR2_MAX_SECTIONS
+struct Var2FramesFoldCascadeArgs {
+    const double *slab;
+    int64_t section_doubles;
+    float *grads[kVar2MaxSections][5];
+    int32_t n_sections;
+    int32_t n_lines;
+    int32_t hop_shift, n_frames;
+    int32_t pieces;                 // per line
+    int64_t frame_stride;
+};
+int launch_var2_frames_link(const Var2FramesLinkArgs &a, hipStream_t stream);          // "var2_frames_link_1d", "var2_frames_link_keep_1d" (a.keep != null)
+int launch_var2_adj_frames_link(const Var2AdjFramesLinkArgs &a, hipStream_t stream);   // "var2_adj_frames_link_1d", "var2_adj_frames_link_keep_1d"
+// the sums of the five frame gradients of a section without grad_in: a.b0, a.b1, a.b2, a.grad_in and a.with_frames are not looked at
+int launch_var2_frames_coef(const Var2FramesGradArgs &a, hipStream_t stream);          // "var2_frames_coef_1d"
+int launch_var2_frames_fold_cascade(const Var2FramesFoldCascadeArgs &a, hipStream_t stream);      // "var2_frames_fold_cascade_1d"
+
 constexpr int kVar2Tile = 64;            // samples of a tile: one lane
 constexpr int kVar2GroupTiles = 64;      // tiles of a group: one wave
 int launch_var2_tails(const Var2Args &a, hipStream_t stream);      // "var2_tails_1d", "var2_adj_tails_1d"

@@ -67,6 +67,14 @@
 //                                  gradients contracted in f64 with the interpolation's transpose, per piece of min(hop, 1024)
 //                                  samples, into a slab of the plan's
 //   var2_frames_fold_1d            the pieces that meet at a frame added in order, rounded once: the five frame gradients
+//
+// A cascade on frames (rf_var2_plan_execute_cascade_frames): the link kernels with every coefficient formed as above.
+//   var2_frames_link_1d            var2_link_1d reading x and seven frame pairs (var2_frames_link_keep_1d: y_k stored too)
+//   var2_adj_frames_link_1d        var2_adj_link_1d likewise, the shifted coefficients as var2_adj_frames_tails_1d reads them
+//                                  (var2_adj_frames_link_keep_1d: lam_k stored too), for
+//   var2_frames_coef_1d            the sums of a section's five frame gradients from lam, x and y: var2_biquad_frames_grad_1d
+//                                  without grad_in, into the section's part of the slab
+//   var2_frames_fold_cascade_1d    var2_frames_fold_1d for all sections in one launch, the section on gridDim.z
 #include "kernels_var2.h"
 
 #include "var_device.h"
@@ -924,6 +932,205 @@ __global__ void __launch_bounds__(64) var2_frames_kernel(Var2FramesArgs a) {
     }
 }
 
+// ---- the boundary between two sections of a cascade on frames ------------------------------------------------------------------------
+// The coefficient of step i of a forward stage from frames, masked by position where it would multiply a sample SHIFT places
+// outside the line (SHIFT 0: b0, masked from n on alone).
+template <bool REV, int SHIFT>
+__device__ __forceinline__ float own_frame(const FramePair &p, int k0, int i, float inv_hop, int n, int t0) {
+    const int at = t0 + i;
+    return (REV ? at >= n - SHIFT : (at < SHIFT || at >= n)) ? 0.0f : frame_lerp(p, k0 + i, inv_hop);
+}
+
+// The coefficient of step i of an adjoint stage from frames: the value SHIFT samples further along the forward's direction (REV:
+// toward the line's end) -- frame_lerp inside the tile, beyond it the values handed in (frame_at at a position clamped into the
+// line) -- then the mask by position of the scan's own direction: shift_and_mask on a value that lives for one step.
+template <bool REV, int SHIFT>
+__device__ __forceinline__ float shifted_frame(const FramePair &p, int k0, int i, float inv_hop, float beyond_near, float beyond_far, int n, int t0) {
+    const int from = REV ? i + SHIFT : i - SHIFT, at = t0 + i;
+    const bool inside = from >= 0 && from < T;
+    const bool nearest = REV ? from == T : from == -1;
+    const float c = inside ? frame_lerp(p, k0 + (inside ? from : 0), inv_hop) : (nearest ? beyond_near : beyond_far);
+    return (REV ? at >= n - SHIFT : (at < SHIFT || at >= n)) ? 0.0f : c;
+}
+
+// the tails of a tile from the state it leaves and the two columns of its matrix: the group scan and the stores every tails
+// stage ends with
+template <bool REV>
+__device__ __forceinline__ void store_tails(float *tails, int n_lines, int tiles, int groups, int line, int g, int t, float y1, float y2, float u1,
+                                            float u2, float w1, float w2) {
+    float own[kVar2Components], map[kVar2Components], whole[kVar2Components];
+    own[VAR2_E0] = y1; own[VAR2_E1] = y2;
+    own[VAR2_P00] = u1; own[VAR2_P10] = u2;
+    own[VAR2_P01] = w1; own[VAR2_P11] = w2;
+    scan_group<REV>(own, map, whole);
+    if (t < tiles) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) tails[map_index_of(n_lines, tiles, i, line, t)] = map[i];
+    }
+    if (threadIdx.x == (REV ? 0 : 63)) {
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++)
+            tails[(int64_t)kVar2Components * n_lines * tiles + ((int64_t)i * n_lines + line) * groups + g] = whole[i];
+    }
+}
+
+// var2_link_kernel with every coefficient formed as var2_frames_kernel forms it: x alone goes through the transposition, one
+// FramePair per coefficient, a value per step.  KEEP: y of the finished section is stored to a.keep (it may be a.x).
+template <bool REV, bool KEEP>
+__global__ void __launch_bounds__(64) var2_frames_link_kernel(Var2FramesLinkArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x, line = blockIdx.y;
+    const int n = a.n;
+    const int s0 = g * kGroupSamples;                 // below 2^30 + 4096
+    const int t = g * kGroupTiles + lane, t0 = t * T;
+    const int64_t first = (int64_t)line * a.stride, frame0 = (int64_t)line * a.frame_stride;
+    const int shift = a.hop_shift;
+    const float inv_hop = a.inv_hop;
+    const int j = min(t0 >> shift, a.n_frames - 2), k0 = t0 & ((1 << shift) - 1);
+    float y[T], v[T];
+    float y_near, y_far;
+    // the final stage of the section behind the boundary: var2_frames_pass2_1d's, y kept in registers
+    {
+        float raw[T];
+        request_group(a.x + first, n, s0, raw);
+        const FramePair f1 = frame_pair(a.a1 + frame0, j), f2 = frame_pair(a.a2 + frame0, j);
+        const int tt = min(t, a.tiles - 1);
+        float m[kVar2Components], y1, y2;
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index_of(a.n_lines, a.tiles, i, line, tt)];
+        apply_map(m, a.carry[((int64_t)0 * a.n_lines + line) * a.groups + g], a.carry[((int64_t)1 * a.n_lines + line) * a.groups + g], y1, y2);
+        y_near = y1; y_far = y2;                      // y one and two samples before the tile, in the order of the recurrence
+        transpose_in(raw, lds, y);
+#pragma unroll
+        for (int i = 0; i < T; i++) y[i] = t0 + i < n ? y[i] : 0.0f;
+#pragma unroll
+        for (int s = 0; s < T; s++) {
+            const int i = REV ? T - 1 - s : s;
+            const float r = step2(own_frame<REV, 1>(f1, k0, i, inv_hop, n, t0), own_frame<REV, 2>(f2, k0, i, inv_hop, n, t0), y[i], y1, y2);
+            y[i] = r; y2 = y1; y1 = r;
+        }
+    }
+    if constexpr (KEEP) {
+        store_group(lds, a.keep + first, n, s0, y);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < T; i++) y[i] = t0 + i < n ? y[i] : 0.0f;
+    // the section in front of the boundary: its feed-forward part on y in feed_forward's order, then its tails stage
+    {
+        const FramePair f0 = frame_pair(a.next_b0 + frame0, j), g1 = frame_pair(a.next_b1 + frame0, j), g2 = frame_pair(a.next_b2 + frame0, j);
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            const float one = REV ? (i + 1 < T ? y[i + 1 < T ? i + 1 : 0] : y_near) : (i >= 1 ? y[i >= 1 ? i - 1 : 0] : y_near);
+            const float two = REV ? (i + 2 < T ? y[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? y_near : y_far))
+                                  : (i >= 2 ? y[i >= 2 ? i - 2 : 0] : (i == 1 ? y_near : y_far));
+            float w = own_frame<REV, 0>(f0, k0, i, inv_hop, n, t0) * y[i];
+            w = __builtin_fmaf(own_frame<REV, 1>(g1, k0, i, inv_hop, n, t0), one, w);
+            v[i] = __builtin_fmaf(own_frame<REV, 2>(g2, k0, i, inv_hop, n, t0), two, w);
+        }
+    }
+    store_group(lds, a.dst + first, n, s0, v);
+    const FramePair h1 = frame_pair(a.next_a1 + frame0, j), h2 = frame_pair(a.next_a2 + frame0, j);
+    float y1 = 0.0f, y2 = 0.0f, u1 = 1.0f, u2 = 0.0f, w1 = 0.0f, w2 = 1.0f;
+#pragma unroll
+    for (int s = 0; s < T; s++) {
+        const int i = REV ? T - 1 - s : s;
+        const float c1 = own_frame<REV, 1>(h1, k0, i, inv_hop, n, t0), c2 = own_frame<REV, 2>(h2, k0, i, inv_hop, n, t0);
+        const float r = step2(c1, c2, v[i], y1, y2);
+        const float u = step2(c1, c2, 0.0f, u1, u2);
+        const float w = step2(c1, c2, 0.0f, w1, w2);
+        y2 = y1; y1 = r; u2 = u1; u1 = u; w2 = w1; w1 = w;
+    }
+    store_tails<REV>(a.tails, a.n_lines, a.tiles, a.groups, line, g, t, y1, y2, u1, u2, w1, w2);
+}
+
+// var2_adj_link_kernel on frames.  REV: the direction of the adjoint recurrence.  The shifted reads -- a1, b1 one sample and a2,
+// b2 two samples along the forward's direction -- are frame_lerp inside the tile and frame_at at a clamped position beyond it
+// (the ADJ branch of var2_frames_kernel).  KEEP: lam of the finished section is stored to a.keep.
+template <bool REV, bool KEEP>
+__global__ void __launch_bounds__(64) var2_adj_frames_link_kernel(Var2AdjFramesLinkArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.x, line = blockIdx.y;
+    const int n = a.n;
+    const int s0 = g * kGroupSamples;                 // below 2^30 + 4096
+    const int t = g * kGroupTiles + lane, t0 = t * T;
+    const int64_t first = (int64_t)line * a.stride, frame0 = (int64_t)line * a.frame_stride;
+    const int shift = a.hop_shift;
+    const float inv_hop = a.inv_hop;
+    const int j = min(t0 >> shift, a.n_frames - 2), k0 = t0 & ((1 << shift) - 1);
+    const int near = REV ? t0 + T : t0 - 1, far = REV ? t0 + T + 1 : t0 - 2;      // beyond the tile, against the recurrence
+    const int at_near = max(min(near, n - 1), 0), at_far = max(min(far, n - 1), 0);
+    float lam[T], v[T];
+    float lam_near, lam_far;
+    // the final stage of section k's adjoint scan: var2_adj_frames_pass2_1d's, lam kept in registers
+    {
+        float raw[T];
+        request_group(a.x + first, n, s0, raw);
+        const FramePair f1 = frame_pair(a.a1 + frame0, j), f2 = frame_pair(a.a2 + frame0, j);
+        const float nb1 = frame_at(a.a1 + frame0, at_near, shift, inv_hop);
+        const float nb2_near = frame_at(a.a2 + frame0, at_near, shift, inv_hop), nb2_far = frame_at(a.a2 + frame0, at_far, shift, inv_hop);
+        const int tt = min(t, a.tiles - 1);
+        float m[kVar2Components], y1, y2;
+#pragma unroll
+        for (int i = 0; i < kVar2Components; i++) m[i] = a.tails[map_index_of(a.n_lines, a.tiles, i, line, tt)];
+        apply_map(m, a.carry[((int64_t)0 * a.n_lines + line) * a.groups + g], a.carry[((int64_t)1 * a.n_lines + line) * a.groups + g], y1, y2);
+        lam_near = y1; lam_far = y2;                  // lam one and two samples before the tile, in the order of the recurrence
+        transpose_in(raw, lds, lam);
+#pragma unroll
+        for (int i = 0; i < T; i++) lam[i] = t0 + i < n ? lam[i] : 0.0f;
+#pragma unroll
+        for (int s = 0; s < T; s++) {
+            const int i = REV ? T - 1 - s : s;
+            const float c1 = shifted_frame<REV, 1>(f1, k0, i, inv_hop, nb1, nb1, n, t0);
+            const float c2 = shifted_frame<REV, 2>(f2, k0, i, inv_hop, nb2_near, nb2_far, n, t0);
+            const float r = step2(c1, c2, lam[i], y1, y2);
+            lam[i] = r; y2 = y1; y1 = r;
+        }
+    }
+    if constexpr (KEEP) {
+        store_group(lds, a.keep + first, n, s0, lam);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < T; i++) lam[i] = t0 + i < n ? lam[i] : 0.0f;
+    // the transposed feed-forward part of section k on lam: var2_biquad_grad_1d's order
+    {
+        const FramePair f0 = frame_pair(a.b0 + frame0, j), g1 = frame_pair(a.b1 + frame0, j), g2 = frame_pair(a.b2 + frame0, j);
+        const float b1_near = frame_at(a.b1 + frame0, at_near, shift, inv_hop);
+        const float b2_near = frame_at(a.b2 + frame0, at_near, shift, inv_hop), b2_far = frame_at(a.b2 + frame0, at_far, shift, inv_hop);
+#pragma unroll
+        for (int i = 0; i < T; i++) {
+            const float one = REV ? (i + 1 < T ? lam[i + 1 < T ? i + 1 : 0] : lam_near) : (i >= 1 ? lam[i >= 1 ? i - 1 : 0] : lam_near);
+            const float two = REV ? (i + 2 < T ? lam[i + 2 < T ? i + 2 : 0] : (i + 2 == T ? lam_near : lam_far))
+                                  : (i >= 2 ? lam[i >= 2 ? i - 2 : 0] : (i == 1 ? lam_near : lam_far));
+            float w = own_frame<REV, 0>(f0, k0, i, inv_hop, n, t0) * lam[i];
+            w = __builtin_fmaf(shifted_frame<REV, 1>(g1, k0, i, inv_hop, b1_near, b1_near, n, t0), one, w);
+            v[i] = __builtin_fmaf(shifted_frame<REV, 2>(g2, k0, i, inv_hop, b2_near, b2_far, n, t0), two, w);
+        }
+    }
+    store_group(lds, a.dst + first, n, s0, v);
+#pragma unroll
+    for (int i = 0; i < T; i++) v[i] = t0 + i < n ? v[i] : 0.0f;
+    // the adjoint tails stage of section k - 1 on v, the gradient that enters it
+    const FramePair h1 = frame_pair(a.prev_a1 + frame0, j), h2 = frame_pair(a.prev_a2 + frame0, j);
+    const float pb1 = frame_at(a.prev_a1 + frame0, at_near, shift, inv_hop);
+    const float pb2_near = frame_at(a.prev_a2 + frame0, at_near, shift, inv_hop), pb2_far = frame_at(a.prev_a2 + frame0, at_far, shift, inv_hop);
+    float y1 = 0.0f, y2 = 0.0f, u1 = 1.0f, u2 = 0.0f, w1 = 0.0f, w2 = 1.0f;
+#pragma unroll
+    for (int s = 0; s < T; s++) {
+        const int i = REV ? T - 1 - s : s;
+        const float c1 = shifted_frame<REV, 1>(h1, k0, i, inv_hop, pb1, pb1, n, t0);
+        const float c2 = shifted_frame<REV, 2>(h2, k0, i, inv_hop, pb2_near, pb2_far, n, t0);
+        const float r = step2(c1, c2, v[i], y1, y2);
+        const float u = step2(c1, c2, 0.0f, u1, u2);
+        const float w = step2(c1, c2, 0.0f, w1, w2);
+        y2 = y1; y1 = r; u2 = u1; u1 = u; w2 = w1; w1 = w;
+    }
+    store_tails<REV>(a.tails, a.n_lines, a.tiles, a.groups, line, g, t, y1, y2, u1, u2, w1, w2);
+}
+
 // one coefficient at audio rate: four samples per lane, which share an interval (hop is a multiple of 4)
 __global__ void __launch_bounds__(kGradLanes) var2_expand_frames_kernel(Var2ExpandArgs a) {
     const int at = (blockIdx.x * kGradLanes + threadIdx.x) * 4;      // below 2^30 + 1024
@@ -939,8 +1146,11 @@ __global__ void __launch_bounds__(kGradLanes) var2_expand_frames_kernel(Var2Expa
 // products and selects, rounded to f32 -- weighted by 1 - k / hop (S0, to the interval's first frame) and k / hop (S1, to its
 // second) and summed in f64, where every product is exact: a lane in the order of its four samples, the lanes of a piece of
 // min(hop, 1024) samples by a fixed tree -- shuffles within a wave, then the piece's first lane over its waves' sums in order.
-template <bool CAUSAL, bool FRAMES>
+// COEF_ONLY (var2_frames_coef_1d): the FRAMES half alone, for a section whose input gradient var2_adj_frames_link_keep_1d has
+// formed -- the same products, the same sums in the same order, from lam, x and y; no tap is read and grad_in is not written.
+template <bool CAUSAL, bool FRAMES, bool COEF_ONLY = false>
 __global__ void __launch_bounds__(kGradLanes) var2_frames_grad_kernel(Var2FramesGradArgs a) {
+    static_assert(!COEF_ONLY || FRAMES, "the sums are what is left");
     static_assert(kGradLanes * 4 == kVar2GradBlock, "a workgroup's samples");
     __shared__ double sums[kGradLanes / 64][kVar2FrameSums];
     const int n = a.n;
@@ -955,19 +1165,24 @@ __global__ void __launch_bounds__(kGradLanes) var2_frames_grad_kernel(Var2Frames
     float lam[6] = {};
     double s[kVar2FrameSums] = {};
     if (inside) {
-        load_six<CAUSAL>(a.lam + first, at, n, lam);
-        float gx[4];
+        if constexpr (COEF_ONLY) {
+            const float4 q = *reinterpret_cast<const float4 *>(a.lam + first + at);
+            lam[L0] = q.x; lam[L0 + 1] = q.y; lam[L0 + 2] = q.z; lam[L0 + 3] = q.w;
+        } else {
+            load_six<CAUSAL>(a.lam + first, at, n, lam);
+            float gx[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int one = CAUSAL ? at + k + 1 : at + k - 1, two = CAUSAL ? at + k + 2 : at + k - 2;
-            const int i1 = CAUSAL ? L0 + k + 1 : L0 + k - 1, i2 = CAUSAL ? L0 + k + 2 : L0 + k - 2;
-            const float t0 = frame_at(a.b0 + frame0, at + k, shift, inv_hop);
-            const float t1 = frame_at(a.b1 + frame0, max(min(one, n - 1), 0), shift, inv_hop);
-            const float t2 = frame_at(a.b2 + frame0, max(min(two, n - 1), 0), shift, inv_hop);
-            const float c1 = (one < 0 || one >= n) ? 0.0f : t1, c2 = (two < 0 || two >= n) ? 0.0f : t2;
-            gx[k] = __builtin_fmaf(c2, lam[i2], __builtin_fmaf(c1, lam[i1], t0 * lam[L0 + k]));
+            for (int k = 0; k < 4; k++) {
+                const int one = CAUSAL ? at + k + 1 : at + k - 1, two = CAUSAL ? at + k + 2 : at + k - 2;
+                const int i1 = CAUSAL ? L0 + k + 1 : L0 + k - 1, i2 = CAUSAL ? L0 + k + 2 : L0 + k - 2;
+                const float t0 = frame_at(a.b0 + frame0, at + k, shift, inv_hop);
+                const float t1 = frame_at(a.b1 + frame0, max(min(one, n - 1), 0), shift, inv_hop);
+                const float t2 = frame_at(a.b2 + frame0, max(min(two, n - 1), 0), shift, inv_hop);
+                const float c1 = (one < 0 || one >= n) ? 0.0f : t1, c2 = (two < 0 || two >= n) ? 0.0f : t2;
+                gx[k] = __builtin_fmaf(c2, lam[i2], __builtin_fmaf(c1, lam[i1], t0 * lam[L0 + k]));
+            }
+            *reinterpret_cast<float4 *>(a.grad_in + first + at) = make_float4(gx[0], gx[1], gx[2], gx[3]);
         }
-        *reinterpret_cast<float4 *>(a.grad_in + first + at) = make_float4(gx[0], gx[1], gx[2], gx[3]);
         if constexpr (FRAMES) {
             float xs[6], ys[6];
             load_six<!CAUSAL>(a.x + first, at, n, xs);
@@ -1021,28 +1236,41 @@ __global__ void __launch_bounds__(kGradLanes) var2_frames_grad_kernel(Var2Frames
 }
 
 // dL/dc_j = (the S0 of interval j's pieces, in order) + (the S1 of interval j - 1's pieces, in order), rounded once to f32.
-// One lane per frame; a piece that begins beyond the line does not exist.
-__global__ void __launch_bounds__(kGradLanes) var2_frames_fold_kernel(Var2FramesGradArgs a) {
-    const int j = blockIdx.x * kGradLanes + threadIdx.x, line = blockIdx.y;
-    if (j >= a.n_frames) return;
-    const int per_interval = max(1, (1 << a.hop_shift) / kVar2GradBlock);
-    const double *slab = a.slab + (int64_t)line * a.pieces * kVar2FrameSums;
-    float *const grads[5] = {a.grad_b0, a.grad_b1, a.grad_b2, a.grad_a1, a.grad_a2};
+// One lane per frame; a piece that begins beyond the line does not exist.  slab: the line's sums; grads: the line's five rows.
+__device__ __forceinline__ void fold_frame(const double *slab, int j, int n_frames, int hop_shift, int pieces, float *const (&grads)[5]) {
+    const int per_interval = max(1, (1 << hop_shift) / kVar2GradBlock);
     double own[5] = {}, before[5] = {};
-    if (j + 1 < a.n_frames) {
-        for (int p = j * per_interval; p < min((j + 1) * per_interval, a.pieces); p++) {
+    if (j + 1 < n_frames) {
+        for (int p = j * per_interval; p < min((j + 1) * per_interval, pieces); p++) {
 #pragma unroll
             for (int c = 0; c < 5; c++) own[c] += slab[(int64_t)p * kVar2FrameSums + 2 * c];
         }
     }
     if (j >= 1) {
-        for (int p = (j - 1) * per_interval; p < min(j * per_interval, a.pieces); p++) {
+        for (int p = (j - 1) * per_interval; p < min(j * per_interval, pieces); p++) {
 #pragma unroll
             for (int c = 0; c < 5; c++) before[c] += slab[(int64_t)p * kVar2FrameSums + 2 * c + 1];
         }
     }
 #pragma unroll
-    for (int c = 0; c < 5; c++) grads[c][(int64_t)line * a.frame_stride + j] = (float)(own[c] + before[c]);
+    for (int c = 0; c < 5; c++) grads[c][j] = (float)(own[c] + before[c]);
+}
+
+__global__ void __launch_bounds__(kGradLanes) var2_frames_fold_kernel(Var2FramesGradArgs a) {
+    const int j = blockIdx.x * kGradLanes + threadIdx.x, line = blockIdx.y;
+    if (j >= a.n_frames) return;
+    const int64_t row = (int64_t)line * a.frame_stride;
+    float *const grads[5] = {a.grad_b0 + row, a.grad_b1 + row, a.grad_b2 + row, a.grad_a1 + row, a.grad_a2 + row};
+    fold_frame(a.slab + (int64_t)line * a.pieces * kVar2FrameSums, j, a.n_frames, a.hop_shift, a.pieces, grads);
+}
+
+// the fold of every section of a cascade: the section on gridDim.z, its sums and gradients from the argument struct
+__global__ void __launch_bounds__(kGradLanes) var2_frames_fold_cascade_kernel(Var2FramesFoldCascadeArgs a) {
+    const int j = blockIdx.x * kGradLanes + threadIdx.x, line = blockIdx.y, k = blockIdx.z;
+    if (j >= a.n_frames) return;
+    const int64_t row = (int64_t)line * a.frame_stride;
+    float *const grads[5] = {a.grads[k][0] + row, a.grads[k][1] + row, a.grads[k][2] + row, a.grads[k][3] + row, a.grads[k][4] + row};
+    fold_frame(a.slab + k * a.section_doubles + (int64_t)line * a.pieces * kVar2FrameSums, j, a.n_frames, a.hop_shift, a.pieces, grads);
 }
 
 int launched(const char *what) {
@@ -1180,6 +1408,43 @@ int launch_var2_frames_fold(const Var2FramesGradArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.n_frames + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
     hipLaunchKernelGGL(var2_frames_fold_kernel, grid, block, 0, stream, a);
     return launched("var2_frames_fold_1d");
+}
+
+int launch_var2_frames_link(const Var2FramesLinkArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.keep) {
+        if (a.causal) hipLaunchKernelGGL((var2_frames_link_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_link_kernel<true, true>), grid, block, 0, stream, a);
+        return launched("var2_frames_link_keep_1d");
+    }
+    if (a.causal) hipLaunchKernelGGL((var2_frames_link_kernel<false, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_frames_link_kernel<true, false>), grid, block, 0, stream, a);
+    return launched("var2_frames_link_1d");
+}
+
+int launch_var2_adj_frames_link(const Var2AdjFramesLinkArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.keep) {
+        if (a.causal) hipLaunchKernelGGL((var2_adj_frames_link_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_adj_frames_link_kernel<true, true>), grid, block, 0, stream, a);
+        return launched("var2_adj_frames_link_keep_1d");
+    }
+    if (a.causal) hipLaunchKernelGGL((var2_adj_frames_link_kernel<false, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_adj_frames_link_kernel<true, false>), grid, block, 0, stream, a);
+    return launched("var2_adj_frames_link_1d");
+}
+
+int launch_var2_frames_coef(const Var2FramesGradArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.causal) hipLaunchKernelGGL((var2_frames_grad_kernel<true, true, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((var2_frames_grad_kernel<false, true, true>), grid, block, 0, stream, a);
+    return launched("var2_frames_coef_1d");
+}
+
+int launch_var2_frames_fold_cascade(const Var2FramesFoldCascadeArgs &a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.n_frames + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines, (unsigned)a.n_sections), block(kGradLanes);
+    hipLaunchKernelGGL(var2_frames_fold_cascade_kernel, grid, block, 0, stream, a);
+    return launched("var2_frames_fold_cascade_1d");
 }
 
 }  // namespace rf

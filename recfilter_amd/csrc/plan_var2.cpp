@@ -870,7 +870,7 @@ int run_var2_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_sec
 
 int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames, int64_t frame_stride,
                                     const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
-                                    hipStream_t stream, float *ms_out) {
+                                    hipStream_t stream, float *ms_out, bool in_required) {
     if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
     int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
     if (rc != RF_OK) return rc;
@@ -880,7 +880,8 @@ int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf
     const int given = (fg.b0 != nullptr) + (fg.b1 != nullptr) + (fg.b2 != nullptr) + (fg.a1 != nullptr) + (fg.a2 != nullptr);
     const bool with_frames = given == 5;
     // (null pointers are refused first; the count of the frame gradients behind them, as the header orders the refusals)
-    rc = check_plane("signal", 0, {{in}, {grad_out}, {grad_in}, {out, with_frames}}, 15u,
+    // (in_required == false: a cascade of one section, which reads nothing of the forward without frame gradients)
+    rc = check_plane("signal", 0, {{in, in_required || with_frames}, {grad_out}, {grad_in}, {out, with_frames}}, 15u,
                      "null pointer (in, grad_out, grad_in; out where frame gradients are asked for)", kFrameAlign);
     if (rc == RF_OK) rc = check_plane("frames", 0, {{frames->b0}, {frames->b1}, {frames->b2}, {frames->a1}, {frames->a2}, {fg.b0, false}, {fg.b1, false},
                                                     {fg.b2, false}, {fg.a1, false}, {fg.a2, false}}, 3u, "null pointer (b0, b1, b2, a1, a2)", kFrameAlign);
@@ -954,6 +955,319 @@ int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf
     if (rc == RF_OK) rc = timer.mark();
     if (rc == RF_OK && with_frames) {
         rc = launch_var2_frames_fold(g, stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+// ---- a cascade of sections on control-rate frames ----------------------------------------------------------------------------------
+//   forward    var2_biquad_frames_tails_1d (v_0 to out, or to kept[0]), then per boundary var2_carry_1d and var2_frames_link_1d
+//              (var2_frames_link_keep_1d where the caller keeps: section k's v, then its result, in kept[k]), then var2_carry_1d and
+//              var2_frames_pass2_1d.  No coefficient signal exists: 8 K + 8 bytes per sample, 4 more per kept signal.
+//   backward   on the kept signals, nothing rerun: var2_adj_frames_tails_1d on grad_out; per boundary from the last one down
+//              var2_carry_1d and var2_adj_frames_link_1d -- with frame gradients var2_adj_frames_link_keep_1d, lam_k to the plan's
+//              lam, and var2_frames_coef_1d: section k's sums into its part of the slab -- then var2_carry_1d,
+//              var2_adj_frames_pass2_1d and var2_biquad_frames_grad_1d for section 0, and var2_frames_fold_cascade_1d for all.
+// One section: run_var2_biquad_frames and run_var2_biquad_frames_backward, their launches and bits.
+const char *var2_cascade_frames_name(const rf_var2_plan *plan, int n_sections, bool keep, size_t i) {
+    if (n_sections == 1) return plan->frames_names[i].c_str();
+    if (i == 0) return "var2_biquad_frames_tails_1d";
+    if (i + 1 == (size_t)var2_cascade_frames_launches(n_sections)) return "var2_frames_pass2_1d";
+    return i % 2 == 1 ? "var2_carry_1d" : keep ? "var2_frames_link_keep_1d" : "var2_frames_link_1d";
+}
+
+const char *var2_cascade_frames_backward_name(const rf_var2_plan *plan, int n_sections, bool with_frames, size_t i) {
+    if (n_sections == 1) return plan->frames_backward_names[with_frames ? 1 : 0][i].c_str();
+    static const char *const last[4] = {"var2_carry_1d", "var2_adj_frames_pass2_1d", "var2_biquad_frames_grad_1d", "var2_frames_fold_cascade_1d"};
+    const size_t launches = (size_t)var2_cascade_frames_backward_launches(n_sections, with_frames), tail = with_frames ? 4 : 3;
+    if (i == 0) return "var2_adj_frames_tails_1d";
+    if (i + tail >= launches) return last[i + tail - launches];
+    const size_t at = (i - 1) % (with_frames ? 3 : 2);      // within the launches of one boundary
+    return at == 0 ? "var2_carry_1d" : at == 2 ? "var2_frames_coef_1d" : with_frames ? "var2_adj_frames_link_keep_1d" : "var2_adj_frames_link_1d";
+}
+
+namespace {
+
+// "frames k: ..." for every section: no pointer null, all 4-byte aligned
+int check_section_frames(const rf_var2_section *frames, int n_sections) {
+    for (int k = 0; k < n_sections; k++) {
+        const rf_var2_section &s = frames[k];
+        int rc = check_plane("frames", k, {{s.b0}, {s.b1}, {s.b2}, {s.a1}, {s.a2}}, 3u, "null pointer (b0, b1, b2, a1, a2)", kFrameAlign);
+        if (rc != RF_OK) return rc;
+    }
+    return RF_OK;
+}
+
+int grow(float **signal, size_t bytes, const char *what) {
+    if (*signal) return RF_OK;
+    if (hipMalloc((void **)signal, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *signal = nullptr;
+        set_error("hipMalloc of %zu bytes for %s failed", bytes, what);
+        return RF_ERR_NOMEM;
+    }
+    return RF_OK;
+}
+
+}  // namespace
+
+int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
+                            int64_t frame_stride, void *out, void *const *kept, hipStream_t stream, float *ms_out, const char **names_out,
+                            int capacity, bool timed) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
+    const int K = n_sections;
+    const bool keep = kept != nullptr && K >= 2;
+    const size_t launches = (size_t)var2_cascade_frames_launches(K);
+    if (timed) {
+        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_frames_name(plan, K, keep, i); }, ms_out, names_out, capacity);
+        if (rc != RF_OK) return rc;
+    }
+    if (K == 1) return run_var2_biquad_frames(plan, in, frames, hop, n_frames, frame_stride, out, stream, ms_out);
+    int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
+    if (rc != RF_OK) return rc;
+    if (!frames) return refuse(RF_ERR_INVALID_ARG, "null frames");
+    rc = check_plane("signal", 0, {{in}, {out}}, 15u, "null pointer (in, out)", kFrameAlign);
+    if (rc == RF_OK && keep) rc = check_kept(kept, K - 1, true);
+    if (rc == RF_OK) rc = check_section_frames(frames, K);
+    if (rc != RF_OK) return rc;
+    const size_t bytes = plan->span_bytes(), frame_bytes = frames_span_bytes(plan->n_lines, n_frames, frame_stride);
+    SectionLists arrays("frames", K);
+    for (int k = 0; k < K; k++) arrays.planes.insert(arrays.planes.end(), {frames[k].b0, frames[k].b1, frames[k].b2, frames[k].a1, frames[k].a2});
+    std::vector<PlaneList> read;
+    const void *const result[1] = {out}, *const input[1] = {in};
+    read.push_back({"in", input, 1, bytes,
+                    ": in == out is not allowed for a biquad (the first launch stores the feed-forward part while neighbouring groups still read in)"});
+    for (int k = 0; k < K; k++) read.push_back(arrays.list(k, 5, frame_bytes, ": a frame array is read while outputs are stored"));
+    const PlaneList written[2] = {{"out", result, 1, bytes}, {"kept", (const void *const *)kept, keep ? K - 1 : 0, bytes}};
+    rc = check_written_planes(written, 1, read.data(), (int)read.size(), {"grad_out", nullptr, 0, bytes});      // out first
+    if (rc != RF_OK) return rc;
+    read.front().why = ": a kept signal is stored while neighbouring groups still read in";
+    rc = check_written_planes(written, 2, read.data(), (int)read.size(), {"grad_out", nullptr, 0, bytes});      // then the kept signals
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    LaunchTimer timer(stream, ms_out, launches);
+    if (timer.status() != RF_OK) return timer.status();
+    float *signals[RF_VAR2_MAX_SECTIONS];      // where section k's v, then its result, lies
+    for (int k = 0; k < K; k++) signals[k] = keep && k + 1 < K ? (float *)kept[k] : (float *)out;
+    Var2FramesArgs a = frames_args(plan, frames[0], hop, n_frames, frame_stride, plan->causal, false);
+    a.x = (const float *)in;
+    a.dst = signals[0];
+    rc = launch_var2_frames_tails(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    const Var2Args carry = scan_args(plan, plan->causal, false);
+    for (int k = 1; k < K && rc == RF_OK; k++) {
+        rc = launch_var2_carry(carry, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        Var2FramesLinkArgs l{};
+        l.x = signals[k - 1];
+        l.a1 = (const float *)frames[k - 1].a1;
+        l.a2 = (const float *)frames[k - 1].a2;
+        l.next_b0 = (const float *)frames[k].b0;
+        l.next_b1 = (const float *)frames[k].b1;
+        l.next_b2 = (const float *)frames[k].b2;
+        l.next_a1 = (const float *)frames[k].a1;
+        l.next_a2 = (const float *)frames[k].a2;
+        l.dst = signals[k];
+        l.keep = keep ? signals[k - 1] : nullptr;
+        l.tails = a.tails;
+        l.carry = a.carry;
+        l.n = a.n;
+        l.tiles = a.tiles;
+        l.groups = a.groups;
+        l.n_lines = a.n_lines;
+        l.causal = a.causal;
+        l.hop_shift = a.hop_shift;
+        l.n_frames = n_frames;
+        l.inv_hop = a.inv_hop;
+        l.stride = a.stride;
+        l.frame_stride = frame_stride;
+        if (rc == RF_OK) rc = launch_var2_frames_link(l, stream);
+        if (rc == RF_OK) rc = timer.mark();
+    }
+    if (rc == RF_OK) rc = launch_var2_carry(carry, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    Var2FramesArgs last = frames_args(plan, frames[K - 1], hop, n_frames, frame_stride, plan->causal, false);
+    last.x = last.dst = (float *)out;
+    if (rc == RF_OK) rc = launch_var2_frames_pass2(last, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    return rc == RF_OK ? timer.finish() : rc;
+}
+
+int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
+                                     int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                     const rf_var2_section_grad *frame_grads, hipStream_t stream, float *ms_out, const char **names_out,
+                                     int capacity, bool timed) {
+    if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
+    if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
+    const int K = n_sections;
+    // with frame gradients: every pointer of every section given.  Anything between that and none at all is refused below
+    int given = 0;
+    bool partial = false;      // a section with one to four of its five
+    for (int k = 0; frame_grads && k < K; k++) {
+        const rf_var2_section_grad &g = frame_grads[k];
+        const int own = (g.b0 != nullptr) + (g.b1 != nullptr) + (g.b2 != nullptr) + (g.a1 != nullptr) + (g.a2 != nullptr);
+        partial = partial || (own != 0 && own != 5);
+        given += own;
+    }
+    const bool with_frames = given == 5 * K;
+    const size_t launches = (size_t)var2_cascade_frames_backward_launches(K, with_frames);
+    if (timed) {
+        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_frames_backward_name(plan, K, with_frames, i); }, ms_out, names_out, capacity);
+        if (rc != RF_OK) return rc;
+    }
+    if (K == 1)
+        return run_var2_biquad_frames_backward(plan, in, frames, hop, n_frames, frame_stride, out, grad_out, grad_in, frame_grads, stream, ms_out,
+                                               false);
+    int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
+    if (rc != RF_OK) return rc;
+    if (!frames) return refuse(RF_ERR_INVALID_ARG, "null frames");
+    // without frame gradients nothing of the forward is read: in, out and kept may be null
+    rc = check_plane("signal", 0, {{in, with_frames}, {grad_out}, {grad_in}, {out, with_frames}}, 15u,
+                     "null pointer (grad_out, grad_in; in and out where frame gradients are asked for)", kFrameAlign);
+    if (rc == RF_OK) rc = check_kept(kept, K - 1, with_frames);
+    if (rc == RF_OK) rc = check_section_frames(frames, K);
+    for (int k = 0; rc == RF_OK && frame_grads && k < K; k++) {
+        const rf_var2_section_grad &g = frame_grads[k];
+        rc = check_plane("frame gradients", k, {{g.b0, false}, {g.b1, false}, {g.b2, false}, {g.a1, false}, {g.a2, false}}, 3u, "", kFrameAlign);
+    }
+    if (rc != RF_OK) return rc;
+    if (partial || (given != 0 && !with_frames))
+        return refuse(RF_ERR_INVALID_ARG, "the five frame gradients of a section are all given or all null, and every section alike (the fold "
+                                          "forms them all; %lld of %lld pointers given)", given, 5 * K);
+    const size_t bytes = plan->span_bytes(), frame_bytes = frames_span_bytes(plan->n_lines, n_frames, frame_stride);
+    SectionLists arrays("frames", K), gradients("gradient of frames", K);
+    for (int k = 0; k < K; k++) {
+        arrays.planes.insert(arrays.planes.end(), {frames[k].b0, frames[k].b1, frames[k].b2, frames[k].a1, frames[k].a2});
+        if (with_frames)
+            gradients.planes.insert(gradients.planes.end(), {frame_grads[k].b0, frame_grads[k].b1, frame_grads[k].b2, frame_grads[k].a1, frame_grads[k].a2});
+    }
+    const void *const gin[1] = {grad_in}, *const input[1] = {in}, *const result[1] = {out}, *const gout[1] = {grad_out};
+    std::vector<PlaneList> written, read;
+    written.push_back({"grad_in", gin, 1, bytes});
+    for (int k = 0; with_frames && k < K; k++) written.push_back(gradients.list(k, 5, frame_bytes));
+    for (int k = 0; k < K; k++) read.push_back(arrays.list(k, 5, frame_bytes, ": a frame array is read while outputs are stored"));
+    read.push_back({"in", input, with_frames ? 1 : 0, bytes});
+    read.push_back({"out", result, with_frames ? 1 : 0, bytes});
+    read.push_back({"kept", kept, with_frames ? K - 1 : 0, bytes});
+    rc = check_written_planes(written.data(), (int)written.size(), read.data(), (int)read.size(), {"grad_out", gout, 1, bytes});
+    if (rc != RF_OK) return rc;
+    if (plan->host_only) return refuse_host_only();
+    RF_HIP_CHECK(hipSetDevice(plan->device));
+    rc = grow(&plan->lam, bytes, "the adjoint state of the cascade's backward");
+    if (rc != RF_OK) return rc;
+    if (plan->cascade_spans < 1) {
+        rc = grow(&plan->cascade, bytes, "the gradient between the sections of the cascade's backward");
+        if (rc != RF_OK) return rc;
+        plan->cascade_spans = 1;
+    }
+    const size_t section_bytes = plan->frames_slab_needed(hop), slab_bytes = section_bytes * (size_t)K;
+    if (with_frames && plan->frames_slab_bytes < slab_bytes) {
+        // (hipFree waits for the device: no earlier call on this plan still uses the slab)
+        if (plan->frames_slab) (void)hipFree(plan->frames_slab);
+        plan->frames_slab = nullptr;
+        plan->frames_slab_bytes = 0;
+        if (hipMalloc((void **)&plan->frames_slab, slab_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            plan->frames_slab = nullptr;
+            set_error("hipMalloc of %zu bytes for the partial sums of the frame gradients failed", slab_bytes);
+            return RF_ERR_NOMEM;
+        }
+        plan->frames_slab_bytes = slab_bytes;
+    }
+    LaunchTimer timer(stream, ms_out, launches);
+    if (timer.status() != RF_OK) return timer.status();
+    float *between = plan->cascade;                   // G: g_{k-1}
+    const int64_t section_doubles = (int64_t)(section_bytes / sizeof(double));
+    Var2FramesArgs a = frames_args(plan, frames[K - 1], hop, n_frames, frame_stride, !plan->causal, true);
+    a.x = (const float *)grad_out;
+    a.dst = plan->lam;
+    rc = launch_var2_frames_tails(a, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    const Var2Args carry = scan_args(plan, !plan->causal, true);
+    Var2FramesGradArgs g{};
+    g.lam = plan->lam;
+    g.n = (int32_t)plan->length;
+    g.n_lines = plan->n_lines;
+    g.causal = plan->causal ? 1 : 0;
+    g.with_frames = with_frames ? 1 : 0;
+    g.hop_shift = a.hop_shift;
+    g.n_frames = n_frames;
+    g.pieces = (int32_t)var2_frames_pieces(plan->length, hop);
+    g.inv_hop = a.inv_hop;
+    g.stride = plan->stride;
+    g.frame_stride = frame_stride;
+    for (int k = K - 1; k >= 1 && rc == RF_OK; k--) {
+        rc = launch_var2_carry(carry, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        Var2AdjFramesLinkArgs l{};
+        l.x = k == K - 1 ? (const float *)grad_out : between;
+        l.a1 = (const float *)frames[k].a1;
+        l.a2 = (const float *)frames[k].a2;
+        l.b0 = (const float *)frames[k].b0;
+        l.b1 = (const float *)frames[k].b1;
+        l.b2 = (const float *)frames[k].b2;
+        l.prev_a1 = (const float *)frames[k - 1].a1;
+        l.prev_a2 = (const float *)frames[k - 1].a2;
+        l.dst = between;
+        l.keep = with_frames ? plan->lam : nullptr;
+        l.tails = a.tails;
+        l.carry = a.carry;
+        l.n = a.n;
+        l.tiles = a.tiles;
+        l.groups = a.groups;
+        l.n_lines = a.n_lines;
+        l.causal = a.causal;
+        l.hop_shift = a.hop_shift;
+        l.n_frames = n_frames;
+        l.inv_hop = a.inv_hop;
+        l.stride = a.stride;
+        l.frame_stride = frame_stride;
+        if (rc == RF_OK) rc = launch_var2_adj_frames_link(l, stream);
+        if (rc == RF_OK) rc = timer.mark();
+        if (rc == RF_OK && with_frames) {
+            g.x = (const float *)kept[k - 1];
+            g.y = k == K - 1 ? (const float *)out : (const float *)kept[k];
+            g.slab = plan->frames_slab + k * section_doubles;
+            rc = launch_var2_frames_coef(g, stream);
+            if (rc == RF_OK) rc = timer.mark();
+        }
+    }
+    if (rc == RF_OK) rc = launch_var2_carry(carry, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    Var2FramesArgs first = frames_args(plan, frames[0], hop, n_frames, frame_stride, !plan->causal, true);
+    first.x = between;
+    first.dst = plan->lam;
+    if (rc == RF_OK) rc = launch_var2_frames_pass2(first, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    g.x = (const float *)in;
+    g.y = with_frames ? (const float *)kept[0] : nullptr;
+    g.b0 = (const float *)frames[0].b0;
+    g.b1 = (const float *)frames[0].b1;
+    g.b2 = (const float *)frames[0].b2;
+    g.grad_in = (float *)grad_in;
+    g.slab = plan->frames_slab;
+    if (rc == RF_OK) rc = launch_var2_frames_grad(g, stream);
+    if (rc == RF_OK) rc = timer.mark();
+    if (rc == RF_OK && with_frames) {
+        Var2FramesFoldCascadeArgs f{};
+        f.slab = plan->frames_slab;
+        f.section_doubles = section_doubles;
+        for (int k = 0; k < K; k++) {
+            f.grads[k][0] = (float *)frame_grads[k].b0;
+            f.grads[k][1] = (float *)frame_grads[k].b1;
+            f.grads[k][2] = (float *)frame_grads[k].b2;
+            f.grads[k][3] = (float *)frame_grads[k].a1;
+            f.grads[k][4] = (float *)frame_grads[k].a2;
+        }
+        f.n_sections = K;
+        f.n_lines = plan->n_lines;
+        f.hop_shift = a.hop_shift;
+        f.n_frames = n_frames;
+        f.pieces = g.pieces;
+        f.frame_stride = frame_stride;
+        rc = launch_var2_frames_fold_cascade(f, stream);
         if (rc == RF_OK) rc = timer.mark();
     }
     return rc == RF_OK ? timer.finish() : rc;

@@ -64,7 +64,7 @@ int run_var2_biquad_frames(rf_var2_plan *plan, const void *in, const rf_var2_sec
                            hipStream_t stream, float *ms_out);
 int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int hop, int n_frames, int64_t frame_stride,
                                     const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
-                                    hipStream_t stream, float *ms_out);
+                                    hipStream_t stream, float *ms_out, bool in_required = true);
 // a cascade of n_sections direct-form-I sections: the launches' names (string literals), counts and the backward's memory
 const char *var2_cascade_name(int n_sections, size_t i);
 const char *var2_cascade_backward_name(int n_sections, size_t i);
@@ -94,4 +94,23 @@ int run_var2_cascade_keep(rf_var2_plan *plan, const void *in, const rf_var2_sect
 int run_var2_cascade_kept_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *sections, int n_sections, const void *const *kept,
                                    const void *out, const void *grad_out, void *grad_in, const rf_var2_section_grad *grads, hipStream_t stream,
                                    float *ms_out, const char **names_out, int capacity, bool timed);
+// the cascade on control-rate frames: frames[k] = section k's five frame arrays, one hop, n_frames and frame_stride for all;
+// kept null: the plain link, else n_sections - 1 signals of the caller's.  The backward runs on the kept signals; the plan owns
+// lam, the first span of `cascade` and, with frame gradients, n_sections slabs in frames_slab.  One section: the calls above.
+const char *var2_cascade_frames_name(const rf_var2_plan *plan, int n_sections, bool keep, size_t i);
+const char *var2_cascade_frames_backward_name(const rf_var2_plan *plan, int n_sections, bool with_frames, size_t i);
+inline int var2_cascade_frames_launches(int n_sections) { return n_sections == 1 ? 3 : 2 * n_sections + 1; }
+inline int var2_cascade_frames_backward_launches(int n_sections, bool with_frames) {
+    return n_sections == 1 ? (with_frames ? 5 : 4) : with_frames ? 3 * n_sections + 2 : 2 * n_sections + 2;
+}
+inline size_t var2_cascade_frames_backward_bytes(const rf_var2_plan *plan, int n_sections, int hop) {
+    return plan->span_bytes() * (size_t)(n_sections == 1 ? 1 : 2) + (size_t)n_sections * plan->frames_slab_needed(hop);
+}
+int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
+                            int64_t frame_stride, void *out, void *const *kept, hipStream_t stream, float *ms_out, const char **names_out,
+                            int capacity, bool timed);
+int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
+                                     int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                     const rf_var2_section_grad *frame_grads, hipStream_t stream, float *ms_out, const char **names_out,
+                                     int capacity, bool timed);
 }  // namespace rf

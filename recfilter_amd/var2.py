@@ -492,6 +492,109 @@ class Var2Plan(_PlanHandle):
         function = _cascade_kept_function() if keep else _cascade_function()
         return function.apply(self, x, *(t for s in sections for t in s))
 
+    # -- a cascade of sections on control-rate frames ---------------------------------------------
+    #     sections: K tuples of five FRAME tensors (b0, b1, b2, a1, a2), one hop for all; no coefficient signal exists
+    def cascade_frames_num_kernels(self, sections: int) -> int:
+        """2 K + 1 launches (3 at K = 1: execute_biquad_frames')"""
+        return int(capi.lib().rf_var2_plan_cascade_frames_num_kernels(self._h, int(sections)))
+
+    def backward_cascade_frames_num_kernels(self, sections: int, with_frames: bool = False) -> int:
+        """2 K + 2 launches without frame gradients, 3 K + 2 with them; 4 and 5 at K = 1"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_frames_num_kernels(self._h, int(sections), int(bool(with_frames))))
+
+    def backward_cascade_frames_bytes(self, sections: int, hop: int) -> int:
+        """what the plan owns behind a backward_cascade_frames: lam, the gradient between sections (K >= 2) and K slabs of 80 bytes
+        per piece of min(hop, 1024) samples; 0 for a refused K or hop"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_frames_bytes(self._h, int(sections), int(hop)))
+
+    def _sections_frames(self, sections, hop: int, what: str, like=None):
+        """(the rf_var2_section array of K sections' frames or None, K, n_frames, frame_stride): every tensor checked as
+        _frames_array checks it, all of them one distance between rows"""
+        if sections is None:
+            return None, 0, 0, like
+        K = len(sections)
+        array = (capi.Var2Section * max(K, 1))()
+        count, stride = frames_count(self.length, hop), like
+        for k, s in enumerate(sections):
+            one, count, stride = self._frames_array(s, hop, f"{what}[{k}]", like=stride)
+            array[k] = one[0]
+        return array, K, count, count if stride is None else stride      # (no section: the library refuses the count)
+
+    def _host_sections_frames(self, K: int, hop: int, first: int, with_grads: bool = False):
+        """a host-only plan's arguments: `first` signals, K sections' frames, K - 1 kept signals and, where asked for, K
+        sections' frame gradients -- addresses that pass the library's checks and are never dereferenced"""
+        count = int(capi.lib().rf_var2_frames_count(self.length, int(hop)))
+        p = self._placeholders(first + 10 * K + max(K - 1, 0))
+        sections = lambda at: (capi.Var2Section * max(K, 1))(      # noqa: E731
+            *(capi.Var2Section(*(q.value for q in p[at + 5 * k:at + 5 * k + 5])) for k in range(K)))
+        kept = (ctypes.c_void_p * max(K - 1, 1))(*(q.value for q in p[first + 5 * K:first + 5 * K + max(K - 1, 0)]))
+        return p[:first], sections(first), kept, sections(first + 6 * K - 1) if with_grads else None, count, count
+
+    def _cascade_frames_arguments(self, x, sections, hop, out, keep, kept, stream):
+        K = len(sections)
+        if self._host_only:
+            (px, po), array, pk, _, count, stride = self._host_sections_frames(K, hop, 2)
+            return px, array, K, int(hop), count, stride, po, pk if keep else None, None, None, ctypes.c_void_p()
+        if out is None:
+            out = self._like(x)
+        if keep and kept is None:
+            kept = [self._like(x) for _ in range(K - 1)]
+        array, K, count, stride = self._sections_frames(sections, hop, "sections")
+        pk = self._kept_array(kept, max(K - 1, 0)) if keep else None
+        return (self._pointer(x, "x"), array, K, int(hop), count, stride, self._pointer(out, "out"), pk, out, list(kept) if keep else None,
+                self._stream(stream))
+
+    def execute_cascade_frames(self, x, sections: Sequence, hop: int, out=None, keep: bool = False, kept=None, stream=None):
+        """rf_var2_plan_execute_cascade_frames: execute_cascade with every section's five coefficients as frames every `hop`
+        samples, bit for bit what execute_cascade gives on expand_frames of each.  keep=True: returns (out, kept), kept[k]
+        section k's result in K - 1 tensors laid out like x (kept=None allocates them); out has the same bits either way.
+        out=None allocates the output; out may NOT be x.  One section is execute_biquad_frames' launches and bits."""
+        *p, out, kept, s = self._cascade_frames_arguments(x, sections, hop, out, keep or kept is not None, kept, stream)
+        capi.check(capi.lib().rf_var2_plan_execute_cascade_frames(self._h, *p, s))
+        return (out, kept) if keep or kept is not None else out
+
+    def execute_cascade_frames_timed(self, x, sections: Sequence, hop: int, out=None, keep: bool = False, kept=None, stream=None):
+        """rf_var2_plan_execute_cascade_frames_timed: (out, [(kernel name, ms), ...]) or (out, kept, [...]); synchronises the stream."""
+        *p, out, kept, s = self._cascade_frames_arguments(x, sections, hop, out, keep or kept is not None, kept, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_execute_cascade_frames_timed(self._h, *p, s, *report)      # noqa: E731
+        times = _timed(call, self.cascade_frames_num_kernels(len(sections)))
+        return (out, kept, times) if keep or kept is not None else (out, times)
+
+    def _backward_cascade_frames_arguments(self, x, sections, hop, kept, out, grad_out, grad_in, grads, stream):
+        K = len(sections)
+        if grads is not None and len(grads) != K:
+            raise ValueError("grads: one tuple of five frame gradients per section, or None")
+        if self._host_only:
+            (px, po, pgo, pgi), array, pk, garray, count, stride = self._host_sections_frames(K, hop, 4, grads is not None)
+            return px, array, K, int(hop), count, stride, pk, po, pgo, pgi, garray, None, grads, ctypes.c_void_p()
+        if grad_in is None:
+            grad_in = self._like(grad_out)
+        array, K, count, stride = self._sections_frames(sections, hop, "sections")
+        garray, _, _, _ = self._sections_frames(grads, hop, "grads", like=stride)
+        return (self._pointer(x, "x"), array, K, int(hop), count, stride, self._kept_array(kept, max(K - 1, 0)), self._pointer(out, "out"),
+                self._pointer(grad_out, "grad_out"), self._pointer(grad_in, "grad_in"), garray, grad_in, grads, self._stream(stream))
+
+    def backward_cascade_frames(self, x, sections: Sequence, hop: int, kept, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_cascade_frames, the adjoint of execute_cascade_frames on what it kept: nothing is rerun.  grads:
+        None (no frame gradients: x, kept and out may then be None) or K tuples of five tensors laid out like the frames to be
+        WRITTEN: dL/d(frame), contracted in f64 and rounded once.  grad_in=None allocates it; it may be grad_out itself.  Returns
+        (grad_in, grads).  Asynchronous; the plan owns lam, the gradient between sections and the slab (backward_cascade_frames_bytes)."""
+        *p, grad_in, grads, s = self._backward_cascade_frames_arguments(x, sections, hop, kept, out, grad_out, grad_in, grads, stream)
+        capi.check(capi.lib().rf_var2_plan_backward_cascade_frames(self._h, *p, s))
+        return grad_in, grads
+
+    def backward_cascade_frames_timed(self, x, sections: Sequence, hop: int, kept, out, grad_out, grad_in=None, grads=None, stream=None):
+        """rf_var2_plan_backward_cascade_frames_timed: (grad_in, grads, [(kernel name, ms), ...]); synchronises the stream."""
+        *p, grad_in, grads, s = self._backward_cascade_frames_arguments(x, sections, hop, kept, out, grad_out, grad_in, grads, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_backward_cascade_frames_timed(self._h, *p, s, *report)      # noqa: E731
+        return grad_in, grads, _timed(call, self.backward_cascade_frames_num_kernels(len(sections), grads is not None))
+
+    def apply_cascade_frames(self, x, sections: Sequence, hop: int):
+        """execute_cascade_frames as a differentiable torch operation: the values are bit for bit execute_cascade_frames'.  Backward
+        is backward_cascade_frames.  Where any frame tensor requires a gradient the forward keeps, and x, the frames, the result
+        and the K - 1 kept signals are saved; where only x does, the plain forward runs and the frames alone are saved."""
+        return _cascade_frames_function().apply(self, int(hop), x, *(t for s in sections for t in s))
+
 
 _var2_function = None
 _var2_biquad_function = None
@@ -580,6 +683,52 @@ def _cascade_function():
 
 
 _var2_biquad_frames_function = None
+_var2_cascade_frames_function = None
+
+
+def _cascade_frames_function():
+    """the torch.autograd.Function behind Var2Plan.apply_cascade_frames: (plan, hop, x, then the 5 K frame tensors)"""
+    global _var2_cascade_frames_function
+    if _var2_cascade_frames_function is not None:
+        return _var2_cascade_frames_function
+    import torch
+
+    class Var2CascadeFramesFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, hop, x, *frames):
+            ctx.plan, ctx.hop = plan, hop
+            sections = [frames[i:i + 5] for i in range(0, len(frames), 5)]
+            ctx.with_frames = any(ctx.needs_input_grad[3:])
+            with torch.cuda.device(x.device):
+                if ctx.with_frames:
+                    out, kept = plan.execute_cascade_frames(x, sections, hop, keep=True)
+                    ctx.save_for_backward(x, *frames, out, *kept)
+                else:      # the backward reads nothing of the forward
+                    out = plan.execute_cascade_frames(x, sections, hop)
+                    ctx.save_for_backward(*frames)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out):
+            plan = ctx.plan
+            need_x, *need = ctx.needs_input_grad[2:]
+            count = len(need)
+            if ctx.with_frames:
+                x, *rest = ctx.saved_tensors
+                frames, out, kept = rest[:count], rest[count], rest[count + 1:]
+            else:
+                x, frames, out, kept = None, ctx.saved_tensors, None, None
+            sections = [frames[i:i + 5] for i in range(0, count, 5)]
+            g = _plan_layout(plan, grad_out)
+            grads = [tuple(torch.empty_like(t) for t in s) for s in sections] if ctx.with_frames else None
+            with torch.cuda.device(g.device):
+                gin, grads = plan.backward_cascade_frames(x, sections, ctx.hop, kept, out, g, None, grads)
+            given = [t for s in grads for t in s] if grads is not None else [None] * count
+            return (None, None, gin if need_x else None) + tuple(t if wanted else None for t, wanted in zip(given, need))
+
+    _var2_cascade_frames_function = Var2CascadeFramesFunction
+    return _var2_cascade_frames_function
 
 
 def _biquad_frames_function():
@@ -849,4 +998,37 @@ def biquad_scan_frames(x, b0, b1, b2, a1, a2, hop: int, causal: bool = True):
     if pad:
         x = torch.nn.functional.pad(x, (0, pad))
     out = plan.apply_biquad_frames(_plan_layout(plan, x), tuple(t.to(torch.float32).contiguous() for t in frames), hop)
+    return out[..., :n] if pad else out
+
+
+def biquad_cascade_frames(x, sections: Sequence, hop: int, causal: bool = True):
+    """biquad_cascade with every section's five coefficients at a control rate: K sections, 1 <= K <= 16, one behind the other
+    in one direction, in 2 K + 1 launches that read no coefficient signal.  x is (N,) or (L, N); `sections` is K tuples
+    (b0, b1, b2, a1, a2) of frame tensors (F,) or (L, F), F = frames_count(N, hop), frame j at sample j * hop, linear
+    interpolation between two frames by absolute position for either direction; one hop, a power of two in 64..65536, serves
+    all sections.  Differentiable in x and all 5 K frame tensors.  Where a frame tensor requires a gradient the forward keeps
+    every section's result (x, the frames, the result and K - 1 signals are saved) and the backward reruns nothing; where only
+    x does, the frames alone are saved.  The values are biquad_cascade's on expand_frames of every coefficient, bit for bit.
+    It shares biquad_scan's plan cache and pads as biquad_scan_frames does: a length that is no multiple of 4 gets zeros in x
+    behind the END for either direction."""
+    import torch
+    sections = [tuple(s) for s in sections]
+    if not 1 <= len(sections) <= capi.RF_VAR2_MAX_SECTIONS or any(len(s) != 5 for s in sections):
+        raise ValueError(f"sections: 1..{capi.RF_VAR2_MAX_SECTIONS} tuples (b0, b1, b2, a1, a2) of frame tensors")
+    n = int(x.shape[-1])
+    count = frames_count(n, hop)
+    shape = tuple(x.shape[:-1]) + (count,)
+    if x.dim() not in (1, 2) or any(tuple(t.shape) != shape for s in sections for t in s):
+        raise ValueError(f"x is (N,) or (L, N) and every frame tensor {shape} at hop {hop}, got {tuple(x.shape)} and "
+                         f"{sorted({tuple(t.shape) for s in sections for t in s})}")
+    lines = 1 if x.dim() == 1 else int(x.shape[0])
+    pad = -n % 4
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (n + pad, lines, bool(causal), device)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = Var2Plan(n + pad, lines=lines, causal=causal, device=device)
+    if pad:
+        x = torch.nn.functional.pad(x, (0, pad))
+    out = plan.apply_cascade_frames(_plan_layout(plan, x), [tuple(t.to(torch.float32).contiguous() for t in s) for s in sections], hop)
     return out[..., :n] if pad else out
