@@ -1315,4 +1315,54 @@ public:
         return rf_var2_plan_backward_cascade_frames_num_kernels(plan, sections, with_frames ? 1 : 0);
     }
     size_t cascade_frames_gradient_bytes(int sections, int hop) { prepare(); return rf_var2_plan_backward_cascade_frames_bytes(plan, sections, hop); }
+    /** realize_cascade_frames() on one CHUNK of a longer signal (rf_var2_plan_execute_cascade_frames_stream): state_in enters
+     *  (null: silence), state_out receives the state that leaves (null: not wanted) -- K + 1 pairs of f32 per line, pair 0 the
+     *  two last samples of the input, pair k + 1 those of section k's result, the nearest first, state_stride floats from line to
+     *  line (0: dense, 2 (K + 1)).  frames: the chunk's own -- for a chunk that starts at a multiple of hop, the whole signal's
+     *  frame arrays advanced by start / hop.  A filter over -x takes its chunks last to first.  2 K + 1 launches; both state
+     *  pointers null: realize_cascade_frames() itself. */
+    void realize_cascade_frames_stream(const void *in, const std::vector<rf_var2_section> &frames, int hop, void *out, const void *state_in,
+                                       void *state_out, const std::vector<void *> &kept = {}, int64_t frame_stride = 0, int64_t state_stride = 0,
+                                       void *stream = nullptr) {
+        prepare();
+        if (!kept.empty() && kept.size() + 1 != frames.size())
+            throw RecFilterError("realize_cascade_frames_stream: kept is empty or holds one signal per section but the last");
+        const int count = frames_count(hop);
+        if (rf_var2_plan_execute_cascade_frames_stream(plan, in, frames.data(), (int)frames.size(), hop, count, frame_stride > 0 ? frame_stride : count,
+                                                       out, kept.empty() ? nullptr : kept.data(), state_in, state_out,
+                                                       state_stride > 0 ? state_stride : 2 * ((int64_t)frames.size() + 1), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** The adjoint of realize_cascade_frames_stream() on what it kept (rf_var2_plan_backward_cascade_frames_stream):
+     *  gradient_cascade_frames()'s arguments, then state_in (what entered the forward; read for the frame gradients alone),
+     *  grad_state_out (the gradient of the state that left, e.g. the next chunk's grad_state_in; null: zeros) and grad_state_in
+     *  (written; null: not wanted), laid out like the state.  All three null: gradient_cascade_frames() itself. */
+    void gradient_cascade_frames_stream(const void *in, const std::vector<rf_var2_section> &frames, int hop, const std::vector<const void *> &kept,
+                                        const void *out, const void *grad_out, void *grad_in, const void *state_in, const void *grad_state_out,
+                                        void *grad_state_in, const std::vector<rf_var2_section_grad> &frame_grads = {}, int64_t frame_stride = 0,
+                                        int64_t state_stride = 0, void *stream = nullptr) {
+        prepare();
+        if (!frame_grads.empty() && frame_grads.size() != frames.size())
+            throw RecFilterError("gradient_cascade_frames_stream: frame_grads is empty or holds one rf_var2_section_grad per section");
+        if (!kept.empty() && kept.size() + 1 != frames.size())
+            throw RecFilterError("gradient_cascade_frames_stream: kept is empty or holds one signal per section but the last");
+        const int count = frames_count(hop);
+        if (rf_var2_plan_backward_cascade_frames_stream(plan, in, frames.data(), (int)frames.size(), hop, count, frame_stride > 0 ? frame_stride : count,
+                                                        kept.empty() ? nullptr : kept.data(), out, grad_out, grad_in,
+                                                        frame_grads.empty() ? nullptr : frame_grads.data(), state_in, grad_state_out, grad_state_in,
+                                                        state_stride > 0 ? state_stride : 2 * ((int64_t)frames.size() + 1), stream) != RF_OK)
+            throw RecFilterError(rf_last_error_string());
+    }
+    /** 2 K + 2 without frame gradients, 3 K + 2 with them, K = 1 included */
+    int cascade_frames_stream_gradient_num_kernels(int sections, bool with_frames) {
+        prepare();
+        return rf_var2_plan_backward_cascade_frames_stream_num_kernels(plan, sections, with_frames ? 1 : 0);
+    }
+    /** 2 K + 1, K = 1 included */
+    int cascade_frames_stream_num_kernels(int sections) { prepare(); return rf_var2_plan_cascade_frames_stream_num_kernels(plan, sections); }
+    /** the bytes of one state buffer; state_stride 0: dense */
+    size_t cascade_frames_stream_state_bytes(int sections, int64_t state_stride = 0) {
+        prepare();
+        return rf_var2_plan_cascade_frames_stream_state_bytes(plan, sections, state_stride > 0 ? state_stride : 2 * ((int64_t)sections + 1));
+    }
 };

@@ -1250,6 +1250,84 @@ int    rf_var2_plan_cascade_frames_num_kernels(const rf_var2_plan *plan, int n_s
 int    rf_var2_plan_backward_cascade_frames_num_kernels(const rf_var2_plan *plan, int n_sections, int with_frame_gradients);
 size_t rf_var2_plan_backward_cascade_frames_bytes(const rf_var2_plan *plan, int n_sections, int hop);
 
+/* The cascade on frames with a state that enters and leaves the call (rf_var2_plan_execute_cascade_frames_stream): a signal
+ * filtered in chunks -- as audio arrives, or because it does not fit -- gives what one call on the whole signal gives up to
+ * rounding, where every rf_var2_plan_execute_* call above starts from silence.  The arguments are
+ * rf_var2_plan_execute_cascade_frames' and three more.  A line's state is n_sections + 1 PAIRS of f32, [line][K + 1][2],
+ * state_stride >= 2 (K + 1) floats from line to line (4-byte aligned): pair 0 the history of the input, pair k + 1 the history
+ * of section k's result, each pair (the sample one place before the line, the sample two places before it) in the direction of
+ * the plan's recurrence -- (x[-1], x[-2]) for a causal plan; (x[n], x[n+1]) for an anticausal one, whose chunks are fed last
+ * to first.  state_in null: zeros enter.  state_out null: not wanted.  Both null: the call IS
+ * rf_var2_plan_execute_cascade_frames -- its launches, names, bits and refusals.  A chunk's frames are those of its own
+ * samples: frame j of the call at sample j * hop of the chunk, so a chunk that starts at a multiple of hop of the whole signal
+ * takes a slice of the whole signal's frames, frames + start / hop, n_frames = rf_var2_frames_count(length, hop).
+ * Each section keeps its masks by position, and the entering state is folded into the two first samples of its v (src the
+ * section's input, (hx1, hx2) pair k, (hy1, hy2) pair k + 1, every coefficient the interpolated, unmasked one; an anticausal
+ * plan: the mirror image at samples n - 1 and n - 2), each line one rounding:
+ *     v[0] = fma(b2[0], hx2, fma(b1[0], hx1, b0[0] * src[0]))          v[1] = fma(b2[1], hx1, fma(b1[1], src[0], b0[1] * src[1]))
+ *     v[0] = fma(-a1[0], hy1, fma(-a2[0], hy2, v[0]))                  v[1] = fma(-a2[1], hy1, v[1])
+ * The masked recurrence from zero on this v is, bit for bit, the unmasked one from the true state: the tile maps,
+ * "var2_carry_1d" and the final stages run unchanged.  The six coefficient slots per section that no other call reads --
+ * b1[0], b2[0], b2[1], a1[0], a2[0], a2[1] at the line's first samples in the recurrence's order -- are LIVE here whenever
+ * state_in is given: they must be finite.  With state_in of zeros the result equals the call without a state (a zero's sign
+ * apart).  The leaving state is stored by the lane that holds it in registers -- pair 0 by the first launch from x, pair k + 1
+ * by the link that finishes section k, pair K by the last launch -- and is bit for bit the two last samples, in the
+ * recurrence's order, of in, of every kept signal and of out: no further launch, no atomics, two calls give the same bits.
+ * Launches, 2 K + 1 whatever K (rf_var2_plan_cascade_frames_stream_num_kernels): "var2_biquad_frames_tails_stream_1d"; per
+ * boundary "var2_carry_1d" and "var2_frames_link_stream_1d" ("var2_frames_link_keep_stream_1d" where kept is given); then
+ * "var2_carry_1d" and "var2_frames_pass2_stream_1d".  K = 1 runs the same instances (3 launches); kept is not read.  out and
+ * kept have the same bits with and without keeping.  The plan keeps no state between calls: the state is the caller's,
+ * rf_var2_plan_cascade_frames_stream_state_bytes(plan, K, state_stride) = 4 ((n_lines - 1) state_stride + 2 (K + 1)) bytes per
+ * buffer, 0 for a refused K or stride.
+ * Refusals: rf_var2_plan_execute_cascade_frames' in its order up to the overlaps of out and the kept signals; then
+ * state_stride < 2 (K + 1); a state pointer that is not 4-byte aligned; state_out overlapping state_in, in, out, a kept signal
+ * or a frame array; state_in overlapping out or a kept signal (they are stored while it is read); last, a host-only plan.
+ * rf_var2_plan_backward_cascade_frames_stream is the adjoint of such a call on what it kept: the arguments of
+ * rf_var2_plan_backward_cascade_frames, then state_in (what entered the forward; read for the frame gradients alone),
+ * grad_state_out (the gradient of the state that left; null: zeros) and grad_state_in (the gradient of the state that entered;
+ * null: not wanted), all laid out like the state.  The leaving state is made of samples of in, of the kept signals and of out,
+ * so pair k of grad_state_out is ADDED, in f32, to the two last samples (in the recurrence's order) of the gradient that
+ * signal receives: pair K to grad_out as the first two launches read it (grad_out is not written), pair k to g_{k-1} in the
+ * registers of the adjoint link that forms it, pair 0 to grad_in.  The adjoint scans stay masked and start from zero.
+ * grad_state_in comes from lam_k at the forward's two first samples, the coefficients interpolated and unmasked: pair k + 1
+ * receives section k's feedback part (fma(-a1[0], lam[0], -(a2[1] * lam[1])), -(a2[0] * lam[0])) and pair k its feed-forward
+ * part (fma(b1[0], lam[0], b2[1] * lam[1]), b2[0] * lam[0]); pair k + 1 is the f32 sum (feed-forward part of section k + 1) +
+ * (feedback part of section k), formed by the launches that hold the two lam, by one lane, in stream order: no atomics.  With
+ * frame gradients the per-sample gradients at the six boundary slots take the history in place of the selected +0
+ * (grad_a1[0] = -lam[0] * hy1, ...) and enter the f64 contraction like any other sample; state_in null: zeros, the slots
+ * masked as in the call without a state.  Launches, 2 K + 2 without frame gradients and 3 K + 2 with them, K = 1 included
+ * (rf_var2_plan_backward_cascade_frames_stream_num_kernels): "var2_adj_frames_tails_stream_1d"; per boundary "var2_carry_1d",
+ * "var2_adj_frames_link_stream_1d" ("var2_adj_frames_link_keep_stream_1d" and "var2_frames_coef_stream_1d" with frame
+ * gradients); "var2_carry_1d", "var2_adj_frames_pass2_stream_1d", "var2_biquad_frames_grad_stream_1d"; with frame gradients
+ * "var2_frames_fold_cascade_1d".  The plan owns what rf_var2_plan_backward_cascade_frames_bytes says.  All three state pointers
+ * null: the call IS rf_var2_plan_backward_cascade_frames.  Refusals: that call's in its order; then state_stride < 2 (K + 1); a
+ * state pointer that is not 4-byte aligned; grad_state_in overlapping state_in, grad_state_out, a signal, a frame array or a
+ * frame gradient; grad_in or a frame gradient overlapping state_in or grad_state_out; last, a host-only plan.
+ * Out of scope: a state for the audio-rate calls (execute, execute_biquad, execute_cascade) and for rf_var_plan; hops that are
+ * no powers of two; chunk starts off the frame grid; graph capture; 16-bit signals; sharding. */
+int    rf_var2_plan_execute_cascade_frames_stream(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections,
+                                                  int hop, int n_frames, int64_t frame_stride, void *out, void *const *kept,
+                                                  const void *state_in, void *state_out, int64_t state_stride, void *stream);
+int    rf_var2_plan_execute_cascade_frames_stream_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames,
+                                                        int n_sections, int hop, int n_frames, int64_t frame_stride, void *out,
+                                                        void *const *kept, const void *state_in, void *state_out,
+                                                        int64_t state_stride, void *stream, float *ms_out, const char **names_out,
+                                                        int capacity);
+int    rf_var2_plan_cascade_frames_stream_num_kernels(const rf_var2_plan *plan, int n_sections);      /* 0: n_sections out of range */
+size_t rf_var2_plan_cascade_frames_stream_state_bytes(const rf_var2_plan *plan, int n_sections, int64_t state_stride);
+int    rf_var2_plan_backward_cascade_frames_stream(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections,
+                                                   int hop, int n_frames, int64_t frame_stride, const void *const *kept, const void *out,
+                                                   const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
+                                                   const void *state_in, const void *grad_state_out, void *grad_state_in,
+                                                   int64_t state_stride, void *stream);
+int    rf_var2_plan_backward_cascade_frames_stream_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames,
+                                                         int n_sections, int hop, int n_frames, int64_t frame_stride,
+                                                         const void *const *kept, const void *out, const void *grad_out, void *grad_in,
+                                                         const rf_var2_section_grad *frame_grads, const void *state_in,
+                                                         const void *grad_state_out, void *grad_state_in, int64_t state_stride,
+                                                         void *stream, float *ms_out, const char **names_out, int capacity);
+int    rf_var2_plan_backward_cascade_frames_stream_num_kernels(const rf_var2_plan *plan, int n_sections, int with_frame_gradients);
+
 /* ---- misc ------------------------------------------------------------------------------- */
 const char *rf_last_error_string(void);
 const char *rf_version(void);

@@ -14,7 +14,8 @@ from .plan import (Plan, box_difference, tap_filter, stream_copy_ms, gaussian_bo
 from .varscan import (SmoothPlan, VarPlan, domain_transform_bases, domain_transform_distances, domain_transform_distances_backward,
                       domain_transform_distances_volume, domain_transform_distances_volume_backward, domain_transform_weights, edge_aware_smooth, edge_aware_smooth_volume, smooth_samples,
                       var_scan, var_scan_signal, var_scan_volume)
-from .var2 import Var2Plan, allpole_scan, biquad_cascade, biquad_cascade_frames, biquad_scan, biquad_scan_frames, expand_frames, frames_count
+from .var2 import (BiquadCascadeStream, Var2Plan, allpole_scan, biquad_cascade, biquad_cascade_frames, biquad_cascade_frames_stream, biquad_scan,
+                   biquad_scan_frames, expand_frames, frames_count)
 
 __all__ = [
     "capi", "RecFilterError", "build_library", "Pointwise", "RecFilter", "RecFilterDim", "RecFilterDimAndCausality",
@@ -23,5 +24,5 @@ __all__ = [
     "domain_transform_bases", "domain_transform_distances", "SmoothPlan", "var_scan", "var_scan_signal", "smooth_samples",
     "domain_transform_distances_backward", "recursive_filter", "var_scan_volume", "domain_transform_distances_volume",
     "edge_aware_smooth_volume", "domain_transform_distances_volume_backward",
-    "Var2Plan", "allpole_scan", "biquad_scan", "biquad_cascade", "biquad_cascade_frames", "biquad_scan_frames", "expand_frames", "frames_count",
+    "Var2Plan", "allpole_scan", "biquad_scan", "biquad_cascade", "biquad_cascade_frames", "biquad_cascade_frames_stream", "BiquadCascadeStream", "biquad_scan_frames", "expand_frames", "frames_count",
 ]

@@ -99,6 +99,10 @@ EXPORTED_SYMBOLS = [
     "rf_var2_plan_execute_cascade_frames", "rf_var2_plan_execute_cascade_frames_timed", "rf_var2_plan_backward_cascade_frames",
     "rf_var2_plan_backward_cascade_frames_timed", "rf_var2_plan_cascade_frames_num_kernels",
     "rf_var2_plan_backward_cascade_frames_num_kernels", "rf_var2_plan_backward_cascade_frames_bytes",
+    "rf_var2_plan_execute_cascade_frames_stream", "rf_var2_plan_execute_cascade_frames_stream_timed",
+    "rf_var2_plan_cascade_frames_stream_num_kernels", "rf_var2_plan_cascade_frames_stream_state_bytes",
+    "rf_var2_plan_backward_cascade_frames_stream", "rf_var2_plan_backward_cascade_frames_stream_timed",
+    "rf_var2_plan_backward_cascade_frames_stream_num_kernels",
 ]
 
 
@@ -363,6 +367,16 @@ def lib() -> ctypes.CDLL:
     L.rf_var2_plan_backward_cascade_frames_num_kernels.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.rf_var2_plan_backward_cascade_frames_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.rf_var2_plan_backward_cascade_frames_bytes.restype = ctypes.c_size_t
+    state = [vp, vp, ctypes.c_int64]      # state_in, state_out, state_stride
+    L.rf_var2_plan_execute_cascade_frames_stream.argtypes = cascade_frames + [vp, kp] + state + [vp]
+    L.rf_var2_plan_execute_cascade_frames_stream_timed.argtypes = cascade_frames + [vp, kp] + state + [vp] + report
+    L.rf_var2_plan_cascade_frames_stream_num_kernels.argtypes = [vp, ctypes.c_int]
+    L.rf_var2_plan_cascade_frames_stream_state_bytes.argtypes = [vp, ctypes.c_int, ctypes.c_int64]
+    L.rf_var2_plan_cascade_frames_stream_state_bytes.restype = ctypes.c_size_t
+    grad_state = [vp, vp, vp, ctypes.c_int64]      # state_in, grad_state_out, grad_state_in, state_stride
+    L.rf_var2_plan_backward_cascade_frames_stream.argtypes = cascade_frames + [kp, vp, vp, vp, sp] + grad_state + [vp]
+    L.rf_var2_plan_backward_cascade_frames_stream_timed.argtypes = cascade_frames + [kp, vp, vp, vp, sp] + grad_state + [vp] + report
+    L.rf_var2_plan_backward_cascade_frames_stream_num_kernels.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.rf_last_error_string.restype = ctypes.c_char_p
     L.rf_version.restype = ctypes.c_char_p
     _lib = L

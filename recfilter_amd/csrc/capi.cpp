@@ -945,6 +945,63 @@ int rf_var2_plan_execute_cascade_frames_timed(rf_var2_plan *plan, const void *in
     });
 }
 
+// ---- the cascade on frames with a state that enters and leaves the call -----------------------------------------------------------------
+int rf_var2_plan_cascade_frames_stream_num_kernels(const rf_var2_plan *plan, int n_sections) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_frames_stream_launches(n_sections) : 0;
+}
+size_t rf_var2_plan_cascade_frames_stream_state_bytes(const rf_var2_plan *plan, int n_sections, int64_t state_stride) {
+    if (!plan || n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS || state_stride < 2 * ((int64_t)n_sections + 1)) return 0;
+    return (size_t)((int64_t)(plan->n_lines - 1) * state_stride + 2 * ((int64_t)n_sections + 1)) * sizeof(float);
+}
+
+int rf_var2_plan_execute_cascade_frames_stream(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                               int n_frames, int64_t frame_stride, void *out, void *const *kept, const void *state_in,
+                                               void *state_out, int64_t state_stride, void *stream) {
+    return fenced("rf_var2_plan_execute_cascade_frames_stream", [&] {
+        const Var2State state{state_in, state_out, state_stride};
+        return run_var2_cascade_frames(plan, in, frames, n_sections, hop, n_frames, frame_stride, out, kept, (hipStream_t)stream, nullptr, nullptr, 0,
+                                       false, &state);
+    });
+}
+
+int rf_var2_plan_execute_cascade_frames_stream_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                                     int n_frames, int64_t frame_stride, void *out, void *const *kept, const void *state_in,
+                                                     void *state_out, int64_t state_stride, void *stream, float *ms_out, const char **names_out,
+                                                     int capacity) {
+    return fenced("rf_var2_plan_execute_cascade_frames_stream_timed", [&] {
+        const Var2State state{state_in, state_out, state_stride};
+        return run_var2_cascade_frames(plan, in, frames, n_sections, hop, n_frames, frame_stride, out, kept, (hipStream_t)stream, ms_out, names_out,
+                                       capacity, true, &state);
+    });
+}
+
+int rf_var2_plan_backward_cascade_frames_stream_num_kernels(const rf_var2_plan *plan, int n_sections, int with_frame_gradients) {
+    return plan && n_sections >= 1 && n_sections <= RF_VAR2_MAX_SECTIONS ? var2_cascade_frames_stream_backward_launches(n_sections, with_frame_gradients != 0) : 0;
+}
+
+int rf_var2_plan_backward_cascade_frames_stream(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                                int n_frames, int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out,
+                                                void *grad_in, const rf_var2_section_grad *frame_grads, const void *state_in,
+                                                const void *grad_state_out, void *grad_state_in, int64_t state_stride, void *stream) {
+    return fenced("rf_var2_plan_backward_cascade_frames_stream", [&] {
+        const Var2GradState state{state_in, grad_state_out, grad_state_in, state_stride};
+        return run_var2_cascade_frames_backward(plan, in, frames, n_sections, hop, n_frames, frame_stride, kept, out, grad_out, grad_in, frame_grads,
+                                                (hipStream_t)stream, nullptr, nullptr, 0, false, &state);
+    });
+}
+
+int rf_var2_plan_backward_cascade_frames_stream_timed(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop,
+                                                      int n_frames, int64_t frame_stride, const void *const *kept, const void *out,
+                                                      const void *grad_out, void *grad_in, const rf_var2_section_grad *frame_grads,
+                                                      const void *state_in, const void *grad_state_out, void *grad_state_in, int64_t state_stride,
+                                                      void *stream, float *ms_out, const char **names_out, int capacity) {
+    return fenced("rf_var2_plan_backward_cascade_frames_stream_timed", [&] {
+        const Var2GradState state{state_in, grad_state_out, grad_state_in, state_stride};
+        return run_var2_cascade_frames_backward(plan, in, frames, n_sections, hop, n_frames, frame_stride, kept, out, grad_out, grad_in, frame_grads,
+                                                (hipStream_t)stream, ms_out, names_out, capacity, true, &state);
+    });
+}
+
 int rf_var2_plan_backward_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
                                          int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out, void *grad_in,
                                          const rf_var2_section_grad *frame_grads, void *stream) {

@@ -128,6 +128,22 @@ struct Var2FramesArgs {
     int32_t hop_shift, n_frames;
     float inv_hop;
     int64_t stride, frame_stride;
+    // a call with a state (rf_var2_plan_execute_cascade_frames_stream), forward stages alone: [line][K + 1][2] f32, state_stride
+    // floats from line to line; either pointer null: no state enters / none is wanted; both null: the instances without a state.
+    // The FF stage (pair 0) folds pairs 0 and 1 of state_in into v and stores pair 0 of state_out from x; the final stage stores
+    // pair `pair` = K from the result.  The names then end in "_stream_1d".
+    const float *state_in;
+    float *state_out;
+    int64_t state_stride;
+    int32_t pair;
+    // the backward of such a call (stream != 0: the adjoint STREAM instances): grad_state_out and grad_state_in are laid out like
+    // the state.  Pair add_pair of grad_state_out is added to x at the forward's two last samples where x is grad_out (-1: x
+    // holds it already); the final stage, which holds lam of section `pair`, adds the feedback part of pair `pair` + 1 of
+    // grad_state_in (stores it where pair == last_section) and stores the feed-forward part of pair `pair`.
+    const float *grad_state_out;
+    float *grad_state_in;
+    int32_t add_pair, last_section;
+    int32_t stream;
 };
 
 constexpr int kVar2FrameSums = 10;           // per piece of an interval: S0 and S1 of b0, b1, b2, a1, a2
@@ -151,6 +167,13 @@ struct Var2FramesGradArgs {
     int32_t pieces;                 // per line
     float inv_hop;
     int64_t stride, frame_stride;
+    // stream != 0 (the backward of a call with a state): pairs `pair` and `pair` + 1 of state_in are the section's history, read
+    // where the forward read it; pair 0 of grad_state_out is added to the two last samples of grad_in.  Either may be null.
+    const float *state_in;
+    const float *grad_state_out;
+    int64_t state_stride;
+    int32_t pair;
+    int32_t stream;
 };
 inline int64_t var2_frames_pieces(int64_t n, int hop) { const int64_t piece = hop < kVar2GradBlock ? hop : kVar2GradBlock; return (n + piece - 1) / piece; }
 
@@ -165,7 +188,8 @@ struct Var2ExpandArgs {
     int64_t stride, frame_stride;
 };
 int launch_var2_expand_frames(const Var2ExpandArgs &a, hipStream_t stream);      // "var2_expand_frames_1d"
-// "var2_biquad_frames_tails_1d" (a.adjoint == 0), "var2_adj_frames_tails_1d"
+// "var2_biquad_frames_tails_1d" (a.adjoint == 0), "var2_adj_frames_tails_1d"; with a state "var2_biquad_frames_tails_stream_1d" and
+// "var2_frames_pass2_stream_1d"
 int launch_var2_frames_tails(const Var2FramesArgs &a, hipStream_t stream);
 int launch_var2_frames_pass2(const Var2FramesArgs &a, hipStream_t stream);       // "var2_frames_pass2_1d", "var2_adj_frames_pass2_1d"
 int launch_var2_frames_grad(const Var2FramesGradArgs &a, hipStream_t stream);    // "var2_biquad_frames_grad_1d"
@@ -189,6 +213,12 @@ struct Var2FramesLinkArgs {
     int32_t hop_shift, n_frames;
     float inv_hop;
     int64_t stride, frame_stride;
+    // as in Var2FramesArgs; pair = k + 1 for the link that finishes section k: that pair of state_out from y_k, that pair and the
+    // next of state_in folded into v_{k+1}
+    const float *state_in;
+    float *state_out;
+    int64_t state_stride;
+    int32_t pair;
 };
 struct Var2AdjFramesLinkArgs {
     const float *x;
@@ -206,6 +236,13 @@ struct Var2AdjFramesLinkArgs {
     int32_t hop_shift, n_frames;
     float inv_hop;
     int64_t stride, frame_stride;
+    // as the adjoint fields of Var2FramesArgs; pair = k, and pair k of grad_state_out is added to g_{k-1} at the forward's two
+    // last samples before it is stored
+    const float *grad_state_out;
+    float *grad_state_in;
+    int64_t state_stride;
+    int32_t pair, add_pair, last_section;
+    int32_t stream;
 };
 // The fold of all sections in one launch (var2_frames_fold_cascade_1d): section k's sums lie k * section_doubles behind slab, laid
 // out as Var2FramesGradArgs::slab; grads[k] = its five [line][frame] gradients (b0, b1, b2, a1, a2).  The sections ride on gridDim.z.
@@ -220,7 +257,8 @@ struct Var2FramesFoldCascadeArgs {
     int32_t pieces;                 // per line
     int64_t frame_stride;
 };
-int launch_var2_frames_link(const Var2FramesLinkArgs &a, hipStream_t stream);          // "var2_frames_link_1d", "var2_frames_link_keep_1d" (a.keep != null)
+// "var2_frames_link_1d", "var2_frames_link_keep_1d" (a.keep != null); with a state "var2_frames_link_stream_1d", "var2_frames_link_keep_stream_1d"
+int launch_var2_frames_link(const Var2FramesLinkArgs &a, hipStream_t stream);
 int launch_var2_adj_frames_link(const Var2AdjFramesLinkArgs &a, hipStream_t stream);   // "var2_adj_frames_link_1d", "var2_adj_frames_link_keep_1d"
 // the sums of the five frame gradients of a section without grad_in: a.b0, a.b1, a.b2, a.grad_in and a.with_frames are not looked at
 int launch_var2_frames_coef(const Var2FramesGradArgs &a, hipStream_t stream);          // "var2_frames_coef_1d"

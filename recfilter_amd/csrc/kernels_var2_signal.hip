@@ -75,6 +75,12 @@
 //   var2_frames_coef_1d            the sums of a section's five frame gradients from lam, x and y: var2_biquad_frames_grad_1d
 //                                  without grad_in, into the section's part of the slab
 //   var2_frames_fold_cascade_1d    var2_frames_fold_1d for all sections in one launch, the section on gridDim.z
+//
+// The cascade on frames with a state that enters and leaves the call (rf_var2_plan_execute_cascade_frames_stream): the STREAM
+// instances of the forward stages -- var2_biquad_frames_tails_stream_1d, var2_frames_link_stream_1d,
+// var2_frames_link_keep_stream_1d, var2_frames_pass2_stream_1d; var2_carry_1d serves unchanged.  The lane whose tile holds the
+// line's two first samples in the order of the recurrence folds the entering state into them (fold_entering_state); the lane
+// whose tile holds the two last stores the leaving pair from its registers (store_leaving_pair).  O(1) more work per line.
 #include "kernels_var2.h"
 
 #include "var_device.h"
@@ -804,13 +810,96 @@ __device__ __forceinline__ float frame_at(const float *frames, int at, int shift
     return frame_lerp(frame_pair(frames, at >> shift), at & ((1 << shift) - 1), inv_hop);
 }
 
+// ---- a state that enters and leaves a call (rf_var2_plan_execute_cascade_frames_stream) ---------------------------------------------
+// A line's state is K + 1 pairs (the sample one place before the line, the one two places before it) in the order of the
+// recurrence: pair 0 of the input, pair k + 1 of section k's result.  The entering state is folded into the two first samples of a
+// section's v, by the lane whose tile holds them (n is a multiple of 4: one tile holds both); the masked recurrence from zero on
+// that v is the unmasked one from the true state, so the tails, the carry and the final stage run as they are.
+//   v[0] = fma(b2[0], hx2, fma(b1[0], hx1, b0[0] * src[0]))          v[0] = fma(-a1[0], hy1, fma(-a2[0], hy2, v[0]))
+//   v[1] = fma(b2[1], hx1, fma(b1[1], src[0], b0[1] * src[1]))       v[1] = fma(-a2[1], hy1, v[1])
+// (REV: samples n - 1 and n - 2.)  pairs: (hx1, hx2, hy1, hy2), the section's input and result pairs, adjacent in the layout.
+template <bool REV>
+__device__ __forceinline__ void fold_entering_state(const float *pairs, const float (&src)[T], float (&v)[T], const FramePair &b0, const FramePair &b1,
+                                                    const FramePair &b2, const FramePair &a1, const FramePair &a2, int k0, float inv_hop, int n, int t0) {
+    const int i0 = REV ? n - 1 - t0 : 0, i1 = REV ? i0 - 1 : 1;      // the first and the second sample of the recurrence, in the tile
+    const float hx1 = pairs[0], hx2 = pairs[1], hy1 = pairs[2], hy2 = pairs[3];
+    float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        s0 = i == i0 ? src[i] : s0;
+        s1 = i == i1 ? src[i] : s1;
+    }
+    float v0 = frame_lerp(b0, k0 + i0, inv_hop) * s0;
+    v0 = __builtin_fmaf(frame_lerp(b1, k0 + i0, inv_hop), hx1, v0);
+    v0 = __builtin_fmaf(frame_lerp(b2, k0 + i0, inv_hop), hx2, v0);
+    float v1 = frame_lerp(b0, k0 + i1, inv_hop) * s1;
+    v1 = __builtin_fmaf(frame_lerp(b1, k0 + i1, inv_hop), s0, v1);
+    v1 = __builtin_fmaf(frame_lerp(b2, k0 + i1, inv_hop), hx1, v1);
+    v0 = step2(frame_lerp(a1, k0 + i0, inv_hop), frame_lerp(a2, k0 + i0, inv_hop), v0, hy1, hy2);
+    v1 = __builtin_fmaf(-frame_lerp(a2, k0 + i1, inv_hop), hy1, v1);
+#pragma unroll
+    for (int i = 0; i < T; i++) v[i] = i == i0 ? v0 : (i == i1 ? v1 : v[i]);
+}
+
+// the leaving pair of a signal from the tile that holds the line's two last samples in the order of the recurrence
+template <bool REV>
+__device__ __forceinline__ void store_leaving_pair(float *pair, const float (&y)[T], int n, int t0) {
+    const int i0 = REV ? 0 : n - 1 - t0, i1 = REV ? 1 : i0 - 1;
+    float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        s0 = i == i0 ? y[i] : s0;
+        s1 = i == i1 ? y[i] : s1;
+    }
+    pair[0] = s0;
+    pair[1] = s1;
+}
+
+// The backward of a call with a state.  The leaving state is made of samples of x, of the kept signals and of out, so its gradient
+// is ADDED to the two last samples (the adjoint recurrence's two first) of the gradient each of them receives; the adjoint scans
+// themselves stay masked and start from zero.  REV: the direction of the adjoint recurrence.
+template <bool REV>
+__device__ __forceinline__ void add_leaving_gradient(const float *pair, float (&g)[T], int n, int t0) {
+    const int i0 = REV ? n - 1 - t0 : 0, i1 = REV ? i0 - 1 : 1;
+    const float g0 = pair[0], g1 = pair[1];
+#pragma unroll
+    for (int i = 0; i < T; i++) g[i] = i == i0 ? g[i] + g0 : (i == i1 ? g[i] + g1 : g[i]);
+}
+
+// The gradient of the entering state from lam_j of the tile that holds the forward's two first samples (the adjoint's two last):
+//   feedback part, to pair j + 1     (fma(-a1[0], lam[0], -(a2[1] * lam[1])), -(a2[0] * lam[0]))     added to what section j + 1 left there
+//   feed-forward part, to pair j     (fma(b1[0], lam[0], b2[1] * lam[1]), b2[0] * lam[0])            stored
+// by one lane, in stream order: no atomic.  first: nothing was left in pair j + 1 (the last section).
+template <bool REV>
+__device__ __forceinline__ void store_entering_gradient(float *pairs, bool first, const float (&lam)[T], const FramePair &b1, const FramePair &b2,
+                                                        const FramePair &a1, const FramePair &a2, int k0, float inv_hop, int n, int t0) {
+    const int i0 = REV ? 0 : n - 1 - t0, i1 = REV ? 1 : i0 - 1;      // the forward's first and second sample, in the tile
+    float l0 = 0.0f, l1 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        l0 = i == i0 ? lam[i] : l0;
+        l1 = i == i1 ? lam[i] : l1;
+    }
+    const float fb0 = __builtin_fmaf(-frame_lerp(a1, k0 + i0, inv_hop), l0, -(frame_lerp(a2, k0 + i1, inv_hop) * l1));
+    const float fb1 = -(frame_lerp(a2, k0 + i0, inv_hop) * l0);
+    const float ff0 = __builtin_fmaf(frame_lerp(b1, k0 + i0, inv_hop), l0, frame_lerp(b2, k0 + i1, inv_hop) * l1);
+    const float ff1 = frame_lerp(b2, k0 + i0, inv_hop) * l0;
+    pairs[2] = first ? fb0 : pairs[2] + fb0;
+    pairs[3] = first ? fb1 : pairs[3] + fb1;
+    pairs[0] = ff0;
+    pairs[1] = ff1;
+}
+
 // var2_signal_kernel with the coefficient signals formed in registers: the same masks by position, the same order of the
 // feed-forward part, the same recurrences, scan and stores.  Nothing but x goes through the transposition, and a coefficient
 // lives for one step.  ADJ: the three coefficients its shifted reads reach beyond the tile come from frame_at at a position
 // clamped into the line -- the next interval's where the tile ends at a frame -- and are masked by position like the rest.
-template <bool REV, bool ADJ, bool FINAL, bool FF = false>
+// STREAM (var2_biquad_frames_tails_stream_1d, var2_frames_pass2_stream_1d): a.state_in folded into v by the FF stage, the
+// leaving pair a.pair of a.state_out from the tile in registers -- x by the FF stage, the result by the final one.
+template <bool REV, bool ADJ, bool FINAL, bool FF = false, bool STREAM = false>
 __global__ void __launch_bounds__(64) var2_frames_kernel(Var2FramesArgs a) {
     static_assert(!FF || (!ADJ && !FINAL), "the feed-forward part stands in front of a forward tails stage");
+    static_assert(!STREAM || ADJ || FF || FINAL, "the state enters in the FF stage and leaves there and in the final one");
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
     const int g = blockIdx.x, line = blockIdx.y;
@@ -863,6 +952,11 @@ __global__ void __launch_bounds__(64) var2_frames_kernel(Var2FramesArgs a) {
             v = __builtin_fmaf(no_one ? 0.0f : frame_lerp(g1, k0 + i, inv_hop), one, v);
             x[i] = __builtin_fmaf(no_two ? 0.0f : frame_lerp(g2, k0 + i, inv_hop), two, v);
         }
+        if constexpr (STREAM) {
+            const int64_t state0 = (int64_t)line * a.state_stride + 2 * a.pair;
+            if (a.state_in && t == (REV ? a.tiles - 1 : 0)) fold_entering_state<REV>(a.state_in + state0, u, x, f0, g1, g2, f1, f2, k0, inv_hop, n, t0);
+            if (a.state_out && t == (REV ? 0 : a.tiles - 1)) store_leaving_pair<REV>(a.state_out + state0, u, n, t0);
+        }
         store_group(lds, a.dst + first, n, s0, x);      // v: what var2_frames_pass2_1d reads, in place
 #pragma unroll
         for (int i = 0; i < T; i++) x[i] = t0 + i < n ? x[i] : 0.0f;
@@ -870,6 +964,10 @@ __global__ void __launch_bounds__(64) var2_frames_kernel(Var2FramesArgs a) {
         transpose_in(raw, lds, x);
 #pragma unroll
         for (int i = 0; i < T; i++) x[i] = t0 + i < n ? x[i] : 0.0f;
+        if constexpr (STREAM && ADJ) {      // x is grad_out: the gradient of the result's leaving pair
+            if (a.grad_state_out && a.add_pair >= 0 && t == (REV ? a.tiles - 1 : 0))
+                add_leaving_gradient<REV>(a.grad_state_out + (int64_t)line * a.state_stride + 2 * a.add_pair, x, n, t0);
+        }
     }
     // the coefficients of step i, masked by position: the tile's own, or (ADJ) those one and two samples further along the
     // forward's direction
@@ -901,6 +999,14 @@ __global__ void __launch_bounds__(64) var2_frames_kernel(Var2FramesArgs a) {
             coefficients(i, c1, c2);
             const float y = step2(c1, c2, x[i], y1, y2);
             x[i] = y; y2 = y1; y1 = y;
+        }
+        if constexpr (STREAM && !ADJ) {
+            if (a.state_out && t == (REV ? 0 : a.tiles - 1)) store_leaving_pair<REV>(a.state_out + (int64_t)line * a.state_stride + 2 * a.pair, x, n, t0);
+        }
+        if constexpr (STREAM && ADJ) {      // x is lam of section a.pair
+            if (a.grad_state_in && t == (REV ? 0 : a.tiles - 1))
+                store_entering_gradient<REV>(a.grad_state_in + (int64_t)line * a.state_stride + 2 * a.pair, a.pair == a.last_section, x,
+                                             frame_pair(a.b1 + frame0, j), frame_pair(a.b2 + frame0, j), f1, f2, k0, inv_hop, n, t0);
         }
         store_group(lds, a.dst + first, n, s0, x);
     } else {
@@ -976,7 +1082,9 @@ __device__ __forceinline__ void store_tails(float *tails, int n_lines, int tiles
 
 // var2_link_kernel with every coefficient formed as var2_frames_kernel forms it: x alone goes through the transposition, one
 // FramePair per coefficient, a value per step.  KEEP: y of the finished section is stored to a.keep (it may be a.x).
-template <bool REV, bool KEEP>
+// STREAM (var2_frames_link_stream_1d, var2_frames_link_keep_stream_1d): pair a.pair of the state is the finished section's -- its
+// leaving pair from y in registers, and with the pair behind it what enters the next section, folded into v.
+template <bool REV, bool KEEP, bool STREAM = false>
 __global__ void __launch_bounds__(64) var2_frames_link_kernel(Var2FramesLinkArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
@@ -1029,6 +1137,13 @@ __global__ void __launch_bounds__(64) var2_frames_link_kernel(Var2FramesLinkArgs
             w = __builtin_fmaf(own_frame<REV, 1>(g1, k0, i, inv_hop, n, t0), one, w);
             v[i] = __builtin_fmaf(own_frame<REV, 2>(g2, k0, i, inv_hop, n, t0), two, w);
         }
+        if constexpr (STREAM) {
+            const int64_t state0 = (int64_t)line * a.state_stride + 2 * a.pair;
+            if (a.state_in && t == (REV ? a.tiles - 1 : 0))
+                fold_entering_state<REV>(a.state_in + state0, y, v, f0, g1, g2, frame_pair(a.next_a1 + frame0, j), frame_pair(a.next_a2 + frame0, j), k0,
+                                         inv_hop, n, t0);
+            if (a.state_out && t == (REV ? 0 : a.tiles - 1)) store_leaving_pair<REV>(a.state_out + state0, y, n, t0);
+        }
     }
     store_group(lds, a.dst + first, n, s0, v);
     const FramePair h1 = frame_pair(a.next_a1 + frame0, j), h2 = frame_pair(a.next_a2 + frame0, j);
@@ -1048,7 +1163,10 @@ __global__ void __launch_bounds__(64) var2_frames_link_kernel(Var2FramesLinkArgs
 // var2_adj_link_kernel on frames.  REV: the direction of the adjoint recurrence.  The shifted reads -- a1, b1 one sample and a2,
 // b2 two samples along the forward's direction -- are frame_lerp inside the tile and frame_at at a clamped position beyond it
 // (the ADJ branch of var2_frames_kernel).  KEEP: lam of the finished section is stored to a.keep.
-template <bool REV, bool KEEP>
+// STREAM (var2_adj_frames_link_stream_1d, var2_adj_frames_link_keep_stream_1d): a.pair = k.  Where x is grad_out (a.add_pair >= 0) the
+// gradient of the result's leaving pair is added to it in registers; lam_k gives its parts of grad_state_in; the gradient of pair k
+// is added to g_{k-1} before it is stored and scanned.
+template <bool REV, bool KEEP, bool STREAM = false>
 __global__ void __launch_bounds__(64) var2_adj_frames_link_kernel(Var2AdjFramesLinkArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[T * LDS_PITCH];
     const int lane = threadIdx.x;
@@ -1080,6 +1198,10 @@ __global__ void __launch_bounds__(64) var2_adj_frames_link_kernel(Var2AdjFramesL
         transpose_in(raw, lds, lam);
 #pragma unroll
         for (int i = 0; i < T; i++) lam[i] = t0 + i < n ? lam[i] : 0.0f;
+        if constexpr (STREAM) {
+            if (a.grad_state_out && a.add_pair >= 0 && t == (REV ? a.tiles - 1 : 0))
+                add_leaving_gradient<REV>(a.grad_state_out + (int64_t)line * a.state_stride + 2 * a.add_pair, lam, n, t0);
+        }
 #pragma unroll
         for (int s = 0; s < T; s++) {
             const int i = REV ? T - 1 - s : s;
@@ -1108,6 +1230,13 @@ __global__ void __launch_bounds__(64) var2_adj_frames_link_kernel(Var2AdjFramesL
             float w = own_frame<REV, 0>(f0, k0, i, inv_hop, n, t0) * lam[i];
             w = __builtin_fmaf(shifted_frame<REV, 1>(g1, k0, i, inv_hop, b1_near, b1_near, n, t0), one, w);
             v[i] = __builtin_fmaf(shifted_frame<REV, 2>(g2, k0, i, inv_hop, b2_near, b2_far, n, t0), two, w);
+        }
+        if constexpr (STREAM) {
+            const int64_t state0 = (int64_t)line * a.state_stride + 2 * a.pair;
+            if (a.grad_state_in && t == (REV ? 0 : a.tiles - 1))
+                store_entering_gradient<REV>(a.grad_state_in + state0, a.pair == a.last_section, lam, g1, g2, frame_pair(a.a1 + frame0, j),
+                                             frame_pair(a.a2 + frame0, j), k0, inv_hop, n, t0);
+            if (a.grad_state_out && t == (REV ? a.tiles - 1 : 0)) add_leaving_gradient<REV>(a.grad_state_out + state0, v, n, t0);
         }
     }
     store_group(lds, a.dst + first, n, s0, v);
@@ -1148,7 +1277,10 @@ __global__ void __launch_bounds__(kGradLanes) var2_expand_frames_kernel(Var2Expa
 // min(hop, 1024) samples by a fixed tree -- shuffles within a wave, then the piece's first lane over its waves' sums in order.
 // COEF_ONLY (var2_frames_coef_1d): the FRAMES half alone, for a section whose input gradient var2_adj_frames_link_keep_1d has
 // formed -- the same products, the same sums in the same order, from lam, x and y; no tap is read and grad_in is not written.
-template <bool CAUSAL, bool FRAMES, bool COEF_ONLY = false>
+// STREAM: the section's history -- pairs a.pair (its input's) and a.pair + 1 (its result's) of a.state_in -- stands where the
+// forward read it, in place of the 0 beyond the line, and the six slots masked elsewhere are live; the gradient of the input's
+// leaving pair (pair 0 of a.grad_state_out) is added to the two last samples of grad_in.
+template <bool CAUSAL, bool FRAMES, bool COEF_ONLY = false, bool STREAM = false>
 __global__ void __launch_bounds__(kGradLanes) var2_frames_grad_kernel(Var2FramesGradArgs a) {
     static_assert(!COEF_ONLY || FRAMES, "the sums are what is left");
     static_assert(kGradLanes * 4 == kVar2GradBlock, "a workgroup's samples");
@@ -1181,18 +1313,34 @@ __global__ void __launch_bounds__(kGradLanes) var2_frames_grad_kernel(Var2Frames
                 const float c1 = (one < 0 || one >= n) ? 0.0f : t1, c2 = (two < 0 || two >= n) ? 0.0f : t2;
                 gx[k] = __builtin_fmaf(c2, lam[i2], __builtin_fmaf(c1, lam[i1], t0 * lam[L0 + k]));
             }
+            if constexpr (STREAM) {
+                if (a.grad_state_out && at == (CAUSAL ? n - 4 : 0)) {      // the forward's two last samples
+                    const float *pair = a.grad_state_out + (int64_t)blockIdx.y * a.state_stride;
+                    gx[CAUSAL ? 3 : 0] += pair[0];
+                    gx[CAUSAL ? 2 : 1] += pair[1];
+                }
+            }
             *reinterpret_cast<float4 *>(a.grad_in + first + at) = make_float4(gx[0], gx[1], gx[2], gx[3]);
         }
         if constexpr (FRAMES) {
             float xs[6], ys[6];
             load_six<!CAUSAL>(a.x + first, at, n, xs);
             load_six<!CAUSAL>(a.y + first, at, n, ys);
+            bool live = false;      // the history stands beyond the line: nothing is masked
+            if constexpr (STREAM) {
+                live = a.state_in != nullptr;
+                if (live && at == (CAUSAL ? 0 : n - 4)) {      // the forward's two first samples
+                    const float *pairs = a.state_in + (int64_t)blockIdx.y * a.state_stride + 2 * a.pair;
+                    xs[CAUSAL ? 1 : 4] = pairs[0]; xs[CAUSAL ? 0 : 5] = pairs[1];
+                    ys[CAUSAL ? 1 : 4] = pairs[2]; ys[CAUSAL ? 0 : 5] = pairs[3];
+                }
+            }
             const int k0 = at & ((1 << shift) - 1), hop = 1 << shift;
             const double scale = (double)inv_hop;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int i1 = CAUSAL ? X0 + k - 1 : X0 + k + 1, i2 = CAUSAL ? X0 + k - 2 : X0 + k + 2;
-                const bool no_one = CAUSAL ? at + k < 1 : at + k >= n - 1, no_two = CAUSAL ? at + k < 2 : at + k >= n - 2;
+                const bool no_one = !live && (CAUSAL ? at + k < 1 : at + k >= n - 1), no_two = !live && (CAUSAL ? at + k < 2 : at + k >= n - 2);
                 const float l = lam[L0 + k];
                 const float gc[5] = {l * xs[X0 + k], no_one ? 0.0f : l * xs[i1], no_two ? 0.0f : l * xs[i2],
                                      no_one ? 0.0f : -l * ys[i1], no_two ? 0.0f : -l * ys[i2]};
@@ -1372,10 +1520,26 @@ namespace {
 template <bool FINAL>
 int launch_frames_pass(const Var2FramesArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.adjoint && a.stream) {
+        if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, true, FINAL, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_kernel<true, true, FINAL, false, true>), grid, block, 0, stream, a);
+        return launched(FINAL ? "var2_adj_frames_pass2_stream_1d" : "var2_adj_frames_tails_stream_1d");
+    }
     if (a.adjoint) {
         if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, true, FINAL>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((var2_frames_kernel<true, true, FINAL>), grid, block, 0, stream, a);
         return launched(FINAL ? "var2_adj_frames_pass2_1d" : "var2_adj_frames_tails_1d");
+    }
+    if (a.state_in || a.state_out) {
+        if constexpr (FINAL) {
+            if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, false, true, false, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((var2_frames_kernel<true, false, true, false, true>), grid, block, 0, stream, a);
+            return launched("var2_frames_pass2_stream_1d");
+        } else {
+            if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, false, false, true, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((var2_frames_kernel<true, false, false, true, true>), grid, block, 0, stream, a);
+            return launched("var2_biquad_frames_tails_stream_1d");
+        }
     }
     if constexpr (FINAL) {
         if (a.causal) hipLaunchKernelGGL((var2_frames_kernel<false, false, true>), grid, block, 0, stream, a);
@@ -1394,6 +1558,16 @@ int launch_var2_frames_pass2(const Var2FramesArgs &a, hipStream_t stream) { retu
 
 int launch_var2_frames_grad(const Var2FramesGradArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.stream) {
+        if (a.causal) {
+            if (a.with_frames) hipLaunchKernelGGL((var2_frames_grad_kernel<true, true, false, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((var2_frames_grad_kernel<true, false, false, true>), grid, block, 0, stream, a);
+        } else {
+            if (a.with_frames) hipLaunchKernelGGL((var2_frames_grad_kernel<false, true, false, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((var2_frames_grad_kernel<false, false, false, true>), grid, block, 0, stream, a);
+        }
+        return launched("var2_biquad_frames_grad_stream_1d");
+    }
     if (a.causal) {
         if (a.with_frames) hipLaunchKernelGGL((var2_frames_grad_kernel<true, true>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((var2_frames_grad_kernel<true, false>), grid, block, 0, stream, a);
@@ -1412,6 +1586,16 @@ int launch_var2_frames_fold(const Var2FramesGradArgs &a, hipStream_t stream) {
 
 int launch_var2_frames_link(const Var2FramesLinkArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.state_in || a.state_out) {
+        if (a.keep) {
+            if (a.causal) hipLaunchKernelGGL((var2_frames_link_kernel<false, true, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((var2_frames_link_kernel<true, true, true>), grid, block, 0, stream, a);
+            return launched("var2_frames_link_keep_stream_1d");
+        }
+        if (a.causal) hipLaunchKernelGGL((var2_frames_link_kernel<false, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_link_kernel<true, false, true>), grid, block, 0, stream, a);
+        return launched("var2_frames_link_stream_1d");
+    }
     if (a.keep) {
         if (a.causal) hipLaunchKernelGGL((var2_frames_link_kernel<false, true>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((var2_frames_link_kernel<true, true>), grid, block, 0, stream, a);
@@ -1424,6 +1608,16 @@ int launch_var2_frames_link(const Var2FramesLinkArgs &a, hipStream_t stream) {
 
 int launch_var2_adj_frames_link(const Var2AdjFramesLinkArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)a.groups, (unsigned)a.n_lines), block(64);
+    if (a.stream) {
+        if (a.keep) {
+            if (a.causal) hipLaunchKernelGGL((var2_adj_frames_link_kernel<false, true, true>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((var2_adj_frames_link_kernel<true, true, true>), grid, block, 0, stream, a);
+            return launched("var2_adj_frames_link_keep_stream_1d");
+        }
+        if (a.causal) hipLaunchKernelGGL((var2_adj_frames_link_kernel<false, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_adj_frames_link_kernel<true, false, true>), grid, block, 0, stream, a);
+        return launched("var2_adj_frames_link_stream_1d");
+    }
     if (a.keep) {
         if (a.causal) hipLaunchKernelGGL((var2_adj_frames_link_kernel<false, true>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((var2_adj_frames_link_kernel<true, true>), grid, block, 0, stream, a);
@@ -1436,6 +1630,11 @@ int launch_var2_adj_frames_link(const Var2AdjFramesLinkArgs &a, hipStream_t stre
 
 int launch_var2_frames_coef(const Var2FramesGradArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.n / 4 + kGradLanes - 1) / kGradLanes), (unsigned)a.n_lines), block(kGradLanes);
+    if (a.stream) {
+        if (a.causal) hipLaunchKernelGGL((var2_frames_grad_kernel<true, true, true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((var2_frames_grad_kernel<false, true, true, true>), grid, block, 0, stream, a);
+        return launched("var2_frames_coef_stream_1d");
+    }
     if (a.causal) hipLaunchKernelGGL((var2_frames_grad_kernel<true, true, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((var2_frames_grad_kernel<false, true, true>), grid, block, 0, stream, a);
     return launched("var2_frames_coef_1d");

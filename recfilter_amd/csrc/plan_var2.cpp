@@ -969,11 +969,28 @@ int run_var2_biquad_frames_backward(rf_var2_plan *plan, const void *in, const rf
 //              lam, and var2_frames_coef_1d: section k's sums into its part of the slab -- then var2_carry_1d,
 //              var2_adj_frames_pass2_1d and var2_biquad_frames_grad_1d for section 0, and var2_frames_fold_cascade_1d for all.
 // One section: run_var2_biquad_frames and run_var2_biquad_frames_backward, their launches and bits.
+//   with a state (rf_var2_plan_execute_cascade_frames_stream; `state` with either pointer given): the forward's launches on
+//              their STREAM instances, one section included; the state's checks follow the call's own.
 const char *var2_cascade_frames_name(const rf_var2_plan *plan, int n_sections, bool keep, size_t i) {
     if (n_sections == 1) return plan->frames_names[i].c_str();
     if (i == 0) return "var2_biquad_frames_tails_1d";
     if (i + 1 == (size_t)var2_cascade_frames_launches(n_sections)) return "var2_frames_pass2_1d";
     return i % 2 == 1 ? "var2_carry_1d" : keep ? "var2_frames_link_keep_1d" : "var2_frames_link_1d";
+}
+
+const char *var2_cascade_frames_stream_name(int n_sections, bool keep, size_t i) {
+    if (i == 0) return "var2_biquad_frames_tails_stream_1d";
+    if (i + 1 == (size_t)var2_cascade_frames_stream_launches(n_sections)) return "var2_frames_pass2_stream_1d";
+    return i % 2 == 1 ? "var2_carry_1d" : keep ? "var2_frames_link_keep_stream_1d" : "var2_frames_link_stream_1d";
+}
+
+const char *var2_cascade_frames_stream_backward_name(int n_sections, bool with_frames, size_t i) {
+    static const char *const last[4] = {"var2_carry_1d", "var2_adj_frames_pass2_stream_1d", "var2_biquad_frames_grad_stream_1d", "var2_frames_fold_cascade_1d"};
+    const size_t launches = (size_t)var2_cascade_frames_stream_backward_launches(n_sections, with_frames), tail = with_frames ? 4 : 3;
+    if (i == 0) return "var2_adj_frames_tails_stream_1d";
+    if (i + tail >= launches) return last[i + tail - launches];
+    const size_t at = (i - 1) % (with_frames ? 3 : 2);      // within the launches of one boundary
+    return at == 0 ? "var2_carry_1d" : at == 2 ? "var2_frames_coef_stream_1d" : with_frames ? "var2_adj_frames_link_keep_stream_1d" : "var2_adj_frames_link_stream_1d";
 }
 
 const char *var2_cascade_frames_backward_name(const rf_var2_plan *plan, int n_sections, bool with_frames, size_t i) {
@@ -1013,17 +1030,20 @@ int grow(float **signal, size_t bytes, const char *what) {
 
 int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
                             int64_t frame_stride, void *out, void *const *kept, hipStream_t stream, float *ms_out, const char **names_out,
-                            int capacity, bool timed) {
+                            int capacity, bool timed, const Var2State *state) {
     if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
     if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
     const int K = n_sections;
     const bool keep = kept != nullptr && K >= 2;
-    const size_t launches = (size_t)var2_cascade_frames_launches(K);
+    // a call with a state: the STREAM instances, one section included; both pointers null: the call without one
+    const bool streamed = state && (state->in || state->out);
+    const size_t launches = streamed ? (size_t)var2_cascade_frames_stream_launches(K) : (size_t)var2_cascade_frames_launches(K);
     if (timed) {
-        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_frames_name(plan, K, keep, i); }, ms_out, names_out, capacity);
+        int rc = timed_names(launches, [&](size_t i) { return streamed ? var2_cascade_frames_stream_name(K, keep, i) : var2_cascade_frames_name(plan, K, keep, i); },
+                             ms_out, names_out, capacity);
         if (rc != RF_OK) return rc;
     }
-    if (K == 1) return run_var2_biquad_frames(plan, in, frames, hop, n_frames, frame_stride, out, stream, ms_out);
+    if (K == 1 && !streamed) return run_var2_biquad_frames(plan, in, frames, hop, n_frames, frame_stride, out, stream, ms_out);
     int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
     if (rc != RF_OK) return rc;
     if (!frames) return refuse(RF_ERR_INVALID_ARG, "null frames");
@@ -1045,6 +1065,30 @@ int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_se
     read.front().why = ": a kept signal is stored while neighbouring groups still read in";
     rc = check_written_planes(written, 2, read.data(), (int)read.size(), {"grad_out", nullptr, 0, bytes});      // then the kept signals
     if (rc != RF_OK) return rc;
+    if (streamed) {
+        // the state: K + 1 pairs per line; state_out is written while everything else may still be read
+        const int64_t pairs = 2 * ((int64_t)K + 1);
+        if (state->stride < pairs) return refuse(RF_ERR_INVALID_ARG, "state_stride must be at least 2 (n_sections + 1) = %lld (got %lld)", pairs, state->stride);
+        if (((uintptr_t)state->in & 3u) != 0 || ((uintptr_t)state->out & 3u) != 0) return refuse(RF_ERR_INVALID_ARG, "state: state buffers need 4-byte aligned pointers");
+        const size_t state_bytes = (size_t)((int64_t)(plan->n_lines - 1) * state->stride + pairs) * sizeof(float);
+        if (state->out) {
+            if (state->in && overlap(state->out, state_bytes, state->in, state_bytes)) return refuse(RF_ERR_INVALID_ARG, "state_out overlaps state_in");
+            if (overlap(state->out, state_bytes, in, bytes)) return refuse(RF_ERR_INVALID_ARG, "state_out overlaps in");
+            if (overlap(state->out, state_bytes, out, bytes)) return refuse(RF_ERR_INVALID_ARG, "state_out overlaps out");
+            for (int k = 0; keep && k + 1 < K; k++)
+                if (overlap(state->out, state_bytes, kept[k], bytes)) return refuse(RF_ERR_INVALID_ARG, "state_out overlaps kept plane %lld", k);
+            for (int k = 0; k < K; k++)
+                for (int i = 0; i < 5; i++)
+                    if (overlap(state->out, state_bytes, arrays.planes[(size_t)(5 * k + i)], frame_bytes))
+                        return refuse(RF_ERR_INVALID_ARG, "state_out overlaps frames of section %lld plane %lld", k, i);
+        }
+        if (state->in) {
+            // (out and the kept signals are stored while the first tile's lane may still read state_in)
+            if (overlap(state->in, state_bytes, out, bytes)) return refuse(RF_ERR_INVALID_ARG, "state_in overlaps out");
+            for (int k = 0; keep && k + 1 < K; k++)
+                if (overlap(state->in, state_bytes, kept[k], bytes)) return refuse(RF_ERR_INVALID_ARG, "state_in overlaps kept plane %lld", k);
+        }
+    }
     if (plan->host_only) return refuse_host_only();
     RF_HIP_CHECK(hipSetDevice(plan->device));
     LaunchTimer timer(stream, ms_out, launches);
@@ -1054,6 +1098,12 @@ int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_se
     Var2FramesArgs a = frames_args(plan, frames[0], hop, n_frames, frame_stride, plan->causal, false);
     a.x = (const float *)in;
     a.dst = signals[0];
+    if (streamed) {
+        a.state_in = (const float *)state->in;
+        a.state_out = (float *)state->out;
+        a.state_stride = state->stride;
+        a.pair = 0;
+    }
     rc = launch_var2_frames_tails(a, stream);
     if (rc == RF_OK) rc = timer.mark();
     const Var2Args carry = scan_args(plan, plan->causal, false);
@@ -1083,6 +1133,12 @@ int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_se
         l.inv_hop = a.inv_hop;
         l.stride = a.stride;
         l.frame_stride = frame_stride;
+        if (streamed) {
+            l.state_in = a.state_in;
+            l.state_out = a.state_out;
+            l.state_stride = a.state_stride;
+            l.pair = k;      // section k - 1's
+        }
         if (rc == RF_OK) rc = launch_var2_frames_link(l, stream);
         if (rc == RF_OK) rc = timer.mark();
     }
@@ -1090,6 +1146,12 @@ int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_se
     if (rc == RF_OK) rc = timer.mark();
     Var2FramesArgs last = frames_args(plan, frames[K - 1], hop, n_frames, frame_stride, plan->causal, false);
     last.x = last.dst = (float *)out;
+    if (streamed) {
+        last.state_in = a.state_in;        // (not read: the state has entered.  Given alone it still selects the STREAM instance)
+        last.state_out = a.state_out;
+        last.state_stride = a.state_stride;
+        last.pair = K;
+    }
     if (rc == RF_OK) rc = launch_var2_frames_pass2(last, stream);
     if (rc == RF_OK) rc = timer.mark();
     return rc == RF_OK ? timer.finish() : rc;
@@ -1098,10 +1160,12 @@ int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_se
 int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
                                      int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out, void *grad_in,
                                      const rf_var2_section_grad *frame_grads, hipStream_t stream, float *ms_out, const char **names_out,
-                                     int capacity, bool timed) {
+                                     int capacity, bool timed, const Var2GradState *state) {
     if (!plan) return refuse(RF_ERR_INVALID_ARG, "null argument");
     if (n_sections < 1 || n_sections > RF_VAR2_MAX_SECTIONS) return refuse(RF_ERR_INVALID_ARG, kSectionCount, RF_VAR2_MAX_SECTIONS, n_sections);
     const int K = n_sections;
+    // the backward of a call with a state: the STREAM instances, one section included; every pointer null: the call without one
+    const bool streamed = state && (state->in || state->grad_out || state->grad_in);
     // with frame gradients: every pointer of every section given.  Anything between that and none at all is refused below
     int given = 0;
     bool partial = false;      // a section with one to four of its five
@@ -1112,12 +1176,15 @@ int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const r
         given += own;
     }
     const bool with_frames = given == 5 * K;
-    const size_t launches = (size_t)var2_cascade_frames_backward_launches(K, with_frames);
+    const size_t launches = streamed ? (size_t)var2_cascade_frames_stream_backward_launches(K, with_frames)
+                                     : (size_t)var2_cascade_frames_backward_launches(K, with_frames);
     if (timed) {
-        int rc = timed_names(launches, [&](size_t i) { return var2_cascade_frames_backward_name(plan, K, with_frames, i); }, ms_out, names_out, capacity);
+        int rc = timed_names(launches, [&](size_t i) {
+            return streamed ? var2_cascade_frames_stream_backward_name(K, with_frames, i) : var2_cascade_frames_backward_name(plan, K, with_frames, i);
+        }, ms_out, names_out, capacity);
         if (rc != RF_OK) return rc;
     }
-    if (K == 1)
+    if (K == 1 && !streamed)
         return run_var2_biquad_frames_backward(plan, in, frames, hop, n_frames, frame_stride, out, grad_out, grad_in, frame_grads, stream, ms_out,
                                                false);
     int rc = check_frames_layout(plan->length, hop, n_frames, frame_stride);
@@ -1153,11 +1220,46 @@ int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const r
     read.push_back({"kept", kept, with_frames ? K - 1 : 0, bytes});
     rc = check_written_planes(written.data(), (int)written.size(), read.data(), (int)read.size(), {"grad_out", gout, 1, bytes});
     if (rc != RF_OK) return rc;
+    if (streamed) {
+        // the three state buffers: K + 1 pairs per line; grad_state_in is written while everything else may still be read
+        const int64_t pairs = 2 * ((int64_t)K + 1);
+        if (state->stride < pairs) return refuse(RF_ERR_INVALID_ARG, "state_stride must be at least 2 (n_sections + 1) = %lld (got %lld)", pairs, state->stride);
+        if ((((uintptr_t)state->in | (uintptr_t)state->grad_out | (uintptr_t)state->grad_in) & 3u) != 0)
+            return refuse(RF_ERR_INVALID_ARG, "state: state buffers need 4-byte aligned pointers");
+        const size_t state_bytes = (size_t)((int64_t)(plan->n_lines - 1) * state->stride + pairs) * sizeof(float);
+        if (state->grad_in) {
+            if (state->in && overlap(state->grad_in, state_bytes, state->in, state_bytes)) return refuse(RF_ERR_INVALID_ARG, "grad_state_in overlaps state_in");
+            if (state->grad_out && overlap(state->grad_in, state_bytes, state->grad_out, state_bytes))
+                return refuse(RF_ERR_INVALID_ARG, "grad_state_in overlaps grad_state_out");
+            const void *const signals[4] = {in, out, grad_out, grad_in};
+            static const char *const nouns[4] = {"grad_state_in overlaps in", "grad_state_in overlaps out", "grad_state_in overlaps grad_out", "grad_state_in overlaps grad_in"};
+            for (int i = 0; i < 4; i++)
+                if (signals[i] && overlap(state->grad_in, state_bytes, signals[i], bytes)) return refuse(RF_ERR_INVALID_ARG, nouns[i]);
+            for (int k = 0; kept && with_frames && k + 1 < K; k++)
+                if (overlap(state->grad_in, state_bytes, kept[k], bytes)) return refuse(RF_ERR_INVALID_ARG, "grad_state_in overlaps kept plane %lld", k);
+            for (int k = 0; k < K; k++)
+                for (int i = 0; i < 5; i++) {
+                    if (overlap(state->grad_in, state_bytes, arrays.planes[(size_t)(5 * k + i)], frame_bytes))
+                        return refuse(RF_ERR_INVALID_ARG, "grad_state_in overlaps frames of section %lld plane %lld", k, i);
+                    if (with_frames && overlap(state->grad_in, state_bytes, gradients.planes[(size_t)(5 * k + i)], frame_bytes))
+                        return refuse(RF_ERR_INVALID_ARG, "grad_state_in overlaps gradient of frames of section %lld plane %lld", k, i);
+                }
+        }
+        // (grad_in and the frame gradients are stored while state_in and grad_state_out may still be read)
+        for (const void *read_state : {state->in, (const void *)state->grad_out}) {
+            if (!read_state) continue;
+            if (overlap(read_state, state_bytes, grad_in, bytes)) return refuse(RF_ERR_INVALID_ARG, "grad_in overlaps a state buffer that is read");
+            for (int k = 0; with_frames && k < K; k++)
+                for (int i = 0; i < 5; i++)
+                    if (overlap(read_state, state_bytes, gradients.planes[(size_t)(5 * k + i)], frame_bytes))
+                        return refuse(RF_ERR_INVALID_ARG, "gradient of frames of section %lld plane %lld overlaps a state buffer that is read", k, i);
+        }
+    }
     if (plan->host_only) return refuse_host_only();
     RF_HIP_CHECK(hipSetDevice(plan->device));
     rc = grow(&plan->lam, bytes, "the adjoint state of the cascade's backward");
     if (rc != RF_OK) return rc;
-    if (plan->cascade_spans < 1) {
+    if (K >= 2 && plan->cascade_spans < 1) {
         rc = grow(&plan->cascade, bytes, "the gradient between the sections of the cascade's backward");
         if (rc != RF_OK) return rc;
         plan->cascade_spans = 1;
@@ -1183,10 +1285,23 @@ int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const r
     Var2FramesArgs a = frames_args(plan, frames[K - 1], hop, n_frames, frame_stride, !plan->causal, true);
     a.x = (const float *)grad_out;
     a.dst = plan->lam;
+    if (streamed) {
+        a.stream = 1;
+        a.grad_state_out = (const float *)state->grad_out;
+        a.grad_state_in = (float *)state->grad_in;
+        a.state_stride = state->stride;
+        a.add_pair = K;      // x is grad_out
+        a.last_section = K - 1;
+    }
     rc = launch_var2_frames_tails(a, stream);
     if (rc == RF_OK) rc = timer.mark();
     const Var2Args carry = scan_args(plan, !plan->causal, true);
     Var2FramesGradArgs g{};
+    if (streamed) {
+        g.stream = 1;
+        g.state_in = (const float *)state->in;
+        g.state_stride = state->stride;
+    }
     g.lam = plan->lam;
     g.n = (int32_t)plan->length;
     g.n_lines = plan->n_lines;
@@ -1224,9 +1339,19 @@ int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const r
         l.inv_hop = a.inv_hop;
         l.stride = a.stride;
         l.frame_stride = frame_stride;
+        if (streamed) {
+            l.stream = 1;
+            l.grad_state_out = a.grad_state_out;
+            l.grad_state_in = a.grad_state_in;
+            l.state_stride = a.state_stride;
+            l.pair = k;
+            l.add_pair = k == K - 1 ? K : -1;      // x is grad_out, or holds the addition already
+            l.last_section = K - 1;
+        }
         if (rc == RF_OK) rc = launch_var2_adj_frames_link(l, stream);
         if (rc == RF_OK) rc = timer.mark();
         if (rc == RF_OK && with_frames) {
+            if (streamed) g.pair = k;
             g.x = (const float *)kept[k - 1];
             g.y = k == K - 1 ? (const float *)out : (const float *)kept[k];
             g.slab = plan->frames_slab + k * section_doubles;
@@ -1237,12 +1362,25 @@ int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const r
     if (rc == RF_OK) rc = launch_var2_carry(carry, stream);
     if (rc == RF_OK) rc = timer.mark();
     Var2FramesArgs first = frames_args(plan, frames[0], hop, n_frames, frame_stride, !plan->causal, true);
-    first.x = between;
+    first.x = K == 1 ? (const float *)grad_out : between;
     first.dst = plan->lam;
+    if (streamed) {
+        first.stream = 1;
+        first.grad_state_out = a.grad_state_out;
+        first.grad_state_in = a.grad_state_in;
+        first.state_stride = a.state_stride;
+        first.pair = 0;
+        first.add_pair = K == 1 ? K : -1;
+        first.last_section = K - 1;
+    }
     if (rc == RF_OK) rc = launch_var2_frames_pass2(first, stream);
     if (rc == RF_OK) rc = timer.mark();
+    if (streamed) {
+        g.pair = 0;
+        g.grad_state_out = (const float *)state->grad_out;
+    }
     g.x = (const float *)in;
-    g.y = with_frames ? (const float *)kept[0] : nullptr;
+    g.y = !with_frames ? nullptr : K == 1 ? (const float *)out : (const float *)kept[0];
     g.b0 = (const float *)frames[0].b0;
     g.b1 = (const float *)frames[0].b1;
     g.b2 = (const float *)frames[0].b2;

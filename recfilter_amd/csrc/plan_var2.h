@@ -106,11 +106,31 @@ inline int var2_cascade_frames_backward_launches(int n_sections, bool with_frame
 inline size_t var2_cascade_frames_backward_bytes(const rf_var2_plan *plan, int n_sections, int hop) {
     return plan->span_bytes() * (size_t)(n_sections == 1 ? 1 : 2) + (size_t)n_sections * plan->frames_slab_needed(hop);
 }
+// state (rf_var2_plan_execute_cascade_frames_stream): [line][n_sections + 1][2] f32, `stride` floats from line to line; in null:
+// zeros enter; out null: not wanted; state null or both pointers null: the call without a state, its launches, names and bits
+struct Var2State {
+    const void *in;
+    void *out;
+    int64_t stride;
+};
+const char *var2_cascade_frames_stream_name(int n_sections, bool keep, size_t i);
+inline int var2_cascade_frames_stream_launches(int n_sections) { return 2 * n_sections + 1; }
 int run_var2_cascade_frames(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
                             int64_t frame_stride, void *out, void *const *kept, hipStream_t stream, float *ms_out, const char **names_out,
-                            int capacity, bool timed);
+                            int capacity, bool timed, const Var2State *state = nullptr);
+// state (rf_var2_plan_backward_cascade_frames_stream): the state that entered the forward (read for the frame gradients alone),
+// the gradient of the state that left it (null: zeros) and the gradient of the state that entered (null: not wanted), all laid
+// out like the state; state null or every pointer null: the call without a state
+struct Var2GradState {
+    const void *in;
+    const void *grad_out;
+    void *grad_in;
+    int64_t stride;
+};
+const char *var2_cascade_frames_stream_backward_name(int n_sections, bool with_frames, size_t i);
+inline int var2_cascade_frames_stream_backward_launches(int n_sections, bool with_frames) { return with_frames ? 3 * n_sections + 2 : 2 * n_sections + 2; }
 int run_var2_cascade_frames_backward(rf_var2_plan *plan, const void *in, const rf_var2_section *frames, int n_sections, int hop, int n_frames,
                                      int64_t frame_stride, const void *const *kept, const void *out, const void *grad_out, void *grad_in,
                                      const rf_var2_section_grad *frame_grads, hipStream_t stream, float *ms_out, const char **names_out,
-                                     int capacity, bool timed);
+                                     int capacity, bool timed, const Var2GradState *state = nullptr);
 }  // namespace rf

@@ -595,6 +595,138 @@ class Var2Plan(_PlanHandle):
         and the K - 1 kept signals are saved; where only x does, the plain forward runs and the frames alone are saved."""
         return _cascade_frames_function().apply(self, int(hop), x, *(t for s in sections for t in s))
 
+    # -- the cascade on frames with a state that enters and leaves the call --------------------------
+    #     state: (K + 1, 2) (lines == 1) or (lines, K + 1, 2): pair 0 the input's history, pair k + 1 section k's result's, each
+    #     (one place before the line, two places before it) in the direction of the recurrence
+    def cascade_frames_stream_num_kernels(self, sections: int) -> int:
+        """2 K + 1 launches, K = 1 included"""
+        return int(capi.lib().rf_var2_plan_cascade_frames_stream_num_kernels(self._h, int(sections)))
+
+    def cascade_frames_stream_state_bytes(self, sections: int, state_stride: int = None) -> int:
+        """the bytes of one state buffer, 4 ((lines - 1) state_stride + 2 (K + 1)); state_stride defaults to 2 (K + 1); 0 for a
+        refused K or stride"""
+        stride = 2 * (int(sections) + 1) if state_stride is None else int(state_stride)
+        return int(capi.lib().rf_var2_plan_cascade_frames_stream_state_bytes(self._h, int(sections), stride))
+
+    def _state_pointer(self, t, K: int, what: str, stride=None):
+        """(the address of a state tensor after its checks, the distance between lines).  The state buffers of one call share one
+        distance: `stride` is what the buffers before this one fixed (None: none was given yet), a tensor with another raises,
+        and a null one (None) passes it on -- so the calls chain this function over their buffers and the rule holds whichever
+        of them are given."""
+        import torch
+        pairs = 2 * (K + 1)
+        if t is None:
+            return ctypes.c_void_p(), stride
+        shapes = [(self.lines, K + 1, 2)] + ([(K + 1, 2)] if self.lines == 1 else [])
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{what}: shape {tuple(t.shape)}, {K} sections on this plan take {' or '.join(str(s) for s in shapes)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: float32 states only, got {t.dtype}")
+        own = int(t.stride(0)) if t.dim() == 3 and self.lines > 1 else pairs
+        if not t.is_cuda or t.stride(-1) != 1 or t.stride(-2) != 2 or (stride is not None and own != stride):
+            raise ValueError(f"{what}: a device tensor with dense (K + 1, 2) blocks, state and state_out the same distance apart")
+        return ctypes.c_void_p(t.data_ptr()), own
+
+    @staticmethod
+    def _dense_state_stride(stride, K: int) -> int:
+        """the distance the library is handed: what the buffers fixed, or dense where none was given"""
+        return 2 * (K + 1) if stride is None else stride
+
+    def _cascade_frames_stream_arguments(self, x, sections, hop, state, out, keep, kept, state_out, stream):
+        K = len(sections)
+        if self._host_only:
+            (px, po, psi, pso), array, pk, _, count, stride = self._host_sections_frames(K, hop, 4)
+            null = ctypes.c_void_p()
+            return (px, array, K, int(hop), count, stride, po, pk if keep else None, psi if state is not None else null,
+                    pso if state_out is not False else null, 2 * (K + 1), None, None, None, null)
+        import torch
+        *p, out, kept, s = self._cascade_frames_arguments(x, sections, hop, out, keep, kept, stream)
+        psi, stride = self._state_pointer(state, K, "state")
+        if state_out is None:
+            shape = (K + 1, 2) if x.dim() == 1 else (self.lines, K + 1, 2)
+            state_out = (torch.empty_strided(tuple(state.shape), state.stride(), dtype=torch.float32, device=x.device) if state is not None
+                         else torch.empty(shape, dtype=torch.float32, device=x.device))
+        elif state_out is False:
+            state_out = None
+        pso, stride = self._state_pointer(state_out, K, "state_out", stride)
+        return (*p, psi, pso, self._dense_state_stride(stride, K), out, kept, state_out, s)
+
+    def execute_cascade_frames_stream(self, x, sections: Sequence, hop: int, state=None, out=None, keep: bool = False, kept=None,
+                                      state_out=None, stream=None):
+        """rf_var2_plan_execute_cascade_frames_stream: execute_cascade_frames on one chunk of a longer signal.  `state` enters (None:
+        silence) and the state that leaves is returned: (out, state_out), or (out, kept, state_out) where keeping.  `sections`
+        holds the CHUNK's frames -- for a chunk that starts at sample s of the whole signal, a multiple of hop, the slice
+        [..., s // hop : s // hop + frames_count(length, hop)] of the whole signal's.  An anticausal plan takes its chunks last to
+        first.  state_out: a tensor to be written (apart from `state`), None allocates it, False: not wanted (None is returned;
+        with state=None too the call is execute_cascade_frames itself).  The plan keeps no state."""
+        *p, out, kept, state_out, s = self._cascade_frames_stream_arguments(x, sections, hop, state, out, keep or kept is not None, kept, state_out, stream)
+        capi.check(capi.lib().rf_var2_plan_execute_cascade_frames_stream(self._h, *p, s))
+        return (out, kept, state_out) if keep or kept is not None else (out, state_out)
+
+    def execute_cascade_frames_stream_timed(self, x, sections: Sequence, hop: int, state=None, out=None, keep: bool = False, kept=None,
+                                            state_out=None, stream=None):
+        """rf_var2_plan_execute_cascade_frames_stream_timed: execute_cascade_frames_stream's results and [(kernel name, ms), ...]
+        behind them; synchronises the stream."""
+        *p, out, kept, state_out, s = self._cascade_frames_stream_arguments(x, sections, hop, state, out, keep or kept is not None, kept, state_out, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_execute_cascade_frames_stream_timed(self._h, *p, s, *report)      # noqa: E731
+        streamed = state is not None or state_out is not None
+        times = _timed(call, self.cascade_frames_stream_num_kernels(len(sections)) if streamed else self.cascade_frames_num_kernels(len(sections)))
+        return (out, kept, state_out, times) if keep or kept is not None else (out, state_out, times)
+
+    def backward_cascade_frames_stream_num_kernels(self, sections: int, with_frames: bool = False) -> int:
+        """2 K + 2 launches without frame gradients, 3 K + 2 with them, K = 1 included"""
+        return int(capi.lib().rf_var2_plan_backward_cascade_frames_stream_num_kernels(self._h, int(sections), int(bool(with_frames))))
+
+    def _backward_cascade_frames_stream_arguments(self, x, sections, hop, kept, out, grad_out, grad_in, grads, state, grad_state_out, grad_state_in, stream):
+        K = len(sections)
+        *p, grad_in, grads, s = self._backward_cascade_frames_arguments(x, sections, hop, kept, out, grad_out, grad_in, grads, stream)
+        if self._host_only:
+            psi, pgo, pgi = self._placeholders(7 + 11 * K)[-3:]
+            null = ctypes.c_void_p()
+            return (*p, psi if state is not None else null, pgo if grad_state_out is not None else null, pgi if grad_state_in is not False else null,
+                    2 * (K + 1), None, grads, None, null)
+        import torch
+        psi, stride = self._state_pointer(state, K, "state")
+        pgo, stride = self._state_pointer(grad_state_out, K, "grad_state_out", stride)
+        like = state if state is not None else grad_state_out      # what a grad_state_in allocated here is laid out like
+        if grad_state_in is None:
+            shape = (K + 1, 2) if grad_out.dim() == 1 else (self.lines, K + 1, 2)
+            grad_state_in = (torch.empty_strided(tuple(like.shape), like.stride(), dtype=torch.float32, device=grad_out.device) if like is not None
+                             else torch.empty(shape, dtype=torch.float32, device=grad_out.device))
+        elif grad_state_in is False:
+            grad_state_in = None
+        pgi, stride = self._state_pointer(grad_state_in, K, "grad_state_in", stride)
+        return (*p, psi, pgo, pgi, self._dense_state_stride(stride, K), grad_in, grads, grad_state_in, s)
+
+    def backward_cascade_frames_stream(self, x, sections: Sequence, hop: int, kept, out, grad_out, grad_in=None, grads=None, state=None,
+                                       grad_state_out=None, grad_state_in=None, stream=None):
+        """rf_var2_plan_backward_cascade_frames_stream, the adjoint of execute_cascade_frames_stream on what it kept: backward_cascade_frames'
+        arguments, then `state` (what entered the forward; read for the frame gradients alone), grad_state_out (the gradient of the
+        state that left; None: zeros) and grad_state_in (a tensor to be WRITTEN, None allocates it, False: not wanted).  Returns
+        (grad_in, grads, grad_state_in)."""
+        *p, grad_in, grads, grad_state_in, s = self._backward_cascade_frames_stream_arguments(x, sections, hop, kept, out, grad_out, grad_in, grads, state,
+                                                                                              grad_state_out, grad_state_in, stream)
+        capi.check(capi.lib().rf_var2_plan_backward_cascade_frames_stream(self._h, *p, s))
+        return grad_in, grads, grad_state_in
+
+    def backward_cascade_frames_stream_timed(self, x, sections: Sequence, hop: int, kept, out, grad_out, grad_in=None, grads=None, state=None,
+                                             grad_state_out=None, grad_state_in=None, stream=None):
+        """rf_var2_plan_backward_cascade_frames_stream_timed: (grad_in, grads, grad_state_in, [(kernel name, ms), ...]); synchronises the stream."""
+        streamed = state is not None or grad_state_out is not None or grad_state_in is not False
+        *p, grad_in, grads, grad_state_in, s = self._backward_cascade_frames_stream_arguments(x, sections, hop, kept, out, grad_out, grad_in, grads, state,
+                                                                                              grad_state_out, grad_state_in, stream)
+        call = lambda *report: capi.lib().rf_var2_plan_backward_cascade_frames_stream_timed(self._h, *p, s, *report)      # noqa: E731
+        count = (self.backward_cascade_frames_stream_num_kernels if streamed else self.backward_cascade_frames_num_kernels)(len(sections), grads is not None)
+        return grad_in, grads, grad_state_in, _timed(call, count)
+
+    def apply_cascade_frames_stream(self, x, sections: Sequence, hop: int, state=None):
+        """execute_cascade_frames_stream as a differentiable torch operation: (out, state), the values bit for bit that call's.
+        Differentiable in x, in all 5 K frame tensors and in `state`, and a gradient may flow into the returned state (the next
+        chunk's): backward is backward_cascade_frames_stream.  Where a frame tensor requires a gradient the forward keeps, and x,
+        the frames, the state, the result and the K - 1 kept signals are saved; otherwise the frames alone."""
+        return _cascade_frames_stream_function().apply(self, int(hop), x, state, *(t for s in sections for t in s))
+
+
 
 _var2_function = None
 _var2_biquad_function = None
@@ -684,6 +816,59 @@ def _cascade_function():
 
 _var2_biquad_frames_function = None
 _var2_cascade_frames_function = None
+_var2_cascade_frames_stream_function = None
+
+
+def _cascade_frames_stream_function():
+    """the torch.autograd.Function behind Var2Plan.apply_cascade_frames_stream: (plan, hop, x, state or None, then the 5 K frame
+    tensors) -> (out, the state that leaves)"""
+    global _var2_cascade_frames_stream_function
+    if _var2_cascade_frames_stream_function is not None:
+        return _var2_cascade_frames_stream_function
+    import torch
+
+    class Var2CascadeFramesStreamFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, hop, x, state, *frames):
+            ctx.plan, ctx.hop, ctx.has_state = plan, hop, state is not None
+            sections = [frames[i:i + 5] for i in range(0, len(frames), 5)]
+            ctx.with_frames = any(ctx.needs_input_grad[4:])
+            with torch.cuda.device(x.device):
+                if ctx.with_frames:
+                    out, kept, leaving = plan.execute_cascade_frames_stream(x, sections, hop, state, keep=True)
+                    ctx.save_for_backward(x, *frames, out, *kept, *([state] if state is not None else []))
+                else:      # the backward reads nothing of the forward
+                    out, leaving = plan.execute_cascade_frames_stream(x, sections, hop, state)
+                    ctx.save_for_backward(*frames)
+            ctx.shape, ctx.state_shape = tuple(out.shape), tuple(leaving.shape)
+            return out, leaving
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad_out, grad_leaving):
+            plan = ctx.plan
+            need_x, need_state, *need = ctx.needs_input_grad[2:]
+            count = len(need)
+            if ctx.with_frames:
+                x, *rest = ctx.saved_tensors
+                state = rest.pop() if ctx.has_state else None
+                frames, out, kept = rest[:count], rest[count], rest[count + 1:]
+            else:
+                x, frames, out, kept, state = None, ctx.saved_tensors, None, None, None
+            sections = [frames[i:i + 5] for i in range(0, count, 5)]
+            device = (grad_out if grad_out is not None else grad_leaving).device
+            g = _plan_layout(plan, grad_out) if grad_out is not None else torch.zeros(ctx.shape, dtype=torch.float32, device=device)
+            if grad_leaving is not None:
+                grad_leaving = grad_leaving.to(torch.float32).contiguous()
+            grads = [tuple(torch.empty_like(t) for t in s) for s in sections] if ctx.with_frames else None
+            with torch.cuda.device(device):
+                gin, grads, gstate = plan.backward_cascade_frames_stream(x, sections, ctx.hop, kept, out, g, None, grads, state, grad_leaving,
+                                                                         None if need_state else False)
+            given = [t for s in grads for t in s] if grads is not None else [None] * count
+            return (None, None, gin if need_x else None, gstate if need_state else None) + tuple(t if wanted else None for t, wanted in zip(given, need))
+
+    _var2_cascade_frames_stream_function = Var2CascadeFramesStreamFunction
+    return _var2_cascade_frames_stream_function
 
 
 def _cascade_frames_function():
@@ -1032,3 +1217,91 @@ def biquad_cascade_frames(x, sections: Sequence, hop: int, causal: bool = True):
         x = torch.nn.functional.pad(x, (0, pad))
     out = plan.apply_cascade_frames(_plan_layout(plan, x), [tuple(t.to(torch.float32).contiguous() for t in s) for s in sections], hop)
     return out[..., :n] if pad else out
+
+
+def biquad_cascade_frames_stream(x, sections: Sequence, hop: int, state=None, causal: bool = True):
+    """biquad_cascade_frames on one chunk of a longer signal: (y, state).  `state` is what the call on the chunk before returned
+    (None: silence), (K + 1, 2) for x of shape (N,) or (L, K + 1, 2) for (L, N): pair 0 the two last samples of the input so far,
+    pair k + 1 those of section k's result, the nearest first.  N must be a multiple of 4 -- padding would corrupt the state that
+    leaves -- so a ragged length raises ValueError.  `sections` holds the chunk's frames, F = frames_count(N, hop) per tensor: for
+    a chunk that starts at sample s of the whole signal, s a multiple of hop, the slice [..., s // hop : s // hop + F] of the
+    whole signal's frames.  causal=False: the chunks are fed last to first and the state is (x[n], x[n+1]), ...  Chunks chained
+    this way give what one biquad_cascade_frames call on the whole signal gives, to rounding.  Differentiable in x, in all 5 K
+    frame tensors and in `state`, and a gradient flows into the returned state: a loss on a chain of chunks reaches every chunk
+    (detach the state for truncated back-propagation through time).  It shares biquad_scan's plan cache."""
+    import torch
+    sections = [tuple(s) for s in sections]
+    K = len(sections)
+    if not 1 <= K <= capi.RF_VAR2_MAX_SECTIONS or any(len(s) != 5 for s in sections):
+        raise ValueError(f"sections: 1..{capi.RF_VAR2_MAX_SECTIONS} tuples (b0, b1, b2, a1, a2) of frame tensors")
+    n = int(x.shape[-1])
+    if n < 4 or n % 4 != 0:
+        raise ValueError(f"a chunk's length must be a positive multiple of 4 (padding would corrupt the state that leaves), got {n}")
+    count = frames_count(n, hop)
+    shape = tuple(x.shape[:-1]) + (count,)
+    if x.dim() not in (1, 2) or any(tuple(t.shape) != shape for s in sections for t in s):
+        raise ValueError(f"x is (N,) or (L, N) and every frame tensor {shape} at hop {hop}, got {tuple(x.shape)} and "
+                         f"{sorted({tuple(t.shape) for s in sections for t in s})}")
+    lines = 1 if x.dim() == 1 else int(x.shape[0])
+    if state is not None and tuple(state.shape) != tuple(x.shape[:-1]) + (K + 1, 2):
+        raise ValueError(f"state: shape {tuple(state.shape)}, x of shape {tuple(x.shape)} and {K} sections take {tuple(x.shape[:-1]) + (K + 1, 2)}")
+    device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (n, lines, bool(causal), device)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = Var2Plan(n, lines=lines, causal=causal, device=device)
+    if state is not None:
+        state = state.to(torch.float32).contiguous()
+    out, state = plan.apply_cascade_frames_stream(_plan_layout(plan, x), [tuple(t.to(torch.float32).contiguous() for t in s) for s in sections], hop, state)
+    return out, state.reshape(tuple(x.shape[:-1]) + (K + 1, 2))
+
+
+class BiquadCascadeStream:
+    """A cascade of K sections on control-rate frames that remembers where it stopped: push(x, sections) filters the next chunk
+    and returns its result; chunks pushed one after the other give what biquad_cascade_frames gives on their concatenation, to
+    rounding.  x is (N,) (lines == 1) or (lines, N), N a multiple of 4; `sections` the chunk's frames as
+    biquad_cascade_frames_stream takes them; causal=False: push the chunks last to first.  The state is detached and lives in two
+    buffers that swap roles: one enters a call while the other receives what leaves it.  reset() returns to silence; between two
+    resets every chunk has one device and one layout ((N,) or (lines, N)): anything else raises."""
+
+    def __init__(self, K: int, hop: int, lines: int = 1, causal: bool = True):
+        if not 1 <= int(K) <= capi.RF_VAR2_MAX_SECTIONS:
+            raise ValueError(f"K: 1..{capi.RF_VAR2_MAX_SECTIONS} sections")
+        frames_count(4, hop)      # (refuses the hop)
+        self.K, self.hop, self.lines, self.causal = int(K), int(hop), int(lines), bool(causal)
+        self._buffers = None
+        self._entering = None      # the index of the buffer that enters the next push; None: silence
+
+    def reset(self) -> None:
+        self._entering = None
+
+    @property
+    def state(self):
+        """the state that enters the next push (a view of the stream's buffer; None: silence)"""
+        return None if self._entering is None else self._buffers[self._entering]
+
+    def push(self, x, sections: Sequence):
+        import torch
+        if x.dim() not in (1, 2) or (x.dim() == 1 and self.lines != 1) or (x.dim() == 2 and int(x.shape[0]) != self.lines) or len(sections) != self.K:
+            raise ValueError(f"x: ({self.lines}, N) and {self.K} sections, got {tuple(x.shape)} and {len(sections)}")
+        shape = (self.K + 1, 2) if x.dim() == 1 else (self.lines, self.K + 1, 2)
+        if self._entering is not None and (self._buffers[0].device != x.device or tuple(self._buffers[0].shape) != shape):
+            # a stream that went on from silence here would be wrong without a word
+            raise ValueError(f"x: the stream holds a state of shape {tuple(self._buffers[0].shape)} on {self._buffers[0].device}, got x of shape "
+                             f"{tuple(x.shape)} on {x.device}; reset() first")
+        if self._buffers is None or self._buffers[0].device != x.device or tuple(self._buffers[0].shape) != shape:
+            self._buffers = [torch.empty(shape, dtype=torch.float32, device=x.device) for _ in range(2)]
+        n = int(x.shape[-1])
+        if n < 4 or n % 4 != 0:
+            raise ValueError(f"a chunk's length must be a positive multiple of 4, got {n}")
+        device = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        key = (n, self.lines, self.causal, device)
+        plan = _plans.get(key)
+        if plan is None:
+            plan = _plans[key] = Var2Plan(n, lines=self.lines, causal=self.causal, device=device)
+        leaving = 0 if self._entering is None else 1 - self._entering
+        with torch.no_grad(), torch.cuda.device(x.device):
+            frames = [tuple(t.detach().to(torch.float32).contiguous() for t in s) for s in sections]
+            out, _ = plan.execute_cascade_frames_stream(_plan_layout(plan, x.detach()), frames, self.hop, self.state, state_out=self._buffers[leaving])
+        self._entering = leaving
+        return out
